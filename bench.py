@@ -33,6 +33,11 @@ DEFAULT_READS = 65536
 PEAK_HBM_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md); ~6.3 TB/s is what a copy reaches
 METRIC = "MB/s encode+decode, int16 signal, 1/2/4/8 MI355X vs CPU; ratio preserved"
 SVB_BYTES_PER_SAMPLE = 1.261  # svb stream bytes per int16 sample of this workload
+# --dump-outputs: what the last timed step returned, as .npy files, so that two builds can be compared output for output
+DUMP_BYTES = 64 << 20   # all files together
+DUMP_BUFFERS = 32       # buffers whose compressed bytes and decoded values are written: a seeded sample of the step's
+DUMP_SEED = 5
+DUMP_RESIDENT = 8       # resident batches of a dumping run of the reads workload ("as many as fit" would tie its inputs to free HBM)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -430,6 +435,42 @@ def max_compressed_sizes(sizes, level):
     return svb + 4
 
 
+def dump_outputs(path, first, n, comp, coff, csize, cap, out, off, size, res, kind):
+    """--dump-outputs: write under `path` what the last timed step returned to its caller, buffers [first, first + n) of the
+    generator in the batch's layout (`comp` / `out` arenas at `coff` / `off`; `kind` "i16" or "u32" values):
+      compressed_sizes.npy  every buffer's compressed size (the compress call's result), float64
+      decode_results.npy    every buffer's decode result (bytes decoded, or a VBZ error code read as int32), float64
+      sampled_buffers.npy   a seeded sample of at most DUMP_BUFFERS of the buffers: rows of (the generator's index of the buffer,
+                            its position in the step, i.e. its row of the two files above), float64
+      compressed_bytes.npy  those buffers' compressed bytes, concatenated, float32
+      decoded_values.npy    those buffers' decoded values, concatenated: float32 (int16) or float64 (uint32)
+    At most DUMP_BYTES in all: a sampled buffer larger than its share contributes its leading bytes / values."""
+    import numpy as np
+    import torch
+
+    vtype, ftype = ("<i2", np.float32) if kind == "i16" else ("<u4", np.float64)
+    elem, fsize = np.dtype(vtype).itemsize, np.dtype(ftype).itemsize
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_BUFFERS), replace=False))
+    share = (DUMP_BYTES - 4096 - 16 * n - 16 * len(pick)) // (2 * len(pick))   # (4 KB: the five .npy headers)
+    if share < 4 * elem:
+        raise SystemExit("bench.py --dump-outputs: %d buffers per step leave no room for their bytes in %d MB" % (n, DUMP_BYTES >> 20))
+    idx = torch.as_tensor(pick, device=coff.device)
+    co, cs, ca = coff[idx].tolist(), csize[idx].tolist(), cap[idx].tolist()
+    vo, vs = off[idx].tolist(), size[idx].tolist()
+    cbytes = [comp[o : o + min(max(c, 0), k, share // 4)] for o, c, k in zip(co, cs, ca)]
+    vbytes = [out[o : o + min(s, share // fsize * elem) // elem * elem] for o, s in zip(vo, vs)]
+    arrays = {
+        "compressed_sizes": csize[:n].cpu().numpy().astype(np.float64),
+        "decode_results": res[:n].cpu().numpy().astype(np.float64),
+        "sampled_buffers": np.stack([first + pick, pick], 1).astype(np.float64),
+        "compressed_bytes": torch.cat(cbytes).cpu().numpy().astype(np.float32),
+        "decoded_values": torch.cat(vbytes).cpu().numpy().view(vtype).astype(ftype),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------------------------------------------------
@@ -541,11 +582,18 @@ def run_rank(args):
     free = torch.cuda.mem_get_info(dev)[0]
     per_read = 200e3
     fixed = lambda k: k * per_read * (2.14 + 1.0 + 2.125 * 1.125) + 20e9  # noqa: E731
-    if n == DEFAULT_READS:  # the default needs ~85 GB for one batch: step down on a GPU that does not have it free
-        while n > 8192 and free < fixed(n) + n * per_read:
-            n //= 2
-    R = args.resident or max(1, min(args.steps, 16, int((free - fixed(n)) // (n * per_read * 1.02))))
     fixed_job = args.workload == "config5"
+    if args.dump_outputs:
+        # the inputs of a dumping run follow from its arguments alone: --reads as given and a fixed number of resident batches
+        R = args.resident or min(args.steps, DUMP_RESIDENT)
+        if not fixed_job and free < fixed(n) + R * n * per_read * 1.02:
+            raise SystemExit("bench.py --dump-outputs: %d batches of %d reads do not fit %.0f GB of free HBM; lower --reads or --resident"
+                             % (R, n, free / 1e9))
+    else:
+        if n == DEFAULT_READS:  # the default needs ~85 GB for one batch: step down on a GPU that does not have it free
+            while n > 8192 and free < fixed(n) + n * per_read:
+                n //= 2
+        R = args.resident or max(1, min(args.steps, 16, int((free - fixed(n)) // (n * per_read * 1.02))))
 
     # ---- the work queue: rank 0 owns the read table (lengths of world x R x n reads), every rank takes the contiguous,
     # sample-balanced range the partition gives it and cuts it into R batches (weak scaling: per-GPU work is fixed).
@@ -651,6 +699,10 @@ def run_rank(args):
         enc_ms += prev.elapsed_time(evm[i])
         dec_ms += evm[i].elapsed_time(eve[i])
         prev = eve[i]
+
+    if rank == 0 and args.dump_outputs:   # (before the legs below reuse the arenas)
+        B = batches[(args.steps - 1) % R]
+        dump_outputs(args.dump_outputs, B["first"], B["n"], comp, B["coff"], B["csize"], B["cap"], back, B["off"], B["size"], res, "i16")
 
     if rank == 0:
         # ---- stage level: svb only (zstd level 0), same batch, a few steps
@@ -819,12 +871,13 @@ def run_rank(args):
 
 
 def run_large(args, codec, dev, rank, world, coll_dev, barrier, coll):
-    out = measure_large(args.workload, args.buffers, args.steps, args.warmup, codec, dev, rank, world, coll_dev, barrier, coll, cpu=not args.no_cpu)
+    out = measure_large(args.workload, args.buffers, args.steps, args.warmup, codec, dev, rank, world, coll_dev, barrier, coll, cpu=not args.no_cpu,
+                        dump=args.dump_outputs)
     if out is not None:
         print(json.dumps(out), flush=True)
 
 
-def measure_large(workload, buffers, steps, warmup, codec, dev, rank, world, coll_dev, barrier, coll, cpu=True, cpu_seconds=6.0):
+def measure_large(workload, buffers, steps, warmup, codec, dev, rank, world, coll_dev, barrier, coll, cpu=True, cpu_seconds=6.0, dump=""):
     """BASELINE.json configs[3] (`--workload config4`: uint32, no zig-zag, level 3, 10 M-element buffers) and configs[0]
     (`--workload config1`: one 400 k-sample int16 read): batches of few, large buffers, which the library spreads over many
     workgroups (segmented svb kernels, one wavefront per span of the entropy stage)."""
@@ -905,6 +958,8 @@ def measure_large(workload, buffers, steps, warmup, codec, dev, rank, world, col
         prev = eve[i]
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, first, nbuf, comp, coffd, csize, cap32, back, offd, size32, res, kind)
     per_launch = {k: v[1] / max(v[0], 1) for k, v in prof.items()}
     # per direction: elem + c bytes per value ("for uint32 config: 4 + c4 per element per direction")
     c = elem / ratio
@@ -998,7 +1053,13 @@ def main():
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-resident (PCIe-inclusive) leg")
     ap.add_argument("--no-stages", action="store_true", help="skip the svb-only stage line")
     ap.add_argument("--no-configs", action="store_true", help="skip the short configs[0] / configs[3] runs of the default line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one returned to DIR as .npy files (rank 0's; float32 / float64, at most 64 MB: "
+                         "a seeded sample of the buffers).  The reads workload then keeps --resident or min(--steps, %d) batches resident "
+                         "and --reads as given, so that runs with the same arguments code the same inputs" % DUMP_RESIDENT)
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the codec: not with --dry-run")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if not args.dry_run:
             # the parent must not touch the HIP runtime (its children would be forks of an initialised process): the GPUs are

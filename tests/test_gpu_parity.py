@@ -1567,6 +1567,51 @@ def test_bench_line_contract():
     assert d["config"]["distinct_reads"] >= 512
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs DIR writes what the last timed step returned as float .npy files of at most 64 MB, the same files
+    from run to run; the sampled reads' decoded values are the generator's samples, and their compressed bytes are frames the
+    reference path decodes to them."""
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        out = str(tmp_path / ("run%d" % k))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reads", "512", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-pcie",
+                            "--no-stages", "--no-configs", "--dump-outputs", out], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        names = sorted(os.listdir(out))
+        assert names == ["compressed_bytes.npy", "compressed_sizes.npy", "decode_results.npy", "decoded_values.npy", "sampled_buffers.npy"]
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in names) <= 64 << 20
+        runs.append({f[:-4]: np.load(os.path.join(out, f)) for f in names})
+    a, b = runs
+    for name, v in a.items():
+        assert v.dtype in (np.float32, np.float64), name
+        assert np.array_equal(v, b[name]), name
+    sample = a["sampled_buffers"].astype(np.int64)
+    assert sample.shape == (32, 2) and len(a["compressed_sizes"]) == len(a["decode_results"]) >= 32
+    first = int(sample[0, 0] - sample[0, 1])   # the step's reads are consecutive reads of the generator
+    assert (sample[:, 0] - sample[:, 1] == first).all()
+    for row, size in enumerate(a["decode_results"].astype(np.int64)):
+        assert size == 2 * O.synth_read_length(5, first + row), row
+    oo = O.options(True, 2, 1, 1)
+    cpos = vpos = 0
+    for i, row in sample.tolist():
+        want = O.synth_signal(5, i, O.synth_read_length(5, i))
+        assert np.array_equal(a["decoded_values"][vpos : vpos + want.size], want.astype(np.float32)), i
+        vpos += want.size
+        c = int(a["compressed_sizes"][row])
+        frame = a["compressed_bytes"][cpos : cpos + c].astype(np.uint8)
+        cpos += c
+        back = O.decompress(frame, want.nbytes, oo)
+        assert not isinstance(back, int) and back.tobytes() == want.tobytes(), i
+    assert vpos == a["decoded_values"].size and cpos == a["compressed_bytes"].size
+
+
 def test_many_tiny_reads_in_one_batch():
     """150 000 reads of 0 ... 300 samples in ONE call (more workgroups than a 16-bit grid index holds, 147 workgroups of the
     slot plan): every read round-trips on the device, a sample of 600 of them is byte-checked against the oracle in both
