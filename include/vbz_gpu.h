@@ -109,6 +109,21 @@ VBZ_EXPORT void vbz_gpu_set_trailers(vbz_gpu_ctx* ctx, int enable);
  * with one 100 k-sample read: ~0.4 ms instead of ~0.14).  Decoding is unaffected.  The single-buffer API of vbz.h, the HDF5 plugin and
  * the re-packer follow the environment variable VBZ_HIP_CANONICAL (0 / 1, default 0). */
 VBZ_EXPORT void vbz_gpu_set_canonical(vbz_gpu_ctx* ctx, int enable);
+/* Content checksums (RFC 8878 3.1.1).  Decoding: a frame whose header carries Content_Checksum_flag is held to the low 32 bits of
+ * XXH64 (seed 0) of its content -- the svb stream, or the raw bytes at integer_size 0 -- stored behind its last block; a mismatch is
+ * VBZ_ZSTD_ERROR for that read, the verdict libzstd (checksum_wrong), hence the reference's vbz_decompress, gives.  Always on: one short
+ * launch per decode that reads one byte of each frame without the flag.
+ * Encoding: enable = 1 writes every zstd frame with the flag and the checksum (between the last block and the skippable trailers; a frame
+ * whose trailers would then not fit vbz_max_compressed_size loses the trailers, which are hints only).  Every decoder of zstd frames checks
+ * it: damaged data is an error at read time instead of a silent change.  The frames are otherwise the same bytes; enable = 0 (the default)
+ * writes exactly what this library wrote before.  Level 0 writes no zstd frame: the knob does nothing there.  Cost: every read's svb
+ * stream is hashed once more (in front of the entropy stage) and its trailers moved (behind it).  Measured on one MI355X, 65 536 reads of
+ * ~100 k int16 samples: 1.70 ms per encode call, 1.64 ms per decode call of checksummed frames (the hash runs at ~5 TB/s over the svb
+ * streams); bench.py 587 -> 508 GB/s.  ONE large read is hashed by one quad of lanes, bound by the latency of its serial chain
+ * (57 cycles a round of 32 bytes: ~1.35 GB/s at best) and partly by load latency: ~1 GB/s measured, a 40 MB buffer ~41 ms, so a
+ * 10 M-element uint32 buffer costs ~16 ms per direction instead of ~0.2 ms (profiles/HISTORY.md).  The single-buffer API of
+ * vbz.h, the HDF5 plugin and the re-packer follow the environment variable VBZ_HIP_CHECKSUM (0 / 1, default 0). */
+VBZ_EXPORT void vbz_gpu_set_checksum(vbz_gpu_ctx* ctx, int enable);
 /* wait for everything queued on the context's stream; returns 0 or a negative HIP error */
 VBZ_EXPORT int vbz_gpu_synchronize(vbz_gpu_ctx* ctx);
 
@@ -131,8 +146,14 @@ VBZ_EXPORT int vbz_gpu_svb_decompress_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batc
                                             int zigzag, int version);
 /* key_bytes (device, nullable): length of the control-byte section of each svb stream, which the
  * encoder codes with its own Huffman table; NULL codes the whole stream as one region. */
+/* With vbz_gpu_set_checksum on, a read whose frame and checksum do not fit dst_cap[i] gets VBZ_DESTINATION_SIZE_ERROR (a slot of
+ * ZSTD_COMPRESSBOUND(src_size[i]) + 4 bytes always fits). */
 VBZ_EXPORT int vbz_gpu_zstd_compress_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const uint32_t* key_bytes);
 VBZ_EXPORT int vbz_gpu_zstd_decompress_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch);
+/* XXH64 (seed 0) of every read's src bytes into out[i] (device, n_reads x u64); dst fields unused.  One quad of lanes per read, one
+ * accumulator each (the four are independent, the rounds within one a serial chain): many reads at memory speed (65 536 reads of
+ * ~100 KB: 1.3 ms, ~5 TB/s), one read near the speed of its chain (one 40 MB buffer: ~41 ms, ~1 GB/s). */
+VBZ_EXPORT int vbz_gpu_xxh64_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, uint64_t* out);
 
 /* Synthetic workload of SURVEY.md section 8(d), generated on the device (no host data needed).
  *   lengths:  out_len[i] = samples of read first_read+i (90 000 + mix(..) % 20 001), i < n_reads

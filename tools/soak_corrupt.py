@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Randomised corruption soak of the decoder on a GPU box (not part of the test suite).
 
-    python tools/soak_corrupt.py [--seconds 120] [--seed 1]
+    python tools/soak_corrupt.py [--seconds 120] [--seed 1] [--checksum]
 
 Every round compresses a few reads on the device (random dtype / shape / level 1 or 4; sometimes few large reads, whose
 frames carry a span index), damages the compressed buffers -- bit flips, byte overwrites, truncation, garbage appended,
 a damaged trailer -- and decodes them on the device.  Required: no fault, and whenever the device returns samples the
 reference path (oracle + libzstd) must return the same samples (the device may refuse what libzstd's leniency lets
-through, never the other way round)."""
+through, never the other way round).  --checksum: the device writes every frame with its content checksum (vbz_gpu_set_checksum),
+and the reference path's libzstd verifies it: the verdicts of both decoders on damaged checksummed frames are held to each other the
+same way, and the refusals both agree on are counted."""
 import argparse
 import os
 import sys
@@ -58,10 +60,15 @@ def main():
     ap.add_argument("--writer", choices=["device", "reference"], default="device",
                     help="reference: the frames are libzstd's (the oracle's compressor, levels 1 and 3), int16 reads long enough for the chain walk and the "
                          "literals beside it -- run with VBZ_HIP_REF_CHAINS=2, which walks in calls of any size")
+    ap.add_argument("--checksum", action="store_true", help="the device writes its frames with content checksums (device writer only)")
     args = ap.parse_args()
+    if args.checksum:
+        if args.writer != "device":
+            ap.error("--checksum needs --writer device")
+        G.codec().set_checksum(1)
     rng = np.random.default_rng(args.seed)
     t0 = time.time()
-    rounds = decoded = refused = stricter = 0
+    rounds = decoded = refused = stricter = both_refused = 0
     while time.time() - t0 < args.seconds:
         size = int(rng.choice([1, 2, 2, 2, 4]))
         dt = {1: np.int8, 2: np.int16, 4: np.int32}[size]
@@ -86,6 +93,9 @@ def main():
         for b, f in zip(bufs, frames):
             if isinstance(f, int):
                 continue
+            if args.checksum and level != 0 and not f[4 + (4 if sized else 0)] & 4:
+                print("FRAME WITHOUT CHECKSUM seed %d round %d" % (args.seed, rounds))
+                return 1
             for _ in range(4):
                 bad.append(damage(rng, f))
                 want.append(b.nbytes)
@@ -95,6 +105,7 @@ def main():
             if isinstance(g, int):
                 refused += 1
                 stricter += 0 if isinstance(ref, int) else 1
+                both_refused += 1 if isinstance(ref, int) else 0
             else:
                 decoded += 1
                 if isinstance(ref, int) or ref.tobytes() != g.tobytes():
@@ -109,8 +120,9 @@ def main():
                     print("reproducer written to", out)
                     return 1
         rounds += 1
-    print("corruption soak ok: %d rounds, %d damaged buffers decoded like the reference, %d refused (%d of them accepted by libzstd), %.0f s, seed %d"
-          % (rounds, decoded, refused, stricter, time.time() - t0, args.seed))
+    print("corruption soak ok%s: %d rounds, %d damaged buffers decoded like the reference, %d refused (%d of them accepted by libzstd, %d refused "
+          "by both), %.0f s, seed %d" % (" (checksum writer)" if args.checksum else "", rounds, decoded, refused, stricter, both_refused,
+                                         time.time() - t0, args.seed))
     return 0
 
 

@@ -169,6 +169,66 @@ __global__ __launch_bounds__(256) void k_s_add_u32(Stamp* st, unsigned* sink, un
 typedef void (*Kern)(Stamp*, unsigned*, unsigned);
 struct Case { const char* name; Kern k; };
 
+// 64-bit multiplies (the XXH64 round of xxh64.hip is two of them, a 64-bit add and a rotation, as one dependent chain per lane).
+// v_mad_u64_u32: eight independent 64-bit accumulators, one instruction each, as the other classes.
+#define M8(OP) OP " %0, vcc, %8, %9, %0\n" OP " %1, vcc, %8, %9, %1\n" OP " %2, vcc, %8, %9, %2\n" OP " %3, vcc, %8, %9, %3\n" \
+               OP " %4, vcc, %8, %9, %4\n" OP " %5, vcc, %8, %9, %5\n" OP " %6, vcc, %8, %9, %6\n" OP " %7, vcc, %8, %9, %7\n"
+__global__ __launch_bounds__(256) void k_mad_u64_u32(Stamp* st, unsigned* sink, unsigned seed)
+{
+    unsigned long long a0 = threadIdx.x + seed, a1 = a0 * 3, a2 = a0 * 5, a3 = a0 * 7, a4 = a0 * 9, a5 = a0 * 11, a6 = a0 * 13, a7 = a0 * 17;
+    unsigned b = seed | 1u, c = threadIdx.x * 9u;
+    unsigned long long t0 = __builtin_readcyclecounter();
+    for (int it = 0; it < ITER; ++it)
+        asm volatile(M8("v_mad_u64_u32") M8("v_mad_u64_u32") M8("v_mad_u64_u32") M8("v_mad_u64_u32")
+                     : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
+                     : "v"(b), "v"(c)
+                     : "vcc");
+    unsigned long long t1 = __builtin_readcyclecounter();
+    if ((threadIdx.x & 63) == 0) st[blockIdx.x * 4 + (threadIdx.x >> 6)] = Stamp{ t0, t1 };
+    sink[blockIdx.x * 256 + threadIdx.x] = (unsigned)(a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7);
+}
+// a full 64 x 64 -> 64 multiply as the compiler emits it (v_mad_u64_u32 + 2 v_mul_lo_u32 + v_add3_u32): eight independent products,
+// 32 per trip; the row counts one PRODUCT as one "instruction"
+__global__ __launch_bounds__(256) void k_mul64(Stamp* st, unsigned* sink, unsigned seed)
+{
+    unsigned long long a[8];
+    for (int i = 0; i < 8; ++i) a[i] = (threadIdx.x + seed) * (2ull * i + 3) | 1;
+    const unsigned long long m = 0x9E3779B185EBCA87ull ^ ((unsigned long long)seed << 32);
+    unsigned long long t0 = __builtin_readcyclecounter();
+    for (int it = 0; it < ITER; ++it) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a[i] *= m;
+            // (opaque between the rounds: otherwise the compiler multiplies once by m^4)
+            asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]));
+        }
+    }
+    unsigned long long t1 = __builtin_readcyclecounter();
+    if ((threadIdx.x & 63) == 0) st[blockIdx.x * 4 + (threadIdx.x >> 6)] = Stamp{ t0, t1 };
+    unsigned long long x = 0;
+    for (int i = 0; i < 8; ++i) x ^= a[i];
+    sink[blockIdx.x * 256 + threadIdx.x] = (unsigned)x;
+}
+// the XXH64 round (acc += w * P2; acc = rotl(acc, 31); acc *= P1) as ONE dependent chain per lane: with one wavefront per SIMD the
+// "cycles" column is the chain's latency per round -- what one large buffer's hash (one quad, xxh64.hip) is bound by when its loads
+// are hidden.  The row counts one ROUND as one "instruction".
+__global__ __launch_bounds__(256) void k_xxh64_chain(Stamp* st, unsigned* sink, unsigned seed)
+{
+    const unsigned long long P1 = 0x9E3779B185EBCA87ull, P2 = 0xC2B2AE3D27D4EB4Full;
+    unsigned long long acc = threadIdx.x + seed, w = (unsigned long long)seed * 0x100000001ull + threadIdx.x;
+    unsigned long long t0 = __builtin_readcyclecounter();
+    for (int it = 0; it < ITER * GROUP; ++it) {
+        acc += w * P2;
+        acc = (acc << 31) | (acc >> 33);
+        acc *= P1;
+        asm volatile("" : "+v"(w));   // (w is an input the compiler cannot hoist the product of)
+    }
+    unsigned long long t1 = __builtin_readcyclecounter();
+    if ((threadIdx.x & 63) == 0) st[blockIdx.x * 4 + (threadIdx.x >> 6)] = Stamp{ t0, t1 };
+    sink[blockIdx.x * 256 + threadIdx.x] = (unsigned)acc;
+}
+
 int main(int argc, char** argv)
 {
     int dev = 0;
@@ -189,6 +249,7 @@ int main(int argc, char** argv)
         { "v_cndmask_b32 (vcc never written)", k_cndmask }, { "sub_u32", k_sub_u32 }, { "and_b32", k_and_b32 }, { "or_b32", k_or_b32 }, { "min_u32", k_min_u32 }, { "lshrrev_b32", k_lshrrev_b32 }, { "ashrrev_i32", k_ashrrev_i32 }, { "mul_u32_u24", k_mul_u32_u24 }, { "add3_u32", k_add3_u32 }, { "and_or_b32", k_and_or_b32 }, { "or3_b32", k_or3_b32 }, { "xad_u32", k_xad_u32 }, { "lshl_add_u32", k_lshl_add_u32 }, { "add_lshl_u32", k_add_lshl_u32 }, { "alignbyte_b32", k_alignbyte_b32 }, { "pk_sub_i16", k_pk_sub_i16 }, { "pk_ashrrev_i16", k_pk_ashrrev_i16 }, { "pk_min_u16", k_pk_min_u16 }, { "mbcnt_lo", k_mbcnt_lo }, { "mov_b32", k_mov_b32 }, { "bitop3", k_bitop3 }, { "cmp + vcc", k_cmp_vcc }, { "cmp + cndmask", k_cmp_cndmask }, { "cmp + sgpr + cndmask", k_cmp_sgpr_cndmask }, { "cmp + addc", k_cmp_addc }, { "readlane", k_readlane }, { "ds_bpermute", k_ds_bpermute },  { "v_mov_b32_dpp row_shr:1", k_mov_dpp }, { "v_lshlrev_b64", k_lshlrev_b64 }, { "s_add_u32", k_s_add_u32 },
         { "ds_write_b32", k_ds_write_b32 }, { "ds_write_b8", k_ds_write_b8 }, { "ds_or_b32", k_ds_or_b32 }, { "ds_add_u32", k_ds_add_u32 },
         { "ds_read_b32", k_ds_read_b32 }, { "ds_read_u8", k_ds_read_u8 },
+        { "v_mad_u64_u32", k_mad_u64_u32 }, { "64x64->64 multiply (sequence)", k_mul64 }, { "xxh64 round (dependent chain)", k_xxh64_chain },
     };
     const int maxw = 8;
     Stamp* st;

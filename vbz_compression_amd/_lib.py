@@ -70,6 +70,7 @@ GPU_API = [
     "vbz_gpu_last_error",
     "vbz_gpu_set_trailers",
     "vbz_gpu_set_canonical",
+    "vbz_gpu_set_checksum",
     "vbz_gpu_synchronize",
     "vbz_gpu_compress_batch",
     "vbz_gpu_decompress_batch",
@@ -77,6 +78,7 @@ GPU_API = [
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
     "vbz_gpu_zstd_decompress_batch",
+    "vbz_gpu_xxh64_batch",
     "vbz_gpu_synth_lengths",
     "vbz_gpu_synth_signal",
     "vbz_gpu_synth_u32",
@@ -131,6 +133,12 @@ def load():
     if hasattr(L, "vbz_gpu_set_canonical"):   # (builds of earlier rounds, loaded through VBZ_HIP_LIB, do not have it)
         L.vbz_gpu_set_canonical.restype = None
         L.vbz_gpu_set_canonical.argtypes = [vp, ctypes.c_int]
+    if hasattr(L, "vbz_gpu_set_checksum"):   # (likewise: builds of earlier rounds have no content checksums)
+        L.vbz_gpu_set_checksum.restype = None
+        L.vbz_gpu_set_checksum.argtypes = [vp, ctypes.c_int]
+    if hasattr(L, "vbz_gpu_xxh64_batch"):
+        L.vbz_gpu_xxh64_batch.restype = ctypes.c_int
+        L.vbz_gpu_xxh64_batch.argtypes = [vp, bp, vp]
     L.vbz_gpu_synchronize.restype = ctypes.c_int
     L.vbz_gpu_synchronize.argtypes = [vp]
     for name in ("vbz_gpu_compress_batch", "vbz_gpu_decompress_batch"):

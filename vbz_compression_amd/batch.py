@@ -53,6 +53,11 @@ class GpuCodec:
         (include/vbz_gpu.h: vbz_gpu_set_canonical)."""
         self.L.vbz_gpu_set_canonical(self.ctx, int(bool(enable)))
 
+    def set_checksum(self, enable):
+        """Write every zstd frame with its content checksum (XXH64 of the svb stream), which every zstd decoder verifies: off by default
+        (include/vbz_gpu.h: vbz_gpu_set_checksum).  Decoding always verifies checksums that frames carry."""
+        self.L.vbz_gpu_set_checksum(self.ctx, int(bool(enable)))
+
     def close(self):
         if getattr(self, "ctx", None):
             self.L.vbz_gpu_destroy(self.ctx)
@@ -139,6 +144,25 @@ class GpuCodec:
         cur = self._enter()
         try:
             self._rc(self.L.vbz_gpu_zstd_decompress_batch(self.ctx, ctypes.byref(b)), "zstd_decompress_batch")
+        finally:
+            self._exit(cur)
+
+    def xxh64(self, src, src_off, src_size, out):
+        """out[i] = XXH64 (seed 0) of src[src_off[i] : src_off[i] + src_size[i]]; out: an int64 tensor of n entries whose bits are
+        the uint64 hashes (include/vbz_gpu.h: vbz_gpu_xxh64_batch)."""
+        n = int(src_off.numel())
+        for t, dt in ((src_off, torch.int64), (src_size, torch.int32), (out, torch.int64)):
+            assert t.dtype == dt and t.is_contiguous() and t.device == self.device, (t.dtype, dt, t.device)
+        assert src.dtype == torch.uint8 and int(out.numel()) >= n
+        b = _lib.GpuBatch()
+        b.n_reads = n
+        b.src = src.data_ptr()
+        b.src_off = src_off.data_ptr()
+        b.src_size = src_size.data_ptr()
+        b.src_bytes = src.numel()
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_xxh64_batch(self.ctx, ctypes.byref(b), out.data_ptr()), "xxh64_batch")
         finally:
             self._exit(cur)
 

@@ -103,6 +103,8 @@ struct vbz_gpu_ctx
     uint32_t last_span_frames = 0;          // ... of the last call on the large-read path, and its redo[] (in spanmeta)
     const uint32_t* last_span_redo = nullptr;
     bool trailers = true;      // decoder hints (checkpoints, span index) in skippable frames behind the zstd frame
+    bool checksum = false;     // vbz_gpu_set_checksum / VBZ_HIP_CHECKSUM=1: frames written with the content checksum (xxh64.hip)
+    DevBuf cksum;              // the hashes of a compress launch group (8 bytes per read)
     int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
     bool zero_run_sequences = true;
     bool fuse_svb = false;     // VBZ_HIP_FUSE_SVB=1: the frame's wavefront decodes the svb stream too (measured slower: DESIGN.md 4.4)
@@ -404,6 +406,37 @@ struct Preplanned
     hipEvent_t after_first = nullptr;   // recorded on the group's stream behind its first large launch (the other half may wait for it)
 };
 
+// The content checksum of the frames of an entropy stage (vbz_gpu_set_checksum), in two launches of its own around the stage, whatever
+// path writes the frames.  z = that stage's batch (src: the frames' content, dst / result: the frames), gate: the group's (nullable).
+// checksum_content runs IN FRONT of the stage: the staged encoder rewrites the control bytes of an svb stream in its scratch slot in place.
+int checksum_content(vbz_gpu_ctx* c, const ReadBatch& z, const uint32_t* gate)
+{
+    if (!c->checksum || z.n_reads == 0) return 0;
+    if (!ensure(c, c->cksum, (size_t)z.n_reads * 8 + 64)) return -1;
+    Timed t(c, "checksum");
+    HIPCHK(c, launch_xxh64_batch(z.src, z.src_off, z.src_size, gate, nullptr, z.n_reads, reinterpret_cast<uint64_t*>(c->cksum.p), c->stream), "xxh64 launch");
+    return 0;
+}
+// ... and behind it: the frames get the flag and the checksum.  raw_size (nullable) + integer_size: what bounds the result.
+int checksum_frames(vbz_gpu_ctx* c, const ReadBatch& z, const uint32_t* gate, uint32_t hdr, const uint32_t* raw_size, uint32_t integer_size)
+{
+    if (!c->checksum || z.n_reads == 0) return 0;
+    Timed t(c, "checksum");
+    ReadBatch w = z;
+    w.gate = gate;
+    HIPCHK(c, launch_checksum_insert(w, reinterpret_cast<const uint64_t*>(c->cksum.p), hdr, raw_size, integer_size, c->stream), "checksum insert launch");
+    return 0;
+}
+
+// A decode's zstd stage is done (z: frames, their content and its sizes): frames that carry a content checksum are held to it.  One short
+// launch that looks at one byte of every frame without the flag.
+int verify_checksums(vbz_gpu_ctx* c, const ReadBatch& z)
+{
+    Timed t(c, "checksum_verify");
+    HIPCHK(c, launch_xxh64_verify(z, c->stream), "checksum verify launch");
+    return 0;
+}
+
 // One launch group of a compress call: the reads of rb_in (those whose gate is closed left alone), on the one-workgroup path or
 // on the large-read path.  src_bytes: extent of the raw bytes of the group's reads.
 int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, const CompressionOptions* o, int sized, bool segmented,
@@ -464,9 +497,12 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
         return 0;
     }
     if (o->integer_size == 0) {  // zstd only
-        Timed t(c, "zstd_encode");
-        HIPCHK(c, launch_zstd_encode(rb, bt->src_size, 0, nullptr, hdr, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, s), "zstd_encode launch");
-        return 0;
+        if (checksum_content(c, rb, rb.gate) != 0) return -1;
+        {
+            Timed t(c, "zstd_encode");
+            HIPCHK(c, launch_zstd_encode(rb, bt->src_size, 0, nullptr, hdr, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, s), "zstd_encode launch");
+        }
+        return checksum_frames(c, rb, rb.gate, hdr, bt->src_size, 0);
     }
     // the long-repeat matcher (every level: the reference's libzstd matches at every level; its workspace is the top of the
     // destination slots)
@@ -508,6 +544,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
     z.src = (const uint8_t*)scratch_base;
     z.src_off = svb_off;
     z.src_size = svb_size;
+    if (checksum_content(c, z, gate) != 0) return -1;
     if (segmented) {  // few, large reads: one wavefront per span of a stream, then compaction
         const uint32_t max_spans = zstd_span_max_spans(scratch_need, n);
         if (!max_spans) {
@@ -552,7 +589,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
                                            c->zero_run_sequences ? c->seqtab.p : nullptr, desc, span_first, span_count, max_spans,
                                            (uint8_t*)c->spantmp.p, tmp_bytes, span_size, span_trail, span_dst, c->trailers, regions, shspan, s),
                "zstd_encode (spans) launch");
-        return 0;
+        return checksum_frames(c, z, gate, hdr, bt->src_size, o->integer_size);
     }
     {
         Timed t(c, "zstd_encode");
@@ -567,7 +604,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
             : c->phase_timing == 2 ? "zstd_encode planning launch: setup hist plan - store+sequences - | plan: sort merge lengths codes weights tree"
                                    : "zstd_encode: setup hist plan size hdr encode",
             dbg);
-    return 0;
+    return checksum_frames(c, z, gate, hdr, bt->src_size, o->integer_size);
 }
 
 constexpr uint32_t REF_MIN_READS = 2560;   // calls of fewer reads: the one-wavefront decoder walks reference-written chains itself
@@ -695,9 +732,10 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
         if (segmented) {
             Timed t(c, "zstd_decode");
             HIPCHK(c, launch_zstd_decode(rb, E_DESTINATION_SIZE, nullptr, c->seqdtab.p, s), "zstd_decode launch");
-            return 0;
+        } else if (zstd_frames(c, rb, E_DESTINATION_SIZE, dst_bytes, nullptr) != 0) {
+            return -1;
         }
-        return zstd_frames(c, rb, E_DESTINATION_SIZE, dst_bytes, nullptr);
+        return verify_checksums(c, rb);
     }
     // entropy stage into scratch (sized for the largest svb stream the expected output can have),
     // then svb decode into dst (vbz.cpp:234-299)
@@ -714,7 +752,7 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     unsigned long long* dbg = segmented ? nullptr : dbg_begin(c, n);
     // the hot path -- int16 zig-zag samples, one wavefront per frame: optionally (VBZ_HIP_FUSE_SVB=1) the wavefront decodes the
     // svb stream it has just written while it is still in the caches, straight into the destination, and there is no
-    // svb_decode launch (measured slower than the separate launch: profiles/r03_fused_svb_decode.md)
+    // svb_decode launch (measured slower than the separate launch: profiles/r03_fused_svb_decode.md; it does not verify content checksums)
 #ifdef VBZ_EXPERIMENTS
     if (!segmented && !dbg && c->fuse_svb && o->integer_size == 2 && o->perform_delta_zig_zag) {
         z.result = rb.result;
@@ -750,6 +788,7 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     }
     if (pre && pre->after_first) HIPCHK(c, hipEventRecord(pre->after_first, s), "event record");
     dbg_end(c, n, "zstd_decode: parse flush seqtables chain place huftable header queue | general sequences: flush tables records literals matches", dbg);
+    if (verify_checksums(c, z) != 0) return -1;
     ReadBatch d = rb;
     d.src = (const uint8_t*)scratch_base;
     d.src_off = svb_off;
@@ -810,6 +849,7 @@ int ensure_large(vbz_gpu_ctx* c)
     c->large->long_repeats = c->long_repeats;
     c->large->shared_tables = c->shared_tables;
     c->large->canonical = c->canonical;
+    c->large->checksum = c->checksum;
     c->large->segmented = 1;
     return 0;
 }
@@ -895,6 +935,7 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
     }
     vbz_gpu_ctx* k = c->half;
     k->trailers = c->trailers;
+    k->checksum = c->checksum;
     k->zero_run_sequences = c->zero_run_sequences;
     k->long_repeats = c->long_repeats;
     k->staged_encode = c->staged_encode;
@@ -1189,6 +1230,7 @@ vbz_gpu_ctx* vbz_gpu_create(int device, void* stream)
     if (const char* e = getenv("VBZ_HIP_SEGMENTED")) c->segmented = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_TRAILERS")) c->trailers = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_CANONICAL")) c->canonical = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_CHECKSUM")) c->checksum = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_SPLIT_MIN")) c->split_min = (uint32_t)strtoul(e, nullptr, 10);   // 0: a batch is never coded as two halves
     if (const char* e = getenv("VBZ_HIP_SPLIT_STAGGER")) c->split_stagger = atoi(e);
 #ifdef VBZ_EXPERIMENTS
@@ -1239,7 +1281,7 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
         (void)hipEventDestroy(p.stop);
     }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev })
+    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum })
         if (b->p) (void)hipFree(b->p);
     if (c->large) vbz_gpu_destroy(c->large);
     if (c->half) vbz_gpu_destroy(c->half);
@@ -1267,6 +1309,10 @@ void vbz_gpu_set_trailers(vbz_gpu_ctx* c, int enable)
 void vbz_gpu_set_canonical(vbz_gpu_ctx* c, int enable)
 {
     if (c) c->canonical = enable != 0;
+}
+void vbz_gpu_set_checksum(vbz_gpu_ctx* c, int enable)
+{
+    if (c) c->checksum = enable != 0;
 }
 const char* vbz_gpu_last_error(vbz_gpu_ctx* c) { return c ? c->error.c_str() : "no context"; }
 
@@ -1325,9 +1371,10 @@ int vbz_gpu_zstd_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const u
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
+    if (checksum_content(c, to_rb(bt), nullptr) != 0) return -1;
     Timed t(c, "zstd_encode");
     HIPCHK(c, launch_zstd_encode(to_rb(bt), bt->src_size, 0, key_bytes, 0, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, c->stream), "zstd_encode launch");
-    return 0;
+    return checksum_frames(c, to_rb(bt), nullptr, 0, nullptr, 0);
 }
 
 int vbz_gpu_zstd_decompress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt)
@@ -1335,7 +1382,17 @@ int vbz_gpu_zstd_decompress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt)
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
     if (!plausible_extents(c, bt)) return -2;
-    return zstd_frames(c, to_rb(bt), E_ZSTD, bt->dst_bytes, nullptr);
+    if (zstd_frames(c, to_rb(bt), E_ZSTD, bt->dst_bytes, nullptr) != 0) return -1;
+    return verify_checksums(c, to_rb(bt));
+}
+
+int vbz_gpu_xxh64_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, uint64_t* out)
+{
+    if (!c || !bt || !out) return -1;
+    DeviceGuard dg(c->device);
+    Timed t(c, "xxh64");
+    HIPCHK(c, launch_xxh64_batch((const uint8_t*)bt->src, bt->src_off, bt->src_size, nullptr, nullptr, bt->n_reads, out, c->stream), "xxh64 launch");
+    return 0;
 }
 
 int vbz_gpu_synth_lengths(vbz_gpu_ctx* c, uint64_t seed, uint64_t first, uint32_t n, uint32_t* out_len)

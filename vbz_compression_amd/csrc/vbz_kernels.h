@@ -236,6 +236,19 @@ uint32_t zstd_dspan_max_spans(uint64_t content_bytes, uint32_t n_reads);  // 0: 
 hipError_t launch_zstd_decode_spans(const ReadBatch& b, uint32_t toosmall_code, const void* seq_dtables, void* dspan_desc, uint32_t* dspan_first,
                                     uint32_t* dspan_count, uint32_t max_spans, uint32_t* dspan_status, uint32_t* redo, hipStream_t s);
 
+// ---- the zstd content checksum (xxh64.hip) ------------------------------------------------------
+// out[i] = XXH64 (seed 0) of src[off[i] .. off[i] + len[i]); reads with len[i] or skip[i] >= E_FIRST, gate[i] >= GATE_SKIP are left alone (gate, skip
+// nullable).  One quad of lanes per buffer.
+hipError_t launch_xxh64_batch(const uint8_t* src, const uint64_t* off, const uint32_t* len, const uint32_t* gate, const uint32_t* skip, uint32_t n,
+                              uint64_t* out, hipStream_t s);
+// After the zstd stage of a decode (b: the frames, their decoded content at dst + dst_off[i], result[i] its size): a frame with
+// Content_Checksum_flag whose content does not hash to the stored value gets result[i] = E_ZSTD.  Frames without the flag: one byte read.
+hipError_t launch_xxh64_verify(const ReadBatch& b, hipStream_t s);
+// After the entropy stage of an encode (b: the frames written, result[i] bytes at dst + dst_off[i] including `hdr` bytes of sized header;
+// hash[i] = XXH64 of the frame's content): Content_Checksum_flag and the checksum behind the last block, the trailers moved behind it.
+// raw_size (nullable) + integer_size: the raw read sizes whose vbz_max_compressed_size the result must not exceed.
+hipError_t launch_checksum_insert(const ReadBatch& b, const uint64_t* hash, uint32_t hdr, const uint32_t* raw_size, uint32_t integer_size, hipStream_t s);
+
 // ---- helpers (helpers.hip) ---------------------------------------------------------------------
 // scratch slots for the intermediate svb streams: slot(i) = align16(ceil(raw_size[i]*num/den)+8)+48,
 // off[i] = exclusive scan + 16, cap[i] = slot - 32; gate[i] = E_OOM if the slot exceeds `limit` bytes.

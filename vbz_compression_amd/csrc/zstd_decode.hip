@@ -2677,7 +2677,8 @@ __global__ __launch_bounds__(1024) void zstd_dspan_plan_kernel(ReadBatch b, uint
     for (uint32_t base = 0; base < b.n_reads; base += 1024) {
         const uint32_t i = base + tid;
         const uint32_t here = (b.n_reads - base) < 1024u ? (b.n_reads - base) : 1024u;
-        // (1) one thread per read: frame header (single segment, no dictionary, no checksum: what zstd_encode.hip writes)
+        // (1) one thread per read: frame header (single segment, no dictionary, with or without a content checksum: what zstd_encode.hip
+        // writes; the checksum stands between the last span's last block and the trailers)
         // and the envelope of the index trailer
         q_ok[tid] = 0;
         q_T[tid] = 0;
@@ -2691,7 +2692,7 @@ __global__ __launch_bounds__(1024) void zstd_dspan_plan_kernel(ReadBatch b, uint
                 const uint32_t fhd = src[4];
                 const int fcs_flag = fhd >> 6;
                 uint64_t fcs = 0;
-                bool ok = magic == 0xFD2FB528u && (fhd & 0x3F) == 0x20;
+                bool ok = magic == 0xFD2FB528u && (fhd & 0x3B) == 0x20;
                 if (ok) {
                     const uint32_t fsz = fcs_flag == 0 ? 1u : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
                     for (uint32_t k = 0; k < fsz; ++k) fcs |= (uint64_t)src[5 + k] << (8 * k);
