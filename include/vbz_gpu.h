@@ -155,6 +155,32 @@ VBZ_EXPORT int vbz_gpu_zstd_decompress_batch(vbz_gpu_ctx* ctx, const vbz_gpu_bat
  * ~100 KB: 1.3 ms, ~5 TB/s), one read near the speed of its chain (one 40 MB buffer: ~41 ms, ~1 GB/s). */
 VBZ_EXPORT int vbz_gpu_xxh64_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, uint64_t* out);
 
+/* Dense arenas.  A compress call leaves every read in a slot of vbz_max_compressed_size(raw) bytes; these two calls lay a batch out
+ * contiguously instead, each byte count rounded up to `align` (a power of two, 1 ... 4096), error entries taking no bytes:
+ * off[i] = the exclusive scan of the rounded counts, off[n] = the total (device tables of n + 1 and n words).  Both are asynchronous
+ * on the context's stream and return 0 when queued, -1 for a NULL context or batch or a launch failure, -2 for bad arguments,
+ * refused on the host before anything is launched: `align`, unknown options, a NULL pointer among the fields the call uses, a declared
+ * extent beyond 2^46 bytes.
+ *
+ * vbz_gpu_pack_batch: the dense arena of a finished compress (or decompress) call.  Uses n_reads, dst, dst_off, dst_cap, dst_bytes and
+ * result; the src fields are not looked at.  result[] is untrusted like the descriptor tables: a read takes space only when result[i]
+ * is a byte count (!vbz_is_error) that fits dst_cap[i] and its slot lies inside [0, dst_bytes); packed_size[i] = that count,
+ * result[i] unchanged when it is an error code, VBZ_INPUT_SIZE_ERROR for a count that does not fit its slot (whose bytes are then
+ * never read).  The bytes -- and zeros in the padding between reads -- are written to packed only when packed != NULL and
+ * packed_off[n] <= packed_cap; otherwise nothing in packed is touched (packed = NULL: the tables alone, one synchronisation away from
+ * sizing the arena; an arena too small fails whole, it never holds some of the reads).  packed must not overlap the dst arena (-2).
+ * With align >= 16, (packed, packed_off, packed_size) are directly the src tables of a vbz_gpu_decompress_batch on the decoders'
+ * aligned path; like every src arena, the packed one must then stay readable for 16 bytes behind packed_off[n].
+ * Measured on one MI355X: profiles/HISTORY.md (dense arenas). */
+VBZ_EXPORT int vbz_gpu_pack_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, uint32_t align, void* packed, uint64_t packed_cap,
+                                  uint64_t* packed_off /* n + 1 */, uint32_t* packed_size /* n */);
+/* vbz_gpu_decompressed_size_batch: n x vbz_decompressed_size over sized buffers (vbz_compress_sized, the HDF5 filter's chunks), and the
+ * layout of their decoded output.  Uses n_reads, src, src_off, src_size and src_bytes; the dst fields are not looked at.  raw_size[i] =
+ * the buffer's 4-byte little-endian header, VBZ_INPUT_SIZE_ERROR for a buffer shorter than 4 bytes or outside [0, src_bytes).  Header
+ * values are taken as they are: a damaged one can ask for up to 4 GB, which the caller sees in raw_off[n] before allocating. */
+VBZ_EXPORT int vbz_gpu_decompressed_size_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                               uint32_t align, uint32_t* raw_size /* n */, uint64_t* raw_off /* n + 1 */);
+
 /* Synthetic workload of SURVEY.md section 8(d), generated on the device (no host data needed).
  *   lengths:  out_len[i] = samples of read first_read+i (90 000 + mix(..) % 20 001), i < n_reads
  *   signal:   int16 samples of read first_read+i written at dst + off[i] (bytes), len[i] samples

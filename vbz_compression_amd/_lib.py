@@ -79,6 +79,8 @@ GPU_API = [
     "vbz_gpu_zstd_compress_batch",
     "vbz_gpu_zstd_decompress_batch",
     "vbz_gpu_xxh64_batch",
+    "vbz_gpu_pack_batch",
+    "vbz_gpu_decompressed_size_batch",
     "vbz_gpu_synth_lengths",
     "vbz_gpu_synth_signal",
     "vbz_gpu_synth_u32",
@@ -139,6 +141,11 @@ def load():
     if hasattr(L, "vbz_gpu_xxh64_batch"):
         L.vbz_gpu_xxh64_batch.restype = ctypes.c_int
         L.vbz_gpu_xxh64_batch.argtypes = [vp, bp, vp]
+    if hasattr(L, "vbz_gpu_pack_batch"):   # (likewise: builds of earlier rounds have no dense arenas)
+        L.vbz_gpu_pack_batch.restype = ctypes.c_int
+        L.vbz_gpu_pack_batch.argtypes = [vp, bp, u32, vp, u64, vp, vp]
+        L.vbz_gpu_decompressed_size_batch.restype = ctypes.c_int
+        L.vbz_gpu_decompressed_size_batch.argtypes = [vp, bp, op, u32, vp, vp]
     L.vbz_gpu_synchronize.restype = ctypes.c_int
     L.vbz_gpu_synchronize.argtypes = [vp]
     for name in ("vbz_gpu_compress_batch", "vbz_gpu_decompress_batch"):

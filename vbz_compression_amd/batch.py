@@ -166,6 +166,84 @@ class GpuCodec:
         finally:
             self._exit(cur)
 
+    # -- dense arenas ------------------------------------------------------------------------------
+    def _sync_total(self, off):
+        """off[-1] (an int64 table the codec's stream has written) on the host: one synchronisation"""
+        self._rc(self.L.vbz_gpu_synchronize(self.ctx), "synchronize")
+        return int(off[-1].item())
+
+    def pack(self, dst, dst_off, dst_cap, result, align=16, out=None):
+        """Dense arena of a finished compress (or decompress) call (include/vbz_gpu.h: vbz_gpu_pack_batch) -> (packed, packed_off,
+        packed_size): read i's result[i] bytes at packed[packed_off[i]:], packed_off int64 [n + 1] (packed_off[n] = the total), packed_size
+        int32 [n] whose bits are the byte count or the error code.  Without `out` the tables are computed first, one synchronisation reads
+        the total and the arena is allocated (total + 64 bytes: the decoders' slack); with `out` (uint8) nothing synchronises, and an `out`
+        smaller than the total is left untouched."""
+        n = int(dst_off.numel())
+        for t, dt in ((dst_off, torch.int64), (dst_cap, torch.int32), (result, torch.int32)):
+            assert t.dtype == dt and t.is_contiguous() and t.device == self.device, (t.dtype, dt, t.device)
+        assert dst.dtype == torch.uint8 and int(dst_cap.numel()) == n and int(result.numel()) == n
+        b = _lib.GpuBatch()
+        b.n_reads = n
+        b.dst = dst.data_ptr()
+        b.dst_off = dst_off.data_ptr()
+        b.dst_cap = dst_cap.data_ptr()
+        b.dst_bytes = dst.numel()
+        b.result = result.data_ptr()
+        packed_off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        packed_size = torch.empty(n, dtype=torch.int32, device=self.device)
+        cur = self._enter()
+        try:
+            if out is None:
+                self._rc(self.L.vbz_gpu_pack_batch(self.ctx, ctypes.byref(b), align, None, 0, packed_off.data_ptr(), packed_size.data_ptr()), "pack_batch")
+                out = torch.empty(self._sync_total(packed_off) + 64, dtype=torch.uint8, device=self.device)
+            assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+            self._rc(self.L.vbz_gpu_pack_batch(self.ctx, ctypes.byref(b), align, out.data_ptr(), out.numel(), packed_off.data_ptr(), packed_size.data_ptr()),
+                     "pack_batch")
+        finally:
+            self._exit(cur)
+        return out, packed_off, packed_size
+
+    def decompressed_sizes(self, src, src_off, src_size, opts, align=16):
+        """n x vbz_decompressed_size of sized buffers and their output layout (include/vbz_gpu.h: vbz_gpu_decompressed_size_batch) ->
+        (raw_size int32 [n], bits = the size or an error code; raw_off int64 [n + 1], raw_off[n] = the total)."""
+        n = int(src_off.numel())
+        for t, dt in ((src_off, torch.int64), (src_size, torch.int32)):
+            assert t.dtype == dt and t.is_contiguous() and t.device == self.device, (t.dtype, dt, t.device)
+        assert src.dtype == torch.uint8 and int(src_size.numel()) == n
+        b = _lib.GpuBatch()
+        b.n_reads = n
+        b.src = src.data_ptr()
+        b.src_off = src_off.data_ptr()
+        b.src_size = src_size.data_ptr()
+        b.src_bytes = src.numel()
+        raw_size = torch.empty(n, dtype=torch.int32, device=self.device)
+        raw_off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_decompressed_size_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), align, raw_size.data_ptr(), raw_off.data_ptr()),
+                     "decompressed_size_batch")
+        finally:
+            self._exit(cur)
+        return raw_size, raw_off
+
+    def decompress_packed(self, packed, packed_off, packed_size, opts, align=16):
+        """Decode a dense arena of sized buffers (pack() of a sized compress call): the sizes come from the headers, the output is
+        allocated (one synchronisation) and the batch decoded -> (raw, raw_off, raw_size, result).  An entry whose size is an error code
+        gets dst_cap = 0, so the decoder gives the verdict vbz_decompress_sized gives for that buffer (VBZ_INPUT_SIZE_ERROR under 4 bytes)."""
+        n = int(packed_size.numel())
+        src_off = packed_off[:n]
+        raw_size, raw_off = self.decompressed_sizes(packed, src_off, packed_size, opts, align)
+        cur = self._enter()
+        try:
+            raw = torch.empty(self._sync_total(raw_off) + 64, dtype=torch.uint8, device=self.device)
+        finally:
+            self._exit(cur)
+        err = (raw_size < 0) & (raw_size >= _lib.VBZ_DEVICE_ERROR - (1 << 32))
+        dst_cap = torch.where(err, torch.zeros_like(raw_size), raw_size)
+        result = torch.empty(n, dtype=torch.int32, device=self.device)
+        self.decompress(packed, src_off, packed_size, raw, raw_off[:n], dst_cap, result, opts, sized=True)
+        return raw, raw_off, raw_size, result
+
     # -- synthetic workload (SURVEY.md 8d) ----------------------------------------------------------
     def synth_lengths(self, seed, first_read, n_reads):
         out = torch.empty(n_reads, dtype=torch.int32, device=self.device)

@@ -381,9 +381,10 @@ bool run_batch(Gpu& g, const std::vector<const std::vector<uint8_t>*>& in, const
         doff[i] = dbytes;
         dbytes += ((uint64_t)out_cap[i] + 15) & ~15ull;
     }
-    DevBuf dsrc, ddst, dmeta;
-    const size_t meta = (size_t)n * (8 + 8 + 4 + 4 + 4);
-    if (!dsrc.alloc(sbytes + 64) || !ddst.alloc(dbytes + 64) || !dmeta.alloc(meta)) {
+    DevBuf dsrc, ddst, dmeta, dpack;
+    const size_t tab_at = ((size_t)n * (8 + 8 + 4 + 4 + 4) + 7) & ~(size_t)7;
+    const size_t meta = tab_at + 8ull * (n + 1) + 4ull * n;   // ... + the packed arena's tables, adjacent
+    if (!dsrc.alloc(sbytes + 64) || !ddst.alloc(dbytes + 64) || !dmeta.alloc(meta) || !dpack.alloc(dbytes + 64)) {
         fprintf(stderr, "vbz_fast5_repack: out of device memory (%llu + %llu bytes)\n", (unsigned long long)sbytes, (unsigned long long)dbytes);
         return false;
     }
@@ -394,6 +395,8 @@ bool run_batch(Gpu& g, const std::vector<const std::vector<uint8_t>*>& in, const
     uint32_t* d_ssize = (uint32_t*)(m + 16ull * n);
     uint32_t* d_cap = (uint32_t*)(m + 20ull * n);
     uint32_t* d_res = (uint32_t*)(m + 24ull * n);
+    uint64_t* d_poff = (uint64_t*)(m + tab_at);          // packed_off [n + 1], then packed_size [n]: one copy back
+    uint32_t* d_psize = (uint32_t*)(m + tab_at + 8ull * (n + 1));
     bool ok = hipMemcpy(d_soff, soff.data(), 8ull * n, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_doff, doff.data(), 8ull * n, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_ssize, ssize.data(), 4ull * n, hipMemcpyHostToDevice) == hipSuccess &&
@@ -424,16 +427,28 @@ bool run_batch(Gpu& g, const std::vector<const std::vector<uint8_t>*>& in, const
         return false;
     }
     t.gpu += now_ms() - t1;
+    // the results packed into one dense arena on the device (packed_size[i] = res[i], error codes included), then two copies: the
+    // tables, and the arena
     const double t2 = now_ms();
-    ok = hipMemcpy(res.data(), d_res, 4ull * n, hipMemcpyDeviceToHost) == hipSuccess;
-    for (uint32_t i = 0; ok && i < n; ++i) {
+    if (vbz_gpu_pack_batch(g.ctx, &b, 1, dpack.p, dbytes + 64, d_poff, d_psize) != 0 || vbz_gpu_synchronize(g.ctx) != 0) {
+        fprintf(stderr, "vbz_fast5_repack: %s\n", vbz_gpu_last_error(g.ctx));
+        return false;
+    }
+    std::vector<uint8_t> tables(12ull * n + 8);
+    ok = hipMemcpy(tables.data(), d_poff, tables.size(), hipMemcpyDeviceToHost) == hipSuccess;
+    std::vector<uint64_t> poff(n + 1);
+    if (ok) {
+        memcpy(poff.data(), tables.data(), 8ull * (n + 1));
+        memcpy(res.data(), tables.data() + 8ull * (n + 1), 4ull * n);
+    }
+    for (uint32_t i = 0; ok && i < n; ++i)
         if (vbz_is_error(res[i])) {
             fprintf(stderr, "vbz_fast5_repack: read %u: %s\n", i, vbz_error_string(res[i]));
             return false;
         }
-        out[i]->resize(res[i]);
-        if (res[i]) ok = hipMemcpy(out[i]->data(), (uint8_t*)ddst.p + doff[i], res[i], hipMemcpyDeviceToHost) == hipSuccess;
-    }
+    std::vector<uint8_t> arena(ok ? poff[n] : 0);
+    if (ok && poff[n]) ok = hipMemcpy(arena.data(), dpack.p, poff[n], hipMemcpyDeviceToHost) == hipSuccess;
+    for (uint32_t i = 0; ok && i < n; ++i) out[i]->assign(arena.data() + poff[i], arena.data() + poff[i] + res[i]);
     t.copies += now_ms() - t2;
     return ok;
 }

@@ -1,0 +1,366 @@
+// pack.hip -- dense arenas of a batch (include/vbz_gpu.h: vbz_gpu_pack_batch, vbz_gpu_decompressed_size_batch).
+//
+// Layout: every read gets a byte count (its result, or the raw size its sized header states) or an error code, and a packed offset:
+// the exclusive scan of the counts, each rounded up to `align`, error entries taking nothing; off[n] = the total.  The scan is
+// reduce-then-scan in three short launches (per 1024-read tile: sum; the tile sums; the tile's own scan), O(n) loads at any n.  The
+// tile sums travel in the offset table itself, at off[t * 1024], which only tile t's last launch overwrites.
+//
+// Gather: one wavefront per unit of 8 KB of the DESTINATION (eight rows of 64 lanes x 16 bytes, every store a whole aligned dwordx4),
+// grid-stride over the units.  A wave finds the read that holds its unit's first byte by a 64-ary search in the packed offsets, keeps
+// 64 consecutive reads' offsets, sizes and source addresses in LDS, and every lane finds its chunk's read there.  A chunk inside one
+// read's bytes is loaded as aligned dwords and shifted with v_alignbit_b32; a chunk inside padding is zeros; a chunk at a read's edge
+// (or holding several reads) is put together byte by byte.  Every load lies inside a read's own bytes [src, src + size): no address
+// outside a slot the layout launch accepted is formed.
+#include "vbz_kernels.h"
+
+namespace vbzhip {
+
+namespace {
+
+constexpr uint32_t TILE = 1024;           // reads per workgroup of the scan launches
+constexpr uint32_t ROWS = 8;              // rows of 64 x 16 bytes per gather unit
+constexpr uint32_t UNIT = ROWS * 1024;    // destination bytes per unit (one wavefront)
+constexpr uint32_t GATHER_WAVES = 4;      // wavefronts per gather workgroup
+constexpr uint32_t GATHER_MAX_WGS = 16384;
+
+__device__ __forceinline__ uint64_t round_up(uint32_t v, uint32_t align) { return ((uint64_t)v + align - 1) & ~(uint64_t)(align - 1); }
+__device__ __forceinline__ uint32_t bytes_of(uint32_t s) { return s >= E_FIRST ? 0u : s; }   // error entries occupy no bytes
+
+// sum of v over the 1024 threads, in thread 0
+__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* wsum)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    if (lane == 0) wsum[w] = v;
+    __syncthreads();
+    uint64_t t = 0;
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 16; ++k) t += wsum[k];
+    return t;
+}
+
+// exclusive prefix of v over the 1024 threads; total = the sum
+__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t* wsum, uint64_t& total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint64_t pre = 0, tot = 0;
+    for (int k = 0; k < 16; ++k) {
+        const uint64_t s = wsum[k];
+        pre += k < w ? s : 0;
+        tot += s;
+    }
+    __syncthreads();
+    total = tot;
+    return pre + inc - v;
+}
+
+// ---- layout, launch 1: per-read byte counts and the tile sums -------------------------------------------------------------------
+// pack: the result table is untrusted; a count takes space only when it fits its slot and the slot lies inside [0, dst_bytes).
+__global__ __launch_bounds__(1024) void pack_sizes_kernel(uint32_t n, const uint32_t* result, const uint64_t* dst_off, const uint32_t* dst_cap,
+                                                          uint64_t dst_bytes, uint32_t align, uint64_t* off, uint32_t* size)
+{
+    __shared__ uint64_t wsum[16];
+    const uint32_t i = blockIdx.x * TILE + threadIdx.x;
+    uint64_t take = 0;
+    if (i < n) {
+        const uint32_t r = result[i];
+        uint32_t s = r;
+        if (r < E_FIRST) {
+            const uint64_t o = dst_off[i];
+            const uint32_t cap = dst_cap[i];
+            if (r > cap || o > dst_bytes || (uint64_t)cap > dst_bytes - o) s = E_INPUT_SIZE;
+            else take = round_up(r, align);
+        }
+        size[i] = s;
+    }
+    const uint64_t t = block_sum_u64(take, wsum);
+    if (threadIdx.x == 0) off[blockIdx.x * TILE] = t;
+}
+
+// sized buffers: raw_size[i] = what vbz_decompressed_size returns (the 4-byte little-endian header; VBZ_INPUT_SIZE_ERROR for a buffer
+// shorter than 4 bytes or outside [0, src_bytes))
+__global__ __launch_bounds__(1024) void sized_sizes_kernel(uint32_t n, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_size,
+                                                           uint64_t src_bytes, uint32_t align, uint64_t* off, uint32_t* size)
+{
+    __shared__ uint64_t wsum[16];
+    const uint32_t i = blockIdx.x * TILE + threadIdx.x;
+    uint64_t take = 0;
+    if (i < n) {
+        const uint64_t o = src_off[i];
+        const uint32_t sz = src_size[i];
+        uint32_t s = E_INPUT_SIZE;
+        if (o <= src_bytes && (uint64_t)sz <= src_bytes - o && sz >= 4) {
+            const uint8_t* p = src + o;
+            s = p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+            take = s >= E_FIRST ? 0 : round_up(s, align);
+        }
+        size[i] = s;
+    }
+    const uint64_t t = block_sum_u64(take, wsum);
+    if (threadIdx.x == 0) off[blockIdx.x * TILE] = t;
+}
+
+// ---- launch 2: the exclusive scan of the tile sums (one workgroup); off[n] = the total
+__global__ __launch_bounds__(1024) void pack_scan_tiles_kernel(uint32_t n, uint64_t* off)
+{
+    __shared__ uint64_t wsum[16];
+    const uint32_t tiles = (n + TILE - 1) / TILE;
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < tiles; base += 1024) {
+        const uint32_t t = base + threadIdx.x;
+        const uint64_t v = t < tiles ? off[(uint64_t)t * TILE] : 0;
+        uint64_t sum;
+        const uint64_t pre = block_excl_scan_u64(v, wsum, sum);
+        if (t < tiles) off[(uint64_t)t * TILE] = carry + pre;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) off[n] = carry;
+}
+
+// ---- launch 3: every tile's own scan from its prefix
+__global__ __launch_bounds__(1024) void pack_scan_reads_kernel(uint32_t n, uint32_t align, const uint32_t* size, uint64_t* off)
+{
+    __shared__ uint64_t wsum[16];
+    __shared__ uint64_t prefix;
+    const uint32_t i = blockIdx.x * TILE + threadIdx.x;
+    if (threadIdx.x == 0) prefix = off[blockIdx.x * TILE];
+    const uint64_t take = i < n ? round_up(bytes_of(size[i]), align) : 0;
+    __syncthreads();
+    uint64_t sum;
+    const uint64_t pre = block_excl_scan_u64(take, wsum, sum);
+    if (i < n) off[i] = prefix + pre;
+}
+
+// ---- gather -------------------------------------------------------------------------------------------------------------------
+struct WaveCache  // 64 consecutive reads j .. j+63 of the layout (reads at or beyond n: offset = the total, no bytes)
+{
+    uint64_t lo[65];   // packed offsets of reads j .. j+64
+    uint64_t src[64];  // dst_off of each read (its bytes' source)
+    uint32_t sz[64];   // bytes of each read
+};
+
+// largest k in [0, n) with off[k] <= x (off[0] = 0 <= x): a 64-ary search by the whole wave
+__device__ uint32_t wave_find(const uint64_t* off, uint32_t n, uint64_t x)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t lo = 0, len = n;
+    while (len > 1) {
+        const uint32_t step = (len + 63) / 64;
+        const uint64_t idx = (uint64_t)lo + (uint64_t)lane * step;
+        const bool ok = idx < (uint64_t)lo + len && off[idx] <= x;
+        const uint64_t m = __ballot(ok);
+        const uint32_t l = 63 - __builtin_clzll(m);
+        const uint32_t nlo = lo + l * step;
+        len = min(step, lo + len - nlo);
+        lo = nlo;
+    }
+    return lo;
+}
+
+// lane-local binary search: largest k in [lo, n) with off[k] <= x, given off[lo] <= x
+__device__ uint32_t lane_find(const uint64_t* off, uint32_t lo, uint32_t n, uint64_t x)
+{
+    uint32_t hi = n;   // off[hi] > x or hi == n
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (off[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void wave_fill(WaveCache& c, uint32_t j, uint32_t n, const uint64_t* off, const uint32_t* size, const uint8_t* dst,
+                                          const uint64_t* dst_off, uint64_t& my_lo)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t k = (uint64_t)j + lane;
+    wave_lds_sync();   // (the lanes' last reads of the previous cache come first)
+    my_lo = off[k < n ? k : n];
+    c.lo[lane] = my_lo;
+    c.sz[lane] = k < n ? bytes_of(size[k]) : 0u;
+    c.src[lane] = k < n ? dst_off[k] : 0ull;
+    if (lane == 63) c.lo[64] = off[k + 1 < n ? k + 1 : n];
+    wave_lds_sync();
+}
+
+template <typename T>
+__device__ __forceinline__ T table_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+__global__ __launch_bounds__(256) void pack_gather_kernel(uint32_t n, const uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
+                                                          const uint64_t* __restrict__ off, const uint32_t* __restrict__ size,
+                                                          uint8_t* __restrict__ packed, uint64_t packed_cap, uint64_t units)
+{
+    __shared__ WaveCache caches[GATHER_WAVES];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    WaveCache& c = caches[w];
+    const uint64_t total = off[n];
+    if (total > packed_cap) return;   // the whole arena or nothing
+    // chunk boundaries are 16-byte aligned ADDRESSES: position p of the arena is packed + p, units start at -a0
+    const int64_t a0 = (int64_t)((uintptr_t)packed & 15);
+    const uint64_t stride = (uint64_t)gridDim.x * GATHER_WAVES;
+    for (uint64_t g = (uint64_t)blockIdx.x * GATHER_WAVES + w; g < units; g += stride) {
+        const int64_t P = (int64_t)(g * UNIT) - a0;
+        if (P >= (int64_t)total) break;
+        uint32_t j = wave_find(off, n, (uint64_t)(P > 0 ? P : 0));
+        uint64_t my_lo;
+        wave_fill(c, j, n, off, size, dst, dst_off, my_lo);
+
+        uint32_t v[ROWS][5];
+        uint32_t mode[ROWS];   // 0: nothing to store, 1: shifted copy, 2: ready in v[r][0..3]
+        uint32_t shift[ROWS];
+#pragma unroll
+        for (uint32_t r = 0; r < ROWS; ++r) {
+            mode[r] = 0;
+            shift[r] = 0;
+            const int64_t rs = P + (int64_t)r * 1024;
+            if (rs >= (int64_t)total) continue;   // (wave-uniform)
+            // the row runs past the cached reads: move the cache up to the read that holds the row's first byte
+            if ((uint64_t)(rs + 1024) > c.lo[64] && c.lo[64] < total) {
+                const uint64_t m = __ballot(my_lo <= (uint64_t)(rs > 0 ? rs : 0));
+                const uint32_t l = 63 - __builtin_clzll(m);
+                if (l > 0) {
+                    j += l;
+                    wave_fill(c, j, n, off, size, dst, dst_off, my_lo);
+                }
+            }
+            const int64_t p = rs + (int64_t)lane * 16;
+            if (p >= (int64_t)total) continue;
+            const uint64_t x0 = p > 0 ? (uint64_t)p : 0;
+            // the read that holds the chunk's first byte
+            uint32_t k;
+            if (x0 < c.lo[64]) {
+                uint32_t a = 0;
+#pragma unroll
+                for (uint32_t s = 32; s > 0; s >>= 1)
+                    if (c.lo[a + s] <= x0) a += s;
+                k = j + a;
+            } else {
+                k = lane_find(off, j + 63 < n ? j + 63 : n - 1, n, x0);
+            }
+            // (reads past the cache come from the tables themselves; a relaxed atomic load there keeps hipcc from merging the two loads
+            // into one flat load from a selected address)
+            auto lo_of = [&](uint32_t q) -> uint64_t { return q - j <= 64 ? c.lo[q - j] : table_load(off + (q < n ? q : n)); };
+            auto sz_of = [&](uint32_t q) -> uint32_t { return q - j < 64 ? c.sz[q - j] : bytes_of(table_load(size + q)); };
+            auto src_of = [&](uint32_t q) -> uint64_t { return q - j < 64 ? c.src[q - j] : table_load(dst_off + q); };
+            const uint64_t lo = lo_of(k), end = lo + sz_of(k);
+            const bool whole = p >= 0 && (uint64_t)p + 16 <= total;
+            if (whole && (uint64_t)p >= end && (uint64_t)p + 16 <= lo_of(k + 1)) {   // padding
+                mode[r] = 2;
+                v[r][0] = v[r][1] = v[r][2] = v[r][3] = 0;
+                continue;
+            }
+            if (whole && (uint64_t)p + 16 <= end) {
+                const uint64_t s0 = src_of(k), s = s0 + ((uint64_t)p - lo), sa = s & ~3ull;
+                const uint32_t sh = (uint32_t)(s & 3);
+                if (sa >= s0 && sa + (sh ? 20 : 16) <= s0 + (end - lo)) {   // aligned dwords inside the read's bytes
+                    const u32x4_a4 q = *reinterpret_cast<const u32x4_a4*>(dst + sa);
+                    v[r][0] = q.x;
+                    v[r][1] = q.y;
+                    v[r][2] = q.z;
+                    v[r][3] = q.w;
+                    v[r][4] = sh ? *reinterpret_cast<const uint32_t*>(dst + sa + 16) : 0u;
+                    shift[r] = sh * 8;
+                    mode[r] = 1;
+                    continue;
+                }
+            }
+            // byte by byte: read edges, several reads in one chunk, the arena's own ends
+            uint32_t d[4] = { 0, 0, 0, 0 };
+            uint32_t q = k;
+            uint64_t qlo = lo, qend = end, qhi = lo_of(k + 1), qsrc = src_of(k);
+#pragma unroll
+            for (uint32_t b = 0; b < 16; ++b) {
+                const int64_t x = p + (int64_t)b;
+                if (x < 0 || (uint64_t)x >= total) continue;
+                while ((uint64_t)x >= qhi) {
+                    ++q;
+                    qlo = qhi;
+                    qend = qlo + sz_of(q);
+                    qhi = lo_of(q + 1);
+                    qsrc = src_of(q);
+                }
+                if ((uint64_t)x < qend) d[b >> 2] |= (uint32_t)dst[qsrc + ((uint64_t)x - qlo)] << (8 * (b & 3));
+            }
+            v[r][0] = d[0];
+            v[r][1] = d[1];
+            v[r][2] = d[2];
+            v[r][3] = d[3];
+            mode[r] = 2;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < ROWS; ++r) {
+            if (!mode[r]) continue;
+            const int64_t p = P + (int64_t)r * 1024 + (int64_t)lane * 16;
+            uint4 o;
+            if (mode[r] == 1) {
+                const uint32_t sh = shift[r];
+                o.x = __builtin_amdgcn_alignbit(v[r][1], v[r][0], sh);
+                o.y = __builtin_amdgcn_alignbit(v[r][2], v[r][1], sh);
+                o.z = __builtin_amdgcn_alignbit(v[r][3], v[r][2], sh);
+                o.w = __builtin_amdgcn_alignbit(v[r][4], v[r][3], sh);
+            } else {
+                o = make_uint4(v[r][0], v[r][1], v[r][2], v[r][3]);
+            }
+            if (p >= 0 && (uint64_t)p + 16 <= total) {
+                *reinterpret_cast<uint4*>(packed + p) = o;
+            } else {
+                const uint32_t ow[4] = { o.x, o.y, o.z, o.w };
+#pragma unroll
+                for (uint32_t b = 0; b < 16; ++b) {
+                    const int64_t x = p + (int64_t)b;
+                    if (x >= 0 && (uint64_t)x < total) packed[x] = (uint8_t)(ow[b >> 2] >> (8 * (b & 3)));
+                }
+            }
+        }
+    }
+}
+
+hipError_t scan_launches(uint32_t n, uint32_t align, const uint32_t* size, uint64_t* off, hipStream_t s)
+{
+    hipLaunchKernelGGL(pack_scan_tiles_kernel, dim3(1), dim3(1024), 0, s, n, off);
+    hipLaunchKernelGGL(pack_scan_reads_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, n, align, size, off);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_pack_layout(uint32_t n, const uint32_t* result, const uint64_t* dst_off, const uint32_t* dst_cap, uint64_t dst_bytes, uint32_t align,
+                              uint64_t* packed_off, uint32_t* packed_size, hipStream_t s)
+{
+    if (n == 0) return hipMemsetAsync(packed_off, 0, 8, s);
+    hipLaunchKernelGGL(pack_sizes_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, n, result, dst_off, dst_cap, dst_bytes, align, packed_off,
+                       packed_size);
+    return scan_launches(n, align, packed_size, packed_off, s);
+}
+
+hipError_t launch_sized_layout(uint32_t n, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_size, uint64_t src_bytes, uint32_t align,
+                               uint32_t* raw_size, uint64_t* raw_off, hipStream_t s)
+{
+    if (n == 0) return hipMemsetAsync(raw_off, 0, 8, s);
+    hipLaunchKernelGGL(sized_sizes_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, n, src, src_off, src_size, src_bytes, align, raw_off, raw_size);
+    return scan_launches(n, align, raw_size, raw_off, s);
+}
+
+hipError_t launch_pack_gather(uint32_t n, const uint8_t* dst, const uint64_t* dst_off, const uint64_t* packed_off, const uint32_t* packed_size,
+                              uint8_t* packed, uint64_t packed_cap, hipStream_t s)
+{
+    if (n == 0 || packed_cap == 0) return hipSuccess;
+    const uint64_t units = (packed_cap + 15 + UNIT - 1) / UNIT;   // (+15: the unit in front of an unaligned arena's first line)
+    const uint64_t wgs = (units + GATHER_WAVES - 1) / GATHER_WAVES;
+    hipLaunchKernelGGL(pack_gather_kernel, dim3((uint32_t)(wgs < GATHER_MAX_WGS ? wgs : GATHER_MAX_WGS)), dim3(64 * GATHER_WAVES), 0, s, n, dst, dst_off,
+                       packed_off, packed_size, packed, packed_cap, units);
+    return hipGetLastError();
+}
+
+}  // namespace vbzhip

@@ -1395,6 +1395,72 @@ int vbz_gpu_xxh64_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, uint64_t* out)
     return 0;
 }
 
+// Dense arenas (pack.hip).  Arguments are checked here, before anything is launched; each call looks only at the side of the batch
+// it reads (plausible_extents' rules for those fields).
+static bool pack_align_ok(vbz_gpu_ctx* c, uint32_t align)
+{
+    if (align >= 1 && align <= 4096 && (align & (align - 1)) == 0) return true;
+    set_error(c, "align %u is not a power of two in 1 ... 4096", align);
+    return false;
+}
+
+int vbz_gpu_pack_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, uint32_t align, void* packed, uint64_t packed_cap, uint64_t* packed_off,
+                       uint32_t* packed_size)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!pack_align_ok(c, align)) return -2;
+    const uint32_t n = bt->n_reads;
+    if (!packed_off || (n != 0 && (!bt->dst_off || !bt->dst_cap || !bt->result || !packed_size || (!bt->dst && bt->dst_bytes != 0)))) {
+        set_error(c, "a table or arena pointer of the pack call is NULL");
+        return -2;
+    }
+    if (bt->dst_bytes > EXTENT_MAX || (packed && packed_cap > EXTENT_MAX)) {
+        set_error(c, "declared arena extents are not plausible (dst_bytes %llu, packed_cap %llu)", (unsigned long long)bt->dst_bytes,
+                  (unsigned long long)packed_cap);
+        return -2;
+    }
+    const uintptr_t d0 = (uintptr_t)bt->dst, p0 = (uintptr_t)packed;
+    if (packed && packed_cap && bt->dst_bytes && p0 < d0 + bt->dst_bytes && d0 < p0 + packed_cap) {
+        set_error(c, "the packed arena overlaps the dst arena");
+        return -2;
+    }
+    {
+        Timed t(c, "pack_layout");
+        HIPCHK(c, launch_pack_layout(n, bt->result, bt->dst_off, bt->dst_cap, bt->dst_bytes, align, packed_off, packed_size, c->stream), "pack layout launch");
+    }
+    if (!packed) return 0;
+    Timed t(c, "pack_gather");
+    HIPCHK(c, launch_pack_gather(n, (const uint8_t*)bt->dst, bt->dst_off, packed_off, packed_size, (uint8_t*)packed, packed_cap, c->stream),
+           "pack gather launch");
+    return 0;
+}
+
+int vbz_gpu_decompressed_size_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t align, uint32_t* raw_size,
+                                    uint64_t* raw_off)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!o || !valid_int_size(o)) {
+        set_error(c, "unsupported options");
+        return -2;
+    }
+    if (!pack_align_ok(c, align)) return -2;
+    const uint32_t n = bt->n_reads;
+    if (!raw_off || (n != 0 && (!bt->src_off || !bt->src_size || !raw_size || (!bt->src && bt->src_bytes != 0)))) {
+        set_error(c, "a table or arena pointer of the size query is NULL");
+        return -2;
+    }
+    if (bt->src_bytes > EXTENT_MAX) {
+        set_error(c, "declared arena extent is not plausible (src_bytes %llu)", (unsigned long long)bt->src_bytes);
+        return -2;
+    }
+    Timed t(c, "sized_layout");
+    HIPCHK(c, launch_sized_layout(n, (const uint8_t*)bt->src, bt->src_off, bt->src_size, bt->src_bytes, align, raw_size, raw_off, c->stream),
+           "sized layout launch");
+    return 0;
+}
+
 int vbz_gpu_synth_lengths(vbz_gpu_ctx* c, uint64_t seed, uint64_t first, uint32_t n, uint32_t* out_len)
 {
     if (!c) return -1;

@@ -249,6 +249,21 @@ hipError_t launch_xxh64_verify(const ReadBatch& b, hipStream_t s);
 // raw_size (nullable) + integer_size: the raw read sizes whose vbz_max_compressed_size the result must not exceed.
 hipError_t launch_checksum_insert(const ReadBatch& b, const uint64_t* hash, uint32_t hdr, const uint32_t* raw_size, uint32_t integer_size, hipStream_t s);
 
+// ---- dense arenas (pack.hip) ----------------------------------------------------------------------
+// Layout of a batch's byte counts, each rounded up to `align` (a power of two): size[i] = the count or an error code (error entries
+// occupy no bytes), off[i] = the exclusive scan, off[n] = the total.  Three launches (tile sums, their scan, the tiles' scans).
+//   pack:  the count is result[i] when that is no error code, fits dst_cap[i] and the slot lies inside [0, dst_bytes); a count that
+//          does not fit gets E_INPUT_SIZE, an error code stays as it is (vbz_gpu_pack_batch)
+//   sized: the little-endian u32 header of every buffer, E_INPUT_SIZE for a buffer under 4 bytes or outside [0, src_bytes)
+hipError_t launch_pack_layout(uint32_t n, const uint32_t* result, const uint64_t* dst_off, const uint32_t* dst_cap, uint64_t dst_bytes, uint32_t align,
+                              uint64_t* packed_off, uint32_t* packed_size, hipStream_t s);
+hipError_t launch_sized_layout(uint32_t n, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_size, uint64_t src_bytes, uint32_t align,
+                               uint32_t* raw_size, uint64_t* raw_off, hipStream_t s);
+// After launch_pack_layout: every read's packed_size[i] bytes (if no error code) from dst + dst_off[i] to packed + packed_off[i], the
+// padding between them zero; nothing at all when packed_off[n] > packed_cap.  packed must not overlap the slots.
+hipError_t launch_pack_gather(uint32_t n, const uint8_t* dst, const uint64_t* dst_off, const uint64_t* packed_off, const uint32_t* packed_size,
+                              uint8_t* packed, uint64_t packed_cap, hipStream_t s);
+
 // ---- helpers (helpers.hip) ---------------------------------------------------------------------
 // scratch slots for the intermediate svb streams: slot(i) = align16(ceil(raw_size[i]*num/den)+8)+48,
 // off[i] = exclusive scan + 16, cap[i] = slot - 32; gate[i] = E_OOM if the slot exceeds `limit` bytes.
