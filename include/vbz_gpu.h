@@ -135,6 +135,38 @@ VBZ_EXPORT int vbz_gpu_compress_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* bat
 VBZ_EXPORT int vbz_gpu_decompress_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch,
                                         const struct CompressionOptions* options, int sized);
 
+/* Calibrated signal.  vbz_gpu_decompress_signal_batch decodes int16 signal (options->integer_size must be 2; any zig-zag setting, version 0
+ * or 1, any level, sized or not) straight into float32, float16 or bfloat16: sample x of read i becomes
+ *     y = ((float)x + offset[i]) * scale[i]
+ * in float32 arithmetic, each operation rounded to nearest even, the add before the multiply, no fused multiply-add; for F16 / BF16 the
+ * float32 y is rounded once (to nearest even) to the output type.  Float32 output is therefore bit for bit numpy's
+ * (x.astype(np.float32) + np.float32(o)) * np.float32(s).  Overflow gives +-inf; a NaN among the constants gives NaN (its bits unspecified).
+ * fast5: offset = the channel's offset, scale = range / digitisation; POD5: offset and scale as stored.
+ * The src side of the batch is as for vbz_gpu_decompress_batch.  The dst side describes the TYPED arena, E = 4 (F32) or 2 bytes per
+ * sample: unsized, dst_cap[i] = samples * E exactly; sized, dst_cap[i] is the capacity and the header gives the sample count.
+ * result[i] = samples * E, or the error code vbz_gpu_decompress_batch gives for the same source with the int16 capacity dst_cap[i] / E * 2;
+ * a slot whose dst_off[i] or dst_cap[i] is not a multiple of E gets VBZ_DESTINATION_SIZE_ERROR and is never written.  Nothing outside the
+ * slots is written; what a slot holds after an error is unspecified.  Returns 0 when queued, -1 for a NULL context or batch or a launch
+ * failure, -2 (nothing launched) for options other than those above, a NULL format, an unknown out_type, is_signed not 0 / 1, a NULL table
+ * of the batch or a declared extent beyond 2^46 bytes.
+ * The conversion is the svb decode stage's store (there is no second pass over the samples): every decode path of the int16 call
+ * (split batches, routed long reads, the large-read path, level 0, frames libzstd wrote) carries it.  Slots 16-byte aligned take the
+ * wide stores; E-aligned slots that are not decode correctly on a slower path.  Measured on one MI355X, 65 536 reads of ~100 k samples
+ * (tools/time_signal.py, profiles/HISTORY.md "Calibrated signal"): int16 call 11.2 ms; float16 11.4 ms, bfloat16 11.3 ms, float32
+ * 14.2 ms; the int16 call followed by torch's (x.float() + o) * s 46.5 ms. */
+#define VBZ_GPU_SIGNAL_F32 1
+#define VBZ_GPU_SIGNAL_F16 2
+#define VBZ_GPU_SIGNAL_BF16 3
+typedef struct vbz_gpu_signal_format
+{
+    uint32_t out_type;   /* VBZ_GPU_SIGNAL_* */
+    uint32_t is_signed;  /* 1: the 16-bit samples are int16, 0: uint16 (the format does not say which) */
+    const float* offset; /* device, n_reads floats; NULL: 0 for every read */
+    const float* scale;  /* device, n_reads floats; NULL: 1 for every read */
+} vbz_gpu_signal_format;
+VBZ_EXPORT int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                               int sized, const vbz_gpu_signal_format* format);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -53,6 +53,22 @@ class GpuBatch(ctypes.Structure):
     ]
 
 
+VBZ_GPU_SIGNAL_F32 = 1
+VBZ_GPU_SIGNAL_F16 = 2
+VBZ_GPU_SIGNAL_BF16 = 3
+
+
+class GpuSignalFormat(ctypes.Structure):
+    """struct vbz_gpu_signal_format of include/vbz_gpu.h."""
+
+    _fields_ = [
+        ("out_type", ctypes.c_uint32),
+        ("is_signed", ctypes.c_uint32),
+        ("offset", ctypes.c_void_p),
+        ("scale", ctypes.c_void_p),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -74,6 +90,7 @@ GPU_API = [
     "vbz_gpu_synchronize",
     "vbz_gpu_compress_batch",
     "vbz_gpu_decompress_batch",
+    "vbz_gpu_decompress_signal_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -152,6 +169,9 @@ def load():
         f = getattr(L, name)
         f.restype = ctypes.c_int
         f.argtypes = [vp, bp, op, ctypes.c_int]
+    if hasattr(L, "vbz_gpu_decompress_signal_batch"):   # (likewise: builds of earlier rounds decode to int16 only)
+        L.vbz_gpu_decompress_signal_batch.restype = ctypes.c_int
+        L.vbz_gpu_decompress_signal_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.POINTER(GpuSignalFormat)]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

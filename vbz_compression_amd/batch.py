@@ -113,6 +113,31 @@ class GpuCodec:
         finally:
             self._exit(cur)
 
+    _SIGNAL_TYPES = {torch.float32: _lib.VBZ_GPU_SIGNAL_F32, torch.float16: _lib.VBZ_GPU_SIGNAL_F16, torch.bfloat16: _lib.VBZ_GPU_SIGNAL_BF16}
+
+    def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False):
+        """Decode int16 signal straight to calibrated samples, y = (x + offset[i]) * scale[i] in float32 arithmetic (include/vbz_gpu.h:
+        vbz_gpu_decompress_signal_batch).  dst: a 1-D float32, float16 or bfloat16 tensor (its dtype is the output type); dst_off / dst_cap
+        in bytes of dst, as everywhere in this class (unsized: dst_cap[i] = samples * element size); result[i] = samples * element size or
+        an error code.  scale / offset: float32 tensors of n entries on the codec's device, or None (1 / 0 for every read).  signed: the
+        16-bit samples are int16 (True) or uint16."""
+        assert dst.dtype in self._SIGNAL_TYPES and dst.dim() == 1 and dst.is_contiguous(), (dst.dtype, dst.shape)
+        n = int(src_off.numel())
+        f = _lib.GpuSignalFormat()
+        f.out_type = self._SIGNAL_TYPES[dst.dtype]
+        f.is_signed = int(bool(signed))
+        for name, t in (("offset", offset), ("scale", scale)):
+            if t is not None:
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) >= n, (name, t.dtype, t.device)
+                setattr(f, name, t.data_ptr())
+        b = self._batch(src, src_off, src_size, dst.view(torch.uint8), dst_off, dst_cap, result)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_decompress_signal_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f)),
+                     "decompress_signal_batch")
+        finally:
+            self._exit(cur)
+
     # -- stages ----------------------------------------------------------------------------------
     def svb_compress(self, src, src_off, src_size, dst, dst_off, dst_cap, result, size=2, zigzag=True, version=0):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
@@ -243,6 +268,33 @@ class GpuCodec:
         result = torch.empty(n, dtype=torch.int32, device=self.device)
         self.decompress(packed, src_off, packed_size, raw, raw_off[:n], dst_cap, result, opts, sized=True)
         return raw, raw_off, raw_size, result
+
+    def decompress_packed_signal(self, packed, packed_off, packed_size, opts, dtype=torch.float32, scale=None, offset=None, signed=True):
+        """decompress_packed into calibrated samples (decompress_signal): the sample counts come from the headers, the output (`dtype`)
+        is laid out with 16-byte aligned slots and allocated (one synchronisation), and the batch decoded -> (out, out_off, samples,
+        result): read i is out[out_off[i] : out_off[i] + samples[i]] (out_off int64 and samples int32, in elements) when result[i] is no
+        error code."""
+        assert dtype in self._SIGNAL_TYPES, dtype
+        n = int(packed_size.numel())
+        src_off = packed_off[:n]
+        raw_size, raw_off = self.decompressed_sizes(packed, src_off, packed_size, opts, 16)   # (int16 bytes, 16-byte aligned)
+        cur = self._enter()
+        try:
+            total16 = self._sync_total(raw_off)
+        finally:
+            self._exit(cur)
+        elem = torch.empty(0, dtype=dtype).element_size()
+        # an int16 slot of b bytes holds b / 2 samples: its typed slot, b / 2 * elem bytes, keeps the 16-byte alignment
+        out = torch.empty(total16 // 2, dtype=dtype, device=self.device)
+        err = (raw_size < 0) & (raw_size >= _lib.VBZ_DEVICE_ERROR - (1 << 32))
+        raw = torch.where(err, torch.zeros_like(raw_size), raw_size)
+        # (capacity: the header's samples, rounded up -- an odd header gets the verdict the int16 decode gives it)
+        dst_cap = ((raw + 1) // 2 * elem).to(torch.int32)
+        out_off = raw_off[:n] // 2
+        result = torch.empty(n, dtype=torch.int32, device=self.device)
+        self.decompress_signal(packed, src_off, packed_size, out, out_off * elem, dst_cap, result, opts, scale=scale, offset=offset, signed=signed,
+                               sized=True)
+        return out, out_off, (raw // 2).to(torch.int32), result
 
     # -- synthetic workload (SURVEY.md 8d) ----------------------------------------------------------
     def synth_lengths(self, seed, first_read, n_reads):

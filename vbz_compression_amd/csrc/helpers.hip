@@ -173,7 +173,8 @@ __global__ __launch_bounds__(256) void route_flag_kernel(ReadBatch b, const uint
 
 __global__ __launch_bounds__(1024) void route_pick_kernel(ReadBatch b, const uint32_t* raw_size, uint32_t max_reads, uint64_t max_bytes, uint32_t* gate_small,
                                                           const uint32_t* cand, const uint32_t* cand_count, uint64_t* l_src_off, uint32_t* l_src_size,
-                                                          uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map, uint32_t* l_count)
+                                                          uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map, float2* l_cal,
+                                                          uint32_t* l_count)
 {
     __shared__ uint32_t key[ROUTE_CAND_MAX];
     const uint32_t tid = threadIdx.x;
@@ -220,6 +221,7 @@ __global__ __launch_bounds__(1024) void route_pick_kernel(ReadBatch b, const uin
                 l_dst_cap[taken] = b.dst_cap[i];
                 l_gate[taken] = g;
                 l_map[taken] = i;
+                if (b.sig.cal) l_cal[taken] = b.sig.cal[i];
                 ++taken;
             } else {
                 gate_small[i] = g;   // not routed after all
@@ -275,6 +277,20 @@ __global__ void validate_batch_kernel(uint32_t n, const uint64_t* src_off, const
     if (so > src_bytes || (uint64_t)src_size[i] > src_bytes - so) g = E_INPUT_SIZE;
     else if (d0 > dst_bytes || (uint64_t)dst_cap[i] > dst_bytes - d0) g = E_DESTINATION_SIZE;
     gate[i] = g;
+}
+
+// typed decode: see launch_signal_slots (vbz_kernels.h)
+__global__ void signal_slots_kernel(uint32_t n, const uint64_t* dst_off, const uint32_t* dst_cap, uint32_t elem, const float* offset, const float* scale,
+                                    uint64_t* off16, uint32_t* cap16, float2* cal, uint32_t* gate)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t o = dst_off[i];
+    const uint32_t c = dst_cap[i];
+    off16[i] = o / elem * 2u;
+    cap16[i] = c / elem * 2u;
+    cal[i] = make_float2(offset ? offset[i] : 0.0f, scale ? scale[i] : 1.0f);
+    if (o % elem != 0 || c % elem != 0) gate[i] = E_DESTINATION_SIZE;
 }
 
 __global__ void parse_sized_kernel(uint32_t n, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_size,
@@ -431,7 +447,7 @@ hipError_t launch_seg_plan(uint32_t n, const uint32_t* size, uint32_t unit_bytes
 
 hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint32_t min_bytes, uint32_t max_reads, uint64_t max_bytes, uint32_t* gate_small,
                               uint64_t* l_src_off, uint32_t* l_src_size, uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map,
-                              uint32_t* l_count, uint32_t* cand, hipStream_t s)
+                              float2* l_cal, uint32_t* l_count, uint32_t* cand, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
     uint32_t* cand_count = cand + ROUTE_CAND_MAX;
@@ -439,7 +455,7 @@ hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(route_flag_kernel, dim3((b.n_reads + 255) / 256), dim3(256), 0, s, b, raw_size, min_bytes, gate_small, cand, cand_count);
     hipLaunchKernelGGL(route_pick_kernel, dim3(1), dim3(1024), 0, s, b, raw_size, max_reads, max_bytes, gate_small, cand, cand_count, l_src_off, l_src_size,
-                       l_dst_off, l_dst_cap, l_gate, l_map, l_count);
+                       l_dst_off, l_dst_cap, l_gate, l_map, l_cal, l_count);
     return hipGetLastError();
 }
 
@@ -490,6 +506,14 @@ hipError_t launch_validate_batch(uint32_t n, const uint64_t* src_off, const uint
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(validate_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, src_off, src_size, src_bytes, dst_off, dst_cap, dst_bytes, gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_signal_slots(uint32_t n, const uint64_t* dst_off, const uint32_t* dst_cap, uint32_t elem, const float* offset, const float* scale,
+                               uint64_t* off16, uint32_t* cap16, float2* cal, uint32_t* gate, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(signal_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, dst_off, dst_cap, elem, offset, scale, off16, cap16, cal, gate);
     return hipGetLastError();
 }
 

@@ -52,6 +52,86 @@ __device__ __forceinline__ void store_elem(uint8_t* p, int elem, uint32_t v)
     } else __builtin_memcpy(p, &v, 4);
 }
 
+// ---- typed store (SignalOut): a decoded int16 sample -> ((float)x + offset) * scale, rounded once (RNE) to the output type ----------
+// OUT = SIG_* (0: the int16 store itself).  The read's constants are workgroup-uniform (one scalar load per workgroup).
+template <int OUT>
+struct OutBytes
+{
+    static constexpr int value = OUT == SIG_F32 ? 4 : 2;
+};
+struct SigK
+{
+    float o = 0.0f, s = 1.0f;
+    uint32_t bias = 0;   // 0: the low 16 bits are an int16; 0x8000: a uint16
+};
+
+__device__ __forceinline__ SigK sig_constants(const ReadBatch& b, uint32_t r)
+{
+    const float2 c = b.sig.cal[r];
+    SigK k;
+    k.o = c.x;
+    k.s = c.y;
+    k.bias = b.sig.bias;
+    return k;
+}
+
+__device__ __forceinline__ float sig_f32(uint32_t v, const SigK& k)
+{
+#pragma clang fp contract(off)
+    // (sign-extend v ^ bias, add the bias back: the int16 or the uint16 value of the low 16 bits; exact in float)
+    const int32_t x = ((int32_t)((v ^ k.bias) << 16) >> 16) + (int32_t)k.bias;
+    return ((float)x + k.o) * k.s;   // add, then multiply, each rounded (no FMA)
+}
+
+template <int OUT>
+__device__ __forceinline__ uint32_t sig_pack2(float a, float b)
+{
+    if (OUT == SIG_F16) {
+        // (the float32 values are pinned in registers: hipcc folds a multiply and the conversion behind it into v_fma_mixlo_f16, one
+        // rounding straight to float16, whatever the contraction setting -- y must be rounded to float32 first)
+        asm("" : "+v"(a), "+v"(b));   // v_cvt_f16_f32: round to nearest even (not v_cvt_pkrtz_f16_f32)
+        const _Float16 ha = (_Float16)a, hb = (_Float16)b;
+        uint16_t ua, ub;
+        __builtin_memcpy(&ua, &ha, 2);
+        __builtin_memcpy(&ub, &hb, 2);
+        return (uint32_t)ua | ((uint32_t)ub << 16);
+    } else {                // v_cvt_pk_bf16_f32: round to nearest even
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        const bf16x2 h = __builtin_convertvector((f32x2){ a, b }, bf16x2);
+        uint32_t u;
+        __builtin_memcpy(&u, &h, 4);
+        return u;
+    }
+}
+
+// eight consecutive samples base + s[0 .. 7] to p (16-byte aligned): two dwordx4 stores of float32, one of float16 / bfloat16
+template <int OUT>
+__device__ __forceinline__ void sig_store8(uint8_t* p, uint32_t base, const uint32_t s[8], const SigK& k)
+{
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = sig_f32(base + s[j], k);
+    if (OUT == SIG_F32) {
+        *reinterpret_cast<uint4*>(p) = make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
+        *reinterpret_cast<uint4*>(p + 16) = make_uint4(__float_as_uint(f[4]), __float_as_uint(f[5]), __float_as_uint(f[6]), __float_as_uint(f[7]));
+    } else {
+        *reinterpret_cast<uint4*>(p) = make_uint4(sig_pack2<OUT>(f[0], f[1]), sig_pack2<OUT>(f[2], f[3]), sig_pack2<OUT>(f[4], f[5]), sig_pack2<OUT>(f[6], f[7]));
+    }
+}
+
+template <int OUT>
+__device__ __forceinline__ void sig_store1(uint8_t* p, uint32_t v, const SigK& k)
+{
+    const float f = sig_f32(v, k);
+    if (OUT == SIG_F32) {
+        __builtin_memcpy(p, &f, 4);
+    } else {
+        const uint16_t h = (uint16_t)sig_pack2<OUT>(f, f);
+        __builtin_memcpy(p, &h, 2);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // encode
 // ------------------------------------------------------------------------------------------------
@@ -841,6 +921,7 @@ struct I16DecPairs
     uint8_t* out;             // 16-byte aligned
     uint8_t* stage;           // two buffers of BUF bytes
     uint32_t* ws;             // WS_WORDS words, 16-byte aligned
+    SigK sk;                  // run<OUT != 0>: the read's constants
 
     static __device__ __forceinline__ uint32_t announced(uint32_t k) { return 8u + (uint32_t)__popc(k & 0x5555u) + 2u * (uint32_t)__popc(k & 0xAAAAu); }
 
@@ -862,7 +943,8 @@ struct I16DecPairs
     }
 
     // pairs from t0 on while two whole tiles are left; pos / run as in svb_decode_range.  Returns the first value not decoded (a multiple of
-    // the tile size from t0).  All 256 threads; ends with a barrier.
+    // the tile size from t0).  All 256 threads; ends with a barrier.  OUT: the store (SIG_*; out then points to the typed slot).
+    template <int OUT>
     __device__ __forceinline__ uint32_t run(uint32_t t0_in, uint32_t end_in, uint64_t& pos_io, uint32_t& run_io)
     {
         const int tid = threadIdx.x, lane = tid & 63;
@@ -934,6 +1016,12 @@ struct I16DecPairs
                 const uint32_t totA = a4.x + a4.y + a4.z + a4.w, totB = b4.x + b4.y + b4.z + b4.w;
                 const uint32_t baseA = rn + (a4.x & m0) + (a4.y & m1) + (a4.z & m2) + incA - accA;
                 const uint32_t baseB = rn + totA + (b4.x & m0) + (b4.y & m1) + (b4.z & m2) + incB - accB;
+                if (OUT != SIG_NONE) {
+                    constexpr uint32_t OB = OutBytes<OUT>::value;
+                    uint8_t* op = out + ((size_t)tc + (size_t)tid * 8) * OB;
+                    sig_store8<OUT>(op, baseA, sA, sk);
+                    sig_store8<OUT>(op + TILE * OB, baseB, sB, sk);
+                } else {
                 uint32_t w[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) w[k] = ((baseA + sA[2 * k]) & 0xFFFFu) | ((baseA + sA[2 * k + 1]) << 16);
@@ -942,6 +1030,7 @@ struct I16DecPairs
 #pragma unroll
                 for (int k = 0; k < 4; ++k) w[k] = ((baseB + sB[2 * k]) & 0xFFFFu) | ((baseB + sB[2 * k + 1]) << 16);
                 *reinterpret_cast<uint4*>(op + TILE * 2) = make_uint4(w[0], w[1], w[2], w[3]);
+                }
                 rn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(rn + totA + totB));
             }
             have = more;
@@ -978,10 +1067,13 @@ struct I16DecPairs
 //         chain stands at `run`; store them.  MODE 1: only add up the data bytes the control bytes announce.
 //         MODE 2: decode without storing (the total of the deltas is wanted).  pos / run are updated; returns false when
 //         the stream is shorter than its control bytes claim.  All 256 threads.
-template <int ELEM, bool ZZ, bool I16ZZ, int MODE>
+// OUT (ELEM 2, MODE 0): the typed store (SIG_*): out points to the read's typed slot, sk holds its constants.
+template <int ELEM, bool ZZ, bool I16ZZ, int MODE, int OUT = SIG_NONE>
 __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_t* data, uint32_t dataBytes, uint32_t count, uint32_t first,
-                                                 uint32_t end, uint64_t& pos_io, uint32_t& run_io, uint8_t* out, uint8_t* stage, uint32_t* wsum)
+                                                 uint32_t end, uint64_t& pos_io, uint32_t& run_io, uint8_t* out, uint8_t* stage, uint32_t* wsum,
+                                                 const SigK& sk = SigK())
 {
+    static_assert(OUT == SIG_NONE || (ELEM == 2 && MODE == 0), "the typed store is for int16 samples");
     constexpr int VPL = Vpl<ELEM>::value;
     constexpr int TILE = WG * VPL;
     const int tid = threadIdx.x;
@@ -992,8 +1084,8 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
     bool good = true;
     uint32_t t_start = first;
     if (I16ZZ && MODE == 0 && out_aligned && end - first >= 2u * (uint32_t)TILE) {   // pairs of whole tiles: I16DecPairs
-        I16DecPairs dp = { in, data, dataBytes, out, stage, wsum };
-        t_start = dp.run(first, end, pos, run);
+        I16DecPairs dp = { in, data, dataBytes, out, stage, wsum, sk };
+        t_start = dp.run<OUT>(first, end, pos, run);
     }
     for (uint32_t t0 = t_start; t0 < end; t0 += TILE) {
         const uint32_t i0 = t0 + (uint32_t)tid * VPL;
@@ -1078,7 +1170,16 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
             pos += tot;
             continue;
         }
-        if (valid == VPL && out_aligned) {
+        if (OUT != SIG_NONE) {
+            constexpr uint32_t OB = OutBytes<OUT>::value;
+            if (valid == VPL && out_aligned) {
+                sig_store8<OUT>(out + (size_t)i0 * OB, base, s, sk);
+            } else {
+#pragma unroll
+                for (int k = 0; k < VPL; ++k)
+                    if (k < valid) sig_store1<OUT>(out + (size_t)(i0 + k) * OB, base + s[k], sk);
+            }
+        } else if (valid == VPL && out_aligned) {
             uint32_t w[4];
             if (ELEM == 4) {
 #pragma unroll
@@ -1114,7 +1215,7 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
 #ifndef VBZ_SVBDEC_WAVES
 #define VBZ_SVBDEC_WAVES 1
 #endif
-template <int ELEM, bool ZZ, bool I16ZZ>
+template <int ELEM, bool ZZ, bool I16ZZ, int OUT = SIG_NONE>
 __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBatch b)
 {
     constexpr int STAGE = I16ZZ ? 2 * (int)I16DecPairs::BUF : WG * Vpl<ELEM>::value * 4 + 48;   // (int16 zig-zag: the two buffers of I16DecPairs; the tile loop's 8240 bytes fit)
@@ -1145,7 +1246,15 @@ __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBa
     const uint32_t dataBytes = in_size - keyLen;
     uint64_t pos = 0;
     uint32_t run = 0;
-    const bool good = svb_decode_range<ELEM, ZZ, I16ZZ, 0>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst + b.dst_off[r], stage, wsum);
+    bool good;
+    if (OUT != SIG_NONE) {
+        constexpr uint32_t OB = OutBytes<OUT>::value;
+        good = svb_decode_range<ELEM, ZZ, I16ZZ, 0, OUT>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst + (b.dst_off[r] >> 1) * OB, stage,
+                                                         wsum, sig_constants(b, r));
+        if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * OB;
+        return;
+    }
+    good = svb_decode_range<ELEM, ZZ, I16ZZ, 0>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst + b.dst_off[r], stage, wsum);
     if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * ELEM;
 }
 
@@ -1156,7 +1265,8 @@ __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBa
 // SELF (see svb_seg_encode_kernel): no scan launches -- MODE 2 / 0 workgroups add up the announced lengths (seg_val, left by MODE 1)
 // in front of them and over the whole read (the verdict: good iff the total equals the bytes present), MODE 2 leaves its delta
 // totals in seg_run_io and MODE 0 adds those up too; a read's first MODE 0 workgroup writes the read's result.
-template <int ELEM, bool ZZ, bool I16ZZ, int MODE, bool SELF = false>
+// OUT (MODE 0): the typed store.  Segments start at multiples of SEG samples: their typed offsets stay 16-byte aligned.
+template <int ELEM, bool ZZ, bool I16ZZ, int MODE, bool SELF = false, int OUT = SIG_NONE>
 __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const uint32_t* seg_first, uint32_t* seg_val, const uint64_t* seg_pos,
                                                             uint32_t* seg_run_io)
 {
@@ -1184,7 +1294,7 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
             else if (!svb_decode_check<ELEM, I16ZZ>(b.src_size[r], b.dst_cap[r], res0)) {
                 const uint32_t count0 = b.dst_cap[r] / ELEM;
                 const uint32_t dataBytes0 = b.src_size[r] - ((count0 + 3u) >> 2);
-                res0 = self_total == dataBytes0 ? count0 * ELEM : E_STREAM;
+                res0 = self_total == dataBytes0 ? count0 * (OUT != SIG_NONE ? (uint32_t)OutBytes<OUT>::value : (uint32_t)ELEM) : E_STREAM;
             }
             b.result[r] = res0;
         }
@@ -1208,14 +1318,19 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
     uint64_t pos = MODE == 1 ? 0 : (SELF ? self_pos : seg_pos[blockIdx.x]);
     uint32_t run = (MODE == 0 && ZZ) ? (SELF ? (uint32_t)self_run : seg_run[blockIdx.x]) : 0u;
     const uint64_t pos0 = pos;
+    if (OUT != SIG_NONE) {
+        (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE, OUT>(in, in + keyLen, dataBytes, count, first, end, pos, run,
+                                                           b.dst + (b.dst_off[r] >> 1) * OutBytes<OUT>::value, stage, wsum, sig_constants(b, r));
+        return;
+    }
     (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE>(in, in + keyLen, dataBytes, count, first, end, pos, run, b.dst + b.dst_off[r], stage, wsum);
     if (MODE == 1 && tid == 0) seg_val[blockIdx.x] = (uint32_t)(pos - pos0);
     if (MODE == 2 && tid == 0) (SELF ? seg_run_io : seg_val)[blockIdx.x] = run;
 }
 
 // one workgroup per read.  VERDICT: exclusive scan of the announced data bytes -> seg_pos, and the read's result;
-// otherwise: exclusive scan (mod 2^32) of the delta totals -> seg_run.
-template <int ELEM, bool I16ZZ, bool VERDICT>
+// otherwise: exclusive scan (mod 2^32) of the delta totals -> seg_run.  RES: bytes per value in the result (the typed store's).
+template <int ELEM, bool I16ZZ, bool VERDICT, int RES = ELEM>
 __global__ __launch_bounds__(WG) void svb_seg_decode_scan_kernel(ReadBatch b, const uint32_t* seg_first, const uint32_t* seg_val, uint64_t* seg_pos,
                                                                  uint32_t* seg_run)
 {
@@ -1242,7 +1357,7 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_scan_kernel(ReadBatch b, co
         else if (!svb_decode_check<ELEM, I16ZZ>(b.src_size[r], b.dst_cap[r], res)) {
             const uint32_t count = b.dst_cap[r] / ELEM;
             const uint32_t dataBytes = b.src_size[r] - ((count + 3u) >> 2);
-            res = carry == dataBytes ? count * ELEM : E_STREAM;
+            res = carry == dataBytes ? count * RES : E_STREAM;
         }
         b.result[r] = res;
     }
@@ -1513,8 +1628,22 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
     return hipGetLastError();
 }
 
+// b.sig.type: the typed store (int16 samples only), the output type a template argument of its own instantiation
+template <bool Z, bool I>
+hipError_t launch_svb_decode_typed(const ReadBatch& b, hipStream_t s)
+{
+    if (b.sig.type == SIG_F32) return launch1(svb_decode_kernel<2, Z, I, SIG_F32>, b, s);
+    if (b.sig.type == SIG_F16) return launch1(svb_decode_kernel<2, Z, I, SIG_F16>, b, s);
+    if (b.sig.type == SIG_BF16) return launch1(svb_decode_kernel<2, Z, I, SIG_BF16>, b, s);
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s)
 {
+    if (b.sig.type != SIG_NONE) {
+        if (integer_size != 2 || half) return hipErrorInvalidValue;
+        return zigzag ? launch_svb_decode_typed<true, true>(b, s) : launch_svb_decode_typed<false, false>(b, s);
+    }
     if (half) {
         if (integer_size != 1) return hipErrorInvalidValue;
         return zigzag ? launch1(svb_half_decode_kernel<true>, b, s) : launch1(svb_half_decode_kernel<false>, b, s);
@@ -1564,10 +1693,46 @@ hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigz
     return hipGetLastError();
 }
 
+// the launches of launch_svb_decode_seg with the typed store OUT (the passes that do not store are the int16 decode's own)
+template <bool Z, bool I, int OUT>
+hipError_t svb_decode_seg_typed(const ReadBatch& b, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val, uint64_t* seg_pos,
+                                uint32_t* seg_run, hipStream_t s)
+{
+    constexpr int OB = OutBytes<OUT>::value;
+    hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 1>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    if (max_segs <= seg_self_max()) {
+        if (Z) hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 2, true>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 0, true, OUT>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    } else {
+        hipLaunchKernelGGL((svb_seg_decode_scan_kernel<2, I, true, OB>), dim3(b.n_reads), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        if (Z) {
+            hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 2>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+            hipLaunchKernelGGL((svb_seg_decode_scan_kernel<2, I, false>), dim3(b.n_reads), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        }
+        hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 0, false, OUT>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
                                  uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
+    if (b.sig.type != SIG_NONE) {
+        if (integer_size != 2) return hipErrorInvalidValue;
+#define X(Z, I, O) return svb_decode_seg_typed<Z, I, O>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
+        if (zigzag) {
+            if (b.sig.type == SIG_F32) X(true, true, SIG_F32);
+            if (b.sig.type == SIG_F16) X(true, true, SIG_F16);
+            if (b.sig.type == SIG_BF16) X(true, true, SIG_BF16);
+        } else {
+            if (b.sig.type == SIG_F32) X(false, false, SIG_F32);
+            if (b.sig.type == SIG_F16) X(false, false, SIG_F16);
+            if (b.sig.type == SIG_BF16) X(false, false, SIG_BF16);
+        }
+#undef X
+        return hipErrorInvalidValue;
+    }
     const bool self = max_segs <= seg_self_max();
 #define X(E, Z, I)                                                                                                                          \
     hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 1>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);             \

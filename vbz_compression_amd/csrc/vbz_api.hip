@@ -105,6 +105,7 @@ struct vbz_gpu_ctx
     bool trailers = true;      // decoder hints (checkpoints, span index) in skippable frames behind the zstd frame
     bool checksum = false;     // vbz_gpu_set_checksum / VBZ_HIP_CHECKSUM=1: frames written with the content checksum (xxh64.hip)
     DevBuf cksum;              // the hashes of a compress launch group (8 bytes per read)
+    DevBuf sigmeta;            // typed decode: the int16 slot table and the per-read constants (signal_slots)
     int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
     bool zero_run_sequences = true;
     bool fuse_svb = false;     // VBZ_HIP_FUSE_SVB=1: the frame's wavefront decodes the svb stream too (measured slower: DESIGN.md 4.4)
@@ -754,7 +755,7 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     // svb stream it has just written while it is still in the caches, straight into the destination, and there is no
     // svb_decode launch (measured slower than the separate launch: profiles/r03_fused_svb_decode.md; it does not verify content checksums)
 #ifdef VBZ_EXPERIMENTS
-    if (!segmented && !dbg && c->fuse_svb && o->integer_size == 2 && o->perform_delta_zig_zag) {
+    if (!segmented && !dbg && c->fuse_svb && o->integer_size == 2 && o->perform_delta_zig_zag && rb.sig.type == SIG_NONE) {   // (no typed store)
         z.result = rb.result;
         Timed t(c, "zstd_decode");  // (zstd_decode_kernel<false, true>: the frame and its svb stream)
         HIPCHK(c, launch_zstd_decode_svb_i16zz(z, E_STREAM, c->seqdtab.p, rb.dst, rb.dst_off, rb.dst_cap, s), "zstd_decode + svb_decode launch");
@@ -858,7 +859,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
 {
     const uint32_t n = rb.n_reads;
     if (ensure_large(c) != 0) return -1;
-    if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * 48 + route_cand_words() * 4 + 512)) return -1;
+    if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * 56 + route_cand_words() * 4 + 512)) return -1;
     MetaCarver mc(c->route.p);
     r->gate_small = mc.take<uint32_t>(n);
     uint64_t* l_src_off = mc.take<uint64_t>(ROUTE_MAX_READS);
@@ -868,6 +869,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     uint32_t* l_gate = mc.take<uint32_t>(ROUTE_MAX_READS);
     uint32_t* l_result = mc.take<uint32_t>(ROUTE_MAX_READS);
     r->map = mc.take<uint32_t>(ROUTE_MAX_READS);
+    float2* l_cal = mc.take<float2>(ROUTE_MAX_READS);
     r->count = mc.take<uint32_t>(4);
     uint32_t* cand = mc.take<uint32_t>(route_cand_words());
     r->large = rb;
@@ -878,9 +880,10 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     r->large.dst_cap = l_dst_cap;
     r->large.gate = l_gate;
     r->large.result = l_result;
+    if (rb.sig.cal) r->large.sig.cal = l_cal;   // (the routed reads' constants, gathered through the map)
     Timed t(c, "route");
     HIPCHK(c, launch_route_reads(rb, raw_size, ROUTE_MIN_BYTES, ROUTE_MAX_READS, ROUTE_MAX_BYTES, r->gate_small, l_src_off, l_src_size, l_dst_off, l_dst_cap,
-                                 l_gate, r->map, r->count, cand, c->stream),
+                                 l_gate, r->map, l_cal, r->count, cand, c->stream),
            "route launch");
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream), "event record");
     HIPCHK(c, hipStreamWaitEvent(c->large->stream, c->ev_fork, 0), "stream wait");
@@ -980,6 +983,7 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
     u.dst_cap += h;
     u.result += h;
     if (u.gate) u.gate += h;
+    if (u.sig.cal) u.sig.cal += h;
     return u;
 }
 
@@ -1126,7 +1130,36 @@ int compress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressi
     return rc;
 }
 
-int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, bool own_descriptors = false)
+// Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
+// through the int16 slot table made from it here -- offsets and capacities / E * 2, the extent likewise -- so that the descriptor checks,
+// the sized headers, the scratch plan, routing and the split see exactly what an int16 call with those capacities sees; the svb stage
+// alone stores the typed samples (rb.sig).  A slot whose offset or capacity is not a multiple of E gets VBZ_DESTINATION_SIZE_ERROR.
+// The typed slots lie inside [0, dst_bytes) iff the int16 ones lie inside [0, dst_bytes / E * 2): validate_descriptors looked at the former.
+static_assert(SIG_F32 == VBZ_GPU_SIGNAL_F32 && SIG_F16 == VBZ_GPU_SIGNAL_F16 && SIG_BF16 == VBZ_GPU_SIGNAL_BF16, "the ABI's output types");
+int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_format* f, ReadBatch* rb, uint64_t* dst_bytes)
+{
+    const uint32_t n = bt->n_reads, elem = f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u;
+    if (!ensure(c, c->sigmeta, (size_t)n * 20 + 256)) return -1;
+    MetaCarver mc(c->sigmeta.p);
+    uint64_t* off16 = mc.take<uint64_t>(n);
+    uint32_t* cap16 = mc.take<uint32_t>(n);
+    float2* cal = mc.take<float2>(n);
+    Timed t(c, "signal_slots");
+    HIPCHK(c, launch_signal_slots(n, bt->dst_off, bt->dst_cap, elem, f->offset, f->scale, off16, cap16, cal, reinterpret_cast<uint32_t*>(c->vgate.p),
+                                  c->stream),
+           "signal slots launch");
+    rb->dst_off = off16;
+    rb->dst_cap = cap16;
+    rb->sig.cal = cal;
+    rb->sig.type = f->out_type;
+    rb->sig.bias = f->is_signed ? 0u : 0x8000u;
+    *dst_bytes = bt->dst_bytes / elem * 2u;
+    return 0;
+}
+
+// sig (nullable): a typed decode (signal_slots)
+int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, bool own_descriptors = false,
+                          const vbz_gpu_signal_format* sig = nullptr)
 {
     const uint32_t n = bt->n_reads;
     c->last_frames = 0;
@@ -1135,6 +1168,8 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     hipStream_t s = c->stream;
     ReadBatch rb = to_rb(bt);
     if (!own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
+    uint64_t dst_bytes = bt->dst_bytes;
+    if (sig && signal_slots(c, bt, sig, &rb, &dst_bytes) != 0) return -1;
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
         if (!ensure(c, c->meta, (size_t)n * 24 + 512)) return -1;
         MetaCarver mc(c->meta.p);
@@ -1143,14 +1178,14 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         uint32_t* orig_size = mc.take<uint32_t>(n);
         uint32_t* gate = mc.take<uint32_t>(n);
         Timed t(c, "parse_sized");
-        HIPCHK(c, launch_parse_sized(n, rb.src, bt->src_off, bt->src_size, bt->dst_cap, rb.gate, pay_off, pay_size, orig_size, gate, s),
+        HIPCHK(c, launch_parse_sized(n, rb.src, bt->src_off, bt->src_size, rb.dst_cap, rb.gate, pay_off, pay_size, orig_size, gate, s),
                "parse_sized launch");
         rb.src_off = pay_off;
         rb.src_size = pay_size;
         rb.dst_cap = orig_size;
         rb.gate = gate;
     }
-    const bool by_shape = o->integer_size != 0 && !half_codec(o) && use_segments(c, bt->dst_bytes, n, true);
+    const bool by_shape = o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
     if (c->foreign_pending && hipEventQuery(c->ev_foreign) == hipSuccess) {   // what the call before this one found (see foreign_host)
         c->mostly_foreign = 2ull * c->foreign_host[0] > c->foreign_host[1];
         c->foreign_state = c->foreign_host[0] != 0 ? 1 : 0;
@@ -1160,15 +1195,15 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     }
     const bool split = !by_shape && split_applies(c, o, n) && !c->mostly_foreign;
     c->last_split = false;
-    if (by_shape || !routing_applies(c, o, bt->dst_bytes, n))
-        return split ? decompress_split(c, rb, bt->dst_bytes, o) : decompress_group(c, rb, bt->dst_bytes, o, by_shape);
+    if (by_shape || !routing_applies(c, o, dst_bytes, n))
+        return split ? decompress_split(c, rb, dst_bytes, o) : decompress_group(c, rb, dst_bytes, o, by_shape);
     Routed r;
     if (route(c, rb, rb.dst_cap, &r) != 0) return -1;   // by the decoded size
     ReadBatch small = rb;
     small.gate = r.gate_small;
     int rc = 0;   // (as in compress_batch_impl: the second stream is joined whatever happens)
     if (c->routing != 2 && decompress_group(c->large, r.large, ROUTE_MAX_BYTES, o, true) != 0) rc = -1;
-    if (rc == 0 && (split ? decompress_split(c, small, bt->dst_bytes, o) : decompress_group(c, small, bt->dst_bytes, o, false)) != 0) rc = -1;
+    if (rc == 0 && (split ? decompress_split(c, small, dst_bytes, o) : decompress_group(c, small, dst_bytes, o, false)) != 0) rc = -1;
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
     if (route_join(c, r, bt->result) != 0) rc = -1;
     return rc;
@@ -1281,7 +1316,7 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
         (void)hipEventDestroy(p.stop);
     }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum })
+    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta })
         if (b->p) (void)hipFree(b->p);
     if (c->large) vbz_gpu_destroy(c->large);
     if (c->half) vbz_gpu_destroy(c->half);
@@ -1345,6 +1380,22 @@ int vbz_gpu_decompress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Comp
     }
     if (!plausible_extents(c, bt)) return -2;
     return decompress_batch_impl(c, bt, o, sized);
+}
+
+int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!o || o->integer_size != 2 || o->vbz_version > 1) {
+        set_error(c, "unsupported options for a signal decode (integer_size must be 2, version 0 or 1)");
+        return -2;
+    }
+    if (!f || f->out_type < VBZ_GPU_SIGNAL_F32 || f->out_type > VBZ_GPU_SIGNAL_BF16 || f->is_signed > 1) {
+        set_error(c, "signal format: NULL, unknown out_type or is_signed not 0 / 1");
+        return -2;
+    }
+    if (!plausible_extents(c, bt)) return -2;
+    return decompress_batch_impl(c, bt, o, sized, false, f);
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

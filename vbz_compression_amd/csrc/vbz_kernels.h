@@ -20,6 +20,18 @@ constexpr uint32_t E_FIRST = E_DEVICE;
 constexpr uint32_t GATE_SKIP = E_FIRST - 1u;   // gate value "not in this launch group"; gate >= GATE_SKIP: no work here
 constexpr int PHASE_SLOTS = 12;  // per-read cycle counters of the timed kernel builds (debug aid)
 
+// Typed decode (vbz_gpu_decompress_signal_batch): the svb decoder of int16 streams stores sample x of read i as
+// ((float)x + cal[i].x) * cal[i].y in the output type (SIG_*: the VBZ_GPU_SIGNAL_* values), x being int16 (bias 0) or uint16
+// (bias 0x8000).  dst_off / dst_cap of the batch then count int16 bytes: the read's typed slot starts at dst + dst_off[i] / 2 * E
+// (E = 4 or 2 bytes per sample) and result[i] is samples * E.  type == SIG_NONE: the int16 samples themselves.
+constexpr uint32_t SIG_NONE = 0, SIG_F32 = 1, SIG_F16 = 2, SIG_BF16 = 3;
+struct SignalOut
+{
+    const float2* cal = nullptr;   // per read {offset, scale}, in the batch's read order
+    uint32_t type = SIG_NONE;
+    uint32_t bias = 0;
+};
+
 // One batch of independent reads ("reads" in the reference's vocabulary: one HDF5 chunk each).
 // All pointers are device pointers.  `result[i]` receives the bytes produced or an error code.
 // If `gate` is non-null, reads whose gate[i] is an error code are skipped and the error is kept; reads whose gate[i] is
@@ -35,6 +47,7 @@ struct ReadBatch
     const uint32_t* dst_cap;
     uint32_t* result;
     const uint32_t* gate;
+    SignalOut sig;   // decode only: what the svb stage stores (every other stage ignores it)
 };
 
 // ---- the per-read plans of the staged encoder (zstd_encode.hip), and what the svb encoder leaves in them ---------------------------
@@ -84,6 +97,7 @@ inline EncPlan* zstd_encode_plans(void* plan_meta) { return reinterpret_cast<Enc
 hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, uint32_t hdr, bool strict_cap, bool half, uint32_t* period_hint,
                              void* plans, hipStream_t s);
 bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half);   // does launch_svb_encode(plans) write every read's hist_mode?
+// Decode: b.sig.type != SIG_NONE (integer_size 2 only; launch_svb_decode_seg too) stores the typed samples of SignalOut.
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
@@ -291,9 +305,10 @@ hipError_t launch_count_nonzero(const uint32_t* a, uint32_t n, uint32_t* out, hi
 hipError_t launch_canon_classify(uint32_t n, const uint32_t* raw_size, const uint32_t* gate, uint32_t min_bytes, uint32_t* gate_small, uint32_t* gate_large,
                                  uint32_t* counts, hipStream_t s);
 // per-read routing: see route_reads_kernel (helpers.hip).  raw_size[i] = the read's raw (decoded) byte count.
+// l_cal: the routed reads' b.sig.cal entries (not written when b.sig.cal is NULL).
 hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint32_t min_bytes, uint32_t max_reads, uint64_t max_bytes, uint32_t* gate_small,
                               uint64_t* l_src_off, uint32_t* l_src_size, uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map,
-                              uint32_t* l_count, uint32_t* cand, hipStream_t s);   // cand: route_cand_words() words of scratch
+                              float2* l_cal, uint32_t* l_count, uint32_t* cand, hipStream_t s);   // cand: route_cand_words() words of scratch
 size_t route_cand_words();
 hipError_t launch_route_results(const uint32_t* l_result, const uint32_t* l_map, const uint32_t* l_count, uint32_t max_reads, uint32_t* result, hipStream_t s);
 // sized decode: read the 4-byte headers -> payload offsets/sizes, original sizes, gate errors (gate_in, nullable: reads that
@@ -309,6 +324,11 @@ hipError_t launch_parse_sized(uint32_t n, const uint8_t* src, const uint64_t* sr
 hipError_t launch_hand_back(const uint32_t* result, const uint8_t* src, uint32_t* host, uint32_t host_cap, uint32_t seq, uint32_t* ticket, hipStream_t s);
 hipError_t launch_validate_batch(uint32_t n, const uint64_t* src_off, const uint32_t* src_size, uint64_t src_bytes, const uint64_t* dst_off,
                                  const uint32_t* dst_cap, uint64_t dst_bytes, uint32_t* gate, hipStream_t s);
+// typed decode (SignalOut): the caller's typed slot table -> the int16 one every decode launch plans with, off16[i] = dst_off[i] / elem * 2
+// and cap16[i] = dst_cap[i] / elem * 2; cal[i] = {offset ? offset[i] : 0, scale ? scale[i] : 1}.  A slot whose offset or capacity is not a
+// multiple of elem gets gate[i] = E_DESTINATION_SIZE (gate: launch_validate_batch's verdicts on the typed table, updated in place).
+hipError_t launch_signal_slots(uint32_t n, const uint64_t* dst_off, const uint32_t* dst_cap, uint32_t elem, const float* offset, const float* scale,
+                               uint64_t* off16, uint32_t* cap16, float2* cal, uint32_t* gate, hipStream_t s);
 // integer_size == 0 && level == 0: per-read copy (reference vbz/vbz.cpp:130-133)
 hipError_t launch_copy_bytes(const ReadBatch& b, uint32_t hdr, hipStream_t s);
 hipError_t launch_synth_lengths(uint64_t seed, uint64_t first, uint32_t n, uint32_t* out_len, hipStream_t s);
