@@ -167,6 +167,50 @@ typedef struct vbz_gpu_signal_format
 VBZ_EXPORT int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
                                                int sized, const vbz_gpu_signal_format* format);
 
+/* Model-input chunks.  A model takes a dense [chunks, L] tensor of fixed-length windows, not ragged reads.  The chunking of a read of T
+ * samples (L = chunk_len, S = step):
+ *   T == 0: no chunk.  0 < T <= L: one chunk, starting at 0.  T > L: K = k* + 1 chunks, k* = ceil((T - L) / S); chunk k < k* starts at
+ *   k * S, the last one at k* * S (PAD) or at min(k* * S, e), e = ceil((T - L) / end_align) * end_align (END: pulled back to end at most
+ *   end_align - 1 samples past the read's end).  Position p of a chunk starting at s holds sample s + p when s + p < T, else `pad`.
+ * Starts increase strictly.  L and S are multiples of 8, 8 <= S <= L <= 2^20; end_align is 1 ... 4096 for END and 0 for PAD; `pad` is
+ * rounded (to nearest even) to the output type; reserved must be 0.
+ * vbz_gpu_chunk_layout_batch: chunk_first[i] = the exclusive scan of the reads' chunk counts (chunk_first[n] = the total; samples[i] of
+ * 2^31 or more -- an error code of vbz_gpu_decompressed_size_batch -- counts 0).  chunk_info (nullable; written only when the total is at
+ * most info_cap, otherwise untouched): chunk_info[2c] = the read of row c, chunk_info[2c + 1] = its start sample.  A first call with NULL
+ * sizes the table (one synchronisation).  Returns 0 when queued, -1 for a NULL context or a launch failure, -2 (nothing launched) for a
+ * chunking outside the rules, a NULL chunk_first, or a NULL samples when n > 0.
+ * vbz_gpu_decompress_chunks_batch: decodes int16 signal as vbz_gpu_decompress_signal_batch does (the same options and format) and stores
+ * chunk k of read i as row chunk_first[i] + k of `chunks`, a row-major [chunk_rows, L] arena of the output type, 16-byte aligned.  The
+ * dst side of the batch (dst_off, dst_cap, dst_bytes) is the int16 layout vbz_gpu_decompress_batch would take for the same reads
+ * (unsized: dst_cap[i] = 2 * T; sized: the capacity); batch->dst is neither read nor written and may be NULL.  Per read, in this order:
+ * the descriptor checks; sized, the header verdicts; then the chunk check -- chunk_first is untrusted: chunk_first[i + 1] - chunk_first[i]
+ * != K(T), chunk_first[i] > chunk_first[i + 1] or chunk_first[i + 1] > chunk_rows gives VBZ_DESTINATION_SIZE_ERROR and not one byte of
+ * chunks is written for the read; otherwise the signal call's verdict.  result[i] = T * E (E = 4 or 2 bytes per sample) on success, when
+ * every position of the read's K rows has been written.  Rows of a read that fails after the chunk check hold unspecified contents; rows
+ * chunk_first[n] ... chunk_rows - 1 are never written.  Returns 0 when queued, -1 for a NULL context or batch or a launch failure, -2
+ * (nothing launched) for everything the signal call refuses, a chunking outside the rules, a NULL chunk_first or chunks when n > 0, a
+ * chunks arena not 16-byte aligned, or chunk_rows * L * E beyond 2^46 bytes.
+ * The placement is the svb decode stage's store (no per-read intermediate, no second pass): each sample is converted once and stored in
+ * every chunk that holds it, as whole 16-byte stores, the END chunk's unaligned start included; the padding is written in the same launch.
+ * Measured on one MI355X, 65 536 reads of ~100 k samples, L = 10 000, S = 9 504, float16 (tools/time_chunks.py, profiles/HISTORY.md
+ * "Model-input chunks"): signal call 10.9 ms; chunks PAD 11.6 ms, END 11.9 ms; the signal call followed by a torch gather 30.5 ms. */
+#define VBZ_GPU_CHUNK_PAD 0 /* chunk k starts at k * step; the last one is padded past the read's end */
+#define VBZ_GPU_CHUNK_END 1 /* the last chunk is pulled back to end at the read's end */
+typedef struct vbz_gpu_chunking
+{
+    uint32_t chunk_len; /* L: samples per chunk, a multiple of 8, 8 <= L <= 2^20 */
+    uint32_t step;      /* S: samples between consecutive chunk starts, a multiple of 8, 8 <= S <= L (overlap L - S) */
+    uint32_t mode;      /* VBZ_GPU_CHUNK_PAD or VBZ_GPU_CHUNK_END */
+    uint32_t end_align; /* END only: the last chunk's start is rounded UP to a multiple of this, 1 ... 4096 (PAD: must be 0) */
+    float pad;          /* the value of positions past the read's end, rounded (RNE) to the output type */
+    uint32_t reserved;  /* must be 0 */
+} vbz_gpu_chunking;     /* 24 bytes */
+VBZ_EXPORT int vbz_gpu_chunk_layout_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const uint32_t* samples, const vbz_gpu_chunking* chunking,
+                                          uint64_t* chunk_first, uint32_t* chunk_info, uint64_t info_cap);
+VBZ_EXPORT int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                               const vbz_gpu_signal_format* format, const vbz_gpu_chunking* chunking,
+                                               const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

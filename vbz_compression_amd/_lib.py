@@ -69,6 +69,23 @@ class GpuSignalFormat(ctypes.Structure):
     ]
 
 
+VBZ_GPU_CHUNK_PAD = 0
+VBZ_GPU_CHUNK_END = 1
+
+
+class GpuChunking(ctypes.Structure):
+    """struct vbz_gpu_chunking of include/vbz_gpu.h (24 bytes)."""
+
+    _fields_ = [
+        ("chunk_len", ctypes.c_uint32),
+        ("step", ctypes.c_uint32),
+        ("mode", ctypes.c_uint32),
+        ("end_align", ctypes.c_uint32),
+        ("pad", ctypes.c_float),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -91,6 +108,8 @@ GPU_API = [
     "vbz_gpu_compress_batch",
     "vbz_gpu_decompress_batch",
     "vbz_gpu_decompress_signal_batch",
+    "vbz_gpu_chunk_layout_batch",
+    "vbz_gpu_decompress_chunks_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -172,6 +191,12 @@ def load():
     if hasattr(L, "vbz_gpu_decompress_signal_batch"):   # (likewise: builds of earlier rounds decode to int16 only)
         L.vbz_gpu_decompress_signal_batch.restype = ctypes.c_int
         L.vbz_gpu_decompress_signal_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.POINTER(GpuSignalFormat)]
+    if hasattr(L, "vbz_gpu_decompress_chunks_batch"):   # (likewise: builds of earlier rounds have no chunk decode)
+        cp = ctypes.POINTER(GpuChunking)
+        L.vbz_gpu_chunk_layout_batch.restype = ctypes.c_int
+        L.vbz_gpu_chunk_layout_batch.argtypes = [vp, u32, vp, cp, vp, vp, u64]
+        L.vbz_gpu_decompress_chunks_batch.restype = ctypes.c_int
+        L.vbz_gpu_decompress_chunks_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.POINTER(GpuSignalFormat), cp, vp, vp, u64]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -296,6 +296,107 @@ class GpuCodec:
                                sized=True)
         return out, out_off, (raw // 2).to(torch.int32), result
 
+    # -- model-input chunks ------------------------------------------------------------------------
+    _CHUNK_MODES = {"pad": _lib.VBZ_GPU_CHUNK_PAD, "end": _lib.VBZ_GPU_CHUNK_END}
+
+    def _chunking(self, chunk_len, step, mode, end_align, pad=0.0):
+        assert mode in self._CHUNK_MODES, mode
+        ch = _lib.GpuChunking()
+        ch.chunk_len, ch.step, ch.mode = int(chunk_len), int(step), self._CHUNK_MODES[mode]
+        ch.end_align = int(end_align) if mode == "end" else 0
+        ch.pad = float(pad)
+        return ch
+
+    def _chunk_layout_call(self, samples, ch, chunk_first, info=None, info_cap=0):
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_chunk_layout_batch(self.ctx, int(samples.numel()), samples.data_ptr(), ctypes.byref(ch), chunk_first.data_ptr(),
+                                                       info.data_ptr() if info is not None else None, int(info_cap)), "chunk_layout_batch")
+        finally:
+            self._exit(cur)
+
+    def _chunk_tables(self, samples, ch, info, also=None):
+        """chunk_first (and chunk_info) of `samples` (int32 on the device, uint32 bits) under ch, with ONE synchronisation for the total;
+        also: an int64 device scalar wanted on the host in the same synchronisation -> (chunk_first, chunk_info or None, also's value)"""
+        assert samples.dtype == torch.int32 and samples.is_contiguous() and samples.device == self.device, (samples.dtype, samples.device)
+        n = int(samples.numel())
+        chunk_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        self._chunk_layout_call(samples, ch, chunk_first)
+        self._rc(self.L.vbz_gpu_synchronize(self.ctx), "synchronize")
+        host = torch.stack([chunk_first[-1], also if also is not None else chunk_first[-1]]).cpu().tolist()
+        chunk_info = None
+        if info:
+            chunk_info = torch.empty((host[0], 2), dtype=torch.int32, device=self.device)
+            self._chunk_layout_call(samples, ch, chunk_first, chunk_info, host[0])
+        return chunk_first, chunk_info, host
+
+    def chunk_layout(self, samples, chunk_len, step, mode="pad", end_align=1, info=True):
+        """The chunk layout of reads of `samples` samples (int32 on the device; 2^31 or more as uint32 -- an error code of
+        decompressed_sizes -- counts 0 chunks) (include/vbz_gpu.h: vbz_gpu_chunk_layout_batch) -> (chunk_first int64 [n + 1],
+        chunk_info int32 [total, 2] = (read, start sample) per row, or None).  One synchronisation for the total."""
+        chunk_first, chunk_info, _ = self._chunk_tables(samples, self._chunking(chunk_len, step, mode, end_align), info)
+        return chunk_first, chunk_info
+
+    def _decode_chunks(self, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, ch, chunk_first, chunks, dtype, scale, offset,
+                       signed):
+        assert dtype in self._SIGNAL_TYPES and chunks.dtype == dtype and chunks.is_contiguous(), (dtype, chunks.dtype)
+        n = int(src_off.numel())
+        f = _lib.GpuSignalFormat()
+        f.out_type = self._SIGNAL_TYPES[dtype]
+        f.is_signed = int(bool(signed))
+        for name, t in (("offset", offset), ("scale", scale)):
+            if t is not None:
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) >= n, (name, t.dtype, t.device)
+                setattr(f, name, t.data_ptr())
+        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
+        b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
+        b.dst = None     # (the int16 layout only describes the reads: nothing is stored there)
+        b.dst_bytes = int(dst_bytes)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f), ctypes.byref(ch),
+                                                            chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0])),
+                     "decompress_chunks_batch")
+        finally:
+            self._exit(cur)
+
+    def decompress_chunks(self, src, src_off, src_size, samples, result, opts, chunk_len, step, mode="pad", end_align=1, pad=0.0, dtype=torch.float16,
+                          scale=None, offset=None, signed=True):
+        """Decode unsized int16 reads of `samples` samples (int32 on the device) straight into model-input chunks (include/vbz_gpu.h:
+        vbz_gpu_decompress_chunks_batch), calibrated as decompress_signal does -> (chunks [total, chunk_len] of dtype, chunk_first int64
+        [n + 1], chunk_info int32 [total, 2]): chunk k of read i is chunks[chunk_first[i] + k] when result[i] is no error code (result[i] =
+        samples * element size).  The int16 layout the call describes the reads with is built here; one synchronisation."""
+        n = int(src_off.numel())
+        assert int(samples.numel()) == n
+        ch = self._chunking(chunk_len, step, mode, end_align, pad)
+        dst_cap = (samples.to(torch.int64) * 2).to(torch.int32)
+        dst_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        if n:
+            dst_off[1:] = torch.cumsum(samples.to(torch.int64) * 2, 0)
+        chunk_first, chunk_info, host = self._chunk_tables(samples, ch, True, also=dst_off[-1])
+        chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
+        self._decode_chunks(src, src_off, src_size, dst_off[:n], dst_cap, host[1], result, opts, False, ch, chunk_first, chunks, dtype, scale, offset,
+                            signed)
+        return chunks, chunk_first, chunk_info
+
+    def decompress_packed_chunks(self, packed, packed_off, packed_size, opts, chunk_len, step, mode="pad", end_align=1, pad=0.0, dtype=torch.float16,
+                                 scale=None, offset=None, signed=True):
+        """decompress_packed into model-input chunks (decompress_chunks): the sample counts come from the headers (decompressed_sizes),
+        then the layout and the decode -> (chunks, chunk_first, chunk_info, result).  One synchronisation."""
+        n = int(packed_size.numel())
+        src_off = packed_off[:n]
+        ch = self._chunking(chunk_len, step, mode, end_align, pad)
+        raw_size, raw_off = self.decompressed_sizes(packed, src_off, packed_size, opts, 16)   # (int16 bytes, 16-byte aligned)
+        err = (raw_size < 0) & (raw_size >= _lib.VBZ_DEVICE_ERROR - (1 << 32))
+        raw = torch.where(err, torch.zeros_like(raw_size), raw_size)
+        samples = torch.where(err, raw_size, raw // 2)   # (an error code: no chunks)
+        chunk_first, chunk_info, host = self._chunk_tables(samples, ch, True, also=raw_off[-1])
+        chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
+        result = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._decode_chunks(packed, src_off, packed_size, raw_off[:n], raw, host[1], result, opts, True, ch, chunk_first, chunks, dtype, scale, offset,
+                            signed)
+        return chunks, chunk_first, chunk_info, result
+
     # -- synthetic workload (SURVEY.md 8d) ----------------------------------------------------------
     def synth_lengths(self, seed, first_read, n_reads):
         out = torch.empty(n_reads, dtype=torch.int32, device=self.device)

@@ -267,6 +267,13 @@ __global__ void route_results_kernel(const uint32_t* l_result, const uint32_t* l
 
 // The descriptor table of a batch is untrusted like the data (include/vbz_gpu.h): a read whose source or destination slot does not
 // lie inside the arena the caller declared gets its error here, before any kernel forms an address from it.
+// chunk decode: the routed reads' first chunk rows, gathered through the routing map (route_pick_kernel's l_map / l_count)
+__global__ void route_rows_kernel(const uint64_t* row, const uint32_t* l_map, const uint32_t* l_count, uint32_t max_reads, uint64_t* l_row)
+{
+    const uint32_t j = threadIdx.x;
+    if (j < max_reads && j < l_count[0]) l_row[j] = row[l_map[j]];
+}
+
 __global__ void validate_batch_kernel(uint32_t n, const uint64_t* src_off, const uint32_t* src_size, uint64_t src_bytes,
                                       const uint64_t* dst_off, const uint32_t* dst_cap, uint64_t dst_bytes, uint32_t* gate)
 {
@@ -291,6 +298,18 @@ __global__ void signal_slots_kernel(uint32_t n, const uint64_t* dst_off, const u
     cap16[i] = c / elem * 2u;
     cal[i] = make_float2(offset ? offset[i] : 0.0f, scale ? scale[i] : 1.0f);
     if (o % elem != 0 || c % elem != 0) gate[i] = E_DESTINATION_SIZE;
+}
+
+// chunk decode: see launch_chunk_slots (vbz_kernels.h)
+__global__ void chunk_slots_kernel(uint32_t n, const uint32_t* cap16, const float* offset, const float* scale, uint32_t L, uint32_t S,
+                                   const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    cal[i] = make_float2(offset ? offset[i] : 0.0f, scale ? scale[i] : 1.0f);
+    if (gate[i] >= GATE_SKIP) return;
+    const uint64_t a = chunk_first[i], z = chunk_first[i + 1];
+    if (a > z || z > chunk_rows || z - a != chunk_count(cap16[i] / 2u, L, S)) gate[i] = E_DESTINATION_SIZE;
 }
 
 __global__ void parse_sized_kernel(uint32_t n, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_size,
@@ -447,7 +466,7 @@ hipError_t launch_seg_plan(uint32_t n, const uint32_t* size, uint32_t unit_bytes
 
 hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint32_t min_bytes, uint32_t max_reads, uint64_t max_bytes, uint32_t* gate_small,
                               uint64_t* l_src_off, uint32_t* l_src_size, uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map,
-                              float2* l_cal, uint32_t* l_count, uint32_t* cand, hipStream_t s)
+                              float2* l_cal, uint64_t* l_row, uint32_t* l_count, uint32_t* cand, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
     uint32_t* cand_count = cand + ROUTE_CAND_MAX;
@@ -456,6 +475,7 @@ hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint
     hipLaunchKernelGGL(route_flag_kernel, dim3((b.n_reads + 255) / 256), dim3(256), 0, s, b, raw_size, min_bytes, gate_small, cand, cand_count);
     hipLaunchKernelGGL(route_pick_kernel, dim3(1), dim3(1024), 0, s, b, raw_size, max_reads, max_bytes, gate_small, cand, cand_count, l_src_off, l_src_size,
                        l_dst_off, l_dst_cap, l_gate, l_map, l_cal, l_count);
+    if (b.sig.row) hipLaunchKernelGGL(route_rows_kernel, dim3(1), dim3(64), 0, s, b.sig.row, l_map, l_count, max_reads, l_row);
     return hipGetLastError();
 }
 
@@ -514,6 +534,14 @@ hipError_t launch_signal_slots(uint32_t n, const uint64_t* dst_off, const uint32
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(signal_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, dst_off, dst_cap, elem, offset, scale, off16, cap16, cal, gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_chunk_slots(uint32_t n, const uint32_t* cap16, const float* offset, const float* scale, uint32_t L, uint32_t S,
+                              const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(chunk_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, cap16, offset, scale, L, S, chunk_first, chunk_rows, cal, gate);
     return hipGetLastError();
 }
 

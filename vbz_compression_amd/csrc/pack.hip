@@ -109,6 +109,22 @@ __global__ __launch_bounds__(1024) void sized_sizes_kernel(uint32_t n, const uin
     if (threadIdx.x == 0) off[blockIdx.x * TILE] = t;
 }
 
+// chunk layout (vbz_gpu_chunk_layout_batch): the counts are the reads' chunk counts (align 1 in the launches behind)
+__global__ __launch_bounds__(1024) void chunk_counts_kernel(uint32_t n, const uint32_t* samples, uint32_t L, uint32_t S, uint64_t* off, uint32_t* count)
+{
+    __shared__ uint64_t wsum[16];
+    const uint32_t i = blockIdx.x * TILE + threadIdx.x;
+    uint64_t take = 0;
+    if (i < n) {
+        const uint32_t t = samples[i];
+        const uint32_t k = t >= 0x80000000u ? 0u : chunk_count(t, L, S);   // (an error code of the size query: no chunks)
+        count[i] = k;
+        take = k;
+    }
+    const uint64_t t = block_sum_u64(take, wsum);
+    if (threadIdx.x == 0) off[blockIdx.x * TILE] = t;
+}
+
 // ---- launch 2: the exclusive scan of the tile sums (one workgroup); off[n] = the total
 __global__ __launch_bounds__(1024) void pack_scan_tiles_kernel(uint32_t n, uint64_t* off)
 {
@@ -350,6 +366,36 @@ hipError_t launch_sized_layout(uint32_t n, const uint8_t* src, const uint64_t* s
     if (n == 0) return hipMemsetAsync(raw_off, 0, 8, s);
     hipLaunchKernelGGL(sized_sizes_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, n, src, src_off, src_size, src_bytes, align, raw_off, raw_size);
     return scan_launches(n, align, raw_size, raw_off, s);
+}
+
+// row c of the layout -> its read (the last k with chunk_first[k] <= c: reads without chunks share their successor's offset) and start
+__global__ __launch_bounds__(256) void chunk_info_kernel(uint32_t n, const uint32_t* samples, uint32_t L, uint32_t S, uint32_t mode, uint32_t end_align,
+                                                         const uint64_t* chunk_first, uint32_t* info, uint64_t info_cap)
+{
+    const uint64_t total = chunk_first[n];
+    if (total > info_cap) return;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = lane_find(chunk_first, 0, n, c);
+        const uint32_t T = samples[r];
+        const uint32_t K = chunk_count(T, L, S), k = (uint32_t)(c - chunk_first[r]);
+        info[2 * c] = r;
+        info[2 * c + 1] = k + 1 < K ? k * S : chunk_last_start(T, K, L, S, mode, end_align);
+    }
+}
+
+hipError_t launch_chunk_layout(uint32_t n, const uint32_t* samples, uint32_t L, uint32_t S, uint32_t* count, uint64_t* chunk_first, hipStream_t s)
+{
+    if (n == 0) return hipMemsetAsync(chunk_first, 0, 8, s);
+    hipLaunchKernelGGL(chunk_counts_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, n, samples, L, S, chunk_first, count);
+    return scan_launches(n, 1, count, chunk_first, s);
+}
+
+hipError_t launch_chunk_info(uint32_t n, const uint32_t* samples, uint32_t L, uint32_t S, uint32_t mode, uint32_t end_align, const uint64_t* chunk_first,
+                             uint32_t* info, uint64_t info_cap, hipStream_t s)
+{
+    if (n == 0 || info == nullptr) return hipSuccess;
+    hipLaunchKernelGGL(chunk_info_kernel, dim3(2048), dim3(256), 0, s, n, samples, L, S, mode, end_align, chunk_first, info, info_cap);
+    return hipGetLastError();
 }
 
 hipError_t launch_pack_gather(uint32_t n, const uint8_t* dst, const uint64_t* dst_off, const uint64_t* packed_off, const uint32_t* packed_size,

@@ -57,7 +57,7 @@ __device__ __forceinline__ void store_elem(uint8_t* p, int elem, uint32_t v)
 template <int OUT>
 struct OutBytes
 {
-    static constexpr int value = OUT == SIG_F32 ? 4 : 2;
+    static constexpr int value = (OUT & 3) == SIG_F32 ? 4 : 2;   // (OUT & SIG_CHUNK: the chunk store of the same type)
 };
 struct SigK
 {
@@ -130,6 +130,186 @@ __device__ __forceinline__ void sig_store1(uint8_t* p, uint32_t v, const SigK& k
         const uint16_t h = (uint16_t)sig_pack2<OUT>(f, f);
         __builtin_memcpy(p, &h, 2);
     }
+}
+
+// ---- chunk store (SignalOut::row; OUT = SIG_* | SIG_CHUNK): the typed samples into fixed-length chunks --------------------------------
+// Chunk k of the read is row k of the read's rows (ChunkK::base), row-major, L * E bytes (16-byte aligned: L is a multiple of 8).  The
+// chunks on the grid k * S start at multiples of 8, so a lane's eight samples i0 ... i0 + 7 (i0 a multiple of 8) lie wholly inside or
+// outside each of them and go out as whole 16-byte stores, one per chunk that holds them (at most ceil(L / S) + 1).  The END chunk starts
+// at `last`, d = last % 8 samples past a multiple of 8: its 8-sample line starting at sample i0 + d is put together from the lane's
+// samples d ... 7 and the next lane's 0 ... d - 1 (one shuffle per dword) and stored whole -- except where the next group belongs to
+// another wavefront (lane 63): there the two lanes store their parts element by element (disjoint bytes).  Positions past the read's
+// end take the pad value: in a line that holds samples, the lane storing the line puts it there; the lines that hold none are written
+// by chunk_pad.  No two stores of a launch write the same bytes.
+struct ChunkK
+{
+    uint8_t* base = nullptr;   // the read's first row
+    uint64_t row_bytes = 0;    // L * E
+    uint32_t T = 0, L = 0, S = 0, K = 0, last = 0;   // samples, chunk length, step, chunks, the last chunk's start
+    uint32_t nG = 0;           // chunks on the grid k * S (END with K >= 2: all but the last)
+    uint32_t inv = 0;          // floor(2^32 / S): k = floor(i0 / S) by one multiply-high and a correction
+    uint32_t padw = 0;         // the pad value's bits in the output type
+    bool extra = false;        // END with K >= 2: the last chunk is the pulled-back one at `last`
+};
+
+template <int OUT>
+__device__ __forceinline__ ChunkK chunk_constants(const ReadBatch& b, uint32_t r, uint32_t T)
+{
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    ChunkK c;
+    c.T = T;
+    c.L = b.sig.chunk_len;
+    c.S = b.sig.step;
+    c.K = chunk_count(T, c.L, c.S);
+    c.last = chunk_last_start(T, c.K, c.L, c.S, b.sig.mode, b.sig.end_align);
+    c.extra = b.sig.mode == CHUNK_END && c.K >= 2;
+    c.nG = c.extra ? c.K - 1 : c.K;
+    c.row_bytes = (uint64_t)c.L * OB;
+    c.base = b.dst + b.sig.row[r] * c.row_bytes;
+    c.inv = (uint32_t)(0x100000000ull / c.S);
+    if (OB == 4) c.padw = __float_as_uint(b.sig.pad);
+    else c.padw = sig_pack2<OUT & 3>(b.sig.pad, b.sig.pad) & 0xFFFFu;
+    return c;
+}
+
+// e[0 .. 7]: the output type's bits of eight consecutive positions (16-bit types in the low halves) -> p, 16-byte aligned
+template <int OUT>
+__device__ __forceinline__ void chunk_put8(uint8_t* p, const uint32_t e[8])
+{
+    if (OutBytes<OUT>::value == 4) {
+        *reinterpret_cast<uint4*>(p) = make_uint4(e[0], e[1], e[2], e[3]);
+        *reinterpret_cast<uint4*>(p + 16) = make_uint4(e[4], e[5], e[6], e[7]);
+    } else {
+        *reinterpret_cast<uint4*>(p) = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+    }
+}
+
+template <int OUT>
+__device__ __forceinline__ void chunk_put1(uint8_t* p, uint32_t e)
+{
+    if (OutBytes<OUT>::value == 4) {
+        __builtin_memcpy(p, &e, 4);
+    } else {
+        const uint16_t h = (uint16_t)e;
+        __builtin_memcpy(p, &h, 2);
+    }
+}
+
+template <int D>
+__device__ __forceinline__ void chunk_shift(const uint32_t a[8], const uint32_t n[8], uint32_t o[8])
+{
+#pragma unroll
+    for (int m = 0; m < 8; ++m) o[m] = m + D < 8 ? a[m + D] : n[m + D - 8];
+}
+
+// one lane's eight consecutive samples i0 ... i0 + 7 (i0 a multiple of 8), the first `valid` of them decoded (base + s[j]), into every
+// chunk that holds them.  Every lane of the workgroup calls it at the same point (the END chunk's lines take a cross-lane shuffle).
+template <int OUT>
+__device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int valid, uint32_t base, const uint32_t s[8], const SigK& sk)
+{
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    uint32_t e[8];
+    {
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = sig_f32(base + s[j], sk);
+        if (OB == 4) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) e[j] = __float_as_uint(f[j]);
+        } else {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const uint32_t w = sig_pack2<OUT & 3>(f[2 * m], f[2 * m + 1]);
+                e[2 * m] = w & 0xFFFFu;
+                e[2 * m + 1] = w >> 16;
+            }
+        }
+    }
+    if (valid < 8) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j >= valid) e[j] = ck.padw;
+    }
+    // the grid chunks: k = floor(i0 / S) down to the first chunk that still reaches i0
+    if (valid > 0) {
+        uint32_t k = __umulhi(i0, ck.inv);
+        if (i0 - k * ck.S >= ck.S) ++k;
+        if (k > ck.nG - 1u) k = ck.nG - 1u;
+        uint32_t off = i0 - k * ck.S;
+        uint8_t* p = ck.base + (uint64_t)k * ck.row_bytes + (size_t)off * OB;
+        const int64_t back = (int64_t)ck.S * OB - (int64_t)ck.row_bytes;   // one chunk back: the same sample S positions further on
+        while (off < ck.L) {
+            chunk_put8<OUT>(p, e);
+            if (k == 0) break;
+            --k;
+            off += ck.S;
+            p += back;
+        }
+    }
+    if (!ck.extra) return;
+    // the END chunk
+    const uint32_t sl = ck.last, d = sl & 7u, g0 = sl - d;
+    uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
+    if (d == 0) {
+        if (valid > 0 && i0 >= sl && i0 - sl < ck.L) chunk_put8<OUT>(row + (size_t)(i0 - sl) * OB, e);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const bool in = valid > 0 && i0 >= g0 && i0 - g0 < ck.L;                           // the line that starts at sample i0 + d
+    const bool in0 = lane == 0 && valid > 0 && i0 >= g0 + 8u && i0 - 8u - g0 < ck.L;   // lane 0: the line that starts in the group before
+    if (!__any(in || in0)) return;
+    uint32_t n[8];
+    if (OB == 4) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) n[j] = (uint32_t)__shfl_down((int)e[j], 1, 64);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t w = (uint32_t)__shfl_down((int)(e[2 * m] | (e[2 * m + 1] << 16)), 1, 64);
+            n[2 * m] = w & 0xFFFFu;
+            n[2 * m + 1] = w >> 16;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (i0 + 8u + (uint32_t)j >= ck.T) n[j] = ck.padw;
+    if (in) {
+        if (i0 + 8u >= ck.T || lane != 63) {
+            uint32_t o[8];
+            switch (d) {
+            case 1: chunk_shift<1>(e, n, o); break;
+            case 2: chunk_shift<2>(e, n, o); break;
+            case 3: chunk_shift<3>(e, n, o); break;
+            case 4: chunk_shift<4>(e, n, o); break;
+            case 5: chunk_shift<5>(e, n, o); break;
+            case 6: chunk_shift<6>(e, n, o); break;
+            default: chunk_shift<7>(e, n, o); break;
+            }
+            chunk_put8<OUT>(row + (size_t)(i0 - g0) * OB, o);
+        } else {   // (the next group is another wavefront's: its lane 0 stores the rest of the line)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if ((uint32_t)j >= d) chunk_put1<OUT>(row + (size_t)(i0 - g0 + (uint32_t)j - d) * OB, e[j]);
+        }
+    }
+    if (in0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if ((uint32_t)j < d) chunk_put1<OUT>(row + (size_t)(i0 + (uint32_t)j - sl) * OB, e[j]);
+    }
+}
+
+// the last chunk's lines past the read's end (no sample in them): the pad value, by the whole workgroup
+template <int OUT>
+__device__ __forceinline__ void chunk_pad(const ChunkK& ck)
+{
+    if (ck.K == 0) return;
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
+    uint32_t e[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) e[j] = ck.padw;
+    for (uint32_t j = ((ck.T - ck.last + 7u) >> 3) + threadIdx.x; j < (ck.L >> 3); j += WG) chunk_put8<OUT>(row + (size_t)j * 8u * OB, e);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -922,6 +1102,7 @@ struct I16DecPairs
     uint8_t* stage;           // two buffers of BUF bytes
     uint32_t* ws;             // WS_WORDS words, 16-byte aligned
     SigK sk;                  // run<OUT != 0>: the read's constants
+    ChunkK ck;                // run<OUT & SIG_CHUNK>: the read's chunks
 
     static __device__ __forceinline__ uint32_t announced(uint32_t k) { return 8u + (uint32_t)__popc(k & 0x5555u) + 2u * (uint32_t)__popc(k & 0xAAAAu); }
 
@@ -1016,7 +1197,10 @@ struct I16DecPairs
                 const uint32_t totA = a4.x + a4.y + a4.z + a4.w, totB = b4.x + b4.y + b4.z + b4.w;
                 const uint32_t baseA = rn + (a4.x & m0) + (a4.y & m1) + (a4.z & m2) + incA - accA;
                 const uint32_t baseB = rn + totA + (b4.x & m0) + (b4.y & m1) + (b4.z & m2) + incB - accB;
-                if (OUT != SIG_NONE) {
+                if (OUT & SIG_CHUNK) {
+                    chunk_store8<OUT>(ck, tc + (uint32_t)tid * 8u, 8, baseA, sA, sk);
+                    chunk_store8<OUT>(ck, tc + TILE + (uint32_t)tid * 8u, 8, baseB, sB, sk);
+                } else if (OUT != SIG_NONE) {
                     constexpr uint32_t OB = OutBytes<OUT>::value;
                     uint8_t* op = out + ((size_t)tc + (size_t)tid * 8) * OB;
                     sig_store8<OUT>(op, baseA, sA, sk);
@@ -1067,11 +1251,12 @@ struct I16DecPairs
 //         chain stands at `run`; store them.  MODE 1: only add up the data bytes the control bytes announce.
 //         MODE 2: decode without storing (the total of the deltas is wanted).  pos / run are updated; returns false when
 //         the stream is shorter than its control bytes claim.  All 256 threads.
-// OUT (ELEM 2, MODE 0): the typed store (SIG_*): out points to the read's typed slot, sk holds its constants.
+// OUT (ELEM 2, MODE 0): the typed store (SIG_*): out points to the read's typed slot, sk holds its constants.  OUT | SIG_CHUNK: the chunk
+// store (ck: the read's chunks; out is the 16-byte aligned chunk arena).
 template <int ELEM, bool ZZ, bool I16ZZ, int MODE, int OUT = SIG_NONE>
 __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_t* data, uint32_t dataBytes, uint32_t count, uint32_t first,
                                                  uint32_t end, uint64_t& pos_io, uint32_t& run_io, uint8_t* out, uint8_t* stage, uint32_t* wsum,
-                                                 const SigK& sk = SigK())
+                                                 const SigK& sk = SigK(), const ChunkK& ck = ChunkK())
 {
     static_assert(OUT == SIG_NONE || (ELEM == 2 && MODE == 0), "the typed store is for int16 samples");
     constexpr int VPL = Vpl<ELEM>::value;
@@ -1084,7 +1269,7 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
     bool good = true;
     uint32_t t_start = first;
     if (I16ZZ && MODE == 0 && out_aligned && end - first >= 2u * (uint32_t)TILE) {   // pairs of whole tiles: I16DecPairs
-        I16DecPairs dp = { in, data, dataBytes, out, stage, wsum, sk };
+        I16DecPairs dp = { in, data, dataBytes, out, stage, wsum, sk, ck };
         t_start = dp.run<OUT>(first, end, pos, run);
     }
     for (uint32_t t0 = t_start; t0 < end; t0 += TILE) {
@@ -1170,7 +1355,9 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
             pos += tot;
             continue;
         }
-        if (OUT != SIG_NONE) {
+        if (OUT & SIG_CHUNK) {
+            chunk_store8<OUT>(ck, i0, valid, base, s, sk);
+        } else if (OUT != SIG_NONE) {
             constexpr uint32_t OB = OutBytes<OUT>::value;
             if (valid == VPL && out_aligned) {
                 sig_store8<OUT>(out + (size_t)i0 * OB, base, s, sk);
@@ -1247,6 +1434,14 @@ __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBa
     uint64_t pos = 0;
     uint32_t run = 0;
     bool good;
+    if (OUT & SIG_CHUNK) {
+        constexpr uint32_t OB = OutBytes<OUT>::value;
+        const ChunkK ck = chunk_constants<OUT>(b, r, count);
+        good = svb_decode_range<ELEM, ZZ, I16ZZ, 0, OUT>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst, stage, wsum, sig_constants(b, r), ck);
+        chunk_pad<OUT>(ck);
+        if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * OB;
+        return;
+    }
     if (OUT != SIG_NONE) {
         constexpr uint32_t OB = OutBytes<OUT>::value;
         good = svb_decode_range<ELEM, ZZ, I16ZZ, 0, OUT>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst + (b.dst_off[r] >> 1) * OB, stage,
@@ -1318,6 +1513,13 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
     uint64_t pos = MODE == 1 ? 0 : (SELF ? self_pos : seg_pos[blockIdx.x]);
     uint32_t run = (MODE == 0 && ZZ) ? (SELF ? (uint32_t)self_run : seg_run[blockIdx.x]) : 0u;
     const uint64_t pos0 = pos;
+    if (OUT & SIG_CHUNK) {   // (MODE 0; the read's first segment pads its last chunk)
+        const ChunkK ck = chunk_constants<OUT>(b, r, count);
+        (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE, OUT>(in, in + keyLen, dataBytes, count, first, end, pos, run, b.dst, stage, wsum,
+                                                           sig_constants(b, r), ck);
+        if (k == 0) chunk_pad<OUT>(ck);
+        return;
+    }
     if (OUT != SIG_NONE) {
         (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE, OUT>(in, in + keyLen, dataBytes, count, first, end, pos, run,
                                                            b.dst + (b.dst_off[r] >> 1) * OutBytes<OUT>::value, stage, wsum, sig_constants(b, r));
@@ -1632,6 +1834,12 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
 template <bool Z, bool I>
 hipError_t launch_svb_decode_typed(const ReadBatch& b, hipStream_t s)
 {
+    if (b.sig.row) {   // the chunk store
+        if (b.sig.type == SIG_F32) return launch1(svb_decode_kernel<2, Z, I, SIG_F32 | SIG_CHUNK>, b, s);
+        if (b.sig.type == SIG_F16) return launch1(svb_decode_kernel<2, Z, I, SIG_F16 | SIG_CHUNK>, b, s);
+        if (b.sig.type == SIG_BF16) return launch1(svb_decode_kernel<2, Z, I, SIG_BF16 | SIG_CHUNK>, b, s);
+        return hipErrorInvalidValue;
+    }
     if (b.sig.type == SIG_F32) return launch1(svb_decode_kernel<2, Z, I, SIG_F32>, b, s);
     if (b.sig.type == SIG_F16) return launch1(svb_decode_kernel<2, Z, I, SIG_F16>, b, s);
     if (b.sig.type == SIG_BF16) return launch1(svb_decode_kernel<2, Z, I, SIG_BF16>, b, s);
@@ -1721,6 +1929,18 @@ hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigz
     if (b.sig.type != SIG_NONE) {
         if (integer_size != 2) return hipErrorInvalidValue;
 #define X(Z, I, O) return svb_decode_seg_typed<Z, I, O>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
+        if (b.sig.row) {   // the chunk store
+            if (zigzag) {
+                if (b.sig.type == SIG_F32) X(true, true, SIG_F32 | SIG_CHUNK);
+                if (b.sig.type == SIG_F16) X(true, true, SIG_F16 | SIG_CHUNK);
+                if (b.sig.type == SIG_BF16) X(true, true, SIG_BF16 | SIG_CHUNK);
+            } else {
+                if (b.sig.type == SIG_F32) X(false, false, SIG_F32 | SIG_CHUNK);
+                if (b.sig.type == SIG_F16) X(false, false, SIG_F16 | SIG_CHUNK);
+                if (b.sig.type == SIG_BF16) X(false, false, SIG_BF16 | SIG_CHUNK);
+            }
+            return hipErrorInvalidValue;
+        }
         if (zigzag) {
             if (b.sig.type == SIG_F32) X(true, true, SIG_F32);
             if (b.sig.type == SIG_F16) X(true, true, SIG_F16);

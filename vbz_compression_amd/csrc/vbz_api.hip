@@ -106,6 +106,7 @@ struct vbz_gpu_ctx
     bool checksum = false;     // vbz_gpu_set_checksum / VBZ_HIP_CHECKSUM=1: frames written with the content checksum (xxh64.hip)
     DevBuf cksum;              // the hashes of a compress launch group (8 bytes per read)
     DevBuf sigmeta;            // typed decode: the int16 slot table and the per-read constants (signal_slots)
+    DevBuf chunkmeta;          // chunk layout: the per-read chunk counts
     int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
     bool zero_run_sequences = true;
     bool fuse_svb = false;     // VBZ_HIP_FUSE_SVB=1: the frame's wavefront decodes the svb stream too (measured slower: DESIGN.md 4.4)
@@ -859,7 +860,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
 {
     const uint32_t n = rb.n_reads;
     if (ensure_large(c) != 0) return -1;
-    if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * 56 + route_cand_words() * 4 + 512)) return -1;
+    if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * 64 + route_cand_words() * 4 + 512)) return -1;
     MetaCarver mc(c->route.p);
     r->gate_small = mc.take<uint32_t>(n);
     uint64_t* l_src_off = mc.take<uint64_t>(ROUTE_MAX_READS);
@@ -870,6 +871,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     uint32_t* l_result = mc.take<uint32_t>(ROUTE_MAX_READS);
     r->map = mc.take<uint32_t>(ROUTE_MAX_READS);
     float2* l_cal = mc.take<float2>(ROUTE_MAX_READS);
+    uint64_t* l_row = mc.take<uint64_t>(ROUTE_MAX_READS);
     r->count = mc.take<uint32_t>(4);
     uint32_t* cand = mc.take<uint32_t>(route_cand_words());
     r->large = rb;
@@ -881,9 +883,10 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     r->large.gate = l_gate;
     r->large.result = l_result;
     if (rb.sig.cal) r->large.sig.cal = l_cal;   // (the routed reads' constants, gathered through the map)
+    if (rb.sig.row) r->large.sig.row = l_row;   // (and their first chunk rows)
     Timed t(c, "route");
     HIPCHK(c, launch_route_reads(rb, raw_size, ROUTE_MIN_BYTES, ROUTE_MAX_READS, ROUTE_MAX_BYTES, r->gate_small, l_src_off, l_src_size, l_dst_off, l_dst_cap,
-                                 l_gate, r->map, l_cal, r->count, cand, c->stream),
+                                 l_gate, r->map, l_cal, l_row, r->count, cand, c->stream),
            "route launch");
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream), "event record");
     HIPCHK(c, hipStreamWaitEvent(c->large->stream, c->ev_fork, 0), "stream wait");
@@ -984,6 +987,7 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
     u.result += h;
     if (u.gate) u.gate += h;
     if (u.sig.cal) u.sig.cal += h;
+    if (u.sig.row) u.sig.row += h;
     return u;
 }
 
@@ -1157,9 +1161,22 @@ int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_f
     return 0;
 }
 
-// sig (nullable): a typed decode (signal_slots)
+// Chunk decode (vbz_gpu_decompress_chunks_batch): the caller's dst side is the int16 layout of the same reads, so the descriptor checks,
+// sized headers, scratch plan, routing and the split are the int16 call's; rb.dst becomes the chunk arena and the svb stage stores the
+// typed samples into the reads' chunks (rb.sig.row: chunk_first, untrusted -- chunk_slots gates every read whose entries are not exactly
+// its chunks before anything of it is decoded).
+struct ChunkCall
+{
+    const vbz_gpu_signal_format* f;
+    const vbz_gpu_chunking* ch;
+    const uint64_t* chunk_first;
+    void* chunks;
+    uint64_t chunk_rows;
+};
+
+// sig (nullable): a typed decode (signal_slots); chunks (nullable): a chunk decode
 int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, bool own_descriptors = false,
-                          const vbz_gpu_signal_format* sig = nullptr)
+                          const vbz_gpu_signal_format* sig = nullptr, const ChunkCall* chunks = nullptr)
 {
     const uint32_t n = bt->n_reads;
     c->last_frames = 0;
@@ -1170,6 +1187,21 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (!own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
     uint64_t dst_bytes = bt->dst_bytes;
     if (sig && signal_slots(c, bt, sig, &rb, &dst_bytes) != 0) return -1;
+    float2* chunk_cal = nullptr;
+    if (chunks) {
+        if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
+        chunk_cal = reinterpret_cast<float2*>(c->sigmeta.p);
+        rb.dst = (uint8_t*)chunks->chunks;
+        rb.sig.cal = chunk_cal;
+        rb.sig.type = chunks->f->out_type;
+        rb.sig.bias = chunks->f->is_signed ? 0u : 0x8000u;
+        rb.sig.row = chunks->chunk_first;
+        rb.sig.chunk_len = chunks->ch->chunk_len;
+        rb.sig.step = chunks->ch->step;
+        rb.sig.mode = chunks->ch->mode;
+        rb.sig.end_align = chunks->ch->end_align;
+        rb.sig.pad = chunks->ch->pad;
+    }
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
         if (!ensure(c, c->meta, (size_t)n * 24 + 512)) return -1;
         MetaCarver mc(c->meta.p);
@@ -1184,6 +1216,12 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         rb.src_size = pay_size;
         rb.dst_cap = orig_size;
         rb.gate = gate;
+    }
+    if (chunks) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
+        Timed t(c, "chunk_slots");
+        HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, chunks->f->offset, chunks->f->scale, rb.sig.chunk_len, rb.sig.step, chunks->chunk_first, chunks->chunk_rows,
+                                     chunk_cal, const_cast<uint32_t*>(rb.gate), s),
+               "chunk slots launch");
     }
     const bool by_shape = o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
     if (c->foreign_pending && hipEventQuery(c->ev_foreign) == hipSuccess) {   // what the call before this one found (see foreign_host)
@@ -1316,7 +1354,7 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
         (void)hipEventDestroy(p.stop);
     }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta })
+    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta })
         if (b->p) (void)hipFree(b->p);
     if (c->large) vbz_gpu_destroy(c->large);
     if (c->half) vbz_gpu_destroy(c->half);
@@ -1396,6 +1434,76 @@ int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
     }
     if (!plausible_extents(c, bt)) return -2;
     return decompress_batch_impl(c, bt, o, sized, false, f);
+}
+
+static_assert(CHUNK_PAD == VBZ_GPU_CHUNK_PAD && CHUNK_END == VBZ_GPU_CHUNK_END, "the ABI's chunk modes");
+static_assert(sizeof(vbz_gpu_chunking) == 24, "vbz_gpu_chunking is 24 bytes");
+bool chunking_ok(vbz_gpu_ctx* c, const vbz_gpu_chunking* ch)
+{
+    if (!ch) {
+        set_error(c, "chunking is NULL");
+        return false;
+    }
+    const uint32_t L = ch->chunk_len, S = ch->step;
+    const bool align_ok = ch->mode == VBZ_GPU_CHUNK_PAD ? ch->end_align == 0 : (ch->end_align >= 1 && ch->end_align <= 4096);
+    if (L < 8 || L > (1u << 20) || L % 8 != 0 || S < 8 || S > L || S % 8 != 0 || ch->mode > VBZ_GPU_CHUNK_END || !align_ok || ch->reserved != 0) {
+        set_error(c, "chunking outside the rules (chunk_len %u, step %u, mode %u, end_align %u, reserved %u)", L, S, ch->mode, ch->end_align, ch->reserved);
+        return false;
+    }
+    return true;
+}
+
+int vbz_gpu_chunk_layout_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* samples, const vbz_gpu_chunking* ch, uint64_t* chunk_first,
+                               uint32_t* chunk_info, uint64_t info_cap)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!chunking_ok(c, ch)) return -2;
+    if (!chunk_first || (n != 0 && !samples)) {
+        set_error(c, "a table of the chunk layout call is NULL");
+        return -2;
+    }
+    if (!ensure(c, c->chunkmeta, (size_t)n * 4 + 64)) return -1;
+    Timed t(c, "chunk_layout");
+    HIPCHK(c, launch_chunk_layout(n, samples, ch->chunk_len, ch->step, reinterpret_cast<uint32_t*>(c->chunkmeta.p), chunk_first, c->stream),
+           "chunk layout launch");
+    HIPCHK(c, launch_chunk_info(n, samples, ch->chunk_len, ch->step, ch->mode, ch->end_align, chunk_first, chunk_info, info_cap, c->stream),
+           "chunk info launch");
+    return 0;
+}
+
+int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                    const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!o || o->integer_size != 2 || o->vbz_version > 1) {
+        set_error(c, "unsupported options for a chunk decode (integer_size must be 2, version 0 or 1)");
+        return -2;
+    }
+    if (!f || f->out_type < VBZ_GPU_SIGNAL_F32 || f->out_type > VBZ_GPU_SIGNAL_BF16 || f->is_signed > 1) {
+        set_error(c, "signal format: NULL, unknown out_type or is_signed not 0 / 1");
+        return -2;
+    }
+    if (!chunking_ok(c, ch)) return -2;
+    if (bt->n_reads != 0 && (!chunk_first || !chunks)) {
+        set_error(c, "chunk_first or the chunk arena is NULL");
+        return -2;
+    }
+    if (((uintptr_t)chunks & 15u) != 0) {
+        set_error(c, "the chunk arena is not 16-byte aligned");
+        return -2;
+    }
+    const uint64_t row_bytes = (uint64_t)ch->chunk_len * (f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u);
+    if (chunk_rows > EXTENT_MAX / row_bytes) {
+        set_error(c, "declared chunk arena is not plausible (%llu rows of %llu bytes)", (unsigned long long)chunk_rows, (unsigned long long)row_bytes);
+        return -2;
+    }
+    vbz_gpu_batch b = *bt;   // (batch->dst is not used: the svb stage stores into the chunk arena)
+    b.dst = chunks;
+    if (!plausible_extents(c, &b)) return -2;
+    const ChunkCall cc = { f, ch, chunk_first, chunks, chunk_rows };
+    return decompress_batch_impl(c, &b, o, sized, false, nullptr, &cc);
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

@@ -24,13 +24,36 @@ constexpr int PHASE_SLOTS = 12;  // per-read cycle counters of the timed kernel 
 // ((float)x + cal[i].x) * cal[i].y in the output type (SIG_*: the VBZ_GPU_SIGNAL_* values), x being int16 (bias 0) or uint16
 // (bias 0x8000).  dst_off / dst_cap of the batch then count int16 bytes: the read's typed slot starts at dst + dst_off[i] / 2 * E
 // (E = 4 or 2 bytes per sample) and result[i] is samples * E.  type == SIG_NONE: the int16 samples themselves.
+// Chunk store (vbz_gpu_decompress_chunks_batch; row != NULL): the typed samples go to fixed-length chunks instead of a slot -- chunk k of
+// read i is row row[i] + k of a row-major [rows, chunk_len] arena at dst (see chunk_count / chunk_last_start); dst_off is not used.
 constexpr uint32_t SIG_NONE = 0, SIG_F32 = 1, SIG_F16 = 2, SIG_BF16 = 3;
+constexpr uint32_t SIG_CHUNK = 4;   // (or-ed into the svb decoder's OUT template argument: the chunk store of that output type)
+constexpr uint32_t CHUNK_PAD = 0, CHUNK_END = 1;
 struct SignalOut
 {
     const float2* cal = nullptr;   // per read {offset, scale}, in the batch's read order
     uint32_t type = SIG_NONE;
     uint32_t bias = 0;
+    const uint64_t* row = nullptr;   // chunk store: per read, its first row (chunk_first), in the batch's read order
+    uint32_t chunk_len = 0, step = 0, mode = 0, end_align = 0;
+    float pad = 0.0f;
 };
+
+// the chunking of a read of T samples (include/vbz_gpu.h, vbz_gpu_chunking): K chunks, the last one starting at chunk_last_start
+__host__ __device__ inline uint32_t chunk_count(uint32_t T, uint32_t L, uint32_t S)
+{
+    if (T == 0) return 0;
+    if (T <= L) return 1;
+    return (T - L + S - 1) / S + 1;
+}
+__host__ __device__ inline uint32_t chunk_last_start(uint32_t T, uint32_t K, uint32_t L, uint32_t S, uint32_t mode, uint32_t end_align)
+{
+    if (K <= 1) return 0;
+    const uint32_t g = (K - 1) * S;
+    if (mode != CHUNK_END) return g;
+    const uint32_t e = (T - L + end_align - 1) / end_align * end_align;
+    return e < g ? e : g;
+}
 
 // One batch of independent reads ("reads" in the reference's vocabulary: one HDF5 chunk each).
 // All pointers are device pointers.  `result[i]` receives the bytes produced or an error code.
@@ -305,10 +328,10 @@ hipError_t launch_count_nonzero(const uint32_t* a, uint32_t n, uint32_t* out, hi
 hipError_t launch_canon_classify(uint32_t n, const uint32_t* raw_size, const uint32_t* gate, uint32_t min_bytes, uint32_t* gate_small, uint32_t* gate_large,
                                  uint32_t* counts, hipStream_t s);
 // per-read routing: see route_reads_kernel (helpers.hip).  raw_size[i] = the read's raw (decoded) byte count.
-// l_cal: the routed reads' b.sig.cal entries (not written when b.sig.cal is NULL).
+// l_cal / l_row: the routed reads' b.sig.cal / b.sig.row entries (not written when those are NULL).
 hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint32_t min_bytes, uint32_t max_reads, uint64_t max_bytes, uint32_t* gate_small,
                               uint64_t* l_src_off, uint32_t* l_src_size, uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map,
-                              float2* l_cal, uint32_t* l_count, uint32_t* cand, hipStream_t s);   // cand: route_cand_words() words of scratch
+                              float2* l_cal, uint64_t* l_row, uint32_t* l_count, uint32_t* cand, hipStream_t s);   // cand: route_cand_words() words of scratch
 size_t route_cand_words();
 hipError_t launch_route_results(const uint32_t* l_result, const uint32_t* l_map, const uint32_t* l_count, uint32_t max_reads, uint32_t* result, hipStream_t s);
 // sized decode: read the 4-byte headers -> payload offsets/sizes, original sizes, gate errors (gate_in, nullable: reads that
@@ -329,6 +352,18 @@ hipError_t launch_validate_batch(uint32_t n, const uint64_t* src_off, const uint
 // multiple of elem gets gate[i] = E_DESTINATION_SIZE (gate: launch_validate_batch's verdicts on the typed table, updated in place).
 hipError_t launch_signal_slots(uint32_t n, const uint64_t* dst_off, const uint32_t* dst_cap, uint32_t elem, const float* offset, const float* scale,
                                uint64_t* off16, uint32_t* cap16, float2* cal, uint32_t* gate, hipStream_t s);
+// chunk decode (SignalOut::row): the per-read table and the chunk check, once the int16 capacities are final (unsized: the caller's; sized:
+// the headers' sizes).  cal[i] as in launch_signal_slots; a read whose gate is no error and whose chunk_first entries are not exactly
+// its chunks (chunk_first[i] <= chunk_first[i + 1] <= chunk_rows, the difference chunk_count(cap16[i] / 2, L, S)) gets
+// gate[i] = E_DESTINATION_SIZE: nothing of it is decoded or stored.
+hipError_t launch_chunk_slots(uint32_t n, const uint32_t* cap16, const float* offset, const float* scale, uint32_t L, uint32_t S,
+                              const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate, hipStream_t s);
+// chunk layout (pack.hip): chunk_first[i] = the exclusive scan of chunk_count(samples[i]) (samples of 2^31 or more: 0 chunks), chunk_first[n]
+// the total; count: n words of scratch.  launch_chunk_info: when chunk_first[n] <= info_cap, info[2c] / info[2c + 1] = the read / start
+// sample of row c (a grid-stride launch; nothing when the total is larger).
+hipError_t launch_chunk_layout(uint32_t n, const uint32_t* samples, uint32_t L, uint32_t S, uint32_t* count, uint64_t* chunk_first, hipStream_t s);
+hipError_t launch_chunk_info(uint32_t n, const uint32_t* samples, uint32_t L, uint32_t S, uint32_t mode, uint32_t end_align, const uint64_t* chunk_first,
+                             uint32_t* info, uint64_t info_cap, hipStream_t s);
 // integer_size == 0 && level == 0: per-read copy (reference vbz/vbz.cpp:130-133)
 hipError_t launch_copy_bytes(const ReadBatch& b, uint32_t hdr, hipStream_t s);
 hipError_t launch_synth_lengths(uint64_t seed, uint64_t first, uint32_t n, uint32_t* out_len, hipStream_t s);
