@@ -115,6 +115,17 @@ class GpuCodec:
 
     _SIGNAL_TYPES = {torch.float32: _lib.VBZ_GPU_SIGNAL_F32, torch.float16: _lib.VBZ_GPU_SIGNAL_F16, torch.bfloat16: _lib.VBZ_GPU_SIGNAL_BF16}
 
+    def _signal_format(self, dtype, n, scale, offset, signed):
+        """The GpuSignalFormat of n reads decoded to dtype (see decompress_signal)."""
+        f = _lib.GpuSignalFormat()
+        f.out_type = self._SIGNAL_TYPES[dtype]
+        f.is_signed = int(bool(signed))
+        for name, t in (("offset", offset), ("scale", scale)):
+            if t is not None:
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) >= n, (name, t.dtype, t.device)
+                setattr(f, name, t.data_ptr())
+        return f
+
     def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False):
         """Decode int16 signal straight to calibrated samples, y = (x + offset[i]) * scale[i] in float32 arithmetic (include/vbz_gpu.h:
         vbz_gpu_decompress_signal_batch).  dst: a 1-D float32, float16 or bfloat16 tensor (its dtype is the output type); dst_off / dst_cap
@@ -122,14 +133,7 @@ class GpuCodec:
         an error code.  scale / offset: float32 tensors of n entries on the codec's device, or None (1 / 0 for every read).  signed: the
         16-bit samples are int16 (True) or uint16."""
         assert dst.dtype in self._SIGNAL_TYPES and dst.dim() == 1 and dst.is_contiguous(), (dst.dtype, dst.shape)
-        n = int(src_off.numel())
-        f = _lib.GpuSignalFormat()
-        f.out_type = self._SIGNAL_TYPES[dst.dtype]
-        f.is_signed = int(bool(signed))
-        for name, t in (("offset", offset), ("scale", scale)):
-            if t is not None:
-                assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) >= n, (name, t.dtype, t.device)
-                setattr(f, name, t.data_ptr())
+        f = self._signal_format(dst.dtype, int(src_off.numel()), scale, offset, signed)
         b = self._batch(src, src_off, src_size, dst.view(torch.uint8), dst_off, dst_cap, result)
         cur = self._enter()
         try:
@@ -340,14 +344,7 @@ class GpuCodec:
     def _decode_chunks(self, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, ch, chunk_first, chunks, dtype, scale, offset,
                        signed):
         assert dtype in self._SIGNAL_TYPES and chunks.dtype == dtype and chunks.is_contiguous(), (dtype, chunks.dtype)
-        n = int(src_off.numel())
-        f = _lib.GpuSignalFormat()
-        f.out_type = self._SIGNAL_TYPES[dtype]
-        f.is_signed = int(bool(signed))
-        for name, t in (("offset", offset), ("scale", scale)):
-            if t is not None:
-                assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) >= n, (name, t.dtype, t.device)
-                setattr(f, name, t.data_ptr())
+        f = self._signal_format(dtype, int(src_off.numel()), scale, offset, signed)
         no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
         b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
         b.dst = None     # (the int16 layout only describes the reads: nothing is stored there)

@@ -312,6 +312,87 @@ __device__ __forceinline__ void chunk_pad(const ChunkK& ck)
     for (uint32_t j = ((ck.T - ck.last + 7u) >> 3) + threadIdx.x; j < (ck.L >> 3); j += WG) chunk_put8<OUT>(row + (size_t)j * 8u * OB, e);
 }
 
+// ---- the decoder's output: what svb_decode_range and I16DecPairs store, where, and in how many bytes per value -----------------------
+// OUT = SIG_NONE: the ELEM-byte values into the read's slot (dst + dst_off[r]).  SIG_*: the typed samples of int16 values into the read's
+// typed slot (dst + dst_off[r] / 2 * E: dst_off is the int16 layout's).  SIG_* | SIG_CHUNK: the typed samples into the read's chunks.
+template <int ELEM, int OUT>
+struct DecStore
+{
+    static_assert(OUT == SIG_NONE || ELEM == 2, "the typed stores are for int16 samples");
+    static constexpr int VPL = Vpl<ELEM>::value;
+    static constexpr uint32_t BYTES = OUT == SIG_NONE ? ELEM : OutBytes<OUT>::value;   // per value: result[r] = count * BYTES
+    uint8_t* out;   // the read's slot (the chunk store: the 16-byte aligned chunk arena)
+    SigK sk;
+    ChunkK ck;
+
+    // b: the batch, for the typed stores only -- SIG_NONE gets nullptr and the batch's fields (a reference to the kernel's ReadBatch
+    // argument would cost its loads their scalar form)
+    __device__ __forceinline__ DecStore(uint8_t* dst, const uint64_t* dst_off, const ReadBatch* b, uint32_t r, uint32_t count)
+    {
+        if (OUT == SIG_NONE) {
+            out = dst + dst_off[r];
+        } else if (OUT & SIG_CHUNK) {
+            out = dst;
+            ck = chunk_constants<OUT>(*b, r, count);
+            sk = sig_constants(*b, r);
+        } else {
+            out = dst + (dst_off[r] >> 1) * BYTES;
+            sk = sig_constants(*b, r);
+        }
+    }
+
+    // whole 16-byte lines may be stored: the tile loop's lanes of VPL values, and I16DecPairs at all
+    __device__ __forceinline__ bool aligned() const { return (((uintptr_t)out) & 15u) == 0; }
+
+    // one lane's values i0 ... i0 + valid - 1 (base + s[k]).  The chunk store takes every lane of the workgroup at the same point.
+    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[VPL]) const
+    {
+        if (OUT & SIG_CHUNK) {
+            chunk_store8<OUT>(ck, i0, valid, base, s, sk);
+        } else if (OUT != SIG_NONE) {
+            if (valid == VPL && aligned()) {
+                sig_store8<OUT>(out + (size_t)i0 * BYTES, base, s, sk);
+            } else {
+#pragma unroll
+                for (int k = 0; k < VPL; ++k)
+                    if (k < valid) sig_store1<OUT>(out + (size_t)(i0 + k) * BYTES, base + s[k], sk);
+            }
+        } else if (valid == VPL && aligned()) {
+            uint32_t w[4];
+            if (ELEM == 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) w[k] = base + s[k % VPL];
+            } else if (ELEM == 2) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    w[k] = ((base + s[(2 * k) % VPL]) & 0xFFFFu) | ((base + s[(2 * k + 1) % VPL]) << 16);
+            } else {
+                w[2] = w[3] = 0;
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+                    w[k] = ((base + s[(4 * k) % VPL]) & 0xFFu) | (((base + s[(4 * k + 1) % VPL]) & 0xFFu) << 8) |
+                           (((base + s[(4 * k + 2) % VPL]) & 0xFFu) << 16) | ((base + s[(4 * k + 3) % VPL]) << 24);
+            }
+            if (ELEM == 1) {
+                *reinterpret_cast<uint2*>(out + (size_t)i0) = make_uint2(w[0], w[1]);
+            } else {
+                *reinterpret_cast<uint4*>(out + (size_t)i0 * ELEM) = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < VPL; ++k)
+                if (k < valid) store_elem(out + (size_t)(i0 + k) * ELEM, ELEM, base + s[k]);
+        }
+    }
+
+    // after the read's values, by the whole workgroup (svb_decode_range: the range at the read's start): the chunk store's lines past the
+    // read's end
+    __device__ __forceinline__ void finish() const
+    {
+        if (OUT & SIG_CHUNK) chunk_pad<OUT>(ck);
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // encode
 // ------------------------------------------------------------------------------------------------
@@ -1098,11 +1179,8 @@ struct I16DecPairs
     const uint8_t* in;        // control bytes
     const uint8_t* data;
     uint32_t dataBytes;
-    uint8_t* out;             // 16-byte aligned
     uint8_t* stage;           // two buffers of BUF bytes
     uint32_t* ws;             // WS_WORDS words, 16-byte aligned
-    SigK sk;                  // run<OUT != 0>: the read's constants
-    ChunkK ck;                // run<OUT & SIG_CHUNK>: the read's chunks
 
     static __device__ __forceinline__ uint32_t announced(uint32_t k) { return 8u + (uint32_t)__popc(k & 0x5555u) + 2u * (uint32_t)__popc(k & 0xAAAAu); }
 
@@ -1124,9 +1202,9 @@ struct I16DecPairs
     }
 
     // pairs from t0 on while two whole tiles are left; pos / run as in svb_decode_range.  Returns the first value not decoded (a multiple of
-    // the tile size from t0).  All 256 threads; ends with a barrier.  OUT: the store (SIG_*; out then points to the typed slot).
-    template <int OUT>
-    __device__ __forceinline__ uint32_t run(uint32_t t0_in, uint32_t end_in, uint64_t& pos_io, uint32_t& run_io)
+    // the tile size from t0).  All 256 threads; ends with a barrier.  st: the store, of whole lines (st.aligned()).
+    template <class Store>
+    __device__ __forceinline__ uint32_t run(const Store& st, uint32_t t0_in, uint32_t end_in, uint64_t& pos_io, uint32_t& run_io)
     {
         const int tid = threadIdx.x, lane = tid & 63;
         const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1197,24 +1275,8 @@ struct I16DecPairs
                 const uint32_t totA = a4.x + a4.y + a4.z + a4.w, totB = b4.x + b4.y + b4.z + b4.w;
                 const uint32_t baseA = rn + (a4.x & m0) + (a4.y & m1) + (a4.z & m2) + incA - accA;
                 const uint32_t baseB = rn + totA + (b4.x & m0) + (b4.y & m1) + (b4.z & m2) + incB - accB;
-                if (OUT & SIG_CHUNK) {
-                    chunk_store8<OUT>(ck, tc + (uint32_t)tid * 8u, 8, baseA, sA, sk);
-                    chunk_store8<OUT>(ck, tc + TILE + (uint32_t)tid * 8u, 8, baseB, sB, sk);
-                } else if (OUT != SIG_NONE) {
-                    constexpr uint32_t OB = OutBytes<OUT>::value;
-                    uint8_t* op = out + ((size_t)tc + (size_t)tid * 8) * OB;
-                    sig_store8<OUT>(op, baseA, sA, sk);
-                    sig_store8<OUT>(op + TILE * OB, baseB, sB, sk);
-                } else {
-                uint32_t w[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) w[k] = ((baseA + sA[2 * k]) & 0xFFFFu) | ((baseA + sA[2 * k + 1]) << 16);
-                uint8_t* op = out + ((size_t)tc + (size_t)tid * 8) * 2;
-                *reinterpret_cast<uint4*>(op) = make_uint4(w[0], w[1], w[2], w[3]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) w[k] = ((baseB + sB[2 * k]) & 0xFFFFu) | ((baseB + sB[2 * k + 1]) << 16);
-                *reinterpret_cast<uint4*>(op + TILE * 2) = make_uint4(w[0], w[1], w[2], w[3]);
-                }
+                st.put(tc + (uint32_t)tid * 8u, 8, baseA, sA);
+                st.put(tc + TILE + (uint32_t)tid * 8u, 8, baseB, sB);
                 rn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(rn + totA + totB));
             }
             have = more;
@@ -1250,27 +1312,25 @@ struct I16DecPairs
 // MODE 0: decode values [first, end) of a stream of `count` values whose data bytes start at data[pos] and whose delta
 //         chain stands at `run`; store them.  MODE 1: only add up the data bytes the control bytes announce.
 //         MODE 2: decode without storing (the total of the deltas is wanted).  pos / run are updated; returns false when
-//         the stream is shorter than its control bytes claim.  All 256 threads.
-// OUT (ELEM 2, MODE 0): the typed store (SIG_*): out points to the read's typed slot, sk holds its constants.  OUT | SIG_CHUNK: the chunk
-// store (ck: the read's chunks; out is the 16-byte aligned chunk arena).
-template <int ELEM, bool ZZ, bool I16ZZ, int MODE, int OUT = SIG_NONE>
+//         the stream is shorter than its control bytes claim.  All 256 threads.  st: where MODE 0 stores (a typed store: MODE 0 only);
+//         the MODE 0 range that starts at the read's first value (the whole read, or its first segment) also finishes it.
+template <int ELEM, bool ZZ, bool I16ZZ, int MODE, int OUT>
 __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_t* data, uint32_t dataBytes, uint32_t count, uint32_t first,
-                                                 uint32_t end, uint64_t& pos_io, uint32_t& run_io, uint8_t* out, uint8_t* stage, uint32_t* wsum,
-                                                 const SigK& sk = SigK(), const ChunkK& ck = ChunkK())
+                                                 uint32_t end, uint64_t& pos_io, uint32_t& run_io, const DecStore<ELEM, OUT>& st, uint8_t* stage,
+                                                 uint32_t* wsum)
 {
-    static_assert(OUT == SIG_NONE || (ELEM == 2 && MODE == 0), "the typed store is for int16 samples");
+    static_assert(OUT == SIG_NONE || MODE == 0, "the typed stores are the storing pass's");
     constexpr int VPL = Vpl<ELEM>::value;
     constexpr int TILE = WG * VPL;
     const int tid = threadIdx.x;
-    const bool out_aligned = (((uintptr_t)out) & 15u) == 0;
     const uint32_t* stage32 = reinterpret_cast<const uint32_t*>(stage);
     uint64_t pos = pos_io;   // data bytes consumed so far
     uint32_t run = run_io;   // running value of the delta chain
     bool good = true;
     uint32_t t_start = first;
-    if (I16ZZ && MODE == 0 && out_aligned && end - first >= 2u * (uint32_t)TILE) {   // pairs of whole tiles: I16DecPairs
-        I16DecPairs dp = { in, data, dataBytes, out, stage, wsum, sk, ck };
-        t_start = dp.run<OUT>(first, end, pos, run);
+    if (I16ZZ && MODE == 0 && st.aligned() && end - first >= 2u * (uint32_t)TILE) {   // pairs of whole tiles: I16DecPairs
+        I16DecPairs dp = { in, data, dataBytes, stage, wsum };
+        t_start = dp.run(st, first, end, pos, run);
     }
     for (uint32_t t0 = t_start; t0 < end; t0 += TILE) {
         const uint32_t i0 = t0 + (uint32_t)tid * VPL;
@@ -1355,45 +1415,10 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
             pos += tot;
             continue;
         }
-        if (OUT & SIG_CHUNK) {
-            chunk_store8<OUT>(ck, i0, valid, base, s, sk);
-        } else if (OUT != SIG_NONE) {
-            constexpr uint32_t OB = OutBytes<OUT>::value;
-            if (valid == VPL && out_aligned) {
-                sig_store8<OUT>(out + (size_t)i0 * OB, base, s, sk);
-            } else {
-#pragma unroll
-                for (int k = 0; k < VPL; ++k)
-                    if (k < valid) sig_store1<OUT>(out + (size_t)(i0 + k) * OB, base + s[k], sk);
-            }
-        } else if (valid == VPL && out_aligned) {
-            uint32_t w[4];
-            if (ELEM == 4) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) w[k] = base + s[k % VPL];
-            } else if (ELEM == 2) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    w[k] = ((base + s[(2 * k) % VPL]) & 0xFFFFu) | ((base + s[(2 * k + 1) % VPL]) << 16);
-            } else {
-                w[2] = w[3] = 0;
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-                    w[k] = ((base + s[(4 * k) % VPL]) & 0xFFu) | (((base + s[(4 * k + 1) % VPL]) & 0xFFu) << 8) |
-                           (((base + s[(4 * k + 2) % VPL]) & 0xFFu) << 16) | ((base + s[(4 * k + 3) % VPL]) << 24);
-            }
-            if (ELEM == 1) {
-                *reinterpret_cast<uint2*>(out + (size_t)i0) = make_uint2(w[0], w[1]);
-            } else {
-                *reinterpret_cast<uint4*>(out + (size_t)i0 * ELEM) = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < VPL; ++k)
-                if (k < valid) store_elem(out + (size_t)(i0 + k) * ELEM, ELEM, base + s[k]);
-        }
+        st.put(i0, valid, base, s);
         pos += tot;
     }
+    if (MODE == 0 && first == 0) st.finish();   // (the read's first range: the whole read, or its first segment)
     pos_io = pos;
     run_io = run;
     return good;
@@ -1433,24 +1458,9 @@ __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBa
     const uint32_t dataBytes = in_size - keyLen;
     uint64_t pos = 0;
     uint32_t run = 0;
-    bool good;
-    if (OUT & SIG_CHUNK) {
-        constexpr uint32_t OB = OutBytes<OUT>::value;
-        const ChunkK ck = chunk_constants<OUT>(b, r, count);
-        good = svb_decode_range<ELEM, ZZ, I16ZZ, 0, OUT>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst, stage, wsum, sig_constants(b, r), ck);
-        chunk_pad<OUT>(ck);
-        if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * OB;
-        return;
-    }
-    if (OUT != SIG_NONE) {
-        constexpr uint32_t OB = OutBytes<OUT>::value;
-        good = svb_decode_range<ELEM, ZZ, I16ZZ, 0, OUT>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst + (b.dst_off[r] >> 1) * OB, stage,
-                                                         wsum, sig_constants(b, r));
-        if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * OB;
-        return;
-    }
-    good = svb_decode_range<ELEM, ZZ, I16ZZ, 0>(in, in + keyLen, dataBytes, count, 0, count, pos, run, b.dst + b.dst_off[r], stage, wsum);
-    if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * ELEM;
+    const DecStore<ELEM, OUT> st(b.dst, b.dst_off, OUT == SIG_NONE ? nullptr : &b, r, count);
+    const bool good = svb_decode_range<ELEM, ZZ, I16ZZ, 0>(in, in + keyLen, dataBytes, count, 0, count, pos, run, st, stage, wsum);
+    if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * st.BYTES;
 }
 
 // ---- segmented decode: pass 1 adds up the data bytes each segment's control bytes announce; a scan gives every
@@ -1489,7 +1499,7 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
             else if (!svb_decode_check<ELEM, I16ZZ>(b.src_size[r], b.dst_cap[r], res0)) {
                 const uint32_t count0 = b.dst_cap[r] / ELEM;
                 const uint32_t dataBytes0 = b.src_size[r] - ((count0 + 3u) >> 2);
-                res0 = self_total == dataBytes0 ? count0 * (OUT != SIG_NONE ? (uint32_t)OutBytes<OUT>::value : (uint32_t)ELEM) : E_STREAM;
+                res0 = self_total == dataBytes0 ? count0 * DecStore<ELEM, OUT>::BYTES : E_STREAM;
             }
             b.result[r] = res0;
         }
@@ -1513,19 +1523,8 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
     uint64_t pos = MODE == 1 ? 0 : (SELF ? self_pos : seg_pos[blockIdx.x]);
     uint32_t run = (MODE == 0 && ZZ) ? (SELF ? (uint32_t)self_run : seg_run[blockIdx.x]) : 0u;
     const uint64_t pos0 = pos;
-    if (OUT & SIG_CHUNK) {   // (MODE 0; the read's first segment pads its last chunk)
-        const ChunkK ck = chunk_constants<OUT>(b, r, count);
-        (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE, OUT>(in, in + keyLen, dataBytes, count, first, end, pos, run, b.dst, stage, wsum,
-                                                           sig_constants(b, r), ck);
-        if (k == 0) chunk_pad<OUT>(ck);
-        return;
-    }
-    if (OUT != SIG_NONE) {
-        (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE, OUT>(in, in + keyLen, dataBytes, count, first, end, pos, run,
-                                                           b.dst + (b.dst_off[r] >> 1) * OutBytes<OUT>::value, stage, wsum, sig_constants(b, r));
-        return;
-    }
-    (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE>(in, in + keyLen, dataBytes, count, first, end, pos, run, b.dst + b.dst_off[r], stage, wsum);
+    const DecStore<ELEM, OUT> st(b.dst, b.dst_off, OUT == SIG_NONE ? nullptr : &b, r, count);
+    (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE>(in, in + keyLen, dataBytes, count, first, end, pos, run, st, stage, wsum);
     if (MODE == 1 && tid == 0) seg_val[blockIdx.x] = (uint32_t)(pos - pos0);
     if (MODE == 2 && tid == 0) (SELF ? seg_run_io : seg_val)[blockIdx.x] = run;
 }
@@ -1791,6 +1790,65 @@ hipError_t launch1(K kernel, const ReadBatch& b, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---- the svb decoder's launches with the store OUT (DecStore; the typed stores: int16 samples only) -------------------------------------
+// b.sig's store: OUT = b.sig.type, | SIG_CHUNK with chunk rows
+uint32_t svb_decode_out(const ReadBatch& b) { return b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u); }
+
+template <int OUT>
+hipError_t svb_decode_launch(const ReadBatch& b, int integer_size, bool zigzag, hipStream_t s)
+{
+    if (integer_size == 2) return zigzag ? launch1(svb_decode_kernel<2, true, true, OUT>, b, s) : launch1(svb_decode_kernel<2, false, false, OUT>, b, s);
+    if constexpr (OUT == SIG_NONE) {
+        if (integer_size == 4) return zigzag ? launch1(svb_decode_kernel<4, true, false>, b, s) : launch1(svb_decode_kernel<4, false, false>, b, s);
+        if (integer_size == 1) return zigzag ? launch1(svb_decode_kernel<1, true, false>, b, s) : launch1(svb_decode_kernel<1, false, false>, b, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// the segmented decode: MODE 1, then (SELF) MODE 2 and MODE 0, or the verdict scan, MODE 2 and its scan, and MODE 0; only MODE 0 stores
+template <int E, bool Z, bool I, int OUT>
+hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val, uint64_t* seg_pos,
+                                   uint32_t* seg_run, hipStream_t s)
+{
+    const dim3 segs(max_segs), reads(b.n_reads), t(WG);
+    hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 1>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    if (max_segs <= seg_self_max()) {
+        if (Z) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    } else {
+        hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, true, DecStore<E, OUT>::BYTES>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        if (Z) {
+            hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+            hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, false>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        }
+        hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    }
+    return hipGetLastError();
+}
+
+template <int OUT>
+hipError_t svb_decode_seg_launch(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val,
+                                 uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s)
+{
+#define X(E, Z, I) return svb_decode_seg_sequence<E, Z, I, OUT>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
+    if (integer_size == 2) {
+        if (zigzag) X(2, true, true);
+        X(2, false, false);
+    }
+    if constexpr (OUT == SIG_NONE) {
+        if (integer_size == 4) {
+            if (zigzag) X(4, true, false);
+            X(4, false, false);
+        }
+        if (integer_size == 1) {
+            if (zigzag) X(1, true, false);
+            X(1, false, false);
+        }
+    }
+#undef X
+    return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half) { return integer_size == 2 && zigzag && !half; }
@@ -1830,39 +1888,22 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
     return hipGetLastError();
 }
 
-// b.sig.type: the typed store (int16 samples only), the output type a template argument of its own instantiation
-template <bool Z, bool I>
-hipError_t launch_svb_decode_typed(const ReadBatch& b, hipStream_t s)
-{
-    if (b.sig.row) {   // the chunk store
-        if (b.sig.type == SIG_F32) return launch1(svb_decode_kernel<2, Z, I, SIG_F32 | SIG_CHUNK>, b, s);
-        if (b.sig.type == SIG_F16) return launch1(svb_decode_kernel<2, Z, I, SIG_F16 | SIG_CHUNK>, b, s);
-        if (b.sig.type == SIG_BF16) return launch1(svb_decode_kernel<2, Z, I, SIG_BF16 | SIG_CHUNK>, b, s);
-        return hipErrorInvalidValue;
-    }
-    if (b.sig.type == SIG_F32) return launch1(svb_decode_kernel<2, Z, I, SIG_F32>, b, s);
-    if (b.sig.type == SIG_F16) return launch1(svb_decode_kernel<2, Z, I, SIG_F16>, b, s);
-    if (b.sig.type == SIG_BF16) return launch1(svb_decode_kernel<2, Z, I, SIG_BF16>, b, s);
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s)
 {
-    if (b.sig.type != SIG_NONE) {
-        if (integer_size != 2 || half) return hipErrorInvalidValue;
-        return zigzag ? launch_svb_decode_typed<true, true>(b, s) : launch_svb_decode_typed<false, false>(b, s);
-    }
     if (half) {
-        if (integer_size != 1) return hipErrorInvalidValue;
+        if (integer_size != 1 || b.sig.type != SIG_NONE) return hipErrorInvalidValue;
         return zigzag ? launch1(svb_half_decode_kernel<true>, b, s) : launch1(svb_half_decode_kernel<false>, b, s);
     }
-    if (integer_size == 2 && zigzag) return launch1(svb_decode_kernel<2, true, true>, b, s);
-    if (integer_size == 2) return launch1(svb_decode_kernel<2, false, false>, b, s);
-    if (integer_size == 4 && zigzag) return launch1(svb_decode_kernel<4, true, false>, b, s);
-    if (integer_size == 4) return launch1(svb_decode_kernel<4, false, false>, b, s);
-    if (integer_size == 1 && zigzag) return launch1(svb_decode_kernel<1, true, false>, b, s);
-    if (integer_size == 1) return launch1(svb_decode_kernel<1, false, false>, b, s);
-    return hipErrorInvalidValue;
+    switch (svb_decode_out(b)) {
+    case SIG_NONE: return svb_decode_launch<SIG_NONE>(b, integer_size, zigzag, s);
+    case SIG_F32: return svb_decode_launch<SIG_F32>(b, integer_size, zigzag, s);
+    case SIG_F16: return svb_decode_launch<SIG_F16>(b, integer_size, zigzag, s);
+    case SIG_BF16: return svb_decode_launch<SIG_BF16>(b, integer_size, zigzag, s);
+    case SIG_F32 | SIG_CHUNK: return svb_decode_launch<SIG_F32 | SIG_CHUNK>(b, integer_size, zigzag, s);
+    case SIG_F16 | SIG_CHUNK: return svb_decode_launch<SIG_F16 | SIG_CHUNK>(b, integer_size, zigzag, s);
+    case SIG_BF16 | SIG_CHUNK: return svb_decode_launch<SIG_BF16 | SIG_CHUNK>(b, integer_size, zigzag, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 // ---- segmented launches (few, large reads) --------------------------------------------------------------------------
@@ -1901,75 +1942,22 @@ hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigz
     return hipGetLastError();
 }
 
-// the launches of launch_svb_decode_seg with the typed store OUT (the passes that do not store are the int16 decode's own)
-template <bool Z, bool I, int OUT>
-hipError_t svb_decode_seg_typed(const ReadBatch& b, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val, uint64_t* seg_pos,
-                                uint32_t* seg_run, hipStream_t s)
-{
-    constexpr int OB = OutBytes<OUT>::value;
-    hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 1>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    if (max_segs <= seg_self_max()) {
-        if (Z) hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 2, true>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-        hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 0, true, OUT>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    } else {
-        hipLaunchKernelGGL((svb_seg_decode_scan_kernel<2, I, true, OB>), dim3(b.n_reads), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-        if (Z) {
-            hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 2>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-            hipLaunchKernelGGL((svb_seg_decode_scan_kernel<2, I, false>), dim3(b.n_reads), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-        }
-        hipLaunchKernelGGL((svb_seg_decode_kernel<2, Z, I, 0, false, OUT>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
                                  uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    if (b.sig.type != SIG_NONE) {
-        if (integer_size != 2) return hipErrorInvalidValue;
-#define X(Z, I, O) return svb_decode_seg_typed<Z, I, O>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
-        if (b.sig.row) {   // the chunk store
-            if (zigzag) {
-                if (b.sig.type == SIG_F32) X(true, true, SIG_F32 | SIG_CHUNK);
-                if (b.sig.type == SIG_F16) X(true, true, SIG_F16 | SIG_CHUNK);
-                if (b.sig.type == SIG_BF16) X(true, true, SIG_BF16 | SIG_CHUNK);
-            } else {
-                if (b.sig.type == SIG_F32) X(false, false, SIG_F32 | SIG_CHUNK);
-                if (b.sig.type == SIG_F16) X(false, false, SIG_F16 | SIG_CHUNK);
-                if (b.sig.type == SIG_BF16) X(false, false, SIG_BF16 | SIG_CHUNK);
-            }
-            return hipErrorInvalidValue;
-        }
-        if (zigzag) {
-            if (b.sig.type == SIG_F32) X(true, true, SIG_F32);
-            if (b.sig.type == SIG_F16) X(true, true, SIG_F16);
-            if (b.sig.type == SIG_BF16) X(true, true, SIG_BF16);
-        } else {
-            if (b.sig.type == SIG_F32) X(false, false, SIG_F32);
-            if (b.sig.type == SIG_F16) X(false, false, SIG_F16);
-            if (b.sig.type == SIG_BF16) X(false, false, SIG_BF16);
-        }
-#undef X
-        return hipErrorInvalidValue;
+#define X(O) return svb_decode_seg_launch<O>(b, integer_size, zigzag, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
+    switch (svb_decode_out(b)) {
+    case SIG_NONE: X(SIG_NONE);
+    case SIG_F32: X(SIG_F32);
+    case SIG_F16: X(SIG_F16);
+    case SIG_BF16: X(SIG_BF16);
+    case SIG_F32 | SIG_CHUNK: X(SIG_F32 | SIG_CHUNK);
+    case SIG_F16 | SIG_CHUNK: X(SIG_F16 | SIG_CHUNK);
+    case SIG_BF16 | SIG_CHUNK: X(SIG_BF16 | SIG_CHUNK);
+    default: return hipErrorInvalidValue;
     }
-    const bool self = max_segs <= seg_self_max();
-#define X(E, Z, I)                                                                                                                          \
-    hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 1>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);             \
-    if (self) {                                                                                                                             \
-        if (Z) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2, true>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run); \
-        hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);   \
-    } else {                                                                                                                                \
-        hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, true>), dim3(b.n_reads), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);   \
-        if (Z) {                                                                                                                            \
-            hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);     \
-            hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, false>), dim3(b.n_reads), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run); \
-        }                                                                                                                                   \
-        hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0>), dim3(max_segs), dim3(WG), 0, s, b, seg_first, seg_val, seg_pos, seg_run);         \
-    }
-    VBZ_SVB_DISPATCH(X);
 #undef X
-    return hipGetLastError();
 }
 
 }  // namespace vbzhip

@@ -1134,29 +1134,41 @@ int compress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressi
     return rc;
 }
 
+// the options and the sample format of a signal or chunk decode (`what`: which decode, for the error text)
+bool typed_args_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_signal_format* f, const char* what)
+{
+    if (!o || o->integer_size != 2 || o->vbz_version > 1) {
+        set_error(c, "unsupported options for a %s decode (integer_size must be 2, version 0 or 1)", what);
+        return false;
+    }
+    if (!f || f->out_type < VBZ_GPU_SIGNAL_F32 || f->out_type > VBZ_GPU_SIGNAL_BF16 || f->is_signed > 1) {
+        set_error(c, "signal format: NULL, unknown out_type or is_signed not 0 / 1");
+        return false;
+    }
+    return true;
+}
+
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
 // through the int16 slot table made from it here -- offsets and capacities / E * 2, the extent likewise -- so that the descriptor checks,
 // the sized headers, the scratch plan, routing and the split see exactly what an int16 call with those capacities sees; the svb stage
 // alone stores the typed samples (rb.sig).  A slot whose offset or capacity is not a multiple of E gets VBZ_DESTINATION_SIZE_ERROR.
 // The typed slots lie inside [0, dst_bytes) iff the int16 ones lie inside [0, dst_bytes / E * 2): validate_descriptors looked at the former.
 static_assert(SIG_F32 == VBZ_GPU_SIGNAL_F32 && SIG_F16 == VBZ_GPU_SIGNAL_F16 && SIG_BF16 == VBZ_GPU_SIGNAL_BF16, "the ABI's output types");
-int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_format* f, ReadBatch* rb, uint64_t* dst_bytes)
+// *cal: the per-read constants, for rb->sig.cal
+int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_format* f, ReadBatch* rb, uint64_t* dst_bytes, float2** cal)
 {
     const uint32_t n = bt->n_reads, elem = f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u;
     if (!ensure(c, c->sigmeta, (size_t)n * 20 + 256)) return -1;
     MetaCarver mc(c->sigmeta.p);
     uint64_t* off16 = mc.take<uint64_t>(n);
     uint32_t* cap16 = mc.take<uint32_t>(n);
-    float2* cal = mc.take<float2>(n);
+    *cal = mc.take<float2>(n);
     Timed t(c, "signal_slots");
-    HIPCHK(c, launch_signal_slots(n, bt->dst_off, bt->dst_cap, elem, f->offset, f->scale, off16, cap16, cal, reinterpret_cast<uint32_t*>(c->vgate.p),
+    HIPCHK(c, launch_signal_slots(n, bt->dst_off, bt->dst_cap, elem, f->offset, f->scale, off16, cap16, *cal, reinterpret_cast<uint32_t*>(c->vgate.p),
                                   c->stream),
            "signal slots launch");
     rb->dst_off = off16;
     rb->dst_cap = cap16;
-    rb->sig.cal = cal;
-    rb->sig.type = f->out_type;
-    rb->sig.bias = f->is_signed ? 0u : 0x8000u;
     *dst_bytes = bt->dst_bytes / elem * 2u;
     return 0;
 }
@@ -1165,18 +1177,19 @@ int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_f
 // sized headers, scratch plan, routing and the split are the int16 call's; rb.dst becomes the chunk arena and the svb stage stores the
 // typed samples into the reads' chunks (rb.sig.row: chunk_first, untrusted -- chunk_slots gates every read whose entries are not exactly
 // its chunks before anything of it is decoded).
-struct ChunkCall
+// TypedOut: what a typed decode stores -- f the samples' format; ch != nullptr: a chunk decode into `chunks`.
+struct TypedOut
 {
     const vbz_gpu_signal_format* f;
-    const vbz_gpu_chunking* ch;
-    const uint64_t* chunk_first;
-    void* chunks;
-    uint64_t chunk_rows;
+    const vbz_gpu_chunking* ch = nullptr;
+    const uint64_t* chunk_first = nullptr;
+    void* chunks = nullptr;
+    uint64_t chunk_rows = 0;
 };
 
-// sig (nullable): a typed decode (signal_slots); chunks (nullable): a chunk decode
+// out (nullable): a typed decode (signal_slots) or a chunk decode (out->ch)
 int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, bool own_descriptors = false,
-                          const vbz_gpu_signal_format* sig = nullptr, const ChunkCall* chunks = nullptr)
+                          const TypedOut* out = nullptr)
 {
     const uint32_t n = bt->n_reads;
     c->last_frames = 0;
@@ -1186,21 +1199,25 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     ReadBatch rb = to_rb(bt);
     if (!own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
     uint64_t dst_bytes = bt->dst_bytes;
-    if (sig && signal_slots(c, bt, sig, &rb, &dst_bytes) != 0) return -1;
-    float2* chunk_cal = nullptr;
+    const bool chunks = out && out->ch;
+    float2* cal = nullptr;   // the per-read constants (a chunk decode: chunk_slots fills them in)
     if (chunks) {
         if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
-        chunk_cal = reinterpret_cast<float2*>(c->sigmeta.p);
-        rb.dst = (uint8_t*)chunks->chunks;
-        rb.sig.cal = chunk_cal;
-        rb.sig.type = chunks->f->out_type;
-        rb.sig.bias = chunks->f->is_signed ? 0u : 0x8000u;
-        rb.sig.row = chunks->chunk_first;
-        rb.sig.chunk_len = chunks->ch->chunk_len;
-        rb.sig.step = chunks->ch->step;
-        rb.sig.mode = chunks->ch->mode;
-        rb.sig.end_align = chunks->ch->end_align;
-        rb.sig.pad = chunks->ch->pad;
+        cal = reinterpret_cast<float2*>(c->sigmeta.p);
+        rb.dst = (uint8_t*)out->chunks;
+        rb.sig.row = out->chunk_first;
+        rb.sig.chunk_len = out->ch->chunk_len;
+        rb.sig.step = out->ch->step;
+        rb.sig.mode = out->ch->mode;
+        rb.sig.end_align = out->ch->end_align;
+        rb.sig.pad = out->ch->pad;
+    } else if (out && signal_slots(c, bt, out->f, &rb, &dst_bytes, &cal) != 0) {
+        return -1;
+    }
+    if (out) {
+        rb.sig.cal = cal;
+        rb.sig.type = out->f->out_type;
+        rb.sig.bias = out->f->is_signed ? 0u : 0x8000u;
     }
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
         if (!ensure(c, c->meta, (size_t)n * 24 + 512)) return -1;
@@ -1219,8 +1236,8 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     }
     if (chunks) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "chunk_slots");
-        HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, chunks->f->offset, chunks->f->scale, rb.sig.chunk_len, rb.sig.step, chunks->chunk_first, chunks->chunk_rows,
-                                     chunk_cal, const_cast<uint32_t*>(rb.gate), s),
+        HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, out->f->offset, out->f->scale, rb.sig.chunk_len, rb.sig.step, out->chunk_first, out->chunk_rows,
+                                     cal, const_cast<uint32_t*>(rb.gate), s),
                "chunk slots launch");
     }
     const bool by_shape = o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
@@ -1424,16 +1441,10 @@ int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
-    if (!o || o->integer_size != 2 || o->vbz_version > 1) {
-        set_error(c, "unsupported options for a signal decode (integer_size must be 2, version 0 or 1)");
-        return -2;
-    }
-    if (!f || f->out_type < VBZ_GPU_SIGNAL_F32 || f->out_type > VBZ_GPU_SIGNAL_BF16 || f->is_signed > 1) {
-        set_error(c, "signal format: NULL, unknown out_type or is_signed not 0 / 1");
-        return -2;
-    }
+    if (!typed_args_ok(c, o, f, "signal")) return -2;
     if (!plausible_extents(c, bt)) return -2;
-    return decompress_batch_impl(c, bt, o, sized, false, f);
+    const TypedOut out = { f };
+    return decompress_batch_impl(c, bt, o, sized, false, &out);
 }
 
 static_assert(CHUNK_PAD == VBZ_GPU_CHUNK_PAD && CHUNK_END == VBZ_GPU_CHUNK_END, "the ABI's chunk modes");
@@ -1477,14 +1488,7 @@ int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
-    if (!o || o->integer_size != 2 || o->vbz_version > 1) {
-        set_error(c, "unsupported options for a chunk decode (integer_size must be 2, version 0 or 1)");
-        return -2;
-    }
-    if (!f || f->out_type < VBZ_GPU_SIGNAL_F32 || f->out_type > VBZ_GPU_SIGNAL_BF16 || f->is_signed > 1) {
-        set_error(c, "signal format: NULL, unknown out_type or is_signed not 0 / 1");
-        return -2;
-    }
+    if (!typed_args_ok(c, o, f, "chunk")) return -2;
     if (!chunking_ok(c, ch)) return -2;
     if (bt->n_reads != 0 && (!chunk_first || !chunks)) {
         set_error(c, "chunk_first or the chunk arena is NULL");
@@ -1502,8 +1506,8 @@ int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
     vbz_gpu_batch b = *bt;   // (batch->dst is not used: the svb stage stores into the chunk arena)
     b.dst = chunks;
     if (!plausible_extents(c, &b)) return -2;
-    const ChunkCall cc = { f, ch, chunk_first, chunks, chunk_rows };
-    return decompress_batch_impl(c, &b, o, sized, false, nullptr, &cc);
+    const TypedOut out = { f, ch, chunk_first, chunks, chunk_rows };
+    return decompress_batch_impl(c, &b, o, sized, false, &out);
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

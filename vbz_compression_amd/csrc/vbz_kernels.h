@@ -27,7 +27,7 @@ constexpr int PHASE_SLOTS = 12;  // per-read cycle counters of the timed kernel 
 // Chunk store (vbz_gpu_decompress_chunks_batch; row != NULL): the typed samples go to fixed-length chunks instead of a slot -- chunk k of
 // read i is row row[i] + k of a row-major [rows, chunk_len] arena at dst (see chunk_count / chunk_last_start); dst_off is not used.
 constexpr uint32_t SIG_NONE = 0, SIG_F32 = 1, SIG_F16 = 2, SIG_BF16 = 3;
-constexpr uint32_t SIG_CHUNK = 4;   // (or-ed into the svb decoder's OUT template argument: the chunk store of that output type)
+constexpr uint32_t SIG_CHUNK = 4;   // (or-ed into the chunk store's type: the svb decoder's OUT, the store DecStore<ELEM, OUT> of its kernels)
 constexpr uint32_t CHUNK_PAD = 0, CHUNK_END = 1;
 struct SignalOut
 {
@@ -120,7 +120,8 @@ inline EncPlan* zstd_encode_plans(void* plan_meta) { return reinterpret_cast<Enc
 hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, uint32_t hdr, bool strict_cap, bool half, uint32_t* period_hint,
                              void* plans, hipStream_t s);
 bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half);   // does launch_svb_encode(plans) write every read's hist_mode?
-// Decode: b.sig.type != SIG_NONE (integer_size 2 only; launch_svb_decode_seg too) stores the typed samples of SignalOut.
+// Decode: b.sig.type != SIG_NONE (integer_size 2 only; launch_svb_decode_seg too) stores the typed samples of SignalOut (OUT = b.sig.type,
+// | SIG_CHUNK with b.sig.row).
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
