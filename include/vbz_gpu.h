@@ -211,6 +211,62 @@ VBZ_EXPORT int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* ctx, const vbz_gpu_b
                                                const vbz_gpu_signal_format* format, const vbz_gpu_chunking* chunking,
                                                const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows);
 
+/* Per-read normalisation.  A model wants each read normalised by statistics of its own signal, which exist only once the read is decoded.
+ * These calls derive them on the device, from the svb streams the decode leaves in its scratch, by extra passes of the svb stage that store
+ * nothing; the zstd stage still runs once.  The statistics are order statistics of the read's T raw 16-bit values (int16 or uint16 per
+ * is_signed), x_(0) <= ... <= x_(T-1), in float64 arithmetic, each operation rounded to nearest even, no fused multiply-add:
+ *   MED_MAD:  c = the median (x_(floor((T-1)/2)) + x_(ceil((T-1)/2))) / 2, w = the median of the T values |x_j - c| by the same rule
+ *             (both bit for bit numpy's np.median on float64);
+ *   QUANTILE: Q(q) is numpy's np.quantile(x.astype(float64), float64(q)) (method "linear"): h = float64(q) * (T - 1), j = floor(h),
+ *             t = h - j, a = x_(j), b = x_(min(j + 1, T - 1)), d = b - a, Q = t < 0.5 ? a + d * t : b - d * (1 - t);
+ *             c = Q(quantile_a) + Q(quantile_b), w = Q(quantile_b) - Q(quantile_a);
+ *   T == 0:   c = w = 0.
+ * shift = float32(max(float64(shift_min), float64(shift_mul) * c)), scale = float32(max(float64(scale_min), float64(scale_mul) * w)).
+ * Bonito / Remora: MED_MAD, shift_mul 1, scale_mul 1.4826, shift_min -INFINITY, scale_min FLT_MIN: (x - med) / (1.4826 MAD).  Dorado:
+ * QUANTILE 0.2 / 0.9, shift_mul 0.51, scale_mul 0.53, shift_min 10, scale_min 1.
+ * The decode calls then store ((float)x - shift) * scale' with scale' = float32(1.0 / float64(scale)) -- a MULTIPLY BY A ROUNDED
+ * RECIPROCAL, not a division by scale: exactly the signal call's formula with offset = -shift and scale = scale' (its rounding rules,
+ * F16 / BF16 rounded once from the float32 value).
+ * shift_scale (device, n_reads x {float shift, float scale}; nullable for the two decode calls, required for the statistics alone) gets
+ * every read's shift and scale; for a read whose result[i] is an error code the entry is unspecified.
+ * vbz_gpu_decompress_signal_norm_batch and vbz_gpu_decompress_chunks_norm_batch behave exactly like vbz_gpu_decompress_signal_batch and
+ * vbz_gpu_decompress_chunks_batch (options, format, chunking, descriptor checks, sized headers, verdicts, result[i], what is and is not
+ * written), except that read i's constants come from its statistics: format->offset and format->scale must be NULL.
+ * vbz_gpu_signal_norm_batch computes the statistics alone: the dst side of the batch is the int16 layout (as for the chunk call), batch->dst
+ * may be NULL and is never written, result[i] is what vbz_gpu_decompress_batch gives for the read.
+ * All three return 0 when queued, -1 for a NULL context or batch or a launch failure, -2 (nothing launched) for everything their
+ * counterparts refuse, and: a NULL norm, an unknown method, reserved != 0, quantile fields outside their rules, NaN or +-inf where the struct
+ * says finite, a scale_min that is not a normal positive float, format->offset or format->scale not NULL, a NULL shift_scale (statistics
+ * call).
+ * How: a counting pass of the svb decoder histograms the read's values into 4 x 1024 bins of LDS around its first sample, and the ranks
+ * are read off the counts at the pass's end (on the large-read path the segments add their counts up in scratch, and a launch of its own
+ * selects); a rank outside those bins costs two more passes (the bracket shrinks 1024-fold a pass), a MAD outside them two more.  A call
+ * launches every pass a read may need (MED_MAD 5, QUANTILE 3); reads already finished leave a pass at once.  Measured on one MI355X, 65 536
+ * reads of ~100 k samples, L = 10 000, S = 9 504, PAD, float16 (tools/time_norm.py, profiles/HISTORY.md "Normalised chunks"): chunk call
+ * with given constants 11.7 ms; normalised chunks MED_MAD 16.9 ms, QUANTILE 16.7 ms; statistics alone 11.8 ms; int16 decode + torch
+ * per-read median / MAD + chunk call 708 ms.  The first counting pass costs about what the store pass costs (LDS atomics on crowded bins). */
+#define VBZ_GPU_NORM_MED_MAD 1
+#define VBZ_GPU_NORM_QUANTILE 2
+typedef struct vbz_gpu_normalization
+{
+    uint32_t method;            /* VBZ_GPU_NORM_* */
+    uint32_t reserved;          /* must be 0 */
+    float quantile_a;           /* QUANTILE: 0 <= quantile_a <= quantile_b <= 1; MED_MAD: both must be 0 */
+    float quantile_b;
+    float shift_mul, scale_mul; /* finite */
+    float shift_min;            /* finite, or -INFINITY (no floor) */
+    float scale_min;            /* finite, normal, > 0 */
+} vbz_gpu_normalization;        /* 32 bytes */
+VBZ_EXPORT int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                         uint32_t is_signed, const vbz_gpu_normalization* norm, float* shift_scale);
+VBZ_EXPORT int vbz_gpu_decompress_signal_norm_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                    int sized, const vbz_gpu_signal_format* format, const vbz_gpu_normalization* norm,
+                                                    float* shift_scale);
+VBZ_EXPORT int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                    int sized, const vbz_gpu_signal_format* format, const vbz_gpu_chunking* chunking,
+                                                    const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
+                                                    const vbz_gpu_normalization* norm, float* shift_scale);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

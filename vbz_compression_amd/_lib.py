@@ -86,6 +86,25 @@ class GpuChunking(ctypes.Structure):
     ]
 
 
+VBZ_GPU_NORM_MED_MAD = 1
+VBZ_GPU_NORM_QUANTILE = 2
+
+
+class GpuNormalization(ctypes.Structure):
+    """struct vbz_gpu_normalization of include/vbz_gpu.h (32 bytes)."""
+
+    _fields_ = [
+        ("method", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("quantile_a", ctypes.c_float),
+        ("quantile_b", ctypes.c_float),
+        ("shift_mul", ctypes.c_float),
+        ("scale_mul", ctypes.c_float),
+        ("shift_min", ctypes.c_float),
+        ("scale_min", ctypes.c_float),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -110,6 +129,9 @@ GPU_API = [
     "vbz_gpu_decompress_signal_batch",
     "vbz_gpu_chunk_layout_batch",
     "vbz_gpu_decompress_chunks_batch",
+    "vbz_gpu_signal_norm_batch",
+    "vbz_gpu_decompress_signal_norm_batch",
+    "vbz_gpu_decompress_chunks_norm_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -197,6 +219,16 @@ def load():
         L.vbz_gpu_chunk_layout_batch.argtypes = [vp, u32, vp, cp, vp, vp, u64]
         L.vbz_gpu_decompress_chunks_batch.restype = ctypes.c_int
         L.vbz_gpu_decompress_chunks_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.POINTER(GpuSignalFormat), cp, vp, vp, u64]
+    if hasattr(L, "vbz_gpu_signal_norm_batch"):   # (likewise: builds of earlier rounds have no normalising decode)
+        np_ = ctypes.POINTER(GpuNormalization)
+        fp = ctypes.POINTER(GpuSignalFormat)
+        cp = ctypes.POINTER(GpuChunking)
+        L.vbz_gpu_signal_norm_batch.restype = ctypes.c_int
+        L.vbz_gpu_signal_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, u32, np_, vp]
+        L.vbz_gpu_decompress_signal_norm_batch.restype = ctypes.c_int
+        L.vbz_gpu_decompress_signal_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, np_, vp]
+        L.vbz_gpu_decompress_chunks_norm_batch.restype = ctypes.c_int
+        L.vbz_gpu_decompress_chunks_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, cp, vp, vp, u64, np_, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

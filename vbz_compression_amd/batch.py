@@ -5,10 +5,41 @@ library.  All tensors must live on the codec's device.  Offsets are int64, sizes
 tensors whose bits are read as uint64 / uint32 by the C ABI.
 """
 import ctypes
+import dataclasses
 
 import torch
 
 from . import _lib
+
+FLT_MIN = 1.1754943508222875e-38   # the smallest normal float32
+
+
+@dataclasses.dataclass(frozen=True)
+class Normalization:
+    """Per-read normalisation from the read's own statistics (include/vbz_gpu.h: vbz_gpu_normalization): method "med_mad" (c = median,
+    w = MAD) or "quantile" (c = Q(a) + Q(b), w = Q(b) - Q(a)); shift = max(shift_min, shift_mul c), scale = max(scale_min, scale_mul w),
+    and a sample becomes (x - shift) * float32(1 / scale)."""
+
+    method: str
+    quantile_a: float = 0.0
+    quantile_b: float = 0.0
+    shift_mul: float = 1.0
+    scale_mul: float = 1.0
+    shift_min: float = float("-inf")
+    scale_min: float = FLT_MIN
+
+    _METHODS = {"med_mad": _lib.VBZ_GPU_NORM_MED_MAD, "quantile": _lib.VBZ_GPU_NORM_QUANTILE}
+
+    def c_struct(self):
+        m = _lib.GpuNormalization()
+        m.method = self._METHODS.get(self.method, 0xFFFFFFFF)
+        m.quantile_a, m.quantile_b = self.quantile_a, self.quantile_b
+        m.shift_mul, m.scale_mul, m.shift_min, m.scale_min = self.shift_mul, self.scale_mul, self.shift_min, self.scale_min
+        return m
+
+
+MED_MAD = Normalization("med_mad", scale_mul=1.4826)                                  # Bonito / Remora: (x - med) / (1.4826 MAD)
+DORADO_QUANTILE = Normalization("quantile", 0.2, 0.9, 0.51, 0.53, 10.0, 1.0)          # Dorado: q20 / q90
 
 
 def _u32(t):
@@ -126,19 +157,57 @@ class GpuCodec:
                 setattr(f, name, t.data_ptr())
         return f
 
-    def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False):
+    def _norm_args(self, n, norm, norm_out, scale, offset):
+        """(the C struct, shift_scale pointer) of a normalising call; norm_out: a float32 [n, 2] tensor on the codec's device, or None"""
+        assert scale is None and offset is None, "norm= replaces scale and offset"
+        assert isinstance(norm, Normalization), norm
+        if norm_out is not None:
+            assert norm_out.dtype == torch.float32 and norm_out.is_contiguous() and norm_out.device == self.device and tuple(norm_out.shape) == (n, 2), (
+                norm_out.dtype, norm_out.shape)
+        return norm.c_struct(), (norm_out.data_ptr() if norm_out is not None else None)
+
+    def signal_norm(self, src, src_off, src_size, dst_off, dst_cap, result, opts, norm, shift_scale=None, signed=True, sized=False):
+        """Every read's normalisation constants alone (include/vbz_gpu.h: vbz_gpu_signal_norm_batch) -> shift_scale, float32 [n, 2] of
+        (shift, scale) per read (allocated when None).  dst_off / dst_cap: the int16 layout of the reads (nothing is stored); result[i] is
+        what decompress gives."""
+        n = int(src_off.numel())
+        if shift_scale is None:
+            shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        m, ss = self._norm_args(n, norm, shift_scale, None, None)
+        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
+        b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
+        b.dst = None
+        b.dst_bytes = int(dst_off.max().item() + dst_cap.to(torch.int64).max().item()) if n else 0
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)), ctypes.byref(m), ss),
+                     "signal_norm_batch")
+        finally:
+            self._exit(cur)
+        return shift_scale
+
+    def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False,
+                          norm=None, norm_out=None):
         """Decode int16 signal straight to calibrated samples, y = (x + offset[i]) * scale[i] in float32 arithmetic (include/vbz_gpu.h:
         vbz_gpu_decompress_signal_batch).  dst: a 1-D float32, float16 or bfloat16 tensor (its dtype is the output type); dst_off / dst_cap
         in bytes of dst, as everywhere in this class (unsized: dst_cap[i] = samples * element size); result[i] = samples * element size or
         an error code.  scale / offset: float32 tensors of n entries on the codec's device, or None (1 / 0 for every read).  signed: the
-        16-bit samples are int16 (True) or uint16."""
+        16-bit samples are int16 (True) or uint16.  norm (a Normalization; not with scale / offset): every read normalised by its own
+        statistics instead (vbz_gpu_decompress_signal_norm_batch), its (shift, scale) left in norm_out (float32 [n, 2], or None)."""
         assert dst.dtype in self._SIGNAL_TYPES and dst.dim() == 1 and dst.is_contiguous(), (dst.dtype, dst.shape)
-        f = self._signal_format(dst.dtype, int(src_off.numel()), scale, offset, signed)
+        n = int(src_off.numel())
+        if norm is not None:
+            m, ss = self._norm_args(n, norm, norm_out, scale, offset)
+        f = self._signal_format(dst.dtype, n, scale, offset, signed)
         b = self._batch(src, src_off, src_size, dst.view(torch.uint8), dst_off, dst_cap, result)
         cur = self._enter()
         try:
-            self._rc(self.L.vbz_gpu_decompress_signal_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f)),
-                     "decompress_signal_batch")
+            if norm is None:
+                self._rc(self.L.vbz_gpu_decompress_signal_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f)),
+                         "decompress_signal_batch")
+            else:
+                self._rc(self.L.vbz_gpu_decompress_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f),
+                                                                     ctypes.byref(m), ss), "decompress_signal_norm_batch")
         finally:
             self._exit(cur)
 
@@ -273,7 +342,8 @@ class GpuCodec:
         self.decompress(packed, src_off, packed_size, raw, raw_off[:n], dst_cap, result, opts, sized=True)
         return raw, raw_off, raw_size, result
 
-    def decompress_packed_signal(self, packed, packed_off, packed_size, opts, dtype=torch.float32, scale=None, offset=None, signed=True):
+    def decompress_packed_signal(self, packed, packed_off, packed_size, opts, dtype=torch.float32, scale=None, offset=None, signed=True, norm=None,
+                                 norm_out=None):
         """decompress_packed into calibrated samples (decompress_signal): the sample counts come from the headers, the output (`dtype`)
         is laid out with 16-byte aligned slots and allocated (one synchronisation), and the batch decoded -> (out, out_off, samples,
         result): read i is out[out_off[i] : out_off[i] + samples[i]] (out_off int64 and samples int32, in elements) when result[i] is no
@@ -297,7 +367,7 @@ class GpuCodec:
         out_off = raw_off[:n] // 2
         result = torch.empty(n, dtype=torch.int32, device=self.device)
         self.decompress_signal(packed, src_off, packed_size, out, out_off * elem, dst_cap, result, opts, scale=scale, offset=offset, signed=signed,
-                               sized=True)
+                               sized=True, norm=norm, norm_out=norm_out)
         return out, out_off, (raw // 2).to(torch.int32), result
 
     # -- model-input chunks ------------------------------------------------------------------------
@@ -342,27 +412,36 @@ class GpuCodec:
         return chunk_first, chunk_info
 
     def _decode_chunks(self, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, ch, chunk_first, chunks, dtype, scale, offset,
-                       signed):
+                       signed, norm=None, norm_out=None):
         assert dtype in self._SIGNAL_TYPES and chunks.dtype == dtype and chunks.is_contiguous(), (dtype, chunks.dtype)
-        f = self._signal_format(dtype, int(src_off.numel()), scale, offset, signed)
+        n = int(src_off.numel())
+        if norm is not None:
+            m, ss = self._norm_args(n, norm, norm_out, scale, offset)
+        f = self._signal_format(dtype, n, scale, offset, signed)
         no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
         b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
         b.dst = None     # (the int16 layout only describes the reads: nothing is stored there)
         b.dst_bytes = int(dst_bytes)
         cur = self._enter()
         try:
-            self._rc(self.L.vbz_gpu_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f), ctypes.byref(ch),
-                                                            chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0])),
-                     "decompress_chunks_batch")
+            if norm is None:
+                self._rc(self.L.vbz_gpu_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f), ctypes.byref(ch),
+                                                                chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0])),
+                         "decompress_chunks_batch")
+            else:
+                self._rc(self.L.vbz_gpu_decompress_chunks_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f),
+                                                                     ctypes.byref(ch), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
+                                                                     ctypes.byref(m), ss), "decompress_chunks_norm_batch")
         finally:
             self._exit(cur)
 
     def decompress_chunks(self, src, src_off, src_size, samples, result, opts, chunk_len, step, mode="pad", end_align=1, pad=0.0, dtype=torch.float16,
-                          scale=None, offset=None, signed=True):
+                          scale=None, offset=None, signed=True, norm=None, norm_out=None):
         """Decode unsized int16 reads of `samples` samples (int32 on the device) straight into model-input chunks (include/vbz_gpu.h:
         vbz_gpu_decompress_chunks_batch), calibrated as decompress_signal does -> (chunks [total, chunk_len] of dtype, chunk_first int64
         [n + 1], chunk_info int32 [total, 2]): chunk k of read i is chunks[chunk_first[i] + k] when result[i] is no error code (result[i] =
-        samples * element size).  The int16 layout the call describes the reads with is built here; one synchronisation."""
+        samples * element size).  The int16 layout the call describes the reads with is built here; one synchronisation.  norm / norm_out:
+        as for decompress_signal (vbz_gpu_decompress_chunks_norm_batch)."""
         n = int(src_off.numel())
         assert int(samples.numel()) == n
         ch = self._chunking(chunk_len, step, mode, end_align, pad)
@@ -373,11 +452,11 @@ class GpuCodec:
         chunk_first, chunk_info, host = self._chunk_tables(samples, ch, True, also=dst_off[-1])
         chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
         self._decode_chunks(src, src_off, src_size, dst_off[:n], dst_cap, host[1], result, opts, False, ch, chunk_first, chunks, dtype, scale, offset,
-                            signed)
+                            signed, norm, norm_out)
         return chunks, chunk_first, chunk_info
 
     def decompress_packed_chunks(self, packed, packed_off, packed_size, opts, chunk_len, step, mode="pad", end_align=1, pad=0.0, dtype=torch.float16,
-                                 scale=None, offset=None, signed=True):
+                                 scale=None, offset=None, signed=True, norm=None, norm_out=None):
         """decompress_packed into model-input chunks (decompress_chunks): the sample counts come from the headers (decompressed_sizes),
         then the layout and the decode -> (chunks, chunk_first, chunk_info, result).  One synchronisation."""
         n = int(packed_size.numel())
@@ -391,7 +470,7 @@ class GpuCodec:
         chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
         result = torch.empty(n, dtype=torch.int32, device=self.device)
         self._decode_chunks(packed, src_off, packed_size, raw_off[:n], raw, host[1], result, opts, True, ch, chunk_first, chunks, dtype, scale, offset,
-                            signed)
+                            signed, norm, norm_out)
         return chunks, chunk_first, chunk_info, result
 
     # -- synthetic workload ----------------------------------------------------------

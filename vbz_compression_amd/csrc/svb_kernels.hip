@@ -312,6 +312,244 @@ __device__ __forceinline__ void chunk_pad(const ChunkK& ck)
     for (uint32_t j = ((ck.T - ck.last + 7u) >> 3) + threadIdx.x; j < (ck.L >> 3); j += WG) chunk_put8<OUT>(row + (size_t)j * 8u * OB, e);
 }
 
+// ---- normalisation statistics (OUT = SIG_COUNT; vbz_kernels.h NormRead) -------------------------------------------------------------
+// The counting pass histograms a read's keys into the windows of its NormRead in LDS; the select turns the counts into ranks.  A read on
+// one workgroup is selected at the end of its pass with the counts still in LDS; on the large-read path every segment adds its counts to
+// the read's slab (no-return atomics) and norm_select_kernel selects from there in a launch of its own.
+struct NormLds
+{
+    uint32_t h[NORM_WINDOWS * NORM_BINS];   // the windows' bins (the select turns each window into its inclusive prefix sums)
+    uint32_t below[NORM_WINDOWS];           // keys below each window (anchored: below window 0 only)
+    uint32_t tot[NORM_WINDOWS];             // keys in each window
+    uint32_t az[2 * NORM_WINDOWS];          // the targets' new brackets
+};
+__device__ __forceinline__ NormLds* norm_lds()
+{
+    __shared__ __attribute__((aligned(16))) NormLds L;
+    return &L;
+}
+
+// the smallest x in [lo, hi] with pred(x), pred monotone and true at hi: 64 candidates a round, every lane of the wave (wave-uniform)
+template <class P>
+__device__ __forceinline__ uint32_t wave_search(uint32_t lo, uint32_t hi, P pred)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    while (lo < hi) {
+        const uint32_t step = (hi - lo + 64u) >> 6;
+        const uint32_t e0 = lo + (lane + 1u) * step - 1u, e = e0 < hi ? e0 : hi;
+        const uint64_t m = __ballot(pred(e) ? 1 : 0);
+        const uint32_t f = m ? (uint32_t)__ffsll((unsigned long long)m) - 1u : 63u;   // (m == 0 only if the caller's promise fails)
+        const uint32_t nhi = lo + (f + 1u) * step - 1u;
+        lo += f * step;
+        hi = nhi < hi ? nhi : hi;
+    }
+    return lo;
+}
+
+// the ranks (0-based, in sorted order) whose values a stage wants: MED_MAD the two middle ones (both stages); QUANTILE floor(q (T - 1))
+// and the one above it, for both quantiles.  T >= 1.
+__device__ __forceinline__ double norm_h(float q, uint32_t T) { return __dmul_rn((double)q, (double)(T - 1u)); }
+__device__ __forceinline__ void norm_ranks(const NormOut& no, uint32_t T, uint32_t R[NORM_WINDOWS])
+{
+    if (no.method == NORM_MED_MAD) {
+        R[0] = (T - 1u) >> 1;
+        R[1] = R[2] = R[3] = T >> 1;
+    } else {
+        const uint32_t ja = (uint32_t)floor(norm_h(no.qa, T)), jb = (uint32_t)floor(norm_h(no.qb, T));
+        R[0] = ja;
+        R[1] = ja + 1u < T ? ja + 1u : T - 1u;
+        R[2] = jb;
+        R[3] = jb + 1u < T ? jb + 1u : T - 1u;
+    }
+}
+
+// numpy's quantile (method "linear") from the two values around rank h = q (T - 1), in float64 without contraction
+__device__ __forceinline__ double norm_quantile(float q, uint32_t T, double a, double b)
+{
+    const double h = norm_h(q, T), t = __dsub_rn(h, floor(h)), d = __dsub_rn(b, a);
+    return t < 0.5 ? __dadd_rn(a, __dmul_rn(d, t)) : __dsub_rn(b, __dmul_rn(d, __dsub_rn(1.0, t)));
+}
+
+// c, w -> shift = max(shift_min, shift_mul c), scale = max(scale_min, scale_mul w) (float64, rounded once to float32); the store's
+// constants {-shift, float32(1 / float64(scale))}
+__device__ __forceinline__ void norm_finish(const ReadBatch& b, uint32_t r, double c, double w)
+{
+    const NormOut& no = b.sig.norm;
+    const double sd = fmax((double)no.shift_min, __dmul_rn((double)no.shift_mul, c));
+    const double kd = fmax((double)no.scale_min, __dmul_rn((double)no.scale_mul, w));
+    const float shift = __double2float_rn(sd), scale = __double2float_rn(kd);
+    const_cast<float2*>(b.sig.cal)[r] = make_float2(-shift, __double2float_rn(__ddiv_rn(1.0, (double)scale)));
+    no.ss[no.map ? no.map[r] : r] = make_float2(shift, scale);
+}
+
+// the windows of the next pass: one per unresolved bracket (equal brackets share one), wide enough to hold it whole
+__device__ __forceinline__ void norm_windows(NormRead* sp, const uint32_t A[NORM_WINDOWS], const uint32_t Z[NORM_WINDOWS])
+{
+#pragma unroll
+    for (int t = 0; t < (int)NORM_WINDOWS; ++t) {
+        bool off = A[t] == Z[t];
+#pragma unroll
+        for (int v = 0; v < t; ++v) off = off || (A[v] == A[t] && Z[v] == Z[t]);
+        uint32_t s = 0;
+        while ((NORM_BINS << s) < Z[t] - A[t] + 1u) ++s;
+        sp->lo[t] = A[t];
+        sp->sh[t] = off ? NORM_OFF : s;
+        sp->a[t] = A[t];
+        sp->z[t] = Z[t];
+    }
+    sp->anchored = 0;
+}
+
+// The select, by the whole workgroup, from the counts of read r (T >= 1 values) in L: every target's bracket is narrowed; when all are
+// found the stage ends (the value stage of MED_MAD hands over to the MAD's, which the first pass's adjacent windows often answer at once),
+// and the read's constants are written.  L->h is overwritten.  xoff: key - value (0x8000 for int16, 0 for uint16).
+__device__ __forceinline__ void norm_select(NormLds* L, const ReadBatch& b, uint32_t r, uint32_t T, uint32_t xoff)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const NormOut& no = b.sig.norm;
+    NormRead* sp = no.st + r;
+    {   // wave w: the inclusive prefix sums of window w, in place
+        uint32_t* h = L->h + wv * NORM_BINS + lane * 16;
+        uint32_t v[16];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint4 q = *reinterpret_cast<const uint4*>(h + 4 * j);
+            v[4 * j] = q.x;
+            v[4 * j + 1] = q.y;
+            v[4 * j + 2] = q.z;
+            v[4 * j + 3] = q.w;
+        }
+        uint32_t sum = 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) sum += v[j];
+        const uint32_t inc = wave_incl_scan_u32(sum);
+        uint32_t run = inc - sum;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            run += v[j];
+            v[j] = run;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<uint4*>(h + 4 * j) = make_uint4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+        if (lane == 63) L->tot[wv] = inc;
+    }
+    wg_lds_barrier();
+    const uint32_t phase = sp->phase, anchored = sp->anchored;
+    uint32_t lo[NORM_WINDOWS], sh[NORM_WINDOWS], below[NORM_WINDOWS], cum[NORM_WINDOWS], R[NORM_WINDOWS];
+    uint32_t c = 0;
+#pragma unroll
+    for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
+        lo[w] = sp->lo[w];
+        sh[w] = sp->sh[w];
+        cum[w] = c;   // (anchored: keys in the windows before w)
+        below[w] = anchored ? L->below[0] + c : L->below[w];
+        c += L->tot[w];
+    }
+    norm_ranks(no, T, R);
+    {   // wave t: target t
+        const int t = wv;
+        uint32_t a = sp->a[t], z = sp->z[t];
+        if (a != z) {
+#pragma unroll
+            for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
+                if (sh[w] == NORM_OFF) continue;
+                const uint32_t B = below[w], tw = L->tot[w], end = lo[w] + (NORM_BINS << sh[w]);
+                if (R[t] >= B && R[t] - B < tw) {   // in window w: the bin where the prefix sums pass the rank
+                    const uint32_t g = R[t] - B;
+                    const uint32_t* P = L->h + w * NORM_BINS;
+                    const uint32_t bin = wave_search(0u, NORM_BINS - 1u, [&](uint32_t x) { return P[x] > g; });
+                    const uint32_t a1 = lo[w] + (bin << sh[w]), z1 = a1 + (1u << sh[w]) - 1u;
+                    a = a1 > a ? a1 : a;
+                    z = z1 < z ? z1 : z;
+                    break;
+                }
+                if (R[t] < B) {
+                    if (lo[w] != 0 && lo[w] - 1u < z) z = lo[w] - 1u;
+                } else if (end > a) {
+                    a = end;
+                }
+            }
+            if (a > z) a = z;   // (only a stream whose counts disagree with its length comes here: it gets an error verdict)
+        }
+        if (lane == 0) {
+            L->az[t] = a;
+            L->az[NORM_WINDOWS + t] = z;
+        }
+    }
+    wg_lds_barrier();
+    if (wv != 0) return;
+    uint32_t A[NORM_WINDOWS], Z[NORM_WINDOWS];
+    bool all = true;
+#pragma unroll
+    for (int t = 0; t < (int)NORM_WINDOWS; ++t) {
+        A[t] = L->az[t];
+        Z[t] = L->az[NORM_WINDOWS + t];
+        all = all && A[t] == Z[t];
+    }
+    auto x = [&](uint32_t u) { return (double)((int32_t)u - (int32_t)xoff); };
+    if (!all) {
+        if (lane == 0) norm_windows(sp, A, Z);
+        return;
+    }
+    if (phase == NORM_DEV) {   // |x - c| = d / 2: the MAD is (d0 + d1) / 4, exactly
+        if (lane == 0) {
+            norm_finish(b, r, (double)((int32_t)(sp->c2) - 2 * (int32_t)xoff) * 0.5, (double)(A[0] + A[1]) * 0.25);
+            sp->phase = NORM_DONE;
+        }
+        return;
+    }
+    if (no.method == NORM_QUANTILE) {
+        if (lane == 0) {
+            const double qa = norm_quantile(no.qa, T, x(A[0]), x(A[1])), qb = norm_quantile(no.qb, T, x(A[2]), x(A[3]));
+            norm_finish(b, r, __dadd_rn(qa, qb), __dsub_rn(qb, qa));
+            sp->phase = NORM_DONE;
+        }
+        return;
+    }
+    // MED_MAD: the median is known; the MAD's ranks of d = |2u - c2| straight from the first pass's 4 x NORM_BINS adjacent keys, when
+    // the band they need lies inside them
+    const uint32_t c2 = A[0] + A[1];
+    if (anchored && c2 >= 2u * lo[0] && c2 <= 2u * (lo[0] + NORM_WINDOWS * NORM_BINS - 1u)) {   // (always so, unless counts disagree)
+        const uint32_t L0 = lo[0], Dmax = min(c2 - 2u * L0, 2u * L0 + 2u * NORM_WINDOWS * NORM_BINS - 1u - c2);
+        auto G = [&](uint32_t u) -> uint32_t {   // keys <= u, for u in [L0 - 1, L0 + 4095]
+            if (u + 1u == L0) return below[0];
+            const uint32_t i = u - L0, w = i / NORM_BINS;
+            return below[0] + cum[w] + L->h[i];
+        };
+        auto cnt = [&](uint32_t D) { return G((c2 + D) >> 1) - G(((c2 - D + 1u) >> 1) - 1u); };   // deviations d <= D
+        if (cnt(Dmax) > R[1]) {
+            const uint32_t d0 = wave_search(0u, Dmax, [&](uint32_t D) { return cnt(D) > R[0]; });
+            const uint32_t d1 = wave_search(0u, Dmax, [&](uint32_t D) { return cnt(D) > R[1]; });
+            if (lane == 0) {
+                norm_finish(b, r, __dadd_rn(x(A[0]), x(A[1])) * 0.5, (double)(d0 + d1) * 0.25);
+                sp->phase = NORM_DONE;
+            }
+            return;
+        }
+    }
+    if (lane == 0) {
+        uint32_t A2[NORM_WINDOWS], Z2[NORM_WINDOWS];
+#pragma unroll
+        for (int t = 0; t < (int)NORM_WINDOWS; ++t) {
+            A2[t] = 0;
+            Z2[t] = 2u * 0xFFFFu;
+        }
+        norm_windows(sp, A2, Z2);
+        sp->c2 = c2;
+        sp->phase = NORM_DEV;
+    }
+}
+
+// the counting store's state: the read's windows (workgroup-uniform) and this lane's counts of keys below them
+struct NormK
+{
+    NormLds* L = nullptr;
+    const ReadBatch* b = nullptr;
+    uint32_t r = 0, T = 0, kx = 0, c2 = 0, lo0 = 0;
+    bool dev = false, anchored = false;
+    uint32_t lo[NORM_WINDOWS] = {}, sh[NORM_WINDOWS] = {};
+};
+
 // ---- the decoder's output: what svb_decode_range and I16DecPairs store, where, and in how many bytes per value -----------------------
 // OUT = SIG_NONE: the ELEM-byte values into the read's slot (dst + dst_off[r]).  SIG_*: the typed samples of int16 values into the read's
 // typed slot (dst + dst_off[r] / 2 * E: dst_off is the int16 layout's).  SIG_* | SIG_CHUNK: the typed samples into the read's chunks.
@@ -324,6 +562,8 @@ struct DecStore
     uint8_t* out;   // the read's slot (the chunk store: the 16-byte aligned chunk arena)
     SigK sk;
     ChunkK ck;
+    NormK nk;                                    // SIG_COUNT
+    mutable uint32_t nbelow[NORM_WINDOWS] = {};  // SIG_COUNT: this lane's keys below each window
 
     // b: the batch, for the typed stores only -- SIG_NONE gets nullptr and the batch's fields (a reference to the kernel's ReadBatch
     // argument would cost its loads their scalar form)
@@ -331,6 +571,27 @@ struct DecStore
     {
         if (OUT == SIG_NONE) {
             out = dst + dst_off[r];
+        } else if (OUT == SIG_COUNT) {   // (all threads of the workgroup: the bins are zeroed here)
+            out = nullptr;
+            const NormRead* sp = b->sig.norm.st + r;
+            nk.L = norm_lds();
+            nk.b = b;
+            nk.r = r;
+            nk.T = count;
+            nk.kx = b->sig.bias ^ 0x8000u;
+            nk.dev = sp->phase == NORM_DEV;
+            nk.anchored = sp->anchored != 0;
+            nk.c2 = sp->c2;
+#pragma unroll
+            for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
+                nk.lo[w] = sp->lo[w];
+                nk.sh[w] = sp->sh[w];
+            }
+            nk.lo0 = nk.lo[0];
+            uint4* h = reinterpret_cast<uint4*>(nk.L->h);
+            for (uint32_t i = threadIdx.x; i < NORM_WINDOWS * NORM_BINS / 4; i += WG) h[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (threadIdx.x < NORM_WINDOWS) nk.L->below[threadIdx.x] = 0;
+            __syncthreads();
         } else if (OUT & SIG_CHUNK) {
             out = dst;
             ck = chunk_constants<OUT>(*b, r, count);
@@ -341,13 +602,33 @@ struct DecStore
         }
     }
 
-    // whole 16-byte lines may be stored: the tile loop's lanes of VPL values, and I16DecPairs at all
+    // whole 16-byte lines may be stored: the tile loop's lanes of VPL values, and I16DecPairs at all (the counting pass stores nothing)
     __device__ __forceinline__ bool aligned() const { return (((uintptr_t)out) & 15u) == 0; }
 
     // one lane's values i0 ... i0 + valid - 1 (base + s[k]).  The chunk store takes every lane of the workgroup at the same point.
     __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[VPL]) const
     {
-        if (OUT & SIG_CHUNK) {
+        if (OUT == SIG_COUNT) {   // one LDS increment per value: its key's bin
+#pragma unroll
+            for (int k = 0; k < VPL; ++k) {
+                if (k >= valid) continue;
+                const uint32_t u = ((base + s[k]) ^ nk.kx) & 0xFFFFu;
+                const uint32_t key = nk.dev ? (uint32_t)abs((int32_t)(2u * u) - (int32_t)nk.c2) : u;
+                if (nk.anchored) {   // four adjacent windows of width 1
+                    const uint32_t d = key - nk.lo0;
+                    if (d < NORM_WINDOWS * NORM_BINS) atomicAdd(&nk.L->h[d], 1u);
+                    else if (key < nk.lo0) ++nbelow[0];
+                } else {
+#pragma unroll
+                    for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
+                        if (nk.sh[w] == NORM_OFF) continue;
+                        const uint32_t d = key - nk.lo[w];
+                        if ((d >> nk.sh[w]) < NORM_BINS) atomicAdd(&nk.L->h[w * NORM_BINS + (d >> nk.sh[w])], 1u);
+                        else if (key < nk.lo[w]) ++nbelow[w];
+                    }
+                }
+            }
+        } else if (OUT & SIG_CHUNK) {
             chunk_store8<OUT>(ck, i0, valid, base, s, sk);
         } else if (OUT != SIG_NONE) {
             if (valid == VPL && aligned()) {
@@ -390,6 +671,31 @@ struct DecStore
     __device__ __forceinline__ void finish() const
     {
         if (OUT & SIG_CHUNK) chunk_pad<OUT>(ck);
+    }
+
+    // after this workgroup's values (svb_decode_range, MODE 0), by the whole workgroup: the counting pass's counts are complete -- a read
+    // on one workgroup is selected from LDS, a segment of the large-read path adds them to the read's slab
+    __device__ __forceinline__ void done() const
+    {
+        if (OUT != SIG_COUNT) return;
+        const int lane = threadIdx.x & 63;
+#pragma unroll
+        for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
+            const uint32_t t = wave_incl_scan_u32(nbelow[w]);
+            if (lane == 63 && t != 0) atomicAdd(&nk.L->below[w], t);
+        }
+        __syncthreads();
+        const NormOut& no = nk.b->sig.norm;
+        if (no.slab) {
+            uint32_t* slab = no.slab + (size_t)nk.r * NORM_SLAB;
+            for (uint32_t i = threadIdx.x; i < NORM_WINDOWS * NORM_BINS; i += WG) {
+                const uint32_t v = nk.L->h[i];
+                if (v) atomicAdd(slab + i, v);
+            }
+            if (threadIdx.x < NORM_WINDOWS && nk.L->below[threadIdx.x]) atomicAdd(slab + NORM_WINDOWS * NORM_BINS + threadIdx.x, nk.L->below[threadIdx.x]);
+        } else {
+            norm_select(nk.L, *nk.b, nk.r, nk.T, nk.kx);
+        }
     }
 };
 
@@ -1419,6 +1725,7 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
         pos += tot;
     }
     if (MODE == 0 && first == 0) st.finish();   // (the read's first range: the whole read, or its first segment)
+    if (MODE == 0) st.done();
     pos_io = pos;
     run_io = run;
     return good;
@@ -1452,6 +1759,7 @@ __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBa
         if (tid == 0) b.result[r] = res;
         return;
     }
+    if (OUT == SIG_COUNT && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
     const uint32_t count = out_size / ELEM;
     const uint32_t keyLen = (count + 3u) >> 2;
     const uint8_t* in = b.src + b.src_off[r];
@@ -1513,6 +1821,7 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
     if (SELF) {
         if (MODE != 1 && self_total != (uint64_t)(in_size - ((out_size / ELEM + 3u) >> 2))) return;   // the stream is malformed
     } else if (MODE != 1 && b.result[r] >= E_FIRST) return;  // the scan found the stream malformed
+    if (OUT == SIG_COUNT && b.sig.norm.st[r].phase == NORM_DONE) return;
     const uint32_t count = out_size / ELEM;
     const uint32_t keyLen = (count + 3u) >> 2;
     const uint32_t first = k * (uint32_t)SEG;
@@ -1782,6 +2091,72 @@ __global__ __launch_bounds__(WG) void svb_half_decode_kernel(ReadBatch b)
     if (tid == 0) b.result[r] = (bad || ((posn + 1u) >> 1) != dataBytes) ? E_STREAM : count;
 }
 
+// ---- normalising decode: the reads' starting windows, and the select of the large-read path --------------------------------------------
+// One thread per read: the first pass's windows are NORM_WINDOWS x NORM_BINS adjacent keys around the read's first sample, which the
+// stream's first control and data bytes give (any anchor gives the same statistics; a good one saves the later passes).  A read of no
+// samples is finished here (c = w = 0).
+__global__ __launch_bounds__(WG) void norm_init_kernel(ReadBatch b, uint32_t zigzag)
+{
+    const uint32_t r = blockIdx.x * WG + threadIdx.x;
+    if (r >= b.n_reads || (b.gate && b.gate[r] >= GATE_SKIP)) return;
+    const uint32_t in_size = b.src_size[r], out_size = b.dst_cap[r];
+    if (in_size >= E_FIRST || (out_size & 1u)) return;
+    const uint32_t T = out_size >> 1, keyLen = (T + 3u) >> 2;
+    NormRead* sp = b.sig.norm.st + r;
+    if (T == 0) {
+        norm_finish(b, r, 0.0, 0.0);
+        sp->phase = NORM_DONE;
+        return;
+    }
+    uint32_t a = 0x8000u;
+    if (in_size >= keyLen + 2u) {
+        const uint8_t* in = b.src + b.src_off[r];
+        uint32_t v = in[keyLen] | ((in[0] & 3u) ? (uint32_t)in[keyLen + 1] << 8 : 0u);
+        if (zigzag) v = (v >> 1) ^ (0u - (v & 1u));
+        a = (v ^ b.sig.bias ^ 0x8000u) & 0xFFFFu;
+    }
+    constexpr uint32_t SPAN = NORM_WINDOWS * NORM_BINS;
+    uint32_t L0 = a < SPAN / 2 ? 0u : a - SPAN / 2;
+    if (L0 > 0x10000u - SPAN) L0 = 0x10000u - SPAN;
+    sp->phase = NORM_VALUE;
+    sp->c2 = 0;
+    sp->anchored = 1;
+#pragma unroll
+    for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
+        sp->lo[w] = L0 + (uint32_t)w * NORM_BINS;
+        sp->sh[w] = 0;
+        sp->a[w] = 0;
+        sp->z[w] = 0xFFFFu;
+    }
+}
+
+// one workgroup per read: the counts the segments added to the read's slab (zeroed again for the next pass) -> the select
+__global__ __launch_bounds__(WG) void norm_select_kernel(ReadBatch b)
+{
+    const uint32_t r = blockIdx.x;
+    if (b.gate && b.gate[r] >= GATE_SKIP) return;
+    const uint32_t in_size = b.src_size[r], out_size = b.dst_cap[r];
+    if (in_size >= E_FIRST || (out_size & 1u) || out_size == 0 || b.sig.norm.st[r].phase == NORM_DONE) return;
+    NormLds* L = norm_lds();
+    uint32_t* slab = b.sig.norm.slab + (size_t)r * NORM_SLAB;
+    for (uint32_t i = threadIdx.x; i < NORM_WINDOWS * NORM_BINS; i += WG) {
+        L->h[i] = slab[i];
+        slab[i] = 0;
+    }
+    if (threadIdx.x < NORM_WINDOWS) {
+        L->below[threadIdx.x] = slab[NORM_WINDOWS * NORM_BINS + threadIdx.x];
+        slab[NORM_WINDOWS * NORM_BINS + threadIdx.x] = 0;
+    }
+    __syncthreads();
+    norm_select(L, b, r, out_size >> 1, b.sig.bias ^ 0x8000u);
+}
+
+hipError_t launch_norm_init(const ReadBatch& b, bool zigzag, hipStream_t s)
+{
+    hipLaunchKernelGGL(norm_init_kernel, dim3((b.n_reads + WG - 1) / WG), dim3(WG), 0, s, b, zigzag ? 1u : 0u);
+    return hipGetLastError();
+}
+
 template <typename K>
 hipError_t launch1(K kernel, const ReadBatch& b, hipStream_t s)
 {
@@ -1811,18 +2186,29 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
                                    uint32_t* seg_run, hipStream_t s)
 {
     const dim3 segs(max_segs), reads(b.n_reads), t(WG);
+    const bool self = max_segs <= seg_self_max();
     hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 1>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    if (max_segs <= seg_self_max()) {
+    if (self) {
         if (Z) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-        hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
     } else {
         hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, true, DecStore<E, OUT>::BYTES>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
         if (Z) {
             hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
             hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, false>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
         }
-        hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
     }
+    if constexpr (E == 2) {
+        if (b.sig.norm.st) {   // the counting passes at the storing pass's positions, each behind a select launch
+            for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p) {
+                if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, SIG_COUNT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+                else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, SIG_COUNT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+                hipLaunchKernelGGL(norm_select_kernel, reads, t, 0, s, b);
+            }
+            if (b.sig.type == SIG_NONE) return hipGetLastError();   // (the statistics only)
+        }
+    }
+    if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
     return hipGetLastError();
 }
 
@@ -1894,6 +2280,13 @@ hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, 
         if (integer_size != 1 || b.sig.type != SIG_NONE) return hipErrorInvalidValue;
         return zigzag ? launch1(svb_half_decode_kernel<true>, b, s) : launch1(svb_half_decode_kernel<false>, b, s);
     }
+    if (b.sig.norm.st) {   // the counting passes (each selects at its end), then the store -- none for the statistics alone
+        if (integer_size != 2) return hipErrorInvalidValue;
+        if (b.n_reads == 0) return hipSuccess;
+        hipError_t e = launch_norm_init(b, zigzag, s);
+        for (uint32_t p = 0; e == hipSuccess && p < norm_passes(b.sig.norm.method); ++p) e = svb_decode_launch<SIG_COUNT>(b, 2, zigzag, s);
+        if (e != hipSuccess || b.sig.type == SIG_NONE) return e;
+    }
     switch (svb_decode_out(b)) {
     case SIG_NONE: return svb_decode_launch<SIG_NONE>(b, integer_size, zigzag, s);
     case SIG_F32: return svb_decode_launch<SIG_F32>(b, integer_size, zigzag, s);
@@ -1946,6 +2339,12 @@ hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigz
                                  uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
+    if (b.sig.norm.st) {
+        if (integer_size != 2 || !b.sig.norm.slab) return hipErrorInvalidValue;
+        (void)hipMemsetAsync(b.sig.norm.slab, 0, 4ull * NORM_SLAB * b.n_reads, s);
+        const hipError_t e = launch_norm_init(b, zigzag, s);
+        if (e != hipSuccess) return e;
+    }
 #define X(O) return svb_decode_seg_launch<O>(b, integer_size, zigzag, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
     switch (svb_decode_out(b)) {
     case SIG_NONE: X(SIG_NONE);

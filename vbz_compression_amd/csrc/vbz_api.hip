@@ -5,6 +5,7 @@
 // HIP kernels; there is no CPU implementation of either stage in this library.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -107,6 +108,8 @@ struct vbz_gpu_ctx
     DevBuf cksum;              // the hashes of a compress launch group (8 bytes per read)
     DevBuf sigmeta;            // typed decode: the int16 slot table and the per-read constants (signal_slots)
     DevBuf chunkmeta;          // chunk layout: the per-read chunk counts
+    DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call
+    DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
     bool zero_run_sequences = true;
     bool fuse_svb = false;     // VBZ_HIP_FUSE_SVB=1: the frame's wavefront decodes the svb stream too (measured slower: DESIGN.md 4.4)
@@ -694,6 +697,10 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
         return 0;
     }
     SegTables seg;
+    if (rb.sig.norm.st && segmented) {   // (a normalising decode on the large-read path: the segments' counts add up here)
+        if (!ensure(c, c->normslab, (size_t)n * NORM_SLAB * 4)) return -1;
+        rb.sig.norm.slab = reinterpret_cast<uint32_t*>(c->normslab.p);
+    }
     // (both stages: the scratch slots are planned with the segments when they can be -- two launches less for a call of few reads)
     const bool both_stages = o->integer_size != 0 && o->zstd_compression_level != 0;
     uint32_t num = 1, den = 1;
@@ -756,7 +763,7 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     // svb stream it has just written while it is still in the caches, straight into the destination, and there is no
     // svb_decode launch (measured slower than the separate launch: profiles/r03_fused_svb_decode.md; it does not verify content checksums)
 #ifdef VBZ_EXPERIMENTS
-    if (!segmented && !dbg && c->fuse_svb && o->integer_size == 2 && o->perform_delta_zig_zag && rb.sig.type == SIG_NONE) {   // (no typed store)
+    if (!segmented && !dbg && c->fuse_svb && o->integer_size == 2 && o->perform_delta_zig_zag && rb.sig.type == SIG_NONE && !rb.sig.norm.st) {   // (no typed store)
         z.result = rb.result;
         Timed t(c, "zstd_decode");  // (zstd_decode_kernel<false, true>: the frame and its svb stream)
         HIPCHK(c, launch_zstd_decode_svb_i16zz(z, E_STREAM, c->seqdtab.p, rb.dst, rb.dst_off, rb.dst_cap, s), "zstd_decode + svb_decode launch");
@@ -860,7 +867,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
 {
     const uint32_t n = rb.n_reads;
     if (ensure_large(c) != 0) return -1;
-    if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * 64 + route_cand_words() * 4 + 512)) return -1;
+    if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * (64 + sizeof(NormRead)) + route_cand_words() * 4 + 512)) return -1;
     MetaCarver mc(c->route.p);
     r->gate_small = mc.take<uint32_t>(n);
     uint64_t* l_src_off = mc.take<uint64_t>(ROUTE_MAX_READS);
@@ -872,6 +879,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     r->map = mc.take<uint32_t>(ROUTE_MAX_READS);
     float2* l_cal = mc.take<float2>(ROUTE_MAX_READS);
     uint64_t* l_row = mc.take<uint64_t>(ROUTE_MAX_READS);
+    NormRead* l_norm = mc.take<NormRead>(ROUTE_MAX_READS);
     r->count = mc.take<uint32_t>(4);
     uint32_t* cand = mc.take<uint32_t>(route_cand_words());
     r->large = rb;
@@ -884,6 +892,10 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     r->large.result = l_result;
     if (rb.sig.cal) r->large.sig.cal = l_cal;   // (the routed reads' constants, gathered through the map)
     if (rb.sig.row) r->large.sig.row = l_row;   // (and their first chunk rows)
+    if (rb.sig.norm.st) {   // (a normalising decode: states of their own; shift_scale written back through the map)
+        r->large.sig.norm.st = l_norm;
+        r->large.sig.norm.map = r->map;
+    }
     Timed t(c, "route");
     HIPCHK(c, launch_route_reads(rb, raw_size, ROUTE_MIN_BYTES, ROUTE_MAX_READS, ROUTE_MAX_BYTES, r->gate_small, l_src_off, l_src_size, l_dst_off, l_dst_cap,
                                  l_gate, r->map, l_cal, l_row, r->count, cand, c->stream),
@@ -988,6 +1000,10 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
     if (u.gate) u.gate += h;
     if (u.sig.cal) u.sig.cal += h;
     if (u.sig.row) u.sig.row += h;
+    if (u.sig.norm.st) {
+        u.sig.norm.st += h;
+        u.sig.norm.ss += h;
+    }
     return u;
 }
 
@@ -1177,7 +1193,9 @@ int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_f
 // sized headers, scratch plan, routing and the split are the int16 call's; rb.dst becomes the chunk arena and the svb stage stores the
 // typed samples into the reads' chunks (rb.sig.row: chunk_first, untrusted -- chunk_slots gates every read whose entries are not exactly
 // its chunks before anything of it is decoded).
-// TypedOut: what a typed decode stores -- f the samples' format; ch != nullptr: a chunk decode into `chunks`.
+// TypedOut: what a typed decode stores -- f the samples' format; ch != nullptr: a chunk decode into `chunks`.  norm != nullptr: a
+// normalising decode (the constants from the reads' statistics, into cal and shift_scale); with f->out_type == SIG_NONE the statistics
+// alone (the int16 layout, nothing stored).
 struct TypedOut
 {
     const vbz_gpu_signal_format* f;
@@ -1185,6 +1203,8 @@ struct TypedOut
     const uint64_t* chunk_first = nullptr;
     void* chunks = nullptr;
     uint64_t chunk_rows = 0;
+    const vbz_gpu_normalization* norm = nullptr;
+    float* shift_scale = nullptr;
 };
 
 // out (nullable): a typed decode (signal_slots) or a chunk decode (out->ch)
@@ -1201,7 +1221,10 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     uint64_t dst_bytes = bt->dst_bytes;
     const bool chunks = out && out->ch;
     float2* cal = nullptr;   // the per-read constants (a chunk decode: chunk_slots fills them in)
-    if (chunks) {
+    if (out && out->f->out_type == SIG_NONE) {   // (the statistics alone: the constants' table is the selects' only)
+        if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
+        cal = reinterpret_cast<float2*>(c->sigmeta.p);
+    } else if (chunks) {
         if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
         cal = reinterpret_cast<float2*>(c->sigmeta.p);
         rb.dst = (uint8_t*)out->chunks;
@@ -1218,6 +1241,21 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         rb.sig.cal = cal;
         rb.sig.type = out->f->out_type;
         rb.sig.bias = out->f->is_signed ? 0u : 0x8000u;
+    }
+    if (out && out->norm) {
+        if (!ensure(c, c->normmeta, (size_t)n * (sizeof(NormRead) + 8) + 256)) return -1;
+        MetaCarver mc(c->normmeta.p);
+        NormOut& no = rb.sig.norm;
+        no.st = mc.take<NormRead>(n);
+        float2* ss = mc.take<float2>(n);   // (the caller passed no shift_scale: a table of the call's own)
+        no.ss = out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : ss;
+        no.method = out->norm->method;
+        no.qa = out->norm->quantile_a;
+        no.qb = out->norm->quantile_b;
+        no.shift_mul = out->norm->shift_mul;
+        no.scale_mul = out->norm->scale_mul;
+        no.shift_min = out->norm->shift_min;
+        no.scale_min = out->norm->scale_min;
     }
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
         if (!ensure(c, c->meta, (size_t)n * 24 + 512)) return -1;
@@ -1371,7 +1409,7 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
         (void)hipEventDestroy(p.stop);
     }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta })
+    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta, &c->normmeta, &c->normslab })
         if (b->p) (void)hipFree(b->p);
     if (c->large) vbz_gpu_destroy(c->large);
     if (c->half) vbz_gpu_destroy(c->half);
@@ -1483,12 +1521,11 @@ int vbz_gpu_chunk_layout_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* sampl
     return 0;
 }
 
-int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
-                                    const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows)
+// the chunk call's own checks and the call (typed_args_ok has passed); norm: a normalising chunk decode
+static int chunks_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                       const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows, const vbz_gpu_normalization* norm,
+                       float* shift_scale)
 {
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, f, "chunk")) return -2;
     if (!chunking_ok(c, ch)) return -2;
     if (bt->n_reads != 0 && (!chunk_first || !chunks)) {
         set_error(c, "chunk_first or the chunk arena is NULL");
@@ -1506,8 +1543,87 @@ int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
     vbz_gpu_batch b = *bt;   // (batch->dst is not used: the svb stage stores into the chunk arena)
     b.dst = chunks;
     if (!plausible_extents(c, &b)) return -2;
-    const TypedOut out = { f, ch, chunk_first, chunks, chunk_rows };
+    const TypedOut out = { f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale };
     return decompress_batch_impl(c, &b, o, sized, false, &out);
+}
+
+int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                    const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!typed_args_ok(c, o, f, "chunk")) return -2;
+    return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, nullptr, nullptr);
+}
+
+static_assert(NORM_MED_MAD == VBZ_GPU_NORM_MED_MAD && NORM_QUANTILE == VBZ_GPU_NORM_QUANTILE, "the ABI's methods");
+static_assert(sizeof(vbz_gpu_normalization) == 32, "vbz_gpu_normalization is 32 bytes");
+// the normalisation's fields (include/vbz_gpu.h), and a format whose constants the call would ignore
+static bool norm_ok(vbz_gpu_ctx* c, const vbz_gpu_normalization* m, const vbz_gpu_signal_format* f)
+{
+    if (!m) {
+        set_error(c, "normalization is NULL");
+        return false;
+    }
+    const bool fin = std::isfinite(m->shift_mul) && std::isfinite(m->scale_mul) && (std::isfinite(m->shift_min) || m->shift_min == -INFINITY);
+    const bool q = m->method == VBZ_GPU_NORM_MED_MAD ? m->quantile_a == 0.0f && m->quantile_b == 0.0f
+                                                      : 0.0f <= m->quantile_a && m->quantile_a <= m->quantile_b && m->quantile_b <= 1.0f;
+    const bool known = m->method == VBZ_GPU_NORM_MED_MAD || m->method == VBZ_GPU_NORM_QUANTILE;
+    if (!known || m->reserved != 0 || !q || !fin || !std::isnormal(m->scale_min) || !(m->scale_min > 0.0f)) {
+        set_error(c, "normalization outside its rules (method %u, reserved %u, quantiles %g / %g, shift_mul %g, scale_mul %g, shift_min %g, scale_min %g)",
+                  m->method, m->reserved, (double)m->quantile_a, (double)m->quantile_b, (double)m->shift_mul, (double)m->scale_mul,
+                  (double)m->shift_min, (double)m->scale_min);
+        return false;
+    }
+    if (f && (f->offset || f->scale)) {
+        set_error(c, "a normalising decode takes no offset or scale table (the statistics give them)");
+        return false;
+    }
+    return true;
+}
+
+int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                              const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
+    const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };   // (what typed_args_ok checks: options, is_signed)
+    if (!typed_args_ok(c, o, &probe, "statistics") || !norm_ok(c, norm, nullptr)) return -2;
+    if (!shift_scale) {
+        set_error(c, "shift_scale is NULL");
+        return -2;
+    }
+    vbz_gpu_batch b = *bt;   // (batch->dst may be NULL: nothing is stored)
+    if (!b.dst) b.dst = shift_scale;
+    if (!plausible_extents(c, &b)) return -2;
+    TypedOut out = { &f };
+    out.norm = norm;
+    out.shift_scale = shift_scale;
+    return decompress_batch_impl(c, bt, o, sized, false, &out);
+}
+
+int vbz_gpu_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                         const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!typed_args_ok(c, o, f, "signal") || !norm_ok(c, norm, f)) return -2;
+    if (!plausible_extents(c, bt)) return -2;
+    TypedOut out = { f };
+    out.norm = norm;
+    out.shift_scale = shift_scale;
+    return decompress_batch_impl(c, bt, o, sized, false, &out);
+}
+
+int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                         const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
+                                         const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!typed_args_ok(c, o, f, "chunk") || !norm_ok(c, norm, f)) return -2;
+    return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale);
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

@@ -28,15 +28,47 @@ constexpr int PHASE_SLOTS = 12;  // per-read cycle counters of the timed kernel 
 // read i is row row[i] + k of a row-major [rows, chunk_len] arena at dst (see chunk_count / chunk_last_start); dst_off is not used.
 constexpr uint32_t SIG_NONE = 0, SIG_F32 = 1, SIG_F16 = 2, SIG_BF16 = 3;
 constexpr uint32_t SIG_CHUNK = 4;   // (or-ed into the chunk store's type: the svb decoder's OUT, the store DecStore<ELEM, OUT> of its kernels)
+constexpr uint32_t SIG_COUNT = 8;   // the svb decoder's counting pass of a normalising decode (OUT only: it stores nothing)
 constexpr uint32_t CHUNK_PAD = 0, CHUNK_END = 1;
+
+// Normalising decode (vbz_gpu_*_norm_batch): every read's {-shift, 1 / scale} are derived on the device from order statistics of its own
+// 16-bit values, written to SignalOut::cal, and the store pass reads them there.  The statistics are found by counting passes of the svb
+// decoder (OUT = SIG_COUNT) over keys: the value's key u = the 16-bit value made monotone (int16: x + 32768; uint16: x), or, for the MAD,
+// d = |2u - c2| (c2 = twice the median in keys).  A pass counts up to NORM_WINDOWS windows of NORM_BINS bins, window w holding the keys
+// [lo[w], lo[w] + NORM_BINS << sh[w]) and a count of the keys below it; after it, the select narrows every wanted rank's bracket [a, z].
+// The first pass's windows are four adjacent ones of width 1 around the read's first sample (NormRead::anchored); every later window
+// covers one unresolved bracket whole, so a bracket shrinks NORM_BINS-fold per pass.
+constexpr uint32_t NORM_MED_MAD = 1, NORM_QUANTILE = 2;   // (= VBZ_GPU_NORM_*)
+constexpr uint32_t NORM_VALUE = 0, NORM_DEV = 1, NORM_DONE = 2;   // NormRead::phase: keys u, keys d, finished
+constexpr uint32_t NORM_WINDOWS = 4, NORM_BINS = 1024, NORM_OFF = 0xFFu;   // sh[w] == NORM_OFF: window w is not counted
+constexpr uint32_t NORM_SLAB = NORM_WINDOWS * NORM_BINS + 8;   // words per read of the large-read path's counts (bins, then below[4])
+struct NormRead
+{
+    uint32_t phase, c2, anchored, pad;
+    uint32_t lo[NORM_WINDOWS], sh[NORM_WINDOWS];   // the next pass's windows
+    uint32_t a[NORM_WINDOWS], z[NORM_WINDOWS];     // target t's key lies in [a[t], z[t]] (a == z: found)
+};
+struct NormOut
+{
+    NormRead* st = nullptr;          // per read, in the batch's read order; non-null: a normalising decode
+    float2* ss = nullptr;            // the caller's shift_scale ({shift, scale}) at map ? map[r] : r
+    const uint32_t* map = nullptr;   // (routed reads: their index in the call's batch)
+    uint32_t* slab = nullptr;        // large-read path: NORM_SLAB words per read the segments add their counts into (zero between passes)
+    uint32_t method = 0;
+    float qa = 0.0f, qb = 0.0f, shift_mul = 0.0f, scale_mul = 0.0f, shift_min = 0.0f, scale_min = 0.0f;
+};
+// counting passes a method may need (the first pass, then <= 2 per stage of keys): every read is finished after them
+inline uint32_t norm_passes(uint32_t method) { return method == NORM_MED_MAD ? 5u : 3u; }
+
 struct SignalOut
 {
-    const float2* cal = nullptr;   // per read {offset, scale}, in the batch's read order
-    uint32_t type = SIG_NONE;
+    const float2* cal = nullptr;   // per read {offset, scale}, in the batch's read order (a normalising decode: its select writes them)
+    uint32_t type = SIG_NONE;      // (a normalising decode with SIG_NONE: the statistics only, no store)
     uint32_t bias = 0;
     const uint64_t* row = nullptr;   // chunk store: per read, its first row (chunk_first), in the batch's read order
     uint32_t chunk_len = 0, step = 0, mode = 0, end_align = 0;
     float pad = 0.0f;
+    NormOut norm;
 };
 
 // the chunking of a read of T samples (include/vbz_gpu.h, vbz_gpu_chunking): K chunks, the last one starting at chunk_last_start
@@ -121,7 +153,9 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
                              void* plans, hipStream_t s);
 bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half);   // does launch_svb_encode(plans) write every read's hist_mode?
 // Decode: b.sig.type != SIG_NONE (integer_size 2 only; launch_svb_decode_seg too) stores the typed samples of SignalOut (OUT = b.sig.type,
-// | SIG_CHUNK with b.sig.row).
+// | SIG_CHUNK with b.sig.row).  b.sig.norm.st (integer_size 2 only; both launchers): the counting passes and their selects run in front of
+// the store and leave every read's constants in b.sig.cal (and b.sig.norm.ss); with b.sig.type == SIG_NONE they are all that runs (the
+// results are the int16 decode's; launch_svb_decode_seg: b.sig.norm.slab must be set).
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
