@@ -272,3 +272,201 @@ def bench_roundtrip(n_reads, threads, min_seconds, opts, u32_count=0, simd=False
     if rc != 0:
         raise RuntimeError("oracle bench failed (%d)" % rc)
     return dict(raw_bytes=out[0], comp_bytes=out[1], best_s=out[2], enc_thread_s=out[3], dec_thread_s=out[4], passes=int(out[5]))
+
+
+# ---- libzstd itself for chosen block layouts (ctypes on libzstd.so.1: the pinned dependency, no header needed) --------------------------
+# A one-shot ZSTD_compress cuts its input into blocks of block_max = min(window, 128 KiB) bytes; a writer that flushes
+# (ZSTD_compressStream2 with ZSTD_e_flush, as streaming writers and libzstd >= 1.5 do) ends a block wherever it flushes.
+BLOCK_MAX = 128 << 10
+ZSTD_c_compressionLevel, ZSTD_c_windowLog, ZSTD_c_checksumFlag = 100, 101, 201
+ZSTD_e_flush, ZSTD_e_end = 1, 2
+
+
+class _ZBuf(ctypes.Structure):   # ZSTD_inBuffer / ZSTD_outBuffer
+    _fields_ = [("ptr", ctypes.c_void_p), ("size", ctypes.c_size_t), ("pos", ctypes.c_size_t)]
+
+
+_zstd = None
+
+
+def libzstd():
+    global _zstd
+    if _zstd is None:
+        L = ctypes.CDLL("libzstd.so.1")
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        L.ZSTD_isError.restype = ctypes.c_uint
+        L.ZSTD_isError.argtypes = [sz]
+        L.ZSTD_compressBound.restype = sz
+        L.ZSTD_compressBound.argtypes = [sz]
+        L.ZSTD_createCCtx.restype = vp
+        L.ZSTD_freeCCtx.argtypes = [vp]
+        L.ZSTD_CCtx_setParameter.restype = sz
+        L.ZSTD_CCtx_setParameter.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+        L.ZSTD_CCtx_setPledgedSrcSize.restype = sz
+        L.ZSTD_CCtx_setPledgedSrcSize.argtypes = [vp, ctypes.c_ulonglong]
+        L.ZSTD_compressStream2.restype = sz
+        L.ZSTD_compressStream2.argtypes = [vp, ctypes.POINTER(_ZBuf), ctypes.POINTER(_ZBuf), ctypes.c_int]
+        L.ZSTD_compress2.restype = sz
+        L.ZSTD_compress2.argtypes = [vp, vp, sz, vp, sz]
+        L.ZSTD_createDCtx.restype = vp
+        L.ZSTD_freeDCtx.argtypes = [vp]
+        L.ZSTD_decompressBegin.restype = sz
+        L.ZSTD_decompressBegin.argtypes = [vp]
+        L.ZSTD_nextSrcSizeToDecompress.restype = sz
+        L.ZSTD_nextSrcSizeToDecompress.argtypes = [vp]
+        L.ZSTD_nextInputType.restype = ctypes.c_int
+        L.ZSTD_nextInputType.argtypes = [vp]
+        L.ZSTD_decompressContinue.restype = sz
+        L.ZSTD_decompressContinue.argtypes = [vp, vp, sz, vp, sz]
+        _zstd = L
+    return _zstd
+
+
+def zstd_compress_cuts(data, cuts=(), level=1, window_log=0, checksum=False):
+    """A libzstd frame of `data` (content size in the header) whose blocks end at every cut -- and wherever libzstd itself ends one:
+    every block_max bytes of a stretch between cuts.  cuts: strictly increasing, each in (0, len(data)).  No cuts: ZSTD_compress2."""
+    a = np.ascontiguousarray(data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)).view(np.uint8).reshape(-1)
+    n = a.nbytes
+    cuts = [int(c) for c in cuts]
+    if any(not 0 < c < n for c in cuts) or any(x >= y for x, y in zip(cuts, cuts[1:])):
+        raise ValueError("cuts must increase strictly inside (0, %d): %s" % (n, cuts))
+    Z = libzstd()
+    cap = Z.ZSTD_compressBound(n) + 64 * (len(cuts) + 1) + 64
+    out = np.zeros(cap, np.uint8)
+    cc = Z.ZSTD_createCCtx()
+    assert cc
+    try:
+        for p, v in ((ZSTD_c_compressionLevel, level), (ZSTD_c_windowLog, window_log), (ZSTD_c_checksumFlag, 1 if checksum else 0)):
+            assert not Z.ZSTD_isError(Z.ZSTD_CCtx_setParameter(cc, p, int(v))), (p, v)
+        assert not Z.ZSTD_isError(Z.ZSTD_CCtx_setPledgedSrcSize(cc, n))
+        src = a.ctypes.data if n else None
+        if not cuts:
+            r = Z.ZSTD_compress2(cc, out.ctypes.data, cap, src, n)
+            assert not Z.ZSTD_isError(r), r
+            return out[:r].copy()
+        ob = _ZBuf(out.ctypes.data, cap, 0)
+        prev = 0
+        for c in cuts + [n]:
+            ib = _ZBuf(src + prev, c - prev, 0)
+            mode = ZSTD_e_flush if c < n else ZSTD_e_end
+            while True:
+                r = Z.ZSTD_compressStream2(cc, ctypes.byref(ob), ctypes.byref(ib), mode)
+                assert not Z.ZSTD_isError(r), r
+                if ib.pos == ib.size and r == 0:
+                    break
+                assert ob.pos < cap
+            prev = c
+        return out[: ob.pos].copy()
+    finally:
+        Z.ZSTD_freeCCtx(cc)
+
+
+def zstd_block_ends(frame, cap):
+    """Where every block of a one-frame buffer ends in the content, by libzstd's bufferless decoder (None: libzstd refuses the frame)."""
+    f = np.ascontiguousarray(frame if isinstance(frame, np.ndarray) else np.frombuffer(bytes(frame), np.uint8))
+    Z = libzstd()
+    out = np.zeros(max(int(cap), 1), np.uint8)
+    dc = Z.ZSTD_createDCtx()
+    assert dc
+    ends, ipos, opos = [], 0, 0
+    try:
+        if Z.ZSTD_isError(Z.ZSTD_decompressBegin(dc)):
+            return None
+        while True:
+            need = Z.ZSTD_nextSrcSizeToDecompress(dc)
+            if need == 0:
+                return ends
+            if ipos + need > len(f):
+                return None
+            kind = Z.ZSTD_nextInputType(dc)   # ZSTDnit_block = 2, ZSTDnit_lastBlock = 3
+            r = Z.ZSTD_decompressContinue(dc, out.ctypes.data + opos, len(out) - opos, f.ctypes.data + ipos, need)
+            if Z.ZSTD_isError(r):
+                return None
+            ipos += need
+            opos += r
+            if kind in (2, 3):
+                ends.append(opos)
+    finally:
+        Z.ZSTD_freeDCtx(dc)
+
+
+def zstd_frame_geometry(frame):
+    """(header bytes, content size, block_max, checksum flag) of a frame with a content size -- RFC 8878 3.1.1.1, as the device reads it."""
+    f = bytes(frame[:18])
+    fhd = f[4]
+    single, fcs_flag = (fhd >> 5) & 1, fhd >> 6
+    pos = 5
+    window = 0
+    if not single:
+        wd = f[pos]
+        pos += 1
+        wlog = 10 + (wd >> 3)
+        window = (1 << wlog) + ((1 << wlog) >> 3) * (wd & 7)
+    pos += (0, 1, 2, 4)[fhd & 3]
+    fsz = (1 if single else 0, 2, 4, 8)[fcs_flag]
+    assert fsz, "no content size"
+    fcs = int.from_bytes(f[pos : pos + fsz], "little") + (256 if fsz == 2 else 0)
+    pos += fsz
+    if single:
+        window = fcs
+    return pos, fcs, min(window, BLOCK_MAX), (fhd >> 2) & 1
+
+
+def ref_literal_units(frame, max_units=4):
+    """A restatement, in outline, of which blocks of a reference-written frame get their literals decoded beside the chain walk (a
+    "unit": compressed literals in four streams of at least 4 x 384 bytes, under a tree of their own or an earlier unit's; at most four a
+    frame) and of where those literals are put ahead of the decoder if the block is not the frame's last: at a guessed block end
+    G = min((ordinal + 1) x block_max, content size), the frame's content size for its last block.  One dict per unit: ordinal, last,
+    regen (the literals' count), guess G and the range [G - regen, G) they would be written to.  Not a model of the device's output: it
+    is here to show that a frame holds units whose ranges overlap."""
+    f = bytes(frame)
+    pos, fcs, bmax, _ = zstd_frame_geometry(f)
+    units = []
+    have_tree = False
+    bidx = 0
+    while len(units) < max_units and pos + 3 <= len(f):
+        bh = int.from_bytes(f[pos : pos + 3], "little")
+        last, btype, bsize = bh & 1, (bh >> 1) & 3, bh >> 3
+        if btype == 3:
+            break
+        blk = pos + 3
+        unit = False
+        if btype == 2 and 5 <= bsize < BLOCK_MAX:
+            v = int.from_bytes(f[blk : blk + 5], "little")
+            ltype, fmt = v & 3, (v >> 2) & 3
+            if ltype >= 2 and fmt != 0:
+                lh, rb, cb = {1: (3, 10, 10), 2: (4, 14, 14), 3: (5, 18, 18)}[fmt]
+                regen, csize = (v >> 4) & ((1 << rb) - 1), (v >> (4 + rb)) & ((1 << cb) - 1)
+                tree = 0
+                if ltype == 2:
+                    hb = f[blk + lh]
+                    tree = 1 + ((hb - 127) + 1) // 2 if hb >= 128 else 1 + hb
+                ok = regen and csize > tree + 10 and (ltype == 2 or have_tree)
+                if ok:
+                    q = blk + lh + tree
+                    s1, s2, s3 = (int.from_bytes(f[q + 2 * k : q + 2 * k + 2], "little") for k in range(3))
+                    s4 = csize - tree - 6 - s1 - s2 - s3
+                    if min(s1, s2, s3, s4) >= 4 * 384:
+                        g = fcs if last else min((bidx + 1) * bmax, fcs)
+                        units.append(dict(ordinal=bidx, last=bool(last), regen=regen, guess=g, range=(g - regen, g) if g >= regen else None))
+                        unit = True
+                        if ltype == 2:
+                            have_tree = True
+            if not unit and ltype == 2:
+                have_tree = False
+        pos = blk + (1 if btype == 1 else bsize)
+        bidx += 1
+        if last:
+            break
+    return units
+
+
+def overlapping_units(units):
+    """Pairs (i, j) of units whose write ranges overlap: a wrong guess of one puts its literals inside the other's range."""
+    pairs = []
+    for i, a in enumerate(units):
+        for j in range(i + 1, len(units)):
+            b = units[j]
+            if a["range"] and b["range"] and a["range"][0] < b["range"][1] and b["range"][0] < a["range"][1]:
+                pairs.append((i, j))
+    return pairs

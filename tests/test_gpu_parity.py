@@ -2071,3 +2071,22 @@ def test_reference_frames_literals_decoded_beside_the_walk():
         assert not isinstance(b, int) and b.tobytes() == a.tobytes(), i
     forced = n == 0   # (the suite is also run with every call forced onto the large-read path: no report from there)
     assert forced or (n == len(reads) and walked >= 2600 and 1900 <= ahead <= 2650), (n, batched, walked, ahead)
+    # ... and frames of a writer that flushes: 150 KB and more of content, the first block cut short of 128 KiB, the last
+    # of 15 .. 60 KiB -- a short non-last block's literals would be put at a guessed block end inside the last block's range
+    flushed, fread = [], []
+    for i in range(2600):
+        a = reads[i]
+        if a.nbytes < 150000:
+            a = O.synth_signal(5, 9000 + i, int(rng.integers(75000, 150000)))
+        s = O.svb_compress(a, 2, True, 1)
+        cut = min(len(s) - int(rng.integers(15 << 10, 60 << 10)), (128 << 10) - int(rng.integers(2 << 10, 30 << 10)))
+        flushed.append(O.zstd_compress_cuts(s, [cut] if 0 < cut < len(s) else [], level=1))
+        fread.append(a)
+    back = G.decompress(flushed, [a.nbytes for a in fread], opts)
+    n, batched, walked = G.codec().decode_paths()
+    ahead = G.codec().decode_literals_ahead()
+    for i, (a, b) in enumerate(zip(fread, back)):
+        assert not isinstance(b, int) and b.tobytes() == a.tobytes(), i
+    # (calibrated: 2 585 walked, 1 752 with literals ahead -- a frame of less than ~ 210 KB of stream has no room for the stripes behind a
+    # whole block's staging place in a slot of its samples' size: ref_lit_scan_kernel)
+    assert forced or (n == len(flushed) and walked >= 2500 and ahead >= 1600), (n, batched, walked, ahead)

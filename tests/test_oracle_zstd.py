@@ -120,3 +120,86 @@ def test_weights_alphabet_ends_at_eleven():
         if mine is not None:
             lz = O.zstd_decompress(b, 60000)
             assert lz is not None and lz.tobytes() == mine.tobytes()
+
+
+# ---- frames of chosen block layouts (oracle_lib.zstd_compress_cuts: libzstd's streaming compressor, flushed at every cut) ----------------
+def _svb(seed, n):
+    return O.svb_compress(O.synth_signal(5, seed, n), 2, True, 1)
+
+
+def test_flushed_frames_end_their_blocks_at_the_cuts():
+    """A flush ends a block: the block ends libzstd's bufferless decoder reports are the cuts, the content size, and libzstd's own
+    splits every 128 KiB of a stretch between cuts.  The restated decoder reads every such frame as libzstd does."""
+    if O.lib().vbo_zstd_version() is None:
+        pytest.skip("no libzstd.so.1 on this box")
+    rng = np.random.default_rng(17)
+    B = O.BLOCK_MAX
+    layouts = [[125000], [110000], [B + 118000], [1, 17, 4096], [B, 2 * B], [5000, 5000 + B + 7], [B - 1, B + 1]]
+    for it, cuts in enumerate(layouts + [sorted(set(int(x) for x in rng.integers(1, 390000, 3))) for _ in range(6)]):
+        s = _svb(100 + it, 260000)
+        cuts = [c for c in cuts if c < len(s)]
+        for level, checksum in ((1, False), (3, True), (9, False)):
+            f = O.zstd_compress_cuts(s, cuts, level=level, checksum=checksum)
+            assert O.zstd_content_size(f) == len(s)
+            assert O.zstd_frame_geometry(f)[3] == int(checksum)
+            want, start = [], 0
+            for end in cuts + [len(s)]:
+                want += list(range(start + B, end, B)) + [end]
+                start = end
+            assert O.zstd_block_ends(f, len(s)) == want, (it, level, cuts)
+            for dec in (O.zstd_decompress, O.zstd_restate_decompress):
+                out = dec(f, len(s))
+                assert out is not None and out.tobytes() == s.tobytes(), (it, level, dec.__name__)
+    # cuts at k x 128 KiB give the one-shot frame's layout -- and, at level 1, its bytes
+    s = _svb(7, 300000)
+    one = O.zstd_compress(s, 1)
+    f = O.zstd_compress_cuts(s, [B, 2 * B], level=1)
+    assert O.zstd_block_ends(f, len(s)) == O.zstd_block_ends(one, len(s)) == [B, 2 * B, len(s)]
+    for bad in ([0], [len(s)], [len(s) + 5], [B, B], [2 * B, B]):
+        with pytest.raises(ValueError):
+            O.zstd_compress_cuts(s, bad)
+
+
+def test_small_windows_cut_blocks_of_the_window():
+    """ZSTD_c_windowLog 10 .. 16: block_max is the window, every block but the last is that long (and the frame has a window descriptor
+    that says so); 17 is the 128 KiB of a one-shot frame."""
+    if O.lib().vbo_zstd_version() is None:
+        pytest.skip("no libzstd.so.1 on this box")
+    s = _svb(11, 200000)
+    for wlog in (10, 12, 16, 17):
+        for level, checksum in ((1, False), (3, True)):
+            f = O.zstd_compress_cuts(s, (), level=level, window_log=wlog, checksum=checksum)
+            _, fcs, bmax, ck = O.zstd_frame_geometry(f)
+            assert (fcs, bmax, ck) == (len(s), min(1 << wlog, O.BLOCK_MAX), int(checksum))
+            assert O.zstd_block_ends(f, len(s)) == list(range(bmax, len(s), bmax)) + [len(s)], wlog
+            assert O.zstd_restate_decompress(f, len(s)).tobytes() == s.tobytes()
+            assert O.zstd_decompress(f, len(s)).tobytes() == s.tobytes()
+
+
+def test_flushed_layouts_have_overlapping_literal_ranges():
+    """The device puts the literals of a non-last block's unit at a guessed block end (oracle_lib.ref_literal_units).  The layouts
+    tests/test_gpu_block_layouts.py relies on must really hold units whose ranges overlap -- a short non-last block's wrong guess lands in a
+    later unit's range --, else that test would pass without testing what it is for.  One-shot frames never do."""
+    if O.lib().vbo_zstd_version() is None:
+        pytest.skip("no libzstd.so.1 on this box")
+    B = O.BLOCK_MAX
+    # (the rows of the issue's table: the int16 svb stream of synth_signal(5, 3, samples), flushed once)
+    for samples, n, cuts, pair in ((120000, 151364, [125000], (0, 1)), (120000, 151364, [110000], (0, 1)), (230000, 290131, [B + 118000], (1, 2))):
+        s = O.svb_compress(O.synth_signal(5, 3, samples), 2, True, 0)
+        assert len(s) == n
+        f = O.zstd_compress_cuts(s, cuts)
+        u = O.ref_literal_units(f)
+        assert pair in O.overlapping_units(u), (n, cuts, u)
+        wrong = u[pair[0]]
+        assert not wrong["last"] and wrong["guess"] != O.zstd_block_ends(f, n)[wrong["ordinal"]], u
+    # the test's own generator: the first block cut 2 .. 30 KiB short, a last block of 15 .. 60 KiB
+    import test_gpu_block_layouts as T
+
+    for cuts, _, s in T.short_first_blocks():
+        assert O.overlapping_units(O.ref_literal_units(O.zstd_compress_cuts(s, cuts))), cuts
+    for cuts, _, s in T.short_middle_blocks():
+        assert O.overlapping_units(O.ref_literal_units(O.zstd_compress_cuts(s, cuts))), cuts
+    for r in range(6):
+        s = _svb(300 + r, 100000 + 60000 * r)
+        assert not O.overlapping_units(O.ref_literal_units(O.zstd_compress(s, 1)))
+        assert not O.overlapping_units(O.ref_literal_units(O.zstd_compress_cuts(s, [], window_log=16)))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised corruption soak of the decoder on a GPU box (not part of the test suite).
 
-    python tools/soak_corrupt.py [--seconds 120] [--seed 1] [--checksum]
+    python tools/soak_corrupt.py [--seconds 120] [--seed 1] [--checksum] [--writer device|reference|flushed]
 
 Every round compresses a few reads on the device (random dtype / shape / level 1 or 4; sometimes few large reads, whose
 frames carry a span index), damages the compressed buffers -- bit flips, byte overwrites, truncation, garbage appended,
@@ -52,14 +52,24 @@ def damage(rng, f):
     return np.ascontiguousarray(g)
 
 
+def flushed_frame(rng, svb, level):
+    """the svb stream in a libzstd frame flushed at random places, sometimes with a small window (an unsized frame of version 0)"""
+    n = len(svb)
+    cuts = sorted(set(int(x) for x in rng.integers(1, n, int(rng.integers(1, 4))))) if n > 1 else []
+    wlog = int(rng.choice([0, 0, 0, 10, 12, 16]))
+    return O.zstd_compress_cuts(svb, cuts, level=level, window_log=wlog)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--writer", choices=["device", "reference"], default="device",
+    ap.add_argument("--writer", choices=["device", "reference", "flushed"], default="device",
                     help="reference: the frames are libzstd's (the oracle's compressor, levels 1 and 3), int16 reads long enough for the chain walk and the "
-                         "literals beside it -- run with VBZ_HIP_REF_CHAINS=2, which walks in calls of any size")
+                         "literals beside it -- run with VBZ_HIP_REF_CHAINS=2, which walks in calls of any size; flushed: the same reads, libzstd's "
+                         "streaming compressor flushed at one to three random places (blocks shorter than 128 KiB anywhere in the frame), levels 1, 3 and "
+                         "9, sometimes a window of 1, 4 or 64 KiB (oracle_lib.zstd_compress_cuts)")
     ap.add_argument("--checksum", action="store_true", help="the device writes its frames with content checksums (device writer only)")
     args = ap.parse_args()
     if args.checksum:
@@ -79,16 +89,22 @@ def main():
             lens = [int(x) for x in rng.integers(300000, 900000, 2)]
         else:
             lens = [int(x) for x in rng.choice([0, 5, 64, 257, 4097, 20000, 100003], 6)] + [int(x) for x in rng.integers(0, 120000, 2)]
-        if args.writer == "reference":
+        if args.writer != "device":
             size, dt, sized = 2, np.int16, bool(rng.integers(0, 2))
-            level = int(rng.choice([1, 1, 3]))
+            level = int(rng.choice([1, 1, 3] if args.writer == "reference" else [1, 3, 9]))
             lens = [int(x) for x in rng.integers(25000, 160000, 5)] + [int(x) for x in rng.integers(0, 30000, 2)] + [int(rng.integers(160000, 520000))]
-        bufs = [soak.make_read(rng, dt, int(rng.choice([0, 0, 0, 5, 6, 3])) if args.writer == "reference" else int(rng.integers(0, 7)), n) for n in lens]
+        bufs = [soak.make_read(rng, dt, int(rng.choice([0, 0, 0, 5, 6, 3])) if args.writer != "device" else int(rng.integers(0, 7)), n) for n in lens]
         if args.verbose:
             print("round %d: %s zz %d level %d sized %d lens %s" % (rounds, np.dtype(dt).name, zz, level, sized, lens), flush=True)
         go = G.codec().options(zz, size, level, 0)
         oo = O.options(zz, size, level, 0)
-        frames = [O.compress(b, oo, sized=sized) for b in bufs] if args.writer == "reference" else G.compress(bufs, go, sized=sized)
+        if args.writer == "flushed":
+            sized = False
+            frames = [flushed_frame(rng, O.svb_compress(b, size, zz, 0), level) for b in bufs]
+        elif args.writer == "reference":
+            frames = [O.compress(b, oo, sized=sized) for b in bufs]
+        else:
+            frames = G.compress(bufs, go, sized=sized)
         bad, want = [], []
         for b, f in zip(bufs, frames):
             if isinstance(f, int):

@@ -807,7 +807,7 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
     if (!scan_frame_header(src, cap, &H, &pos, &has_checksum)) return;
     // where the decoder stages the literals of a block whose chains are walked ahead (zstd_decode_kernel: ws_plit, par)
     const uint64_t at = ((uint64_t)H.fcs + 15u) & ~15ull;
-    uint32_t nunit = 0, tree_unit = REF_NONE, regens[REF_UNITS] = { 0u, 0u, 0u, 0u };
+    uint32_t nunit = 0, tree_unit = REF_NONE, regens[REF_UNITS] = { 0u, 0u, 0u, 0u }, tails[REF_UNITS] = { 0u, 0u, 0u, 0u };
     uint64_t sum_regen = 0;
     bool more_blocks = false;
     for (uint32_t bidx = 0; nunit < max_units; ++bidx) {
@@ -871,10 +871,8 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
                         F.ws_lit = (uint32_t)at;
                         F.pad[0] = pos;      // the block header
                         F.pad[1] = csize;
-                        F.pad[2] = last;
                         F.pad[3] = gs;
                         F.pad[4] = ltype == 2 ? u : tree_unit;   // whose weights
-                        F.pad[7] = bidx;
                         F.pad[8] = noseq ? 1u : 0u;
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
@@ -887,6 +885,10 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
                         }
                         frames[u] = F;
                         regens[nunit] = regen;
+                        // where the block presumably ends: the frame's content size for its last block, else a whole block_max from the
+                        // frame's start (what a one-shot libzstd writes; a writer that flushes may end a block anywhere)
+                        const uint64_t full = ((uint64_t)bidx + 1u) * H.block_max;
+                        tails[nunit] = last ? H.fcs : (full < H.fcs ? (uint32_t)full : H.fcs);
                         sum_regen += regen;
                         if (ltype == 2) tree_unit = u;
                         ++nunit;
@@ -908,10 +910,19 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
     if (s0 + 4096u > cap) return;
     const uint64_t room = cap - s0;
     uint64_t off = s0;
+    // Which units put their literals at their block's presumed end ahead of the decoder (pad[9]: that end, 0: none).  The decoder skips
+    // its copy of a unit's tail only if the block really ends there, so a wrong guess cannot hurt the unit itself -- but its literals land
+    // in [G - regen, G) all the same, and if that range meets another unit's whose guess was right, the decoder trusts a tail the stray
+    // write may have overwritten (the units run in unordered workgroups).  Hence a unit places its literals only if its range is disjoint
+    // from every other unit's of the frame; the others leave them in the stripes, and the decoder copies them from there.
     for (uint32_t k = 0; k < nunit; ++k) {
+        bool place = tails[k] >= regens[k];
+        for (uint32_t q = 0; q < nunit; ++q)
+            if (q != k && tails[q] >= regens[q] && tails[k] - regens[k] < tails[q] && tails[q] - regens[q] < tails[k]) place = false;
         const uint64_t share = (room * regens[k] / sum_regen) & ~127ull;
         frames[(size_t)k * nr + r].pad[5] = (uint32_t)off;
         frames[(size_t)k * nr + r].pad[6] = (uint32_t)share;
+        frames[(size_t)k * nr + r].pad[9] = place ? tails[k] : 0u;
         off += share;
         skip[(size_t)k * nr + r] = 0;
     }
@@ -1164,11 +1175,11 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
     // sequences are: the stripes go there now, whole (what lands below the first such literal is overwritten by the decoder's output later, which
     // never reads it), and the decoder finds its longest copy done (RefLits.tail).  Piece after piece by the whole wavefront -- an
     // instruction is a kilobyte of whole lines --, eight pieces' loads in flight before their stores.
-    // (A block that is not the frame's last: libzstd cuts its input into blocks of BLOCK_MAX bytes, so the k-th such block ends at k x
-    // block_max -- a guess the decoder checks like everything else: it skips its copy only if the literals' place comes out where they were put.)
-    const uint64_t full = ((uint64_t)F->pad[7] + 1u) * F->block_max;   // (the block's ordinal in the frame)
-    const uint32_t tail_end = F->pad[2] ? F->fcs : (full < F->fcs ? (uint32_t)full : F->fcs);
-    if (tail_end >= regen) {
+    // (A block that is not the frame's last: a one-shot libzstd cuts its input into blocks of block_max bytes, so the k-th such block ends at
+    // k x block_max -- a guess: the decoder skips its copy only if the literals' place comes out where they were put, and the scan lets a unit
+    // place them only where a wrong guess cannot land in another unit's tail: pad[9], 0 if not.)
+    const uint32_t tail_end = F->pad[9];
+    if (tail_end != 0u && tail_end >= regen) {
         typedef __attribute__((address_space(1), aligned(16))) const u32x4 gl4;
         typedef __attribute__((address_space(1), aligned(1))) u32x4 gst4;
         const uint32_t dpos = tail_end - regen + lit0;
