@@ -283,6 +283,24 @@ int vbo_debug_huf_lengths(const uint8_t* p, size_t n, uint8_t* nbits_out /*256*/
     return h.log;
 }
 
+/* test helpers: the FSE table description and the decoding table as this restatement reads and builds them */
+int vbo_debug_fse_read_ncount(const uint8_t* p, size_t n, int16_t* norm /*256*/, int max_symbol, int max_log, int* out_log, int* out_nsym)
+{
+    return fse_read_ncount(p, n, norm, max_symbol, max_log, out_log, out_nsym);
+}
+
+int vbo_debug_fse_build(const int16_t* norm, int nsym, int log, uint8_t* sym, uint8_t* nbits, uint16_t* base /* 1 << log each */)
+{
+    static _Thread_local fse_table t;
+    if (fse_build(&t, norm, nsym, log) != 0) return -1;
+    for (int u = 0; u < (1 << log); ++u) {
+        sym[u] = t.e[u].symbol;
+        nbits[u] = t.e[u].nbits;
+        base[u] = t.e[u].base;
+    }
+    return 0;
+}
+
 static int huf_decode_stream(const huf_table* h, const uint8_t* p, size_t n, uint8_t* out, size_t count)
 {
     bitr b;

@@ -1,5 +1,6 @@
-"""Host harness around vbz_compression_amd/csrc/zstd_entropy.h (tests only): the serial statement of
-the Huffman table construction, compiled with g++, driven through ctypes."""
+"""Host harness around vbz_compression_amd/csrc/zstd_entropy.h and zstd_tables.h (tests only): the serial
+statements of the Huffman table construction and of the decoders' table readers, compiled with g++, driven
+through ctypes."""
 import ctypes
 import os
 import subprocess
@@ -10,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host", "entropy_harness.cpp")
 HDR = os.path.join(ROOT, "vbz_compression_amd", "csrc", "zstd_entropy.h")
+TABLES = os.path.join(ROOT, "vbz_compression_amd", "csrc", "zstd_tables.h")
 SO = os.path.join(HERE, "host", "libentropy_harness.so")
 _lib = None
 
@@ -17,7 +19,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or max(os.path.getmtime(SRC), os.path.getmtime(HDR)) > os.path.getmtime(SO):
+        if not os.path.exists(SO) or max(os.path.getmtime(f) for f in (SRC, HDR, TABLES)) > os.path.getmtime(SO):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + os.path.dirname(HDR), "-o", SO, SRC])
         _lib = ctypes.CDLL(SO)
     return _lib
@@ -40,6 +42,34 @@ def tree_description(data, package_merge=False):
     out = np.zeros(300, np.uint8)
     ts = H.h_huf_write_tree(out.ctypes.data_as(u8p), 300, nb.ctypes.data_as(u8p), maxsym, tl)
     return tl, nb, (bytes(out[:ts]) if ts > 0 else None)
+
+
+def fse_read_ncount(desc, max_symbol, max_log):
+    """zstd_tables.h's FSE table description reader over the bytes `desc`: (bytes used or -1, log, normalised counts)."""
+    desc = np.frombuffer(bytes(desc), np.uint8).copy()
+    norm = np.zeros(256, np.int16)
+    log, nsym = ctypes.c_int(0), ctypes.c_int(0)
+    r = lib().h_fse_read_ncount(desc.ctypes.data_as(ctypes.c_void_p), len(desc), max_symbol, max_log, norm.ctypes.data_as(ctypes.c_void_p),
+                                ctypes.byref(log), ctypes.byref(nsym))
+    return (r, log.value, norm[: nsym.value].copy()) if r >= 0 else (r, None, None)
+
+
+def fse_build(norm, log):
+    """zstd_tables.h's FSE decoding table: None, or the cells (symbol | nbBits << 8 | base << 16)."""
+    norm = np.ascontiguousarray(norm, np.int16)
+    cells = np.zeros(1 << log, np.uint32)
+    r = lib().h_fse_build(norm.ctypes.data_as(ctypes.c_void_p), len(norm), log, cells.ctypes.data_as(ctypes.c_void_p))
+    return cells if r == 0 else None
+
+
+def huf_read_weights(desc, max_log):
+    """zstd_tables.h's tree description reader: (bytes used, -1 or -2; table log; weights, the implied last one included)."""
+    desc = np.frombuffer(bytes(desc), np.uint8).copy()
+    w = np.zeros(256, np.uint8)
+    nw, log = ctypes.c_int(0), ctypes.c_int(0)
+    r = lib().h_huf_read_weights(desc.ctypes.data_as(ctypes.c_void_p), len(desc), max_log, w.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nw),
+                                 ctypes.byref(log))
+    return (r, log.value, w[: nw.value].copy()) if r >= 0 else (r, None, None)
 
 
 def parse_first_block_literals(frame):

@@ -1,8 +1,10 @@
 // Host harness (tests only): exposes the serial table-construction functions of
 // vbz_compression_amd/csrc/zstd_entropy.h to ctypes so the CPU suite can check them against
-// what libzstd emits for the same histogram.  Built by tests/test_entropy_host.py with g++.
+// what libzstd emits for the same histogram, and the table readers of zstd_tables.h to check them
+// against the oracle's restatement.  Built by tests/entropy_host.py with g++.
 #include <cstring>
 #include "zstd_entropy.h"
+#include "zstd_tables.h"
 #include "zstd_reference_huffman.h"   // libzstd's construction: the yardstick (BSD notice inside)
 
 using namespace vbzhip;
@@ -24,6 +26,49 @@ int h_huf_build_pm(const uint32_t* count, uint32_t maxSymbolValue, uint32_t maxN
 uint32_t h_optimal_table_log(uint32_t maxTableLog, uint32_t srcSize, uint32_t maxSymbolValue, uint32_t minus)
 {
     return optimal_table_log(maxTableLog, srcSize, maxSymbolValue, minus);
+}
+
+// zstd_tables.h with plain arrays for the policies
+struct HostFse
+{
+    int16_t nrm[256];
+    uint16_t nx[256];
+    uint32_t tab[512];
+    int norm(int s) const { return nrm[s]; }
+    void set_norm(int s, int c) { nrm[s] = (int16_t)c; }
+    uint16_t& next(int s) { return nx[s]; }
+    uint32_t& cell(int u) { return tab[u]; }
+    void entry(int u, uint32_t s, uint32_t nb, uint32_t base) { tab[u] = fse_entry(s, nb, base); }
+};
+
+int h_fse_read_ncount(const uint8_t* p, int n, int max_symbol, int max_log, int16_t* norm, int* log, int* nsym)
+{
+    return fse_read_ncount([&](uint32_t pos, int k) { return le_bits(p, n, pos, k); }, n, max_symbol, max_log,
+                           [&](int s, int c) { norm[s] = (int16_t)c; }, log, nsym);
+}
+
+// cells[u] = symbol | nbBits << 8 | base << 16
+int h_fse_build(const int16_t* norm, int nsym, int log, uint32_t* cells)
+{
+    static HostFse t;
+    memcpy(t.nrm, norm, sizeof(int16_t) * (size_t)nsym);
+    if (!fse_build(t, nsym, log)) return -1;
+    memcpy(cells, t.tab, sizeof(uint32_t) << log);
+    return 0;
+}
+
+// weights[0 .. *nw) of a tree description; returns bytes used, -1 or -2 (a table log beyond max_log)
+int h_huf_read_weights(const uint8_t* p, int n, int max_log, uint8_t* weights, int* nw, int* log)
+{
+    struct Src
+    {
+        const uint8_t* p;
+        int hb;
+        uint32_t byte(int i) const { return p[i]; }
+        uint32_t bits(uint32_t pos, int k) const { return le_bits(p + 1, hb, pos, k); }
+    } src = { p, n > 0 ? p[0] : 0 };
+    static HostFse t;
+    return huf_read_weights(src, n, max_log, t, [&](int i, uint32_t w) { weights[i] = (uint8_t)w; }, nw, log);
 }
 
 int h_huf_write_tree(uint8_t* dst, int cap, const uint8_t* nbBits, uint32_t maxSymbolValue, uint32_t huffLog)

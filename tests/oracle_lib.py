@@ -97,6 +97,12 @@ def lib():
             getattr(L, name).argtypes = [vp, u32, vp]
         L.vbo_i16zz_decompress_simd.restype = u32
         L.vbo_i16zz_decompress_simd.argtypes = [vp, u32, vp, u32]
+        L.vbo_debug_fse_read_ncount.restype = ctypes.c_int
+        L.vbo_debug_fse_read_ncount.argtypes = [vp, sz, vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        L.vbo_debug_fse_build.restype = ctypes.c_int
+        L.vbo_debug_fse_build.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+        L.vbo_debug_huf_lengths.restype = ctypes.c_int
+        L.vbo_debug_huf_lengths.argtypes = [vp, sz, vp, ctypes.POINTER(ctypes.c_int)]
         L.vbo_fuzz_max_destination.restype = u32
         L.vbo_fuzz_max_destination.argtypes = [u32, op]
         L.vbo_fuzz_decompress_sweep.restype = ctypes.c_int

@@ -18,10 +18,13 @@
 // present), their literal streams with everybody else's, the runs placed afterwards from prefix sums.
 // Other blocks with sequences are executed in order: lane 0 walks the three FSE state machines, the wave
 // copies literals and matches cooperatively.
+// The table descriptions (FSE counts and tables, the sequence tables, Huffman weights and their rules, the Huffman table fill) are
+// the serial statements of zstd_tables.h, which the batched decoders (zstd_decode_ref.hip, zstd_decode_fast.hip) instantiate too.
 // Algorithmic HBM bytes per svb byte: ~0.67 read + 1 written.
 #include "vbz_kernels.h"
 #include "svb_wave.h"
 #include "zstd_runs.h"
+#include "zstd_tables.h"
 
 namespace vbzhip {
 
@@ -157,209 +160,39 @@ __device__ __forceinline__ uint32_t lane_write(uint32_t reg, uint32_t l, uint32_
 }
 #pragma clang diagnostic pop
 
-// FSE table description (RFC 8878 4.1.1) read from LDS bytes; lane 0 only.
-// returns bytes consumed or -1; fills L.u.p.norm[0..nsym)
-__device__ int read_ncount(const uint8_t* p, int n, int max_symbol, int max_log, int* out_log, int* out_nsym)
+// The table policy of zstd_tables.h for lane 0: counts and state numbers in L.u.p, the cells in `tab` (packed: fse_entry)
+struct DecFse
 {
-    if (n < 1) return -1;
-    auto bits = [&](uint32_t bitpos, int k) -> uint32_t {
-        uint32_t v = 0;
-        const uint32_t by = bitpos >> 3;
-        // gather up to 4 bytes (k <= 10 + 7 shift bits)
-        for (int i = 0; i < 3; ++i) {
-            const uint32_t idx = by + (uint32_t)i;
-            v |= (idx < (uint32_t)n ? (uint32_t)p[idx] : 0u) << (8 * i);
-        }
-        return (v >> (bitpos & 7u)) & ((1u << k) - 1u);
-    };
-    const int log = (int)(p[0] & 0xF) + 5;
-    if (log > max_log) return -1;
-    uint32_t bitpos = 4;
-    int remaining = (1 << log) + 1, threshold = 1 << log, nbits = log + 1, sym = 0;
-    bool prev0 = false;
-    while (remaining > 1 && sym <= max_symbol) {
-        if (prev0) {
-            for (;;) {
-                const uint32_t rr = bits(bitpos, 2);
-                bitpos += 2;
-                for (uint32_t k = 0; k < rr; ++k) {
-                    if (sym > max_symbol) return -1;
-                    L.u.p.norm[sym++] = 0;
-                }
-                if (rr != 3) break;
-            }
-            prev0 = false;
-            if (sym > max_symbol) break;
-            continue;
-        }
-        const int max = (2 * threshold - 1) - remaining;
-        const uint32_t v = bits(bitpos, nbits);
-        int count;
-        if ((int)(v & (uint32_t)(threshold - 1)) < max) {
-            count = (int)(v & (uint32_t)(threshold - 1));
-            bitpos += (uint32_t)(nbits - 1);
-        } else {
-            count = (int)(v & (uint32_t)(2 * threshold - 1));
-            if (count >= threshold) count -= max;
-            bitpos += (uint32_t)nbits;
-        }
-        count--;
-        remaining -= count < 0 ? -count : count;
-        L.u.p.norm[sym++] = (int16_t)count;
-        prev0 = (count == 0);
-        while (remaining < threshold) {
-            nbits--;
-            threshold >>= 1;
-        }
-    }
-    if (remaining != 1) return -1;
-    if (sym > max_symbol + 1) return -1;
-    const int used = (int)((bitpos + 7) >> 3);
-    if (used > n) return -1;
-    *out_log = log;
-    *out_nsym = sym;
-    return used;
-}
+    uint32_t* tab;
+    __device__ int norm(int s) const { return L.u.p.norm[s]; }
+    __device__ void set_norm(int s, int c) const { L.u.p.norm[s] = (int16_t)c; }
+    __device__ uint16_t& next(int s) const { return L.u.p.symnext[s]; }
+    __device__ uint32_t& cell(int u) const { return tab[u]; }
+    __device__ void entry(int u, uint32_t s, uint32_t nb, uint32_t base) const { tab[u] = fse_entry(s, nb, base); }
+};
 
-// FSE decoding table from L.u.p.norm (lane 0 only): RFC 8878 4.1.1
-__device__ int fse_build(uint32_t* tab, int nsym, int log)
-{
-    const int size = 1 << log;
-    int high = size - 1;
-    for (int s = 0; s < nsym; ++s) {
-        if (L.u.p.norm[s] == -1) {
-            tab[high--] = (uint32_t)s;
-            L.u.p.symnext[s] = 1;
-        } else {
-            L.u.p.symnext[s] = (uint16_t)L.u.p.norm[s];
-        }
-    }
-    const int step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    int pos = 0;
-    for (int s = 0; s < nsym; ++s) {
-        for (int i = 0; i < L.u.p.norm[s]; ++i) {
-            tab[pos] = (uint32_t)s;
-            do {
-                pos = (pos + step) & mask;
-            } while (pos > high);
-        }
-    }
-    if (pos != 0) return -1;
-    for (int u = 0; u < size; ++u) {
-        const uint32_t s = tab[u] & 0xFF;
-        const uint32_t ns = L.u.p.symnext[s]++;
-        const int nb = log - hbit(ns);
-        tab[u] = s | ((uint32_t)nb << 8) | ((((ns << nb) - (uint32_t)size) & 0xFFFFu) << 16);
-    }
-    return 0;
-}
-
-// one sequence-table definition (lane 0): mode 0 predefined, 1 RLE, 2 FSE, 3 repeat.
+// one sequence-table definition (lane 0): zstd_tables.h's seq_table over the bytes p[0..n) into `tab`.
 // returns bytes consumed from p, or -1
 __device__ __noinline__ int seq_table(uint32_t* tab, int* log_io, bool* have, int mode, const uint8_t* p, int n,
                          const int16_t* def, int def_n, int def_log, int max_sym, int max_log)
 {
-    if (mode == 0) {
-        for (int i = 0; i < def_n; ++i) L.u.p.norm[i] = def[i];
-        if (fse_build(tab, def_n, def_log) != 0) return -1;
-        *log_io = def_log;
-        *have = true;
-        return 0;
-    }
-    if (mode == 1) {
-        if (n < 1 || p[0] > max_sym) return -1;
-        tab[0] = p[0];
-        *log_io = 0;
-        *have = true;
-        return 1;
-    }
-    if (mode == 2) {
-        int log, nsym;
-        const int used = read_ncount(p, n, max_sym, max_log, &log, &nsym);
-        if (used < 0) return -1;
-        if (fse_build(tab, nsym, log) != 0) return -1;
-        *log_io = log;
-        *have = true;
-        return used;
-    }
-    return *have ? 0 : -1;
+    DecFse t = { tab };
+    return vbzhip::seq_table(t, [&](uint32_t pos, int k) { return le_bits(p, n, pos, k); }, mode, n, def, def_n, def_log, max_sym, max_log,
+                             log_io, have);
 }
 
-// Huffman tree description -> weights in L.weights (lane 0). returns bytes consumed or -1; sets nw/log
+// Huffman tree description -> weights in L.weights (lane 0): zstd_tables.h's huf_read_weights. returns bytes consumed or -1; sets nw/log
 __device__ __noinline__ int huf_read_weights(const uint8_t* p, int n, int* out_nw, int* out_log)
 {
-    if (n < 1) return -1;
-    int nw = 0, used;
-    const int hb = p[0];
-    if (hb >= 128) {
-        nw = hb - 127;
-        used = 1 + (nw + 1) / 2;
-        if (used > n) return -1;
-        for (int i = 0; i < nw; ++i) L.weights[i] = (i & 1) ? (p[1 + i / 2] & 0xF) : (p[1 + i / 2] >> 4);
-    } else {
-        used = 1 + hb;
-        if (hb == 0 || used > n) return -1;
-        int log, nsym;
-        // (the weights' alphabet ends at 11 = HUF_TABLELOG_MAX - 1: libzstd >= 1.4.7 refuses a description that lists a symbol beyond it)
-        const int hdr = read_ncount(p + 1, hb, 11, 6, &log, &nsym);
-        if (hdr < 0) return -1;
-        uint32_t* tab = L.wfse;
-        if (fse_build(tab, nsym, log) != 0) return -1;
-        // two interleaved FSE states over an LDS-resident backward bit stream (at most 127 bytes)
-        const uint8_t* q = p + 1 + hdr;
-        const int qn = hb - hdr;
-        if (qn < 1 || q[qn - 1] == 0) return -1;
-        const int top = hbit(q[qn - 1]);
-        int left = (qn - 1) * 8 + top;  // unread bits of the stream
-        uint64_t buf = top ? ((uint64_t)(q[qn - 1] & ((1u << top) - 1u)) << (64 - top)) : 0ull;
-        int avail = top, nextb = qn - 1;
-        auto rd = [&](int nb) -> uint32_t {
-            while (avail <= 56 && nextb > 0) {
-                --nextb;
-                buf |= (uint64_t)q[nextb] << (56 - avail);
-                avail += 8;
-            }
-            const uint32_t v = nb ? (uint32_t)(buf >> (64 - nb)) : 0u;
-            buf <<= nb;
-            avail = avail > nb ? avail - nb : 0;
-            left -= nb;
-            return v;
-        };
-        uint32_t s1 = rd(log), s2 = rd(log);
-        if (left < 0) return -1;
-        for (;;) {
-            if (nw > 253) return -1;
-            uint32_t e = tab[s1];
-            L.weights[nw++] = (uint8_t)e;
-            s1 = (e >> 16) + rd((int)((e >> 8) & 0xFF));
-            if (left < 0) { L.weights[nw++] = (uint8_t)tab[s2]; break; }
-            if (nw > 253) return -1;
-            e = tab[s2];
-            L.weights[nw++] = (uint8_t)e;
-            s2 = (e >> 16) + rd((int)((e >> 8) & 0xFF));
-            if (left < 0) { L.weights[nw++] = (uint8_t)tab[s1]; break; }
-        }
-    }
-    uint32_t total = 0;
-    int r1 = 0;
-    for (int i = 0; i < nw; ++i) {
-        const uint32_t wt = L.weights[i];
-        if (wt >= 12) return -1;
-        total += wt ? (1u << (wt - 1)) : 0u;
-        r1 += (wt == 1);
-    }
-    if (total == 0) return -1;
-    const int log = hbit(total) + 1;
-    if (log > 12) return -1;
-    const uint32_t rest = (1u << log) - total;
-    if (rest & (rest - 1)) return -1;
-    const uint32_t lastw = (uint32_t)hbit(rest) + 1;
-    L.weights[nw++] = (uint8_t)lastw;
-    r1 += (lastw == 1);
-    if (r1 < 2 || (r1 & 1)) return -1;
-    *out_nw = nw;
-    *out_log = log;
-    return used;
+    struct Src
+    {
+        const uint8_t* p;
+        int hb;
+        __device__ uint32_t byte(int i) const { return p[i]; }
+        __device__ uint32_t bits(uint32_t pos, int k) const { return le_bits(p + 1, hb, pos, k); }
+    } src = { p, p[0] };
+    DecFse t = { L.wfse };
+    return vbzhip::huf_read_weights(src, n, HUF_LOG_LIMIT, t, [](int i, uint32_t w) { L.weights[i] = (uint8_t)w; }, out_nw, out_log);
 }
 
 // all lanes.  Huffman tree description at g[0..n) -> weights in L.weights, like huf_read_weights, with the description
@@ -591,78 +424,22 @@ __device__ __noinline__ int huf_read_tree(const uint8_t* g, uint32_t n_, int lan
     }
     if (__any(badw)) return -1;
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(part), 63);
-    uint32_t r1 = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(ones), 63);
-    if (total == 0) return -1;
-    const uint32_t tlog = (uint32_t)hbit(total) + 1;
-    if (tlog > 12) return -1;
-    const uint32_t rest = (1u << tlog) - total;
-    if (rest & (rest - 1)) return -1;
-    const uint32_t lastw = (uint32_t)hbit(rest) + 1;
+    const uint32_t r1 = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(ones), 63);
+    uint32_t lastw = 0;
+    const int tlog = huf_weights_close(total, r1, HUF_LOG_LIMIT, &lastw);
+    if (tlog < 0) return -1;
     if (lane == 0) L.weights[nw] = (uint8_t)lastw;
     ++nw;
-    r1 += lastw == 1 ? 1u : 0u;
-    if (r1 < 2 || (r1 & 1)) return -1;
     *out_nw = nw;
     *out_log = tlog;
     __syncthreads();
     return (int)used;
 }
 
-// all lanes: fill a Huffman decoding table from L.weights[0..nw) (RFC 8878 4.2.1: increasing weight, then
-// increasing symbol value).  Table start of a symbol = cells of all lighter symbols + cells of the equally
-// heavy symbols before it, found with ballots in symbol order; short runs are written by the owning lane,
-// long ones by the whole wave.
+// all lanes: fill a Huffman decoding table from L.weights[0..nw) (zstd_tables.h: huf_fill_wave)
 __device__ __noinline__ void huf_fill_table(uint16_t* T, uint32_t nw, uint32_t tlog, int lane)
 {
-    if (lane < 16) L.ctl[8 + lane] = 0;  // cells per weight live in ctl[8..23]
-    __syncthreads();
-    uint32_t wt[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t s = (uint32_t)lane + 64u * j;
-        wt[j] = s < nw ? L.weights[s] : 0u;
-        if (wt[j]) atomicAdd(&L.ctl[8 + wt[j]], 1u);
-    }
-    __syncthreads();
-    uint32_t base[13];
-    {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int v = 1; v <= 12; ++v) {
-            base[v] = acc;
-            acc += L.ctl[8 + v] << (v - 1);
-        }
-        base[0] = 0;
-    }
-    const uint64_t below = (1ull << lane) - 1ull;
-    uint32_t st[4], len[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        st[j] = 0;
-        len[j] = wt[j] ? 1u << (wt[j] - 1) : 0u;
-#pragma unroll
-        for (int v = 1; v <= 12; ++v) {
-            const uint64_t m = __ballot(wt[j] == (uint32_t)v);
-            if (wt[j] == (uint32_t)v) st[j] = base[v] + ((uint32_t)__popcll(m & below) << (v - 1));
-            base[v] += (uint32_t)__popcll(m) << (v - 1);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t s = (uint32_t)lane + 64u * j;
-        const uint16_t ent = (uint16_t)(s | ((tlog + 1 - wt[j]) << 8));
-        if (len[j] && len[j] < 64)
-            for (uint32_t i = 0; i < len[j]; ++i) T[st[j] + i] = ent;
-        uint64_t big = __ballot(len[j] >= 64);
-        while (big) {
-            const int src_lane = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const uint32_t bst = (uint32_t)__shfl((int)st[j], src_lane, 64);
-            const uint32_t blen = (uint32_t)__shfl((int)len[j], src_lane, 64);
-            const uint32_t bent = (uint32_t)__shfl((int)ent, src_lane, 64);
-            for (uint32_t i = lane; i < blen; i += WAVE) T[bst + i] = (uint16_t)bent;
-        }
-    }
+    huf_fill_wave(T, L.weights, nw, tlog, lane);
     __syncthreads();
 }
 
@@ -2922,8 +2699,8 @@ hipError_t launch_zstd_decode_spans(const ReadBatch& b, uint32_t toosmall_code, 
     return hipGetLastError();
 }
 
-// host: decoding tables of the predefined LL / ML distributions (RFC 8878 3.1.1.3.2.2), built the way
-// fse_build builds them on the device, in the compact form of SeqDTables (uploaded once per context)
+// host: decoding tables of the predefined LL / ML distributions (RFC 8878 3.1.1.3.2.2), built by zstd_tables.h's fse_build
+// in the compact form of SeqDTables (uploaded once per context)
 size_t seq_dtables_bytes() { return sizeof(SeqDTables); }
 
 void seq_dtables_build(void* host_buffer)
@@ -2941,32 +2718,20 @@ void seq_dtables_build(void* host_buffer)
                                          1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16 };
     SeqDTables* t = static_cast<SeqDTables*>(host_buffer);
     auto build = [](uint2* out, const int16_t* norm, int nsym, const uint32_t* base, const uint8_t* bits) {
-        const int log = 6, size = 1 << log, mask = size - 1;
-        int sym[64], next[64], high = size - 1;
-        for (int s = 0; s < nsym; ++s) {
-            if (norm[s] == -1) {
-                sym[high--] = s;
-                next[s] = 1;
-            } else {
-                next[s] = norm[s];
-            }
-        }
-        const int step = (size >> 1) + (size >> 3) + 3;
-        int pos = 0;
-        for (int s = 0; s < nsym; ++s)
-            for (int i = 0; i < norm[s]; ++i) {
-                sym[pos] = s;
-                pos = (pos + step) & mask;
-                while (pos > high) pos = (pos + step) & mask;
-            }
-        for (int u = 0; u < size; ++u) {
-            const int s = sym[u], ns = next[s]++;
-            int hb = 0;
-            while ((2 << hb) <= ns) ++hb;
-            const int nb = log - hb;
-            const uint32_t nbase = (uint32_t)((ns << nb) - size);
-            out[u] = make_uint2(base[s], nbase | ((uint32_t)bits[s] << 16) | ((uint32_t)nb << 24));
-        }
+        struct Tab
+        {
+            const int16_t* nrm;
+            uint2* out;
+            const uint32_t* base;
+            const uint8_t* bits;
+            int sym[64];
+            uint16_t nx[64];
+            int norm(int s) const { return nrm[s]; }
+            uint16_t& next(int s) { return nx[s]; }
+            int& cell(int u) { return sym[u]; }
+            void entry(int u, uint32_t s, uint32_t nb, uint32_t nbase) { out[u] = make_uint2(base[s], nbase | ((uint32_t)bits[s] << 16) | (nb << 24)); }
+        } tab = { norm, out, base, bits, {}, {} };
+        fse_build(tab, nsym, 6);
     };
     build(t->ll, ll_norm, 36, ll_base, ll_bits);
     build(t->ml, ml_norm, 53, ml_base, ml_bits);

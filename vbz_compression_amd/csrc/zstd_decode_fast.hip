@@ -19,13 +19,15 @@
 // or that fails any check on the way (a stream that does not end on its first bit, a chain that does not regenerate what the later
 // blocks leave of the content size ...), is marked in redo[] and decoded by zstd_decode_kernel in a last launch gated by that
 // array -- which is also what decides every error verdict.  A frame decoded here gets exactly the bytes the one-wavefront decoder
-// writes: same tables, same streams, same placement code.
+// writes: same tables, same streams, same placement code.  The tree descriptions and the Huffman tables are read and filled by
+// zstd_tables.h, as in zstd_decode.hip.
 // Replaces, like zstd_decode.hip, the reference's ZSTD_decompress call (vbz/vbz.cpp:236-273).
 #include <algorithm>
 #include <cstdlib>
 
 #include "vbz_kernels.h"
 #include "zstd_runs.h"
+#include "zstd_tables.h"
 
 namespace vbzhip {
 
@@ -258,10 +260,9 @@ __global__ __launch_bounds__(256) void fast_scan_kernel(ReadBatch b, FastFrame* 
 }
 
 // ---- one lane per tree description ---------------------------------------------------------------------------------------------------
-// The serial reader of zstd_decode.hip (huf_read_weights: read_ncount, fse_build, two interleaved FSE states over a backward bit
-// stream, the checks on the weights) with one description per LANE: what it indexes lives in LDS columns of its own ([index][lane]:
-// no bank conflicts), the weights go to memory.  Descriptions it cannot hold (a
-// 12-bit code) are left to the careful decoder like every failure.
+// zstd_tables.h's huf_read_weights with one description per LANE: what it indexes lives in LDS columns of its own ([index][lane]: no
+// bank conflicts), the weights go to memory.  Descriptions it cannot hold (a 12-bit code) are left to the careful decoder like every
+// failure.
 constexpr int WMAXS = 11;   // the weights' alphabet: 0 .. HUF_TABLELOG_MAX - 1 (libzstd >= 1.4.7 refuses a description that lists more)
 struct WeightsLds
 {
@@ -285,239 +286,50 @@ __global__ __launch_bounds__(WAVE) void fast_weights_kernel(ReadBatch b, FastFra
     const uint8_t* g = b.src + b.src_off[r % b.n_reads] + F->tree_off[k];
     const uint32_t used = F->tree_len[k];
     uint8_t* W = weights + ((size_t)r * 2 + k) * 256;
-    const uint32_t hb = g[0];
-    uint32_t nw = 0;
-#define WFAIL()       \
-    do {              \
-        redo[r] = 1;  \
-        return;       \
-    } while (0)
-    // (the checks on the weights -- 4.2.1 -- are made as they are produced: reading them back took one memory round trip per weight,
-    // 0.18 ms per launch whatever the number of trees, because every load stood behind the branch on the one before)
-    uint32_t total = 0;
-    int r1 = 0;
-    bool wide = false;
-    auto put = [&](uint32_t wt) {
-        W[nw++] = (uint8_t)wt;
-        wide |= wt >= 12u;
-        total += (wt != 0u && wt < 12u) ? (1u << (wt - 1u)) : 0u;
-        r1 += (wt == 1u);
-    };
-    if (hb >= 128) {  // direct representation: 4 bits per weight
-        const uint32_t cnt = hb - 127;
-        for (uint32_t i = 0; i < cnt; ++i) {
-            const uint32_t by = g[1 + i / 2];
-            put((i & 1) ? (by & 0xF) : (by >> 4));
+    for (uint32_t j = 0; j < 34; ++j) {
+        const uint32_t off = 1 + 4 * j;
+        uint32_t v = 0;
+        if (off < used) {
+            v = ld32(g + off);
+            if (off + 4 > used) v &= (1u << (8 * (used - off))) - 1u;
         }
-    } else {
-        for (uint32_t j = 0; j < 34; ++j) {
-            const uint32_t off = 1 + 4 * j;
-            uint32_t v = 0;
-            if (off < used) {
-                v = ld32(g + off);
-                if (off + 4 > used) v &= (1u << (8 * (used - off))) - 1u;
-            }
-            S.desc[j][lane] = v;
-        }
-        auto bits = [&](uint32_t bitpos, uint32_t nb) -> uint32_t {  // nb <= 16 bits at bit position bitpos of the description
+        S.desc[j][lane] = v;
+    }
+    struct Src
+    {
+        const WeightsLds& S;
+        int lane;
+        uint32_t hb;
+        __device__ uint32_t byte(int i) const { return i == 0 ? hb : (S.desc[(i - 1) >> 2][lane] >> (8 * ((i - 1) & 3))) & 0xFF; }
+        __device__ uint32_t bits(uint32_t bitpos, int nb) const  // nb <= 16 bits at bit position bitpos of the description
+        {
             const uint32_t idx = bitpos >> 5;
             const uint64_t v = (uint64_t)S.desc[idx < 33 ? idx : 33][lane] | ((uint64_t)S.desc[idx < 32 ? idx + 1 : 33][lane] << 32);
             return (uint32_t)(v >> (bitpos & 31)) & ((1u << nb) - 1u);
-        };
-        // ---- probabilities (RFC 8878 4.1.1): read_ncount(p + 1, hb, 255, 6) of zstd_decode.hip
-        const int log = (int)bits(0, 4) + 5;
-        if (log > 6) WFAIL();
-        uint32_t bitpos = 4;
-        int remaining = (1 << log) + 1, threshold = 1 << log, nbits = log + 1, sym = 0;
-        bool prev0 = false;
-        while (remaining > 1 && sym <= WMAXS) {
-            if (bitpos > 8u * 128u) WFAIL();
-            if (prev0) {
-                for (;;) {
-                    const uint32_t rr = bits(bitpos, 2);
-                    bitpos += 2;
-                    for (uint32_t i = 0; i < rr; ++i) {
-                        if (sym > WMAXS) WFAIL();
-                        S.norm[sym++][lane] = 0;
-                    }
-                    if (rr != 3) break;
-                    if (bitpos > 8u * 128u) WFAIL();
-                }
-                prev0 = false;
-                if (sym > WMAXS) break;
-                continue;
-            }
-            const int max = (2 * threshold - 1) - remaining;
-            const uint32_t v = bits(bitpos, (uint32_t)nbits);
-            int count;
-            if ((int)(v & (uint32_t)(threshold - 1)) < max) {
-                count = (int)(v & (uint32_t)(threshold - 1));
-                bitpos += (uint32_t)(nbits - 1);
-            } else {
-                count = (int)(v & (uint32_t)(2 * threshold - 1));
-                if (count >= threshold) count -= max;
-                bitpos += (uint32_t)nbits;
-            }
-            count--;
-            remaining -= count < 0 ? -count : count;
-            S.norm[sym++][lane] = (int16_t)count;
-            prev0 = (count == 0);
-            while (remaining < threshold) {
-                nbits--;
-                threshold >>= 1;
-            }
         }
-        if (remaining != 1 || sym > WMAXS + 1) WFAIL();
-        const uint32_t hdr = (bitpos + 7) >> 3;
-        if (hdr > hb) WFAIL();
-        const int nsym = sym;
-        // ---- decoding table: fse_build
-        const int size = 1 << log;
-        {
-            int high = size - 1;
-            for (int s = 0; s < nsym; ++s) {
-                const int c = S.norm[s][lane];
-                if (c == -1) {
-                    S.tab[high--][lane] = (uint32_t)s;
-                    S.symnext[s][lane] = 1;
-                } else {
-                    S.symnext[s][lane] = (uint16_t)c;
-                }
-            }
-            const int step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-            int p = 0;
-            for (int s = 0; s < nsym; ++s) {
-                const int c = S.norm[s][lane];
-                for (int i = 0; i < c; ++i) {
-                    S.tab[p][lane] = (uint32_t)s;
-                    do {
-                        p = (p + step) & mask;
-                    } while (p > high);
-                }
-            }
-            if (p != 0) WFAIL();
-            for (int u = 0; u < size; ++u) {
-                const uint32_t s = S.tab[u][lane] & 0xFF;
-                const uint32_t ns = S.symnext[s][lane];
-                S.symnext[s][lane] = (uint16_t)(ns + 1);
-                const int nb = log - hbit(ns);
-                S.tab[u][lane] = s | ((uint32_t)nb << 8) | ((((ns << nb) - (uint32_t)size) & 0xFFFFu) << 16);
-            }
-        }
-        // ---- two interleaved states over the backward bit stream behind the probabilities
-        const int qn = (int)hb - (int)hdr;
-        auto qbyte = [&](int i) -> uint32_t {
-            const uint32_t o = hdr + (uint32_t)i;
-            return (S.desc[o >> 2][lane] >> (8 * (o & 3))) & 0xFF;
-        };
-        if (qn < 1 || qbyte(qn - 1) == 0) WFAIL();
-        const int top = hbit(qbyte(qn - 1));
-        int left = (qn - 1) * 8 + top;
-        uint64_t buf = top ? ((uint64_t)(qbyte(qn - 1) & ((1u << top) - 1u)) << (64 - top)) : 0ull;
-        int avail = top, nextb = qn - 1;
-        auto rd = [&](int nb) -> uint32_t {
-            while (avail <= 56 && nextb > 0) {
-                --nextb;
-                buf |= (uint64_t)qbyte(nextb) << (56 - avail);
-                avail += 8;
-            }
-            const uint32_t v = nb ? (uint32_t)(buf >> (64 - nb)) : 0u;
-            buf <<= nb;
-            avail = avail > nb ? avail - nb : 0;
-            left -= nb;
-            return v;
-        };
-        uint32_t s1 = rd(log), s2 = rd(log);
-        if (left < 0) WFAIL();
-        for (;;) {
-            if (nw > 253) WFAIL();
-            uint32_t e = S.tab[s1][lane];
-            put(e & 0xFFu);
-            s1 = (e >> 16) + rd((int)((e >> 8) & 0xFF));
-            if (left < 0) {
-                put(S.tab[s2][lane] & 0xFFu);
-                break;
-            }
-            if (nw > 253) WFAIL();
-            e = S.tab[s2][lane];
-            put(e & 0xFFu);
-            s2 = (e >> 16) + rd((int)((e >> 8) & 0xFF));
-            if (left < 0) {
-                put(S.tab[s1][lane] & 0xFFu);
-                break;
-            }
-        }
+    } src = { S, lane, g[0] };
+    struct Tab
+    {
+        WeightsLds& S;
+        int lane;
+        __device__ int norm(int s) const { return S.norm[s][lane]; }
+        __device__ void set_norm(int s, int c) const { S.norm[s][lane] = (int16_t)c; }
+        __device__ uint16_t& next(int s) const { return S.symnext[s][lane]; }
+        __device__ uint32_t& cell(int u) const { return S.tab[u][lane]; }
+        __device__ void entry(int u, uint32_t s, uint32_t nb, uint32_t base) const { S.tab[u][lane] = fse_entry(s, nb, base); }
+    } tab = { S, lane };
+    // (each weight is checked as it is produced: reading them back took one memory round trip per weight, 0.18 ms per launch whatever
+    // the number of trees, because every load stood behind the branch on the one before)
+    int nw = 0, tlog = 0;
+    if (huf_read_weights(src, (int)used, 11, tab, [&](int i, uint32_t w) { W[i] = (uint8_t)w; }, &nw, &tlog) < 0) {
+        redo[r] = 1;  // (-2, a 12-bit code, included: the careful decoder has the table for it)
+        return;
     }
-    // ---- the weights must describe a complete code (4.2.1): the last weight follows from the others
-    if (wide || total == 0) WFAIL();
-    const int tlog = hbit(total) + 1;
-    if (tlog > 11) WFAIL();  // (12-bit codes are legal: the careful decoder has the table for them)
-    const uint32_t rest = (1u << tlog) - total;
-    if (rest & (rest - 1)) WFAIL();
-    const uint32_t lastw = (uint32_t)hbit(rest) + 1;
-    W[nw++] = (uint8_t)lastw;
-    r1 += (lastw == 1);
-    if (r1 < 2 || (r1 & 1)) WFAIL();
     F->tlog[k] = (uint32_t)tlog;
-    F->nw[k] = nw;
-#undef WFAIL
+    F->nw[k] = (uint32_t)nw;
 }
 
 // ---- one wavefront per frame: the streams ---------------------------------------------------------------------------------------------
-// Table of a tree from its weight bytes: like huf_fill_table of zstd_decode.hip (cells by increasing weight, then symbol value; starts
-// from ballots), the cells per weight counted with ballots too.
-__device__ __forceinline__ void fast_fill_table(uint16_t* T, const uint8_t* W, uint32_t nw, uint32_t tlog, int lane)
-{
-    uint32_t wt[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t s = (uint32_t)lane + 64u * j;
-        wt[j] = s < nw ? W[s] : 0u;
-    }
-    uint32_t base[13];
-    {
-        uint32_t acc = 0;
-#pragma unroll
-        for (int v = 1; v <= 12; ++v) {
-            uint32_t c = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) c += (uint32_t)__popcll(__ballot(wt[j] == (uint32_t)v));
-            base[v] = acc;
-            acc += c << (v - 1);
-        }
-        base[0] = 0;
-    }
-    const uint64_t below = (1ull << lane) - 1ull;
-    uint32_t st[4], len[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        st[j] = 0;
-        len[j] = wt[j] ? 1u << (wt[j] - 1) : 0u;
-#pragma unroll
-        for (int v = 1; v <= 12; ++v) {
-            const uint64_t m = __ballot(wt[j] == (uint32_t)v);
-            if (wt[j] == (uint32_t)v) st[j] = base[v] + ((uint32_t)__popcll(m & below) << (v - 1));
-            base[v] += (uint32_t)__popcll(m) << (v - 1);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t s = (uint32_t)lane + 64u * j;
-        const uint16_t ent = (uint16_t)(s | ((tlog + 1 - wt[j]) << 8));
-        if (len[j] && len[j] < 64)
-            for (uint32_t i = 0; i < len[j]; ++i) T[st[j] + i] = ent;
-        uint64_t big = __ballot(len[j] >= 64);
-        while (big) {
-            const int src_lane = __ffsll((long long)big) - 1;
-            big &= big - 1;
-            const uint32_t bst = (uint32_t)__builtin_amdgcn_readlane((int)st[j], src_lane);
-            const uint32_t blen = (uint32_t)__builtin_amdgcn_readlane((int)len[j], src_lane);
-            const uint32_t bent = (uint32_t)__builtin_amdgcn_readlane((int)ent, src_lane);
-            for (uint32_t i = lane; i < blen; i += WAVE) T[bst + i] = (uint16_t)bent;
-        }
-    }
-}
-
 // Round 6: a 32-dword ring, 64-byte requests, a look at the ring's room every 16 symbols -- 13.5 KB of LDS per wavefront instead of 21.8:
 // eleven wavefronts per CU instead of seven.  The kernel is a chain of dependent LDS look-ups (two per symbol pair, ~220 cycles per symbol
 // and lane at seven wavefronts, VALU 25 - 44 % busy, LDS pipe 35 %): wavefronts in flight are what its throughput follows.  Looking at the
@@ -572,8 +384,8 @@ __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const F
             return;
         }
     }
-    fast_fill_table(T + tb0, weights + ((size_t)r * 2) * 256, F->nw[0], tlog0, lane);
-    if (ntree > 1) fast_fill_table(T + tb1, weights + ((size_t)r * 2 + 1) * 256, F->nw[1], tlog1, lane);
+    huf_fill_wave(T + tb0, weights + ((size_t)r * 2) * 256, F->nw[0], tlog0, lane);
+    if (ntree > 1) huf_fill_wave(T + tb1, weights + ((size_t)r * 2 + 1) * 256, F->nw[1], tlog1, lane);
     const uint8_t* src = b.src + b.src_off[r];
     uint8_t* dst = b.dst + b.dst_off[r];
     const bool mine = (uint32_t)lane < ntask;
@@ -956,7 +768,7 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
     if (tu > u || tu % b.n_reads != r || skip[tu]) LEAVE();
     const uint32_t tlog = frames[tu].tlog[0];
     if (tlog > 11 || tlog == 0) LEAVE();
-    fast_fill_table(T, weights + ((size_t)tu * 2) * 256, frames[tu].nw[0], tlog, lane);
+    huf_fill_wave(T, weights + ((size_t)tu * 2) * 256, frames[tu].nw[0], tlog, lane);
     const uint8_t* src = b.src + b.src_off[r];
     uint8_t* dst = b.dst + b.dst_off[r];
     // G = 16, 8 or 4 pieces a stream (the scan's choice): lanes [0, 4 G) each walk a piece, the others idle along (their piece is empty)

@@ -21,11 +21,13 @@
 // handle (more than REF_MAXBLK blocks with sequences, the zero-run blocks of zstd_encode.hip, a sequences header longer than REF_HDR
 // bytes, more sequences than its share of the workspace) -- is left with ok = 0 and the one-wavefront decoder treats it exactly as
 // before, which is also what produces every error verdict.  The accept conditions are those of general_sequence_records
-// (zstd_decode.hip) and of read_ncount / fse_build / seq_table there, restated per lane.
+// (zstd_decode.hip), restated per lane; the three table descriptions are read by zstd_tables.h's seq_table, the statement the
+// one-wavefront decoder instantiates too.
 #include <cstdlib>
 
 #include "vbz_kernels.h"
 #include "zstd_runs.h"
+#include "zstd_tables.h"
 
 namespace vbzhip {
 
@@ -104,20 +106,6 @@ __device__ __forceinline__ uint32_t get_cx(const RefLds<FPW, INLDS>& S, RefGloba
     if constexpr (INLDS) return S.t.cx[at][l];
     else return G.cx[at];
 }
-// the symbol of state u of the table under construction at t0
-template <int FPW, bool INLDS>
-__device__ __forceinline__ void sp_put(RefLds<FPW, INLDS>& S, int l, uint32_t t0, uint32_t u, uint32_t sym)
-{
-    if constexpr (INLDS) S.t.cx[t0 + u][l] = (uint8_t)sym;
-    else S.t.spread[u][l] = (uint8_t)sym;
-}
-template <int FPW, bool INLDS>
-__device__ __forceinline__ uint32_t sp_get(const RefLds<FPW, INLDS>& S, int l, uint32_t t0, uint32_t u)
-{
-    if constexpr (INLDS) return S.t.cx[t0 + u][l];
-    else return S.t.spread[u][l];
-}
-
 // bits [bitpos, bitpos + k) of the lane's staged header bytes, k <= 17 (little-endian bit order: RFC 8878 4.1.1)
 template <int FPW, bool INLDS>
 __device__ __forceinline__ uint32_t hdr_bits(const RefLds<FPW, INLDS>& S, int l, uint32_t bitpos, int k)
@@ -130,70 +118,6 @@ template <int FPW, bool INLDS>
 __device__ __forceinline__ uint32_t hdr_byte(const RefLds<FPW, INLDS>& S, int l, uint32_t i)
 {
     return (S.u.p.hdr[i >> 2][l] >> (8u * (i & 3u))) & 0xFFu;
-}
-
-// read_ncount of zstd_decode.hip for one lane: the description starts at byte `at` of the staged header, n bytes are there.
-// Returns bytes consumed or -1; fills the lane's norm[0..nsym).
-template <int FPW, bool INLDS>
-__device__ int ref_read_ncount(RefLds<FPW, INLDS>& S, int l, uint32_t at, int n, int max_symbol, int max_log, int* out_log, int* out_nsym)
-{
-    if (n < 1) return -1;
-    auto bits = [&](uint32_t bitpos, int k) -> uint32_t {  // bytes beyond n read as zero
-        const uint32_t avail = 8u * (uint32_t)n;
-        if (bitpos >= avail) return 0u;
-        uint32_t v = hdr_bits(S, l, 8u * at + bitpos, k);
-        if (bitpos + (uint32_t)k > avail) v &= (1u << (avail - bitpos)) - 1u;
-        return v;
-    };
-    const int log = (int)(hdr_byte(S, l, at) & 0xF) + 5;
-    if (log > max_log) return -1;
-    uint32_t bitpos = 4;
-    int remaining = (1 << log) + 1, threshold = 1 << log, nbits = log + 1, sym = 0;
-    bool prev0 = false;
-    while (remaining > 1 && sym <= max_symbol) {
-        if (bitpos > 8u * (uint32_t)n + 32u) return -1;  // (far beyond the description: stop; the byte count below fails anyway)
-        if (prev0) {
-            for (;;) {
-                const uint32_t rr = bits(bitpos, 2);
-                bitpos += 2;
-                for (uint32_t k = 0; k < rr; ++k) {
-                    if (sym > max_symbol) return -1;
-                    S.u.p.norm[sym++][l] = 0;
-                }
-                if (rr != 3) break;
-                if (bitpos > 8u * (uint32_t)n + 32u) return -1;
-            }
-            prev0 = false;
-            if (sym > max_symbol) break;
-            continue;
-        }
-        const int max = (2 * threshold - 1) - remaining;
-        const uint32_t v = bits(bitpos, nbits);
-        int count;
-        if ((int)(v & (uint32_t)(threshold - 1)) < max) {
-            count = (int)(v & (uint32_t)(threshold - 1));
-            bitpos += (uint32_t)(nbits - 1);
-        } else {
-            count = (int)(v & (uint32_t)(2 * threshold - 1));
-            if (count >= threshold) count -= max;
-            bitpos += (uint32_t)nbits;
-        }
-        count--;
-        remaining -= count < 0 ? -count : count;
-        S.u.p.norm[sym++][l] = (int16_t)count;
-        prev0 = (count == 0);
-        while (remaining < threshold) {
-            nbits--;
-            threshold >>= 1;
-        }
-    }
-    if (remaining != 1) return -1;
-    if (sym > max_symbol + 1) return -1;
-    const int used = (int)((bitpos + 7) >> 3);
-    if (used > n) return -1;
-    *out_log = log;
-    *out_nsym = sym;
-    return used;
 }
 
 // extra bits of a code: kind 0 literal lengths, 1 offsets, 2 match lengths
@@ -214,76 +138,44 @@ __device__ __forceinline__ void put_entry(RefLds<FPW, INLDS>& S, RefGlobal G, in
     }
 }
 
-// fse_build of zstd_decode.hip for one lane (RFC 8878 4.1.1), in place in the lane's table at `t0`
+// The table policy of zstd_tables.h for one lane: counts and state numbers in the lane's LDS columns, the table at t0 -- its cells
+// while it is spread in cx (INLDS) or in the spread column, its entries through put_entry
 template <int FPW, bool INLDS>
-__device__ bool ref_fse_build(RefLds<FPW, INLDS>& S, RefGlobal G, int l, uint32_t t0, int nsym, int log, int kind)
+struct RefFse
 {
-    const int size = 1 << log;
-    int high = size - 1;
-    for (int s = 0; s < nsym; ++s) {
-        const int c = S.u.p.norm[s][l];
-        if (c == -1) {
-            sp_put(S, l, t0, (uint32_t)high--, (uint32_t)s);
-            S.u.p.symnext[s][l] = 1;
-        } else {
-            S.u.p.symnext[s][l] = (uint16_t)c;
-        }
+    RefLds<FPW, INLDS>& S;
+    RefGlobal G;
+    int l;
+    uint32_t t0;
+    int kind;
+    __device__ int norm(int s) const { return S.u.p.norm[s][l]; }
+    __device__ void set_norm(int s, int c) const { S.u.p.norm[s][l] = (int16_t)c; }
+    __device__ uint16_t& next(int s) const { return S.u.p.symnext[s][l]; }
+    __device__ uint8_t& cell(int u) const
+    {
+        if constexpr (INLDS) return S.t.cx[t0 + (uint32_t)u][l];
+        else return S.t.spread[u][l];
     }
-    const int step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    int pos = 0;
-    for (int s = 0; s < nsym; ++s) {
-        const int c = S.u.p.norm[s][l];
-        for (int i = 0; i < c; ++i) {
-            sp_put(S, l, t0, (uint32_t)pos, (uint32_t)s);
-            do {
-                pos = (pos + step) & mask;
-            } while (pos > high);
-        }
-    }
-    if (pos != 0) return false;
-    for (int u = 0; u < size; ++u) {
-        const uint32_t s = sp_get(S, l, t0, (uint32_t)u);
-        const uint32_t ns = S.u.p.symnext[s][l];
-        S.u.p.symnext[s][l] = (uint16_t)(ns + 1);
-        const int nb = log - hbit(ns);
-        put_entry(S, G, l, t0 + (uint32_t)u, s, (uint32_t)nb, ((ns << nb) - (uint32_t)size) & 0x1FFu, kind);
-    }
-    return true;
-}
+    __device__ void entry(int u, uint32_t s, uint32_t nb, uint32_t base) const { put_entry(S, G, l, t0 + (uint32_t)u, s, nb, base & 0x1FFu, kind); }
+};
 
-// seq_table of zstd_decode.hip for one lane.  Returns bytes consumed from the staged header at `at`, or -1.
+// one sequence table for one lane: zstd_tables.h's seq_table over the staged header from byte `at` (n bytes there) into the lane's
+// table at t0.  Returns bytes consumed, or -1.
 template <int FPW, bool INLDS>
 __device__ int ref_seq_table(RefLds<FPW, INLDS>& S, RefGlobal G, int l, uint32_t t0, int* log_io, bool* have, int mode, uint32_t at, int n, int kind)
 {
     const int16_t* def = kind == 0 ? LL_DEFAULT : (kind == 1 ? OF_DEFAULT : ML_DEFAULT);
     const int def_n = kind == 0 ? 36 : (kind == 1 ? 29 : 53), def_log = kind == 1 ? 5 : 6;
     const int max_sym = kind == 0 ? 35 : (kind == 1 ? 31 : 52), max_log = kind == 1 ? 8 : 9;
-    if (mode == 0) {
-        for (int i = 0; i < def_n; ++i) S.u.p.norm[i][l] = def[i];
-        if (!ref_fse_build(S, G, l, t0, def_n, def_log, kind)) return -1;
-        *log_io = def_log;
-        *have = true;
-        return 0;
-    }
-    if (mode == 1) {
-        if (n < 1) return -1;
-        const uint32_t code = hdr_byte(S, l, at);
-        if (code > (uint32_t)max_sym) return -1;
-        put_entry(S, G, l, t0, code, 0u, 0u, kind);
-        *log_io = 0;
-        *have = true;
-        return 1;
-    }
-    if (mode == 2) {
-        int log, nsym;
-        const int used = ref_read_ncount(S, l, at, n, max_sym, max_log, &log, &nsym);
-        if (used < 0) return -1;
-        if (!ref_fse_build(S, G, l, t0, nsym, log, kind)) return -1;
-        *log_io = log;
-        *have = true;
-        return used;
-    }
-    return *have ? 0 : -1;
+    auto bits = [&](uint32_t bitpos, int k) -> uint32_t {  // bytes beyond n read as zero
+        const uint32_t avail = 8u * (uint32_t)n;
+        if (bitpos >= avail) return 0u;
+        uint32_t v = hdr_bits(S, l, 8u * at + bitpos, k);
+        if (bitpos + (uint32_t)k > avail) v &= (1u << (avail - bitpos)) - 1u;
+        return v;
+    };
+    RefFse<FPW, INLDS> t = { S, G, l, t0, kind };
+    return seq_table(t, bits, mode, n, def, def_n, def_log, max_sym, max_log, log_io, have);
 }
 
 // The 64 bits that follow bit s (counted from the top, s <= 127) of the 128-bit value hi:lo
