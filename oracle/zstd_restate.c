@@ -368,35 +368,35 @@ static int seq_table(fse_table* t, int* have, int mode, const uint8_t** pp, cons
 
 /* decode one compressed block into out[base..]; `base` bytes of history precede it in out.
  * Bytes at positions >= cap are not stored (but the block is still fully validated). */
-static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t* out, size_t base, size_t cap, uint8_t* lit)
+/* literals section header (RFC 8878 3.1.1.3.1.1) of the n >= 1 bytes at src: the header's bytes, or -1 if they are not all there;
+ * csize is 0 for raw and RLE literals */
+static int lit_header(const uint8_t* src, size_t n, int* type_out, size_t* regen_out, size_t* csize_out, int* streams_out)
 {
-    if (n < 1) return ZR_ERR;
-    /* ---- literals section header, RFC 8878 3.1.1.3.1.1 */
     int type = src[0] & 3, fmt = (src[0] >> 2) & 3;
     size_t hsz, regen, csize = 0;
     int streams = 1;
     if (type < 2) {
         if (fmt == 0 || fmt == 2) { hsz = 1; regen = src[0] >> 3; }
-        else if (fmt == 1) { hsz = 2; if (n < 2) return ZR_ERR; regen = (src[0] >> 4) | ((size_t)src[1] << 4); }
-        else { hsz = 3; if (n < 3) return ZR_ERR; regen = (src[0] >> 4) | ((size_t)src[1] << 4) | ((size_t)src[2] << 12); }
+        else if (fmt == 1) { hsz = 2; if (n < 2) return -1; regen = (src[0] >> 4) | ((size_t)src[1] << 4); }
+        else { hsz = 3; if (n < 3) return -1; regen = (src[0] >> 4) | ((size_t)src[1] << 4) | ((size_t)src[2] << 12); }
     } else {
         if (fmt < 2) {
             hsz = 3;
-            if (n < 3) return ZR_ERR;
+            if (n < 3) return -1;
             uint32_t v = src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16);
             regen = (v >> 4) & 0x3FF;
             csize = v >> 14;
             streams = fmt == 0 ? 1 : 4;
         } else if (fmt == 2) {
             hsz = 4;
-            if (n < 4) return ZR_ERR;
+            if (n < 4) return -1;
             uint32_t v = src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16) | ((uint32_t)src[3] << 24);
             regen = (v >> 4) & 0x3FFF;
             csize = v >> 18;
             streams = 4;
         } else {
             hsz = 5;
-            if (n < 5) return ZR_ERR;
+            if (n < 5) return -1;
             uint64_t v = src[0] | ((uint64_t)src[1] << 8) | ((uint64_t)src[2] << 16) | ((uint64_t)src[3] << 24) |
                          ((uint64_t)src[4] << 32);
             regen = (size_t)((v >> 4) & 0x3FFFF);
@@ -404,6 +404,67 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
             streams = 4;
         }
     }
+    *type_out = type;
+    *regen_out = regen;
+    *csize_out = csize;
+    *streams_out = streams;
+    return (int)hsz;
+}
+
+/* Number_of_Sequences (RFC 8878 3.1.1.3.2.1) of the n bytes at p: the field's bytes, or -1 */
+static int read_nseq(const uint8_t* p, size_t n, size_t* nseq_out)
+{
+    if (n < 1) return -1;
+    size_t nseq = p[0];
+    int used = 1;
+    if (nseq >= 128) {
+        if (nseq == 255) {
+            if (n < 3) return -1;
+            nseq = (size_t)p[1] + ((size_t)p[2] << 8) + 0x7F00;
+            used = 3;
+        } else {
+            if (n < 2) return -1;
+            nseq = ((nseq - 128) << 8) + p[1];
+            used = 2;
+        }
+    }
+    *nseq_out = nseq;
+    return used;
+}
+
+/* test helpers: the two as decode_block reads them.  vbo_debug_lit_header: out[] = { type, regenerated size, compressed size (raw: the
+ * regenerated size, RLE: 1), streams } */
+int vbo_debug_lit_header(const uint8_t* src, size_t n, uint32_t* out)
+{
+    int type, streams;
+    size_t regen, csize;
+    if (n < 1) return -1;
+    const int hsz = lit_header(src, n, &type, &regen, &csize, &streams);
+    if (hsz < 0) return -1;
+    out[0] = (uint32_t)type;
+    out[1] = (uint32_t)regen;
+    out[2] = (uint32_t)(type == 0 ? regen : (type == 1 ? 1 : csize));
+    out[3] = (uint32_t)streams;
+    return hsz;
+}
+
+int vbo_debug_nseq(const uint8_t* p, size_t n, uint32_t* nseq)
+{
+    size_t ns;
+    const int used = read_nseq(p, n, &ns);
+    if (used >= 0) *nseq = (uint32_t)ns;
+    return used;
+}
+
+static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t* out, size_t base, size_t cap, uint8_t* lit)
+{
+    if (n < 1) return ZR_ERR;
+    /* ---- literals section header, RFC 8878 3.1.1.3.1.1 */
+    int type, streams;
+    size_t regen, csize;
+    const int hh = lit_header(src, n, &type, &regen, &csize, &streams);
+    if (hh < 0) return ZR_ERR;
+    const size_t hsz = (size_t)hh;
     if (regen > ZR_BLOCK_MAX) return ZR_ERR;
     const uint8_t* p = src + hsz;
     const uint8_t* end = src + n;
@@ -447,17 +508,10 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
     }
     /* ---- sequences section header, RFC 8878 3.1.1.3.2.1 */
     if (p >= end) return ZR_ERR;
-    size_t nseq = *p++;
-    if (nseq >= 128) {
-        if (nseq == 255) {
-            if (end - p < 2) return ZR_ERR;
-            nseq = (size_t)p[0] + ((size_t)p[1] << 8) + 0x7F00;
-            p += 2;
-        } else {
-            if (end - p < 1) return ZR_ERR;
-            nseq = ((nseq - 128) << 8) + *p++;
-        }
-    }
+    size_t nseq;
+    const int nu = read_nseq(p, (size_t)(end - p), &nseq);
+    if (nu < 0) return ZR_ERR;
+    p += nu;
     size_t opos = base; /* logical output position */
     size_t lpos = 0;
 #define PUT(byte_expr)                                    \

@@ -1,6 +1,6 @@
-"""Host harness around vbz_compression_amd/csrc/zstd_entropy.h and zstd_tables.h (tests only): the serial
-statements of the Huffman table construction and of the decoders' table readers, compiled with g++, driven
-through ctypes."""
+"""Host harness around vbz_compression_amd/csrc/zstd_entropy.h, zstd_tables.h and zstd_frame.h (tests only): the
+serial statements of the Huffman table construction and of the decoders' table and header readers, compiled with
+g++, driven through ctypes."""
 import ctypes
 import os
 import subprocess
@@ -12,6 +12,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host", "entropy_harness.cpp")
 HDR = os.path.join(ROOT, "vbz_compression_amd", "csrc", "zstd_entropy.h")
 TABLES = os.path.join(ROOT, "vbz_compression_amd", "csrc", "zstd_tables.h")
+FRAME = os.path.join(ROOT, "vbz_compression_amd", "csrc", "zstd_frame.h")
 SO = os.path.join(HERE, "host", "libentropy_harness.so")
 _lib = None
 
@@ -19,7 +20,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or max(os.path.getmtime(f) for f in (SRC, HDR, TABLES)) > os.path.getmtime(SO):
+        if not os.path.exists(SO) or max(os.path.getmtime(f) for f in (SRC, HDR, TABLES, FRAME)) > os.path.getmtime(SO):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + os.path.dirname(HDR), "-o", SO, SRC])
         _lib = ctypes.CDLL(SO)
     return _lib

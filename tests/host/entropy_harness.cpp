@@ -1,10 +1,11 @@
 // Host harness (tests only): exposes the serial table-construction functions of
 // vbz_compression_amd/csrc/zstd_entropy.h to ctypes so the CPU suite can check them against
-// what libzstd emits for the same histogram, and the table readers of zstd_tables.h to check them
-// against the oracle's restatement.  Built by tests/entropy_host.py with g++.
+// what libzstd emits for the same histogram, the table readers of zstd_tables.h to check them
+// against the oracle's restatement, and the header readers of zstd_frame.h.  Built by tests/entropy_host.py with g++.
 #include <cstring>
 #include "zstd_entropy.h"
 #include "zstd_tables.h"
+#include "zstd_frame.h"
 #include "zstd_reference_huffman.h"   // libzstd's construction: the yardstick (BSD notice inside)
 
 using namespace vbzhip;
@@ -69,6 +70,65 @@ int h_huf_read_weights(const uint8_t* p, int n, int max_log, uint8_t* weights, i
     } src = { p, n > 0 ? p[0] : 0 };
     static HostFse t;
     return huf_read_weights(src, n, max_log, t, [&](int i, uint32_t w) { weights[i] = (uint8_t)w; }, nw, log);
+}
+
+// zstd_frame.h over plain byte arrays.  h_frame_header: 1 if the header ends inside the n bytes; out[] = { magic, fhd, len, wlog,
+// did_bytes, did, fcs_bytes, checksum }, big[] = { fcs, window }
+int h_frame_header(const uint8_t* p, uint32_t n, uint32_t* out, uint64_t* big)
+{
+    ZFrameHeader h;
+    const bool whole = zstd_frame_header([&](uint32_t i) { return (uint32_t)p[i]; }, n, &h);
+    const uint32_t o[8] = { h.magic, h.fhd, h.len, h.wlog, h.did_bytes, h.did, h.fcs_bytes, h.checksum };
+    memcpy(out, o, sizeof(o));
+    big[0] = h.fcs;
+    big[1] = h.window;
+    return whole ? 1 : 0;
+}
+
+// out[] = { last, type, size, src }
+void h_block_header(uint32_t bh, uint32_t* out)
+{
+    const ZBlockHeader k = zstd_block_header(bh);
+    out[0] = k.last;
+    out[1] = k.type;
+    out[2] = k.size;
+    out[3] = k.src;
+}
+
+// out[] = { type, fmt, hsize, regen, csize, streams }
+void h_lit_header(uint64_t v, uint32_t* out)
+{
+    const ZLitHeader l = zstd_lit_header(v);
+    const uint32_t o[6] = { l.type, l.fmt, l.hsize, l.regen, l.csize, l.streams };
+    memcpy(out, o, sizeof(o));
+}
+
+uint32_t h_nseq(const uint8_t* p, uint32_t n, uint32_t* used)
+{
+    return zstd_nseq([&](uint32_t i) { return (uint32_t)p[i]; }, n, used);
+}
+
+uint32_t h_huf_desc_size(uint32_t hb) { return huf_desc_size(hb); }
+
+static uint32_t le32(const uint8_t* p, uint32_t o)
+{
+    uint32_t v;
+    memcpy(&v, p + o, 4);
+    return v;
+}
+
+// out[] = { off, count, spacing }
+void h_checkpoints(const uint8_t* p, uint32_t n, uint32_t* out)
+{
+    const ZCheckpoints c = zstd_checkpoints([&](uint32_t o) { return le32(p, o); }, n);
+    out[0] = c.off;
+    out[1] = c.count;
+    out[2] = c.spacing;
+}
+
+uint32_t h_skip_frames(const uint8_t* p, uint32_t pos, uint32_t n)
+{
+    return zstd_skip_frames([&](uint32_t o) { return le32(p, o); }, pos, n);
 }
 
 int h_huf_write_tree(uint8_t* dst, int cap, const uint8_t* nbBits, uint32_t maxSymbolValue, uint32_t huffLog)

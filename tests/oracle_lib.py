@@ -103,6 +103,10 @@ def lib():
         L.vbo_debug_fse_build.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
         L.vbo_debug_huf_lengths.restype = ctypes.c_int
         L.vbo_debug_huf_lengths.argtypes = [vp, sz, vp, ctypes.POINTER(ctypes.c_int)]
+        L.vbo_debug_lit_header.restype = ctypes.c_int
+        L.vbo_debug_lit_header.argtypes = [vp, sz, vp]
+        L.vbo_debug_nseq.restype = ctypes.c_int
+        L.vbo_debug_nseq.argtypes = [vp, sz, vp]
         L.vbo_fuzz_max_destination.restype = u32
         L.vbo_fuzz_max_destination.argtypes = [u32, op]
         L.vbo_fuzz_decompress_sweep.restype = ctypes.c_int

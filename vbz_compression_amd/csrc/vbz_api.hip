@@ -1901,11 +1901,11 @@ static int decode_paths_one(vbz_gpu_ctx* c, uint32_t* batched, uint32_t* walked)
     if (c->trace && !pre.empty()) {  // why frames of other writers were left to the one-wavefront decoder (zstd_decode_ref.hip: BAIL)
         std::map<uint32_t, uint32_t> why;
         for (uint32_t i = 0; i < n; ++i)
-            if (redo[i] && !pre[i].ok) ++why[pre[i].pad[0]];
+            if (redo[i] && !pre[i].ok) ++why[pre[i].why];
         for (auto& e : why) fprintf(stderr, "vbz_hip: chains not walked: reason %u, %u frame(s)\n", e.first, e.second);
         double tb = 0, ch = 0, ns = 0;
         for (uint32_t i = 0; i < n; ++i)
-            if (pre[i].ok) tb += pre[i].pad[1], ch += pre[i].pad[2], ns += pre[i].pad[3];
+            if (pre[i].ok) tb += pre[i].tab_cycles, ch += pre[i].chain_cycles, ns += pre[i].nseq_last;
         if (nw) fprintf(stderr, "vbz_hip: walked chains: %u frames, last block: %.0f cycles for the tables, %.0f for the chain, %.0f sequences\n", nw, tb / nw, ch / nw, ns / nw);
     }
     if (batched) *batched = nb;

@@ -247,7 +247,10 @@ struct RefBlock
 };
 struct RefPre
 {
-    uint32_t ok, nblk, pad[6];
+    uint32_t ok, nblk;
+    uint32_t why;                                // BAIL: why the frame was left alone (diagnostics, VBZ_HIP_TRACE)
+    uint32_t tab_cycles, chain_cycles, nseq_last;   // the frame's last block: cycles of its tables and of its chain, its sequences
+    uint32_t pad[2];
     RefBlock blk[REF_MAXBLK];
 };
 // The literals of a reference-written frame's first block, decoded ahead of the one-wavefront decoder BESIDE the chain walk (the walk is a

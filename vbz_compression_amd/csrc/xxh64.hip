@@ -8,6 +8,7 @@
 // The serial statement of the same steps, which the kernel must agree with, is xxh64.h.
 #include "vbz_kernels.h"
 #include "xxh64.h"
+#include "zstd_frame.h"
 
 namespace vbzhip {
 
@@ -79,17 +80,16 @@ __global__ __launch_bounds__(256) void xxh64_batch_kernel(const uint8_t* src, co
 __device__ uint32_t frame_blocks_end(const uint8_t* f, uint32_t n)
 {
     if (n < 6) return 0;
-    const uint32_t fhd = f[4];
-    const uint32_t single = (fhd >> 5) & 1, fcs_flag = fhd >> 6, did = fhd & 3;
-    uint32_t pos = 5 + (single ? 0u : 1u) + (did == 3 ? 4u : did) + (fcs_flag == 0 ? (single ? 1u : 0u) : (1u << fcs_flag));
-    for (;;) {
+    auto at = [&](uint32_t i) { return (uint32_t)f[i]; };
+    ZFrameHeader h;
+    zstd_frame_header(at, n, &h);
+    for (uint32_t pos = h.len;;) {
         if ((uint64_t)pos + 3 > n) return 0;
-        const uint32_t bh = f[pos] | ((uint32_t)f[pos + 1] << 8) | ((uint32_t)f[pos + 2] << 16);
-        const uint32_t btype = (bh >> 1) & 3, bsize = bh >> 3;
-        const uint64_t next = (uint64_t)pos + 3 + (btype == 1 ? 1u : bsize);
+        const ZBlockHeader bk = zstd_block_header(at(pos) | (at(pos + 1) << 8) | (at(pos + 2) << 16));
+        const uint64_t next = (uint64_t)pos + 3 + bk.src;
         if (next > n) return 0;
         pos = (uint32_t)next;
-        if (bh & 1) return pos;
+        if (bk.last) return pos;
     }
 }
 

@@ -24,6 +24,7 @@
 #include "vbz_kernels.h"
 #include "svb_wave.h"
 #include "zstd_runs.h"
+#include "zstd_frame.h"
 #include "zstd_tables.h"
 
 namespace vbzhip {
@@ -179,6 +180,41 @@ __device__ __noinline__ int seq_table(uint32_t* tab, int* log_io, bool* have, in
     DecFse t = { tab };
     return vbzhip::seq_table(t, [&](uint32_t pos, int k) { return le_bits(p, n, pos, k); }, mode, n, def, def_n, def_log, max_sym, max_log,
                              log_io, have);
+}
+
+// lane 0: the sequences section header (3.1.1.3.2.1) of a section of sqn bytes, staged in L.u.p.hbuf -- Number_of_Sequences, the modes
+// and the three tables, in L.u.p.fse.  L.ctl[C_ERR] = 0, 1 (a bad header) or 3 (lost: a repeated table that a ring flush has overwritten --
+// decode the frame again, carefully); L.ctl[C_I] = the number of sequences, L.ctl[C_J] = the header's bytes.
+__device__ __noinline__ void seq_section_header(uint32_t sqn, bool lost, int& log_ll, bool& have_ll, int& log_of, bool& have_of, int& log_ml,
+                                                   bool& have_ml)
+{
+    uint32_t err = 0, used;
+    const uint8_t* h = L.u.p.hbuf;
+    const int hn = (int)(sqn < HBUF ? sqn : HBUF);
+    const uint32_t ns = zstd_nseq([&](uint32_t i) { return (uint32_t)h[i]; }, (uint32_t)hn, &used);
+    if (used == 0 || (int)used >= hn) err = 1;
+    if (!err) {
+        const uint32_t modes = h[used++];
+        if (modes & 3) err = 1;
+        if (!err && lost && (((modes >> 6) & 3) == 3 || ((modes >> 4) & 3) == 3 || ((modes >> 2) & 3) == 3)) err = 3;
+        int u;
+        if (!err) {
+            u = seq_table(L.u.p.fse[0], &log_ll, &have_ll, (modes >> 6) & 3, h + used, hn - (int)used, LL_DEFAULT, 36, 6, 35, 9);
+            if (u < 0) err = 1; else used += (uint32_t)u;
+        }
+        if (!err) {
+            u = seq_table(L.u.p.fse[1], &log_of, &have_of, (modes >> 4) & 3, h + used, hn - (int)used, OF_DEFAULT, 29, 5, 31, 8);
+            if (u < 0) err = 1; else used += (uint32_t)u;
+        }
+        if (!err) {
+            u = seq_table(L.u.p.fse[2], &log_ml, &have_ml, (modes >> 2) & 3, h + used, hn - (int)used, ML_DEFAULT, 53, 6, 52, 9);
+            if (u < 0) err = 1; else used += (uint32_t)u;
+        }
+        if (!err && used >= sqn) err = 1;
+    }
+    L.ctl[C_ERR] = err;
+    L.ctl[C_I] = ns;
+    L.ctl[C_J] = used;
 }
 
 // Huffman tree description -> weights in L.weights (lane 0): zstd_tables.h's huf_read_weights. returns bytes consumed or -1; sets nw/log
@@ -1305,7 +1341,6 @@ constexpr uint32_t DSPAN_WHOLE = 1, DSPAN_LAST = 2, DSPAN_FIRST = 4;
 // block did (status word 3: DSPAN_ST_*), and a frame stands only if T brought its tree in its first block and nowhere else, and no
 // span behind T brought any: then the table in force at every span behind T is T's, by the frame's own rules.
 constexpr uint32_t DSPAN_ST_REP1 = 1, DSPAN_ST_TREE_FIRST = 2, DSPAN_ST_TREE_LATER = 4;
-constexpr uint32_t IDX_MAGIC = 0x184D2A5Cu;      // zstd_encode.hip: the span index trailer
 constexpr uint32_t DSPAN_MIN_CONTENT = 4u << 10;    // an honest index has at most fcs / this + 4 spans (the writer's shortest spans hold 4 KB of control bytes)
 // A span whose block carries zero-run sequences stages its literals and (literal, match) length pairs behind the frame's
 // content in the destination slot, in a stripe of its own: DSPAN_WS_FACTOR bytes per byte of its content (literals <= content, eight
@@ -1387,48 +1422,21 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
     // ---- frame header (RFC 8878 3.1.1.1)
     stage_bytes(L.u.p.hbuf, src, n < 32 ? n : 32, lane);
     if (lane == 0) {
-        uint32_t err = 0, pos = 0;
-        uint64_t fcs = 0, window = 0;
-        const uint8_t* h = L.u.p.hbuf;
+        uint32_t err = 0;
+        ZFrameHeader h;
         if (n < 6) err = 1;
         if (!err) {
-            const uint32_t magic = h[0] | (h[1] << 8) | (h[2] << 16) | ((uint32_t)h[3] << 24);
-            const uint32_t fhd = h[4];
-            const int fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, did_flag = fhd & 3;
-            if (magic != 0xFD2FB528u || (fhd & 0x08)) err = 1;
-            pos = 5;
-            if (!single) {
-                const uint32_t wd = h[pos++];
-                const int wlog = 10 + (int)(wd >> 3);
-                if (wlog > 31) err = 1;
-                window = (1ull << wlog) + ((1ull << wlog) >> 3) * (wd & 7);
-            }
-            // Dictionary_ID field (0, 1, 2 or 4 bytes): the value 0 means "no dictionary" and is accepted like libzstd does;
-            // any other dictionary is one this decoder does not have (libzstd: dictionary_wrong), reported behind the
-            // content-size check like ZSTD_getFrameContentSize + ZSTD_decompress would (vbz.cpp:236-273)
-            bool foreign_dict = false;
-            {
-                const uint32_t dsz = did_flag == 3 ? 4u : (uint32_t)did_flag;
-                if (pos + dsz > n) err = 1;
-                else
-                    for (uint32_t i = 0; i < dsz; ++i) foreign_dict |= h[pos + i] != 0;
-                pos += dsz;
-            }
-            const int fsz = fcs_flag == 0 ? (single ? 1 : 0) : (fcs_flag == 1 ? 2 : (fcs_flag == 2 ? 4 : 8));
-            if (fsz == 0) err = 1;  // unknown content size: the reference rejects it too (vbz.cpp:236-240)
-            if (pos + fsz > n) err = 1;
-            if (!err) {
-                for (int i = 0; i < fsz; ++i) fcs |= (uint64_t)h[pos + i] << (8 * i);
-                if (fsz == 2) fcs += 256;
-                pos += fsz;
-                if (single) window = fcs;
-                if (!err && fcs > cap) err = 2;  // dstSize_tooSmall
-                if (!err && foreign_dict) err = 1;
-            }
-            L.ctl[C_A] = pos;
-            L.ctl[C_B] = (uint32_t)fcs;
-            L.ctl[C_C] = (uint32_t)(window < BLOCK_MAX ? window : BLOCK_MAX);
-            L.ctl[C_D] = (fhd >> 2) & 1;
+            // Dictionary_ID field: the value 0 means "no dictionary" and is accepted like libzstd does; any other dictionary is one this
+            // decoder does not have (libzstd: dictionary_wrong), reported behind the content-size check like ZSTD_getFrameContentSize +
+            // ZSTD_decompress would (vbz.cpp:236-273).  No content size: the reference rejects it too (vbz.cpp:236-240).
+            const bool whole = zstd_frame_header([&](uint32_t i) { return (uint32_t)L.u.p.hbuf[i]; }, n, &h);
+            if (!whole || h.magic != ZSTD_MAGIC || (h.fhd & 0x08) || h.wlog > 31 || h.fcs_bytes == 0) err = 1;
+            else if (h.fcs > cap) err = 2;  // dstSize_tooSmall
+            else if (h.did != 0) err = 1;
+            L.ctl[C_A] = h.len;
+            L.ctl[C_B] = (uint32_t)h.fcs;
+            L.ctl[C_C] = (uint32_t)(h.window < BLOCK_MAX ? h.window : BLOCK_MAX);
+            L.ctl[C_D] = h.checksum;
         }
         L.ctl[C_ERR] = err;
     }
@@ -1445,30 +1453,9 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
     const uint32_t has_checksum = L.ctl[C_D];
 
     // the encoder's checkpoint trailer (a skippable frame that ends the buffer), if any: see zero_run_chain_segments
-    const uint8_t* cp_tab = nullptr;
-    uint32_t cp_count = 0, cp_spacing = 0;
-    if (n >= 64) {
-        uint32_t tb, ne = n;  // ne: where the checkpoint trailer would end (an index trailer may follow it)
-        __builtin_memcpy(&tb, src + n - 4, 4);
-        if (tb >= 24 && tb <= n - 16 && (tb & 7u) == 0) {  // (n >= 64; no sum that could wrap: these are arbitrary bytes)
-            uint32_t m[2];
-            __builtin_memcpy(m, src + n - tb, 8);
-            if (m[0] == IDX_MAGIC && m[1] == tb - 8) {
-                ne = n - tb;
-                __builtin_memcpy(&tb, src + ne - 4, 4);
-            }
-        }
-        if (tb >= 20 && tb <= 8 + 4 + 4 * 63 + 4 && tb + 16 <= ne) {
-            uint32_t m[3];
-            __builtin_memcpy(m, src + ne - tb, 12);
-            const uint32_t cnt = m[2] >> 16;
-            if (m[0] == 0x184D2A5Bu && m[1] == tb - 8 && tb == 16 + 4 * cnt && cnt >= 1) {
-                cp_tab = src + ne - tb + 12;
-                cp_count = cnt;
-                cp_spacing = m[2] & 0xFFFFu;
-            }
-        }
-    }
+    const ZCheckpoints cp = zstd_checkpoints([&](uint32_t o) { uint32_t v; __builtin_memcpy(&v, src + o, 4); return v; }, n);
+    const uint8_t* cp_tab = cp.count ? src + cp.off : nullptr;
+    const uint32_t cp_count = cp.count, cp_spacing = cp.spacing;
     // a frame whose sequence chains are already walked (zstd_decode_ref.hip): its records are taken, nothing else changes
     const RefPre* mypre = (chains.pre != nullptr && !dspans && chains.pre[r].ok) ? chains.pre + r : nullptr;
     const uint32_t first_block = partial ? sp.src_pos : pos;
@@ -1531,13 +1518,13 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
             const uint32_t sh = 8u * (o & 7u);
             return sh ? ((a >> sh) | (c << (64u - sh))) : a;
         };
-        const uint32_t bh = (uint32_t)H0 & 0xFFFFFFu;
+        const ZBlockHeader bk = zstd_block_header((uint32_t)H0);
         pos += 3;
-        const uint32_t last = bh & 1, btype = (bh >> 1) & 3, bsize = bh >> 3;
+        const uint32_t last = bk.last, btype = bk.type, bsize = bk.size;
         if (btype == 3 || (SPANS && tree_only && btype != 2)) FAIL();
         pf_ok = false;
         if (!last) {
-            const uint64_t nextpos = (uint64_t)pos + (btype == 1 ? 1u : bsize);
+            const uint64_t nextpos = (uint64_t)pos + bk.src;
             if (nextpos + 3 <= n) {
                 pf_byte = (lane < 24 && nextpos + (uint32_t)lane < n) ? src[nextpos + (uint32_t)lane] : 0u;
                 pf_ok = true;
@@ -1549,13 +1536,9 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
         // later.  Anything else about the block sends it down the general path.
         bool quick = false;
         if (btype == 2 && huf_valid && ntask + 4 <= (uint32_t)WAVE && bsize >= 5 && bsize < BLOCK_MAX && (uint64_t)pos + bsize <= n) {
-            const uint64_t v = hwin(3);
-            const uint32_t h0 = (uint32_t)v & 0xFF, fmt = (h0 >> 2) & 3;
-            if ((h0 & 3) == 3 && fmt != 0) {
-                uint32_t lh, regen, csize;
-                if (fmt == 1) { lh = 3; regen = (uint32_t)(v >> 4) & 0x3FF; csize = (uint32_t)(v >> 14) & 0x3FF; }
-                else if (fmt == 2) { lh = 4; regen = (uint32_t)(v >> 4) & 0x3FFF; csize = (uint32_t)(v >> 18) & 0x3FFF; }
-                else { lh = 5; regen = (uint32_t)(v >> 4) & 0x3FFFF; csize = (uint32_t)(v >> 22) & 0x3FFFF; }
+            const ZLitHeader lit = zstd_lit_header(hwin(3));
+            if (lit.type == 3 && lit.fmt != 0) {
+                const uint32_t lh = lit.hsize, regen = lit.regen, csize = lit.csize;
                 const uint64_t j = hwin(3 + lh);
                 const uint32_t s1 = (uint32_t)j & 0xFFFFu, s2 = (uint32_t)(j >> 16) & 0xFFFFu, s3 = (uint32_t)(j >> 32) & 0xFFFFu;
                 const uint32_t seg = (regen + 3) >> 2;
@@ -1607,28 +1590,13 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
             if (bsize >= BLOCK_MAX || pos + bsize > n || bsize < 2) FAIL();
             const uint8_t* blk = src + pos;
             // ---- literals section header (3.1.1.3.1.1), parsed by every lane from the staged bytes
-            uint32_t ltype, lh = 0, regen = 0, csize = 0, streams = 1, tree_used = 0, nw = 0, tlog = 0;
+            const ZLitHeader lit = zstd_lit_header(hwin(3));  // h[0..7] of the literals section
+            const uint32_t ltype = lit.type, lh = lit.hsize, regen = lit.regen, csize = lit.csize, streams = lit.streams;
+            uint32_t tree_used = 0, nw = 0, tlog = 0;
             uint32_t jt[3] = { 0, 0, 0 };  // jump table when it sits right behind the header (treeless blocks)
             {
-                const uint64_t v = hwin(3);  // h[0..7] of the literals section
-                const uint32_t h0 = (uint32_t)v & 0xFF;
-                const uint32_t fmt = (h0 >> 2) & 3;
-                ltype = h0 & 3;
-                if (ltype < 2) {
-                    if (fmt == 0 || fmt == 2) { lh = 1; regen = h0 >> 3; }
-                    else if (fmt == 1) { lh = 2; regen = ((uint32_t)v & 0xFFFFu) >> 4; }
-                    else { lh = 3; regen = ((uint32_t)v & 0xFFFFFFu) >> 4; }
-                    if (lh > bsize) FAIL();
-                    csize = ltype == 0 ? regen : 1;
-                } else {
-                    if (bsize < 5) FAIL();  // libzstd: srcSize >= 5 for compressed literals
-                    if (fmt < 2) { lh = 3; regen = (uint32_t)(v >> 4) & 0x3FF; csize = (uint32_t)(v >> 14) & 0x3FF; streams = fmt == 0 ? 1 : 4; }
-                    else if (fmt == 2) { lh = 4; regen = (uint32_t)(v >> 4) & 0x3FFF; csize = (uint32_t)(v >> 18) & 0x3FFF; streams = 4; }
-                    else { lh = 5; regen = (uint32_t)(v >> 4) & 0x3FFFF; csize = (uint32_t)(v >> 22) & 0x3FFFF; streams = 4; }
-                    if (regen == 0 || csize == 0) FAIL();
-                }
-                if (regen > BLOCK_MAX) FAIL();
-                if ((uint64_t)lh + csize > bsize) FAIL();
+                // (libzstd: srcSize >= 5 for compressed literals)
+                if ((ltype < 2 ? lh > bsize : (bsize < 5 || regen == 0 || csize == 0)) || regen > BLOCK_MAX || (uint64_t)lh + csize > bsize) FAIL();
                 if (ltype == 3 && !huf_valid) FAIL();
                 if (ltype == 3) {
                     const uint64_t j = hwin(3 + lh);
@@ -1725,8 +1693,8 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
                 if (d_active) FLUSH();
                 uint32_t go = 0;
                 if (lane == 0 && sqn >= 4) {
-                    const uint32_t used0 = nseq < 128 ? 1u : (nseq < 255 ? 2u : 3u);
-                    const uint32_t ns0 = nseq < 128 ? nseq : (nseq < 255 ? ((nseq - 128) << 8) + SQB(1) : SQB(1) + (SQB(2) << 8) + 0x7F00);
+                    uint32_t used0;
+                    const uint32_t ns0 = zstd_nseq([&](uint32_t i) { return SQB(i); }, sqn, &used0);
                     if (used0 + 2 < sqn) {
                         const uint32_t modes = SQB(used0);
                         const uint32_t llm = modes >> 6, ofm = (modes >> 4) & 3;
@@ -1761,7 +1729,8 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
             bool par = false;
             uint32_t ws_plit = 0, ws_seq = 0;
             if (has_seq && !defer) {
-                const uint32_t ns_hdr = nseq < 128 ? nseq : (nseq < 255 ? ((nseq - 128) << 8) + SQB(1) : SQB(1) + (SQB(2) << 8) + 0x7F00);
+                uint32_t used_hdr;   // (the count its bytes say: the header is checked where it is read)
+                const uint32_t ns_hdr = zstd_nseq([&](uint32_t i) { return SQB(i); }, 3u, &used_hdr);
                 ws_plit = (fcs + 15u) & ~15u;
                 ws_seq = ws_plit + (ltype >= 2 ? ((regen + 15u) & ~15u) : 0u);
                 par = (uint64_t)ws_seq + (use_pre ? 0ull : 16ull * ns_hdr) + 16 <= cap;  // (walked chains: the records are elsewhere)
@@ -1842,43 +1811,7 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
                 } else {
                     // tables of this block (the union LDS is free: queued tasks are only descriptors)
                     stage_bytes(L.u.p.hbuf, sq, sqn < HBUF ? sqn : HBUF, lane);
-                    if (lane == 0) {
-                        uint32_t err = 0, used = 1, ns = nseq;
-                        const bool lost = tables_lost;
-                        const uint8_t* h = L.u.p.hbuf;
-                        const int hn = (int)(sqn < HBUF ? sqn : HBUF);
-                        if (ns >= 128) {
-                            if (ns == 255) {
-                                if (hn < 3) err = 1; else { ns = h[1] + ((uint32_t)h[2] << 8) + 0x7F00; used = 3; }
-                            } else {
-                                if (hn < 2) err = 1; else { ns = ((ns - 128) << 8) + h[1]; used = 2; }
-                            }
-                        }
-                        if (!err && (int)used >= hn) err = 1;
-                        if (!err) {
-                            const uint32_t modes = h[used++];
-                            if (modes & 3) err = 1;
-                            // a repeated table that a ring flush has overwritten: decode the frame again, carefully
-                            if (!err && lost && (((modes >> 6) & 3) == 3 || ((modes >> 4) & 3) == 3 || ((modes >> 2) & 3) == 3)) err = 3;
-                            int u;
-                            if (!err) {
-                                u = seq_table(L.u.p.fse[0], &log_ll, &have_ll, (modes >> 6) & 3, h + used, hn - (int)used, LL_DEFAULT, 36, 6, 35, 9);
-                                if (u < 0) err = 1; else used += (uint32_t)u;
-                            }
-                            if (!err) {
-                                u = seq_table(L.u.p.fse[1], &log_of, &have_of, (modes >> 4) & 3, h + used, hn - (int)used, OF_DEFAULT, 29, 5, 31, 8);
-                                if (u < 0) err = 1; else used += (uint32_t)u;
-                            }
-                            if (!err) {
-                                u = seq_table(L.u.p.fse[2], &log_ml, &have_ml, (modes >> 2) & 3, h + used, hn - (int)used, ML_DEFAULT, 53, 6, 52, 9);
-                                if (u < 0) err = 1; else used += (uint32_t)u;
-                            }
-                            if (!err && used >= sqn) err = 1;
-                        }
-                        L.ctl[C_ERR] = err;
-                        L.ctl[C_I] = ns;
-                        L.ctl[C_J] = used;
-                    }
+                    if (lane == 0) seq_section_header(sqn, tables_lost, log_ll, have_ll, log_of, have_of, log_ml, have_ml);
                     __syncthreads();
                     if (L.ctl[C_ERR] == 3) {
                         restart = true;
@@ -1960,43 +1893,7 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
                     nseq = uni(pb->nseq);
                 } else {
                 stage_bytes(L.u.p.hbuf, sq, sqn < HBUF ? sqn : HBUF, lane);
-                if (lane == 0) {
-                    uint32_t err = 0, used = 1, ns = nseq;
-                    const bool lost = tables_lost;
-                    const uint8_t* h = L.u.p.hbuf;
-                    const int hn = (int)(sqn < HBUF ? sqn : HBUF);
-                    if (ns >= 128) {
-                        if (ns == 255) {
-                            if (hn < 3) err = 1; else { ns = h[1] + ((uint32_t)h[2] << 8) + 0x7F00; used = 3; }
-                        } else {
-                            if (hn < 2) err = 1; else { ns = ((ns - 128) << 8) + h[1]; used = 2; }
-                        }
-                    }
-                    if (!err && (int)used >= hn) err = 1;
-                    if (!err) {
-                        const uint32_t modes = h[used++];
-                        if (modes & 3) err = 1;
-                        // a repeated table that a ring flush has overwritten: decode the frame again, carefully
-                        if (!err && lost && (((modes >> 6) & 3) == 3 || ((modes >> 4) & 3) == 3 || ((modes >> 2) & 3) == 3)) err = 3;
-                        int u;
-                        if (!err) {
-                            u = seq_table(L.u.p.fse[0], &log_ll, &have_ll, (modes >> 6) & 3, h + used, hn - (int)used, LL_DEFAULT, 36, 6, 35, 9);
-                            if (u < 0) err = 1; else used += (uint32_t)u;
-                        }
-                        if (!err) {
-                            u = seq_table(L.u.p.fse[1], &log_of, &have_of, (modes >> 4) & 3, h + used, hn - (int)used, OF_DEFAULT, 29, 5, 31, 8);
-                            if (u < 0) err = 1; else used += (uint32_t)u;
-                        }
-                        if (!err) {
-                            u = seq_table(L.u.p.fse[2], &log_ml, &have_ml, (modes >> 2) & 3, h + used, hn - (int)used, ML_DEFAULT, 53, 6, 52, 9);
-                            if (u < 0) err = 1; else used += (uint32_t)u;
-                        }
-                        if (!err && used >= sqn) err = 1;
-                    }
-                    L.ctl[C_ERR] = err;
-                    L.ctl[C_I] = ns;
-                    L.ctl[C_J] = used;
-                }
+                if (lane == 0) seq_section_header(sqn, tables_lost, log_ll, have_ll, log_of, have_of, log_ml, have_ml);
                 __syncthreads();
                 if (L.ctl[C_ERR] == 3) {
                     restart = true;
@@ -2399,12 +2296,7 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
     }
     // skippable frames behind the frame are legal and ignored (RFC 8878 3.1.2); a second data frame is not what
     // vbz writes and is rejected
-    while (n - pos >= 8) {
-        uint32_t m[2];
-        __builtin_memcpy(m, src + pos, 8);
-        if ((m[0] & 0xFFFFFFF0u) != 0x184D2A50u || (uint64_t)pos + 8 + m[1] > n) break;
-        pos += 8 + m[1];
-    }
+    pos = zstd_skip_frames([&](uint32_t o) { uint32_t v; __builtin_memcpy(&v, src + o, 4); return v; }, pos, n);
     if (pos != n) FAIL();
     if (opos != fcs) FAIL();
     if (partial) {
@@ -2464,19 +2356,11 @@ __global__ __launch_bounds__(1024) void zstd_dspan_plan_kernel(ReadBatch b, uint
             const bool gated = (b.gate && b.gate[i] >= GATE_SKIP) || n >= E_FIRST;
             if (!gated && n >= 64) {
                 const uint8_t* src = b.src + b.src_off[i];
-                uint32_t magic, hl = 0;
-                __builtin_memcpy(&magic, src, 4);
-                const uint32_t fhd = src[4];
-                const int fcs_flag = fhd >> 6;
-                uint64_t fcs = 0;
-                bool ok = magic == 0xFD2FB528u && (fhd & 0x3B) == 0x20;
-                if (ok) {
-                    const uint32_t fsz = fcs_flag == 0 ? 1u : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-                    for (uint32_t k = 0; k < fsz; ++k) fcs |= (uint64_t)src[5 + k] << (8 * k);
-                    if (fsz == 2) fcs += 256;
-                    hl = 5 + fsz;
-                    ok = fcs <= b.dst_cap[i] && fcs < 0xFFFFFFF0ull;
-                }
+                ZFrameHeader h;
+                bool ok = zstd_frame_header([&](uint32_t k) { return (uint32_t)src[k]; }, n, &h) && h.magic == ZSTD_MAGIC && (h.fhd & 0x3B) == 0x20;
+                const uint32_t hl = ok ? h.len : 0u;
+                const uint64_t fcs = ok ? h.fcs : 0ull;
+                ok = ok && fcs <= b.dst_cap[i] && fcs < 0xFFFFFFF0ull;
                 uint32_t tb = 0, ns = 0, treeless = 0;
                 if (ok) {
                     __builtin_memcpy(&tb, src + n - 4, 4);

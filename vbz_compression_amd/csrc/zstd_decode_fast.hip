@@ -27,6 +27,7 @@
 
 #include "vbz_kernels.h"
 #include "zstd_runs.h"
+#include "zstd_frame.h"
 #include "zstd_tables.h"
 
 namespace vbzhip {
@@ -34,7 +35,6 @@ namespace vbzhip {
 namespace {
 
 constexpr uint32_t FAST_TASKS = 64;
-constexpr uint32_t CP_MAGIC = 0x184D2A5Bu, IDX_MAGIC = 0x184D2A5Cu;
 constexpr uint32_t TASK_REL = 1u << 31, TASK_TAB = 1u << 30, TASK_CNT = TASK_TAB - 1u;
 
 struct FastFrame  // 128 bytes per read
@@ -46,7 +46,13 @@ struct FastFrame  // 128 bytes per read
     uint32_t b0_regen, base_out;      // its literals; the bytes it regenerates = where the later blocks' content starts
     uint32_t ws_lit, ws_pairs;        // staging in the destination slot (literals, length pairs)
     uint32_t cp_off, cp_count, cp_spacing;
-    uint32_t pad[10];
+    // a unit of ref_lit_scan_kernel (read by ref_pieces_kernel)
+    uint32_t blk, lit_csize;          // where the block header sits in the frame; the literals' compressed size
+    uint32_t pieces_log, tree_unit;   // pieces a stream (log2); the unit whose tree the block is coded under (itself or an earlier one)
+    uint32_t stripe_off, stripe_len;  // the unit's share of the slot's free space
+    uint32_t noseq;                   // the block has no sequences: its literals are its content
+    uint32_t tail;                    // != 0: the block's presumed end in the content, where the unit places its literals ahead
+    uint32_t pad[2];
 };
 static_assert(sizeof(FastFrame) == 128, "FastFrame");
 
@@ -81,28 +87,15 @@ __device__ __forceinline__ bool scan_frame_header(const uint8_t* src, uint32_t c
     const uint64_t h0 = ld64(src), h1 = ld64(src + 8);
     auto hb = [&](uint32_t i) -> uint32_t { return (uint32_t)((i < 8 ? h0 >> (8 * i) : h1 >> (8 * (i - 8))) & 0xFF); };
     const uint32_t fhd = hb(4);
-    if ((uint32_t)h0 != 0xFD2FB528u || (fhd & 0x08) || (fhd & 3)) return false;  // (a Dictionary_ID field: the careful decoder)
-    const uint32_t single = (fhd >> 5) & 1, fcs_flag = fhd >> 6;
-    uint32_t pos = 5;
-    uint64_t window = 0;
-    if (!single) {
-        const uint32_t wd = hb(pos++);
-        const uint32_t wlog = 10 + (wd >> 3);
-        if (wlog > 31) return false;
-        window = (1ull << wlog) + ((1ull << wlog) >> 3) * (wd & 7);
-    }
-    const uint32_t fsz = fcs_flag == 0 ? (single ? 1u : 0u) : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-    if (fsz == 0) return false;
-    uint64_t fcs = 0;
-    for (uint32_t i = 0; i < fsz; ++i) fcs |= (uint64_t)hb(pos + i) << (8 * i);
-    if (fsz == 2) fcs += 256;
-    pos += fsz;
-    if (fcs > cap || fcs >= (1u << 30)) return false;
-    if (single) window = fcs;
-    F->fcs = (uint32_t)fcs;
-    F->block_max = (uint32_t)(window < BLOCK_MAX ? window : BLOCK_MAX);
-    *has_checksum = (fhd >> 2) & 1;
-    *pos_out = pos;
+    if ((uint32_t)h0 != ZSTD_MAGIC || (fhd & 0x08) || (fhd & 3)) return false;  // (a Dictionary_ID field: the careful decoder)
+    ZFrameHeader h;
+    zstd_frame_header(hb, 16u, &h);  // (without a Dictionary_ID field the header ends inside the 16 bytes)
+    if (h.wlog > 31 || h.fcs_bytes == 0) return false;
+    if (h.fcs > cap || h.fcs >= (1u << 30)) return false;
+    F->fcs = (uint32_t)h.fcs;
+    F->block_max = (uint32_t)(h.window < BLOCK_MAX ? h.window : BLOCK_MAX);
+    *has_checksum = h.checksum;
+    *pos_out = h.len;
     return true;
 }
 
@@ -125,24 +118,11 @@ __global__ __launch_bounds__(256) void fast_scan_kernel(ReadBatch b, FastFrame* 
     uint32_t has_checksum;
     if (!scan_frame_header(src, cap, &F, &pos, &has_checksum)) return;
     // the encoder's checkpoint trailer (see zero_run_chain_segments); an index trailer may follow it
-    if (n >= 64) {
-        uint32_t tb = ld32(src + n - 4), ne = n;
-        if (tb >= 24 && tb <= n - 16 && (tb & 7u) == 0) {
-            if (ld32(src + n - tb) == IDX_MAGIC && ld32(src + n - tb + 4) == tb - 8) {
-                ne = n - tb;
-                tb = ld32(src + ne - 4);
-            }
-        }
-        if (tb >= 20 && tb <= 8 + 4 + 4 * 63 + 4 && tb + 16 <= ne) {
-            const uint32_t m0 = ld32(src + ne - tb), m1 = ld32(src + ne - tb + 4), m2 = ld32(src + ne - tb + 8);
-            const uint32_t cnt = m2 >> 16;
-            if (m0 == CP_MAGIC && m1 == tb - 8 && tb == 16 + 4 * cnt && cnt >= 1) {
-                F.cp_off = ne - tb + 12;
-                F.cp_count = cnt;
-                F.cp_spacing = m2 & 0xFFFFu;
-            }
-        }
-    }
+    auto at32 = [&](uint32_t o) { return ld32(src + o); };
+    const ZCheckpoints cp = zstd_checkpoints(at32, n);
+    F.cp_off = cp.off;
+    F.cp_count = cp.count;
+    F.cp_spacing = cp.spacing;
     FastTask* T = tasks + (size_t)r * FAST_TASKS;
     uint32_t ntask = 0, ntree = 0;
     uint64_t rel = 0;  // content of the blocks behind the zero-run block (or of all blocks)
@@ -151,29 +131,20 @@ __global__ __launch_bounds__(256) void fast_scan_kernel(ReadBatch b, FastFrame* 
         if (pos + 3 > n) return;
         const uint64_t a0 = ld64(src + pos), a1 = ld64(src + pos + 8);
         auto win = [&](uint32_t o) -> uint64_t { return o == 0 ? a0 : ((a0 >> (8 * o)) | (a1 << (64 - 8 * o))); };  // 8 bytes from offset o <= 8
-        const uint32_t bh = (uint32_t)a0 & 0xFFFFFFu;
-        const uint32_t last = bh & 1, btype = (bh >> 1) & 3, bsize = bh >> 3;
+        const ZBlockHeader bk = zstd_block_header((uint32_t)a0);
+        const uint32_t last = bk.last, btype = bk.type, bsize = bk.size;
         if (btype != 2 || bsize < 5 || bsize >= BLOCK_MAX || (uint64_t)pos + 3 + bsize > n) return;
         const uint32_t blk = pos + 3;
-        uint32_t lh, regen, csize;
-        uint32_t ltype;
-        {
-            const uint64_t v = win(3);
-            const uint32_t h0 = (uint32_t)v & 0xFF, fmt = (h0 >> 2) & 3;
-            ltype = h0 & 3;
-            if (ltype < 2 || fmt == 0) return;
-            if (fmt == 1) { lh = 3; regen = (uint32_t)(v >> 4) & 0x3FF; csize = (uint32_t)(v >> 14) & 0x3FF; }
-            else if (fmt == 2) { lh = 4; regen = (uint32_t)(v >> 4) & 0x3FFF; csize = (uint32_t)(v >> 18) & 0x3FFF; }
-            else { lh = 5; regen = (uint32_t)(v >> 4) & 0x3FFFF; csize = (uint32_t)(v >> 22) & 0x3FFFF; }
-        }
+        const ZLitHeader lit = zstd_lit_header(win(3));
+        const uint32_t ltype = lit.type, lh = lit.hsize, regen = lit.regen, csize = lit.csize;
+        if (ltype < 2 || lit.fmt == 0) return;
         if (regen == 0 || csize == 0 || regen > BLOCK_MAX || lh + csize >= bsize) return;
         uint32_t tree_used = 0;
         if (ltype == 2) {
             if (ntree == 2) return;
             const uint32_t hb = src[blk + lh];
-            if (hb >= 128) tree_used = 1 + ((hb - 127) + 1) / 2;
-            else if (hb == 0) return;
-            else tree_used = 1 + hb;
+            if (hb == 0) return;
+            tree_used = huf_desc_size(hb);
             if (tree_used > csize) return;
             F.tree_off[ntree] = blk + lh;
             F.tree_len[ntree] = tree_used;
@@ -203,9 +174,8 @@ __global__ __launch_bounds__(256) void fast_scan_kernel(ReadBatch b, FastFrame* 
         } else {
             // zero-run sequences: the first block only, predefined LL / ML tables, OF = RLE of code 0 (repeat offset 1 is 1 there)
             if (ntask != 0 || sqn < 4) return;
-            const uint32_t used0 = nseq0 < 128 ? 1u : (nseq0 < 255 ? 2u : 3u);
-            const uint32_t b1 = (uint32_t)(sq8 >> 8) & 0xFF, b2 = (uint32_t)(sq8 >> 16) & 0xFF;
-            const uint32_t ns0 = nseq0 < 128 ? nseq0 : (nseq0 < 255 ? ((nseq0 - 128) << 8) + b1 : b1 + (b2 << 8) + 0x7F00);
+            uint32_t used0;
+            const uint32_t ns0 = zstd_nseq([&](uint32_t i) { return (uint32_t)(sq8 >> (8 * i)) & 0xFF; }, sqn, &used0);
             if (used0 + 2 >= sqn || ns0 == 0) return;
             if (((uint32_t)(sq8 >> (8 * used0)) & 0xFF) != 0x10u || ((uint32_t)(sq8 >> (8 * (used0 + 1))) & 0xFF) != 0u) return;
             const uint64_t ws_lit64 = ((uint64_t)F.fcs + 15u) & ~15ull;
@@ -241,11 +211,7 @@ __global__ __launch_bounds__(256) void fast_scan_kernel(ReadBatch b, FastFrame* 
         if (pos + 4 > n) return;
         pos += 4;  // xxh64 of the content: not verified (like zstd_decode_kernel)
     }
-    while (n - pos >= 8) {  // skippable frames behind the frame
-        const uint32_t m0 = ld32(src + pos), m1 = ld32(src + pos + 4);
-        if ((m0 & 0xFFFFFFF0u) != 0x184D2A50u || (uint64_t)pos + 8 + m1 > n) break;
-        pos += 8 + m1;
-    }
+    pos = zstd_skip_frames(at32, pos, n);  // skippable frames behind the frame
     if (pos != n) return;
     if (F.nseq) {
         F.base_out = F.fcs - (uint32_t)rel;  // what the zero-run block must regenerate (fast_runs_kernel holds it to that)
@@ -625,32 +591,24 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
     for (uint32_t bidx = 0; nunit < max_units; ++bidx) {
         if ((uint64_t)pos + 3 + 16 > n) break;
         const uint64_t a0 = ld64(src + pos), a1 = ld64(src + pos + 8);
-        const uint32_t bh = (uint32_t)a0 & 0xFFFFFFu;
-        const uint32_t last = bh & 1u, btype = (bh >> 1) & 3, bsize = bh >> 3;
+        const ZBlockHeader bk = zstd_block_header((uint32_t)a0);
+        const uint32_t last = bk.last, btype = bk.type, bsize = bk.size;
         if (btype == 3) break;
-        const uint64_t next = (uint64_t)pos + 3 + (btype == 1 ? 1u : bsize);
+        const uint64_t next = (uint64_t)pos + 3 + bk.src;
         if (next > n) break;
         if (bidx != 0 || !last) more_blocks = true;
         const uint32_t blk = pos + 3;
         bool unit = false;
         if (btype == 2 && bsize >= 5 && bsize < BLOCK_MAX) {
             FastFrame F = H;
-            uint32_t lh = 0, regen = 0, csize = 0;
-            const uint64_t v = (a0 >> 24) | (a1 << 40);
-            const uint32_t h0 = (uint32_t)v & 0xFF, fmt = (h0 >> 2) & 3, ltype = h0 & 3;
-            bool ok = ltype >= 2 && fmt != 0;    // compressed literals in four streams, under a tree of their own or the one before
-            if (ok) {
-                if (fmt == 1) { lh = 3; regen = (uint32_t)(v >> 4) & 0x3FF; csize = (uint32_t)(v >> 14) & 0x3FF; }
-                else if (fmt == 2) { lh = 4; regen = (uint32_t)(v >> 4) & 0x3FFF; csize = (uint32_t)(v >> 18) & 0x3FFF; }
-                else { lh = 5; regen = (uint32_t)(v >> 4) & 0x3FFFF; csize = (uint32_t)(v >> 22) & 0x3FFFF; }
-                ok = regen != 0 && csize != 0 && regen <= BLOCK_MAX && lh + csize < bsize && regen <= H.fcs;
-            }
+            const ZLitHeader lit = zstd_lit_header((a0 >> 24) | (a1 << 40));
+            const uint32_t ltype = lit.type, lh = lit.hsize, regen = lit.regen, csize = lit.csize;
+            // compressed literals in four streams, under a tree of their own or the one before
+            bool ok = ltype >= 2 && lit.fmt != 0 && regen != 0 && csize != 0 && regen <= BLOCK_MAX && lh + csize < bsize && regen <= H.fcs;
             uint32_t tree_used = 0;
             if (ok && ltype == 2) {
-                const uint32_t hb = src[blk + lh];
-                if (hb >= 128) tree_used = 1 + ((hb - 127) + 1) / 2;
-                else if (hb == 0) ok = false;
-                else tree_used = 1 + hb;
+                tree_used = huf_desc_size(src[blk + lh]);
+                ok = tree_used != 0;
             } else if (ok) {
                 ok = tree_unit != REF_NONE;      // a treeless block under a tree this kernel has no record of
             }
@@ -681,11 +639,11 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
                         F.tree_len[0] = tree_used;
                         F.b0_regen = regen;
                         F.ws_lit = (uint32_t)at;
-                        F.pad[0] = pos;      // the block header
-                        F.pad[1] = csize;
-                        F.pad[3] = gs;
-                        F.pad[4] = ltype == 2 ? u : tree_unit;   // whose weights
-                        F.pad[8] = noseq ? 1u : 0u;
+                        F.blk = pos;
+                        F.lit_csize = csize;
+                        F.pieces_log = gs;
+                        F.tree_unit = ltype == 2 ? u : tree_unit;
+                        F.noseq = noseq ? 1u : 0u;
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             FastTask t;
@@ -722,7 +680,7 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
     if (s0 + 4096u > cap) return;
     const uint64_t room = cap - s0;
     uint64_t off = s0;
-    // Which units put their literals at their block's presumed end ahead of the decoder (pad[9]: that end, 0: none).  The decoder skips
+    // Which units put their literals at their block's presumed end ahead of the decoder (tail: that end, 0: none).  The decoder skips
     // its copy of a unit's tail only if the block really ends there, so a wrong guess cannot hurt the unit itself -- but its literals land
     // in [G - regen, G) all the same, and if that range meets another unit's whose guess was right, the decoder trusts a tail the stray
     // write may have overwritten (the units run in unordered workgroups).  Hence a unit places its literals only if its range is disjoint
@@ -732,9 +690,9 @@ __global__ __launch_bounds__(256) void ref_lit_scan_kernel(ReadBatch b, const ui
         for (uint32_t q = 0; q < nunit; ++q)
             if (q != k && tails[q] >= regens[q] && tails[k] - regens[k] < tails[q] && tails[q] - regens[q] < tails[k]) place = false;
         const uint64_t share = (room * regens[k] / sum_regen) & ~127ull;
-        frames[(size_t)k * nr + r].pad[5] = (uint32_t)off;
-        frames[(size_t)k * nr + r].pad[6] = (uint32_t)share;
-        frames[(size_t)k * nr + r].pad[9] = place ? tails[k] : 0u;
+        frames[(size_t)k * nr + r].stripe_off = (uint32_t)off;
+        frames[(size_t)k * nr + r].stripe_len = (uint32_t)share;
+        frames[(size_t)k * nr + r].tail = place ? tails[k] : 0u;
         off += share;
         skip[(size_t)k * nr + r] = 0;
     }
@@ -764,7 +722,7 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
     } while (0)
     if (skip[u]) LEAVE();
     const FastFrame* F = frames + u;
-    const uint32_t tu = F->pad[4];   // the unit whose tree this block is coded under (itself, or an earlier one of the frame)
+    const uint32_t tu = F->tree_unit;   // the unit whose tree this block is coded under (itself, or an earlier one of the frame)
     if (tu > u || tu % b.n_reads != r || skip[tu]) LEAVE();
     const uint32_t tlog = frames[tu].tlog[0];
     if (tlog > 11 || tlog == 0) LEAVE();
@@ -772,7 +730,7 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
     const uint8_t* src = b.src + b.src_off[r];
     uint8_t* dst = b.dst + b.dst_off[r];
     // G = 16, 8 or 4 pieces a stream (the scan's choice): lanes [0, 4 G) each walk a piece, the others idle along (their piece is empty)
-    const uint32_t gs = F->pad[3], G = 1u << gs, nact = REF_TASKS << gs;
+    const uint32_t gs = F->pieces_log, G = 1u << gs, nact = REF_TASKS << gs;
     if (gs < REF_PIECES_LOG_MIN || gs > REF_PIECES_LOG) LEAVE();
     const bool act = (uint32_t)lane < nact;
     const uint32_t st = act ? (uint32_t)lane >> gs : 0u, j = (uint32_t)lane & (G - 1u);
@@ -787,7 +745,7 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
     // the stripes: what the slot has behind the literals' place, 128-byte aligned, a 64th each; a piece holds its share of the
     // stream's symbols give or take a few per cent -- a stripe must have room for a quarter more, else the frame is not done here
     const uint32_t regen = F->b0_regen;
-    const uint64_t tb = ((uint64_t)(dst + F->pad[5]) + 127ull) & ~127ull, te = (uint64_t)(dst + F->pad[5]) + F->pad[6];   // (the unit's share: the scan)
+    const uint64_t tb = ((uint64_t)(dst + F->stripe_off) + 127ull) & ~127ull, te = (uint64_t)(dst + F->stripe_off) + F->stripe_len;   // (the unit's share: the scan)
     const uint32_t pcap = te > tb ? (uint32_t)(((te - tb) >> (gs + 2u)) < 0x10000ull ? ((te - tb) >> (gs + 2u)) : 0x10000ull) & ~127u : 0u;
     if (__any((cnt >> gs) + (cnt >> (gs + 2u)) + 256u > pcap)) LEAVE();
     gu8* o = (gu8*)(tb + (uint64_t)lane * pcap);
@@ -989,8 +947,8 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
     // instruction is a kilobyte of whole lines --, eight pieces' loads in flight before their stores.
     // (A block that is not the frame's last: a one-shot libzstd cuts its input into blocks of block_max bytes, so the k-th such block ends at
     // k x block_max -- a guess: the decoder skips its copy only if the literals' place comes out where they were put, and the scan lets a unit
-    // place them only where a wrong guess cannot land in another unit's tail: pad[9], 0 if not.)
-    const uint32_t tail_end = F->pad[9];
+    // place them only where a wrong guess cannot land in another unit's tail: tail, 0 if not.)
+    const uint32_t tail_end = F->tail;
     if (tail_end != 0u && tail_end >= regen) {
         typedef __attribute__((address_space(1), aligned(16))) const u32x4 gl4;
         typedef __attribute__((address_space(1), aligned(1))) u32x4 gst4;
@@ -1026,12 +984,12 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
             }
         }
         res.tail = tail_end;
-    } else if (F->pad[8]) {
+    } else if (F->noseq) {
         LEAVE();   // (a block without sequences whose literals could not be put in place: nothing to hand over)
     }
-    res.blk = F->pad[0];
+    res.blk = F->blk;
     res.regen = regen;
-    res.csize = F->pad[1];
+    res.csize = F->lit_csize;
     res.at = F->ws_lit;
     res.tb = (uint32_t)(tb - (uint64_t)dst);
     res.pcap = pcap;

@@ -27,6 +27,7 @@
 
 #include "vbz_kernels.h"
 #include "zstd_runs.h"
+#include "zstd_frame.h"
 #include "zstd_tables.h"
 
 namespace vbzhip {
@@ -349,8 +350,8 @@ __device__ uint32_t ref_chain(RefLds<FPW, INLDS>& S, RefGlobal G, int l, const u
     return 0u;
 }
 
-// (why a frame was left alone: RefPre.pad[0], a diagnostic that vbz_gpu_decode_paths prints under VBZ_HIP_TRACE)
-#define BAIL(k) do { P->pad[0] = (k); return false; } while (0)
+// (why a frame was left alone: RefPre.why, a diagnostic that vbz_gpu_decode_paths prints under VBZ_HIP_TRACE)
+#define BAIL(k) do { P->why = (k); return false; } while (0)
 template <int FPW, bool INLDS>
 __device__ bool ref_frame(RefLds<FPW, INLDS>& S, RefGlobal G, int l, const ReadBatch& b, uint32_t r, RefPre* P, uint4* recs, uint64_t recs_cap,
                           unsigned long long* recs_used)
@@ -366,26 +367,15 @@ __device__ bool ref_frame(RefLds<FPW, INLDS>& S, RefGlobal G, int l, const ReadB
         const uint64_t h0 = rld64(src), h1 = rld64(src + 8);
         auto hb = [&](uint32_t i) -> uint32_t { return (uint32_t)((i < 8 ? h0 >> (8 * i) : h1 >> (8 * (i - 8))) & 0xFF); };
         const uint32_t fhd = hb(4);
-        if ((uint32_t)h0 != 0xFD2FB528u || (fhd & 0x08) || (fhd & 3)) BAIL(3);  // (a Dictionary_ID field: the careful decoder)
-        const uint32_t single = (fhd >> 5) & 1, fcs_flag = fhd >> 6;
-        pos = 5;
-        uint64_t window = 0;
-        if (!single) {
-            const uint32_t wd = hb(pos++);
-            const uint32_t wlog = 10 + (wd >> 3);
-            if (wlog > 31) BAIL(4);
-            window = (1ull << wlog) + ((1ull << wlog) >> 3) * (wd & 7);
-        }
-        const uint32_t fsz = fcs_flag == 0 ? (single ? 1u : 0u) : (fcs_flag == 1 ? 2u : (fcs_flag == 2 ? 4u : 8u));
-        if (fsz == 0) BAIL(5);
-        uint64_t f = 0;
-        for (uint32_t i = 0; i < fsz; ++i) f |= (uint64_t)hb(pos + i) << (8 * i);
-        if (fsz == 2) f += 256;
-        pos += fsz;
-        if (f > cap || f >= (1u << 30)) BAIL(6);
-        if (single) window = f;
-        fcs = (uint32_t)f;
-        block_max = (uint32_t)(window < BLOCK_MAX ? window : BLOCK_MAX);
+        if ((uint32_t)h0 != ZSTD_MAGIC || (fhd & 0x08) || (fhd & 3)) BAIL(3);  // (a Dictionary_ID field: the careful decoder)
+        ZFrameHeader h;
+        zstd_frame_header(hb, 16u, &h);  // (without a Dictionary_ID field the header ends inside the 16 bytes)
+        if (h.wlog > 31) BAIL(4);
+        if (h.fcs_bytes == 0) BAIL(5);
+        if (h.fcs > cap || h.fcs >= (1u << 30)) BAIL(6);
+        pos = h.len;
+        fcs = (uint32_t)h.fcs;
+        block_max = (uint32_t)(h.window < BLOCK_MAX ? h.window : BLOCK_MAX);
     }
     uint32_t nblk = 0, opos = 0;
     uint64_t frame_ns = 0;
@@ -394,37 +384,27 @@ __device__ bool ref_frame(RefLds<FPW, INLDS>& S, RefGlobal G, int l, const ReadB
     int log_ll = 0, log_of = 0, log_ml = 0;
     for (;;) {
         if (pos + 3 > n) BAIL(7);
-        const uint32_t bh = rld32(src + pos) & 0xFFFFFFu;
+        const ZBlockHeader bk = zstd_block_header(rld32(src + pos));
         const uint32_t block_at = pos;
         pos += 3;
-        const uint32_t last = bh & 1, btype = (bh >> 1) & 3, bsize = bh >> 3;
+        const uint32_t last = bk.last, btype = bk.type, bsize = bk.size;
         if (btype == 3) BAIL(8);
         if (btype == 0 || btype == 1) {
-            if (bsize > block_max || (uint64_t)pos + (btype == 0 ? bsize : 1u) > n || (uint64_t)opos + bsize > fcs) BAIL(9);
+            if (bsize > block_max || (uint64_t)pos + bk.src > n || (uint64_t)opos + bsize > fcs) BAIL(9);
             opos += bsize;
-            pos += btype == 0 ? bsize : 1u;
+            pos += bk.src;
         } else {
             if (bsize >= BLOCK_MAX || (uint64_t)pos + bsize > n || bsize < 2) BAIL(10);
             const uint8_t* blk = src + pos;
-            uint32_t lh, regen, csize;
-            {
-                const uint64_t v = rld64(blk);
-                const uint32_t h0 = (uint32_t)v & 0xFF, fmt = (h0 >> 2) & 3, ltype = h0 & 3;
-                if (ltype < 2) {
-                    if (fmt == 0 || fmt == 2) { lh = 1; regen = h0 >> 3; }
-                    else if (fmt == 1) { lh = 2; regen = ((uint32_t)v & 0xFFFFu) >> 4; }
-                    else { lh = 3; regen = ((uint32_t)v & 0xFFFFFFu) >> 4; }
-                    if (lh > bsize) BAIL(11);
-                    csize = ltype == 0 ? regen : 1;
-                } else {
-                    if (bsize < 5) BAIL(12);
-                    if (fmt < 2) { lh = 3; regen = (uint32_t)(v >> 4) & 0x3FF; csize = (uint32_t)(v >> 14) & 0x3FF; }
-                    else if (fmt == 2) { lh = 4; regen = (uint32_t)(v >> 4) & 0x3FFF; csize = (uint32_t)(v >> 18) & 0x3FFF; }
-                    else { lh = 5; regen = (uint32_t)(v >> 4) & 0x3FFFF; csize = (uint32_t)(v >> 22) & 0x3FFFF; }
-                    if (regen == 0 || csize == 0) BAIL(13);
-                }
-                if (regen > BLOCK_MAX || (uint64_t)lh + csize >= bsize) BAIL(14);
+            const ZLitHeader lit = zstd_lit_header(rld64(blk));
+            const uint32_t lh = lit.hsize, regen = lit.regen, csize = lit.csize;
+            if (lit.type < 2) {
+                if (lh > bsize) BAIL(11);
+            } else {
+                if (bsize < 5) BAIL(12);
+                if (regen == 0 || csize == 0) BAIL(13);
             }
+            if (regen > BLOCK_MAX || (uint64_t)lh + csize >= bsize) BAIL(14);
             const uint32_t lit_end = lh + csize;
             const uint8_t* sq = blk + lit_end;
             const uint32_t sqn = bsize - lit_end;
@@ -444,18 +424,9 @@ __device__ bool ref_frame(RefLds<FPW, INLDS>& S, RefGlobal G, int l, const ReadB
                     S.u.p.hdr[4 * k + 2][l] = (uint32_t)c;
                     S.u.p.hdr[4 * k + 3][l] = (uint32_t)(c >> 32);
                 }
-                uint32_t ns = hdr_byte(S, l, 0), used = 1;
-                if (ns >= 128) {
-                    if (ns == 255) {
-                        if (hn < 3) BAIL(18);
-                        ns = hdr_byte(S, l, 1) + (hdr_byte(S, l, 2) << 8) + 0x7F00;
-                        used = 3;
-                    } else {
-                        if (hn < 2) BAIL(19);
-                        ns = ((ns - 128) << 8) + hdr_byte(S, l, 1);
-                        used = 2;
-                    }
-                }
+                uint32_t used;
+                const uint32_t ns = zstd_nseq([&](uint32_t i) { return hdr_byte(S, l, i); }, hn, &used);
+                if (used == 0) BAIL(hdr_byte(S, l, 0) == 255 ? 18 : 19);
                 if (used >= hn) BAIL(20);
                 const uint32_t modes = hdr_byte(S, l, used++);
                 if (modes & 3) BAIL(21);
@@ -487,9 +458,9 @@ __device__ bool ref_frame(RefLds<FPW, INLDS>& S, RefGlobal G, int l, const ReadB
                                                (uint32_t)log_ml, recs + first, ns, regen, opos, fcs, rep, &end);
                 if (why) BAIL(why);
                 const unsigned long long t2 = __builtin_readcyclecounter();
-                P->pad[1] = (uint32_t)(t1 - t0);   // (diagnostics: cycles of the tables and of the chain of the frame's last block)
-                P->pad[2] = (uint32_t)(t2 - t1);
-                P->pad[3] = ns;
+                P->tab_cycles = (uint32_t)(t1 - t0);
+                P->chain_cycles = (uint32_t)(t2 - t1);
+                P->nseq_last = ns;
                 if (end > fcs || end - opos > BLOCK_MAX || end - opos > block_max) BAIL(29);
                 RefBlock& B = P->blk[nblk++];
                 B.pos = block_at;

@@ -19,7 +19,7 @@
 //   * the control-byte region becomes one block whose long zero runs are zstd SEQUENCES (copy from
 //     offset 1 = repeat offset 1, which costs no bits) -- what libzstd's match finder gets out of
 //     that region, found here with a bit-parallel tokeniser instead of a hash chain -- followed by
-//     a skippable frame with decoder checkpoints (CP_MAGIC below);
+//     a skippable frame with decoder checkpoints (CP_MAGIC, zstd_frame.h);
 //   * raw and RLE blocks are used where Huffman coding does not pay (tiny or constant regions), which
 //     also reproduces the reference's known answers for tiny inputs (vbz/test/vbz_test.cpp:238).
 //
@@ -32,6 +32,7 @@
 // Algorithmic HBM bytes per svb byte: 1 read + ~0.67 written.
 #include "vbz_kernels.h"
 #include "zstd_entropy.h"
+#include "zstd_frame.h"
 
 namespace vbzhip {
 
@@ -1128,9 +1129,8 @@ __device__ void period_mask(const uint8_t* in, uint32_t S, uint32_t D, uint16_t*
 // frame* behind the frame (RFC 8878 3.1.2: decoders skip it; libzstd's ZSTD_decompress and
 // ZSTD_getFrameContentSize are unaffected).  zstd_decode.hip walks the segments in parallel, one lane each, and
 // accepts the result only if every segment ends exactly in the next checkpoint, so a wrong or missing trailer
-// costs speed, never correctness.  Layout: magic 0x184D2A5B, u32 size, { u16 spacing, u16 count,
-// count x u32 (unread bits | LL state << 20 | ML state << 26), u32 total trailer bytes }.
-constexpr uint32_t CP_MAGIC = 0x184D2A5Bu;
+// costs speed, never correctness.  Layout: magic CP_MAGIC, u32 size, { u16 spacing, u16 count,
+// count x u32 (unread bits | LL state << 20 | ML state << 26), u32 total trailer bytes }.  (CP_MAGIC: zstd_frame.h)
 constexpr uint32_t CP_MIN_SPACING = 32;
 
 // all lanes.  Sequences section (RFC 8878 3.1.1.3.2) for the records of tokenise_runs: LL and ML with the predefined
@@ -1174,8 +1174,8 @@ __device__ __forceinline__ uint32_t encode_zero_run_sequences(LDS& L, uint8_t* d
     if (lane == 0) {
         uint8_t* op = dst;
         if (nseq < 128) { *op++ = (uint8_t)nseq; }
-        else if (nseq < 0x7F00) { *op++ = (uint8_t)((nseq >> 8) + 128); *op++ = (uint8_t)nseq; }
-        else { *op++ = 255; *op++ = (uint8_t)(nseq - 0x7F00); *op++ = (uint8_t)((nseq - 0x7F00) >> 8); }
+        else if (nseq < NSEQ_LONG_BASE) { *op++ = (uint8_t)((nseq >> 8) + 128); *op++ = (uint8_t)nseq; }
+        else { *op++ = 255; *op++ = (uint8_t)(nseq - NSEQ_LONG_BASE); *op++ = (uint8_t)((nseq - NSEQ_LONG_BASE) >> 8); }
         *op++ = 0x10;  // LL predefined | OF RLE | ML predefined
         *op++ = (uint8_t)of_code;
         hdr = (uint32_t)(op - dst);
@@ -1618,7 +1618,7 @@ __global__ __launch_bounds__(WAVE, VBZ_ENC_WAVES) void zstd_encode_kernel(ReadBa
         if (lane == 0) {
             if (hdr) put_le(out, orig_size[r], 4);
             uint8_t* p = out + hdr;
-            put_le(p, 0xFD2FB528u, 4);
+            put_le(p, ZSTD_MAGIC, 4);
             if (N < 256) { p[4] = 0x20; p[5] = (uint8_t)N; }
             else if (N < 65536 + 256) { p[4] = 0x60; put_le(p + 5, N - 256, 2); }
             else { p[4] = 0xA0; put_le(p + 5, N, 4); }
@@ -2665,7 +2665,7 @@ __global__ __launch_bounds__(WAVE, VBZ_ENC_PACK_WAVES) void zstd_pack_kernel(Rea
     if (lane == 0) {
         if (hdr) put_le(out, orig_size[r], 4);
         uint8_t* p = out + hdr;
-        put_le(p, 0xFD2FB528u, 4);
+        put_le(p, ZSTD_MAGIC, 4);
         if (N < 256) { p[4] = 0x20; p[5] = (uint8_t)N; }
         else if (N < 65536 + 256) { p[4] = 0x60; put_le(p + 5, N - 256, 2); }
         else { p[4] = 0xA0; put_le(p + 5, N, 4); }
@@ -2716,9 +2716,8 @@ __global__ __launch_bounds__(WAVE, VBZ_ENC_PACK_WAVES) void zstd_pack_kernel(Rea
 // any) goes an INDEX of the spans in a second skippable frame -- where each span's first block starts in the frame and in
 // the content -- with which zstd_decode.hip decodes the spans on different wavefronts; like the checkpoints it is verified,
 // never trusted (a decoder without it, e.g. libzstd, walks the blocks one after the other).
-//   layout: magic 0x184D2A5C, u32 payload bytes, { u32 nspans (bit 31: some spans begin with a treeless block), nspans x { u32 frame offset,
-//           u32 content offset }, u32 total bytes }
-constexpr uint32_t IDX_MAGIC = 0x184D2A5Cu;
+//   layout: magic IDX_MAGIC, u32 payload bytes, { u32 nspans (bit 31: some spans begin with a treeless block), nspans x { u32 frame offset,
+//           u32 content offset }, u32 total bytes }  (IDX_MAGIC: zstd_frame.h)
 
 __global__ __launch_bounds__(1024) void zstd_span_plan_kernel(uint32_t n, const uint32_t* svb_size, const uint32_t* orig_size, uint32_t key_elem,
                                                               const uint32_t* gate, uint32_t seq_enabled, uint32_t max_spans, uint64_t tmp_limit,
