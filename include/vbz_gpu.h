@@ -267,6 +267,27 @@ VBZ_EXPORT int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* ctx, const vbz_
                                                     const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
                                                     const vbz_gpu_normalization* norm, float* shift_scale);
 
+/* POD5 signal rows.  options->vbz_version = VBZ_GPU_VERSION_POD5 (the bytes "POD5") with integer_size 2 and perform_delta_zig_zag 1
+ * selects the codec of the POD5 format's signal table: a row of n int16 samples x_j is one zstd frame (RFC 8878; pod5 writes libzstd level 1,
+ * content size present, no checksum) whose content is the svb16 stream of
+ *     d_j = (x_j - x_{j-1}) mod 2^16 (x_{-1} = 0: every row starts from 0),  z_j = ((d_j << 1) ^ (int16(d_j) >> 15)) & 0xFFFF:
+ * K = ceil(n / 8) key bytes -- bit j % 8 (LSB first) of byte j / 8 is 1 when z_j takes two data bytes; unused bits are written 0 and
+ * ignored -- then, for j = 0 ... n - 1, z_j as one byte (z_j < 256) or two, little-endian.  svb16_max(n) = K + 2n; n = 0 is an empty stream.
+ * The value exists in this batched API only: vbz.h's calls, the HDF5 filter and vbz.py give VBZ_VERSION_ERROR for it, as the reference does.
+ * Accepted with sized = 0 and zstd_compression_level >= 1 (levels above 1 write level-1 frames, as for v0); sized = 1, level 0, zig-zag 0 or
+ * integer_size != 2 return -2 before anything is launched, and vbz_gpu_decompressed_size_batch refuses the options (a row has no header;
+ * its sample count is the file's `samples` column).  Calls that take them, with the semantics they document, one batch entry per row:
+ * vbz_gpu_compress_batch / vbz_gpu_decompress_batch, vbz_gpu_decompress_signal_batch, vbz_gpu_decompress_chunks_batch, the three
+ * normalising calls (a row counts as a read: its chunks and statistics are the row's), and the svb stage entry points with
+ * version = VBZ_GPU_VERSION_POD5 (the svb16 stream alone).  Compress slots need dst_cap[i] >= vbz_gpu_pod5_max_compressed_size(samples)
+ * = ZSTD_COMPRESSBOUND(svb16_max(n)), pod5's compressed_signal_max_size.  Decode verdicts per row: a zstd failure or frame content longer
+ * than svb16_max(n) is VBZ_ZSTD_ERROR; a stream whose length is not K + n + popcount(the first n key bits) is VBZ_STREAMVBYTE_STREAM_ERROR;
+ * descriptor, capacity and alignment failures are the v0 int16 call's.  Trailers, checksums and canonical mode act on POD5 frames as on
+ * v0's; libzstd decodes them.  The rows of one read decode into one contiguous signal when their slots are adjacent
+ * (batch.pod5_read_layout).  The svb16 stage runs one workgroup per row on every path. */
+#define VBZ_GPU_VERSION_POD5 0x35444F50u
+VBZ_EXPORT uint64_t vbz_gpu_pod5_max_compressed_size(uint32_t samples);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

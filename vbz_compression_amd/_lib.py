@@ -89,6 +89,8 @@ class GpuChunking(ctypes.Structure):
 VBZ_GPU_NORM_MED_MAD = 1
 VBZ_GPU_NORM_QUANTILE = 2
 
+VBZ_GPU_VERSION_POD5 = 0x35444F50   # CompressionOptions.vbz_version of POD5 signal rows (svb16 + zstd; the batched API only)
+
 
 class GpuNormalization(ctypes.Structure):
     """struct vbz_gpu_normalization of include/vbz_gpu.h (32 bytes)."""
@@ -132,6 +134,7 @@ GPU_API = [
     "vbz_gpu_signal_norm_batch",
     "vbz_gpu_decompress_signal_norm_batch",
     "vbz_gpu_decompress_chunks_norm_batch",
+    "vbz_gpu_pod5_max_compressed_size",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -229,6 +232,9 @@ def load():
         L.vbz_gpu_decompress_signal_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, np_, vp]
         L.vbz_gpu_decompress_chunks_norm_batch.restype = ctypes.c_int
         L.vbz_gpu_decompress_chunks_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, cp, vp, vp, u64, np_, vp]
+    if hasattr(L, "vbz_gpu_pod5_max_compressed_size"):   # (likewise: builds of earlier rounds have no POD5 codec)
+        L.vbz_gpu_pod5_max_compressed_size.restype = u64
+        L.vbz_gpu_pod5_max_compressed_size.argtypes = [u32]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, streams, torch.distributed); the codec 
 library.  All tensors must live on the codec's device.  Offsets are int64, sizes/results int32
 tensors whose bits are read as uint64 / uint32 by the C ABI.
 """
+import collections
 import ctypes
 import dataclasses
 
@@ -212,6 +213,7 @@ class GpuCodec:
             self._exit(cur)
 
     # -- stages ----------------------------------------------------------------------------------
+    # (version: 0, 1, or _lib.VBZ_GPU_VERSION_POD5 -- the svb16 stream of POD5 rows, size 2 with zig-zag)
     def svb_compress(self, src, src_off, src_size, dst, dst_off, dst_cap, result, size=2, zigzag=True, version=0):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
         cur = self._enter()
@@ -548,3 +550,45 @@ def layout(sizes, align=64, device="cpu"):
         off[1:] = torch.cumsum(padded, 0)[:-1]
     total = int(padded.sum().item()) + 64
     return off.to(device), total
+
+
+# -- POD5 signal rows (include/vbz_gpu.h: VBZ_GPU_VERSION_POD5) ----------------------------------------------------------------
+def pod5_options(level=1):
+    """CompressionOptions of POD5 signal rows: int16 samples, delta + zig-zag, svb16 + one zstd frame (levels above 1 write level-1
+    frames).  Unsized calls only: a row's sample count is the file's `samples` column."""
+    return _lib.CompressionOptions(True, 2, int(level), _lib.VBZ_GPU_VERSION_POD5)
+
+
+def pod5_max_compressed_size(samples):
+    """ZSTD_COMPRESSBOUND(ceil(samples / 8) + 2 samples): the capacity a compress slot of a row needs (pod5's compressed_signal_max_size)."""
+    return int(_lib.load().vbz_gpu_pod5_max_compressed_size(int(samples)))
+
+
+Pod5Layout = collections.namedtuple("Pod5Layout", "dst_off dst_cap read_off read_len total")
+
+
+def pod5_read_layout(row_samples, read_first_row, elem=2, align=16, device="cpu"):
+    """The decode layout of POD5 reads stored as several signal rows: the rows of a read are laid out adjacently, so that its decoded
+    rows form one contiguous signal, and every read starts `align`-aligned.  row_samples: the rows' sample counts, in file order;
+    read_first_row: the first row of every read (ascending from 0; read k owns rows read_first_row[k] ... read_first_row[k + 1] - 1,
+    the last read the rows up to the end).  elem: bytes per decoded sample (2: int16; 4 / 2: float32 / float16 or bfloat16 of
+    decompress_signal, whose offset and scale are then passed once per ROW).
+    -> Pod5Layout(dst_off int64 [rows] bytes, dst_cap int32 [rows] bytes, read_off int64 [reads] bytes, read_len int64 [reads] samples,
+    total bytes): read k is bytes read_off[k] ... read_off[k] + elem * read_len[k] of the destination."""
+    assert align >= 1 and align & (align - 1) == 0 and elem in (2, 4), (align, elem)
+    rows = torch.as_tensor(row_samples, dtype=torch.int64).reshape(-1)
+    first = torch.as_tensor(read_first_row, dtype=torch.int64).reshape(-1)
+    n_rows, n_reads = int(rows.numel()), int(first.numel())
+    bounds = torch.cat([first, torch.tensor([n_rows], dtype=torch.int64)])
+    assert (n_reads == 0 or int(first[0]) == 0) and bool((bounds[1:] >= bounds[:-1]).all()) and int(bounds[-2 if n_reads else -1]) <= n_rows, \
+        "read_first_row must ascend from 0 within the rows"
+    read = torch.repeat_interleave(torch.arange(n_reads, dtype=torch.int64), bounds[1:] - bounds[:-1])   # the read of every row
+    row_bytes = rows * elem
+    read_len = torch.zeros(n_reads, dtype=torch.int64).index_add_(0, read, rows)
+    padded = (read_len * elem + (align - 1)) // align * align
+    read_off = torch.zeros(n_reads, dtype=torch.int64)
+    if n_reads > 1:
+        read_off[1:] = torch.cumsum(padded, 0)[:-1]
+    excl = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(row_bytes, 0)])   # (bytes of the rows in front of each row)
+    dst_off = read_off[read] + excl[:-1] - excl[first][read]   # (... and in front of the row within its read)
+    return Pod5Layout(dst_off.to(device), row_bytes.to(torch.int32).to(device), read_off.to(device), read_len.to(device), int(padded.sum().item()))

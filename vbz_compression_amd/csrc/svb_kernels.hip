@@ -2091,17 +2091,213 @@ __global__ __launch_bounds__(WG) void svb_half_decode_kernel(ReadBatch b)
     if (tid == 0) b.result[r] = (bad || ((posn + 1u) >> 1) != dataBytes) ? E_STREAM : count;
 }
 
+// ------------------------------------------------------------------------------------------------
+// svb16: the svb stage of POD5 signal rows (VBZ_GPU_VERSION_POD5; the format: include/vbz_gpu.h)
+//   ceil(n / 8) key bytes, bit j % 8 of byte j / 8 set when zig-zag delta z_j takes two data bytes; then the data bytes, z_j as one
+//   byte (z_j < 256) or two, little-endian.  Delta coding starts from 0 in every row, 16-bit wrap-around, as v0's int16 path.
+// The one-workgroup-per-read shape of the byte codec above, one tile (256 lanes x 8 samples) per trip: at VPL = 8 a lane's samples
+// are exactly one key byte, its data length is 8 + popcount(key), one workgroup scan gives the data offsets and a second one the
+// delta sums; data bytes are staged through LDS so that HBM sees aligned 16-byte lines.  The decoder stores through DecStore<2, OUT>:
+// the int16, typed, chunk and counting stores of v0's int16 decoder.  Both run on the large-read path too (one workgroup per read;
+// DESIGN.md 4.13).
+// ------------------------------------------------------------------------------------------------
+constexpr int SVB16_TILE = WG * 8;
+
+__global__ __launch_bounds__(WG) void svb16_encode_kernel(ReadBatch b, uint32_t* period_hint)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 32];   // the bytes short of a line + one tile's worst case
+    __shared__ uint32_t wsum[4];
+
+    const uint32_t r = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (period_hint && tid == 0) period_hint[r] = 0;   // (the svb16 stream is not probed: the entropy stage's matcher stays off)
+    if (b.gate && b.gate[r] >= GATE_SKIP) {
+        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
+        return;
+    }
+    const uint32_t size = b.src_size[r];
+    if (size & 1u) {
+        if (tid == 0) b.result[r] = E_INPUT_SIZE;
+        return;
+    }
+    const uint32_t n = size >> 1, K = (n + 7u) >> 3;
+    const uint64_t worst = (uint64_t)K + 2ull * n;   // svb16_max(n)
+    if (worst > b.dst_cap[r]) {
+        if (tid == 0) b.result[r] = worst > 0xFFFFFFF0ull ? E_INPUT_SIZE : E_DESTINATION_SIZE;
+        return;
+    }
+    const uint8_t* in = b.src + b.src_off[r];
+    uint8_t* keys = b.dst + b.dst_off[r];
+    uint8_t* data = keys + K;
+    const uint32_t A = (uint32_t)((uintptr_t)data & 15u);
+    uint8_t* gal = data - A;   // the 16-byte aligned address space of the data bytes
+    const bool in_aligned = (((uintptr_t)in) & 15u) == 0;
+    uint64_t F = 0;   // bytes of the aligned space flushed (a multiple of 16)
+    uint64_t P = A;   // the next byte position; stage[] holds [F, P)
+    for (uint32_t t0 = 0; t0 < n; t0 += SVB16_TILE) {
+        const uint32_t i0 = t0 + (uint32_t)tid * 8u;
+        const int valid = i0 >= n ? 0 : (n - i0 >= 8u ? 8 : (int)(n - i0));
+        uint32_t x[8];
+        if (valid == 8 && in_aligned) {
+            const uint4 q = *reinterpret_cast<const uint4*>(in + (size_t)i0 * 2);
+            const uint32_t w[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = k < valid ? (uint32_t)(uint16_t)load_elem(in + (size_t)(i0 + k) * 2, 2) : 0u;
+        }
+        // the sample in front: the lane below's last one; lane 0 of a wavefront reads it
+        uint32_t prev = wave_prev_lane_u32(x[7]);
+        if (lane == 0) prev = (i0 == 0 || valid == 0) ? 0u : (uint32_t)(uint16_t)load_elem(in + (size_t)(i0 - 1) * 2, 2);
+        uint32_t z[8], key = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t d = (x[k] - prev) & 0xFFFFu;   // wrap-around delta, 16-bit zig-zag
+            z[k] = ((d << 1) ^ (0u - (d >> 15))) & 0xFFFFu;
+            prev = x[k];
+            if (k < valid && z[k] > 0xFFu) key |= 1u << k;
+        }
+        if (valid > 0) keys[i0 >> 3] = (uint8_t)key;
+        const uint32_t L = (uint32_t)valid + (uint32_t)__popc(key);
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan_u32(L, wsum, tot);
+        uint32_t o = (uint32_t)(P - F) + ex;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k < valid) {
+                stage[o++] = (uint8_t)z[k];
+                if (z[k] > 0xFFu) stage[o++] = (uint8_t)(z[k] >> 8);
+            }
+        }
+        wg_lds_barrier();
+        const uint32_t endidx = (uint32_t)(P - F) + tot, nch = endidx >> 4;
+        for (uint32_t c = tid; c < nch; c += WG) {
+            uint8_t* g = gal + F + 16ull * c;
+            if (F == 0 && c == 0 && A != 0) {
+                for (uint32_t j = A; j < 16; ++j) g[j] = stage[j];
+            } else {
+                *reinterpret_cast<uint4*>(g) = *reinterpret_cast<const uint4*>(stage + 16u * c);
+            }
+        }
+        const uint32_t rem = endidx & 15u;
+        uint8_t keep = 0;
+        if ((uint32_t)tid < rem) keep = stage[16u * nch + tid];
+        wg_lds_barrier();
+        if (nch > 0 && (uint32_t)tid < rem) stage[tid] = keep;
+        F += 16ull * nch;
+        P += tot;
+        // (the scan at the top of the next tile holds the barrier that orders these LDS writes)
+    }
+    wg_lds_barrier();
+    {   // the tail: bytes [F, P) still in LDS
+        const uint32_t rem = (uint32_t)(P - F), lo = F == 0 ? A : 0u;
+        if ((uint32_t)tid >= lo && (uint32_t)tid < rem) gal[F + tid] = stage[tid];
+    }
+    if (tid == 0) b.result[r] = K + (uint32_t)(P - A);
+}
+
+// The verdicts of a POD5 row: content longer than svb16_max(n) is the zstd stage's (E_ZSTD), a stream whose length is not
+// K + n + popcount(the first n key bits) -- bytes missing or left over -- E_STREAM.
+template <int OUT>
+__global__ __launch_bounds__(WG) void svb16_decode_kernel(ReadBatch b)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+
+    const uint32_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (b.gate && b.gate[r] >= GATE_SKIP) {
+        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
+        return;
+    }
+    const uint32_t in_size = b.src_size[r];
+    if (in_size >= E_FIRST) {   // the previous stage failed for this read
+        if (tid == 0) b.result[r] = in_size;
+        return;
+    }
+    const uint32_t out_size = b.dst_cap[r];
+    if (out_size & 1u) {
+        if (tid == 0) b.result[r] = E_DESTINATION_SIZE;
+        return;
+    }
+    const uint32_t count = out_size >> 1, K = (count + 7u) >> 3;
+    if ((uint64_t)in_size > (uint64_t)K + 2ull * count || in_size < K) {
+        if (tid == 0) b.result[r] = in_size < K ? E_STREAM : E_ZSTD;
+        return;
+    }
+    if (count == 0) {   // (an empty stream: nothing to store or count -- every pass gives the verdict)
+        if (tid == 0) b.result[r] = 0;
+        return;
+    }
+    if (OUT == SIG_COUNT && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
+    const uint8_t* in = b.src + b.src_off[r];
+    const uint8_t* data = in + K;
+    const uint32_t dataBytes = in_size - K;
+    const DecStore<2, OUT> st(b.dst, b.dst_off, OUT == SIG_NONE ? nullptr : &b, r, count);
+    uint64_t pos = 0;   // data bytes consumed
+    uint32_t run = 0;   // the delta chain's running value
+    bool good = true;
+    for (uint32_t t0 = 0; t0 < count; t0 += SVB16_TILE) {
+        const uint32_t i0 = t0 + (uint32_t)tid * 8u;
+        const int valid = i0 >= count ? 0 : (count - i0 >= 8u ? 8 : (int)(count - i0));
+        const uint32_t key = valid > 0 ? (uint32_t)in[i0 >> 3] & ((1u << valid) - 1u) : 0u;   // (unused key bits ignored)
+        const uint32_t L = (uint32_t)valid + (uint32_t)__popc(key);
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan_u32(L, wsum, tot);
+        if (pos + tot > dataBytes) {   // (workgroup-uniform) fewer data bytes than the key bits announce
+            good = false;
+            break;
+        }
+        const uint8_t* g0 = data + pos;
+        const uint32_t mis = (uint32_t)((uintptr_t)g0 & 15u);
+        const uint8_t* ga = g0 - mis;
+        const uint32_t nch = (mis + tot + 15u) >> 4;
+        for (uint32_t c = tid; c < nch; c += WG)
+            *reinterpret_cast<uint4*>(stage + 16u * c) = *reinterpret_cast<const uint4*>(ga + 16ull * c);
+        wg_lds_barrier();
+        uint32_t o = mis + ex, s[8], acc = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t two = (key >> k) & 1u;
+            uint32_t v = stage[o] | (two ? (uint32_t)stage[o + 1] << 8 : 0u);
+            o += 1u + two;
+            v = (v >> 1) ^ (0u - (v & 1u));
+            acc += k < valid ? v : 0u;
+            s[k] = acc;
+        }
+        uint32_t ttot;
+        const uint32_t base = run + block_excl_scan_u32(acc, wsum, ttot);   // (its barriers also keep the next tile's staging behind these reads)
+        run += ttot;
+        st.put(i0, valid, base, s);
+        pos += tot;
+    }
+    st.finish();
+    st.done();
+    if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * st.BYTES;
+}
+
+// the raw byte count whose 32-bit key region ((x / 4 + 3) / 4 bytes: the entropy stage's key_elem = 4) is svb16's ceil(n / 8)
+__global__ __launch_bounds__(WG) void svb16_key_raw_kernel(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw)
+{
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t k = ((uint64_t)(raw_size[i] >> 1) + 7u) >> 3;
+    key_raw[i] = (uint32_t)std::min<uint64_t>(16u * k, 0xFFFFFFF0ull);
+}
+
 // ---- normalising decode: the reads' starting windows, and the select of the large-read path --------------------------------------------
 // One thread per read: the first pass's windows are NORM_WINDOWS x NORM_BINS adjacent keys around the read's first sample, which the
 // stream's first control and data bytes give (any anchor gives the same statistics; a good one saves the later passes).  A read of no
-// samples is finished here (c = w = 0).
-__global__ __launch_bounds__(WG) void norm_init_kernel(ReadBatch b, uint32_t zigzag)
+// samples is finished here (c = w = 0).  SVB16: the stream is svb16's (one key bit per sample).
+template <bool SVB16>
+__device__ __forceinline__ void norm_init_read(const ReadBatch& b, uint32_t zigzag)
 {
     const uint32_t r = blockIdx.x * WG + threadIdx.x;
     if (r >= b.n_reads || (b.gate && b.gate[r] >= GATE_SKIP)) return;
     const uint32_t in_size = b.src_size[r], out_size = b.dst_cap[r];
     if (in_size >= E_FIRST || (out_size & 1u)) return;
-    const uint32_t T = out_size >> 1, keyLen = (T + 3u) >> 2;
+    const uint32_t T = out_size >> 1, keyLen = SVB16 ? (T + 7u) >> 3 : (T + 3u) >> 2;
     NormRead* sp = b.sig.norm.st + r;
     if (T == 0) {
         norm_finish(b, r, 0.0, 0.0);
@@ -2111,7 +2307,7 @@ __global__ __launch_bounds__(WG) void norm_init_kernel(ReadBatch b, uint32_t zig
     uint32_t a = 0x8000u;
     if (in_size >= keyLen + 2u) {
         const uint8_t* in = b.src + b.src_off[r];
-        uint32_t v = in[keyLen] | ((in[0] & 3u) ? (uint32_t)in[keyLen + 1] << 8 : 0u);
+        uint32_t v = in[keyLen] | ((in[0] & (SVB16 ? 1u : 3u)) ? (uint32_t)in[keyLen + 1] << 8 : 0u);
         if (zigzag) v = (v >> 1) ^ (0u - (v & 1u));
         a = (v ^ b.sig.bias ^ 0x8000u) & 0xFFFFu;
     }
@@ -2129,6 +2325,8 @@ __global__ __launch_bounds__(WG) void norm_init_kernel(ReadBatch b, uint32_t zig
         sp->z[w] = 0xFFFFu;
     }
 }
+__global__ __launch_bounds__(WG) void norm_init_kernel(ReadBatch b, uint32_t zigzag) { norm_init_read<false>(b, zigzag); }
+__global__ __launch_bounds__(WG) void norm_init16_kernel(ReadBatch b) { norm_init_read<true>(b, 1u); }
 
 // one workgroup per read: the counts the segments added to the read's slab (zeroed again for the next pass) -> the select
 __global__ __launch_bounds__(WG) void norm_select_kernel(ReadBatch b)
@@ -2297,6 +2495,42 @@ hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, 
     case SIG_BF16 | SIG_CHUNK: return svb_decode_launch<SIG_BF16 | SIG_CHUNK>(b, integer_size, zigzag, s);
     default: return hipErrorInvalidValue;
     }
+}
+
+// ---- svb16 (POD5) ---------------------------------------------------------------------------------------------------
+hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStream_t s)
+{
+    if (b.n_reads == 0) return hipSuccess;
+    hipLaunchKernelGGL(svb16_encode_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, period_hint);
+    return hipGetLastError();
+}
+
+hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s)
+{
+    if (b.n_reads == 0) return hipSuccess;
+    if (b.sig.norm.st) {   // the counting passes (each selects at its end: one workgroup per read), then the store
+        if (b.sig.norm.slab) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(norm_init16_kernel, dim3((b.n_reads + WG - 1) / WG), dim3(WG), 0, s, b);
+        for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p) hipLaunchKernelGGL(svb16_decode_kernel<SIG_COUNT>, dim3(b.n_reads), dim3(WG), 0, s, b);
+        if (b.sig.type == SIG_NONE) return hipGetLastError();
+    }
+    switch (svb_decode_out(b)) {
+    case SIG_NONE: return launch1(svb16_decode_kernel<SIG_NONE>, b, s);
+    case SIG_F32: return launch1(svb16_decode_kernel<SIG_F32>, b, s);
+    case SIG_F16: return launch1(svb16_decode_kernel<SIG_F16>, b, s);
+    case SIG_BF16: return launch1(svb16_decode_kernel<SIG_BF16>, b, s);
+    case SIG_F32 | SIG_CHUNK: return launch1(svb16_decode_kernel<SIG_F32 | SIG_CHUNK>, b, s);
+    case SIG_F16 | SIG_CHUNK: return launch1(svb16_decode_kernel<SIG_F16 | SIG_CHUNK>, b, s);
+    case SIG_BF16 | SIG_CHUNK: return launch1(svb16_decode_kernel<SIG_BF16 | SIG_CHUNK>, b, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_svb16_key_raw(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(svb16_key_raw_kernel, dim3((n + WG - 1) / WG), dim3(WG), 0, s, n, raw_size, key_raw);
+    return hipGetLastError();
 }
 
 // ---- segmented launches (few, large reads) --------------------------------------------------------------------------

@@ -245,9 +245,19 @@ void dbg_end(vbz_gpu_ctx* c, uint32_t n, const char* what, unsigned long long* d
 // v1 codes 1-byte integers with the nibble codec (vbz/v1/vbz_streamvbyte.cpp:22-113)
 bool half_codec(const CompressionOptions* o) { return o->vbz_version == 1 && o->integer_size == 1; }
 
+// POD5 signal rows (VBZ_GPU_VERSION_POD5): svb16 + one zstd frame, int16 zig-zag samples, no sized header, level >= 1
+bool pod5_codec(const CompressionOptions* o) { return o->vbz_version == VBZ_GPU_VERSION_POD5; }
+
 bool valid_int_size(const CompressionOptions* o)  // vbz/vbz.cpp:44-50
 {
     return o->integer_size == 0 || o->integer_size == 1 || o->integer_size == 2 || o->integer_size == 4;
+}
+
+// the options of the batched calls: the reference's (versions 0 and 1), or POD5 rows with their one layout
+bool batch_options_ok(const CompressionOptions* o, int sized)
+{
+    if (pod5_codec(o)) return o->integer_size == 2 && o->perform_delta_zig_zag && o->zstd_compression_level >= 1 && sized == 0;
+    return valid_int_size(o) && (o->integer_size == 0 || o->vbz_version <= 1);
 }
 
 // worst-case svb bytes per raw byte as a fraction, for what the device encoder can really emit
@@ -465,7 +475,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
     uint32_t num = 1, den = 1;
     size_t scratch_need = 0;
     uint64_t* svb_off = nullptr;
-    uint32_t *svb_cap = nullptr, *svb_size = nullptr, *gate = nullptr, *deep_d = nullptr;
+    uint32_t *svb_cap = nullptr, *svb_size = nullptr, *gate = nullptr, *deep_d = nullptr, *key_raw = nullptr;
     bool scratch_planned = false;
     MetaCarver mc(nullptr);
     if (both_stages) {
@@ -479,6 +489,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
         svb_size = mc.take<uint32_t>(n);
         gate = mc.take<uint32_t>(n);
         deep_d = mc.take<uint32_t>(n);
+        if (pod5_codec(o)) key_raw = mc.take<uint32_t>(n);
         if (pre) {   // (both stages, one-workgroup path: what split_batch asks for)
             svb_off = pre->svb_off;
             svb_cap = pre->svb_cap;
@@ -527,15 +538,26 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
     // histogram of int16 zig-zag reads (svb_kernels.hip CNT)
     unsigned long long* dbg = segmented ? nullptr : dbg_begin(c, n);
     const bool staged = !segmented && c->staged_encode && (!dbg || c->phase_timing == 3) && c->zero_run_sequences;
-    const bool pre_filled = staged && svb_encode_fills_plans((int)o->integer_size, o->perform_delta_zig_zag, half_codec(o));
+    const bool pod5 = pod5_codec(o);
+    const bool pre_filled = staged && !pod5 && svb_encode_fills_plans((int)o->integer_size, o->perform_delta_zig_zag, half_codec(o));
     void* plan = nullptr;
     if (staged) {
         if (!ensure(c, c->encplan, zstd_encode_plan_bytes(n))) return -1;
         plan = c->encplan.p;
     }
+    // the entropy stage's key region: ceil(n / 4) bytes of the raw size at integer_size, or svb16's ceil(n / 8) through key_raw (POD5)
+    const uint32_t* key_orig = bt->src_size;
+    uint32_t key_elem = o->integer_size;
+    if (pod5) {
+        HIPCHK(c, launch_svb16_key_raw(n, bt->src_size, key_raw, s), "svb16 key launch");
+        key_orig = key_raw;
+        key_elem = SVB16_KEY_ELEM;
+    }
     {
         Timed t(c, "svb_encode");
-        if (segmented)
+        if (pod5)   // (one workgroup per read on every path: DESIGN.md 4.13)
+            HIPCHK(c, launch_svb16_encode(a, (matcher && !segmented) ? deep_d : nullptr, s), "svb16_encode launch");
+        else if (segmented)
             HIPCHK(c, launch_svb_encode_seg(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, seg.first, seg.max_segs, seg.val, seg.off, s),
                    "svb_encode (segmented) launch");
         else
@@ -584,22 +606,22 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
             // a long read's data bytes only (PROBE_WINDOW in zstd_encode.hip): two short launches for a read that has no period.
             uint32_t* gate2 = mc.take<uint32_t>(n);
             Timed t(c, "zstd_encode_matcher");
-            HIPCHK(c, launch_zstd_encode_matcher(z, bt->src_size, o->integer_size, hdr, svb_cap, c->seqtab.p, c->trailers, 0xFFFFFFFFu,
+            HIPCHK(c, launch_zstd_encode_matcher(z, key_orig, key_elem, hdr, svb_cap, c->seqtab.p, c->trailers, 0xFFFFFFFFu,
                                                  deep_d, gate, gate2, s),
                    "zstd_encode (matcher) launch");
             z.gate = gate2;
         }
         Timed t(c, "zstd_encode");
-        HIPCHK(c, launch_zstd_encode_spans(z, bt->src_size, o->integer_size, hdr, c->zero_run_sequences ? svb_cap : nullptr,
+        HIPCHK(c, launch_zstd_encode_spans(z, key_orig, key_elem, hdr, c->zero_run_sequences ? svb_cap : nullptr,
                                            c->zero_run_sequences ? c->seqtab.p : nullptr, desc, span_first, span_count, max_spans,
                                            (uint8_t*)c->spantmp.p, tmp_bytes, span_size, span_trail, span_dst, c->trailers, regions, shspan, s),
                "zstd_encode (spans) launch");
-        return checksum_frames(c, z, gate, hdr, bt->src_size, o->integer_size);
+        return checksum_frames(c, z, gate, hdr, pod5 ? nullptr : bt->src_size, o->integer_size);
     }
     {
         Timed t(c, "zstd_encode");
         // (phase timing 2: the planning launch's counters, 3: the packing launch's; both under load, the other launches as they are)
-        HIPCHK(c, launch_zstd_encode(z, bt->src_size, o->integer_size, nullptr, hdr, c->phase_timing == 3 ? nullptr : dbg,
+        HIPCHK(c, launch_zstd_encode(z, key_orig, key_elem, nullptr, hdr, c->phase_timing == 3 ? nullptr : dbg,
                                      c->zero_run_sequences ? svb_cap : nullptr, c->zero_run_sequences ? c->seqtab.p : nullptr, c->trailers,
                                      (matcher && !dbg && c->long_repeats != 2) ? deep_d : nullptr, plan, staged, pre_filled, c->phase_timing == 3 ? dbg : nullptr, s),
                "zstd_encode launch");
@@ -609,7 +631,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
             : c->phase_timing == 2 ? "zstd_encode planning launch: setup hist plan - store+sequences - | plan: sort merge lengths codes weights tree"
                                    : "zstd_encode: setup hist plan size hdr encode",
             dbg);
-    return checksum_frames(c, z, gate, hdr, bt->src_size, o->integer_size);
+    return checksum_frames(c, z, gate, hdr, pod5 ? nullptr : bt->src_size, o->integer_size);
 }
 
 constexpr uint32_t REF_MIN_READS = 2560;   // calls of fewer reads: the one-wavefront decoder walks reference-written chains itself
@@ -697,7 +719,8 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
         return 0;
     }
     SegTables seg;
-    if (rb.sig.norm.st && segmented) {   // (a normalising decode on the large-read path: the segments' counts add up here)
+    const bool pod5 = pod5_codec(o);
+    if (rb.sig.norm.st && segmented && !pod5) {   // (a normalising decode on the large-read path: the segments' counts add up here)
         if (!ensure(c, c->normslab, (size_t)n * NORM_SLAB * 4)) return -1;
         rb.sig.norm.slab = reinterpret_cast<uint32_t*>(c->normslab.p);
     }
@@ -784,7 +807,7 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
         uint32_t* dspan_status = sm.take<uint32_t>((size_t)max_spans * 4);
         uint32_t* redo = sm.take<uint32_t>(n);
         Timed t(c, "zstd_decode");
-        HIPCHK(c, launch_zstd_decode_spans(z, E_STREAM, c->seqdtab.p, desc, dspan_first, dspan_count, max_spans, dspan_status, redo, s),
+        HIPCHK(c, launch_zstd_decode_spans(z, pod5 ? E_ZSTD : E_STREAM, c->seqdtab.p, desc, dspan_first, dspan_count, max_spans, dspan_status, redo, s),
                "zstd_decode (spans) launch");
         c->last_frames = 0;
         c->last_span_frames = n;
@@ -792,8 +815,8 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     } else {
         c->last_span_frames = 0;
         // a frame whose content cannot be a valid svb stream of the expected size: the reference would
-        // decode it and then fail in the svb stage with a stream error
-        if (zstd_frames(c, z, E_STREAM, dst_bytes, dbg) != 0) return -1;
+        // decode it and then fail in the svb stage with a stream error (POD5: content beyond svb16_max(n) is the zstd stage's error)
+        if (zstd_frames(c, z, pod5 ? E_ZSTD : E_STREAM, dst_bytes, dbg) != 0) return -1;
     }
     if (pre && pre->after_first) HIPCHK(c, hipEventRecord(pre->after_first, s), "event record");
     dbg_end(c, n, "zstd_decode: parse flush seqtables chain place huftable header queue | general sequences: flush tables records literals matches", dbg);
@@ -805,7 +828,9 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     d.gate = gate;
     {
         Timed t(c, "svb_decode");
-        if (segmented)
+        if (pod5)   // (one workgroup per read on every path: DESIGN.md 4.13)
+            HIPCHK(c, launch_svb16_decode(d, s), "svb16_decode launch");
+        else if (segmented)
             HIPCHK(c, launch_svb_decode_seg(d, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, s),
                    "svb_decode (segmented) launch");
         else
@@ -1151,10 +1176,10 @@ int compress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressi
 }
 
 // the options and the sample format of a signal or chunk decode (`what`: which decode, for the error text)
-bool typed_args_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_signal_format* f, const char* what)
+bool typed_args_ok(vbz_gpu_ctx* c, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f, const char* what)
 {
-    if (!o || o->integer_size != 2 || o->vbz_version > 1) {
-        set_error(c, "unsupported options for a %s decode (integer_size must be 2, version 0 or 1)", what);
+    if (!o || o->integer_size != 2 || !batch_options_ok(o, sized)) {
+        set_error(c, "unsupported options for a %s decode (integer_size must be 2, version 0, 1 or POD5)", what);
         return false;
     }
     if (!f || f->out_type < VBZ_GPU_SIGNAL_F32 || f->out_type > VBZ_GPU_SIGNAL_BF16 || f->is_signed > 1) {
@@ -1455,8 +1480,9 @@ int vbz_gpu_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compre
 {
     if (!c || !bt || !o) return -1;
     DeviceGuard dg(c->device);
-    if (!valid_int_size(o) || (o->integer_size != 0 && o->vbz_version > 1)) {
-        set_error(c, "unsupported options (integer_size=%u version=%u)", o->integer_size, o->vbz_version);
+    if (!batch_options_ok(o, sized)) {
+        set_error(c, "unsupported options (integer_size=%u version=%u sized=%d level=%d zigzag=%d)", o->integer_size, o->vbz_version, sized,
+                  o->zstd_compression_level, (int)o->perform_delta_zig_zag);
         return -2;
     }
     if (!plausible_extents(c, bt)) return -2;
@@ -1467,8 +1493,9 @@ int vbz_gpu_decompress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Comp
 {
     if (!c || !bt || !o) return -1;
     DeviceGuard dg(c->device);
-    if (!valid_int_size(o) || (o->integer_size != 0 && o->vbz_version > 1)) {
-        set_error(c, "unsupported options (integer_size=%u version=%u)", o->integer_size, o->vbz_version);
+    if (!batch_options_ok(o, sized)) {
+        set_error(c, "unsupported options (integer_size=%u version=%u sized=%d level=%d zigzag=%d)", o->integer_size, o->vbz_version, sized,
+                  o->zstd_compression_level, (int)o->perform_delta_zig_zag);
         return -2;
     }
     if (!plausible_extents(c, bt)) return -2;
@@ -1479,7 +1506,7 @@ int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, f, "signal")) return -2;
+    if (!typed_args_ok(c, o, sized, f, "signal")) return -2;
     if (!plausible_extents(c, bt)) return -2;
     const TypedOut out = { f };
     return decompress_batch_impl(c, bt, o, sized, false, &out);
@@ -1552,7 +1579,7 @@ int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, f, "chunk")) return -2;
+    if (!typed_args_ok(c, o, sized, f, "chunk")) return -2;
     return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, nullptr, nullptr);
 }
 
@@ -1589,7 +1616,7 @@ int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Com
     DeviceGuard dg(c->device);
     const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
     const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };   // (what typed_args_ok checks: options, is_signed)
-    if (!typed_args_ok(c, o, &probe, "statistics") || !norm_ok(c, norm, nullptr)) return -2;
+    if (!typed_args_ok(c, o, sized, &probe, "statistics") || !norm_ok(c, norm, nullptr)) return -2;
     if (!shift_scale) {
         set_error(c, "shift_scale is NULL");
         return -2;
@@ -1608,7 +1635,7 @@ int vbz_gpu_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, f, "signal") || !norm_ok(c, norm, f)) return -2;
+    if (!typed_args_ok(c, o, sized, f, "signal") || !norm_ok(c, norm, f)) return -2;
     if (!plausible_extents(c, bt)) return -2;
     TypedOut out = { f };
     out.norm = norm;
@@ -1622,7 +1649,7 @@ int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, f, "chunk") || !norm_ok(c, norm, f)) return -2;
+    if (!typed_args_ok(c, o, sized, f, "chunk") || !norm_ok(c, norm, f)) return -2;
     return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale);
 }
 
@@ -1630,6 +1657,12 @@ int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int inte
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
+    if ((unsigned)version == VBZ_GPU_VERSION_POD5) {
+        if (integer_size != 2 || !zigzag) return -2;
+        Timed t(c, "svb_encode");
+        HIPCHK(c, launch_svb16_encode(to_rb(bt), nullptr, c->stream), "svb16_encode launch");
+        return 0;
+    }
     if ((integer_size != 1 && integer_size != 2 && integer_size != 4) || version > 1 || version < 0) return -2;
     Timed t(c, "svb_encode");
     HIPCHK(c, launch_svb_encode(to_rb(bt), integer_size, zigzag != 0, 0, true, version == 1 && integer_size == 1, nullptr, nullptr, c->stream), "svb_encode launch");
@@ -1640,10 +1673,22 @@ int vbz_gpu_svb_decompress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int in
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
+    if ((unsigned)version == VBZ_GPU_VERSION_POD5) {
+        if (integer_size != 2 || !zigzag) return -2;
+        Timed t(c, "svb_decode");
+        HIPCHK(c, launch_svb16_decode(to_rb(bt), c->stream), "svb16_decode launch");
+        return 0;
+    }
     if ((integer_size != 1 && integer_size != 2 && integer_size != 4) || version > 1 || version < 0) return -2;
     Timed t(c, "svb_decode");
     HIPCHK(c, launch_svb_decode(to_rb(bt), integer_size, zigzag != 0, version == 1 && integer_size == 1, c->stream), "svb_decode launch");
     return 0;
+}
+
+uint64_t vbz_gpu_pod5_max_compressed_size(uint32_t samples)
+{
+    const uint64_t n = samples, svb = (n + 7) / 8 + 2 * n;   // svb16_max(n)
+    return svb + (svb >> 8) + (svb < (128u << 10) ? (((128u << 10) - svb) >> 11) : 0);   // ZSTD_COMPRESSBOUND
 }
 
 int vbz_gpu_zstd_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const uint32_t* key_bytes)
@@ -1720,7 +1765,7 @@ int vbz_gpu_decompressed_size_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
-    if (!o || !valid_int_size(o)) {
+    if (!o || !valid_int_size(o) || pod5_codec(o)) {   // (POD5 rows carry no size header)
         set_error(c, "unsupported options");
         return -2;
     }

@@ -157,6 +157,15 @@ bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half);   // does
 // the store and leave every read's constants in b.sig.cal (and b.sig.norm.ss); with b.sig.type == SIG_NONE they are all that runs (the
 // results are the int16 decode's; launch_svb_decode_seg: b.sig.norm.slab must be set).
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s);
+// svb16, the svb stage of POD5 signal rows (int16 samples, delta + zig-zag; one key bit per sample): one workgroup per read, on every
+// path.  Encode: the worst case ceil(n / 8) + 2n must fit dst_cap (else E_DESTINATION_SIZE); period_hint (nullable) is zeroed (no
+// matcher).  Decode: the stores of launch_svb_decode(2, zigzag) (b.sig; b.sig.norm.slab must be NULL); a stream longer than
+// ceil(n / 8) + 2n is E_ZSTD, one whose length the key bits do not announce E_STREAM.
+hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStream_t s);
+hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s);
+// key_raw[i]: the raw size whose key region at key_elem = 4 is svb16's ceil(n / 8) bytes (the entropy stage's orig_size for POD5, hdr 0)
+hipError_t launch_svb16_key_raw(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw, hipStream_t s);
+constexpr uint32_t SVB16_KEY_ELEM = 4;
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
 // bounds the total segment count (the grid); seg_* are scratch arrays of max_segs entries.  Not for the nibble codec.
