@@ -254,13 +254,12 @@ def test_svb_int16_decoder_body_tail_split():
 
 
 def test_wave_svb_decoder_behind_the_entropy_stage():
-    """The int16 zig-zag stream behind the entropy stage has two decoders: svb_decode_kernel with its block path (lanes own
-    32 consecutive values, packed 16-bit arithmetic), and -- VBZ_HIP_FUSE_SVB=1 -- the wavefront that decoded the frame
-    (svb_wave.h).  Same verdicts from both: foreign and malformed svb streams (codes 2 / 3, wrong lengths, short and long
-    streams, every length class of the block paths) packed into frames by libzstd -- what a foreign writer could store --
+    """The int16 zig-zag stream behind the entropy stage is decoded by svb_decode_kernel with its block path (lanes own 32
+    consecutive values, packed 16-bit arithmetic).  Foreign and malformed svb streams (codes 2 / 3, wrong lengths, short and
+    long streams, every length class of the block paths) packed into frames by libzstd -- what a foreign writer could store --
     must give the oracle's samples or the oracle's error."""
     import gpu_util as G
-    from vbz_compression_amd import _lib, batch
+    from vbz_compression_amd import _lib
 
     rng = np.random.default_rng(77)
     cases = []   # (svb stream, claimed output bytes)
@@ -277,7 +276,7 @@ def test_wave_svb_decoder_behind_the_entropy_stage():
         codes = np.array([(keys[i >> 2] >> (2 * (i & 3))) & 3 for i in range(n)])
         data = rng.integers(0, 256, int((codes + 1).sum()), dtype=np.uint8)
         cases.append((np.concatenate([keys, data]), 2 * n))
-    a = O.synth_signal(5, 99, 30000)   # wide codes in the middle of an ordinary stream: the pipeline hands over to the tile loop
+    a = O.synth_signal(5, 99, 30000)   # wide codes in the middle of an ordinary stream: the block path hands over to the tile loop
     st = O.svb_compress(a, 2, True, 0).copy()
     K = (len(a) + 3) // 4
     wide = st.copy()
@@ -289,22 +288,9 @@ def test_wave_svb_decoder_behind_the_entropy_stage():
     frames = [O.zstd_compress(st, 1) for st, _ in cases]
     want = [O.decompress(f, nb, oo) for f, (_, nb) in zip(frames, cases)]
     assert sum(1 for w in want if isinstance(w, int)) >= 40 and sum(1 for w in want if not isinstance(w, int)) >= 20
-    keep = G._codec, _lib._lib, _lib.LIB_PATH
-    try:
-        for fuse in ("0", "1"):   # the separate svb_decode launch (the product), and the frame's own wavefront (experiments build)
-            if fuse == "1":
-                _lib._lib, _lib.LIB_PATH = None, _lib.EXPERIMENTS_LIB_PATH
-            os.environ["VBZ_HIP_FUSE_SVB"] = fuse
-            try:
-                G._codec = batch.GpuCodec(0)
-                assert (b"+experiments" in G._codec.L.vbz_gpu_version()) == (fuse == "1")
-            finally:
-                del os.environ["VBZ_HIP_FUSE_SVB"]
-            got = G.decompress(frames, [nb for _, nb in cases], _lib.CompressionOptions(True, 2, 1, 1))
-            for i, (w, g) in enumerate(zip(want, got)):
-                assert _same(g, w), (fuse, i, len(cases[i][0]), cases[i][1], g if isinstance(g, int) else "samples", w if isinstance(w, int) else "samples")
-    finally:
-        G._codec, _lib._lib, _lib.LIB_PATH = keep
+    got = G.decompress(frames, [nb for _, nb in cases], _lib.CompressionOptions(True, 2, 1, 1))
+    for i, (w, g) in enumerate(zip(want, got)):
+        assert _same(g, w), (i, len(cases[i][0]), cases[i][1], g if isinstance(g, int) else "samples", w if isinstance(w, int) else "samples")
 
 
 # ------------------------------------------------------------------------------------------------

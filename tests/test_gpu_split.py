@@ -12,20 +12,18 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _codec(split_min, stagger=1):
+def _codec(split_min):
     from vbz_compression_amd import batch
 
-    old = {k: os.environ.get(k) for k in ("VBZ_HIP_SPLIT_MIN", "VBZ_HIP_SPLIT_STAGGER")}
+    old = os.environ.get("VBZ_HIP_SPLIT_MIN")
     os.environ["VBZ_HIP_SPLIT_MIN"] = str(split_min)
-    os.environ["VBZ_HIP_SPLIT_STAGGER"] = str(stagger)
     try:
-        return batch.GpuCodec(0)   # (the knobs are read when the context is created)
+        return batch.GpuCodec(0)   # (the knob is read when the context is created)
     finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+        if old is None:
+            os.environ.pop("VBZ_HIP_SPLIT_MIN", None)
+        else:
+            os.environ["VBZ_HIP_SPLIT_MIN"] = old
 
 
 def _make(c, first, n, opts, sized, long_reads=False, bad=()):
@@ -82,12 +80,11 @@ def _roundtrip(c, B, opts):
 
 
 @pytest.mark.parametrize("sized", [False, True])
-@pytest.mark.parametrize("stagger", [0, 1])
-def test_split_call_writes_what_the_unsplit_call_writes(sized, stagger):
+def test_split_call_writes_what_the_unsplit_call_writes(sized):
     import torch
 
     plain = _codec(0)
-    split = _codec(64, stagger)
+    split = _codec(64)
     opts = plain.options(True, 2, 1, 1)
     n = 301                                              # an odd count: the halves differ
     B = _make(plain, 1000, n, opts, sized, bad=(17, n - 9))

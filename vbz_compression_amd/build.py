@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SOURCES = ["svb_kernels.hip", "zstd_encode.hip", "zstd_decode.hip", "zstd_decode_fast.hip", "zstd_decode_ref.hip", "helpers.hip", "xxh64.hip", "pack.hip", "vbz_api.hip"]
-HEADERS = ["vbz_kernels.h", "xxh64.h", "zstd_entropy.h", "svb_wave.h", "zstd_runs.h", "zstd_tables.h", "zstd_frame.h", "../../include/vbz.h", "../../include/vbz_gpu.h", "../../include/vbz_hdf_plugin.h"]
+HEADERS = ["vbz_kernels.h", "xxh64.h", "zstd_entropy.h", "zstd_runs.h", "zstd_tables.h", "zstd_frame.h", "../../include/vbz.h", "../../include/vbz_gpu.h", "../../include/vbz_hdf_plugin.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The SDWA peephole is off: a byte-1 SDWA shift feeding v_bitop3_b16 produced a wrong block-header byte on hardware
@@ -56,9 +56,9 @@ def _build_lib(name, objsub, extra, force, verbose):
 
 
 def build_experiments(force=False, verbose=True):
-    """lib/libvbz_hip_x.so: the same sources with -DVBZ_EXPERIMENTS -- the timed kernel instantiations (VBZ_HIP_PHASE_TIMING) and the
-    measured-slower variants (VBZ_HIP_FUSE_SVB, VBZ_HIP_LONG_REPEATS=2|3, VBZ_HIP_ROUTING=2) for tools/ and for the tests that hold
-    them to the product's bytes.  Not linked by the plugin or the re-packer; select it with VBZ_HIP_LIB."""
+    """lib/libvbz_hip_x.so: the same sources with -DVBZ_EXPERIMENTS -- the timed kernel instantiations (VBZ_HIP_PHASE_TIMING) for
+    tools/ and the svb hand-over test aid (vbz_gpu_x_svb_handover) for tests/test_gpu_handover.py.  Not linked by the plugin or the
+    re-packer; select it with VBZ_HIP_LIB."""
     os.makedirs(LIBDIR, exist_ok=True)
     return _build_lib("libvbz_hip_x.so", "obj_x", ["-DVBZ_EXPERIMENTS"], force, verbose)
 

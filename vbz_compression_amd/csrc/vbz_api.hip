@@ -55,16 +55,14 @@ struct vbz_gpu_ctx
     DevBuf meta;      // per-read bookkeeping arrays
     DevBuf gmeta;     // ... of one launch group of a decompress call
     DevBuf route;     // per-read routing: the first group's gates, the second group's compact descriptors
-    int routing = 1;       // VBZ_HIP_ROUTING=0: by batch shape only (2: experiment, the second group is not launched)
+    bool routing = true;   // VBZ_HIP_ROUTING=0: by batch shape only
     vbz_gpu_ctx* large = nullptr;   // per-read routing: the second group's own stream and buffers (it runs beside the first group)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // A large batch on the one-workgroup path is coded as TWO HALVES on two streams (split_batch): the upper half on this child context
     vbz_gpu_ctx* half = nullptr;
-    hipEvent_t ev_hfork = nullptr, ev_hjoin = nullptr, ev_hstagger = nullptr;
+    hipEvent_t ev_hfork = nullptr, ev_hjoin = nullptr;
     DevBuf splitmeta;          // the scratch plan of the whole batch (slot offsets, capacities, gates), shared by the two halves
     uint32_t split_min = 16384;   // VBZ_HIP_SPLIT_MIN: batches of this many reads and more are split (0: never)
-    int split_stagger = 0;        // VBZ_HIP_SPLIT_STAGGER=1: the upper half starts behind the lower half's first large launch (measured: 548 GB/s
-                                  // against 565 when both halves start together -- the device interleaves the two queues by itself)
     bool last_split = false;      // vbz_gpu_decode_paths: the last decompress call ran as halves
     // Frames of OTHER writers (every vbz file in existence: the reference's libzstd frames) decode on one wavefront each behind a chain walk
     // of fixed latency, and two halves of such a call do not run beside each other (482 GB/s as one group, 420 as halves); the host
@@ -112,8 +110,7 @@ struct vbz_gpu_ctx
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
     bool zero_run_sequences = true;
-    bool fuse_svb = false;     // VBZ_HIP_FUSE_SVB=1: the frame's wavefront decodes the svb stream too (measured slower: DESIGN.md 4.4)
-    int long_repeats = 1;  // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance (experiments: 2 = probe only, 3 = second launch only)
+    bool long_repeats = true;  // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance
     int phase_timing = 0;      // VBZ_HIP_PHASE_TIMING: 1 phase counters of the entropy kernels (one launch per frame), 2 / 3 of the encoder's planning / packing launch (staged, under load)
     bool trace = false;        // VBZ_HIP_TRACE=1: synchronise after every launch group and name it on stderr (to find a faulting kernel)
     void* pinned = nullptr;
@@ -418,7 +415,6 @@ struct Preplanned
     void* scratch = nullptr;
     uint64_t* svb_off = nullptr;
     uint32_t *svb_cap = nullptr, *gate = nullptr;
-    hipEvent_t after_first = nullptr;   // recorded on the group's stream behind its first large launch (the other half may wait for it)
 };
 
 // The content checksum of the frames of an entropy stage (vbz_gpu_set_checksum), in two launches of its own around the stage, whatever
@@ -561,12 +557,10 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
             HIPCHK(c, launch_svb_encode_seg(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, seg.first, seg.max_segs, seg.val, seg.off, s),
                    "svb_encode (segmented) launch");
         else
-            HIPCHK(c, launch_svb_encode(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, half_codec(o), (matcher && c->long_repeats != 3) ? deep_d : nullptr,
+            HIPCHK(c, launch_svb_encode(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, half_codec(o), matcher ? deep_d : nullptr,
                                         pre_filled ? plan : nullptr, s),
                    "svb_encode launch");
-        if (matcher && c->long_repeats == 3) (void)hipMemsetAsync(deep_d, 0, 4ull * n, s);
     }
-    if (pre && pre->after_first) HIPCHK(c, hipEventRecord(pre->after_first, s), "event record");
     ReadBatch z = rb;
     z.src = (const uint8_t*)scratch_base;
     z.src_off = svb_off;
@@ -623,7 +617,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
         // (phase timing 2: the planning launch's counters, 3: the packing launch's; both under load, the other launches as they are)
         HIPCHK(c, launch_zstd_encode(z, key_orig, key_elem, nullptr, hdr, c->phase_timing == 3 ? nullptr : dbg,
                                      c->zero_run_sequences ? svb_cap : nullptr, c->zero_run_sequences ? c->seqtab.p : nullptr, c->trailers,
-                                     (matcher && !dbg && c->long_repeats != 2) ? deep_d : nullptr, plan, staged, pre_filled, c->phase_timing == 3 ? dbg : nullptr, s),
+                                     (matcher && !dbg) ? deep_d : nullptr, plan, staged, pre_filled, c->phase_timing == 3 ? dbg : nullptr, s),
                "zstd_encode launch");
     }
     dbg_end(c, n,
@@ -782,17 +776,6 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     z.result = svb_size;
     z.gate = gate;
     unsigned long long* dbg = segmented ? nullptr : dbg_begin(c, n);
-    // the hot path -- int16 zig-zag samples, one wavefront per frame: optionally (VBZ_HIP_FUSE_SVB=1) the wavefront decodes the
-    // svb stream it has just written while it is still in the caches, straight into the destination, and there is no
-    // svb_decode launch (measured slower than the separate launch: profiles/r03_fused_svb_decode.md; it does not verify content checksums)
-#ifdef VBZ_EXPERIMENTS
-    if (!segmented && !dbg && c->fuse_svb && o->integer_size == 2 && o->perform_delta_zig_zag && rb.sig.type == SIG_NONE && !rb.sig.norm.st) {   // (no typed store)
-        z.result = rb.result;
-        Timed t(c, "zstd_decode");  // (zstd_decode_kernel<false, true>: the frame and its svb stream)
-        HIPCHK(c, launch_zstd_decode_svb_i16zz(z, E_STREAM, c->seqdtab.p, rb.dst, rb.dst_off, rb.dst_cap, s), "zstd_decode + svb_decode launch");
-        return 0;
-    }
-#endif
     if (segmented) {  // few, large reads: frames with a span index are decoded one span per wavefront
         const uint32_t max_spans = zstd_dspan_max_spans(scratch_need, n);
         if (!max_spans) {
@@ -818,7 +801,6 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
         // decode it and then fail in the svb stage with a stream error (POD5: content beyond svb16_max(n) is the zstd stage's error)
         if (zstd_frames(c, z, pod5 ? E_ZSTD : E_STREAM, dst_bytes, dbg) != 0) return -1;
     }
-    if (pre && pre->after_first) HIPCHK(c, hipEventRecord(pre->after_first, s), "event record");
     dbg_end(c, n, "zstd_decode: parse flush seqtables chain place huftable header queue | general sequences: flush tables records literals matches", dbg);
     if (verify_checksums(c, z) != 0) return -1;
     ReadBatch d = rb;
@@ -875,7 +857,7 @@ int ensure_large(vbz_gpu_ctx* c)
             set_error(c, "could not create the context of the routed reads");
             return -1;
         }
-        c->large->routing = 0;
+        c->large->routing = false;
         c->large->split_min = 0;
     }
     c->large->trailers = c->trailers;
@@ -967,12 +949,11 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
     if (!c->half) {
         c->half = vbz_gpu_create(c->device, nullptr);
         if (!c->half || hipEventCreateWithFlags(&c->ev_hfork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_hjoin, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_hstagger, hipEventDisableTiming) != hipSuccess) {
+            hipEventCreateWithFlags(&c->ev_hjoin, hipEventDisableTiming) != hipSuccess) {
             set_error(c, "could not create the context of a batch's upper half");
             return -1;
         }
-        c->half->routing = 0;
+        c->half->routing = false;
         c->half->split_min = 0;
         c->half->segmented = 0;
     }
@@ -984,7 +965,6 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
     k->staged_encode = c->staged_encode;
     k->fast_decode = c->fast_decode;
     k->ref_chains = c->ref_chains;
-    k->fuse_svb = c->fuse_svb;
     k->profiling = c->profiling;
     k->foreign_state = c->foreign_state;
     const size_t scratch_need = (size_t)(((unsigned __int128)raw_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
@@ -1007,7 +987,6 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
     sp->hi.svb_off = svb_off + sp->h;
     sp->hi.svb_cap = svb_cap + sp->h;
     sp->hi.gate = gate + sp->h;
-    if (c->split_stagger) sp->lo.after_first = c->ev_hstagger;
     HIPCHK(c, hipEventRecord(c->ev_hfork, s), "event record");
     HIPCHK(c, hipStreamWaitEvent(k->stream, c->ev_hfork, 0), "stream wait");
     return 0;
@@ -1050,7 +1029,6 @@ int compress_split(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t src_bytes, cons
     ReadBatch lo = rb;
     lo.n_reads = sp.h;
     int rc = compress_group(c, lo, src_bytes, o, sized, false, &sp.lo);
-    if (rc == 0 && c->split_stagger && hipStreamWaitEvent(c->half->stream, c->ev_hstagger, 0) != hipSuccess) rc = -1;
     if (rc == 0) rc = compress_group(c->half, upper_half(rb, sp.h), src_bytes, o, sized, false, &sp.hi);
     if (split_join(c) != 0) rc = -1;
     return rc;
@@ -1065,7 +1043,6 @@ int decompress_split(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t dst_bytes, co
     ReadBatch lo = rb;
     lo.n_reads = sp.h;
     int rc = decompress_group(c, lo, dst_bytes, o, false, &sp.lo);
-    if (rc == 0 && c->split_stagger && hipStreamWaitEvent(c->half->stream, c->ev_hstagger, 0) != hipSuccess) rc = -1;
     if (rc == 0) rc = decompress_group(c->half, upper_half(rb, sp.h), dst_bytes, o, false, &sp.hi);
     if (split_join(c) != 0) rc = -1;
     c->last_split = rc == 0;
@@ -1168,7 +1145,7 @@ int compress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressi
     // (the second group first: its launches are short.)  Whatever fails from here on, the second stream is joined before the call
     // returns -- it may still be writing the caller's arenas -- and its error message becomes the context's
     int rc = 0;
-    if (c->routing != 2 && compress_group(c->large, r.large, ROUTE_MAX_BYTES, o, sized, true) != 0) rc = -1;
+    if (compress_group(c->large, r.large, ROUTE_MAX_BYTES, o, sized, true) != 0) rc = -1;
     if (rc == 0 && (split ? compress_split(c, small, bt->src_bytes, o, sized) : compress_group(c, small, bt->src_bytes, o, sized, false)) != 0) rc = -1;
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
     if (route_join(c, r, bt->result) != 0) rc = -1;
@@ -1320,7 +1297,7 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     ReadBatch small = rb;
     small.gate = r.gate_small;
     int rc = 0;   // (as in compress_batch_impl: the second stream is joined whatever happens)
-    if (c->routing != 2 && decompress_group(c->large, r.large, ROUTE_MAX_BYTES, o, true) != 0) rc = -1;
+    if (decompress_group(c->large, r.large, ROUTE_MAX_BYTES, o, true) != 0) rc = -1;
     if (rc == 0 && (split ? decompress_split(c, small, dst_bytes, o) : decompress_group(c, small, dst_bytes, o, false)) != 0) rc = -1;
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
     if (route_join(c, r, bt->result) != 0) rc = -1;
@@ -1369,9 +1346,9 @@ vbz_gpu_ctx* vbz_gpu_create(int device, void* stream)
     }
     vbz_gpu_ctx* c = new vbz_gpu_ctx();
     c->device = device;
-    // The knobs of the shipped library (README.md): every one selects between paths the suites run.  Known-slower variants and
-    // the timed kernel instantiations are compiled into the experiments build only (-DVBZ_EXPERIMENTS: lib/libvbz_hip_x.so,
-    // for tools/ and the tests that keep those variants honest); here their values do nothing.
+    // The knobs of the shipped library (README.md): every one selects between paths the suites run.  The timed kernel
+    // instantiations are compiled into the experiments build only (-DVBZ_EXPERIMENTS: lib/libvbz_hip_x.so, for tools/);
+    // here VBZ_HIP_PHASE_TIMING does nothing.
     if (const char* e = getenv("VBZ_HIP_TRACE")) c->trace = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_ZERO_RUN_SEQUENCES")) c->zero_run_sequences = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_LONG_REPEATS")) c->long_repeats = atoi(e) != 0;
@@ -1385,12 +1362,8 @@ vbz_gpu_ctx* vbz_gpu_create(int device, void* stream)
     if (const char* e = getenv("VBZ_HIP_CANONICAL")) c->canonical = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_CHECKSUM")) c->checksum = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_SPLIT_MIN")) c->split_min = (uint32_t)strtoul(e, nullptr, 10);   // 0: a batch is never coded as two halves
-    if (const char* e = getenv("VBZ_HIP_SPLIT_STAGGER")) c->split_stagger = atoi(e);
 #ifdef VBZ_EXPERIMENTS
     if (const char* e = getenv("VBZ_HIP_PHASE_TIMING")) c->phase_timing = atoi(e);   // timed instantiations of the entropy kernels
-    if (const char* e = getenv("VBZ_HIP_LONG_REPEATS")) c->long_repeats = atoi(e);   // 2: probe only, 3: second launch only
-    if (const char* e = getenv("VBZ_HIP_FUSE_SVB")) c->fuse_svb = atoi(e) != 0;      // svb decode on the frame's wavefront (slower)
-    if (const char* e = getenv("VBZ_HIP_ROUTING")) c->routing = atoi(e);             // 2: the second launch group is not launched
 #endif
     {
         std::vector<uint8_t> host(seq_tables_bytes());
@@ -1438,7 +1411,7 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
         if (b->p) (void)hipFree(b->p);
     if (c->large) vbz_gpu_destroy(c->large);
     if (c->half) vbz_gpu_destroy(c->half);
-    for (hipEvent_t e : { c->ev_hfork, c->ev_hjoin, c->ev_hstagger })
+    for (hipEvent_t e : { c->ev_hfork, c->ev_hjoin })
         if (e) (void)hipEventDestroy(e);
     if (c->side.fork) (void)hipEventDestroy(c->side.fork);
     if (c->side.join) (void)hipEventDestroy(c->side.join);

@@ -22,7 +22,6 @@
 // the serial statements of zstd_tables.h, which the batched decoders (zstd_decode_ref.hip, zstd_decode_fast.hip) instantiate too.
 // Algorithmic HBM bytes per svb byte: ~0.67 read + 1 written.
 #include "vbz_kernels.h"
-#include "svb_wave.h"
 #include "zstd_runs.h"
 #include "zstd_frame.h"
 #include "zstd_tables.h"
@@ -1350,22 +1349,12 @@ constexpr uint32_t DSPAN_MIN_CONTENT = 4u << 10;    // an honest index has at mo
 constexpr uint32_t DSPAN_WS_FACTOR = 3;
 // TIMED: per-phase shader-clock counters (VBZ_HIP_PHASE_TIMING); a separate instantiation, the counters cost
 // dozens of registers in the production kernel otherwise
-// FUSED: the frame's content is the svb stream of int16 zig-zag samples and b.dst its slot in the library's scratch: once the
-// frame is decoded the same wave decodes the stream (svb_wave.h) into the read's final destination (fuse.out) and
-// b.result[] gets the FINAL verdict -- the stream is read back while it is still in the caches, and no svb_decode launch
-// follows.
-struct SvbFuse
-{
-    uint8_t* out;
-    const uint64_t* out_off;
-    const uint32_t* out_size;   // exact decoded byte count of every read
-};
 // SPANS: the span-mode instantiation (dspans != nullptr; the other one carries none of its code: the ordinary decoder's register
 // allocation is not the spans' business)
-template <bool TIMED, bool FUSED, bool SPANS = false>
+template <bool TIMED, bool SPANS = false>
 __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBatch b, uint32_t toosmall_code, unsigned long long* dbg, const SeqDTables* dtabs,
                                                                       const DecSpan* dspans_, const uint32_t* dspan_count, uint32_t* dspan_status,
-                                                                      const uint32_t* only, SvbFuse fuse, RefChains chains)
+                                                                      const uint32_t* only, RefChains chains)
 {
     const DecSpan* const dspans = SPANS ? dspans_ : nullptr;
     unsigned long long tph[PHASE_SLOTS] = {};
@@ -2308,14 +2297,7 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
         }
         return;
     }
-    if (FUSED) {
-        static_assert(sizeof(DecLds) >= svbwave::LDS_TOTAL, "the wave's svb decoder works in the frame decoder's LDS");
-        __syncthreads();  // every byte of the stream is in memory (raw / RLE blocks store without a drain)
-        const uint32_t res = svbwave::svb_decode_wave_i16zz(dst, fcs, fuse.out + fuse.out_off[r], fuse.out_size[r], reinterpret_cast<uint8_t*>(&L), lane);
-        if (lane == 0) b.result[r] = res;
-    } else if (lane == 0) {
-        b.result[r] = fcs;
-    }
+    if (lane == 0) b.result[r] = fcs;
 #ifdef VBZ_SPLIT_DEBUG
     tph[2] = split_dbg[0];
     tph[3] = split_dbg[1];
@@ -2515,17 +2497,16 @@ hipError_t launch_zstd_decode(const ReadBatch& b, uint32_t toosmall_code, unsign
                               hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    const SvbFuse none = { nullptr, nullptr, nullptr };
 #ifdef VBZ_EXPERIMENTS   // the timed instantiation (phase cycle counters) is part of the experiments build only
     if (dbg) {
-        hipLaunchKernelGGL((zstd_decode_kernel<true, false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, dbg,
-                           reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, nullptr, none, RefChains());
+        hipLaunchKernelGGL((zstd_decode_kernel<true>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, dbg,
+                           reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, nullptr, RefChains());
         return hipGetLastError();
     }
 #endif
     (void)dbg;
-    hipLaunchKernelGGL((zstd_decode_kernel<false, false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, nullptr,
-                       reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, nullptr, none, RefChains());
+    hipLaunchKernelGGL((zstd_decode_kernel<false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, nullptr,
+                       reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, nullptr, RefChains());
     return hipGetLastError();
 }
 
@@ -2533,31 +2514,18 @@ hipError_t launch_zstd_decode_only(const ReadBatch& b, uint32_t toosmall_code, c
                                    unsigned long long* dbg, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    const SvbFuse none = { nullptr, nullptr, nullptr };
 #ifdef VBZ_EXPERIMENTS
     if (dbg) {
-        hipLaunchKernelGGL((zstd_decode_kernel<true, false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, dbg,
-                           reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, only, none, chains);
+        hipLaunchKernelGGL((zstd_decode_kernel<true>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, dbg,
+                           reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, only, chains);
         return hipGetLastError();
     }
 #endif
     (void)dbg;
-    hipLaunchKernelGGL((zstd_decode_kernel<false, false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, nullptr,
-                       reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, only, none, chains);
+    hipLaunchKernelGGL((zstd_decode_kernel<false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, nullptr,
+                       reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, only, chains);
     return hipGetLastError();
 }
-
-#ifdef VBZ_EXPERIMENTS   // the svb decoder on the frame's wavefront: measured slower (profiles/r03_fused_svb_decode.md), kept for tools/ only
-hipError_t launch_zstd_decode_svb_i16zz(const ReadBatch& b, uint32_t toosmall_code, const void* seq_dtables, uint8_t* out, const uint64_t* out_off,
-                                        const uint32_t* out_size, hipStream_t s)
-{
-    if (b.n_reads == 0) return hipSuccess;
-    const SvbFuse fuse = { out, out_off, out_size };
-    hipLaunchKernelGGL((zstd_decode_kernel<false, true>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, nullptr,
-                       reinterpret_cast<const SeqDTables*>(seq_dtables), nullptr, nullptr, nullptr, nullptr, fuse, RefChains());
-    return hipGetLastError();
-}
-#endif
 
 // ---- span mode (few, large reads) ------------------------------------------------------------------------------------------
 size_t zstd_dspan_desc_bytes() { return sizeof(DecSpan); }
@@ -2575,11 +2543,10 @@ hipError_t launch_zstd_decode_spans(const ReadBatch& b, uint32_t toosmall_code, 
     DecSpan* spans = reinterpret_cast<DecSpan*>(dspan_desc);
     const SeqDTables* dt = reinterpret_cast<const SeqDTables*>(seq_dtables);
     hipLaunchKernelGGL(zstd_dspan_plan_kernel, dim3(1), dim3(1024), 0, s, b, max_spans, spans, dspan_first, dspan_count, dspan_status);
-    const SvbFuse none = { nullptr, nullptr, nullptr };
-    hipLaunchKernelGGL((zstd_decode_kernel<false, false, true>), dim3(max_spans), dim3(WAVE), 0, s, b, toosmall_code, nullptr, dt, spans, dspan_count, dspan_status,
-                       nullptr, none, RefChains());
+    hipLaunchKernelGGL((zstd_decode_kernel<false, true>), dim3(max_spans), dim3(WAVE), 0, s, b, toosmall_code, nullptr, dt, spans, dspan_count, dspan_status,
+                       nullptr, RefChains());
     hipLaunchKernelGGL(zstd_dspan_finish_kernel, dim3(b.n_reads), dim3(256), 0, s, b, spans, dspan_first, max_spans, dspan_status, redo);
-    hipLaunchKernelGGL((zstd_decode_kernel<false, false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, nullptr, dt, nullptr, nullptr, nullptr, redo, none, RefChains());
+    hipLaunchKernelGGL((zstd_decode_kernel<false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, toosmall_code, nullptr, dt, nullptr, nullptr, nullptr, redo, RefChains());
     return hipGetLastError();
 }
 
