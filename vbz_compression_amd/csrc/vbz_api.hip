@@ -217,17 +217,42 @@ void drain_profile(vbz_gpu_ctx* c)
 }
 
 // debug aid: per-phase shader-clock cycles of the entropy kernels, averaged over the batch, on stderr
-unsigned long long* dbg_begin(vbz_gpu_ctx* c, uint32_t n)
+// per_role: the counters of the encoder's planning launch (VBZ_HIP_PHASE_TIMING=2), two wavefronts per read
+unsigned long long* dbg_begin(vbz_gpu_ctx* c, uint32_t n, bool per_role = false)
 {
     if (!c->phase_timing) return nullptr;
+    if (per_role) n *= 2;
     if (!ensure(c, c->dbg, (size_t)n * PHASE_SLOTS * 8)) return nullptr;
     (void)hipMemsetAsync(c->dbg.p, 0, (size_t)n * PHASE_SLOTS * 8, c->stream);
     return (unsigned long long*)c->dbg.p;
 }
 
-void dbg_end(vbz_gpu_ctx* c, uint32_t n, const char* what, unsigned long long* d)
+// VBZ_HIP_PHASE_TIMING=2: the planning launch's counters, two per read (one per role), averaged per role over the wavefronts that planned
+void dbg_end_roles(vbz_gpu_ctx* c, uint32_t n, const char* what, unsigned long long* d)
+{
+    std::vector<unsigned long long> h((size_t)n * PHASE_SLOTS);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipMemcpy(h.data(), d, (size_t)n * PHASE_SLOTS * 8, hipMemcpyDeviceToHost);
+    for (uint32_t role = 0; role < 2; ++role) {
+        double sum[PHASE_SLOTS] = {};
+        uint32_t m = 0;
+        for (uint32_t i = role; i < n; i += 2) {
+            unsigned long long t = 0;
+            for (int k = 0; k < PHASE_SLOTS; ++k) t += h[(size_t)i * PHASE_SLOTS + k];
+            if (!t) continue;
+            ++m;
+            for (int k = 0; k < PHASE_SLOTS; ++k) sum[k] += (double)h[(size_t)i * PHASE_SLOTS + k];
+        }
+        fprintf(stderr, "vbz_hip phase cycles/read (%s, role %u, n=%u):", what, role, m);
+        for (int k = 0; k < PHASE_SLOTS; ++k) fprintf(stderr, " p%d=%.0f", k, m ? sum[k] / m : 0.0);
+        fprintf(stderr, "\n");
+    }
+}
+
+void dbg_end(vbz_gpu_ctx* c, uint32_t n, const char* what, unsigned long long* d, bool per_role = false)
 {
     if (!d) return;
+    if (per_role) return dbg_end_roles(c, 2 * n, what, d);
     std::vector<unsigned long long> h((size_t)n * PHASE_SLOTS);
     (void)hipStreamSynchronize(c->stream);
     (void)hipMemcpy(h.data(), d, (size_t)n * PHASE_SLOTS * 8, hipMemcpyDeviceToHost);
@@ -512,7 +537,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
         if (checksum_content(c, rb, rb.gate) != 0) return -1;
         {
             Timed t(c, "zstd_encode");
-            HIPCHK(c, launch_zstd_encode(rb, bt->src_size, 0, nullptr, hdr, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, s), "zstd_encode launch");
+            HIPCHK(c, launch_zstd_encode(rb, bt->src_size, 0, nullptr, hdr, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, nullptr, s), "zstd_encode launch");
         }
         return checksum_frames(c, rb, rb.gate, hdr, bt->src_size, 0);
     }
@@ -532,8 +557,8 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
     a.gate = gate;
     // the per-read plans of the entropy stage (one-wavefront path, staged encoder), in which the svb encoder leaves the data bytes'
     // histogram of int16 zig-zag reads (svb_kernels.hip CNT)
-    unsigned long long* dbg = segmented ? nullptr : dbg_begin(c, n);
-    const bool staged = !segmented && c->staged_encode && (!dbg || c->phase_timing == 3) && c->zero_run_sequences;
+    unsigned long long* dbg = segmented ? nullptr : dbg_begin(c, n, c->phase_timing == 2);
+    const bool staged = !segmented && c->staged_encode && (!dbg || c->phase_timing == 2 || c->phase_timing == 3) && c->zero_run_sequences;
     const bool pod5 = pod5_codec(o);
     const bool pre_filled = staged && !pod5 && svb_encode_fills_plans((int)o->integer_size, o->perform_delta_zig_zag, half_codec(o));
     void* plan = nullptr;
@@ -615,16 +640,18 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
     {
         Timed t(c, "zstd_encode");
         // (phase timing 2: the planning launch's counters, 3: the packing launch's; both under load, the other launches as they are)
-        HIPCHK(c, launch_zstd_encode(z, key_orig, key_elem, nullptr, hdr, c->phase_timing == 3 ? nullptr : dbg,
+        const bool staged_timing = c->phase_timing == 2 || c->phase_timing == 3;
+        HIPCHK(c, launch_zstd_encode(z, key_orig, key_elem, nullptr, hdr, staged_timing ? nullptr : dbg,
                                      c->zero_run_sequences ? svb_cap : nullptr, c->zero_run_sequences ? c->seqtab.p : nullptr, c->trailers,
-                                     (matcher && !dbg) ? deep_d : nullptr, plan, staged, pre_filled, c->phase_timing == 3 ? dbg : nullptr, s),
+                                     (matcher && !dbg) ? deep_d : nullptr, plan, staged, pre_filled, c->phase_timing == 2 ? dbg : nullptr,
+                                     c->phase_timing == 3 ? dbg : nullptr, s),
                "zstd_encode launch");
     }
     dbg_end(c, n,
             c->phase_timing == 3   ? "zstd_pack: setup region lookups+scan bits quads ends+headers sequences trailer"
-            : c->phase_timing == 2 ? "zstd_encode planning launch: setup hist plan - store+sequences - | plan: sort merge lengths codes weights tree"
+            : c->phase_timing == 2 ? "zstd_plan: setup tokeniser sequences hist store rest | sort merge leaves lengths codes+weights tree"
                                    : "zstd_encode: setup hist plan size hdr encode",
-            dbg);
+            dbg, c->phase_timing == 2);
     return checksum_frames(c, z, gate, hdr, pod5 ? nullptr : bt->src_size, o->integer_size);
 }
 
@@ -1670,7 +1697,7 @@ int vbz_gpu_zstd_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const u
     DeviceGuard dg(c->device);
     if (checksum_content(c, to_rb(bt), nullptr) != 0) return -1;
     Timed t(c, "zstd_encode");
-    HIPCHK(c, launch_zstd_encode(to_rb(bt), bt->src_size, 0, key_bytes, 0, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, c->stream), "zstd_encode launch");
+    HIPCHK(c, launch_zstd_encode(to_rb(bt), bt->src_size, 0, key_bytes, 0, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, nullptr, c->stream), "zstd_encode launch");
     return checksum_frames(c, to_rb(bt), nullptr, 0, nullptr, 0);
 }
 

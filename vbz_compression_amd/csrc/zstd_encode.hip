@@ -170,23 +170,40 @@ struct EncLds
     __device__ __forceinline__ void set_code(uint32_t s, uint32_t code, uint32_t nb) { ctable[s] = make_uint2(code, nb); }
 };
 
+// What huf_build_wave keeps in LDS of the package-merge workspace (the lists themselves are in registers): the sorted leaves, their
+// symbols, and per level which items of its list are packages -- the masks take the leaves' place once the leaves are in registers.
+struct HufPmWave
+{
+    uint32_t leaf[256];
+    uint8_t sym[256];
+};
+static_assert(sizeof(HufPmWave::leaf) >= 8 * 8 * (HUF_MAX_BITS + 1), "the package masks ([level][8] x 64 bits) fit in the leaves' place");
+
 // The staged encoder's planning launch (zstd_plan_kernel) works on the same functions with LDS of its own, two wavefronts per read:
-// a region's table -- histogram, code lengths, codes, tree description
+// a region's table -- histogram, code lengths, codes, tree description.  The four sub-histograms of region_histogram share their
+// place with everything but L.hist: nothing else of the table is live while the bytes are counted.  5 KB per wavefront.
 struct TableLds
 {
     uint32_t hist[256];
-    uint32_t ctable[256];      // code | length << 16 (what the plan stores)
-    uint8_t nbBits[256];
-    uint8_t weights[260];
-    uint8_t tree[136];
-    int32_t treeSize;
-    uint32_t mode;      // 0 raw, 1 rle, 2 huffman
-    uint32_t huffLog;
-    uint32_t rankcnt[16];
     union
     {
-        HufPmWksp pm;
-        FseWeightWksp fw;
+        uint32_t sub[4 * 256];
+        struct
+        {
+            uint32_t ctable[256];      // code | length << 16 (what the plan stores)
+            uint8_t nbBits[256];
+            uint8_t weights[260];
+            uint8_t tree[136];
+            int32_t treeSize;
+            uint32_t mode;      // 0 raw, 1 rle, 2 huffman
+            uint32_t huffLog;
+            uint32_t rankcnt[16];
+            union
+            {
+                HufPmWave pm;
+                FseWeightWksp fw;
+            };
+        };
     };
     __device__ __forceinline__ void set_code(uint32_t s, uint32_t code, uint32_t nb) { ctable[s] = code | (nb << 16); }
 };
@@ -287,11 +304,19 @@ __device__ __forceinline__ uint32_t region_histogram_from_plan(LDS& L, const uin
     return n;
 }
 
+// where region_histogram counts: four sub-histograms of 256 counters
+template <class LDS>
+__device__ __forceinline__ uint32_t* hist_subs(LDS& L)
+{
+    static_assert(sizeof(L.pm) >= 4 * 256 * sizeof(uint32_t), "the sub-histograms live in the table-construction workspace");
+    return reinterpret_cast<uint32_t*>(&L.pm);
+}
+__device__ __forceinline__ uint32_t* hist_subs(TableLds& L) { return L.sub; }
+
 template <class LDS>
 __device__ __forceinline__ uint32_t region_histogram(LDS& L, const uint8_t* in, uint32_t n, int lane, bool allow_sample)
 {
-    static_assert(sizeof(HufPmWksp) >= 4 * 256 * sizeof(uint32_t), "the sub-histograms live in the table-construction workspace");
-    uint32_t* sub = reinterpret_cast<uint32_t*>(&L.pm);
+    uint32_t* sub = hist_subs(L);
     for (int i = lane; i < 4 * 256; i += WAVE) sub[i] = 0;
     wave_lds_sync();
     uint32_t* mine = sub + 256 * (lane & 3);
@@ -381,7 +406,7 @@ __device__ __forceinline__ uint32_t sorted_count(const uint32_t* arr, uint32_t v
 template <class LDS>
 __device__ __forceinline__ uint32_t huf_build_wave(LDS& L, uint32_t maxSym, uint32_t maxNbBits, int lane, unsigned long long* tsub = nullptr, unsigned long long* tl = nullptr)
 {
-    HufPmWksp& K = L.pm;
+    auto& K = L.pm;   // (HufPmWksp or HufPmWave: leaf[] and sym[] are all this function uses)
     // --- sort the present symbols by (count, 255 - symbol), ascending: bitonic network over 256 keys, element e = 4*lane + j
     uint32_t key[4];
     {
@@ -393,7 +418,6 @@ __device__ __forceinline__ uint32_t huf_build_wave(LDS& L, uint32_t maxSym, uint
             key[j] = (sy <= maxSym && c[j]) ? ((c[j] << 8) | (255u - sy)) : 0xFFFFFFFFu;
         }
     }
-    for (int i = lane; i < (HUF_MAX_BITS + 1) * 16; i += WAVE) (&K.isPkg[0][0])[i] = 0;
 #pragma unroll
     for (int k = 2; k <= 256; k <<= 1) {
 #pragma unroll
@@ -472,8 +496,8 @@ __device__ __forceinline__ uint32_t huf_build_wave(LDS& L, uint32_t maxSym, uint
         const uint32_t t = 4u * (uint32_t)lane + (uint32_t)q;
         pk4[q] = t < m ? ((((lk[2 * q] >> 1) + (lk[2 * q + 1] >> 1)) << 1) | 1u) : PM_INF;
     }
-    wave_lds_sync();   // (the leaves have been read: the masks below reuse the workspace's list area)
-    uint64_t* const masks = reinterpret_cast<uint64_t*>(K.merged);   // [level][8]
+    wave_lds_sync();   // (the leaves have been read: the masks below take their place)
+    uint64_t* const masks = reinterpret_cast<uint64_t*>(K.leaf);   // [level][8]
     uint32_t levSame = maxNbBits;   // levels above this one equal it
     for (uint32_t lev = 2; lev <= maxNbBits; ++lev) {
         const bool last = lev == maxNbBits;
@@ -864,14 +888,22 @@ __device__ void tokenise_runs(uint8_t* k, uint32_t K, uint2* rec, uint32_t& Lit,
     uint32_t carry60 = 0, carry61 = 0;  // masks of the 32 positions in front of the payload
     uint32_t carryw = 0;                // the dword that ends in front of the payload (its top byte precedes position pb)
     const uint64_t below = (1ull << lane) - 1ull;
+    // A trip's 16 bytes per lane are requested one trip ahead, in front of the trip before's stores: the compaction only moves bytes DOWN
+    // (trip t stores below pb + TOK_PAYLOAD, where trip t + 1's lanes begin to read), so the request may overtake them, and the load's
+    // latency hides behind a trip of work instead of standing at the head of every trip.
+    auto request = [&](uint32_t pb_) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        const int64_t lo_ = (int64_t)pb_ + 16 * ((int64_t)lane - 2);
+        if (lane >= 2 && lo_ < (int64_t)K) __builtin_memcpy(&v, k + lo_, 16);  // the slot has 16+ bytes of slack behind the stream
+        return v;
+    };
+    uint4 next = request(0);
     for (uint32_t pb = 0; pb < K; pb += TOK_PAYLOAD) {
         const int64_t lo = (int64_t)pb + 16 * ((int64_t)lane - 2);
-        uint32_t w[4] = { 0, 0, 0, 0 };
+        uint32_t w[4] = { next.x, next.y, next.z, next.w };
+        if (pb + TOK_PAYLOAD < K) next = request(pb + TOK_PAYLOAD);
         uint32_t zm = 0, valid = 0;
         if (lane >= 2 && lo < (int64_t)K) {
-            uint4 v;
-            __builtin_memcpy(&v, k + lo, 16);  // the slot has 16+ bytes of slack behind the stream
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
             const uint32_t nvalid = (K - (uint32_t)lo) >= 16 ? 16u : (K - (uint32_t)lo);
             valid = nvalid >= 16 ? 0xFFFFu : ((1u << nvalid) - 1u);
         }
@@ -2152,7 +2184,7 @@ __global__ __launch_bounds__(WAVE, VBZ_ENC_WAVES) void zstd_encode_kernel(ReadBa
 // ---- the planning launches of the staged encoder ---------------------------------------------------------------------------------
 // Round 4 planned a read (tokeniser, two histograms, two table constructions, the sequences section) in one launch of the big kernel
 // above: 128 registers and 10 KB of LDS per wavefront, 16 wavefronts per CU (profiles/r04_experiments.md: 505 k cycles per frame).  Now
-// every read is planned by TWO wavefronts of 8 KB of LDS and 71 registers each (zstd_plan_kernel below: 20 per CU), the data bytes'
+// every read is planned by TWO wavefronts of 5 KB of LDS and 53 registers each (zstd_plan_kernel below: 28 per CU; 20 at 7.9 KB), the data bytes'
 // histogram comes from the svb encoder (svb_kernels.hip CNT), and zstd_pack_kernel packs the reads whose plans are complete; everything
 // else stays in redo[] for the kernel above.  What round 5 measured on the way (profiles/r05_experiments.md): the launch is bound by
 // instruction issue (VALU 65 % busy, LDS 46 % with half of it bank conflicts), not by latency alone -- each phase as a launch of its
@@ -2160,7 +2192,7 @@ __global__ __launch_bounds__(WAVE, VBZ_ENC_WAVES) void zstd_encode_kernel(ReadBa
 // wavefronts of different phases sharing a CU is what pays.
 // Byte for byte the frames the one-launch form writes (tests/test_gpu_soak_slice.py holds the two against each other).
 #ifndef VBZ_TABLE_WAVES
-#define VBZ_TABLE_WAVES 5
+#define VBZ_TABLE_WAVES 7
 #endif
 
 // per read: block size target, the control-byte region (0: none)
@@ -2200,14 +2232,22 @@ struct PlanLds
     };
 };
 
+// TIMED (VBZ_HIP_PHASE_TIMING=2, a separate instantiation): shader-clock counters per read and role (dbg[(2 * read + role) * PHASE_SLOTS + k]),
+// under load -- 0 set-up, 1 the tokeniser, 2 the sequences section, 3 the histogram, 4 the plan's store, 5 the rest (waits in front of the
+// flags); of region_plan: 6 its set-up and the sort, 7 package-merge, 8 which leaves each level takes, 9 code lengths, 10 codes and
+// weights, 11 the tree description.  A read that leaves the launch early writes nothing.
+#define PT(k) do { if (TIMED) { const unsigned long long tn_ = __builtin_readcyclecounter(); tph[k] += tn_ - tlast; tlast = tn_; } } while (0)
+
 // the table of one region into the read's plan; returns whether the region is of the ordinary kind (Huffman coded, one pass of streams)
+template <bool TIMED>
 __device__ __forceinline__ bool plan_region_table(TableLds& L, EncPlan* FP, uint32_t region, const uint8_t* rin, uint32_t S, uint32_t nblk, bool seqmode,
-                                                  uint32_t nrec, bool from_plan, int lane)
+                                                  uint32_t nrec, bool from_plan, int lane, unsigned long long* tph, unsigned long long& tlast)
 {
     uint32_t Sh;
     if (from_plan) Sh = region_histogram_from_plan(L, rin, S, lane, true, FP->reg[1].ctable, FP->hist_mode == 2u ? FP->histB : nullptr);
     else Sh = region_histogram(L, rin, S, lane, !seqmode);
-    region_plan(L, S, Sh, nblk, lane);
+    PT(3);
+    region_plan(L, S, Sh, nblk, lane, TIMED ? tph : nullptr, &tlast);
     wave_lds_sync();
     // a sample that says "does not pay" is not believed (the one-launch kernel counts again, exactly); raw / RLE regions and more
     // than 16 blocks are its business too
@@ -2225,16 +2265,25 @@ __device__ __forceinline__ bool plan_region_table(TableLds& L, EncPlan* FP, uint
         P->treeSize = (uint32_t)L.treeSize;
         P->huffLog = L.huffLog;
     }
+    PT(4);
     return nblk <= (uint32_t)MAXBLK;
 }
 
+template <bool TIMED>
 __global__ __launch_bounds__(WAVE, VBZ_TABLE_WAVES) void zstd_plan_kernel(ReadBatch b, const uint32_t* orig_size, uint32_t key_elem, const uint32_t* key_bytes,
                                                                           uint32_t hdr, const uint32_t* src_cap, const SeqCTables* seqtab, uint32_t* deep_d,
-                                                                          EncPlan* plans, uint32_t* pstate, uint32_t pre_filled)
+                                                                          EncPlan* plans, uint32_t* pstate, uint32_t pre_filled, unsigned long long* dbg)
 {
     __shared__ __attribute__((aligned(16))) PlanLds LL;
     const int lane = threadIdx.x;
     const uint32_t r = blockIdx.x >> 1, role = blockIdx.x & 1u;
+    unsigned long long tph[TIMED ? PHASE_SLOTS : 1] = {};
+    unsigned long long tlast = TIMED ? __builtin_readcyclecounter() : 0ull;
+    auto timed_out = [&]() {
+        PT(5);
+        if (TIMED && lane == 0)
+            for (int k = 0; k < PHASE_SLOTS; ++k) dbg[(size_t)blockIdx.x * PHASE_SLOTS + k] = tph[k];
+    };
     EncPlan* FP = &plans[r];
     if (role == 0 && lane == 0) {
         FP->tok_done = 0;
@@ -2260,9 +2309,11 @@ __global__ __launch_bounds__(WAVE, VBZ_TABLE_WAVES) void zstd_plan_kernel(ReadBa
             Td = Td < MIN_BLOCK ? MIN_BLOCK : (Td > HUF_BLOCK_MAX ? HUF_BLOCK_MAX : Td);
             nblk = (S + Td - 1) / Td;
         }
-        const bool ok = plan_region_table(LL.tb, FP, 1, in + K, S, nblk, false, 0, pre_filled && FP->hist_mode != 0, lane);
+        PT(0);
+        const bool ok = plan_region_table<TIMED>(LL.tb, FP, 1, in + K, S, nblk, false, 0, pre_filled && FP->hist_mode != 0, lane, tph, tlast);
         __syncthreads();   // the plan is in memory before the bit that says so
         if (ok && lane == 0) atomicOr(&pstate[r], PLAN_REG1);
+        timed_out();
         return;
     }
     const uint32_t cap = b.dst_cap[r];
@@ -2295,8 +2346,10 @@ __global__ __launch_bounds__(WAVE, VBZ_TABLE_WAVES) void zstd_plan_kernel(ReadBa
         const uint64_t need = (uint64_t)N + 16 + 8ull * recs_all;
         if (need <= slot) {
             uint8_t* ws = const_cast<uint8_t*>(in) + ((slot - 8u * recs_all) & ~7u);
+            PT(0);
             tokenise_runs<false>(const_cast<uint8_t*>(in), S0, reinterpret_cast<uint2*>(ws), Lit, nrec, nullptr, lane);
             __syncthreads();  // the compacted literals and the records are re-read below (vmcnt drain)
+            PT(1);
             rec = reinterpret_cast<const uint2*>(ws);
             if (lane == 0) {
                 FP->tok_nrec = nrec;
@@ -2329,13 +2382,17 @@ __global__ __launch_bounds__(WAVE, VBZ_TABLE_WAVES) void zstd_plan_kernel(ReadBa
             FP->cpSpacing = L.cpSpacing;
         }
         wave_lds_sync();   // (the table workspace below shares this LDS)
+        PT(2);
     }
     const uint32_t S = nrec ? Lit : S0;
     const uint32_t nblk = nrec ? 1u : (S + T - 1) / T;
-    const bool ok = plan_region_table(LL.tb, FP, 0, in, S, nblk, nrec != 0, nrec, false, lane);
+    PT(0);
+    const bool ok = plan_region_table<TIMED>(LL.tb, FP, 0, in, S, nblk, nrec != 0, nrec, false, lane, tph, tlast);
     __syncthreads();
     if (ok && lane == 0) atomicOr(&pstate[r], PLAN_OPEN | PLAN_REG0 | (K == 0 ? PLAN_REG1 : 0u));
+    timed_out();
 }
+#undef PT
 
 // ---- the packing launch of the staged encoder ---------------------------------------------------------------------------------
 // What zstd_encode_kernel does behind its table constructions, for the reads whose plans the launches above have completed: frame
@@ -3120,7 +3177,8 @@ __global__ __launch_bounds__(256) void period_probe_kernel(ReadBatch b, const ui
 
 hipError_t launch_zstd_encode(const ReadBatch& b, const uint32_t* orig_size, uint32_t key_elem, const uint32_t* key_bytes,
                               uint32_t hdr, unsigned long long* dbg, const uint32_t* src_cap, const void* seq_tables, bool trailers,
-                              uint32_t* deep_d, void* plan_meta, bool staged, bool pre_filled, unsigned long long* pack_dbg, hipStream_t s)
+                              uint32_t* deep_d, void* plan_meta, bool staged, bool pre_filled, unsigned long long* plan_dbg, unsigned long long* pack_dbg,
+                              hipStream_t s)
 {
     if (!plan_meta) staged = pre_filled = false;
     const uint32_t tr = (trailers ? ENC_TRAILERS : 0u) | (pre_filled ? ENC_PRE_FILLED : 0u);
@@ -3134,6 +3192,7 @@ hipError_t launch_zstd_encode(const ReadBatch& b, const uint32_t* orig_size, uin
     }
 #else
     dbg = nullptr;
+    plan_dbg = nullptr;
     pack_dbg = nullptr;
 #endif
     EncPlan* plans = reinterpret_cast<EncPlan*>(plan_meta);
@@ -3142,8 +3201,14 @@ hipError_t launch_zstd_encode(const ReadBatch& b, const uint32_t* orig_size, uin
         // the ordinary read in stages (tokeniser + sequences section, tables per region, packing); whatever they leave in redo[] in the
         // one-launch form behind them
         (void)hipMemsetAsync(redo, 0, 4ull * b.n_reads, s);   // pstate[]
-        hipLaunchKernelGGL(zstd_plan_kernel, dim3(2 * b.n_reads), dim3(WAVE), 0, s, b, orig_size, key_elem, key_bytes, hdr, src_cap, st, deep_d, plans, redo,
-                           pre_filled ? 1u : 0u);
+#ifdef VBZ_EXPERIMENTS
+        if (plan_dbg)   // VBZ_HIP_PHASE_TIMING=2: the planning launch with its phase counters
+            hipLaunchKernelGGL(zstd_plan_kernel<true>, dim3(2 * b.n_reads), dim3(WAVE), 0, s, b, orig_size, key_elem, key_bytes, hdr, src_cap, st, deep_d, plans,
+                               redo, pre_filled ? 1u : 0u, plan_dbg);
+        else
+#endif
+        hipLaunchKernelGGL(zstd_plan_kernel<false>, dim3(2 * b.n_reads), dim3(WAVE), 0, s, b, orig_size, key_elem, key_bytes, hdr, src_cap, st, deep_d, plans,
+                           redo, pre_filled ? 1u : 0u, (unsigned long long*)nullptr);
 #ifdef VBZ_EXPERIMENTS
         if (pack_dbg)   // VBZ_HIP_PHASE_TIMING=3: the packing launch with its phase counters
             hipLaunchKernelGGL(zstd_pack_kernel<true>, dim3(b.n_reads), dim3(WAVE), 0, s, b, orig_size, key_elem, key_bytes, hdr, tr, plans, redo, pack_dbg);
