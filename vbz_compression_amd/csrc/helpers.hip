@@ -464,18 +464,18 @@ hipError_t launch_seg_plan(uint32_t n, const uint32_t* size, uint32_t unit_bytes
     return hipGetLastError();
 }
 
-hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint32_t min_bytes, uint32_t max_reads, uint64_t max_bytes, uint32_t* gate_small,
-                              uint64_t* l_src_off, uint32_t* l_src_size, uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map,
-                              float2* l_cal, uint64_t* l_row, uint32_t* l_count, uint32_t* cand, hipStream_t s)
+hipError_t launch_route_reads(const ReadBatch& b, const RouteArgs& a, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
+    const RoutedTable& l = a.large;
+    uint32_t* const cand = a.cand;
     uint32_t* cand_count = cand + ROUTE_CAND_MAX;
     hipError_t e = hipMemsetAsync(cand_count, 0, 4, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(route_flag_kernel, dim3((b.n_reads + 255) / 256), dim3(256), 0, s, b, raw_size, min_bytes, gate_small, cand, cand_count);
-    hipLaunchKernelGGL(route_pick_kernel, dim3(1), dim3(1024), 0, s, b, raw_size, max_reads, max_bytes, gate_small, cand, cand_count, l_src_off, l_src_size,
-                       l_dst_off, l_dst_cap, l_gate, l_map, l_cal, l_count);
-    if (b.sig.row) hipLaunchKernelGGL(route_rows_kernel, dim3(1), dim3(64), 0, s, b.sig.row, l_map, l_count, max_reads, l_row);
+    hipLaunchKernelGGL(route_flag_kernel, dim3((b.n_reads + 255) / 256), dim3(256), 0, s, b, a.raw_size, a.min_bytes, a.gate_small, cand, cand_count);
+    hipLaunchKernelGGL(route_pick_kernel, dim3(1), dim3(1024), 0, s, b, a.raw_size, a.max_reads, a.max_bytes, a.gate_small, cand, cand_count, l.src_off, l.src_size,
+                       l.dst_off, l.dst_cap, l.gate, l.map, l.cal, l.count);
+    if (b.sig.row) hipLaunchKernelGGL(route_rows_kernel, dim3(1), dim3(64), 0, s, b.sig.row, l.map, l.count, a.max_reads, l.row);
     return hipGetLastError();
 }
 

@@ -17,6 +17,8 @@
 // Algorithmic HBM bytes per int16 sample: encode 2 read + ~1.26 written; decode the reverse.
 #include "vbz_kernels.h"
 
+#include <type_traits>
+
 namespace vbzhip {
 
 namespace {
@@ -2395,19 +2397,63 @@ hipError_t launch1(K kernel, const ReadBatch& b, hipStream_t s)
     return hipGetLastError();
 }
 
-// ---- the svb decoder's launches with the store OUT (DecStore; the typed stores: int16 samples only) -------------------------------------
-// b.sig's store: OUT = b.sig.type, | SIG_CHUNK with chunk rows
-uint32_t svb_decode_out(const ReadBatch& b) { return b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u); }
+// ---- the launchers' two dispatches: the element kind and the decoder's store --------------------------------------------------------
+template <int V> using Int = std::integral_constant<int, V>;
+template <bool V> using Bool = std::integral_constant<bool, V>;
 
+// (integer_size, zigzag) -> f(ELEM, ZZ, I16ZZ) as compile-time tags; SMALL: sizes 1 and 4 exist (the typed and chunk stores: int16 only)
+template <bool SMALL = true, class F>
+hipError_t svb_dispatch_elem(int integer_size, bool zigzag, F&& f)
+{
+    if (integer_size == 2) return zigzag ? f(Int<2>{}, Bool<true>{}, Bool<true>{}) : f(Int<2>{}, Bool<false>{}, Bool<false>{});
+    if constexpr (SMALL) {
+        if (integer_size == 4) return zigzag ? f(Int<4>{}, Bool<true>{}, Bool<false>{}) : f(Int<4>{}, Bool<false>{}, Bool<false>{});
+        if (integer_size == 1) return zigzag ? f(Int<1>{}, Bool<true>{}, Bool<false>{}) : f(Int<1>{}, Bool<false>{}, Bool<false>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// b.sig's store -> f(OUT): OUT = b.sig.type, | SIG_CHUNK with chunk rows (DecStore)
+template <class F>
+hipError_t svb_dispatch_store(const ReadBatch& b, F&& f)
+{
+    switch (b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u)) {
+    case SIG_NONE: return f(Int<SIG_NONE>{});
+    case SIG_F32: return f(Int<SIG_F32>{});
+    case SIG_F16: return f(Int<SIG_F16>{});
+    case SIG_BF16: return f(Int<SIG_BF16>{});
+    case SIG_F32 | SIG_CHUNK: return f(Int<SIG_F32 | SIG_CHUNK>{});
+    case SIG_F16 | SIG_CHUNK: return f(Int<SIG_F16 | SIG_CHUNK>{});
+    case SIG_BF16 | SIG_CHUNK: return f(Int<SIG_BF16 | SIG_CHUNK>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// the one-workgroup decoder with the store OUT
 template <int OUT>
 hipError_t svb_decode_launch(const ReadBatch& b, int integer_size, bool zigzag, hipStream_t s)
 {
-    if (integer_size == 2) return zigzag ? launch1(svb_decode_kernel<2, true, true, OUT>, b, s) : launch1(svb_decode_kernel<2, false, false, OUT>, b, s);
-    if constexpr (OUT == SIG_NONE) {
-        if (integer_size == 4) return zigzag ? launch1(svb_decode_kernel<4, true, false>, b, s) : launch1(svb_decode_kernel<4, false, false>, b, s);
-        if (integer_size == 1) return zigzag ? launch1(svb_decode_kernel<1, true, false>, b, s) : launch1(svb_decode_kernel<1, false, false>, b, s);
-    }
-    return hipErrorInvalidValue;
+    return svb_dispatch_elem<OUT == SIG_NONE>(integer_size, zigzag, [&](auto e, auto z, auto i) {
+        return launch1(svb_decode_kernel<e(), z(), i(), OUT>, b, s);
+    });
+}
+
+// The pre-passes of a normalising decode (b.sig.norm.st; int16 samples only), in front of the store: init(), `lead` (launches the counting
+// passes need behind the init: the segmented decoder's position passes), then norm_passes() x count(), every pass ending in its select.
+// *store = false: b.sig.type == SIG_NONE, the statistics are all that runs.  Without b.sig.norm.st: lead() alone.
+// slab: b.sig.norm.slab must be set (the segments add their counts there) or must not be (one workgroup per read counts in LDS).
+template <class Init, class Lead, class Count>
+hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, Init init, Lead lead, Count count, bool* store)
+{
+    *store = true;
+    if (!b.sig.norm.st) return lead();
+    if (integer_size != 2 || slab != (b.sig.norm.slab != nullptr)) return hipErrorInvalidValue;
+    *store = b.sig.type != SIG_NONE && b.n_reads != 0;
+    if (b.n_reads == 0) return hipSuccess;
+    hipError_t e = init();
+    if (e == hipSuccess) e = lead();
+    for (uint32_t p = 0; e == hipSuccess && p < norm_passes(b.sig.norm.method); ++p) e = count();
+    return e;
 }
 
 // the segmented decode: MODE 1, then (SELF) MODE 2 and MODE 0, or the verdict scan, MODE 2 and its scan, and MODE 0; only MODE 0 stores
@@ -2417,52 +2463,41 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
 {
     const dim3 segs(max_segs), reads(b.n_reads), t(WG);
     const bool self = max_segs <= seg_self_max();
-    hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 1>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    if (self) {
-        if (Z) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    } else {
-        hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, true, DecStore<E, OUT>::BYTES>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-        if (Z) {
-            hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-            hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, false>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-        }
-    }
-    if constexpr (E == 2) {
-        if (b.sig.norm.st) {   // the counting passes at the storing pass's positions, each behind a select launch
-            for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p) {
-                if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, SIG_COUNT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-                else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, SIG_COUNT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+    auto mode0 = [&](auto o) {
+        if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+        return hipGetLastError();
+    };
+    bool store;
+    const hipError_t e = norm_prepasses(
+        b, E, true,
+        [&] {
+            (void)hipMemsetAsync(b.sig.norm.slab, 0, 4ull * NORM_SLAB * b.n_reads, s);
+            return launch_norm_init(b, Z, s);
+        },
+        [&] {
+            hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 1>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+            if (self) {
+                if (Z) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+            } else {
+                hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, true, DecStore<E, OUT>::BYTES>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+                if (Z) {
+                    hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 2>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+                    hipLaunchKernelGGL((svb_seg_decode_scan_kernel<E, I, false>), reads, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
+                }
+            }
+            return hipGetLastError();
+        },
+        [&] {   // a counting pass at the storing pass's positions, behind it a select launch
+            if constexpr (E == 2) {
+                const hipError_t ec = mode0(Int<SIG_COUNT>{});
+                if (ec != hipSuccess) return ec;
                 hipLaunchKernelGGL(norm_select_kernel, reads, t, 0, s, b);
             }
-            if (b.sig.type == SIG_NONE) return hipGetLastError();   // (the statistics only)
-        }
-    }
-    if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, OUT>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
-    return hipGetLastError();
-}
-
-template <int OUT>
-hipError_t svb_decode_seg_launch(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val,
-                                 uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s)
-{
-#define X(E, Z, I) return svb_decode_seg_sequence<E, Z, I, OUT>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
-    if (integer_size == 2) {
-        if (zigzag) X(2, true, true);
-        X(2, false, false);
-    }
-    if constexpr (OUT == SIG_NONE) {
-        if (integer_size == 4) {
-            if (zigzag) X(4, true, false);
-            X(4, false, false);
-        }
-        if (integer_size == 1) {
-            if (zigzag) X(1, true, false);
-            X(1, false, false);
-        }
-    }
-#undef X
-    return hipErrorInvalidValue;
+            return hipGetLastError();
+        },
+        &store);
+    return e == hipSuccess && store ? mode0(Int<OUT>{}) : e;   // (no store: the statistics only)
 }
 
 }  // namespace
@@ -2490,18 +2525,11 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
         return hipGetLastError();
     }
     pre = nullptr;
-#define X(E, Z, I)                                                                                                         \
-    if (period_hint) hipLaunchKernelGGL((svb_encode_kernel<E, Z, I, true>), g, t, 0, s, b, hdr, sc, period_hint, pre);     \
-    else hipLaunchKernelGGL((svb_encode_kernel<E, Z, I, false>), g, t, 0, s, b, hdr, sc, period_hint, pre)
-    if (integer_size == 2 && zigzag) { X(2, true, true); }
-    else if (integer_size == 2) { X(2, false, false); }
-    else if (integer_size == 4 && zigzag) { X(4, true, false); }
-    else if (integer_size == 4) { X(4, false, false); }
-    else if (integer_size == 1 && zigzag) { X(1, true, false); }
-    else if (integer_size == 1) { X(1, false, false); }
-    else return hipErrorInvalidValue;
-#undef X
-    return hipGetLastError();
+    return svb_dispatch_elem(integer_size, zigzag, [&](auto e, auto z, auto i) {
+        if (period_hint) hipLaunchKernelGGL((svb_encode_kernel<e(), z(), i(), true>), g, t, 0, s, b, hdr, sc, period_hint, pre);
+        else hipLaunchKernelGGL((svb_encode_kernel<e(), z(), i(), false>), g, t, 0, s, b, hdr, sc, period_hint, pre);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s)
@@ -2510,23 +2538,12 @@ hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, 
         if (integer_size != 1 || b.sig.type != SIG_NONE) return hipErrorInvalidValue;
         return zigzag ? launch1(svb_half_decode_kernel<true>, b, s) : launch1(svb_half_decode_kernel<false>, b, s);
     }
-    if (b.sig.norm.st) {   // the counting passes (each selects at its end), then the store -- none for the statistics alone
-        if (integer_size != 2) return hipErrorInvalidValue;
-        if (b.n_reads == 0) return hipSuccess;
-        hipError_t e = launch_norm_init(b, zigzag, s);
-        for (uint32_t p = 0; e == hipSuccess && p < norm_passes(b.sig.norm.method); ++p) e = svb_decode_launch<SIG_COUNT>(b, 2, zigzag, s);
-        if (e != hipSuccess || b.sig.type == SIG_NONE) return e;
-    }
-    switch (svb_decode_out(b)) {
-    case SIG_NONE: return svb_decode_launch<SIG_NONE>(b, integer_size, zigzag, s);
-    case SIG_F32: return svb_decode_launch<SIG_F32>(b, integer_size, zigzag, s);
-    case SIG_F16: return svb_decode_launch<SIG_F16>(b, integer_size, zigzag, s);
-    case SIG_BF16: return svb_decode_launch<SIG_BF16>(b, integer_size, zigzag, s);
-    case SIG_F32 | SIG_CHUNK: return svb_decode_launch<SIG_F32 | SIG_CHUNK>(b, integer_size, zigzag, s);
-    case SIG_F16 | SIG_CHUNK: return svb_decode_launch<SIG_F16 | SIG_CHUNK>(b, integer_size, zigzag, s);
-    case SIG_BF16 | SIG_CHUNK: return svb_decode_launch<SIG_BF16 | SIG_CHUNK>(b, integer_size, zigzag, s);
-    default: return hipErrorInvalidValue;
-    }
+    bool store;   // the counting passes (each selects at its end), then the store -- none for the statistics alone
+    const hipError_t e = norm_prepasses(
+        b, integer_size, false, [&] { return launch_norm_init(b, zigzag, s); }, [] { return hipSuccess; },
+        [&] { return svb_decode_launch<SIG_COUNT>(b, 2, zigzag, s); }, &store);
+    if (e != hipSuccess || !store) return e;
+    return svb_dispatch_store(b, [&](auto out) { return svb_decode_launch<out()>(b, integer_size, zigzag, s); });
 }
 
 // ---- svb16 (POD5) ---------------------------------------------------------------------------------------------------
@@ -2540,22 +2557,16 @@ hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStr
 hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    if (b.sig.norm.st) {   // the counting passes (each selects at its end: one workgroup per read), then the store
-        if (b.sig.norm.slab) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(norm_init16_kernel, dim3((b.n_reads + WG - 1) / WG), dim3(WG), 0, s, b);
-        for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p) hipLaunchKernelGGL(svb16_decode_kernel<SIG_COUNT>, dim3(b.n_reads), dim3(WG), 0, s, b);
-        if (b.sig.type == SIG_NONE) return hipGetLastError();
-    }
-    switch (svb_decode_out(b)) {
-    case SIG_NONE: return launch1(svb16_decode_kernel<SIG_NONE>, b, s);
-    case SIG_F32: return launch1(svb16_decode_kernel<SIG_F32>, b, s);
-    case SIG_F16: return launch1(svb16_decode_kernel<SIG_F16>, b, s);
-    case SIG_BF16: return launch1(svb16_decode_kernel<SIG_BF16>, b, s);
-    case SIG_F32 | SIG_CHUNK: return launch1(svb16_decode_kernel<SIG_F32 | SIG_CHUNK>, b, s);
-    case SIG_F16 | SIG_CHUNK: return launch1(svb16_decode_kernel<SIG_F16 | SIG_CHUNK>, b, s);
-    case SIG_BF16 | SIG_CHUNK: return launch1(svb16_decode_kernel<SIG_BF16 | SIG_CHUNK>, b, s);
-    default: return hipErrorInvalidValue;
-    }
+    bool store;   // the counting passes (each selects at its end: one workgroup per read), then the store
+    const hipError_t e = norm_prepasses(
+        b, 2, false,
+        [&] {
+            hipLaunchKernelGGL(norm_init16_kernel, dim3((b.n_reads + WG - 1) / WG), dim3(WG), 0, s, b);
+            return hipGetLastError();
+        },
+        [] { return hipSuccess; }, [&] { return launch1(svb16_decode_kernel<SIG_COUNT>, b, s); }, &store);
+    if (e != hipSuccess || !store) return e;
+    return svb_dispatch_store(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); });
 }
 
 hipError_t launch_svb16_key_raw(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw, hipStream_t s)
@@ -2571,58 +2582,36 @@ uint32_t svb_seg_unit_bytes(int integer_size)
     return (uint32_t)(WG * (integer_size == 4 ? 4 : 8) * SEG_TILES * integer_size);  // raw bytes of one segment
 }
 
-#define VBZ_SVB_DISPATCH(X)                                      \
-    do {                                                         \
-        if (integer_size == 2 && zigzag) { X(2, true, true); }   \
-        else if (integer_size == 2) { X(2, false, false); }      \
-        else if (integer_size == 4 && zigzag) { X(4, true, false); } \
-        else if (integer_size == 4) { X(4, false, false); }      \
-        else if (integer_size == 1 && zigzag) { X(1, true, false); } \
-        else if (integer_size == 1) { X(1, false, false); }      \
-        else return hipErrorInvalidValue;                        \
-    } while (0)
-
 hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigzag, uint32_t hdr, bool strict_cap, const uint32_t* seg_first,
                                  uint32_t max_segs, uint32_t* seg_bytes, uint64_t* seg_off, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
     const uint32_t sc = strict_cap ? 1u : 0u;
     const bool self = max_segs <= seg_self_max();
-#define X(E, Z, I)                                                                                                                   \
-    hipLaunchKernelGGL((svb_seg_encode_kernel<E, Z, I, true>), dim3(max_segs), dim3(WG), 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off);  \
-    if (self) {                                                                                                                      \
-        hipLaunchKernelGGL((svb_seg_encode_kernel<E, Z, I, false, true>), dim3(max_segs), dim3(WG), 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off); \
-    } else {                                                                                                                         \
-        hipLaunchKernelGGL((svb_seg_encode_scan_kernel<E, I>), dim3(b.n_reads), dim3(WG), 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off);    \
-        hipLaunchKernelGGL((svb_seg_encode_kernel<E, Z, I, false>), dim3(max_segs), dim3(WG), 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off); \
-    }
-    VBZ_SVB_DISPATCH(X);
-#undef X
-    return hipGetLastError();
+    const dim3 segs(max_segs), reads(b.n_reads), t(WG);
+    return svb_dispatch_elem(integer_size, zigzag, [&](auto e, auto z, auto i) {
+        constexpr int E = e();
+        constexpr bool Z = z(), I = i();
+        hipLaunchKernelGGL((svb_seg_encode_kernel<E, Z, I, true>), segs, t, 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off);
+        if (self) {
+            hipLaunchKernelGGL((svb_seg_encode_kernel<E, Z, I, false, true>), segs, t, 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off);
+        } else {
+            hipLaunchKernelGGL((svb_seg_encode_scan_kernel<E, I>), reads, t, 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off);
+            hipLaunchKernelGGL((svb_seg_encode_kernel<E, Z, I, false>), segs, t, 0, s, b, hdr, sc, seg_first, seg_bytes, seg_off);
+        }
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
                                  uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    if (b.sig.norm.st) {
-        if (integer_size != 2 || !b.sig.norm.slab) return hipErrorInvalidValue;
-        (void)hipMemsetAsync(b.sig.norm.slab, 0, 4ull * NORM_SLAB * b.n_reads, s);
-        const hipError_t e = launch_norm_init(b, zigzag, s);
-        if (e != hipSuccess) return e;
-    }
-#define X(O) return svb_decode_seg_launch<O>(b, integer_size, zigzag, seg_first, max_segs, seg_val, seg_pos, seg_run, s)
-    switch (svb_decode_out(b)) {
-    case SIG_NONE: X(SIG_NONE);
-    case SIG_F32: X(SIG_F32);
-    case SIG_F16: X(SIG_F16);
-    case SIG_BF16: X(SIG_BF16);
-    case SIG_F32 | SIG_CHUNK: X(SIG_F32 | SIG_CHUNK);
-    case SIG_F16 | SIG_CHUNK: X(SIG_F16 | SIG_CHUNK);
-    case SIG_BF16 | SIG_CHUNK: X(SIG_BF16 | SIG_CHUNK);
-    default: return hipErrorInvalidValue;
-    }
-#undef X
+    return svb_dispatch_store(b, [&](auto out) {
+        return svb_dispatch_elem<out() == SIG_NONE>(integer_size, zigzag, [&](auto e, auto z, auto i) {
+            return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s);
+        });
+    });
 }
 
 }  // namespace vbzhip

@@ -53,7 +53,7 @@ struct vbz_gpu_ctx
     std::string error;
     DevBuf scratch;   // intermediate svb streams of a batch
     DevBuf meta;      // per-read bookkeeping arrays
-    DevBuf gmeta;     // ... of one launch group of a decompress call
+    DevBuf gmeta;     // ... of one launch group (StageSlots)
     DevBuf route;     // per-read routing: the first group's gates, the second group's compact descriptors
     bool routing = true;   // VBZ_HIP_ROUTING=0: by batch shape only
     vbz_gpu_ctx* large = nullptr;   // per-read routing: the second group's own stream and buffers (it runs beside the first group)
@@ -323,22 +323,6 @@ struct DeviceGuard
         }                                                                          \
     } while (0)
 
-// carve n-element arrays out of ctx->meta
-struct MetaCarver
-{
-    uint8_t* p;
-    size_t off = 0;
-    explicit MetaCarver(void* base) : p((uint8_t*)base) {}
-    template <typename T>
-    T* take(size_t n)
-    {
-        off = (off + 15) & ~(size_t)15;
-        T* r = (T*)(p + off);
-        off += n * sizeof(T);
-        return r;
-    }
-};
-
 // One read per workgroup (svb) / per wavefront (entropy stage) fills the GPU when a batch has thousands of reads.  A batch of
 // few, large reads (BASELINE configs[0] and [3]: one 400 k-sample read, one 10 M-element buffer; the HDF5 filter's one chunk
 // per call) takes the segmented kernels instead: every read is spread over many workgroups.  The rule looks at the batch
@@ -473,6 +457,163 @@ int verify_checksums(vbz_gpu_ctx* c, const ReadBatch& z)
     return 0;
 }
 
+// The per-read arrays of a launch group's intermediate svb streams, carved from ctx->gmeta (base == nullptr: measure)
+struct StageSlots
+{
+    uint64_t* svb_off = nullptr;
+    uint32_t *svb_cap = nullptr, *svb_size = nullptr, *gate = nullptr;
+    uint32_t *deep_d = nullptr, *key_raw = nullptr, *gate2 = nullptr;   // encode: the matcher's distances, POD5's key sizes, the spans' gate
+    size_t carve(void* base, uint32_t n)
+    {
+        MetaCarver mc(base);
+        svb_off = mc.take<uint64_t>(n);
+        svb_cap = mc.take<uint32_t>(n);
+        svb_size = mc.take<uint32_t>(n);
+        gate = mc.take<uint32_t>(n);
+        deep_d = mc.take<uint32_t>(n);
+        key_raw = mc.take<uint32_t>(n);
+        gate2 = mc.take<uint32_t>(n);
+        return mc.bytes();
+    }
+};
+
+// What both kinds of launch group start with: the per-read arrays, on the large-read path the segment tables, and for both stages the
+// scratch that holds the svb streams between them -- its slots planned with the segments when they can be (two launches less for a call
+// of few reads), adopted from a split call's Preplanned, or left to launch_stage_plan.
+struct StagePlan
+{
+    StageSlots m;
+    SegTables seg;
+    bool both_stages = false, planned = false;
+    uint32_t num = 1, den = 1;   // svb_factor
+    size_t scratch_need = 0;
+    void* scratch_base = nullptr;
+};
+// sizes / arena_bytes: the reads' raw byte counts and their extent -- src_size / src_bytes of a compress group, dst_cap / dst_bytes of a
+// decompress group.  zigzag: whether svb_factor may count on it (a decode passes false: any code length may appear in a foreign stream).
+int plan_stage_scratch(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* sizes, uint64_t arena_bytes, const CompressionOptions* o, bool zigzag,
+                       bool segmented, const Preplanned* pre, StagePlan* p)
+{
+    const uint32_t n = rb.n_reads;
+    // svb into scratch, then the entropy stage into dst (vbz.cpp:163-207), or the entropy stage into scratch (sized for the largest svb
+    // stream the expected output can have), then svb decode into dst (vbz.cpp:234-299)
+    p->both_stages = o->integer_size != 0 && o->zstd_compression_level != 0;
+    if (p->both_stages) {
+        svb_factor(o->integer_size, zigzag, &p->num, &p->den);
+        p->scratch_need = (size_t)(((unsigned __int128)arena_bytes * p->num + p->den - 1) / p->den) + (size_t)n * 96 + 256;
+        if (!pre && !ensure(c, c->scratch, p->scratch_need)) return -1;
+    }
+    if (!ensure(c, c->gmeta, StageSlots().carve(nullptr, n))) return -1;
+    p->m.carve(c->gmeta.p, n);
+    p->scratch_base = pre ? pre->scratch : c->scratch.p;
+    if (pre) {   // (both stages, one-workgroup path: what split_batch asks for) -- slots and gates planned once for the whole batch
+        p->m.svb_off = pre->svb_off;
+        p->m.svb_cap = pre->svb_cap;
+        p->m.gate = pre->gate;
+        p->planned = true;
+    }
+    const ScratchPlan splan = { p->num, p->den, c->scratch.cap, p->m.svb_off, p->m.svb_cap, p->m.gate };
+    if (segmented && plan_segments(c, n, sizes, pre ? pre->gate : rb.gate, arena_bytes, svb_seg_unit_bytes((int)o->integer_size), &p->seg,
+                                   p->both_stages ? &splan : nullptr, &p->planned) != 0)
+        return -1;
+    return 0;
+}
+
+// Both stages, slots not planned yet: the plan's own launch.  gate_src (nullable): the gate the reads come with (the caller's; on the
+// large-read path the segments', E_OOM for a read whose segments do not fit the tables) -- copied, the plan adds its own E_OOM.
+int launch_stage_plan(vbz_gpu_ctx* c, uint32_t n, const uint32_t* sizes, const uint32_t* gate_src, const StagePlan& p)
+{
+    if (p.planned) return 0;
+    if (gate_src) HIPCHK(c, hipMemcpyAsync(p.m.gate, gate_src, 4ull * n, hipMemcpyDeviceToDevice, c->stream), "gate copy");
+    Timed t(c, "plan_scratch");
+    HIPCHK(c, launch_plan_scratch(n, sizes, p.num, p.den, c->scratch.cap, p.m.svb_off, p.m.svb_cap, p.m.gate, gate_src != nullptr, c->stream), "plan launch");
+    return 0;
+}
+
+// VBZ_HIP_PHASE_TIMING on the one-wavefront encoder: whose launch gets the phase counters, whether the encoder is staged under them, and
+// what dbg_end prints.  1: the whole frame in one launch (never staged); 2: the planning launch's counters (two per read, one per role),
+// 3: the packing launch's -- both under load, the other launches as they are.  The large-read path has no counters.
+struct EncodeTiming
+{
+    bool staged = false, per_role = false;
+    unsigned long long* counters = nullptr;
+    EncDebug dbg;
+    const char* label = "";
+};
+EncodeTiming encode_timing(vbz_gpu_ctx* c, uint32_t n, bool segmented)
+{
+    EncodeTiming t;
+    const int pt = segmented ? 0 : c->phase_timing;
+    t.per_role = pt == 2;
+    t.counters = pt ? dbg_begin(c, n, t.per_role) : nullptr;
+    t.staged = !segmented && c->staged_encode && (!t.counters || pt == 2 || pt == 3) && c->zero_run_sequences;
+    (pt == 2 ? t.dbg.plan : pt == 3 ? t.dbg.pack : t.dbg.frame) = t.counters;
+    t.label = pt == 3   ? "zstd_pack: setup region lookups+scan bits quads ends+headers sequences trailer"
+              : pt == 2 ? "zstd_plan: setup tokeniser sequences hist store rest | sort merge leaves lengths codes+weights tree"
+                        : "zstd_encode: setup hist plan size hdr encode";
+    return t;
+}
+
+// The entropy stage of a compress group on the large-read path (few, large reads): one wavefront per span of a stream, then compaction.
+// z: the svb streams in scratch -> the frames; a: key, hdr (runs and trailers are the context's).
+int entropy_encode_spans(vbz_gpu_ctx* c, ReadBatch z, ZstdEncodeArgs a, const CompressionOptions* o, const StagePlan& p)
+{
+    const uint32_t n = z.n_reads;
+    hipStream_t s = c->stream;
+    SpanEncodeWork w;
+    w.stream_bytes = p.scratch_need;
+    // Shared tables (zstd_encode.hip, SpanRegion): the data bytes of a read get ONE table, built beside the control-byte spans, and are
+    // packed in spans of 8 KB by a launch of their own.  For calls that are a matter of latency (zstd_span_shared_bytes) and for 8 / 16-bit
+    // elements, whose control bytes are mostly zero and cheap to code: 0.176 -> 0.140 ms per call for a 100 k-sample read.  The
+    // control-byte spans of 32-bit elements take as long as the table construction itself (a 40 MB buffer: 100 us in the first launch,
+    // + 15 us counting + 34 us packing against 125 us for everything in one launch) -- they keep a table per span.
+    // (canonical mode: whether the data bytes share a table must not follow from the call's size -- every span its own table)
+    w.shared_span_bytes = (c->shared_tables && !c->canonical && (o->integer_size == 1 || o->integer_size == 2)) ? zstd_span_shared_bytes(p.scratch_need) : 0u;
+    const size_t meta_bytes = zstd_span_meta_bytes(p.scratch_need, n, w.shared_span_bytes);
+    if (!meta_bytes) {
+        set_error(c, "batch too large for the span path");
+        return -1;
+    }
+    if (!ensure(c, c->spantmp, zstd_span_tmp_bytes(p.scratch_need, n)) || !ensure(c, c->spanmeta, meta_bytes)) return -1;
+    w.meta = c->spanmeta.p;
+    w.tmp = (uint8_t*)c->spantmp.p;
+    a.runs = { p.m.svb_cap, c->seqtab.p };
+    a.trailers = c->trailers;
+    z.gate = p.m.gate;
+    if (c->zero_run_sequences && c->long_repeats && o->integer_size != 0) {
+        // reads that repeat at one distance go to the one-wavefront matcher after all, whatever their length: a read that
+        // cycles a template (the reference's own perf generator: vbz/perf/test_data_generator.h:61-67) is 15-30 x smaller as
+        // matches than as spans of Huffman blocks, which is worth one wavefront's time on it (libzstd, the reference's
+        // coder, finds those matches at every level and every length: vbz/vbz.cpp:194-207).  The probe looks at the head of
+        // a long read's data bytes only (PROBE_WINDOW in zstd_encode.hip): two short launches for a read that has no period.
+        a.deep_d = p.m.deep_d;
+        Timed t(c, "zstd_encode_matcher");
+        HIPCHK(c, launch_zstd_encode_matcher(z, a, 0xFFFFFFFFu, p.m.gate, p.m.gate2, s), "zstd_encode (matcher) launch");
+        z.gate = p.m.gate2;
+    }
+    if (!c->zero_run_sequences) a.runs = ZeroRuns();
+    Timed t(c, "zstd_encode");
+    HIPCHK(c, launch_zstd_encode_spans(z, a, w, s), "zstd_encode (spans) launch");
+    return 0;
+}
+
+// ... and on the one-workgroup path: one wavefront per read, staged (the per-read plans, in which the svb encoder has left the data
+// bytes' histogram of int16 zig-zag reads when pre_filled: svb_kernels.hip CNT) or in one launch; the long-repeat matcher behind it.
+int entropy_encode_reads(vbz_gpu_ctx* c, const ReadBatch& z, ZstdEncodeArgs a, const StagePlan& p, const EncodeTiming& tm, bool matcher)
+{
+    {
+        Timed t(c, "zstd_encode");
+        if (c->zero_run_sequences) a.runs = { p.m.svb_cap, c->seqtab.p };
+        a.trailers = c->trailers;
+        a.deep_d = (matcher && !tm.counters) ? p.m.deep_d : nullptr;
+        a.staged = tm.staged;
+        a.dbg = tm.dbg;
+        HIPCHK(c, launch_zstd_encode(z, a, c->stream), "zstd_encode launch");
+    }
+    dbg_end(c, z.n_reads, tm.label, tm.counters, tm.per_role);
+    return 0;
+}
+
 // One launch group of a compress call: the reads of rb_in (those whose gate is closed left alone), on the one-workgroup path or
 // on the large-read path.  src_bytes: extent of the raw bytes of the group's reads.
 int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, const CompressionOptions* o, int sized, bool segmented,
@@ -483,48 +624,16 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
     const uint32_t hdr = sized ? 4u : 0u;
     hipStream_t s = c->stream;
     ReadBatch rb = rb_in;
-    struct { const uint32_t* src_size; uint64_t src_bytes; } view = { rb_in.src_size, src_bytes };
-    const auto* bt = &view;   // (the body below was written against the batch descriptor)
     if (o->integer_size == 0 && o->zstd_compression_level == 0) {  // vbz.cpp:130-133
         Timed t(c, "copy_bytes");
         HIPCHK(c, launch_copy_bytes(rb, hdr, s), "copy launch");
         return 0;
     }
-    SegTables seg;
-    // svb into scratch, then the entropy stage into dst (vbz.cpp:163-207): the scratch slots are planned with the segments when they can be
-    const bool both_stages = o->integer_size != 0 && o->zstd_compression_level != 0;
-    uint32_t num = 1, den = 1;
-    size_t scratch_need = 0;
-    uint64_t* svb_off = nullptr;
-    uint32_t *svb_cap = nullptr, *svb_size = nullptr, *gate = nullptr, *deep_d = nullptr, *key_raw = nullptr;
-    bool scratch_planned = false;
-    MetaCarver mc(nullptr);
-    if (both_stages) {
-        svb_factor(o->integer_size, o->perform_delta_zig_zag, &num, &den);
-        scratch_need = (size_t)(((unsigned __int128)bt->src_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
-        if (!pre && !ensure(c, c->scratch, scratch_need)) return -1;
-        if (!ensure(c, c->meta, (size_t)n * 40 + 256)) return -1;
-        mc = MetaCarver(c->meta.p);
-        svb_off = mc.take<uint64_t>(n);
-        svb_cap = mc.take<uint32_t>(n);
-        svb_size = mc.take<uint32_t>(n);
-        gate = mc.take<uint32_t>(n);
-        deep_d = mc.take<uint32_t>(n);
-        if (pod5_codec(o)) key_raw = mc.take<uint32_t>(n);
-        if (pre) {   // (both stages, one-workgroup path: what split_batch asks for)
-            svb_off = pre->svb_off;
-            svb_cap = pre->svb_cap;
-            gate = pre->gate;
-            scratch_planned = true;
-        }
-    }
-    void* const scratch_base = pre ? pre->scratch : c->scratch.p;
-    const ScratchPlan splan = { num, den, c->scratch.cap, svb_off, svb_cap, gate };
-    if (segmented && plan_segments(c, n, bt->src_size, rb_in.gate, bt->src_bytes, svb_seg_unit_bytes((int)o->integer_size), &seg,
-                                   both_stages ? &splan : nullptr, &scratch_planned) != 0)
-        return -1;
+    StagePlan p;
+    if (plan_stage_scratch(c, rb, rb.src_size, src_bytes, o, o->perform_delta_zig_zag, segmented, pre, &p) != 0) return -1;
+    const SegTables& seg = p.seg;
     if (segmented) rb.gate = seg.gate;   // (E_OOM for a read whose segments do not fit the tables)
-    if (o->integer_size != 0 && o->zstd_compression_level == 0) {  // vbz.cpp:171-192: svb straight into dst
+    if (o->zstd_compression_level == 0) {  // vbz.cpp:171-192: svb straight into dst
         Timed t(c, "svb_encode");
         if (segmented)
             HIPCHK(c, launch_svb_encode_seg(rb, (int)o->integer_size, o->perform_delta_zig_zag, hdr, true, seg.first, seg.max_segs, seg.val, seg.off, s),
@@ -533,126 +642,61 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
             HIPCHK(c, launch_svb_encode(rb, (int)o->integer_size, o->perform_delta_zig_zag, hdr, true, half_codec(o), nullptr, nullptr, s), "svb_encode launch");
         return 0;
     }
+    ZstdEncodeArgs za;
+    za.key.orig_size = rb.src_size;
+    za.hdr = hdr;
     if (o->integer_size == 0) {  // zstd only
         if (checksum_content(c, rb, rb.gate) != 0) return -1;
         {
             Timed t(c, "zstd_encode");
-            HIPCHK(c, launch_zstd_encode(rb, bt->src_size, 0, nullptr, hdr, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, nullptr, s), "zstd_encode launch");
+            za.trailers = c->trailers;
+            HIPCHK(c, launch_zstd_encode(rb, za, s), "zstd_encode launch");
         }
-        return checksum_frames(c, rb, rb.gate, hdr, bt->src_size, 0);
+        return checksum_frames(c, rb, rb.gate, hdr, rb.src_size, 0);
     }
     // the long-repeat matcher (every level: the reference's libzstd matches at every level; its workspace is the top of the
     // destination slots)
     const bool matcher = !segmented && c->zero_run_sequences && c->long_repeats;
-    if (!scratch_planned) {
-        if (rb.gate) HIPCHK(c, hipMemcpyAsync(gate, rb.gate, 4ull * n, hipMemcpyDeviceToDevice, s), "gate copy");
-        Timed t(c, "plan_scratch");
-        HIPCHK(c, launch_plan_scratch(n, bt->src_size, num, den, c->scratch.cap, svb_off, svb_cap, gate, rb.gate != nullptr, s), "plan launch");
-    }
-    ReadBatch a = rb;
-    a.dst = (uint8_t*)scratch_base;
-    a.dst_off = svb_off;
-    a.dst_cap = svb_cap;
-    a.result = svb_size;
-    a.gate = gate;
-    // the per-read plans of the entropy stage (one-wavefront path, staged encoder), in which the svb encoder leaves the data bytes'
-    // histogram of int16 zig-zag reads (svb_kernels.hip CNT)
-    unsigned long long* dbg = segmented ? nullptr : dbg_begin(c, n, c->phase_timing == 2);
-    const bool staged = !segmented && c->staged_encode && (!dbg || c->phase_timing == 2 || c->phase_timing == 3) && c->zero_run_sequences;
+    if (launch_stage_plan(c, n, rb.src_size, pre ? nullptr : rb.gate, p) != 0) return -1;
+    const EncodeTiming tm = encode_timing(c, n, segmented);
     const bool pod5 = pod5_codec(o);
-    const bool pre_filled = staged && !pod5 && svb_encode_fills_plans((int)o->integer_size, o->perform_delta_zig_zag, half_codec(o));
-    void* plan = nullptr;
-    if (staged) {
+    za.pre_filled = tm.staged && !pod5 && svb_encode_fills_plans((int)o->integer_size, o->perform_delta_zig_zag, half_codec(o));
+    if (tm.staged) {
         if (!ensure(c, c->encplan, zstd_encode_plan_bytes(n))) return -1;
-        plan = c->encplan.p;
+        za.plan_meta = c->encplan.p;
     }
     // the entropy stage's key region: ceil(n / 4) bytes of the raw size at integer_size, or svb16's ceil(n / 8) through key_raw (POD5)
-    const uint32_t* key_orig = bt->src_size;
-    uint32_t key_elem = o->integer_size;
+    za.key.key_elem = o->integer_size;
     if (pod5) {
-        HIPCHK(c, launch_svb16_key_raw(n, bt->src_size, key_raw, s), "svb16 key launch");
-        key_orig = key_raw;
-        key_elem = SVB16_KEY_ELEM;
+        HIPCHK(c, launch_svb16_key_raw(n, rb.src_size, p.m.key_raw, s), "svb16 key launch");
+        za.key.orig_size = p.m.key_raw;
+        za.key.key_elem = SVB16_KEY_ELEM;
     }
+    ReadBatch a = rb;   // the svb stage: the reads -> their streams in scratch
+    a.dst = (uint8_t*)p.scratch_base;
+    a.dst_off = p.m.svb_off;
+    a.dst_cap = p.m.svb_cap;
+    a.result = p.m.svb_size;
+    a.gate = p.m.gate;
     {
         Timed t(c, "svb_encode");
         if (pod5)   // (one workgroup per read on every path: DESIGN.md 4.13)
-            HIPCHK(c, launch_svb16_encode(a, (matcher && !segmented) ? deep_d : nullptr, s), "svb16_encode launch");
+            HIPCHK(c, launch_svb16_encode(a, matcher ? p.m.deep_d : nullptr, s), "svb16_encode launch");
         else if (segmented)
             HIPCHK(c, launch_svb_encode_seg(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, seg.first, seg.max_segs, seg.val, seg.off, s),
                    "svb_encode (segmented) launch");
         else
-            HIPCHK(c, launch_svb_encode(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, half_codec(o), matcher ? deep_d : nullptr,
-                                        pre_filled ? plan : nullptr, s),
+            HIPCHK(c, launch_svb_encode(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, half_codec(o), matcher ? p.m.deep_d : nullptr,
+                                        za.pre_filled ? za.plan_meta : nullptr, s),
                    "svb_encode launch");
     }
-    ReadBatch z = rb;
-    z.src = (const uint8_t*)scratch_base;
-    z.src_off = svb_off;
-    z.src_size = svb_size;
-    if (checksum_content(c, z, gate) != 0) return -1;
-    if (segmented) {  // few, large reads: one wavefront per span of a stream, then compaction
-        const uint32_t max_spans = zstd_span_max_spans(scratch_need, n);
-        if (!max_spans) {
-            set_error(c, "batch too large for the span path");
-            return -1;
-        }
-        const uint64_t tmp_bytes = zstd_span_tmp_bytes(scratch_need, n, max_spans);
-        if (!ensure(c, c->spantmp, tmp_bytes)) return -1;
-        // Shared tables (zstd_encode.hip, SpanRegion): the data bytes of a read get ONE table, built beside the control-byte spans, and are
-        // packed in spans of 8 KB by a launch of their own.  For calls that are a matter of latency (zstd_span_shared_bytes) and for 8 / 16-bit
-        // elements, whose control bytes are mostly zero and cheap to code: 0.176 -> 0.140 ms per call for a 100 k-sample read.  The
-        // control-byte spans of 32-bit elements take as long as the table construction itself (a 40 MB buffer: 100 us in the first launch,
-        // + 15 us counting + 34 us packing against 125 us for everything in one launch) -- they keep a table per span.
-        // (canonical mode: whether the data bytes share a table must not follow from the call's size -- every span its own table)
-        const uint32_t shspan = (c->shared_tables && !c->canonical && (o->integer_size == 1 || o->integer_size == 2)) ? zstd_span_shared_bytes(scratch_need) : 0u;
-        const bool shared = shspan != 0;
-        if (!ensure(c, c->spanmeta, (size_t)max_spans * (zstd_span_desc_bytes() + 12) + ((size_t)n + 2) * 4 + 256 + (shared ? zstd_span_region_bytes(n) + 64 : 0))) return -1;
-        MetaCarver sm(c->spanmeta.p);
-        uint8_t* regions = shared ? sm.take<uint8_t>(zstd_span_region_bytes(n)) : nullptr;
-        uint8_t* desc = sm.take<uint8_t>((size_t)max_spans * zstd_span_desc_bytes());
-        uint32_t* span_first = sm.take<uint32_t>((size_t)n + 1);
-        uint32_t* span_count = sm.take<uint32_t>(1);
-        uint32_t* span_size = sm.take<uint32_t>(max_spans);
-        uint32_t* span_trail = sm.take<uint32_t>(max_spans);
-        uint32_t* span_dst = sm.take<uint32_t>(max_spans);
-        z.gate = gate;
-        if (c->zero_run_sequences && c->long_repeats && o->integer_size != 0) {
-            // reads that repeat at one distance go to the one-wavefront matcher after all, whatever their length: a read that
-            // cycles a template (the reference's own perf generator: vbz/perf/test_data_generator.h:61-67) is 15-30 x smaller as
-            // matches than as spans of Huffman blocks, which is worth one wavefront's time on it (libzstd, the reference's
-            // coder, finds those matches at every level and every length: vbz/vbz.cpp:194-207).  The probe looks at the head of
-            // a long read's data bytes only (PROBE_WINDOW in zstd_encode.hip): two short launches for a read that has no period.
-            uint32_t* gate2 = mc.take<uint32_t>(n);
-            Timed t(c, "zstd_encode_matcher");
-            HIPCHK(c, launch_zstd_encode_matcher(z, key_orig, key_elem, hdr, svb_cap, c->seqtab.p, c->trailers, 0xFFFFFFFFu,
-                                                 deep_d, gate, gate2, s),
-                   "zstd_encode (matcher) launch");
-            z.gate = gate2;
-        }
-        Timed t(c, "zstd_encode");
-        HIPCHK(c, launch_zstd_encode_spans(z, key_orig, key_elem, hdr, c->zero_run_sequences ? svb_cap : nullptr,
-                                           c->zero_run_sequences ? c->seqtab.p : nullptr, desc, span_first, span_count, max_spans,
-                                           (uint8_t*)c->spantmp.p, tmp_bytes, span_size, span_trail, span_dst, c->trailers, regions, shspan, s),
-               "zstd_encode (spans) launch");
-        return checksum_frames(c, z, gate, hdr, pod5 ? nullptr : bt->src_size, o->integer_size);
-    }
-    {
-        Timed t(c, "zstd_encode");
-        // (phase timing 2: the planning launch's counters, 3: the packing launch's; both under load, the other launches as they are)
-        const bool staged_timing = c->phase_timing == 2 || c->phase_timing == 3;
-        HIPCHK(c, launch_zstd_encode(z, key_orig, key_elem, nullptr, hdr, staged_timing ? nullptr : dbg,
-                                     c->zero_run_sequences ? svb_cap : nullptr, c->zero_run_sequences ? c->seqtab.p : nullptr, c->trailers,
-                                     (matcher && !dbg) ? deep_d : nullptr, plan, staged, pre_filled, c->phase_timing == 2 ? dbg : nullptr,
-                                     c->phase_timing == 3 ? dbg : nullptr, s),
-               "zstd_encode launch");
-    }
-    dbg_end(c, n,
-            c->phase_timing == 3   ? "zstd_pack: setup region lookups+scan bits quads ends+headers sequences trailer"
-            : c->phase_timing == 2 ? "zstd_plan: setup tokeniser sequences hist store rest | sort merge leaves lengths codes+weights tree"
-                                   : "zstd_encode: setup hist plan size hdr encode",
-            dbg, c->phase_timing == 2);
-    return checksum_frames(c, z, gate, hdr, pod5 ? nullptr : bt->src_size, o->integer_size);
+    ReadBatch z = rb;   // the entropy stage: the streams -> the frames
+    z.src = (const uint8_t*)p.scratch_base;
+    z.src_off = p.m.svb_off;
+    z.src_size = p.m.svb_size;
+    if (checksum_content(c, z, p.m.gate) != 0) return -1;
+    if ((segmented ? entropy_encode_spans(c, z, za, o, p) : entropy_encode_reads(c, z, za, p, tm, matcher)) != 0) return -1;
+    return checksum_frames(c, z, p.m.gate, hdr, pod5 ? nullptr : rb.src_size, o->integer_size);
 }
 
 constexpr uint32_t REF_MIN_READS = 2560;   // calls of fewer reads: the one-wavefront decoder walks reference-written chains itself
@@ -660,6 +704,7 @@ constexpr uint32_t REF_MIN_READS = 2560;   // calls of fewer reads: the one-wave
 // The frames of a launch group on the one-workgroup path (not the large-read path): frames of this library's shape on the batched
 // decoder, the sequence chains of frames the reference wrote walked one lane per frame, everything else -- and every error verdict --
 // from the one-wavefront decoder.  content_bytes bounds the frames' content in all.
+// (decompress_split passes the WHOLE call's dst_bytes for each half: avg_content doubles and refrecs is sized for the call twice -- ADVICE.md)
 int zstd_frames(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_code, uint64_t content_bytes, unsigned long long* dbg)
 {
     const uint32_t n = z.n_reads;
@@ -693,9 +738,19 @@ int zstd_frames(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_code, uint
     // (content_bytes is the caller's bound: the decoded bytes of the call, 1.6 x the frames' content where an svb stage follows)
     const uint32_t lit_units = avg_content <= (96u << 10) ? 1u : (uint32_t)std::min<uint64_t>(avg_content / (256u << 10) + 2u, zstd_ref_lit_units());
     c->last_lit_units = lits ? lit_units : 0;
-    HIPCHK(c, launch_zstd_decode_fast(z, toosmall_code, c->seqdtab.p, c->fastmeta.p, walk ? c->refpre.p : nullptr, c->reftab.p, c->refrecs.p,
-                                      recs_bytes / 16, lits ? c->reflits.p : nullptr, lit_units, dbg, c->side, s),
-           "zstd_decode (batched) launch");
+    FastDecodeArgs a;
+    a.toosmall_code = toosmall_code;
+    a.seq_dtables = c->seqdtab.p;
+    a.meta = c->fastmeta.p;
+    a.ref.pre = walk ? c->refpre.p : nullptr;
+    a.ref.tables = c->reftab.p;
+    a.ref.recs = c->refrecs.p;
+    a.ref.recs_cap = recs_bytes / 16;
+    a.ref.lits = lits ? c->reflits.p : nullptr;
+    a.ref.lit_units = lit_units;
+    a.dbg = dbg;
+    a.side = c->side;
+    HIPCHK(c, launch_zstd_decode_fast(z, a, s), "zstd_decode (batched) launch");
     c->last_walked = walk;
     c->last_frames = dbg ? 0 : n;
     if (c->split_min != 0 && n >= c->split_min / 2 && !dbg) {   // (the context of a call that may be split: see foreign_host)
@@ -719,6 +774,43 @@ int zstd_frames(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_code, uint
     return 0;
 }
 
+// The entropy stage of a decompress group on the large-read path (few, large reads): frames with a span index are decoded one span per
+// wavefront.  z: the frames -> their content in scratch.
+int entropy_decode_spans(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_code, const StagePlan& p)
+{
+    SpanDecodeArgs a;
+    a.toosmall_code = toosmall_code;
+    a.seq_dtables = c->seqdtab.p;
+    a.content_bytes = p.scratch_need;
+    const size_t meta_bytes = zstd_dspan_meta_bytes(p.scratch_need, z.n_reads);
+    if (!meta_bytes) {
+        set_error(c, "batch too large for the span path");
+        return -1;
+    }
+    if (!ensure(c, c->spanmeta, meta_bytes)) return -1;
+    a.meta = c->spanmeta.p;
+    Timed t(c, "zstd_decode");
+    HIPCHK(c, launch_zstd_decode_spans(z, &a, c->stream), "zstd_decode (spans) launch");
+    c->last_frames = 0;
+    c->last_span_frames = z.n_reads;
+    c->last_span_redo = a.redo;
+    return 0;
+}
+
+// The svb stage of a decompress group (d: the streams -> the reads, with the store and the normalising passes of d.sig)
+int svb_decode_stage(vbz_gpu_ctx* c, const ReadBatch& d, const CompressionOptions* o, bool segmented, const SegTables& seg)
+{
+    Timed t(c, "svb_decode");
+    if (pod5_codec(o))   // (one workgroup per read on every path: DESIGN.md 4.13)
+        HIPCHK(c, launch_svb16_decode(d, c->stream), "svb16_decode launch");
+    else if (segmented)
+        HIPCHK(c, launch_svb_decode_seg(d, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->stream),
+               "svb_decode (segmented) launch");
+    else
+        HIPCHK(c, launch_svb_decode(d, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream), "svb_decode launch");
+    return 0;
+}
+
 // One launch group of a decompress call: the reads of rb_in (dst_cap = the exact decoded byte counts; those whose gate is closed
 // left alone), on the one-workgroup path or on the large-read path.  dst_bytes: extent of the decoded bytes of the group.
 int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes, const CompressionOptions* o, bool segmented,
@@ -727,60 +819,25 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     const uint32_t n = rb_in.n_reads;
     if (n == 0) return 0;
     hipStream_t s = c->stream;
-    if (!ensure(c, c->gmeta, (size_t)n * 24 + 512)) return -1;
-    MetaCarver mc(c->gmeta.p);
-    uint64_t* svb_off = mc.take<uint64_t>(n);
-    uint32_t* gate = mc.take<uint32_t>(n);
-    uint32_t* svb_cap = mc.take<uint32_t>(n);
-    uint32_t* svb_size = mc.take<uint32_t>(n);
     ReadBatch rb = rb_in;
     if (o->integer_size == 0 && o->zstd_compression_level == 0) {
         Timed t(c, "copy_bytes");
         HIPCHK(c, launch_copy_bytes(rb, 0, s), "copy launch");
         return 0;
     }
-    SegTables seg;
     const bool pod5 = pod5_codec(o);
     if (rb.sig.norm.st && segmented && !pod5) {   // (a normalising decode on the large-read path: the segments' counts add up here)
         if (!ensure(c, c->normslab, (size_t)n * NORM_SLAB * 4)) return -1;
         rb.sig.norm.slab = reinterpret_cast<uint32_t*>(c->normslab.p);
     }
-    // (both stages: the scratch slots are planned with the segments when they can be -- two launches less for a call of few reads)
-    const bool both_stages = o->integer_size != 0 && o->zstd_compression_level != 0;
-    uint32_t num = 1, den = 1;
-    size_t scratch_need = 0;
-    if (both_stages) {
-        svb_factor(o->integer_size, false, &num, &den);  // any code length may appear in a foreign stream
-        scratch_need = (size_t)(((unsigned __int128)dst_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
-        if (!pre && !ensure(c, c->scratch, scratch_need)) return -1;
-    }
-    const ScratchPlan splan = { num, den, c->scratch.cap, svb_off, svb_cap, gate };
-    bool scratch_planned = false;
-    void* const scratch_base = pre ? pre->scratch : c->scratch.p;
-    if (pre) {   // (both stages, one-workgroup path: split_batch) -- slots and gates planned once for the whole batch
-        svb_off = pre->svb_off;
-        svb_cap = pre->svb_cap;
-        gate = pre->gate;
-        rb.gate = gate;
-        scratch_planned = true;
-    }
-    if (segmented && plan_segments(c, n, rb.dst_cap, rb.gate, dst_bytes, svb_seg_unit_bytes((int)o->integer_size), &seg, both_stages ? &splan : nullptr,
-                                   &scratch_planned) != 0)
-        return -1;
-    const bool gate_in = !pre && (segmented || rb.gate != nullptr);
-    if (gate_in) {   // (the caller's gate; E_OOM for a read whose segments do not fit the tables)
-        if (!scratch_planned) HIPCHK(c, hipMemcpyAsync(gate, segmented ? seg.gate : rb.gate, 4ull * n, hipMemcpyDeviceToDevice, s), "gate copy");
-        rb.gate = gate;
-    }
-    if (o->zstd_compression_level == 0) {
-        Timed t(c, "svb_decode");
-        if (segmented)
-            HIPCHK(c, launch_svb_decode_seg(rb, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, s),
-                   "svb_decode (segmented) launch");
-        else
-            HIPCHK(c, launch_svb_decode(rb, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), s), "svb_decode launch");
-        return 0;
-    }
+    StagePlan p;
+    if (plan_stage_scratch(c, rb, rb.dst_cap, dst_bytes, o, false, segmented, pre, &p) != 0) return -1;
+    // the gate the reads come with: a split call's (planned), the segments' (E_OOM for a read whose segments do not fit the tables) or
+    // the caller's; every stage runs under the group's copy of it
+    const uint32_t* const gate_src = pre ? nullptr : segmented ? p.seg.gate : rb.gate;
+    if (!p.both_stages && gate_src) HIPCHK(c, hipMemcpyAsync(p.m.gate, gate_src, 4ull * n, hipMemcpyDeviceToDevice, s), "gate copy");
+    if (pre || gate_src) rb.gate = p.m.gate;
+    if (o->zstd_compression_level == 0) return svb_decode_stage(c, rb, o, segmented, p.seg);
     if (o->integer_size == 0) {  // vbz.cpp:259-262: content larger than the destination -> DESTINATION_SIZE
         if (segmented) {
             Timed t(c, "zstd_decode");
@@ -790,62 +847,31 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
         }
         return verify_checksums(c, rb);
     }
-    // entropy stage into scratch (sized for the largest svb stream the expected output can have),
-    // then svb decode into dst (vbz.cpp:234-299)
-    if (!scratch_planned) {
-        Timed t(c, "plan_scratch");
-        HIPCHK(c, launch_plan_scratch(n, rb.dst_cap, num, den, c->scratch.cap, svb_off, svb_cap, gate, gate_in, s), "plan launch");
-    }
-    ReadBatch z = rb;
-    z.dst = (uint8_t*)scratch_base;
-    z.dst_off = svb_off;
-    z.dst_cap = svb_cap;
-    z.result = svb_size;
-    z.gate = gate;
+    if (launch_stage_plan(c, n, rb.dst_cap, gate_src, p) != 0) return -1;
+    ReadBatch z = rb;   // the entropy stage: the frames -> their content in scratch
+    z.dst = (uint8_t*)p.scratch_base;
+    z.dst_off = p.m.svb_off;
+    z.dst_cap = p.m.svb_cap;
+    z.result = p.m.svb_size;
+    z.gate = p.m.gate;
+    // a frame whose content cannot be a valid svb stream of the expected size: the reference would
+    // decode it and then fail in the svb stage with a stream error (POD5: content beyond svb16_max(n) is the zstd stage's error)
+    const uint32_t toosmall_code = pod5 ? E_ZSTD : E_STREAM;
     unsigned long long* dbg = segmented ? nullptr : dbg_begin(c, n);
-    if (segmented) {  // few, large reads: frames with a span index are decoded one span per wavefront
-        const uint32_t max_spans = zstd_dspan_max_spans(scratch_need, n);
-        if (!max_spans) {
-            set_error(c, "batch too large for the span path");
-            return -1;
-        }
-        if (!ensure(c, c->spanmeta, (size_t)max_spans * (zstd_dspan_desc_bytes() + 16) + ((size_t)n + 2) * 8 + 256)) return -1;
-        MetaCarver sm(c->spanmeta.p);
-        uint8_t* desc = sm.take<uint8_t>((size_t)max_spans * zstd_dspan_desc_bytes());
-        uint32_t* dspan_first = sm.take<uint32_t>((size_t)n + 1);
-        uint32_t* dspan_count = sm.take<uint32_t>(1);
-        uint32_t* dspan_status = sm.take<uint32_t>((size_t)max_spans * 4);
-        uint32_t* redo = sm.take<uint32_t>(n);
-        Timed t(c, "zstd_decode");
-        HIPCHK(c, launch_zstd_decode_spans(z, pod5 ? E_ZSTD : E_STREAM, c->seqdtab.p, desc, dspan_first, dspan_count, max_spans, dspan_status, redo, s),
-               "zstd_decode (spans) launch");
-        c->last_frames = 0;
-        c->last_span_frames = n;
-        c->last_span_redo = redo;
+    if (segmented) {
+        if (entropy_decode_spans(c, z, toosmall_code, p) != 0) return -1;
     } else {
         c->last_span_frames = 0;
-        // a frame whose content cannot be a valid svb stream of the expected size: the reference would
-        // decode it and then fail in the svb stage with a stream error (POD5: content beyond svb16_max(n) is the zstd stage's error)
-        if (zstd_frames(c, z, pod5 ? E_ZSTD : E_STREAM, dst_bytes, dbg) != 0) return -1;
+        if (zstd_frames(c, z, toosmall_code, dst_bytes, dbg) != 0) return -1;
     }
     dbg_end(c, n, "zstd_decode: parse flush seqtables chain place huftable header queue | general sequences: flush tables records literals matches", dbg);
     if (verify_checksums(c, z) != 0) return -1;
-    ReadBatch d = rb;
-    d.src = (const uint8_t*)scratch_base;
-    d.src_off = svb_off;
-    d.src_size = svb_size;
-    d.gate = gate;
-    {
-        Timed t(c, "svb_decode");
-        if (pod5)   // (one workgroup per read on every path: DESIGN.md 4.13)
-            HIPCHK(c, launch_svb16_decode(d, s), "svb16_decode launch");
-        else if (segmented)
-            HIPCHK(c, launch_svb_decode_seg(d, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, s),
-                   "svb_decode (segmented) launch");
-        else
-            HIPCHK(c, launch_svb_decode(d, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), s), "svb_decode launch");
-    }
-    return 0;
+    ReadBatch d = rb;   // the svb stage: the streams -> the reads
+    d.src = (const uint8_t*)p.scratch_base;
+    d.src_off = p.m.svb_off;
+    d.src_size = p.m.svb_size;
+    d.gate = p.m.gate;
+    return svb_decode_stage(c, d, o, segmented, p.seg);
 }
 
 // ---- per-read routing ----------------------------------------------------------------------------------------------------
@@ -904,36 +930,41 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * (64 + sizeof(NormRead)) + route_cand_words() * 4 + 512)) return -1;
     MetaCarver mc(c->route.p);
     r->gate_small = mc.take<uint32_t>(n);
-    uint64_t* l_src_off = mc.take<uint64_t>(ROUTE_MAX_READS);
-    uint64_t* l_dst_off = mc.take<uint64_t>(ROUTE_MAX_READS);
-    uint32_t* l_src_size = mc.take<uint32_t>(ROUTE_MAX_READS);
-    uint32_t* l_dst_cap = mc.take<uint32_t>(ROUTE_MAX_READS);
-    uint32_t* l_gate = mc.take<uint32_t>(ROUTE_MAX_READS);
+    RouteArgs a;
+    RoutedTable& l = a.large;
+    l.src_off = mc.take<uint64_t>(ROUTE_MAX_READS);
+    l.dst_off = mc.take<uint64_t>(ROUTE_MAX_READS);
+    l.src_size = mc.take<uint32_t>(ROUTE_MAX_READS);
+    l.dst_cap = mc.take<uint32_t>(ROUTE_MAX_READS);
+    l.gate = mc.take<uint32_t>(ROUTE_MAX_READS);
     uint32_t* l_result = mc.take<uint32_t>(ROUTE_MAX_READS);
-    r->map = mc.take<uint32_t>(ROUTE_MAX_READS);
-    float2* l_cal = mc.take<float2>(ROUTE_MAX_READS);
-    uint64_t* l_row = mc.take<uint64_t>(ROUTE_MAX_READS);
+    l.map = r->map = mc.take<uint32_t>(ROUTE_MAX_READS);
+    l.cal = mc.take<float2>(ROUTE_MAX_READS);
+    l.row = mc.take<uint64_t>(ROUTE_MAX_READS);
     NormRead* l_norm = mc.take<NormRead>(ROUTE_MAX_READS);
-    r->count = mc.take<uint32_t>(4);
-    uint32_t* cand = mc.take<uint32_t>(route_cand_words());
+    l.count = r->count = mc.take<uint32_t>(4);
+    a.cand = mc.take<uint32_t>(route_cand_words());
     r->large = rb;
     r->large.n_reads = ROUTE_MAX_READS;
-    r->large.src_off = l_src_off;
-    r->large.src_size = l_src_size;
-    r->large.dst_off = l_dst_off;
-    r->large.dst_cap = l_dst_cap;
-    r->large.gate = l_gate;
+    r->large.src_off = l.src_off;
+    r->large.src_size = l.src_size;
+    r->large.dst_off = l.dst_off;
+    r->large.dst_cap = l.dst_cap;
+    r->large.gate = l.gate;
     r->large.result = l_result;
-    if (rb.sig.cal) r->large.sig.cal = l_cal;   // (the routed reads' constants, gathered through the map)
-    if (rb.sig.row) r->large.sig.row = l_row;   // (and their first chunk rows)
+    if (rb.sig.cal) r->large.sig.cal = l.cal;   // (the routed reads' constants, gathered through the map)
+    if (rb.sig.row) r->large.sig.row = l.row;   // (and their first chunk rows)
     if (rb.sig.norm.st) {   // (a normalising decode: states of their own; shift_scale written back through the map)
         r->large.sig.norm.st = l_norm;
         r->large.sig.norm.map = r->map;
     }
     Timed t(c, "route");
-    HIPCHK(c, launch_route_reads(rb, raw_size, ROUTE_MIN_BYTES, ROUTE_MAX_READS, ROUTE_MAX_BYTES, r->gate_small, l_src_off, l_src_size, l_dst_off, l_dst_cap,
-                                 l_gate, r->map, l_cal, l_row, r->count, cand, c->stream),
-           "route launch");
+    a.raw_size = raw_size;
+    a.min_bytes = ROUTE_MIN_BYTES;
+    a.max_reads = ROUTE_MAX_READS;
+    a.max_bytes = ROUTE_MAX_BYTES;
+    a.gate_small = r->gate_small;
+    HIPCHK(c, launch_route_reads(rb, a, c->stream), "route launch");
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream), "event record");
     HIPCHK(c, hipStreamWaitEvent(c->large->stream, c->ev_fork, 0), "stream wait");
     return 0;
@@ -1287,12 +1318,18 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         no.scale_min = out->norm->scale_min;
     }
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
-        if (!ensure(c, c->meta, (size_t)n * 24 + 512)) return -1;
-        MetaCarver mc(c->meta.p);
-        uint64_t* pay_off = mc.take<uint64_t>(n);
-        uint32_t* pay_size = mc.take<uint32_t>(n);
-        uint32_t* orig_size = mc.take<uint32_t>(n);
-        uint32_t* gate = mc.take<uint32_t>(n);
+        uint64_t* pay_off;
+        uint32_t *pay_size, *orig_size, *gate;
+        auto carve = [&](void* base) {
+            MetaCarver mc(base);
+            pay_off = mc.take<uint64_t>(n);
+            pay_size = mc.take<uint32_t>(n);
+            orig_size = mc.take<uint32_t>(n);
+            gate = mc.take<uint32_t>(n);
+            return mc.bytes();
+        };
+        if (!ensure(c, c->meta, carve(nullptr))) return -1;
+        carve(c->meta.p);
         Timed t(c, "parse_sized");
         HIPCHK(c, launch_parse_sized(n, rb.src, bt->src_off, bt->src_size, rb.dst_cap, rb.gate, pay_off, pay_size, orig_size, gate, s),
                "parse_sized launch");
@@ -1697,7 +1734,11 @@ int vbz_gpu_zstd_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const u
     DeviceGuard dg(c->device);
     if (checksum_content(c, to_rb(bt), nullptr) != 0) return -1;
     Timed t(c, "zstd_encode");
-    HIPCHK(c, launch_zstd_encode(to_rb(bt), bt->src_size, 0, key_bytes, 0, nullptr, nullptr, nullptr, c->trailers, nullptr, nullptr, false, false, nullptr, nullptr, c->stream), "zstd_encode launch");
+    ZstdEncodeArgs a;
+    a.key.orig_size = bt->src_size;
+    a.key.key_bytes = key_bytes;
+    a.trailers = c->trailers;
+    HIPCHK(c, launch_zstd_encode(to_rb(bt), a, c->stream), "zstd_encode launch");
     return checksum_frames(c, to_rb(bt), nullptr, 0, nullptr, 0);
 }
 
@@ -1828,12 +1869,11 @@ VBZ_EXPORT int vbz_gpu_x_svb_handover(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, v
     uint32_t num, den;
     svb_factor(2, true, &num, &den);
     const size_t scratch_need = (size_t)(((unsigned __int128)bt->src_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
-    if (!ensure(c, c->scratch, scratch_need) || !ensure(c, c->meta, (size_t)n * 40 + 256) || !ensure(c, c->encplan, zstd_encode_plan_bytes(n))) return -1;
-    MetaCarver mc(c->meta.p);
-    uint64_t* svb_off = mc.take<uint64_t>(n);
-    uint32_t* svb_cap = mc.take<uint32_t>(n);
-    uint32_t* svb_size = mc.take<uint32_t>(n);
-    uint32_t* gate = mc.take<uint32_t>(n);
+    StageSlots m;
+    if (!ensure(c, c->scratch, scratch_need) || !ensure(c, c->meta, m.carve(nullptr, n)) || !ensure(c, c->encplan, zstd_encode_plan_bytes(n))) return -1;
+    m.carve(c->meta.p, n);
+    uint64_t* const svb_off = m.svb_off;
+    uint32_t *const svb_cap = m.svb_cap, *const svb_size = m.svb_size, *const gate = m.gate;
     HIPCHK(c, launch_plan_scratch(n, bt->src_size, num, den, c->scratch.cap, svb_off, svb_cap, gate, false, s), "plan launch");
     ReadBatch a = rb;
     a.dst = (uint8_t*)c->scratch.p;

@@ -87,6 +87,25 @@ __host__ __device__ inline uint32_t chunk_last_start(uint32_t T, uint32_t K, uin
     return e < g ? e : g;
 }
 
+// Arrays carved out of one buffer of device scratch, each 16-byte aligned (host only).  base == nullptr measures: the same take<>() calls
+// carve nothing, and bytes() behind them is what to allocate -- the arrays and a quarter more + 512 bytes of headroom (allocations are
+// not sized to the byte: a kernel that reads a vector past the end of its array stays inside the buffer).
+struct MetaCarver
+{
+    uint8_t* p;
+    size_t off = 0;
+    explicit MetaCarver(void* base) : p((uint8_t*)base) {}
+    template <typename T>
+    T* take(size_t n)
+    {
+        off = (off + 15) & ~(size_t)15;
+        T* r = p ? (T*)(p + off) : nullptr;
+        off += n * sizeof(T);
+        return r;
+    }
+    size_t bytes() const { return off + off / 4 + 512; }
+};
+
 // One batch of independent reads ("reads" in the reference's vocabulary: one HDF5 chunk each).
 // All pointers are device pointers.  `result[i]` receives the bytes produced or an error code.
 // If `gate` is non-null, reads whose gate[i] is an error code are skipped and the error is kept; reads whose gate[i] is
@@ -176,26 +195,49 @@ hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigz
                                  uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s);
 
 // ---- zstd-format entropy stage (zstd_encode.hip / zstd_decode.hip) -----------------------------
-// encode: frame content = src read; key_elem = integer size whose key section (ceil(n/4) bytes, n
-// derived from `orig_size[i] / key_elem`) is split into its own blocks; 0 = no split.
-// hdr: 0 or 4 (sized header carrying orig_size[i] in front of the frame).
-// key_bytes (nullable) gives the key-section length per read directly and overrides key_elem.
-// dbg (nullable): 8 x u64 per read, shader-clock cycles spent per phase (debug aid, VBZ_HIP_PHASE_TIMING=1)
-// src_cap + seq_tables (both nullable): the source streams live in library-owned scratch slots of that
+// encode: frame content = src read.  The launchers' arguments are host-side aggregates, filled field by field; what is not set is not used.
+// The key region: key_elem = integer size whose key section (ceil(n/4) bytes, n derived from `orig_size[i] / key_elem`) is split into
+// its own blocks; 0 = no split.  key_bytes (nullable) gives the key-section length per read directly and overrides key_elem.
+struct KeyRegion
+{
+    const uint32_t* orig_size = nullptr;
+    uint32_t key_elem = 0;
+    const uint32_t* key_bytes = nullptr;
+};
+// src_cap + seq_tables (both or neither): the source streams live in library-owned scratch slots of that
 // capacity, which lets the encoder rewrite the control-byte region as literals + zero-run sequences.
-// trailers: append the decoder-checkpoint skippable frame when a sequences section was written (see zstd_encode.hip)
-// deep_d (nullable, n_reads words): the repeat distance launch_svb_encode's probe proposes for every read (0: none).  Reads
-// whose proposal holds are coded by a second launch with the long-repeat matcher (what libzstd's match finder gets out of
-// template-cycling signal, at every level); deep_d[r] is rewritten with the verdict.  The matcher's workspace is the top of
-// the destination slot (reads whose slot is too small for frame and workspace are coded without it).
-// plan_meta (nullable, zstd_encode_plan_bytes(n_reads) bytes of device scratch): the per-read plans.  staged: the ordinary read is
-// coded by the staged launches (tokeniser + sequences section, tables, packing -- each at the occupancy its own footprint allows) and
-// only what they leave over by the one-launch kernel; same frames either way.  pre_filled: launch_svb_encode(plans) has left every
-// read's hist_mode (and histogram) in the plans.
-hipError_t launch_zstd_encode(const ReadBatch& b, const uint32_t* orig_size, uint32_t key_elem, const uint32_t* key_bytes,
-                              uint32_t hdr, unsigned long long* dbg, const uint32_t* src_cap, const void* seq_tables, bool trailers,
-                              uint32_t* deep_d, void* plan_meta, bool staged, bool pre_filled, unsigned long long* plan_dbg, unsigned long long* pack_dbg,
-                              hipStream_t s);
+struct ZeroRuns
+{
+    const uint32_t* src_cap = nullptr;
+    const void* seq_tables = nullptr;
+};
+// 8 x u64 per read, shader-clock cycles spent per phase (debug aid, VBZ_HIP_PHASE_TIMING): of the whole frame in one launch (= 1), of
+// the staged encoder's planning launch (= 2: two per read, one per role) or of its packing launch (= 3)
+struct EncDebug
+{
+    unsigned long long *frame = nullptr, *plan = nullptr, *pack = nullptr;
+};
+struct ZstdEncodeArgs
+{
+    KeyRegion key;
+    uint32_t hdr = 0;        // 0 or 4 (sized header carrying orig_size[i] in front of the frame)
+    ZeroRuns runs;
+    bool trailers = false;   // append the decoder-checkpoint skippable frame when a sequences section was written (see zstd_encode.hip);
+                             // (spans: checkpoints and span index behind the frame)
+    // deep_d (n_reads words): the repeat distance launch_svb_encode's probe proposes for every read (0: none).  Reads
+    // whose proposal holds are coded by a second launch with the long-repeat matcher (what libzstd's match finder gets out of
+    // template-cycling signal, at every level); deep_d[r] is rewritten with the verdict.  The matcher's workspace is the top of
+    // the destination slot (reads whose slot is too small for frame and workspace are coded without it).
+    uint32_t* deep_d = nullptr;
+    // plan_meta (zstd_encode_plan_bytes(n_reads) bytes of device scratch): the per-read plans.  staged: the ordinary read is
+    // coded by the staged launches (tokeniser + sequences section, tables, packing -- each at the occupancy its own footprint allows) and
+    // only what they leave over by the one-launch kernel; same frames either way.  pre_filled: launch_svb_encode(plans) has left every
+    // read's hist_mode (and histogram) in the plans.  (launch_zstd_encode only)
+    void* plan_meta = nullptr;
+    bool staged = false, pre_filled = false;
+    EncDebug dbg;
+};
+hipError_t launch_zstd_encode(const ReadBatch& b, const ZstdEncodeArgs& a, hipStream_t s);
 size_t zstd_encode_plan_bytes(uint32_t n_reads);
 size_t seq_tables_bytes();
 void seq_tables_build(void* host_buffer);
@@ -207,30 +249,30 @@ struct SideStream
     hipEvent_t fork = nullptr, join = nullptr;
 };
 typedef SideStream FastSide;
-// The same stage for batches of few, large reads: one wavefront per SPAN of a read's stream (see zstd_encode.hip).
-// stream_bytes bounds the total of the source streams.  span_desc: max_spans x zstd_span_desc_bytes(); span_first[n_reads + 1];
-// span_count[1]; span_size / span_trail / span_dst [max_spans]; span_tmp: zstd_span_tmp_bytes(...) bytes.
-size_t zstd_span_desc_bytes();
-uint32_t zstd_span_max_spans(uint64_t stream_bytes, uint32_t n_reads);  // 0: too large
-uint64_t zstd_span_tmp_bytes(uint64_t stream_bytes, uint32_t n_reads, uint32_t max_spans);
-hipError_t launch_zstd_encode_spans(const ReadBatch& b, const uint32_t* orig_size, uint32_t key_elem, uint32_t hdr, const uint32_t* src_cap,
-                                    const void* seq_tables, void* span_desc, uint32_t* span_first, uint32_t* span_count, uint32_t max_spans,
-                                    uint8_t* span_tmp, uint64_t span_tmp_bytes, uint32_t* span_size, uint32_t* span_trail, uint32_t* span_dst,
-                                    bool trailers, void* shared_regions, uint32_t shared_span_bytes, hipStream_t s);  // trailers: checkpoints and span index behind the frame
-// shared_regions (nullable: every span builds its own table): zstd_span_region_bytes(n_reads) bytes of device scratch, 16-byte aligned -- the
-// data bytes of a read with a control-byte region get ONE table (counted and built by extra wavefronts of the launch that codes the
-// control-byte spans) and are packed one wavefront per 8 KB span by the launch behind it.
-// shared_span_bytes: zstd_span_shared_bytes(the call's stream bytes) -- 0 (pass shared_regions = nullptr then): a batch of large buffers,
-// a matter of throughput, where every span builds its own table in one launch.
-size_t zstd_span_region_bytes(uint32_t n_reads);
+// The same stage for batches of few, large reads: one wavefront per SPAN of a read's stream (see zstd_encode.hip).  a: key, hdr, runs,
+// trailers.  stream_bytes bounds the total of the source streams; meta / tmp: zstd_span_meta_bytes / zstd_span_tmp_bytes of device
+// scratch for the same stream_bytes, n_reads and shared_span_bytes (meta 16-byte aligned; the launcher carves its tables from it).
+// shared_span_bytes: zstd_span_shared_bytes(the call's stream bytes), or 0 -- not 0: the data bytes of a read with a control-byte region
+// get ONE table (counted and built by extra wavefronts of the launch that codes the control-byte spans) and are packed one wavefront
+// per 8 KB span by the launch behind it; 0: a batch of large buffers, a matter of throughput, where every span builds its own table in
+// one launch.
+struct SpanEncodeWork
+{
+    uint64_t stream_bytes = 0;
+    void* meta = nullptr;
+    uint8_t* tmp = nullptr;
+    uint32_t shared_span_bytes = 0;
+};
+size_t zstd_span_meta_bytes(uint64_t stream_bytes, uint32_t n_reads, uint32_t shared_span_bytes);  // 0: too large
+uint64_t zstd_span_tmp_bytes(uint64_t stream_bytes, uint32_t n_reads);
 uint32_t zstd_span_shared_bytes(uint64_t stream_bytes);
+hipError_t launch_zstd_encode_spans(const ReadBatch& b, const ZstdEncodeArgs& a, const SpanEncodeWork& w, hipStream_t s);
 // The long-repeat matcher in front of the span launches (batches too small to fill the device run as spans): a probe over
 // every read below max_raw bytes, the check of launch_zstd_encode's first launch, and its matcher instantiation for the reads
-// whose distance holds.  deep_d[n_reads] is scratch; gate_out[i] = GATE_SKIP for the reads coded here (the spans skip them),
-// gate_in[i] otherwise.  b: as for launch_zstd_encode (source streams in library-owned slots of src_cap[i] bytes).
-hipError_t launch_zstd_encode_matcher(const ReadBatch& b, const uint32_t* orig_size, uint32_t key_elem, uint32_t hdr, const uint32_t* src_cap,
-                                      const void* seq_tables, bool trailers, uint32_t max_raw, uint32_t* deep_d, const uint32_t* gate_in,
-                                      uint32_t* gate_out, hipStream_t s);
+// whose distance holds.  a: key, hdr, runs, trailers, and deep_d[n_reads] as scratch; gate_out[i] = GATE_SKIP for the reads coded here
+// (the spans skip them), gate_in[i] otherwise.  b: as for launch_zstd_encode (source streams in library-owned slots of src_cap[i] bytes).
+hipError_t launch_zstd_encode_matcher(const ReadBatch& b, const ZstdEncodeArgs& a, uint32_t max_raw, const uint32_t* gate_in, uint32_t* gate_out,
+                                      hipStream_t s);
 // decode: result[i] = frame content size, E_ZSTD for a malformed frame, or `toosmall_code` when the
 // frame's content size exceeds dst_cap[i].
 // seq_dtables (device, from seq_dtables_build): decoding tables of the predefined LL / ML distributions.
@@ -287,18 +329,33 @@ hipError_t launch_zstd_decode_only(const ReadBatch& b, uint32_t toosmall_code, c
 // Batched decoder for frames of the shape zstd_encode.hip writes (zstd_decode_fast.hip: one lane per frame for the headers, one lane
 // per tree description, one wavefront per frame for nothing but the streams, one for the zero-run block); every frame that is not of
 // that shape or fails a check, and every error verdict, goes through launch_zstd_decode_only at the end.  Same results as
-// launch_zstd_decode.  meta: zstd_fast_meta_bytes(n_reads) bytes of device scratch.
-// ref_*: scratch of launch_zstd_ref_chain (ref_pre == nullptr: frames of other writers go to the one-wavefront decoder as they are).
-// dbg (nullable): phase cycle counters of the one-wavefront decoder, which then decodes EVERY frame (walked chains included).
+// launch_zstd_decode.
 size_t zstd_fast_meta_bytes(uint32_t n_reads);
 const RefLits* zstd_ref_lits(const void* lit_meta, uint32_t n_reads);   // (diagnostics: zstd_ref_lit_units() records per read; blk != 0 = that block's literals were decoded ahead)
 bool zstd_ref_literals_enabled();                                   // VBZ_HIP_REF_LITERALS
 const uint32_t* zstd_fast_redo(const void* meta, uint32_t n_reads);  // after the call: redo[i] == 0 <=> frame i was decoded by the batched decoder
-hipError_t launch_zstd_decode_fast(const ReadBatch& b, uint32_t toosmall_code, const void* seq_dtables, void* meta, void* ref_pre, void* ref_tables,
-                                   void* ref_recs, uint64_t ref_recs_cap, void* ref_lits, uint32_t ref_units, unsigned long long* dbg, FastSide side,
-                                   hipStream_t s);
-// ref_lits (nullable): zstd_ref_lit_meta_bytes(n_reads) bytes for the literals decoded beside the walk (zstd_ref_lit_units() records per read;
-// ref_units: how many of them this call fills -- blocks per frame that get a workgroup)
+// The batched decoder's arguments.  meta: zstd_fast_meta_bytes(n_reads) bytes of device scratch.
+// ref.*: scratch of launch_zstd_ref_chain (ref.pre == nullptr: frames of other writers go to the one-wavefront decoder as they are);
+// ref.lits (nullable): zstd_ref_lit_meta_bytes(n_reads) bytes for the literals decoded beside the walk (zstd_ref_lit_units() records per
+// read; ref.lit_units: how many of them this call fills -- blocks per frame that get a workgroup).
+// dbg (nullable): phase cycle counters of the one-wavefront decoder, which then decodes EVERY frame (walked chains included).
+struct RefWork
+{
+    void *pre = nullptr, *tables = nullptr, *recs = nullptr;
+    uint64_t recs_cap = 0;   // records of 16 bytes
+    void* lits = nullptr;
+    uint32_t lit_units = 0;
+};
+struct FastDecodeArgs
+{
+    uint32_t toosmall_code = 0;
+    const void* seq_dtables = nullptr;
+    void* meta = nullptr;
+    RefWork ref;
+    unsigned long long* dbg = nullptr;
+    FastSide side;
+};
+hipError_t launch_zstd_decode_fast(const ReadBatch& b, const FastDecodeArgs& a, hipStream_t s);
 size_t zstd_ref_lit_meta_bytes(uint32_t n_reads);
 uint32_t zstd_ref_lit_units();
 const uint32_t* zstd_ref_lit_skip(const void* lit_meta, uint32_t n_reads);   // (diagnostics: 0 = the scan made the block a unit)
@@ -306,12 +363,19 @@ size_t seq_dtables_bytes();
 void seq_dtables_build(void* host_buffer);
 // The same for batches of few, large reads: frames that carry the encoder's span index are decoded one span per wavefront
 // (verified; anything else, and every error verdict, comes from the ordinary decoder in a second launch gated by redo[]).
-// content_bytes bounds the total frame content.  dspan_desc: max_spans x zstd_dspan_desc_bytes(); dspan_first[n_reads + 1];
-// dspan_count[1]; dspan_status[4 * max_spans]; redo[n_reads].
-size_t zstd_dspan_desc_bytes();
-uint32_t zstd_dspan_max_spans(uint64_t content_bytes, uint32_t n_reads);  // 0: too large
-hipError_t launch_zstd_decode_spans(const ReadBatch& b, uint32_t toosmall_code, const void* seq_dtables, void* dspan_desc, uint32_t* dspan_first,
-                                    uint32_t* dspan_count, uint32_t max_spans, uint32_t* dspan_status, uint32_t* redo, hipStream_t s);
+// content_bytes bounds the total frame content; meta: zstd_dspan_meta_bytes(content_bytes, n_reads) bytes of device scratch, 16-byte
+// aligned (the launcher carves its tables from it).  redo (out): n_reads words inside meta, after the call redo[i] == 0 <=> frame i was
+// decoded as spans.
+struct SpanDecodeArgs
+{
+    uint32_t toosmall_code = 0;
+    const void* seq_dtables = nullptr;
+    uint64_t content_bytes = 0;
+    void* meta = nullptr;
+    const uint32_t* redo = nullptr;
+};
+size_t zstd_dspan_meta_bytes(uint64_t content_bytes, uint32_t n_reads);  // 0: too large
+hipError_t launch_zstd_decode_spans(const ReadBatch& b, SpanDecodeArgs* a, hipStream_t s);
 
 // ---- the zstd content checksum (xxh64.hip) ------------------------------------------------------
 // out[i] = XXH64 (seed 0) of src[off[i] .. off[i] + len[i]); reads with len[i] or skip[i] >= E_FIRST, gate[i] >= GATE_SKIP are left alone (gate, skip
@@ -368,10 +432,28 @@ hipError_t launch_count_nonzero(const uint32_t* a, uint32_t n, uint32_t* out, hi
 hipError_t launch_canon_classify(uint32_t n, const uint32_t* raw_size, const uint32_t* gate, uint32_t min_bytes, uint32_t* gate_small, uint32_t* gate_large,
                                  uint32_t* counts, hipStream_t s);
 // per-read routing: see route_reads_kernel (helpers.hip).  raw_size[i] = the read's raw (decoded) byte count.
-// l_cal / l_row: the routed reads' b.sig.cal / b.sig.row entries (not written when those are NULL).
-hipError_t launch_route_reads(const ReadBatch& b, const uint32_t* raw_size, uint32_t min_bytes, uint32_t max_reads, uint64_t max_bytes, uint32_t* gate_small,
-                              uint64_t* l_src_off, uint32_t* l_src_size, uint64_t* l_dst_off, uint32_t* l_dst_cap, uint32_t* l_gate, uint32_t* l_map,
-                              float2* l_cal, uint64_t* l_row, uint32_t* l_count, uint32_t* cand, hipStream_t s);   // cand: route_cand_words() words of scratch
+// large: the routed reads' table, max_reads entries each (cal / row: their b.sig.cal / b.sig.row entries, not written when those are NULL);
+// map[k] = routed read k's index in b, count: how many there are.  cand: route_cand_words() words of scratch.
+struct RoutedTable
+{
+    uint64_t* src_off = nullptr;
+    uint32_t* src_size = nullptr;
+    uint64_t* dst_off = nullptr;
+    uint32_t *dst_cap = nullptr, *gate = nullptr, *map = nullptr;
+    float2* cal = nullptr;
+    uint64_t* row = nullptr;
+    uint32_t* count = nullptr;
+};
+struct RouteArgs
+{
+    const uint32_t* raw_size = nullptr;
+    uint32_t min_bytes = 0, max_reads = 0;
+    uint64_t max_bytes = 0;
+    uint32_t* gate_small = nullptr;
+    RoutedTable large;
+    uint32_t* cand = nullptr;
+};
+hipError_t launch_route_reads(const ReadBatch& b, const RouteArgs& a, hipStream_t s);
 size_t route_cand_words();
 hipError_t launch_route_results(const uint32_t* l_result, const uint32_t* l_map, const uint32_t* l_count, uint32_t max_reads, uint32_t* result, hipStream_t s);
 // sized decode: read the 4-byte headers -> payload offsets/sizes, original sizes, gate errors (gate_in, nullable: reads that

@@ -2528,20 +2528,33 @@ hipError_t launch_zstd_decode_only(const ReadBatch& b, uint32_t toosmall_code, c
 }
 
 // ---- span mode (few, large reads) ------------------------------------------------------------------------------------------
-size_t zstd_dspan_desc_bytes() { return sizeof(DecSpan); }
-
-uint32_t zstd_dspan_max_spans(uint64_t content_bytes, uint32_t n_reads)
+static uint32_t dspan_max_spans(uint64_t content_bytes, uint32_t n_reads)   // 0: too large
 {
     const uint64_t v = content_bytes / DSPAN_MIN_CONTENT + 5ull * n_reads + 1;
     return v > 0x7FFFFFF0ull ? 0u : (uint32_t)v;
 }
 
-hipError_t launch_zstd_decode_spans(const ReadBatch& b, uint32_t toosmall_code, const void* seq_dtables, void* dspan_desc, uint32_t* dspan_first,
-                                    uint32_t* dspan_count, uint32_t max_spans, uint32_t* dspan_status, uint32_t* redo, hipStream_t s)
+// SpanDecodeArgs::meta: a descriptor and four status words per span, the reads' first spans, the count, and redo[] behind them
+size_t zstd_dspan_meta_bytes(uint64_t content_bytes, uint32_t n_reads)
+{
+    const uint32_t max_spans = dspan_max_spans(content_bytes, n_reads);
+    return max_spans ? (size_t)max_spans * (sizeof(DecSpan) + 16) + ((size_t)n_reads + 2) * 8 + 256 : 0;
+}
+
+hipError_t launch_zstd_decode_spans(const ReadBatch& b, SpanDecodeArgs* a, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    DecSpan* spans = reinterpret_cast<DecSpan*>(dspan_desc);
-    const SeqDTables* dt = reinterpret_cast<const SeqDTables*>(seq_dtables);
+    const uint32_t max_spans = dspan_max_spans(a->content_bytes, b.n_reads);
+    if (!max_spans || !a->meta) return hipErrorInvalidValue;
+    MetaCarver sm(a->meta);
+    DecSpan* spans = reinterpret_cast<DecSpan*>(sm.take<uint8_t>((size_t)max_spans * sizeof(DecSpan)));
+    uint32_t* dspan_first = sm.take<uint32_t>((size_t)b.n_reads + 1);
+    uint32_t* dspan_count = sm.take<uint32_t>(1);
+    uint32_t* dspan_status = sm.take<uint32_t>((size_t)max_spans * 4);
+    uint32_t* redo = sm.take<uint32_t>(b.n_reads);
+    a->redo = redo;
+    const uint32_t toosmall_code = a->toosmall_code;
+    const SeqDTables* dt = reinterpret_cast<const SeqDTables*>(a->seq_dtables);
     hipLaunchKernelGGL(zstd_dspan_plan_kernel, dim3(1), dim3(1024), 0, s, b, max_spans, spans, dspan_first, dspan_count, dspan_status);
     hipLaunchKernelGGL((zstd_decode_kernel<false, true>), dim3(max_spans), dim3(WAVE), 0, s, b, toosmall_code, nullptr, dt, spans, dspan_count, dspan_status,
                        nullptr, RefChains());

@@ -1124,10 +1124,14 @@ bool zstd_ref_literals_enabled() { return ref_lits_ahead() != 0; }
 
 const uint32_t* zstd_fast_redo(const void* meta, uint32_t n_reads) { return fast_meta(const_cast<void*>(meta), n_reads).redo; }
 
-hipError_t launch_zstd_decode_fast(const ReadBatch& b, uint32_t toosmall_code, const void* seq_dtables, void* meta, void* ref_pre, void* ref_tables,
-                                   void* ref_recs, uint64_t ref_recs_cap, void* ref_lits, uint32_t ref_units, unsigned long long* dbg, FastSide side,
-                                   hipStream_t s)
+hipError_t launch_zstd_decode_fast(const ReadBatch& b, const FastDecodeArgs& a, hipStream_t s)
 {
+    const uint32_t toosmall_code = a.toosmall_code, ref_units = a.ref.lit_units;
+    const void* const seq_dtables = a.seq_dtables;
+    void *const meta = a.meta, *const ref_pre = a.ref.pre, *const ref_tables = a.ref.tables, *const ref_recs = a.ref.recs, *const ref_lits = a.ref.lits;
+    const uint64_t ref_recs_cap = a.ref.recs_cap;
+    unsigned long long* const dbg = a.dbg;
+    const FastSide side = a.side;
     const uint32_t n = b.n_reads;
     if (n == 0) return hipSuccess;
     const FastMeta M = fast_meta(meta, n);

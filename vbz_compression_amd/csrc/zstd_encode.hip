@@ -3175,25 +3175,27 @@ __global__ __launch_bounds__(256) void period_probe_kernel(ReadBatch b, const ui
 
 }  // namespace
 
-hipError_t launch_zstd_encode(const ReadBatch& b, const uint32_t* orig_size, uint32_t key_elem, const uint32_t* key_bytes,
-                              uint32_t hdr, unsigned long long* dbg, const uint32_t* src_cap, const void* seq_tables, bool trailers,
-                              uint32_t* deep_d, void* plan_meta, bool staged, bool pre_filled, unsigned long long* plan_dbg, unsigned long long* pack_dbg,
-                              hipStream_t s)
+hipError_t launch_zstd_encode(const ReadBatch& b, const ZstdEncodeArgs& a, hipStream_t s)
 {
+    const uint32_t* const orig_size = a.key.orig_size;
+    const uint32_t key_elem = a.key.key_elem, hdr = a.hdr;
+    const uint32_t* const key_bytes = a.key.key_bytes;
+    const uint32_t* const src_cap = a.runs.src_cap;
+    const bool trailers = a.trailers;
+    uint32_t* const deep_d = a.deep_d;
+    void* const plan_meta = a.plan_meta;
+    bool staged = a.staged, pre_filled = a.pre_filled;
     if (!plan_meta) staged = pre_filled = false;
     const uint32_t tr = (trailers ? ENC_TRAILERS : 0u) | (pre_filled ? ENC_PRE_FILLED : 0u);
     if (b.n_reads == 0) return hipSuccess;
-    const SeqCTables* st = reinterpret_cast<const SeqCTables*>(seq_tables);
+    const SeqCTables* st = reinterpret_cast<const SeqCTables*>(a.runs.seq_tables);
 #ifdef VBZ_EXPERIMENTS   // the timed instantiations (phase cycle counters) are part of the experiments build only
+    unsigned long long *const dbg = a.dbg.frame, *const plan_dbg = a.dbg.plan, *const pack_dbg = a.dbg.pack;
     if (dbg && !plan_meta) {   // phase counters of the whole frame in one launch
         hipLaunchKernelGGL((zstd_encode_kernel<true, false>), dim3(b.n_reads), dim3(WAVE), 0, s, b, orig_size, key_elem, key_bytes, hdr, dbg,
                            src_cap, st, nullptr, nullptr, nullptr, nullptr, nullptr, tr, nullptr, nullptr, nullptr, SpanShared{});
         return hipGetLastError();
     }
-#else
-    dbg = nullptr;
-    plan_dbg = nullptr;
-    pack_dbg = nullptr;
 #endif
     EncPlan* plans = reinterpret_cast<EncPlan*>(plan_meta);
     uint32_t* redo = plans ? reinterpret_cast<uint32_t*>(plans + b.n_reads) : nullptr;
@@ -3229,12 +3231,16 @@ hipError_t launch_zstd_encode(const ReadBatch& b, const uint32_t* orig_size, uin
 size_t zstd_encode_plan_bytes(uint32_t n_reads) { return (size_t)n_reads * (sizeof(EncPlan) + 4) + 256; }   // plans, pstate[]
 
 // ---- the long-repeat matcher in front of span mode ----------------------------------------------------------------------------
-hipError_t launch_zstd_encode_matcher(const ReadBatch& b, const uint32_t* orig_size, uint32_t key_elem, uint32_t hdr, const uint32_t* src_cap,
-                                      const void* seq_tables, bool trailers, uint32_t max_raw, uint32_t* deep_d, const uint32_t* gate_in,
-                                      uint32_t* gate_out, hipStream_t s)
+hipError_t launch_zstd_encode_matcher(const ReadBatch& b, const ZstdEncodeArgs& a, uint32_t max_raw, const uint32_t* gate_in, uint32_t* gate_out,
+                                      hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    const SeqCTables* st = reinterpret_cast<const SeqCTables*>(seq_tables);
+    const uint32_t* const orig_size = a.key.orig_size;
+    const uint32_t key_elem = a.key.key_elem, hdr = a.hdr;
+    const uint32_t* const src_cap = a.runs.src_cap;
+    const bool trailers = a.trailers;
+    uint32_t* const deep_d = a.deep_d;
+    const SeqCTables* st = reinterpret_cast<const SeqCTables*>(a.runs.seq_tables);
     hipLaunchKernelGGL(period_probe_kernel, dim3(b.n_reads), dim3(256), 0, s, b, orig_size, key_elem, hdr, src_cap, max_raw, gate_in, deep_d, gate_out);
     ReadBatch g = b;
     g.gate = gate_in;
@@ -3244,30 +3250,63 @@ hipError_t launch_zstd_encode_matcher(const ReadBatch& b, const uint32_t* orig_s
 }
 
 // ---- span mode (few, large reads) ------------------------------------------------------------------------------------------
-size_t zstd_span_desc_bytes() { return sizeof(EncSpan); }
-size_t zstd_span_region_bytes(uint32_t n_reads) { return (size_t)n_reads * sizeof(SpanRegion); }
 uint32_t zstd_span_shared_bytes(uint64_t stream_bytes) { return stream_bytes < SHSPAN_BATCH_FROM ? SHSPAN_BYTES : 0u; }
 
-uint32_t zstd_span_max_spans(uint64_t stream_bytes, uint32_t n_reads)
+static uint32_t span_max_spans(uint64_t stream_bytes, uint32_t n_reads)   // 0: too large
 {
     const uint64_t v = stream_bytes / (KEYSPAN_BYTES_SHARED / 2) + 4ull * n_reads + 1;  // spans are cut evenly: none is below half its limit
     return v > 0x7FFFFFF0ull ? 0u : (uint32_t)v;
 }
 
-uint64_t zstd_span_tmp_bytes(uint64_t stream_bytes, uint32_t n_reads, uint32_t max_spans)
+uint64_t zstd_span_tmp_bytes(uint64_t stream_bytes, uint32_t n_reads)
 {
     // a span's slot: its bytes + 1/128 + 1 KB, and for a control-byte span 8 bytes per possible sequence (<= 8/RMIN per byte)
-    return stream_bytes + (stream_bytes >> 7) + stream_bytes * 8u / RMIN + (uint64_t)max_spans * 2048u + 4096u;
+    return stream_bytes + (stream_bytes >> 7) + stream_bytes * 8u / RMIN + (uint64_t)span_max_spans(stream_bytes, n_reads) * 2048u + 4096u;
 }
 
-hipError_t launch_zstd_encode_spans(const ReadBatch& b, const uint32_t* orig_size, uint32_t key_elem, uint32_t hdr, const uint32_t* src_cap,
-                                    const void* seq_tables, void* span_desc, uint32_t* span_first, uint32_t* span_count, uint32_t max_spans,
-                                    uint8_t* span_tmp, uint64_t span_tmp_bytes, uint32_t* span_size, uint32_t* span_trail, uint32_t* span_dst,
-                                    bool index_trailer, void* shared_regions, uint32_t shared_span_bytes, hipStream_t s)
+// the tables of a span launch inside SpanEncodeWork::meta: a descriptor and three words of bookkeeping per span, the reads' first spans,
+// the count, and the shared regions (one per read) in front of them
+struct SpanTables
+{
+    SpanRegion* regions;
+    EncSpan* spans;
+    uint32_t *first, *count, *size, *trail, *dst;
+    SpanTables(void* meta, uint32_t n_reads, uint32_t max_spans, bool shared)
+    {
+        MetaCarver sm(meta);
+        regions = shared ? reinterpret_cast<SpanRegion*>(sm.take<uint8_t>((size_t)n_reads * sizeof(SpanRegion))) : nullptr;
+        spans = reinterpret_cast<EncSpan*>(sm.take<uint8_t>((size_t)max_spans * sizeof(EncSpan)));
+        first = sm.take<uint32_t>((size_t)n_reads + 1);
+        count = sm.take<uint32_t>(1);
+        size = sm.take<uint32_t>(max_spans);
+        trail = sm.take<uint32_t>(max_spans);
+        dst = sm.take<uint32_t>(max_spans);
+    }
+};
+
+size_t zstd_span_meta_bytes(uint64_t stream_bytes, uint32_t n_reads, uint32_t shared_span_bytes)
+{
+    const uint32_t max_spans = span_max_spans(stream_bytes, n_reads);
+    if (!max_spans) return 0;
+    return (size_t)max_spans * (sizeof(EncSpan) + 12) + ((size_t)n_reads + 2) * 4 + 256 + (shared_span_bytes ? (size_t)n_reads * sizeof(SpanRegion) + 64 : 0);
+}
+
+hipError_t launch_zstd_encode_spans(const ReadBatch& b, const ZstdEncodeArgs& a, const SpanEncodeWork& w, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
-    EncSpan* spans = reinterpret_cast<EncSpan*>(span_desc);
-    SpanRegion* regions = reinterpret_cast<SpanRegion*>(shared_regions);
+    const uint32_t max_spans = span_max_spans(w.stream_bytes, b.n_reads);
+    if (!max_spans || !w.meta) return hipErrorInvalidValue;
+    const SpanTables T(w.meta, b.n_reads, max_spans, w.shared_span_bytes != 0);
+    const uint32_t* const orig_size = a.key.orig_size;
+    const uint32_t key_elem = a.key.key_elem, hdr = a.hdr, shared_span_bytes = w.shared_span_bytes;
+    const uint32_t* const src_cap = a.runs.src_cap;
+    const void* const seq_tables = a.runs.seq_tables;
+    const bool index_trailer = a.trailers;
+    uint8_t* const span_tmp = w.tmp;
+    const uint64_t span_tmp_bytes = zstd_span_tmp_bytes(w.stream_bytes, b.n_reads);
+    EncSpan* const spans = T.spans;
+    SpanRegion* const regions = T.regions;
+    uint32_t *const span_first = T.first, *const span_count = T.count, *const span_size = T.size, *const span_trail = T.trail, *const span_dst = T.dst;
     hipLaunchKernelGGL(zstd_span_plan_kernel, dim3(1), dim3(1024), 0, s, b.n_reads, b.src_size, orig_size, key_elem, b.gate,
                        (src_cap && seq_tables) ? 1u : 0u, max_spans, span_tmp_bytes, spans, span_first, span_count, regions, shared_span_bytes);
     // (shared tables: the wavefronts behind the spans' are in the table role; the data bytes' spans are packed by the launch behind)
