@@ -278,7 +278,7 @@ VBZ_EXPORT int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* ctx, const vbz_
  * integer_size != 2 return -2 before anything is launched, and vbz_gpu_decompressed_size_batch refuses the options (a row has no header;
  * its sample count is the file's `samples` column).  Calls that take them, with the semantics they document, one batch entry per row:
  * vbz_gpu_compress_batch / vbz_gpu_decompress_batch, vbz_gpu_decompress_signal_batch, vbz_gpu_decompress_chunks_batch, the three
- * normalising calls (a row counts as a read: its chunks and statistics are the row's), and the svb stage entry points with
+ * normalising calls (a row counts as a read: its chunks and statistics are the row's; reads of several rows: the vbz_gpu_pod5_* calls below), and the svb stage entry points with
  * version = VBZ_GPU_VERSION_POD5 (the svb16 stream alone).  Compress slots need dst_cap[i] >= vbz_gpu_pod5_max_compressed_size(samples)
  * = ZSTD_COMPRESSBOUND(svb16_max(n)), pod5's compressed_signal_max_size.  Decode verdicts per row: a zstd failure or frame content longer
  * than svb16_max(n) is VBZ_ZSTD_ERROR; a stream whose length is not K + n + popcount(the first n key bits) is VBZ_STREAMVBYTE_STREAM_ERROR;
@@ -287,6 +287,62 @@ VBZ_EXPORT int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* ctx, const vbz_
  * (batch.pod5_read_layout).  The svb16 stage runs one workgroup per row on every path. */
 #define VBZ_GPU_VERSION_POD5 0x35444F50u
 VBZ_EXPORT uint64_t vbz_gpu_pod5_max_compressed_size(uint32_t samples);
+
+/* POD5 reads of several rows.  A pod5 file cuts a read into signal rows (102 400 samples by default); the four calls below take the rows
+ * as the batch's entries -- one zstd frame each, dst_cap[i] = 2 x the row's samples in the int16 layout, exactly as above -- and a table
+ * that says which rows form a read.  The read's signal is the concatenation of its rows, T = the sum of their samples; its chunks are
+ * vbz_gpu_chunking's for T samples and its statistics those of its T values.  POD5 options only (anything else: -2, nothing launched); all
+ * are asynchronous on the context's stream.
+ * Bit-exactness: a read's chunks and its {shift, scale} are, bit for bit, what vbz_gpu_decompress_chunks[_norm]_batch and
+ * vbz_gpu_signal_norm_batch give for the concatenated signal passed as ONE read (the chunking rules and the statistics above, the multiply
+ * by the rounded reciprocal included); a read of one row is the row-wise call's.
+ * result[i] stays per ROW: the verdict the row-wise call gives (descriptor checks, zstd and stream verdicts; the row's samples x E on
+ * success), except that the chunk check is per READ -- chunk_first[r + 1] - chunk_first[r] != K(T), chunk_first[r] > chunk_first[r + 1]
+ * or chunk_first[r + 1] > chunk_rows, and likewise a read of 2^31 samples or more, gives VBZ_DESTINATION_SIZE_ERROR to EVERY row of the
+ * read, and not one byte of chunks is written for it.  read_result[k] = T x E (E = bytes per stored sample; 2 for the statistics call), or
+ * the error code of the read's first failing row in row order.  A failing row inside a read leaves the read's chunk rows and its
+ * shift_scale entry unspecified; its other rows keep their own verdicts, and other reads are untouched and exact.
+ * first_row is untrusted and fails whole: first_row[0] != 0, a decreasing pair or first_row[n_reads] != batch->n_reads makes every
+ * result[i] and read_result[k] VBZ_INPUT_SIZE_ERROR; no address is formed from the table and nothing in chunks / dst / shift_scale is
+ * written (one launch checks it before any other kernel reads it).
+ * A read without rows, or of empty rows only, has T = 0: no chunk, c = w = 0.  Empty rows anywhere in a read are legal, and row sample
+ * counts need not be multiples of 8.  Nothing outside a read's chunk rows, the rows' slots and the shift_scale entries is written.
+ * -2 (nothing launched): everything the row-wise counterparts refuse, a NULL reads, reserved != 0, a NULL first_row, n_reads > 0 with a
+ * NULL table the call needs (chunk_first, chunks, read_samples, shift_scale of the statistics call), norm with format->offset or
+ * format->scale.
+ * vbz_gpu_pod5_read_samples_batch: read_samples[k] = the sum of the read's row_samples (device, n_rows words); 2^31 or more gives
+ * VBZ_DESTINATION_SIZE_ERROR and a bad first_row VBZ_INPUT_SIZE_ERROR in every entry, both of which vbz_gpu_chunk_layout_batch counts as 0
+ * chunks: its output feeds that call unchanged (chunk_first has n_reads + 1 entries, chunk_info names reads).
+ * vbz_gpu_pod5_decompress_chunks_batch: chunk k of read r is row chunk_first[r] + k of chunks.  norm == NULL: format->offset / scale are
+ * per READ (n_reads floats, nullable); norm != NULL: the read's own statistics, format->offset and format->scale must be NULL, and
+ * shift_scale (nullable) has n_reads entries.
+ * vbz_gpu_pod5_signal_norm_batch: the statistics alone, per read; result[i] is the int16 decode's for the row.
+ * vbz_gpu_pod5_decompress_signal_norm_batch: every row is decoded into its own typed slot as vbz_gpu_decompress_signal_batch does (adjacent
+ * slots under batch.pod5_read_layout make the read contiguous), normalised by its READ's statistics.
+ * How: the rows pass the entropy stage as any batch's (rows are not routed to the large-read path); one launch then
+ * gives every row its place in its read, and the svb16 store -- still one workgroup per row -- places its samples by read position: whole
+ * 16-byte lines for a row that begins at a multiple of 8 samples of its read (every row behind full default-size rows), element by
+ * element otherwise and wherever a line holds samples of two rows.  The counting passes run one workgroup per READ, walking its rows. */
+typedef struct vbz_gpu_pod5_reads
+{
+    uint32_t n_reads;          /* reads the batch's rows form */
+    uint32_t reserved;         /* must be 0 */
+    const uint32_t* first_row; /* device, n_reads + 1 words: read k owns rows first_row[k] ... first_row[k + 1] - 1, in signal order;
+                                  first_row[0] == 0, non-decreasing, first_row[n_reads] == batch->n_reads.  A read may own no row. */
+    uint32_t* read_result;     /* device, n_reads words, nullable: per read, T * E on success, else the error code of its first failing row */
+} vbz_gpu_pod5_reads;          /* 24 bytes */
+VBZ_EXPORT int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* ctx, uint32_t n_rows, const uint32_t* row_samples, const vbz_gpu_pod5_reads* reads,
+                                               uint32_t* read_samples);
+VBZ_EXPORT int vbz_gpu_pod5_decompress_chunks_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                    const vbz_gpu_signal_format* format, const vbz_gpu_chunking* chunking,
+                                                    const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
+                                                    const vbz_gpu_normalization* norm, float* shift_scale);
+VBZ_EXPORT int vbz_gpu_pod5_signal_norm_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                              uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm,
+                                              float* shift_scale);
+VBZ_EXPORT int vbz_gpu_pod5_decompress_signal_norm_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                         const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
+                                                         const vbz_gpu_normalization* norm, float* shift_scale);
 
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}

@@ -92,6 +92,17 @@ VBZ_GPU_NORM_QUANTILE = 2
 VBZ_GPU_VERSION_POD5 = 0x35444F50   # CompressionOptions.vbz_version of POD5 signal rows (svb16 + zstd; the batched API only)
 
 
+class GpuPod5Reads(ctypes.Structure):
+    """struct vbz_gpu_pod5_reads of include/vbz_gpu.h (24 bytes)."""
+
+    _fields_ = [
+        ("n_reads", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("first_row", ctypes.c_void_p),
+        ("read_result", ctypes.c_void_p),
+    ]
+
+
 class GpuNormalization(ctypes.Structure):
     """struct vbz_gpu_normalization of include/vbz_gpu.h (32 bytes)."""
 
@@ -135,6 +146,10 @@ GPU_API = [
     "vbz_gpu_decompress_signal_norm_batch",
     "vbz_gpu_decompress_chunks_norm_batch",
     "vbz_gpu_pod5_max_compressed_size",
+    "vbz_gpu_pod5_read_samples_batch",
+    "vbz_gpu_pod5_decompress_chunks_batch",
+    "vbz_gpu_pod5_signal_norm_batch",
+    "vbz_gpu_pod5_decompress_signal_norm_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -235,6 +250,19 @@ def load():
     if hasattr(L, "vbz_gpu_pod5_max_compressed_size"):   # (likewise: builds of earlier rounds have no POD5 codec)
         L.vbz_gpu_pod5_max_compressed_size.restype = u64
         L.vbz_gpu_pod5_max_compressed_size.argtypes = [u32]
+    if hasattr(L, "vbz_gpu_pod5_read_samples_batch"):   # (likewise: builds of earlier rounds take POD5 rows one by one)
+        np_ = ctypes.POINTER(GpuNormalization)
+        fp = ctypes.POINTER(GpuSignalFormat)
+        cp = ctypes.POINTER(GpuChunking)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        L.vbz_gpu_pod5_read_samples_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_read_samples_batch.argtypes = [vp, u32, vp, rp, vp]
+        L.vbz_gpu_pod5_decompress_chunks_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_decompress_chunks_batch.argtypes = [vp, bp, op, fp, cp, rp, vp, vp, u64, np_, vp]
+        L.vbz_gpu_pod5_signal_norm_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_signal_norm_batch.argtypes = [vp, bp, op, u32, rp, np_, vp]
+        L.vbz_gpu_pod5_decompress_signal_norm_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_decompress_signal_norm_batch.argtypes = [vp, bp, op, fp, rp, np_, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

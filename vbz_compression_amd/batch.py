@@ -475,6 +475,112 @@ class GpuCodec:
                             signed, norm, norm_out)
         return chunks, chunk_first, chunk_info, result
 
+    # -- POD5 reads of several rows (include/vbz_gpu.h: vbz_gpu_pod5_reads) ---------------------------
+    def _pod5_reads(self, n_rows, read_first_row, read_result):
+        """(the C struct, first_row int32 [n_reads + 1] on the device, read_result) of rows grouped by read_first_row: the first row of
+        every read, ascending from 0 (a tensor or a sequence of n_reads entries; the last read owns the rows up to the end)."""
+        first = torch.as_tensor(read_first_row, dtype=torch.int64).reshape(-1).to(self.device)
+        n_reads = int(first.numel())
+        table = torch.cat([first, torch.tensor([n_rows], dtype=torch.int64, device=self.device)]).to(torch.int32).contiguous()
+        if read_result is None:
+            read_result = torch.empty(n_reads, dtype=torch.int32, device=self.device)
+        assert read_result.dtype == torch.int32 and read_result.is_contiguous() and read_result.device == self.device and int(read_result.numel()) >= n_reads
+        r = _lib.GpuPod5Reads()
+        r.n_reads = n_reads
+        r.first_row = table.data_ptr()
+        r.read_result = read_result.data_ptr()
+        return r, table, read_result
+
+    def _row_layout(self, row_samples):
+        """the int16 layout that describes rows of row_samples samples: (dst_off int64 [n], dst_cap int32 [n], total: a device scalar)"""
+        n = int(row_samples.numel())
+        assert row_samples.dtype == torch.int32 and row_samples.is_contiguous() and row_samples.device == self.device
+        dst_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        if n:
+            dst_off[1:] = torch.cumsum(row_samples.to(torch.int64) * 2, 0)
+        return dst_off, (row_samples.to(torch.int64) * 2).to(torch.int32)
+
+    def pod5_decompress_chunks(self, src, src_off, src_size, row_samples, read_first_row, result, chunk_len, step, mode="pad", end_align=1, pad=0.0,
+                               dtype=torch.float16, scale=None, offset=None, signed=True, norm=None, norm_out=None):
+        """Decode POD5 signal rows, grouped into reads by read_first_row, straight into model-input chunks of the READS (include/vbz_gpu.h:
+        vbz_gpu_pod5_decompress_chunks_batch) -> (chunks [total, chunk_len], chunk_first int64 [n_reads + 1], chunk_info int32 [total, 2] =
+        (read, start sample), read_result int32 [n_reads]).  row_samples: int32 on the device, one per row; result: int32 per ROW.  scale /
+        offset / norm_out are per read.  One synchronisation."""
+        n = int(src_off.numel())
+        assert int(row_samples.numel()) == n
+        opts = pod5_options()
+        ch = self._chunking(chunk_len, step, mode, end_align, pad)
+        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        read_samples = torch.empty(r.n_reads, dtype=torch.int32, device=self.device)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_pod5_read_samples_batch(self.ctx, n, row_samples.data_ptr(), ctypes.byref(r), read_samples.data_ptr()),
+                     "pod5_read_samples_batch")
+        finally:
+            self._exit(cur)
+        chunk_first, chunk_info, host = self._chunk_tables(read_samples, ch, True, also=dst_off[-1])
+        chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
+        assert dtype in self._SIGNAL_TYPES
+        m, ss = self._norm_args(r.n_reads, norm, norm_out, scale, offset) if norm is not None else (None, None)
+        f = self._signal_format(dtype, r.n_reads, scale, offset, signed)
+        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
+        b = self._batch(src, src_off, src_size, no_dst, dst_off[:n], dst_cap, result)
+        b.dst = None
+        b.dst_bytes = int(host[1])
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_pod5_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(ch),
+                                                                 ctypes.byref(r), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
+                                                                 ctypes.byref(m) if m is not None else None, ss), "pod5_decompress_chunks_batch")
+        finally:
+            self._exit(cur)
+        return chunks, chunk_first, chunk_info, read_result
+
+    def pod5_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, shift_scale=None, signed=True):
+        """Every READ's normalisation constants alone (vbz_gpu_pod5_signal_norm_batch) -> (shift_scale float32 [n_reads, 2], read_result)."""
+        n = int(src_off.numel())
+        opts = pod5_options()
+        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        if shift_scale is None:
+            shift_scale = torch.empty((r.n_reads, 2), dtype=torch.float32, device=self.device)
+        m, ss = self._norm_args(r.n_reads, norm, shift_scale, None, None)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
+        b = self._batch(src, src_off, src_size, no_dst, dst_off[:n], dst_cap, result)
+        b.dst = None
+        b.dst_bytes = int(dst_off[-1].item())
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_pod5_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
+                                                           ctypes.byref(m), ss), "pod5_signal_norm_batch")
+        finally:
+            self._exit(cur)
+        return shift_scale, read_result
+
+    def pod5_decompress_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, dtype=torch.float32, signed=True,
+                                    norm_out=None, align=16):
+        """Decode POD5 rows into the contiguous signal of their reads (pod5_read_layout), every row normalised by its READ's statistics
+        (vbz_gpu_pod5_decompress_signal_norm_batch) -> (out: 1-D `dtype`, Pod5Layout in bytes of out, read_result).  row_samples and
+        read_first_row: host sequences or tensors (the layout is computed on the host)."""
+        assert dtype in self._SIGNAL_TYPES, dtype
+        n = int(src_off.numel())
+        opts = pod5_options()
+        elem = torch.empty(0, dtype=dtype).element_size()
+        lay = pod5_read_layout(torch.as_tensor(row_samples).cpu(), torch.as_tensor(read_first_row).cpu(), elem=elem, align=align, device=self.device)
+        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        m, ss = self._norm_args(r.n_reads, norm, norm_out, None, None)
+        f = self._signal_format(dtype, r.n_reads, None, None, signed)
+        out = torch.empty(lay.total // elem + 32, dtype=dtype, device=self.device)
+        b = self._batch(src, src_off, src_size, out.view(torch.uint8), lay.dst_off, lay.dst_cap, result)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_pod5_decompress_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(r),
+                                                                      ctypes.byref(m), ss), "pod5_decompress_signal_norm_batch")
+        finally:
+            self._exit(cur)
+        return out, lay, read_result
+
     # -- synthetic workload (SURVEY.md 8d) ----------------------------------------------------------
     def synth_lengths(self, seed, first_read, n_reads):
         out = torch.empty(n_reads, dtype=torch.int32, device=self.device)

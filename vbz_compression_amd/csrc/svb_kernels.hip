@@ -203,27 +203,22 @@ __device__ __forceinline__ void chunk_shift(const uint32_t a[8], const uint32_t 
     for (int m = 0; m < 8; ++m) o[m] = m + D < 8 ? a[m + D] : n[m + D - 8];
 }
 
-// one lane's eight consecutive samples i0 ... i0 + 7 (i0 a multiple of 8), the first `valid` of them decoded (base + s[j]), into every
-// chunk that holds them.  Every lane of the workgroup calls it at the same point (the END chunk's lines take a cross-lane shuffle).
+// e[0 .. 7]: the output type's bits of a lane's eight samples base + s[j], the pad value behind the first `valid` of them
 template <int OUT>
-__device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int valid, uint32_t base, const uint32_t s[8], const SigK& sk)
+__device__ __forceinline__ void chunk_elems8(const ChunkK& ck, int valid, uint32_t base, const uint32_t s[8], const SigK& sk, uint32_t e[8])
 {
-    constexpr uint32_t OB = OutBytes<OUT>::value;
-    uint32_t e[8];
-    {
-        float f[8];
+    float f[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = sig_f32(base + s[j], sk);
-        if (OB == 4) {
+    for (int j = 0; j < 8; ++j) f[j] = sig_f32(base + s[j], sk);
+    if (OutBytes<OUT>::value == 4) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) e[j] = __float_as_uint(f[j]);
-        } else {
+        for (int j = 0; j < 8; ++j) e[j] = __float_as_uint(f[j]);
+    } else {
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const uint32_t w = sig_pack2<OUT & 3>(f[2 * m], f[2 * m + 1]);
-                e[2 * m] = w & 0xFFFFu;
-                e[2 * m + 1] = w >> 16;
-            }
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t w = sig_pack2<OUT & 3>(f[2 * m], f[2 * m + 1]);
+            e[2 * m] = w & 0xFFFFu;
+            e[2 * m + 1] = w >> 16;
         }
     }
     if (valid < 8) {
@@ -231,6 +226,16 @@ __device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int 
         for (int j = 0; j < 8; ++j)
             if (j >= valid) e[j] = ck.padw;
     }
+}
+
+// one lane's eight consecutive samples i0 ... i0 + 7 (i0 a multiple of 8), the first `valid` of them decoded (base + s[j]), into every
+// chunk that holds them.  Every lane of the workgroup calls it at the same point (the END chunk's lines take a cross-lane shuffle).
+template <int OUT>
+__device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int valid, uint32_t base, const uint32_t s[8], const SigK& sk)
+{
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    uint32_t e[8];
+    chunk_elems8<OUT>(ck, valid, base, s, sk, e);
     // the grid chunks: k = floor(i0 / S) down to the first chunk that still reaches i0
     if (valid > 0) {
         uint32_t k = __umulhi(i0, ck.inv);
@@ -568,7 +573,9 @@ struct DecStore
 
     // b: the batch, for the typed stores only -- SIG_NONE gets nullptr and the batch's fields (a reference to the kernel's ReadBatch
     // argument would cost its loads their scalar form)
-    __device__ __forceinline__ DecStore(uint8_t* dst, const uint64_t* dst_off, const ReadBatch* b, uint32_t r, uint32_t count)
+    __device__ __forceinline__ DecStore(uint8_t* dst, const uint64_t* dst_off, const ReadBatch* b, uint32_t r, uint32_t count) : DecStore(dst, dst_off, b, r, count, r) {}
+    // cr: whose constants (b->sig.cal) the typed store takes -- a POD5 row decoded with its read's
+    __device__ __forceinline__ DecStore(uint8_t* dst, const uint64_t* dst_off, const ReadBatch* b, uint32_t r, uint32_t count, uint32_t cr)
     {
         if (OUT == SIG_NONE) {
             out = dst + dst_off[r];
@@ -599,7 +606,7 @@ struct DecStore
             sk = sig_constants(*b, r);
         } else {
             out = dst + (dst_off[r] >> 1) * BYTES;
-            sk = sig_constants(*b, r);
+            sk = sig_constants(*b, cr);
         }
     }
 
@@ -2231,6 +2238,56 @@ __global__ __launch_bounds__(WG) void svb16_encode_kernel(ReadBatch b, uint32_t*
     if (tid == 0) b.result[r] = K + (uint32_t)(P - A);
 }
 
+// One row's stream (in_size bytes at `in`, K <= in_size <= svb16_max(count)) through st.put(), a tile a trip, by the whole workgroup:
+// whether the stream is exactly as long as its key bits announce.  stage / wsum: the kernel's LDS.  This is svb16_decode_kernel's tile
+// loop for the kernels over reads; that kernel keeps its own text, which as a call of this function compiles to other registers.
+template <class Store>
+__device__ __forceinline__ bool svb16_decode_row(const uint8_t* in, uint32_t in_size, uint32_t count, const Store& st, uint8_t* stage, uint32_t* wsum)
+{
+    const int tid = threadIdx.x;
+    const uint32_t K = (count + 7u) >> 3;
+    const uint8_t* data = in + K;
+    const uint32_t dataBytes = in_size - K;
+    uint64_t pos = 0;   // data bytes consumed
+    uint32_t run = 0;   // the delta chain's running value
+    bool good = true;
+    for (uint32_t t0 = 0; t0 < count; t0 += SVB16_TILE) {
+        const uint32_t i0 = t0 + (uint32_t)tid * 8u;
+        const int valid = i0 >= count ? 0 : (count - i0 >= 8u ? 8 : (int)(count - i0));
+        const uint32_t key = valid > 0 ? (uint32_t)in[i0 >> 3] & ((1u << valid) - 1u) : 0u;   // (unused key bits ignored)
+        const uint32_t L = (uint32_t)valid + (uint32_t)__popc(key);
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan_u32(L, wsum, tot);
+        if (pos + tot > dataBytes) {   // (workgroup-uniform) fewer data bytes than the key bits announce
+            good = false;
+            break;
+        }
+        const uint8_t* g0 = data + pos;
+        const uint32_t mis = (uint32_t)((uintptr_t)g0 & 15u);
+        const uint8_t* ga = g0 - mis;
+        const uint32_t nch = (mis + tot + 15u) >> 4;
+        for (uint32_t c = tid; c < nch; c += WG)
+            *reinterpret_cast<uint4*>(stage + 16u * c) = *reinterpret_cast<const uint4*>(ga + 16ull * c);
+        wg_lds_barrier();
+        uint32_t o = mis + ex, s[8], acc = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t two = (key >> k) & 1u;
+            uint32_t v = stage[o] | (two ? (uint32_t)stage[o + 1] << 8 : 0u);
+            o += 1u + two;
+            v = (v >> 1) ^ (0u - (v & 1u));
+            acc += k < valid ? v : 0u;
+            s[k] = acc;
+        }
+        uint32_t ttot;
+        const uint32_t base = run + block_excl_scan_u32(acc, wsum, ttot);   // (its barriers also keep the next tile's staging behind these reads)
+        run += ttot;
+        st.put(i0, valid, base, s);
+        pos += tot;
+    }
+    return good && pos == dataBytes;
+}
+
 // The verdicts of a POD5 row: content longer than svb16_max(n) is the zstd stage's (E_ZSTD), a stream whose length is not
 // K + n + popcount(the first n key bits) -- bytes missing or left over -- E_STREAM.
 template <int OUT>
@@ -2320,6 +2377,24 @@ __global__ __launch_bounds__(WG) void svb16_key_raw_kernel(uint32_t n, const uin
     key_raw[i] = (uint32_t)std::min<uint64_t>(16u * k, 0xFFFFFFF0ull);
 }
 
+// the first pass's windows: NORM_WINDOWS x NORM_BINS adjacent keys around key a
+__device__ __forceinline__ void norm_first_windows(NormRead* sp, uint32_t a)
+{
+    constexpr uint32_t SPAN = NORM_WINDOWS * NORM_BINS;
+    uint32_t L0 = a < SPAN / 2 ? 0u : a - SPAN / 2;
+    if (L0 > 0x10000u - SPAN) L0 = 0x10000u - SPAN;
+    sp->phase = NORM_VALUE;
+    sp->c2 = 0;
+    sp->anchored = 1;
+#pragma unroll
+    for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
+        sp->lo[w] = L0 + (uint32_t)w * NORM_BINS;
+        sp->sh[w] = 0;
+        sp->a[w] = 0;
+        sp->z[w] = 0xFFFFu;
+    }
+}
+
 // ---- normalising decode: the reads' starting windows, and the select of the large-read path --------------------------------------------
 // One thread per read: the first pass's windows are NORM_WINDOWS x NORM_BINS adjacent keys around the read's first sample, which the
 // stream's first control and data bytes give (any anchor gives the same statistics; a good one saves the later passes).  A read of no
@@ -2345,19 +2420,7 @@ __device__ __forceinline__ void norm_init_read(const ReadBatch& b, uint32_t zigz
         if (zigzag) v = (v >> 1) ^ (0u - (v & 1u));
         a = (v ^ b.sig.bias ^ 0x8000u) & 0xFFFFu;
     }
-    constexpr uint32_t SPAN = NORM_WINDOWS * NORM_BINS;
-    uint32_t L0 = a < SPAN / 2 ? 0u : a - SPAN / 2;
-    if (L0 > 0x10000u - SPAN) L0 = 0x10000u - SPAN;
-    sp->phase = NORM_VALUE;
-    sp->c2 = 0;
-    sp->anchored = 1;
-#pragma unroll
-    for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
-        sp->lo[w] = L0 + (uint32_t)w * NORM_BINS;
-        sp->sh[w] = 0;
-        sp->a[w] = 0;
-        sp->z[w] = 0xFFFFu;
-    }
+    norm_first_windows(sp, a);
 }
 __global__ __launch_bounds__(WG) void norm_init_kernel(ReadBatch b, uint32_t zigzag) { norm_init_read<false>(b, zigzag); }
 __global__ __launch_bounds__(WG) void norm_init16_kernel(ReadBatch b) { norm_init_read<true>(b, 1u); }
@@ -2381,6 +2444,364 @@ __global__ __launch_bounds__(WG) void norm_select_kernel(ReadBatch b)
     }
     __syncthreads();
     norm_select(L, b, r, out_size >> 1, b.sig.bias ^ 0x8000u);
+}
+
+// ---- POD5 reads of several rows (vbz_kernels.h Pod5Reads) ----------------------------------------------------------------
+// The batch's entries stay rows, one workgroup each in the store pass; the plan below tells every row where it lies in its read, and the
+// chunk store and the counting passes then reason about the read: its T samples, its chunks, its constants.
+__global__ __launch_bounds__(WG) void pod5_reads_check_kernel(uint32_t n_rows, Pod5Reads pr)
+{
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i > pr.n_reads) return;
+    const uint32_t v = pr.first_row[i];
+    if ((i == 0 && v != 0) || (i == pr.n_reads ? v != n_rows : v > pr.first_row[i + 1])) *pr.bad = 1u;
+}
+__global__ __launch_bounds__(WG) void pod5_reads_bad_kernel(Pod5Reads pr, uint32_t* out)
+{
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i < pr.n_reads && *pr.bad) out[i] = E_INPUT_SIZE;
+}
+__global__ __launch_bounds__(WG) void pod5_read_samples_kernel(Pod5Reads pr, const uint32_t* row_samples, uint32_t* read_samples)
+{
+    const uint32_t k = blockIdx.x * WG + threadIdx.x;
+    if (k >= pr.n_reads || *pr.bad) return;
+    uint64_t T = 0;
+    for (uint32_t j = pr.first_row[k]; j < pr.first_row[k + 1]; ++j) T += row_samples[j];
+    read_samples[k] = T >> 31 ? E_DESTINATION_SIZE : (uint32_t)T;
+}
+
+// whether row r is to be decoded (*in_size, *count: its stream and its samples); else *verdict is its result (GATE_SKIP: none to write)
+__device__ __forceinline__ bool svb16_row_open(const ReadBatch& b, uint32_t r, uint32_t* in_size, uint32_t* count, uint32_t* verdict)
+{
+    if (b.gate && b.gate[r] >= GATE_SKIP) {
+        *verdict = b.gate[r];
+        return false;
+    }
+    *in_size = b.src_size[r];
+    *verdict = *in_size;
+    if (*in_size >= E_FIRST) return false;   // the previous stage failed for this row
+    const uint32_t out_size = b.dst_cap[r];
+    *verdict = E_DESTINATION_SIZE;
+    if (out_size & 1u) return false;
+    *count = out_size >> 1;
+    const uint32_t K = (*count + 7u) >> 3;
+    *verdict = *in_size < K ? E_STREAM : E_ZSTD;
+    if ((uint64_t)*in_size > (uint64_t)K + 2ull * *count || *in_size < K) return false;
+    *verdict = 0;
+    return *count != 0;   // (an empty stream: nothing to store or count)
+}
+
+// One thread per row and per read.  A bad table closes every row's gate with E_INPUT_SIZE (its result too) and nothing else happens.  Otherwise the read's
+// thread walks its rows: their places (Pod5Row), T, the chunk check (chunk_first is untrusted; 2^31 samples and more fail too) -- a read
+// that fails closes its rows' gates with E_DESTINATION_SIZE -- and the read's constants: the given ones, or (a normalising call) the
+// first pass's windows around the first sample of its first row that has one.
+__global__ __launch_bounds__(WG) void pod5_reads_plan_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale, uint64_t chunk_rows)
+{
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    uint32_t* gate = const_cast<uint32_t*>(b.gate);
+    if (*pr.bad) {
+        if (i < b.n_reads) {
+            gate[i] = b.result[i] = E_INPUT_SIZE;
+            pr.rows[i] = Pod5Row{ 0u, 0u, 0u, 0u };
+        }
+        return;
+    }
+    if (i >= pr.n_reads) return;
+    const uint32_t first = pr.first_row[i], end = pr.first_row[i + 1];
+    uint64_t T64 = 0;
+    uint32_t last_s0 = 0;   // where the last row that has samples begins
+    for (uint32_t j = first; j < end; ++j) {
+        const uint32_t n = b.dst_cap[j] >> 1;
+        pr.rows[j] = Pod5Row{ (uint32_t)T64, i, j + 1u == end && b.sig.row ? POD5_ROW_PAD : 0u, 0u };
+        if (n) last_s0 = (uint32_t)T64;
+        T64 += n;
+    }
+    const uint32_t T = (uint32_t)T64;
+    bool fail = (T64 >> 31) != 0;
+    uint64_t c0 = 0;
+    if (b.sig.row && !fail) {
+        c0 = b.sig.row[i];
+        const uint64_t c1 = b.sig.row[i + 1];
+        fail = c0 > c1 || c1 > chunk_rows || c1 - c0 != chunk_count(T, b.sig.chunk_len, b.sig.step);
+    }
+    if (fail) {
+        for (uint32_t j = first; j < end; ++j) {
+            gate[j] = E_DESTINATION_SIZE;
+            pr.rows[j].flags = 0;
+        }
+        pr.reads[i] = Pod5Read{ 0u, POD5_READ_FAIL, 0ull };
+        if (b.sig.norm.st) b.sig.norm.st[i].phase = NORM_DONE;
+        return;
+    }
+    pr.reads[i] = Pod5Read{ T, (last_s0 & 7u) ? POD5_READ_PAD_ELEMS : 0u, c0 };
+    if (!b.sig.norm.st) {
+        if (b.sig.cal) const_cast<float2*>(b.sig.cal)[i] = make_float2(offset ? offset[i] : 0.0f, scale ? scale[i] : 1.0f);
+        return;
+    }
+    NormRead* sp = b.sig.norm.st + i;
+    if (T == 0) {
+        norm_finish(b, i, 0.0, 0.0);
+        sp->phase = NORM_DONE;
+        return;
+    }
+    uint32_t a = 0x8000u;
+    for (uint32_t j = first; j < end; ++j) {
+        uint32_t in_size, n, verdict;
+        if (!svb16_row_open(b, j, &in_size, &n, &verdict)) continue;
+        const uint32_t K = (n + 7u) >> 3;
+        if (in_size >= K + 2u) {
+            const uint8_t* in = b.src + b.src_off[j];
+            uint32_t v = in[K] | ((in[0] & 1u) ? (uint32_t)in[K + 1] << 8 : 0u);
+            v = (v >> 1) ^ (0u - (v & 1u));
+            a = (v ^ b.sig.bias ^ 0x8000u) & 0xFFFFu;
+        }
+        break;
+    }
+    norm_first_windows(sp, a);
+}
+
+// the sample at position p of the read (its bits e in the output type) into every chunk that holds it
+template <int OUT>
+__device__ __forceinline__ void chunk_put_sample(const ChunkK& ck, uint32_t p, uint32_t e)
+{
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    uint32_t k = __umulhi(p, ck.inv);
+    if (p - k * ck.S >= ck.S) ++k;
+    if (k > ck.nG - 1u) k = ck.nG - 1u;
+    uint32_t off = p - k * ck.S;
+    uint8_t* q = ck.base + (uint64_t)k * ck.row_bytes + (size_t)off * OB;
+    const int64_t back = (int64_t)ck.S * OB - (int64_t)ck.row_bytes;
+    while (off < ck.L) {
+        chunk_put1<OUT>(q, e);
+        if (k == 0) break;
+        --k;
+        off += ck.S;
+        q += back;
+    }
+    if (ck.extra && p >= ck.last && p - ck.last < ck.L) chunk_put1<OUT>(ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes + (size_t)(p - ck.last) * OB, e);
+}
+
+// chunk_store8 for a row of a read: i0 is the lane's position in the READ (a multiple of 8: the row begins at one), re where the row ends
+// there.  A lane stores whole lines only where all eight positions are this workgroup's samples or lie behind the read's end; the row's
+// last group, when later rows go on in the same line, and the END chunk's lines that reach into the next row are stored element by
+// element, each workgroup its own samples, so that no two stores of the launch touch the same bytes.
+template <int OUT>
+__device__ __forceinline__ void chunk_store8_row(const ChunkK& ck, uint32_t i0, int valid, uint32_t re, uint32_t base, const uint32_t s[8], const SigK& sk)
+{
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    uint32_t e[8];
+    chunk_elems8<OUT>(ck, valid, base, s, sk, e);
+    const bool tail = re < ck.T;                          // samples of later rows follow
+    const bool partial = valid > 0 && valid < 8 && tail;   // ... in this lane's line
+    if (partial) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < valid) chunk_put_sample<OUT>(ck, i0 + (uint32_t)j, e[j]);
+    } else if (valid > 0) {   // the grid chunks, as chunk_store8
+        uint32_t k = __umulhi(i0, ck.inv);
+        if (i0 - k * ck.S >= ck.S) ++k;
+        if (k > ck.nG - 1u) k = ck.nG - 1u;
+        uint32_t off = i0 - k * ck.S;
+        uint8_t* p = ck.base + (uint64_t)k * ck.row_bytes + (size_t)off * OB;
+        const int64_t back = (int64_t)ck.S * OB - (int64_t)ck.row_bytes;
+        while (off < ck.L) {
+            chunk_put8<OUT>(p, e);
+            if (k == 0) break;
+            --k;
+            off += ck.S;
+            p += back;
+        }
+    }
+    if (!ck.extra) return;
+    // the END chunk (a partial lane has stored its samples there already)
+    const uint32_t sl = ck.last, d = sl & 7u, g0 = sl - d;
+    uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
+    if (d == 0) {
+        if (!partial && valid > 0 && i0 >= sl && i0 - sl < ck.L) chunk_put8<OUT>(row + (size_t)(i0 - sl) * OB, e);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const bool in = !partial && valid > 0 && i0 >= g0 && i0 - g0 < ck.L && i0 + d < ck.T;   // the line that starts at sample i0 + d
+    const bool in0 = !partial && lane == 0 && valid > 0 && i0 >= g0 + 8u && i0 - 8u - g0 < ck.L;   // lane 0: the line that starts in the group before
+    if (!__any(in || in0)) return;
+    uint32_t n[8];
+    if (OB == 4) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) n[j] = (uint32_t)__shfl_down((int)e[j], 1, 64);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t w = (uint32_t)__shfl_down((int)(e[2 * m] | (e[2 * m + 1] << 16)), 1, 64);
+            n[2 * m] = w & 0xFFFFu;
+            n[2 * m + 1] = w >> 16;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (i0 + 8u + (uint32_t)j >= ck.T) n[j] = ck.padw;
+    if (in) {
+        // whole: the next group is behind the read's end, or the next lane's and all of it this row's
+        if (i0 + 8u >= ck.T || (lane != 63 && !(tail && i0 + 16u > re))) {
+            uint32_t o[8];
+            switch (d) {
+            case 1: chunk_shift<1>(e, n, o); break;
+            case 2: chunk_shift<2>(e, n, o); break;
+            case 3: chunk_shift<3>(e, n, o); break;
+            case 4: chunk_shift<4>(e, n, o); break;
+            case 5: chunk_shift<5>(e, n, o); break;
+            case 6: chunk_shift<6>(e, n, o); break;
+            default: chunk_shift<7>(e, n, o); break;
+            }
+            chunk_put8<OUT>(row + (size_t)(i0 - g0) * OB, o);
+        } else {   // (the rest of the line is stored by whoever holds the next group: lane 0 below, a partial lane, the next row)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if ((uint32_t)j >= d) chunk_put1<OUT>(row + (size_t)(i0 - g0 + (uint32_t)j - d) * OB, e[j]);
+        }
+    }
+    if (in0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if ((uint32_t)j < d) chunk_put1<OUT>(row + (size_t)(i0 + (uint32_t)j - sl) * OB, e[j]);
+    }
+}
+
+// the chunk store of a row of a read: the row's samples at s0 ... s0 + count - 1 of the read's signal
+template <int OUT>
+struct RowChunkStore
+{
+    static constexpr uint32_t BYTES = OutBytes<OUT>::value;
+    ChunkK ck;
+    SigK sk;
+    uint32_t s0, re;
+    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
+    {
+        if ((s0 & 7u) == 0) {
+            chunk_store8_row<OUT>(ck, s0 + i0, valid, re, base, s, sk);
+        } else {   // (the row begins inside a line: every sample on its own)
+            uint32_t e[8];
+            chunk_elems8<OUT>(ck, valid, base, s, sk, e);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < valid) chunk_put_sample<OUT>(ck, s0 + i0 + (uint32_t)j, e[j]);
+        }
+    }
+};
+
+// the read's chunk constants (chunk_constants with the plan's T and first chunk row)
+template <int OUT>
+__device__ __forceinline__ ChunkK chunk_constants_read(const ReadBatch& b, const Pod5Read& rd)
+{
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    ChunkK c;
+    c.T = rd.T;
+    c.L = b.sig.chunk_len;
+    c.S = b.sig.step;
+    c.K = chunk_count(c.T, c.L, c.S);
+    c.last = chunk_last_start(c.T, c.K, c.L, c.S, b.sig.mode, b.sig.end_align);
+    c.extra = b.sig.mode == CHUNK_END && c.K >= 2;
+    c.nG = c.extra ? c.K - 1 : c.K;
+    c.row_bytes = (uint64_t)c.L * OB;
+    c.base = b.dst + rd.row * c.row_bytes;
+    c.inv = (uint32_t)(0x100000000ull / c.S);
+    if (OB == 4) c.padw = __float_as_uint(b.sig.pad);
+    else c.padw = sig_pack2<OUT & 3>(b.sig.pad, b.sig.pad) & 0xFFFFu;
+    return c;
+}
+
+// The store pass over reads: one workgroup per row, OUT a typed or a chunk store.  The read's pad positions are written here, once, by
+// the workgroup of its last row -- before anything can send that workgroup home (an empty row, a closed gate, a failed stream).
+template <int OUT>
+__global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5Reads pr)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+
+    const uint32_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    const Pod5Row rw = pr.rows[r];
+    if ((OUT & SIG_CHUNK) && (rw.flags & POD5_ROW_PAD)) {
+        constexpr uint32_t OB = OutBytes<OUT>::value;
+        const Pod5Read rd = pr.reads[rw.read];
+        const ChunkK ck = chunk_constants_read<OUT>(b, rd);
+        if (ck.K != 0) {
+            uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
+            const uint32_t p0 = ck.T - ck.last, l0 = (p0 + 7u) >> 3;   // the first pad position, the first line of nothing else
+            if ((rd.flags & POD5_READ_PAD_ELEMS) && p0 + (uint32_t)tid < l0 * 8u) chunk_put1<OUT>(row + (size_t)(p0 + (uint32_t)tid) * OB, ck.padw);
+            uint32_t e[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) e[j] = ck.padw;
+            for (uint32_t j = l0 + (uint32_t)tid; j < (ck.L >> 3); j += WG) chunk_put8<OUT>(row + (size_t)j * 8u * OB, e);
+        }
+    }
+    uint32_t in_size = 0, count = 0, verdict;
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
+        if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
+        return;
+    }
+    const uint8_t* in = b.src + b.src_off[r];
+    bool good;
+    if (OUT & SIG_CHUNK) {
+        RowChunkStore<OUT> st;
+        st.ck = chunk_constants_read<OUT>(b, pr.reads[rw.read]);
+        st.sk = sig_constants(b, rw.read);
+        st.s0 = rw.s0;
+        st.re = rw.s0 + count;
+        good = svb16_decode_row(in, in_size, count, st, stage, wsum);
+    } else {
+        const DecStore<2, OUT> st(b.dst, b.dst_off, &b, r, count, rw.read);
+        good = svb16_decode_row(in, in_size, count, st, stage, wsum);
+    }
+    if (tid == 0) b.result[r] = good ? count * OutBytes<OUT>::value : E_STREAM;
+}
+
+// A counting pass over reads: one workgroup per read walks its rows in turn -- the delta chain and the data position restart with every
+// row, the bins and the below-counts carry on -- and selects with the read's histogram in LDS.  verdicts != 0 (the first pass of the
+// statistics alone, which has no store pass): every row's result is written here, the int16 decode's.
+__global__ __launch_bounds__(WG) void svb16_count_reads_kernel(ReadBatch b, Pod5Reads pr, uint32_t verdicts)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+
+    if (*pr.bad) return;
+    const uint32_t k = blockIdx.x;
+    const int tid = threadIdx.x;
+    const uint32_t first = pr.first_row[k], end = pr.first_row[k + 1];
+    if (b.sig.norm.st[k].phase == NORM_DONE) {   // finished (no sample, or failed): no row of it has samples to walk
+        if (!verdicts) return;
+        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) {
+            uint32_t in_size, count, verdict;
+            (void)svb16_row_open(b, r, &in_size, &count, &verdict);
+            if (verdict != GATE_SKIP) b.result[r] = verdict;
+        }
+        return;
+    }
+    const DecStore<2, SIG_COUNT> st(nullptr, nullptr, &b, k, pr.reads[k].T);
+    for (uint32_t r = first; r < end; ++r) {
+        uint32_t in_size = 0, count = 0, verdict;
+        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
+            if (verdicts && tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
+            continue;
+        }
+        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, stage, wsum);
+        if (verdicts && tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
+    }
+    st.done();
+}
+
+// read_result[k]: the code of the read's first failing row, else T * elem
+__global__ __launch_bounds__(WG) void pod5_read_results_kernel(ReadBatch b, Pod5Reads pr, uint32_t elem)
+{
+    const uint32_t k = blockIdx.x * WG + threadIdx.x;
+    if (k >= pr.n_reads || *pr.bad) return;
+    uint32_t v = pr.reads[k].T * elem;
+    for (uint32_t j = pr.first_row[k]; j < pr.first_row[k + 1]; ++j) {
+        if (b.result[j] >= E_FIRST) {
+            v = b.result[j];
+            break;
+        }
+    }
+    pr.read_result[k] = v;
 }
 
 hipError_t launch_norm_init(const ReadBatch& b, bool zigzag, hipStream_t s)
@@ -2567,6 +2988,52 @@ hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s)
         [] { return hipSuccess; }, [&] { return launch1(svb16_decode_kernel<SIG_COUNT>, b, s); }, &store);
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); });
+}
+
+// ---- POD5 reads of several rows -----------------------------------------------------------------------------------------
+hipError_t launch_pod5_reads_check(uint32_t n_rows, const Pod5Reads& pr, uint32_t* out, hipStream_t s)
+{
+    (void)hipMemsetAsync(pr.bad, 0, 4, s);
+    hipLaunchKernelGGL(pod5_reads_check_kernel, dim3(pr.n_reads / WG + 1), dim3(WG), 0, s, n_rows, pr);
+    if (out && pr.n_reads) hipLaunchKernelGGL(pod5_reads_bad_kernel, dim3((pr.n_reads + WG - 1) / WG), dim3(WG), 0, s, pr, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_samples, uint32_t* read_samples, hipStream_t s)
+{
+    if (pr.n_reads == 0) return hipSuccess;
+    hipLaunchKernelGGL(pod5_read_samples_kernel, dim3((pr.n_reads + WG - 1) / WG), dim3(WG), 0, s, pr, row_samples, read_samples);
+    return hipGetLastError();
+}
+
+hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
+                                     hipStream_t s)
+{
+    const uint32_t most = std::max(b.n_reads, pr.n_reads);
+    if (most == 0) return hipSuccess;
+    if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st) || b.sig.norm.slab) return hipErrorInvalidValue;
+    const dim3 rows(b.n_reads), reads(pr.n_reads), t(WG);
+    hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
+    const bool store = b.sig.type != SIG_NONE;
+    if (b.sig.norm.st && pr.n_reads)
+        for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p)
+            hipLaunchKernelGGL(svb16_count_reads_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (b.n_reads) {
+        if (store) {
+            e = svb_dispatch_store(b, [&](auto out) {
+                if constexpr (out() != SIG_NONE) hipLaunchKernelGGL(svb16_decode_rows_kernel<out()>, rows, t, 0, s, b, pr);
+                return hipGetLastError();
+            });
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (pr.read_result && pr.n_reads) {
+        const uint32_t elem = b.sig.type == SIG_F32 ? 4u : 2u;
+        hipLaunchKernelGGL(pod5_read_results_kernel, dim3((pr.n_reads + WG - 1) / WG), t, 0, s, b, pr, elem);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_svb16_key_raw(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw, hipStream_t s)

@@ -108,6 +108,7 @@ struct vbz_gpu_ctx
     DevBuf chunkmeta;          // chunk layout: the per-read chunk counts
     DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
+    DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables (Pod5Reads), the reads' constants
     int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
     bool zero_run_sequences = true;
     bool long_repeats = true;  // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance
@@ -424,6 +425,7 @@ struct Preplanned
     void* scratch = nullptr;
     uint64_t* svb_off = nullptr;
     uint32_t *svb_cap = nullptr, *gate = nullptr;
+    uint32_t* svb_size = nullptr;   // (nullable) where the halves leave their streams' sizes: one table for a stage behind the join
 };
 
 // The content checksum of the frames of an entropy stage (vbz_gpu_set_checksum), in two launches of its own around the stage, whatever
@@ -510,6 +512,7 @@ int plan_stage_scratch(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* size
         p->m.svb_off = pre->svb_off;
         p->m.svb_cap = pre->svb_cap;
         p->m.gate = pre->gate;
+        if (pre->svb_size) p->m.svb_size = pre->svb_size;
         p->planned = true;
     }
     const ScratchPlan splan = { p->num, p->den, c->scratch.cap, p->m.svb_off, p->m.svb_cap, p->m.gate };
@@ -813,8 +816,9 @@ int svb_decode_stage(vbz_gpu_ctx* c, const ReadBatch& d, const CompressionOption
 
 // One launch group of a decompress call: the reads of rb_in (dst_cap = the exact decoded byte counts; those whose gate is closed
 // left alone), on the one-workgroup path or on the large-read path.  dst_bytes: extent of the decoded bytes of the group.
+// streams (nullable; both stages only): the svb stage is the caller's -- *streams is what it decodes (the streams, the group's gate)
 int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes, const CompressionOptions* o, bool segmented,
-                     const Preplanned* pre = nullptr)
+                     const Preplanned* pre = nullptr, ReadBatch* streams = nullptr)
 {
     const uint32_t n = rb_in.n_reads;
     if (n == 0) return 0;
@@ -871,6 +875,10 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     d.src_off = p.m.svb_off;
     d.src_size = p.m.svb_size;
     d.gate = p.m.gate;
+    if (streams) {
+        *streams = d;
+        return 0;
+    }
     return svb_decode_stage(c, d, o, segmented, p.seg);
 }
 
@@ -1001,7 +1009,9 @@ struct Split
 };
 
 // raw_size: the reads' raw (decoded) byte counts; num / den as the group would have chosen them
-int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, uint64_t raw_bytes, uint32_t num, uint32_t den, Split* sp)
+// one_sizes: the halves leave their streams' sizes in one table (Preplanned::svb_size)
+int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, uint64_t raw_bytes, uint32_t num, uint32_t den, Split* sp,
+               bool one_sizes = false)
 {
     const uint32_t n = rb.n_reads;
     if (!c->half) {
@@ -1026,11 +1036,12 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
     k->profiling = c->profiling;
     k->foreign_state = c->foreign_state;
     const size_t scratch_need = (size_t)(((unsigned __int128)raw_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
-    if (!ensure(c, c->scratch, scratch_need) || !ensure(c, c->splitmeta, (size_t)n * 16 + 256)) return -1;
+    if (!ensure(c, c->scratch, scratch_need) || !ensure(c, c->splitmeta, (size_t)n * 20 + 256)) return -1;
     MetaCarver mc(c->splitmeta.p);
     uint64_t* svb_off = mc.take<uint64_t>(n);
     uint32_t* svb_cap = mc.take<uint32_t>(n);
     uint32_t* gate = mc.take<uint32_t>(n);
+    uint32_t* svb_size = mc.take<uint32_t>(n);
     hipStream_t s = c->stream;
     if (rb.gate) HIPCHK(c, hipMemcpyAsync(gate, rb.gate, 4ull * n, hipMemcpyDeviceToDevice, s), "gate copy");
     {
@@ -1045,6 +1056,10 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
     sp->hi.svb_off = svb_off + sp->h;
     sp->hi.svb_cap = svb_cap + sp->h;
     sp->hi.gate = gate + sp->h;
+    if (one_sizes) {
+        sp->lo.svb_size = svb_size;
+        sp->hi.svb_size = svb_size + sp->h;
+    }
     HIPCHK(c, hipEventRecord(c->ev_hfork, s), "event record");
     HIPCHK(c, hipStreamWaitEvent(k->stream, c->ev_hfork, 0), "stream wait");
     return 0;
@@ -1092,17 +1107,19 @@ int compress_split(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t src_bytes, cons
     return rc;
 }
 
-int decompress_split(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t dst_bytes, const CompressionOptions* o)
+// streams (nullable): as for decompress_group -- the halves run the entropy stage, *streams is the whole batch's behind the join
+int decompress_split(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t dst_bytes, const CompressionOptions* o, ReadBatch* streams = nullptr)
 {
     uint32_t num, den;
     svb_factor(o->integer_size, false, &num, &den);
     Split sp;
-    if (split_plan(c, rb, rb.dst_cap, dst_bytes, num, den, &sp) != 0) return -1;
-    ReadBatch lo = rb;
+    if (split_plan(c, rb, rb.dst_cap, dst_bytes, num, den, &sp, streams != nullptr) != 0) return -1;
+    ReadBatch lo = rb, hi_streams;
     lo.n_reads = sp.h;
-    int rc = decompress_group(c, lo, dst_bytes, o, false, &sp.lo);
-    if (rc == 0) rc = decompress_group(c->half, upper_half(rb, sp.h), dst_bytes, o, false, &sp.hi);
+    int rc = decompress_group(c, lo, dst_bytes, o, false, &sp.lo, streams);
+    if (rc == 0) rc = decompress_group(c->half, upper_half(rb, sp.h), dst_bytes, o, false, &sp.hi, streams ? &hi_streams : nullptr);
     if (split_join(c) != 0) rc = -1;
+    if (streams) streams->n_reads = rb.n_reads;   // (the lower half's tables are the whole batch's, cut at h)
     c->last_split = rc == 0;
     return rc;
 }
@@ -1265,7 +1282,27 @@ struct TypedOut
     uint64_t chunk_rows = 0;
     const vbz_gpu_normalization* norm = nullptr;
     float* shift_scale = nullptr;
+    const vbz_gpu_pod5_reads* reads = nullptr;   // POD5 reads of several rows: the constants, chunk_first and shift_scale are per read
 };
+
+// The call's tables over POD5 reads (Pod5Reads) and the reads' constants, from ctx->pod5meta; the check of first_row is queued here, before
+// any other launch of the call (out: read_result or read_samples, nullable -- E_INPUT_SIZE in every entry when the table is bad)
+int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* reads, uint32_t* out, Pod5Reads* pr, float2** cal)
+{
+    const uint32_t R = reads->n_reads;
+    if (!ensure(c, c->pod5meta, (size_t)n_rows * sizeof(Pod5Row) + (size_t)R * (sizeof(Pod5Read) + 8) + 256)) return -1;
+    MetaCarver mc(c->pod5meta.p);
+    pr->n_reads = R;
+    pr->first_row = reads->first_row;
+    pr->read_result = reads->read_result;
+    pr->bad = mc.take<uint32_t>(4);
+    pr->rows = mc.take<Pod5Row>(n_rows);
+    pr->reads = mc.take<Pod5Read>(R);
+    *cal = mc.take<float2>(R);
+    Timed t(c, "pod5_reads_check");
+    HIPCHK(c, launch_pod5_reads_check(n_rows, *pr, out, c->stream), "pod5 reads check launch");
+    return 0;
+}
 
 // out (nullable): a typed decode (signal_slots) or a chunk decode (out->ch)
 int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, bool own_descriptors = false,
@@ -1274,14 +1311,29 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     const uint32_t n = bt->n_reads;
     c->last_frames = 0;
     c->last_span_frames = 0;
-    if (n == 0) return 0;
+    const vbz_gpu_pod5_reads* const reads = out ? out->reads : nullptr;
+    if (n == 0 && !(reads && reads->n_reads)) return 0;
     hipStream_t s = c->stream;
     ReadBatch rb = to_rb(bt);
-    if (!own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
+    Pod5Reads pr;
+    float2* read_cal = nullptr;
+    if (reads && pod5_reads_begin(c, n, reads, reads->read_result, &pr, &read_cal) != 0) return -1;
+    if (n != 0 && !own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
     uint64_t dst_bytes = bt->dst_bytes;
     const bool chunks = out && out->ch;
+    const uint32_t n_const = reads ? reads->n_reads : n;   // how many reads have constants and statistics
     float2* cal = nullptr;   // the per-read constants (a chunk decode: chunk_slots fills them in)
-    if (out && out->f->out_type == SIG_NONE) {   // (the statistics alone: the constants' table is the selects' only)
+    if (reads && (chunks || out->f->out_type == SIG_NONE)) {
+        if (chunks) {
+            rb.dst = (uint8_t*)out->chunks;
+            rb.sig.row = out->chunk_first;
+            rb.sig.chunk_len = out->ch->chunk_len;
+            rb.sig.step = out->ch->step;
+            rb.sig.mode = out->ch->mode;
+            rb.sig.end_align = out->ch->end_align;
+            rb.sig.pad = out->ch->pad;
+        }
+    } else if (out && out->f->out_type == SIG_NONE) {   // (the statistics alone: the constants' table is the selects' only)
         if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
         cal = reinterpret_cast<float2*>(c->sigmeta.p);
     } else if (chunks) {
@@ -1297,17 +1349,18 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     } else if (out && signal_slots(c, bt, out->f, &rb, &dst_bytes, &cal) != 0) {
         return -1;
     }
+    if (reads) cal = read_cal;
     if (out) {
         rb.sig.cal = cal;
         rb.sig.type = out->f->out_type;
         rb.sig.bias = out->f->is_signed ? 0u : 0x8000u;
     }
     if (out && out->norm) {
-        if (!ensure(c, c->normmeta, (size_t)n * (sizeof(NormRead) + 8) + 256)) return -1;
+        if (!ensure(c, c->normmeta, (size_t)n_const * (sizeof(NormRead) + 8) + 256)) return -1;
         MetaCarver mc(c->normmeta.p);
         NormOut& no = rb.sig.norm;
-        no.st = mc.take<NormRead>(n);
-        float2* ss = mc.take<float2>(n);   // (the caller passed no shift_scale: a table of the call's own)
+        no.st = mc.take<NormRead>(n_const);
+        float2* ss = mc.take<float2>(n_const);   // (the caller passed no shift_scale: a table of the call's own)
         no.ss = out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : ss;
         no.method = out->norm->method;
         no.qa = out->norm->quantile_a;
@@ -1338,13 +1391,13 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         rb.dst_cap = orig_size;
         rb.gate = gate;
     }
-    if (chunks) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
+    if (chunks && !reads) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "chunk_slots");
         HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, out->f->offset, out->f->scale, rb.sig.chunk_len, rb.sig.step, out->chunk_first, out->chunk_rows,
                                      cal, const_cast<uint32_t*>(rb.gate), s),
                "chunk slots launch");
     }
-    const bool by_shape = o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
+    const bool by_shape = n != 0 && o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
     if (c->foreign_pending && hipEventQuery(c->ev_foreign) == hipSuccess) {   // what the call before this one found (see foreign_host)
         c->mostly_foreign = 2ull * c->foreign_host[0] > c->foreign_host[1];
         c->foreign_state = c->foreign_host[0] != 0 ? 1 : 0;
@@ -1354,6 +1407,21 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     }
     const bool split = !by_shape && split_applies(c, o, n) && !c->mostly_foreign;
     c->last_split = false;
+    if (reads) {
+        // The rows go through the entropy stage as any batch's (a split call's halves included; rows are not routed: a read's rows meet
+        // again in ONE svb stage behind the join, where the plan, the counting passes over reads and the store see all of them).
+        ReadBatch streams = rb;
+        if (n != 0) {
+            ReadBatch e = rb;
+            e.sig = SignalOut();
+            const int rc = split ? decompress_split(c, e, dst_bytes, o, &streams) : decompress_group(c, e, dst_bytes, o, by_shape, nullptr, &streams);
+            if (rc != 0) return rc;
+            streams.sig = rb.sig;
+        }
+        Timed t(c, "svb_decode");
+        HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s), "svb16_decode (reads) launch");
+        return 0;
+    }
     if (by_shape || !routing_applies(c, o, dst_bytes, n))
         return split ? decompress_split(c, rb, dst_bytes, o) : decompress_group(c, rb, dst_bytes, o, by_shape);
     Routed r;
@@ -1471,7 +1539,7 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
         (void)hipEventDestroy(p.stop);
     }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta, &c->normmeta, &c->normslab })
+    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta, &c->normmeta, &c->normslab, &c->pod5meta })
         if (b->p) (void)hipFree(b->p);
     if (c->large) vbz_gpu_destroy(c->large);
     if (c->half) vbz_gpu_destroy(c->half);
@@ -1688,6 +1756,101 @@ int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt
     DeviceGuard dg(c->device);
     if (!typed_args_ok(c, o, sized, f, "chunk") || !norm_ok(c, norm, f)) return -2;
     return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale);
+}
+
+// ---- POD5 reads of several rows ------------------------------------------------------------------------------------------------------
+static_assert(sizeof(vbz_gpu_pod5_reads) == 24, "vbz_gpu_pod5_reads is 24 bytes");
+static bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_pod5_reads* reads)
+{
+    if (o && !pod5_codec(o)) {
+        set_error(c, "the calls over POD5 reads take POD5 options only");
+        return false;
+    }
+    if (!reads || reads->reserved != 0 || !reads->first_row) {
+        set_error(c, "reads: NULL, reserved not 0 or a NULL first_row");
+        return false;
+    }
+    return true;
+}
+
+int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint32_t* row_samples, const vbz_gpu_pod5_reads* reads, uint32_t* read_samples)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!pod5_reads_ok(c, nullptr, reads)) return -2;
+    if ((n_rows != 0 && !row_samples) || (reads->n_reads != 0 && !read_samples)) {
+        set_error(c, "row_samples or read_samples is NULL");
+        return -2;
+    }
+    Pod5Reads pr;
+    float2* cal;
+    if (pod5_reads_begin(c, n_rows, reads, read_samples, &pr, &cal) != 0) return -1;
+    HIPCHK(c, launch_pod5_read_samples(pr, row_samples, read_samples, c->stream), "pod5 read samples launch");
+    return 0;
+}
+
+int vbz_gpu_pod5_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                         const vbz_gpu_chunking* ch, const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
+                                         uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!typed_args_ok(c, o, 0, f, "chunk") || !pod5_reads_ok(c, o, reads) || (norm && !norm_ok(c, norm, f)) || !chunking_ok(c, ch)) return -2;
+    if (reads->n_reads != 0 && (!chunk_first || !chunks)) {
+        set_error(c, "chunk_first or the chunk arena is NULL");
+        return -2;
+    }
+    if (((uintptr_t)chunks & 15u) != 0) {
+        set_error(c, "the chunk arena is not 16-byte aligned");
+        return -2;
+    }
+    const uint64_t row_bytes = (uint64_t)ch->chunk_len * (f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u);
+    if (chunk_rows > EXTENT_MAX / row_bytes) {
+        set_error(c, "declared chunk arena is not plausible (%llu rows of %llu bytes)", (unsigned long long)chunk_rows, (unsigned long long)row_bytes);
+        return -2;
+    }
+    vbz_gpu_batch b = *bt;   // (batch->dst is not used: the svb stage stores into the chunk arena; without reads nothing is stored)
+    b.dst = chunks ? chunks : (void*)reads->first_row;
+    if (!plausible_extents(c, &b)) return -2;
+    TypedOut out = { f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale };
+    out.reads = reads;
+    return decompress_batch_impl(c, &b, o, 0, false, &out);
+}
+
+int vbz_gpu_pod5_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                   const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
+    const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };
+    if (!typed_args_ok(c, o, 0, &probe, "statistics") || !pod5_reads_ok(c, o, reads) || !norm_ok(c, norm, nullptr)) return -2;
+    if (reads->n_reads != 0 && !shift_scale) {
+        set_error(c, "shift_scale is NULL");
+        return -2;
+    }
+    vbz_gpu_batch b = *bt;   // (batch->dst may be NULL: nothing is stored)
+    if (!b.dst) b.dst = (void*)reads->first_row;
+    if (!plausible_extents(c, &b)) return -2;
+    TypedOut out = { &f };
+    out.norm = norm;
+    out.shift_scale = shift_scale;
+    out.reads = reads;
+    return decompress_batch_impl(c, bt, o, 0, false, &out);
+}
+
+int vbz_gpu_pod5_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                              const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!typed_args_ok(c, o, 0, f, "signal") || !pod5_reads_ok(c, o, reads) || !norm_ok(c, norm, f)) return -2;
+    if (!plausible_extents(c, bt)) return -2;
+    TypedOut out = { f };
+    out.norm = norm;
+    out.shift_scale = shift_scale;
+    out.reads = reads;
+    return decompress_batch_impl(c, bt, o, 0, false, &out);
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

@@ -185,6 +185,43 @@ hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s);
 // key_raw[i]: the raw size whose key region at key_elem = 4 is svb16's ceil(n / 8) bytes (the entropy stage's orig_size for POD5, hdr 0)
 hipError_t launch_svb16_key_raw(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw, hipStream_t s);
 constexpr uint32_t SVB16_KEY_ELEM = 4;
+// POD5 reads of several rows (vbz_gpu_pod5_* of include/vbz_gpu.h): the batch's entries are rows, first_row (untrusted) says which rows
+// form a read, and the chunk store and the counting passes see a read's rows as one signal.  The tables are the call's scratch, filled by
+// the plan launch: row i lies s0 samples into read `read`; the read has T samples, its chunks start at chunk row `row`.
+constexpr uint32_t POD5_ROW_PAD = 1;     // Pod5Row::flags: this row's workgroup writes the read's pad lines (the read's last row)
+constexpr uint32_t POD5_READ_FAIL = 1;   // Pod5Read::flags: the read failed its check (chunk_first, or 2^31 samples and more): nothing of it is stored
+constexpr uint32_t POD5_READ_PAD_ELEMS = 2;   // the line that holds the read's last sample was stored element by element: its pad positions are the pad writer's
+struct Pod5Row
+{
+    uint32_t s0, read, flags, pad;
+};
+struct Pod5Read
+{
+    uint32_t T, flags;
+    uint64_t row;
+};
+struct Pod5Reads
+{
+    uint32_t n_reads = 0;
+    const uint32_t* first_row = nullptr;   // the caller's, n_reads + 1 words; no kernel but the check reads it while *bad is not known to be 0
+    uint32_t* read_result = nullptr;       // the caller's (nullable)
+    Pod5Row* rows = nullptr;               // per row of the batch
+    Pod5Read* reads = nullptr;             // per read
+    uint32_t* bad = nullptr;               // one word: != 0 when first_row is not a partition of the batch's rows
+};
+// *bad = whether first_row is bad (first entry not 0, a decreasing pair, last entry not n_rows); when it is and out != NULL (n_reads words:
+// read_result or read_samples), every out[k] = E_INPUT_SIZE
+hipError_t launch_pod5_reads_check(uint32_t n_rows, const Pod5Reads& pr, uint32_t* out, hipStream_t s);
+// read_samples[k] = the sum of the read's row_samples (2^31 and more: E_DESTINATION_SIZE); behind launch_pod5_reads_check
+hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_samples, uint32_t* read_samples, hipStream_t s);
+// The svb16 stage of a call over reads, behind launch_pod5_reads_check.  b: the rows (src: their svb16 streams; gate: the rows' gate,
+// WRITABLE -- a bad table closes every row's with E_INPUT_SIZE, a read that fails its check its rows' with E_DESTINATION_SIZE), while
+// b.sig.cal, b.sig.row (the caller's chunk_first) and b.sig.norm.st / ss are per READ.  offset / scale (nullable): the reads' given
+// constants (without b.sig.norm.st).  Launches: the plan (tables, checks, constants or the reads' starting windows), the counting passes
+// (one workgroup per read, its rows in turn), the store (one workgroup per row; none for the statistics alone, whose first counting
+// pass gives the rows' verdicts), the read results.
+hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
+                                     hipStream_t s);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
 // bounds the total segment count (the grid); seg_* are scratch arrays of max_segs entries.  Not for the nibble codec.
