@@ -344,6 +344,66 @@ VBZ_EXPORT int vbz_gpu_pod5_decompress_signal_norm_batch(vbz_gpu_ctx* ctx, const
                                                          const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
                                                          const vbz_gpu_normalization* norm, float* shift_scale);
 
+/* Sample ranges.  No caller of the chunk and normalising calls wants the whole read: Bonito trims the start of the signal, then normalises
+ * and chunks signal[trim:]; Dorado normalises over the whole read and drops signal[:trim] before it chunks; Remora and re-squiggle
+ * workflows slice by the ts / ns of an earlier basecall; training loaders cut windows.  The *_range_batch calls below are the chunk and
+ * statistics calls with one more argument, a per-read [begin, end) in samples.
+ * The range: for a read of T samples, e = min(end[i], T), b = min(begin[i], e), T' = e - b.  The tables are untrusted and are clamped,
+ * never refused: begin > end or begin >= T is an empty range, end = 0xFFFFFFFF means "to the end"; no address is formed from a table
+ * value before it is clamped.  A NULL begin is 0 for every read, a NULL end the read's sample count.
+ * Bit-exactness: the read's chunks, and under VBZ_GPU_RANGE_STATS_RANGE its {shift, scale}, are bit for bit what
+ * vbz_gpu_decompress_chunks[_norm]_batch and vbz_gpu_signal_norm_batch give for the signal x[b:e] passed as ONE read of T' samples: the
+ * chunking rules for T' (PAD, and END with end_align), the pad value, the float64 order statistics, the multiply by the rounded
+ * reciprocal; T' == 0: no chunk, c = w = 0.  Under VBZ_GPU_RANGE_STATS_READ the constants are the whole read's (all T values) and only the
+ * chunking sees the range.  Without norm, format->offset and format->scale apply as in the chunk call.
+ * Verdicts do not change: result[i] is what the un-ranged call gives (descriptor checks, sized headers, the zstd and stream verdicts; on
+ * success T x E with T the read's FULL count), and every stream is still walked to its end, so damage behind `end` keeps its verdict.  The
+ * one exception is the chunk check, which is against K(T'): chunk_first entries that are not exactly the range's chunks give
+ * VBZ_DESTINATION_SIZE_ERROR and not one byte of chunks is written for the read.  Nothing outside a read's K(T') chunk rows and its
+ * shift_scale entry is written.
+ * ranges == NULL, or begin and end both NULL, is the un-ranged call (the same kernels).  -2 (nothing launched): everything the
+ * counterpart refuses, reserved != 0, an unknown stats.
+ * vbz_gpu_range_samples_batch: range_samples[i] = T' for samples[i] = T (device tables of n_reads words); a samples[i] of 2^31 or more (an
+ * error code) passes through unchanged, so the output feeds vbz_gpu_chunk_layout_batch as it is, and chunk_info's start samples are then
+ * relative to b.
+ * vbz_gpu_decompress_chunks_range_batch: the arguments of vbz_gpu_decompress_chunks_norm_batch with norm and shift_scale nullable as in
+ * the POD5 chunk call (norm == NULL: the given constants), plus ranges.  vbz_gpu_signal_norm_range_batch: the statistics alone, over the
+ * range (under VBZ_GPU_RANGE_STATS_READ: the un-ranged call).  The two vbz_gpu_pod5_*_range_batch calls are the same over POD5 reads of
+ * several rows: the tables are per READ, in positions of the concatenated signal; result[] stays per row and read_result[] per read, both
+ * as in the un-ranged calls (read_result[k] = T x E with the full T); the chunk check is per read, against K(T').
+ * How: samples outside the range are decoded, because the delta chain needs them, and are neither converted, stored nor
+ * counted.  With b a multiple of 8 a lane's eight samples are still one aligned 16-byte line of the range's signal and the whole-line
+ * stores of the chunk call are kept; any other b stores sample by sample.  Measured on one MI355X, 65 536 reads of ~100 k samples,
+ * L = 10 000, S = 9 504, PAD, float16 (tools/time_ranges.py, profiles/HISTORY.md "Sample ranges"): chunk call 11.7 ms; range call with
+ * [0, T) 12.3 ms, begin = 2 000 12.2 ms, begin = 2 003 16.5 ms; [2 000, T - 2 000) with MED_MAD 18.1 ms (statistics of the range) and
+ * 17.4 ms (of the read) against 16.7 ms un-ranged; int16 decode + torch slice statistics + signal decode + gather 700 ms. */
+#define VBZ_GPU_RANGE_STATS_RANGE 0 /* statistics of the range's samples (Bonito: trim, then normalise) */
+#define VBZ_GPU_RANGE_STATS_READ 1  /* statistics of the whole read (Dorado: normalise, then trim) */
+typedef struct vbz_gpu_sample_ranges
+{
+    const uint32_t* begin; /* device, one word per read, nullable: 0 */
+    const uint32_t* end;   /* device, one word per read, nullable: the read's sample count */
+    uint32_t stats;        /* VBZ_GPU_RANGE_STATS_*; ignored without norm */
+    uint32_t reserved;     /* must be 0 */
+} vbz_gpu_sample_ranges;   /* 24 bytes */
+VBZ_EXPORT int vbz_gpu_range_samples_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const uint32_t* samples, const vbz_gpu_sample_ranges* ranges,
+                                           uint32_t* range_samples);
+VBZ_EXPORT int vbz_gpu_decompress_chunks_range_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                     int sized, const vbz_gpu_signal_format* format, const vbz_gpu_chunking* chunking,
+                                                     const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
+                                                     const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges);
+VBZ_EXPORT int vbz_gpu_signal_norm_range_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                               uint32_t is_signed, const vbz_gpu_normalization* norm, float* shift_scale,
+                                               const vbz_gpu_sample_ranges* ranges);
+VBZ_EXPORT int vbz_gpu_pod5_decompress_chunks_range_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                          const vbz_gpu_signal_format* format, const vbz_gpu_chunking* chunking,
+                                                          const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
+                                                          uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale,
+                                                          const vbz_gpu_sample_ranges* ranges);
+VBZ_EXPORT int vbz_gpu_pod5_signal_norm_range_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                    uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm,
+                                                    float* shift_scale, const vbz_gpu_sample_ranges* ranges);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

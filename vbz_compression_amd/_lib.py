@@ -88,6 +88,8 @@ class GpuChunking(ctypes.Structure):
 
 VBZ_GPU_NORM_MED_MAD = 1
 VBZ_GPU_NORM_QUANTILE = 2
+VBZ_GPU_RANGE_STATS_RANGE = 0   # statistics of the range's samples
+VBZ_GPU_RANGE_STATS_READ = 1    # statistics of the whole read
 
 VBZ_GPU_VERSION_POD5 = 0x35444F50   # CompressionOptions.vbz_version of POD5 signal rows (svb16 + zstd; the batched API only)
 
@@ -115,6 +117,17 @@ class GpuNormalization(ctypes.Structure):
         ("scale_mul", ctypes.c_float),
         ("shift_min", ctypes.c_float),
         ("scale_min", ctypes.c_float),
+    ]
+
+
+class GpuSampleRanges(ctypes.Structure):
+    """struct vbz_gpu_sample_ranges of include/vbz_gpu.h (24 bytes)."""
+
+    _fields_ = [
+        ("begin", ctypes.c_void_p),
+        ("end", ctypes.c_void_p),
+        ("stats", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
     ]
 
 
@@ -150,6 +163,11 @@ GPU_API = [
     "vbz_gpu_pod5_decompress_chunks_batch",
     "vbz_gpu_pod5_signal_norm_batch",
     "vbz_gpu_pod5_decompress_signal_norm_batch",
+    "vbz_gpu_range_samples_batch",
+    "vbz_gpu_decompress_chunks_range_batch",
+    "vbz_gpu_signal_norm_range_batch",
+    "vbz_gpu_pod5_decompress_chunks_range_batch",
+    "vbz_gpu_pod5_signal_norm_range_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -263,6 +281,22 @@ def load():
         L.vbz_gpu_pod5_signal_norm_batch.argtypes = [vp, bp, op, u32, rp, np_, vp]
         L.vbz_gpu_pod5_decompress_signal_norm_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_decompress_signal_norm_batch.argtypes = [vp, bp, op, fp, rp, np_, vp]
+    if hasattr(L, "vbz_gpu_range_samples_batch"):   # (likewise: builds of earlier rounds have no sample ranges)
+        np_ = ctypes.POINTER(GpuNormalization)
+        fp = ctypes.POINTER(GpuSignalFormat)
+        cp = ctypes.POINTER(GpuChunking)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        gp = ctypes.POINTER(GpuSampleRanges)
+        L.vbz_gpu_range_samples_batch.restype = ctypes.c_int
+        L.vbz_gpu_range_samples_batch.argtypes = [vp, u32, vp, gp, vp]
+        L.vbz_gpu_decompress_chunks_range_batch.restype = ctypes.c_int
+        L.vbz_gpu_decompress_chunks_range_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, cp, vp, vp, u64, np_, vp, gp]
+        L.vbz_gpu_signal_norm_range_batch.restype = ctypes.c_int
+        L.vbz_gpu_signal_norm_range_batch.argtypes = [vp, bp, op, ctypes.c_int, u32, np_, vp, gp]
+        L.vbz_gpu_pod5_decompress_chunks_range_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_decompress_chunks_range_batch.argtypes = [vp, bp, op, fp, cp, rp, vp, vp, u64, np_, vp, gp]
+        L.vbz_gpu_pod5_signal_norm_range_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_signal_norm_range_batch.argtypes = [vp, bp, op, u32, rp, np_, vp, gp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -167,11 +167,56 @@ class GpuCodec:
                 norm_out.dtype, norm_out.shape)
         return norm.c_struct(), (norm_out.data_ptr() if norm_out is not None else None)
 
-    def signal_norm(self, src, src_off, src_size, dst_off, dst_cap, result, opts, norm, shift_scale=None, signed=True, sized=False):
+    # -- per-read sample ranges (include/vbz_gpu.h: vbz_gpu_sample_ranges) ---------------------------
+    _RANGE_STATS = {"range": _lib.VBZ_GPU_RANGE_STATS_RANGE, "read": _lib.VBZ_GPU_RANGE_STATS_READ}
+
+    def _range_table(self, n, t):
+        """a begin / end table (a tensor or a sequence of n values 0 ... 0xFFFFFFFF, or None) as int32 on the device (uint32 bits)"""
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
+            w = torch.as_tensor(t, dtype=torch.int64).reshape(-1)
+            t = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+        t = t.to(self.device).contiguous()
+        assert int(t.numel()) == n, (int(t.numel()), n)
+        return t
+
+    def _ranges(self, n, begin, end, stats):
+        """(the C struct or None, the tables it points to) of begin= / end= / stats=; both tables None: the un-ranged call"""
+        if begin is None and end is None:
+            assert stats is None, "stats= goes with begin= / end="
+            return None, ()
+        assert stats is None or stats in self._RANGE_STATS, stats
+        tb, te = self._range_table(n, begin), self._range_table(n, end)
+        g = _lib.GpuSampleRanges()
+        g.begin = tb.data_ptr() if tb is not None else None
+        g.end = te.data_ptr() if te is not None else None
+        g.stats = self._RANGE_STATS[stats or "range"]
+        return g, (tb, te)
+
+    def range_samples(self, samples, begin=None, end=None):
+        """The sample counts of the reads' clamped ranges (include/vbz_gpu.h: vbz_gpu_range_samples_batch): min(end, T) - min(begin, end, T)
+        for T = samples[i] (int32 on the device; 2^31 or more as uint32 passes through) -> int32 [n] on the device; it feeds chunk_layout."""
+        assert samples.dtype == torch.int32 and samples.is_contiguous() and samples.device == self.device, (samples.dtype, samples.device)
+        n = int(samples.numel())
+        g, keep = self._ranges(n, begin, end, None)
+        out = torch.empty(n, dtype=torch.int32, device=self.device)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_range_samples_batch(self.ctx, n, samples.data_ptr(), ctypes.byref(g) if g is not None else None, out.data_ptr()),
+                     "range_samples_batch")
+        finally:
+            self._exit(cur)
+        return out
+
+    def signal_norm(self, src, src_off, src_size, dst_off, dst_cap, result, opts, norm, shift_scale=None, signed=True, sized=False, begin=None,
+                    end=None, stats=None):
         """Every read's normalisation constants alone (include/vbz_gpu.h: vbz_gpu_signal_norm_batch) -> shift_scale, float32 [n, 2] of
         (shift, scale) per read (allocated when None).  dst_off / dst_cap: the int16 layout of the reads (nothing is stored); result[i] is
-        what decompress gives."""
+        what decompress gives.  begin / end (per-read sample positions, clamped; either may be None): the statistics of that range of
+        every read (vbz_gpu_signal_norm_range_batch)."""
         n = int(src_off.numel())
+        g, keep = self._ranges(n, begin, end, stats)
         if shift_scale is None:
             shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
         m, ss = self._norm_args(n, norm, shift_scale, None, None)
@@ -181,8 +226,12 @@ class GpuCodec:
         b.dst_bytes = int(dst_off.max().item() + dst_cap.to(torch.int64).max().item()) if n else 0
         cur = self._enter()
         try:
-            self._rc(self.L.vbz_gpu_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)), ctypes.byref(m), ss),
-                     "signal_norm_batch")
+            if g is None:
+                self._rc(self.L.vbz_gpu_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)), ctypes.byref(m), ss),
+                         "signal_norm_batch")
+            else:
+                self._rc(self.L.vbz_gpu_signal_norm_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)),
+                                                                ctypes.byref(m), ss, ctypes.byref(g)), "signal_norm_range_batch")
         finally:
             self._exit(cur)
         return shift_scale
@@ -414,9 +463,10 @@ class GpuCodec:
         return chunk_first, chunk_info
 
     def _decode_chunks(self, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, ch, chunk_first, chunks, dtype, scale, offset,
-                       signed, norm=None, norm_out=None):
+                       signed, norm=None, norm_out=None, ranges=None):
         assert dtype in self._SIGNAL_TYPES and chunks.dtype == dtype and chunks.is_contiguous(), (dtype, chunks.dtype)
         n = int(src_off.numel())
+        m, ss = None, None
         if norm is not None:
             m, ss = self._norm_args(n, norm, norm_out, scale, offset)
         f = self._signal_format(dtype, n, scale, offset, signed)
@@ -426,7 +476,12 @@ class GpuCodec:
         b.dst_bytes = int(dst_bytes)
         cur = self._enter()
         try:
-            if norm is None:
+            if ranges is not None:
+                self._rc(self.L.vbz_gpu_decompress_chunks_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f),
+                                                                      ctypes.byref(ch), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
+                                                                      ctypes.byref(m) if m is not None else None, ss, ctypes.byref(ranges)),
+                         "decompress_chunks_range_batch")
+            elif norm is None:
                 self._rc(self.L.vbz_gpu_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f), ctypes.byref(ch),
                                                                 chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0])),
                          "decompress_chunks_batch")
@@ -438,41 +493,49 @@ class GpuCodec:
             self._exit(cur)
 
     def decompress_chunks(self, src, src_off, src_size, samples, result, opts, chunk_len, step, mode="pad", end_align=1, pad=0.0, dtype=torch.float16,
-                          scale=None, offset=None, signed=True, norm=None, norm_out=None):
+                          scale=None, offset=None, signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None):
         """Decode unsized int16 reads of `samples` samples (int32 on the device) straight into model-input chunks (include/vbz_gpu.h:
         vbz_gpu_decompress_chunks_batch), calibrated as decompress_signal does -> (chunks [total, chunk_len] of dtype, chunk_first int64
         [n + 1], chunk_info int32 [total, 2]): chunk k of read i is chunks[chunk_first[i] + k] when result[i] is no error code (result[i] =
         samples * element size).  The int16 layout the call describes the reads with is built here; one synchronisation.  norm / norm_out:
-        as for decompress_signal (vbz_gpu_decompress_chunks_norm_batch)."""
+        as for decompress_signal (vbz_gpu_decompress_chunks_norm_batch).  begin / end (per-read sample positions, clamped; either
+        may be None): the chunks are those of that range of every read, chunk_info's start samples relative to its begin, and with norm=
+        the statistics are the range's (stats="range", the default) or the whole read's (stats="read")
+        (vbz_gpu_decompress_chunks_range_batch)."""
         n = int(src_off.numel())
         assert int(samples.numel()) == n
         ch = self._chunking(chunk_len, step, mode, end_align, pad)
+        g, keep = self._ranges(n, begin, end, stats)
         dst_cap = (samples.to(torch.int64) * 2).to(torch.int32)
         dst_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
         if n:
             dst_off[1:] = torch.cumsum(samples.to(torch.int64) * 2, 0)
-        chunk_first, chunk_info, host = self._chunk_tables(samples, ch, True, also=dst_off[-1])
+        laid = samples if g is None else self.range_samples(samples, begin=keep[0], end=keep[1])
+        chunk_first, chunk_info, host = self._chunk_tables(laid, ch, True, also=dst_off[-1])
         chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
         self._decode_chunks(src, src_off, src_size, dst_off[:n], dst_cap, host[1], result, opts, False, ch, chunk_first, chunks, dtype, scale, offset,
-                            signed, norm, norm_out)
+                            signed, norm, norm_out, g)
         return chunks, chunk_first, chunk_info
 
     def decompress_packed_chunks(self, packed, packed_off, packed_size, opts, chunk_len, step, mode="pad", end_align=1, pad=0.0, dtype=torch.float16,
-                                 scale=None, offset=None, signed=True, norm=None, norm_out=None):
+                                 scale=None, offset=None, signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None):
         """decompress_packed into model-input chunks (decompress_chunks): the sample counts come from the headers (decompressed_sizes),
-        then the layout and the decode -> (chunks, chunk_first, chunk_info, result).  One synchronisation."""
+        then the layout and the decode -> (chunks, chunk_first, chunk_info, result).  One synchronisation.  begin / end / stats: as for
+        decompress_chunks."""
         n = int(packed_size.numel())
+        g, keep = self._ranges(n, begin, end, stats)
         src_off = packed_off[:n]
         ch = self._chunking(chunk_len, step, mode, end_align, pad)
         raw_size, raw_off = self.decompressed_sizes(packed, src_off, packed_size, opts, 16)   # (int16 bytes, 16-byte aligned)
         err = (raw_size < 0) & (raw_size >= _lib.VBZ_DEVICE_ERROR - (1 << 32))
         raw = torch.where(err, torch.zeros_like(raw_size), raw_size)
         samples = torch.where(err, raw_size, raw // 2)   # (an error code: no chunks)
-        chunk_first, chunk_info, host = self._chunk_tables(samples, ch, True, also=raw_off[-1])
+        laid = samples if g is None else self.range_samples(samples.contiguous(), begin=keep[0], end=keep[1])
+        chunk_first, chunk_info, host = self._chunk_tables(laid, ch, True, also=raw_off[-1])
         chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
         result = torch.empty(n, dtype=torch.int32, device=self.device)
         self._decode_chunks(packed, src_off, packed_size, raw_off[:n], raw, host[1], result, opts, True, ch, chunk_first, chunks, dtype, scale, offset,
-                            signed, norm, norm_out)
+                            signed, norm, norm_out, g)
         return chunks, chunk_first, chunk_info, result
 
     # -- POD5 reads of several rows (include/vbz_gpu.h: vbz_gpu_pod5_reads) ---------------------------
@@ -501,16 +564,18 @@ class GpuCodec:
         return dst_off, (row_samples.to(torch.int64) * 2).to(torch.int32)
 
     def pod5_decompress_chunks(self, src, src_off, src_size, row_samples, read_first_row, result, chunk_len, step, mode="pad", end_align=1, pad=0.0,
-                               dtype=torch.float16, scale=None, offset=None, signed=True, norm=None, norm_out=None):
+                               dtype=torch.float16, scale=None, offset=None, signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None):
         """Decode POD5 signal rows, grouped into reads by read_first_row, straight into model-input chunks of the READS (include/vbz_gpu.h:
         vbz_gpu_pod5_decompress_chunks_batch) -> (chunks [total, chunk_len], chunk_first int64 [n_reads + 1], chunk_info int32 [total, 2] =
         (read, start sample), read_result int32 [n_reads]).  row_samples: int32 on the device, one per row; result: int32 per ROW.  scale /
-        offset / norm_out are per read.  One synchronisation."""
+        offset / norm_out are per read.  One synchronisation.  begin / end / stats: as for decompress_chunks, per READ, in positions
+        of the read's concatenated signal (vbz_gpu_pod5_decompress_chunks_range_batch)."""
         n = int(src_off.numel())
         assert int(row_samples.numel()) == n
         opts = pod5_options()
         ch = self._chunking(chunk_len, step, mode, end_align, pad)
         r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        g, keep = self._ranges(r.n_reads, begin, end, stats)
         read_samples = torch.empty(r.n_reads, dtype=torch.int32, device=self.device)
         dst_off, dst_cap = self._row_layout(row_samples)
         cur = self._enter()
@@ -519,7 +584,8 @@ class GpuCodec:
                      "pod5_read_samples_batch")
         finally:
             self._exit(cur)
-        chunk_first, chunk_info, host = self._chunk_tables(read_samples, ch, True, also=dst_off[-1])
+        laid = read_samples if g is None else self.range_samples(read_samples, begin=keep[0], end=keep[1])
+        chunk_first, chunk_info, host = self._chunk_tables(laid, ch, True, also=dst_off[-1])
         chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
         assert dtype in self._SIGNAL_TYPES
         m, ss = self._norm_args(r.n_reads, norm, norm_out, scale, offset) if norm is not None else (None, None)
@@ -530,18 +596,27 @@ class GpuCodec:
         b.dst_bytes = int(host[1])
         cur = self._enter()
         try:
-            self._rc(self.L.vbz_gpu_pod5_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(ch),
-                                                                 ctypes.byref(r), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
-                                                                 ctypes.byref(m) if m is not None else None, ss), "pod5_decompress_chunks_batch")
+            if g is None:
+                self._rc(self.L.vbz_gpu_pod5_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(ch),
+                                                                     ctypes.byref(r), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
+                                                                     ctypes.byref(m) if m is not None else None, ss), "pod5_decompress_chunks_batch")
+            else:
+                self._rc(self.L.vbz_gpu_pod5_decompress_chunks_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(ch),
+                                                                           ctypes.byref(r), chunk_first.data_ptr(), chunks.data_ptr(),
+                                                                           int(chunks.shape[0]), ctypes.byref(m) if m is not None else None, ss,
+                                                                           ctypes.byref(g)), "pod5_decompress_chunks_range_batch")
         finally:
             self._exit(cur)
         return chunks, chunk_first, chunk_info, read_result
 
-    def pod5_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, shift_scale=None, signed=True):
-        """Every READ's normalisation constants alone (vbz_gpu_pod5_signal_norm_batch) -> (shift_scale float32 [n_reads, 2], read_result)."""
+    def pod5_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, shift_scale=None, signed=True, begin=None,
+                         end=None, stats=None):
+        """Every READ's normalisation constants alone (vbz_gpu_pod5_signal_norm_batch) -> (shift_scale float32 [n_reads, 2], read_result).
+        begin / end: the statistics of that range of every read's concatenated signal (vbz_gpu_pod5_signal_norm_range_batch)."""
         n = int(src_off.numel())
         opts = pod5_options()
         r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        g, keep = self._ranges(r.n_reads, begin, end, stats)
         if shift_scale is None:
             shift_scale = torch.empty((r.n_reads, 2), dtype=torch.float32, device=self.device)
         m, ss = self._norm_args(r.n_reads, norm, shift_scale, None, None)
@@ -552,8 +627,12 @@ class GpuCodec:
         b.dst_bytes = int(dst_off[-1].item())
         cur = self._enter()
         try:
-            self._rc(self.L.vbz_gpu_pod5_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
-                                                           ctypes.byref(m), ss), "pod5_signal_norm_batch")
+            if g is None:
+                self._rc(self.L.vbz_gpu_pod5_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
+                                                               ctypes.byref(m), ss), "pod5_signal_norm_batch")
+            else:
+                self._rc(self.L.vbz_gpu_pod5_signal_norm_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
+                                                                     ctypes.byref(m), ss, ctypes.byref(g)), "pod5_signal_norm_range_batch")
         finally:
             self._exit(cur)
         return shift_scale, read_result

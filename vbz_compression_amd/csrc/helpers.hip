@@ -312,6 +312,37 @@ __global__ void chunk_slots_kernel(uint32_t n, const uint32_t* cap16, const floa
     if (a > z || z > chunk_rows || z - a != chunk_count(cap16[i] / 2u, L, S)) gate[i] = E_DESTINATION_SIZE;
 }
 
+// the same for a ranged call: the chunk check is against the chunks of the range's samples (the tables are clamped in sample_range)
+__global__ void chunk_slots_range_kernel(uint32_t n, const uint32_t* cap16, const float* offset, const float* scale, uint32_t L, uint32_t S,
+                                         const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate, SignalOut sig)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    cal[i] = make_float2(offset ? offset[i] : 0.0f, scale ? scale[i] : 1.0f);
+    if (gate[i] >= GATE_SKIP) return;
+    uint32_t rb, re;
+    sample_range(sig, i, cap16[i] / 2u, &rb, &re);
+    const uint64_t a = chunk_first[i], z = chunk_first[i + 1];
+    if (a > z || z > chunk_rows || z - a != chunk_count(re - rb, L, S)) gate[i] = E_DESTINATION_SIZE;
+}
+
+__global__ void range_samples_kernel(uint32_t n, const uint32_t* samples, const uint32_t* begin, const uint32_t* end, uint32_t* range_samples)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t T = samples[i];
+    if (T >> 31) {
+        range_samples[i] = T;
+        return;
+    }
+    SignalOut sig;
+    sig.rbegin = begin;
+    sig.rend = end;
+    uint32_t rb, re;
+    sample_range(sig, i, T, &rb, &re);
+    range_samples[i] = re - rb;
+}
+
 __global__ void parse_sized_kernel(uint32_t n, const uint8_t* src, const uint64_t* src_off, const uint32_t* src_size,
                                    const uint32_t* dst_cap, const uint32_t* gate_in, uint64_t* pay_off, uint32_t* pay_size, uint32_t* orig_size,
                                    uint32_t* gate)
@@ -538,10 +569,21 @@ hipError_t launch_signal_slots(uint32_t n, const uint64_t* dst_off, const uint32
 }
 
 hipError_t launch_chunk_slots(uint32_t n, const uint32_t* cap16, const float* offset, const float* scale, uint32_t L, uint32_t S,
-                              const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate, hipStream_t s)
+                              const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate, const SignalOut* sig, hipStream_t s)
 {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(chunk_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, cap16, offset, scale, L, S, chunk_first, chunk_rows, cal, gate);
+    if (sig && sig->ranged())
+        hipLaunchKernelGGL(chunk_slots_range_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, cap16, offset, scale, L, S, chunk_first, chunk_rows, cal,
+                           gate, *sig);
+    else
+        hipLaunchKernelGGL(chunk_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, cap16, offset, scale, L, S, chunk_first, chunk_rows, cal, gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_samples(uint32_t n, const uint32_t* samples, const uint32_t* begin, const uint32_t* end, uint32_t* range_samples, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(range_samples_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, samples, begin, end, range_samples);
     return hipGetLastError();
 }
 

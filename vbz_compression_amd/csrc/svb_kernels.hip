@@ -556,9 +556,29 @@ struct NormK
     uint32_t lo[NORM_WINDOWS] = {}, sh[NORM_WINDOWS] = {};
 };
 
+template <int OUT>
+__device__ __forceinline__ void chunk_put_sample(const ChunkK& ck, uint32_t p, uint32_t e);
+
+// the range of a ranged store (OUT & SIG_RANGE; vbz_kernels.h sample_range): positions [b, e) of the read are the store's [0, e - b).
+// s0: where the values handed to put() begin in the read (a POD5 read's counting pass sets it row by row)
+template <bool ON>
+struct RangeK
+{
+};
+template <>
+struct RangeK<true>
+{
+    uint32_t b = 0, e = 0;
+    mutable uint32_t s0 = 0;
+};
+
 // ---- the decoder's output: what svb_decode_range and I16DecPairs store, where, and in how many bytes per value -----------------------
 // OUT = SIG_NONE: the ELEM-byte values into the read's slot (dst + dst_off[r]).  SIG_*: the typed samples of int16 values into the read's
 // typed slot (dst + dst_off[r] / 2 * E: dst_off is the int16 layout's).  SIG_* | SIG_CHUNK: the typed samples into the read's chunks.
+// | SIG_RANGE (the chunk stores and SIG_COUNT): the read is its samples [b, e) -- the others are decoded (the delta chain needs them) and
+// neither converted, stored nor counted.  b a multiple of 8: a lane's eight samples are still one aligned line of the range's signal and
+// go through chunk_store8 at i0 - b, `valid` cut at e; any other b: sample by sample (chunk_put_sample), the pad positions of the line
+// that holds the range's last sample by finish().  Either way every byte of the read's rows has one writer, as in the whole read's store.
 template <int ELEM, int OUT>
 struct DecStore
 {
@@ -570,6 +590,8 @@ struct DecStore
     ChunkK ck;
     NormK nk;                                    // SIG_COUNT
     mutable uint32_t nbelow[NORM_WINDOWS] = {};  // SIG_COUNT: this lane's keys below each window
+    static constexpr bool RANGED = (OUT & SIG_RANGE) != 0;
+    [[no_unique_address]] RangeK<RANGED> rg;     // SIG_RANGE
 
     // b: the batch, for the typed stores only -- SIG_NONE gets nullptr and the batch's fields (a reference to the kernel's ReadBatch
     // argument would cost its loads their scalar form)
@@ -577,9 +599,14 @@ struct DecStore
     // cr: whose constants (b->sig.cal) the typed store takes -- a POD5 row decoded with its read's
     __device__ __forceinline__ DecStore(uint8_t* dst, const uint64_t* dst_off, const ReadBatch* b, uint32_t r, uint32_t count, uint32_t cr)
     {
+        if constexpr (RANGED) {   // the store's read is the range
+            static_assert((OUT & (SIG_CHUNK | SIG_COUNT)) != 0, "ranges: the chunk stores and the counting pass");
+            sample_range(b->sig, r, count, &rg.b, &rg.e);
+            count = rg.e - rg.b;
+        }
         if (OUT == SIG_NONE) {
             out = dst + dst_off[r];
-        } else if (OUT == SIG_COUNT) {   // (all threads of the workgroup: the bins are zeroed here)
+        } else if (OUT & SIG_COUNT) {   // (all threads of the workgroup: the bins are zeroed here)
             out = nullptr;
             const NormRead* sp = b->sig.norm.st + r;
             nk.L = norm_lds();
@@ -616,10 +643,13 @@ struct DecStore
     // one lane's values i0 ... i0 + valid - 1 (base + s[k]).  The chunk store takes every lane of the workgroup at the same point.
     __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[VPL]) const
     {
-        if (OUT == SIG_COUNT) {   // one LDS increment per value: its key's bin
+        if (OUT & SIG_COUNT) {   // one LDS increment per value: its key's bin
 #pragma unroll
             for (int k = 0; k < VPL; ++k) {
                 if (k >= valid) continue;
+                if constexpr (RANGED) {
+                    if (rg.s0 + i0 + (uint32_t)k - rg.b >= rg.e - rg.b) continue;   // (outside [b, e))
+                }
                 const uint32_t u = ((base + s[k]) ^ nk.kx) & 0xFFFFu;
                 const uint32_t key = nk.dev ? (uint32_t)abs((int32_t)(2u * u) - (int32_t)nk.c2) : u;
                 if (nk.anchored) {   // four adjacent windows of width 1
@@ -637,7 +667,20 @@ struct DecStore
                 }
             }
         } else if (OUT & SIG_CHUNK) {
-            chunk_store8<OUT>(ck, i0, valid, base, s, sk);
+            if constexpr (RANGED) {
+                if ((rg.b & 7u) == 0) {   // whole lines of the range's signal
+                    const int v = (i0 < rg.b || i0 >= rg.e) ? 0 : (rg.e - i0 < (uint32_t)valid ? (int)(rg.e - i0) : valid);
+                    chunk_store8<OUT>(ck, i0 - rg.b, v, base, s, sk);
+                } else {
+                    uint32_t e[8];
+                    chunk_elems8<OUT>(ck, valid, base, s, sk, e);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (j < valid && i0 + (uint32_t)j - rg.b < rg.e - rg.b) chunk_put_sample<OUT>(ck, i0 + (uint32_t)j - rg.b, e[j]);
+                }
+            } else {
+                chunk_store8<OUT>(ck, i0, valid, base, s, sk);
+            }
         } else if (OUT != SIG_NONE) {
             if (valid == VPL && aligned()) {
                 sig_store8<OUT>(out + (size_t)i0 * BYTES, base, s, sk);
@@ -679,13 +722,20 @@ struct DecStore
     __device__ __forceinline__ void finish() const
     {
         if (OUT & SIG_CHUNK) chunk_pad<OUT>(ck);
+        if constexpr (RANGED && (OUT & SIG_CHUNK) != 0) {
+            if ((rg.b & 7u) != 0 && ck.K != 0) {   // (sample by sample: the pad positions behind the last sample, up to the lines of chunk_pad)
+                const uint32_t p0 = ck.T - ck.last, l0 = (p0 + 7u) >> 3;
+                if (p0 + threadIdx.x < l0 * 8u)
+                    chunk_put1<OUT>(ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes + (size_t)(p0 + threadIdx.x) * OutBytes<OUT>::value, ck.padw);
+            }
+        }
     }
 
     // after this workgroup's values (svb_decode_range, MODE 0), by the whole workgroup: the counting pass's counts are complete -- a read
     // on one workgroup is selected from LDS, a segment of the large-read path adds them to the read's slab
     __device__ __forceinline__ void done() const
     {
-        if (OUT != SIG_COUNT) return;
+        if (!(OUT & SIG_COUNT)) return;
         const int lane = threadIdx.x & 63;
 #pragma unroll
         for (int w = 0; w < (int)NORM_WINDOWS; ++w) {
@@ -701,6 +751,11 @@ struct DecStore
                 if (v) atomicAdd(slab + i, v);
             }
             if (threadIdx.x < NORM_WINDOWS && nk.L->below[threadIdx.x]) atomicAdd(slab + NORM_WINDOWS * NORM_BINS + threadIdx.x, nk.L->below[threadIdx.x]);
+        } else if (RANGED && nk.T == 0) {   // (an empty range of a read that has samples: c = w = 0, as norm_init_read says for an empty read)
+            if (threadIdx.x == 0) {
+                norm_finish(*nk.b, nk.r, 0.0, 0.0);
+                no.st[nk.r].phase = NORM_DONE;
+            }
         } else {
             norm_select(nk.L, *nk.b, nk.r, nk.T, nk.kx);
         }
@@ -1800,7 +1855,7 @@ __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBa
         if (tid == 0) b.result[r] = res;
         return;
     }
-    if (OUT == SIG_COUNT && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
+    if ((OUT & SIG_COUNT) && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
     const uint32_t count = out_size / ELEM;
     const uint32_t keyLen = (count + 3u) >> 2;
     const uint8_t* in = b.src + b.src_off[r];
@@ -1862,7 +1917,7 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
     if (SELF) {
         if (MODE != 1 && self_total != (uint64_t)(in_size - ((out_size / ELEM + 3u) >> 2))) return;   // the stream is malformed
     } else if (MODE != 1 && b.result[r] >= E_FIRST) return;  // the scan found the stream malformed
-    if (OUT == SIG_COUNT && b.sig.norm.st[r].phase == NORM_DONE) return;
+    if ((OUT & SIG_COUNT) && b.sig.norm.st[r].phase == NORM_DONE) return;
     const uint32_t count = out_size / ELEM;
     const uint32_t keyLen = (count + 3u) >> 2;
     const uint32_t first = k * (uint32_t)SEG;
@@ -2321,7 +2376,7 @@ __global__ __launch_bounds__(WG) void svb16_decode_kernel(ReadBatch b)
         if (tid == 0) b.result[r] = 0;
         return;
     }
-    if (OUT == SIG_COUNT && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
+    if ((OUT & SIG_COUNT) && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
     const uint8_t* in = b.src + b.src_off[r];
     const uint8_t* data = in + K;
     const uint32_t dataBytes = in_size - K;
@@ -2426,12 +2481,26 @@ __global__ __launch_bounds__(WG) void norm_init_kernel(ReadBatch b, uint32_t zig
 __global__ __launch_bounds__(WG) void norm_init16_kernel(ReadBatch b) { norm_init_read<true>(b, 1u); }
 
 // one workgroup per read: the counts the segments added to the read's slab (zeroed again for the next pass) -> the select
-__global__ __launch_bounds__(WG) void norm_select_kernel(ReadBatch b)
+template <bool RANGED>
+__device__ __forceinline__ void norm_select_read(const ReadBatch& b)
 {
     const uint32_t r = blockIdx.x;
     if (b.gate && b.gate[r] >= GATE_SKIP) return;
     const uint32_t in_size = b.src_size[r], out_size = b.dst_cap[r];
     if (in_size >= E_FIRST || (out_size & 1u) || out_size == 0 || b.sig.norm.st[r].phase == NORM_DONE) return;
+    uint32_t T = out_size >> 1;
+    if (RANGED) {   // the ranks are the range's
+        uint32_t rb, re;
+        sample_range(b.sig, r, T, &rb, &re);
+        T = re - rb;
+        if (T == 0) {   // (nothing was counted: c = w = 0, and the slab is zero as it was)
+            if (threadIdx.x == 0) {
+                norm_finish(b, r, 0.0, 0.0);
+                b.sig.norm.st[r].phase = NORM_DONE;
+            }
+            return;
+        }
+    }
     NormLds* L = norm_lds();
     uint32_t* slab = b.sig.norm.slab + (size_t)r * NORM_SLAB;
     for (uint32_t i = threadIdx.x; i < NORM_WINDOWS * NORM_BINS; i += WG) {
@@ -2443,8 +2512,10 @@ __global__ __launch_bounds__(WG) void norm_select_kernel(ReadBatch b)
         slab[NORM_WINDOWS * NORM_BINS + threadIdx.x] = 0;
     }
     __syncthreads();
-    norm_select(L, b, r, out_size >> 1, b.sig.bias ^ 0x8000u);
+    norm_select(L, b, r, T, b.sig.bias ^ 0x8000u);
 }
+__global__ __launch_bounds__(WG) void norm_select_kernel(ReadBatch b) { norm_select_read<false>(b); }
+__global__ __launch_bounds__(WG) void norm_select_range_kernel(ReadBatch b) { norm_select_read<true>(b); }
 
 // ---- POD5 reads of several rows (vbz_kernels.h Pod5Reads) ----------------------------------------------------------------
 // The batch's entries stay rows, one workgroup each in the store pass; the plan below tells every row where it lies in its read, and the
@@ -2495,7 +2566,10 @@ __device__ __forceinline__ bool svb16_row_open(const ReadBatch& b, uint32_t r, u
 // thread walks its rows: their places (Pod5Row), T, the chunk check (chunk_first is untrusted; 2^31 samples and more fail too) -- a read
 // that fails closes its rows' gates with E_DESTINATION_SIZE -- and the read's constants: the given ones, or (a normalising call) the
 // first pass's windows around the first sample of its first row that has one.
-__global__ __launch_bounds__(WG) void pod5_reads_plan_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale, uint64_t chunk_rows)
+// RANGED: the read's clamped range goes to pr.range, the chunk check is against the range's chunks, and the element-wise flag is about the
+// row that holds the range's last sample (rows lie at s0 - b of the range's signal).
+template <bool RANGED>
+__device__ __forceinline__ void pod5_reads_plan(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows)
 {
     const uint32_t i = blockIdx.x * WG + threadIdx.x;
     uint32_t* gate = const_cast<uint32_t*>(b.gate);
@@ -2518,17 +2592,26 @@ __global__ __launch_bounds__(WG) void pod5_reads_plan_kernel(ReadBatch b, Pod5Re
     }
     const uint32_t T = (uint32_t)T64;
     bool fail = (T64 >> 31) != 0;
+    uint32_t rb = 0, re = T;
+    if (RANGED && !fail) {
+        sample_range(b.sig, i, T, &rb, &re);
+        pr.range[i] = make_uint2(rb, re);
+        last_s0 = 0;
+        for (uint32_t j = first; j < end; ++j)   // the row that holds sample e - 1
+            if (pr.rows[j].s0 < re && (b.dst_cap[j] >> 1) != 0) last_s0 = pr.rows[j].s0 - rb;
+    }
     uint64_t c0 = 0;
     if (b.sig.row && !fail) {
         c0 = b.sig.row[i];
         const uint64_t c1 = b.sig.row[i + 1];
-        fail = c0 > c1 || c1 > chunk_rows || c1 - c0 != chunk_count(T, b.sig.chunk_len, b.sig.step);
+        fail = c0 > c1 || c1 > chunk_rows || c1 - c0 != chunk_count(re - rb, b.sig.chunk_len, b.sig.step);
     }
     if (fail) {
         for (uint32_t j = first; j < end; ++j) {
             gate[j] = E_DESTINATION_SIZE;
             pr.rows[j].flags = 0;
         }
+        if (RANGED) pr.range[i] = make_uint2(0u, 0u);
         pr.reads[i] = Pod5Read{ 0u, POD5_READ_FAIL, 0ull };
         if (b.sig.norm.st) b.sig.norm.st[i].phase = NORM_DONE;
         return;
@@ -2558,6 +2641,14 @@ __global__ __launch_bounds__(WG) void pod5_reads_plan_kernel(ReadBatch b, Pod5Re
         break;
     }
     norm_first_windows(sp, a);
+}
+__global__ __launch_bounds__(WG) void pod5_reads_plan_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale, uint64_t chunk_rows)
+{
+    pod5_reads_plan<false>(b, pr, offset, scale, chunk_rows);
+}
+__global__ __launch_bounds__(WG) void pod5_reads_plan_range_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale, uint64_t chunk_rows)
+{
+    pod5_reads_plan<true>(b, pr, offset, scale, chunk_rows);
 }
 
 // the sample at position p of the read (its bits e in the output type) into every chunk that holds it
@@ -2674,9 +2765,23 @@ struct RowChunkStore
     ChunkK ck;
     SigK sk;
     uint32_t s0, re;
+    uint32_t rb = 0, rend = 0;   // OUT & SIG_RANGE: the read's range; ck is the range's, and the row lies at s0 - rb of the range's signal
     __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
     {
-        if ((s0 & 7u) == 0) {
+        if constexpr ((OUT & SIG_RANGE) != 0) {
+            const uint32_t p = s0 + i0;   // the lane's first sample in the read
+            if (((s0 - rb) & 7u) == 0) {   // (p - rb is a multiple of 8: the lane is wholly in front of the range, or starts inside a line of it)
+                const int v = (p < rb || p >= rend) ? 0 : (rend - p < (uint32_t)valid ? (int)(rend - p) : valid);
+                const uint32_t rowend = re < rend ? re : rend;   // where the row's samples end in the range ...
+                chunk_store8_row<OUT>(ck, p - rb, v, rowend > rb ? rowend - rb : 0u, base, s, sk);   // ... in the range's positions
+            } else {
+                uint32_t e[8];
+                chunk_elems8<OUT>(ck, valid, base, s, sk, e);
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j < valid && p + (uint32_t)j - rb < rend - rb) chunk_put_sample<OUT>(ck, p + (uint32_t)j - rb, e[j]);
+            }
+        } else if ((s0 & 7u) == 0) {
             chunk_store8_row<OUT>(ck, s0 + i0, valid, re, base, s, sk);
         } else {   // (the row begins inside a line: every sample on its own)
             uint32_t e[8];
@@ -2722,7 +2827,8 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
     const Pod5Row rw = pr.rows[r];
     if ((OUT & SIG_CHUNK) && (rw.flags & POD5_ROW_PAD)) {
         constexpr uint32_t OB = OutBytes<OUT>::value;
-        const Pod5Read rd = pr.reads[rw.read];
+        Pod5Read rd = pr.reads[rw.read];
+        if (OUT & SIG_RANGE) rd.T = pr.range[rw.read].y - pr.range[rw.read].x;   // (the chunking is the range's)
         const ChunkK ck = chunk_constants_read<OUT>(b, rd);
         if (ck.K != 0) {
             uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
@@ -2743,7 +2849,14 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
     bool good;
     if (OUT & SIG_CHUNK) {
         RowChunkStore<OUT> st;
-        st.ck = chunk_constants_read<OUT>(b, pr.reads[rw.read]);
+        Pod5Read rd = pr.reads[rw.read];
+        if (OUT & SIG_RANGE) {
+            const uint2 g = pr.range[rw.read];
+            st.rb = g.x;
+            st.rend = g.y;
+            rd.T = g.y - g.x;
+        }
+        st.ck = chunk_constants_read<OUT>(b, rd);
         st.sk = sig_constants(b, rw.read);
         st.s0 = rw.s0;
         st.re = rw.s0 + count;
@@ -2758,7 +2871,8 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
 // A counting pass over reads: one workgroup per read walks its rows in turn -- the delta chain and the data position restart with every
 // row, the bins and the below-counts carry on -- and selects with the read's histogram in LDS.  verdicts != 0 (the first pass of the
 // statistics alone, which has no store pass): every row's result is written here, the int16 decode's.
-__global__ __launch_bounds__(WG) void svb16_count_reads_kernel(ReadBatch b, Pod5Reads pr, uint32_t verdicts)
+template <int OUT>
+__device__ __forceinline__ void svb16_count_reads(const ReadBatch& b, const Pod5Reads& pr, uint32_t verdicts)
 {
     __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
     __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
@@ -2776,17 +2890,26 @@ __global__ __launch_bounds__(WG) void svb16_count_reads_kernel(ReadBatch b, Pod5
         }
         return;
     }
-    const DecStore<2, SIG_COUNT> st(nullptr, nullptr, &b, k, pr.reads[k].T);
+    const DecStore<2, OUT> st(nullptr, nullptr, &b, k, pr.reads[k].T);
     for (uint32_t r = first; r < end; ++r) {
         uint32_t in_size = 0, count = 0, verdict;
         if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
             if (verdicts && tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
             continue;
         }
+        if constexpr ((OUT & SIG_RANGE) != 0) st.rg.s0 = pr.rows[r].s0;   // (put() gets positions in the row)
         const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, stage, wsum);
         if (verdicts && tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
     }
     st.done();
+}
+__global__ __launch_bounds__(WG) void svb16_count_reads_kernel(ReadBatch b, Pod5Reads pr, uint32_t verdicts)
+{
+    svb16_count_reads<SIG_COUNT>(b, pr, verdicts);
+}
+__global__ __launch_bounds__(WG) void svb16_count_reads_range_kernel(ReadBatch b, Pod5Reads pr, uint32_t verdicts)
+{
+    svb16_count_reads<SIG_COUNT | SIG_RANGE>(b, pr, verdicts);
 }
 
 // read_result[k]: the code of the read's first failing row, else T * elem
@@ -2834,11 +2957,14 @@ hipError_t svb_dispatch_elem(int integer_size, bool zigzag, F&& f)
     return hipErrorInvalidValue;
 }
 
-// b.sig's store -> f(OUT): OUT = b.sig.type, | SIG_CHUNK with chunk rows (DecStore)
+// b.sig's store -> f(OUT): OUT = b.sig.type, | SIG_CHUNK with chunk rows, | SIG_RANGE with range tables (DecStore; chunk stores only)
 template <class F>
 hipError_t svb_dispatch_store(const ReadBatch& b, F&& f)
 {
-    switch (b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u)) {
+    switch (b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u) | (b.sig.ranged() ? SIG_RANGE : 0u)) {
+    case SIG_F32 | SIG_CHUNK | SIG_RANGE: return f(Int<SIG_F32 | SIG_CHUNK | SIG_RANGE>{});
+    case SIG_F16 | SIG_CHUNK | SIG_RANGE: return f(Int<SIG_F16 | SIG_CHUNK | SIG_RANGE>{});
+    case SIG_BF16 | SIG_CHUNK | SIG_RANGE: return f(Int<SIG_BF16 | SIG_CHUNK | SIG_RANGE>{});
     case SIG_NONE: return f(Int<SIG_NONE>{});
     case SIG_F32: return f(Int<SIG_F32>{});
     case SIG_F16: return f(Int<SIG_F16>{});
@@ -2857,6 +2983,13 @@ hipError_t svb_decode_launch(const ReadBatch& b, int integer_size, bool zigzag, 
     return svb_dispatch_elem<OUT == SIG_NONE>(integer_size, zigzag, [&](auto e, auto z, auto i) {
         return launch1(svb_decode_kernel<e(), z(), i(), OUT>, b, s);
     });
+}
+
+// the counting pass's store -> f(OUT): the range's values alone when the statistics are the range's
+template <class F>
+hipError_t svb_dispatch_count(const ReadBatch& b, F&& f)
+{
+    return b.sig.ranged_stats() ? f(Int<SIG_COUNT | SIG_RANGE>{}) : f(Int<SIG_COUNT>{});
 }
 
 // The pre-passes of a normalising decode (b.sig.norm.st; int16 samples only), in front of the store: init(), `lead` (launches the counting
@@ -2911,9 +3044,10 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
         },
         [&] {   // a counting pass at the storing pass's positions, behind it a select launch
             if constexpr (E == 2) {
-                const hipError_t ec = mode0(Int<SIG_COUNT>{});
+                const hipError_t ec = svb_dispatch_count(b, mode0);
                 if (ec != hipSuccess) return ec;
-                hipLaunchKernelGGL(norm_select_kernel, reads, t, 0, s, b);
+                if (b.sig.ranged_stats()) hipLaunchKernelGGL(norm_select_range_kernel, reads, t, 0, s, b);
+                else hipLaunchKernelGGL(norm_select_kernel, reads, t, 0, s, b);
             }
             return hipGetLastError();
         },
@@ -2962,7 +3096,7 @@ hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, 
     bool store;   // the counting passes (each selects at its end), then the store -- none for the statistics alone
     const hipError_t e = norm_prepasses(
         b, integer_size, false, [&] { return launch_norm_init(b, zigzag, s); }, [] { return hipSuccess; },
-        [&] { return svb_decode_launch<SIG_COUNT>(b, 2, zigzag, s); }, &store);
+        [&] { return svb_dispatch_count(b, [&](auto out) { return svb_decode_launch<out()>(b, 2, zigzag, s); }); }, &store);
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return svb_decode_launch<out()>(b, integer_size, zigzag, s); });
 }
@@ -2985,7 +3119,7 @@ hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s)
             hipLaunchKernelGGL(norm_init16_kernel, dim3((b.n_reads + WG - 1) / WG), dim3(WG), 0, s, b);
             return hipGetLastError();
         },
-        [] { return hipSuccess; }, [&] { return launch1(svb16_decode_kernel<SIG_COUNT>, b, s); }, &store);
+        [] { return hipSuccess; }, [&] { return svb_dispatch_count(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); }); }, &store);
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); });
 }
@@ -3013,11 +3147,15 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
     if (most == 0) return hipSuccess;
     if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st) || b.sig.norm.slab) return hipErrorInvalidValue;
     const dim3 rows(b.n_reads), reads(pr.n_reads), t(WG);
-    hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
+    if (b.sig.ranged() && !pr.range) return hipErrorInvalidValue;
+    if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
+    else hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
     const bool store = b.sig.type != SIG_NONE;
     if (b.sig.norm.st && pr.n_reads)
-        for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p)
-            hipLaunchKernelGGL(svb16_count_reads_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
+        for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p) {
+            if (b.sig.ranged_stats()) hipLaunchKernelGGL(svb16_count_reads_range_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
+            else hipLaunchKernelGGL(svb16_count_reads_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
+        }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (b.n_reads) {

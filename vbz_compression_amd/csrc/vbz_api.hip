@@ -966,6 +966,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
         r->large.sig.norm.st = l_norm;
         r->large.sig.norm.map = r->map;
     }
+    if (rb.sig.ranged()) r->large.sig.rmap = r->map;   // (their ranges: the call's tables, through the map)
     Timed t(c, "route");
     a.raw_size = raw_size;
     a.min_bytes = ROUTE_MIN_BYTES;
@@ -1081,6 +1082,8 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
         u.sig.norm.st += h;
         u.sig.norm.ss += h;
     }
+    if (u.sig.rbegin) u.sig.rbegin += h;
+    if (u.sig.rend) u.sig.rend += h;
     return u;
 }
 
@@ -1283,6 +1286,7 @@ struct TypedOut
     const vbz_gpu_normalization* norm = nullptr;
     float* shift_scale = nullptr;
     const vbz_gpu_pod5_reads* reads = nullptr;   // POD5 reads of several rows: the constants, chunk_first and shift_scale are per read
+    const vbz_gpu_sample_ranges* ranges = nullptr;   // the per-read sample ranges of the *_range_batch calls (per READ with `reads`)
 };
 
 // The call's tables over POD5 reads (Pod5Reads) and the reads' constants, from ctx->pod5meta; the check of first_row is queued here, before
@@ -1290,7 +1294,7 @@ struct TypedOut
 int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* reads, uint32_t* out, Pod5Reads* pr, float2** cal)
 {
     const uint32_t R = reads->n_reads;
-    if (!ensure(c, c->pod5meta, (size_t)n_rows * sizeof(Pod5Row) + (size_t)R * (sizeof(Pod5Read) + 8) + 256)) return -1;
+    if (!ensure(c, c->pod5meta, (size_t)n_rows * sizeof(Pod5Row) + (size_t)R * (sizeof(Pod5Read) + 16) + 256)) return -1;
     MetaCarver mc(c->pod5meta.p);
     pr->n_reads = R;
     pr->first_row = reads->first_row;
@@ -1299,6 +1303,7 @@ int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* 
     pr->rows = mc.take<Pod5Row>(n_rows);
     pr->reads = mc.take<Pod5Read>(R);
     *cal = mc.take<float2>(R);
+    pr->range = mc.take<uint2>(R);
     Timed t(c, "pod5_reads_check");
     HIPCHK(c, launch_pod5_reads_check(n_rows, *pr, out, c->stream), "pod5 reads check launch");
     return 0;
@@ -1354,6 +1359,11 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         rb.sig.cal = cal;
         rb.sig.type = out->f->out_type;
         rb.sig.bias = out->f->is_signed ? 0u : 0x8000u;
+        if (out->ranges) {   // (both tables NULL: the un-ranged call)
+            rb.sig.rbegin = out->ranges->begin;
+            rb.sig.rend = out->ranges->end;
+            rb.sig.rstats = out->ranges->stats;
+        }
     }
     if (out && out->norm) {
         if (!ensure(c, c->normmeta, (size_t)n_const * (sizeof(NormRead) + 8) + 256)) return -1;
@@ -1394,7 +1404,7 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (chunks && !reads) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "chunk_slots");
         HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, out->f->offset, out->f->scale, rb.sig.chunk_len, rb.sig.step, out->chunk_first, out->chunk_rows,
-                                     cal, const_cast<uint32_t*>(rb.gate), s),
+                                     cal, const_cast<uint32_t*>(rb.gate), &rb.sig, s),
                "chunk slots launch");
     }
     const bool by_shape = n != 0 && o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
@@ -1653,10 +1663,22 @@ int vbz_gpu_chunk_layout_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* sampl
     return 0;
 }
 
+// the ranges of a *_range_batch call (nullable: the un-ranged call)
+static_assert(RANGE_STATS_RANGE == VBZ_GPU_RANGE_STATS_RANGE && RANGE_STATS_READ == VBZ_GPU_RANGE_STATS_READ, "the ABI's stats modes");
+static_assert(sizeof(vbz_gpu_sample_ranges) == 24, "vbz_gpu_sample_ranges is 24 bytes");
+static bool ranges_ok(vbz_gpu_ctx* c, const vbz_gpu_sample_ranges* g)
+{
+    if (g && (g->reserved != 0 || g->stats > VBZ_GPU_RANGE_STATS_READ)) {
+        set_error(c, "sample ranges outside their rules (stats %u, reserved %u)", g->stats, g->reserved);
+        return false;
+    }
+    return true;
+}
+
 // the chunk call's own checks and the call (typed_args_ok has passed); norm: a normalising chunk decode
 static int chunks_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
                        const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows, const vbz_gpu_normalization* norm,
-                       float* shift_scale)
+                       float* shift_scale, const vbz_gpu_sample_ranges* ranges = nullptr)
 {
     if (!chunking_ok(c, ch)) return -2;
     if (bt->n_reads != 0 && (!chunk_first || !chunks)) {
@@ -1675,7 +1697,8 @@ static int chunks_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressio
     vbz_gpu_batch b = *bt;   // (batch->dst is not used: the svb stage stores into the chunk arena)
     b.dst = chunks;
     if (!plausible_extents(c, &b)) return -2;
-    const TypedOut out = { f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale };
+    TypedOut out = { f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale };
+    out.ranges = ranges;
     return decompress_batch_impl(c, &b, o, sized, false, &out);
 }
 
@@ -1714,11 +1737,12 @@ static bool norm_ok(vbz_gpu_ctx* c, const vbz_gpu_normalization* m, const vbz_gp
     return true;
 }
 
-int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
-                              const vbz_gpu_normalization* norm, float* shift_scale)
+static int signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                            const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
+    if (!ranges_ok(c, ranges)) return -2;
     const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
     const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };   // (what typed_args_ok checks: options, is_signed)
     if (!typed_args_ok(c, o, sized, &probe, "statistics") || !norm_ok(c, norm, nullptr)) return -2;
@@ -1732,7 +1756,45 @@ int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Com
     TypedOut out = { &f };
     out.norm = norm;
     out.shift_scale = shift_scale;
+    out.ranges = ranges;
     return decompress_batch_impl(c, bt, o, sized, false, &out);
+}
+
+int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                              const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    return signal_norm_call(c, bt, o, sized, is_signed, norm, shift_scale, nullptr);
+}
+
+int vbz_gpu_signal_norm_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                                    const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+{
+    return signal_norm_call(c, bt, o, sized, is_signed, norm, shift_scale, ranges);
+}
+
+int vbz_gpu_range_samples_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* samples, const vbz_gpu_sample_ranges* ranges, uint32_t* range_samples)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!ranges_ok(c, ranges)) return -2;
+    if (n != 0 && (!samples || !range_samples)) {
+        set_error(c, "a table of the range samples call is NULL");
+        return -2;
+    }
+    Timed t(c, "range_samples");
+    HIPCHK(c, launch_range_samples(n, samples, ranges ? ranges->begin : nullptr, ranges ? ranges->end : nullptr, range_samples, c->stream),
+           "range samples launch");
+    return 0;
+}
+
+int vbz_gpu_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                          const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
+                                          const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+{
+    if (!c || !bt) return -1;
+    DeviceGuard dg(c->device);
+    if (!typed_args_ok(c, o, sized, f, "chunk") || (norm && !norm_ok(c, norm, f)) || !ranges_ok(c, ranges)) return -2;
+    return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale, ranges);
 }
 
 int vbz_gpu_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
@@ -1789,12 +1851,13 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
     return 0;
 }
 
-int vbz_gpu_pod5_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
-                                         const vbz_gpu_chunking* ch, const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
-                                         uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale)
+static int pod5_chunks_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                            const vbz_gpu_chunking* ch, const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
+                            uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
+    if (!ranges_ok(c, ranges)) return -2;
     if (!typed_args_ok(c, o, 0, f, "chunk") || !pod5_reads_ok(c, o, reads) || (norm && !norm_ok(c, norm, f)) || !chunking_ok(c, ch)) return -2;
     if (reads->n_reads != 0 && (!chunk_first || !chunks)) {
         set_error(c, "chunk_first or the chunk arena is NULL");
@@ -1814,14 +1877,32 @@ int vbz_gpu_pod5_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt
     if (!plausible_extents(c, &b)) return -2;
     TypedOut out = { f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale };
     out.reads = reads;
+    out.ranges = ranges;
     return decompress_batch_impl(c, &b, o, 0, false, &out);
 }
 
-int vbz_gpu_pod5_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
-                                   const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale)
+int vbz_gpu_pod5_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                         const vbz_gpu_chunking* ch, const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
+                                         uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    return pod5_chunks_call(c, bt, o, f, ch, reads, chunk_first, chunks, chunk_rows, norm, shift_scale, nullptr);
+}
+
+int vbz_gpu_pod5_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                               const vbz_gpu_chunking* ch, const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
+                                               uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale,
+                                               const vbz_gpu_sample_ranges* ranges)
+{
+    return pod5_chunks_call(c, bt, o, f, ch, reads, chunk_first, chunks, chunk_rows, norm, shift_scale, ranges);
+}
+
+static int pod5_signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                 const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
+                                 const vbz_gpu_sample_ranges* ranges)
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
+    if (!ranges_ok(c, ranges)) return -2;
     const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
     const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };
     if (!typed_args_ok(c, o, 0, &probe, "statistics") || !pod5_reads_ok(c, o, reads) || !norm_ok(c, norm, nullptr)) return -2;
@@ -1836,7 +1917,21 @@ int vbz_gpu_pod5_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, cons
     out.norm = norm;
     out.shift_scale = shift_scale;
     out.reads = reads;
+    out.ranges = ranges;
     return decompress_batch_impl(c, bt, o, 0, false, &out);
+}
+
+int vbz_gpu_pod5_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                   const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    return pod5_signal_norm_call(c, bt, o, is_signed, reads, norm, shift_scale, nullptr);
+}
+
+int vbz_gpu_pod5_signal_norm_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                         const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
+                                         const vbz_gpu_sample_ranges* ranges)
+{
+    return pod5_signal_norm_call(c, bt, o, is_signed, reads, norm, shift_scale, ranges);
 }
 
 int vbz_gpu_pod5_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,

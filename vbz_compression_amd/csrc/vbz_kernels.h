@@ -29,6 +29,8 @@ constexpr int PHASE_SLOTS = 12;  // per-read cycle counters of the timed kernel 
 constexpr uint32_t SIG_NONE = 0, SIG_F32 = 1, SIG_F16 = 2, SIG_BF16 = 3;
 constexpr uint32_t SIG_CHUNK = 4;   // (or-ed into the chunk store's type: the svb decoder's OUT, the store DecStore<ELEM, OUT> of its kernels)
 constexpr uint32_t SIG_COUNT = 8;   // the svb decoder's counting pass of a normalising decode (OUT only: it stores nothing)
+constexpr uint32_t SIG_RANGE = 16;  // (or-ed into a chunk store's or the counting pass's OUT: only the samples of SignalOut's per-read range)
+constexpr uint32_t RANGE_STATS_RANGE = 0, RANGE_STATS_READ = 1;   // (= VBZ_GPU_RANGE_STATS_*)
 constexpr uint32_t CHUNK_PAD = 0, CHUNK_END = 1;
 
 // Normalising decode (vbz_gpu_*_norm_batch): every read's {-shift, 1 / scale} are derived on the device from order statistics of its own
@@ -69,7 +71,26 @@ struct SignalOut
     uint32_t chunk_len = 0, step = 0, mode = 0, end_align = 0;
     float pad = 0.0f;
     NormOut norm;
+    // Sample ranges (vbz_gpu_*_range_batch): read i's chunks (and, with rstats == RANGE_STATS_RANGE, its statistics) are those of its
+    // samples [b, e) -- e = min(rend[i], T), b = min(rbegin[i], e); a NULL table: 0 / T -- taken as a read of e - b samples.  The tables
+    // are the caller's (untrusted); entry rmap ? rmap[r] : r is read r's (routed reads: their index in the call's batch; POD5: per READ).
+    const uint32_t* rbegin = nullptr;
+    const uint32_t* rend = nullptr;
+    const uint32_t* rmap = nullptr;
+    uint32_t rstats = RANGE_STATS_RANGE;
+    __host__ __device__ bool ranged() const { return rbegin || rend; }
+    __host__ __device__ bool ranged_stats() const { return ranged() && rstats == RANGE_STATS_RANGE; }
 };
+
+// the clamped range of read r of T samples: *rb <= *re <= T (no address is formed from a table value before this)
+__device__ inline void sample_range(const SignalOut& sg, uint32_t r, uint32_t T, uint32_t* rb, uint32_t* re)
+{
+    const uint32_t i = sg.rmap ? sg.rmap[r] : r;
+    const uint32_t e0 = sg.rend ? sg.rend[i] : T, e = e0 < T ? e0 : T;
+    const uint32_t b0 = sg.rbegin ? sg.rbegin[i] : 0u;
+    *re = e;
+    *rb = b0 < e ? b0 : e;
+}
 
 // the chunking of a read of T samples (include/vbz_gpu.h, vbz_gpu_chunking): K chunks, the last one starting at chunk_last_start
 __host__ __device__ inline uint32_t chunk_count(uint32_t T, uint32_t L, uint32_t S)
@@ -175,6 +196,8 @@ bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half);   // does
 // | SIG_CHUNK with b.sig.row).  b.sig.norm.st (integer_size 2 only; both launchers): the counting passes and their selects run in front of
 // the store and leave every read's constants in b.sig.cal (and b.sig.norm.ss); with b.sig.type == SIG_NONE they are all that runs (the
 // results are the int16 decode's; launch_svb_decode_seg: b.sig.norm.slab must be set).
+// b.sig.rbegin / rend (the chunk stores and the counting passes only; launch_svb16_decode and launch_svb_decode_seg too): the ranged
+// instantiations (OUT | SIG_RANGE) store the chunks of every read's clamped range, and with rstats == RANGE_STATS_RANGE count its values alone.
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s);
 // svb16, the svb stage of POD5 signal rows (int16 samples, delta + zig-zag; one key bit per sample): one workgroup per read, on every
 // path.  Encode: the worst case ceil(n / 8) + 2n must fit dst_cap (else E_DESTINATION_SIZE); period_hint (nullable) is zeroed (no
@@ -208,6 +231,7 @@ struct Pod5Reads
     Pod5Row* rows = nullptr;               // per row of the batch
     Pod5Read* reads = nullptr;             // per read
     uint32_t* bad = nullptr;               // one word: != 0 when first_row is not a partition of the batch's rows
+    uint2* range = nullptr;                // per read, a ranged call only: the clamped {b, e} of SignalOut's range (the plan writes them)
 };
 // *bad = whether first_row is bad (first entry not 0, a decreasing pair, last entry not n_rows); when it is and out != NULL (n_reads words:
 // read_result or read_samples), every out[k] = E_INPUT_SIZE
@@ -219,7 +243,7 @@ hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_sam
 // b.sig.cal, b.sig.row (the caller's chunk_first) and b.sig.norm.st / ss are per READ.  offset / scale (nullable): the reads' given
 // constants (without b.sig.norm.st).  Launches: the plan (tables, checks, constants or the reads' starting windows), the counting passes
 // (one workgroup per read, its rows in turn), the store (one workgroup per row; none for the statistics alone, whose first counting
-// pass gives the rows' verdicts), the read results.
+// pass gives the rows' verdicts), the read results.  b.sig.rbegin / rend: per READ; pr.range must then be set (the plan fills it).
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
                                      hipStream_t s);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
@@ -515,8 +539,11 @@ hipError_t launch_signal_slots(uint32_t n, const uint64_t* dst_off, const uint32
 // the headers' sizes).  cal[i] as in launch_signal_slots; a read whose gate is no error and whose chunk_first entries are not exactly
 // its chunks (chunk_first[i] <= chunk_first[i + 1] <= chunk_rows, the difference chunk_count(cap16[i] / 2, L, S)) gets
 // gate[i] = E_DESTINATION_SIZE: nothing of it is decoded or stored.
+// sig (nullable): a ranged call's tables (SignalOut::rbegin / rend) -- the chunk check is then against the range's sample count.
 hipError_t launch_chunk_slots(uint32_t n, const uint32_t* cap16, const float* offset, const float* scale, uint32_t L, uint32_t S,
-                              const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate, hipStream_t s);
+                              const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate, const SignalOut* sig, hipStream_t s);
+// range_samples[i] = the sample count of read i's clamped range (samples[i] of 2^31 or more, an error code, passes through)
+hipError_t launch_range_samples(uint32_t n, const uint32_t* samples, const uint32_t* begin, const uint32_t* end, uint32_t* range_samples, hipStream_t s);
 // chunk layout (pack.hip): chunk_first[i] = the exclusive scan of chunk_count(samples[i]) (samples of 2^31 or more: 0 chunks), chunk_first[n]
 // the total; count: n words of scratch.  launch_chunk_info: when chunk_first[n] <= info_cap, info[2c] / info[2c + 1] = the read / start
 // sample of row c (a grid-stride launch; nothing when the total is larger).
