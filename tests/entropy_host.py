@@ -30,12 +30,17 @@ def tree_description(data, package_merge=False):
     """(table log, code lengths[256], tree description bytes) for the byte histogram of `data`,
     as libzstd's HUF_buildCTable / HUF_writeCTable produce them for a block of len(data) <= 128 KiB;
     package_merge: code lengths by huf_build_pm (what the device encoder builds) instead of libzstd's construction."""
-    H = lib()
     data = np.ascontiguousarray(data, dtype=np.uint8)
-    cnt = np.bincount(data, minlength=256).astype(np.uint32)
+    return tree_description_counts(np.bincount(data, minlength=256), package_merge)
+
+
+def tree_description_counts(counts, package_merge=False):
+    """tree_description for a region with the byte histogram counts[256] (at least two values occur)"""
+    H = lib()
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
     maxsym = int(np.nonzero(cnt)[0].max())
     u8p, u16p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint32)
-    n = min(len(data), 128 << 10)
+    n = min(int(cnt.sum()), 128 << 10)
     hl = H.h_optimal_table_log(11, n, maxsym, 1)
     nb = np.zeros(256, np.uint8)
     code = np.zeros(256, np.uint16)
@@ -101,6 +106,77 @@ def parse_first_block_literals(frame):
         tl = 1 + hb if hb < 128 else 1 + (hb - 127 + 1) // 2
         tree = b[q : q + tl]
     return (t, regen, cs, tree, b[q + cs])
+
+
+def weights_report(nb, maxsym, tl):
+    """The way huf_write_tree takes for the code lengths nb[0 .. maxsym] at table log tl: (method, kind, low, size) --
+    method 0: the weights are never normalised (all equal, every value once, fewer than two), 1 / 2: fse_normalize's first / second
+    method; kind 'fse', 'direct' or 'none' (no description can be written); low: weight values given the low-probability count;
+    size: bytes of the description."""
+    w = np.array([tl + 1 - int(x) if x else 0 for x in nb[:maxsym]], np.uint8)
+    out = np.zeros(4, np.uint32)
+    r = lib().h_weights_report(w.ctypes.data_as(ctypes.c_void_p), len(w), out.ctypes.data_as(ctypes.c_void_p))
+    assert r == 0, "the restated choice between the normalisation methods disagrees with fse_normalize"
+    return int(out[0]), ("fse", "direct", "none")[int(out[1])], int(out[2]), int(out[3])
+
+
+def frame_trailers(frame):
+    """The library's skippable frames behind a zstd frame: {magic: payload bytes}."""
+    b = bytes(frame)
+    out = {}
+    pos = [end for _, _, end in walk_blocks(b)][-1] + (4 if (b[4] >> 2) & 1 else 0)
+    while pos + 8 <= len(b):
+        magic, size = int.from_bytes(b[pos : pos + 4], "little"), int.from_bytes(b[pos + 4 : pos + 8], "little")
+        if magic & 0xFFFFFFF0 != 0x184D2A50 or pos + 8 + size > len(b):
+            break
+        out[magic] = b[pos + 8 : pos + 8 + size]
+        pos += 8 + size
+    return out
+
+
+def walk_blocks(frame):
+    """Every block of a zstd frame with a content size, in order: (block type, literals, end offset of the block) -- block type 0 raw,
+    1 RLE (literals None; see `size` below), 2 compressed with literals = parse_first_block_literals' tuple (literals type, regenerated
+    size, compressed size, tree description or None, number of sequences -- the whole count, not its first byte).  For raw and RLE
+    blocks `literals` is (None, block size, None, None, 0): the block's content bytes."""
+    b = bytes(frame)
+    assert int.from_bytes(b[:4], "little") == 0xFD2FB528
+    fhd = b[4]
+    single = (fhd >> 5) & 1
+    pos = 5 + (0 if single else 1) + (0, 1, 2, 4)[fhd & 3] + [1 if single else 0, 2, 4, 8][fhd >> 6]
+    while True:
+        bh = b[pos] | b[pos + 1] << 8 | b[pos + 2] << 16
+        last, btype, size = bh & 1, (bh >> 1) & 3, bh >> 3
+        pos += 3
+        assert btype != 3
+        if btype < 2:
+            pos += size if btype == 0 else 1
+            yield btype, (None, size, None, None, 0), pos
+        else:
+            v = int.from_bytes(b[pos : pos + 5], "little")
+            t, fmt = v & 3, (v >> 2) & 3
+            if t < 2:
+                h = 1 if fmt in (0, 2) else (2 if fmt == 1 else 3)
+                regen = (v & ((1 << 8 * h) - 1)) >> (3 if h == 1 else 4)
+                cs, tree = (regen if t == 0 else 1), None
+            else:
+                if fmt < 2:
+                    regen, cs, h = (v >> 4) & 0x3FF, (v >> 14) & 0x3FF, 3
+                elif fmt == 2:
+                    regen, cs, h = (v >> 4) & 0x3FFF, (v >> 18) & 0x3FFF, 4
+                else:
+                    regen, cs, h = (v >> 4) & 0x3FFFF, (v >> 22) & 0x3FFFF, 5
+                tree = None
+                if t == 2:
+                    hb = b[pos + h]
+                    tree = b[pos + h : pos + h + (1 + hb if hb < 128 else 1 + (hb - 127 + 1) // 2)]
+            q = pos + h + cs
+            n0 = b[q]
+            nseq = n0 if n0 < 128 else (b[q + 1] + (b[q + 2] << 8) + 0x7F00 if n0 == 255 else ((n0 - 128) << 8) + b[q + 1])
+            pos += size
+            yield 2, (t, regen, cs, tree, nseq), pos
+        if last:
+            return
 
 
 def weights_from_tree(tree):

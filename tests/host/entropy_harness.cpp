@@ -137,6 +137,58 @@ int h_huf_write_tree(uint8_t* dst, int cap, const uint8_t* nbBits, uint32_t maxS
     uint8_t weights[260];
     return huf_write_tree(dst, cap, nbBits, maxSymbolValue, huffLog, weights, &w);
 }
+
+// Which way a weight list (weights[0 .. wtSize), the last symbol's left out as in a tree description) takes through huf_write_tree:
+// out[] = { method, kind, low, size }.  method: 0 the weights are never normalised (fewer than two, all equal, or every value once:
+// huf_compress_weights returns before fse_normalize), 1 / 2 fse_normalize's first / second method; kind: 0 FSE-coded, 1 direct 4-bit
+// weights, 2 no description can be written; low: weight values at or below the low-probability threshold (norm = lowProbCount);
+// size: the description's bytes (0 for kind 2).  The decision between the methods is restated here (fse_normalize does not report
+// it) and held against fse_normalize's own result: -1 if the first method's restatement gives other counts than the function.
+int h_weights_report(const uint8_t* weights, uint32_t wtSize, uint32_t* out)
+{
+    static FseWeightWksp w;
+    uint8_t scratch[260], dst[300];
+    out[0] = out[1] = out[2] = out[3] = 0;
+    for (int i = 0; i < 16; ++i) w.count[i] = 0;
+    for (uint32_t i = 0; i < wtSize; ++i) {
+        if (weights[i] > HUF_ABS_MAX_BITS) return -1;
+        w.count[weights[i]]++;
+        scratch[i] = weights[i];
+    }
+    uint32_t maxSV = HUF_ABS_MAX_BITS, maxCount = 0;
+    while (maxSV > 0 && w.count[maxSV] == 0) maxSV--;
+    for (uint32_t s = 0; s <= maxSV; ++s) maxCount = w.count[s] > maxCount ? w.count[s] : maxCount;
+    if (wtSize > 1 && maxCount != wtSize && maxCount != 1) {
+        const uint32_t tableLog = optimal_table_log(6, wtSize, maxSV, 2), total = wtSize;
+        const uint64_t scale = 62 - tableLog, step = ((uint64_t)1 << 62) / total, vStep = 1ull << (scale - 20);
+        const uint32_t rtb[8] = { 0, 473195, 504333, 520860, 550000, 700000, 750000, 830000 };
+        int still = 1 << tableLog, first[16];
+        uint32_t largest = 0;
+        int largestP = 0;
+        for (uint32_t s = 0; s <= maxSV; ++s) {
+            first[s] = 0;
+            if (w.count[s] == 0) continue;
+            if (w.count[s] <= (total >> tableLog)) { first[s] = 1; still--; out[2]++; continue; }
+            int proba = (int)((w.count[s] * step) >> scale);
+            if (proba < 8 && ((w.count[s] * step) - ((uint64_t)proba << scale)) > vStep * rtb[proba]) proba++;
+            if (proba > largestP) { largestP = proba; largest = s; }
+            first[s] = proba;
+            still -= proba;
+        }
+        out[0] = -still >= (first[largest] >> 1) ? 2 : 1;
+        int16_t norm[16];
+        if (fse_normalize(norm, tableLog, w.count, total, maxSV, 1) <= 0) return -1;
+        if (out[0] == 1) {
+            first[largest] += still;
+            for (uint32_t s = 0; s <= maxSV; ++s)
+                if (norm[s] != first[s]) return -1;
+        }
+    }
+    const int ts = huf_write_tree(dst, 300, nullptr, wtSize, 0, scratch, &w, true);
+    out[1] = ts < 0 ? 2u : (dst[0] >= 128 ? 1u : 0u);
+    out[3] = ts < 0 ? 0u : (uint32_t)ts;
+    return 0;
+}
 }
 
 // ---- prototype of the "zero-run sequences" block (tests only): the serial statement of what the device

@@ -1723,6 +1723,11 @@ __global__ __launch_bounds__(WAVE, VBZ_DEC_WAVES) void zstd_decode_kernel(ReadBa
                 ws_plit = (fcs + 15u) & ~15u;
                 ws_seq = ws_plit + (ltype >= 2 ? ((regen + 15u) & ~15u) : 0u);
                 par = (uint64_t)ws_seq + (use_pre ? 0ull : 16ull * ns_hdr) + 16 <= cap;  // (walked chains: the records are elsewhere)
+                // A span has no other place for them: the end of the frame's output is the last span's, which another wavefront writes
+                // at the same time (a stream that fills its slot -- one-byte integers of 128 and more -- used to come back with control
+                // bytes in its last data bytes, now and then), and behind the first span's stripe the later spans' stripes begin.  The
+                // frame goes to the ordinary decoder.
+                if (partial && (!par || (uint64_t)ws_seq + 16ull * ns_hdr + 16 > (uint64_t)ws_plit + (uint64_t)DSPAN_WS_FACTOR * sp.dst_len + 32u)) FAIL();
             }
             const uint32_t lit_dst = !has_seq ? opos : (defer ? ws_lit : (par ? ws_plit : fcs - regen));
             const uint8_t* lit_src = blk + lh;  // raw literals are read in place
