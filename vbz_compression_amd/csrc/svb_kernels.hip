@@ -139,9 +139,9 @@ __device__ __forceinline__ void sig_store1(uint8_t* p, uint32_t v, const SigK& k
 // outside each of them and go out as whole 16-byte stores, one per chunk that holds them (at most ceil(L / S) + 1).  The END chunk starts
 // at `last`, d = last % 8 samples past a multiple of 8: its 8-sample line starting at sample i0 + d is put together from the lane's
 // samples d ... 7 and the next lane's 0 ... d - 1 (one shuffle per dword) and stored whole -- except where the next group belongs to
-// another wavefront (lane 63): there the two lanes store their parts element by element (disjoint bytes).  Positions past the read's
-// end take the pad value: in a line that holds samples, the lane storing the line puts it there; the lines that hold none are written
-// by chunk_pad.  No two stores of a launch write the same bytes.
+// another wavefront (lane 63) or to the next row of a POD5 read: there the two lanes store their parts element by element (disjoint
+// bytes).  Positions past the read's end take the pad value: in a line that holds samples, the lane storing the line puts it there; the
+// lines that hold none are written by chunk_pad.  No two stores of a launch write the same bytes (the argument: DESIGN.md 4.11).
 struct ChunkK
 {
     uint8_t* base = nullptr;   // the read's first row
@@ -153,8 +153,9 @@ struct ChunkK
     bool extra = false;        // END with K >= 2: the last chunk is the pulled-back one at `last`
 };
 
+// the chunks of a signal of T samples whose chunk 0 is row first_row of the arena (a read: b.sig.row[r]; a POD5 read: the plan's)
 template <int OUT>
-__device__ __forceinline__ ChunkK chunk_constants(const ReadBatch& b, uint32_t r, uint32_t T)
+__device__ __forceinline__ ChunkK chunk_constants(const ReadBatch& b, uint32_t T, uint64_t first_row)
 {
     constexpr uint32_t OB = OutBytes<OUT>::value;
     ChunkK c;
@@ -166,7 +167,7 @@ __device__ __forceinline__ ChunkK chunk_constants(const ReadBatch& b, uint32_t r
     c.extra = b.sig.mode == CHUNK_END && c.K >= 2;
     c.nG = c.extra ? c.K - 1 : c.K;
     c.row_bytes = (uint64_t)c.L * OB;
-    c.base = b.dst + b.sig.row[r] * c.row_bytes;
+    c.base = b.dst + first_row * c.row_bytes;
     c.inv = (uint32_t)(0x100000000ull / c.S);
     if (OB == 4) c.padw = __float_as_uint(b.sig.pad);
     else c.padw = sig_pack2<OUT & 3>(b.sig.pad, b.sig.pad) & 0xFFFFu;
@@ -228,41 +229,70 @@ __device__ __forceinline__ void chunk_elems8(const ChunkK& ck, int valid, uint32
     }
 }
 
-// one lane's eight consecutive samples i0 ... i0 + 7 (i0 a multiple of 8), the first `valid` of them decoded (base + s[j]), into every
-// chunk that holds them.  Every lane of the workgroup calls it at the same point (the END chunk's lines take a cross-lane shuffle).
+// the grid chunks that hold position p of the signal: put(q), q the address of position p, in k = floor(p / S) (at most the grid's last)
+// and in every chunk before it that still reaches p
+template <int OUT, class Put>
+__device__ __forceinline__ void chunk_walk(const ChunkK& ck, uint32_t p, Put put)
+{
+    constexpr uint32_t OB = OutBytes<OUT>::value;
+    uint32_t k = __umulhi(p, ck.inv);
+    if (p - k * ck.S >= ck.S) ++k;
+    if (k > ck.nG - 1u) k = ck.nG - 1u;
+    uint32_t off = p - k * ck.S;
+    uint8_t* q = ck.base + (uint64_t)k * ck.row_bytes + (size_t)off * OB;
+    const int64_t back = (int64_t)ck.S * OB - (int64_t)ck.row_bytes;   // one chunk back: the same sample S positions further on
+    while (off < ck.L) {
+        put(q);
+        if (k == 0) break;
+        --k;
+        off += ck.S;
+        q += back;
+    }
+}
+
+// the sample at position p of the signal (its bits e in the output type) into every chunk that holds it
 template <int OUT>
-__device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int valid, uint32_t base, const uint32_t s[8], const SigK& sk)
+__device__ __forceinline__ void chunk_put_sample(const ChunkK& ck, uint32_t p, uint32_t e)
+{
+    chunk_walk<OUT>(ck, p, [&](uint8_t* q) { chunk_put1<OUT>(q, e); });
+    if (ck.extra && p >= ck.last && p - ck.last < ck.L)
+        chunk_put1<OUT>(ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes + (size_t)(p - ck.last) * OutBytes<OUT>::value, e);
+}
+
+// one lane's eight consecutive samples i0 ... i0 + 7 of the signal (i0 a multiple of 8), the first `valid` of them decoded (base + s[j]),
+// into every chunk that holds them.  Every lane of the workgroup calls it at the same point (the END chunk's lines take a cross-lane
+// shuffle).  ROWS: the workgroup's samples may end at re in front of the signal's end, the next workgroup (a POD5 read's next row) going on
+// from there.  A lane then stores whole lines only where all eight positions are this workgroup's samples or lie behind the signal's end;
+// its last group, when the next row goes on in the same line, and the END chunk's lines that reach into the next row are stored element by
+// element, each workgroup its own samples.  Without ROWS (a read, or a segment of one: segments end at multiples of 8 * 64) re is not
+// looked at.
+template <int OUT, bool ROWS>
+__device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int valid, uint32_t re, uint32_t base, const uint32_t s[8], const SigK& sk)
 {
     constexpr uint32_t OB = OutBytes<OUT>::value;
     uint32_t e[8];
     chunk_elems8<OUT>(ck, valid, base, s, sk, e);
-    // the grid chunks: k = floor(i0 / S) down to the first chunk that still reaches i0
-    if (valid > 0) {
-        uint32_t k = __umulhi(i0, ck.inv);
-        if (i0 - k * ck.S >= ck.S) ++k;
-        if (k > ck.nG - 1u) k = ck.nG - 1u;
-        uint32_t off = i0 - k * ck.S;
-        uint8_t* p = ck.base + (uint64_t)k * ck.row_bytes + (size_t)off * OB;
-        const int64_t back = (int64_t)ck.S * OB - (int64_t)ck.row_bytes;   // one chunk back: the same sample S positions further on
-        while (off < ck.L) {
-            chunk_put8<OUT>(p, e);
-            if (k == 0) break;
-            --k;
-            off += ck.S;
-            p += back;
-        }
+    const bool tail = ROWS && re < ck.T;                   // samples of later rows follow
+    const bool partial = tail && valid > 0 && valid < 8;   // ... in this lane's line
+    if (partial) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < valid) chunk_put_sample<OUT>(ck, i0 + (uint32_t)j, e[j]);
+    } else if (valid > 0) {
+        chunk_walk<OUT>(ck, i0, [&](uint8_t* q) { chunk_put8<OUT>(q, e); });
     }
     if (!ck.extra) return;
-    // the END chunk
+    // the END chunk (a partial lane has stored its samples there already)
     const uint32_t sl = ck.last, d = sl & 7u, g0 = sl - d;
     uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
     if (d == 0) {
-        if (valid > 0 && i0 >= sl && i0 - sl < ck.L) chunk_put8<OUT>(row + (size_t)(i0 - sl) * OB, e);
+        if (!partial && valid > 0 && i0 >= sl && i0 - sl < ck.L) chunk_put8<OUT>(row + (size_t)(i0 - sl) * OB, e);
         return;
     }
     const int lane = threadIdx.x & 63;
-    const bool in = valid > 0 && i0 >= g0 && i0 - g0 < ck.L;                           // the line that starts at sample i0 + d
-    const bool in0 = lane == 0 && valid > 0 && i0 >= g0 + 8u && i0 - 8u - g0 < ck.L;   // lane 0: the line that starts in the group before
+    // the line that starts at sample i0 + d (behind the signal's end it holds no sample: chunk_pad's)
+    const bool in = !partial && valid > 0 && i0 >= g0 && i0 - g0 < ck.L && i0 + d < ck.T;
+    const bool in0 = !partial && lane == 0 && valid > 0 && i0 >= g0 + 8u && i0 - 8u - g0 < ck.L;   // lane 0: the line that starts in the group before
     if (!__any(in || in0)) return;
     uint32_t n[8];
     if (OB == 4) {
@@ -280,7 +310,8 @@ __device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int 
     for (int j = 0; j < 8; ++j)
         if (i0 + 8u + (uint32_t)j >= ck.T) n[j] = ck.padw;
     if (in) {
-        if (i0 + 8u >= ck.T || lane != 63) {
+        // whole: the next group is behind the signal's end, or the next lane's and all of it this workgroup's
+        if (i0 + 8u >= ck.T || (lane != 63 && !(tail && i0 + 16u > re))) {
             uint32_t o[8];
             switch (d) {
             case 1: chunk_shift<1>(e, n, o); break;
@@ -292,7 +323,7 @@ __device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int 
             default: chunk_shift<7>(e, n, o); break;
             }
             chunk_put8<OUT>(row + (size_t)(i0 - g0) * OB, o);
-        } else {   // (the next group is another wavefront's: its lane 0 stores the rest of the line)
+        } else {   // (the rest of the line is stored by whoever holds the next group: lane 0 below, a partial lane, the next row)
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if ((uint32_t)j >= d) chunk_put1<OUT>(row + (size_t)(i0 - g0 + (uint32_t)j - d) * OB, e[j]);
@@ -305,18 +336,63 @@ __device__ __forceinline__ void chunk_store8(const ChunkK& ck, uint32_t i0, int 
     }
 }
 
-// the last chunk's lines past the read's end (no sample in them): the pad value, by the whole workgroup
+// the pad behind the signal's last sample, by the whole workgroup: the last chunk's lines that hold no sample and, with `elems` (the line
+// of the last sample was stored sample by sample), the positions between that sample and the first such line
 template <int OUT>
-__device__ __forceinline__ void chunk_pad(const ChunkK& ck)
+__device__ __forceinline__ void chunk_pad(const ChunkK& ck, bool elems)
 {
     if (ck.K == 0) return;
     constexpr uint32_t OB = OutBytes<OUT>::value;
     uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
+    const uint32_t p0 = ck.T - ck.last, l0 = (p0 + 7u) >> 3;   // the first pad position, the first line of nothing else
+    if (elems && p0 + threadIdx.x < l0 * 8u) chunk_put1<OUT>(row + (size_t)(p0 + threadIdx.x) * OB, ck.padw);
     uint32_t e[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) e[j] = ck.padw;
-    for (uint32_t j = ((ck.T - ck.last + 7u) >> 3) + threadIdx.x; j < (ck.L >> 3); j += WG) chunk_put8<OUT>(row + (size_t)j * 8u * OB, e);
+    for (uint32_t j = l0 + threadIdx.x; j < (ck.L >> 3); j += WG) chunk_put8<OUT>(row + (size_t)j * 8u * OB, e);
 }
+
+// The chunk store of one workgroup: its values are the samples s0 ... re - 1 of a read whose samples [rb, rend) are the signal that is
+// chunked (ck is that signal's; OUT & SIG_RANGE, else the whole read).  A whole read on one workgroup is s0 = 0, rb = 0, rend = re = T; a
+// segment of the large-read path the same (put() gets positions in the read); a row of a POD5 read (ROWS) lies at s0.
+template <int OUT, bool ROWS>
+struct ChunkStore
+{
+    static constexpr bool RANGED = (OUT & SIG_RANGE) != 0;
+    ChunkK ck;
+    SigK sk;
+    uint32_t s0 = 0, re = 0;      // ROWS (else 0 and not looked at)
+    uint32_t rb = 0, rend = 0;    // RANGED
+    bool pad_elems = false;       // finish(): the line of the signal's last sample is stored sample by sample (ROWS: by whichever row holds it)
+
+    // one lane's values i0 ... i0 + valid - 1 of the workgroup's (base + s[k]), every lane of the workgroup at the same point.  A lane that
+    // starts at a multiple of 8 of the signal stores lines (`valid` cut at the range's ends; a lane outside still takes part in the END
+    // chunk's shuffle), any other every sample on its own
+    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
+    {
+        const uint32_t first = ROWS ? s0 : 0u, b0 = RANGED ? rb : 0u;
+        const uint32_t p = first + i0;   // the lane's first sample in the read
+        if (((first - b0) & 7u) == 0) {
+            int v = valid;
+            uint32_t end = re;   // where the workgroup's samples end in the signal
+            if constexpr (RANGED) {
+                v = (p < rb || p >= rend) ? 0 : (rend - p < (uint32_t)valid ? (int)(rend - p) : valid);
+                const uint32_t rowend = re < rend ? re : rend;
+                end = rowend > rb ? rowend - rb : 0u;
+            }
+            chunk_store8<OUT, ROWS>(ck, p - b0, v, end, base, s, sk);
+        } else {
+            uint32_t e[8];
+            chunk_elems8<OUT>(ck, valid, base, s, sk, e);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < valid && (!RANGED || p + (uint32_t)j - rb < rend - rb)) chunk_put_sample<OUT>(ck, p + (uint32_t)j - b0, e[j]);
+        }
+    }
+
+    // the signal's pad, by the whole workgroup, once per read
+    __device__ __forceinline__ void finish() const { chunk_pad<OUT>(ck, (ROWS || RANGED) && pad_elems); }
+};
 
 // ---- normalisation statistics (OUT = SIG_COUNT; vbz_kernels.h NormRead) -------------------------------------------------------------
 // The counting pass histograms a read's keys into the windows of its NormRead in LDS; the select turns the counts into ranks.  A read on
@@ -556,10 +632,8 @@ struct NormK
     uint32_t lo[NORM_WINDOWS] = {}, sh[NORM_WINDOWS] = {};
 };
 
-template <int OUT>
-__device__ __forceinline__ void chunk_put_sample(const ChunkK& ck, uint32_t p, uint32_t e);
-
-// the range of a ranged store (OUT & SIG_RANGE; vbz_kernels.h sample_range): positions [b, e) of the read are the store's [0, e - b).
+// the range of a ranged counting pass (SIG_COUNT | SIG_RANGE; vbz_kernels.h sample_range): positions [b, e) of the read are counted (a
+// ranged chunk store keeps its range in its ChunkStore).
 // s0: where the values handed to put() begin in the read (a POD5 read's counting pass sets it row by row)
 template <bool ON>
 struct RangeK
@@ -576,9 +650,7 @@ struct RangeK<true>
 // OUT = SIG_NONE: the ELEM-byte values into the read's slot (dst + dst_off[r]).  SIG_*: the typed samples of int16 values into the read's
 // typed slot (dst + dst_off[r] / 2 * E: dst_off is the int16 layout's).  SIG_* | SIG_CHUNK: the typed samples into the read's chunks.
 // | SIG_RANGE (the chunk stores and SIG_COUNT): the read is its samples [b, e) -- the others are decoded (the delta chain needs them) and
-// neither converted, stored nor counted.  b a multiple of 8: a lane's eight samples are still one aligned line of the range's signal and
-// go through chunk_store8 at i0 - b, `valid` cut at e; any other b: sample by sample (chunk_put_sample), the pad positions of the line
-// that holds the range's last sample by finish().  Either way every byte of the read's rows has one writer, as in the whole read's store.
+// neither converted, stored nor counted.  The chunk case is a ChunkStore with s0 = 0 and re = T: put() and finish() are its.
 template <int ELEM, int OUT>
 struct DecStore
 {
@@ -587,11 +659,11 @@ struct DecStore
     static constexpr uint32_t BYTES = OUT == SIG_NONE ? ELEM : OutBytes<OUT>::value;   // per value: result[r] = count * BYTES
     uint8_t* out;   // the read's slot (the chunk store: the 16-byte aligned chunk arena)
     SigK sk;
-    ChunkK ck;
+    ChunkStore<OUT, false> cs;                   // SIG_CHUNK
     NormK nk;                                    // SIG_COUNT
     mutable uint32_t nbelow[NORM_WINDOWS] = {};  // SIG_COUNT: this lane's keys below each window
     static constexpr bool RANGED = (OUT & SIG_RANGE) != 0;
-    [[no_unique_address]] RangeK<RANGED> rg;     // SIG_RANGE
+    [[no_unique_address]] RangeK<RANGED> rg;     // SIG_COUNT | SIG_RANGE
 
     // b: the batch, for the typed stores only -- SIG_NONE gets nullptr and the batch's fields (a reference to the kernel's ReadBatch
     // argument would cost its loads their scalar form)
@@ -599,11 +671,15 @@ struct DecStore
     // cr: whose constants (b->sig.cal) the typed store takes -- a POD5 row decoded with its read's
     __device__ __forceinline__ DecStore(uint8_t* dst, const uint64_t* dst_off, const ReadBatch* b, uint32_t r, uint32_t count, uint32_t cr)
     {
+        uint32_t rb = 0, rend = count;
         if constexpr (RANGED) {   // the store's read is the range
             static_assert((OUT & (SIG_CHUNK | SIG_COUNT)) != 0, "ranges: the chunk stores and the counting pass");
-            sample_range(b->sig, r, count, &rg.b, &rg.e);
-            count = rg.e - rg.b;
+            sample_range(b->sig, r, count, &rb, &rend);
+            rg.b = rb;
+            rg.e = rend;
         }
+        const uint32_t T = count;
+        count = rend - rb;
         if (OUT == SIG_NONE) {
             out = dst + dst_off[r];
         } else if (OUT & SIG_COUNT) {   // (all threads of the workgroup: the bins are zeroed here)
@@ -629,8 +705,12 @@ struct DecStore
             __syncthreads();
         } else if (OUT & SIG_CHUNK) {
             out = dst;
-            ck = chunk_constants<OUT>(*b, r, count);
-            sk = sig_constants(*b, r);
+            cs.ck = chunk_constants<OUT>(*b, count, b->sig.row[r]);
+            cs.sk = sig_constants(*b, r);
+            cs.re = T;
+            cs.rb = rb;
+            cs.rend = rend;
+            cs.pad_elems = (rb & 7u) != 0;
         } else {
             out = dst + (dst_off[r] >> 1) * BYTES;
             sk = sig_constants(*b, cr);
@@ -667,20 +747,7 @@ struct DecStore
                 }
             }
         } else if (OUT & SIG_CHUNK) {
-            if constexpr (RANGED) {
-                if ((rg.b & 7u) == 0) {   // whole lines of the range's signal
-                    const int v = (i0 < rg.b || i0 >= rg.e) ? 0 : (rg.e - i0 < (uint32_t)valid ? (int)(rg.e - i0) : valid);
-                    chunk_store8<OUT>(ck, i0 - rg.b, v, base, s, sk);
-                } else {
-                    uint32_t e[8];
-                    chunk_elems8<OUT>(ck, valid, base, s, sk, e);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if (j < valid && i0 + (uint32_t)j - rg.b < rg.e - rg.b) chunk_put_sample<OUT>(ck, i0 + (uint32_t)j - rg.b, e[j]);
-                }
-            } else {
-                chunk_store8<OUT>(ck, i0, valid, base, s, sk);
-            }
+            cs.put(i0, valid, base, s);
         } else if (OUT != SIG_NONE) {
             if (valid == VPL && aligned()) {
                 sig_store8<OUT>(out + (size_t)i0 * BYTES, base, s, sk);
@@ -717,18 +784,10 @@ struct DecStore
         }
     }
 
-    // after the read's values, by the whole workgroup (svb_decode_range: the range at the read's start): the chunk store's lines past the
-    // read's end
+    // after the read's values, by the whole workgroup (svb_decode_range: the range at the read's start): the chunk store's pad
     __device__ __forceinline__ void finish() const
     {
-        if (OUT & SIG_CHUNK) chunk_pad<OUT>(ck);
-        if constexpr (RANGED && (OUT & SIG_CHUNK) != 0) {
-            if ((rg.b & 7u) != 0 && ck.K != 0) {   // (sample by sample: the pad positions behind the last sample, up to the lines of chunk_pad)
-                const uint32_t p0 = ck.T - ck.last, l0 = (p0 + 7u) >> 3;
-                if (p0 + threadIdx.x < l0 * 8u)
-                    chunk_put1<OUT>(ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes + (size_t)(p0 + threadIdx.x) * OutBytes<OUT>::value, ck.padw);
-            }
-        }
+        if (OUT & SIG_CHUNK) cs.finish();
     }
 
     // after this workgroup's values (svb_decode_range, MODE 0), by the whole workgroup: the counting pass's counts are complete -- a read
@@ -2345,6 +2404,28 @@ __device__ __forceinline__ bool svb16_decode_row(const uint8_t* in, uint32_t in_
 
 // The verdicts of a POD5 row: content longer than svb16_max(n) is the zstd stage's (E_ZSTD), a stream whose length is not
 // K + n + popcount(the first n key bits) -- bytes missing or left over -- E_STREAM.
+// svb16_row_open: whether row r is to be decoded (*in_size, *count: its stream and its samples); else *verdict is its result (GATE_SKIP:
+// none to write)
+__device__ __forceinline__ bool svb16_row_open(const ReadBatch& b, uint32_t r, uint32_t* in_size, uint32_t* count, uint32_t* verdict)
+{
+    if (b.gate && b.gate[r] >= GATE_SKIP) {
+        *verdict = b.gate[r];
+        return false;
+    }
+    *in_size = b.src_size[r];
+    *verdict = *in_size;
+    if (*in_size >= E_FIRST) return false;   // the previous stage failed for this row
+    const uint32_t out_size = b.dst_cap[r];
+    *verdict = E_DESTINATION_SIZE;
+    if (out_size & 1u) return false;
+    *count = out_size >> 1;
+    const uint32_t K = (*count + 7u) >> 3;
+    *verdict = *in_size < K ? E_STREAM : E_ZSTD;
+    if ((uint64_t)*in_size > (uint64_t)K + 2ull * *count || *in_size < K) return false;
+    *verdict = 0;
+    return *count != 0;   // (an empty stream: nothing to store or count)
+}
+
 template <int OUT>
 __global__ __launch_bounds__(WG) void svb16_decode_kernel(ReadBatch b)
 {
@@ -2353,30 +2434,13 @@ __global__ __launch_bounds__(WG) void svb16_decode_kernel(ReadBatch b)
 
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
-        return;
-    }
-    const uint32_t in_size = b.src_size[r];
-    if (in_size >= E_FIRST) {   // the previous stage failed for this read
-        if (tid == 0) b.result[r] = in_size;
-        return;
-    }
-    const uint32_t out_size = b.dst_cap[r];
-    if (out_size & 1u) {
-        if (tid == 0) b.result[r] = E_DESTINATION_SIZE;
-        return;
-    }
-    const uint32_t count = out_size >> 1, K = (count + 7u) >> 3;
-    if ((uint64_t)in_size > (uint64_t)K + 2ull * count || in_size < K) {
-        if (tid == 0) b.result[r] = in_size < K ? E_STREAM : E_ZSTD;
-        return;
-    }
-    if (count == 0) {   // (an empty stream: nothing to store or count -- every pass gives the verdict)
-        if (tid == 0) b.result[r] = 0;
+    uint32_t in_size = 0, count = 0, verdict;
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {   // (every pass gives the verdict)
+        if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
         return;
     }
     if ((OUT & SIG_COUNT) && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
+    const uint32_t K = (count + 7u) >> 3;
     const uint8_t* in = b.src + b.src_off[r];
     const uint8_t* data = in + K;
     const uint32_t dataBytes = in_size - K;
@@ -2541,27 +2605,6 @@ __global__ __launch_bounds__(WG) void pod5_read_samples_kernel(Pod5Reads pr, con
     read_samples[k] = T >> 31 ? E_DESTINATION_SIZE : (uint32_t)T;
 }
 
-// whether row r is to be decoded (*in_size, *count: its stream and its samples); else *verdict is its result (GATE_SKIP: none to write)
-__device__ __forceinline__ bool svb16_row_open(const ReadBatch& b, uint32_t r, uint32_t* in_size, uint32_t* count, uint32_t* verdict)
-{
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        *verdict = b.gate[r];
-        return false;
-    }
-    *in_size = b.src_size[r];
-    *verdict = *in_size;
-    if (*in_size >= E_FIRST) return false;   // the previous stage failed for this row
-    const uint32_t out_size = b.dst_cap[r];
-    *verdict = E_DESTINATION_SIZE;
-    if (out_size & 1u) return false;
-    *count = out_size >> 1;
-    const uint32_t K = (*count + 7u) >> 3;
-    *verdict = *in_size < K ? E_STREAM : E_ZSTD;
-    if ((uint64_t)*in_size > (uint64_t)K + 2ull * *count || *in_size < K) return false;
-    *verdict = 0;
-    return *count != 0;   // (an empty stream: nothing to store or count)
-}
-
 // One thread per row and per read.  A bad table closes every row's gate with E_INPUT_SIZE (its result too) and nothing else happens.  Otherwise the read's
 // thread walks its rows: their places (Pod5Row), T, the chunk check (chunk_first is untrusted; 2^31 samples and more fail too) -- a read
 // that fails closes its rows' gates with E_DESTINATION_SIZE -- and the read's constants: the given ones, or (a normalising call) the
@@ -2651,167 +2694,24 @@ __global__ __launch_bounds__(WG) void pod5_reads_plan_range_kernel(ReadBatch b, 
     pod5_reads_plan<true>(b, pr, offset, scale, chunk_rows);
 }
 
-// the sample at position p of the read (its bits e in the output type) into every chunk that holds it
+// the chunk store of row r of a read, from the plan: the row's `count` samples lie at s0 of the read's signal
 template <int OUT>
-__device__ __forceinline__ void chunk_put_sample(const ChunkK& ck, uint32_t p, uint32_t e)
+__device__ __forceinline__ ChunkStore<OUT, true> row_chunk_store(const ReadBatch& b, const Pod5Reads& pr, const Pod5Row& rw, uint32_t count)
 {
-    constexpr uint32_t OB = OutBytes<OUT>::value;
-    uint32_t k = __umulhi(p, ck.inv);
-    if (p - k * ck.S >= ck.S) ++k;
-    if (k > ck.nG - 1u) k = ck.nG - 1u;
-    uint32_t off = p - k * ck.S;
-    uint8_t* q = ck.base + (uint64_t)k * ck.row_bytes + (size_t)off * OB;
-    const int64_t back = (int64_t)ck.S * OB - (int64_t)ck.row_bytes;
-    while (off < ck.L) {
-        chunk_put1<OUT>(q, e);
-        if (k == 0) break;
-        --k;
-        off += ck.S;
-        q += back;
+    ChunkStore<OUT, true> st;
+    const Pod5Read rd = pr.reads[rw.read];
+    st.rend = rd.T;
+    if (OUT & SIG_RANGE) {   // (the chunking is the range's)
+        const uint2 g = pr.range[rw.read];
+        st.rb = g.x;
+        st.rend = g.y;
     }
-    if (ck.extra && p >= ck.last && p - ck.last < ck.L) chunk_put1<OUT>(ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes + (size_t)(p - ck.last) * OB, e);
-}
-
-// chunk_store8 for a row of a read: i0 is the lane's position in the READ (a multiple of 8: the row begins at one), re where the row ends
-// there.  A lane stores whole lines only where all eight positions are this workgroup's samples or lie behind the read's end; the row's
-// last group, when later rows go on in the same line, and the END chunk's lines that reach into the next row are stored element by
-// element, each workgroup its own samples, so that no two stores of the launch touch the same bytes.
-template <int OUT>
-__device__ __forceinline__ void chunk_store8_row(const ChunkK& ck, uint32_t i0, int valid, uint32_t re, uint32_t base, const uint32_t s[8], const SigK& sk)
-{
-    constexpr uint32_t OB = OutBytes<OUT>::value;
-    uint32_t e[8];
-    chunk_elems8<OUT>(ck, valid, base, s, sk, e);
-    const bool tail = re < ck.T;                          // samples of later rows follow
-    const bool partial = valid > 0 && valid < 8 && tail;   // ... in this lane's line
-    if (partial) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (j < valid) chunk_put_sample<OUT>(ck, i0 + (uint32_t)j, e[j]);
-    } else if (valid > 0) {   // the grid chunks, as chunk_store8
-        uint32_t k = __umulhi(i0, ck.inv);
-        if (i0 - k * ck.S >= ck.S) ++k;
-        if (k > ck.nG - 1u) k = ck.nG - 1u;
-        uint32_t off = i0 - k * ck.S;
-        uint8_t* p = ck.base + (uint64_t)k * ck.row_bytes + (size_t)off * OB;
-        const int64_t back = (int64_t)ck.S * OB - (int64_t)ck.row_bytes;
-        while (off < ck.L) {
-            chunk_put8<OUT>(p, e);
-            if (k == 0) break;
-            --k;
-            off += ck.S;
-            p += back;
-        }
-    }
-    if (!ck.extra) return;
-    // the END chunk (a partial lane has stored its samples there already)
-    const uint32_t sl = ck.last, d = sl & 7u, g0 = sl - d;
-    uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
-    if (d == 0) {
-        if (!partial && valid > 0 && i0 >= sl && i0 - sl < ck.L) chunk_put8<OUT>(row + (size_t)(i0 - sl) * OB, e);
-        return;
-    }
-    const int lane = threadIdx.x & 63;
-    const bool in = !partial && valid > 0 && i0 >= g0 && i0 - g0 < ck.L && i0 + d < ck.T;   // the line that starts at sample i0 + d
-    const bool in0 = !partial && lane == 0 && valid > 0 && i0 >= g0 + 8u && i0 - 8u - g0 < ck.L;   // lane 0: the line that starts in the group before
-    if (!__any(in || in0)) return;
-    uint32_t n[8];
-    if (OB == 4) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) n[j] = (uint32_t)__shfl_down((int)e[j], 1, 64);
-    } else {
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const uint32_t w = (uint32_t)__shfl_down((int)(e[2 * m] | (e[2 * m + 1] << 16)), 1, 64);
-            n[2 * m] = w & 0xFFFFu;
-            n[2 * m + 1] = w >> 16;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        if (i0 + 8u + (uint32_t)j >= ck.T) n[j] = ck.padw;
-    if (in) {
-        // whole: the next group is behind the read's end, or the next lane's and all of it this row's
-        if (i0 + 8u >= ck.T || (lane != 63 && !(tail && i0 + 16u > re))) {
-            uint32_t o[8];
-            switch (d) {
-            case 1: chunk_shift<1>(e, n, o); break;
-            case 2: chunk_shift<2>(e, n, o); break;
-            case 3: chunk_shift<3>(e, n, o); break;
-            case 4: chunk_shift<4>(e, n, o); break;
-            case 5: chunk_shift<5>(e, n, o); break;
-            case 6: chunk_shift<6>(e, n, o); break;
-            default: chunk_shift<7>(e, n, o); break;
-            }
-            chunk_put8<OUT>(row + (size_t)(i0 - g0) * OB, o);
-        } else {   // (the rest of the line is stored by whoever holds the next group: lane 0 below, a partial lane, the next row)
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if ((uint32_t)j >= d) chunk_put1<OUT>(row + (size_t)(i0 - g0 + (uint32_t)j - d) * OB, e[j]);
-        }
-    }
-    if (in0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if ((uint32_t)j < d) chunk_put1<OUT>(row + (size_t)(i0 + (uint32_t)j - sl) * OB, e[j]);
-    }
-}
-
-// the chunk store of a row of a read: the row's samples at s0 ... s0 + count - 1 of the read's signal
-template <int OUT>
-struct RowChunkStore
-{
-    static constexpr uint32_t BYTES = OutBytes<OUT>::value;
-    ChunkK ck;
-    SigK sk;
-    uint32_t s0, re;
-    uint32_t rb = 0, rend = 0;   // OUT & SIG_RANGE: the read's range; ck is the range's, and the row lies at s0 - rb of the range's signal
-    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
-    {
-        if constexpr ((OUT & SIG_RANGE) != 0) {
-            const uint32_t p = s0 + i0;   // the lane's first sample in the read
-            if (((s0 - rb) & 7u) == 0) {   // (p - rb is a multiple of 8: the lane is wholly in front of the range, or starts inside a line of it)
-                const int v = (p < rb || p >= rend) ? 0 : (rend - p < (uint32_t)valid ? (int)(rend - p) : valid);
-                const uint32_t rowend = re < rend ? re : rend;   // where the row's samples end in the range ...
-                chunk_store8_row<OUT>(ck, p - rb, v, rowend > rb ? rowend - rb : 0u, base, s, sk);   // ... in the range's positions
-            } else {
-                uint32_t e[8];
-                chunk_elems8<OUT>(ck, valid, base, s, sk, e);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (j < valid && p + (uint32_t)j - rb < rend - rb) chunk_put_sample<OUT>(ck, p + (uint32_t)j - rb, e[j]);
-            }
-        } else if ((s0 & 7u) == 0) {
-            chunk_store8_row<OUT>(ck, s0 + i0, valid, re, base, s, sk);
-        } else {   // (the row begins inside a line: every sample on its own)
-            uint32_t e[8];
-            chunk_elems8<OUT>(ck, valid, base, s, sk, e);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (j < valid) chunk_put_sample<OUT>(ck, s0 + i0 + (uint32_t)j, e[j]);
-        }
-    }
-};
-
-// the read's chunk constants (chunk_constants with the plan's T and first chunk row)
-template <int OUT>
-__device__ __forceinline__ ChunkK chunk_constants_read(const ReadBatch& b, const Pod5Read& rd)
-{
-    constexpr uint32_t OB = OutBytes<OUT>::value;
-    ChunkK c;
-    c.T = rd.T;
-    c.L = b.sig.chunk_len;
-    c.S = b.sig.step;
-    c.K = chunk_count(c.T, c.L, c.S);
-    c.last = chunk_last_start(c.T, c.K, c.L, c.S, b.sig.mode, b.sig.end_align);
-    c.extra = b.sig.mode == CHUNK_END && c.K >= 2;
-    c.nG = c.extra ? c.K - 1 : c.K;
-    c.row_bytes = (uint64_t)c.L * OB;
-    c.base = b.dst + rd.row * c.row_bytes;
-    c.inv = (uint32_t)(0x100000000ull / c.S);
-    if (OB == 4) c.padw = __float_as_uint(b.sig.pad);
-    else c.padw = sig_pack2<OUT & 3>(b.sig.pad, b.sig.pad) & 0xFFFFu;
-    return c;
+    st.ck = chunk_constants<OUT>(b, st.rend - st.rb, rd.row);
+    st.sk = sig_constants(b, rw.read);
+    st.s0 = rw.s0;
+    st.re = rw.s0 + count;
+    st.pad_elems = (rd.flags & POD5_READ_PAD_ELEMS) != 0;
+    return st;
 }
 
 // The store pass over reads: one workgroup per row, OUT a typed or a chunk store.  The read's pad positions are written here, once, by
@@ -2825,21 +2725,7 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
     const Pod5Row rw = pr.rows[r];
-    if ((OUT & SIG_CHUNK) && (rw.flags & POD5_ROW_PAD)) {
-        constexpr uint32_t OB = OutBytes<OUT>::value;
-        Pod5Read rd = pr.reads[rw.read];
-        if (OUT & SIG_RANGE) rd.T = pr.range[rw.read].y - pr.range[rw.read].x;   // (the chunking is the range's)
-        const ChunkK ck = chunk_constants_read<OUT>(b, rd);
-        if (ck.K != 0) {
-            uint8_t* row = ck.base + (uint64_t)(ck.K - 1u) * ck.row_bytes;
-            const uint32_t p0 = ck.T - ck.last, l0 = (p0 + 7u) >> 3;   // the first pad position, the first line of nothing else
-            if ((rd.flags & POD5_READ_PAD_ELEMS) && p0 + (uint32_t)tid < l0 * 8u) chunk_put1<OUT>(row + (size_t)(p0 + (uint32_t)tid) * OB, ck.padw);
-            uint32_t e[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) e[j] = ck.padw;
-            for (uint32_t j = l0 + (uint32_t)tid; j < (ck.L >> 3); j += WG) chunk_put8<OUT>(row + (size_t)j * 8u * OB, e);
-        }
-    }
+    if ((OUT & SIG_CHUNK) && (rw.flags & POD5_ROW_PAD)) row_chunk_store<OUT>(b, pr, rw, 0u).finish();
     uint32_t in_size = 0, count = 0, verdict;
     if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
         if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
@@ -2848,18 +2734,7 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
     const uint8_t* in = b.src + b.src_off[r];
     bool good;
     if (OUT & SIG_CHUNK) {
-        RowChunkStore<OUT> st;
-        Pod5Read rd = pr.reads[rw.read];
-        if (OUT & SIG_RANGE) {
-            const uint2 g = pr.range[rw.read];
-            st.rb = g.x;
-            st.rend = g.y;
-            rd.T = g.y - g.x;
-        }
-        st.ck = chunk_constants_read<OUT>(b, rd);
-        st.sk = sig_constants(b, rw.read);
-        st.s0 = rw.s0;
-        st.re = rw.s0 + count;
+        const ChunkStore<OUT, true> st = row_chunk_store<OUT>(b, pr, rw, count);
         good = svb16_decode_row(in, in_size, count, st, stage, wsum);
     } else {
         const DecStore<2, OUT> st(b.dst, b.dst_off, &b, r, count, rw.read);
