@@ -404,6 +404,67 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_norm_range_batch(vbz_gpu_ctx* ctx, const vbz_
                                                     uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm,
                                                     float* shift_scale, const vbz_gpu_sample_ranges* ranges);
 
+/* Signal trim.  The two calls below find, on the device, the sample at which each read's signal proper begins -- the trim point the
+ * basecallers cut at -- and write it to a per-read table begin[] that is, as it stands, the vbz_gpu_sample_ranges.begin of the *_range_batch
+ * calls above: no host round trip lies between finding the trim and chunking signal[trim:].  They are the statistics-alone calls
+ * (vbz_gpu_signal_norm_range_batch, vbz_gpu_pod5_signal_norm_range_batch) with one more pass of the svb decoder behind the counting passes;
+ * the zstd stage still runs once per call.
+ * The rule.  A read has T raw 16-bit values x_j (int16 or uint16 per is_signed).  {shift, scale} is the float32 pair the statistics call
+ * gives for the same norm and ranges (ranges applies to the statistics only -- NULL: the whole read; either `stats` value is accepted, with
+ * the meaning it has there).  With W = window, m = min_elements, t0 = min_trim, M = max_samples, f = threshold_factor:
+ *   threshold   thr = float64(shift) + float64(f) * float64(scale): one multiply, then one add, each rounded to nearest even (no fused
+ *               multiply-add).
+ *   high        sample j is high when float64(x_j) > thr; a sample equal to thr is not.
+ *   windows     N = min(M, T); nW = N > t0 ? (N - t0) / W : 0 (integer division); window k covers positions [t0 + k W, t0 + (k + 1) W) and
+ *               ends at e_k = t0 + (k + 1) W.
+ *   scan        walk k = 0 ... nW - 1 with seen = false.  A window that holds MORE than m high samples sets seen.  While seen is not set
+ *               the walk goes on to the next window.  Once it is set (the window that set it included): a window whose last sample
+ *               x[e_k - 1] is high -- whatever its count -- goes on to the next window; the first whose last sample is not high stops the walk.
+ *   verdict     on the stopping window: min(t0, T) when VBZ_GPU_TRIM_REJECT_AT_END is set and e_k >= N; min(t0, T) when
+ *               float64(e_k) > float64(max_fraction) * float64(T); otherwise e_k.  A walk that ends without stopping -- no peak, or a peak that
+ *               never comes down -- gives min(t0, T).
+ * begin[i] (device, one word per read) is the answer for read i, and 0 for a read whose result[i] is an error code.  result[i] is what the
+ * statistics call gives; the pod5 call also writes read_result[k] as that call does.  shift_scale (nullable here) is written when given.
+ * Nothing else is written; batch->dst may be NULL.  POD5 reads of several rows: everything is per READ, over the concatenated signal; begin
+ * has n_reads entries; a read with a failing row gets 0; a bad first_row fails whole as in the statistics call, and begin is not written.
+ * Both return 0 when queued, -1 for a NULL context or batch or a launch failure, and -2 (nothing launched) for everything the statistics call
+ * refuses, a NULL trim or begin, a field outside its rule, reserved != 0, unknown flags, and (M - min(t0, M)) / W > 4096: a read's windows
+ * must fit the counting passes' bins.
+ * The tools.  With VBZ_GPU_NORM_MED_MAD or VBZ_GPU_NORM_QUANTILE as norm, W = 40, m = 3, t0 = 10, M = 8000 and f = 2.4 this is the shape of
+ * the trim Bonito and Dorado apply; they differ in which samples the statistics are taken over (the range table says that) and in the two
+ * rejection rules (max_fraction and VBZ_GPU_TRIM_REJECT_AT_END say those).  This library was written without either tool's source: the
+ * rule above is the contract, not "what Bonito does".
+ * The hand-over.  begin[] goes straight into vbz_gpu_range_samples_batch (as ranges.begin), its output into vbz_gpu_chunk_layout_batch, and
+ * both into vbz_gpu_decompress_chunks_range_batch, all on the context's stream.  A caller that normalises by the whole read can hand the
+ * chunk call format->offset = -shift and format->scale = float32(1 / float64(scale)) from shift_scale as given constants (norm = NULL): that
+ * saves its counting passes, and the chunks are bit for bit those of VBZ_GPU_RANGE_STATS_READ.
+ * How: the trim pass is one more store of the svb decoder.  It turns thr into the smallest high key once per read, counts
+ * the high samples of the prefix [t0, t0 + nW W) per window in the LDS bins of the counting passes (most samples are not high and cost no
+ * LDS operation), leaves the tile loop behind the prefix, and one wavefront scans the window words by ballot; on the large-read path the
+ * segments add their words up in scratch and a launch of its own scans.  Measured on one MI355X, 65 536 reads of ~100 k samples, the
+ * defaults above (tools/time_trim.py, profiles/HISTORY.md "Signal trim"): statistics alone 11.7 ms (MED_MAD) / 11.6 ms (QUANTILE), the trim
+ * call 12.3 / 12.1 ms -- the trim pass costs about 0.5 ms, its kernel 5 - 6 % of the first counting pass's time; trim call + range_samples +
+ * layout + ranged normalised chunk call 34.7 ms; int16 decode + torch median / MAD + the window walk in torch + the same chunk call 735 ms.
+ * One 20 M-sample read: statistics 0.435 ms, trim call 0.439 ms. */
+#define VBZ_GPU_TRIM_REJECT_AT_END 1u
+typedef struct vbz_gpu_trim
+{
+    uint32_t window;        /* W: samples per window, 1 ... 65536 */
+    uint32_t min_elements;  /* m: a window opens the peak when MORE than m of its samples are high */
+    uint32_t min_trim;      /* t0: samples in front of the first window; also the answer when no trim is found */
+    uint32_t max_samples;   /* M >= 1: only the first min(M, T) samples are looked at */
+    float threshold_factor; /* f, finite */
+    float max_fraction;     /* finite, 0 < max_fraction <= 1: a trim beyond this share of the read is rejected (1: never) */
+    uint32_t flags;         /* VBZ_GPU_TRIM_* */
+    uint32_t reserved;      /* must be 0 */
+} vbz_gpu_trim;             /* 32 bytes */
+VBZ_EXPORT int vbz_gpu_signal_trim_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                         uint32_t is_signed, const vbz_gpu_normalization* norm, const vbz_gpu_sample_ranges* ranges,
+                                         const vbz_gpu_trim* trim, float* shift_scale, uint32_t* begin);
+VBZ_EXPORT int vbz_gpu_pod5_signal_trim_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                              uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm,
+                                              const vbz_gpu_sample_ranges* ranges, const vbz_gpu_trim* trim, float* shift_scale, uint32_t* begin);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -131,6 +131,24 @@ class GpuSampleRanges(ctypes.Structure):
     ]
 
 
+VBZ_GPU_TRIM_REJECT_AT_END = 1   # vbz_gpu_trim.flags: a trim whose window ends at the end of the samples looked at is rejected
+
+
+class GpuTrim(ctypes.Structure):
+    """struct vbz_gpu_trim of include/vbz_gpu.h (32 bytes)."""
+
+    _fields_ = [
+        ("window", ctypes.c_uint32),
+        ("min_elements", ctypes.c_uint32),
+        ("min_trim", ctypes.c_uint32),
+        ("max_samples", ctypes.c_uint32),
+        ("threshold_factor", ctypes.c_float),
+        ("max_fraction", ctypes.c_float),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -168,6 +186,8 @@ GPU_API = [
     "vbz_gpu_signal_norm_range_batch",
     "vbz_gpu_pod5_decompress_chunks_range_batch",
     "vbz_gpu_pod5_signal_norm_range_batch",
+    "vbz_gpu_signal_trim_batch",
+    "vbz_gpu_pod5_signal_trim_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -297,6 +317,15 @@ def load():
         L.vbz_gpu_pod5_decompress_chunks_range_batch.argtypes = [vp, bp, op, fp, cp, rp, vp, vp, u64, np_, vp, gp]
         L.vbz_gpu_pod5_signal_norm_range_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_signal_norm_range_batch.argtypes = [vp, bp, op, u32, rp, np_, vp, gp]
+    if hasattr(L, "vbz_gpu_signal_trim_batch"):   # (likewise: builds of earlier rounds find no trim point)
+        np_ = ctypes.POINTER(GpuNormalization)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        gp = ctypes.POINTER(GpuSampleRanges)
+        tp = ctypes.POINTER(GpuTrim)
+        L.vbz_gpu_signal_trim_batch.restype = ctypes.c_int
+        L.vbz_gpu_signal_trim_batch.argtypes = [vp, bp, op, ctypes.c_int, u32, np_, gp, tp, vp, vp]
+        L.vbz_gpu_pod5_signal_trim_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_signal_trim_batch.argtypes = [vp, bp, op, u32, rp, np_, gp, tp, vp, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -43,6 +43,30 @@ MED_MAD = Normalization("med_mad", scale_mul=1.4826)                            
 DORADO_QUANTILE = Normalization("quantile", 0.2, 0.9, 0.51, 0.53, 10.0, 1.0)          # Dorado: q20 / q90
 
 
+@dataclasses.dataclass(frozen=True)
+class Trim:
+    """Where a read's signal proper begins (include/vbz_gpu.h: vbz_gpu_trim): a sample is high above shift + threshold_factor * scale;
+    the first window of `window` samples behind min_trim with more than min_elements high samples opens the peak, the first window at
+    or behind it whose last sample is not high ends it, and that window's end is the trim -- min_trim when there is none in the first
+    max_samples samples, when it lies beyond max_fraction of the read, or (reject_at_end) when its window is the last one looked at.
+    The defaults are the shape of the trim Bonito and Dorado apply."""
+
+    window: int = 40
+    min_elements: int = 3
+    min_trim: int = 10
+    max_samples: int = 8000
+    threshold_factor: float = 2.4
+    max_fraction: float = 1.0
+    reject_at_end: bool = False
+
+    def c_struct(self):
+        t = _lib.GpuTrim()
+        t.window, t.min_elements, t.min_trim, t.max_samples = self.window, self.min_elements, self.min_trim, self.max_samples
+        t.threshold_factor, t.max_fraction = self.threshold_factor, self.max_fraction
+        t.flags = _lib.VBZ_GPU_TRIM_REJECT_AT_END if self.reject_at_end else 0
+        return t
+
+
 def _u32(t):
     """view an int32 result tensor as python ints in [0, 2**32)"""
     return [int(x) & 0xFFFFFFFF for x in t.tolist()]
@@ -235,6 +259,42 @@ class GpuCodec:
         finally:
             self._exit(cur)
         return shift_scale
+
+    def _trim_args(self, n, trim, out, shift_scale):
+        """(the C struct, the begin table, shift_scale or None) of a trim call over n reads.  out: an int32 tensor of n entries on the
+        device (allocated when None); shift_scale: None (not wanted), True (allocated) or a float32 [n, 2] tensor"""
+        trim = Trim() if trim is None else trim
+        assert isinstance(trim, Trim), trim
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and int(out.numel()) == n, (out.dtype, out.shape)
+        if shift_scale is True:
+            shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        return trim.c_struct(), out, shift_scale
+
+    def signal_trim(self, src, src_off, src_size, dst_off, dst_cap, result, opts, norm, trim=None, out=None, shift_scale=None, signed=True,
+                    sized=False, begin=None, end=None, stats=None):
+        """Every read's trim point (include/vbz_gpu.h: vbz_gpu_signal_trim_batch) -> int32 [n] on the device (uint32 bits; `out` when
+        given), which is the begin= of decompress_chunks and range_samples as it stands.  trim: a Trim (None: the defaults).  The
+        threshold comes from the statistics signal_norm gives for the same norm / begin / end / stats -- those three say which samples
+        the STATISTICS are taken over, nothing else.  shift_scale: True or a float32 [n, 2] tensor to get the constants as well; the
+        return is then (begin, shift_scale).  dst_off / dst_cap: the int16 layout of the reads (nothing is stored)."""
+        n = int(src_off.numel())
+        g, keep = self._ranges(n, begin, end, stats)
+        t, out, shift_scale = self._trim_args(n, trim, out, shift_scale)
+        m, ss = self._norm_args(n, norm, shift_scale, None, None)
+        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
+        b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
+        b.dst = None
+        b.dst_bytes = int(dst_off.max().item() + dst_cap.to(torch.int64).max().item()) if n else 0
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_signal_trim_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)), ctypes.byref(m),
+                                                      ctypes.byref(g) if g is not None else None, ctypes.byref(t), ss, out.data_ptr()),
+                     "signal_trim_batch")
+        finally:
+            self._exit(cur)
+        return out if shift_scale is None else (out, shift_scale)
 
     def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False,
                           norm=None, norm_out=None):
@@ -636,6 +696,31 @@ class GpuCodec:
         finally:
             self._exit(cur)
         return shift_scale, read_result
+
+    def pod5_signal_trim(self, src, src_off, src_size, row_samples, read_first_row, result, norm, trim=None, out=None, shift_scale=None,
+                         signed=True, begin=None, end=None, stats=None):
+        """Every READ's trim point over its concatenated signal (vbz_gpu_pod5_signal_trim_batch) -> (begin int32 [n_reads], read_result),
+        or (begin, shift_scale, read_result) with shift_scale (True, or a float32 [n_reads, 2] tensor).  The arguments are signal_trim's,
+        per read; result is per ROW."""
+        n = int(src_off.numel())
+        opts = pod5_options()
+        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        g, keep = self._ranges(r.n_reads, begin, end, stats)
+        t, out, shift_scale = self._trim_args(r.n_reads, trim, out, shift_scale)
+        m, ss = self._norm_args(r.n_reads, norm, shift_scale, None, None)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
+        b = self._batch(src, src_off, src_size, no_dst, dst_off[:n], dst_cap, result)
+        b.dst = None
+        b.dst_bytes = int(dst_off[-1].item())
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_pod5_signal_trim_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
+                                                           ctypes.byref(m), ctypes.byref(g) if g is not None else None, ctypes.byref(t), ss,
+                                                           out.data_ptr()), "pod5_signal_trim_batch")
+        finally:
+            self._exit(cur)
+        return (out, read_result) if shift_scale is None else (out, shift_scale, read_result)
 
     def pod5_decompress_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, dtype=torch.float32, signed=True,
                                     norm_out=None, align=16):

@@ -646,11 +646,95 @@ struct RangeK<true>
     mutable uint32_t s0 = 0;
 };
 
+// ---- signal trim (OUT = SIG_TRIM; vbz_kernels.h TrimOut; the rule: include/vbz_gpu.h) ---------------------------------------------------
+// The trim store's state, per read and workgroup-uniform.  A sample is high when float64(x) > thr; on the key u the counting pass forms
+// (x = u - kx) that is u >= hk, hk the smallest high key, clamped to [0, 65536] (65536: no sample is high).  Window k = (p - t0) / W of
+// the nW windows in front of `end` = t0 + nW W <= N = min(M, T); word k of the counting passes' bins (NormLds::h; the large-read path:
+// the read's slab) counts the window's high samples, and its bit 31 says that the window's last sample is high.
+template <bool ON>
+struct TrimK
+{
+};
+template <>
+struct TrimK<true>
+{
+    NormLds* L = nullptr;
+    uint32_t* out = nullptr;    // the read's entry of TrimOut::begin
+    uint32_t* slab = nullptr;   // large-read path: the read's words in scratch (the segments add theirs up there), else nullptr
+    uint32_t hk = 0x10000u, kx = 0;
+    uint32_t t0 = 0, W = 1, m = 0, flags = 0, T = 0, N = 0, nW = 0, span = 0, end = 0;   // span = nW W
+    uint32_t mul = 0, sh = 0;   // d / W = d mul >> sh for d < 2^28 (span <= TRIM_MAX_WINDOWS x 65536 = 2^28)
+    float max_fraction = 1.0f;
+    mutable uint32_t s0 = 0;    // where the values handed to put() begin in the read (a POD5 read's pass sets it row by row)
+};
+
+// the state of read r of T samples whose statistics are final (its {shift, scale} in NormOut::ss)
+__device__ __forceinline__ TrimK<true> trim_state(const ReadBatch& b, const TrimOut& tr, uint32_t r, uint32_t T)
+{
+    const NormOut& no = b.sig.norm;
+    const uint32_t i = no.map ? no.map[r] : r;
+    TrimK<true> k;
+    k.out = tr.begin + i;
+    k.kx = b.sig.bias ^ 0x8000u;
+    k.t0 = tr.t0;
+    k.W = tr.W;
+    k.m = tr.m;
+    k.flags = tr.flags;
+    k.max_fraction = tr.max_fraction;
+    k.T = T;
+    k.N = tr.M < T ? tr.M : T;
+    k.nW = k.N > k.t0 ? (k.N - k.t0) / k.W : 0u;
+    if (k.nW > TRIM_MAX_WINDOWS) k.nW = TRIM_MAX_WINDOWS;   // (the host refuses such a trim: no word is formed outside the bins whatever comes in)
+    k.span = k.nW * k.W;
+    k.end = k.nW ? k.t0 + k.span : 0u;
+    uint32_t l = 0;
+    while ((1u << l) < k.W) ++l;   // d < 2^28 and W <= 2^l: ceil(2^(28 + l) / W) <= 2^29 gives the exact quotient
+    k.sh = 28u + l;
+    k.mul = (uint32_t)((((uint64_t)1 << k.sh) + k.W - 1u) / k.W);
+    if (k.nW) {
+        const float2 ss = no.ss[i];
+        const double thr = __dadd_rn((double)ss.x, __dmul_rn((double)tr.f, (double)ss.y));   // (multiply, then add: no FMA)
+        const double h = floor(thr) + 1.0 + (double)k.kx;   // the smallest key above thr (exact: |thr| beyond 2^52 only where it is clamped)
+        k.hk = !(thr == thr) ? 0x10000u : (h >= 65536.0 ? 0x10000u : (h > 0.0 ? (uint32_t)h : 0u));
+    }
+    return k;
+}
+
+// The scan of a read's nW window words h[], by one wavefront (wave-uniform): the first window with more than m high samples opens the
+// peak, the first window at or behind it whose last sample is not high ends it, and that window's end is the answer unless one of the
+// two rejections sends it back to min(t0, T) -- as no peak and a peak that never comes down do.  Lane 0 writes the read's begin entry.
+__device__ __forceinline__ void trim_scan(const uint32_t* h, const TrimK<true>& k)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t ans = k.t0 < k.T ? k.t0 : k.T;
+    bool seen = false;
+    for (uint32_t base = 0; base < k.nW; base += 64u) {
+        const bool valid = base + lane < k.nW;
+        const uint32_t v = valid ? h[base + lane] : 0u;
+        uint64_t from = ~0ull;
+        if (!seen) {
+            const uint64_t mo = __ballot(valid && (v & 0x7FFFFFFFu) > k.m ? 1 : 0);
+            if (!mo) continue;
+            seen = true;
+            from <<= (uint32_t)__ffsll((unsigned long long)mo) - 1u;
+        }
+        const uint64_t ms = __ballot(valid && !(v >> 31) ? 1 : 0) & from;
+        if (ms) {
+            const uint32_t e = k.t0 + (base + (uint32_t)__ffsll((unsigned long long)ms)) * k.W;   // the stopping window's end
+            const bool reject = ((k.flags & TRIM_REJECT_AT_END) && e >= k.N) || (double)e > __dmul_rn((double)k.max_fraction, (double)k.T);
+            if (!reject) ans = e;
+            break;
+        }
+    }
+    if (lane == 0) *k.out = ans;
+}
+
 // ---- the decoder's output: what svb_decode_range and I16DecPairs store, where, and in how many bytes per value -----------------------
 // OUT = SIG_NONE: the ELEM-byte values into the read's slot (dst + dst_off[r]).  SIG_*: the typed samples of int16 values into the read's
 // typed slot (dst + dst_off[r] / 2 * E: dst_off is the int16 layout's).  SIG_* | SIG_CHUNK: the typed samples into the read's chunks.
 // | SIG_RANGE (the chunk stores and SIG_COUNT): the read is its samples [b, e) -- the others are decoded (the delta chain needs them) and
 // neither converted, stored nor counted.  The chunk case is a ChunkStore with s0 = 0 and re = T: put() and finish() are its.
+// SIG_TRIM: the trim pass -- nothing is stored; the high samples of the read's prefix are counted per window (open_trim() gives the state).
 template <int ELEM, int OUT>
 struct DecStore
 {
@@ -664,6 +748,8 @@ struct DecStore
     mutable uint32_t nbelow[NORM_WINDOWS] = {};  // SIG_COUNT: this lane's keys below each window
     static constexpr bool RANGED = (OUT & SIG_RANGE) != 0;
     [[no_unique_address]] RangeK<RANGED> rg;     // SIG_COUNT | SIG_RANGE
+    static constexpr bool TRIM = (OUT & SIG_TRIM) != 0;
+    [[no_unique_address]] TrimK<TRIM> tk;        // SIG_TRIM
 
     // b: the batch, for the typed stores only -- SIG_NONE gets nullptr and the batch's fields (a reference to the kernel's ReadBatch
     // argument would cost its loads their scalar form)
@@ -703,6 +789,8 @@ struct DecStore
             for (uint32_t i = threadIdx.x; i < NORM_WINDOWS * NORM_BINS / 4; i += WG) h[i] = make_uint4(0u, 0u, 0u, 0u);
             if (threadIdx.x < NORM_WINDOWS) nk.L->below[threadIdx.x] = 0;
             __syncthreads();
+        } else if (OUT & SIG_TRIM) {
+            out = nullptr;
         } else if (OUT & SIG_CHUNK) {
             out = dst;
             cs.ck = chunk_constants<OUT>(*b, count, b->sig.row[r]);
@@ -717,12 +805,34 @@ struct DecStore
         }
     }
 
+    // SIG_TRIM, all threads of the workgroup: the read's state, and its window words zeroed
+    __device__ __forceinline__ void open_trim(const TrimK<TRIM>& k)
+    {
+        if constexpr (TRIM) {
+            tk = k;
+            tk.L = norm_lds();
+            for (uint32_t i = threadIdx.x; i < tk.nW; i += WG) tk.L->h[i] = 0;
+            __syncthreads();
+        }
+    }
+
     // whole 16-byte lines may be stored: the tile loop's lanes of VPL values, and I16DecPairs at all (the counting pass stores nothing)
     __device__ __forceinline__ bool aligned() const { return (((uintptr_t)out) & 15u) == 0; }
 
     // one lane's values i0 ... i0 + valid - 1 (base + s[k]).  The chunk store takes every lane of the workgroup at the same point.
     __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[VPL]) const
     {
+        if constexpr (TRIM) {   // one LDS increment per HIGH value of the prefix: its window's word (most values are not high)
+#pragma unroll
+            for (int k = 0; k < VPL; ++k) {
+                const uint32_t u = ((base + s[k]) ^ tk.kx) & 0xFFFFu, d = tk.s0 + i0 + (uint32_t)k - tk.t0;
+                if (k < valid && u >= tk.hk && d < tk.span) {
+                    const uint32_t w = (uint32_t)(((uint64_t)d * tk.mul) >> tk.sh);
+                    atomicAdd(&tk.L->h[w], d - w * tk.W == tk.W - 1u ? 0x80000001u : 1u);   // (bit 31: the window's last sample)
+                }
+            }
+            return;
+        }
         if (OUT & SIG_COUNT) {   // one LDS increment per value: its key's bin
 #pragma unroll
             for (int k = 0; k < VPL; ++k) {
@@ -792,8 +902,22 @@ struct DecStore
 
     // after this workgroup's values (svb_decode_range, MODE 0), by the whole workgroup: the counting pass's counts are complete -- a read
     // on one workgroup is selected from LDS, a segment of the large-read path adds them to the read's slab
+    // The trim pass: a read on one workgroup is scanned from LDS by one wavefront; a segment adds its non-zero words to the read's slab
+    // (added, never stored: a window may straddle two segments; bit 31 comes from one sample only, so the sums do not carry into it).
     __device__ __forceinline__ void done() const
     {
+        if constexpr (TRIM) {
+            __syncthreads();
+            if (tk.slab) {
+                for (uint32_t i = threadIdx.x; i < tk.nW; i += WG) {
+                    const uint32_t v = tk.L->h[i];
+                    if (v) atomicAdd(tk.slab + i, v);
+                }
+            } else if (threadIdx.x < 64) {
+                trim_scan(tk.L->h, tk);
+            }
+            return;
+        }
         if (!(OUT & SIG_COUNT)) return;
         const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -2355,8 +2479,10 @@ __global__ __launch_bounds__(WG) void svb16_encode_kernel(ReadBatch b, uint32_t*
 // One row's stream (in_size bytes at `in`, K <= in_size <= svb16_max(count)) through st.put(), a tile a trip, by the whole workgroup:
 // whether the stream is exactly as long as its key bits announce.  stage / wsum: the kernel's LDS.  This is svb16_decode_kernel's tile
 // loop for the kernels over reads; that kernel keeps its own text, which as a call of this function compiles to other registers.
-template <class Store>
-__device__ __forceinline__ bool svb16_decode_row(const uint8_t* in, uint32_t in_size, uint32_t count, const Store& st, uint8_t* stage, uint32_t* wsum)
+// PREFIX (the trim pass): only the row's first min(stop, count) samples are walked, and the return says nothing about the stream's length.
+template <class Store, bool PREFIX = false>
+__device__ __forceinline__ bool svb16_decode_row(const uint8_t* in, uint32_t in_size, uint32_t count, const Store& st, uint8_t* stage, uint32_t* wsum,
+                                                 uint32_t stop = 0)
 {
     const int tid = threadIdx.x;
     const uint32_t K = (count + 7u) >> 3;
@@ -2365,9 +2491,10 @@ __device__ __forceinline__ bool svb16_decode_row(const uint8_t* in, uint32_t in_
     uint64_t pos = 0;   // data bytes consumed
     uint32_t run = 0;   // the delta chain's running value
     bool good = true;
-    for (uint32_t t0 = 0; t0 < count; t0 += SVB16_TILE) {
+    const uint32_t lim = PREFIX && stop < count ? stop : count;
+    for (uint32_t t0 = 0; t0 < lim; t0 += SVB16_TILE) {
         const uint32_t i0 = t0 + (uint32_t)tid * 8u;
-        const int valid = i0 >= count ? 0 : (count - i0 >= 8u ? 8 : (int)(count - i0));
+        const int valid = i0 >= lim ? 0 : (lim - i0 >= 8u ? 8 : (int)(lim - i0));
         const uint32_t key = valid > 0 ? (uint32_t)in[i0 >> 3] & ((1u << valid) - 1u) : 0u;   // (unused key bits ignored)
         const uint32_t L = (uint32_t)valid + (uint32_t)__popc(key);
         uint32_t tot;
@@ -2787,6 +2914,149 @@ __global__ __launch_bounds__(WG) void svb16_count_reads_range_kernel(ReadBatch b
     svb16_count_reads<SIG_COUNT | SIG_RANGE>(b, pr, verdicts);
 }
 
+// ---- the trim pass (OUT = SIG_TRIM; vbz_kernels.h TrimOut), behind the last counting pass ------------------------------------------------
+// The counting passes walked every stream to its end and left the verdicts, so this pass owes none: it reads result[] and walks only the
+// prefix [0, t0 + nW W) of every read that has no error -- whatever its NormRead::phase.  Every begin entry has one writer: the read's
+// workgroup (one wavefront of it), or on the large-read path trim_select_kernel's.
+// Read r of a trim launch, by the whole workgroup: false when there is nothing to decode -- the read is another launch group's (nothing is
+// written), it has an error verdict (begin 0) or no window (begin min(t0, T)); else *k is its state.
+__device__ __forceinline__ bool trim_read_open(const ReadBatch& b, const TrimOut& tr, uint32_t r, TrimK<true>* k)
+{
+    const uint32_t g = b.gate ? b.gate[r] : 0u;
+    if (g == GATE_SKIP) return false;
+    if (g >= E_FIRST || b.result[r] >= E_FIRST) {
+        if (threadIdx.x == 0) tr.begin[b.sig.norm.map ? b.sig.norm.map[r] : r] = 0;
+        return false;
+    }
+    *k = trim_state(b, tr, r, b.dst_cap[r] >> 1);
+    if (k->nW == 0) {
+        if (threadIdx.x == 0) *k->out = k->t0 < k->T ? k->t0 : k->T;
+        return false;
+    }
+    return true;
+}
+
+// one workgroup per read: svb_decode_kernel's walk, left behind the prefix
+template <bool ZZ, bool I16ZZ>
+__global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_trim_kernel(ReadBatch b, TrimOut tr)
+{
+    constexpr int STAGE = I16ZZ ? 2 * (int)I16DecPairs::BUF : WG * Vpl<2>::value * 4 + 48;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[I16ZZ ? (int)I16DecPairs::WS_WORDS : 4];
+
+    const uint32_t r = blockIdx.x;
+    TrimK<true> k;
+    if (!trim_read_open(b, tr, r, &k)) return;
+    const uint32_t in_size = b.src_size[r], count = k.T, keyLen = (count + 3u) >> 2;
+    const uint8_t* in = b.src + b.src_off[r];
+    uint64_t pos = 0;
+    uint32_t run = 0;
+    DecStore<2, SIG_TRIM> st(nullptr, nullptr, &b, r, count);
+    st.open_trim(k);
+    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, in_size - keyLen, count, 0, k.end, pos, run, st, stage, wsum);
+}
+
+// The large-read path: svb_seg_decode_kernel's MODE 0 at the positions its passes left (seg_val / seg_pos / seg_run as that kernel reads
+// them).  A segment that starts at or behind the prefix's end returns at once; the others add their words to the read's slab.
+template <bool ZZ, bool I16ZZ, bool SELF>
+__global__ __launch_bounds__(WG) void svb_seg_trim_kernel(ReadBatch b, const uint32_t* seg_first, const uint32_t* seg_val, const uint64_t* seg_pos,
+                                                          const uint32_t* seg_run, TrimOut tr)
+{
+    constexpr uint32_t SEG = WG * Vpl<2>::value * SEG_TILES;
+    constexpr int STAGE = I16ZZ ? 2 * (int)I16DecPairs::BUF : WG * Vpl<2>::value * 4 + 48;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[I16ZZ ? (int)I16DecPairs::WS_WORDS : 4];
+    __shared__ uint64_t sums_s[8];
+    uint32_t r, sg;
+    if (!seg_locate(seg_first, b.n_reads, blockIdx.x, r, sg)) return;
+    if ((b.gate && b.gate[r] >= GATE_SKIP) || b.result[r] >= E_FIRST) return;   // (trim_select_kernel writes the read's 0)
+    const uint32_t count = b.dst_cap[r] >> 1, first = sg * SEG;
+    TrimK<true> k = trim_state(b, tr, r, count);
+    if (first >= k.end) return;
+    k.slab = b.sig.norm.slab + (size_t)r * NORM_SLAB;
+    uint64_t pos = 0;
+    uint32_t run = 0;
+    if (SELF) {
+        uint64_t total, self_run = 0;
+        seg_sums(seg_val, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, pos, total);
+        if (ZZ) seg_sums(seg_run, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_run, total);
+        run = (uint32_t)self_run;
+    } else {
+        pos = seg_pos[blockIdx.x];
+        run = ZZ ? seg_run[blockIdx.x] : 0u;
+    }
+    const uint32_t end = k.end - first > SEG ? first + SEG : k.end, keyLen = (count + 3u) >> 2;
+    const uint8_t* in = b.src + b.src_off[r];
+    DecStore<2, SIG_TRIM> st(nullptr, nullptr, &b, r, count);
+    st.open_trim(k);
+    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, b.src_size[r] - keyLen, count, first, end, pos, run, st, stage, wsum);
+}
+
+// one workgroup per read of the large-read path: the words the segments added to the read's slab (zeroed again) -> the scan
+__global__ __launch_bounds__(WG) void trim_select_kernel(ReadBatch b, TrimOut tr)
+{
+    const uint32_t r = blockIdx.x;
+    TrimK<true> k;
+    if (!trim_read_open(b, tr, r, &k)) return;
+    NormLds* L = norm_lds();
+    uint32_t* slab = b.sig.norm.slab + (size_t)r * NORM_SLAB;
+    for (uint32_t i = threadIdx.x; i < k.nW; i += WG) {
+        L->h[i] = slab[i];
+        slab[i] = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) trim_scan(L->h, k);
+}
+
+// a POD5 row as a read of its own
+__global__ __launch_bounds__(WG) void svb16_trim_kernel(ReadBatch b, TrimOut tr)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+
+    const uint32_t r = blockIdx.x;
+    TrimK<true> k;
+    if (!trim_read_open(b, tr, r, &k)) return;
+    DecStore<2, SIG_TRIM> st(nullptr, nullptr, &b, r, k.T);
+    st.open_trim(k);
+    (void)svb16_decode_row<DecStore<2, SIG_TRIM>, true>(b.src + b.src_off[r], b.src_size[r], k.T, st, stage, wsum, k.end);
+    st.done();
+}
+
+// POD5 reads of several rows: one workgroup per READ walks its rows as svb16_count_reads does, up to the row that holds the prefix's last
+// sample.  A read with a failing row gets 0; a bad first_row leaves begin alone.
+__global__ __launch_bounds__(WG) void svb16_trim_reads_kernel(ReadBatch b, Pod5Reads pr, TrimOut tr)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+
+    if (*pr.bad) return;
+    const uint32_t q = blockIdx.x;
+    const uint32_t first = pr.first_row[q], end = pr.first_row[q + 1];
+    int failed = 0;
+    for (uint32_t r = first + threadIdx.x; r < end; r += WG) failed |= b.result[r] >= E_FIRST ? 1 : 0;
+    if (__syncthreads_or(failed)) {
+        if (threadIdx.x == 0) tr.begin[q] = 0;
+        return;
+    }
+    const TrimK<true> k = trim_state(b, tr, q, pr.reads[q].T);
+    if (k.nW == 0) {
+        if (threadIdx.x == 0) *k.out = k.t0 < k.T ? k.t0 : k.T;
+        return;
+    }
+    DecStore<2, SIG_TRIM> st(nullptr, nullptr, &b, q, k.T);
+    st.open_trim(k);
+    for (uint32_t r = first; r < end; ++r) {
+        const uint32_t s0 = pr.rows[r].s0;
+        if (s0 >= k.end) break;
+        uint32_t in_size = 0, count = 0, verdict;
+        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) continue;   // (an empty row)
+        st.tk.s0 = s0;   // (put() gets positions in the row)
+        (void)svb16_decode_row<DecStore<2, SIG_TRIM>, true>(b.src + b.src_off[r], in_size, count, st, stage, wsum, k.end - s0);
+    }
+    st.done();
+}
+
 // read_result[k]: the code of the read's first failing row, else T * elem
 __global__ __launch_bounds__(WG) void pod5_read_results_kernel(ReadBatch b, Pod5Reads pr, uint32_t elem)
 {
@@ -2871,8 +3141,9 @@ hipError_t svb_dispatch_count(const ReadBatch& b, F&& f)
 // passes need behind the init: the segmented decoder's position passes), then norm_passes() x count(), every pass ending in its select.
 // *store = false: b.sig.type == SIG_NONE, the statistics are all that runs.  Without b.sig.norm.st: lead() alone.
 // slab: b.sig.norm.slab must be set (the segments add their counts there) or must not be (one workgroup per read counts in LDS).
-template <class Init, class Lead, class Count>
-hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, Init init, Lead lead, Count count, bool* store)
+// trim(): the trim pass behind the last counting pass (a call without TrimOut: nothing).
+template <class Init, class Lead, class Count, class Trim>
+hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, Init init, Lead lead, Count count, Trim trim, bool* store)
 {
     *store = true;
     if (!b.sig.norm.st) return lead();
@@ -2882,13 +3153,14 @@ hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, Init 
     hipError_t e = init();
     if (e == hipSuccess) e = lead();
     for (uint32_t p = 0; e == hipSuccess && p < norm_passes(b.sig.norm.method); ++p) e = count();
+    if (e == hipSuccess) e = trim();
     return e;
 }
 
 // the segmented decode: MODE 1, then (SELF) MODE 2 and MODE 0, or the verdict scan, MODE 2 and its scan, and MODE 0; only MODE 0 stores
 template <int E, bool Z, bool I, int OUT>
 hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val, uint64_t* seg_pos,
-                                   uint32_t* seg_run, hipStream_t s)
+                                   uint32_t* seg_run, hipStream_t s, const TrimOut* trim)
 {
     const dim3 segs(max_segs), reads(b.n_reads), t(WG);
     const bool self = max_segs <= seg_self_max();
@@ -2923,6 +3195,15 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
                 if (ec != hipSuccess) return ec;
                 if (b.sig.ranged_stats()) hipLaunchKernelGGL(norm_select_range_kernel, reads, t, 0, s, b);
                 else hipLaunchKernelGGL(norm_select_kernel, reads, t, 0, s, b);
+            }
+            return hipGetLastError();
+        },
+        [&] {   // the trim pass at the same positions, behind it the scan launch
+            if constexpr (E == 2) {
+                if (!trim) return hipSuccess;
+                if (self) hipLaunchKernelGGL((svb_seg_trim_kernel<Z, I, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *trim);
+                else hipLaunchKernelGGL((svb_seg_trim_kernel<Z, I, false>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *trim);
+                hipLaunchKernelGGL(trim_select_kernel, reads, t, 0, s, b, *trim);
             }
             return hipGetLastError();
         },
@@ -2962,8 +3243,9 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
     });
 }
 
-hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s)
+hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s, const TrimOut* trim)
 {
+    if (trim && (half || !b.sig.norm.st)) return hipErrorInvalidValue;
     if (half) {
         if (integer_size != 1 || b.sig.type != SIG_NONE) return hipErrorInvalidValue;
         return zigzag ? launch1(svb_half_decode_kernel<true>, b, s) : launch1(svb_half_decode_kernel<false>, b, s);
@@ -2971,7 +3253,14 @@ hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, 
     bool store;   // the counting passes (each selects at its end), then the store -- none for the statistics alone
     const hipError_t e = norm_prepasses(
         b, integer_size, false, [&] { return launch_norm_init(b, zigzag, s); }, [] { return hipSuccess; },
-        [&] { return svb_dispatch_count(b, [&](auto out) { return svb_decode_launch<out()>(b, 2, zigzag, s); }); }, &store);
+        [&] { return svb_dispatch_count(b, [&](auto out) { return svb_decode_launch<out()>(b, 2, zigzag, s); }); },
+        [&] {
+            if (!trim) return hipSuccess;
+            if (zigzag) hipLaunchKernelGGL((svb_trim_kernel<true, true>), dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
+            else hipLaunchKernelGGL((svb_trim_kernel<false, false>), dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
+            return hipGetLastError();
+        },
+        &store);
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return svb_decode_launch<out()>(b, integer_size, zigzag, s); });
 }
@@ -2984,9 +3273,10 @@ hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStr
     return hipGetLastError();
 }
 
-hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s)
+hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut* trim)
 {
     if (b.n_reads == 0) return hipSuccess;
+    if (trim && !b.sig.norm.st) return hipErrorInvalidValue;
     bool store;   // the counting passes (each selects at its end: one workgroup per read), then the store
     const hipError_t e = norm_prepasses(
         b, 2, false,
@@ -2994,7 +3284,12 @@ hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s)
             hipLaunchKernelGGL(norm_init16_kernel, dim3((b.n_reads + WG - 1) / WG), dim3(WG), 0, s, b);
             return hipGetLastError();
         },
-        [] { return hipSuccess; }, [&] { return svb_dispatch_count(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); }); }, &store);
+        [] { return hipSuccess; }, [&] { return svb_dispatch_count(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); }); },
+        [&] {
+            if (trim) hipLaunchKernelGGL(svb16_trim_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
+            return hipGetLastError();
+        },
+        &store);
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); });
 }
@@ -3016,11 +3311,11 @@ hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_sam
 }
 
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s)
+                                     hipStream_t s, const TrimOut* trim)
 {
     const uint32_t most = std::max(b.n_reads, pr.n_reads);
     if (most == 0) return hipSuccess;
-    if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st) || b.sig.norm.slab) return hipErrorInvalidValue;
+    if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st) || b.sig.norm.slab || (trim && !b.sig.norm.st)) return hipErrorInvalidValue;
     const dim3 rows(b.n_reads), reads(pr.n_reads), t(WG);
     if (b.sig.ranged() && !pr.range) return hipErrorInvalidValue;
     if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
@@ -3031,6 +3326,7 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
             if (b.sig.ranged_stats()) hipLaunchKernelGGL(svb16_count_reads_range_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
             else hipLaunchKernelGGL(svb16_count_reads_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
         }
+    if (trim && pr.n_reads) hipLaunchKernelGGL(svb16_trim_reads_kernel, reads, t, 0, s, b, pr, *trim);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (b.n_reads) {
@@ -3084,12 +3380,13 @@ hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigz
 }
 
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
-                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s)
+                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s, const TrimOut* trim)
 {
     if (b.n_reads == 0) return hipSuccess;
+    if (trim && !b.sig.norm.st) return hipErrorInvalidValue;
     return svb_dispatch_store(b, [&](auto out) {
         return svb_dispatch_elem<out() == SIG_NONE>(integer_size, zigzag, [&](auto e, auto z, auto i) {
-            return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s);
+            return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s, trim);
         });
     });
 }

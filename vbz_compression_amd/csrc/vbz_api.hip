@@ -109,6 +109,8 @@ struct vbz_gpu_ctx
     DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables (Pod5Reads), the reads' constants
+    TrimOut trim;              // the signal trim of the decompress call in flight (begin == nullptr: none); every decompress call sets it,
+                               // and the contexts of a batch's upper half and of the routed reads get theirs from it
     int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
     bool zero_run_sequences = true;
     bool long_repeats = true;  // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance
@@ -804,13 +806,14 @@ int entropy_decode_spans(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_c
 int svb_decode_stage(vbz_gpu_ctx* c, const ReadBatch& d, const CompressionOptions* o, bool segmented, const SegTables& seg)
 {
     Timed t(c, "svb_decode");
+    const TrimOut* const trim = c->trim.begin ? &c->trim : nullptr;
     if (pod5_codec(o))   // (one workgroup per read on every path: DESIGN.md 4.13)
-        HIPCHK(c, launch_svb16_decode(d, c->stream), "svb16_decode launch");
+        HIPCHK(c, launch_svb16_decode(d, c->stream, trim), "svb16_decode launch");
     else if (segmented)
-        HIPCHK(c, launch_svb_decode_seg(d, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->stream),
+        HIPCHK(c, launch_svb_decode_seg(d, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->stream, trim),
                "svb_decode (segmented) launch");
     else
-        HIPCHK(c, launch_svb_decode(d, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream), "svb_decode launch");
+        HIPCHK(c, launch_svb_decode(d, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream, trim), "svb_decode launch");
     return 0;
 }
 
@@ -928,6 +931,7 @@ int ensure_large(vbz_gpu_ctx* c)
     c->large->canonical = c->canonical;
     c->large->checksum = c->checksum;
     c->large->segmented = 1;
+    c->large->trim = c->trim;   // (the routed reads write begin through the routing map, as they do shift_scale)
     return 0;
 }
 
@@ -1036,6 +1040,8 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
     k->ref_chains = c->ref_chains;
     k->profiling = c->profiling;
     k->foreign_state = c->foreign_state;
+    k->trim = c->trim;   // (the upper half's begin entries: the table offset, as upper_half() offsets shift_scale)
+    if (k->trim.begin) k->trim.begin += n / 2;
     const size_t scratch_need = (size_t)(((unsigned __int128)raw_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
     if (!ensure(c, c->scratch, scratch_need) || !ensure(c, c->splitmeta, (size_t)n * 20 + 256)) return -1;
     MetaCarver mc(c->splitmeta.p);
@@ -1287,6 +1293,8 @@ struct TypedOut
     float* shift_scale = nullptr;
     const vbz_gpu_pod5_reads* reads = nullptr;   // POD5 reads of several rows: the constants, chunk_first and shift_scale are per read
     const vbz_gpu_sample_ranges* ranges = nullptr;   // the per-read sample ranges of the *_range_batch calls (per READ with `reads`)
+    const vbz_gpu_trim* trim = nullptr;              // the trim calls (the statistics alone, then the trim pass): the rule, and the table
+    uint32_t* begin = nullptr;                       // ... it fills (per READ with `reads`)
 };
 
 // The call's tables over POD5 reads (Pod5Reads) and the reads' constants, from ctx->pod5meta; the check of first_row is queued here, before
@@ -1316,6 +1324,18 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     const uint32_t n = bt->n_reads;
     c->last_frames = 0;
     c->last_span_frames = 0;
+    c->trim = TrimOut();
+    if (out && out->trim) {
+        const vbz_gpu_trim* t = out->trim;
+        c->trim.begin = out->begin;
+        c->trim.W = t->window;
+        c->trim.m = t->min_elements;
+        c->trim.t0 = t->min_trim;
+        c->trim.M = t->max_samples;
+        c->trim.flags = t->flags;
+        c->trim.f = t->threshold_factor;
+        c->trim.max_fraction = t->max_fraction;
+    }
     const vbz_gpu_pod5_reads* const reads = out ? out->reads : nullptr;
     if (n == 0 && !(reads && reads->n_reads)) return 0;
     hipStream_t s = c->stream;
@@ -1429,7 +1449,8 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
             streams.sig = rb.sig;
         }
         Timed t(c, "svb_decode");
-        HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s), "svb16_decode (reads) launch");
+        HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s, c->trim.begin ? &c->trim : nullptr),
+               "svb16_decode (reads) launch");
         return 0;
     }
     if (by_shape || !routing_applies(c, o, dst_bytes, n))
@@ -1737,8 +1758,32 @@ static bool norm_ok(vbz_gpu_ctx* c, const vbz_gpu_normalization* m, const vbz_gp
     return true;
 }
 
+// the trim's fields (include/vbz_gpu.h) and its table; a read's windows must fit the counting passes' bins
+static_assert(TRIM_REJECT_AT_END == VBZ_GPU_TRIM_REJECT_AT_END, "the ABI's trim flags");
+static_assert(sizeof(vbz_gpu_trim) == 32, "vbz_gpu_trim is 32 bytes");
+static bool trim_ok(vbz_gpu_ctx* c, const vbz_gpu_trim* t, const uint32_t* begin)
+{
+    if (!t || !begin) {
+        set_error(c, "trim or begin is NULL");
+        return false;
+    }
+    const bool fields = t->window >= 1 && t->window <= 65536 && t->max_samples >= 1 && std::isfinite(t->threshold_factor) &&
+                        std::isfinite(t->max_fraction) && t->max_fraction > 0.0f && t->max_fraction <= 1.0f &&
+                        (t->flags & ~(uint32_t)VBZ_GPU_TRIM_REJECT_AT_END) == 0 && t->reserved == 0;
+    if (!fields || (t->max_samples - std::min(t->min_trim, t->max_samples)) / t->window > TRIM_MAX_WINDOWS) {
+        set_error(c, "trim outside its rules (window %u, min_elements %u, min_trim %u, max_samples %u, threshold_factor %g, max_fraction %g, flags %u, "
+                     "reserved %u; at most %u windows)",
+                  t->window, t->min_elements, t->min_trim, t->max_samples, (double)t->threshold_factor, (double)t->max_fraction, t->flags, t->reserved,
+                  TRIM_MAX_WINDOWS);
+        return false;
+    }
+    return true;
+}
+
+// the statistics alone; with_trim: ... and the trim pass behind them (shift_scale is then nullable)
 static int signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
-                            const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+                            const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, bool with_trim = false,
+                            const vbz_gpu_trim* trim = nullptr, uint32_t* begin = nullptr)
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
@@ -1746,18 +1791,27 @@ static int signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compr
     const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
     const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };   // (what typed_args_ok checks: options, is_signed)
     if (!typed_args_ok(c, o, sized, &probe, "statistics") || !norm_ok(c, norm, nullptr)) return -2;
-    if (!shift_scale) {
-        set_error(c, "shift_scale is NULL");
+    if (with_trim ? !trim_ok(c, trim, begin) : !shift_scale) {
+        if (!with_trim) set_error(c, "shift_scale is NULL");
         return -2;
     }
     vbz_gpu_batch b = *bt;   // (batch->dst may be NULL: nothing is stored)
-    if (!b.dst) b.dst = shift_scale;
+    if (!b.dst) b.dst = with_trim ? (void*)begin : (void*)shift_scale;
     if (!plausible_extents(c, &b)) return -2;
     TypedOut out = { &f };
     out.norm = norm;
     out.shift_scale = shift_scale;
     out.ranges = ranges;
+    out.trim = trim;
+    out.begin = begin;
     return decompress_batch_impl(c, bt, o, sized, false, &out);
+}
+
+int vbz_gpu_signal_trim_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                              const vbz_gpu_normalization* norm, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_trim* trim, float* shift_scale,
+                              uint32_t* begin)
+{
+    return signal_norm_call(c, bt, o, sized, is_signed, norm, shift_scale, ranges, true, trim, begin);
 }
 
 int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
@@ -1898,7 +1952,8 @@ int vbz_gpu_pod5_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_bat
 
 static int pod5_signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
                                  const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
-                                 const vbz_gpu_sample_ranges* ranges)
+                                 const vbz_gpu_sample_ranges* ranges, bool with_trim = false, const vbz_gpu_trim* trim = nullptr,
+                                 uint32_t* begin = nullptr)
 {
     if (!c || !bt) return -1;
     DeviceGuard dg(c->device);
@@ -1906,7 +1961,9 @@ static int pod5_signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const 
     const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
     const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };
     if (!typed_args_ok(c, o, 0, &probe, "statistics") || !pod5_reads_ok(c, o, reads) || !norm_ok(c, norm, nullptr)) return -2;
-    if (reads->n_reads != 0 && !shift_scale) {
+    if (with_trim) {
+        if (!trim_ok(c, trim, begin)) return -2;
+    } else if (reads->n_reads != 0 && !shift_scale) {
         set_error(c, "shift_scale is NULL");
         return -2;
     }
@@ -1918,7 +1975,16 @@ static int pod5_signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const 
     out.shift_scale = shift_scale;
     out.reads = reads;
     out.ranges = ranges;
+    out.trim = trim;
+    out.begin = begin;
     return decompress_batch_impl(c, bt, o, 0, false, &out);
+}
+
+int vbz_gpu_pod5_signal_trim_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                   const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, const vbz_gpu_sample_ranges* ranges,
+                                   const vbz_gpu_trim* trim, float* shift_scale, uint32_t* begin)
+{
+    return pod5_signal_norm_call(c, bt, o, is_signed, reads, norm, shift_scale, ranges, true, trim, begin);
 }
 
 int vbz_gpu_pod5_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,

@@ -30,6 +30,7 @@ constexpr uint32_t SIG_NONE = 0, SIG_F32 = 1, SIG_F16 = 2, SIG_BF16 = 3;
 constexpr uint32_t SIG_CHUNK = 4;   // (or-ed into the chunk store's type: the svb decoder's OUT, the store DecStore<ELEM, OUT> of its kernels)
 constexpr uint32_t SIG_COUNT = 8;   // the svb decoder's counting pass of a normalising decode (OUT only: it stores nothing)
 constexpr uint32_t SIG_RANGE = 16;  // (or-ed into a chunk store's or the counting pass's OUT: only the samples of SignalOut's per-read range)
+constexpr uint32_t SIG_TRIM = 32;   // the svb decoder's trim pass behind the counting passes (OUT only: it stores nothing; TrimOut below)
 constexpr uint32_t RANGE_STATS_RANGE = 0, RANGE_STATS_READ = 1;   // (= VBZ_GPU_RANGE_STATS_*)
 constexpr uint32_t CHUNK_PAD = 0, CHUNK_END = 1;
 
@@ -80,6 +81,20 @@ struct SignalOut
     uint32_t rstats = RANGE_STATS_RANGE;
     __host__ __device__ bool ranged() const { return rbegin || rend; }
     __host__ __device__ bool ranged_stats() const { return ranged() && rstats == RANGE_STATS_RANGE; }
+};
+
+// Signal trim (vbz_gpu_*_signal_trim_batch; the rule: include/vbz_gpu.h): behind the counting passes of a statistics call one more pass of
+// the svb decoder (OUT = SIG_TRIM) counts, window by window, the samples above thr = shift + f * scale in the first
+// t0 + nW * W <= min(M, T) positions of every read, and the scan of those counts writes the read's trim point to begin[].  The trim is an
+// argument of its own of the kernels that take it, beside their ReadBatch: no other kernel's arguments change.  begin: the caller's table,
+// entry norm.map ? norm.map[r] : r (POD5 reads of several rows: per READ); nullptr: no trim pass.
+constexpr uint32_t TRIM_REJECT_AT_END = 1;   // (= VBZ_GPU_TRIM_REJECT_AT_END)
+constexpr uint32_t TRIM_MAX_WINDOWS = NORM_WINDOWS * NORM_BINS;   // a read's window counts live in the counting passes' bins (NormLds::h, NormOut::slab)
+struct TrimOut
+{
+    uint32_t* begin = nullptr;
+    uint32_t W = 0, m = 0, t0 = 0, M = 0, flags = 0;
+    float f = 0.0f, max_fraction = 1.0f;
 };
 
 // the clamped range of read r of T samples: *rb <= *re <= T (no address is formed from a table value before this)
@@ -198,13 +213,14 @@ bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half);   // does
 // results are the int16 decode's; launch_svb_decode_seg: b.sig.norm.slab must be set).
 // b.sig.rbegin / rend (the chunk stores and the counting passes only; launch_svb16_decode and launch_svb_decode_seg too): the ranged
 // instantiations (OUT | SIG_RANGE) store the chunks of every read's clamped range, and with rstats == RANGE_STATS_RANGE count its values alone.
-hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s);
+// trim (nullable; with b.sig.norm.st only; every decode launcher below too): the trim pass behind the last counting pass.
+hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s, const TrimOut* trim = nullptr);
 // svb16, the svb stage of POD5 signal rows (int16 samples, delta + zig-zag; one key bit per sample): one workgroup per read, on every
 // path.  Encode: the worst case ceil(n / 8) + 2n must fit dst_cap (else E_DESTINATION_SIZE); period_hint (nullable) is zeroed (no
 // matcher).  Decode: the stores of launch_svb_decode(2, zigzag) (b.sig; b.sig.norm.slab must be NULL); a stream longer than
 // ceil(n / 8) + 2n is E_ZSTD, one whose length the key bits do not announce E_STREAM.
 hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStream_t s);
-hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s);
+hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut* trim = nullptr);
 // key_raw[i]: the raw size whose key region at key_elem = 4 is svb16's ceil(n / 8) bytes (the entropy stage's orig_size for POD5, hdr 0)
 hipError_t launch_svb16_key_raw(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw, hipStream_t s);
 constexpr uint32_t SVB16_KEY_ELEM = 4;
@@ -245,7 +261,7 @@ hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_sam
 // (one workgroup per read, its rows in turn), the store (one workgroup per row; none for the statistics alone, whose first counting
 // pass gives the rows' verdicts), the read results.  b.sig.rbegin / rend: per READ; pr.range must then be set (the plan fills it).
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s);
+                                     hipStream_t s, const TrimOut* trim = nullptr);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
 // bounds the total segment count (the grid); seg_* are scratch arrays of max_segs entries.  Not for the nibble codec.
@@ -253,7 +269,7 @@ uint32_t svb_seg_unit_bytes(int integer_size);
 hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigzag, uint32_t hdr, bool strict_cap, const uint32_t* seg_first,
                                  uint32_t max_segs, uint32_t* seg_bytes, uint64_t* seg_off, hipStream_t s);
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
-                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s);
+                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s, const TrimOut* trim = nullptr);
 
 // ---- zstd-format entropy stage (zstd_encode.hip / zstd_decode.hip) -----------------------------
 // encode: frame content = src read.  The launchers' arguments are host-side aggregates, filled field by field; what is not set is not used.
