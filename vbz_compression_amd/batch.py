@@ -148,6 +148,42 @@ class GpuCodec:
         if rc != 0:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self.L.vbz_gpu_last_error(self.ctx).decode()))
 
+    def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
+               chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None):
+        """One typed decode (include/vbz_gpu.h): the batch, the device entered and left once, and the most general C entry of the call's
+        family, NULL for every part that is None.  dst None: nothing is stored in the batch's dst (a chunk decode, the statistics) --
+        dst_off / dst_cap are the int16 layout that describes the reads, dst_bytes its extent.  f (a GpuSignalFormat): what is stored,
+        with ch (a GpuChunking) into `chunks` at chunk_first; f None: the statistics alone of `signed` samples, with t (a GpuTrim) the
+        trim points behind them, into `out`.  m / ss: the GpuNormalization and the shift_scale pointer; g: a GpuSampleRanges; r: a
+        GpuPod5Reads (the pod5_ entries: unsized)."""
+        b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
+                        result)
+        if dst is None:
+            b.dst, b.dst_bytes = None, int(dst_bytes)
+
+        def ref(s):
+            return ctypes.byref(s) if s is not None else None
+
+        reads = [ref(r)] if r is not None else []
+        if ch is not None:
+            name, args = "decompress_chunks_range", [ref(f), ref(ch)] + reads + [chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]), ref(m),
+                                                                                 ss, ref(g)]
+        elif f is None and t is not None:
+            name, args = "signal_trim", [int(bool(signed))] + reads + [ref(m), ref(g), ref(t), ss, out.data_ptr()]
+        elif f is None:
+            name, args = "signal_norm_range", [int(bool(signed))] + reads + [ref(m), ss, ref(g)]
+        elif m is None:   # (the one choice between two entries: no signal entry takes a NULL norm)
+            name, args = "decompress_signal", [ref(f)]
+        else:
+            name, args = "decompress_signal_norm", [ref(f)] + reads + [ref(m), ss]
+        name = ("pod5_" if r is not None else "") + name + "_batch"
+        head = [self.ctx, ref(b), ref(opts)] + ([int(sized)] if r is None else [])
+        cur = self._enter()
+        try:
+            self._rc(getattr(self.L, "vbz_gpu_" + name)(*head, *args), name)
+        finally:
+            self._exit(cur)
+
     @staticmethod
     def options(zigzag=True, size=2, level=1, version=1):
         return _lib.CompressionOptions(bool(zigzag), int(size), int(level), int(version))
@@ -233,6 +269,11 @@ class GpuCodec:
             self._exit(cur)
         return out
 
+    @staticmethod
+    def _extent(n, dst_off, dst_cap):
+        """the extent of the arena that the n slots dst_off / dst_cap describe (two host copies)"""
+        return int(dst_off.max().item() + dst_cap.to(torch.int64).max().item()) if n else 0
+
     def signal_norm(self, src, src_off, src_size, dst_off, dst_cap, result, opts, norm, shift_scale=None, signed=True, sized=False, begin=None,
                     end=None, stats=None):
         """Every read's normalisation constants alone (include/vbz_gpu.h: vbz_gpu_signal_norm_batch) -> shift_scale, float32 [n, 2] of
@@ -244,20 +285,7 @@ class GpuCodec:
         if shift_scale is None:
             shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
         m, ss = self._norm_args(n, norm, shift_scale, None, None)
-        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
-        b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
-        b.dst = None
-        b.dst_bytes = int(dst_off.max().item() + dst_cap.to(torch.int64).max().item()) if n else 0
-        cur = self._enter()
-        try:
-            if g is None:
-                self._rc(self.L.vbz_gpu_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)), ctypes.byref(m), ss),
-                         "signal_norm_batch")
-            else:
-                self._rc(self.L.vbz_gpu_signal_norm_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)),
-                                                                ctypes.byref(m), ss, ctypes.byref(g)), "signal_norm_range_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, self._extent(n, dst_off, dst_cap), signed=signed, m=m, ss=ss, g=g)
         return shift_scale
 
     def _trim_args(self, n, trim, out, shift_scale):
@@ -283,17 +311,8 @@ class GpuCodec:
         g, keep = self._ranges(n, begin, end, stats)
         t, out, shift_scale = self._trim_args(n, trim, out, shift_scale)
         m, ss = self._norm_args(n, norm, shift_scale, None, None)
-        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
-        b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
-        b.dst = None
-        b.dst_bytes = int(dst_off.max().item() + dst_cap.to(torch.int64).max().item()) if n else 0
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_signal_trim_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), int(bool(signed)), ctypes.byref(m),
-                                                      ctypes.byref(g) if g is not None else None, ctypes.byref(t), ss, out.data_ptr()),
-                     "signal_trim_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, self._extent(n, dst_off, dst_cap), signed=signed, m=m, ss=ss, g=g,
+                    t=t, out=out)
         return out if shift_scale is None else (out, shift_scale)
 
     def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False,
@@ -306,20 +325,9 @@ class GpuCodec:
         statistics instead (vbz_gpu_decompress_signal_norm_batch), its (shift, scale) left in norm_out (float32 [n, 2], or None)."""
         assert dst.dtype in self._SIGNAL_TYPES and dst.dim() == 1 and dst.is_contiguous(), (dst.dtype, dst.shape)
         n = int(src_off.numel())
-        if norm is not None:
-            m, ss = self._norm_args(n, norm, norm_out, scale, offset)
+        m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(dst.dtype, n, scale, offset, signed)
-        b = self._batch(src, src_off, src_size, dst.view(torch.uint8), dst_off, dst_cap, result)
-        cur = self._enter()
-        try:
-            if norm is None:
-                self._rc(self.L.vbz_gpu_decompress_signal_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f)),
-                         "decompress_signal_batch")
-            else:
-                self._rc(self.L.vbz_gpu_decompress_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f),
-                                                                     ctypes.byref(m), ss), "decompress_signal_norm_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, dst.view(torch.uint8), dst_off, dst_cap, result, opts, sized, f=f, m=m, ss=ss)
 
     # -- stages ----------------------------------------------------------------------------------
     # (version: 0, 1, or _lib.VBZ_GPU_VERSION_POD5 -- the svb16 stream of POD5 rows, size 2 with zig-zag)
@@ -522,35 +530,18 @@ class GpuCodec:
         chunk_first, chunk_info, _ = self._chunk_tables(samples, self._chunking(chunk_len, step, mode, end_align), info)
         return chunk_first, chunk_info
 
+    def _chunk_arena(self, rows, chunk_len, dtype):
+        """an uninitialised [rows, chunk_len] arena (a valid pointer when it has no rows)"""
+        return torch.empty((max(rows, 1), int(chunk_len)), dtype=dtype, device=self.device)[:rows]
+
     def _decode_chunks(self, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, ch, chunk_first, chunks, dtype, scale, offset,
                        signed, norm=None, norm_out=None, ranges=None):
         assert dtype in self._SIGNAL_TYPES and chunks.dtype == dtype and chunks.is_contiguous(), (dtype, chunks.dtype)
         n = int(src_off.numel())
-        m, ss = None, None
-        if norm is not None:
-            m, ss = self._norm_args(n, norm, norm_out, scale, offset)
+        m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(dtype, n, scale, offset, signed)
-        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
-        b = self._batch(src, src_off, src_size, no_dst, dst_off, dst_cap, result)
-        b.dst = None     # (the int16 layout only describes the reads: nothing is stored there)
-        b.dst_bytes = int(dst_bytes)
-        cur = self._enter()
-        try:
-            if ranges is not None:
-                self._rc(self.L.vbz_gpu_decompress_chunks_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f),
-                                                                      ctypes.byref(ch), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
-                                                                      ctypes.byref(m) if m is not None else None, ss, ctypes.byref(ranges)),
-                         "decompress_chunks_range_batch")
-            elif norm is None:
-                self._rc(self.L.vbz_gpu_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f), ctypes.byref(ch),
-                                                                chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0])),
-                         "decompress_chunks_batch")
-            else:
-                self._rc(self.L.vbz_gpu_decompress_chunks_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f),
-                                                                     ctypes.byref(ch), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
-                                                                     ctypes.byref(m), ss), "decompress_chunks_norm_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, ch=ch, chunk_first=chunk_first, chunks=chunks,
+                    m=m, ss=ss, g=ranges)
 
     def decompress_chunks(self, src, src_off, src_size, samples, result, opts, chunk_len, step, mode="pad", end_align=1, pad=0.0, dtype=torch.float16,
                           scale=None, offset=None, signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None):
@@ -566,13 +557,10 @@ class GpuCodec:
         assert int(samples.numel()) == n
         ch = self._chunking(chunk_len, step, mode, end_align, pad)
         g, keep = self._ranges(n, begin, end, stats)
-        dst_cap = (samples.to(torch.int64) * 2).to(torch.int32)
-        dst_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
-        if n:
-            dst_off[1:] = torch.cumsum(samples.to(torch.int64) * 2, 0)
+        dst_off, dst_cap = self._row_layout(samples)
         laid = samples if g is None else self.range_samples(samples, begin=keep[0], end=keep[1])
         chunk_first, chunk_info, host = self._chunk_tables(laid, ch, True, also=dst_off[-1])
-        chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
+        chunks = self._chunk_arena(host[0], chunk_len, dtype)
         self._decode_chunks(src, src_off, src_size, dst_off[:n], dst_cap, host[1], result, opts, False, ch, chunk_first, chunks, dtype, scale, offset,
                             signed, norm, norm_out, g)
         return chunks, chunk_first, chunk_info
@@ -592,7 +580,7 @@ class GpuCodec:
         samples = torch.where(err, raw_size, raw // 2)   # (an error code: no chunks)
         laid = samples if g is None else self.range_samples(samples.contiguous(), begin=keep[0], end=keep[1])
         chunk_first, chunk_info, host = self._chunk_tables(laid, ch, True, also=raw_off[-1])
-        chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
+        chunks = self._chunk_arena(host[0], chunk_len, dtype)
         result = torch.empty(n, dtype=torch.int32, device=self.device)
         self._decode_chunks(packed, src_off, packed_size, raw_off[:n], raw, host[1], result, opts, True, ch, chunk_first, chunks, dtype, scale, offset,
                             signed, norm, norm_out, g)
@@ -615,7 +603,7 @@ class GpuCodec:
         return r, table, read_result
 
     def _row_layout(self, row_samples):
-        """the int16 layout that describes rows of row_samples samples: (dst_off int64 [n], dst_cap int32 [n], total: a device scalar)"""
+        """the int16 layout that describes reads (or rows) of row_samples samples: (dst_off int64 [n + 1], dst_off[n] = the total; dst_cap int32 [n])"""
         n = int(row_samples.numel())
         assert row_samples.dtype == torch.int32 and row_samples.is_contiguous() and row_samples.device == self.device
         dst_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
@@ -646,27 +634,12 @@ class GpuCodec:
             self._exit(cur)
         laid = read_samples if g is None else self.range_samples(read_samples, begin=keep[0], end=keep[1])
         chunk_first, chunk_info, host = self._chunk_tables(laid, ch, True, also=dst_off[-1])
-        chunks = torch.empty((max(host[0], 1), int(chunk_len)), dtype=dtype, device=self.device)[: host[0]]   # (a valid pointer when empty)
+        chunks = self._chunk_arena(host[0], chunk_len, dtype)
         assert dtype in self._SIGNAL_TYPES
         m, ss = self._norm_args(r.n_reads, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(dtype, r.n_reads, scale, offset, signed)
-        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
-        b = self._batch(src, src_off, src_size, no_dst, dst_off[:n], dst_cap, result)
-        b.dst = None
-        b.dst_bytes = int(host[1])
-        cur = self._enter()
-        try:
-            if g is None:
-                self._rc(self.L.vbz_gpu_pod5_decompress_chunks_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(ch),
-                                                                     ctypes.byref(r), chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]),
-                                                                     ctypes.byref(m) if m is not None else None, ss), "pod5_decompress_chunks_batch")
-            else:
-                self._rc(self.L.vbz_gpu_pod5_decompress_chunks_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(ch),
-                                                                           ctypes.byref(r), chunk_first.data_ptr(), chunks.data_ptr(),
-                                                                           int(chunks.shape[0]), ctypes.byref(m) if m is not None else None, ss,
-                                                                           ctypes.byref(g)), "pod5_decompress_chunks_range_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, opts, dst_bytes=host[1], f=f, ch=ch, chunk_first=chunk_first, chunks=chunks,
+                    m=m, ss=ss, g=g, r=r)
         return chunks, chunk_first, chunk_info, read_result
 
     def pod5_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, shift_scale=None, signed=True, begin=None,
@@ -681,20 +654,7 @@ class GpuCodec:
             shift_scale = torch.empty((r.n_reads, 2), dtype=torch.float32, device=self.device)
         m, ss = self._norm_args(r.n_reads, norm, shift_scale, None, None)
         dst_off, dst_cap = self._row_layout(row_samples)
-        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
-        b = self._batch(src, src_off, src_size, no_dst, dst_off[:n], dst_cap, result)
-        b.dst = None
-        b.dst_bytes = int(dst_off[-1].item())
-        cur = self._enter()
-        try:
-            if g is None:
-                self._rc(self.L.vbz_gpu_pod5_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
-                                                               ctypes.byref(m), ss), "pod5_signal_norm_batch")
-            else:
-                self._rc(self.L.vbz_gpu_pod5_signal_norm_range_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
-                                                                     ctypes.byref(m), ss, ctypes.byref(g)), "pod5_signal_norm_range_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, opts, dst_bytes=dst_off[-1].item(), signed=signed, m=m, ss=ss, g=g, r=r)
         return shift_scale, read_result
 
     def pod5_signal_trim(self, src, src_off, src_size, row_samples, read_first_row, result, norm, trim=None, out=None, shift_scale=None,
@@ -709,17 +669,8 @@ class GpuCodec:
         t, out, shift_scale = self._trim_args(r.n_reads, trim, out, shift_scale)
         m, ss = self._norm_args(r.n_reads, norm, shift_scale, None, None)
         dst_off, dst_cap = self._row_layout(row_samples)
-        no_dst = torch.empty(0, dtype=torch.uint8, device=self.device)
-        b = self._batch(src, src_off, src_size, no_dst, dst_off[:n], dst_cap, result)
-        b.dst = None
-        b.dst_bytes = int(dst_off[-1].item())
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_pod5_signal_trim_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(bool(signed)), ctypes.byref(r),
-                                                           ctypes.byref(m), ctypes.byref(g) if g is not None else None, ctypes.byref(t), ss,
-                                                           out.data_ptr()), "pod5_signal_trim_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, opts, dst_bytes=dst_off[-1].item(), signed=signed, m=m, ss=ss, g=g, r=r,
+                    t=t, out=out)
         return (out, read_result) if shift_scale is None else (out, shift_scale, read_result)
 
     def pod5_decompress_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, dtype=torch.float32, signed=True,
@@ -736,13 +687,7 @@ class GpuCodec:
         m, ss = self._norm_args(r.n_reads, norm, norm_out, None, None)
         f = self._signal_format(dtype, r.n_reads, None, None, signed)
         out = torch.empty(lay.total // elem + 32, dtype=dtype, device=self.device)
-        b = self._batch(src, src_off, src_size, out.view(torch.uint8), lay.dst_off, lay.dst_cap, result)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_pod5_decompress_signal_norm_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), ctypes.byref(f), ctypes.byref(r),
-                                                                      ctypes.byref(m), ss), "pod5_decompress_signal_norm_batch")
-        finally:
-            self._exit(cur)
+        self._typed(src, src_off, src_size, out.view(torch.uint8), lay.dst_off, lay.dst_cap, result, opts, f=f, m=m, ss=ss, r=r)
         return out, lay, read_result
 
     # -- synthetic workload ----------------------------------------------------------

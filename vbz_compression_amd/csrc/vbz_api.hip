@@ -1236,19 +1236,195 @@ int compress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressi
     return rc;
 }
 
-// the options and the sample format of a signal or chunk decode (`what`: which decode, for the error text)
-bool typed_args_ok(vbz_gpu_ctx* c, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f, const char* what)
+// ---- typed decodes: the checks of the ABI's structs, the request (TypedCall), the decode, the one way in (typed_decode) ---------------
+// the options of a typed decode and what it stores (`what`: which decode, for the error text).  type_ok: the format is there and its
+// out_type known (the statistics alone store nothing and have no format: true)
+bool typed_args_ok(vbz_gpu_ctx* c, const CompressionOptions* o, int sized, const char* what, bool type_ok, uint32_t is_signed)
 {
     if (!o || o->integer_size != 2 || !batch_options_ok(o, sized)) {
         set_error(c, "unsupported options for a %s decode (integer_size must be 2, version 0, 1 or POD5)", what);
         return false;
     }
-    if (!f || f->out_type < VBZ_GPU_SIGNAL_F32 || f->out_type > VBZ_GPU_SIGNAL_BF16 || f->is_signed > 1) {
+    if (!type_ok || is_signed > 1) {
         set_error(c, "signal format: NULL, unknown out_type or is_signed not 0 / 1");
         return false;
     }
     return true;
 }
+
+static_assert(CHUNK_PAD == VBZ_GPU_CHUNK_PAD && CHUNK_END == VBZ_GPU_CHUNK_END, "the ABI's chunk modes");
+static_assert(sizeof(vbz_gpu_chunking) == 24, "vbz_gpu_chunking is 24 bytes");
+bool chunking_ok(vbz_gpu_ctx* c, const vbz_gpu_chunking* ch)
+{
+    if (!ch) {
+        set_error(c, "chunking is NULL");
+        return false;
+    }
+    const uint32_t L = ch->chunk_len, S = ch->step;
+    const bool align_ok = ch->mode == VBZ_GPU_CHUNK_PAD ? ch->end_align == 0 : (ch->end_align >= 1 && ch->end_align <= 4096);
+    if (L < 8 || L > (1u << 20) || L % 8 != 0 || S < 8 || S > L || S % 8 != 0 || ch->mode > VBZ_GPU_CHUNK_END || !align_ok || ch->reserved != 0) {
+        set_error(c, "chunking outside the rules (chunk_len %u, step %u, mode %u, end_align %u, reserved %u)", L, S, ch->mode, ch->end_align, ch->reserved);
+        return false;
+    }
+    return true;
+}
+// the chunk part of SignalOut, and the arena the svb stage stores into (rb->dst: the caller's dst side only describes the reads)
+void chunk_out(const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, ReadBatch* rb)
+{
+    rb->dst = (uint8_t*)chunks;
+    rb->sig.row = chunk_first;
+    rb->sig.chunk_len = ch->chunk_len;
+    rb->sig.step = ch->step;
+    rb->sig.mode = ch->mode;
+    rb->sig.end_align = ch->end_align;
+    rb->sig.pad = ch->pad;
+}
+
+// the ranges of a *_range_batch call (nullable: the un-ranged call)
+static_assert(RANGE_STATS_RANGE == VBZ_GPU_RANGE_STATS_RANGE && RANGE_STATS_READ == VBZ_GPU_RANGE_STATS_READ, "the ABI's stats modes");
+static_assert(sizeof(vbz_gpu_sample_ranges) == 24, "vbz_gpu_sample_ranges is 24 bytes");
+bool ranges_ok(vbz_gpu_ctx* c, const vbz_gpu_sample_ranges* g)
+{
+    if (g && (g->reserved != 0 || g->stats > VBZ_GPU_RANGE_STATS_READ)) {
+        set_error(c, "sample ranges outside their rules (stats %u, reserved %u)", g->stats, g->reserved);
+        return false;
+    }
+    return true;
+}
+
+static_assert(NORM_MED_MAD == VBZ_GPU_NORM_MED_MAD && NORM_QUANTILE == VBZ_GPU_NORM_QUANTILE, "the ABI's methods");
+static_assert(sizeof(vbz_gpu_normalization) == 32, "vbz_gpu_normalization is 32 bytes");
+// the normalisation's fields (include/vbz_gpu.h), and a format whose constants the call would ignore
+bool norm_ok(vbz_gpu_ctx* c, const vbz_gpu_normalization* m, const vbz_gpu_signal_format* f)
+{
+    if (!m) {
+        set_error(c, "normalization is NULL");
+        return false;
+    }
+    const bool fin = std::isfinite(m->shift_mul) && std::isfinite(m->scale_mul) && (std::isfinite(m->shift_min) || m->shift_min == -INFINITY);
+    const bool q = m->method == VBZ_GPU_NORM_MED_MAD ? m->quantile_a == 0.0f && m->quantile_b == 0.0f
+                                                      : 0.0f <= m->quantile_a && m->quantile_a <= m->quantile_b && m->quantile_b <= 1.0f;
+    const bool known = m->method == VBZ_GPU_NORM_MED_MAD || m->method == VBZ_GPU_NORM_QUANTILE;
+    if (!known || m->reserved != 0 || !q || !fin || !std::isnormal(m->scale_min) || !(m->scale_min > 0.0f)) {
+        set_error(c, "normalization outside its rules (method %u, reserved %u, quantiles %g / %g, shift_mul %g, scale_mul %g, shift_min %g, scale_min %g)",
+                  m->method, m->reserved, (double)m->quantile_a, (double)m->quantile_b, (double)m->shift_mul, (double)m->scale_mul,
+                  (double)m->shift_min, (double)m->scale_min);
+        return false;
+    }
+    if (f && (f->offset || f->scale)) {
+        set_error(c, "a normalising decode takes no offset or scale table (the statistics give them)");
+        return false;
+    }
+    return true;
+}
+// st: the call's per-read state; ss: where the reads' {shift, scale} go
+NormOut norm_out(const vbz_gpu_normalization* m, NormRead* st, float2* ss)
+{
+    NormOut no;
+    no.st = st;
+    no.ss = ss;
+    no.method = m->method;
+    no.qa = m->quantile_a;
+    no.qb = m->quantile_b;
+    no.shift_mul = m->shift_mul;
+    no.scale_mul = m->scale_mul;
+    no.shift_min = m->shift_min;
+    no.scale_min = m->scale_min;
+    return no;
+}
+
+// the trim's fields (include/vbz_gpu.h) and its table; a read's windows must fit the counting passes' bins
+static_assert(TRIM_REJECT_AT_END == VBZ_GPU_TRIM_REJECT_AT_END, "the ABI's trim flags");
+static_assert(sizeof(vbz_gpu_trim) == 32, "vbz_gpu_trim is 32 bytes");
+bool trim_ok(vbz_gpu_ctx* c, const vbz_gpu_trim* t, const uint32_t* begin)
+{
+    if (!t || !begin) {
+        set_error(c, "trim or begin is NULL");
+        return false;
+    }
+    const bool fields = t->window >= 1 && t->window <= 65536 && t->max_samples >= 1 && std::isfinite(t->threshold_factor) &&
+                        std::isfinite(t->max_fraction) && t->max_fraction > 0.0f && t->max_fraction <= 1.0f &&
+                        (t->flags & ~(uint32_t)VBZ_GPU_TRIM_REJECT_AT_END) == 0 && t->reserved == 0;
+    if (!fields || (t->max_samples - std::min(t->min_trim, t->max_samples)) / t->window > TRIM_MAX_WINDOWS) {
+        set_error(c, "trim outside its rules (window %u, min_elements %u, min_trim %u, max_samples %u, threshold_factor %g, max_fraction %g, flags %u, "
+                     "reserved %u; at most %u windows)",
+                  t->window, t->min_elements, t->min_trim, t->max_samples, (double)t->threshold_factor, (double)t->max_fraction, t->flags, t->reserved,
+                  TRIM_MAX_WINDOWS);
+        return false;
+    }
+    return true;
+}
+TrimOut trim_out(const vbz_gpu_trim* t, uint32_t* begin)
+{
+    TrimOut to;
+    to.begin = begin;
+    to.W = t->window;
+    to.m = t->min_elements;
+    to.t0 = t->min_trim;
+    to.M = t->max_samples;
+    to.flags = t->flags;
+    to.f = t->threshold_factor;
+    to.max_fraction = t->max_fraction;
+    return to;
+}
+
+// POD5 reads of several rows (o nullable: a call without options)
+static_assert(sizeof(vbz_gpu_pod5_reads) == 24, "vbz_gpu_pod5_reads is 24 bytes");
+bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_pod5_reads* reads)
+{
+    if (o && !pod5_codec(o)) {
+        set_error(c, "the calls over POD5 reads take POD5 options only");
+        return false;
+    }
+    if (!reads || reads->reserved != 0 || !reads->first_row) {
+        set_error(c, "reads: NULL, reserved not 0 or a NULL first_row");
+        return false;
+    }
+    return true;
+}
+
+// TypedCall: one typed decode as its entry point states it (the table of entries: in front of them, below).  A part the entry does not
+// have keeps its default.  Where the entries' rules for a NULL differ, the entry says which one holds (Null); it is not inferred.
+enum class Typed { SIGNAL, CHUNKS, STATISTICS };   // what is stored: typed samples in the reads' slots; in chunks; nothing (the constants alone)
+enum class Null { ALLOWED, REFUSED, REFUSED_WITH_READS };   // REFUSED_WITH_READS: refused unless the call has no read to write an entry for
+struct TypedCall
+{
+    Typed kind;
+    int sized;
+    const vbz_gpu_signal_format* f = nullptr;   // SIGNAL, CHUNKS: the caller's.  STATISTICS: none, is_signed alone (typed_decode gives
+    uint32_t is_signed = 0;                     // ... the decode {SIG_NONE, is_signed} here)
+    const vbz_gpu_chunking* ch = nullptr;       // CHUNKS: rb.dst becomes the chunk arena and the svb stage stores the typed samples into
+    const uint64_t* chunk_first = nullptr;      // ... the reads' chunks (untrusted: chunk_slots gates every read whose entries are not
+    void* chunks = nullptr;                     // ... exactly its chunks before anything of it is decoded)
+    uint64_t chunk_rows = 0;
+    const vbz_gpu_normalization* norm = nullptr;   // non-null: a normalising decode (the constants from the reads' statistics, into cal
+    Null norm_null = Null::ALLOWED;                // ... and shift_scale)
+    float* shift_scale = nullptr;
+    Null shift_scale_null = Null::ALLOWED;
+    const vbz_gpu_sample_ranges* ranges = nullptr;   // nullable in every entry that has it (per READ with `reads`)
+    bool pod5 = false;                               // the entry is over POD5 reads of several rows: `reads` must be there, and the
+    const vbz_gpu_pod5_reads* reads = nullptr;       // ... constants, chunk_first, shift_scale, ranges and begin are per READ
+    bool with_trim = false;                          // a trim call (the statistics, then the trim pass): the rule, and the table it fills
+    const vbz_gpu_trim* trim = nullptr;
+    uint32_t* begin = nullptr;
+
+    TypedCall(Typed k, int s) : kind(k), sized(s) {}
+    TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
+    TypedCall& statistics(uint32_t is_signed_) { is_signed = is_signed_; return *this; }
+    TypedCall& chunking(const vbz_gpu_chunking* ch_, const uint64_t* first, void* arena, uint64_t rows)
+    {
+        ch = ch_, chunk_first = first, chunks = arena, chunk_rows = rows;
+        return *this;
+    }
+    TypedCall& normalise(const vbz_gpu_normalization* m, Null m_null, float* ss, Null ss_null)
+    {
+        norm = m, norm_null = m_null, shift_scale = ss, shift_scale_null = ss_null;
+        return *this;
+    }
+    TypedCall& range(const vbz_gpu_sample_ranges* g) { ranges = g; return *this; }
+    TypedCall& pod5_reads(const vbz_gpu_pod5_reads* r) { pod5 = true, reads = r; return *this; }
+    TypedCall& trimmed(const vbz_gpu_trim* t, uint32_t* b) { with_trim = true, trim = t, begin = b; return *this; }
+};
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
 // through the int16 slot table made from it here -- offsets and capacities / E * 2, the extent likewise -- so that the descriptor checks,
@@ -1276,26 +1452,7 @@ int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_f
 }
 
 // Chunk decode (vbz_gpu_decompress_chunks_batch): the caller's dst side is the int16 layout of the same reads, so the descriptor checks,
-// sized headers, scratch plan, routing and the split are the int16 call's; rb.dst becomes the chunk arena and the svb stage stores the
-// typed samples into the reads' chunks (rb.sig.row: chunk_first, untrusted -- chunk_slots gates every read whose entries are not exactly
-// its chunks before anything of it is decoded).
-// TypedOut: what a typed decode stores -- f the samples' format; ch != nullptr: a chunk decode into `chunks`.  norm != nullptr: a
-// normalising decode (the constants from the reads' statistics, into cal and shift_scale); with f->out_type == SIG_NONE the statistics
-// alone (the int16 layout, nothing stored).
-struct TypedOut
-{
-    const vbz_gpu_signal_format* f;
-    const vbz_gpu_chunking* ch = nullptr;
-    const uint64_t* chunk_first = nullptr;
-    void* chunks = nullptr;
-    uint64_t chunk_rows = 0;
-    const vbz_gpu_normalization* norm = nullptr;
-    float* shift_scale = nullptr;
-    const vbz_gpu_pod5_reads* reads = nullptr;   // POD5 reads of several rows: the constants, chunk_first and shift_scale are per read
-    const vbz_gpu_sample_ranges* ranges = nullptr;   // the per-read sample ranges of the *_range_batch calls (per READ with `reads`)
-    const vbz_gpu_trim* trim = nullptr;              // the trim calls (the statistics alone, then the trim pass): the rule, and the table
-    uint32_t* begin = nullptr;                       // ... it fills (per READ with `reads`)
-};
+// sized headers, scratch plan, routing and the split are the int16 call's (chunk_out: where the samples go instead).
 
 // The call's tables over POD5 reads (Pod5Reads) and the reads' constants, from ctx->pod5meta; the check of first_row is queued here, before
 // any other launch of the call (out: read_result or read_samples, nullable -- E_INPUT_SIZE in every entry when the table is bad)
@@ -1317,25 +1474,14 @@ int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* 
     return 0;
 }
 
-// out (nullable): a typed decode (signal_slots) or a chunk decode (out->ch)
+// out (nullable): a typed decode that typed_decode has checked (out->f is set)
 int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, bool own_descriptors = false,
-                          const TypedOut* out = nullptr)
+                          const TypedCall* out = nullptr)
 {
     const uint32_t n = bt->n_reads;
     c->last_frames = 0;
     c->last_span_frames = 0;
-    c->trim = TrimOut();
-    if (out && out->trim) {
-        const vbz_gpu_trim* t = out->trim;
-        c->trim.begin = out->begin;
-        c->trim.W = t->window;
-        c->trim.m = t->min_elements;
-        c->trim.t0 = t->min_trim;
-        c->trim.M = t->max_samples;
-        c->trim.flags = t->flags;
-        c->trim.f = t->threshold_factor;
-        c->trim.max_fraction = t->max_fraction;
-    }
+    c->trim = out && out->with_trim ? trim_out(out->trim, out->begin) : TrimOut();
     const vbz_gpu_pod5_reads* const reads = out ? out->reads : nullptr;
     if (n == 0 && !(reads && reads->n_reads)) return 0;
     hipStream_t s = c->stream;
@@ -1345,34 +1491,15 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (reads && pod5_reads_begin(c, n, reads, reads->read_result, &pr, &read_cal) != 0) return -1;
     if (n != 0 && !own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
     uint64_t dst_bytes = bt->dst_bytes;
-    const bool chunks = out && out->ch;
+    const bool chunks = out && out->kind == Typed::CHUNKS, stats = out && out->kind == Typed::STATISTICS;
     const uint32_t n_const = reads ? reads->n_reads : n;   // how many reads have constants and statistics
-    float2* cal = nullptr;   // the per-read constants (a chunk decode: chunk_slots fills them in)
-    if (reads && (chunks || out->f->out_type == SIG_NONE)) {
-        if (chunks) {
-            rb.dst = (uint8_t*)out->chunks;
-            rb.sig.row = out->chunk_first;
-            rb.sig.chunk_len = out->ch->chunk_len;
-            rb.sig.step = out->ch->step;
-            rb.sig.mode = out->ch->mode;
-            rb.sig.end_align = out->ch->end_align;
-            rb.sig.pad = out->ch->pad;
-        }
-    } else if (out && out->f->out_type == SIG_NONE) {   // (the statistics alone: the constants' table is the selects' only)
+    float2* cal = nullptr;   // the per-read constants
+    if (chunks) chunk_out(out->ch, out->chunk_first, out->chunks, &rb);
+    if (out && !chunks && !stats) {   // typed slots (of POD5 rows too)
+        if (signal_slots(c, bt, out->f, &rb, &dst_bytes, &cal) != 0) return -1;
+    } else if (out && !reads) {   // the int16 layout as it is; the constants' table is chunk_slots' or the selects' to fill
         if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
         cal = reinterpret_cast<float2*>(c->sigmeta.p);
-    } else if (chunks) {
-        if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
-        cal = reinterpret_cast<float2*>(c->sigmeta.p);
-        rb.dst = (uint8_t*)out->chunks;
-        rb.sig.row = out->chunk_first;
-        rb.sig.chunk_len = out->ch->chunk_len;
-        rb.sig.step = out->ch->step;
-        rb.sig.mode = out->ch->mode;
-        rb.sig.end_align = out->ch->end_align;
-        rb.sig.pad = out->ch->pad;
-    } else if (out && signal_slots(c, bt, out->f, &rb, &dst_bytes, &cal) != 0) {
-        return -1;
     }
     if (reads) cal = read_cal;
     if (out) {
@@ -1388,17 +1515,9 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (out && out->norm) {
         if (!ensure(c, c->normmeta, (size_t)n_const * (sizeof(NormRead) + 8) + 256)) return -1;
         MetaCarver mc(c->normmeta.p);
-        NormOut& no = rb.sig.norm;
-        no.st = mc.take<NormRead>(n_const);
+        NormRead* st = mc.take<NormRead>(n_const);
         float2* ss = mc.take<float2>(n_const);   // (the caller passed no shift_scale: a table of the call's own)
-        no.ss = out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : ss;
-        no.method = out->norm->method;
-        no.qa = out->norm->quantile_a;
-        no.qb = out->norm->quantile_b;
-        no.shift_mul = out->norm->shift_mul;
-        no.scale_mul = out->norm->scale_mul;
-        no.shift_min = out->norm->shift_min;
-        no.scale_min = out->norm->scale_min;
+        rb.sig.norm = norm_out(out->norm, st, out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : ss);
     }
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
         uint64_t* pay_off;
@@ -1465,6 +1584,53 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
     if (route_join(c, r, bt->result) != 0) rc = -1;
     return rc;
+}
+
+// The one way into a typed decode: every check of every entry, in this order, then the decode.  A call with one fault gets that fault's
+// message; with several, the first in this order.
+int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const TypedCall& call)
+{
+    static const char* const WHAT[] = { "signal", "chunk", "statistics" };
+    if (!c || !bt) return -1;                                                                                        // 1
+    DeviceGuard dg(c->device);                                                                                       // 2
+    TypedCall t = call;
+    const bool stats = t.kind == Typed::STATISTICS;
+    const bool type_ok = stats || (t.f && t.f->out_type >= VBZ_GPU_SIGNAL_F32 && t.f->out_type <= VBZ_GPU_SIGNAL_BF16);
+    if (!typed_args_ok(c, o, t.sized, WHAT[(int)t.kind], type_ok, stats ? t.is_signed : t.f ? t.f->is_signed : 0u)) return -2;   // 3
+    if (t.pod5 && !pod5_reads_ok(c, o, t.reads)) return -2;                                                         // 4
+    if ((t.norm || t.norm_null != Null::ALLOWED) && !norm_ok(c, t.norm, t.f)) return -2;                            // 5
+    if (!ranges_ok(c, t.ranges)) return -2;                                                                          // 6
+    const uint32_t n_out = t.pod5 ? t.reads->n_reads : bt->n_reads;   // the reads the per-read tables have an entry for
+    if (t.with_trim && !trim_ok(c, t.trim, t.begin)) return -2;                                                      // 7
+    if (!t.shift_scale && (t.shift_scale_null == Null::REFUSED || (t.shift_scale_null == Null::REFUSED_WITH_READS && n_out != 0))) {
+        set_error(c, "shift_scale is NULL");
+        return -2;
+    }
+    if (t.kind == Typed::CHUNKS) {                                                                                   // 8
+        if (!chunking_ok(c, t.ch)) return -2;
+        if (n_out != 0 && (!t.chunk_first || !t.chunks)) {
+            set_error(c, "chunk_first or the chunk arena is NULL");
+            return -2;
+        }
+        if (((uintptr_t)t.chunks & 15u) != 0) {
+            set_error(c, "the chunk arena is not 16-byte aligned");
+            return -2;
+        }
+        const uint64_t row_bytes = (uint64_t)t.ch->chunk_len * (t.f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u);
+        if (t.chunk_rows > EXTENT_MAX / row_bytes) {
+            set_error(c, "declared chunk arena is not plausible (%llu rows of %llu bytes)", (unsigned long long)t.chunk_rows, (unsigned long long)row_bytes);
+            return -2;
+        }
+    }
+    // 9. batch->dst is an arena of a SIGNAL decode alone: a chunk decode stores into `chunks` and the statistics store nothing, so their
+    // callers may leave it NULL beside the dst_bytes of the int16 layout that describes the reads.  plausible_extents, which refuses a
+    // NULL arena of a declared size, therefore sees a batch whose dst is not NULL; the decode gets the caller's batch and reads no dst.
+    vbz_gpu_batch b = *bt;
+    if (t.kind != Typed::SIGNAL) b.dst = &b;
+    if (!plausible_extents(c, &b)) return -2;                                                                        // 10
+    const vbz_gpu_signal_format none = { SIG_NONE, t.is_signed, nullptr, nullptr };
+    if (stats) t.f = &none;
+    return decompress_batch_impl(c, bt, o, t.sized, false, &t);                                                      // 11
 }
 
 }  // namespace
@@ -1638,33 +1804,6 @@ int vbz_gpu_decompress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Comp
     return decompress_batch_impl(c, bt, o, sized);
 }
 
-int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f)
-{
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, sized, f, "signal")) return -2;
-    if (!plausible_extents(c, bt)) return -2;
-    const TypedOut out = { f };
-    return decompress_batch_impl(c, bt, o, sized, false, &out);
-}
-
-static_assert(CHUNK_PAD == VBZ_GPU_CHUNK_PAD && CHUNK_END == VBZ_GPU_CHUNK_END, "the ABI's chunk modes");
-static_assert(sizeof(vbz_gpu_chunking) == 24, "vbz_gpu_chunking is 24 bytes");
-bool chunking_ok(vbz_gpu_ctx* c, const vbz_gpu_chunking* ch)
-{
-    if (!ch) {
-        set_error(c, "chunking is NULL");
-        return false;
-    }
-    const uint32_t L = ch->chunk_len, S = ch->step;
-    const bool align_ok = ch->mode == VBZ_GPU_CHUNK_PAD ? ch->end_align == 0 : (ch->end_align >= 1 && ch->end_align <= 4096);
-    if (L < 8 || L > (1u << 20) || L % 8 != 0 || S < 8 || S > L || S % 8 != 0 || ch->mode > VBZ_GPU_CHUNK_END || !align_ok || ch->reserved != 0) {
-        set_error(c, "chunking outside the rules (chunk_len %u, step %u, mode %u, end_align %u, reserved %u)", L, S, ch->mode, ch->end_align, ch->reserved);
-        return false;
-    }
-    return true;
-}
-
 int vbz_gpu_chunk_layout_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* samples, const vbz_gpu_chunking* ch, uint64_t* chunk_first,
                                uint32_t* chunk_info, uint64_t info_cap)
 {
@@ -1684,148 +1823,6 @@ int vbz_gpu_chunk_layout_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* sampl
     return 0;
 }
 
-// the ranges of a *_range_batch call (nullable: the un-ranged call)
-static_assert(RANGE_STATS_RANGE == VBZ_GPU_RANGE_STATS_RANGE && RANGE_STATS_READ == VBZ_GPU_RANGE_STATS_READ, "the ABI's stats modes");
-static_assert(sizeof(vbz_gpu_sample_ranges) == 24, "vbz_gpu_sample_ranges is 24 bytes");
-static bool ranges_ok(vbz_gpu_ctx* c, const vbz_gpu_sample_ranges* g)
-{
-    if (g && (g->reserved != 0 || g->stats > VBZ_GPU_RANGE_STATS_READ)) {
-        set_error(c, "sample ranges outside their rules (stats %u, reserved %u)", g->stats, g->reserved);
-        return false;
-    }
-    return true;
-}
-
-// the chunk call's own checks and the call (typed_args_ok has passed); norm: a normalising chunk decode
-static int chunks_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
-                       const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows, const vbz_gpu_normalization* norm,
-                       float* shift_scale, const vbz_gpu_sample_ranges* ranges = nullptr)
-{
-    if (!chunking_ok(c, ch)) return -2;
-    if (bt->n_reads != 0 && (!chunk_first || !chunks)) {
-        set_error(c, "chunk_first or the chunk arena is NULL");
-        return -2;
-    }
-    if (((uintptr_t)chunks & 15u) != 0) {
-        set_error(c, "the chunk arena is not 16-byte aligned");
-        return -2;
-    }
-    const uint64_t row_bytes = (uint64_t)ch->chunk_len * (f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u);
-    if (chunk_rows > EXTENT_MAX / row_bytes) {
-        set_error(c, "declared chunk arena is not plausible (%llu rows of %llu bytes)", (unsigned long long)chunk_rows, (unsigned long long)row_bytes);
-        return -2;
-    }
-    vbz_gpu_batch b = *bt;   // (batch->dst is not used: the svb stage stores into the chunk arena)
-    b.dst = chunks;
-    if (!plausible_extents(c, &b)) return -2;
-    TypedOut out = { f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale };
-    out.ranges = ranges;
-    return decompress_batch_impl(c, &b, o, sized, false, &out);
-}
-
-int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
-                                    const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows)
-{
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, sized, f, "chunk")) return -2;
-    return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, nullptr, nullptr);
-}
-
-static_assert(NORM_MED_MAD == VBZ_GPU_NORM_MED_MAD && NORM_QUANTILE == VBZ_GPU_NORM_QUANTILE, "the ABI's methods");
-static_assert(sizeof(vbz_gpu_normalization) == 32, "vbz_gpu_normalization is 32 bytes");
-// the normalisation's fields (include/vbz_gpu.h), and a format whose constants the call would ignore
-static bool norm_ok(vbz_gpu_ctx* c, const vbz_gpu_normalization* m, const vbz_gpu_signal_format* f)
-{
-    if (!m) {
-        set_error(c, "normalization is NULL");
-        return false;
-    }
-    const bool fin = std::isfinite(m->shift_mul) && std::isfinite(m->scale_mul) && (std::isfinite(m->shift_min) || m->shift_min == -INFINITY);
-    const bool q = m->method == VBZ_GPU_NORM_MED_MAD ? m->quantile_a == 0.0f && m->quantile_b == 0.0f
-                                                      : 0.0f <= m->quantile_a && m->quantile_a <= m->quantile_b && m->quantile_b <= 1.0f;
-    const bool known = m->method == VBZ_GPU_NORM_MED_MAD || m->method == VBZ_GPU_NORM_QUANTILE;
-    if (!known || m->reserved != 0 || !q || !fin || !std::isnormal(m->scale_min) || !(m->scale_min > 0.0f)) {
-        set_error(c, "normalization outside its rules (method %u, reserved %u, quantiles %g / %g, shift_mul %g, scale_mul %g, shift_min %g, scale_min %g)",
-                  m->method, m->reserved, (double)m->quantile_a, (double)m->quantile_b, (double)m->shift_mul, (double)m->scale_mul,
-                  (double)m->shift_min, (double)m->scale_min);
-        return false;
-    }
-    if (f && (f->offset || f->scale)) {
-        set_error(c, "a normalising decode takes no offset or scale table (the statistics give them)");
-        return false;
-    }
-    return true;
-}
-
-// the trim's fields (include/vbz_gpu.h) and its table; a read's windows must fit the counting passes' bins
-static_assert(TRIM_REJECT_AT_END == VBZ_GPU_TRIM_REJECT_AT_END, "the ABI's trim flags");
-static_assert(sizeof(vbz_gpu_trim) == 32, "vbz_gpu_trim is 32 bytes");
-static bool trim_ok(vbz_gpu_ctx* c, const vbz_gpu_trim* t, const uint32_t* begin)
-{
-    if (!t || !begin) {
-        set_error(c, "trim or begin is NULL");
-        return false;
-    }
-    const bool fields = t->window >= 1 && t->window <= 65536 && t->max_samples >= 1 && std::isfinite(t->threshold_factor) &&
-                        std::isfinite(t->max_fraction) && t->max_fraction > 0.0f && t->max_fraction <= 1.0f &&
-                        (t->flags & ~(uint32_t)VBZ_GPU_TRIM_REJECT_AT_END) == 0 && t->reserved == 0;
-    if (!fields || (t->max_samples - std::min(t->min_trim, t->max_samples)) / t->window > TRIM_MAX_WINDOWS) {
-        set_error(c, "trim outside its rules (window %u, min_elements %u, min_trim %u, max_samples %u, threshold_factor %g, max_fraction %g, flags %u, "
-                     "reserved %u; at most %u windows)",
-                  t->window, t->min_elements, t->min_trim, t->max_samples, (double)t->threshold_factor, (double)t->max_fraction, t->flags, t->reserved,
-                  TRIM_MAX_WINDOWS);
-        return false;
-    }
-    return true;
-}
-
-// the statistics alone; with_trim: ... and the trim pass behind them (shift_scale is then nullable)
-static int signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
-                            const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, bool with_trim = false,
-                            const vbz_gpu_trim* trim = nullptr, uint32_t* begin = nullptr)
-{
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!ranges_ok(c, ranges)) return -2;
-    const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
-    const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };   // (what typed_args_ok checks: options, is_signed)
-    if (!typed_args_ok(c, o, sized, &probe, "statistics") || !norm_ok(c, norm, nullptr)) return -2;
-    if (with_trim ? !trim_ok(c, trim, begin) : !shift_scale) {
-        if (!with_trim) set_error(c, "shift_scale is NULL");
-        return -2;
-    }
-    vbz_gpu_batch b = *bt;   // (batch->dst may be NULL: nothing is stored)
-    if (!b.dst) b.dst = with_trim ? (void*)begin : (void*)shift_scale;
-    if (!plausible_extents(c, &b)) return -2;
-    TypedOut out = { &f };
-    out.norm = norm;
-    out.shift_scale = shift_scale;
-    out.ranges = ranges;
-    out.trim = trim;
-    out.begin = begin;
-    return decompress_batch_impl(c, bt, o, sized, false, &out);
-}
-
-int vbz_gpu_signal_trim_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
-                              const vbz_gpu_normalization* norm, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_trim* trim, float* shift_scale,
-                              uint32_t* begin)
-{
-    return signal_norm_call(c, bt, o, sized, is_signed, norm, shift_scale, ranges, true, trim, begin);
-}
-
-int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
-                              const vbz_gpu_normalization* norm, float* shift_scale)
-{
-    return signal_norm_call(c, bt, o, sized, is_signed, norm, shift_scale, nullptr);
-}
-
-int vbz_gpu_signal_norm_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
-                                    const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
-{
-    return signal_norm_call(c, bt, o, sized, is_signed, norm, shift_scale, ranges);
-}
-
 int vbz_gpu_range_samples_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* samples, const vbz_gpu_sample_ranges* ranges, uint32_t* range_samples)
 {
     if (!c) return -1;
@@ -1839,54 +1836,6 @@ int vbz_gpu_range_samples_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* samp
     HIPCHK(c, launch_range_samples(n, samples, ranges ? ranges->begin : nullptr, ranges ? ranges->end : nullptr, range_samples, c->stream),
            "range samples launch");
     return 0;
-}
-
-int vbz_gpu_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
-                                          const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
-                                          const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
-{
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, sized, f, "chunk") || (norm && !norm_ok(c, norm, f)) || !ranges_ok(c, ranges)) return -2;
-    return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale, ranges);
-}
-
-int vbz_gpu_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
-                                         const vbz_gpu_normalization* norm, float* shift_scale)
-{
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, sized, f, "signal") || !norm_ok(c, norm, f)) return -2;
-    if (!plausible_extents(c, bt)) return -2;
-    TypedOut out = { f };
-    out.norm = norm;
-    out.shift_scale = shift_scale;
-    return decompress_batch_impl(c, bt, o, sized, false, &out);
-}
-
-int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
-                                         const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
-                                         const vbz_gpu_normalization* norm, float* shift_scale)
-{
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, sized, f, "chunk") || !norm_ok(c, norm, f)) return -2;
-    return chunks_call(c, bt, o, sized, f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale);
-}
-
-// ---- POD5 reads of several rows ------------------------------------------------------------------------------------------------------
-static_assert(sizeof(vbz_gpu_pod5_reads) == 24, "vbz_gpu_pod5_reads is 24 bytes");
-static bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_pod5_reads* reads)
-{
-    if (o && !pod5_codec(o)) {
-        set_error(c, "the calls over POD5 reads take POD5 options only");
-        return false;
-    }
-    if (!reads || reads->reserved != 0 || !reads->first_row) {
-        set_error(c, "reads: NULL, reserved not 0 or a NULL first_row");
-        return false;
-    }
-    return true;
 }
 
 int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint32_t* row_samples, const vbz_gpu_pod5_reads* reads, uint32_t* read_samples)
@@ -1905,41 +1854,97 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
     return 0;
 }
 
-static int pod5_chunks_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
-                            const vbz_gpu_chunking* ch, const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
-                            uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+// The fourteen typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
+//
+//   vbz_gpu_..._batch             kind        sized  chunking  norm      shift_scale          ranges    reads  trim
+//   decompress_signal             SIGNAL      arg    -         -         -                    -         -      -
+//   decompress_signal_norm        SIGNAL      arg    -         required  nullable             -         -      -
+//   decompress_chunks             CHUNKS      arg    yes       -         -                    -         -      -
+//   decompress_chunks_norm        CHUNKS      arg    yes       required  nullable             -         -      -
+//   decompress_chunks_range       CHUNKS      arg    yes       nullable  nullable             nullable  -      -
+//   signal_norm                   STATISTICS  arg    -         required  required             -         -      -
+//   signal_norm_range             STATISTICS  arg    -         required  required             nullable  -      -
+//   signal_trim                   STATISTICS  arg    -         required  nullable             nullable  -      yes
+//   pod5_decompress_signal_norm   SIGNAL      0      -         required  nullable             -         yes    -
+//   pod5_decompress_chunks        CHUNKS      0      yes       nullable  nullable             -         yes    -
+//   pod5_decompress_chunks_range  CHUNKS      0      yes       nullable  nullable             nullable  yes    -
+//   pod5_signal_norm              STATISTICS  0      -         required  required with reads  -         yes    -
+//   pod5_signal_norm_range        STATISTICS  0      -         required  required with reads  nullable  yes    -
+//   pod5_signal_trim              STATISTICS  0      -         required  nullable             nullable  yes    yes
+//
+// The NULL rules that differ between entries, kept as they were when the entries were written one by one:
+// - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
+//   only when reads->n_reads != 0.
+// - norm: NULL is a chunk decode without normalisation in decompress_chunks_range and the POD5 chunk entries, and a fault everywhere else.
+// - chunk_first and the chunk arena may be NULL when there is no read to store: batch->n_reads == 0, or, over POD5 reads,
+//   reads->n_reads == 0 (whatever the number of rows).
+int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f)
 {
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!ranges_ok(c, ranges)) return -2;
-    if (!typed_args_ok(c, o, 0, f, "chunk") || !pod5_reads_ok(c, o, reads) || (norm && !norm_ok(c, norm, f)) || !chunking_ok(c, ch)) return -2;
-    if (reads->n_reads != 0 && (!chunk_first || !chunks)) {
-        set_error(c, "chunk_first or the chunk arena is NULL");
-        return -2;
-    }
-    if (((uintptr_t)chunks & 15u) != 0) {
-        set_error(c, "the chunk arena is not 16-byte aligned");
-        return -2;
-    }
-    const uint64_t row_bytes = (uint64_t)ch->chunk_len * (f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u);
-    if (chunk_rows > EXTENT_MAX / row_bytes) {
-        set_error(c, "declared chunk arena is not plausible (%llu rows of %llu bytes)", (unsigned long long)chunk_rows, (unsigned long long)row_bytes);
-        return -2;
-    }
-    vbz_gpu_batch b = *bt;   // (batch->dst is not used: the svb stage stores into the chunk arena; without reads nothing is stored)
-    b.dst = chunks ? chunks : (void*)reads->first_row;
-    if (!plausible_extents(c, &b)) return -2;
-    TypedOut out = { f, ch, chunk_first, chunks, chunk_rows, norm, shift_scale };
-    out.reads = reads;
-    out.ranges = ranges;
-    return decompress_batch_impl(c, &b, o, 0, false, &out);
+    return typed_decode(c, bt, o, TypedCall(Typed::SIGNAL, sized).format(f));
+}
+
+int vbz_gpu_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                         const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::SIGNAL, sized).format(f).normalise(norm, Null::REFUSED, shift_scale, Null::ALLOWED));
+}
+
+int vbz_gpu_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                    const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).chunking(ch, chunk_first, chunks, chunk_rows));
+}
+
+int vbz_gpu_decompress_chunks_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                         const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
+                                         const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).chunking(ch, chunk_first, chunks, chunk_rows)
+                                      .normalise(norm, Null::REFUSED, shift_scale, Null::ALLOWED));
+}
+
+int vbz_gpu_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                          const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* chunks, uint64_t chunk_rows,
+                                          const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).chunking(ch, chunk_first, chunks, chunk_rows)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                              const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::STATISTICS, sized).statistics(is_signed).normalise(norm, Null::REFUSED, shift_scale, Null::REFUSED));
+}
+
+int vbz_gpu_signal_norm_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                                    const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::STATISTICS, sized).statistics(is_signed).normalise(norm, Null::REFUSED, shift_scale, Null::REFUSED)
+                                      .range(ranges));
+}
+
+int vbz_gpu_signal_trim_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                              const vbz_gpu_normalization* norm, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_trim* trim, float* shift_scale,
+                              uint32_t* begin)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::STATISTICS, sized).statistics(is_signed).normalise(norm, Null::REFUSED, shift_scale, Null::ALLOWED)
+                                      .range(ranges).trimmed(trim, begin));
+}
+
+// ---- POD5 reads of several rows ------------------------------------------------------------------------------------------------------
+int vbz_gpu_pod5_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                              const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::SIGNAL, 0).format(f).pod5_reads(reads).normalise(norm, Null::REFUSED, shift_scale, Null::ALLOWED));
 }
 
 int vbz_gpu_pod5_decompress_chunks_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
                                          const vbz_gpu_chunking* ch, const vbz_gpu_pod5_reads* reads, const uint64_t* chunk_first, void* chunks,
                                          uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale)
 {
-    return pod5_chunks_call(c, bt, o, f, ch, reads, chunk_first, chunks, chunk_rows, norm, shift_scale, nullptr);
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).chunking(ch, chunk_first, chunks, chunk_rows)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED));
 }
 
 int vbz_gpu_pod5_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
@@ -1947,71 +1952,31 @@ int vbz_gpu_pod5_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_bat
                                                uint64_t chunk_rows, const vbz_gpu_normalization* norm, float* shift_scale,
                                                const vbz_gpu_sample_ranges* ranges)
 {
-    return pod5_chunks_call(c, bt, o, f, ch, reads, chunk_first, chunks, chunk_rows, norm, shift_scale, ranges);
-}
-
-static int pod5_signal_norm_call(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
-                                 const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
-                                 const vbz_gpu_sample_ranges* ranges, bool with_trim = false, const vbz_gpu_trim* trim = nullptr,
-                                 uint32_t* begin = nullptr)
-{
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!ranges_ok(c, ranges)) return -2;
-    const vbz_gpu_signal_format f = { SIG_NONE, is_signed, nullptr, nullptr };
-    const vbz_gpu_signal_format probe = { VBZ_GPU_SIGNAL_F32, is_signed, nullptr, nullptr };
-    if (!typed_args_ok(c, o, 0, &probe, "statistics") || !pod5_reads_ok(c, o, reads) || !norm_ok(c, norm, nullptr)) return -2;
-    if (with_trim) {
-        if (!trim_ok(c, trim, begin)) return -2;
-    } else if (reads->n_reads != 0 && !shift_scale) {
-        set_error(c, "shift_scale is NULL");
-        return -2;
-    }
-    vbz_gpu_batch b = *bt;   // (batch->dst may be NULL: nothing is stored)
-    if (!b.dst) b.dst = (void*)reads->first_row;
-    if (!plausible_extents(c, &b)) return -2;
-    TypedOut out = { &f };
-    out.norm = norm;
-    out.shift_scale = shift_scale;
-    out.reads = reads;
-    out.ranges = ranges;
-    out.trim = trim;
-    out.begin = begin;
-    return decompress_batch_impl(c, bt, o, 0, false, &out);
-}
-
-int vbz_gpu_pod5_signal_trim_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
-                                   const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, const vbz_gpu_sample_ranges* ranges,
-                                   const vbz_gpu_trim* trim, float* shift_scale, uint32_t* begin)
-{
-    return pod5_signal_norm_call(c, bt, o, is_signed, reads, norm, shift_scale, ranges, true, trim, begin);
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).chunking(ch, chunk_first, chunks, chunk_rows)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
 int vbz_gpu_pod5_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
                                    const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale)
 {
-    return pod5_signal_norm_call(c, bt, o, is_signed, reads, norm, shift_scale, nullptr);
+    return typed_decode(c, bt, o, TypedCall(Typed::STATISTICS, 0).statistics(is_signed).pod5_reads(reads)
+                                      .normalise(norm, Null::REFUSED, shift_scale, Null::REFUSED_WITH_READS));
 }
 
 int vbz_gpu_pod5_signal_norm_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
                                          const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
                                          const vbz_gpu_sample_ranges* ranges)
 {
-    return pod5_signal_norm_call(c, bt, o, is_signed, reads, norm, shift_scale, ranges);
+    return typed_decode(c, bt, o, TypedCall(Typed::STATISTICS, 0).statistics(is_signed).pod5_reads(reads)
+                                      .normalise(norm, Null::REFUSED, shift_scale, Null::REFUSED_WITH_READS).range(ranges));
 }
 
-int vbz_gpu_pod5_decompress_signal_norm_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
-                                              const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale)
+int vbz_gpu_pod5_signal_trim_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                   const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, const vbz_gpu_sample_ranges* ranges,
+                                   const vbz_gpu_trim* trim, float* shift_scale, uint32_t* begin)
 {
-    if (!c || !bt) return -1;
-    DeviceGuard dg(c->device);
-    if (!typed_args_ok(c, o, 0, f, "signal") || !pod5_reads_ok(c, o, reads) || !norm_ok(c, norm, f)) return -2;
-    if (!plausible_extents(c, bt)) return -2;
-    TypedOut out = { f };
-    out.norm = norm;
-    out.shift_scale = shift_scale;
-    out.reads = reads;
-    return decompress_batch_impl(c, bt, o, 0, false, &out);
+    return typed_decode(c, bt, o, TypedCall(Typed::STATISTICS, 0).statistics(is_signed).pod5_reads(reads)
+                                      .normalise(norm, Null::REFUSED, shift_scale, Null::ALLOWED).range(ranges).trimmed(trim, begin));
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)
