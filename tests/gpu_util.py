@@ -2,19 +2,12 @@
 import numpy as np
 import torch
 
+from typed_support import codec   # noqa: F401  (the suite's one context cache)
 from vbz_compression_amd import _lib, batch
 
-_codec = None
 SRC_ALIGN = 64   # tests may lower these to exercise unaligned arena offsets
 DST_ALIGN = 64
 SRC_SKEW = 0     # extra bytes in front of the first buffer
-
-
-def codec():
-    global _codec
-    if _codec is None:
-        _codec = batch.GpuCodec(0)
-    return _codec
 
 
 def _pack(bufs, align=None):

@@ -3,6 +3,7 @@ is the concatenation of its rows; its chunks are vbz_gpu_chunking's for the conc
 import numpy as np
 
 import norm_ref as R
+from signal_ref import chunk_rows, chunk_starts, pad_bits, typed_bits   # noqa: F401  (the one statement of each; a read's rows concatenated are a signal to them)
 
 
 def bounds(first_row, n_rows):
@@ -14,45 +15,6 @@ def read_signals(rows, first_row):
     """the concatenated int16 signal of every read"""
     b = bounds(first_row, len(rows))
     return [np.concatenate([np.asarray(x, np.int16) for x in rows[b[k] : b[k + 1]]] + [np.zeros(0, np.int16)]) for k in range(len(first_row))]
-
-
-def chunk_starts(T, L, S, mode, end_align):
-    """start samples of the chunks of a read of T samples (mode "pad" or "end")"""
-    if T == 0:
-        return []
-    if T <= L:
-        return [0]
-    ks = -(-(T - L) // S)
-    starts = [k * S for k in range(ks + 1)]
-    if mode == "end":
-        starts[-1] = min(starts[-1], -(-(T - L) // end_align) * end_align)
-    return starts
-
-
-def typed_bits(x, o, s, dtype):
-    """bits of ((float32)x + o) * s rounded once to dtype ("f32", "f16", "bf16"): uint32 or uint16"""
-    y = (np.asarray(x).astype(np.float32) + np.float32(o)) * np.float32(s)
-    if dtype == "f32":
-        return y.view(np.uint32)
-    if dtype == "f16":
-        return y.astype(np.float16).view(np.uint16)
-    u = y.view(np.uint32).astype(np.uint64)   # bfloat16: round to nearest even on the upper half (finite values)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def pad_bits(pad, dtype):
-    return typed_bits(np.zeros(1, np.int16), pad, 1.0, dtype)[0]
-
-
-def chunk_rows(x, L, S, mode, end_align, o, s, pad, dtype):
-    """the [K, L] chunk rows (bits) of the signal x calibrated with (o, s)"""
-    starts = chunk_starts(len(x), L, S, mode, end_align)
-    bits = typed_bits(x, o, s, dtype)
-    out = np.full((len(starts), L), pad_bits(pad, dtype), bits.dtype)
-    for k, a in enumerate(starts):
-        seg = bits[a : a + L]
-        out[k, : len(seg)] = seg
-    return starts, out
 
 
 def shift_scale(x, norm, signed=True):

@@ -12,6 +12,7 @@ import torch
 
 import gpu_util as G
 import oracle_lib as O
+import typed_support as S
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -91,13 +92,14 @@ def libzstd_ok(frame, cap):
 @pytest.fixture
 def fresh_codec():
     """a context of its own (per-context state such as the walk's knowledge of earlier calls does not leak between tests)"""
-    old = G._codec
-    G._codec = batch.GpuCodec(0)
+    old = S._codecs.get(())
+    S._codecs[()] = batch.GpuCodec(0)   # (what codec() with no knob returns: gpu_util's stages run in it)
     try:
-        yield G._codec
+        yield S._codecs[()]
     finally:
-        G._codec.close()
-        G._codec = old
+        S._codecs.pop(()).close()
+        if old is not None:
+            S._codecs[()] = old
 
 
 @pytest.fixture

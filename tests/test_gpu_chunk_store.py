@@ -13,8 +13,7 @@ import pytest
 
 import pod5_ref as P
 import pod5_reads_ref as PR
-import test_gpu_pod5_reads as TP
-import test_gpu_ranges as TR
+from typed_support import ELEM, PAD, Call, Frames, Run, check_chunks, codec, expect_results, sine_signal
 
 pytestmark = pytest.mark.gpu
 
@@ -69,9 +68,9 @@ def inputs(c):
     """x per T; (a) the x as reads; (b) their rows as pod5 wrote them; (c) the y with their begins -- compressed once"""
     if "i" not in _inputs:
         rng = np.random.default_rng(23)
-        xs = [TR.signal_like(rng, T) if k % 3 else rng.integers(-32768, 32768, T).astype(np.int16) for k, T in enumerate(SIZES)]
+        xs = [sine_signal(rng, T) if k % 3 else rng.integers(-32768, 32768, T).astype(np.int16) for k, T in enumerate(SIZES)]
         opts = c.options(True, 2, 1, 1)
-        whole = TR.Frames(c, xs, opts)
+        whole = Frames(c, xs, opts)
         rows, first, of_rows = [], [], []
         for k, x in enumerate(xs):
             for lens in row_lengths(len(x)):
@@ -87,38 +86,38 @@ def inputs(c):
                     ys.append(np.concatenate([rng.integers(-32768, 32768, b).astype(np.int16), x, rng.integers(-32768, 32768, 5).astype(np.int16)]))
                     begins.append(b)
                     of_ys.append(k)
-        _inputs["i"] = dict(xs=xs, whole=whole, rows=rows, first=first, frames=frames, of_rows=of_rows, ranged=TR.Frames(c, ys, opts), begins=begins, of_ys=of_ys)
+        _inputs["i"] = dict(xs=xs, whole=whole, rows=rows, first=first, frames=frames, of_rows=of_rows, ranged=Frames(c, ys, opts), begins=begins, of_ys=of_ys)
     return _inputs["i"]
 
 
 @pytest.mark.parametrize("mode,ea", MODES, ids=lambda v: str(v))
 @pytest.mark.parametrize("L,S", CHUNKINGS)
 def test_read_rows_and_range_are_one_store(L, S, mode, ea):
-    c = TP.codec()
+    c = codec()
     I = inputs(c)
     xs = I["xs"]
     chunking = (L, S, mode, ea)
     rng = np.random.default_rng(L + ea)
     o, s = rng.uniform(-600, 600, len(xs)).astype(np.float32), rng.uniform(0.01, 2.5, len(xs)).astype(np.float32)
     for dtype in DTYPES:
-        want = [PR.chunk_rows(x, L, S, mode, ea, o[k], s[k], TR.PAD, dtype)[1] for k, x in enumerate(xs)]   # the reference, once
+        want = [PR.chunk_rows(x, L, S, mode, ea, o[k], s[k], PAD, dtype)[1] for k, x in enumerate(xs)]   # the reference, once
         # (a) one read each, the un-ranged call
-        a = TR.Run(I["whole"], chunking, dtype, offset=o, scale=s, ranges=False).check()
+        a = Run(I["whole"], chunking, dtype, offset=o, scale=s, ranges=False).check()
         got = a.bits()
         for k in range(len(xs)):
             assert np.array_equal(got[a.table[k] : a.table[k + 1]], want[k]), ("read", chunking, dtype, len(xs[k]))
         # (b) POD5 rows
         of = I["of_rows"]
-        call = TP.Call(c, I["frames"], [len(r) for r in I["rows"]], PR.bounds(I["first"], len(I["rows"])), dtype, chunking, offset=o[of], scale=s[of])
+        call = Call(c, I["frames"], [len(r) for r in I["rows"]], PR.bounds(I["first"], len(I["rows"])), dtype, chunking, offset=o[of], scale=s[of])
         assert call.chunk_call() == 0, c.L.vbz_gpu_last_error(c.ctx)
-        TP.expect_results(call, I["rows"], I["first"], TP.ELEM[dtype])
-        TP.check_chunks(call, I["rows"], I["first"], chunking, list(zip(o[of], s[of])))
+        expect_results(call, I["rows"], I["first"], ELEM[dtype])
+        check_chunks(call, I["rows"], I["first"], chunking, list(zip(o[of], s[of])))
         got, cf = call.chunk_bits(), call.first_host
         for j, k in enumerate(of):
             assert np.array_equal(got[cf[j] : cf[j + 1]], want[k]), ("rows", chunking, dtype, len(xs[k]), j)
         # (c) a range of a longer read
         of, bg = I["of_ys"], I["begins"]
-        r = TR.Run(I["ranged"], chunking, dtype, bg, [b + len(xs[k]) for b, k in zip(bg, of)], offset=o[of], scale=s[of]).check()
+        r = Run(I["ranged"], chunking, dtype, bg, [b + len(xs[k]) for b, k in zip(bg, of)], offset=o[of], scale=s[of]).check()
         got = r.bits()
         for j, k in enumerate(of):
             assert np.array_equal(got[r.table[j] : r.table[j + 1]], want[k]), ("range", chunking, dtype, len(xs[k]), bg[j])

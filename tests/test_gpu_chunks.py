@@ -11,6 +11,8 @@ import pytest
 import torch
 
 import oracle_lib as O
+from signal_ref import chunk_starts, is_nan_bits, pad_bits, ref_rows, table_of, typed_bits
+from typed_support import CANARY, ELEM, arena, codec, compress, device_frames, fmt, i32, key, u32
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -18,150 +20,11 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 E_DEST = 0xFFFFFFFC
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-ELEM = {torch.float32: 4, torch.float16: 2, torch.bfloat16: 2}
-CANARY = 0x5A
 SCHEMES = [(8, 8), (16, 8), (4000, 4000), (4096, 1024), (10000, 9504)]
 MODES = [("pad", 0), ("end", 1), ("end", 6), ("end", 8), ("end", 4096)]
 
-_codec = None
-
-
-def codec():
-    global _codec
-    if _codec is None:
-        _codec = batch.GpuCodec(0)
-    return _codec
-
-
-def i32(vals):
-    return torch.tensor(np.asarray(vals, np.uint64).astype(np.uint32).view(np.int32), dtype=torch.int32)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32).astype(np.uint64)
-
-
-# ---- the numpy statement of the scheme ----------------------------------------------------------------------------------------
-def ref_starts(T, L, S, mode, end_align):
-    """the chunk starts of a read of T samples"""
-    if T == 0:
-        return np.zeros(0, np.int64)
-    if T <= L:
-        return np.zeros(1, np.int64)
-    ks = -(-(T - L) // S)
-    starts = np.arange(ks + 1, dtype=np.int64) * S
-    if mode == "end":
-        e = -(-(T - L) // end_align) * end_align
-        starts[-1] = min(starts[-1], e)
-    assert (np.diff(starts) > 0).all()
-    return starts
-
-
-def ref_layout(Ts, L, S, mode, end_align):
-    counts = [len(ref_starts(int(t), L, S, mode, end_align)) for t in Ts]
-    first = np.zeros(len(Ts) + 1, np.int64)
-    first[1:] = np.cumsum(counts)
-    return first
-
-
-def ref_bits(x16, o, s, signed, dtype):
-    """numpy's statement of the conversion (as tests/test_gpu_signal.py): the output's bits (uint32 / uint16) for 16-bit samples x16
-    (uint16 bits) and per-sample float32 offset / scale"""
-    x = x16.view(np.int16) if signed else x16
-    y = (x.astype(np.float32) + o) * s
-    if dtype == torch.float32:
-        return y.view(np.uint32)
-    if dtype == torch.float16:
-        return y.astype(np.float16).view(np.uint16)
-    return torch.from_numpy(y).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
-
-
-def pad_bits(pad, dtype):
-    return int(ref_bits(np.zeros(1, np.uint16), np.float32(pad), np.float32(1.0), True, dtype)[0])
-
-
-def is_nan_bits(bits, dtype):
-    if dtype == torch.float32:
-        return np.isnan(bits.view(np.float32))
-    if dtype == torch.float16:
-        return np.isnan(bits.view(np.float16))
-    return ((bits & 0x7F80) == 0x7F80) & ((bits & 0x7F) != 0)
-
-
-def ref_rows(bits, T, L, S, mode, end_align, padb):
-    """numpy's chunking of one read's converted samples `bits` (T of them)"""
-    starts = ref_starts(T, L, S, mode, end_align)
-    idx = starts[:, None] + np.arange(L, dtype=np.int64)[None, :]
-    out = np.full(idx.shape, padb, bits.dtype)
-    m = idx < T
-    out[m] = bits[idx[m]]
-    return out
-
-
-# ---- batches ----------------------------------------------------------------------------------------------------------------
-def arena(bufs, align=64):
-    """host buffers -> (src, src_off, src_size) on the device"""
-    dev = codec().device
-    sizes = [int(b.nbytes) for b in bufs]
-    off, total = batch.layout(sizes, align)
-    a = np.zeros(total + 64, np.uint8)
-    for b, o in zip(bufs, off.tolist()):
-        a[o : o + b.nbytes] = np.frombuffer(np.ascontiguousarray(b).tobytes(), np.uint8)
-    return torch.from_numpy(a).to(dev), off.to(dev), i32(sizes).to(dev)
-
-
-def compress_reads(c, reads, opts, sized=False):
-    dev = c.device
-    raw, off, size = arena(reads)
-    caps = [c.L.vbz_max_compressed_size(int(a.nbytes), ctypes.byref(opts)) for a in reads]
-    coff, ctotal = batch.layout(caps, 64)
-    comp = torch.empty(ctotal + 64, dtype=torch.uint8, device=dev)
-    res = torch.zeros(len(reads), dtype=torch.int32, device=dev)
-    c.compress(raw, off, size, comp, coff.to(dev), i32(caps).to(dev), res, opts, sized=sized)
-    torch.cuda.synchronize()
-    assert not any(_lib.is_error(r) for r in u32(res)), "compress"
-    return comp, coff.to(dev), res
-
-
-def device_frames(c, lens, seed, opts, sized=False):
-    dev = c.device
-    lens_t = torch.tensor(lens, dtype=torch.int32, device=dev)
-    sizes = [2 * n for n in lens]
-    off, total = batch.layout(sizes, 64)
-    raw = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
-    c.synth_signal(seed, 0, raw, off.to(dev), lens_t)
-    caps = [c.L.vbz_max_compressed_size(s, ctypes.byref(opts)) for s in sizes]
-    coff, ctotal = batch.layout(caps, 64)
-    comp = torch.empty(ctotal + 64, dtype=torch.uint8, device=dev)
-    res = torch.zeros(len(lens), dtype=torch.int32, device=dev)
-    c.compress(raw, off.to(dev), i32(sizes).to(dev), comp, coff.to(dev), i32(caps).to(dev), res, opts, sized=sized)
-    torch.cuda.synchronize()
-    assert not any(_lib.is_error(r) for r in u32(res)), "compress"
-    return comp, coff.to(dev), res
-
-
 def calibration(rng, n):
     return rng.uniform(-600.0, 600.0, n).astype(np.float32), rng.uniform(0.01, 2.5, n).astype(np.float32)
-
-
-def chunking(L, S, mode, end_align, pad):
-    ch = _lib.GpuChunking()
-    ch.chunk_len, ch.step = L, S
-    ch.mode = _lib.VBZ_GPU_CHUNK_END if mode == "end" else _lib.VBZ_GPU_CHUNK_PAD
-    ch.end_align = end_align if mode == "end" else 0
-    ch.pad = pad
-    return ch
-
-
-def fmt(dtype, signed, offset=None, scale=None):
-    f = _lib.GpuSignalFormat()
-    f.out_type = {torch.float32: 1, torch.float16: 2, torch.bfloat16: 3}[dtype]
-    f.is_signed = int(signed)
-    if offset is not None:
-        f.offset = offset.data_ptr()
-    if scale is not None:
-        f.scale = scale.data_ptr()
-    return f
 
 
 def host_samples(src, src_off, src_size, caps16, sized):
@@ -184,12 +47,13 @@ def decode_chunks_both(c, src, src_off, src_size, caps16, opts, sized, dtype, L,
     hold the canary.  Returns (chunk results, int16 results, the arena's bits)."""
     dev = c.device
     n = len(caps16)
-    E = ELEM[dtype]
+    dt = key(dtype)
+    E = ELEM[dt]
     off16, tot16 = batch.layout([int(x) for x in caps16], 64)
     off16_d = off16.to(dev)
     caps_d = i32(caps16).to(dev)
     Ts = host_samples(src, src_off, src_size, caps16, sized)
-    table = ref_layout(Ts, L, S, mode, end_align) if first is None else np.asarray(first, np.int64)
+    table = table_of(Ts, L, S, mode, end_align) if first is None else np.asarray(first, np.int64)
     total = int(table[-1])
     nrows = total + spare if rows is None else rows
     arena_rows = max(nrows, total) + spare
@@ -203,7 +67,7 @@ def decode_chunks_both(c, src, src_off, src_size, caps16, opts, sized, dtype, L,
     b = c._batch(src, src_off, src_size, torch.empty(0, dtype=torch.uint8, device=dev), off16_d, caps_d, res)
     b.dst = None
     b.dst_bytes = tot16
-    ch = chunking(L, S, mode, end_align, pad)
+    ch = c._chunking(L, S, mode, end_align, pad)
     f = fmt(dtype, signed, o_d, s_d)
     torch.cuda.synchronize()
     rc = c.L.vbz_gpu_decompress_chunks_batch(c.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized), ctypes.byref(f), ctypes.byref(ch), first_d.data_ptr(),
@@ -219,7 +83,7 @@ def decode_chunks_both(c, src, src_off, src_size, caps16, opts, sized, dtype, L,
     r16, rc_ = u32(res16), u32(res)
     raw_h = raw.cpu().numpy()
     bits = chunks.cpu().numpy().view(np.uint32 if E == 4 else np.uint16).reshape(arena_rows, L)
-    padb = pad_bits(pad, dtype)
+    padb = pad_bits(pad, dt)
     owned = np.zeros(arena_rows, bool)
     refused = np.zeros(arena_rows, bool)
     offs = off16.tolist()
@@ -235,14 +99,14 @@ def decode_chunks_both(c, src, src_off, src_size, caps16, opts, sized, dtype, L,
         if _lib.is_error(want):
             continue
         T = want // E
-        x16 = raw_h[offs[i] : offs[i] + 2 * T].view(np.uint16)
-        ref = ref_rows(ref_bits(x16, np.full(T, o_all[i], np.float32), np.full(T, s_all[i], np.float32), signed, dtype), T, L, S, mode, end_align, padb)
+        x16 = raw_h[offs[i] : offs[i] + 2 * T].view(np.int16 if signed else np.uint16)
+        ref = ref_rows(typed_bits(x16, o_all[i], s_all[i], dt), T, L, S, mode, end_align, padb)
         assert hi - lo == ref.shape[0], (i, hi - lo, ref.shape)
         got = bits[lo:hi]
-        nan = is_nan_bits(ref, dtype)
+        nan = is_nan_bits(ref, dt)
         bad = (got != ref) & ~nan
         assert not bad.any(), (i, T, np.argwhere(bad)[:4].tolist())
-        assert is_nan_bits(got[nan], dtype).all(), i
+        assert is_nan_bits(got[nan], dt).all(), i
         owned[lo:hi] = True
     assert (bits[refused & ~owned].view(np.uint8) == CANARY).all(), "a row of a read the chunk check refused was written"
     tail = bits[total:]
@@ -265,9 +129,9 @@ def test_layout_matches_numpy(L, S):
         first, info = c.chunk_layout(samples, L, S, mode=mode, end_align=ea)
         torch.cuda.synchronize()
         Tr = [t if t < 0x80000000 else 0 for t in Ts]
-        want = ref_layout(Tr, L, S, mode, ea)
+        want = table_of(Tr, L, S, mode, ea)
         assert np.array_equal(first.cpu().numpy(), want), (mode, ea)
-        rows = [(i, int(s)) for i, t in enumerate(Tr) for s in ref_starts(t, L, S, mode, ea)]
+        rows = [(i, int(s)) for i, t in enumerate(Tr) for s in chunk_starts(t, L, S, mode, ea)]
         assert np.array_equal(info.cpu().numpy().astype(np.int64), np.array(rows, np.int64).reshape(-1, 2)), (mode, ea)
 
 
@@ -288,7 +152,7 @@ def test_layout_of_a_million_reads():
     assert np.array_equal(inf[:, 0], np.repeat(np.arange(n), K))
     for i in (1, 2, 3, n // 2 + 1, n - 1):   # (a few reads' starts in full)
         lo, hi = want[i], want[i + 1]
-        assert np.array_equal(inf[lo:hi, 1], ref_starts(int(Ts[i]), L, S, "end", 6)), i
+        assert np.array_equal(inf[lo:hi, 1], chunk_starts(int(Ts[i]), L, S, "end", 6)), i
 
 
 def test_layout_leaves_a_small_info_untouched():
@@ -297,8 +161,8 @@ def test_layout_leaves_a_small_info_untouched():
     Ts = [100, 5000, 20000]
     samples = i32(Ts).to(dev)
     first = torch.empty(4, dtype=torch.int64, device=dev)
-    ch = chunking(1024, 512, "pad", 0, 0.0)
-    total = int(ref_layout(Ts, 1024, 512, "pad", 0)[-1])
+    ch = c._chunking(1024, 512, "pad", 0, 0.0)
+    total = int(table_of(Ts, 1024, 512, "pad", 0)[-1])
     info = torch.full((total + 4, 2), -3, dtype=torch.int32, device=dev)
     assert c.L.vbz_gpu_chunk_layout_batch(c.ctx, 3, samples.data_ptr(), ctypes.byref(ch), first.data_ptr(), info.data_ptr(), total - 1) == 0
     c.synchronize()
@@ -307,7 +171,7 @@ def test_layout_leaves_a_small_info_untouched():
     assert c.L.vbz_gpu_chunk_layout_batch(c.ctx, 3, samples.data_ptr(), ctypes.byref(ch), first.data_ptr(), info.data_ptr(), total) == 0
     c.synchronize()
     assert (info[total:] == -3).all()
-    assert (info[:total, 0].cpu().numpy() == np.repeat(np.arange(3), np.diff(ref_layout(Ts, 1024, 512, "pad", 0)))).all()
+    assert (info[:total, 0].cpu().numpy() == np.repeat(np.arange(3), np.diff(table_of(Ts, 1024, 512, "pad", 0)))).all()
 
 
 # ---- 2. content: the option grid ------------------------------------------------------------------------------------------------
@@ -326,7 +190,7 @@ def test_bit_exact_grid(dtype, zz, version, level, sized):
             reads = [O.synth_signal(3, i, x) for i, x in enumerate(lens)]
         else:
             reads = [rng.integers(0, 1 << 16, x).astype(np.uint16) for x in lens]
-        src, off, size = compress_reads(c, reads, opts, sized)
+        src, off, size = compress(c, reads, opts, sized)
         caps = [a.nbytes + (2 * int(rng.integers(0, 40)) if sized else 0) for a in reads]
         o, s = calibration(rng, len(reads))
         for mi, (mode, ea) in enumerate(MODES):
@@ -411,7 +275,7 @@ def test_frames_libzstd_wrote_are_walked():
     lens = _ragged(rng, n, 1000, 3000)
     reads = [O.synth_signal(15, i, x) for i, x in enumerate(lens)]
     frames = [O.compress(a, O.options(True, 2, 1, 0)) for a in reads]
-    src, off, size = arena(frames)
+    src, off, size = arena(c, frames, 64)
     opts = c.options(True, 2, 1, 0)
     o, s = calibration(rng, n)
     paths = []
@@ -426,7 +290,7 @@ def test_fast5_chunks():
     idx = json.load(open(os.path.join(GOLDEN, "fast5_chunks.json")))
     blob = np.fromfile(os.path.join(GOLDEN, "fast5_chunks.bin"), np.uint8)
     bufs = [blob[e["chunk_offset"] : e["chunk_offset"] + e["chunk_size"]] for e in idx]
-    src, off, size = arena(bufs, 16)
+    src, off, size = arena(c, bufs, 16)
     opts = c.options(True, 2, 1, 0)
     caps = [2 * e["samples"] for e in idx]
     rc, _, _ = decode_chunks_both(c, src, off, size, caps, opts, True, torch.float16, 4000, 3600, "end", 8)
@@ -459,7 +323,7 @@ def test_damaged_frames_give_the_int16_verdicts(dtype):
         opts = c.options(True, 2, 1, 1)
         c.set_checksum(checksum)
         try:
-            src, off, size = compress_reads(c, reads, opts, sized)
+            src, off, size = compress(c, reads, opts, sized)
         finally:
             c.set_checksum(False)
         sz = u32(size)
@@ -493,7 +357,7 @@ def test_fuzz_corpus_verdicts():
         for cap in (0, 2, 64, 2 * f.nbytes, 8 * f.nbytes):
             bufs.append(f)
             caps.append(cap)
-    src, off, size = arena(bufs)
+    src, off, size = arena(c, bufs, 64)
     for zz, level, version in ((True, 1, 0), (False, 1, 1), (True, 0, 1)):
         opts = c.options(zz, 2, level, version)
         for sized in (False, True):
@@ -505,7 +369,7 @@ def _table_batch(c):
     lens = [5000, 12345, 801, 9000, 3, 40000, 7777]
     reads = [O.synth_signal(22, i, x) for i, x in enumerate(lens)]
     opts = c.options(True, 2, 1, 1)
-    src, off, size = compress_reads(c, reads, opts)
+    src, off, size = compress(c, reads, opts)
     return lens, reads, opts, src, off, size
 
 
@@ -515,7 +379,7 @@ def test_wrong_table_entries_write_nothing(dtype):
     lens, reads, opts, src, off, size = _table_batch(c)
     caps = [a.nbytes for a in reads]
     L, S = 1000, 904
-    good = ref_layout(lens, L, S, "end", 1)
+    good = table_of(lens, L, S, "end", 1)
     # read 2 one row short (read 3 one row long), read 5 one row long (read 6 one row short)
     t = good.copy()
     t[3] -= 1
@@ -534,7 +398,7 @@ def test_empty_read_writes_nothing():
     c = codec()
     reads = [np.zeros(0, np.int16), O.synth_signal(23, 1, 100), np.zeros(0, np.int16)]
     opts = c.options(True, 2, 1, 1)
-    src, off, size = compress_reads(c, reads, opts)
+    src, off, size = compress(c, reads, opts)
     rc, _, bits = decode_chunks_both(c, src, off, size, [0, 200, 0], opts, False, torch.float16, 256, 256, "pad", 0, pad=0.5, spare=2)
     assert [int(r) for r in rc] == [0, 200, 0]
     assert (bits[1:].view(np.uint8) == CANARY).all()   # (one row: read 1; nothing else)
@@ -547,7 +411,7 @@ def test_host_refusals():
     L_ = c.L
     reads = [O.synth_signal(19, 0, 1000)]
     opts = c.options(True, 2, 1, 1)
-    src, off, size = compress_reads(c, reads, opts)
+    src, off, size = compress(c, reads, opts)
     doff = torch.zeros(1, dtype=torch.int64, device=dev)
     dcap = i32([2000]).to(dev)
     res = torch.full((1,), -8, dtype=torch.int32, device=dev)
@@ -562,7 +426,7 @@ def test_host_refusals():
 
     def call(o=opts, f="ok", ch="ok", bt="ok", fp="ok", cp="ok", rows=1):
         f = fmt(torch.float16, True) if f == "ok" else f
-        ch = chunking(1024, 1024, "pad", 0, 0.0) if ch == "ok" else ch
+        ch = c._chunking(1024, 1024, "pad", 0, 0.0) if ch == "ok" else ch
         bt = batch_() if bt == "ok" else bt
         fp = first.data_ptr() if fp == "ok" else fp
         cp = chunks.data_ptr() if cp == "ok" else cp
@@ -571,7 +435,7 @@ def test_host_refusals():
                                                   rows)
 
     def bad_ch(**kw):
-        ch = chunking(1024, 512, "end", 1, 0.0)
+        ch = c._chunking(1024, 512, "end", 1, 0.0)
         for k, v in kw.items():
             setattr(ch, k, v)
         return ch
@@ -588,7 +452,7 @@ def test_host_refusals():
     for kw in ({"chunk_len": 0}, {"chunk_len": 12}, {"chunk_len": (1 << 20) + 8}, {"step": 0}, {"step": 4}, {"step": 1028}, {"step": 2048},
                {"mode": 2}, {"end_align": 0}, {"end_align": 4097}, {"reserved": 1}):
         assert call(ch=bad_ch(**kw)) == -2, kw
-    pad_mode = chunking(1024, 512, "pad", 0, 0.0)
+    pad_mode = c._chunking(1024, 512, "pad", 0, 0.0)
     pad_mode.end_align = 1
     assert call(ch=pad_mode) == -2
     assert call(fp=None) == -2
@@ -609,7 +473,7 @@ def test_host_refusals():
     assert (chunks == CANARY).all()
     assert int(first[1]) == 1
     assert L_.vbz_gpu_decompress_chunks_batch(c.ctx, None, ctypes.byref(opts), 0, ctypes.byref(fmt(torch.float16, True)),
-                                              ctypes.byref(chunking(1024, 1024, "pad", 0, 0.0)), first.data_ptr(), chunks.data_ptr(), 1) == -1
+                                              ctypes.byref(c._chunking(1024, 1024, "pad", 0, 0.0)), first.data_ptr(), chunks.data_ptr(), 1) == -1
     assert call() == 0
     torch.cuda.synchronize()
     assert int(res[0]) == 2000
@@ -624,7 +488,7 @@ def test_packed_round_trip(dtype, mode, ea):
     lens = [0, 1, 17] + _ragged(rng, 200, 100, 60000) + [300_000]
     reads = [O.synth_signal(20, i, x) for i, x in enumerate(lens)]
     opts = c.options(True, 2, 1, 1)
-    comp, coff, res = compress_reads(c, reads, opts, sized=True)
+    comp, coff, res = compress(c, reads, opts, sized=True)
     caps = [c.L.vbz_max_compressed_size(int(a.nbytes), ctypes.byref(opts)) for a in reads]
     packed, poff, psize = c.pack(comp, coff, i32(caps).to(c.device), res, align=16)
     o, s = calibration(rng, len(reads))
@@ -643,8 +507,8 @@ def test_packed_round_trip(dtype, mode, ea):
     flat = out_off[rd][:, None] + torch.where(inside, pos, torch.zeros_like(pos))
     want = torch.where(inside, out[flat], torch.full_like(out[flat], -0.25))
     assert chunks.dtype == dtype and chunks.shape == (int(first[-1]), L)
-    assert torch.equal(chunks.view(torch.int16 if ELEM[dtype] == 2 else torch.int32), want.view(torch.int16 if ELEM[dtype] == 2 else torch.int32))
-    assert int(first[-1]) == int(ref_layout(lens, L, S, mode, ea)[-1])
+    assert torch.equal(chunks.view(torch.int16 if ELEM[key(dtype)] == 2 else torch.int32), want.view(torch.int16 if ELEM[key(dtype)] == 2 else torch.int32))
+    assert int(first[-1]) == int(table_of(lens, L, S, mode, ea)[-1])
 
 
 def test_unsized_python_call():
@@ -658,7 +522,7 @@ def test_unsized_python_call():
     chunks, first, info = c.decompress_chunks(src, off, size, samples, result, opts, 10000, 9504, mode="end", end_align=1)
     torch.cuda.synchronize()
     assert [int(r) for r in result.cpu()] == [2 * x for x in lens]
-    assert np.array_equal(first.cpu().numpy(), ref_layout(lens, 10000, 9504, "end", 1))
+    assert np.array_equal(first.cpu().numpy(), table_of(lens, 10000, 9504, "end", 1))
     assert chunks.shape == (int(first[-1]), 10000) and chunks.dtype == torch.float16
     # against the signal decode of the same batch
     off16, tot16 = batch.layout([2 * x for x in lens], 16)

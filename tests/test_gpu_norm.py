@@ -10,52 +10,27 @@ import torch
 
 import norm_ref as R
 import oracle_lib as O
+from signal_ref import typed_bits
+from typed_support import ELEM, Frames, arena, codec, key, norm_of, u32, walk_signal
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-ELEM = {torch.float32: 4, torch.float16: 2, torch.bfloat16: 2}
-
-_codec = None
-
-
-def codec():
-    global _codec
-    if _codec is None:
-        _codec = batch.GpuCodec(0)
-    return _codec
-
-
-def norm_of(p):
-    method = {R.MED_MAD: "med_mad", R.QUANTILE: "quantile"}[p[0]]
-    return batch.Normalization(method, p[1], p[2], p[3], p[4], p[5], p[6])
-
-
-def i32(vals):
-    return torch.tensor(np.asarray(vals, np.uint64).astype(np.uint32).view(np.int32), dtype=torch.int32)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32).astype(np.uint64)
 
 
 # ---- reads ------------------------------------------------------------------------------------------------------------------
-def signal_like(rng, T):
-    return np.clip(330 + np.cumsum(rng.normal(0, 3, T)) * 0.05 + rng.normal(0, 40, T), 80, 580).astype(np.int16)
-
-
 def mixed_reads(seed, signed=True, long_len=100_003):
     """every kind of read the statistics must be exact for"""
     rng = np.random.default_rng(seed)
     out = []
     for T in (0, 1, 2, 3, 8, 999, 1000, 4096, 20_001, long_len):
-        out.append(signal_like(rng, T))
+        out.append(walk_signal(rng, T))
         out.append(rng.integers(-32768, 32768, T).astype(np.int16))           # full-range noise: every stage falls back
         out.append(np.full(T, rng.integers(-32768, 32768), np.int16))         # constant
         two = np.where(rng.random(T) < 0.5, -30000, 31000).astype(np.int16)   # two values far apart
         out.append(two)
-        far = signal_like(rng, T)                                             # a far outlier first: the first window misses
+        far = walk_signal(rng, T)                                             # a far outlier first: the first window misses
         if T:
             far[0] = -31000
         out.append(far)
@@ -68,89 +43,38 @@ def mixed_reads(seed, signed=True, long_len=100_003):
     return out
 
 
-def arena(bufs, align=64):
-    dev = codec().device
-    sizes = [int(b.nbytes) for b in bufs]
-    off, total = batch.layout(sizes, align)
-    a = np.zeros(total + 64, np.uint8)
-    for b, o in zip(bufs, off.tolist()):
-        a[o : o + b.nbytes] = np.frombuffer(np.ascontiguousarray(b).tobytes(), np.uint8)
-    return torch.from_numpy(a).to(dev), off.to(dev), i32(sizes).to(dev)
+def compress_oracle(c, reads, oopts, sized=False):
+    return arena(c, [O.compress(x.view(np.int16), oopts, sized=sized) for x in reads], 64)
 
 
-def compress_gpu(c, reads, opts, sized=False):
-    dev = c.device
-    raw, off, size = arena(reads)
-    caps = [c.L.vbz_max_compressed_size(int(a.nbytes), ctypes.byref(opts)) for a in reads]
-    coff, ctotal = batch.layout(caps, 64)
-    comp = torch.empty(ctotal + 64, dtype=torch.uint8, device=dev)
-    res = torch.zeros(len(reads), dtype=torch.int32, device=dev)
-    c.compress(raw, off, size, comp, coff.to(dev), i32(caps).to(dev), res, opts, sized=sized)
+def int16(case):
+    c = case.c
+    dst = torch.zeros(case.dst_bytes + 64, dtype=torch.uint8, device=c.device)
+    res = torch.zeros(case.n, dtype=torch.int32, device=c.device)
+    c.decompress(case.src, case.off, case.size, dst, case.doff, case.dcap, res, case.opts, sized=case.sized)
     torch.cuda.synchronize()
-    assert not any(_lib.is_error(r) for r in u32(res)), "compress"
-    return comp, coff.to(dev), res
+    return u32(res)
 
 
-def compress_oracle(reads, oopts, sized=False):
-    bufs = [O.compress(x.view(np.int16), oopts, sized=sized) for x in reads]
-    comp, off, size = arena(bufs)
-    return comp, off, size
-
-
-class Case:
-    """compressed reads and the int16 layout that describes them"""
-
-    def __init__(self, reads, opts, sized=False, comp=None):
-        c = codec()
-        self.reads, self.opts, self.sized = reads, opts, sized
-        if comp is None:
-            self.src, self.src_off, self.src_size = compress_gpu(c, reads, opts, sized)
-        else:
-            self.src, self.src_off, self.src_size = comp
-        self.n = len(reads)
-        self.T = [len(x) for x in reads]
-        dev = c.device
-        off, total = batch.layout([2 * t for t in self.T], 16)
-        self.dst_off = off.to(dev)
-        self.dst_cap = i32([2 * t for t in self.T]).to(dev)
-        self.dst_bytes = total
-
-    def int16(self):
-        c = codec()
-        dst = torch.zeros(self.dst_bytes + 64, dtype=torch.uint8, device=c.device)
-        res = torch.zeros(self.n, dtype=torch.int32, device=c.device)
-        c.decompress(self.src, self.src_off, self.src_size, dst, self.dst_off, self.dst_cap, res, self.opts, sized=self.sized)
-        torch.cuda.synchronize()
-        return u32(res)
-
-    def stats(self, p, signed=True):
-        c = codec()
-        res = torch.full((self.n,), -1, dtype=torch.int32, device=c.device)
-        ss = c.signal_norm(self.src, self.src_off, self.src_size, self.dst_off, self.dst_cap, res, self.opts, norm_of(p), signed=signed,
-                           sized=self.sized)
-        torch.cuda.synchronize()
-        return ss.cpu().numpy(), u32(res)
+def stats(case, p, signed=True):
+    c = case.c
+    res = torch.full((case.n,), -1, dtype=torch.int32, device=c.device)
+    ss = c.signal_norm(case.src, case.off, case.size, case.doff, case.dcap, res, case.opts, norm_of(p), signed=signed, sized=case.sized)
+    torch.cuda.synchronize()
+    return ss.cpu().numpy(), u32(res)
 
 
 def check_stats(case, p, signed=True):
-    ss, res = case.stats(p, signed)
-    assert (res == case.int16()).all()
+    ss, res = stats(case, p, signed)
+    assert (res == int16(case)).all()
     for i, x in enumerate(case.reads):
+        x = x if signed else x.view(np.uint16)
         assert res[i] == 2 * len(x), (i, res[i])
         shift, scale = R.shift_scale(x, p)
         got = ss[i]
         assert got[0].view(np.uint32) == shift.view(np.uint32) and got[1].view(np.uint32) == scale.view(np.uint32), (
             i, len(x), p, got, shift, scale)
     return ss, res
-
-
-def ref_bits(x, o, s, dtype):
-    y = (x.astype(np.float32) + o) * s
-    if dtype == torch.float32:
-        return y.view(np.uint32)
-    if dtype == torch.float16:
-        return y.astype(np.float16).view(np.uint16)
-    return torch.from_numpy(y).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
 
 
 # ---- 1. the statistics --------------------------------------------------------------------------------------------------------
@@ -160,13 +84,13 @@ OPTS = [(True, 1, 1, False), (True, 1, 0, False), (True, 0, 1, True), (False, 1,
 @pytest.mark.parametrize("zz,level,version,sized", OPTS)
 @pytest.mark.parametrize("pi", range(len(R.PARAMS)))
 def test_stats_exact(zz, level, version, sized, pi):
-    case = Case(mixed_reads(7 + pi), _lib.CompressionOptions(zz, 2, level, version), sized)
+    case = Frames(codec(), mixed_reads(7 + pi), _lib.CompressionOptions(zz, 2, level, version), sized)
     check_stats(case, R.PARAMS[pi])
 
 
 @pytest.mark.parametrize("pi", range(len(R.PARAMS)))
 def test_stats_uint16(pi):
-    case = Case(mixed_reads(11, signed=False), _lib.CompressionOptions(True, 2, 1, 1))
+    case = Frames(codec(), mixed_reads(11, signed=False), _lib.CompressionOptions(True, 2, 1, 1))
     check_stats(case, R.PARAMS[pi], signed=False)
 
 
@@ -177,26 +101,26 @@ def test_stats_uint16(pi):
 def test_signal_norm(dtype, pi, signed):
     c = codec()
     reads = mixed_reads(21, signed=signed, long_len=30_001)
-    case = Case(reads, _lib.CompressionOptions(True, 2, 1, 1))
+    case = Frames(codec(), reads, _lib.CompressionOptions(True, 2, 1, 1))
     p = R.PARAMS[pi]
-    E = ELEM[dtype]
+    E = ELEM[key(dtype)]
     n = case.n
     out = torch.zeros((case.dst_bytes // 2 + 64), dtype=dtype, device=c.device)
     res = torch.zeros(n, dtype=torch.int32, device=c.device)
     ss = torch.zeros((n, 2), dtype=torch.float32, device=c.device)
-    c.decompress_signal(case.src, case.src_off, case.src_size, out, case.dst_off // 2 * E, (case.dst_cap // 2) * E, res, case.opts, signed=signed,
+    c.decompress_signal(case.src, case.off, case.size, out, case.doff // 2 * E, (case.dcap // 2) * E, res, case.opts, signed=signed,
                         norm=norm_of(p), norm_out=ss)
     torch.cuda.synchronize()
     res = u32(res)
     ss = ss.cpu().numpy()
     bits = out.view(torch.int32 if E == 4 else torch.int16).cpu().numpy().view(np.uint32 if E == 4 else np.uint16)
-    offs = (case.dst_off // 2).cpu().numpy()
+    offs = (case.doff // 2).cpu().numpy()
     for i, x in enumerate(reads):
         assert res[i] == len(x) * E, (i, res[i])
         shift, scale, o, s = R.constants(*R.stats(x, p), p)
         assert ss[i][0] == shift and ss[i][1] == scale
         got = bits[offs[i] : offs[i] + len(x)]
-        want = ref_bits(x.view(np.int16) if signed else x, o, s, dtype)
+        want = typed_bits(x.view(np.int16) if signed else x, o, s, key(dtype))
         assert (got == want).all(), (i, len(x))
 
 
@@ -206,17 +130,17 @@ def test_signal_norm(dtype, pi, signed):
 def test_chunks_norm(mode, end_align, pi):
     c = codec()
     reads = mixed_reads(31, long_len=40_000)
-    case = Case(reads, _lib.CompressionOptions(True, 2, 1, 1))
+    case = Frames(codec(), reads, _lib.CompressionOptions(True, 2, 1, 1))
     samples = torch.tensor(case.T, dtype=torch.int32, device=c.device)
     ss = torch.zeros((case.n, 2), dtype=torch.float32, device=c.device)
     res_n = torch.zeros(case.n, dtype=torch.int32, device=c.device)
-    ch_n, first_n, _ = c.decompress_chunks(case.src, case.src_off, case.src_size, samples, res_n, case.opts, 1000, 504, mode, max(end_align, 1),
+    ch_n, first_n, _ = c.decompress_chunks(case.src, case.off, case.size, samples, res_n, case.opts, 1000, 504, mode, max(end_align, 1),
                                            pad=0.0, dtype=torch.float16, norm=norm_of(R.PARAMS[pi]), norm_out=ss)
     torch.cuda.synchronize()
     offset = (-ss[:, 0]).contiguous()
     scale = (1.0 / ss[:, 1].double()).float().contiguous()
     res_p = torch.zeros(case.n, dtype=torch.int32, device=c.device)
-    ch_p, first_p, _ = c.decompress_chunks(case.src, case.src_off, case.src_size, samples, res_p, case.opts, 1000, 504, mode, max(end_align, 1),
+    ch_p, first_p, _ = c.decompress_chunks(case.src, case.off, case.size, samples, res_p, case.opts, 1000, 504, mode, max(end_align, 1),
                                            pad=0.0, dtype=torch.float16, scale=scale, offset=offset)
     torch.cuda.synchronize()
     assert (u32(res_n) == u32(res_p)).all()
@@ -234,13 +158,13 @@ def small_reads(seed, n, lo=50, hi=400):
     out = []
     for i in range(n):
         T = int(rng.integers(lo, hi))
-        out.append(signal_like(rng, T) if i % 3 else rng.integers(-32768, 32768, T).astype(np.int16))
+        out.append(walk_signal(rng, T) if i % 3 else rng.integers(-32768, 32768, T).astype(np.int16))
     return out
 
 
 @pytest.mark.parametrize("pi", [0, 1])
 def test_split_batch(pi):
-    case = Case(small_reads(41, 16_500), _lib.CompressionOptions(True, 2, 1, 1))
+    case = Frames(codec(), small_reads(41, 16_500), _lib.CompressionOptions(True, 2, 1, 1))
     check_stats(case, R.PARAMS[pi])
 
 
@@ -248,43 +172,43 @@ def test_split_batch(pi):
 def test_routed_long_reads(pi):
     rng = np.random.default_rng(51)
     reads = small_reads(52, 600, 1000, 3000)
-    far = signal_like(rng, 300_000)
+    far = walk_signal(rng, 300_000)
     far[0] = 30000
     reads[100] = far
     reads[400] = rng.integers(-32768, 32768, 280_000).astype(np.int16)
-    reads[500] = signal_like(rng, 400_001)
-    case = Case(reads, _lib.CompressionOptions(True, 2, 1, 1))
+    reads[500] = walk_signal(rng, 400_001)
+    case = Frames(codec(), reads, _lib.CompressionOptions(True, 2, 1, 1))
     check_stats(case, R.PARAMS[pi])
 
 
 @pytest.mark.parametrize("pi", [0, 1, 2])
 def test_large_read_path(pi):
     rng = np.random.default_rng(61)
-    reads = [signal_like(rng, 400_000), rng.integers(-32768, 32768, 400_001).astype(np.int16), np.full(400_000, -5, np.int16)]
-    far = signal_like(rng, 399_999)
+    reads = [walk_signal(rng, 400_000), rng.integers(-32768, 32768, 400_001).astype(np.int16), np.full(400_000, -5, np.int16)]
+    far = walk_signal(rng, 399_999)
     far[0] = -32000
     reads.append(far)
-    check_stats(Case(reads, _lib.CompressionOptions(True, 2, 1, 1)), R.PARAMS[pi])
-    check_stats(Case(reads, _lib.CompressionOptions(True, 2, 0, 1), sized=True), R.PARAMS[pi])
+    check_stats(Frames(codec(), reads, _lib.CompressionOptions(True, 2, 1, 1)), R.PARAMS[pi])
+    check_stats(Frames(codec(), reads, _lib.CompressionOptions(True, 2, 0, 1), sized=True), R.PARAMS[pi])
 
 
 def test_one_huge_read():
     rng = np.random.default_rng(71)
-    x = signal_like(rng, 20_000_000)
-    case = Case([x], _lib.CompressionOptions(True, 2, 1, 1))
+    x = walk_signal(rng, 20_000_000)
+    case = Frames(codec(), [x], _lib.CompressionOptions(True, 2, 1, 1))
     for p in (R.BONITO, R.DORADO):
         check_stats(case, p)
     # counts above 2^16 per value, and the fallback: values far from the first sample
     y = np.where(rng.random(20_000_000) < 0.5, -20000, 25000).astype(np.int16)
     y[0] = 0
-    check_stats(Case([y], _lib.CompressionOptions(True, 2, 1, 1)), R.BONITO)
+    check_stats(Frames(codec(), [y], _lib.CompressionOptions(True, 2, 1, 1)), R.BONITO)
 
 
 @pytest.mark.parametrize("pi", [0, 1])
 def test_libzstd_frames(pi):
     reads = mixed_reads(81, long_len=50_000)
     oo = O.options(True, 2, 1, 1)
-    case = Case(reads, _lib.CompressionOptions(True, 2, 1, 1), sized=True, comp=compress_oracle(reads, oo, sized=True))
+    case = Frames(codec(), reads, _lib.CompressionOptions(True, 2, 1, 1), sized=True, comp=compress_oracle(codec(), reads, oo, sized=True))
     check_stats(case, R.PARAMS[pi])
 
 
@@ -292,7 +216,7 @@ def test_checksummed_frames():
     c = codec()
     c.set_checksum(1)
     try:
-        case = Case(mixed_reads(91, long_len=60_000), _lib.CompressionOptions(True, 2, 1, 1))
+        case = Frames(codec(), mixed_reads(91, long_len=60_000), _lib.CompressionOptions(True, 2, 1, 1))
     finally:
         c.set_checksum(0)
     check_stats(case, R.BONITO)
@@ -303,10 +227,10 @@ def test_checksummed_frames():
 def test_damaged_frames_and_bad_descriptors():
     c = codec()
     reads = mixed_reads(101, long_len=20_000)
-    case = Case(reads, _lib.CompressionOptions(True, 2, 1, 1))
+    case = Frames(codec(), reads, _lib.CompressionOptions(True, 2, 1, 1))
     src = case.src.clone()
-    offs = case.src_off.cpu().numpy()
-    sizes = u32(case.src_size)
+    offs = case.off.cpu().numpy()
+    sizes = u32(case.size)
     bad = set()
     for i in range(5, case.n, 7):   # damage the middle of some frames
         if sizes[i] > 16:
@@ -314,15 +238,15 @@ def test_damaged_frames_and_bad_descriptors():
             src[o : o + 4] ^= 0x5A
             bad.add(i)
     case.src = src
-    cap = case.dst_cap.clone()
+    cap = case.dcap.clone()
     for i in range(3, case.n, 11):   # wrong capacity: a destination size error
         if case.T[i] > 0:
             cap[i] = cap[i] + 2
             bad.add(i)
-    case.dst_cap = cap
+    case.dcap = cap
     for p in (R.BONITO, R.DORADO):
-        ss, res = case.stats(p)
-        want = case.int16()
+        ss, res = stats(case, p)
+        want = int16(case)
         assert (res == want).all()
         for i, x in enumerate(reads):
             if _lib.is_error(int(res[i])) or i in bad:
@@ -336,12 +260,12 @@ def test_refusals():
     c = codec()
     L = c.L
     reads = mixed_reads(111, long_len=1000)[6:12]   # (one sample each)
-    case = Case(reads, _lib.CompressionOptions(True, 2, 1, 1))
+    case = Frames(codec(), reads, _lib.CompressionOptions(True, 2, 1, 1))
     n = case.n
     ss = torch.full((n, 2), 7.0, dtype=torch.float32, device=c.device)
     res = torch.full((n,), 12345, dtype=torch.int32, device=c.device)
     out = torch.full((case.dst_bytes // 2 + 64,), 3.0, dtype=torch.float16, device=c.device)
-    b = c._batch(case.src, case.src_off, case.src_size, out.view(torch.uint8), case.dst_off, case.dst_cap, res)
+    b = c._batch(case.src, case.off, case.size, out.view(torch.uint8), case.doff, case.dcap, res)
     opts = case.opts
     f = _lib.GpuSignalFormat()
     f.out_type, f.is_signed = _lib.VBZ_GPU_SIGNAL_F16, 1

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import oracle_lib as O
+from typed_support import codec, i32, u32
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -17,24 +18,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 U32 = 0xFFFFFFFF
-
-_codec = None
-
-
-def codec():
-    global _codec
-    if _codec is None:
-        _codec = batch.GpuCodec(0)
-    return _codec
-
-
-def i32(vals):
-    return torch.tensor(np.asarray(vals, np.uint64).astype(np.uint32).view(np.int32), dtype=torch.int32)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32).astype(np.uint64)
-
 
 def ref_pack(dst, dst_bytes, dst_off, dst_cap, result, align):
     """numpy statement of vbz_gpu_pack_batch: (packed_off [n + 1], packed_size [n], arena bytes)"""

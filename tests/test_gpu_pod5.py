@@ -10,6 +10,8 @@ import torch
 import norm_ref as R
 import oracle_lib as O
 import pod5_ref as P
+from signal_ref import chunk_rows, typed_bits
+from typed_support import CANARY, ELEM, arena, codec, i32, key, pod5_compress, u32, walk_signal
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -17,29 +19,6 @@ pytestmark = pytest.mark.gpu
 POD5 = _lib.VBZ_GPU_VERSION_POD5
 E_ZSTD, E_DEST, E_STREAM = 0xFFFFFFFF, 0xFFFFFFFC, 0xFFFFFFFB
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-ELEM = {torch.float32: 4, torch.float16: 2, torch.bfloat16: 2}
-CANARY = 0x5A
-
-_codec = None
-
-
-def codec():
-    global _codec
-    if _codec is None:
-        _codec = batch.GpuCodec(0)
-    return _codec
-
-
-def i32(vals):
-    return torch.tensor(np.asarray(vals, np.uint64).astype(np.uint32).view(np.int32), dtype=torch.int32)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32).astype(np.uint64)
-
-
-def signal_like(rng, T):
-    return np.clip(330 + np.cumsum(rng.normal(0, 3, T)) * 0.05 + rng.normal(0, 40, T), 80, 580).astype(np.int16)
 
 
 def rows_of(seed, lens):
@@ -53,45 +32,19 @@ def rows_of(seed, lens):
         elif kind == 2:
             out.append(O.synth_signal(seed, k, T))
         else:
-            out.append(signal_like(rng, T))
+            out.append(walk_signal(rng, T))
     return out
 
 
-def arena(bufs, align=16):
-    dev = codec().device
-    sizes = [int(b.nbytes) for b in bufs]
-    off, total = batch.layout(sizes, align)
-    a = np.zeros(total + 64, np.uint8)
-    for b, o in zip(bufs, off.tolist()):
-        a[o : o + b.nbytes] = np.frombuffer(np.ascontiguousarray(b).tobytes(), np.uint8)
-    return torch.from_numpy(a).to(dev), off.to(dev), i32(sizes).to(dev)
-
-
-def int16_layout(rows):
-    dev = codec().device
+def int16_layout(c, rows):
+    dev = c.device
     off, total = batch.layout([2 * len(x) for x in rows], 16)
     return off.to(dev), i32([2 * len(x) for x in rows]).to(dev), total
 
 
-def lib_compress(c, rows, level=1):
-    """the library's POD5 frames of host rows -> list of numpy frames"""
-    dev = c.device
-    raw, off, size = arena(rows)
-    caps = [batch.pod5_max_compressed_size(len(x)) for x in rows]
-    coff, ctotal = batch.layout(caps, 16)
-    comp = torch.zeros(ctotal + 64, dtype=torch.uint8, device=dev)
-    res = torch.full((len(rows),), -8, dtype=torch.int32, device=dev)
-    c.compress(raw, off, size, comp, coff.to(dev), i32(caps).to(dev), res, batch.pod5_options(level))
-    torch.cuda.synchronize()
-    res = u32(res)
-    assert not any(_lib.is_error(int(r)) for r in res), [hex(int(r)) for r in res if _lib.is_error(int(r))][:4]
-    host = comp.cpu().numpy()
-    return [host[o : o + int(r)].copy() for o, r in zip(coff.tolist(), res)]
-
-
 def decode_int16(c, frames, rows, caps=None):
-    src, off, size = arena(frames)
-    doff, dcap, total = int16_layout(rows)
+    src, off, size = arena(c, frames, 16)
+    doff, dcap, total = int16_layout(c, rows)
     if caps is not None:   # (slots of the given capacities, apart)
         o, total = batch.layout([max(int(k), 2 * len(x)) + 16 for k, x in zip(caps, rows)], 16)
         doff, dcap = o.to(c.device), i32(caps).to(c.device)
@@ -103,28 +56,6 @@ def decode_int16(c, frames, rows, caps=None):
     return u32(res), [host[o : o + 2 * len(x)].view(np.int16) for o, x in zip(doff.tolist(), rows)]
 
 
-def ref_bits(x, o, s, dtype):
-    y = (x.astype(np.float32) + o) * s
-    if dtype == torch.float32:
-        return y.view(np.uint32)
-    if dtype == torch.float16:
-        return y.astype(np.float16).view(np.uint16)
-    return torch.from_numpy(y).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
-
-
-def chunk_starts(T, L, S, mode, end_align):
-    if T == 0:
-        return []
-    if T <= L:
-        return [0]
-    ks = -(-(T - L) // S)
-    starts = [k * S for k in range(ks + 1)]
-    if mode == "end":
-        e = -(-(T - L) // end_align) * end_align
-        starts[-1] = min(starts[-1], e)
-    return starts
-
-
 def check_outputs(c, frames, rows, typed=DTYPES, chunks=True, norms=True, seed=0):
     """every output of the decode against numpy: int16, calibrated F32 / F16 / BF16, chunks PAD / END (float16), MED_MAD / QUANTILE"""
     n = len(rows)
@@ -133,12 +64,12 @@ def check_outputs(c, frames, rows, typed=DTYPES, chunks=True, norms=True, seed=0
     assert all(int(r) == 2 * len(x) for r, x in zip(res, rows)), [(i, hex(int(r))) for i, r in enumerate(res) if int(r) != 2 * len(rows[i])][:4]
     for i, (g, x) in enumerate(zip(got, rows)):
         assert g.tobytes() == x.tobytes(), i
-    src, off, size = arena(frames)
+    src, off, size = arena(c, frames, 16)
     rng = np.random.default_rng(seed)
     o = rng.uniform(-600, 600, n).astype(np.float32)
     s = rng.uniform(0.01, 2.5, n).astype(np.float32)
     for dtype in typed:
-        E = ELEM[dtype]
+        E = ELEM[key(dtype)]
         toff, tot = batch.layout([E * len(x) for x in rows], 16)
         dst = torch.zeros((tot + 64) // E, dtype=dtype, device=dev)
         tres = torch.full((n,), -8, dtype=torch.int32, device=dev)
@@ -148,7 +79,7 @@ def check_outputs(c, frames, rows, typed=DTYPES, chunks=True, norms=True, seed=0
         assert (u32(tres) == np.array([E * len(x) for x in rows])).all(), dtype
         host = dst.view(torch.uint8).cpu().numpy()
         for i, x in enumerate(rows):
-            want = ref_bits(x, o[i], s[i], dtype)
+            want = typed_bits(x, o[i], s[i], key(dtype))
             assert host[toff[i] : toff[i] + E * len(x)].view(want.dtype).tobytes() == want.tobytes(), (dtype, i)
     if chunks:
         samples = i32([len(x) for x in rows]).to(dev)
@@ -161,18 +92,13 @@ def check_outputs(c, frames, rows, typed=DTYPES, chunks=True, norms=True, seed=0
             assert (u32(res) == np.array([2 * len(x) for x in rows])).all(), mode
             hc = ch.view(torch.int16).cpu().numpy().view(np.uint16)
             first = first.cpu().numpy()
-            padv = np.float16(-7.0).view(np.uint16)
             for i, x in enumerate(rows):
-                st = chunk_starts(len(x), L, S, mode, ea)
+                st, want = chunk_rows(x, L, S, mode, ea, o[i], s[i], -7.0, "f16")
                 assert first[i + 1] - first[i] == len(st), (mode, i)
-                bits = ref_bits(x, o[i], s[i], torch.float16)
-                for k, a in enumerate(st):
-                    want = np.full(L, padv, np.uint16)
-                    seg = bits[a : a + L]
-                    want[: len(seg)] = seg
-                    assert (hc[first[i] + k] == want).all(), (mode, i, k)
+                bad = np.argwhere(hc[first[i] : first[i + 1]] != want)
+                assert bad.size == 0, (mode, i, bad[:4].tolist())
     if norms:
-        doff, dcap, _ = int16_layout(rows)
+        doff, dcap, _ = int16_layout(c, rows)
         for p, nm in ((R.BONITO, batch.MED_MAD), (R.DORADO, batch.DORADO_QUANTILE)):
             res = torch.full((n,), -8, dtype=torch.int32, device=dev)
             ss = c.signal_norm(src, off, size, doff, dcap, res, batch.pod5_options(), nm)
@@ -191,7 +117,7 @@ def check_outputs(c, frames, rows, typed=DTYPES, chunks=True, norms=True, seed=0
             host = dst.view(torch.uint8).cpu().numpy()
             for i, x in enumerate(rows[:64]):
                 _, _, so, sc = R.constants(*R.stats(x, p), p)
-                want = ref_bits(x, so, sc, torch.float16)
+                want = typed_bits(x, so, sc, "f16")
                 assert host[toff[i] : toff[i] + E * len(x)].view(np.uint16).tobytes() == want.tobytes(), i
 
 
@@ -199,7 +125,7 @@ def check_outputs(c, frames, rows, typed=DTYPES, chunks=True, norms=True, seed=0
 def stage(fn, bufs, caps):
     c = codec()
     dev = c.device
-    src, off, size = arena(bufs)
+    src, off, size = arena(c, bufs, 16)
     doff, tot = batch.layout([int(x) + 32 for x in caps], 16)
     dst = torch.zeros(tot + 64, dtype=torch.uint8, device=dev)
     res = torch.full((len(bufs),), -8, dtype=torch.int32, device=dev)
@@ -279,7 +205,7 @@ def test_library_rows_decode_with_libzstd(trailers, checksum):
         rng = np.random.default_rng(7)
         for lens in ([102_400, 3, 0, 50_001, 700_000], rng.integers(0, 9000, 3000).tolist()):
             rows = rows_of(7, lens)
-            frames = lib_compress(c, rows)
+            frames = pod5_compress(c, rows)
             for i, (f, x) in enumerate(zip(frames, rows)):
                 assert len(f) <= P.max_compressed_size(len(x)), i
                 back = P.decompress_row(f, len(x))
@@ -298,9 +224,9 @@ def test_canonical_bytes():
     try:
         rng = np.random.default_rng(8)
         rows = rows_of(8, rng.integers(2000, 20_000, 4096).tolist())
-        whole = lib_compress(c, rows)
+        whole = pod5_compress(c, rows)
         for i in (0, 1, 2, 3, 1000, 4095):
-            assert lib_compress(c, [rows[i]])[0].tobytes() == whole[i].tobytes(), i
+            assert pod5_compress(c, [rows[i]])[0].tobytes() == whole[i].tobytes(), i
     finally:
         c.set_canonical(False)
 
@@ -330,7 +256,7 @@ def test_verdicts_row_by_row():
     for i in (5, 7):
         assert got[i].tobytes() == rows[i].tobytes()
     # the same frames through the chunk and signal calls: the same verdicts
-    src, off, size = arena(frames)
+    src, off, size = arena(c, frames, 16)
     dst = torch.zeros(8 * 5000 * 4 + 4096, dtype=torch.float32, device=c.device)
     toff, _ = batch.layout([4 * len(x) for x in rows], 16)
     tres = torch.full((len(rows),), -8, dtype=torch.int32, device=c.device)
@@ -352,8 +278,8 @@ def test_dst_cap_mismatch_and_odd_caps():
     assert int(res[4]) == 6000
     # an odd capacity: what the v0 int16 call gives for the same slot
     v0 = [O.compress(x, O.options(True, 2, 1, 0)) for x in rows]
-    src, off, size = arena(v0)
-    doff, _, total = int16_layout(rows)
+    src, off, size = arena(c, v0, 16)
+    doff, _, total = int16_layout(c, rows)
     dst = torch.zeros(total + 64, dtype=torch.uint8, device=c.device)
     r0 = torch.full((5,), -8, dtype=torch.int32, device=c.device)
     c.decompress(src, off, size, dst, doff, i32(caps).to(c.device), r0, c.options(True, 2, 1, 0))
@@ -366,7 +292,7 @@ def test_unaligned_typed_slots_keep_canaries():
     dev = c.device
     rows = rows_of(11, [1000, 1001, 999, 1000])
     frames = [P.compress_row(x) for x in rows]
-    src, off, size = arena(frames)
+    src, off, size = arena(c, frames, 16)
     E = 4
     toff = [0, 4096 + 2, 8192, 12288 + 4]   # the second slot is not 4-byte aligned
     tcap = [E * len(x) for x in rows]
@@ -390,7 +316,7 @@ def test_host_refusals():
     c = codec()
     L = c.L
     rows = rows_of(12, [100, 200])
-    raw, off, size = arena(rows)
+    raw, off, size = arena(c, rows, 16)
     dst = torch.zeros(4096, dtype=torch.uint8, device=c.device)
     doff = torch.tensor([0, 1024], dtype=torch.int64, device=c.device)
     cap = i32([1024, 1024]).to(c.device)
@@ -419,14 +345,14 @@ def test_read_layout_contiguous_reads():
     c = codec()
     dev = c.device
     rng = np.random.default_rng(13)
-    reads = [signal_like(rng, 2 * P.ROW + 5000), signal_like(rng, 777), signal_like(rng, P.ROW + 3)]
+    reads = [walk_signal(rng, 2 * P.ROW + 5000), walk_signal(rng, 777), walk_signal(rng, P.ROW + 3)]
     rows, first = [], []
     for x in reads:
         first.append(len(rows))
         rows += [x[s : s + P.ROW] for s in range(0, len(x), P.ROW)]
     assert first == [0, 3, 4]
     frames = [P.compress_row(x) for x in rows]
-    src, off, size = arena(frames)
+    src, off, size = arena(c, frames, 16)
     lay = batch.pod5_read_layout([len(x) for x in rows], first, device=dev)
     dst = torch.zeros(lay.total + 64, dtype=torch.uint8, device=dev)
     res = torch.full((len(rows),), -8, dtype=torch.int32, device=dev)
@@ -459,6 +385,6 @@ def test_ratio_against_libzstd_level1():
     lens = [O.synth_read_length(5, i) for i in range(256)]
     synth = [O.synth_signal(5, i, n) for i, n in enumerate(lens)]
     for rows in (golden, synth):
-        ours = sum(len(f) for f in lib_compress(c, rows))
+        ours = sum(len(f) for f in pod5_compress(c, rows))
         ref = sum(len(P.compress_row(x)) for x in rows)
         assert ours <= ref / 0.9, (ours, ref)

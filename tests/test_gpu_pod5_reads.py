@@ -3,7 +3,6 @@ as one signal.  Chunks, shift / scale and the normalised typed signal are held b
 and norm_ref on the concatenated rows) for grouping shapes that reach every boundary of the svb16 tile (2 048 samples) and of a 16-byte
 line, on the one-wavefront and the large-read path, in split and routed call shapes; then verdicts, untrusted tables, refusals."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -13,176 +12,15 @@ import norm_ref as R
 import oracle_lib as O
 import pod5_ref as P
 import pod5_reads_ref as PR
+from typed_support import CANARY, ELEM, SHAPES, TORCH, Call, arena, check_chunks, codec, expect_results, frames_of, i32, pod5_compress, u32
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
 
 E_ZSTD, E_INPUT, E_DEST, E_STREAM = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFC, 0xFFFFFFFB
-TORCH = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-ELEM = {"f32": 4, "f16": 2, "bf16": 2}
-SIG = {"f32": _lib.VBZ_GPU_SIGNAL_F32, "f16": _lib.VBZ_GPU_SIGNAL_F16, "bf16": _lib.VBZ_GPU_SIGNAL_BF16}
-CANARY = 0x5A
-GUARD = 4   # canary chunk rows behind the arena's last row
 
-# the grouping shapes: rows per read (sample counts)
-SHAPES = [
-    [1500],                                # one row: the row-wise call's chunks
-    [2048, 100],
-    [13, 7, 1, 2047, 2049],                # rows that begin inside a 16-byte line
-    [800, 0, 800],                         # an empty row in the middle
-    [1200, 0],                             # the last row is empty
-    [],                                    # no rows
-    [0, 0],                                # only empty rows
-    [300] * 40,                            # a chunk spans more than 3 rows
-    [4096, 4096, 5],
-    [24, 8, 2056, 16],                     # every row begins at a multiple of 8: whole lines across rows
-]
 CHUNKINGS = [(8, 8, "pad", 0), (1024, 1000, "pad", 0), (4096, 4096, "pad", 0), (1024, 1000, "end", 1), (1024, 1000, "end", 6), (1024, 1000, "end", 8),
              (8, 8, "end", 6)]
-
-_codecs = {}
-
-
-def codec(**env):
-    """a codec whose context was created under the given VBZ_HIP_* knobs (read when the context is created)"""
-    key = tuple(sorted(env.items()))
-    if key not in _codecs:
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update({k: str(v) for k, v in env.items()})
-        try:
-            _codecs[key] = batch.GpuCodec(0)
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-    return _codecs[key]
-
-
-def i32(vals):
-    return torch.tensor(np.asarray(vals, np.uint64).astype(np.uint32).view(np.int32), dtype=torch.int32)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32).astype(np.uint64)
-
-
-def make_rows(seed, shapes):
-    """(rows, first_row) of reads with the given row lengths: signal-like int16, every third read full-range noise"""
-    rng = np.random.default_rng(seed)
-    rows, first = [], []
-    for k, lens in enumerate(shapes):
-        first.append(len(rows))
-        for n in lens:
-            if k % 3 == 2:
-                rows.append(rng.integers(-32768, 32768, n).astype(np.int16))
-            else:
-                rows.append(np.clip(330 + rng.normal(0, 40, n) + 60 * np.sin(np.arange(n) / 50.0), -500, 900).astype(np.int16))
-    return rows, first
-
-
-_frames = {}
-
-
-def frames_of(seed, shapes):
-    """the rows of make_rows as libzstd wrote them (pod5's frames), computed once"""
-    key = (seed, repr(shapes))
-    if key not in _frames:
-        rows, first = make_rows(seed, shapes)
-        _frames[key] = (rows, first, [P.compress_row(x) for x in rows])
-    return _frames[key]
-
-
-def arena(c, bufs, align=16):
-    sizes = [int(b.nbytes) for b in bufs]
-    off, total = batch.layout(sizes, align)
-    a = np.zeros(total + 64, np.uint8)
-    for b, o in zip(bufs, off.tolist()):
-        a[o : o + b.nbytes] = np.frombuffer(np.ascontiguousarray(b).tobytes(), np.uint8)
-    return torch.from_numpy(a).to(c.device), off.to(c.device), i32(sizes).to(c.device)
-
-
-class Call:
-    """One raw call over reads: the batch, the tables and canary-filled outputs, all kept alive on the object."""
-
-    def __init__(self, c, frames, row_samples, table, dtype="f16", chunking=None, norm=None, offset=None, scale=None, chunk_first=None, signed=True):
-        dev = c.device
-        self.c, self.n, self.R, self.dtype = c, len(frames), len(table) - 1, dtype
-        self.src, self.off, self.size = arena(c, frames)
-        caps = [2 * int(s) for s in row_samples]
-        doff, self.total = batch.layout(caps, 16)
-        self.doff, self.dcap = doff.to(dev), i32(caps).to(dev)
-        self.result = torch.full((max(self.n, 1),), -8, dtype=torch.int32, device=dev)
-        self.read_result = torch.full((max(self.R, 1),), -8, dtype=torch.int32, device=dev)
-        self.table = i32(table).to(dev)
-        self.reads = _lib.GpuPod5Reads()
-        self.reads.n_reads, self.reads.first_row, self.reads.read_result = self.R, self.table.data_ptr(), self.read_result.data_ptr()
-        self.b = c._batch(self.src, self.off, self.size, torch.empty(0, dtype=torch.uint8, device=dev), self.doff, self.dcap, self.result)
-        self.b.dst, self.b.dst_bytes = None, self.total
-        self.f = _lib.GpuSignalFormat()
-        self.f.out_type, self.f.is_signed = SIG[dtype], int(signed)
-        self.keep = []
-        for name, t in (("offset", offset), ("scale", scale)):
-            if t is not None:
-                t = torch.from_numpy(np.asarray(t, np.float32)).to(dev)
-                self.keep.append(t)
-                setattr(self.f, name, t.data_ptr())
-        self.m = norm.c_struct() if norm is not None else None
-        self.ss = torch.full((max(self.R, 1), 2), -777.0, dtype=torch.float32, device=dev)
-        self.opts = batch.pod5_options()
-        self.ch = None
-        if chunking is not None:
-            L, S, mode, ea = chunking
-            self.ch = c._chunking(L, S, mode, ea, -7.0)
-            T = [sum(int(s) for s in row_samples[table[k] : table[k + 1]]) if table[k] <= table[k + 1] <= self.n else 0 for k in range(self.R)]
-            counts = [len(PR.chunk_starts(t, L, S, mode, ea)) for t in T]
-            first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64) if chunk_first is None else np.asarray(chunk_first, np.int64)
-            self.first_host = first
-            self.chunk_first = torch.from_numpy(first).to(dev)
-            self.rows = int(np.sum(counts)) if chunk_first is None else int(max(first))
-            self.chunks = torch.full(((self.rows + GUARD) * L * ELEM[dtype],), CANARY, dtype=torch.uint8, device=dev)
-
-    def chunk_call(self):
-        m = ctypes.byref(self.m) if self.m is not None else None
-        rc = self.c.L.vbz_gpu_pod5_decompress_chunks_batch(self.c.ctx, ctypes.byref(self.b), ctypes.byref(self.opts), ctypes.byref(self.f), ctypes.byref(self.ch),
-                                                           ctypes.byref(self.reads), self.chunk_first.data_ptr(), self.chunks.data_ptr(), self.rows, m,
-                                                           self.ss.data_ptr() if self.m is not None else None)
-        self.c.synchronize()
-        return rc
-
-    def stats_call(self, signed=True):
-        rc = self.c.L.vbz_gpu_pod5_signal_norm_batch(self.c.ctx, ctypes.byref(self.b), ctypes.byref(self.opts), int(signed), ctypes.byref(self.reads),
-                                                     ctypes.byref(self.m), self.ss.data_ptr())
-        self.c.synchronize()
-        return rc
-
-    def chunk_bits(self):
-        L = self.ch.chunk_len
-        host = self.chunks.cpu().numpy()
-        return host.view(np.uint32 if self.dtype == "f32" else np.uint16).reshape(self.rows + GUARD, L)
-
-
-def check_chunks(call, rows, first, chunking, consts, skip=()):
-    """every read's chunk rows against the reference, the canary behind the arena; consts[k] = (offset, scale) of read k"""
-    L, S, mode, ea = chunking
-    got = call.chunk_bits()
-    sig = PR.read_signals(rows, first)
-    cf = call.first_host
-    for k, x in enumerate(sig):
-        if k in skip:
-            continue
-        starts, want = PR.chunk_rows(x, L, S, mode, ea, consts[k][0], consts[k][1], -7.0, call.dtype)
-        assert cf[k + 1] - cf[k] == len(starts), k
-        bad = np.argwhere(got[cf[k] : cf[k + 1]] != want)
-        assert bad.size == 0, (chunking, call.dtype, "read", k, "chunk, position", bad[:4].tolist())
-    assert (call.chunks.cpu().numpy()[call.rows * L * ELEM[call.dtype] :] == CANARY).all(), "rows behind chunk_first[n] were written"
-
-
-def expect_results(call, rows, first, E):
-    b = PR.bounds(first, len(rows))
-    assert u32(call.result)[: call.n].tolist() == [E * len(x) for x in rows]
-    assert u32(call.read_result)[: call.R].tolist() == [E * sum(len(x) for x in rows[b[k] : b[k + 1]]) for k in range(call.R)]
 
 
 # ---- grouping shapes, chunk parameters, dtypes -------------------------------------------------------------------------------------
@@ -204,7 +42,7 @@ def test_grouping_shapes_chunks(segmented, chunking):
 def test_one_row_read_equals_row_wise_call_and_chunk_info():
     c = codec()
     rows, first, frames = frames_of(1, SHAPES)
-    src, off, size = arena(c, frames)
+    src, off, size = arena(c, frames, 16)
     samples = i32([len(x) for x in rows]).to(c.device)
     res = torch.full((len(rows),), -8, dtype=torch.int32, device=c.device)
     ch, cf, info, rr = c.pod5_decompress_chunks(src, off, size, samples, first, res, 1024, 1000, mode="end", end_align=6, pad=-7.0)
@@ -259,16 +97,7 @@ def golden():
     if _golden is None:
         rows, owner = P.golden_rows()
         first = [i for i in range(len(rows)) if i == 0 or owner[i] != owner[i - 1]]
-        c = codec()
-        raw, off, size = arena(c, rows)
-        caps = [batch.pod5_max_compressed_size(len(x)) for x in rows]
-        coff, ctotal = batch.layout(caps, 16)
-        comp = torch.zeros(ctotal + 64, dtype=torch.uint8, device=c.device)
-        res = torch.full((len(rows),), -8, dtype=torch.int32, device=c.device)
-        c.compress(raw, off, size, comp, coff.to(c.device), i32(caps).to(c.device), res, batch.pod5_options())
-        torch.cuda.synchronize()
-        host = comp.cpu().numpy()
-        own = [host[o : o + int(r)].copy() for o, r in zip(coff.tolist(), u32(res))]
+        own = pod5_compress(codec(), rows)
         _golden = (rows, first, PR.read_signals(rows, first), [P.compress_row(x) for x in rows], own)
     return _golden
 
@@ -297,7 +126,7 @@ def test_real_signal_normalised_chunks_and_signal(writer):
             if signed:   # (the reference's typed_bits takes int16 values: the uint16 reading is held to its statistics)
                 check_chunks(call, rows, first, chunking, consts)
     # the normalised typed signal over pod5_read_layout: every read contiguous, normalised by its own statistics
-    src, off, size = arena(c, frames)
+    src, off, size = arena(c, frames, 16)
     for dtype in ("f32", "f16"):
         res = torch.full((len(rows),), -8, dtype=torch.int32, device=c.device)
         out, lay, rr = c.pod5_decompress_signal_norm(src, off, size, samples, first, res, batch.MED_MAD, dtype=TORCH[dtype])
@@ -351,7 +180,7 @@ def test_failing_row_inside_a_read():
     frames[7] = O.zstd_compress(P.svb16_encode(rows[7])[:-1], 1)   # a stream with a byte cut off in the middle row of read 3
     samples = [len(x) for x in rows]
     # what the row-wise call says
-    src, off, size = arena(c, frames)
+    src, off, size = arena(c, frames, 16)
     res = torch.full((len(rows),), -8, dtype=torch.int32, device=c.device)
     c.decompress_chunks(src, off, size, i32(samples).to(c.device), res, batch.pod5_options(), 1024, 1000)
     torch.cuda.synchronize()

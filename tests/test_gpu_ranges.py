@@ -14,155 +14,15 @@ import oracle_lib as O
 import pod5_ref as P
 import pod5_reads_ref as PR
 import ranges_ref as G
-import test_gpu_pod5_reads as TP
+from signal_ref import table_of
+from typed_support import (CANARY, ELEM, NORMS, PAD, SHAPES, Call, Frames, Run, arena, codec, expect_results, frames_of, full, i32, ranges_struct, sine_signal,
+                           u32, unranged_results)
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
 
 E_ZSTD, E_INPUT, E_DEST, E_STREAM = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFC, 0xFFFFFFFB
 TO_END = 0xFFFFFFFF
-DT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-ELEM = {"f32": 4, "f16": 2, "bf16": 2}
-SIG = TP.SIG
-CANARY = 0x5A
-GUARD = 3
-PAD = -7.0
-NORMS = {"med_mad": (R.BONITO, batch.MED_MAD), "quantile": (R.DORADO, batch.DORADO_QUANTILE)}
-
-codec = TP.codec
-i32 = TP.i32
-u32 = TP.u32
-
-
-def signal_like(rng, T):
-    return np.clip(330 + rng.normal(0, 40, T) + 60 * np.sin(np.arange(T) / 50.0), -500, 900).astype(np.int16)
-
-
-def ranges_struct(c, begin, end, stats=0, reserved=0):
-    """(the C struct, its tables): begin / end per-read sequences, or None for a NULL table"""
-    g = _lib.GpuSampleRanges()
-    keep = []
-    for name, t in (("begin", begin), ("end", end)):
-        if t is not None:
-            d = i32([int(v) & 0xFFFFFFFF for v in t]).to(c.device)
-            keep.append(d)
-            setattr(g, name, d.data_ptr())
-    g.stats, g.reserved = stats, reserved
-    return g, keep
-
-
-class Frames:
-    """reads (int16 bits) compressed once, and the int16 layout that describes them"""
-
-    def __init__(self, c, reads, opts, sized=False, comp=None, slack=0):
-        self.c, self.reads, self.opts, self.sized, self.n = c, [np.asarray(x).view(np.int16) for x in reads], opts, sized, len(reads)
-        if comp is None:
-            raw, off, size = TP.arena(c, self.reads, 64)
-            caps = [c.L.vbz_max_compressed_size(int(a.nbytes), ctypes.byref(opts)) for a in self.reads]
-            coff, ctotal = batch.layout(caps, 64)
-            self.src = torch.empty(ctotal + 64, dtype=torch.uint8, device=c.device)
-            self.off = coff.to(c.device)
-            self.size = torch.zeros(self.n, dtype=torch.int32, device=c.device)
-            c.compress(raw, off, size, self.src, self.off, i32(caps).to(c.device), self.size, opts, sized=sized)
-            torch.cuda.synchronize()
-            assert not any(_lib.is_error(int(r)) for r in u32(self.size)), "compress"
-        else:
-            self.src, self.off, self.size = comp
-        self.T = [len(x) for x in self.reads]
-        caps16 = [2 * t + (slack if sized else 0) for t in self.T]   # (sized: the capacity may exceed the header's size)
-        doff, self.dst_bytes = batch.layout(caps16, 16)
-        self.doff, self.dcap = doff.to(c.device), i32(caps16).to(c.device)
-
-
-def table_of(Tp, L, S, mode, ea):
-    counts = [len(PR.chunk_starts(int(t), L, S, mode, ea)) for t in Tp]
-    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-
-
-def full(vals, n):
-    return [None] * n if vals is None else list(vals)
-
-
-class Run:
-    """one raw vbz_gpu_decompress_chunks_range_batch call into a canary arena, and its check against ranges_ref"""
-
-    def __init__(self, fr, chunking, dtype="f16", begin=None, end=None, norm=None, stats=0, signed=True, offset=None, scale=None, chunk_first=None,
-                 ranges=True, src=None):
-        c = fr.c
-        self.fr, self.chunking, self.dtype, self.begin, self.end, self.norm, self.stats, self.signed = fr, chunking, dtype, begin, end, norm, stats, signed
-        L, S, mode, ea = chunking
-        n, dev = fr.n, c.device
-        self.bg, self.en = full(begin, n), full(end, n)
-        self.Tp = [G.clamp(fr.T[i], self.bg[i], self.en[i]) for i in range(n)]
-        self.table = table_of([e - b for b, e in self.Tp], L, S, mode, ea) if chunk_first is None else np.asarray(chunk_first, np.int64)
-        self.rows = int(self.table[-1]) if chunk_first is None else int(max(self.table))
-        self.chunks = torch.full(((self.rows + GUARD) * L * ELEM[dtype],), CANARY, dtype=torch.uint8, device=dev)
-        self.first_d = torch.from_numpy(self.table).to(dev)
-        self.result = torch.full((max(n, 1),), -8, dtype=torch.int32, device=dev)
-        self.ss = torch.full((max(n, 1), 2), -777.0, dtype=torch.float32, device=dev)
-        self.o = np.zeros(n, np.float32) if offset is None else np.asarray(offset, np.float32)
-        self.s = np.ones(n, np.float32) if scale is None else np.asarray(scale, np.float32)
-        self.keep = []
-        f = _lib.GpuSignalFormat()
-        f.out_type, f.is_signed = SIG[dtype], int(signed)
-        for name, t in (("offset", offset), ("scale", scale)):
-            if t is not None:
-                d = torch.from_numpy(np.asarray(t, np.float32)).to(dev)
-                self.keep.append(d)
-                setattr(f, name, d.data_ptr())
-        b = c._batch(fr.src if src is None else src, fr.off, fr.size, torch.empty(0, dtype=torch.uint8, device=dev), fr.doff, fr.dcap, self.result)
-        b.dst, b.dst_bytes = None, fr.dst_bytes
-        ch = c._chunking(L, S, mode, ea, PAD)
-        m = norm[1].c_struct() if norm is not None else None
-        g, keep = ranges_struct(c, begin, end, stats)
-        self.keep += keep
-        torch.cuda.synchronize()
-        self.rc = c.L.vbz_gpu_decompress_chunks_range_batch(c.ctx, ctypes.byref(b), ctypes.byref(fr.opts), int(fr.sized), ctypes.byref(f), ctypes.byref(ch),
-                                                            self.first_d.data_ptr(), self.chunks.data_ptr(), self.rows,
-                                                            ctypes.byref(m) if m is not None else None, self.ss.data_ptr() if m is not None else None,
-                                                            ctypes.byref(g) if ranges else None)
-        c.synchronize()
-        self.err = c.L.vbz_gpu_last_error(c.ctx)
-
-    def bits(self):
-        L = self.chunking[0]
-        return self.chunks.cpu().numpy().view(np.uint32 if self.dtype == "f32" else np.uint16).reshape(self.rows + GUARD, L)
-
-    def values(self, i):
-        x = self.fr.reads[i]
-        return x if self.signed else x.view(np.uint16)
-
-    def check(self, expect=None, skip=()):
-        """verdicts (expect[i]: another verdict than T x E), every read's rows and constants, the canary everywhere else"""
-        assert self.rc == 0, self.err
-        fr = self.fr
-        L, S, mode, ea = self.chunking
-        E = ELEM[self.dtype]
-        res = u32(self.result)
-        got = self.bits()
-        ss = self.ss.cpu().numpy()
-        owned = np.zeros(self.rows + GUARD, bool)
-        for i in range(fr.n):
-            want_res = fr.T[i] * E if not (expect and i in expect) else expect[i]
-            assert int(res[i]) == want_res, (i, hex(int(res[i])), hex(want_res))
-            if _lib.is_error(want_res) or i in skip:
-                if i in skip:   # (rows left unspecified: a stream that failed while it was stored)
-                    owned[self.table[i] : self.table[i + 1]] = True
-                continue
-            x = self.values(i)
-            if self.norm is not None:
-                starts, want, shift, scale = G.norm_chunk_rows(x, self.bg[i], self.en[i], L, S, mode, ea, self.norm[0], self.stats, PAD, self.dtype)
-                assert (ss[i][0].view(np.uint32), ss[i][1].view(np.uint32)) == (shift.view(np.uint32), scale.view(np.uint32)), (
-                    "shift_scale", i, fr.T[i], self.bg[i], self.en[i], ss[i], shift, scale)
-            else:
-                starts, want = G.chunk_rows(x, self.bg[i], self.en[i], L, S, mode, ea, self.o[i], self.s[i], PAD, self.dtype)
-            lo, hi = int(self.table[i]), int(self.table[i + 1])
-            assert hi - lo == len(starts), (i, lo, hi, len(starts))
-            bad = np.argwhere(got[lo:hi] != want)
-            assert bad.size == 0, (self.chunking, self.dtype, "read", i, "T", fr.T[i], "range", self.bg[i], self.en[i], "chunk, position", bad[:4].tolist())
-            owned[lo:hi] = True
-        assert (got[~owned].view(np.uint8) == CANARY).all(), "a chunk row outside the reads' rows was written"
-        return self
 
 
 # ---- 1. small reads: sizes x begins x ends, chunkings x modes -----------------------------------------------------------------------------
@@ -184,7 +44,7 @@ def grid(c):
     """every size crossed with every begin and end, a read each: (Frames, begin, end)"""
     if "g" not in _grid:
         rng = np.random.default_rng(17)
-        base = {T: (signal_like(rng, T) if k % 3 else rng.integers(-32768, 32768, T).astype(np.int16)) for k, T in enumerate(SIZES)}
+        base = {T: (sine_signal(rng, T) if k % 3 else rng.integers(-32768, 32768, T).astype(np.int16)) for k, T in enumerate(SIZES)}
         reads, bg, en = [], [], []
         for T in SIZES:
             for b in begins_of(T):
@@ -232,7 +92,7 @@ def test_output_types_and_options(zz, version, level, sized):
     rng = np.random.default_rng(version * 8 + level * 4 + sized * 2 + zz)
     reads, bg, en = [], [], []
     for k, T in enumerate([0, 1, 7, 9, 513, 2049, 4101, 20_000]):
-        x = signal_like(rng, T) if (zz and k % 2) else rng.integers(-32768, 32768, T).astype(np.int16)
+        x = sine_signal(rng, T) if (zz and k % 2) else rng.integers(-32768, 32768, T).astype(np.int16)
         for b, e in option_ranges(T):
             reads.append(x)
             bg.append(b)
@@ -253,7 +113,7 @@ LARGE_RANGES = [(SEG - 8, 2 * SEG), (SEG, 2 * SEG + 1), (SEG + 1, 2 * SEG - 1), 
 
 def large_read_checks(c):
     rng = np.random.default_rng(23)
-    x = signal_like(rng, 40_000)
+    x = sine_signal(rng, 40_000)
     x[:3000] += 3000
     fr = Frames(c, [x], c.options(True, 2, 1, 1))
     for k, (b, e) in enumerate(LARGE_RANGES):
@@ -277,7 +137,7 @@ def small_batch(seed, n, lo=50, hi=3000):
     reads, bg, en = [], [], []
     for i in range(n):
         T = int(rng.integers(lo, hi))
-        reads.append(signal_like(rng, T) if i % 3 else rng.integers(-32768, 32768, T).astype(np.int16))
+        reads.append(sine_signal(rng, T) if i % 3 else rng.integers(-32768, 32768, T).astype(np.int16))
         b = int(rng.integers(0, T + 20))
         bg.append(b & ~7 if i % 2 else b)   # (every other begin a multiple of 8)
         en.append(int(rng.integers(0, T + 20)) if i % 5 else TO_END)
@@ -301,7 +161,7 @@ def test_routed_long_read_among_small_ones():
     reads, bg, en = small_batch(41, 600, 500, 5000)
     rng = np.random.default_rng(42)
     for i, (T, b, e) in {100: (300_000, 2000, 298_000), 400: (300_000, 2003, TO_END), 500: (280_001, SEG + 1, 3 * SEG)}.items():
-        reads[i] = signal_like(rng, T)
+        reads[i] = sine_signal(rng, T)
         reads[i][:b] += 3000
         bg[i], en[i] = b, e
     fr = Frames(c, reads, c.options(True, 2, 1, 1))
@@ -315,7 +175,7 @@ def other_frames_reads():
     reads, bg, en = [], [], []
     for T in (0, 1, 9, 2049, 4101, 50_000):
         for b, e in ((8, T), (3, max(T - 5, 0)), (2048, TO_END), (2051, T + 1)):
-            reads.append(signal_like(rng, T))
+            reads.append(sine_signal(rng, T))
             bg.append(b)
             en.append(e)
     return reads, bg, en
@@ -324,7 +184,7 @@ def other_frames_reads():
 def test_libzstd_frames():
     c = codec()
     reads, bg, en = other_frames_reads()
-    comp = TP.arena(c, [O.compress(x, O.options(True, 2, 1, 1), sized=True) for x in reads], 64)
+    comp = arena(c, [O.compress(x, O.options(True, 2, 1, 1), sized=True) for x in reads], 64)
     fr = Frames(c, reads, c.options(True, 2, 1, 1), sized=True, comp=comp)
     Run(fr, (1024, 1000, "end", 6), "f16", bg, en, norm=NORMS["med_mad"]).check()
     Run(fr, (16, 8, "pad", 0), "f32", bg, en).check()
@@ -364,7 +224,7 @@ def stats_reads():
     rng = np.random.default_rng(61)
     reads, bg, en = [], [], []
     for T, b in ((9000, 2000), (9001, 2003), (2049, 8), (513, 100)):
-        x = signal_like(rng, T) - 330      # the first `begin` samples at +3 000, the rest around 0
+        x = sine_signal(rng, T) - 330      # the first `begin` samples at +3 000, the rest around 0
         x[:b] += 3000
         reads.append(x.astype(np.int16))
         bg.append(b)
@@ -379,7 +239,7 @@ def stats_reads():
         en.append(T - 7)
     for Tp in (0, 1, 2):   # ranges of 0, 1 and 2 samples, at an aligned and at an odd begin
         for b in (16, 21):
-            reads.append(signal_like(rng, 700))
+            reads.append(sine_signal(rng, 700))
             bg.append(b)
             en.append(b + Tp)
     return reads, bg, en
@@ -430,12 +290,12 @@ def pod5_case(shapes=POD5_SHAPES):
             all_shapes.append(lens)
             bg.append(b)
             en.append(e)
-    rows, first, frames = TP.frames_of(71, all_shapes)
+    rows, first, frames = frames_of(71, all_shapes)
     return rows, first, frames, bg, en
 
 
-class RangedCall(TP.Call):
-    """TP.Call with the reads' ranges: chunk_first is the layout of the ranges' sample counts"""
+class RangedCall(Call):
+    """Call with the reads' ranges: chunk_first is the layout of the ranges' sample counts"""
 
     def __init__(self, c, frames, rows, first, begin, end, dtype="f16", chunking=None, norm=None, stats=0, chunk_first=None, **kw):
         table = PR.bounds(first, len(rows))
@@ -474,10 +334,10 @@ class RangedCall(TP.Call):
             if k in skip:
                 continue
             if norm is not None:
-                starts, want, shift, scale = G.norm_chunk_rows(x, self.bg[k], self.en[k], L, S, mode, ea, norm, self.stats, -7.0, self.dtype)
+                starts, want, shift, scale = G.norm_chunk_rows(x, self.bg[k], self.en[k], L, S, mode, ea, norm, self.stats, PAD, self.dtype)
                 assert (ss[k][0].view(np.uint32), ss[k][1].view(np.uint32)) == (shift.view(np.uint32), scale.view(np.uint32)), ("shift_scale", k)
             else:
-                starts, want = G.chunk_rows(x, self.bg[k], self.en[k], L, S, mode, ea, consts[k][0], consts[k][1], -7.0, self.dtype)
+                starts, want = G.chunk_rows(x, self.bg[k], self.en[k], L, S, mode, ea, consts[k][0], consts[k][1], PAD, self.dtype)
             assert cf[k + 1] - cf[k] == len(starts), k
             bad = np.argwhere(got[cf[k] : cf[k + 1]] != want)
             assert bad.size == 0, (chunking, self.dtype, "read", k, "range", self.bg[k], self.en[k], "chunk, position", bad[:4].tolist())
@@ -488,12 +348,6 @@ class RangedCall(TP.Call):
         for k, x in enumerate(self.sig):
             shift, scale, _, _ = G.shift_scale(x if signed else x.view(np.uint16), self.bg[k], self.en[k], norm, self.stats)
             assert (ss[k][0].view(np.uint32), ss[k][1].view(np.uint32)) == (shift.view(np.uint32), scale.view(np.uint32)), (k, len(x), self.bg[k], self.en[k])
-
-
-def unranged_results(c, frames, rows, first, chunking=None, norm=None):
-    call = TP.Call(c, frames, [len(x) for x in rows], PR.bounds(first, len(rows)), "f16", chunking, norm=norm)
-    assert (call.chunk_call() if chunking is not None else call.stats_call()) == 0
-    return u32(call.result)[: call.n].tolist(), u32(call.read_result)[: call.R].tolist()
 
 
 @pytest.mark.parametrize("segmented", [0, 1])
@@ -508,7 +362,7 @@ def test_pod5_reads(segmented, chunking):
     for dtype in (("f32", "f16", "bf16") if chunking[3] == 6 else ("f16",)):
         call = RangedCall(c, frames, rows, first, bg, en, dtype, chunking, offset=o, scale=s)
         assert call.chunk_call() == 0, c.L.vbz_gpu_last_error(c.ctx)
-        TP.expect_results(call, rows, first, ELEM[dtype])
+        expect_results(call, rows, first, ELEM[dtype])
         if dtype == "f16":
             assert (u32(call.result)[: call.n].tolist(), u32(call.read_result)[: call.R].tolist()) == want
         call.check_chunks(chunking, consts=list(zip(o, s)))
@@ -528,7 +382,7 @@ def test_pod5_reads_statistics(segmented):
             call.check_stats(p)
             call = RangedCall(c, frames, rows, first, bg, en, "f16", chunking, norm=nm, stats=stats)
             assert call.chunk_call() == 0
-            TP.expect_results(call, rows, first, 2)
+            expect_results(call, rows, first, 2)
             call.check_chunks(chunking, norm=p)
     call = RangedCall(c, frames, rows, first, bg, en, norm=batch.MED_MAD, signed=False)
     assert call.stats_call(signed=False) == 0
@@ -538,7 +392,7 @@ def test_pod5_reads_statistics(segmented):
 def test_pod5_reads_split_shape():
     rng = np.random.default_rng(81)
     shapes = [[int(v) for v in rng.integers(0, 900, int(rng.integers(1, 6)))] for _ in range(70)]
-    rows, first, frames = TP.frames_of(81, shapes)
+    rows, first, frames = frames_of(81, shapes)
     bg, en = [], []
     for k, lens in enumerate(shapes):
         T = sum(lens)
@@ -550,7 +404,7 @@ def test_pod5_reads_split_shape():
     for c in (codec(VBZ_HIP_SPLIT_MIN=64), codec(VBZ_HIP_SPLIT_MIN=0)):
         call = RangedCall(c, frames, rows, first, bg, en, "f16", chunking, norm=batch.MED_MAD)
         assert call.chunk_call() == 0
-        TP.expect_results(call, rows, first, 2)
+        expect_results(call, rows, first, 2)
         call.check_chunks(chunking, norm=R.BONITO)
         outs.append((call.chunks.cpu().numpy().tobytes(), call.ss.cpu().numpy().tobytes()))
     assert outs[0] == outs[1]
@@ -560,13 +414,13 @@ def test_pod5_rows_as_reads_of_their_own():
     """the row-wise calls with POD5 options (a row counts as a read): the svb16 decoder's ranged stores and counting pass"""
     c = codec()
     lens = [0, 1, 7, 9, 513, 2047, 2049, 4101, 20_000]
-    rows, first, frames = TP.frames_of(73, [[n] for n in lens for _ in range(6)])
+    rows, first, frames = frames_of(73, [[n] for n in lens for _ in range(6)])
     bg, en = [], []
     for n in lens:
         for b, e in ((8, n), (3, max(n - 5, 0)), (2048, TO_END), (2051, n + 1), (0, n), (n, 0)):
             bg.append(b)
             en.append(e)
-    fr = Frames(c, rows, batch.pod5_options(), comp=TP.arena(c, frames, 64))
+    fr = Frames(c, rows, batch.pod5_options(), comp=arena(c, frames, 64))
     Run(fr, (1024, 1000, "end", 6), "f16", bg, en, norm=NORMS["med_mad"]).check()
     Run(fr, (16, 8, "pad", 0), "f32", bg, en, norm=NORMS["quantile"], stats=1).check()
     Run(fr, (4096, 1024, "end", 1), "bf16", bg, en, offset=np.full(fr.n, -37.5, np.float32), scale=np.full(fr.n, 0.173, np.float32)).check()
@@ -577,7 +431,7 @@ def test_pod5_rows_as_reads_of_their_own():
 def test_chunk_first_of_the_whole_read_is_refused():
     c = codec()
     rng = np.random.default_rng(91)
-    reads = [signal_like(rng, T) for T in (5000, 3000, 2500, 900)]
+    reads = [sine_signal(rng, T) for T in (5000, 3000, 2500, 900)]
     bg, en = [0, 2000, 8, 100], [5000, TO_END, 1500, 200]   # K(T') != K(T) for reads 1 and 2; read 3 has one chunk either way
     fr = Frames(c, reads, c.options(True, 2, 1, 1))
     chunking = (1024, 1000, "pad", 0)
@@ -594,7 +448,7 @@ def test_chunk_first_of_the_whole_read_is_refused():
 def test_damage_behind_the_end_keeps_its_verdict():
     c = codec()
     rng = np.random.default_rng(92)
-    reads = [signal_like(rng, 9000) for _ in range(6)]
+    reads = [sine_signal(rng, 9000) for _ in range(6)]
     opts = c.options(True, 2, 0, 1)   # (level 0: the svb stream itself, so the damage is the stream's)
     fr = Frames(c, reads, opts)
     src = fr.src.clone()
@@ -633,7 +487,7 @@ def test_damage_behind_the_end_keeps_its_verdict():
 def test_pod5_row_failing_inside_a_read():
     c = codec()
     shapes = [[600, 700], [900, 1000, 1100], [500], [900, 1000, 1100], [640]]
-    rows, first, good = TP.frames_of(21, shapes)
+    rows, first, good = frames_of(21, shapes)
     frames = list(good)
     frames[3] = good[3][: len(good[3]) // 2]                       # a damaged frame in the middle row of read 1
     frames[7] = O.zstd_compress(P.svb16_encode(rows[7])[:-1], 1)   # a stream with a byte cut off in the middle row of read 3
@@ -666,7 +520,7 @@ def test_host_refusals_launch_nothing():
     c = codec()
     L = c.L
     rng = np.random.default_rng(93)
-    reads = [signal_like(rng, 500) for _ in range(4)]
+    reads = [sine_signal(rng, 500) for _ in range(4)]
     fr = Frames(c, reads, c.options(True, 2, 1, 1))
     n = fr.n
     res = torch.full((n,), 12345, dtype=torch.int32, device=c.device)
@@ -681,8 +535,8 @@ def test_host_refusals_launch_nothing():
     f.out_type, f.is_signed = _lib.VBZ_GPU_SIGNAL_F16, 1
     ch = c._chunking(1024, 1000, "pad", 0)
     m = batch.MED_MAD.c_struct()
-    rows, rfirst, frames = TP.frames_of(22, [[600, 700], [900, 1000, 1100], [500, 20]])
-    pc = TP.Call(c, frames, [len(x) for x in rows], PR.bounds(rfirst, len(rows)), "f16", (1024, 1000, "pad", 0), norm=batch.MED_MAD)
+    rows, rfirst, frames = frames_of(22, [[600, 700], [900, 1000, 1100], [500, 20]])
+    pc = Call(c, frames, [len(x) for x in rows], PR.bounds(rfirst, len(rows)), "f16", (1024, 1000, "pad", 0), norm=batch.MED_MAD)
 
     def calls(g, which=range(5), o=fr.opts, fmt=f, chk=ch, mp=m):
         gp = ctypes.byref(g)
@@ -766,8 +620,8 @@ def test_no_ranges_and_whole_ranges_are_the_existing_calls():
         r = Run(fr, (1024, 1000, "end", 6), "f16", norm=(R.BONITO, norm) if norm is not None else None, ranges=False)
         assert r.rc == 0 and r.chunks.cpu().numpy()[: len(outs[0][0])].tobytes() == outs[0][0] and u32(r.result).tolist() == outs[0][3]
     # the POD5 calls
-    rows, first, frames = TP.frames_of(1, TP.SHAPES)
-    src, off, size = TP.arena(c, frames)
+    rows, first, frames = frames_of(1, SHAPES)
+    src, off, size = arena(c, frames, 16)
     rs = i32([len(x) for x in rows]).to(c.device)
     sig = G.pod5_signals(rows, first)
     outs = []

@@ -11,6 +11,8 @@ import pytest
 import torch
 
 import oracle_lib as O
+from signal_ref import is_nan_bits, typed_bits
+from typed_support import CANARY, ELEM, arena, codec, compress, device_frames, i32, key, u32
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -19,88 +21,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 U32 = 0xFFFFFFFF
 E_ZSTD, E_INPUT, E_DEST = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFC
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-ELEM = {torch.float32: 4, torch.float16: 2, torch.bfloat16: 2}
-CANARY = 0x5A
-
-_codec = None
-
-
-def codec():
-    global _codec
-    if _codec is None:
-        _codec = batch.GpuCodec(0)
-    return _codec
-
-
-def i32(vals):
-    return torch.tensor(np.asarray(vals, np.uint64).astype(np.uint32).view(np.int32), dtype=torch.int32)
-
-
-def u32(t):
-    return t.cpu().numpy().view(np.uint32).astype(np.uint64)
-
-
-def ref_bits(x16, o, s, signed, dtype):
-    """numpy's statement of the conversion: the output's bits (uint32 / uint16) for 16-bit samples x16 (uint16 bits) and per-sample
-    float32 offset / scale"""
-    x = x16.view(np.int16) if signed else x16
-    y = (x.astype(np.float32) + o) * s
-    if dtype == torch.float32:
-        return y.view(np.uint32)
-    if dtype == torch.float16:
-        return y.astype(np.float16).view(np.uint16)
-    return torch.from_numpy(y).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
-
-
-def is_nan_bits(bits, dtype):
-    if dtype == torch.float32:
-        return np.isnan(bits.view(np.float32))
-    if dtype == torch.float16:
-        return np.isnan(bits.view(np.float16))
-    return ((bits & 0x7F80) == 0x7F80) & ((bits & 0x7F) != 0)
-
-
-def arena(bufs, align=64):
-    """host buffers -> (src, src_off, src_size) on the device"""
-    dev = codec().device
-    sizes = [int(b.nbytes) for b in bufs]
-    off, total = batch.layout(sizes, align)
-    a = np.zeros(total + 64, np.uint8)
-    for b, o in zip(bufs, off.tolist()):
-        a[o : o + b.nbytes] = np.frombuffer(np.ascontiguousarray(b).tobytes(), np.uint8)
-    return torch.from_numpy(a).to(dev), off.to(dev), i32(sizes).to(dev)
-
-
-def compress_reads(c, reads, opts, sized=False):
-    """the library's frames of host reads -> (src, src_off, src_size) on the device"""
-    dev = c.device
-    raw, off, size = arena(reads)
-    caps = [c.L.vbz_max_compressed_size(int(a.nbytes), ctypes.byref(opts)) for a in reads]
-    coff, ctotal = batch.layout(caps, 64)
-    comp = torch.empty(ctotal + 64, dtype=torch.uint8, device=dev)
-    res = torch.zeros(len(reads), dtype=torch.int32, device=dev)
-    c.compress(raw, off, size, comp, coff.to(dev), i32(caps).to(dev), res, opts, sized=sized)
-    torch.cuda.synchronize()
-    assert not any(_lib.is_error(r) for r in u32(res)), "compress"
-    return comp, coff.to(dev), res
-
-
-def device_frames(c, lens, seed, opts, sized=False):
-    """the library's frames of device-synthesised signal (reads of `lens` samples) -> (src, src_off, src_size) on the device"""
-    dev = c.device
-    lens_t = torch.tensor(lens, dtype=torch.int32, device=dev)
-    sizes = [2 * n for n in lens]
-    off, total = batch.layout(sizes, 64)
-    raw = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
-    c.synth_signal(seed, 0, raw, off.to(dev), lens_t)
-    caps = [c.L.vbz_max_compressed_size(s, ctypes.byref(opts)) for s in sizes]
-    coff, ctotal = batch.layout(caps, 64)
-    comp = torch.empty(ctotal + 64, dtype=torch.uint8, device=dev)
-    res = torch.zeros(len(lens), dtype=torch.int32, device=dev)
-    c.compress(raw, off.to(dev), i32(sizes).to(dev), comp, coff.to(dev), i32(caps).to(dev), res, opts, sized=sized)
-    torch.cuda.synchronize()
-    assert not any(_lib.is_error(r) for r in u32(res)), "compress"
-    return comp, coff.to(dev), res
 
 
 def calibration(rng, n, overflow=True):
@@ -119,7 +39,8 @@ def decode_both(c, src, src_off, src_size, caps16, opts, sized, dtype, offset=No
     typed verdict.  Checks every verdict, every sample, and the canary around and between the typed slots.  Returns the typed results."""
     dev = c.device
     n = len(caps16)
-    E = ELEM[dtype]
+    dt = key(dtype)
+    E = ELEM[dt]
     off16, tot16 = batch.layout([int(x) + 32 for x in caps16], 64)
     off16 = off16.tolist()
     tcap = [int(x) // 2 * E for x in caps16] if typed_cap is None else [int(x) for x in typed_cap]
@@ -157,12 +78,12 @@ def decode_both(c, src, src_off, src_size, caps16, opts, sized, dtype, offset=No
                 assert (t_h[toff[i] : toff[i] + tcap[i]] == CANARY).all(), i
             continue
         k = want // E
-        x16 = raw_h[off16[i] : off16[i] + 2 * k].view(np.uint16)
-        ref = ref_bits(x16, np.full(k, o_all[i], np.float32), np.full(k, s_all[i], np.float32), signed, dtype)
+        x16 = raw_h[off16[i] : off16[i] + 2 * k].view(np.int16 if signed else np.uint16)
+        ref = typed_bits(x16, o_all[i], s_all[i], dt)
         got = t_h[toff[i] : toff[i] + k * E].view(ref.dtype)
-        nan = is_nan_bits(ref, dtype)
+        nan = is_nan_bits(ref, dt)
         assert np.array_equal(got[~nan], ref[~nan]), (i, int(np.argmax(got != ref)))
-        assert is_nan_bits(got[nan], dtype).all(), i
+        assert is_nan_bits(got[nan], dt).all(), i
     assert (t_h[~written] == CANARY).all(), "a byte outside every slot was written"
     return rt
 
@@ -184,7 +105,7 @@ def test_bit_exact_grid(dtype, zz, version, level, sized):
     else:    # uint16 samples over the whole range (zig-zag off)
         reads = [rng.integers(0, 1 << 16, n).astype(np.uint16) for n in LENS]
     opts = c.options(zz, 2, level, version)
-    src, off, size = compress_reads(c, reads, opts, sized)
+    src, off, size = compress(c, reads, opts, sized)
     caps = [a.nbytes + (2 * int(rng.integers(0, 40)) if sized else 0) for a in reads]
     o, s = calibration(rng, len(reads))
     decode_both(c, src, off, size, caps, opts, sized, dtype, offset=o, scale=s, signed=zz)
@@ -195,7 +116,7 @@ def test_nan_constants_give_nan():
     c = codec()
     reads = [O.synth_signal(4, i, 5000) for i in range(3)]
     opts = c.options(True, 2, 1, 1)
-    src, off, size = compress_reads(c, reads, opts)
+    src, off, size = compress(c, reads, opts)
     o = np.array([0.0, np.nan, 1.0], np.float32)
     s = np.array([np.nan, 1.0, 2.0], np.float32)
     for dtype in DTYPES:
@@ -273,7 +194,7 @@ def test_frames_libzstd_wrote_are_walked():
     lens = _ragged(rng, n, 1000, 3000)
     reads = [O.synth_signal(15, i, x) for i, x in enumerate(lens)]
     frames = [O.compress(a, O.options(True, 2, 1, 0)) for a in reads]
-    src, off, size = arena(frames)
+    src, off, size = arena(c, frames, 64)
     opts = c.options(True, 2, 1, 0)
     o, s = calibration(rng, n)
     paths = []
@@ -288,14 +209,14 @@ def test_fast5_chunks():
     idx = json.load(open(os.path.join(GOLDEN, "fast5_chunks.json")))
     blob = np.fromfile(os.path.join(GOLDEN, "fast5_chunks.bin"), np.uint8)
     chunks = [blob[e["chunk_offset"] : e["chunk_offset"] + e["chunk_size"]] for e in idx]
-    src, off, size = arena(chunks, 16)
+    src, off, size = arena(c, chunks, 16)
     opts = c.options(True, 2, 1, 0)
     rng = np.random.default_rng(51)
     o, s = calibration(rng, len(idx), overflow=False)
     caps = [2 * e["samples"] for e in idx]
     for dtype in DTYPES:
         rt = decode_both(c, src, off, size, caps, opts, True, dtype, offset=o, scale=s)
-        assert [int(r) for r in rt] == [e["samples"] * ELEM[dtype] for e in idx]
+        assert [int(r) for r in rt] == [e["samples"] * ELEM[key(dtype)] for e in idx]
     # (and the int16 samples those were held to are the golden ones)
     dev = c.device
     roff, rtot = batch.layout(caps, 64)
@@ -334,7 +255,7 @@ def test_damaged_frames_give_the_int16_verdicts(dtype):
         opts = c.options(True, 2, 1, 1)
         c.set_checksum(checksum)
         try:
-            src, off, size = compress_reads(c, reads, opts, sized)
+            src, off, size = compress(c, reads, opts, sized)
         finally:
             c.set_checksum(False)
         sz = u32(size)
@@ -370,7 +291,7 @@ def test_fuzz_corpus_verdicts():
         for cap in (0, 2, 64, 2 * f.nbytes, 8 * f.nbytes):
             bufs.append(f)
             caps.append(cap)
-    src, off, size = arena(bufs)
+    src, off, size = arena(c, bufs, 64)
     for zz, level, version in ((True, 1, 0), (False, 1, 1), (True, 0, 1)):
         opts = c.options(zz, 2, level, version)
         for sized in (False, True):
@@ -383,11 +304,11 @@ def test_slot_alignment(dtype):
     """Offsets or capacities that are not multiples of E: VBZ_DESTINATION_SIZE_ERROR, the slot untouched; E-aligned slots off the 16-byte
     grid (every skew of E bytes) decode on the scalar store path."""
     c = codec()
-    E = ELEM[dtype]
+    E = ELEM[key(dtype)]
     lens = [3, 8, 2047, 4096, 70001, 100000]
     reads = [O.synth_signal(18, i, x) for i, x in enumerate(lens)]
     opts = c.options(True, 2, 1, 1)
-    src, off, size = compress_reads(c, reads, opts)
+    src, off, size = compress(c, reads, opts)
     caps16 = [a.nbytes for a in reads]
     rng = np.random.default_rng(81)
     o, s = calibration(rng, len(reads), overflow=False)
@@ -411,7 +332,7 @@ def test_host_refusals():
     L = c.L
     reads = [O.synth_signal(19, 0, 1000)]
     opts = c.options(True, 2, 1, 1)
-    src, off, size = compress_reads(c, reads, opts)
+    src, off, size = compress(c, reads, opts)
     dst = torch.zeros(4096, dtype=torch.uint8, device=dev)
     doff = torch.zeros(1, dtype=torch.int64, device=dev)
     dcap = i32([4000]).to(dev)
@@ -458,7 +379,7 @@ def test_packed_round_trip(dtype):
     lens = [0, 1, 17] + _ragged(rng, 200, 100, 60000) + [300_000]
     reads = [O.synth_signal(20, i, x) for i, x in enumerate(lens)]
     opts = c.options(True, 2, 1, 1)
-    comp, coff, res = compress_reads(c, reads, opts, sized=True)
+    comp, coff, res = compress(c, reads, opts, sized=True)
     caps = [c.L.vbz_max_compressed_size(int(a.nbytes), ctypes.byref(opts)) for a in reads]
     packed, poff, psize = c.pack(comp, coff, i32(caps).to(c.device), res, align=16)
     o, s = calibration(rng, len(reads), overflow=False)
@@ -466,11 +387,11 @@ def test_packed_round_trip(dtype):
                                                                scale=torch.from_numpy(s).to(c.device))
     torch.cuda.synchronize()
     assert out.dtype == dtype
-    E = ELEM[dtype]
+    E = ELEM[key(dtype)]
     oo, ss, rr = out_off.cpu().tolist(), samples.cpu().tolist(), u32(result)
     h = out.view(torch.int16 if E == 2 else torch.int32).cpu().numpy()
     for i, a in enumerate(reads):
         assert ss[i] == a.size and int(rr[i]) == a.size * E, (i, ss[i], int(rr[i]))
         assert (oo[i] * E) % 16 == 0
-        ref = ref_bits(a.view(np.uint16), np.full(a.size, o[i], np.float32), np.full(a.size, s[i], np.float32), True, dtype)
+        ref = typed_bits(a, o[i], s[i], key(dtype))
         assert np.array_equal(h[oo[i] : oo[i] + a.size].view(ref.dtype), ref), i

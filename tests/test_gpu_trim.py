@@ -14,9 +14,8 @@ import oracle_lib as O
 import pod5_ref as P
 import pod5_reads_ref as PR
 import ranges_ref as G
-import test_gpu_pod5_reads as TP
-import test_gpu_ranges as TR
 import trim_ref as T
+from typed_support import NORMS, Call, Frames, arena, codec, full, i32, ranges_struct, trim_struct, u32, unranged_results
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -25,21 +24,7 @@ E_ZSTD, E_INPUT, E_STREAM = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFB
 TO_END = 0xFFFFFFFF
 GUARD = 5
 GUARD_WORD = 0x5A5A5A5A
-NORMS = TR.NORMS
 SEG = 16_384
-
-codec = TP.codec
-i32 = TP.i32
-u32 = TP.u32
-Frames = TR.Frames
-
-
-def trim_struct(p, reserved=0):
-    """the C struct of trim_ref's parameter tuple"""
-    t = _lib.GpuTrim()
-    t.window, t.min_elements, t.min_trim, t.max_samples, t.threshold_factor, t.max_fraction, t.flags = p
-    t.reserved = reserved
-    return t
 
 
 def guarded(c, n):
@@ -78,7 +63,7 @@ class TrimRun:
         c = fr.c
         self.fr, self.p, self.norm, self.signed, self.stats = fr, p, NORMS[norm] if isinstance(norm, str) else norm, signed, stats
         n, dev = fr.n, c.device
-        self.sb, self.se = TR.full(sb, n), TR.full(se, n)
+        self.sb, self.se = full(sb, n), full(se, n)
         self.begin, ptr = guarded(c, n)
         self.result = torch.full((max(n, 1),), -8, dtype=torch.int32, device=dev)
         self.ss = torch.full((max(n, 1), 2), -777.0, dtype=torch.float32, device=dev) if with_ss else None
@@ -87,7 +72,7 @@ class TrimRun:
         b.dst, b.dst_bytes = None, fr.dst_bytes
         m = self.norm[1].c_struct()
         t = trim_struct(p)
-        g, keep = TR.ranges_struct(c, sb, se, stats)
+        g, keep = ranges_struct(c, sb, se, stats)
         ranged = sb is not None or se is not None
         torch.cuda.synchronize()
         self.rc = c.L.vbz_gpu_signal_trim_batch(c.ctx, ctypes.byref(b), ctypes.byref(fr.opts), int(fr.sized), int(signed), ctypes.byref(m),
@@ -303,7 +288,7 @@ def test_routed_long_read_among_small_ones():
 def test_libzstd_frames():
     c = codec()
     reads = T.gpu_reads(seed=51, sizes=[0, 1, 9, 2049, 4101, 50_000])
-    comp = TP.arena(c, [O.compress(x, O.options(True, 2, 1, 1), sized=True) for x in reads], 64)
+    comp = arena(c, [O.compress(x, O.options(True, 2, 1, 1), sized=True) for x in reads], 64)
     fr = Frames(c, reads, c.options(True, 2, 1, 1), sized=True, comp=comp)
     TrimRun(fr, T.DEFAULT, "med_mad").check()
     TrimRun(fr, (64, 3, 10, 8000, 2.4, 0.3, 1), "quantile").check()
@@ -325,7 +310,7 @@ def test_checksummed_frames():
 def test_pod5_rows_as_reads_of_their_own():
     c = codec()
     rows = T.gpu_reads(seed=61)
-    fr = Frames(c, rows, batch.pod5_options(), comp=TP.arena(c, [P.compress_row(x) for x in rows], 64))
+    fr = Frames(c, rows, batch.pod5_options(), comp=arena(c, [P.compress_row(x) for x in rows], 64))
     for norm in ("med_mad", "quantile"):
         run = TrimRun(fr, T.DEFAULT, norm)
         run.check()
@@ -352,15 +337,15 @@ def pod5_case(seed=71, shapes=POD5_SHAPES, kinds=T.KINDS):
     return rows, first, [P.compress_row(x) for x in rows]
 
 
-class TrimCall(TP.Call):
-    """TP.Call with a guarded begin table: the raw vbz_gpu_pod5_signal_trim_batch call"""
+class TrimCall(Call):
+    """Call with a guarded begin table: the raw vbz_gpu_pod5_signal_trim_batch call"""
 
     def __init__(self, c, frames, rows, first, norm, table=None):
         super().__init__(c, frames, [len(x) for x in rows], PR.bounds(first, len(rows)) if table is None else table, norm=norm)
         self.begin, self.begin_ptr = guarded(c, self.R)
 
     def trim_call(self, p, sb=None, se=None, stats=0, signed=True, with_ss=True):
-        g, self.gkeep = TR.ranges_struct(self.c, sb, se, stats)
+        g, self.gkeep = ranges_struct(self.c, sb, se, stats)
         t = trim_struct(p)
         rc = self.c.L.vbz_gpu_pod5_signal_trim_batch(self.c.ctx, ctypes.byref(self.b), ctypes.byref(self.opts), int(signed), ctypes.byref(self.reads),
                                                      ctypes.byref(self.m), ctypes.byref(g) if (sb is not None or se is not None) else None,
@@ -372,7 +357,7 @@ class TrimCall(TP.Call):
 def check_pod5(call, rows, first, norm, p, sb=None, se=None, stats=0, signed=True, failed=(), with_ss=True):
     got = table_and_guards(call.begin, call.R)
     ss = call.ss.cpu().numpy()
-    sbs, ses = TR.full(sb, call.R), TR.full(se, call.R)
+    sbs, ses = full(sb, call.R), full(se, call.R)
     for k, x in enumerate(PR.read_signals(rows, first)):
         if k in failed:
             assert got[k] == 0, ("begin of a failed read", k, got[k])
@@ -391,7 +376,7 @@ def test_pod5_reads(segmented):
     Ts = [len(x) for x in PR.read_signals(rows, first)]
     moved = 0
     for name, (ref, nm) in NORMS.items():
-        want = TR.unranged_results(c, frames, rows, first, None, nm)
+        want = unranged_results(c, frames, rows, first, None, nm)
         for p in (T.DEFAULT, (40, 3, 10, 8000, 2.4, 0.3, 1), (7, 0, 3, 5000, 2.4, 1.0, 0), (1, 0, 140, 4236, 2.4, 1.0, 0), (64, 3, 10, 100_000, 2.4, 1.0, 0)):
             call = TrimCall(c, frames, rows, first, nm)
             assert call.trim_call(p) == 0, c.L.vbz_gpu_last_error(c.ctx)
@@ -455,7 +440,7 @@ def test_pod5_row_failing_inside_a_read():
     frames = list(good)
     frames[3] = good[3][: len(good[3]) // 2]                       # a damaged frame in the middle row of read 1
     frames[7] = O.zstd_compress(P.svb16_encode(rows[7])[:-1], 1)   # a stream with a byte cut off in the middle row of read 3
-    want = TR.unranged_results(c, frames, rows, first, None, batch.MED_MAD)
+    want = unranged_results(c, frames, rows, first, None, batch.MED_MAD)
     assert want[0][3] == E_ZSTD and want[0][7] == E_STREAM
     call = TrimCall(c, frames, rows, first, batch.MED_MAD)
     assert call.trim_call(T.DEFAULT) == 0
@@ -520,7 +505,7 @@ def test_begin_feeds_the_range_calls_without_a_host_copy():
 def test_pod5_begin_feeds_the_pod5_range_call():
     c = codec()
     rows, first, frames = pod5_case()
-    src, off, size = TP.arena(c, frames)
+    src, off, size = arena(c, frames, 16)
     rs = i32([len(x) for x in rows]).to(c.device)
     res = torch.full((len(rows),), -8, dtype=torch.int32, device=c.device)
     begin, ss, rr = c.pod5_signal_trim(src, off, size, rs, first, res, batch.MED_MAD, shift_scale=True)
@@ -583,7 +568,7 @@ def test_host_refusals_launch_nothing():
     bad_m.method = 9
     assert calls(ok, mp=bad_m) == [-2, -2]
     for kw in ({"reserved": 1}, {"stats": 2}):
-        g, keep = TR.ranges_struct(c, [0] * 4, None, **kw)
+        g, keep = ranges_struct(c, [0] * 4, None, **kw)
         assert calls(ok, g=g) == [-2, -2], kw
     assert L.vbz_gpu_signal_trim_batch(None, ctypes.byref(b), ctypes.byref(fr.opts), 0, 1, ctypes.byref(m), None, ctypes.byref(ok), None, ptr) == -1
     assert L.vbz_gpu_signal_trim_batch(c.ctx, None, ctypes.byref(fr.opts), 0, 1, ctypes.byref(m), None, ctypes.byref(ok), None, ptr) == -1

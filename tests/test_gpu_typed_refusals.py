@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from signal_ref import table_of
+from typed_support import Frames, codec, i32, sine_signal
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -56,57 +58,26 @@ M_TRIM = ("trim outside its rules (window %u, min_elements 3, min_trim 10, max_s
           "reserved %u; at most 4096 windows)")
 
 
-def i32(vals):
-    return torch.tensor(np.asarray(vals, np.uint64).astype(np.uint32).view(np.int32), dtype=torch.int32)
-
-
-_codec = []
-
-
-def codec():
-    if not _codec:
-        _codec.append(batch.GpuCodec(0))
-    return _codec[0]
-
-
-class Frames:
-    """signal-like int16 reads of the given sample counts, compressed once by GpuCodec.compress: the source arena, the int16 layout
-    that describes the reads, and the chunk_first of `groups` (the reads' first entries; None: every entry is a read)"""
-
-    def __init__(self, c, lens, opts, sized, caps, groups=None):
-        dev, rng = c.device, np.random.default_rng(7)
-        self.n, self.lens = len(lens), lens
-        roff, self.total = batch.layout([2 * t for t in lens], 16)
-        raw = np.zeros(self.total, np.uint8)
-        for t, o in zip(lens, roff.tolist()):
-            x = np.clip(330 + rng.normal(0, 40, t) + 60 * np.sin(np.arange(t) / 50.0), -500, 900).astype(np.int16)
-            raw[o : o + 2 * t] = x.view(np.uint8)
-        coff, ctotal = batch.layout(caps, 16)
-        self.src = torch.zeros(ctotal, dtype=torch.uint8, device=dev)
-        self.off, self.size = coff.to(dev), torch.zeros(self.n, dtype=torch.int32, device=dev)
-        self.doff, self.dcap = roff.to(dev), i32([2 * t for t in lens]).to(dev)
-        c.compress(torch.from_numpy(raw).to(dev), self.doff, self.dcap, self.src, self.off, i32(caps).to(dev), self.size, opts, sized=sized)
-        c.synchronize()
-        assert not any(_lib.is_error(v) for v in batch._u32(self.size)), batch._u32(self.size)
-        bounds = list(groups if groups is not None else range(self.n)) + [self.n]
-        T = [sum(lens[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
-        counts = [0 if t == 0 else 1 if t <= CHUNK_LEN else (t - CHUNK_LEN + STEP - 1) // STEP + 1 for t in T]   # (include/vbz_gpu.h: vbz_gpu_chunking)
-        self.n_out, self.rows = len(T), sum(counts)
-        self.chunk_first = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
-        self.first_row = i32(bounds).to(dev)
-
-
 _frames = {}
 
 
 def frames(c, kind):
+    """signal-like int16 reads compressed once by GpuCodec.compress (typed_support.Frames: the source arena and the int16 layout that
+    describes the reads), with the chunk_first of the reads (POD5: of FIRST_ROW's groups of rows)"""
     if kind not in _frames:
+        rng = np.random.default_rng(7)
         if kind == "pod5":
-            _frames[kind] = Frames(c, ROWS, batch.pod5_options(), False, [batch.pod5_max_compressed_size(t) for t in ROWS], FIRST_ROW)
+            lens, opts, sized, caps, bounds = ROWS, batch.pod5_options(), False, [batch.pod5_max_compressed_size(t) for t in ROWS], FIRST_ROW + [len(ROWS)]
         else:
-            opts = c.options(True, 2, 1, 1)
+            lens, opts, sized, bounds = READS, c.options(True, 2, 1, 1), kind == "sized", list(range(len(READS) + 1))
             caps = [int(c.L.vbz_max_compressed_size(2 * t, ctypes.byref(opts))) + 16 for t in READS]
-            _frames[kind] = Frames(c, READS, opts, kind == "sized", caps)
+        fr = Frames(c, [sine_signal(rng, t) for t in lens], opts, sized, align=16, caps=caps)
+        T = [sum(lens[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+        table = table_of(T, CHUNK_LEN, STEP, "pad", 0)
+        fr.n_out, fr.rows = len(T), int(table[-1])
+        fr.chunk_first = torch.from_numpy(table).to(c.device)
+        fr.first_row = i32(bounds).to(c.device)
+        _frames[kind] = fr
     return _frames[kind]
 
 
@@ -123,7 +94,7 @@ def make(c, name, sized=False):
         "ss": (torch.full((R, 2), FLOAT, dtype=torch.float32, device=dev), FLOAT),
         "begin": (torch.full((R,), WORD, dtype=torch.int32, device=dev), WORD),
         "chunks": (torch.full(((fr.rows + GUARD_ROWS) * CHUNK_LEN * 2,), BYTE, dtype=torch.uint8, device=dev), BYTE),
-        "dst": (torch.full((fr.total,), BYTE, dtype=torch.uint8, device=dev), BYTE),   # float16: the int16 layout is the typed arena's
+        "dst": (torch.full((fr.dst_bytes,), BYTE, dtype=torch.uint8, device=dev), BYTE),   # float16: the int16 layout is the typed arena's
     }
     a.b = c._batch(fr.src, fr.off, fr.size, a.out["dst"][0], fr.doff, fr.dcap, a.out["result"][0])
     a.o = batch.pod5_options() if pod5 else c.options(True, 2, 1, 1)
@@ -271,7 +242,7 @@ def test_entry_accepts_and_refuses(name):
         a = make(c, name, sized)
         rc, msg = call(c, name, a)
         out = outputs(c, a)
-        want = [2 * t for t in a.fr.lens]
+        want = [2 * t for t in a.fr.T]
         if rc != 0 or batch._u32(out["result"]) != want:
             bad.append("good call (sized %d): rc %d %r, result %r, want %r" % (sized, rc, msg, batch._u32(out["result"]), want))
         if "reads" in params and any(_lib.is_error(v) or v == WORD for v in batch._u32(out["read_result"])):
