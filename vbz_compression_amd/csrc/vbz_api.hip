@@ -2180,6 +2180,16 @@ VBZ_EXPORT int vbz_gpu_x_svb_handover(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, v
     HIPCHK(c, hipMemcpyAsync(plans_out, c->encplan.p, (size_t)n * sizeof(EncPlan), hipMemcpyDeviceToDevice, s), "plan copy");
     return 0;
 }
+// Measuring aid (experiments build only): which way fast_runs_kernel's zero-run blocks went since the last reset -- chunks of 64
+// sequences, those built in LDS, sequences sections with checkpoints, those staged in LDS (profiles/occ_experiments.md).
+VBZ_EXPORT int vbz_gpu_x_runs_counts(vbz_gpu_ctx* c, unsigned long long* out4, int reset)
+{
+    if (!c || !out4) return -1;
+    DeviceGuard dg(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream), "runs counts sync");
+    HIPCHK(c, zstd_fast_runs_counts(out4, reset != 0), "runs counts");
+    return 0;
+}
 #endif
 
 void vbz_gpu_profile_enable(vbz_gpu_ctx* c, int enable)

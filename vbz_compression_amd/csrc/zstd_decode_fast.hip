@@ -998,8 +998,24 @@ __global__ __launch_bounds__(WAVE, 3) void ref_pieces_kernel(ReadBatch b, const 
 }
 
 // ---- one wavefront per frame: the zero-run block ----------------------------------------------------------------------------------------
-constexpr uint32_t RUNS_LDS = 8704;
-__global__ __launch_bounds__(WAVE) void fast_runs_kernel(ReadBatch b, const FastFrame* frames, const SeqDTables* dtabs, uint32_t* redo)
+// 6 400 B of LDS and 6 waves per SIMD (76 registers with zstd_runs.h's helpers inlined; no scratch): 24 wavefronts per CU -- 8 704 B and
+// 116 registers behind the helpers' calls were 16.  The area holds a chunk of 64 sequences while 3 x its literals (rounded up to 16) + its
+// output + 16 <= RUNS_LDS - 8 (place_zero_runs): every chunk of the benchmark's reads, as 8 704 B did with a dword of shift per literal;
+// at 5 120 B ten chunks in 90 350 take the direct path (tools/zero_run_paths.py, profiles/occ_experiments.md).
+#ifndef VBZ_RUNS_LDS
+#define VBZ_RUNS_LDS 6400
+#endif
+#ifndef VBZ_RUNS_WAVES
+#define VBZ_RUNS_WAVES 6
+#endif
+constexpr uint32_t RUNS_LDS = VBZ_RUNS_LDS;
+#ifdef VBZ_EXPERIMENTS   // which way the zero-run blocks of a call went (zstd_runs.h `count`; read by zstd_fast_runs_counts)
+__device__ unsigned long long runs_counts[4];
+#define RUNS_COUNTS runs_counts
+#else
+#define RUNS_COUNTS nullptr
+#endif
+__global__ __launch_bounds__(WAVE, VBZ_RUNS_WAVES) void fast_runs_kernel(ReadBatch b, const FastFrame* frames, const SeqDTables* dtabs, uint32_t* redo)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds[RUNS_LDS / 4];
     const int lane = threadIdx.x;
@@ -1015,15 +1031,15 @@ __global__ __launch_bounds__(WAVE) void fast_runs_kernel(ReadBatch b, const Fast
     const uint32_t regen = F->b0_regen, base_out = F->base_out;
     uint32_t total = 0, ok = 3;
     if (F->cp_count)
-        ok = zero_run_chain_segments(src + F->seq_off, F->seq_len, pairs, nseq, llt, mlt, regen, src + F->cp_off, F->cp_count, F->cp_spacing, lane, &total, lds,
-                                     RUNS_LDS);
-    if (ok == 3) ok = zero_run_chain(src + F->seq_off, F->seq_len, pairs, nseq, llt, mlt, 6, 6, regen, lane, &total);
+        ok = zero_run_chain_segments_inl(src + F->seq_off, F->seq_len, pairs, nseq, llt, mlt, regen, src + F->cp_off, F->cp_count, F->cp_spacing, lane, &total, lds,
+                                         RUNS_LDS, RUNS_COUNTS);
+    if (ok == 3) ok = zero_run_chain_inl(src + F->seq_off, F->seq_len, pairs, nseq, llt, mlt, 6, 6, regen, lane, &total);
     if (ok != 1 || total != base_out) {  // corrupt, not a pure zero-run block, or not what the other blocks leave of the content size
         if (lane == 0) redo[r] = 1;
         return;
     }
     __syncthreads();  // the pairs are in memory
-    const uint32_t end = place_zero_runs(dst, pairs, nseq, dst + F->ws_lit, 2u, regen, 0u, F->fcs, F->block_max, reinterpret_cast<uint8_t*>(lds), RUNS_LDS - 8u, lane);
+    const uint32_t end = place_zero_runs_inl(dst, pairs, nseq, dst + F->ws_lit, 2u, regen, 0u, F->fcs, F->block_max, reinterpret_cast<uint8_t*>(lds), RUNS_LDS - 8u, lane, RUNS_COUNTS);
     if (lane == 0) {
         if (end != base_out) redo[r] = 1;
         else b.result[r] = F->fcs;
@@ -1031,6 +1047,20 @@ __global__ __launch_bounds__(WAVE) void fast_runs_kernel(ReadBatch b, const Fast
 }
 
 }  // namespace
+
+#ifdef VBZ_EXPERIMENTS
+// { chunks of 64 sequences placed, of them built in LDS, sequences sections with checkpoints, of them staged in LDS } by fast_runs_kernel
+// since the last reset; the device must be idle.
+hipError_t zstd_fast_runs_counts(unsigned long long out[4], bool reset)
+{
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(runs_counts), sizeof(runs_counts));
+    if (e == hipSuccess && reset) {
+        const unsigned long long zero[4] = { 0, 0, 0, 0 };
+        e = hipMemcpyToSymbol(HIP_SYMBOL(runs_counts), zero, sizeof(zero));
+    }
+    return e;
+}
+#endif
 
 // VBZ_HIP_REF_LITERALS=0: no literals ahead of the decoder (measurements, tests of the other path)
 static uint32_t ref_units_max()

@@ -1542,8 +1542,21 @@ __device__ __forceinline__ void span_table_role(EncLds& L, SpanRegion* R, int la
     }
 }
 
+// Waves per SIMD zstd_pack_kernel<false> is compiled for.  The kernel needs 43 registers at any of these bounds (it needed 73 while the
+// copy of the tree description in pack_region was a loop of unknown length: unrolled by eight, sixteen registers of addresses), so the
+// bound decides how many scalar registers it may use and with them how many wavefronts a SIMD holds.  Encoder (planning + packing
+// launch) per 65 536 reads, tools/ab_libs.py in both orders against 6.01 - 6.23 ms of the code before (profiles/occ_experiments.md):
+//   6: 106 SGPRs                    6.01 - 6.07 ms
+//   7:  94 SGPRs                    5.77 ms
+//   8:  78 SGPRs, 14 kept in lanes  4.95 - 4.99 ms   (no scratch at any of them)
 #ifndef VBZ_ENC_PACK_WAVES
-#define VBZ_ENC_PACK_WAVES 5   // waves per SIMD the packing launch is compiled for (6: 80 registers with 20 spilled, slower)
+#define VBZ_ENC_PACK_WAVES 8
+#endif
+#ifndef VBZ_ENC_PACK_WAVES_TIMED
+#define VBZ_ENC_PACK_WAVES_TIMED 5   // ... and its timed instantiation (a measuring tool: the phase counters take registers)
+#endif
+#ifndef VBZ_ENC_SPAN_PACK_WAVES
+#define VBZ_ENC_SPAN_PACK_WAVES 5   // zstd_span_pack_kernel: a bound of its own (47 registers through the shared pack_region; the large-read timings did not move)
 #endif
 #ifndef VBZ_PACK_PREFETCH
 #define VBZ_PACK_PREFETCH 1    // the next step's bytes are requested before the current step is packed
@@ -2398,8 +2411,8 @@ __global__ __launch_bounds__(WAVE, VBZ_TABLE_WAVES) void zstd_plan_kernel(ReadBa
 // What zstd_encode_kernel does behind its table constructions, for the reads whose plans the launches above have completed: frame
 // header; per region the tree description, the streams packed one after the other in frame order (the same loop: 16 symbols per lane
 // and step, a wave prefix sum of the bit counts, bits OR-ed into an LDS buffer, 16-byte quads out), the block headers; the sequences
-// section of the first block moved into place; the checkpoint trailer.  Byte for byte the fused kernel's frame.  80 registers and
-// 5 KB of LDS instead of 128 (+ spills) and 10 KB: 24 waves per CU instead of 16 (profiles/r04_experiments.md).
+// section of the first block moved into place; the checkpoint trailer.  Byte for byte the fused kernel's frame.  43 registers and
+// 5 KB of LDS: 32 waves per CU (round 4: 80 registers, 24 per CU, profiles/r04_experiments.md; now profiles/occ_experiments.md).
 #ifndef VBZ_PACK_TABLE_COPIES
 #define VBZ_PACK_TABLE_COPIES 1
 #endif
@@ -2549,7 +2562,12 @@ __device__ __forceinline__ bool pack_region(PackLds& L, const uint8_t* rin, uint
             const uint32_t tsz = curblk == 0 ? treeSize : 0u;
             const uint32_t hl = 3u + blk_lh(curblk) + tsz + (blk_bs(curblk) < 256u ? 0u : 6u);
             if ((uint64_t)ocur + hl > limit) REDO();
-            for (uint32_t i = lane; i < tsz; i += WAVE) out[ocur + 3u + blk_lh(curblk) + i] = reinterpret_cast<const uint8_t*>(L.tree)[i];
+            static_assert(sizeof(L.tree) <= 3 * WAVE, "a tree description is three bytes per lane at most");
+#pragma unroll
+            for (uint32_t i0 = 0; i0 < 3 * WAVE; i0 += WAVE) {   // (three guarded stores.  As a loop of unknown length it was unrolled by eight: sixteen registers of addresses)
+                const uint32_t i = i0 + (uint32_t)lane;
+                if (i < tsz) out[ocur + 3u + blk_lh(curblk) + i] = reinterpret_cast<const uint8_t*>(L.tree)[i];
+            }
             spos = ocur + hl;
         }
         const uint32_t scnt = s_cnt(st);
@@ -2687,7 +2705,7 @@ __device__ __forceinline__ bool pack_region(PackLds& L, const uint8_t* rin, uint
 }
 
 template <bool TIMED>
-__global__ __launch_bounds__(WAVE, VBZ_ENC_PACK_WAVES) void zstd_pack_kernel(ReadBatch b, const uint32_t* orig_size, uint32_t key_elem, const uint32_t* key_bytes,
+__global__ __launch_bounds__(WAVE, TIMED ? VBZ_ENC_PACK_WAVES_TIMED : VBZ_ENC_PACK_WAVES) void zstd_pack_kernel(ReadBatch b, const uint32_t* orig_size, uint32_t key_elem, const uint32_t* key_bytes,
                                                                              uint32_t hdr, uint32_t trailers, const EncPlan* plans, uint32_t* redo,
                                                                              unsigned long long* dbg_)
 {
@@ -2736,7 +2754,12 @@ __global__ __launch_bounds__(WAVE, VBZ_ENC_PACK_WAVES) void zstd_pack_kernel(Rea
         const EncRegionPlan* P = &FP->reg[region];
         const uint32_t S = P->S, Sh = P->Sh;
         const uint32_t opos_region = opos;
-        if (!pack_region<TIMED>(L, in + r0, r0, out, opos, limit, P->ctable, P->tree, S, P->nblk, P->treeSize, P->seqmode != 0, r1 == N, seqBytes, seqOff, lane,
+        // (a lane number the compiler cannot follow from one region to the next: what pack_region derives from it -- addresses, masks --
+        // is otherwise computed once in front of this loop and held across both regions' packing loops: 49 registers and 34 scalar
+        // registers kept in lanes instead of 43 and 14)
+        int rlane = lane;
+        asm volatile("" : "+v"(rlane));
+        if (!pack_region<TIMED>(L, in + r0, r0, out, opos, limit, P->ctable, P->tree, S, P->nblk, P->treeSize, P->seqmode != 0, r1 == N, seqBytes, seqOff, rlane,
                                 tph, tlast))
             REDO();
         if (Sh != S && opos - opos_region > S + (S >> 6) + 256u) REDO();   // a sample that misled: coded again from the exact histogram
@@ -2904,7 +2927,7 @@ __global__ __launch_bounds__(1024) void zstd_span_plan_kernel(uint32_t n, const 
 // launch's loop) into the span's temporary slot -- which holds the worst case, 11 bits per byte, so that the span with the tree
 // description can never fail; any other span that comes out larger than raw blocks is stored as raw blocks, like a region whose
 // count said that a table does not pay (mode 0); a region of one byte value (mode 1) becomes RLE blocks.
-__global__ __launch_bounds__(WAVE, VBZ_ENC_PACK_WAVES) void zstd_span_pack_kernel(ReadBatch b, const EncSpan* spans, const uint32_t* span_count, uint8_t* span_tmp,
+__global__ __launch_bounds__(WAVE, VBZ_ENC_SPAN_PACK_WAVES) void zstd_span_pack_kernel(ReadBatch b, const EncSpan* spans, const uint32_t* span_count, uint8_t* span_tmp,
                                                                                   uint32_t* span_size, uint32_t* span_trail, const SpanRegion* regions)
 {
     __shared__ __attribute__((aligned(16))) PackLds L;

@@ -36,10 +36,11 @@ __device__ __forceinline__ uint32_t lane_get(uint32_t v, uint32_t l) { return (u
 // match copies the byte in front of it.  Positions come from wave prefix sums, so all sequences of a chunk of 64
 // are placed at once: a lane copies its literals and fills its run; runs of 64+ bytes are filled by the wave.
 // Returns the output position behind the block, or 0xFFFFFFFF if the pairs do not fit the block.
-__device__ __noinline__ uint32_t place_zero_runs(uint8_t* dst, const uint2* pairs, uint32_t nseq, const uint8_t* litp, uint32_t ltype,
-                                    uint32_t regen, uint32_t opos, uint32_t fcs, uint32_t block_max, uint8_t* lds_lit,
-                                    uint32_t lds_cap, int lane)
+__device__ __forceinline__ uint32_t place_zero_runs_inl(uint8_t* dst, const uint2* pairs, uint32_t nseq, const uint8_t* litp, uint32_t ltype,
+                                                        uint32_t regen, uint32_t opos, uint32_t fcs, uint32_t block_max, uint8_t* lds_lit,
+                                                        uint32_t lds_cap, int lane, unsigned long long* count = nullptr)
 {
+    // (count, experiments build: [0] chunks of 64 sequences placed, [1] those of them built in LDS)
     const uint8_t rle_byte = ltype == 1 ? litp[0] : 0;
     uint32_t lposw = 0, oposw = opos;
     uint2 pnext = (uint32_t)lane < nseq ? pairs[lane] : make_uint2(0u, 0u);  // one chunk of pairs is always in flight
@@ -56,17 +57,20 @@ __device__ __noinline__ uint32_t place_zero_runs(uint8_t* dst, const uint2* pair
         // zero fill, every lane drops its literals in place, runs of a non-zero byte are written out -- and copy it
         // to memory with 16-byte stores.  Otherwise the lanes write to memory directly.
         const uint32_t lit_room = (tl + 15u) & ~15u;
-        if (ltype != 1 && 5u * lit_room + tt + 16u <= lds_cap) {
-            // LDS: the chunk's literals, one dword per literal (to become its shift), the chunk's output
-            uint32_t* lds_sh = reinterpret_cast<uint32_t*>(lds_lit + lit_room);
-            uint8_t* lds_out = lds_lit + 5u * lit_room;
+        if (count && lane == 0) atomicAdd(&count[0], 1ull);
+        if (ltype != 1 && 3u * lit_room + tt + 16u <= lds_cap && lds_cap <= 0xFFFFu) {
+            // LDS: the chunk's literals, 16 bits per literal (to become its shift: a sum of match lengths of the chunk, so at most
+            // tt <= lds_cap < 2^16), the chunk's output
+            uint16_t* lds_sh = reinterpret_cast<uint16_t*>(lds_lit + lit_room);
+            uint8_t* lds_out = lds_lit + 3u * lit_room;
+            if (count && lane == 0) atomicAdd(&count[1], 1ull);
             wave_lds_sync();  // one wave: LDS hand-over only, global accesses stay in flight
             for (uint32_t j = lane; 4 * j < tl; j += WAVE) {
                 uint32_t v;
                 __builtin_memcpy(&v, litp + lposw + 4 * j, 4);  // may read 3 bytes past the literals (staging slack)
                 reinterpret_cast<uint32_t*>(lds_lit)[j] = v;
             }
-            for (uint32_t j = 4u * (uint32_t)lane; j < lit_room; j += 4u * WAVE) *reinterpret_cast<uint4*>(lds_sh + j) = make_uint4(0u, 0u, 0u, 0u);
+            for (uint32_t j = 8u * (uint32_t)lane; j < lit_room; j += 8u * WAVE) *reinterpret_cast<uint4*>(lds_sh + j) = make_uint4(0u, 0u, 0u, 0u);
             for (uint32_t j = 16u * (uint32_t)lane; j < tt; j += 16u * WAVE) *reinterpret_cast<uint4*>(lds_out + j) = make_uint4(0u, 0u, 0u, 0u);
             wave_lds_sync();
             // a literal lands (sum of the match lengths in front of it) further down than it sits in the literal
@@ -74,15 +78,15 @@ __device__ __noinline__ uint32_t place_zero_runs(uint8_t* dst, const uint2* pair
             // over the literals -- every lane then moves the same number of literals, however they are spread
             const uint32_t lo = il - ll, oo = it - (ll + ml);
             const uint32_t mprev = wave_prev_lane_u32(ml);
-            if (ll != 0 && lane != 0) lds_sh[lo] = mprev;
+            if (ll != 0 && lane != 0) lds_sh[lo] = (uint16_t)mprev;
             wave_lds_sync();
             uint32_t carry = 0;
             for (uint32_t j0 = 0; j0 < tl; j0 += 8u * WAVE) {
                 const uint32_t j = j0 + 8u * (uint32_t)lane;
                 uint32_t sh[8], run = 0;
-                const uint4 a0 = j < lit_room ? *reinterpret_cast<const uint4*>(lds_sh + j) : make_uint4(0u, 0u, 0u, 0u);
-                const uint4 a1 = j + 4 < lit_room ? *reinterpret_cast<const uint4*>(lds_sh + j + 4) : make_uint4(0u, 0u, 0u, 0u);
-                const uint32_t dl[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+                // (lit_room is a multiple of 16: a lane's eight marks are one quad, inside the area or not at all)
+                const uint4 a = j < lit_room ? *reinterpret_cast<const uint4*>(lds_sh + j) : make_uint4(0u, 0u, 0u, 0u);
+                const uint32_t dl[8] = { a.x & 0xFFFFu, a.x >> 16, a.y & 0xFFFFu, a.y >> 16, a.z & 0xFFFFu, a.z >> 16, a.w & 0xFFFFu, a.w >> 16 };
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     run += dl[k];
@@ -171,6 +175,14 @@ __device__ __noinline__ uint32_t place_zero_runs(uint8_t* dst, const uint2* pair
     if (oposw - opos > BLOCK_MAX || oposw - opos > block_max) return 0xFFFFFFFFu;
     return oposw;
 }
+// (as a call: zstd_decode_kernel, whose own 220 registers are live across it.  fast_runs_kernel instantiates the _inl forms of this and of
+// the two walks below: a call's fixed register set and its 16 bytes of stack are what held that kernel to 16 wavefronts per CU)
+__device__ __noinline__ uint32_t place_zero_runs(uint8_t* dst, const uint2* pairs, uint32_t nseq, const uint8_t* litp, uint32_t ltype,
+                                                 uint32_t regen, uint32_t opos, uint32_t fcs, uint32_t block_max, uint8_t* lds_lit,
+                                                 uint32_t lds_cap, int lane)
+{
+    return place_zero_runs_inl(dst, pairs, nseq, litp, ltype, regen, opos, fcs, block_max, lds_lit, lds_cap, lane);
+}
 
 // Decoding tables of the predefined LL / ML distributions in the compact form the zero-run chain uses:
 // entry = { base value, next-state base | extra bits << 16 | state bits << 24 }, one entry per lane.
@@ -189,8 +201,8 @@ struct SeqDTables
 // latency on the chain except one window load per 2048 bits.
 // Returns 0 = corrupt, 1 = pairs written (*total_out = bytes the block regenerates), 2 = not such a block after
 // all (the caller decodes the frame again, in order).
-__device__ __noinline__ uint32_t zero_run_chain(const uint8_t* bs_, uint32_t bsn_, uint2* ws, uint32_t nseq_, uint2 llt, uint2 mlt,
-                                                uint32_t log_ll_, uint32_t log_ml_, uint32_t regen_, int lane, uint32_t* total_out)
+__device__ __forceinline__ uint32_t zero_run_chain_inl(const uint8_t* bs_, uint32_t bsn_, uint2* ws, uint32_t nseq_, uint2 llt, uint2 mlt,
+                                                       uint32_t log_ll_, uint32_t log_ml_, uint32_t regen_, int lane, uint32_t* total_out)
 {
     const uint32_t bsn = uni(bsn_), nseq = uni(nseq_), log_ll = uni(log_ll_), log_ml = uni(log_ml_), regen = uni(regen_);
     const uint8_t* bs = reinterpret_cast<const uint8_t*>(((uint64_t)uni((uint32_t)((uint64_t)bs_ >> 32)) << 32) |
@@ -268,19 +280,27 @@ __device__ __noinline__ uint32_t zero_run_chain(const uint8_t* bs_, uint32_t bsn
     *total_out = (uint32_t)(sum_all + (regen - sum_ll));
     return 1u;
 }
+__device__ __noinline__ uint32_t zero_run_chain(const uint8_t* bs, uint32_t bsn, uint2* ws, uint32_t nseq, uint2 llt, uint2 mlt,
+                                                uint32_t log_ll, uint32_t log_ml, uint32_t regen, int lane, uint32_t* total_out)
+{
+    return zero_run_chain_inl(bs, bsn, ws, nseq, llt, mlt, log_ll, log_ml, regen, lane, total_out);
+}
 
 // all lanes.  The same walk as zero_run_chain, split at the encoder's checkpoints (zstd_encode.hip, CP_MAGIC): lane
 // j decodes sequences [j * spacing, (j + 1) * spacing) from (unread bits, LL state, ML state) = checkpoint j - 1
 // (lane 0: from the top of the stream).  The bit stream is staged in LDS (`lds`, lds_bytes of it), table entries come from the lanes that hold them (ds_bpermute).  The result is accepted only if every
 // segment ends exactly where the next one started and the last one consumes the stream: then it is the serial
 // walk.  Returns 1 = pairs written, 2 = not a pure zero-run block, 3 = checkpoints unusable (walk serially).
-__device__ __noinline__ uint32_t zero_run_chain_segments(const uint8_t* bs, uint32_t bsn, uint2* ws, uint32_t nseq, uint2 llt, uint2 mlt,
-                                                         uint32_t regen, const uint8_t* cp, uint32_t ncp, uint32_t spacing, int lane,
-                                                         uint32_t* total_out, uint32_t* lds, uint32_t lds_bytes)
+__device__ __forceinline__ uint32_t zero_run_chain_segments_inl(const uint8_t* bs, uint32_t bsn, uint2* ws, uint32_t nseq, uint2 llt, uint2 mlt,
+                                                                uint32_t regen, const uint8_t* cp, uint32_t ncp, uint32_t spacing, int lane,
+                                                                uint32_t* total_out, uint32_t* lds, uint32_t lds_bytes,
+                                                                unsigned long long* count = nullptr)
 {
     const uint32_t CAP = lds_bytes - 16u;  // the bit stream is staged in `lds`
+    if (count && lane == 0) atomicAdd(&count[2], 1ull);   // (experiments build: [2] sequences sections with checkpoints, [3] those staged)
     if (bsn == 0 || bsn > CAP || ncp + 1 > (uint32_t)WAVE || spacing == 0) return 3u;
     if ((uint64_t)(ncp + 1) * spacing < nseq || (uint64_t)ncp * spacing >= nseq) return 3u;
+    if (count && lane == 0) atomicAdd(&count[3], 1ull);
     __syncthreads();
     for (uint32_t i = lane; 4 * i < bsn + 8; i += WAVE) {
         uint32_t v = 0;
@@ -369,6 +389,12 @@ __device__ __noinline__ uint32_t zero_run_chain_segments(const uint8_t* bs, uint
     *total_out = tall + (regen - tll);
     __syncthreads();
     return 1u;
+}
+__device__ __noinline__ uint32_t zero_run_chain_segments(const uint8_t* bs, uint32_t bsn, uint2* ws, uint32_t nseq, uint2 llt, uint2 mlt,
+                                                         uint32_t regen, const uint8_t* cp, uint32_t ncp, uint32_t spacing, int lane,
+                                                         uint32_t* total_out, uint32_t* lds, uint32_t lds_bytes)
+{
+    return zero_run_chain_segments_inl(bs, bsn, ws, nseq, llt, mlt, regen, cp, ncp, spacing, lane, total_out, lds, lds_bytes);
 }
 
 }  // namespace
