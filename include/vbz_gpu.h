@@ -465,6 +465,60 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_trim_batch(vbz_gpu_ctx* ctx, const vbz_gpu_ba
                                               uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm,
                                               const vbz_gpu_sample_ranges* ranges, const vbz_gpu_trim* trim, float* shift_scale, uint32_t* begin);
 
+/* Signal windows.  The chunk calls cut every read on the regular grid k * step.  A modification caller wants a fixed-length context around
+ * every candidate site of a read, a training loader windows at recorded or random offsets: many windows per read, at positions only the
+ * caller knows.  The two calls below are the ranged chunk calls with the chunking replaced by a list of windows per read.
+ * The arena: `out` is a row-major [window_rows, L] arena of format->out_type (L = window_len), 16-byte aligned.  Read i owns rows
+ * window_first[i] ... window_first[i + 1] - 1, and start[c] says where row c's window begins in the read's signal.
+ * The rule for one position: the signal is the read's samples x[b:e) of T' = e - b samples, ranges clamped exactly as in the *_range_batch
+ * calls above (ranges NULL, or both tables NULL: the whole read).  Position p of row c holds the converted sample start[c] + p of that
+ * signal when 0 <= start[c] + p < T' (64-bit arithmetic), and `pad` otherwise.  So a window may hang over the front of the signal (a
+ * negative start) or over its end, or lie wholly outside (all pad); windows may overlap to any degree and may repeat; T' == 0 gives rows
+ * of pad.  The conversion is the signal call's, with its rounding: ((float)x + offset) * scale, the constants format->offset / scale when
+ * norm is NULL, else the read's own statistics as in the *_norm calls (format->offset and scale must then be NULL, shift_scale is nullable,
+ * ranges->stats has its meaning).  `pad` is rounded (to nearest even) to the output type and otherwise taken as it is.
+ * The tables are untrusted.  Per read, in this order: the descriptor checks; sized, the header verdicts; then the window check, which
+ * refuses window_first[i] > window_first[i + 1], window_first[i + 1] > window_rows, more than 2^31 - 1 rows of one read, and a pair
+ * start[c] > start[c + 1] inside the read's rows (the starts of a read must be sorted: a lane then finds a position's windows by a walk,
+ * not a search).  A read refused by it gets VBZ_DESTINATION_SIZE_ERROR and not one byte of out is written for it.  No start[] entry of a
+ * read is read before its two window_first entries have passed, and no address is formed from an unchecked value.  Reads need not tile the
+ * arena and are checked one by one: rows that two reads both list are written by both.
+ * Verdicts otherwise are the chunk call's: result[i] = T x E with the read's FULL sample count on success, when every position of the
+ * read's rows has been written; rows of a read that fails after the window check hold unspecified contents; nothing outside the rows owned
+ * by reads is ever written.
+ * vbz_gpu_pod5_decompress_windows_batch: the same over POD5 reads of several rows.  The constants, window_first, shift_scale and the range
+ * tables are per READ, positions are those of the concatenated signal; result[] stays per row and read_result[] per read as in the POD5
+ * chunk calls; the window check is per READ and gives VBZ_DESTINATION_SIZE_ERROR to every row of the read; a bad first_row fails whole.
+ * Both return 0 when queued, -1 for a NULL context or batch or a launch failure, -2 (nothing launched) for everything
+ * vbz_gpu_decompress_chunks_range_batch / its POD5 twin refuse, a NULL windows, window_len outside its rule, flags or reserved != 0, a NULL
+ * window_first, start (when window_rows > 0) or out while the call has reads, out not 16-byte aligned, window_rows * L * E beyond 2^46 bytes.
+ * How: one more store of the svb decoder, on every decode path.  A lane holds eight consecutive samples; the windows that
+ * hold them are consecutive in the read's sorted list; the workgroup brackets the candidates of each tile of 2 048 samples with two
+ * cursors that only advance, and a lane walks that bracket alone.  A window whose start is congruent to the
+ * lane's position modulo 8 takes whole 16-byte stores; any other is stored sample by sample.  The pad positions are written by one launch
+ * of its own behind the window check, a wavefront per row.  Measured on one MI355X: 65 536 reads of ~100 k samples, float16 (tools/time_windows.py, profiles/HISTORY.md
+ * "Signal windows"; the parent of the commit that adds these calls is 922424a): the PAD grid L = 10 000, S = 9 504 given as windows 14.4 ms
+ * against 11.2 ms for the chunk call itself and 30.0 ms for the signal call (10.6 ms) followed by a torch gather; as many windows at random
+ * starts 16.8 ms against 29.5 ms unfused; L = 512 every 64 samples (coverage 8) over 8 192 reads 18.2 ms against 23.1 ms unfused -- the stores
+ * dominate and the saving shrinks from 2.1 x to 1.27 x.  One 20 M-sample read: 0.354 / 0.367 / 0.487 ms against 0.424 / 0.393 / 0.748 ms. */
+typedef struct vbz_gpu_windows
+{
+    uint32_t window_len;          /* L: samples per window, a multiple of 8, 8 <= L <= 2^20 */
+    float pad;                    /* the value of positions outside the signal, rounded (RNE) to the output type */
+    uint64_t window_rows;         /* rows of the arena = entries of start[] */
+    const uint64_t* window_first; /* device, n_reads + 1: read i owns rows window_first[i] ... window_first[i + 1] - 1 */
+    const int32_t* start;         /* device, window_rows: the first sample of each row's window, in positions of the read's signal */
+    uint32_t flags;               /* must be 0 */
+    uint32_t reserved;            /* must be 0 */
+} vbz_gpu_windows;                /* 40 bytes */
+VBZ_EXPORT int vbz_gpu_decompress_windows_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                                const vbz_gpu_signal_format* format, const vbz_gpu_windows* windows, void* out,
+                                                const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges);
+VBZ_EXPORT int vbz_gpu_pod5_decompress_windows_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                     const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
+                                                     const vbz_gpu_windows* windows, void* out, const vbz_gpu_normalization* norm,
+                                                     float* shift_scale, const vbz_gpu_sample_ranges* ranges);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -131,6 +131,20 @@ class GpuSampleRanges(ctypes.Structure):
     ]
 
 
+class GpuWindows(ctypes.Structure):
+    """struct vbz_gpu_windows of include/vbz_gpu.h (40 bytes)."""
+
+    _fields_ = [
+        ("window_len", ctypes.c_uint32),
+        ("pad", ctypes.c_float),
+        ("window_rows", ctypes.c_uint64),
+        ("window_first", ctypes.c_void_p),
+        ("start", ctypes.c_void_p),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 VBZ_GPU_TRIM_REJECT_AT_END = 1   # vbz_gpu_trim.flags: a trim whose window ends at the end of the samples looked at is rejected
 
 
@@ -188,6 +202,8 @@ GPU_API = [
     "vbz_gpu_pod5_signal_norm_range_batch",
     "vbz_gpu_signal_trim_batch",
     "vbz_gpu_pod5_signal_trim_batch",
+    "vbz_gpu_decompress_windows_batch",
+    "vbz_gpu_pod5_decompress_windows_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -326,6 +342,16 @@ def load():
         L.vbz_gpu_signal_trim_batch.argtypes = [vp, bp, op, ctypes.c_int, u32, np_, gp, tp, vp, vp]
         L.vbz_gpu_pod5_signal_trim_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_signal_trim_batch.argtypes = [vp, bp, op, u32, rp, np_, gp, tp, vp, vp]
+    if hasattr(L, "vbz_gpu_decompress_windows_batch"):   # (likewise: builds of earlier rounds have no signal windows)
+        np_ = ctypes.POINTER(GpuNormalization)
+        fp = ctypes.POINTER(GpuSignalFormat)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        gp = ctypes.POINTER(GpuSampleRanges)
+        wp = ctypes.POINTER(GpuWindows)
+        L.vbz_gpu_decompress_windows_batch.restype = ctypes.c_int
+        L.vbz_gpu_decompress_windows_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, wp, vp, np_, vp, gp]
+        L.vbz_gpu_pod5_decompress_windows_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_decompress_windows_batch.argtypes = [vp, bp, op, fp, rp, wp, vp, np_, vp, gp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

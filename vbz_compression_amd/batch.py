@@ -149,13 +149,14 @@ class GpuCodec:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self.L.vbz_gpu_last_error(self.ctx).decode()))
 
     def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
-               chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None):
+               chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None):
         """One typed decode (include/vbz_gpu.h): the batch, the device entered and left once, and the most general C entry of the call's
         family, NULL for every part that is None.  dst None: nothing is stored in the batch's dst (a chunk decode, the statistics) --
         dst_off / dst_cap are the int16 layout that describes the reads, dst_bytes its extent.  f (a GpuSignalFormat): what is stored,
         with ch (a GpuChunking) into `chunks` at chunk_first; f None: the statistics alone of `signed` samples, with t (a GpuTrim) the
         trim points behind them, into `out`.  m / ss: the GpuNormalization and the shift_scale pointer; g: a GpuSampleRanges; r: a
-        GpuPod5Reads (the pod5_ entries: unsized)."""
+        GpuPod5Reads (the pod5_ entries: unsized).  w (a GpuWindows, in place of ch): the samples go to the caller-listed windows, the
+        rows of `chunks`."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -165,7 +166,10 @@ class GpuCodec:
             return ctypes.byref(s) if s is not None else None
 
         reads = [ref(r)] if r is not None else []
-        if ch is not None:
+        if w is not None:
+            assert ch is None, "a call has a chunking or windows, never both"
+            name, args = "decompress_windows", [ref(f)] + reads + [ref(w), chunks.data_ptr(), ref(m), ss, ref(g)]
+        elif ch is not None:
             name, args = "decompress_chunks_range", [ref(f), ref(ch)] + reads + [chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]), ref(m),
                                                                                  ss, ref(g)]
         elif f is None and t is not None:
@@ -586,6 +590,47 @@ class GpuCodec:
                             signed, norm, norm_out, g)
         return chunks, chunk_first, chunk_info, result
 
+    # -- signal windows (include/vbz_gpu.h: vbz_gpu_windows) -------------------------------------------
+    def _windows(self, n, window_first, start, window_len, pad):
+        """(the C struct, the tables it points to) of n reads' windows: window_first int64 [n + 1] and start int32 [rows] on the device"""
+        assert window_first.dtype == torch.int64 and window_first.is_contiguous() and window_first.device == self.device, (window_first.dtype, window_first.device)
+        assert start.dtype == torch.int32 and start.is_contiguous() and start.device == self.device, (start.dtype, start.device)
+        assert int(window_first.numel()) == n + 1, (int(window_first.numel()), n)
+        w = _lib.GpuWindows()
+        w.window_len = int(window_len)
+        w.pad = float(pad)
+        w.window_rows = int(start.numel())
+        w.window_first = window_first.data_ptr()
+        w.start = start.data_ptr()
+        return w, (window_first, start)
+
+    def _decode_windows(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, window_first, start, window_len, pad, dtype,
+                        scale, offset, signed, norm, norm_out, begin, end, stats, r=None):
+        assert dtype in self._SIGNAL_TYPES, dtype
+        w, keep_w = self._windows(n, window_first, start, window_len, pad)
+        g, keep_g = self._ranges(n, begin, end, stats)
+        if norm is not None and norm_out is None:
+            norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
+        f = self._signal_format(dtype, n, scale, offset, signed)
+        out = self._chunk_arena(int(start.numel()), window_len, dtype)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=out, m=m, ss=ss, g=g, r=r, w=w)
+        return out if norm is None else (out, norm_out)
+
+    def decompress_windows(self, src, src_off, src_size, samples, result, opts, window_first, start, window_len, pad=0.0, dtype=torch.float16,
+                           scale=None, offset=None, signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None):
+        """Decode unsized int16 reads of `samples` samples (int32 on the device) straight into caller-listed windows of their signal
+        (include/vbz_gpu.h: vbz_gpu_decompress_windows_batch), calibrated as decompress_signal does -> windows [rows, window_len] of dtype,
+        and with norm= (windows, shift_scale float32 [n, 2]).  Read i owns rows window_first[i] ... window_first[i + 1] - 1 (int64 [n + 1] on
+        the device); row c holds samples start[c] ... start[c] + window_len - 1 (int32 [rows] on the device, sorted within a read; may
+        hang over either end) of the read's signal -- of its range with begin / end (as for decompress_chunks) -- and `pad` outside it.
+        result[i] = samples * element size when every position of the read's rows has been written.  No synchronisation."""
+        n = int(src_off.numel())
+        assert int(samples.numel()) == n
+        dst_off, dst_cap = self._row_layout(samples)
+        return self._decode_windows(n, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, opts, False, window_first, start,
+                                    window_len, pad, dtype, scale, offset, signed, norm, norm_out, begin, end, stats)
+
     # -- POD5 reads of several rows (include/vbz_gpu.h: vbz_gpu_pod5_reads) ---------------------------
     def _pod5_reads(self, n_rows, read_first_row, read_result):
         """(the C struct, first_row int32 [n_reads + 1] on the device, read_result) of rows grouped by read_first_row: the first row of
@@ -641,6 +686,19 @@ class GpuCodec:
         self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, opts, dst_bytes=host[1], f=f, ch=ch, chunk_first=chunk_first, chunks=chunks,
                     m=m, ss=ss, g=g, r=r)
         return chunks, chunk_first, chunk_info, read_result
+
+    def pod5_decompress_windows(self, src, src_off, src_size, row_samples, read_first_row, result, window_first, start, window_len, pad=0.0,
+                                dtype=torch.float16, scale=None, offset=None, signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None,
+                                read_result=None):
+        """decompress_windows over POD5 signal rows grouped into reads by read_first_row (include/vbz_gpu.h:
+        vbz_gpu_pod5_decompress_windows_batch): window_first, scale / offset / norm_out and begin / end are per READ, the positions those of
+        the read's concatenated signal; result is per ROW, read_result (int32 [n_reads] on the device, optional) per read."""
+        n = int(src_off.numel())
+        assert int(row_samples.numel()) == n
+        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        return self._decode_windows(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
+                                    window_first, start, window_len, pad, dtype, scale, offset, signed, norm, norm_out, begin, end, stats, r=r)
 
     def pod5_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, shift_scale=None, signed=True, begin=None,
                          end=None, stats=None):

@@ -300,7 +300,8 @@ __global__ void signal_slots_kernel(uint32_t n, const uint64_t* dst_off, const u
     if (o % elem != 0 || c % elem != 0) gate[i] = E_DESTINATION_SIZE;
 }
 
-// chunk decode: see launch_chunk_slots (vbz_kernels.h)
+// chunk decode: see launch_chunk_slots (vbz_kernels.h).  (The window calls' counterpart, the window check, is window_counts_kernel and
+// window_sorted_kernel in pack.hip, beside the scan launches it uses: launch_window_check.)
 __global__ void chunk_slots_kernel(uint32_t n, const uint32_t* cap16, const float* offset, const float* scale, uint32_t L, uint32_t S,
                                    const uint64_t* chunk_first, uint64_t chunk_rows, float2* cal, uint32_t* gate)
 {

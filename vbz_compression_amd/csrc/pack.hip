@@ -342,6 +342,60 @@ __global__ __launch_bounds__(256) void pack_gather_kernel(uint32_t n, const uint
     }
 }
 
+// ---- signal windows: the window check (vbz_kernels.h launch_window_check) -------------------------------------------------------------
+// launch 1: every read's row count -- 0 unless its two entries of wfirst are rows of the arena -- and the tile sums.  Reads of a batch:
+// the constants' table too, and a pair that fails closes the read's gate; POD5 reads: the plan has looked at the pairs.
+__global__ __launch_bounds__(1024) void window_counts_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale, uint64_t* off, uint32_t* count)
+{
+    __shared__ uint64_t wsum[16];
+    const bool reads = pr.reads != nullptr;
+    const uint32_t n = reads ? pr.n_reads : b.n_reads;
+    const uint32_t i = blockIdx.x * TILE + threadIdx.x;
+    uint64_t take = 0;
+    if (i < n) {
+        if (reads) {
+            if (!*pr.bad && !(pr.reads[i].flags & POD5_READ_FAIL)) take = b.sig.wfirst[i + 1] - b.sig.wfirst[i];
+        } else {
+            uint32_t* gate = const_cast<uint32_t*>(b.gate);
+            const_cast<float2*>(b.sig.cal)[i] = make_float2(offset ? offset[i] : 0.0f, scale ? scale[i] : 1.0f);
+            if (gate[i] < GATE_SKIP) {
+                const uint64_t a = b.sig.wfirst[i], z = b.sig.wfirst[i + 1];
+                if (a > z || z > b.sig.wrows || z - a > WINDOW_READ_ROWS_MAX) gate[i] = E_DESTINATION_SIZE;
+                else take = z - a;
+            }
+        }
+        count[i] = (uint32_t)take;
+    }
+    const uint64_t t = block_sum_u64(take, wsum);
+    if (threadIdx.x == 0) off[blockIdx.x * TILE] = t;
+}
+
+// launch 4 (behind the scan): the j-th counted row -> its read (scan_find) and its row c of the arena; a pair start[c] > start[c + 1]
+// inside a read's rows closes the read.  Every start read here belongs to a read whose pair has passed.
+__global__ __launch_bounds__(256) void window_sorted_kernel(ReadBatch b, Pod5Reads pr, const uint64_t* scan)
+{
+    const bool reads = pr.reads != nullptr;
+    const uint32_t n = reads ? pr.n_reads : b.n_reads;
+    const uint64_t total = scan[n];
+    uint32_t* gate = const_cast<uint32_t*>(b.gate);
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j + 1 < total; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t i = scan_find(scan, n, j);
+        if (j + 1 >= scan[i + 1]) continue;   // the read's last row
+        const uint64_t c = b.sig.wfirst[i] + (j - scan[i]);
+        if (b.sig.wstart[c] <= b.sig.wstart[c + 1]) continue;
+        if (!reads) {
+            gate[i] = E_DESTINATION_SIZE;
+            continue;
+        }
+        // a POD5 read: closed as the plan closes a read that fails its check -- POD5_READ_FAIL, its rows' gates, its statistics finished.
+        // The plan also zeroes the read's T and range and its rows' flags; they stay here (the plan has passed them: a window call sets no
+        // POD5_ROW_PAD, and every kernel behind this one looks at POD5_READ_FAIL or the rows' gates before it looks at T or the range)
+        atomicOr(&pr.reads[i].flags, POD5_READ_FAIL);
+        for (uint32_t r = pr.first_row[i]; r < pr.first_row[i + 1]; ++r) gate[r] = E_DESTINATION_SIZE;
+        if (b.sig.norm.st) b.sig.norm.st[i].phase = NORM_DONE;
+    }
+}
+
 hipError_t scan_launches(uint32_t n, uint32_t align, const uint32_t* size, uint64_t* off, hipStream_t s)
 {
     hipLaunchKernelGGL(pack_scan_tiles_kernel, dim3(1), dim3(1024), 0, s, n, off);
@@ -350,6 +404,18 @@ hipError_t scan_launches(uint32_t n, uint32_t align, const uint32_t* size, uint6
 }
 
 }  // namespace
+
+hipError_t launch_window_check(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, hipStream_t s)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(window_counts_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, b, pr, offset, scale, w.scan, w.count);
+    const hipError_t e = scan_launches(n, 1, w.count, w.scan, s);
+    if (e != hipSuccess || b.sig.wrows < 2) return e;
+    const uint64_t wgs = (b.sig.wrows + 255) / 256;
+    hipLaunchKernelGGL(window_sorted_kernel, dim3((uint32_t)(wgs < 4096u ? wgs : 4096u)), dim3(256), 0, s, b, pr, w.scan);
+    return hipGetLastError();
+}
 
 hipError_t launch_pack_layout(uint32_t n, const uint32_t* result, const uint64_t* dst_off, const uint32_t* dst_cap, uint64_t dst_bytes, uint32_t align,
                               uint64_t* packed_off, uint32_t* packed_size, hipStream_t s)

@@ -394,6 +394,137 @@ struct ChunkStore
     __device__ __forceinline__ void finish() const { chunk_pad<OUT>(ck, (ROWS || RANGED) && pad_elems); }
 };
 
+// ---- window store (SignalOut::wfirst; OUT = SIG_* | SIG_CHUNK | SIG_WINDOW): the typed samples into caller-listed windows ------------
+// Row w of the read's n rows holds positions start[w] ... start[w] + L - 1 of the signal (the read's samples [rb, rb + T)); the starts are
+// sorted (the window check), so the windows are sorted by their ends too.  A lane holds eight consecutive samples at signal position q0.
+// The windows that hold one of them are consecutive in the list: from the first whose end lies behind the lane's first sample to the last
+// that starts in front of its last one.  Into each of them the lane stores one whole line when all eight are samples of the signal and lie
+// at a multiple of 8 of the window, wholly inside it; otherwise its samples inside the window one by one.  Only positions that hold a
+// sample are ever written here: every other position of the rows is window_pad_kernel's.  No cross-lane exchange: the
+// rule is the same for a read, a segment, a POD5 row and a range.
+struct WindowK
+{
+    uint8_t* base = nullptr;          // the read's first row
+    const int32_t* start = nullptr;   // its rows' starts
+    uint64_t row_bytes = 0;           // L * E
+    uint32_t n = 0, L = 0;            // rows, samples per row
+    uint32_t rb = 0, T = 0;           // the signal: samples [rb, rb + T) of the read
+};
+
+// the windows of the read whose entry of SignalOut::wfirst is i (the window check has passed: the entries are rows of the arena -- a pair
+// that is not gives no row, so no address is formed from it whatever comes in)
+template <int OUT>
+__device__ __forceinline__ WindowK window_constants(const ReadBatch& b, uint32_t i, uint32_t rb, uint32_t rend)
+{
+    WindowK w;
+    const uint64_t a = b.sig.wfirst[i], z = b.sig.wfirst[i + 1];
+    const bool ok = a <= z && z <= b.sig.wrows && z - a <= WINDOW_READ_ROWS_MAX;
+    w.n = ok ? (uint32_t)(z - a) : 0u;
+    w.L = b.sig.chunk_len;
+    w.row_bytes = (uint64_t)w.L * OutBytes<OUT>::value;
+    w.base = b.dst + (ok ? a : 0ull) * w.row_bytes;
+    w.start = b.sig.wstart + (ok ? a : 0ull);
+    w.rb = rb;
+    w.T = rend - rb;
+    return w;
+}
+
+// The window store of one workgroup: its values lie at s0 of the read (ROWS: a row of a POD5 read; else 0 -- put() gets positions in the
+// read).  Every lane of the workgroup calls put() at the same point with i0 = the tile's first value + 8 x its thread number (the tile
+// loops of svb_decode_range, I16DecPairs and svb16_decode_row), so the tile's samples [ta, tb) of the signal are workgroup-uniform, and
+// so is the bracket [lo, hi) of its candidates: lo the first window that still reaches ta, hi the first that starts at or behind tb.
+// The windows are sorted by start, hence by end, and a workgroup's tiles only move forward: both ends only advance, 64 windows a step
+// (one load per lane and a ballot; every wavefront of the workgroup comes to the same values).  One binary search, at the workgroup's
+// first tile that holds samples (a segment and a POD5 row start in the middle of the list; also if a tile ever lay in front of the one
+// before).  A lane then walks the bracket alone, the same window in every lane at the same time.
+template <int OUT, bool ROWS>
+struct WindowStore
+{
+    static constexpr uint32_t UNSET = 0xFFFFFFFFu;
+    WindowK wk;
+    SigK sk;
+    uint32_t s0 = 0;
+    mutable uint32_t lo = UNSET, hi = 0, at = 0;   // the bracket, and the first sample of the tile it was made for
+
+    __device__ __forceinline__ int64_t end_of(uint32_t w) const { return (int64_t)wk.start[w] + (int64_t)wk.L; }
+    // the first window that ends behind position q (n: none): wave-uniform arguments, wave-uniform result
+    __device__ __forceinline__ uint32_t first_behind(int64_t q) const
+    {
+        uint32_t a = 0, z = wk.n;
+        while (a < z) {
+            const uint32_t mid = a + ((z - a) >> 1);
+            if (end_of(mid) > q) z = mid;
+            else a = mid + 1u;
+        }
+        return a;
+    }
+    // the first window at or behind c at which pred fails (n: none), pred holding on a prefix of [c, n): by the whole wavefront
+    template <class P>
+    __device__ __forceinline__ uint32_t advance(uint32_t c, P pred) const
+    {
+        const uint32_t lane = threadIdx.x & 63u;
+        for (;;) {
+            const uint32_t w = c + lane;
+            const uint64_t m = __ballot(w < wk.n && pred(w) ? 1 : 0);
+            const uint32_t k = m == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~m);
+            c += k;
+            if (k < 64u) return c;
+        }
+    }
+
+    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
+    {
+        constexpr uint32_t OB = OutBytes<OUT>::value;
+        if (wk.n == 0) return;
+        // the tile (workgroup-uniform): values t0 ... t0 + 8 WG - 1 of the workgroup's, samples [ta, tb) of the signal
+        const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(i0 - 8u * threadIdx.x));
+        const int64_t tq = (int64_t)(ROWS ? s0 : 0u) + (int64_t)t0 - (int64_t)wk.rb;
+        const int64_t ta = tq < 0 ? 0 : tq, tb = tq + 8 * WG < (int64_t)wk.T ? tq + 8 * WG : (int64_t)wk.T;
+        if (ta >= tb) return;   // no sample of the signal in the tile
+        uint32_t a = lo, z = hi;
+        if (a == UNSET || ta < (int64_t)at) {
+            a = first_behind(ta);
+            z = a;
+        } else {
+            a = advance(a, [&](uint32_t w) { return end_of(w) <= ta; });
+        }
+        z = advance(z > a ? z : a, [&](uint32_t w) { return (int64_t)wk.start[w] < tb; });
+        a = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
+        z = (uint32_t)__builtin_amdgcn_readfirstlane((int)z);
+        lo = a;
+        hi = z;
+        at = (uint32_t)ta;
+        // the lane: values jl ... jh - 1 of its eight are samples of the signal, at positions [qa, qb)
+        const int64_t q0 = tq + 8 * (int64_t)threadIdx.x;
+        const int64_t l0 = q0 < 0 ? -q0 : 0, h0 = (int64_t)wk.T - q0;
+        const int jl = l0 < (int64_t)valid ? (int)l0 : valid, jh = h0 < (int64_t)valid ? (h0 < 0 ? 0 : (int)h0) : valid;
+        if (jl >= jh || a >= z) return;
+        const int64_t qa = q0 + jl, qb = q0 + jh;
+        uint32_t e[8];
+        chunk_elems8<OUT>(ChunkK(), 8, base, s, sk, e);
+        const bool whole = jl == 0 && jh == 8;
+        for (uint32_t c = a; c < z; ++c) {
+            const int64_t st = wk.start[c];
+            if (st >= qb) break;
+            if (st + (int64_t)wk.L <= qa) continue;
+            const int64_t d = q0 - st;   // the lane's first value in the window
+            uint8_t* row = wk.base + (uint64_t)c * wk.row_bytes;
+            if (whole && d >= 0 && d <= (int64_t)wk.L - 8 && (d & 7) == 0) {
+                chunk_put8<OUT>(row + (size_t)d * OB, e);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int64_t pos = d + j;
+                    if (j >= jl && j < jh && pos >= 0 && pos < (int64_t)wk.L) chunk_put1<OUT>(row + (size_t)pos * OB, e[j]);
+                }
+            }
+        }
+    }
+};
+struct NoWindowStore
+{
+};
+
 // ---- normalisation statistics (OUT = SIG_COUNT; vbz_kernels.h NormRead) -------------------------------------------------------------
 // The counting pass histograms a read's keys into the windows of its NormRead in LDS; the select turns the counts into ranks.  A read on
 // one workgroup is selected at the end of its pass with the counts still in LDS; on the large-read path every segment adds its counts to
@@ -734,6 +865,7 @@ __device__ __forceinline__ void trim_scan(const uint32_t* h, const TrimK<true>& 
 // typed slot (dst + dst_off[r] / 2 * E: dst_off is the int16 layout's).  SIG_* | SIG_CHUNK: the typed samples into the read's chunks.
 // | SIG_RANGE (the chunk stores and SIG_COUNT): the read is its samples [b, e) -- the others are decoded (the delta chain needs them) and
 // neither converted, stored nor counted.  The chunk case is a ChunkStore with s0 = 0 and re = T: put() and finish() are its.
+// SIG_* | SIG_CHUNK | SIG_WINDOW: the typed samples into the read's caller-listed windows, a WindowStore with s0 = 0 (put() is its).
 // SIG_TRIM: the trim pass -- nothing is stored; the high samples of the read's prefix are counted per window (open_trim() gives the state).
 template <int ELEM, int OUT>
 struct DecStore
@@ -750,6 +882,8 @@ struct DecStore
     [[no_unique_address]] RangeK<RANGED> rg;     // SIG_COUNT | SIG_RANGE
     static constexpr bool TRIM = (OUT & SIG_TRIM) != 0;
     [[no_unique_address]] TrimK<TRIM> tk;        // SIG_TRIM
+    static constexpr bool WINDOW = (OUT & SIG_WINDOW) != 0;
+    [[no_unique_address]] std::conditional_t<WINDOW, WindowStore<OUT, false>, NoWindowStore> ws;   // SIG_WINDOW
 
     // b: the batch, for the typed stores only -- SIG_NONE gets nullptr and the batch's fields (a reference to the kernel's ReadBatch
     // argument would cost its loads their scalar form)
@@ -791,6 +925,10 @@ struct DecStore
             __syncthreads();
         } else if (OUT & SIG_TRIM) {
             out = nullptr;
+        } else if constexpr (WINDOW) {
+            out = dst;
+            ws.wk = window_constants<OUT>(*b, b->sig.wmap ? b->sig.wmap[r] : r, rb, rend);
+            ws.sk = sig_constants(*b, r);
         } else if (OUT & SIG_CHUNK) {
             out = dst;
             cs.ck = chunk_constants<OUT>(*b, count, b->sig.row[r]);
@@ -831,6 +969,10 @@ struct DecStore
                     atomicAdd(&tk.L->h[w], d - w * tk.W == tk.W - 1u ? 0x80000001u : 1u);   // (bit 31: the window's last sample)
                 }
             }
+            return;
+        }
+        if constexpr (WINDOW) {
+            ws.put(i0, valid, base, s);
             return;
         }
         if (OUT & SIG_COUNT) {   // one LDS increment per value: its key's bin
@@ -897,6 +1039,7 @@ struct DecStore
     // after the read's values, by the whole workgroup (svb_decode_range: the range at the read's start): the chunk store's pad
     __device__ __forceinline__ void finish() const
     {
+        if constexpr (WINDOW) return;   // (the windows' pad: window_pad_kernel)
         if (OUT & SIG_CHUNK) cs.finish();
     }
 
@@ -2738,7 +2881,9 @@ __global__ __launch_bounds__(WG) void pod5_read_samples_kernel(Pod5Reads pr, con
 // first pass's windows around the first sample of its first row that has one.
 // RANGED: the read's clamped range goes to pr.range, the chunk check is against the range's chunks, and the element-wise flag is about the
 // row that holds the range's last sample (rows lie at s0 - b of the range's signal).
-template <bool RANGED>
+// WINDOWS (b.sig.wfirst; b.sig.row is NULL): the check is the first half of the window check -- the read's two entries of wfirst are rows of
+// the arena; window_sorted_kernel looks at the starts behind this launch.
+template <bool RANGED, bool WINDOWS = false>
 __device__ __forceinline__ void pod5_reads_plan(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows)
 {
     const uint32_t i = blockIdx.x * WG + threadIdx.x;
@@ -2771,7 +2916,13 @@ __device__ __forceinline__ void pod5_reads_plan(const ReadBatch& b, const Pod5Re
             if (pr.rows[j].s0 < re && (b.dst_cap[j] >> 1) != 0) last_s0 = pr.rows[j].s0 - rb;
     }
     uint64_t c0 = 0;
-    if (b.sig.row && !fail) {
+    if constexpr (WINDOWS) {
+        if (!fail) {
+            c0 = b.sig.wfirst[i];
+            const uint64_t c1 = b.sig.wfirst[i + 1];
+            fail = c0 > c1 || c1 > b.sig.wrows || c1 - c0 > WINDOW_READ_ROWS_MAX;
+        }
+    } else if (b.sig.row && !fail) {
         c0 = b.sig.row[i];
         const uint64_t c1 = b.sig.row[i + 1];
         fail = c0 > c1 || c1 > chunk_rows || c1 - c0 != chunk_count(re - rb, b.sig.chunk_len, b.sig.step);
@@ -2821,6 +2972,84 @@ __global__ __launch_bounds__(WG) void pod5_reads_plan_range_kernel(ReadBatch b, 
     pod5_reads_plan<true>(b, pr, offset, scale, chunk_rows);
 }
 
+__global__ __launch_bounds__(WG) void pod5_reads_plan_window_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale)
+{
+    pod5_reads_plan<false, true>(b, pr, offset, scale, 0);
+}
+__global__ __launch_bounds__(WG) void pod5_reads_plan_window_range_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale)
+{
+    pod5_reads_plan<true, true>(b, pr, offset, scale, 0);
+}
+
+// the window store of a row of a read, from the plan: the row's samples lie at s0 of the read's signal
+template <int OUT>
+__device__ __forceinline__ WindowStore<OUT, true> row_window_store(const ReadBatch& b, const Pod5Reads& pr, const Pod5Row& rw)
+{
+    WindowStore<OUT, true> st;
+    uint32_t rb = 0, rend = pr.reads[rw.read].T;
+    if (OUT & SIG_RANGE) {
+        const uint2 g = pr.range[rw.read];
+        rb = g.x;
+        rend = g.y;
+    }
+    st.wk = window_constants<OUT>(b, rw.read, rb, rend);
+    st.sk = sig_constants(b, rw.read);
+    st.s0 = rw.s0;
+    return st;
+}
+
+// The pad of the windows (SignalOut::wfirst), behind the window check and independent of the decode: one wavefront per row of a read that
+// passed.  scan: the exclusive scan of the passing reads' row counts (launch_window_check), which says whose row the j-th is.  Row c of a
+// signal of T samples: positions p with start[c] + p < 0 or start[c] + p >= T take the pad value -- exactly the positions no sample
+// store writes -- element by element up to the next line boundary and in whole lines beyond.  pr.reads (a call over POD5 reads): b's
+// entries are rows, the reads' samples and ranges are the plan's, and a read that failed has no row in `scan`.
+__global__ __launch_bounds__(WG) void window_pad_kernel(ReadBatch b, Pod5Reads pr, const uint64_t* scan)
+{
+    const bool reads = pr.reads != nullptr;
+    const uint32_t n = reads ? pr.n_reads : b.n_reads, lane = threadIdx.x & 63u;
+    const uint32_t OB = b.sig.type == SIG_F32 ? 4u : 2u, L = b.sig.chunk_len;
+    const uint32_t padw = b.sig.type == SIG_F32   ? __float_as_uint(b.sig.pad)
+                          : b.sig.type == SIG_F16 ? sig_pack2<SIG_F16>(b.sig.pad, b.sig.pad) & 0xFFFFu
+                                                  : sig_pack2<SIG_BF16>(b.sig.pad, b.sig.pad) & 0xFFFFu;
+    const uint4 line = OB == 4 ? make_uint4(padw, padw, padw, padw) : make_uint4(padw * 0x10001u, padw * 0x10001u, padw * 0x10001u, padw * 0x10001u);
+    const uint64_t total = scan[n], waves = (uint64_t)gridDim.x * (WG / 64);
+    for (uint64_t j = (uint64_t)blockIdx.x * (WG / 64) + (threadIdx.x >> 6); j < total; j += waves) {
+        const uint32_t i = scan_find(scan, n, j);
+        uint32_t rb = 0, re = 0;
+        if (reads) {
+            if (pr.reads[i].flags & POD5_READ_FAIL) continue;   // (the starts decreased)
+            re = pr.reads[i].T;
+            if (b.sig.ranged()) {
+                const uint2 g = pr.range[i];
+                rb = g.x;
+                re = g.y;
+            }
+        } else {
+            if (b.gate[i] >= GATE_SKIP) continue;
+            sample_range(b.sig, i, b.dst_cap[i] >> 1, &rb, &re);
+        }
+        const uint64_t c = b.sig.wfirst[i] + (j - scan[i]);
+        const int64_t st = b.sig.wstart[c], T = (int64_t)(re - rb);
+        const uint32_t f = st >= 0 ? 0u : (-st < (int64_t)L ? (uint32_t)(-st) : L);                 // positions [0, f) lie in front of the signal
+        const uint32_t g = T - st <= 0 ? 0u : (T - st < (int64_t)L ? (uint32_t)(T - st) : L);       // ... and [g, L) behind it (g >= f)
+        uint8_t* row = b.dst + c * ((uint64_t)L * OB);
+        auto put = [&](uint32_t m, uint32_t p0, uint32_t p1) {   // positions [p0, p1) of line m
+            uint8_t* q = row + (size_t)m * 8u * OB;
+            if (p1 - p0 == 8u) {
+                *reinterpret_cast<uint4*>(q) = line;
+                if (OB == 4) *reinterpret_cast<uint4*>(q + 16) = line;
+            } else {
+                for (uint32_t p = p0; p < p1; ++p) {
+                    if (OB == 4) reinterpret_cast<uint32_t*>(q)[p] = padw;
+                    else reinterpret_cast<uint16_t*>(q)[p] = (uint16_t)padw;
+                }
+            }
+        };
+        for (uint32_t m = lane; m < (f + 7u) >> 3; m += 64u) put(m, 0u, f - 8u * m < 8u ? f - 8u * m : 8u);
+        for (uint32_t m = (g >> 3) + lane; m < (L >> 3); m += 64u) put(m, g > 8u * m ? g - 8u * m : 0u, 8u);
+    }
+}
+
 // the chunk store of row r of a read, from the plan: the row's `count` samples lie at s0 of the read's signal
 template <int OUT>
 __device__ __forceinline__ ChunkStore<OUT, true> row_chunk_store(const ReadBatch& b, const Pod5Reads& pr, const Pod5Row& rw, uint32_t count)
@@ -2852,7 +3081,7 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
     const Pod5Row rw = pr.rows[r];
-    if ((OUT & SIG_CHUNK) && (rw.flags & POD5_ROW_PAD)) row_chunk_store<OUT>(b, pr, rw, 0u).finish();
+    if ((OUT & SIG_CHUNK) && !(OUT & SIG_WINDOW) && (rw.flags & POD5_ROW_PAD)) row_chunk_store<OUT>(b, pr, rw, 0u).finish();
     uint32_t in_size = 0, count = 0, verdict;
     if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
         if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
@@ -2860,7 +3089,10 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
     }
     const uint8_t* in = b.src + b.src_off[r];
     bool good;
-    if (OUT & SIG_CHUNK) {
+    if constexpr ((OUT & SIG_WINDOW) != 0) {
+        const WindowStore<OUT, true> st = row_window_store<OUT>(b, pr, rw);
+        good = svb16_decode_row(in, in_size, count, st, stage, wsum);
+    } else if (OUT & SIG_CHUNK) {
         const ChunkStore<OUT, true> st = row_chunk_store<OUT>(b, pr, rw, count);
         good = svb16_decode_row(in, in_size, count, st, stage, wsum);
     } else {
@@ -3102,11 +3334,19 @@ hipError_t svb_dispatch_elem(int integer_size, bool zigzag, F&& f)
     return hipErrorInvalidValue;
 }
 
-// b.sig's store -> f(OUT): OUT = b.sig.type, | SIG_CHUNK with chunk rows, | SIG_RANGE with range tables (DecStore; chunk stores only)
+// b.sig's store -> f(OUT): OUT = b.sig.type, | SIG_CHUNK with chunk rows, | SIG_CHUNK | SIG_WINDOW with window rows, | SIG_RANGE with range
+// tables (DecStore; chunk and window stores only)
 template <class F>
 hipError_t svb_dispatch_store(const ReadBatch& b, F&& f)
 {
-    switch (b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u) | (b.sig.ranged() ? SIG_RANGE : 0u)) {
+    constexpr uint32_t WIN = SIG_CHUNK | SIG_WINDOW;
+    switch (b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u) | (b.sig.wfirst ? WIN : 0u) | (b.sig.ranged() ? SIG_RANGE : 0u)) {
+    case SIG_F32 | WIN: return f(Int<SIG_F32 | WIN>{});
+    case SIG_F16 | WIN: return f(Int<SIG_F16 | WIN>{});
+    case SIG_BF16 | WIN: return f(Int<SIG_BF16 | WIN>{});
+    case SIG_F32 | WIN | SIG_RANGE: return f(Int<SIG_F32 | WIN | SIG_RANGE>{});
+    case SIG_F16 | WIN | SIG_RANGE: return f(Int<SIG_F16 | WIN | SIG_RANGE>{});
+    case SIG_BF16 | WIN | SIG_RANGE: return f(Int<SIG_BF16 | WIN | SIG_RANGE>{});
     case SIG_F32 | SIG_CHUNK | SIG_RANGE: return f(Int<SIG_F32 | SIG_CHUNK | SIG_RANGE>{});
     case SIG_F16 | SIG_CHUNK | SIG_RANGE: return f(Int<SIG_F16 | SIG_CHUNK | SIG_RANGE>{});
     case SIG_BF16 | SIG_CHUNK | SIG_RANGE: return f(Int<SIG_BF16 | SIG_CHUNK | SIG_RANGE>{});
@@ -3310,15 +3550,31 @@ hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_sam
     return hipGetLastError();
 }
 
+hipError_t launch_window_pad(const ReadBatch& b, const Pod5Reads& pr, const WindowScratch& w, hipStream_t s)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (n == 0 || b.sig.wrows == 0) return hipSuccess;
+    const uint64_t wgs = (b.sig.wrows + WG / 64 - 1) / (WG / 64);
+    hipLaunchKernelGGL(window_pad_kernel, dim3((uint32_t)(wgs < 16384u ? wgs : 16384u)), dim3(WG), 0, s, b, pr, w.scan);
+    return hipGetLastError();
+}
+
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s, const TrimOut* trim)
+                                     hipStream_t s, const TrimOut* trim, const WindowScratch* win)
 {
     const uint32_t most = std::max(b.n_reads, pr.n_reads);
     if (most == 0) return hipSuccess;
     if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st) || b.sig.norm.slab || (trim && !b.sig.norm.st)) return hipErrorInvalidValue;
     const dim3 rows(b.n_reads), reads(pr.n_reads), t(WG);
     if (b.sig.ranged() && !pr.range) return hipErrorInvalidValue;
-    if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
+    if (b.sig.wfirst) {   // the plan with the first half of the window check, the second half, the pad
+        if (!win || b.sig.row) return hipErrorInvalidValue;
+        if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_window_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale);
+        else hipLaunchKernelGGL(pod5_reads_plan_window_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale);
+        hipError_t ew = launch_window_check(b, pr, nullptr, nullptr, *win, s);
+        if (ew == hipSuccess) ew = launch_window_pad(b, pr, *win, s);
+        if (ew != hipSuccess) return ew;
+    } else if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
     else hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
     const bool store = b.sig.type != SIG_NONE;
     if (b.sig.norm.st && pr.n_reads)

@@ -106,6 +106,7 @@ struct vbz_gpu_ctx
     DevBuf cksum;              // the hashes of a compress launch group (8 bytes per read)
     DevBuf sigmeta;            // typed decode: the int16 slot table and the per-read constants (signal_slots)
     DevBuf chunkmeta;          // chunk layout: the per-read chunk counts
+    DevBuf winmeta;            // signal windows: the per-read row counts and their scan (WindowScratch)
     DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables (Pod5Reads), the reads' constants
@@ -971,6 +972,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
         r->large.sig.norm.map = r->map;
     }
     if (rb.sig.ranged()) r->large.sig.rmap = r->map;   // (their ranges: the call's tables, through the map)
+    if (rb.sig.wfirst) r->large.sig.wmap = r->map;     // (and their windows)
     Timed t(c, "route");
     a.raw_size = raw_size;
     a.min_bytes = ROUTE_MIN_BYTES;
@@ -1090,6 +1092,7 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
     }
     if (u.sig.rbegin) u.sig.rbegin += h;
     if (u.sig.rend) u.sig.rend += h;
+    if (u.sig.wfirst) u.sig.wfirst += h;
     return u;
 }
 
@@ -1280,6 +1283,50 @@ void chunk_out(const vbz_gpu_chunking* ch, const uint64_t* chunk_first, void* ch
     rb->sig.pad = ch->pad;
 }
 
+// the windows of a *_windows_batch call: the struct's rules, the tables and the arena a call with reads needs (n_out: the reads the tables
+// have entries for), the arena's alignment and extent
+static_assert(sizeof(vbz_gpu_windows) == 40, "vbz_gpu_windows is 40 bytes");
+static_assert(offsetof(vbz_gpu_windows, window_len) == 0 && offsetof(vbz_gpu_windows, pad) == 4 && offsetof(vbz_gpu_windows, window_rows) == 8 &&
+                  offsetof(vbz_gpu_windows, window_first) == 16 && offsetof(vbz_gpu_windows, start) == 24 && offsetof(vbz_gpu_windows, flags) == 32 &&
+                  offsetof(vbz_gpu_windows, reserved) == 36,
+              "the fields of vbz_gpu_windows");
+bool windows_ok(vbz_gpu_ctx* c, const vbz_gpu_windows* w, const void* out, uint32_t n_out, uint32_t elem)
+{
+    if (!w) {
+        set_error(c, "windows is NULL");
+        return false;
+    }
+    const uint32_t L = w->window_len;
+    if (L < 8 || L > (1u << 20) || L % 8 != 0 || w->flags != 0 || w->reserved != 0) {
+        set_error(c, "windows outside the rules (window_len %u, flags %u, reserved %u)", L, w->flags, w->reserved);
+        return false;
+    }
+    if (n_out != 0 && (!w->window_first || (!w->start && w->window_rows != 0) || !out)) {
+        set_error(c, "window_first, start or the window arena is NULL");
+        return false;
+    }
+    if (((uintptr_t)out & 15u) != 0) {
+        set_error(c, "the window arena is not 16-byte aligned");
+        return false;
+    }
+    const uint64_t row_bytes = (uint64_t)L * elem;
+    if (w->window_rows > EXTENT_MAX / row_bytes) {
+        set_error(c, "declared window arena is not plausible (%llu rows of %llu bytes)", (unsigned long long)w->window_rows, (unsigned long long)row_bytes);
+        return false;
+    }
+    return true;
+}
+// the window part of SignalOut, and the arena the svb stage stores into
+void window_out(const vbz_gpu_windows* w, void* out, ReadBatch* rb)
+{
+    rb->dst = (uint8_t*)out;
+    rb->sig.wfirst = w->window_first;
+    rb->sig.wstart = w->start;
+    rb->sig.wrows = w->window_rows;
+    rb->sig.chunk_len = w->window_len;
+    rb->sig.pad = w->pad;
+}
+
 // the ranges of a *_range_batch call (nullable: the un-ranged call)
 static_assert(RANGE_STATS_RANGE == VBZ_GPU_RANGE_STATS_RANGE && RANGE_STATS_READ == VBZ_GPU_RANGE_STATS_READ, "the ABI's stats modes");
 static_assert(sizeof(vbz_gpu_sample_ranges) == 24, "vbz_gpu_sample_ranges is 24 bytes");
@@ -1397,6 +1444,9 @@ struct TypedCall
     const uint64_t* chunk_first = nullptr;      // ... the reads' chunks (untrusted: chunk_slots gates every read whose entries are not
     void* chunks = nullptr;                     // ... exactly its chunks before anything of it is decoded)
     uint64_t chunk_rows = 0;
+    bool with_windows = false;                  // CHUNKS, in place of a chunking (never both): rb.dst becomes the window arena and the svb
+    const vbz_gpu_windows* win = nullptr;       // ... stage stores the typed samples into the reads' windows (untrusted: the window check
+    void* win_out = nullptr;                    // ... gates every read whose rows or starts are not in order before anything of it is stored)
     const vbz_gpu_normalization* norm = nullptr;   // non-null: a normalising decode (the constants from the reads' statistics, into cal
     Null norm_null = Null::ALLOWED;                // ... and shift_scale)
     float* shift_scale = nullptr;
@@ -1414,6 +1464,11 @@ struct TypedCall
     TypedCall& chunking(const vbz_gpu_chunking* ch_, const uint64_t* first, void* arena, uint64_t rows)
     {
         ch = ch_, chunk_first = first, chunks = arena, chunk_rows = rows;
+        return *this;
+    }
+    TypedCall& windows(const vbz_gpu_windows* w, void* arena)
+    {
+        with_windows = true, win = w, win_out = arena;
         return *this;
     }
     TypedCall& normalise(const vbz_gpu_normalization* m, Null m_null, float* ss, Null ss_null)
@@ -1494,7 +1549,17 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     const bool chunks = out && out->kind == Typed::CHUNKS, stats = out && out->kind == Typed::STATISTICS;
     const uint32_t n_const = reads ? reads->n_reads : n;   // how many reads have constants and statistics
     float2* cal = nullptr;   // the per-read constants
-    if (chunks) chunk_out(out->ch, out->chunk_first, out->chunks, &rb);
+    const bool windows = chunks && out->with_windows;
+    WindowScratch wscratch;
+    if (windows) {
+        window_out(out->win, out->win_out, &rb);
+        if (!ensure(c, c->winmeta, (size_t)n_const * 12 + 256)) return -1;
+        MetaCarver mc(c->winmeta.p);
+        wscratch.scan = mc.take<uint64_t>((size_t)n_const + 1);
+        wscratch.count = mc.take<uint32_t>(n_const);
+    } else if (chunks) {
+        chunk_out(out->ch, out->chunk_first, out->chunks, &rb);
+    }
     if (out && !chunks && !stats) {   // typed slots (of POD5 rows too)
         if (signal_slots(c, bt, out->f, &rb, &dst_bytes, &cal) != 0) return -1;
     } else if (out && !reads) {   // the int16 layout as it is; the constants' table is chunk_slots' or the selects' to fill
@@ -1540,7 +1605,11 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         rb.dst_cap = orig_size;
         rb.gate = gate;
     }
-    if (chunks && !reads) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
+    if (windows && !reads) {   // (the window check, and the pad, which wants the final int16 capacities: the headers' sizes when sized)
+        Timed t(c, "window_slots");
+        HIPCHK(c, launch_window_check(rb, Pod5Reads(), out->f->offset, out->f->scale, wscratch, s), "window check launch");
+        HIPCHK(c, launch_window_pad(rb, Pod5Reads(), wscratch, s), "window pad launch");
+    } else if (chunks && !reads) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "chunk_slots");
         HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, out->f->offset, out->f->scale, rb.sig.chunk_len, rb.sig.step, out->chunk_first, out->chunk_rows,
                                      cal, const_cast<uint32_t*>(rb.gate), &rb.sig, s),
@@ -1568,7 +1637,8 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
             streams.sig = rb.sig;
         }
         Timed t(c, "svb_decode");
-        HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s, c->trim.begin ? &c->trim : nullptr),
+        HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s, c->trim.begin ? &c->trim : nullptr,
+                                            windows ? &wscratch : nullptr),
                "svb16_decode (reads) launch");
         return 0;
     }
@@ -1606,7 +1676,9 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
         set_error(c, "shift_scale is NULL");
         return -2;
     }
-    if (t.kind == Typed::CHUNKS) {                                                                                   // 8
+    if (t.kind == Typed::CHUNKS && t.with_windows) {                                                                 // 8 (windows in place of a chunking)
+        if (!windows_ok(c, t.win, t.win_out, n_out, t.f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u)) return -2;
+    } else if (t.kind == Typed::CHUNKS) {
         if (!chunking_ok(c, t.ch)) return -2;
         if (n_out != 0 && (!t.chunk_first || !t.chunks)) {
             set_error(c, "chunk_first or the chunk arena is NULL");
@@ -1736,7 +1808,7 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
         (void)hipEventDestroy(p.stop);
     }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta, &c->normmeta, &c->normslab, &c->pod5meta })
+    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta, &c->winmeta, &c->normmeta, &c->normslab, &c->pod5meta })
         if (b->p) (void)hipFree(b->p);
     if (c->large) vbz_gpu_destroy(c->large);
     if (c->half) vbz_gpu_destroy(c->half);
@@ -1854,20 +1926,23 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
     return 0;
 }
 
-// The fourteen typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
+// The sixteen typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
 //
-//   vbz_gpu_..._batch             kind        sized  chunking  norm      shift_scale          ranges    reads  trim
+//   vbz_gpu_..._batch             kind        sized  chunking  norm      shift_scale          ranges    reads  trim   (chunking "windows": a
+//                                                                                                                   vbz_gpu_windows in its place)
 //   decompress_signal             SIGNAL      arg    -         -         -                    -         -      -
 //   decompress_signal_norm        SIGNAL      arg    -         required  nullable             -         -      -
 //   decompress_chunks             CHUNKS      arg    yes       -         -                    -         -      -
 //   decompress_chunks_norm        CHUNKS      arg    yes       required  nullable             -         -      -
 //   decompress_chunks_range       CHUNKS      arg    yes       nullable  nullable             nullable  -      -
+//   decompress_windows            CHUNKS      arg    windows   nullable  nullable             nullable  -      -
 //   signal_norm                   STATISTICS  arg    -         required  required             -         -      -
 //   signal_norm_range             STATISTICS  arg    -         required  required             nullable  -      -
 //   signal_trim                   STATISTICS  arg    -         required  nullable             nullable  -      yes
 //   pod5_decompress_signal_norm   SIGNAL      0      -         required  nullable             -         yes    -
 //   pod5_decompress_chunks        CHUNKS      0      yes       nullable  nullable             -         yes    -
 //   pod5_decompress_chunks_range  CHUNKS      0      yes       nullable  nullable             nullable  yes    -
+//   pod5_decompress_windows       CHUNKS      0      windows   nullable  nullable             nullable  yes    -
 //   pod5_signal_norm              STATISTICS  0      -         required  required with reads  -         yes    -
 //   pod5_signal_norm_range        STATISTICS  0      -         required  required with reads  nullable  yes    -
 //   pod5_signal_trim              STATISTICS  0      -         required  nullable             nullable  yes    yes
@@ -1875,9 +1950,10 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
 //   only when reads->n_reads != 0.
-// - norm: NULL is a chunk decode without normalisation in decompress_chunks_range and the POD5 chunk entries, and a fault everywhere else.
+// - norm: NULL is a chunk decode without normalisation in decompress_chunks_range, the POD5 chunk entries and the two window entries, and a
+//   fault everywhere else.
 // - chunk_first and the chunk arena may be NULL when there is no read to store: batch->n_reads == 0, or, over POD5 reads,
-//   reads->n_reads == 0 (whatever the number of rows).
+//   reads->n_reads == 0 (whatever the number of rows).  The window entries: window_first, start (with window_rows != 0) and the arena, likewise.
 int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::SIGNAL, sized).format(f));
@@ -1908,6 +1984,14 @@ int vbz_gpu_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* b
                                           const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).chunking(ch, chunk_first, chunks, chunk_rows)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_decompress_windows_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                     const vbz_gpu_windows* windows, void* out, const vbz_gpu_normalization* norm, float* shift_scale,
+                                     const vbz_gpu_sample_ranges* ranges)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).windows(windows, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
@@ -1953,6 +2037,14 @@ int vbz_gpu_pod5_decompress_chunks_range_batch(vbz_gpu_ctx* c, const vbz_gpu_bat
                                                const vbz_gpu_sample_ranges* ranges)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).chunking(ch, chunk_first, chunks, chunk_rows)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_pod5_decompress_windows_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                          const vbz_gpu_pod5_reads* reads, const vbz_gpu_windows* windows, void* out,
+                                          const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).windows(windows, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 

@@ -31,6 +31,7 @@ constexpr uint32_t SIG_CHUNK = 4;   // (or-ed into the chunk store's type: the s
 constexpr uint32_t SIG_COUNT = 8;   // the svb decoder's counting pass of a normalising decode (OUT only: it stores nothing)
 constexpr uint32_t SIG_RANGE = 16;  // (or-ed into a chunk store's or the counting pass's OUT: only the samples of SignalOut's per-read range)
 constexpr uint32_t SIG_TRIM = 32;   // the svb decoder's trim pass behind the counting passes (OUT only: it stores nothing; TrimOut below)
+constexpr uint32_t SIG_WINDOW = 64; // (or-ed into a chunk store's OUT: the rows are caller-listed windows of the signal -- SignalOut::wfirst / wstart)
 constexpr uint32_t RANGE_STATS_RANGE = 0, RANGE_STATS_READ = 1;   // (= VBZ_GPU_RANGE_STATS_*)
 constexpr uint32_t CHUNK_PAD = 0, CHUNK_END = 1;
 
@@ -81,7 +82,16 @@ struct SignalOut
     uint32_t rstats = RANGE_STATS_RANGE;
     __host__ __device__ bool ranged() const { return rbegin || rend; }
     __host__ __device__ bool ranged_stats() const { return ranged() && rstats == RANGE_STATS_RANGE; }
+    // Signal windows (vbz_gpu_*_windows_batch; `row` stays NULL): read i owns rows wfirst[i] ... wfirst[i + 1] - 1 of the [wrows, chunk_len]
+    // arena at dst, row c holding the samples wstart[c] ... wstart[c] + chunk_len - 1 of the read's signal (its range, when ranged) and
+    // `pad` outside it.  The tables are the caller's (untrusted: the window check closes the gate of a read whose entries are not rows of
+    // the arena or whose starts decrease); entry wmap ? wmap[r] : r of wfirst is read r's (routed reads; POD5: per READ).
+    const uint64_t* wfirst = nullptr;
+    const int32_t* wstart = nullptr;
+    const uint32_t* wmap = nullptr;
+    uint64_t wrows = 0;
 };
+constexpr uint32_t WINDOW_READ_ROWS_MAX = 0x7FFFFFFFu;   // rows one read may own (the window check refuses more)
 
 // Signal trim (vbz_gpu_*_signal_trim_batch; the rule: include/vbz_gpu.h): behind the counting passes of a statistics call one more pass of
 // the svb decoder (OUT = SIG_TRIM) counts, window by window, the samples above thr = shift + f * scale in the first
@@ -249,6 +259,34 @@ struct Pod5Reads
     uint32_t* bad = nullptr;               // one word: != 0 when first_row is not a partition of the batch's rows
     uint2* range = nullptr;                // per read, a ranged call only: the clamped {b, e} of SignalOut's range (the plan writes them)
 };
+// Signal windows (SignalOut::wfirst), the launches in front of the decode.  b: the call's reads, or with pr.reads (a call over POD5 reads)
+// its rows, the tables of b.sig being per READ of pr.  w: scratch of the call, n words and n + 1 offsets for n reads.
+// launch_window_check (pack.hip): the window check.  Reads of a batch (pr.reads == NULL): cal[i] = {offset[i], scale[i]} as in
+// launch_chunk_slots, and a read whose gate is open and whose two wfirst entries are not rows of the arena (first > next, next > wrows,
+// more than WINDOW_READ_ROWS_MAX rows) gets gate[i] = E_DESTINATION_SIZE; POD5 reads: the plan has done that (POD5_READ_FAIL).  Then
+// w.scan = the exclusive scan of the passing reads' row counts, and a grid-stride pass over those rows closes every read that has a pair
+// start[c] > start[c + 1] among its rows (POD5: POD5_READ_FAIL, its rows' gates, its statistics finished).  No start is read before its
+// read's pair has passed.
+// launch_window_pad (svb_kernels.hip), behind it: the pad positions of every passing read's rows.
+struct WindowScratch
+{
+    uint32_t* count = nullptr;
+    uint64_t* scan = nullptr;
+};
+hipError_t launch_window_check(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, hipStream_t s);
+hipError_t launch_window_pad(const ReadBatch& b, const Pod5Reads& pr, const WindowScratch& w, hipStream_t s);
+// row j of the rows counted in scan (n + 1 offsets, scan[0] = 0 <= j < scan[n]) -> its read: the last k with scan[k] <= j
+__device__ inline uint32_t scan_find(const uint64_t* scan, uint32_t n, uint64_t j)
+{
+    uint32_t lo = 0, hi = n;   // scan[lo] <= j; scan[hi] > j or hi == n
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (scan[mid] <= j) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // *bad = whether first_row is bad (first entry not 0, a decreasing pair, last entry not n_rows); when it is and out != NULL (n_reads words:
 // read_result or read_samples), every out[k] = E_INPUT_SIZE
 hipError_t launch_pod5_reads_check(uint32_t n_rows, const Pod5Reads& pr, uint32_t* out, hipStream_t s);
@@ -260,8 +298,9 @@ hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_sam
 // constants (without b.sig.norm.st).  Launches: the plan (tables, checks, constants or the reads' starting windows), the counting passes
 // (one workgroup per read, its rows in turn), the store (one workgroup per row; none for the statistics alone, whose first counting
 // pass gives the rows' verdicts), the read results.  b.sig.rbegin / rend: per READ; pr.range must then be set (the plan fills it).
+// b.sig.wfirst (a window call; b.sig.row must be NULL): win must be set; the window check and the pad launch follow the plan.
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s, const TrimOut* trim = nullptr);
+                                     hipStream_t s, const TrimOut* trim = nullptr, const WindowScratch* win = nullptr);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
 // bounds the total segment count (the grid); seg_* are scratch arrays of max_segs entries.  Not for the nibble codec.
