@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <deque>
 #include <mutex>
 #include <string>
 #include <map>
@@ -19,6 +20,7 @@
 #include "../../include/vbz.h"
 #include "../../include/vbz_gpu.h"
 #include "vbz_kernels.h"
+#include "scratch_tables.h"
 
 using namespace vbzhip;
 
@@ -39,91 +41,197 @@ struct PendingEvent
     hipEvent_t start, stop;
 };
 
-struct DevBuf
+// ---- what a context holds: every object is freed by its owner's destructor and never copied (vbz_gpu_destroy deletes the context;
+// nothing is released from a list) ---------------------------------------------------------------------------------------------------
+template <class H, hipError_t (*Free)(H)>
+struct Owned
 {
-    void* p = nullptr;
+    H p = nullptr;
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    ~Owned() { release(); }
+    void release()
+    {
+        if (p) (void)Free(p);
+        p = nullptr;
+    }
+};
+typedef Owned<hipStream_t, hipStreamDestroy> OwnedStream;
+typedef Owned<hipEvent_t, hipEventDestroy> Event;   // (made without timing: make_event)
+static bool make_event(Event& e) { return e.p || hipEventCreateWithFlags(&e.p, hipEventDisableTiming) == hipSuccess; }
+
+template <hipError_t (*Free)(void*)>
+struct OwnedBytes : Owned<void*, Free>   // ... of cap bytes
+{
     size_t cap = 0;
+    void release()
+    {
+        Owned<void*, Free>::release();
+        cap = 0;
+    }
+};
+typedef OwnedBytes<hipFree> DevBuf;   // a device allocation that only grows (ensure)
+
+struct PinnedBuf : OwnedBytes<hipHostFree>   // a block of pinned host memory
+{
+    bool grow(size_t bytes, unsigned flags)   // (what it held is not kept)
+    {
+        if (bytes <= cap) return true;
+        release();
+        if (hipHostMalloc(&p, bytes, flags) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return false;
+        }
+        cap = bytes;
+        return true;
+    }
+    uint32_t* words() const { return (uint32_t*)p; }
 };
 
+struct TimingEvents   // the events of Timed: every one made, and those not in use
+{
+    std::deque<Event> all;   // (a deque: an owner is not moved)
+    std::vector<hipEvent_t> idle;
+    hipEvent_t get()
+    {
+        if (idle.empty()) {
+            all.emplace_back();
+            (void)hipEventCreate(&all.back().p);
+            return all.back().p;
+        }
+        hipEvent_t e = idle.back();
+        idle.pop_back();
+        return e;
+    }
+};
+
+// A second stream with its fork / join events: all three objects or none -- a context never keeps a stream without its events.
+// (FastSide is the plain view of them that the launchers take)
+struct OwnedSide
+{
+    OwnedStream stream;
+    Event fork, join;
+    bool create()
+    {
+        if (stream.p) return true;
+        if (hipStreamCreateWithFlags(&stream.p, hipStreamNonBlocking) == hipSuccess && make_event(fork) && make_event(join)) return true;
+        join.release(), fork.release(), stream.release();
+        return false;
+    }
+    FastSide view() const { return { stream.p, fork.p, join.p }; }
+};
+
+// A child context (its own stream and buffers, for a launch group that runs beside the parent's) with the events that fork it from the
+// parent's stream and join it again: the three are made together or the child is not kept
+static hipError_t destroy_child(vbz_gpu_ctx* c)
+{
+    vbz_gpu_destroy(c);
+    return hipSuccess;
+}
+struct Child
+{
+    Owned<vbz_gpu_ctx*, destroy_child> ctx;
+    Event fork, join;
+    bool create(int device)
+    {
+        if (ctx.p) return true;
+        ctx.p = vbz_gpu_create(device, nullptr);
+        if (ctx.p && make_event(fork) && make_event(join)) return true;
+        join.release(), fork.release(), ctx.release();
+        return false;
+    }
+    operator vbz_gpu_ctx*() const { return ctx.p; }
+    vbz_gpu_ctx* operator->() const { return ctx.p; }
+};
+
+// The settings of a context: read from the environment by vbz_gpu_create (README.md), three of them set by vbz_gpu_set_trailers /
+// _canonical / _checksum.  A child context gets its parent's by assignment before every call it takes part in (inherit_large,
+// inherit_half), so a setter reaches the routed reads and the upper halves by being a field here.
+struct Knobs
+{
+    bool routing = true;          // VBZ_HIP_ROUTING=0: by batch shape only
+    uint32_t split_min = 16384;   // VBZ_HIP_SPLIT_MIN: batches of this many reads and more are split (0: never)
+    // Canonical encoding (vbz_gpu_set_canonical / VBZ_HIP_CANONICAL=1): a read's compressed bytes are a function of the read, the options
+    // and the library version -- not of the batch it arrives in (see compress_canonical)
+    bool canonical = false;
+    bool staged_encode = true;    // VBZ_HIP_STAGED_ENCODE=0: the fused encoder kernel for every read
+    bool shared_tables = true;    // VBZ_HIP_SHARED_TABLES=0: large-read path, every span of the data bytes with a table of its own (round 4's frames)
+    bool fast_decode = true;      // VBZ_HIP_FAST_DECODE=0: every frame through the one-wavefront decoder
+    int ref_chains = 1;           // VBZ_HIP_REF_CHAINS: 0 their sequence chains are walked by the one-wavefront decoder itself, 1 walked ahead of
+                                  // it in calls of REF_MIN_READS reads and more, 2 in every call
+    bool trailers = true;         // decoder hints (checkpoints, span index) in skippable frames behind the zstd frame
+    bool checksum = false;        // vbz_gpu_set_checksum / VBZ_HIP_CHECKSUM=1: frames written with the content checksum (xxh64.hip)
+    int segmented = -1;           // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
+    bool zero_run_sequences = true;
+    bool long_repeats = true;     // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance
+    int phase_timing = 0;         // VBZ_HIP_PHASE_TIMING: 1 phase counters of the entropy kernels (one launch per frame), 2 / 3 of the encoder's planning / packing launch (staged, under load)
+    bool trace = false;           // VBZ_HIP_TRACE=1: synchronise after every launch group and name it on stderr (to find a faulting kernel)
+};
+
+// Members are destroyed last to first: the context's own stream is declared first, so everything that may be queued on it goes before it.
 struct vbz_gpu_ctx
 {
+    OwnedStream own_stream;
+    hipStream_t stream = nullptr;   // own_stream's, or the caller's (which is left alone)
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     std::string error;
+    Knobs knobs;
     DevBuf scratch;   // intermediate svb streams of a batch
-    DevBuf meta;      // per-read bookkeeping arrays
-    DevBuf gmeta;     // ... of one launch group (StageSlots)
-    DevBuf route;     // per-read routing: the first group's gates, the second group's compact descriptors
-    bool routing = true;   // VBZ_HIP_ROUTING=0: by batch shape only
-    vbz_gpu_ctx* large = nullptr;   // per-read routing: the second group's own stream and buffers (it runs beside the first group)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    DevBuf meta;      // the sized headers' tables (SizedTables)
+    DevBuf gmeta;     // per-read bookkeeping arrays of one launch group (StageSlots)
+    DevBuf route;     // per-read routing: the first group's gates, the second group's compact descriptors (RouteTables; CanonGates)
+    Child large;      // per-read routing: the second group's own stream and buffers (it runs beside the first group)
     // A large batch on the one-workgroup path is coded as TWO HALVES on two streams (split_batch): the upper half on this child context
-    vbz_gpu_ctx* half = nullptr;
-    hipEvent_t ev_hfork = nullptr, ev_hjoin = nullptr;
-    DevBuf splitmeta;          // the scratch plan of the whole batch (slot offsets, capacities, gates), shared by the two halves
-    uint32_t split_min = 16384;   // VBZ_HIP_SPLIT_MIN: batches of this many reads and more are split (0: never)
+    Child half;
+    DevBuf splitmeta;          // the scratch plan of the whole batch (slot offsets, capacities, gates), shared by the two halves (SplitTables)
     bool last_split = false;      // vbz_gpu_decode_paths: the last decompress call ran as halves
     // Frames of OTHER writers (every vbz file in existence: the reference's libzstd frames) decode on one wavefront each behind a chain walk
     // of fixed latency, and two halves of such a call do not run beside each other (482 GB/s as one group, 420 as halves); the host
     // does not know whose frames a call holds.  Every decompress call leaves the number of frames the batched decoder did not take in
     // pinned memory (a counting launch and a 4-byte copy behind the call, no wait); the NEXT call looks at it if it has arrived and runs
     // as one group when most frames were foreign.  A matter of speed only: the decoded bytes do not depend on it.
-    uint32_t* foreign_host = nullptr;   // pinned: [frames left to the one-wavefront decoder, frames looked at]
+    PinnedBuf foreign_host;   // [frames left to the one-wavefront decoder, frames looked at]
     DevBuf foreign_dev;
-    hipEvent_t ev_foreign = nullptr;
+    Event ev_foreign;
     bool foreign_pending = false, mostly_foreign = false;
     int foreign_state = -1;   // what the last call that was looked at held: -1 not known, 0 no foreign frame at all, 1 some
-    // Canonical encoding (vbz_gpu_set_canonical / VBZ_HIP_CANONICAL=1): a read's compressed bytes are a function of the read, the options
-    // and the library version -- not of the batch it arrives in (see compress_canonical)
-    bool canonical = false;
-    uint32_t* canon_host = nullptr;   // pinned: the classification's count comes back here
+    PinnedBuf canon_host;     // canonical encoding: the classification's count comes back here
     // single-buffer API staging
-    DevBuf one_in, one_out, one_meta;
+    DevBuf one_in, one_out;
     DevBuf dbg;       // per-read phase timers (VBZ_HIP_PHASE_TIMING=1)
     DevBuf seqtab;    // encoding tables of the predefined sequence distributions
     DevBuf seqdtab;   // decoding tables of the same distributions
-    DevBuf segmeta;   // segment / span tables of the large-read path
+    DevBuf segmeta;   // segment / span tables of the large-read path (SegTables)
     DevBuf spanmeta, spantmp;  // span tables and temporary slots of the entropy stage in the large-read path
     DevBuf vgate;     // verdicts on the caller's descriptor table (one word per read)
     DevBuf encplan;   // per-read plans of the staged encoder (tables of both regions: zstd_encode.hip STAGE 1 / 2)
-    bool staged_encode = true;  // VBZ_HIP_STAGED_ENCODE=0: the fused encoder kernel for every read
-    bool shared_tables = true;  // VBZ_HIP_SHARED_TABLES=0: large-read path, every span of the data bytes with a table of its own (round 4's frames)
     DevBuf fastmeta;  // per-frame descriptors, stream tasks and weights of the batched own-frame decoder (zstd_decode_fast.hip)
-    bool fast_decode = true;   // VBZ_HIP_FAST_DECODE=0: every frame through the one-wavefront decoder
     DevBuf refpre, reftab, refrecs;  // frames the reference wrote: per-frame hand-over, tables (large batches), records (zstd_decode_ref.hip)
     DevBuf reflits;                  // ... their literals decoded beside the walk (zstd_decode_fast.hip: ref_pieces_kernel)
     uint32_t last_lit_units = 0;     // (records per read the last call filled)
-    int ref_chains = 1;        // VBZ_HIP_REF_CHAINS: 0 their sequence chains are walked by the one-wavefront decoder itself, 1 walked ahead of
-                               // it in calls of REF_MIN_READS reads and more, 2 in every call
-    FastSide side;             // the walk's own stream (beside the launches for this library's frames)
+    OwnedSide side;            // the walk's own stream (beside the launches for this library's frames)
     bool last_walked = false;
     uint32_t last_frames = 0;  // vbz_gpu_decode_paths: the frames of the last zstd_frames call (0: none, or not on the batched path)
     uint32_t last_span_frames = 0;          // ... of the last call on the large-read path, and its redo[] (in spanmeta)
     const uint32_t* last_span_redo = nullptr;
-    bool trailers = true;      // decoder hints (checkpoints, span index) in skippable frames behind the zstd frame
-    bool checksum = false;     // vbz_gpu_set_checksum / VBZ_HIP_CHECKSUM=1: frames written with the content checksum (xxh64.hip)
     DevBuf cksum;              // the hashes of a compress launch group (8 bytes per read)
-    DevBuf sigmeta;            // typed decode: the int16 slot table and the per-read constants (signal_slots)
+    DevBuf sigmeta;            // typed decode: the int16 slot table and the per-read constants (TypedSlots), or the constants alone
     DevBuf chunkmeta;          // chunk layout: the per-read chunk counts
     DevBuf winmeta;            // signal windows: the per-read row counts and their scan (WindowScratch)
-    DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call
+    DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call (NormTables)
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
-    DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables (Pod5Reads), the reads' constants
+    DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables, the reads' constants (Pod5Tables)
+    // The state of the call in flight, handed to the children as it is (not a setting: outside Knobs)
     TrimOut trim;              // the signal trim of the decompress call in flight (begin == nullptr: none); every decompress call sets it,
                                // and the contexts of a batch's upper half and of the routed reads get theirs from it
-    int segmented = -1;  // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
-    bool zero_run_sequences = true;
-    bool long_repeats = true;  // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance
-    int phase_timing = 0;      // VBZ_HIP_PHASE_TIMING: 1 phase counters of the entropy kernels (one launch per frame), 2 / 3 of the encoder's planning / packing launch (staged, under load)
-    bool trace = false;        // VBZ_HIP_TRACE=1: synchronise after every launch group and name it on stderr (to find a faulting kernel)
-    void* pinned = nullptr;
-    size_t pinned_cap = 0;
-    uint32_t one_seq = 0;      // the single-buffer API's hand-back flag: a number per call (run_one)
     bool profiling = false;
+    PinnedBuf pinned;          // the single-buffer API's pinned area (run_one)
+    uint32_t one_seq = 0;      // the single-buffer API's hand-back flag: a number per call (run_one)
     std::vector<PendingEvent> pending;
     std::vector<ProfEntry> prof;
-    std::vector<hipEvent_t> event_pool;
+    TimingEvents events;
 };
 
 namespace {
@@ -144,9 +252,7 @@ bool ensure(vbz_gpu_ctx* c, DevBuf& b, size_t bytes)
     if (bytes <= b.cap) return true;
     if (b.p) {
         (void)hipStreamSynchronize(c->stream);  // earlier work may still use the old buffer
-        (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
+        b.release();
     }
     size_t want = bytes + bytes / 8 + 4096;
     hipError_t e = bytes > ((size_t)1 << 60) ? hipErrorOutOfMemory : hipMalloc(&b.p, want);
@@ -160,16 +266,19 @@ bool ensure(vbz_gpu_ctx* c, DevBuf& b, size_t bytes)
     return true;
 }
 
-hipEvent_t get_event(vbz_gpu_ctx* c)
+// A table of scratch_tables.h in a buffer: the table's carve measures, the buffer grows to that, the same carve places the arrays
+template <class T, class... D>
+bool ensure_carved(vbz_gpu_ctx* c, DevBuf& b, T& t, D... dims)
 {
-    if (!c->event_pool.empty()) {
-        hipEvent_t e = c->event_pool.back();
-        c->event_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
-    return e;
+    if (!ensure(c, b, t.carve(nullptr, dims...))) return false;
+    t.carve(b.p, dims...);
+    return true;
+}
+// ... and one array of n elements (nullptr: no memory)
+template <class T>
+T* ensure_array(vbz_gpu_ctx* c, DevBuf& b, size_t n)
+{
+    return ensure(c, b, array_bytes<T>(n)) ? reinterpret_cast<T*>(b.p) : nullptr;
 }
 
 struct Timed  // records a pair of events around one kernel launch when profiling is on
@@ -180,18 +289,18 @@ struct Timed  // records a pair of events around one kernel launch when profilin
     Timed(vbz_gpu_ctx* ctx, const char* n) : c(ctx), name(n)
     {
         if (c->profiling) {
-            start = get_event(c);
+            start = c->events.get();
             (void)hipEventRecord(start, c->stream);
         }
     }
     ~Timed()
     {
-        if (c->trace) {
+        if (c->knobs.trace) {
             const hipError_t e = hipStreamSynchronize(c->stream);
             fprintf(stderr, "vbz_hip trace: %s %s\n", name, e == hipSuccess ? "ok" : hipGetErrorString(e));
         }
         if (start) {
-            hipEvent_t stop = get_event(c);
+            hipEvent_t stop = c->events.get();
             (void)hipEventRecord(stop, c->stream);
             c->pending.push_back({ name, start, stop });
         }
@@ -214,8 +323,8 @@ void drain_profile(vbz_gpu_ctx* c)
                 break;
             }
         if (!found) c->prof.push_back({ p.name, 1, (double)ms });
-        c->event_pool.push_back(p.start);
-        c->event_pool.push_back(p.stop);
+        c->events.idle.push_back(p.start);
+        c->events.idle.push_back(p.stop);
     }
     c->pending.clear();
 }
@@ -224,11 +333,11 @@ void drain_profile(vbz_gpu_ctx* c)
 // per_role: the counters of the encoder's planning launch (VBZ_HIP_PHASE_TIMING=2), two wavefronts per read
 unsigned long long* dbg_begin(vbz_gpu_ctx* c, uint32_t n, bool per_role = false)
 {
-    if (!c->phase_timing) return nullptr;
+    if (!c->knobs.phase_timing) return nullptr;
     if (per_role) n *= 2;
-    if (!ensure(c, c->dbg, (size_t)n * PHASE_SLOTS * 8)) return nullptr;
-    (void)hipMemsetAsync(c->dbg.p, 0, (size_t)n * PHASE_SLOTS * 8, c->stream);
-    return (unsigned long long*)c->dbg.p;
+    unsigned long long* d = ensure_array<unsigned long long>(c, c->dbg, (size_t)n * PHASE_SLOTS);
+    if (d) (void)hipMemsetAsync(d, 0, (size_t)n * PHASE_SLOTS * 8, c->stream);
+    return d;
 }
 
 // VBZ_HIP_PHASE_TIMING=2: the planning launch's counters, two per read (one per role), averaged per role over the wavefronts that planned
@@ -343,44 +452,21 @@ constexpr uint64_t SMALL_BATCH_MIN_AVG = 64u << 10, SMALL_BATCH_MAX_BYTES = 96u 
 constexpr uint64_t TINY_DECODE_MIN_AVG = 8u << 10;
 constexpr uint32_t TINY_DECODE_MAX_READS = 64;
 
-// The context's second stream (the chain walk beside the launches for own frames; the shared-table spans beside the control-byte
-// spans): all three objects or none -- a context must never keep a stream without its events.
+// The context's second stream (the chain walk beside the launches for own frames; the shared-table spans beside the control-byte spans)
 bool ensure_side(vbz_gpu_ctx* c)
 {
-    if (c->side.stream) return true;
-    FastSide side;
-    const bool ok = hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&side.fork, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&side.join, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        const char* why = hipGetErrorString(hipGetLastError());
-        if (side.join) (void)hipEventDestroy(side.join);
-        if (side.fork) (void)hipEventDestroy(side.fork);
-        if (side.stream) (void)hipStreamDestroy(side.stream);
-        set_error(c, "second stream: %s", why);
-        return false;
-    }
-    c->side = side;
-    return true;
+    if (c->side.create()) return true;
+    set_error(c, "second stream: %s", hipGetErrorString(hipGetLastError()));
+    return false;
 }
 
 bool use_segments(const vbz_gpu_ctx* c, uint64_t raw_arena_bytes, uint32_t n, bool decode)
 {
-    if (c->segmented >= 0) return c->segmented != 0;
+    if (c->knobs.segmented >= 0) return c->knobs.segmented != 0;
     const uint64_t avg = raw_arena_bytes / n;
     return avg >= SEGMENTED_MIN_AVG || (avg >= SMALL_BATCH_MIN_AVG && raw_arena_bytes <= SMALL_BATCH_MAX_BYTES) ||
            (decode && n <= TINY_DECODE_MAX_READS && avg >= TINY_DECODE_MIN_AVG);
 }
-
-struct SegTables
-{
-    uint32_t* first = nullptr;  // [n + 1]
-    uint32_t* val = nullptr;    // [max_segs]
-    uint64_t* off = nullptr;    // [max_segs]
-    uint32_t* run = nullptr;    // [max_segs]
-    uint32_t* gate = nullptr;   // [n]: the input gate, plus E_OOM for reads whose segments do not fit the tables
-    uint32_t max_segs = 0;
-};
 
 // segment tables for a batch whose raw bytes span `raw_arena_bytes`; sizes (device) are the reads' raw byte counts
 // scratch (nullable): the group's scratch plan in the same launch (calls of up to 1024 reads: *scratch_done says whether it was)
@@ -392,14 +478,7 @@ int plan_segments(vbz_gpu_ctx* c, uint32_t n, const uint32_t* raw_size, const ui
         set_error(c, "batch too large for the segmented path");
         return -1;
     }
-    t->max_segs = (uint32_t)segs;
-    if (!ensure(c, c->segmeta, ((size_t)n + 1) * 8 + (size_t)segs * 16 + 256)) return -1;
-    MetaCarver mc(c->segmeta.p);
-    t->first = mc.take<uint32_t>((size_t)n + 1);
-    t->gate = mc.take<uint32_t>(n);
-    t->val = mc.take<uint32_t>(segs);
-    t->off = mc.take<uint64_t>(segs);
-    t->run = mc.take<uint32_t>(segs);
+    if (!ensure_carved(c, c->segmeta, *t, n, (uint32_t)segs)) return -1;
     Timed tm(c, "seg_plan");
     HIPCHK(c, launch_seg_plan(n, raw_size, unit, gate, t->max_segs, t->first, t->gate, scratch, c->stream), "seg_plan launch");
     if (scratch_done) *scratch_done = scratch != nullptr && n <= 1024;
@@ -436,16 +515,17 @@ struct Preplanned
 // checksum_content runs IN FRONT of the stage: the staged encoder rewrites the control bytes of an svb stream in its scratch slot in place.
 int checksum_content(vbz_gpu_ctx* c, const ReadBatch& z, const uint32_t* gate)
 {
-    if (!c->checksum || z.n_reads == 0) return 0;
-    if (!ensure(c, c->cksum, (size_t)z.n_reads * 8 + 64)) return -1;
+    if (!c->knobs.checksum || z.n_reads == 0) return 0;
+    uint64_t* const hashes = ensure_array<uint64_t>(c, c->cksum, z.n_reads);
+    if (!hashes) return -1;
     Timed t(c, "checksum");
-    HIPCHK(c, launch_xxh64_batch(z.src, z.src_off, z.src_size, gate, nullptr, z.n_reads, reinterpret_cast<uint64_t*>(c->cksum.p), c->stream), "xxh64 launch");
+    HIPCHK(c, launch_xxh64_batch(z.src, z.src_off, z.src_size, gate, nullptr, z.n_reads, hashes, c->stream), "xxh64 launch");
     return 0;
 }
 // ... and behind it: the frames get the flag and the checksum.  raw_size (nullable) + integer_size: what bounds the result.
 int checksum_frames(vbz_gpu_ctx* c, const ReadBatch& z, const uint32_t* gate, uint32_t hdr, const uint32_t* raw_size, uint32_t integer_size)
 {
-    if (!c->checksum || z.n_reads == 0) return 0;
+    if (!c->knobs.checksum || z.n_reads == 0) return 0;
     Timed t(c, "checksum");
     ReadBatch w = z;
     w.gate = gate;
@@ -461,26 +541,6 @@ int verify_checksums(vbz_gpu_ctx* c, const ReadBatch& z)
     HIPCHK(c, launch_xxh64_verify(z, c->stream), "checksum verify launch");
     return 0;
 }
-
-// The per-read arrays of a launch group's intermediate svb streams, carved from ctx->gmeta (base == nullptr: measure)
-struct StageSlots
-{
-    uint64_t* svb_off = nullptr;
-    uint32_t *svb_cap = nullptr, *svb_size = nullptr, *gate = nullptr;
-    uint32_t *deep_d = nullptr, *key_raw = nullptr, *gate2 = nullptr;   // encode: the matcher's distances, POD5's key sizes, the spans' gate
-    size_t carve(void* base, uint32_t n)
-    {
-        MetaCarver mc(base);
-        svb_off = mc.take<uint64_t>(n);
-        svb_cap = mc.take<uint32_t>(n);
-        svb_size = mc.take<uint32_t>(n);
-        gate = mc.take<uint32_t>(n);
-        deep_d = mc.take<uint32_t>(n);
-        key_raw = mc.take<uint32_t>(n);
-        gate2 = mc.take<uint32_t>(n);
-        return mc.bytes();
-    }
-};
 
 // What both kinds of launch group start with: the per-read arrays, on the large-read path the segment tables, and for both stages the
 // scratch that holds the svb streams between them -- its slots planned with the segments when they can be (two launches less for a call
@@ -508,8 +568,7 @@ int plan_stage_scratch(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* size
         p->scratch_need = (size_t)(((unsigned __int128)arena_bytes * p->num + p->den - 1) / p->den) + (size_t)n * 96 + 256;
         if (!pre && !ensure(c, c->scratch, p->scratch_need)) return -1;
     }
-    if (!ensure(c, c->gmeta, StageSlots().carve(nullptr, n))) return -1;
-    p->m.carve(c->gmeta.p, n);
+    if (!ensure_carved(c, c->gmeta, p->m, n)) return -1;
     p->scratch_base = pre ? pre->scratch : c->scratch.p;
     if (pre) {   // (both stages, one-workgroup path: what split_batch asks for) -- slots and gates planned once for the whole batch
         p->m.svb_off = pre->svb_off;
@@ -549,10 +608,10 @@ struct EncodeTiming
 EncodeTiming encode_timing(vbz_gpu_ctx* c, uint32_t n, bool segmented)
 {
     EncodeTiming t;
-    const int pt = segmented ? 0 : c->phase_timing;
+    const int pt = segmented ? 0 : c->knobs.phase_timing;
     t.per_role = pt == 2;
     t.counters = pt ? dbg_begin(c, n, t.per_role) : nullptr;
-    t.staged = !segmented && c->staged_encode && (!t.counters || pt == 2 || pt == 3) && c->zero_run_sequences;
+    t.staged = !segmented && c->knobs.staged_encode && (!t.counters || pt == 2 || pt == 3) && c->knobs.zero_run_sequences;
     (pt == 2 ? t.dbg.plan : pt == 3 ? t.dbg.pack : t.dbg.frame) = t.counters;
     t.label = pt == 3   ? "zstd_pack: setup region lookups+scan bits quads ends+headers sequences trailer"
               : pt == 2 ? "zstd_plan: setup tokeniser sequences hist store rest | sort merge leaves lengths codes+weights tree"
@@ -574,7 +633,7 @@ int entropy_encode_spans(vbz_gpu_ctx* c, ReadBatch z, ZstdEncodeArgs a, const Co
     // control-byte spans of 32-bit elements take as long as the table construction itself (a 40 MB buffer: 100 us in the first launch,
     // + 15 us counting + 34 us packing against 125 us for everything in one launch) -- they keep a table per span.
     // (canonical mode: whether the data bytes share a table must not follow from the call's size -- every span its own table)
-    w.shared_span_bytes = (c->shared_tables && !c->canonical && (o->integer_size == 1 || o->integer_size == 2)) ? zstd_span_shared_bytes(p.scratch_need) : 0u;
+    w.shared_span_bytes = (c->knobs.shared_tables && !c->knobs.canonical && (o->integer_size == 1 || o->integer_size == 2)) ? zstd_span_shared_bytes(p.scratch_need) : 0u;
     const size_t meta_bytes = zstd_span_meta_bytes(p.scratch_need, n, w.shared_span_bytes);
     if (!meta_bytes) {
         set_error(c, "batch too large for the span path");
@@ -584,9 +643,9 @@ int entropy_encode_spans(vbz_gpu_ctx* c, ReadBatch z, ZstdEncodeArgs a, const Co
     w.meta = c->spanmeta.p;
     w.tmp = (uint8_t*)c->spantmp.p;
     a.runs = { p.m.svb_cap, c->seqtab.p };
-    a.trailers = c->trailers;
+    a.trailers = c->knobs.trailers;
     z.gate = p.m.gate;
-    if (c->zero_run_sequences && c->long_repeats && o->integer_size != 0) {
+    if (c->knobs.zero_run_sequences && c->knobs.long_repeats && o->integer_size != 0) {
         // reads that repeat at one distance go to the one-wavefront matcher after all, whatever their length: a read that
         // cycles a template (the reference's own perf generator: vbz/perf/test_data_generator.h:61-67) is 15-30 x smaller as
         // matches than as spans of Huffman blocks, which is worth one wavefront's time on it (libzstd, the reference's
@@ -597,7 +656,7 @@ int entropy_encode_spans(vbz_gpu_ctx* c, ReadBatch z, ZstdEncodeArgs a, const Co
         HIPCHK(c, launch_zstd_encode_matcher(z, a, 0xFFFFFFFFu, p.m.gate, p.m.gate2, s), "zstd_encode (matcher) launch");
         z.gate = p.m.gate2;
     }
-    if (!c->zero_run_sequences) a.runs = ZeroRuns();
+    if (!c->knobs.zero_run_sequences) a.runs = ZeroRuns();
     Timed t(c, "zstd_encode");
     HIPCHK(c, launch_zstd_encode_spans(z, a, w, s), "zstd_encode (spans) launch");
     return 0;
@@ -609,8 +668,8 @@ int entropy_encode_reads(vbz_gpu_ctx* c, const ReadBatch& z, ZstdEncodeArgs a, c
 {
     {
         Timed t(c, "zstd_encode");
-        if (c->zero_run_sequences) a.runs = { p.m.svb_cap, c->seqtab.p };
-        a.trailers = c->trailers;
+        if (c->knobs.zero_run_sequences) a.runs = { p.m.svb_cap, c->seqtab.p };
+        a.trailers = c->knobs.trailers;
         a.deep_d = (matcher && !tm.counters) ? p.m.deep_d : nullptr;
         a.staged = tm.staged;
         a.dbg = tm.dbg;
@@ -655,14 +714,14 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
         if (checksum_content(c, rb, rb.gate) != 0) return -1;
         {
             Timed t(c, "zstd_encode");
-            za.trailers = c->trailers;
+            za.trailers = c->knobs.trailers;
             HIPCHK(c, launch_zstd_encode(rb, za, s), "zstd_encode launch");
         }
         return checksum_frames(c, rb, rb.gate, hdr, rb.src_size, 0);
     }
     // the long-repeat matcher (every level: the reference's libzstd matches at every level; its workspace is the top of the
     // destination slots)
-    const bool matcher = !segmented && c->zero_run_sequences && c->long_repeats;
+    const bool matcher = !segmented && c->knobs.zero_run_sequences && c->knobs.long_repeats;
     if (launch_stage_plan(c, n, rb.src_size, pre ? nullptr : rb.gate, p) != 0) return -1;
     const EncodeTiming tm = encode_timing(c, n, segmented);
     const bool pod5 = pod5_codec(o);
@@ -717,7 +776,7 @@ int zstd_frames(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_code, uint
     hipStream_t s = c->stream;
     Timed t(c, "zstd_decode");
     c->last_frames = 0;
-    if (!c->fast_decode) {
+    if (!c->knobs.fast_decode) {
         HIPCHK(c, launch_zstd_decode(z, toosmall_code, dbg, c->seqdtab.p, s), "zstd_decode launch");
         return 0;
     }
@@ -731,7 +790,7 @@ int zstd_frames(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_code, uint
     // (a workload that has shown no foreign frame does not launch the walk at all: the -- empty -- launch sits on a side stream, gets its
     // few wavefronts late when the device is full, and the launches behind the join wait for it; should foreign frames appear after all,
     // the one-wavefront decoder walks their chains itself for one call and the next call knows)
-    const bool walk = (c->ref_chains >= 2 || (c->ref_chains == 1 && n >= REF_MIN_READS)) && (c->foreign_state != 0 || c->ref_chains >= 2);
+    const bool walk = (c->knobs.ref_chains >= 2 || (c->knobs.ref_chains == 1 && n >= REF_MIN_READS)) && (c->foreign_state != 0 || c->knobs.ref_chains >= 2);
     const uint64_t recs_bytes = walk ? std::min<uint64_t>(((content_bytes >> 2) + (1ull << 20)) & ~15ull, 1ull << 30) : 0;
     if (walk && (!ensure(c, c->refpre, zstd_ref_pre_bytes(n)) || !ensure(c, c->reftab, zstd_ref_table_bytes(n)) || !ensure(c, c->refrecs, recs_bytes)))
         return -1;
@@ -755,22 +814,20 @@ int zstd_frames(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_code, uint
     a.ref.lits = lits ? c->reflits.p : nullptr;
     a.ref.lit_units = lit_units;
     a.dbg = dbg;
-    a.side = c->side;
+    a.side = c->side.view();
     HIPCHK(c, launch_zstd_decode_fast(z, a, s), "zstd_decode (batched) launch");
     c->last_walked = walk;
     c->last_frames = dbg ? 0 : n;
-    if (c->split_min != 0 && n >= c->split_min / 2 && !dbg) {   // (the context of a call that may be split: see foreign_host)
-        if (!c->foreign_host && (hipHostMalloc((void**)&c->foreign_host, 16, hipHostMallocDefault) != hipSuccess ||
-                                 hipEventCreateWithFlags(&c->ev_foreign, hipEventDisableTiming) != hipSuccess)) {
+    if (c->knobs.split_min != 0 && n >= c->knobs.split_min / 2 && !dbg) {   // (the context of a call that may be split: see foreign_host)
+        if (!c->foreign_host.p && !(c->foreign_host.grow(16, hipHostMallocDefault) && make_event(c->ev_foreign))) {   // (the words and their event, or neither)
             (void)hipGetLastError();
-            if (c->foreign_host) (void)hipHostFree(c->foreign_host);
-            c->foreign_host = nullptr;
+            c->foreign_host.release();
         }
-        if (c->foreign_host && !c->foreign_pending && ensure(c, c->foreign_dev, 16)) {
-            uint32_t* d = (uint32_t*)c->foreign_dev.p;
+        uint32_t* const d = (c->foreign_host.p && !c->foreign_pending) ? ensure_array<uint32_t>(c, c->foreign_dev, 4) : nullptr;
+        if (d) {
             if (launch_count_nonzero(zstd_fast_redo(c->fastmeta.p, n), n, d, s) == hipSuccess &&
-                hipMemcpyAsync(c->foreign_host, d, 4, hipMemcpyDeviceToHost, s) == hipSuccess && hipEventRecord(c->ev_foreign, s) == hipSuccess) {
-                c->foreign_host[1] = n;
+                hipMemcpyAsync(c->foreign_host.p, d, 4, hipMemcpyDeviceToHost, s) == hipSuccess && hipEventRecord(c->ev_foreign.p, s) == hipSuccess) {
+                c->foreign_host.words()[1] = n;
                 c->foreign_pending = true;
             } else {
                 (void)hipGetLastError();
@@ -835,8 +892,7 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     }
     const bool pod5 = pod5_codec(o);
     if (rb.sig.norm.st && segmented && !pod5) {   // (a normalising decode on the large-read path: the segments' counts add up here)
-        if (!ensure(c, c->normslab, (size_t)n * NORM_SLAB * 4)) return -1;
-        rb.sig.norm.slab = reinterpret_cast<uint32_t*>(c->normslab.p);
+        if (!(rb.sig.norm.slab = ensure_array<uint32_t>(c, c->normslab, (size_t)n * NORM_SLAB))) return -1;
     }
     StagePlan p;
     if (plan_stage_scratch(c, rb, rb.dst_cap, dst_bytes, o, false, segmented, pre, &p) != 0) return -1;
@@ -909,54 +965,77 @@ struct Routed
 
 bool routing_applies(const vbz_gpu_ctx* c, const CompressionOptions* o, uint64_t raw_arena_bytes, uint32_t n)
 {
-    return c->routing && c->segmented < 0 && n > 1 && o->integer_size != 0 && !half_codec(o) && raw_arena_bytes >= ROUTE_MIN_BYTES;
+    return c->knobs.routing && c->knobs.segmented < 0 && n > 1 && o->integer_size != 0 && !half_codec(o) && raw_arena_bytes >= ROUTE_MIN_BYTES;
 }
 
-// the second launch group's context (the large-read path beside the first group, on a stream of its own)
-int ensure_large(vbz_gpu_ctx* c)
+// One launch group beside the context's own, on a child's stream: the child's stream waits for what the context has queued so far ...
+int fork(vbz_gpu_ctx* c, const Child& k)
 {
-    if (!c->large) {
-        c->large = vbz_gpu_create(c->device, nullptr);
-        if (!c->large || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-            set_error(c, "could not create the context of the routed reads");
-            return -1;
-        }
-        c->large->routing = false;
-        c->large->split_min = 0;
+    HIPCHK(c, hipEventRecord(k.fork.p, c->stream), "event record");
+    HIPCHK(c, hipStreamWaitEvent(k->stream, k.fork.p, 0), "stream wait");
+    return 0;
+}
+// ... and the context's stream for what the child has queued: the child is done before anything enqueued behind the call runs
+int join(vbz_gpu_ctx* c, const Child& k)
+{
+    HIPCHK(c, hipEventRecord(k.join.p, k->stream), "event record");
+    HIPCHK(c, hipStreamWaitEvent(c->stream, k.join.p, 0), "stream wait");
+    return 0;
+}
+
+// What a child context works with.  Its settings are the parent's, whole (Knobs), with the few that make it the child it is; the state of
+// the call in flight is handed over beside them.  Against the field-by-field copies this replaces: a field that was not copied is read
+// from the environment alone (staged_encode, fast_decode, ref_chains, phase_timing, trace for `large`; phase_timing, trace for `half`),
+// so the parent holds what the child read for itself when it was made -- or the child never reads it: canonical and shared_tables on
+// `half` (compress_batch_impl and the span encoder read them; a half is a launch group on the one-workgroup path).
+// large: the routed reads, and canonical mode's large ones -- the large-read path, nothing routed or split again.
+int inherit_large(vbz_gpu_ctx* c)
+{
+    if (!c->large.create(c->device)) {
+        set_error(c, "could not create the context of the routed reads");
+        return -1;
     }
-    c->large->trailers = c->trailers;
-    c->large->zero_run_sequences = c->zero_run_sequences;
-    c->large->long_repeats = c->long_repeats;
-    c->large->shared_tables = c->shared_tables;
-    c->large->canonical = c->canonical;
-    c->large->checksum = c->checksum;
-    c->large->segmented = 1;
-    c->large->trim = c->trim;   // (the routed reads write begin through the routing map, as they do shift_scale)
+    vbz_gpu_ctx* k = c->large;
+    k->knobs = c->knobs;
+    k->knobs.routing = false;
+    k->knobs.split_min = 0;
+    k->knobs.segmented = 1;
+    k->trim = c->trim;   // (the routed reads write begin through the routing map, as they do shift_scale)
+    return 0;
+}
+// half: the upper half [n / 2, n) of a split call -- the one-workgroup path; it gets the call's profiling switch (its launches count under
+// the parent's labels: vbz_gpu_profile_read) and what is known of foreign frames.
+int inherit_half(vbz_gpu_ctx* c, uint32_t n)
+{
+    if (!c->half.create(c->device)) {
+        set_error(c, "could not create the context of a batch's upper half");
+        return -1;
+    }
+    vbz_gpu_ctx* k = c->half;
+    k->knobs = c->knobs;
+    k->knobs.routing = false;
+    k->knobs.split_min = 0;
+    k->knobs.segmented = 0;
+    k->profiling = c->profiling;
+    k->foreign_state = c->foreign_state;
+    k->trim = c->trim;   // (the upper half's begin entries: the table offset, as upper_half() offsets shift_scale)
+    if (k->trim.begin) k->trim.begin += n / 2;
     return 0;
 }
 
 int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed* r)
 {
     const uint32_t n = rb.n_reads;
-    if (ensure_large(c) != 0) return -1;
-    if (!ensure(c, c->route, (size_t)n * 4 + (size_t)ROUTE_MAX_READS * (64 + sizeof(NormRead)) + route_cand_words() * 4 + 512)) return -1;
-    MetaCarver mc(c->route.p);
-    r->gate_small = mc.take<uint32_t>(n);
+    if (inherit_large(c) != 0) return -1;
+    RouteTables tab;
+    if (!ensure_carved(c, c->route, tab, n, ROUTE_MAX_READS, route_cand_words())) return -1;
     RouteArgs a;
-    RoutedTable& l = a.large;
-    l.src_off = mc.take<uint64_t>(ROUTE_MAX_READS);
-    l.dst_off = mc.take<uint64_t>(ROUTE_MAX_READS);
-    l.src_size = mc.take<uint32_t>(ROUTE_MAX_READS);
-    l.dst_cap = mc.take<uint32_t>(ROUTE_MAX_READS);
-    l.gate = mc.take<uint32_t>(ROUTE_MAX_READS);
-    uint32_t* l_result = mc.take<uint32_t>(ROUTE_MAX_READS);
-    l.map = r->map = mc.take<uint32_t>(ROUTE_MAX_READS);
-    l.cal = mc.take<float2>(ROUTE_MAX_READS);
-    l.row = mc.take<uint64_t>(ROUTE_MAX_READS);
-    NormRead* l_norm = mc.take<NormRead>(ROUTE_MAX_READS);
-    l.count = r->count = mc.take<uint32_t>(4);
-    a.cand = mc.take<uint32_t>(route_cand_words());
+    a.large = tab.large;
+    a.cand = tab.cand;
+    const RoutedTable& l = a.large;
+    r->gate_small = tab.gate_small;
+    r->map = l.map;
+    r->count = l.count;
     r->large = rb;
     r->large.n_reads = ROUTE_MAX_READS;
     r->large.src_off = l.src_off;
@@ -964,11 +1043,11 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     r->large.dst_off = l.dst_off;
     r->large.dst_cap = l.dst_cap;
     r->large.gate = l.gate;
-    r->large.result = l_result;
+    r->large.result = tab.result;
     if (rb.sig.cal) r->large.sig.cal = l.cal;   // (the routed reads' constants, gathered through the map)
     if (rb.sig.row) r->large.sig.row = l.row;   // (and their first chunk rows)
     if (rb.sig.norm.st) {   // (a normalising decode: states of their own; shift_scale written back through the map)
-        r->large.sig.norm.st = l_norm;
+        r->large.sig.norm.st = tab.norm;
         r->large.sig.norm.map = r->map;
     }
     if (rb.sig.ranged()) r->large.sig.rmap = r->map;   // (their ranges: the call's tables, through the map)
@@ -980,18 +1059,14 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     a.max_bytes = ROUTE_MAX_BYTES;
     a.gate_small = r->gate_small;
     HIPCHK(c, launch_route_reads(rb, a, c->stream), "route launch");
-    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream), "event record");
-    HIPCHK(c, hipStreamWaitEvent(c->large->stream, c->ev_fork, 0), "stream wait");
-    return 0;
+    return fork(c, c->large);
 }
 
 // the second group is done before anything enqueued behind the call runs
 int route_join(vbz_gpu_ctx* c, const Routed& r, uint32_t* result)
 {
     HIPCHK(c, launch_route_results(r.large.result, r.map, r.count, ROUTE_MAX_READS, result, c->large->stream), "route results launch");
-    HIPCHK(c, hipEventRecord(c->ev_join, c->large->stream), "event record");
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0), "stream wait");
-    return 0;
+    return join(c, c->large);
 }
 
 
@@ -1006,7 +1081,7 @@ int route_join(vbz_gpu_ctx* c, const Routed& r, uint32_t* result)
 // bytes do not depend on its neighbours, so the output is what the unsplit call writes (tests/test_gpu_split.py: sha256).
 bool split_applies(const vbz_gpu_ctx* c, const CompressionOptions* o, uint32_t n)
 {
-    return c->split_min != 0 && n >= c->split_min && o->integer_size != 0 && o->zstd_compression_level != 0 && !half_codec(o) && !c->phase_timing && !c->trace;
+    return c->knobs.split_min != 0 && n >= c->knobs.split_min && o->integer_size != 0 && o->zstd_compression_level != 0 && !half_codec(o) && !c->knobs.phase_timing && !c->knobs.trace;
 }
 
 struct Split
@@ -1021,57 +1096,29 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
                bool one_sizes = false)
 {
     const uint32_t n = rb.n_reads;
-    if (!c->half) {
-        c->half = vbz_gpu_create(c->device, nullptr);
-        if (!c->half || hipEventCreateWithFlags(&c->ev_hfork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_hjoin, hipEventDisableTiming) != hipSuccess) {
-            set_error(c, "could not create the context of a batch's upper half");
-            return -1;
-        }
-        c->half->routing = false;
-        c->half->split_min = 0;
-        c->half->segmented = 0;
-    }
-    vbz_gpu_ctx* k = c->half;
-    k->trailers = c->trailers;
-    k->checksum = c->checksum;
-    k->zero_run_sequences = c->zero_run_sequences;
-    k->long_repeats = c->long_repeats;
-    k->staged_encode = c->staged_encode;
-    k->fast_decode = c->fast_decode;
-    k->ref_chains = c->ref_chains;
-    k->profiling = c->profiling;
-    k->foreign_state = c->foreign_state;
-    k->trim = c->trim;   // (the upper half's begin entries: the table offset, as upper_half() offsets shift_scale)
-    if (k->trim.begin) k->trim.begin += n / 2;
+    if (inherit_half(c, n) != 0) return -1;
     const size_t scratch_need = (size_t)(((unsigned __int128)raw_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
-    if (!ensure(c, c->scratch, scratch_need) || !ensure(c, c->splitmeta, (size_t)n * 20 + 256)) return -1;
-    MetaCarver mc(c->splitmeta.p);
-    uint64_t* svb_off = mc.take<uint64_t>(n);
-    uint32_t* svb_cap = mc.take<uint32_t>(n);
-    uint32_t* gate = mc.take<uint32_t>(n);
-    uint32_t* svb_size = mc.take<uint32_t>(n);
+    SplitTables tab;
+    if (!ensure(c, c->scratch, scratch_need) || !ensure_carved(c, c->splitmeta, tab, n)) return -1;
     hipStream_t s = c->stream;
-    if (rb.gate) HIPCHK(c, hipMemcpyAsync(gate, rb.gate, 4ull * n, hipMemcpyDeviceToDevice, s), "gate copy");
+    if (rb.gate) HIPCHK(c, hipMemcpyAsync(tab.gate, rb.gate, 4ull * n, hipMemcpyDeviceToDevice, s), "gate copy");
     {
         Timed t(c, "plan_scratch");
-        HIPCHK(c, launch_plan_scratch(n, raw_size, num, den, c->scratch.cap, svb_off, svb_cap, gate, rb.gate != nullptr, s), "plan launch");
+        HIPCHK(c, launch_plan_scratch(n, raw_size, num, den, c->scratch.cap, tab.svb_off, tab.svb_cap, tab.gate, rb.gate != nullptr, s), "plan launch");
     }
     sp->h = n / 2;
     sp->lo.scratch = sp->hi.scratch = c->scratch.p;
-    sp->lo.svb_off = svb_off;
-    sp->lo.svb_cap = svb_cap;
-    sp->lo.gate = gate;
-    sp->hi.svb_off = svb_off + sp->h;
-    sp->hi.svb_cap = svb_cap + sp->h;
-    sp->hi.gate = gate + sp->h;
+    sp->lo.svb_off = tab.svb_off;
+    sp->lo.svb_cap = tab.svb_cap;
+    sp->lo.gate = tab.gate;
+    sp->hi.svb_off = tab.svb_off + sp->h;
+    sp->hi.svb_cap = tab.svb_cap + sp->h;
+    sp->hi.gate = tab.gate + sp->h;
     if (one_sizes) {
-        sp->lo.svb_size = svb_size;
-        sp->hi.svb_size = svb_size + sp->h;
+        sp->lo.svb_size = tab.svb_size;
+        sp->hi.svb_size = tab.svb_size + sp->h;
     }
-    HIPCHK(c, hipEventRecord(c->ev_hfork, s), "event record");
-    HIPCHK(c, hipStreamWaitEvent(k->stream, c->ev_hfork, 0), "stream wait");
-    return 0;
+    return fork(c, c->half);
 }
 
 ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
@@ -1099,8 +1146,7 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
 // the upper half's stream is joined whatever happened in between (it may still be writing the caller's arenas)
 int split_join(vbz_gpu_ctx* c)
 {
-    HIPCHK(c, hipEventRecord(c->ev_hjoin, c->half->stream), "event record");
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_hjoin, 0), "stream wait");
+    if (join(c, c->half) != 0) return -1;
     if (c->error.empty() && !c->half->error.empty()) c->error = c->half->error;
     return 0;
 }
@@ -1154,34 +1200,28 @@ int compress_canonical(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t src_bytes, 
 {
     const uint32_t n = rb.n_reads;
     hipStream_t s = c->stream;
-    if (!c->canon_host && hipHostMalloc((void**)&c->canon_host, 16, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!c->canon_host.grow(16, hipHostMallocDefault)) {
         set_error(c, "pinned word for the canonical classification");
         return -1;
     }
-    if (!ensure(c, c->route, (size_t)n * 8 + 64)) return -1;
-    MetaCarver mc(c->route.p);
-    uint32_t* counts = mc.take<uint32_t>(4);
-    uint32_t* gate_small = mc.take<uint32_t>(n);
-    uint32_t* gate_large = mc.take<uint32_t>(n);
-    HIPCHK(c, launch_canon_classify(n, rb.src_size, rb.gate, CANON_LARGE_BYTES, gate_small, gate_large, counts, s), "classify launch");
-    HIPCHK(c, hipMemcpyAsync(c->canon_host, counts, 8, hipMemcpyDeviceToHost, s), "count copy");
+    CanonGates g;
+    if (!ensure_carved(c, c->route, g, n)) return -1;
+    HIPCHK(c, launch_canon_classify(n, rb.src_size, rb.gate, CANON_LARGE_BYTES, g.gate_small, g.gate_large, g.counts, s), "classify launch");
+    HIPCHK(c, hipMemcpyAsync(c->canon_host.p, g.counts, 8, hipMemcpyDeviceToHost, s), "count copy");
     HIPCHK(c, hipStreamSynchronize(s), "stream synchronize");
-    const uint32_t nbig = c->canon_host[0];
+    const uint32_t nbig = c->canon_host.words()[0];
     const bool split = split_applies(c, o, n);
     if (nbig == 0) return split ? compress_split(c, rb, src_bytes, o, sized) : compress_group(c, rb, src_bytes, o, sized, false);
     if (nbig == n) return compress_group(c, rb, src_bytes, o, sized, true);
-    if (ensure_large(c) != 0) return -1;
-    HIPCHK(c, hipEventRecord(c->ev_fork, s), "event record");
-    HIPCHK(c, hipStreamWaitEvent(c->large->stream, c->ev_fork, 0), "stream wait");
+    if (inherit_large(c) != 0 || fork(c, c->large) != 0) return -1;
     ReadBatch small = rb, large = rb;
-    small.gate = gate_small;
-    large.gate = gate_large;
+    small.gate = g.gate_small;
+    large.gate = g.gate_large;
     int rc = 0;   // (as in compress_batch_impl: the second stream is joined whatever happens)
     if (compress_group(c->large, large, src_bytes, o, sized, true) != 0) rc = -1;
     if (rc == 0 && (split ? compress_split(c, small, src_bytes, o, sized) : compress_group(c, small, src_bytes, o, sized, false)) != 0) rc = -1;
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
-    if (hipEventRecord(c->ev_join, c->large->stream) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) rc = -1;
+    if (join(c, c->large) != 0) rc = -1;
     return rc;
 }
 
@@ -1189,8 +1229,8 @@ int compress_canonical(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t src_bytes, 
 // other kernel forms an address from them; the verdicts are the gate every launch group of the call starts from.
 int validate_descriptors(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, ReadBatch* rb)
 {
-    if (!ensure(c, c->vgate, (size_t)bt->n_reads * 4 + 64)) return -1;
-    uint32_t* g = reinterpret_cast<uint32_t*>(c->vgate.p);
+    uint32_t* g = ensure_array<uint32_t>(c, c->vgate, bt->n_reads);
+    if (!g) return -1;
     HIPCHK(c, launch_validate_batch(bt->n_reads, bt->src_off, bt->src_size, bt->src_bytes, bt->dst_off, bt->dst_cap, bt->dst_bytes, g, c->stream), "validate launch");
     rb->gate = g;
     return 0;
@@ -1219,7 +1259,7 @@ int compress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressi
     if (n == 0) return 0;
     ReadBatch rb = to_rb(bt);
     if (!own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
-    if (c->canonical && c->segmented < 0 && o->integer_size != 0 && o->zstd_compression_level != 0 && !half_codec(o))
+    if (c->knobs.canonical && c->knobs.segmented < 0 && o->integer_size != 0 && o->zstd_compression_level != 0 && !half_codec(o))
         return compress_canonical(c, rb, bt->src_bytes, o, sized);
     const bool by_shape = o->integer_size != 0 && !half_codec(o) && use_segments(c, bt->src_bytes, n, false);
     const bool split = !by_shape && split_applies(c, o, n);
@@ -1491,17 +1531,15 @@ static_assert(SIG_F32 == VBZ_GPU_SIGNAL_F32 && SIG_F16 == VBZ_GPU_SIGNAL_F16 && 
 int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_format* f, ReadBatch* rb, uint64_t* dst_bytes, float2** cal)
 {
     const uint32_t n = bt->n_reads, elem = f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u;
-    if (!ensure(c, c->sigmeta, (size_t)n * 20 + 256)) return -1;
-    MetaCarver mc(c->sigmeta.p);
-    uint64_t* off16 = mc.take<uint64_t>(n);
-    uint32_t* cap16 = mc.take<uint32_t>(n);
-    *cal = mc.take<float2>(n);
+    TypedSlots m;
+    if (!ensure_carved(c, c->sigmeta, m, n)) return -1;
+    *cal = m.cal;
     Timed t(c, "signal_slots");
-    HIPCHK(c, launch_signal_slots(n, bt->dst_off, bt->dst_cap, elem, f->offset, f->scale, off16, cap16, *cal, reinterpret_cast<uint32_t*>(c->vgate.p),
+    HIPCHK(c, launch_signal_slots(n, bt->dst_off, bt->dst_cap, elem, f->offset, f->scale, m.off16, m.cap16, m.cal, reinterpret_cast<uint32_t*>(c->vgate.p),
                                   c->stream),
            "signal slots launch");
-    rb->dst_off = off16;
-    rb->dst_cap = cap16;
+    rb->dst_off = m.off16;
+    rb->dst_cap = m.cap16;
     *dst_bytes = bt->dst_bytes / elem * 2u;
     return 0;
 }
@@ -1513,17 +1551,13 @@ int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_f
 // any other launch of the call (out: read_result or read_samples, nullable -- E_INPUT_SIZE in every entry when the table is bad)
 int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* reads, uint32_t* out, Pod5Reads* pr, float2** cal)
 {
-    const uint32_t R = reads->n_reads;
-    if (!ensure(c, c->pod5meta, (size_t)n_rows * sizeof(Pod5Row) + (size_t)R * (sizeof(Pod5Read) + 16) + 256)) return -1;
-    MetaCarver mc(c->pod5meta.p);
-    pr->n_reads = R;
+    Pod5Tables tab;
+    if (!ensure_carved(c, c->pod5meta, tab, n_rows, reads->n_reads)) return -1;
+    *pr = tab.pr;
+    *cal = tab.cal;
+    pr->n_reads = reads->n_reads;
     pr->first_row = reads->first_row;
     pr->read_result = reads->read_result;
-    pr->bad = mc.take<uint32_t>(4);
-    pr->rows = mc.take<Pod5Row>(n_rows);
-    pr->reads = mc.take<Pod5Read>(R);
-    *cal = mc.take<float2>(R);
-    pr->range = mc.take<uint2>(R);
     Timed t(c, "pod5_reads_check");
     HIPCHK(c, launch_pod5_reads_check(n_rows, *pr, out, c->stream), "pod5 reads check launch");
     return 0;
@@ -1553,18 +1587,14 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     WindowScratch wscratch;
     if (windows) {
         window_out(out->win, out->win_out, &rb);
-        if (!ensure(c, c->winmeta, (size_t)n_const * 12 + 256)) return -1;
-        MetaCarver mc(c->winmeta.p);
-        wscratch.scan = mc.take<uint64_t>((size_t)n_const + 1);
-        wscratch.count = mc.take<uint32_t>(n_const);
+        if (!ensure_carved(c, c->winmeta, wscratch, n_const)) return -1;
     } else if (chunks) {
         chunk_out(out->ch, out->chunk_first, out->chunks, &rb);
     }
     if (out && !chunks && !stats) {   // typed slots (of POD5 rows too)
         if (signal_slots(c, bt, out->f, &rb, &dst_bytes, &cal) != 0) return -1;
     } else if (out && !reads) {   // the int16 layout as it is; the constants' table is chunk_slots' or the selects' to fill
-        if (!ensure(c, c->sigmeta, (size_t)n * 8 + 256)) return -1;
-        cal = reinterpret_cast<float2*>(c->sigmeta.p);
+        if (!(cal = ensure_array<float2>(c, c->sigmeta, n))) return -1;
     }
     if (reads) cal = read_cal;
     if (out) {
@@ -1578,32 +1608,20 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         }
     }
     if (out && out->norm) {
-        if (!ensure(c, c->normmeta, (size_t)n_const * (sizeof(NormRead) + 8) + 256)) return -1;
-        MetaCarver mc(c->normmeta.p);
-        NormRead* st = mc.take<NormRead>(n_const);
-        float2* ss = mc.take<float2>(n_const);   // (the caller passed no shift_scale: a table of the call's own)
-        rb.sig.norm = norm_out(out->norm, st, out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : ss);
+        NormTables t;   // (ss: for a caller that passed no shift_scale)
+        if (!ensure_carved(c, c->normmeta, t, n_const)) return -1;
+        rb.sig.norm = norm_out(out->norm, t.st, out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : t.ss);
     }
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
-        uint64_t* pay_off;
-        uint32_t *pay_size, *orig_size, *gate;
-        auto carve = [&](void* base) {
-            MetaCarver mc(base);
-            pay_off = mc.take<uint64_t>(n);
-            pay_size = mc.take<uint32_t>(n);
-            orig_size = mc.take<uint32_t>(n);
-            gate = mc.take<uint32_t>(n);
-            return mc.bytes();
-        };
-        if (!ensure(c, c->meta, carve(nullptr))) return -1;
-        carve(c->meta.p);
+        SizedTables h;
+        if (!ensure_carved(c, c->meta, h, n)) return -1;
         Timed t(c, "parse_sized");
-        HIPCHK(c, launch_parse_sized(n, rb.src, bt->src_off, bt->src_size, rb.dst_cap, rb.gate, pay_off, pay_size, orig_size, gate, s),
+        HIPCHK(c, launch_parse_sized(n, rb.src, bt->src_off, bt->src_size, rb.dst_cap, rb.gate, h.pay_off, h.pay_size, h.orig_size, h.gate, s),
                "parse_sized launch");
-        rb.src_off = pay_off;
-        rb.src_size = pay_size;
-        rb.dst_cap = orig_size;
-        rb.gate = gate;
+        rb.src_off = h.pay_off;
+        rb.src_size = h.pay_size;
+        rb.dst_cap = h.orig_size;
+        rb.gate = h.gate;
     }
     if (windows && !reads) {   // (the window check, and the pad, which wants the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "window_slots");
@@ -1616,9 +1634,10 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
                "chunk slots launch");
     }
     const bool by_shape = n != 0 && o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
-    if (c->foreign_pending && hipEventQuery(c->ev_foreign) == hipSuccess) {   // what the call before this one found (see foreign_host)
-        c->mostly_foreign = 2ull * c->foreign_host[0] > c->foreign_host[1];
-        c->foreign_state = c->foreign_host[0] != 0 ? 1 : 0;
+    if (c->foreign_pending && hipEventQuery(c->ev_foreign.p) == hipSuccess) {   // what the call before this one found (see foreign_host)
+        const uint32_t* const found = c->foreign_host.words();
+        c->mostly_foreign = 2ull * found[0] > found[1];
+        c->foreign_state = found[0] != 0 ? 1 : 0;
         c->foreign_pending = false;
     } else if (c->foreign_pending) {
         (void)hipGetLastError();   // (hipErrorNotReady is not an error to leave behind)
@@ -1750,21 +1769,21 @@ vbz_gpu_ctx* vbz_gpu_create(int device, void* stream)
     // The knobs of the shipped library (README.md): every one selects between paths the suites run.  The timed kernel
     // instantiations are compiled into the experiments build only (-DVBZ_EXPERIMENTS: lib/libvbz_hip_x.so, for tools/);
     // here VBZ_HIP_PHASE_TIMING does nothing.
-    if (const char* e = getenv("VBZ_HIP_TRACE")) c->trace = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_ZERO_RUN_SEQUENCES")) c->zero_run_sequences = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_LONG_REPEATS")) c->long_repeats = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_FAST_DECODE")) c->fast_decode = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_REF_CHAINS")) c->ref_chains = atoi(e);
-    if (const char* e = getenv("VBZ_HIP_STAGED_ENCODE")) c->staged_encode = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_SHARED_TABLES")) c->shared_tables = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_ROUTING")) c->routing = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_SEGMENTED")) c->segmented = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_TRAILERS")) c->trailers = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_CANONICAL")) c->canonical = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_CHECKSUM")) c->checksum = atoi(e) != 0;
-    if (const char* e = getenv("VBZ_HIP_SPLIT_MIN")) c->split_min = (uint32_t)strtoul(e, nullptr, 10);   // 0: a batch is never coded as two halves
+    if (const char* e = getenv("VBZ_HIP_TRACE")) c->knobs.trace = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_ZERO_RUN_SEQUENCES")) c->knobs.zero_run_sequences = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_LONG_REPEATS")) c->knobs.long_repeats = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_FAST_DECODE")) c->knobs.fast_decode = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_REF_CHAINS")) c->knobs.ref_chains = atoi(e);
+    if (const char* e = getenv("VBZ_HIP_STAGED_ENCODE")) c->knobs.staged_encode = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_SHARED_TABLES")) c->knobs.shared_tables = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_ROUTING")) c->knobs.routing = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_SEGMENTED")) c->knobs.segmented = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_TRAILERS")) c->knobs.trailers = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_CANONICAL")) c->knobs.canonical = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_CHECKSUM")) c->knobs.checksum = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_SPLIT_MIN")) c->knobs.split_min = (uint32_t)strtoul(e, nullptr, 10);   // 0: a batch is never coded as two halves
 #ifdef VBZ_EXPERIMENTS
-    if (const char* e = getenv("VBZ_HIP_PHASE_TIMING")) c->phase_timing = atoi(e);   // timed instantiations of the entropy kernels
+    if (const char* e = getenv("VBZ_HIP_PHASE_TIMING")) c->knobs.phase_timing = atoi(e);   // timed instantiations of the entropy kernels
 #endif
     {
         std::vector<uint8_t> host(seq_tables_bytes());
@@ -1787,13 +1806,13 @@ vbz_gpu_ctx* vbz_gpu_create(int device, void* stream)
     if (stream) {
         c->stream = (hipStream_t)stream;
     } else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+        if (hipStreamCreateWithFlags(&c->own_stream.p, hipStreamNonBlocking) != hipSuccess) {
             set_error(nullptr, "hipStreamCreate failed");
-            c->stream = nullptr;
+            c->own_stream.p = nullptr;
             vbz_gpu_destroy(c);  // frees the uploaded tables as well
             return nullptr;
         }
-        c->own_stream = true;
+        c->stream = c->own_stream.p;
     }
     return c;
 }
@@ -1803,43 +1822,22 @@ void vbz_gpu_destroy(vbz_gpu_ctx* c)
     if (!c) return;
     DeviceGuard dg(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& p : c->pending) {
-        (void)hipEventDestroy(p.start);
-        (void)hipEventDestroy(p.stop);
-    }
-    for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (DevBuf* b : { &c->scratch, &c->meta, &c->gmeta, &c->route, &c->one_in, &c->one_out, &c->one_meta, &c->dbg, &c->seqtab, &c->seqdtab, &c->segmeta, &c->spanmeta, &c->spantmp, &c->fastmeta, &c->vgate, &c->encplan, &c->refpre, &c->reftab, &c->refrecs, &c->reflits, &c->splitmeta, &c->foreign_dev, &c->cksum, &c->sigmeta, &c->chunkmeta, &c->winmeta, &c->normmeta, &c->normslab, &c->pod5meta })
-        if (b->p) (void)hipFree(b->p);
-    if (c->large) vbz_gpu_destroy(c->large);
-    if (c->half) vbz_gpu_destroy(c->half);
-    for (hipEvent_t e : { c->ev_hfork, c->ev_hjoin })
-        if (e) (void)hipEventDestroy(e);
-    if (c->side.fork) (void)hipEventDestroy(c->side.fork);
-    if (c->side.join) (void)hipEventDestroy(c->side.join);
-    if (c->side.stream) (void)hipStreamDestroy(c->side.stream);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->canon_host) (void)hipHostFree(c->canon_host);
-    if (c->foreign_host) (void)hipHostFree(c->foreign_host);
-    if (c->ev_foreign) (void)hipEventDestroy(c->ev_foreign);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // (every member frees what it holds, the children and then the stream last: see vbz_gpu_ctx)
 }
 
 void* vbz_gpu_stream(vbz_gpu_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 void vbz_gpu_set_trailers(vbz_gpu_ctx* c, int enable)
 {
-    if (c) c->trailers = enable != 0;
+    if (c) c->knobs.trailers = enable != 0;
 }
 void vbz_gpu_set_canonical(vbz_gpu_ctx* c, int enable)
 {
-    if (c) c->canonical = enable != 0;
+    if (c) c->knobs.canonical = enable != 0;
 }
 void vbz_gpu_set_checksum(vbz_gpu_ctx* c, int enable)
 {
-    if (c) c->checksum = enable != 0;
+    if (c) c->knobs.checksum = enable != 0;
 }
 const char* vbz_gpu_last_error(vbz_gpu_ctx* c) { return c ? c->error.c_str() : "no context"; }
 
@@ -1886,9 +1884,10 @@ int vbz_gpu_chunk_layout_batch(vbz_gpu_ctx* c, uint32_t n, const uint32_t* sampl
         set_error(c, "a table of the chunk layout call is NULL");
         return -2;
     }
-    if (!ensure(c, c->chunkmeta, (size_t)n * 4 + 64)) return -1;
+    uint32_t* const counts = ensure_array<uint32_t>(c, c->chunkmeta, n);
+    if (!counts) return -1;
     Timed t(c, "chunk_layout");
-    HIPCHK(c, launch_chunk_layout(n, samples, ch->chunk_len, ch->step, reinterpret_cast<uint32_t*>(c->chunkmeta.p), chunk_first, c->stream),
+    HIPCHK(c, launch_chunk_layout(n, samples, ch->chunk_len, ch->step, counts, chunk_first, c->stream),
            "chunk layout launch");
     HIPCHK(c, launch_chunk_info(n, samples, ch->chunk_len, ch->step, ch->mode, ch->end_align, chunk_first, chunk_info, info_cap, c->stream),
            "chunk info launch");
@@ -2118,7 +2117,7 @@ int vbz_gpu_zstd_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const u
     ZstdEncodeArgs a;
     a.key.orig_size = bt->src_size;
     a.key.key_bytes = key_bytes;
-    a.trailers = c->trailers;
+    a.trailers = c->knobs.trailers;
     HIPCHK(c, launch_zstd_encode(to_rb(bt), a, c->stream), "zstd_encode launch");
     return checksum_frames(c, to_rb(bt), nullptr, 0, nullptr, 0);
 }
@@ -2251,8 +2250,7 @@ VBZ_EXPORT int vbz_gpu_x_svb_handover(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, v
     svb_factor(2, true, &num, &den);
     const size_t scratch_need = (size_t)(((unsigned __int128)bt->src_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
     StageSlots m;
-    if (!ensure(c, c->scratch, scratch_need) || !ensure(c, c->meta, m.carve(nullptr, n)) || !ensure(c, c->encplan, zstd_encode_plan_bytes(n))) return -1;
-    m.carve(c->meta.p, n);
+    if (!ensure(c, c->scratch, scratch_need) || !ensure_carved(c, c->meta, m, n) || !ensure(c, c->encplan, zstd_encode_plan_bytes(n))) return -1;
     uint64_t* const svb_off = m.svb_off;
     uint32_t *const svb_cap = m.svb_cap, *const svb_size = m.svb_size, *const gate = m.gate;
     HIPCHK(c, launch_plan_scratch(n, bt->src_size, num, den, c->scratch.cap, svb_off, svb_cap, gate, false, s), "plan launch");
@@ -2335,7 +2333,7 @@ int vbz_gpu_decode_literals_ahead(vbz_gpu_ctx* c)
             (void)hipGetLastError();
             return -1;
         }
-        if (k->trace) {   // per block ordinal: units the scan made, units whose literals stand
+        if (k->knobs.trace) {   // per block ordinal: units the scan made, units whose literals stand
             std::vector<uint32_t> sk((size_t)k->last_frames * per);
             if (hipMemcpy(sk.data(), zstd_ref_lit_skip(k->reflits.p, k->last_frames), 4 * sk.size(), hipMemcpyDeviceToHost) == hipSuccess)
                 for (uint32_t u = 0; u < per; ++u) {
@@ -2374,7 +2372,7 @@ static int decode_paths_one(vbz_gpu_ctx* c, uint32_t* batched, uint32_t* walked)
         nb += redo[i] == 0;
         if (!pre.empty()) nw += pre[i].ok != 0;
     }
-    if (c->trace && !pre.empty()) {  // why frames of other writers were left to the one-wavefront decoder (zstd_decode_ref.hip: BAIL)
+    if (c->knobs.trace && !pre.empty()) {  // why frames of other writers were left to the one-wavefront decoder (zstd_decode_ref.hip: BAIL)
         std::map<uint32_t, uint32_t> why;
         for (uint32_t i = 0; i < n; ++i)
             if (redo[i] && !pre[i].ok) ++why[pre[i].why];
@@ -2541,20 +2539,10 @@ vbz_size_t run_one(bool compress, const void* src, vbz_size_t src_size, void* ds
     const uint32_t out_cap = small_out ? (compress ? dev_cap : dst_cap) : 0u;
     const size_t pin_need = out_off + 64 + out_cap + 64;
     if (!ensure(c, c->one_in, (size_t)src_size + 512) || !ensure(c, c->one_out, (size_t)dev_cap + 64)) return VBZ_OUT_OF_MEMORY_ERROR;
-    if (c->pinned_cap < pin_need) {
-        if (c->pinned) (void)hipHostFree(c->pinned);
-        c->pinned = nullptr;
-        c->pinned_cap = 0;
-        const size_t want = std::max<size_t>(pin_need, 1u << 20);
-        // (host-coherent: the hand-back flag is polled while the kernel that raises it may still be running)
-        if (hipHostMalloc(&c->pinned, want, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-            (void)hipGetLastError();
-            c->pinned = nullptr;
-            return VBZ_OUT_OF_MEMORY_ERROR;
-        }
-        c->pinned_cap = want;
-    }
-    uint8_t* pin = (uint8_t*)c->pinned;
+    // (host-coherent: the hand-back flag is polled while the kernel that raises it may still be running)
+    if (c->pinned.cap < pin_need && !c->pinned.grow(std::max<size_t>(pin_need, 1u << 20), hipHostMallocCoherent | hipHostMallocMapped))
+        return VBZ_OUT_OF_MEMORY_ERROR;
+    uint8_t* pin = (uint8_t*)c->pinned.p;
     OneMeta* hm = (OneMeta*)pin;
     hm->src_off = 0;
     hm->dst_off = 0;

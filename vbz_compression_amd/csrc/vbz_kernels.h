@@ -270,8 +270,15 @@ struct Pod5Reads
 // launch_window_pad (svb_kernels.hip), behind it: the pad positions of every passing read's rows.
 struct WindowScratch
 {
-    uint32_t* count = nullptr;
-    uint64_t* scan = nullptr;
+    uint32_t* count = nullptr;   // [n]
+    uint64_t* scan = nullptr;    // [n + 1]
+    size_t carve(void* base, uint32_t n)   // (host only; base == nullptr measures: scratch_tables.h)
+    {
+        MetaCarver mc(base);
+        scan = mc.take<uint64_t>((size_t)n + 1);
+        count = mc.take<uint32_t>(n);
+        return mc.bytes();
+    }
 };
 hipError_t launch_window_check(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, hipStream_t s);
 hipError_t launch_window_pad(const ReadBatch& b, const Pod5Reads& pr, const WindowScratch& w, hipStream_t s);
