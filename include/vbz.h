@@ -31,6 +31,8 @@
  *     a libzstd built with ZSTD_LEGACY_SUPPORT also decodes, are VBZ_ZSTD_ERROR here (no vbz writer ever produced them;
  *     32 files of the reference's fuzz corpus start with the v0.7 magic).  A frame may carry a Dictionary_ID field of 0
  *     ("no dictionary"); any other dictionary is VBZ_ZSTD_ERROR, as with libzstd when it has not got that dictionary.
+ *     A frame whose header gives no Frame_Content_Size is VBZ_ZSTD_ERROR, as in the reference's vbz_decompress, which asks
+ *     ZSTD_getFrameContentSize first and takes "unknown" for an error (vbz/vbz.cpp:236-240); ZSTD_decompress alone would decode it.
  *     A frame's content checksum, when it carries one, is verified as libzstd verifies it (VBZ_ZSTD_ERROR on a mismatch).
  *     VBZ_HIP_CHECKSUM=1 writes frames with the checksum (vbz_gpu.h: vbz_gpu_set_checksum).
  */

@@ -22,6 +22,11 @@
 #define ZR_ERR ((size_t)-1)
 #define ZR_BLOCK_MAX (128u << 10)
 
+/* the census (vbo_zstd_restate_census): cen is null on the ordinary call, and nothing below decides anything by it */
+#define CEN(cen, k) do { if (cen) (cen)[k] += 1; } while (0)
+#define CEN_ADD(cen, k, v) do { if (cen) (cen)[k] += (uint64_t)(v); } while (0)
+#define CEN_MAX(cen, k, v) do { if ((cen) && (cen)[k] < (uint64_t)(v)) (cen)[k] = (uint64_t)(v); } while (0)
+
 typedef struct {
     uint8_t symbol;
     uint8_t nbits;
@@ -198,10 +203,11 @@ static void fse_build_rle(fse_table* t, uint8_t symbol)
 }
 
 /* --- Huffman tree description, RFC 8878 4.2.1 --------------------------------------------- */
-static int huf_read_table(huf_table* h, const uint8_t* p, size_t n)
+static int huf_read_table(huf_table* h, const uint8_t* p, size_t n, uint64_t* cen)
 {
     uint8_t w[256];
     int nw = 0;
+    int wlog = 0; /* accuracy log of FSE-coded weights (census) */
     size_t used;
     if (n < 1) return -1;
     int hb = p[0];
@@ -222,6 +228,7 @@ static int huf_read_table(huf_table* h, const uint8_t* p, size_t n)
         if (hdr < 0) return -1;
         fse_table t;
         if (fse_build(&t, norm, nsym, log) != 0) return -1;
+        wlog = log;
         bitr b;
         if (bitr_init(&b, p + 1 + hdr, (size_t)hb - (size_t)hdr) != 0) return -1;
         uint32_t s1 = bitr_read(&b, log);
@@ -268,6 +275,19 @@ static int huf_read_table(huf_table* h, const uint8_t* p, size_t n)
     }
     h->log = log;
     h->valid = 1;
+    if (cen) {
+        int syms = 0;
+        for (int i = 0; i < nw; ++i) syms += w[i] != 0;
+        CEN(cen, wlog ? VBO_CEN_HUF_DESC_FSE : VBO_CEN_HUF_DESC_DIRECT);
+        if (wlog) CEN(cen, wlog == 5 ? VBO_CEN_HUF_WEIGHTS_LOG_5 : VBO_CEN_HUF_WEIGHTS_LOG_6);
+        /* the longest code is the table's log: a complete tree has symbols of weight 1 */
+        CEN_MAX(cen, VBO_CEN_HUF_MAX_BITS, log);
+        if (log == 11) CEN(cen, VBO_CEN_HUF_TREES_11_BITS);
+        if (log <= 6) CEN(cen, VBO_CEN_HUF_TREES_UP_TO_6_BITS);
+        CEN_MAX(cen, VBO_CEN_HUF_SYMBOLS_MAX, syms);
+        if (syms <= 16) CEN(cen, VBO_CEN_HUF_SYMBOLS_UP_TO_16);
+        if (syms > 128) CEN(cen, VBO_CEN_HUF_SYMBOLS_ABOVE_128);
+    }
     return (int)used;
 }
 
@@ -275,7 +295,7 @@ static int huf_read_table(huf_table* h, const uint8_t* p, size_t n)
 int vbo_debug_huf_lengths(const uint8_t* p, size_t n, uint8_t* nbits_out /*256*/, int* used_out)
 {
     static _Thread_local huf_table h;
-    int used = huf_read_table(&h, p, n);
+    int used = huf_read_table(&h, p, n, NULL);
     if (used < 0) return -1;
     memset(nbits_out, 0, 256);
     for (int i = 0; i < (1 << h.log); ++i) nbits_out[h.e[i] & 0xFF] = (uint8_t)(h.e[i] >> 8);
@@ -334,12 +354,17 @@ typedef struct {
     fse_table ll, of, ml;
     int have_ll, have_of, have_ml;
     uint32_t rep[3];
+    /* census only: the counters (null on the ordinary call), the block's ordinal and that of the block whose tree is held */
+    uint64_t* cen;
+    uint32_t block, tree_block;
 } frame_ctx;
 
+/* kind (census): 0 literal lengths, 1 offsets, 2 match lengths */
 static int seq_table(fse_table* t, int* have, int mode, const uint8_t** pp, const uint8_t* end, const int16_t* def, int def_n,
-                     int def_log, int max_sym, int max_log)
+                     int def_log, int max_sym, int max_log, uint64_t* cen, int kind)
 {
     const uint8_t* p = *pp;
+    CEN(cen, VBO_CEN_SEQ_LL_PREDEFINED + 4 * kind + mode);
     switch (mode) {
     case 0:
         if (fse_build(t, def, def_n, def_log) != 0) return -1;
@@ -358,6 +383,14 @@ static int seq_table(fse_table* t, int* have, int mode, const uint8_t** pp, cons
         int used = fse_read_ncount(p, (size_t)(end - p), norm, max_sym, max_log, &log, &nsym);
         if (used < 0) return -1;
         if (fse_build(t, norm, nsym, log) != 0) return -1;
+        if (cen) {
+            int less = 0;
+            for (int s = 0; s < nsym; ++s) less |= norm[s] == -1;
+            CEN_MAX(cen, VBO_CEN_SEQ_LL_LOG_MAX + kind, log);
+            if (log == 5) CEN(cen, VBO_CEN_SEQ_LL_LOG_5 + kind);
+            if (log == max_log) CEN(cen, VBO_CEN_SEQ_LL_LOG_LIMIT + kind);
+            if (less) CEN(cen, VBO_CEN_SEQ_LL_LESS_THAN_1 + kind);
+        }
         *pp = p + used;
         *have = 1;
         return 0;
@@ -468,6 +501,9 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
     if (regen > ZR_BLOCK_MAX) return ZR_ERR;
     const uint8_t* p = src + hsz;
     const uint8_t* end = src + n;
+    uint64_t* const cen = fc->cen;
+    /* raw and RLE: by the header's bytes (formats 0 and 2 are the same one byte); compressed and treeless: by the size format */
+    CEN(cen, type < 2 ? VBO_CEN_LIT_RAW_1 + 3 * type + (int)hsz - 1 : VBO_CEN_LIT_HUF_FMT_0 + 4 * (type - 2) + ((src[0] >> 2) & 3));
     if (type == 0) {
         if ((size_t)(end - p) < regen) return ZR_ERR;
         memcpy(lit, p, regen);
@@ -482,12 +518,16 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
         const uint8_t* q = p;
         const uint8_t* qend = p + csize;
         if (type == 2) {
-            int used = huf_read_table(&fc->huf, q, csize);
+            int used = huf_read_table(&fc->huf, q, csize, cen);
             if (used < 0) return ZR_ERR;
             q += used;
+            fc->tree_block = fc->block;
         } else if (!fc->huf.valid) {
             return ZR_ERR;
+        } else {
+            CEN(cen, fc->tree_block + 1 == fc->block ? VBO_CEN_LIT_TREELESS_TREE_OF_PREVIOUS_BLOCK : VBO_CEN_LIT_TREELESS_TREE_OF_EARLIER_BLOCK);
         }
+        CEN(cen, streams == 1 ? VBO_CEN_LIT_STREAMS_1 : VBO_CEN_LIT_STREAMS_4);
         if (streams == 1) {
             if (huf_decode_stream(&fc->huf, q, (size_t)(qend - q), lit, regen) != 0) return ZR_ERR;
         } else {
@@ -512,6 +552,7 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
     const int nu = read_nseq(p, (size_t)(end - p), &nseq);
     if (nu < 0) return ZR_ERR;
     p += nu;
+    CEN(cen, nseq == 0 ? VBO_CEN_SEQ_NONE : VBO_CEN_SEQ_COUNT_1_BYTE + nu - 1);
     size_t opos = base; /* logical output position */
     size_t lpos = 0;
 #define PUT(byte_expr)                                    \
@@ -524,14 +565,15 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
         if (p != end) return ZR_ERR;
         for (size_t i = 0; i < regen; ++i) PUT(lit[i]);
         if (opos - base > ZR_BLOCK_MAX) return ZR_ERR;
+        CEN_ADD(cen, VBO_CEN_LITERAL_BYTES, regen);
         return opos - base;
     }
     if (p >= end) return ZR_ERR;
     int modes = *p++;
     if (modes & 3) return ZR_ERR;
-    if (seq_table(&fc->ll, &fc->have_ll, (modes >> 6) & 3, &p, end, LL_DEFAULT, 36, 6, 35, 9) != 0) return ZR_ERR;
-    if (seq_table(&fc->of, &fc->have_of, (modes >> 4) & 3, &p, end, OF_DEFAULT, 29, 5, 31, 8) != 0) return ZR_ERR;
-    if (seq_table(&fc->ml, &fc->have_ml, (modes >> 2) & 3, &p, end, ML_DEFAULT, 53, 6, 52, 9) != 0) return ZR_ERR;
+    if (seq_table(&fc->ll, &fc->have_ll, (modes >> 6) & 3, &p, end, LL_DEFAULT, 36, 6, 35, 9, cen, 0) != 0) return ZR_ERR;
+    if (seq_table(&fc->of, &fc->have_of, (modes >> 4) & 3, &p, end, OF_DEFAULT, 29, 5, 31, 8, cen, 1) != 0) return ZR_ERR;
+    if (seq_table(&fc->ml, &fc->have_ml, (modes >> 2) & 3, &p, end, ML_DEFAULT, 53, 6, 52, 9, cen, 2) != 0) return ZR_ERR;
     bitr b;
     if (bitr_init(&b, p, (size_t)(end - p)) != 0) return ZR_ERR;
     uint32_t sl = bitr_read(&b, fc->ll.log);
@@ -545,6 +587,16 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
         uint32_t mlen = ML_BASE[mc] + bitr_read(&b, ML_BITS[mc]);
         uint32_t llen = LL_BASE[lc] + bitr_read(&b, LL_BITS[lc]);
         uint32_t offset;
+        if (cen) {
+            CEN_MAX(cen, VBO_CEN_MAX_LL_CODE, lc);
+            CEN_MAX(cen, VBO_CEN_MAX_OF_CODE, oc);
+            CEN_MAX(cen, VBO_CEN_MAX_ML_CODE, mc);
+            if (lc == 35) CEN(cen, VBO_CEN_LL_CODE_35);
+            if (mc == 52) CEN(cen, VBO_CEN_ML_CODE_52);
+            if (llen == 0) CEN(cen, VBO_CEN_SEQ_LITERAL_LENGTH_0);
+            if (ofv > 3) CEN(cen, VBO_CEN_OFF_NEW);
+            else CEN(cen, (llen ? VBO_CEN_OFF_REP0 : VBO_CEN_OFF_LL0_REP1) + ofv - 1);
+        }
         if (ofv > 3) {
             offset = ofv - 3;
             fc->rep[2] = fc->rep[1];
@@ -572,6 +624,15 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
         for (uint32_t k = 0; k < llen; ++k) PUT(lit[lpos + k]);
         lpos += llen;
         if (offset > opos) return ZR_ERR;
+        if (cen) {
+            if (offset < mlen) CEN(cen, VBO_CEN_MATCH_OVERLAPS_ITSELF);
+            if (offset == 1) CEN(cen, VBO_CEN_MATCH_OFFSET_1);
+            if (opos - offset < base) CEN(cen, VBO_CEN_MATCH_FROM_BEFORE_THE_BLOCK);
+            if (offset > (64u << 10)) CEN(cen, VBO_CEN_OFF_ABOVE_64K);
+            if (offset > (128u << 10)) CEN(cen, VBO_CEN_OFF_ABOVE_128K);
+            if (offset > (1u << 20)) CEN(cen, VBO_CEN_OFF_ABOVE_1M);
+            CEN_ADD(cen, VBO_CEN_MATCH_BYTES, mlen);
+        }
         for (uint32_t k = 0; k < mlen; ++k) {
             size_t from = opos - offset;
             PUT(from < cap ? out[from] : 0);
@@ -579,6 +640,8 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
         if (opos - base > ZR_BLOCK_MAX) return ZR_ERR;
     }
     if (b.pos != 0) return ZR_ERR;
+    CEN(cen, lpos < regen ? VBO_CEN_TAIL_LITERALS_SOME : VBO_CEN_TAIL_LITERALS_NONE);
+    CEN_ADD(cen, VBO_CEN_LITERAL_BYTES, regen);
     for (; lpos < regen;) PUT(lit[lpos++]);
 #undef PUT
     if (opos - base > ZR_BLOCK_MAX) return ZR_ERR;
@@ -597,6 +660,7 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
         return 0;
     }
     if (magic != 0xFD2FB528u) return ZR_ERR;
+    uint64_t* const cen = fc->cen;
     uint8_t fhd = src[4];
     int fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, checksum = (fhd >> 2) & 1, did_flag = fhd & 3;
     if (fhd & 0x08) return ZR_ERR; /* reserved bit */
@@ -608,6 +672,7 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
         int wlog = 10 + (wd >> 3);
         if (wlog > 31) return ZR_ERR;
         window = (1ull << wlog) + ((1ull << wlog) >> 3) * (wd & 7);
+        CEN(cen, wlog <= 16 ? VBO_CEN_FRAME_WINDOW_LOG_UP_TO_16 : (wlog <= 19 ? VBO_CEN_FRAME_WINDOW_LOG_17_TO_19 : VBO_CEN_FRAME_WINDOW_LOG_FROM_20));
     }
     static const int did_sz[4] = { 0, 1, 2, 4 };
     if (pos + (size_t)did_sz[did_flag] > n) return ZR_ERR;
@@ -624,6 +689,13 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
     if (single) window = fcs;
     uint64_t block_max = window < ZR_BLOCK_MAX ? window : ZR_BLOCK_MAX;
     memset(fc, 0, sizeof(*fc));
+    fc->cen = cen;
+    if (cen) {
+        CEN(cen, VBO_CEN_FRAMES);
+        CEN(cen, single ? VBO_CEN_FRAME_SINGLE_SEGMENT : VBO_CEN_FRAME_WINDOW_DESCRIPTOR);
+        CEN(cen, VBO_CEN_FRAME_CONTENT_SIZE_0_BYTES + (fcs_sz == 0 ? 0 : (fcs_sz == 1 ? 1 : (fcs_sz == 2 ? 2 : (fcs_sz == 4 ? 3 : 4)))));
+        if (checksum) CEN(cen, VBO_CEN_FRAME_CHECKSUM);
+    }
     fc->rep[0] = 1;
     fc->rep[1] = 4;
     fc->rep[2] = 8;
@@ -635,6 +707,10 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
         int last = bh & 1, btype = (bh >> 1) & 3;
         size_t bsize = bh >> 3;
         if (btype == 3) return ZR_ERR;
+        CEN(cen, VBO_CEN_BLOCK_RAW + btype);
+        CEN(cen, last ? VBO_CEN_BLOCK_LAST : VBO_CEN_BLOCK_NOT_LAST);
+        if (btype < 2) CEN_ADD(cen, VBO_CEN_LITERAL_BYTES, bsize);
+        if (btype == 0 && bsize == 0) CEN(cen, VBO_CEN_BLOCK_RAW_EMPTY);
         if (btype == 0) {
             if (bsize > block_max) return ZR_ERR;
             if (pos + bsize > n) return ZR_ERR;
@@ -657,6 +733,7 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
             out += r;
             pos += bsize;
         }
+        fc->block++;
         if (last) break;
     }
     if (checksum) {
@@ -686,3 +763,39 @@ size_t vbo_zstd_restate_decompress(void* dst, size_t cap, const void* src_, size
     }
     return total;
 }
+
+/* The census: the same decode (nothing is stored: a match's bytes decide nothing), counting what it meets -- vbz_oracle.h, VBO_CENSUS.
+ * Counters of a frame that is refused part-way keep what was counted up to there: the caller discards them. */
+size_t vbo_zstd_restate_census(const void* src_, size_t n, uint64_t* counters, size_t ncounters)
+{
+    static _Thread_local uint8_t lit[ZR_BLOCK_MAX + 32];
+    static _Thread_local frame_ctx fc;
+    const uint8_t* src = (const uint8_t*)src_;
+    size_t total = 0;
+    if (!counters || ncounters < VBO_CEN_COUNT) return ZR_ERR;
+    while (n > 0) {
+        size_t used = 0;
+        fc.cen = counters;
+        size_t r = decode_frame(src, n, NULL, 0, &used, lit, &fc);
+        fc.cen = NULL;
+        if (r == ZR_ERR) return ZR_ERR;
+        total += r;
+        src += used;
+        n -= used;
+    }
+    return total;
+}
+
+static const char* const census_names[VBO_CEN_COUNT] = {
+#define X(id, name, kind) name,
+    VBO_CENSUS(X)
+#undef X
+};
+static const char census_kinds[VBO_CEN_COUNT] = {
+#define X(id, name, kind) kind,
+    VBO_CENSUS(X)
+#undef X
+};
+int vbo_zstd_census_count(void) { return VBO_CEN_COUNT; }
+const char* vbo_zstd_census_name(int k) { return k >= 0 && k < VBO_CEN_COUNT ? census_names[k] : NULL; }
+int vbo_zstd_census_is_max(int k) { return k >= 0 && k < VBO_CEN_COUNT && census_kinds[k] == 'm'; }

@@ -77,6 +77,13 @@ def lib():
         L.vbo_zstd_content_size.argtypes = [vp, sz]
         L.vbo_zstd_restate_decompress.restype = sz
         L.vbo_zstd_restate_decompress.argtypes = [vp, sz, vp, sz]
+        L.vbo_zstd_restate_census.restype = sz
+        L.vbo_zstd_restate_census.argtypes = [vp, sz, vp, sz]
+        L.vbo_zstd_census_count.restype = ctypes.c_int
+        L.vbo_zstd_census_name.restype = ctypes.c_char_p
+        L.vbo_zstd_census_name.argtypes = [ctypes.c_int]
+        L.vbo_zstd_census_is_max.restype = ctypes.c_int
+        L.vbo_zstd_census_is_max.argtypes = [ctypes.c_int]
         L.vbo_mix64.restype = ctypes.c_uint64
         L.vbo_mix64.argtypes = [ctypes.c_uint64]
         L.vbo_synth_read_length.restype = u32
@@ -239,6 +246,30 @@ def zstd_restate_decompress(frame, cap):
     return out[:r].copy()
 
 
+def census_names():
+    """The census counters' names, in the order of oracle/vbz_oracle.h's VBO_CENSUS."""
+    return [lib().vbo_zstd_census_name(k).decode() for k in range(lib().vbo_zstd_census_count())]
+
+
+def census_maxima():
+    """The names of the counters that are maxima (merged over frames with max; every other one adds up)."""
+    return {lib().vbo_zstd_census_name(k).decode() for k in range(lib().vbo_zstd_census_count()) if lib().vbo_zstd_census_is_max(k)}
+
+
+def zstd_census(frame):
+    """{counter name: value} of what the restated decoder meets in the buffer's frames (oracle/vbz_oracle.h, VBO_CENSUS), with the content
+    size under "content_size"; None where the restated decoder refuses the buffer."""
+    a, p, n = _buf(frame if isinstance(frame, np.ndarray) else np.frombuffer(bytes(frame), np.uint8))
+    names = census_names()
+    c = np.zeros(len(names), np.uint64)
+    r = lib().vbo_zstd_restate_census(p, n, c.ctypes.data, len(names))
+    if r == 2**64 - 1:
+        return None
+    out = {k: int(v) for k, v in zip(names, c)}
+    out["content_size"] = int(r)
+    return out
+
+
 def zstd_content_size(frame):
     a, p, n = _buf(frame if isinstance(frame, np.ndarray) else np.frombuffer(bytes(frame), np.uint8))
     return lib().vbo_zstd_content_size(p, n)
@@ -288,7 +319,11 @@ def bench_roundtrip(n_reads, threads, min_seconds, opts, u32_count=0, simd=False
 # A one-shot ZSTD_compress cuts its input into blocks of block_max = min(window, 128 KiB) bytes; a writer that flushes
 # (ZSTD_compressStream2 with ZSTD_e_flush, as streaming writers and libzstd >= 1.5 do) ends a block wherever it flushes.
 BLOCK_MAX = 128 << 10
-ZSTD_c_compressionLevel, ZSTD_c_windowLog, ZSTD_c_checksumFlag = 100, 101, 201
+# ZSTD_cParameter (zstd.h of 1.4.8; the numbers are part of the library's ABI)
+ZSTD_c_compressionLevel, ZSTD_c_windowLog, ZSTD_c_hashLog, ZSTD_c_chainLog, ZSTD_c_searchLog = 100, 101, 102, 103, 104
+ZSTD_c_minMatch, ZSTD_c_targetLength, ZSTD_c_strategy, ZSTD_c_enableLongDistanceMatching = 105, 106, 107, 160
+ZSTD_c_contentSizeFlag, ZSTD_c_checksumFlag = 200, 201
+ZSTD_e_continue = 0
 ZSTD_e_flush, ZSTD_e_end = 1, 2
 
 
@@ -332,43 +367,59 @@ def libzstd():
     return _zstd
 
 
-def zstd_compress_cuts(data, cuts=(), level=1, window_log=0, checksum=False):
-    """A libzstd frame of `data` (content size in the header) whose blocks end at every cut -- and wherever libzstd itself ends one:
-    every block_max bytes of a stretch between cuts.  cuts: strictly increasing, each in (0, len(data)).  No cuts: ZSTD_compress2."""
+def zstd_compress_params(data, params, cuts=(), pledge=True):
+    """A libzstd frame of `data` under `params` ({ZSTD_cParameter number: value}, set in the dict's order), its blocks ending at every cut
+    (a flush) -- and wherever libzstd itself ends one.  cuts: strictly increasing, each in (0, len(data)]; a cut at len(data) flushes
+    everything before the frame is ended, which leaves an empty last block.  pledge: the source size is declared in advance (a content
+    size in the header unless ZSTD_c_contentSizeFlag is 0); without it the frame is streamed and has none.  Pledged and without cuts:
+    ZSTD_compress2."""
     a = np.ascontiguousarray(data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)).view(np.uint8).reshape(-1)
     n = a.nbytes
     cuts = [int(c) for c in cuts]
-    if any(not 0 < c < n for c in cuts) or any(x >= y for x, y in zip(cuts, cuts[1:])):
-        raise ValueError("cuts must increase strictly inside (0, %d): %s" % (n, cuts))
+    if any(not 0 < c <= n for c in cuts) or any(x >= y for x, y in zip(cuts, cuts[1:])):
+        raise ValueError("cuts must increase strictly inside (0, %d]: %s" % (n, cuts))
     Z = libzstd()
     cap = Z.ZSTD_compressBound(n) + 64 * (len(cuts) + 1) + 64
     out = np.zeros(cap, np.uint8)
     cc = Z.ZSTD_createCCtx()
     assert cc
     try:
-        for p, v in ((ZSTD_c_compressionLevel, level), (ZSTD_c_windowLog, window_log), (ZSTD_c_checksumFlag, 1 if checksum else 0)):
-            assert not Z.ZSTD_isError(Z.ZSTD_CCtx_setParameter(cc, p, int(v))), (p, v)
-        assert not Z.ZSTD_isError(Z.ZSTD_CCtx_setPledgedSrcSize(cc, n))
-        src = a.ctypes.data if n else None
-        if not cuts:
-            r = Z.ZSTD_compress2(cc, out.ctypes.data, cap, src, n)
+        for p, v in params.items():
+            assert not Z.ZSTD_isError(Z.ZSTD_CCtx_setParameter(cc, int(p), int(v))), (p, v)
+        if pledge:
+            assert not Z.ZSTD_isError(Z.ZSTD_CCtx_setPledgedSrcSize(cc, n))
+        keep = a if n else np.zeros(1, np.uint8)   # (a valid pointer for the empty content too)
+        src = keep.ctypes.data
+        if not cuts and pledge:
+            r = Z.ZSTD_compress2(cc, out.ctypes.data, cap, src if n else None, n)
             assert not Z.ZSTD_isError(r), r
             return out[:r].copy()
         ob = _ZBuf(out.ctypes.data, cap, 0)
+        # (a frame ended by the first call would get that call's input as its pledge: an unpledged frame's content goes in ahead of the end)
+        steps = [(c, ZSTD_e_flush) for c in cuts] + ([(n, ZSTD_e_continue)] if not pledge and not cuts else []) + [(n, ZSTD_e_end)]
         prev = 0
-        for c in cuts + [n]:
+        for c, mode in steps:
             ib = _ZBuf(src + prev, c - prev, 0)
-            mode = ZSTD_e_flush if c < n else ZSTD_e_end
             while True:
                 r = Z.ZSTD_compressStream2(cc, ctypes.byref(ob), ctypes.byref(ib), mode)
                 assert not Z.ZSTD_isError(r), r
-                if ib.pos == ib.size and r == 0:
+                if ib.pos == ib.size and (r == 0 or mode == ZSTD_e_continue):
                     break
                 assert ob.pos < cap
             prev = c
         return out[: ob.pos].copy()
     finally:
         Z.ZSTD_freeCCtx(cc)
+
+
+def zstd_compress_cuts(data, cuts=(), level=1, window_log=0, checksum=False):
+    """A libzstd frame of `data` (content size in the header) whose blocks end at every cut -- and wherever libzstd itself ends one:
+    every block_max bytes of a stretch between cuts.  cuts: strictly increasing, each in (0, len(data)).  No cuts: ZSTD_compress2."""
+    n = (data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)).nbytes
+    cuts = [int(c) for c in cuts]
+    if any(not 0 < c < n for c in cuts) or any(x >= y for x, y in zip(cuts, cuts[1:])):
+        raise ValueError("cuts must increase strictly inside (0, %d): %s" % (n, cuts))
+    return zstd_compress_params(data, {ZSTD_c_compressionLevel: level, ZSTD_c_windowLog: window_log, ZSTD_c_checksumFlag: 1 if checksum else 0}, cuts)
 
 
 def zstd_block_ends(frame, cap):
