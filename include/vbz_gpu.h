@@ -519,6 +519,79 @@ VBZ_EXPORT int vbz_gpu_pod5_decompress_windows_batch(vbz_gpu_ctx* ctx, const vbz
                                                      const vbz_gpu_windows* windows, void* out, const vbz_gpu_normalization* norm,
                                                      float* shift_scale, const vbz_gpu_sample_ranges* ranges);
 
+/* Signal events.  Every call above gives samples.  A modification caller that reduces a read to one signal level per base along the
+ * basecaller's move table, a re-squiggle or event-align tool, per-k-mer level QC want one record {mean, sd, length} per EVENT, the caller
+ * saying where each event begins.  The two calls below decode and reduce in one pass of the svb decoder: no sample is stored anywhere.
+ * The signal is the read's samples x[b:e) of T' = e - b samples, ranges clamped exactly as in the *_range_batch calls (ranges NULL, or both
+ * tables NULL: the whole read).
+ * The rows: read i owns rows c0 = event_first[i] ... c1 - 1 = event_first[i + 1] - 1 of `out` (and of `moments`).  Row c covers the
+ * positions [a, z) of the signal, a = min(start[c], T'), z = min(start[c + 1], T') when c + 1 < c1 and z = T' for the read's last row.
+ * Samples in front of the read's first start belong to no event; equal starts give an empty event; a start at or behind T' (0xFFFFFFFF
+ * included) gives an empty event.
+ * The moments are exact integers: n = z - a, S1 = sum x_j, S2 = sum x_j^2 over the row's positions, x_j the raw 16-bit value (int16, or
+ * uint16 with format->is_signed == 0).  n < 2^31 keeps |S1| < 2^47 and S2 <= 2^63: nothing wraps.  moments[c] = {S1, S2} when `moments`
+ * is given (NULL: they live in scratch of the context).
+ * The record, in float64, every operation rounded to nearest even and none fused: m = float64(S1) / float64(n);
+ * v = float64(S2) / float64(n) - m * m, 0 when negative; r = sqrt(v), correctly rounded; with the read's constants o and s,
+ * mean = float32((m + float64(o)) * float64(s)) and sd = float32(r * fabs(float64(s))).  o and s are format->offset[i] / scale[i] (NULL:
+ * 0 and 1) when norm is NULL; otherwise o = -shift and s = float32(1 / float64(scale)) from the read's own statistics as in the *_norm
+ * calls (format->offset and scale must then be NULL, shift_scale is nullable, ranges->stats has its meaning).  n == 0 gives
+ * mean = sd = +0; `zero` is written 0.  format->out_type must be VBZ_GPU_SIGNAL_F32.  Integer sums do not depend on the order of the
+ * additions: the records are numpy's bit for bit (tests/events_ref.py).
+ * Verdicts: result[i] is what the statistics-alone call gives -- the int16 decode's verdict, T x 2 with the read's FULL sample count on
+ * success.  The tables are untrusted.  Per read, in this order: the descriptor checks; sized, the header verdicts; then the event check,
+ * which is the window check's rule: event_first[i] > event_first[i + 1], event_first[i + 1] > event_rows, more than 2^31 - 1 rows of one
+ * read, or a pair start[c] > start[c + 1] (unsigned) inside the read's rows.  A read refused by it gets VBZ_DESTINATION_SIZE_ERROR and not
+ * one byte of out or moments is written for it.  No start[] entry of a read is read before its two event_first entries have passed, and
+ * no address is formed from an unchecked value.  Rows of a read that fails after the event check hold unspecified contents; nothing
+ * outside the rows owned by reads, and the shift_scale entries, is ever written; batch->dst may be NULL.
+ * vbz_gpu_pod5_signal_events_batch: the same over POD5 reads of several rows.  event_first, the constants, shift_scale and the range
+ * tables are per READ, positions are those of the concatenated signal; result[] stays per row and read_result[] per read as in the POD5
+ * statistics call; the event check is per READ and reaches every row of the read; a bad first_row fails the whole call.
+ * Both return 0 when queued, -1 for a NULL context or batch or a launch failure, -2 (nothing launched) for everything
+ * vbz_gpu_signal_norm_range_batch / its POD5 twin refuse (a NULL norm is allowed here), a NULL events, flags or reserved != 0, an out_type
+ * other than F32, a NULL event_first, start (when event_rows > 0) or out while the call has reads, out or moments not 16-byte aligned,
+ * event_rows * 16 beyond 2^46 bytes.
+ * How: one more sink of the svb decoder, on every decode path.  A lane holds eight consecutive samples; they lie in
+ * consecutive events of the read's sorted list; the workgroup brackets the starts inside each tile of 2 048 samples with two cursors that
+ * only advance, a lane bisects that bracket for its first sample's event and adds up each run of samples that share an event, sum x in
+ * 32 bits and sum x^2 in 64, and adds the run to the row's two 64-bit words with global integer adds.  The words are zeroed by a launch
+ * behind the event check; one thread per row derives n from the starts, applies the formulas and writes one 16-byte record behind the
+ * pass.  Measured on one MI355X (tools/time_events.py, profiles/HISTORY.md "Signal events"; the parent of the commit that adds these
+ * calls is 7d0484f): 8 192 reads of ~100 k samples cut into 51.2 M events of random dwell 2 ... 30, records and moments: 13.75 ms with
+ * given constants against 1.66 ms for the int16 decode alone and 30.72 ms for the int16 decode followed by a torch reduction (integer
+ * cumulative sums, float64 arithmetic); 14.41 ms with MED_MAD against 2.03 ms for the statistics alone and 32.62 ms unfused.  One
+ * 20 M-sample read: 0.689 / 0.337 / 1.090 ms.  Fusing wins 2.2 x over the unfused route and stays 8 x above the decode: the event pass,
+ * with its global adds, is 10.4 of the 13.75 ms (DESIGN.md 4.19 says what comes next). */
+typedef struct vbz_gpu_events
+{
+    uint64_t event_rows;         /* entries of start[] = rows of out / moments */
+    const uint64_t* event_first; /* device, n_reads + 1: read i owns rows event_first[i] ... event_first[i + 1] - 1 */
+    const uint32_t* start;       /* device, event_rows: first sample of each event, in positions of the read's signal */
+    uint32_t flags;              /* must be 0 */
+    uint32_t reserved;           /* must be 0 */
+} vbz_gpu_events;                /* 32 bytes */
+typedef struct vbz_gpu_event
+{
+    float mean;    /* ((S1 / n) + o) * s */
+    float sd;      /* sqrt(S2 / n - (S1 / n)^2) * |s|: the population standard deviation */
+    uint32_t n;    /* samples of the event */
+    uint32_t zero; /* written 0 */
+} vbz_gpu_event;   /* 16 bytes */
+typedef struct vbz_gpu_event_moments
+{
+    int64_t sum;    /* S1 */
+    uint64_t sumsq; /* S2 */
+} vbz_gpu_event_moments; /* 16 bytes */
+VBZ_EXPORT int vbz_gpu_signal_events_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                           const vbz_gpu_signal_format* format, const vbz_gpu_events* events, vbz_gpu_event* out,
+                                           vbz_gpu_event_moments* moments, const vbz_gpu_normalization* norm, float* shift_scale,
+                                           const vbz_gpu_sample_ranges* ranges);
+VBZ_EXPORT int vbz_gpu_pod5_signal_events_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
+                                                const vbz_gpu_events* events, vbz_gpu_event* out, vbz_gpu_event_moments* moments,
+                                                const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

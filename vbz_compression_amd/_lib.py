@@ -145,6 +145,38 @@ class GpuWindows(ctypes.Structure):
     ]
 
 
+class GpuEvents(ctypes.Structure):
+    """struct vbz_gpu_events of include/vbz_gpu.h (32 bytes)."""
+
+    _fields_ = [
+        ("event_rows", ctypes.c_uint64),
+        ("event_first", ctypes.c_void_p),
+        ("start", ctypes.c_void_p),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class GpuEvent(ctypes.Structure):
+    """struct vbz_gpu_event of include/vbz_gpu.h (16 bytes): one row of the event arena."""
+
+    _fields_ = [
+        ("mean", ctypes.c_float),
+        ("sd", ctypes.c_float),
+        ("n", ctypes.c_uint32),
+        ("zero", ctypes.c_uint32),
+    ]
+
+
+class GpuEventMoments(ctypes.Structure):
+    """struct vbz_gpu_event_moments of include/vbz_gpu.h (16 bytes): one row's exact sums."""
+
+    _fields_ = [
+        ("sum", ctypes.c_int64),
+        ("sumsq", ctypes.c_uint64),
+    ]
+
+
 VBZ_GPU_TRIM_REJECT_AT_END = 1   # vbz_gpu_trim.flags: a trim whose window ends at the end of the samples looked at is rejected
 
 
@@ -204,6 +236,8 @@ GPU_API = [
     "vbz_gpu_pod5_signal_trim_batch",
     "vbz_gpu_decompress_windows_batch",
     "vbz_gpu_pod5_decompress_windows_batch",
+    "vbz_gpu_signal_events_batch",
+    "vbz_gpu_pod5_signal_events_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -352,6 +386,16 @@ def load():
         L.vbz_gpu_decompress_windows_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, wp, vp, np_, vp, gp]
         L.vbz_gpu_pod5_decompress_windows_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_decompress_windows_batch.argtypes = [vp, bp, op, fp, rp, wp, vp, np_, vp, gp]
+    if hasattr(L, "vbz_gpu_signal_events_batch"):   # (likewise: builds of earlier rounds have no signal events)
+        np_ = ctypes.POINTER(GpuNormalization)
+        fp = ctypes.POINTER(GpuSignalFormat)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        gp = ctypes.POINTER(GpuSampleRanges)
+        ep = ctypes.POINTER(GpuEvents)
+        L.vbz_gpu_signal_events_batch.restype = ctypes.c_int
+        L.vbz_gpu_signal_events_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, ep, vp, vp, np_, vp, gp]
+        L.vbz_gpu_pod5_signal_events_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_signal_events_batch.argtypes = [vp, bp, op, fp, rp, ep, vp, vp, np_, vp, gp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -149,14 +149,15 @@ class GpuCodec:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self.L.vbz_gpu_last_error(self.ctx).decode()))
 
     def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
-               chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None):
+               chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None, ev=None, moments=None):
         """One typed decode (include/vbz_gpu.h): the batch, the device entered and left once, and the most general C entry of the call's
         family, NULL for every part that is None.  dst None: nothing is stored in the batch's dst (a chunk decode, the statistics) --
         dst_off / dst_cap are the int16 layout that describes the reads, dst_bytes its extent.  f (a GpuSignalFormat): what is stored,
         with ch (a GpuChunking) into `chunks` at chunk_first; f None: the statistics alone of `signed` samples, with t (a GpuTrim) the
         trim points behind them, into `out`.  m / ss: the GpuNormalization and the shift_scale pointer; g: a GpuSampleRanges; r: a
         GpuPod5Reads (the pod5_ entries: unsized).  w (a GpuWindows, in place of ch): the samples go to the caller-listed windows, the
-        rows of `chunks`."""
+        rows of `chunks`.  ev (a GpuEvents, with f): no sample is stored -- one record per caller-listed event into `out` (int32 [rows, 4]), the
+        exact sums into `moments` (int64 [rows, 2], or None)."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -166,7 +167,10 @@ class GpuCodec:
             return ctypes.byref(s) if s is not None else None
 
         reads = [ref(r)] if r is not None else []
-        if w is not None:
+        if ev is not None:
+            assert ch is None and w is None, "a call has a chunking, windows or events, never two of them"
+            name, args = "signal_events", [ref(f)] + reads + [ref(ev), out.data_ptr(), moments.data_ptr() if moments is not None else None, ref(m), ss, ref(g)]
+        elif w is not None:
             assert ch is None, "a call has a chunking or windows, never both"
             name, args = "decompress_windows", [ref(f)] + reads + [ref(w), chunks.data_ptr(), ref(m), ss, ref(g)]
         elif ch is not None:
@@ -631,6 +635,57 @@ class GpuCodec:
         return self._decode_windows(n, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, opts, False, window_first, start,
                                     window_len, pad, dtype, scale, offset, signed, norm, norm_out, begin, end, stats)
 
+    # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
+    def _events(self, n, event_first, start):
+        """(the C struct, the tables it points to) of n reads' events: event_first int64 [n + 1] on the device; start int32 [rows] on the
+        device (uint32 bits), or any sequence of values 0 ... 0xFFFFFFFF"""
+        assert event_first.dtype == torch.int64 and event_first.is_contiguous() and event_first.device == self.device, (event_first.dtype, event_first.device)
+        assert int(event_first.numel()) == n + 1, (int(event_first.numel()), n)
+        if not (isinstance(start, torch.Tensor) and start.dtype == torch.int32):
+            w = torch.as_tensor(start, dtype=torch.int64).reshape(-1)
+            start = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+        start = start.to(self.device).contiguous()
+        ev = _lib.GpuEvents()
+        ev.event_rows = int(start.numel())
+        ev.event_first = event_first.data_ptr()
+        ev.start = start.data_ptr() if int(start.numel()) else None
+        return ev, (event_first, start)
+
+    def _signal_events(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, event_first, start, scale, offset, signed,
+                       norm, norm_out, begin, end, stats, moments, arena, r=None):
+        ev, keep_e = self._events(n, event_first, start)
+        rows = int(ev.event_rows)
+        g, keep_g = self._ranges(n, begin, end, stats)
+        m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
+        f = self._signal_format(torch.float32, n, scale, offset, signed)
+        if arena is None:
+            arena = torch.empty((rows, 4), dtype=torch.int32, device=self.device)
+        assert arena.dtype == torch.int32 and arena.is_contiguous() and arena.device == self.device and tuple(arena.shape) == (rows, 4), (arena.dtype, arena.shape)
+        if moments is True:
+            moments = torch.empty((rows, 2), dtype=torch.int64, device=self.device)
+        elif moments is False:
+            moments = None
+        if moments is not None:
+            assert moments.dtype == torch.int64 and moments.is_contiguous() and moments.device == self.device and tuple(moments.shape) == (rows, 2), (
+                moments.dtype, moments.shape)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, m=m, ss=ss, g=g, r=r, ev=ev, out=arena, moments=moments)
+        records = (arena[:, 0].view(torch.float32), arena[:, 1].view(torch.float32), arena[:, 2])
+        return records if moments is None else records + (moments,)
+
+    def signal_events(self, src, src_off, src_size, dst_off, dst_cap, result, opts, event_first, start, scale=None, offset=None, signed=True,
+                      sized=False, norm=None, norm_out=None, begin=None, end=None, stats=None, moments=False, arena=None):
+        """One record per caller-listed event of every read, with no sample stored (include/vbz_gpu.h: vbz_gpu_signal_events_batch) ->
+        (mean float32 [rows], sd float32 [rows], n int32 [rows]), views of one int32 [rows, 4] arena (`arena` when given); with
+        moments=True (or an int64 [rows, 2] tensor) also the exact (sum x, sum x^2) per row.  Read i owns rows event_first[i] ...
+        event_first[i + 1] - 1 (int64 [n + 1] on the device); event c begins at sample start[c] of the read's signal -- of its range with
+        begin / end -- and ends where the next one begins, the read's last at the signal's end (starts sorted within a read; uint32).
+        mean = (m + offset) * scale and sd = r * |scale| in float64, rounded once; with norm= the read's own {-shift, 1 / scale}
+        (norm_out: float32 [n, 2], filled with (shift, scale)).  dst_off / dst_cap: the int16 layout of the reads (nothing is stored);
+        result[i] is what decompress gives.  No synchronisation."""
+        n = int(src_off.numel())
+        return self._signal_events(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, event_first, start,
+                                   scale, offset, signed, norm, norm_out, begin, end, stats, moments, arena)
+
     # -- POD5 reads of several rows (include/vbz_gpu.h: vbz_gpu_pod5_reads) ---------------------------
     def _pod5_reads(self, n_rows, read_first_row, read_result):
         """(the C struct, first_row int32 [n_reads + 1] on the device, read_result) of rows grouped by read_first_row: the first row of
@@ -699,6 +754,18 @@ class GpuCodec:
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._decode_windows(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
                                     window_first, start, window_len, pad, dtype, scale, offset, signed, norm, norm_out, begin, end, stats, r=r)
+
+    def pod5_signal_events(self, src, src_off, src_size, row_samples, read_first_row, result, event_first, start, scale=None, offset=None, signed=True,
+                           norm=None, norm_out=None, begin=None, end=None, stats=None, moments=False, arena=None, read_result=None):
+        """signal_events over POD5 signal rows grouped into reads by read_first_row (include/vbz_gpu.h: vbz_gpu_pod5_signal_events_batch):
+        event_first, scale / offset / norm_out and begin / end are per READ, the positions those of the read's concatenated signal; result
+        is per ROW, read_result (int32 [n_reads] on the device, optional) per read."""
+        n = int(src_off.numel())
+        assert int(row_samples.numel()) == n
+        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        return self._signal_events(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
+                                   event_first, start, scale, offset, signed, norm, norm_out, begin, end, stats, moments, arena, r=r)
 
     def pod5_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, shift_scale=None, signed=True, begin=None,
                          end=None, stats=None):

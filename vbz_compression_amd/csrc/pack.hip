@@ -396,6 +396,30 @@ __global__ __launch_bounds__(256) void window_sorted_kernel(ReadBatch b, Pod5Rea
     }
 }
 
+// the same pass of an event call (SignalOut::events): an event's start is unsigned (a window's may be negative), nothing else differs --
+// a kernel of its own, so that the windows' keeps its code
+__global__ __launch_bounds__(256) void event_sorted_kernel(ReadBatch b, Pod5Reads pr, const uint64_t* scan)
+{
+    const bool reads = pr.reads != nullptr;
+    const uint32_t n = reads ? pr.n_reads : b.n_reads;
+    const uint64_t total = scan[n];
+    const uint32_t* start = reinterpret_cast<const uint32_t*>(b.sig.wstart);
+    uint32_t* gate = const_cast<uint32_t*>(b.gate);
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j + 1 < total; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t i = scan_find(scan, n, j);
+        if (j + 1 >= scan[i + 1]) continue;   // the read's last row
+        const uint64_t c = b.sig.wfirst[i] + (j - scan[i]);
+        if (start[c] <= start[c + 1]) continue;
+        if (!reads) {
+            gate[i] = E_DESTINATION_SIZE;
+            continue;
+        }
+        atomicOr(&pr.reads[i].flags, POD5_READ_FAIL);   // (a POD5 read: closed as window_sorted_kernel closes it)
+        for (uint32_t r = pr.first_row[i]; r < pr.first_row[i + 1]; ++r) gate[r] = E_DESTINATION_SIZE;
+        if (b.sig.norm.st) b.sig.norm.st[i].phase = NORM_DONE;
+    }
+}
+
 hipError_t scan_launches(uint32_t n, uint32_t align, const uint32_t* size, uint64_t* off, hipStream_t s)
 {
     hipLaunchKernelGGL(pack_scan_tiles_kernel, dim3(1), dim3(1024), 0, s, n, off);
@@ -413,7 +437,9 @@ hipError_t launch_window_check(const ReadBatch& b, const Pod5Reads& pr, const fl
     const hipError_t e = scan_launches(n, 1, w.count, w.scan, s);
     if (e != hipSuccess || b.sig.wrows < 2) return e;
     const uint64_t wgs = (b.sig.wrows + 255) / 256;
-    hipLaunchKernelGGL(window_sorted_kernel, dim3((uint32_t)(wgs < 4096u ? wgs : 4096u)), dim3(256), 0, s, b, pr, w.scan);
+    const dim3 grid((uint32_t)(wgs < 4096u ? wgs : 4096u));
+    if (b.sig.events) hipLaunchKernelGGL(event_sorted_kernel, grid, dim3(256), 0, s, b, pr, w.scan);   // (the event check: the starts are unsigned)
+    else hipLaunchKernelGGL(window_sorted_kernel, grid, dim3(256), 0, s, b, pr, w.scan);
     return hipGetLastError();
 }
 

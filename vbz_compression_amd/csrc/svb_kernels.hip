@@ -1930,6 +1930,107 @@ __device__ __forceinline__ WindowStore<OUT, true> row_window_store(const ReadBat
     return st;
 }
 
+// the event sink of a row of a read, from the plan: the row's samples lie at s0 of the read's signal
+template <int OUT>
+__device__ __forceinline__ EventStore row_event_store(const ReadBatch& b, const Pod5Reads& pr, const Pod5Row& rw)
+{
+    uint32_t rb = 0, rend = pr.reads[rw.read].T;
+    if (OUT & SIG_RANGE) {
+        const uint2 g = pr.range[rw.read];
+        rb = g.x;
+        rend = g.y;
+    }
+    EventStore st{ event_constants(b, rw.read, rb, rend) };
+    st.begin_row(rw.s0);
+    return st;
+}
+
+// Signal events (SignalOut::events), the two launches around the event pass: one thread per row of a read that passed the event check.
+// scan: the exclusive scan of the passing reads' row counts (launch_window_check), which says whose row the j-th is; a read the sorted
+// pass closed behind the scan (its gate; POD5: POD5_READ_FAIL) is passed over, so not one byte of its rows is written.
+// *rb, *re: the signal of read i (its clamped range); false: the read is closed
+__device__ __forceinline__ bool event_read_open(const ReadBatch& b, const Pod5Reads& pr, uint32_t i, uint32_t* rb, uint32_t* re)
+{
+    if (pr.reads) {
+        if (pr.reads[i].flags & POD5_READ_FAIL) return false;
+        *rb = 0;
+        *re = pr.reads[i].T;
+        if (b.sig.ranged()) {
+            const uint2 g = pr.range[i];
+            *rb = g.x;
+            *re = g.y;
+        }
+        return true;
+    }
+    if (b.gate[i] >= GATE_SKIP) return false;
+    sample_range(b.sig, i, b.dst_cap[i] >> 1, rb, re);
+    return true;
+}
+
+__global__ __launch_bounds__(WG) void event_zero_kernel(ReadBatch b, Pod5Reads pr, const uint64_t* scan)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    const uint64_t total = scan[n];
+    for (uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x; j < total; j += (uint64_t)gridDim.x * WG) {
+        const uint32_t i = scan_find(scan, n, j);
+        uint32_t rb, re;
+        if (!event_read_open(b, pr, i, &rb, &re)) continue;
+        const uint64_t c = b.sig.wfirst[i] + (j - scan[i]);
+        *reinterpret_cast<uint4*>(b.sig.event_moments(b.dst) + 2ull * c) = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// The record of an event of cnt >= 1 samples from its exact moments: m = S1 / n, v = S2 / n - m m clamped at 0, r = sqrt(v),
+// mean = float32((m + o) s), sd = float32(r |s|) -- float64, every operation rounded once.  Contraction is off for this body: the
+// _rn intrinsics of this compiler are the plain operators, and m m would be fused into the subtraction (one rounding less than numpy's;
+// one sd in a few million then rounds the other way to float32).  The device's sqrt(double) is correctly rounded.
+__device__ __forceinline__ void event_record(long long S1, unsigned long long S2, uint32_t cnt, float o, float s, float* mean, float* sd)
+{
+#pragma clang fp contract(off)
+    const double nd = (double)cnt;
+    const double m = (double)S1 / nd;
+    const double q = (double)S2 / nd;
+    const double mm = m * m;
+    double v = q - mm;
+    if (v < 0.0) v = 0.0;
+    const double t = m + (double)o;
+    *mean = __double2float_rn(t * (double)s);
+    *sd = __double2float_rn(__dsqrt_rn(v) * fabs((double)s));
+}
+
+// The records of the rows (include/vbz_gpu.h: vbz_gpu_event): n = z - a from the starts and the signal's length alone, the rest by
+// event_record.  One 16-byte store per row.
+__global__ __launch_bounds__(WG) void event_finish_kernel(ReadBatch b, Pod5Reads pr, const float* offset, const float* scale, const uint64_t* scan, uint4* out)
+{
+    const unsigned long long* mom = b.sig.event_moments(b.dst);
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    const uint64_t total = scan[n];
+    const uint32_t* start = reinterpret_cast<const uint32_t*>(b.sig.wstart);
+    for (uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x; j < total; j += (uint64_t)gridDim.x * WG) {
+        const uint32_t i = scan_find(scan, n, j);
+        uint32_t rb, re;
+        if (!event_read_open(b, pr, i, &rb, &re)) continue;
+        const uint32_t T = re - rb;
+        const uint64_t c = b.sig.wfirst[i] + (j - scan[i]);
+        const uint32_t a0 = start[c], a = a0 < T ? a0 : T;
+        uint32_t z = T;
+        if (j + 1 < scan[i + 1]) {   // (not the read's last row)
+            const uint32_t z0 = start[c + 1];
+            z = z0 < T ? z0 : T;
+        }
+        const uint32_t cnt = z - a;   // (sorted starts: z >= a)
+        float o = offset ? offset[i] : 0.0f, s = scale ? scale[i] : 1.0f;
+        if (b.sig.norm.st) {   // the read's own statistics: the store's constants as norm_finish makes them
+            const float2 ss = b.sig.norm.ss[i];
+            o = -ss.x;
+            s = __double2float_rn(__ddiv_rn(1.0, (double)ss.y));
+        }
+        float mean = 0.0f, sd = 0.0f;
+        if (cnt != 0) event_record((long long)mom[2ull * c], mom[2ull * c + 1u], cnt, o, s, &mean, &sd);
+        out[c] = make_uint4(__float_as_uint(mean), __float_as_uint(sd), cnt, 0u);
+    }
+}
+
 // The pad of the windows (SignalOut::wfirst), behind the window check and independent of the decode: one wavefront per row of a read that
 // passed.  scan: the exclusive scan of the passing reads' row counts (launch_window_check), which says whose row the j-th is.  Row c of a
 // signal of T samples: positions p with start[c] + p < 0 or start[c] + p >= T take the pad value -- exactly the positions no sample
@@ -2006,7 +2107,8 @@ __device__ __forceinline__ ChunkStore<OUT, true> row_chunk_store(const ReadBatch
 template <int OUT>
 __device__ __forceinline__ auto row_store(const ReadBatch& b, const Pod5Reads& pr, const Pod5Row& rw, uint32_t r, uint32_t count)
 {
-    if constexpr ((OUT & SIG_WINDOW) != 0) return row_window_store<OUT>(b, pr, rw);
+    if constexpr ((OUT & SIG_EVENT) != 0) return row_event_store<OUT>(b, pr, rw);
+    else if constexpr ((OUT & SIG_WINDOW) != 0) return row_window_store<OUT>(b, pr, rw);
     else if constexpr ((OUT & SIG_CHUNK) != 0) return row_chunk_store<OUT>(b, pr, rw, count);
     else return dec_store<2, OUT>(b.dst, b.dst_off, &b, r, count, rw.read);
 }
@@ -2263,11 +2365,12 @@ hipError_t svb_dispatch_elem(int integer_size, bool zigzag, F&& f)
 }
 
 // b.sig's store -> f(OUT): OUT = b.sig.type, | SIG_CHUNK with chunk rows, | SIG_CHUNK | SIG_WINDOW with window rows, | SIG_RANGE with range
-// tables (DecStore; chunk and window stores only)
+// tables (DecStore; chunk and window stores only); an event call: SIG_EVENT [| SIG_RANGE], whatever the type
 template <class F>
 hipError_t svb_dispatch_store(const ReadBatch& b, F&& f)
 {
     constexpr uint32_t WIN = SIG_CHUNK | SIG_WINDOW;
+    if (b.sig.events) return b.sig.ranged() ? f(Int<SIG_EVENT | SIG_RANGE>{}) : f(Int<SIG_EVENT>{});   // (an event call: no sample is stored)
     switch (b.sig.type == SIG_NONE ? SIG_NONE : b.sig.type | (b.sig.row ? SIG_CHUNK : 0u) | (b.sig.wfirst ? WIN : 0u) | (b.sig.ranged() ? SIG_RANGE : 0u)) {
     case SIG_F32 | WIN: return f(Int<SIG_F32 | WIN>{});
     case SIG_F16 | WIN: return f(Int<SIG_F16 | WIN>{});
@@ -2487,8 +2590,29 @@ hipError_t launch_window_pad(const ReadBatch& b, const Pod5Reads& pr, const Wind
     return hipGetLastError();
 }
 
+static uint32_t event_grid(uint64_t rows)
+{
+    const uint64_t wgs = (rows + WG - 1) / WG;
+    return (uint32_t)(wgs < 16384u ? wgs : 16384u);
+}
+hipError_t launch_event_zero(const ReadBatch& b, const Pod5Reads& pr, const WindowScratch& w, hipStream_t s)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (n == 0 || b.sig.wrows == 0) return hipSuccess;
+    hipLaunchKernelGGL(event_zero_kernel, dim3(event_grid(b.sig.wrows)), dim3(WG), 0, s, b, pr, w.scan);
+    return hipGetLastError();
+}
+hipError_t launch_event_finish(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, void* out,
+                               hipStream_t s)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (n == 0 || b.sig.wrows == 0) return hipSuccess;
+    hipLaunchKernelGGL(event_finish_kernel, dim3(event_grid(b.sig.wrows)), dim3(WG), 0, s, b, pr, offset, scale, w.scan, reinterpret_cast<uint4*>(out));
+    return hipGetLastError();
+}
+
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s, const TrimOut* trim, const WindowScratch* win)
+                                     hipStream_t s, const TrimOut* trim, const WindowScratch* win, void* event_out)
 {
     const uint32_t most = std::max(b.n_reads, pr.n_reads);
     if (most == 0) return hipSuccess;
@@ -2500,7 +2624,7 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
         if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_window_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale);
         else hipLaunchKernelGGL(pod5_reads_plan_window_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale);
         hipError_t ew = launch_window_check(b, pr, nullptr, nullptr, *win, s);
-        if (ew == hipSuccess) ew = launch_window_pad(b, pr, *win, s);
+        if (ew == hipSuccess) ew = b.sig.events ? launch_event_zero(b, pr, *win, s) : launch_window_pad(b, pr, *win, s);
         if (ew != hipSuccess) return ew;
     } else if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
     else hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
@@ -2522,8 +2646,12 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
             if (e != hipSuccess) return e;
         }
     }
+    if (b.sig.events) {   // the records, behind the event pass and the counting passes
+        e = launch_event_finish(b, pr, offset, scale, *win, event_out, s);
+        if (e != hipSuccess) return e;
+    }
     if (pr.read_result && pr.n_reads) {
-        const uint32_t elem = b.sig.type == SIG_F32 ? 4u : 2u;
+        const uint32_t elem = b.sig.type == SIG_F32 && !b.sig.events ? 4u : 2u;   // (an event call: the int16 decode's verdicts)
         hipLaunchKernelGGL(pod5_read_results_kernel, dim3((pr.n_reads + WG - 1) / WG), t, 0, s, b, pr, elem);
     }
     return hipGetLastError();

@@ -1,6 +1,7 @@
 // svb_store.h -- the output side of the svb decoder (svb_kernels.hip): the sinks its decode loops store through, and what only they use.
 // A sink is what svb_decode_range, I16DecPairs::run and svb16_decode_row (`class Store`) hand their values to:
 //   static constexpr uint32_t BYTES   bytes per value in result[]
+//   begin_row(s)                      (the sinks that walk a POD5 read's rows in turn) the values handed to put() from here on begin at s of the read
 //   aligned()                         whole 16-byte lines may be stored: the tile loop's lanes of VPL values, and I16DecPairs at all
 //   put(i0, valid, base, s)           one lane's values i0 ... i0 + valid - 1 of the workgroup's (base + s[k]), every lane at the same point
 //   finish()                          once per read, by the whole workgroup (svb_decode_range: the range at the read's start)
@@ -518,6 +519,147 @@ struct WindowStore
     __device__ __forceinline__ void finish() const {}   // (the windows' pad: window_pad_kernel)
     __device__ __forceinline__ void done() const {}
     __device__ __forceinline__ bool aligned() const { return (((uintptr_t)arena) & 15u) == 0; }
+};
+
+// ---- event sink (SignalOut::events; OUT = SIG_EVENT [| SIG_RANGE]): per-event exact moments, no sample stored ---------------------------
+// Event c of the read's n rows holds the positions start[c] <= q < start[c + 1] of the signal (the read's samples [rb, rb + T); the last
+// event runs to T; positions in front of start[0] belong to no event).  The starts are sorted (the event check), so a lane's eight
+// consecutive samples lie in consecutive events: the lane adds up each run of samples that share an event -- sum x in 32 bits, sum x^2 in
+// 64, exact -- and adds the run to the event's two 64-bit words of moments when the run ends (no-return global adds: integer sums, so the
+// order of the additions does not matter).  The words were zeroed by a launch in front (launch_event_zero).  The rule is the same for a
+// read, a segment, a POD5 row and a range; no cross-lane exchange.
+struct EventK
+{
+    unsigned long long* mom = nullptr;   // the read's first row's moments (two words a row)
+    const uint32_t* start = nullptr;     // its rows' starts
+    uint32_t n = 0;                      // rows
+    uint32_t rb = 0, T = 0;              // the signal: samples [rb, rb + T) of the read
+    uint32_t bias = 0;                   // SigK::bias
+};
+
+// the events of the read whose entry of SignalOut::wfirst is i (as window_constants: a pair that is not rows of the arena gives no row)
+__device__ __forceinline__ EventK event_constants(const ReadBatch& b, uint32_t i, uint32_t rb, uint32_t rend)
+{
+    EventK k;
+    const uint64_t a = b.sig.wfirst[i], z = b.sig.wfirst[i + 1];
+    const bool ok = a <= z && z <= b.sig.wrows && z - a <= WINDOW_READ_ROWS_MAX;
+    k.n = ok ? (uint32_t)(z - a) : 0u;
+    k.mom = b.sig.event_moments(b.dst) + 2ull * (ok ? a : 0ull);
+    k.start = reinterpret_cast<const uint32_t*>(b.sig.wstart) + (ok ? a : 0ull);
+    k.rb = rb;
+    k.T = rend - rb;
+    k.bias = b.sig.bias;
+    return k;
+}
+
+// The event sink of one workgroup (the contract: this file's head): its values lie at s0 of the read (a row of a POD5 read: begin_row();
+// else 0 -- put() gets positions in the read).  As for the window sink the tile's samples [ta, tb) of the signal are workgroup-uniform,
+// and so is the bracket [lo, hi) of the starts that lie inside the tile: lo the first start behind ta, hi the first at or behind tb.
+// Both ends only advance, 64 starts a ballot step, with one binary search at the workgroup's first tile that holds samples.  The event of
+// a lane's first sample is the last start at or in front of it: all of those lie in front of lo or inside the bracket, so the lane
+// bisects the bracket alone (at most log2 of the tile's starts + 1 steps), then walks forward sample by sample.
+struct EventStore
+{
+    static constexpr uint32_t UNSET = 0xFFFFFFFFu, BYTES = 2;   // (result[] is the int16 decode's)
+    EventK ek;
+    uint32_t s0 = 0;
+    mutable uint32_t lo = UNSET, hi = 0, at = 0;   // the bracket, and the first sample of the tile it was made for
+
+    __device__ __forceinline__ void begin_row(uint32_t s) { s0 = s; }
+    __device__ __forceinline__ bool aligned() const { return true; }   // (nothing is stored)
+    // the first start behind position q (n: none): wave-uniform arguments, wave-uniform result
+    __device__ __forceinline__ uint32_t first_behind(uint32_t q) const
+    {
+        uint32_t a = 0, z = ek.n;
+        while (a < z) {
+            const uint32_t mid = a + ((z - a) >> 1);
+            if (ek.start[mid] > q) z = mid;
+            else a = mid + 1u;
+        }
+        return a;
+    }
+    // the first row at or behind c at which pred fails (n: none), pred holding on a prefix of [c, n): by the whole wavefront
+    template <class P>
+    __device__ __forceinline__ uint32_t advance(uint32_t c, P pred) const
+    {
+        const uint32_t lane = threadIdx.x & 63u;
+        for (;;) {
+            const uint32_t w = c + lane;
+            const uint64_t m = __ballot(w < ek.n && pred(w) ? 1 : 0);
+            const uint32_t k = m == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~m);
+            c += k;
+            if (k < 64u) return c;
+        }
+    }
+    // a run of samples of row c: its sums into the row's moments
+    __device__ __forceinline__ void add(uint32_t c, int32_t s1, uint64_t s2) const
+    {
+        atomicAdd(ek.mom + 2ull * c, (unsigned long long)(long long)s1);
+        atomicAdd(ek.mom + 2ull * c + 1u, (unsigned long long)s2);
+    }
+
+    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
+    {
+        if (ek.n == 0) return;
+        // the tile (workgroup-uniform): values t0 ... t0 + 8 WG - 1 of the workgroup's, samples [ta, tb) of the signal
+        const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(i0 - 8u * threadIdx.x));
+        const int64_t tq = (int64_t)s0 + (int64_t)t0 - (int64_t)ek.rb;
+        const int64_t ta = tq < 0 ? 0 : tq, tb = tq + 8 * WG < (int64_t)ek.T ? tq + 8 * WG : (int64_t)ek.T;
+        if (ta >= tb) return;   // no sample of the signal in the tile
+        uint32_t a = lo, z = hi;
+        if (a == UNSET || ta < (int64_t)at) {
+            a = first_behind((uint32_t)ta);
+            z = a;
+        } else {
+            a = advance(a, [&](uint32_t w) { return (int64_t)ek.start[w] <= ta; });
+        }
+        z = advance(z > a ? z : a, [&](uint32_t w) { return (int64_t)ek.start[w] < tb; });
+        a = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
+        z = (uint32_t)__builtin_amdgcn_readfirstlane((int)z);
+        lo = a;
+        hi = z;
+        at = (uint32_t)ta;
+        // the lane: values jl ... jh - 1 of its eight are samples of the signal, the first of them at position qa
+        const int64_t q0 = tq + 8 * (int64_t)threadIdx.x;
+        const int64_t l0 = q0 < 0 ? -q0 : 0, h0 = (int64_t)ek.T - q0;
+        const int jl = l0 < (int64_t)valid ? (int)l0 : valid, jh = h0 < (int64_t)valid ? (h0 < 0 ? 0 : (int)h0) : valid;
+        if (jl >= jh) return;
+        const uint32_t qa = (uint32_t)(q0 + jl);
+        // c: the first row whose start lies behind qa -- row c - 1 is open (c == 0: none yet)
+        uint32_t c = a, ce = z;
+        while (c < ce) {
+            const uint32_t mid = c + ((ce - c) >> 1);
+            if (ek.start[mid] > qa) ce = mid;
+            else c = mid + 1u;
+        }
+        uint32_t next = c < ek.n ? ek.start[c] : UNSET;   // (UNSET: the last row is open; no sample lies at 2^32 - 1)
+        int32_t s1 = 0;
+        uint64_t s2 = 0;
+        uint32_t m = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j < jl || j >= jh) continue;
+            const uint32_t q = qa + (uint32_t)(j - jl);
+            if (q >= next) {   // the run ends: rows with equal starts in between stay empty
+                if (m != 0 && c != 0) add(c - 1u, s1, s2);
+                s1 = 0;
+                s2 = 0;
+                m = 0;
+                do {
+                    ++c;
+                    next = c < ek.n ? ek.start[c] : UNSET;
+                } while (q >= next);
+            }
+            const uint32_t v = base + s[j];
+            const int32_t x = ((int32_t)((v ^ ek.bias) << 16) >> 16) + (int32_t)ek.bias;   // (as sig_f32: the int16 or the uint16 value)
+            s1 += x;
+            s2 += (uint32_t)x * (uint32_t)x;   // (|x| < 2^16: the square fits 32 bits)
+            ++m;
+        }
+        if (m != 0 && c != 0) add(c - 1u, s1, s2);
+    }
+    __device__ __forceinline__ void finish() const {}
+    __device__ __forceinline__ void done() const {}
 };
 
 // ---- normalisation statistics (OUT = SIG_COUNT; vbz_kernels.h NormRead) -------------------------------------------------------------
@@ -1041,9 +1183,15 @@ template <int ELEM, int OUT>
 __device__ __forceinline__ auto dec_store(uint8_t* dst, const uint64_t* dst_off, const ReadBatch* b, uint32_t r, uint32_t count, uint32_t cr)
 {
     static_assert(OUT == SIG_NONE || ELEM == 2, "the typed stores are for int16 samples");
-    static_assert(!(OUT & SIG_RANGE) || (OUT & (SIG_CHUNK | SIG_COUNT)) != 0, "ranges: the chunk and window stores and the counting pass");
+    static_assert(!(OUT & SIG_RANGE) || (OUT & (SIG_CHUNK | SIG_COUNT | SIG_EVENT)) != 0, "ranges: the chunk, window and event sinks and the counting pass");
     static_assert(!(OUT & SIG_TRIM), "the trim sink is built from the read's TrimK");
+    static_assert(!(OUT & SIG_EVENT) || (OUT & ~(SIG_EVENT | SIG_RANGE)) == 0, "the event sink stores no sample: no output type");
     if constexpr (OUT == SIG_NONE) return RawStore<ELEM>{ dst + dst_off[r] };
+    else if constexpr ((OUT & SIG_EVENT) != 0) {
+        uint32_t rb = 0, rend = count;
+        if constexpr ((OUT & SIG_RANGE) != 0) sample_range(b->sig, r, count, &rb, &rend);   // the sink's read is the range
+        return EventStore{ event_constants(*b, b->sig.wmap ? b->sig.wmap[r] : r, rb, rend) };
+    }
     else if constexpr ((OUT & SIG_COUNT) != 0) return CountStore<(OUT & SIG_RANGE) != 0>(b, r, count);
     else if constexpr ((OUT & SIG_CHUNK) == 0) return TypedStore<OUT>{ dst + (dst_off[r] >> 1) * OutBytes<OUT>::value, sig_constants(*b, cr) };
     else {

@@ -220,6 +220,7 @@ struct vbz_gpu_ctx
     DevBuf sigmeta;            // typed decode: the int16 slot table and the per-read constants (TypedSlots), or the constants alone
     DevBuf chunkmeta;          // chunk layout: the per-read chunk counts
     DevBuf winmeta;            // signal windows: the per-read row counts and their scan (WindowScratch)
+    DevBuf evmeta;             // signal events: the rows' moments of a call whose caller takes none (two 64-bit words a row)
     DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call (NormTables)
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables, the reads' constants (Pod5Tables)
@@ -1367,6 +1368,57 @@ void window_out(const vbz_gpu_windows* w, void* out, ReadBatch* rb)
     rb->sig.pad = w->pad;
 }
 
+// the events of a *_signal_events_batch call: the struct's rules, the output type (records are float32), the tables and the arenas a call
+// with reads needs (n_out: the reads the tables have entries for), the arenas' alignment and extent
+static_assert(sizeof(vbz_gpu_events) == 32, "vbz_gpu_events is 32 bytes");
+static_assert(offsetof(vbz_gpu_events, event_rows) == 0 && offsetof(vbz_gpu_events, event_first) == 8 && offsetof(vbz_gpu_events, start) == 16 &&
+                  offsetof(vbz_gpu_events, flags) == 24 && offsetof(vbz_gpu_events, reserved) == 28,
+              "the fields of vbz_gpu_events");
+static_assert(sizeof(vbz_gpu_event) == 16 && offsetof(vbz_gpu_event, mean) == 0 && offsetof(vbz_gpu_event, sd) == 4 && offsetof(vbz_gpu_event, n) == 8 &&
+                  offsetof(vbz_gpu_event, zero) == 12,
+              "vbz_gpu_event is 16 bytes: mean, sd, n, zero");
+static_assert(sizeof(vbz_gpu_event_moments) == 16 && offsetof(vbz_gpu_event_moments, sum) == 0 && offsetof(vbz_gpu_event_moments, sumsq) == 8,
+              "vbz_gpu_event_moments is 16 bytes: sum, sumsq");
+bool events_ok(vbz_gpu_ctx* c, const vbz_gpu_events* ev, const vbz_gpu_signal_format* f, const vbz_gpu_event* out, const vbz_gpu_event_moments* moments,
+               uint32_t n_out)
+{
+    if (!ev) {
+        set_error(c, "events is NULL");
+        return false;
+    }
+    if (ev->flags != 0 || ev->reserved != 0) {
+        set_error(c, "events outside the rules (flags %u, reserved %u)", ev->flags, ev->reserved);
+        return false;
+    }
+    if (f->out_type != VBZ_GPU_SIGNAL_F32) {
+        set_error(c, "event records are float32 (out_type %u)", f->out_type);
+        return false;
+    }
+    if (n_out != 0 && (!ev->event_first || (!ev->start && ev->event_rows != 0) || !out)) {
+        set_error(c, "event_first, start or the event arena is NULL");
+        return false;
+    }
+    if ((((uintptr_t)out | (uintptr_t)moments) & 15u) != 0) {
+        set_error(c, "the event arena or the moments are not 16-byte aligned");
+        return false;
+    }
+    if (ev->event_rows > EXTENT_MAX / sizeof(vbz_gpu_event)) {
+        set_error(c, "declared event arena is not plausible (%llu rows of 16 bytes)", (unsigned long long)ev->event_rows);
+        return false;
+    }
+    return true;
+}
+// the event part of SignalOut (the windows' tables), and the arena the svb stage adds into: the rows' moments (the caller's, or the call's
+// scratch).  The records' arena is the finish launch's argument.
+void event_out(const vbz_gpu_events* ev, void* moments, ReadBatch* rb)
+{
+    rb->dst = (uint8_t*)moments;
+    rb->sig.wfirst = ev->event_first;
+    rb->sig.wstart = reinterpret_cast<const int32_t*>(ev->start);
+    rb->sig.wrows = ev->event_rows;
+    rb->sig.events = 1;
+}
+
 // the ranges of a *_range_batch call (nullable: the un-ranged call)
 static_assert(RANGE_STATS_RANGE == VBZ_GPU_RANGE_STATS_RANGE && RANGE_STATS_READ == VBZ_GPU_RANGE_STATS_READ, "the ABI's stats modes");
 static_assert(sizeof(vbz_gpu_sample_ranges) == 24, "vbz_gpu_sample_ranges is 24 bytes");
@@ -1472,7 +1524,8 @@ bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_po
 
 // TypedCall: one typed decode as its entry point states it (the table of entries: in front of them, below).  A part the entry does not
 // have keeps its default.  Where the entries' rules for a NULL differ, the entry says which one holds (Null); it is not inferred.
-enum class Typed { SIGNAL, CHUNKS, STATISTICS };   // what is stored: typed samples in the reads' slots; in chunks; nothing (the constants alone)
+enum class Typed { SIGNAL, CHUNKS, STATISTICS, EVENTS };   // what is stored: typed samples in the reads' slots; in chunks; nothing (the constants
+                                                           // alone); one record per caller-listed event
 enum class Null { ALLOWED, REFUSED, REFUSED_WITH_READS };   // REFUSED_WITH_READS: refused unless the call has no read to write an entry for
 struct TypedCall
 {
@@ -1487,6 +1540,9 @@ struct TypedCall
     bool with_windows = false;                  // CHUNKS, in place of a chunking (never both): rb.dst becomes the window arena and the svb
     const vbz_gpu_windows* win = nullptr;       // ... stage stores the typed samples into the reads' windows (untrusted: the window check
     void* win_out = nullptr;                    // ... gates every read whose rows or starts are not in order before anything of it is stored)
+    const vbz_gpu_events* ev = nullptr;         // EVENTS: rb.dst becomes the rows' moments; the svb stage adds them up and a launch behind
+    vbz_gpu_event* ev_out = nullptr;            // ... it writes the records to ev_out (untrusted tables: the event check is the window
+    vbz_gpu_event_moments* ev_moments = nullptr;   // ... check, unsigned).  ev_moments NULL: the moments live in the call's scratch
     const vbz_gpu_normalization* norm = nullptr;   // non-null: a normalising decode (the constants from the reads' statistics, into cal
     Null norm_null = Null::ALLOWED;                // ... and shift_scale)
     float* shift_scale = nullptr;
@@ -1509,6 +1565,11 @@ struct TypedCall
     TypedCall& windows(const vbz_gpu_windows* w, void* arena)
     {
         with_windows = true, win = w, win_out = arena;
+        return *this;
+    }
+    TypedCall& events(const vbz_gpu_events* e, vbz_gpu_event* arena, vbz_gpu_event_moments* moments)
+    {
+        ev = e, ev_out = arena, ev_moments = moments;
         return *this;
     }
     TypedCall& normalise(const vbz_gpu_normalization* m, Null m_null, float* ss, Null ss_null)
@@ -1580,13 +1641,20 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (reads && pod5_reads_begin(c, n, reads, reads->read_result, &pr, &read_cal) != 0) return -1;
     if (n != 0 && !own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
     uint64_t dst_bytes = bt->dst_bytes;
-    const bool chunks = out && out->kind == Typed::CHUNKS, stats = out && out->kind == Typed::STATISTICS;
+    const bool events = out && out->kind == Typed::EVENTS;   // (an event call takes the window call's way: its tables are the windows')
+    const bool chunks = out && (out->kind == Typed::CHUNKS || events), stats = out && out->kind == Typed::STATISTICS;
     const uint32_t n_const = reads ? reads->n_reads : n;   // how many reads have constants and statistics
     float2* cal = nullptr;   // the per-read constants
-    const bool windows = chunks && out->with_windows;
+    const bool windows = chunks && (out->with_windows || events);
     WindowScratch wscratch;
     if (windows) {
-        window_out(out->win, out->win_out, &rb);
+        if (events) {
+            void* const moments = out->ev_moments ? (void*)out->ev_moments : (void*)ensure_array<vbz_gpu_event_moments>(c, c->evmeta, std::max<uint64_t>(out->ev->event_rows, 1));
+            if (!moments) return -1;
+            event_out(out->ev, moments, &rb);
+        } else {
+            window_out(out->win, out->win_out, &rb);
+        }
         if (!ensure_carved(c, c->winmeta, wscratch, n_const)) return -1;
     } else if (chunks) {
         chunk_out(out->ch, out->chunk_first, out->chunks, &rb);
@@ -1626,7 +1694,8 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (windows && !reads) {   // (the window check, and the pad, which wants the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "window_slots");
         HIPCHK(c, launch_window_check(rb, Pod5Reads(), out->f->offset, out->f->scale, wscratch, s), "window check launch");
-        HIPCHK(c, launch_window_pad(rb, Pod5Reads(), wscratch, s), "window pad launch");
+        if (events) HIPCHK(c, launch_event_zero(rb, Pod5Reads(), wscratch, s), "event zero launch");
+        else HIPCHK(c, launch_window_pad(rb, Pod5Reads(), wscratch, s), "window pad launch");
     } else if (chunks && !reads) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "chunk_slots");
         HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, out->f->offset, out->f->scale, rb.sig.chunk_len, rb.sig.step, out->chunk_first, out->chunk_rows,
@@ -1657,12 +1726,19 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         }
         Timed t(c, "svb_decode");
         HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s, c->trim.begin ? &c->trim : nullptr,
-                                            windows ? &wscratch : nullptr),
+                                            windows ? &wscratch : nullptr, events ? out->ev_out : nullptr),
                "svb16_decode (reads) launch");
         return 0;
     }
+    // an event call: the records, behind everything the call has queued (the halves and the routed reads are joined by then)
+    auto finish = [&](int rc) {
+        if (rc != 0 || !events) return rc;
+        Timed t(c, "event_finish");
+        HIPCHK(c, launch_event_finish(rb, Pod5Reads(), out->f->offset, out->f->scale, wscratch, out->ev_out, s), "event finish launch");
+        return 0;
+    };
     if (by_shape || !routing_applies(c, o, dst_bytes, n))
-        return split ? decompress_split(c, rb, dst_bytes, o) : decompress_group(c, rb, dst_bytes, o, by_shape);
+        return finish(split ? decompress_split(c, rb, dst_bytes, o) : decompress_group(c, rb, dst_bytes, o, by_shape));
     Routed r;
     if (route(c, rb, rb.dst_cap, &r) != 0) return -1;   // by the decoded size
     ReadBatch small = rb;
@@ -1672,14 +1748,14 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (rc == 0 && (split ? decompress_split(c, small, dst_bytes, o) : decompress_group(c, small, dst_bytes, o, false)) != 0) rc = -1;
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
     if (route_join(c, r, bt->result) != 0) rc = -1;
-    return rc;
+    return finish(rc);
 }
 
 // The one way into a typed decode: every check of every entry, in this order, then the decode.  A call with one fault gets that fault's
 // message; with several, the first in this order.
 int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const TypedCall& call)
 {
-    static const char* const WHAT[] = { "signal", "chunk", "statistics" };
+    static const char* const WHAT[] = { "signal", "chunk", "statistics", "event" };
     if (!c || !bt) return -1;                                                                                        // 1
     DeviceGuard dg(c->device);                                                                                       // 2
     TypedCall t = call;
@@ -1695,7 +1771,9 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
         set_error(c, "shift_scale is NULL");
         return -2;
     }
-    if (t.kind == Typed::CHUNKS && t.with_windows) {                                                                 // 8 (windows in place of a chunking)
+    if (t.kind == Typed::EVENTS) {                                                                                   // 8 (events)
+        if (!events_ok(c, t.ev, t.f, t.ev_out, t.ev_moments, n_out)) return -2;
+    } else if (t.kind == Typed::CHUNKS && t.with_windows) {                                                          // 8 (windows in place of a chunking)
         if (!windows_ok(c, t.win, t.win_out, n_out, t.f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u)) return -2;
     } else if (t.kind == Typed::CHUNKS) {
         if (!chunking_ok(c, t.ch)) return -2;
@@ -1925,16 +2003,18 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
     return 0;
 }
 
-// The sixteen typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
+// The eighteen typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
 //
 //   vbz_gpu_..._batch             kind        sized  chunking  norm      shift_scale          ranges    reads  trim   (chunking "windows": a
-//                                                                                                                   vbz_gpu_windows in its place)
+//                                                                                                                   vbz_gpu_windows in its place;
+//                                                                                                                   "events": a vbz_gpu_events)
 //   decompress_signal             SIGNAL      arg    -         -         -                    -         -      -
 //   decompress_signal_norm        SIGNAL      arg    -         required  nullable             -         -      -
 //   decompress_chunks             CHUNKS      arg    yes       -         -                    -         -      -
 //   decompress_chunks_norm        CHUNKS      arg    yes       required  nullable             -         -      -
 //   decompress_chunks_range       CHUNKS      arg    yes       nullable  nullable             nullable  -      -
 //   decompress_windows            CHUNKS      arg    windows   nullable  nullable             nullable  -      -
+//   signal_events                 EVENTS      arg    events    nullable  nullable             nullable  -      -
 //   signal_norm                   STATISTICS  arg    -         required  required             -         -      -
 //   signal_norm_range             STATISTICS  arg    -         required  required             nullable  -      -
 //   signal_trim                   STATISTICS  arg    -         required  nullable             nullable  -      yes
@@ -1942,6 +2022,7 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   pod5_decompress_chunks        CHUNKS      0      yes       nullable  nullable             -         yes    -
 //   pod5_decompress_chunks_range  CHUNKS      0      yes       nullable  nullable             nullable  yes    -
 //   pod5_decompress_windows       CHUNKS      0      windows   nullable  nullable             nullable  yes    -
+//   pod5_signal_events            EVENTS      0      events    nullable  nullable             nullable  yes    -
 //   pod5_signal_norm              STATISTICS  0      -         required  required with reads  -         yes    -
 //   pod5_signal_norm_range        STATISTICS  0      -         required  required with reads  nullable  yes    -
 //   pod5_signal_trim              STATISTICS  0      -         required  nullable             nullable  yes    yes
@@ -1949,10 +2030,11 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
 //   only when reads->n_reads != 0.
-// - norm: NULL is a chunk decode without normalisation in decompress_chunks_range, the POD5 chunk entries and the two window entries, and a
-//   fault everywhere else.
+// - norm: NULL is a chunk decode without normalisation in decompress_chunks_range, the POD5 chunk entries and the two window entries,
+//   records under the format's constants in the two event entries, and a fault everywhere else.
 // - chunk_first and the chunk arena may be NULL when there is no read to store: batch->n_reads == 0, or, over POD5 reads,
-//   reads->n_reads == 0 (whatever the number of rows).  The window entries: window_first, start (with window_rows != 0) and the arena, likewise.
+//   reads->n_reads == 0 (whatever the number of rows).  The window entries: window_first, start (with window_rows != 0) and the arena, likewise;
+//   the event entries: event_first, start (with event_rows != 0) and the event arena.
 int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::SIGNAL, sized).format(f));
@@ -1991,6 +2073,14 @@ int vbz_gpu_decompress_windows_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, co
                                      const vbz_gpu_sample_ranges* ranges)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).windows(windows, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_signal_events_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                const vbz_gpu_events* events, vbz_gpu_event* out, vbz_gpu_event_moments* moments, const vbz_gpu_normalization* norm,
+                                float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::EVENTS, sized).format(f).events(events, out, moments)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
@@ -2044,6 +2134,14 @@ int vbz_gpu_pod5_decompress_windows_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* b
                                           const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).windows(windows, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_pod5_signal_events_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                     const vbz_gpu_pod5_reads* reads, const vbz_gpu_events* events, vbz_gpu_event* out, vbz_gpu_event_moments* moments,
+                                     const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::EVENTS, 0).format(f).pod5_reads(reads).events(events, out, moments)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 

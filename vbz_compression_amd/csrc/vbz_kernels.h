@@ -32,6 +32,7 @@ constexpr uint32_t SIG_COUNT = 8;   // the svb decoder's counting pass of a norm
 constexpr uint32_t SIG_RANGE = 16;  // (or-ed into a chunk store's or the counting pass's OUT: only the samples of SignalOut's per-read range)
 constexpr uint32_t SIG_TRIM = 32;   // the svb decoder's trim pass behind the counting passes (OUT only: it stores nothing; TrimOut below)
 constexpr uint32_t SIG_WINDOW = 64; // (or-ed into a chunk store's OUT: the rows are caller-listed windows of the signal -- SignalOut::wfirst / wstart)
+constexpr uint32_t SIG_EVENT = 128; // the svb decoder's event pass (OUT only, | SIG_RANGE: it stores no sample; SignalOut::events)
 constexpr uint32_t RANGE_STATS_RANGE = 0, RANGE_STATS_READ = 1;   // (= VBZ_GPU_RANGE_STATS_*)
 constexpr uint32_t CHUNK_PAD = 0, CHUNK_END = 1;
 
@@ -80,6 +81,7 @@ struct SignalOut
     const uint32_t* rend = nullptr;
     const uint32_t* rmap = nullptr;
     uint32_t rstats = RANGE_STATS_RANGE;
+    uint32_t events = 0;   // != 0: an event call (below; the word fills the struct's padding: no kernel's arguments move)
     __host__ __device__ bool ranged() const { return rbegin || rend; }
     __host__ __device__ bool ranged_stats() const { return ranged() && rstats == RANGE_STATS_RANGE; }
     // Signal windows (vbz_gpu_*_windows_batch; `row` stays NULL): read i owns rows wfirst[i] ... wfirst[i + 1] - 1 of the [wrows, chunk_len]
@@ -90,6 +92,11 @@ struct SignalOut
     const int32_t* wstart = nullptr;
     const uint32_t* wmap = nullptr;
     uint64_t wrows = 0;
+    // Signal events (vbz_gpu_*_signal_events_batch; `events` != 0).  The tables are the windows' -- read i owns rows wfirst[i] ...
+    // wfirst[i + 1] - 1 of wrows, wstart[c] (taken as uint32) is where event c begins in the read's signal, the window check is the event
+    // check -- and the arena at dst holds the rows' exact moments: {sum x, sum x^2} of row c are the two 64-bit words at dst + 16 c, zeroed
+    // by launch_event_zero, added to by the event pass (OUT = SIG_EVENT), read by launch_event_finish, which writes the records.
+    __host__ __device__ unsigned long long* event_moments(uint8_t* dst) const { return reinterpret_cast<unsigned long long*>(dst); }
 };
 constexpr uint32_t WINDOW_READ_ROWS_MAX = 0x7FFFFFFFu;   // rows one read may own (the window check refuses more)
 
@@ -282,6 +289,14 @@ struct WindowScratch
 };
 hipError_t launch_window_check(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, hipStream_t s);
 hipError_t launch_window_pad(const ReadBatch& b, const Pod5Reads& pr, const WindowScratch& w, hipStream_t s);
+// Signal events (SignalOut::events), the launches around the event pass (svb_kernels.hip), both one thread per row counted in w.scan and both
+// passing over the rows of a read the event check has closed.  launch_event_zero, behind launch_window_check: the rows' moments = 0.
+// launch_event_finish, behind the event pass (and the counting passes of a normalising call): the rows' records (include/vbz_gpu.h:
+// vbz_gpu_event) from their moments, into `out` -- the read's constants are {offset[i], scale[i]} (NULL: 0 / 1), or with b.sig.norm.st the
+// read's {-shift, float32(1 / scale)} of b.sig.norm.ss.
+hipError_t launch_event_zero(const ReadBatch& b, const Pod5Reads& pr, const WindowScratch& w, hipStream_t s);
+hipError_t launch_event_finish(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, void* out,
+                               hipStream_t s);
 // row j of the rows counted in scan (n + 1 offsets, scan[0] = 0 <= j < scan[n]) -> its read: the last k with scan[k] <= j
 __device__ inline uint32_t scan_find(const uint64_t* scan, uint32_t n, uint64_t j)
 {
@@ -306,8 +321,9 @@ hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_sam
 // (one workgroup per read, its rows in turn), the store (one workgroup per row; none for the statistics alone, whose first counting
 // pass gives the rows' verdicts), the read results.  b.sig.rbegin / rend: per READ; pr.range must then be set (the plan fills it).
 // b.sig.wfirst (a window call; b.sig.row must be NULL): win must be set; the window check and the pad launch follow the plan.
+// b.sig.events (an event call): the same with the zero launch in the pad's place, and the finish launch into event_out behind the passes.
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s, const TrimOut* trim = nullptr, const WindowScratch* win = nullptr);
+                                     hipStream_t s, const TrimOut* trim = nullptr, const WindowScratch* win = nullptr, void* event_out = nullptr);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
 // bounds the total segment count (the grid); seg_* are scratch arrays of max_segs entries.  Not for the nibble codec.
