@@ -592,6 +592,77 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_events_batch(vbz_gpu_ctx* ctx, const vbz_gpu_
                                                 const vbz_gpu_events* events, vbz_gpu_event* out, vbz_gpu_event_moments* moments,
                                                 const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges);
 
+/* Signal segmentation.  The event calls above take the events' starts from the caller.  A re-squiggle or event-align tool has no move
+ * table to take them from: it segments the raw signal itself.  The two calls below find every read's event starts on the device and
+ * write them in the layout vbz_gpu_events reads as it stands: decode -> segment -> per-event records stays on the context's stream, and
+ * no sample is stored anywhere.  This library was written without the source of any segmentation tool: the rule below is the contract.
+ * It is the familiar two-window t-statistic with a local non-maximum suppression as the picker, so every position's verdict is a function
+ * of a bounded neighbourhood and the result is reproducible bit for bit (tests/segment_ref.py).
+ * The signal is the read's samples x[b:e) of T' = e - b raw 16-bit values (int16, or uint16 with is_signed == 0), ranges clamped exactly
+ * as in the *_range_batch calls (ranges NULL, or both tables NULL: the whole read; ranges->stats is ignored).  Positions q are positions
+ * in this signal, the convention of vbz_gpu_events.start.
+ * Parameters: the short detector has window w1 = short_window, 1 ... 32, and threshold t1 = short_threshold; the long one w2 =
+ * long_window, 0 ... 32 (0: there is no second detector, long_threshold is ignored) and t2 = long_threshold; thresholds are finite
+ * float32 > 0; the radius r = radius is 1 ... 32.
+ * Detector d (window w, threshold t): s_d[q] = 0 unless w <= q <= T' - w.  For such a q, in exact integers: A = sum x[q - w : q),
+ * B = sum x[q : q + w), A2 and B2 the sums of squares over the same two windows, N = w (A - B)^2, D = max(w (A2 + B2) - A^2 - B^2, 1).
+ * With w <= 32, N < 2^47 and D < 2^43: both fit int64 and are exact in float64.  s_d[q] = (float64(N) / float64(D)) / (float64(t) *
+ * float64(t)): one multiply and two divisions, each rounded to nearest even, none fused.  N / D is the squared t-statistic
+ * w dmean^2 / (var_a + var_b); it does not change under offset and scale, so the call takes no format and no normalisation.  D = 0 (both
+ * windows constant) is taken as 1: a step between two plateaus scores as high as the integers allow, a flat stretch scores 0.
+ * The score is s[q] = max(s_1[q], s_2[q]).
+ * Boundary: q in 1 ... T' - 1 is a boundary when s[q] >= 1, s[q] > s[j] for every j in [max(q - r, 0), q), and s[q] >= s[j] for every j
+ * in (q, min(q + r, T')].  Of equal scores the first wins: a later equal score within r of an earlier one is suppressed, whether or not
+ * the earlier one is itself a boundary.  Two boundaries are therefore more than r apart.
+ * The rows of a read: none when T' == 0; otherwise row 0 starts at 0 and one row follows per boundary, ascending.  Hence
+ * rows <= 2 + T' / (r + 1) (integer division): a caller sizes start[] from that bound -- and from vbz_gpu_range_samples_batch's output
+ * when ranges are used -- without a synchronisation.
+ * event_first[0] = 0 and event_first[i + 1] - event_first[i] is read i's row count: 0 for a read whose decode verdict is an error and for
+ * a POD5 read with a failing row.  The table is always complete and holds the true counts, whatever start_cap is.  Read i's starts are
+ * written to start[event_first[i] ... event_first[i + 1]) when event_first[i + 1] <= start_cap; a read that does not fit gets
+ * VBZ_DESTINATION_SIZE_ERROR (on every row of a POD5 read, and its read_result) and not one word of start is written for it; nothing
+ * beyond start_cap and no entry owned by no fitting read is ever written.  start == NULL with start_cap == 0 is the count-only call: it
+ * writes event_first alone and leaves the verdicts alone.  result[i] is otherwise what the statistics-alone call gives: the int16
+ * decode's verdict, T x 2 with the read's FULL sample count on success; the POD5 twin writes read_result[] as that call does, its tables
+ * (event_first, ranges) are per READ, positions those of the concatenated signal, and a bad first_row fails the whole call with nothing
+ * written.  A read whose bit map (below) finds no room in the call's scratch -- possible only when the int16 layout's slots overlap --
+ * gets VBZ_OUT_OF_MEMORY_ERROR.  batch->dst may be NULL.
+ * Both return 0 when queued, -1 for a NULL context or batch or a launch failure, -2 (nothing launched) for everything
+ * vbz_gpu_signal_norm_range_batch / its POD5 twin refuse about the batch, the options, `reads` and `ranges`, a NULL segmentation or
+ * event_first, start == NULL with start_cap != 0, a window, the radius or a threshold outside its rule (NaN and infinities included),
+ * flags != 0, start_cap * 4 beyond 2^46 bytes.
+ * The hand-over: event_first and start go as they are into a vbz_gpu_events of the event calls, event_rows being start_cap (or the total
+ * when the caller has read it), with the same ranges, on the same stream.
+ * How: kernels of their own around the svb decoder's shared walks, with the first sink that needs a neighbourhood of
+ * each sample.  One workgroup walks a read's whole signal in order -- on every path: the long reads of the large-read path and POD5 reads
+ * of several rows included, which is what is built; spreading one long read over workgroups with seams between them is not -- and stages
+ * each tile of 2 048 samples in an LDS ring indexed by signal position.  Behind a barrier a lane scores eight consecutive positions,
+ * sliding the four window sums, into a second ring of float64 scores; the two divisions are made only where N >= 0.99 D t^2.  Behind a
+ * second barrier a lane applies the boundary test to a group of eight positions and writes one byte of the read's bit map in scratch (one
+ * bit a position, 1/16 of the int16 arena).  A count launch that reads result[] first, the scan and an emit launch (one workgroup per
+ * read, rank by rank) follow behind everything the call has queued.  Measured on one MI355X (tools/time_segment.py, profiles/HISTORY.md
+ * "Signal segmentation"; the parent of the commit that adds these calls is d26a89f; median of 20, every table checked bit for bit against
+ * the unfused route): 8 192 step-signal reads of ~100 k samples, w = (3, 6), t = (4, 9), r = 2, 66.0 M rows: 12.77 ms against 5.18 ms for
+ * the int16 decode alone and 278.8 ms for the int16 decode followed by torch (integer cumulative sums, float64 scores, max_pool1d,
+ * nonzero); followed by the event call on its tables 30.36 ms.  One 20 M-sample read: 99.99 ms against 0.648 ms and 7.77 ms -- one
+ * workgroup walks it, and there fusing loses 12.9 x to the unfused route. */
+typedef struct vbz_gpu_segmentation
+{
+    uint32_t short_window;   /* w1: 1 ... 32 */
+    uint32_t long_window;    /* w2: 0 (no second detector) or 1 ... 32 */
+    float short_threshold;   /* t1: finite, > 0 */
+    float long_threshold;    /* t2: finite, > 0; ignored when long_window == 0 */
+    uint32_t radius;         /* r: 1 ... 32 */
+    uint32_t flags;          /* must be 0 */
+    uint64_t start_cap;      /* entries of start[] */
+} vbz_gpu_segmentation;      /* 32 bytes */
+VBZ_EXPORT int vbz_gpu_signal_segment_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                            uint32_t is_signed, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_segmentation* segmentation,
+                                            uint64_t* event_first, uint32_t* start);
+VBZ_EXPORT int vbz_gpu_pod5_signal_segment_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                 uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_sample_ranges* ranges,
+                                                 const vbz_gpu_segmentation* segmentation, uint64_t* event_first, uint32_t* start);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

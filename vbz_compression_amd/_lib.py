@@ -195,6 +195,20 @@ class GpuTrim(ctypes.Structure):
     ]
 
 
+class GpuSegmentation(ctypes.Structure):
+    """struct vbz_gpu_segmentation of include/vbz_gpu.h (32 bytes)."""
+
+    _fields_ = [
+        ("short_window", ctypes.c_uint32),
+        ("long_window", ctypes.c_uint32),
+        ("short_threshold", ctypes.c_float),
+        ("long_threshold", ctypes.c_float),
+        ("radius", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("start_cap", ctypes.c_uint64),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -238,6 +252,8 @@ GPU_API = [
     "vbz_gpu_pod5_decompress_windows_batch",
     "vbz_gpu_signal_events_batch",
     "vbz_gpu_pod5_signal_events_batch",
+    "vbz_gpu_signal_segment_batch",
+    "vbz_gpu_pod5_signal_segment_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -396,6 +412,14 @@ def load():
         L.vbz_gpu_signal_events_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, ep, vp, vp, np_, vp, gp]
         L.vbz_gpu_pod5_signal_events_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_signal_events_batch.argtypes = [vp, bp, op, fp, rp, ep, vp, vp, np_, vp, gp]
+    if hasattr(L, "vbz_gpu_signal_segment_batch"):   # (likewise: builds of earlier rounds have no signal segmentation)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        gp = ctypes.POINTER(GpuSampleRanges)
+        sp = ctypes.POINTER(GpuSegmentation)
+        L.vbz_gpu_signal_segment_batch.restype = ctypes.c_int
+        L.vbz_gpu_signal_segment_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.c_uint32, gp, sp, vp, vp]
+        L.vbz_gpu_pod5_signal_segment_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_signal_segment_batch.argtypes = [vp, bp, op, ctypes.c_uint32, rp, gp, sp, vp, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

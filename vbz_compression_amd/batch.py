@@ -67,6 +67,31 @@ class Trim:
         return t
 
 
+@dataclasses.dataclass(frozen=True)
+class Segmentation:
+    """How a read's signal is cut into events (include/vbz_gpu.h: vbz_gpu_segmentation): two two-window t-statistic detectors -- windows
+    short_window and long_window (0: no second detector), thresholds on the t-statistic itself -- and a local non-maximum suppression of
+    radius `radius`: a position is a boundary when its score (the larger squared t over its threshold's square) is at least 1, larger
+    than every score up to `radius` positions in front of it and no smaller than every score up to `radius` behind it."""
+
+    short_window: int = 3
+    long_window: int = 6
+    short_threshold: float = 4.0
+    long_threshold: float = 9.0
+    radius: int = 2
+
+    def c_struct(self, start_cap=0):
+        g = _lib.GpuSegmentation()
+        g.short_window, g.long_window, g.radius = self.short_window, self.long_window, self.radius
+        g.short_threshold, g.long_threshold = self.short_threshold, self.long_threshold
+        g.start_cap = int(start_cap)
+        return g
+
+    def max_rows(self, samples):
+        """the bound on a read's rows: 2 + T' / (radius + 1)"""
+        return 2 + int(samples) // (self.radius + 1)
+
+
 def _u32(t):
     """view an int32 result tensor as python ints in [0, 2**32)"""
     return [int(x) & 0xFFFFFFFF for x in t.tolist()]
@@ -149,7 +174,8 @@ class GpuCodec:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self.L.vbz_gpu_last_error(self.ctx).decode()))
 
     def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
-               chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None, ev=None, moments=None):
+               chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None, ev=None, moments=None, sg=None,
+               event_first=None, start=None):
         """One typed decode (include/vbz_gpu.h): the batch, the device entered and left once, and the most general C entry of the call's
         family, NULL for every part that is None.  dst None: nothing is stored in the batch's dst (a chunk decode, the statistics) --
         dst_off / dst_cap are the int16 layout that describes the reads, dst_bytes its extent.  f (a GpuSignalFormat): what is stored,
@@ -157,7 +183,8 @@ class GpuCodec:
         trim points behind them, into `out`.  m / ss: the GpuNormalization and the shift_scale pointer; g: a GpuSampleRanges; r: a
         GpuPod5Reads (the pod5_ entries: unsized).  w (a GpuWindows, in place of ch): the samples go to the caller-listed windows, the
         rows of `chunks`.  ev (a GpuEvents, with f): no sample is stored -- one record per caller-listed event into `out` (int32 [rows, 4]), the
-        exact sums into `moments` (int64 [rows, 2], or None)."""
+        exact sums into `moments` (int64 [rows, 2], or None).  sg (a GpuSegmentation, f None): every read's event starts, found on the
+        device, into event_first (int64 [reads + 1]) and start (int32, sg.start_cap entries; None: the count-only call)."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -176,6 +203,8 @@ class GpuCodec:
         elif ch is not None:
             name, args = "decompress_chunks_range", [ref(f), ref(ch)] + reads + [chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]), ref(m),
                                                                                  ss, ref(g)]
+        elif f is None and sg is not None:
+            name, args = "signal_segment", [int(bool(signed))] + reads + [ref(g), ref(sg), event_first.data_ptr(), start.data_ptr() if start is not None else None]
         elif f is None and t is not None:
             name, args = "signal_trim", [int(bool(signed))] + reads + [ref(m), ref(g), ref(t), ss, out.data_ptr()]
         elif f is None:
@@ -322,6 +351,43 @@ class GpuCodec:
         self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, self._extent(n, dst_off, dst_cap), signed=signed, m=m, ss=ss, g=g,
                     t=t, out=out)
         return out if shift_scale is None else (out, shift_scale)
+
+    # -- signal segmentation (include/vbz_gpu.h: vbz_gpu_segmentation) -------------------------------
+    def _segment_args(self, n, segmentation, samples, start_cap, event_first, start):
+        """(the C struct, event_first, start) of a segmentation call over n reads of `samples` (an int tensor: the reads' sample counts).
+        start_cap None: the bound, sum of 2 + T / (radius + 1) (one host copy); 0: the count-only call, start is None"""
+        sg = Segmentation() if segmentation is None else segmentation
+        assert isinstance(sg, Segmentation), sg
+        if start is not None:
+            start_cap = int(start.numel()) if start_cap is None else start_cap
+        elif start_cap is None:
+            start_cap = int((samples.to(torch.int64) // (sg.radius + 1) + 2).sum().item()) if n else 0
+        if start is None and start_cap:
+            start = torch.empty(start_cap, dtype=torch.int32, device=self.device)
+        if start is not None:
+            assert start.dtype == torch.int32 and start.is_contiguous() and start.device == self.device and int(start.numel()) >= start_cap, (
+                start.dtype, start.shape, start_cap)
+        if event_first is None:
+            event_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        assert event_first.dtype == torch.int64 and event_first.is_contiguous() and event_first.device == self.device and int(event_first.numel()) == n + 1, (
+            event_first.dtype, event_first.shape)
+        return sg.c_struct(start_cap), event_first, (start if start_cap else None)
+
+    def signal_segment(self, src, src_off, src_size, dst_off, dst_cap, result, opts, segmentation=None, start_cap=None, signed=True, sized=False,
+                       begin=None, end=None, event_first=None, start=None):
+        """Every read's event starts, found on the device with no sample stored (include/vbz_gpu.h: vbz_gpu_signal_segment_batch) ->
+        (event_first int64 [n + 1], start int32 [start_cap] or None), both on the device and in the layout signal_events reads as it
+        stands: read i owns rows event_first[i] ... event_first[i + 1] - 1, row 0 of a read starts at 0 and one row follows per boundary.
+        segmentation: a Segmentation (None: its defaults).  start_cap: entries of start (None: the bound 2 + T / (radius + 1) per read;
+        0: the count-only call) -- a read whose rows end beyond it gets VBZ_DESTINATION_SIZE_ERROR and no starts.  begin / end: the
+        signal is that range of every read, positions count from its first sample.  dst_off / dst_cap: the int16 layout of the reads
+        (nothing is stored); result[i] is what decompress gives.  No synchronisation."""
+        n = int(src_off.numel())
+        g, keep = self._ranges(n, begin, end, None)
+        sg, event_first, start = self._segment_args(n, segmentation, dst_cap.to(torch.int64) // 2, start_cap, event_first, start)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, self._extent(n, dst_off, dst_cap), signed=signed, g=g, sg=sg,
+                    event_first=event_first, start=start)
+        return event_first, start
 
     def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False,
                           norm=None, norm_out=None):
@@ -797,6 +863,24 @@ class GpuCodec:
         self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, opts, dst_bytes=dst_off[-1].item(), signed=signed, m=m, ss=ss, g=g, r=r,
                     t=t, out=out)
         return (out, read_result) if shift_scale is None else (out, shift_scale, read_result)
+
+    def pod5_signal_segment(self, src, src_off, src_size, row_samples, read_first_row, result, segmentation=None, start_cap=None, signed=True,
+                            begin=None, end=None, event_first=None, start=None, read_result=None):
+        """signal_segment over POD5 signal rows grouped into reads by read_first_row (vbz_gpu_pod5_signal_segment_batch) ->
+        (event_first int64 [n_reads + 1], start, read_result): the tables and begin / end are per READ, the positions those of the read's
+        concatenated signal; result is per ROW."""
+        n = int(src_off.numel())
+        assert int(row_samples.numel()) == n
+        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        g, keep = self._ranges(r.n_reads, begin, end, None)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        if start_cap is None and start is None:   # (the bound: 2 + T / (radius + 1) per read, at most 2 n_reads + all samples / (radius + 1))
+            radius = (segmentation or Segmentation()).radius
+            start_cap = 2 * r.n_reads + int(torch.as_tensor(row_samples).to(torch.int64).sum().item()) // (radius + 1)
+        sg, event_first, start = self._segment_args(r.n_reads, segmentation, None, start_cap, event_first, start)
+        self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, pod5_options(), dst_bytes=dst_off[-1].item(), signed=signed, g=g, r=r,
+                    sg=sg, event_first=event_first, start=start)
+        return event_first, start, read_result
 
     def pod5_decompress_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, dtype=torch.float32, signed=True,
                                     norm_out=None, align=16):

@@ -427,7 +427,129 @@ hipError_t scan_launches(uint32_t n, uint32_t align, const uint32_t* size, uint6
     return hipGetLastError();
 }
 
+// ---- signal segmentation: the maps' layout in front of the pass, and count, scan, emit behind it (vbz_kernels.h SegmentOut) ----------
+// the map of a read of T samples: one bit a position, whole bytes (the scan rounds them up to 4)
+__global__ __launch_bounds__(1024) void segment_sizes_kernel(ReadBatch b, Pod5Reads pr, uint64_t* off, uint32_t* size)
+{
+    __shared__ uint64_t wsum[16];
+    const bool reads = pr.reads != nullptr;
+    const uint32_t n = reads ? pr.n_reads : b.n_reads;
+    const uint32_t i = blockIdx.x * TILE + threadIdx.x;
+    uint64_t take = 0;
+    if (i < n) {
+        uint32_t T = 0;
+        if (reads) T = *pr.bad ? 0u : pr.reads[i].T;
+        else if (!(b.gate && b.gate[i] >= GATE_SKIP)) T = b.dst_cap[i] >> 1;
+        size[i] = (T + 7u) >> 3;
+        take = round_up(size[i], 4);
+    }
+    const uint64_t t = block_sum_u64(take, wsum);
+    if (threadIdx.x == 0) off[blockIdx.x * TILE] = t;
+}
+
+// whether read i passed (result[] is read first: a read whose stream failed mid-pass counts 0), and its samples
+__device__ __forceinline__ bool segment_passed(const ReadBatch& b, const Pod5Reads& pr, uint32_t i, uint32_t* T)
+{
+    if (pr.reads) {
+        for (uint32_t r = pr.first_row[i]; r < pr.first_row[i + 1]; ++r)
+            if (b.result[r] >= E_FIRST) return false;
+        *T = pr.reads[i].T;
+        return !(pr.reads[i].flags & POD5_READ_FAIL);
+    }
+    *T = b.result[i] >> 1;
+    return b.result[i] < E_FIRST;
+}
+
+__global__ __launch_bounds__(1024) void segment_counts_kernel(ReadBatch b, Pod5Reads pr, const uint32_t* rows, uint64_t* off, uint32_t* count)
+{
+    __shared__ uint64_t wsum[16];
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    const uint32_t i = blockIdx.x * TILE + threadIdx.x;
+    uint64_t take = 0;
+    if (i < n && !(pr.reads && *pr.bad)) {
+        uint32_t T;
+        if (segment_passed(b, pr, i, &T) && T != 0) take = rows[i];   // (a read without samples never reached its sink)
+        count[i] = (uint32_t)take;
+    }
+    const uint64_t t = block_sum_u64(take, wsum);
+    if (threadIdx.x == 0) off[blockIdx.x * TILE] = t;
+}
+
+// one workgroup per read: its entry of event_first and, rank by rank, its starts -- 4 096 bytes of the map a trip, a word a thread
+__global__ __launch_bounds__(1024) void segment_emit_kernel(ReadBatch b, Pod5Reads pr, SegmentOut so, const uint32_t* count, const uint64_t* scan,
+                                                            uint64_t* event_first, uint32_t* start, uint64_t start_cap)
+{
+    __shared__ uint64_t wsum[16];
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (pr.reads && *pr.bad) return;
+    const uint32_t i = blockIdx.x;
+    const uint64_t a = scan[i], z = scan[i + 1];
+    if (threadIdx.x == 0) {
+        event_first[i] = a;
+        if (i + 1 == n) event_first[n] = z;
+    }
+    const uint32_t rows = count[i];
+    if (rows == 0 || start == nullptr) return;
+    if (z > start_cap) {   // the read does not fit: not one word of start
+        if (pr.reads) {
+            for (uint32_t r = pr.first_row[i] + threadIdx.x; r < pr.first_row[i + 1]; r += 1024) b.result[r] = E_DESTINATION_SIZE;
+            if (threadIdx.x == 0 && pr.read_result) pr.read_result[i] = E_DESTINATION_SIZE;
+        } else if (threadIdx.x == 0) {
+            b.result[i] = E_DESTINATION_SIZE;
+        }
+        return;
+    }
+    if (threadIdx.x == 0) start[a] = 0;
+    const uint32_t* map = reinterpret_cast<const uint32_t*>(so.map + so.map_off[i]);
+    const uint32_t nbytes = (uint32_t)((so.map_off[i + 1] - so.map_off[i]));   // (rounded up to 4; the bytes behind the map's last hold anything)
+    uint32_t T;
+    (void)segment_passed(b, pr, i, &T);
+    if (!pr.reads) {   // the signal: the read's clamped range
+        uint32_t rb, re;
+        sample_range(b.sig, i, T, &rb, &re);
+        T = re - rb;
+    } else if (b.sig.ranged()) {
+        T = pr.range[i].y - pr.range[i].x;
+    }
+    uint64_t rank = a + 1;
+    for (uint32_t w0 = 0; w0 < nbytes / 4u; w0 += 1024) {
+        const uint32_t w = w0 + threadIdx.x;
+        uint32_t bits = w < nbytes / 4u ? map[w] : 0u;
+        const uint64_t q0 = 32ull * w;
+        if (q0 + 32u > T) bits = q0 >= T ? 0u : bits & (0xFFFFFFFFu >> (32u - (uint32_t)(T - q0)));   // (positions behind the signal: no writer)
+        uint64_t tot;
+        uint64_t at = rank + block_excl_scan_u64((uint64_t)__popc(bits), wsum, tot);
+        while (bits) {
+            const uint32_t j = (uint32_t)__ffs((int)bits) - 1u;
+            bits &= bits - 1u;
+            if (at < z) start[at] = (uint32_t)q0 + j;   // (at < z always: the map's bits are the sink's count)
+            ++at;
+        }
+        rank += tot;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_segment_layout(const ReadBatch& b, const Pod5Reads& pr, const SegmentScratch& sc, hipStream_t s)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (n == 0) return hipMemsetAsync(sc.map_off, 0, 8, s);
+    hipLaunchKernelGGL(segment_sizes_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, b, pr, sc.map_off, sc.size);
+    return scan_launches(n, 4, sc.size, sc.map_off, s);
+}
+
+hipError_t launch_segment_emit(const ReadBatch& b, const Pod5Reads& pr, const SegmentOut& so, const SegmentScratch& sc, uint64_t* event_first,
+                               uint32_t* start, uint64_t start_cap, hipStream_t s)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (n == 0) return hipMemsetAsync(event_first, 0, 8, s);
+    hipLaunchKernelGGL(segment_counts_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, b, pr, sc.rows, sc.scan, sc.count);
+    const hipError_t e = scan_launches(n, 1, sc.count, sc.scan, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(segment_emit_kernel, dim3(n), dim3(1024), 0, s, b, pr, so, sc.count, sc.scan, event_first, start, start_cap);
+    return hipGetLastError();
+}
 
 hipError_t launch_window_check(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, hipStream_t s)
 {

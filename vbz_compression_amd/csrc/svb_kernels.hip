@@ -2319,6 +2319,125 @@ __global__ __launch_bounds__(WG) void svb16_trim_reads_kernel(ReadBatch b, Pod5R
     st.done();
 }
 
+// ---- the segmentation pass (vbz_kernels.h SegmentOut; svb_store.h SegmentStore) -----------------------------------------------------------
+// Kernels of their own, one workgroup per read on every path: the sink needs each sample's neighbourhood, and a workgroup that walks the
+// whole signal in order has it in LDS.  The verdicts are written here, as the int16 decode writes them (there is no counting pass in front).
+// The read's entry of the call's tables, and whether its map lies inside the scratch
+__device__ __forceinline__ uint32_t segment_entry(const SegmentOut& so, uint32_t r) { return so.rmap ? so.rmap[r] : r; }
+__device__ __forceinline__ bool segment_fits(const SegmentOut& so, uint32_t i, uint32_t T)
+{
+    const uint64_t a = so.map_off[i], z = so.map_off[i + 1];
+    return z <= so.map_cap && a <= z && (uint64_t)((T + 7u) >> 3) <= z - a;   // (a map of ceil(T / 8) bytes: no byte is written outside it)
+}
+
+// svb_decode_kernel's walk of an int16 read
+template <bool ZZ, bool I16ZZ>
+__global__ __launch_bounds__(WG) void svb_segment_kernel(ReadBatch b, SegmentOut so)
+{
+    constexpr int STAGE = I16ZZ ? 2 * (int)I16DecPairs::BUF : WG * Vpl<2>::value * 4 + 48;
+    __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[I16ZZ ? (int)I16DecPairs::WS_WORDS : 4];
+
+    const uint32_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (b.gate && b.gate[r] >= GATE_SKIP) {
+        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
+        return;
+    }
+    const uint32_t in_size = b.src_size[r];
+    if (in_size >= E_FIRST) {  // the previous stage failed for this read
+        if (tid == 0) b.result[r] = in_size;
+        return;
+    }
+    const uint32_t out_size = b.dst_cap[r];
+    uint32_t res;
+    if (svb_decode_check<2, I16ZZ>(in_size, out_size, res)) {
+        if (tid == 0) b.result[r] = res;
+        return;
+    }
+    const uint32_t count = out_size / 2u, keyLen = (count + 3u) >> 2;
+    const uint32_t i = segment_entry(so, r);
+    if (!segment_fits(so, i, count)) {
+        if (tid == 0) b.result[r] = E_OOM;
+        return;
+    }
+    const uint8_t* in = b.src + b.src_off[r];
+    const uint32_t dataBytes = in_size - keyLen;
+    uint32_t rb, re;
+    sample_range(b.sig, r, count, &rb, &re);
+    uint64_t pos = 0;
+    uint32_t run = 0;
+    const SegmentStore st(so, i, rb, re - rb, b.sig.bias);
+    const bool good = svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, dataBytes, count, 0, count, pos, run, st, stage, wsum);
+    if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * 2u;
+}
+
+// a POD5 row as a read of its own
+__global__ __launch_bounds__(WG) void svb16_segment_kernel(ReadBatch b, SegmentOut so)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+
+    const uint32_t r = blockIdx.x;
+    uint32_t in_size = 0, count = 0, verdict;
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
+        if (threadIdx.x == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
+        return;
+    }
+    const uint32_t i = segment_entry(so, r);
+    if (!segment_fits(so, i, count)) {
+        if (threadIdx.x == 0) b.result[r] = E_OOM;
+        return;
+    }
+    uint32_t rb, re;
+    sample_range(b.sig, r, count, &rb, &re);
+    const SegmentStore st(so, i, rb, re - rb, b.sig.bias);
+    const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, stage, wsum);
+    st.done();
+    if (threadIdx.x == 0) b.result[r] = good ? count * 2u : E_STREAM;
+}
+
+// POD5 reads of several rows: one workgroup per READ walks its rows in turn, as svb16_count_reads does, and writes their verdicts.  No seam
+// lies between rows: begin_row() places each in the read's signal.  A read the plan failed has its rows' gates closed.
+__global__ __launch_bounds__(WG) void svb16_segment_reads_kernel(ReadBatch b, Pod5Reads pr, SegmentOut so)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+
+    if (*pr.bad) return;
+    const uint32_t k = blockIdx.x;
+    const int tid = threadIdx.x;
+    const uint32_t first = pr.first_row[k], end = pr.first_row[k + 1];
+    const Pod5Read rd = pr.reads[k];
+    const bool failed = (rd.flags & POD5_READ_FAIL) != 0;   // (the plan has closed its rows' gates: every row gets that verdict)
+    if (failed || !segment_fits(so, k, rd.T)) {
+        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) {
+            uint32_t in_size, count, verdict;
+            (void)svb16_row_open(b, r, &in_size, &count, &verdict);
+            if (verdict != GATE_SKIP) b.result[r] = failed || verdict >= E_FIRST ? verdict : E_OOM;
+        }
+        return;
+    }
+    uint32_t rb = 0, re = rd.T;
+    if (b.sig.ranged()) {
+        const uint2 g = pr.range[k];
+        rb = g.x;
+        re = g.y;
+    }
+    SegmentStore st(so, k, rb, re - rb, b.sig.bias);
+    for (uint32_t r = first; r < end; ++r) {
+        uint32_t in_size = 0, count = 0, verdict;
+        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
+            if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
+            continue;
+        }
+        st.begin_row(pr.rows[r].s0);   // (put() gets positions in the row)
+        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, stage, wsum);
+        if (tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
+    }
+    st.done();
+}
+
 // read_result[k]: the code of the read's first failing row, else T * elem
 __global__ __launch_bounds__(WG) void pod5_read_results_kernel(ReadBatch b, Pod5Reads pr, uint32_t elem)
 {
@@ -2654,6 +2773,38 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
         const uint32_t elem = b.sig.type == SIG_F32 && !b.sig.events ? 4u : 2u;   // (an event call: the int16 decode's verdicts)
         hipLaunchKernelGGL(pod5_read_results_kernel, dim3((pr.n_reads + WG - 1) / WG), t, 0, s, b, pr, elem);
     }
+    return hipGetLastError();
+}
+
+// ---- signal segmentation --------------------------------------------------------------------------------------------------------------
+hipError_t launch_svb_segment(const ReadBatch& b, bool zigzag, const SegmentOut& so, hipStream_t s)
+{
+    if (b.n_reads == 0) return hipSuccess;
+    if (zigzag) hipLaunchKernelGGL((svb_segment_kernel<true, true>), dim3(b.n_reads), dim3(WG), 0, s, b, so);
+    else hipLaunchKernelGGL((svb_segment_kernel<false, false>), dim3(b.n_reads), dim3(WG), 0, s, b, so);
+    return hipGetLastError();
+}
+
+hipError_t launch_svb16_segment(const ReadBatch& b, const SegmentOut& so, hipStream_t s)
+{
+    if (b.n_reads == 0) return hipSuccess;
+    hipLaunchKernelGGL(svb16_segment_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, so);
+    return hipGetLastError();
+}
+
+hipError_t launch_svb16_segment_reads(const ReadBatch& b, const Pod5Reads& pr, const SegmentOut& so, const SegmentScratch& sc, hipStream_t s)
+{
+    const uint32_t most = std::max(b.n_reads, pr.n_reads);
+    if (most == 0) return hipSuccess;
+    if ((b.n_reads && !b.gate) || b.sig.norm.st || b.sig.row || b.sig.wfirst || (b.sig.ranged() && !pr.range)) return hipErrorInvalidValue;
+    const dim3 t(WG);
+    if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, nullptr, nullptr, 0ull);
+    else hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, nullptr, nullptr, 0ull);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_segment_layout(b, pr, sc, s);
+    if (e != hipSuccess) return e;
+    if (pr.n_reads) hipLaunchKernelGGL(svb16_segment_reads_kernel, dim3(pr.n_reads), t, 0, s, b, pr, so);
+    if (pr.read_result && pr.n_reads) hipLaunchKernelGGL(pod5_read_results_kernel, dim3((pr.n_reads + WG - 1) / WG), t, 0, s, b, pr, 2u);
     return hipGetLastError();
 }
 

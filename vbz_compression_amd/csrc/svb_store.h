@@ -1175,6 +1175,177 @@ struct TrimStore
     }
 };
 
+// ---- signal segmentation (vbz_kernels.h SegmentOut; the rule: include/vbz_gpu.h) --------------------------------------------------------
+// The first sink that needs a neighbourhood of each sample: a position's verdict depends on the H = max(w1, w2) + r samples on either
+// side of it.  The sink's workgroup walks its read's whole signal in order (one workgroup per read on every path: DESIGN.md 4.20), so the
+// halo is a matter of LDS alone.  put() stages the tile's samples in a ring indexed by signal position; behind one barrier the workgroup
+// scores every position whose two windows are staged by now (a lane takes eight consecutive positions and slides the four window sums),
+// the scores going to a second ring; behind a second barrier a lane takes a group of eight positions whose scores of [8k - r, 8k + 8 + r]
+// are all there, applies the boundary test and writes the group's byte of the read's map.  Both rings hold 4 096 positions: a tile of
+// 2 048, the halo on both sides and the up to 15 positions a group waits for.  The put that stages the signal's last sample also flushes
+// what was waiting for samples past the end (the scores there are 0 by the rule).
+// Ring hazards: staging writes ring positions no score phase reads before the barrier behind it, and the barrier between the score and
+// the boundary phase keeps the next put's staging behind this put's ring reads; the next put's scores are written behind its staging
+// barrier, which every lane reaches only after its boundary phase.
+constexpr uint32_t SEGMENT_RING = 4096;
+#ifndef VBZ_SEGMENT_PRETEST
+#define VBZ_SEGMENT_PRETEST 1   // (0: both divisions at every position -- the build that measures what the pre-test saves)
+#endif
+struct SegmentLds
+{
+    double score[SEGMENT_RING];
+    uint16_t ring[SEGMENT_RING];
+    uint32_t hi, bits;   // positions [0, hi) of the signal are staged; the boundaries found
+};
+__device__ __forceinline__ SegmentLds* segment_lds()
+{
+    __shared__ __attribute__((aligned(16))) SegmentLds L;
+    return &L;
+}
+
+// the scores of positions [qa, qe) of a signal of T samples into the score ring, by the whole workgroup: s = max(s_1, s_2),
+// s_d = (float64(N) / float64(D)) / (float64(t) float64(t)) where w <= q <= T - w, else 0, N and D exact integers.  A score below 1 can
+// neither be a boundary nor suppress one, so it is stored as 0 and the two divisions are only made where N >= 0.99 D t^2 in float64 --
+// the three roundings of the exact expression move it by less than one part in 2^50.  The window sums slide: the values that enter at
+// positions outside the signal are whatever the ring holds there and leave again unchanged (integer sums), and no score is taken from them.
+__device__ __forceinline__ void segment_scores(SegmentLds* L, const SegmentOut& so, uint32_t bias, uint32_t qa, uint32_t qe, uint32_t T)
+{
+#pragma clang fp contract(off)
+    auto X = [&](uint32_t q) -> int64_t {   // (as sig_f32: the int16 or the uint16 value)
+        const uint32_t v = L->ring[q & (SEGMENT_RING - 1u)];
+        return (int64_t)(((int32_t)((v ^ bias) << 16) >> 16) + (int32_t)bias);
+    };
+    for (uint32_t q0 = qa + 8u * threadIdx.x; q0 < qe; q0 += 8u * WG) {
+        double sc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sc[j] = 0.0;
+        for (int d = 0; d < 2; ++d) {
+            const uint32_t w = d ? so.w2 : so.w1;
+            if (w == 0) continue;
+            const double kk = d ? so.k2 : so.k1;
+            int64_t A = 0, B = 0, A2 = 0, B2 = 0;
+            for (uint32_t j = 0; j < w; ++j) {
+                const int64_t a = X(q0 - w + j), c = X(q0 + j);
+                A += a;
+                A2 += a * a;
+                B += c;
+                B2 += c * c;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t q = q0 + (uint32_t)j;
+                if (q < qe && q >= w && q + w <= T) {
+                    const int64_t dm = A - B, N = (int64_t)w * dm * dm;
+                    int64_t D = (int64_t)w * (A2 + B2) - A * A - B * B;
+                    if (D < 1) D = 1;
+                    const double nd = (double)N, dd = (double)D;
+                    if (!VBZ_SEGMENT_PRETEST || nd >= 0.99 * (dd * kk)) {
+                        const double s = (nd / dd) / kk;
+                        if (s > sc[j]) sc[j] = s;
+                    }
+                }
+                const int64_t xm = X(q - w), x0 = X(q), xp = X(q + w);
+                A += x0 - xm;
+                A2 += x0 * x0 - xm * xm;
+                B += xp - x0;
+                B2 += xp * xp - x0 * x0;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (q0 + (uint32_t)j < qe) L->score[(q0 + (uint32_t)j) & (SEGMENT_RING - 1u)] = sc[j] >= 1.0 ? sc[j] : 0.0;
+    }
+}
+
+// The segmentation sink of one workgroup (the contract: this file's head): its values lie at s0 of the read (a row of a POD5 read:
+// begin_row(); else 0), the signal is the read's samples [rb, rb + T).  Built by all threads of the workgroup.
+struct SegmentStore
+{
+    static constexpr uint32_t BYTES = 2;   // (result[] is the int16 decode's)
+    SegmentLds* L;
+    SegmentOut so;
+    uint8_t* map;      // the read's
+    uint32_t* rows;    // the read's entry of SegmentOut::rows
+    uint32_t rb, T, bias, H, wmax;
+    uint32_t s0 = 0;
+    mutable uint32_t scored = 0, lo = 0, nb = 0;   // scores of [0, scored) and groups [0, lo) are done (workgroup-uniform); this lane's boundaries
+
+    __device__ __forceinline__ SegmentStore(const SegmentOut& o, uint32_t i, uint32_t rb_, uint32_t T_, uint32_t bias_)
+        : L(segment_lds()), so(o), map(o.map + o.map_off[i]), rows(o.rows + i), rb(rb_), T(T_), bias(bias_)
+    {
+        wmax = so.w1 > so.w2 ? so.w1 : so.w2;
+        H = wmax + so.r;
+        if (threadIdx.x == 0) {
+            L->hi = 0;
+            L->bits = 0;
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void begin_row(uint32_t s) { s0 = s; }
+    __device__ __forceinline__ bool aligned() const { return true; }   // (nothing is stored)
+
+    // the groups [lo, khi) of eight positions: the boundary test on the scores, one byte of the map per lane and group
+    __device__ __forceinline__ void pick(uint32_t khi) const
+    {
+        const uint32_t r = so.r;
+        auto S = [&](uint32_t q) { return L->score[q & (SEGMENT_RING - 1u)]; };
+        for (uint32_t k = lo + threadIdx.x; k < khi; k += WG) {
+            uint32_t byte = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t q = 8u * k + (uint32_t)j;
+                if (q < 1u || q >= T) continue;
+                const double v = S(q);
+                if (!(v >= 1.0)) continue;
+                bool ok = true;
+                for (uint32_t u = q > r ? q - r : 0u; u < q && ok; ++u) ok = v > S(u);
+                const uint32_t jh = q + r < T ? q + r : T;
+                for (uint32_t u = q + 1u; u <= jh && ok; ++u) ok = v >= S(u);
+                if (ok) byte |= 1u << j;
+            }
+            map[k] = (uint8_t)byte;
+            nb += (uint32_t)__popc(byte);
+        }
+    }
+
+    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
+    {
+        // stage: the lane's samples at their positions of the signal; the wavefront's last lane that has samples says how far they reach
+        const uint32_t p = s0 + i0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t q = p + (uint32_t)j - rb;
+            if (j < valid && q < T) L->ring[q & (SEGMENT_RING - 1u)] = (uint16_t)(base + s[j]);
+        }
+        const uint64_t m = __ballot(valid > 0 ? 1 : 0);
+        if (m != 0 && (threadIdx.x & 63u) == 63u - (uint32_t)__builtin_clzll(m)) {
+            const uint32_t e = p + (uint32_t)valid;
+            atomicMax(&L->hi, e <= rb ? 0u : (e - rb < T ? e - rb : T));
+        }
+        wg_lds_barrier();
+        const uint32_t hi = L->hi;
+        const bool last = hi >= T;
+        const uint32_t shi = last ? T + 1u : (hi >= wmax ? hi - wmax + 1u : 0u);   // scores of [0, shi) can be taken now
+        if (shi > scored) segment_scores(L, so, bias, scored, shi, T);
+        wg_lds_barrier();
+        const uint32_t khi = last ? (T + 7u) >> 3 : (shi >= so.r + 8u ? (shi - so.r) >> 3 : 0u);
+        if (khi > lo) {
+            pick(khi);
+            lo = khi;
+        }
+        if (shi > scored) scored = shi;
+    }
+    __device__ __forceinline__ void finish() const {}
+    // the read's row count: its boundaries and row 0 (an empty signal: none)
+    __device__ __forceinline__ void done() const
+    {
+        const uint32_t t = wave_incl_scan_u32(nb);
+        if ((threadIdx.x & 63u) == 63u && t != 0) atomicAdd(&L->bits, t);
+        __syncthreads();
+        if (threadIdx.x == 0) *rows = T ? L->bits + 1u : 0u;
+    }
+};
+
 // The selection and the builder in one: the sink of read r of `count` values for the whole-read and segment kernels' OUT.  | SIG_RANGE (the
 // chunk and window sinks and SIG_COUNT): the read is its samples [b, e).  b: the batch, for the typed stores only -- SIG_NONE gets nullptr
 // and the batch's fields (a reference to the kernel's ReadBatch argument would cost its loads their scalar form).  cr: whose constants

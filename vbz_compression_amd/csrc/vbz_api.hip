@@ -221,12 +221,15 @@ struct vbz_gpu_ctx
     DevBuf chunkmeta;          // chunk layout: the per-read chunk counts
     DevBuf winmeta;            // signal windows: the per-read row counts and their scan (WindowScratch)
     DevBuf evmeta;             // signal events: the rows' moments of a call whose caller takes none (two 64-bit words a row)
+    DevBuf segmtab;            // signal segmentation: the per-read tables of a call (SegmentScratch)
+    DevBuf segmap;             // ... and the reads' boundary maps, one bit a sample (1/16 of the int16 arena the call never writes)
     DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call (NormTables)
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables, the reads' constants (Pod5Tables)
     // The state of the call in flight, handed to the children as it is (not a setting: outside Knobs)
     TrimOut trim;              // the signal trim of the decompress call in flight (begin == nullptr: none); every decompress call sets it,
                                // and the contexts of a batch's upper half and of the routed reads get theirs from it
+    SegmentOut seg;            // the segmentation of the decompress call in flight (map == nullptr: none), set and handed on as the trim is
     bool profiling = false;
     PinnedBuf pinned;          // the single-buffer API's pinned area (run_one)
     uint32_t one_seq = 0;      // the single-buffer API's hand-back flag: a number per call (run_one)
@@ -866,6 +869,11 @@ int svb_decode_stage(vbz_gpu_ctx* c, const ReadBatch& d, const CompressionOption
 {
     Timed t(c, "svb_decode");
     const TrimOut* const trim = c->trim.begin ? &c->trim : nullptr;
+    if (c->seg.map) {   // (a segmentation call: kernels of their own, one workgroup per read on every path -- DESIGN.md 4.20)
+        if (pod5_codec(o)) HIPCHK(c, launch_svb16_segment(d, c->seg, c->stream), "svb16 segment launch");
+        else HIPCHK(c, launch_svb_segment(d, o->perform_delta_zig_zag, c->seg, c->stream), "svb segment launch");
+        return 0;
+    }
     if (pod5_codec(o))   // (one workgroup per read on every path: DESIGN.md 4.13)
         HIPCHK(c, launch_svb16_decode(d, c->stream, trim), "svb16_decode launch");
     else if (segmented)
@@ -1002,6 +1010,7 @@ int inherit_large(vbz_gpu_ctx* c)
     k->knobs.split_min = 0;
     k->knobs.segmented = 1;
     k->trim = c->trim;   // (the routed reads write begin through the routing map, as they do shift_scale)
+    k->seg = c->seg;     // (and find their maps and row counts through it: route() sets SegmentOut::rmap)
     return 0;
 }
 // half: the upper half [n / 2, n) of a split call -- the one-workgroup path; it gets the call's profiling switch (its launches count under
@@ -1021,6 +1030,8 @@ int inherit_half(vbz_gpu_ctx* c, uint32_t n)
     k->foreign_state = c->foreign_state;
     k->trim = c->trim;   // (the upper half's begin entries: the table offset, as upper_half() offsets shift_scale)
     if (k->trim.begin) k->trim.begin += n / 2;
+    k->seg = c->seg;     // (likewise the segmentation's per-read tables)
+    if (k->seg.map) k->seg.map_off += n / 2, k->seg.rows += n / 2;
     return 0;
 }
 
@@ -1053,6 +1064,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     }
     if (rb.sig.ranged()) r->large.sig.rmap = r->map;   // (their ranges: the call's tables, through the map)
     if (rb.sig.wfirst) r->large.sig.wmap = r->map;     // (and their windows)
+    if (c->seg.map) c->large->seg.rmap = r->map;        // (and their boundary maps)
     Timed t(c, "route");
     a.raw_size = raw_size;
     a.min_bytes = ROUTE_MIN_BYTES;
@@ -1507,6 +1519,50 @@ TrimOut trim_out(const vbz_gpu_trim* t, uint32_t* begin)
     return to;
 }
 
+// the segmentation's fields (include/vbz_gpu.h) and its two tables
+static_assert(sizeof(vbz_gpu_segmentation) == 32, "vbz_gpu_segmentation is 32 bytes");
+static_assert(offsetof(vbz_gpu_segmentation, short_window) == 0 && offsetof(vbz_gpu_segmentation, long_window) == 4 &&
+                  offsetof(vbz_gpu_segmentation, short_threshold) == 8 && offsetof(vbz_gpu_segmentation, long_threshold) == 12 &&
+                  offsetof(vbz_gpu_segmentation, radius) == 16 && offsetof(vbz_gpu_segmentation, flags) == 20 &&
+                  offsetof(vbz_gpu_segmentation, start_cap) == 24,
+              "the fields of vbz_gpu_segmentation");
+bool segmentation_ok(vbz_gpu_ctx* c, const vbz_gpu_segmentation* g, const uint64_t* event_first, const uint32_t* start)
+{
+    if (!g || !event_first) {
+        set_error(c, "segmentation or event_first is NULL");
+        return false;
+    }
+    if (!start && g->start_cap != 0) {
+        set_error(c, "start is NULL with start_cap %llu (the count-only call: NULL and 0)", (unsigned long long)g->start_cap);
+        return false;
+    }
+    auto threshold_ok = [](float t) { return std::isfinite(t) && t > 0.0f; };
+    const bool fields = g->short_window >= 1 && g->short_window <= SEGMENT_WINDOW_MAX && g->long_window <= SEGMENT_WINDOW_MAX && g->radius >= 1 &&
+                        g->radius <= SEGMENT_RADIUS_MAX && threshold_ok(g->short_threshold) && (g->long_window == 0 || threshold_ok(g->long_threshold)) &&
+                        g->flags == 0;
+    if (!fields) {
+        set_error(c, "segmentation outside its rules (short_window %u, long_window %u, short_threshold %g, long_threshold %g, radius %u, flags %u)",
+                  g->short_window, g->long_window, (double)g->short_threshold, (double)g->long_threshold, g->radius, g->flags);
+        return false;
+    }
+    if (g->start_cap > EXTENT_MAX / sizeof(uint32_t)) {
+        set_error(c, "declared start table is not plausible (%llu entries of 4 bytes)", (unsigned long long)g->start_cap);
+        return false;
+    }
+    return true;
+}
+// the rule's part of SegmentOut (the tables and the map: the call's scratch, decompress_batch_impl)
+SegmentOut segment_out(const vbz_gpu_segmentation* g)
+{
+    SegmentOut so;
+    so.w1 = g->short_window;
+    so.w2 = g->long_window;
+    so.r = g->radius;
+    so.k1 = (double)g->short_threshold * (double)g->short_threshold;
+    so.k2 = so.w2 ? (double)g->long_threshold * (double)g->long_threshold : 1.0;
+    return so;
+}
+
 // POD5 reads of several rows (o nullable: a call without options)
 static_assert(sizeof(vbz_gpu_pod5_reads) == 24, "vbz_gpu_pod5_reads is 24 bytes");
 bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_pod5_reads* reads)
@@ -1524,8 +1580,9 @@ bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_po
 
 // TypedCall: one typed decode as its entry point states it (the table of entries: in front of them, below).  A part the entry does not
 // have keeps its default.  Where the entries' rules for a NULL differ, the entry says which one holds (Null); it is not inferred.
-enum class Typed { SIGNAL, CHUNKS, STATISTICS, EVENTS };   // what is stored: typed samples in the reads' slots; in chunks; nothing (the constants
-                                                           // alone); one record per caller-listed event
+enum class Typed { SIGNAL, CHUNKS, STATISTICS, EVENTS, SEGMENT };   // what is stored: typed samples in the reads' slots; in chunks; nothing (the
+                                                                    // constants alone); one record per caller-listed event; nothing in the
+                                                                    // reads' slots either -- every read's event starts, found on the device
 enum class Null { ALLOWED, REFUSED, REFUSED_WITH_READS };   // REFUSED_WITH_READS: refused unless the call has no read to write an entry for
 struct TypedCall
 {
@@ -1553,6 +1610,9 @@ struct TypedCall
     bool with_trim = false;                          // a trim call (the statistics, then the trim pass): the rule, and the table it fills
     const vbz_gpu_trim* trim = nullptr;
     uint32_t* begin = nullptr;
+    const vbz_gpu_segmentation* seg = nullptr;       // SEGMENT (is_signed as for STATISTICS): the rule, and the two tables the call fills --
+    uint64_t* seg_first = nullptr;                   // ... event_first and start, the layout a vbz_gpu_events reads
+    uint32_t* seg_start = nullptr;
 
     TypedCall(Typed k, int s) : kind(k), sized(s) {}
     TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
@@ -1580,6 +1640,7 @@ struct TypedCall
     TypedCall& range(const vbz_gpu_sample_ranges* g) { ranges = g; return *this; }
     TypedCall& pod5_reads(const vbz_gpu_pod5_reads* r) { pod5 = true, reads = r; return *this; }
     TypedCall& trimmed(const vbz_gpu_trim* t, uint32_t* b) { with_trim = true, trim = t, begin = b; return *this; }
+    TypedCall& segmented(const vbz_gpu_segmentation* g, uint64_t* first, uint32_t* start) { seg = g, seg_first = first, seg_start = start; return *this; }
 };
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
@@ -1632,9 +1693,12 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     c->last_frames = 0;
     c->last_span_frames = 0;
     c->trim = out && out->with_trim ? trim_out(out->trim, out->begin) : TrimOut();
+    c->seg = SegmentOut();
     const vbz_gpu_pod5_reads* const reads = out ? out->reads : nullptr;
-    if (n == 0 && !(reads && reads->n_reads)) return 0;
+    const bool segment = out && out->kind == Typed::SEGMENT;
     hipStream_t s = c->stream;
+    if (segment && (reads ? reads->n_reads : n) == 0) HIPCHK(c, hipMemsetAsync(out->seg_first, 0, 8, s), "event_first of no reads");
+    if (n == 0 && !(reads && reads->n_reads)) return 0;
     ReadBatch rb = to_rb(bt);
     Pod5Reads pr;
     float2* read_cal = nullptr;
@@ -1642,7 +1706,7 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (n != 0 && !own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
     uint64_t dst_bytes = bt->dst_bytes;
     const bool events = out && out->kind == Typed::EVENTS;   // (an event call takes the window call's way: its tables are the windows')
-    const bool chunks = out && (out->kind == Typed::CHUNKS || events), stats = out && out->kind == Typed::STATISTICS;
+    const bool chunks = out && (out->kind == Typed::CHUNKS || events), stats = out && (out->kind == Typed::STATISTICS || segment);
     const uint32_t n_const = reads ? reads->n_reads : n;   // how many reads have constants and statistics
     float2* cal = nullptr;   // the per-read constants
     const bool windows = chunks && (out->with_windows || events);
@@ -1680,6 +1744,17 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         if (!ensure_carved(c, c->normmeta, t, n_const)) return -1;
         rb.sig.norm = norm_out(out->norm, t.st, out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : t.ss);
     }
+    SegmentScratch sscratch;
+    if (segment) {   // the tables, and the maps: one bit a sample of the int16 layout, every read's rounded up to 4 bytes
+        const uint64_t map_cap = dst_bytes / 16 + 4ull * n_const + 64;
+        uint8_t* const map = ensure_carved(c, c->segmtab, sscratch, n_const) ? ensure_array<uint8_t>(c, c->segmap, map_cap) : nullptr;
+        if (!map) return -1;
+        c->seg = segment_out(out->seg);
+        c->seg.map = map;
+        c->seg.map_cap = map_cap;
+        c->seg.map_off = sscratch.map_off;
+        c->seg.rows = sscratch.rows;
+    }
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
         SizedTables h;
         if (!ensure_carved(c, c->meta, h, n)) return -1;
@@ -1696,6 +1771,9 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         HIPCHK(c, launch_window_check(rb, Pod5Reads(), out->f->offset, out->f->scale, wscratch, s), "window check launch");
         if (events) HIPCHK(c, launch_event_zero(rb, Pod5Reads(), wscratch, s), "event zero launch");
         else HIPCHK(c, launch_window_pad(rb, Pod5Reads(), wscratch, s), "window pad launch");
+    } else if (segment && !reads) {   // (the maps' layout, from the final int16 capacities: the headers' sizes when sized)
+        Timed t(c, "segment_layout");
+        HIPCHK(c, launch_segment_layout(rb, Pod5Reads(), sscratch, s), "segment layout launch");
     } else if (chunks && !reads) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
         Timed t(c, "chunk_slots");
         HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, out->f->offset, out->f->scale, rb.sig.chunk_len, rb.sig.step, out->chunk_first, out->chunk_rows,
@@ -1725,13 +1803,24 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
             streams.sig = rb.sig;
         }
         Timed t(c, "svb_decode");
+        if (segment) {   // (the pass over reads, then count, scan and emit)
+            HIPCHK(c, launch_svb16_segment_reads(streams, pr, c->seg, sscratch, s), "svb16 segment (reads) launch");
+            HIPCHK(c, launch_segment_emit(streams, pr, c->seg, sscratch, out->seg_first, out->seg_start, out->seg->start_cap, s), "segment emit launch");
+            return 0;
+        }
         HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s, c->trim.begin ? &c->trim : nullptr,
                                             windows ? &wscratch : nullptr, events ? out->ev_out : nullptr),
                "svb16_decode (reads) launch");
         return 0;
     }
-    // an event call: the records, behind everything the call has queued (the halves and the routed reads are joined by then)
+    // an event call: the records, behind everything the call has queued (the halves and the routed reads are joined by then); a
+    // segmentation call: count, scan and emit, at the same place
     auto finish = [&](int rc) {
+        if (rc == 0 && segment) {
+            Timed t(c, "segment_emit");
+            HIPCHK(c, launch_segment_emit(rb, Pod5Reads(), c->seg, sscratch, out->seg_first, out->seg_start, out->seg->start_cap, s), "segment emit launch");
+            return 0;
+        }
         if (rc != 0 || !events) return rc;
         Timed t(c, "event_finish");
         HIPCHK(c, launch_event_finish(rb, Pod5Reads(), out->f->offset, out->f->scale, wscratch, out->ev_out, s), "event finish launch");
@@ -1755,11 +1844,11 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
 // message; with several, the first in this order.
 int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const TypedCall& call)
 {
-    static const char* const WHAT[] = { "signal", "chunk", "statistics", "event" };
+    static const char* const WHAT[] = { "signal", "chunk", "statistics", "event", "segmentation" };
     if (!c || !bt) return -1;                                                                                        // 1
     DeviceGuard dg(c->device);                                                                                       // 2
     TypedCall t = call;
-    const bool stats = t.kind == Typed::STATISTICS;
+    const bool stats = t.kind == Typed::STATISTICS || t.kind == Typed::SEGMENT;   // (no format: is_signed alone)
     const bool type_ok = stats || (t.f && t.f->out_type >= VBZ_GPU_SIGNAL_F32 && t.f->out_type <= VBZ_GPU_SIGNAL_BF16);
     if (!typed_args_ok(c, o, t.sized, WHAT[(int)t.kind], type_ok, stats ? t.is_signed : t.f ? t.f->is_signed : 0u)) return -2;   // 3
     if (t.pod5 && !pod5_reads_ok(c, o, t.reads)) return -2;                                                         // 4
@@ -1767,6 +1856,7 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     if (!ranges_ok(c, t.ranges)) return -2;                                                                          // 6
     const uint32_t n_out = t.pod5 ? t.reads->n_reads : bt->n_reads;   // the reads the per-read tables have an entry for
     if (t.with_trim && !trim_ok(c, t.trim, t.begin)) return -2;                                                      // 7
+    if (t.kind == Typed::SEGMENT && !segmentation_ok(c, t.seg, t.seg_first, t.seg_start)) return -2;                 // 7 (a segmentation in the trim's place)
     if (!t.shift_scale && (t.shift_scale_null == Null::REFUSED || (t.shift_scale_null == Null::REFUSED_WITH_READS && n_out != 0))) {
         set_error(c, "shift_scale is NULL");
         return -2;
@@ -2003,7 +2093,7 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
     return 0;
 }
 
-// The eighteen typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
+// The twenty typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
 //
 //   vbz_gpu_..._batch             kind        sized  chunking  norm      shift_scale          ranges    reads  trim   (chunking "windows": a
 //                                                                                                                   vbz_gpu_windows in its place;
@@ -2018,6 +2108,7 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   signal_norm                   STATISTICS  arg    -         required  required             -         -      -
 //   signal_norm_range             STATISTICS  arg    -         required  required             nullable  -      -
 //   signal_trim                   STATISTICS  arg    -         required  nullable             nullable  -      yes
+//   signal_segment                SEGMENT     arg    -         -         -                    nullable  -      segmentation (in the trim's place)
 //   pod5_decompress_signal_norm   SIGNAL      0      -         required  nullable             -         yes    -
 //   pod5_decompress_chunks        CHUNKS      0      yes       nullable  nullable             -         yes    -
 //   pod5_decompress_chunks_range  CHUNKS      0      yes       nullable  nullable             nullable  yes    -
@@ -2026,6 +2117,7 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   pod5_signal_norm              STATISTICS  0      -         required  required with reads  -         yes    -
 //   pod5_signal_norm_range        STATISTICS  0      -         required  required with reads  nullable  yes    -
 //   pod5_signal_trim              STATISTICS  0      -         required  nullable             nullable  yes    yes
+//   pod5_signal_segment           SEGMENT     0      -         -         -                    nullable  yes    segmentation
 //
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
@@ -2035,6 +2127,8 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 // - chunk_first and the chunk arena may be NULL when there is no read to store: batch->n_reads == 0, or, over POD5 reads,
 //   reads->n_reads == 0 (whatever the number of rows).  The window entries: window_first, start (with window_rows != 0) and the arena, likewise;
 //   the event entries: event_first, start (with event_rows != 0) and the event arena.
+// - the segmentation entries: event_first is never NULL (a call of no reads writes event_first[0]); start is NULL exactly in the
+//   count-only call (start_cap == 0).
 int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::SIGNAL, sized).format(f));
@@ -2166,6 +2260,20 @@ int vbz_gpu_pod5_signal_trim_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, cons
 {
     return typed_decode(c, bt, o, TypedCall(Typed::STATISTICS, 0).statistics(is_signed).pod5_reads(reads)
                                       .normalise(norm, Null::REFUSED, shift_scale, Null::ALLOWED).range(ranges).trimmed(trim, begin));
+}
+
+int vbz_gpu_signal_segment_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                                 const vbz_gpu_sample_ranges* ranges, const vbz_gpu_segmentation* segmentation, uint64_t* event_first, uint32_t* start)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::SEGMENT, sized).statistics(is_signed).range(ranges).segmented(segmentation, event_first, start));
+}
+
+int vbz_gpu_pod5_signal_segment_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                      const vbz_gpu_pod5_reads* reads, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_segmentation* segmentation,
+                                      uint64_t* event_first, uint32_t* start)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::SEGMENT, 0).statistics(is_signed).pod5_reads(reads).range(ranges)
+                                      .segmented(segmentation, event_first, start));
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

@@ -297,6 +297,58 @@ hipError_t launch_window_pad(const ReadBatch& b, const Pod5Reads& pr, const Wind
 hipError_t launch_event_zero(const ReadBatch& b, const Pod5Reads& pr, const WindowScratch& w, hipStream_t s);
 hipError_t launch_event_finish(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, const WindowScratch& w, void* out,
                                hipStream_t s);
+// Signal segmentation (vbz_gpu_*_signal_segment_batch; the rule: include/vbz_gpu.h): a pass of the svb decoder of its own kernels
+// (svb_kernels.hip: SegmentStore) scores every position of a read's signal with the two-window t-statistic, picks the boundaries and
+// leaves them as one bit per position in the read's map -- bytes [map_off[i], map_off[i] + ceil(T' / 8)) of `map`, every byte written by
+// one lane, no sample stored -- and the read's row count (boundaries + 1; 0 for an empty signal) in rows[i].  Like the trim, the call's
+// state is an argument of its own of the kernels that take it.  i: the read's entry of the call's tables (rmap: a routed read's; the
+// upper half of a split call gets the tables offset).  A read whose map does not end inside map_cap gets E_OOM.
+constexpr uint32_t SEGMENT_WINDOW_MAX = 32, SEGMENT_RADIUS_MAX = 32;
+struct SegmentOut
+{
+    uint8_t* map = nullptr;              // nullptr: not a segmentation call
+    const uint64_t* map_off = nullptr;   // [n + 1], multiples of 4 (launch_segment_layout)
+    uint64_t map_cap = 0;
+    uint32_t* rows = nullptr;            // [n]
+    const uint32_t* rmap = nullptr;
+    uint32_t w1 = 1, w2 = 0, r = 1;      // the two windows (w2 0: one detector) and the radius
+    double k1 = 1.0, k2 = 1.0;           // float64(t) * float64(t) of the two thresholds (exact: 48 bits)
+};
+// The tables of a segmentation call, per read of the call (POD5 reads of several rows: per READ): the maps' sizes and offsets, the sinks'
+// row counts, the counts of the reads that passed and their scan.
+struct SegmentScratch
+{
+    uint64_t* map_off = nullptr;   // [n + 1]
+    uint64_t* scan = nullptr;      // [n + 1]
+    uint32_t* size = nullptr;      // [n]
+    uint32_t* rows = nullptr;      // [n]
+    uint32_t* count = nullptr;     // [n]
+    size_t carve(void* base, uint32_t n)   // (host only; base == nullptr measures: scratch_tables.h)
+    {
+        MetaCarver mc(base);
+        map_off = mc.take<uint64_t>((size_t)n + 1);
+        scan = mc.take<uint64_t>((size_t)n + 1);
+        size = mc.take<uint32_t>(n);
+        rows = mc.take<uint32_t>(n);
+        count = mc.take<uint32_t>(n);
+        return mc.bytes();
+    }
+};
+// launch_segment_layout (pack.hip), in front of the pass: map_off = the scan of the maps' sizes, ceil(T / 8) rounded up to 4 bytes, T the
+// read's samples (b.dst_cap; pr.reads, behind the plan: the reads').  launch_segment_emit (pack.hip), behind everything the call has
+// queued: count[i] = rows[i] of a read whose result (POD5: every row's) is no error and has samples, else 0; their scan; then one
+// workgroup per read writes event_first[i] (the last one event_first[n] too) and, where the read's rows end at or in front of start_cap,
+// its starts -- 0 and the positions of its map's bits, in order -- else E_DESTINATION_SIZE to its result (POD5: its rows' and
+// read_result).  start == nullptr: event_first alone.  A bad first_row (*pr.bad): nothing is written.
+hipError_t launch_segment_layout(const ReadBatch& b, const Pod5Reads& pr, const SegmentScratch& sc, hipStream_t s);
+hipError_t launch_segment_emit(const ReadBatch& b, const Pod5Reads& pr, const SegmentOut& so, const SegmentScratch& sc, uint64_t* event_first,
+                               uint32_t* start, uint64_t start_cap, hipStream_t s);
+// The pass itself (svb_kernels.hip), one workgroup per read on every path: launch_svb_segment (the svb codec, int16), launch_svb16_segment
+// (POD5 rows as reads) and launch_svb16_segment_reads (POD5 reads of several rows, behind launch_pod5_reads_check: the plan, the layout,
+// the pass -- a read's workgroup walks its rows in turn and writes their verdicts --, the read results).  result[] is the int16 decode's.
+hipError_t launch_svb_segment(const ReadBatch& b, bool zigzag, const SegmentOut& so, hipStream_t s);
+hipError_t launch_svb16_segment(const ReadBatch& b, const SegmentOut& so, hipStream_t s);
+hipError_t launch_svb16_segment_reads(const ReadBatch& b, const Pod5Reads& pr, const SegmentOut& so, const SegmentScratch& sc, hipStream_t s);
 // row j of the rows counted in scan (n + 1 offsets, scan[0] = 0 <= j < scan[n]) -> its read: the last k with scan[k] <= j
 __device__ inline uint32_t scan_find(const uint64_t* scan, uint32_t n, uint64_t j)
 {
