@@ -178,6 +178,39 @@ def test_split_batch():
     assert outs[0] == outs[1]
 
 
+@pytest.mark.parametrize("ranged", [False, True], ids=["whole", "ranged"])
+@pytest.mark.parametrize("at", [30, 150], ids=["lower-half", "upper-half"])
+def test_routed_long_read_in_a_split_batch(at, ranged, monkeypatch):
+    """both cuts of one call: the routed read finds its map, its row count and its range through the routing map, the upper half through
+    its offset tables"""
+    rng = np.random.default_rng(43)
+    reads = [steps(rng, int(rng.integers(500, 5000))) for _ in range(200)]
+    reads[at] = steps(rng, 262_144)
+    bg = en = None
+    if ranged:   # (odd begins)
+        bg, en = [9 if i % 2 else 3 for i in range(200)], [TO_END if i % 3 else 2000 for i in range(200)]
+        bg[at], en[at] = 2003, 260_000
+    outs = []
+    # (shape: the call's launches of route and svb_decode -- routed and two halves, the routed group's own not counted; one group.  The
+    # context made here has seen no frames, so its first call runs as halves whatever an earlier call held: a context that saw mostly
+    # frames left to the one-wavefront decoder runs its next call as one group)
+    monkeypatch.setenv("VBZ_HIP_SPLIT_MIN", "64")
+    unused = batch.GpuCodec(0)
+    monkeypatch.delenv("VBZ_HIP_SPLIT_MIN")
+    for c, shape in ((unused, (1, 2)), (codec(VBZ_HIP_SPLIT_MIN=64), None), (codec(VBZ_HIP_SPLIT_MIN=0, VBZ_HIP_ROUTING=0), (0, 1))):
+        fr = Frames(c, reads, c.options(True, 2, 1, 1))
+        c.profile_reset()
+        c.profile(True)
+        r = SegRun(fr, PARAMS[3] if ranged else S.DEFAULT, bg, en)
+        c.profile(False)
+        prof = {k: v[0] for k, v in c.profile_read().items()}
+        assert shape is None or (prof.get("route", 0), prof["svb_decode"]) == shape, sorted(prof.items())
+        r.check()
+        assert len(r.want_st[at]) > 3000
+        outs.append((r.t.first.cpu().numpy().tobytes(), r.t.start.cpu().numpy().tobytes(), u32(r.result).tolist()))
+    assert outs[0] == outs[2] and outs[1] == outs[2]
+
+
 # ---- ranges -------------------------------------------------------------------------------------------------------------------------------------
 def test_ranges():
     c = codec()

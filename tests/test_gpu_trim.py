@@ -284,6 +284,77 @@ def test_routed_long_read_among_small_ones():
     assert u32(TrimRun(fr, T.DEFAULT, "med_mad", with_ss=False).result)[: fr.n].tolist() == stats_results(fr, "med_mad")
 
 
+def routed_split_reads(at):
+    """200 small reads and one of 300 000 samples at index `at`, a plateau at [16 000, 17 000): routed out of a batch that runs as halves"""
+    reads = small_batch(45, 200, 500, 5000)
+    reads[at] = T.make_read(np.random.default_rng(46), 300_000, "none")
+    reads[at][16_000:17_000] += 150
+    return reads
+
+
+def unused_codec(monkeypatch, **env):
+    """a context of its own under the knobs.  It has seen no frames, so its first decompress call runs as halves whatever an earlier call
+    held (a context that saw mostly frames left to the one-wavefront decoder runs its next call as one group)"""
+    for name, v in env.items():
+        monkeypatch.setenv(name, str(v))
+    c = batch.GpuCodec(0)
+    for name in env:
+        monkeypatch.delenv(name)
+    return c
+
+
+@pytest.mark.parametrize("at", [30, 150], ids=["lower-half", "upper-half"])
+def test_routed_long_read_in_a_split_batch(at, monkeypatch):
+    """both cuts of one call: the routed read writes begin and shift_scale through the map, the upper half through its offset tables"""
+    reads = routed_split_reads(at)
+    outs = []
+    # (shape: the call's launches of route and svb_decode -- routed and two halves, the routed group's own not counted; one group)
+    for c, shape in ((unused_codec(monkeypatch, VBZ_HIP_SPLIT_MIN=64), (1, 2)), (codec(VBZ_HIP_SPLIT_MIN=64), None),
+                     (codec(VBZ_HIP_SPLIT_MIN=0, VBZ_HIP_ROUTING=0), (0, 1))):
+        fr = Frames(c, reads, c.options(True, 2, 1, 1))
+        c.profile_reset()
+        c.profile(True)
+        run = TrimRun(fr, LARGE_TRIM, "quantile")
+        c.profile(False)
+        prof = {k: v[0] for k, v in c.profile_read().items()}
+        assert shape is None or (prof.get("route", 0), prof["svb_decode"]) == shape, sorted(prof.items())
+        got = run.check()
+        assert got[at] >= 17_000, got[at]
+        outs.append((got, run.ss.cpu().numpy().tobytes(), u32(run.result).tolist()))
+    assert outs[0] == outs[2] and outs[1] == outs[2]
+
+
+def test_a_trim_call_leaves_nothing_behind_on_its_codec(monkeypatch):
+    """a plain decompress and a compress of the same reads behind a trim call that ran routed and as halves (asserted: one route, two
+    svb_decode), so that the upper half's and the routed reads' contexts have served it: the bytes of a context that has run no typed
+    call.  The trim is the call's, not the context's or its children's.  (Which shape the plain decompress takes is the library's
+    choice and not asserted.)"""
+    reads = routed_split_reads(150)
+    outs = []
+    for trim_first in (True, False):
+        c = unused_codec(monkeypatch, VBZ_HIP_SPLIT_MIN=64)
+        opts = c.options(True, 2, 1, 1)
+        fr = Frames(c, reads, opts)
+        if trim_first:
+            c.profile_reset()
+            c.profile(True)
+            run = TrimRun(fr, LARGE_TRIM, "quantile")
+            c.profile(False)
+            prof = {k: v[0] for k, v in c.profile_read().items()}
+            assert (prof.get("route", 0), prof["svb_decode"]) == (1, 2), sorted(prof.items())
+            run.check()
+        back = torch.full((fr.dst_bytes + 64,), 0x5A, dtype=torch.uint8, device=c.device)
+        res = torch.full((fr.n,), -8, dtype=torch.int32, device=c.device)
+        c.decompress(fr.src, fr.off, fr.size, back, fr.doff, fr.dcap, res, opts)
+        again = Frames(c, reads, opts)   # (the compress call)
+        torch.cuda.synchronize()
+        assert u32(res).tolist() == [2 * t for t in fr.T]
+        host = back.cpu().numpy()
+        assert all(host[o : o + 2 * t].tobytes() == x.tobytes() for o, t, x in zip(fr.doff.tolist(), fr.T, fr.reads))
+        outs.append((host.tobytes(), again.src.cpu().numpy().tobytes(), u32(again.size).tolist()))
+    assert outs[0] == outs[1]
+
+
 # ---- 5. frames of other origins --------------------------------------------------------------------------------------------------------------------
 def test_libzstd_frames():
     c = codec()

@@ -13,6 +13,7 @@
 #include <condition_variable>
 #include <deque>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <map>
 #include <vector>
@@ -226,11 +227,7 @@ struct vbz_gpu_ctx
     DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call (NormTables)
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables, the reads' constants (Pod5Tables)
-    // The state of the call in flight, handed to the children as it is (not a setting: outside Knobs)
-    TrimOut trim;              // the signal trim of the decompress call in flight (begin == nullptr: none); every decompress call sets it,
-                               // and the contexts of a batch's upper half and of the routed reads get theirs from it
-    SegmentOut seg;            // the segmentation of the decompress call in flight (map == nullptr: none), set and handed on as the trim is
-    bool profiling = false;
+    bool profiling = false;    // (not a setting: outside Knobs; the upper half of a split call gets the call's)
     PinnedBuf pinned;          // the single-buffer API's pinned area (run_one)
     uint32_t one_seq = 0;      // the single-buffer API's hand-back flag: a number per call (run_one)
     std::vector<PendingEvent> pending;
@@ -864,36 +861,36 @@ int entropy_decode_spans(vbz_gpu_ctx* c, const ReadBatch& z, uint32_t toosmall_c
     return 0;
 }
 
-// The svb stage of a decompress group (d: the streams -> the reads, with the store and the normalising passes of d.sig)
-int svb_decode_stage(vbz_gpu_ctx* c, const ReadBatch& d, const CompressionOptions* o, bool segmented, const SegTables& seg)
+// The svb stage of a decompress group (j.rb: the streams -> the reads, with the store and the normalising passes of its sig)
+int svb_decode_stage(vbz_gpu_ctx* c, const DecodeJob& j, const CompressionOptions* o, bool segmented, const SegTables& seg)
 {
     Timed t(c, "svb_decode");
-    const TrimOut* const trim = c->trim.begin ? &c->trim : nullptr;
-    if (c->seg.map) {   // (a segmentation call: kernels of their own, one workgroup per read on every path -- DESIGN.md 4.20)
-        if (pod5_codec(o)) HIPCHK(c, launch_svb16_segment(d, c->seg, c->stream), "svb16 segment launch");
-        else HIPCHK(c, launch_svb_segment(d, o->perform_delta_zig_zag, c->seg, c->stream), "svb segment launch");
+    const TrimOut* const trim = j.trim.begin ? &j.trim : nullptr;
+    if (j.seg.map) {   // (a segmentation call: kernels of their own, one workgroup per read on every path -- DESIGN.md 4.20)
+        if (pod5_codec(o)) HIPCHK(c, launch_svb16_segment(j.rb, j.seg, c->stream), "svb16 segment launch");
+        else HIPCHK(c, launch_svb_segment(j.rb, o->perform_delta_zig_zag, j.seg, c->stream), "svb segment launch");
         return 0;
     }
     if (pod5_codec(o))   // (one workgroup per read on every path: DESIGN.md 4.13)
-        HIPCHK(c, launch_svb16_decode(d, c->stream, trim), "svb16_decode launch");
+        HIPCHK(c, launch_svb16_decode(j.rb, c->stream, trim), "svb16_decode launch");
     else if (segmented)
-        HIPCHK(c, launch_svb_decode_seg(d, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->stream, trim),
+        HIPCHK(c, launch_svb_decode_seg(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->stream, trim),
                "svb_decode (segmented) launch");
     else
-        HIPCHK(c, launch_svb_decode(d, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream, trim), "svb_decode launch");
+        HIPCHK(c, launch_svb_decode(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream, trim), "svb_decode launch");
     return 0;
 }
 
-// One launch group of a decompress call: the reads of rb_in (dst_cap = the exact decoded byte counts; those whose gate is closed
+// One launch group of a decompress call: the reads of j.rb (dst_cap = the exact decoded byte counts; those whose gate is closed
 // left alone), on the one-workgroup path or on the large-read path.  dst_bytes: extent of the decoded bytes of the group.
 // streams (nullable; both stages only): the svb stage is the caller's -- *streams is what it decodes (the streams, the group's gate)
-int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes, const CompressionOptions* o, bool segmented,
+int decompress_group(vbz_gpu_ctx* c, DecodeJob j, uint64_t dst_bytes, const CompressionOptions* o, bool segmented,
                      const Preplanned* pre = nullptr, ReadBatch* streams = nullptr)
 {
-    const uint32_t n = rb_in.n_reads;
+    const uint32_t n = j.rb.n_reads;
     if (n == 0) return 0;
     hipStream_t s = c->stream;
-    ReadBatch rb = rb_in;
+    ReadBatch& rb = j.rb;
     if (o->integer_size == 0 && o->zstd_compression_level == 0) {
         Timed t(c, "copy_bytes");
         HIPCHK(c, launch_copy_bytes(rb, 0, s), "copy launch");
@@ -910,7 +907,7 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     const uint32_t* const gate_src = pre ? nullptr : segmented ? p.seg.gate : rb.gate;
     if (!p.both_stages && gate_src) HIPCHK(c, hipMemcpyAsync(p.m.gate, gate_src, 4ull * n, hipMemcpyDeviceToDevice, s), "gate copy");
     if (pre || gate_src) rb.gate = p.m.gate;
-    if (o->zstd_compression_level == 0) return svb_decode_stage(c, rb, o, segmented, p.seg);
+    if (o->zstd_compression_level == 0) return svb_decode_stage(c, j, o, segmented, p.seg);
     if (o->integer_size == 0) {  // vbz.cpp:259-262: content larger than the destination -> DESTINATION_SIZE
         if (segmented) {
             Timed t(c, "zstd_decode");
@@ -939,16 +936,15 @@ int decompress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t dst_bytes,
     }
     dbg_end(c, n, "zstd_decode: parse flush seqtables chain place huftable header queue | general sequences: flush tables records literals matches", dbg);
     if (verify_checksums(c, z) != 0) return -1;
-    ReadBatch d = rb;   // the svb stage: the streams -> the reads
-    d.src = (const uint8_t*)p.scratch_base;
-    d.src_off = p.m.svb_off;
-    d.src_size = p.m.svb_size;
-    d.gate = p.m.gate;
+    rb.src = (const uint8_t*)p.scratch_base;   // the svb stage: the streams -> the reads
+    rb.src_off = p.m.svb_off;
+    rb.src_size = p.m.svb_size;
+    rb.gate = p.m.gate;
     if (streams) {
-        *streams = d;
+        *streams = rb;
         return 0;
     }
-    return svb_decode_stage(c, d, o, segmented, p.seg);
+    return svb_decode_stage(c, j, o, segmented, p.seg);
 }
 
 // ---- per-read routing ----------------------------------------------------------------------------------------------------
@@ -966,7 +962,7 @@ constexpr uint64_t ROUTE_MAX_BYTES = 64ull << 20;
 struct Routed
 {
     uint32_t* gate_small = nullptr;   // [n]
-    ReadBatch large;                  // ROUTE_MAX_READS compact entries (gate: GATE_SKIP behind the routed ones)
+    DecodeJob large;                  // ROUTE_MAX_READS compact entries (gate: GATE_SKIP behind the routed ones); compress: large.rb alone
     uint32_t* large_orig = nullptr;   // compress: raw sizes of the routed reads (= large.src_size); decompress: unused
     uint32_t* map = nullptr;          // [ROUTE_MAX_READS] index of each routed read in the batch
     uint32_t* count = nullptr;        // [1]
@@ -992,11 +988,9 @@ int join(vbz_gpu_ctx* c, const Child& k)
     return 0;
 }
 
-// What a child context works with.  Its settings are the parent's, whole (Knobs), with the few that make it the child it is; the state of
-// the call in flight is handed over beside them.  Against the field-by-field copies this replaces: a field that was not copied is read
-// from the environment alone (staged_encode, fast_decode, ref_chains, phase_timing, trace for `large`; phase_timing, trace for `half`),
-// so the parent holds what the child read for itself when it was made -- or the child never reads it: canonical and shared_tables on
-// `half` (compress_batch_impl and the span encoder read them; a half is a launch group on the one-workgroup path).
+// What a child context works with: the parent's settings, whole (Knobs), with the few that make it the child it is -- copied field by
+// field, those left out (staged_encode, fast_decode, ref_chains, phase_timing, trace) were what the child had read from the environment
+// for itself when it was made.  What a decompress call asks of a child is no context's state: it rides on the child's DecodeJob.
 // large: the routed reads, and canonical mode's large ones -- the large-read path, nothing routed or split again.
 int inherit_large(vbz_gpu_ctx* c)
 {
@@ -1009,13 +1003,11 @@ int inherit_large(vbz_gpu_ctx* c)
     k->knobs.routing = false;
     k->knobs.split_min = 0;
     k->knobs.segmented = 1;
-    k->trim = c->trim;   // (the routed reads write begin through the routing map, as they do shift_scale)
-    k->seg = c->seg;     // (and find their maps and row counts through it: route() sets SegmentOut::rmap)
     return 0;
 }
 // half: the upper half [n / 2, n) of a split call -- the one-workgroup path; it gets the call's profiling switch (its launches count under
 // the parent's labels: vbz_gpu_profile_read) and what is known of foreign frames.
-int inherit_half(vbz_gpu_ctx* c, uint32_t n)
+int inherit_half(vbz_gpu_ctx* c)
 {
     if (!c->half.create(c->device)) {
         set_error(c, "could not create the context of a batch's upper half");
@@ -1028,14 +1020,10 @@ int inherit_half(vbz_gpu_ctx* c, uint32_t n)
     k->knobs.segmented = 0;
     k->profiling = c->profiling;
     k->foreign_state = c->foreign_state;
-    k->trim = c->trim;   // (the upper half's begin entries: the table offset, as upper_half() offsets shift_scale)
-    if (k->trim.begin) k->trim.begin += n / 2;
-    k->seg = c->seg;     // (likewise the segmentation's per-read tables)
-    if (k->seg.map) k->seg.map_off += n / 2, k->seg.rows += n / 2;
     return 0;
 }
 
-int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed* r)
+int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed* r, const TrimOut& trim = {}, const SegmentOut& seg = {})
 {
     const uint32_t n = rb.n_reads;
     if (inherit_large(c) != 0) return -1;
@@ -1048,23 +1036,24 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     r->gate_small = tab.gate_small;
     r->map = l.map;
     r->count = l.count;
-    r->large = rb;
-    r->large.n_reads = ROUTE_MAX_READS;
-    r->large.src_off = l.src_off;
-    r->large.src_size = l.src_size;
-    r->large.dst_off = l.dst_off;
-    r->large.dst_cap = l.dst_cap;
-    r->large.gate = l.gate;
-    r->large.result = tab.result;
-    if (rb.sig.cal) r->large.sig.cal = l.cal;   // (the routed reads' constants, gathered through the map)
-    if (rb.sig.row) r->large.sig.row = l.row;   // (and their first chunk rows)
-    if (rb.sig.norm.st) {   // (a normalising decode: states of their own; shift_scale written back through the map)
-        r->large.sig.norm.st = tab.norm;
-        r->large.sig.norm.map = r->map;
+    ReadBatch& g = r->large.rb = rb;
+    g.n_reads = ROUTE_MAX_READS;
+    g.src_off = l.src_off;
+    g.src_size = l.src_size;
+    g.dst_off = l.dst_off;
+    g.dst_cap = l.dst_cap;
+    g.gate = l.gate;
+    g.result = tab.result;
+    if (rb.sig.cal) g.sig.cal = l.cal;   // (the routed reads' constants, gathered through the map)
+    if (rb.sig.row) g.sig.row = l.row;   // (and their first chunk rows)
+    if (rb.sig.norm.st) {   // (a normalising decode: states of their own; shift_scale, and a trim's begin, written back through the map)
+        g.sig.norm.st = tab.norm;
+        g.sig.norm.map = r->map;
     }
-    if (rb.sig.ranged()) r->large.sig.rmap = r->map;   // (their ranges: the call's tables, through the map)
-    if (rb.sig.wfirst) r->large.sig.wmap = r->map;     // (and their windows)
-    if (c->seg.map) c->large->seg.rmap = r->map;        // (and their boundary maps)
+    if (rb.sig.ranged()) g.sig.rmap = r->map;   // (their ranges: the call's tables, through the map)
+    if (rb.sig.wfirst) g.sig.wmap = r->map;     // (and their windows)
+    r->large.trim = trim, r->large.seg = seg;   // (a decompress call's trim and segmentation: the routed reads share them)
+    if (seg.map) r->large.seg.rmap = r->map;    // (their boundary maps and row counts: through the map too)
     Timed t(c, "route");
     a.raw_size = raw_size;
     a.min_bytes = ROUTE_MIN_BYTES;
@@ -1078,7 +1067,7 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
 // the second group is done before anything enqueued behind the call runs
 int route_join(vbz_gpu_ctx* c, const Routed& r, uint32_t* result)
 {
-    HIPCHK(c, launch_route_results(r.large.result, r.map, r.count, ROUTE_MAX_READS, result, c->large->stream), "route results launch");
+    HIPCHK(c, launch_route_results(r.large.rb.result, r.map, r.count, ROUTE_MAX_READS, result, c->large->stream), "route results launch");
     return join(c, c->large);
 }
 
@@ -1109,7 +1098,7 @@ int split_plan(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, ui
                bool one_sizes = false)
 {
     const uint32_t n = rb.n_reads;
-    if (inherit_half(c, n) != 0) return -1;
+    if (inherit_half(c) != 0) return -1;
     const size_t scratch_need = (size_t)(((unsigned __int128)raw_bytes * num + den - 1) / den) + (size_t)n * 96 + 256;
     SplitTables tab;
     if (!ensure(c, c->scratch, scratch_need) || !ensure_carved(c, c->splitmeta, tab, n)) return -1;
@@ -1155,6 +1144,13 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
     if (u.sig.wfirst) u.sig.wfirst += h;
     return u;
 }
+DecodeJob upper_half(const DecodeJob& job, uint32_t h)   // (the same cut of a decompress job: its own per-read tables move with the batch's)
+{
+    DecodeJob u{ upper_half(job.rb, h), job.trim, job.seg };
+    if (u.trim.begin) u.trim.begin += h;
+    if (u.seg.map) u.seg.map_off += h, u.seg.rows += h;
+    return u;
+}
 
 // the upper half's stream is joined whatever happened in between (it may still be writing the caller's arenas)
 int split_join(vbz_gpu_ctx* c)
@@ -1179,18 +1175,19 @@ int compress_split(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t src_bytes, cons
 }
 
 // streams (nullable): as for decompress_group -- the halves run the entropy stage, *streams is the whole batch's behind the join
-int decompress_split(vbz_gpu_ctx* c, const ReadBatch& rb, uint64_t dst_bytes, const CompressionOptions* o, ReadBatch* streams = nullptr)
+int decompress_split(vbz_gpu_ctx* c, const DecodeJob& job, uint64_t dst_bytes, const CompressionOptions* o, ReadBatch* streams = nullptr)
 {
     uint32_t num, den;
     svb_factor(o->integer_size, false, &num, &den);
     Split sp;
-    if (split_plan(c, rb, rb.dst_cap, dst_bytes, num, den, &sp, streams != nullptr) != 0) return -1;
-    ReadBatch lo = rb, hi_streams;
-    lo.n_reads = sp.h;
+    if (split_plan(c, job.rb, job.rb.dst_cap, dst_bytes, num, den, &sp, streams != nullptr) != 0) return -1;
+    DecodeJob lo = job;
+    ReadBatch hi_streams;
+    lo.rb.n_reads = sp.h;
     int rc = decompress_group(c, lo, dst_bytes, o, false, &sp.lo, streams);
-    if (rc == 0) rc = decompress_group(c->half, upper_half(rb, sp.h), dst_bytes, o, false, &sp.hi, streams ? &hi_streams : nullptr);
+    if (rc == 0) rc = decompress_group(c->half, upper_half(job, sp.h), dst_bytes, o, false, &sp.hi, streams ? &hi_streams : nullptr);
     if (split_join(c) != 0) rc = -1;
-    if (streams) streams->n_reads = rb.n_reads;   // (the lower half's tables are the whole batch's, cut at h)
+    if (streams) streams->n_reads = job.rb.n_reads;   // (the lower half's tables are the whole batch's, cut at h)
     c->last_split = rc == 0;
     return rc;
 }
@@ -1285,7 +1282,7 @@ int compress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compressi
     // (the second group first: its launches are short.)  Whatever fails from here on, the second stream is joined before the call
     // returns -- it may still be writing the caller's arenas -- and its error message becomes the context's
     int rc = 0;
-    if (compress_group(c->large, r.large, ROUTE_MAX_BYTES, o, sized, true) != 0) rc = -1;
+    if (compress_group(c->large, r.large.rb, ROUTE_MAX_BYTES, o, sized, true) != 0) rc = -1;
     if (rc == 0 && (split ? compress_split(c, small, bt->src_bytes, o, sized) : compress_group(c, small, bt->src_bytes, o, sized, false)) != 0) rc = -1;
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
     if (route_join(c, r, bt->result) != 0) rc = -1;
@@ -1666,9 +1663,6 @@ int signal_slots(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const vbz_gpu_signal_f
     return 0;
 }
 
-// Chunk decode (vbz_gpu_decompress_chunks_batch): the caller's dst side is the int16 layout of the same reads, so the descriptor checks,
-// sized headers, scratch plan, routing and the split are the int16 call's (chunk_out: where the samples go instead).
-
 // The call's tables over POD5 reads (Pod5Reads) and the reads' constants, from ctx->pod5meta; the check of first_row is queued here, before
 // any other launch of the call (out: read_result or read_samples, nullable -- E_INPUT_SIZE in every entry when the table is bad)
 int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* reads, uint32_t* out, Pod5Reads* pr, float2** cal)
@@ -1685,6 +1679,88 @@ int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* 
     return 0;
 }
 
+struct CallScratch { WindowScratch win; SegmentScratch seg; float2* cal = nullptr; };   // a window or an event call's (scan == nullptr: neither); a segmentation's; the per-read constants
+
+// Outputs: what the call stores and where.  j->rb (the caller's batch so far) gets its sig and the arena the svb stage writes, j->trim /
+// j->seg a trim's or a segmentation's rule and tables; *dst_bytes: the extent of the int16 layout the call decodes through (every kind
+// but SIGNAL: the caller's dst side as it is).  sc->cal comes in as the constants' table of a call over POD5 reads (pod5_reads_begin).
+int typed_outputs(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const TypedCall& t, DecodeJob* j, uint64_t* dst_bytes, CallScratch* sc)
+{
+    ReadBatch& rb = j->rb;
+    const uint32_t n = bt->n_reads, n_const = t.reads ? t.reads->n_reads : n;   // n_const: how many reads have constants and statistics
+    float2* cal = nullptr;   // the per-read constants
+    switch (t.kind) {
+    case Typed::SIGNAL:   // typed slots (of POD5 rows too)
+        if (signal_slots(c, bt, t.f, &rb, dst_bytes, &cal) != 0) return -1;
+        break;
+    case Typed::CHUNKS:
+        if (t.with_windows) window_out(t.win, t.win_out, &rb);
+        else chunk_out(t.ch, t.chunk_first, t.chunks, &rb);
+        if (t.with_windows && !ensure_carved(c, c->winmeta, sc->win, n_const)) return -1;
+        break;
+    case Typed::EVENTS: {   // (an event call takes the window call's way: its tables are the windows')
+        void* const moments = t.ev_moments ? (void*)t.ev_moments : (void*)ensure_array<vbz_gpu_event_moments>(c, c->evmeta, std::max<uint64_t>(t.ev->event_rows, 1));
+        if (!moments || !ensure_carved(c, c->winmeta, sc->win, n_const)) return -1;
+        event_out(t.ev, moments, &rb);
+        break;
+    }
+    case Typed::STATISTICS: break;
+    case Typed::SEGMENT: {   // the tables, and the maps: one bit a sample of the int16 layout, every read's rounded up to 4 bytes
+        const uint64_t map_cap = *dst_bytes / 16 + 4ull * n_const + 64;
+        uint8_t* const map = ensure_carved(c, c->segmtab, sc->seg, n_const) ? ensure_array<uint8_t>(c, c->segmap, map_cap) : nullptr;
+        if (!map) return -1;
+        j->seg = segment_out(t.seg);
+        j->seg.map = map, j->seg.map_cap = map_cap;
+        j->seg.map_off = sc->seg.map_off, j->seg.rows = sc->seg.rows;
+        break;
+    }
+    }
+    if (t.reads) cal = sc->cal;   // (else, but for SIGNAL: the constants' table is chunk_slots' or the selects' to fill)
+    else if (t.kind != Typed::SIGNAL && !(cal = ensure_array<float2>(c, c->sigmeta, n))) return -1;
+    rb.sig.cal = sc->cal = cal, rb.sig.type = t.f->out_type, rb.sig.bias = t.f->is_signed ? 0u : 0x8000u;
+    if (t.ranges) rb.sig.rbegin = t.ranges->begin, rb.sig.rend = t.ranges->end, rb.sig.rstats = t.ranges->stats;   // (both tables NULL: un-ranged)
+    NormTables nt;   // (ss: for a caller that passed no shift_scale)
+    if (t.norm && !ensure_carved(c, c->normmeta, nt, n_const)) return -1;
+    if (t.norm) rb.sig.norm = norm_out(t.norm, nt.st, t.shift_scale ? reinterpret_cast<float2*>(t.shift_scale) : nt.ss);
+    if (t.with_trim) j->trim = trim_out(t.trim, t.begin);
+    return 0;
+}
+
+// Front: the launch a batch call owes in front of its groups, each from the final int16 capacities (the headers' sizes when sized)
+int typed_front(vbz_gpu_ctx* c, const TypedCall& t, const ReadBatch& rb, const CallScratch& sc)
+{
+    if (t.kind == Typed::EVENTS || (t.kind == Typed::CHUNKS && t.with_windows)) {   // (the window check, then the pad or the moments' zero)
+        Timed tm(c, "window_slots");
+        HIPCHK(c, launch_window_check(rb, Pod5Reads(), t.f->offset, t.f->scale, sc.win, c->stream), "window check launch");
+        if (t.kind == Typed::EVENTS) HIPCHK(c, launch_event_zero(rb, Pod5Reads(), sc.win, c->stream), "event zero launch");
+        else HIPCHK(c, launch_window_pad(rb, Pod5Reads(), sc.win, c->stream), "window pad launch");
+    } else if (t.kind == Typed::CHUNKS) {   // (the chunk check)
+        Timed tm(c, "chunk_slots");
+        HIPCHK(c, launch_chunk_slots(rb.n_reads, rb.dst_cap, t.f->offset, t.f->scale, rb.sig.chunk_len, rb.sig.step, t.chunk_first, t.chunk_rows,
+                                     sc.cal, const_cast<uint32_t*>(rb.gate), &rb.sig, c->stream), "chunk slots launch");
+    } else if (t.kind == Typed::SEGMENT) {   // (the maps' layout)
+        Timed tm(c, "segment_layout");
+        HIPCHK(c, launch_segment_layout(rb, Pod5Reads(), sc.seg, c->stream), "segment layout launch");
+    }
+    return 0;
+}
+
+// Finish: the launch a call (t, nullable) owes behind everything it has queued, the halves and the routed reads joined; rc: what that returned
+// (not 0: nothing owed).  j.rb: its reads, or with pr.reads the rows' streams (inside svb_decode's label; the event finish is the launcher's own)
+int typed_finish(vbz_gpu_ctx* c, const TypedCall* t, const DecodeJob& j, const Pod5Reads& pr, const CallScratch& sc, int rc)
+{
+    if (rc != 0 || !t) return rc;
+    std::optional<Timed> tm;
+    if (t->kind == Typed::SEGMENT) {   // (count, scan and emit)
+        if (!pr.reads) tm.emplace(c, "segment_emit");
+        HIPCHK(c, launch_segment_emit(j.rb, pr, j.seg, sc.seg, t->seg_first, t->seg_start, t->seg->start_cap, c->stream), "segment emit launch");
+    } else if (t->kind == Typed::EVENTS) {   // (the records)
+        tm.emplace(c, "event_finish");
+        HIPCHK(c, launch_event_finish(j.rb, pr, t->f->offset, t->f->scale, sc.win, t->ev_out, c->stream), "event finish launch");
+    }
+    return 0;
+}
+
 // out (nullable): a typed decode that typed_decode has checked (out->f is set)
 int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, bool own_descriptors = false,
                           const TypedCall* out = nullptr)
@@ -1692,69 +1768,18 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     const uint32_t n = bt->n_reads;
     c->last_frames = 0;
     c->last_span_frames = 0;
-    c->trim = out && out->with_trim ? trim_out(out->trim, out->begin) : TrimOut();
-    c->seg = SegmentOut();
     const vbz_gpu_pod5_reads* const reads = out ? out->reads : nullptr;
-    const bool segment = out && out->kind == Typed::SEGMENT;
     hipStream_t s = c->stream;
-    if (segment && (reads ? reads->n_reads : n) == 0) HIPCHK(c, hipMemsetAsync(out->seg_first, 0, 8, s), "event_first of no reads");
+    if (out && out->kind == Typed::SEGMENT && (reads ? reads->n_reads : n) == 0) HIPCHK(c, hipMemsetAsync(out->seg_first, 0, 8, s), "event_first of no reads");
     if (n == 0 && !(reads && reads->n_reads)) return 0;
-    ReadBatch rb = to_rb(bt);
+    DecodeJob job{ to_rb(bt) };
+    ReadBatch& rb = job.rb;
     Pod5Reads pr;
-    float2* read_cal = nullptr;
-    if (reads && pod5_reads_begin(c, n, reads, reads->read_result, &pr, &read_cal) != 0) return -1;
+    CallScratch sc;
+    if (reads && pod5_reads_begin(c, n, reads, reads->read_result, &pr, &sc.cal) != 0) return -1;
     if (n != 0 && !own_descriptors && validate_descriptors(c, bt, &rb) != 0) return -1;
     uint64_t dst_bytes = bt->dst_bytes;
-    const bool events = out && out->kind == Typed::EVENTS;   // (an event call takes the window call's way: its tables are the windows')
-    const bool chunks = out && (out->kind == Typed::CHUNKS || events), stats = out && (out->kind == Typed::STATISTICS || segment);
-    const uint32_t n_const = reads ? reads->n_reads : n;   // how many reads have constants and statistics
-    float2* cal = nullptr;   // the per-read constants
-    const bool windows = chunks && (out->with_windows || events);
-    WindowScratch wscratch;
-    if (windows) {
-        if (events) {
-            void* const moments = out->ev_moments ? (void*)out->ev_moments : (void*)ensure_array<vbz_gpu_event_moments>(c, c->evmeta, std::max<uint64_t>(out->ev->event_rows, 1));
-            if (!moments) return -1;
-            event_out(out->ev, moments, &rb);
-        } else {
-            window_out(out->win, out->win_out, &rb);
-        }
-        if (!ensure_carved(c, c->winmeta, wscratch, n_const)) return -1;
-    } else if (chunks) {
-        chunk_out(out->ch, out->chunk_first, out->chunks, &rb);
-    }
-    if (out && !chunks && !stats) {   // typed slots (of POD5 rows too)
-        if (signal_slots(c, bt, out->f, &rb, &dst_bytes, &cal) != 0) return -1;
-    } else if (out && !reads) {   // the int16 layout as it is; the constants' table is chunk_slots' or the selects' to fill
-        if (!(cal = ensure_array<float2>(c, c->sigmeta, n))) return -1;
-    }
-    if (reads) cal = read_cal;
-    if (out) {
-        rb.sig.cal = cal;
-        rb.sig.type = out->f->out_type;
-        rb.sig.bias = out->f->is_signed ? 0u : 0x8000u;
-        if (out->ranges) {   // (both tables NULL: the un-ranged call)
-            rb.sig.rbegin = out->ranges->begin;
-            rb.sig.rend = out->ranges->end;
-            rb.sig.rstats = out->ranges->stats;
-        }
-    }
-    if (out && out->norm) {
-        NormTables t;   // (ss: for a caller that passed no shift_scale)
-        if (!ensure_carved(c, c->normmeta, t, n_const)) return -1;
-        rb.sig.norm = norm_out(out->norm, t.st, out->shift_scale ? reinterpret_cast<float2*>(out->shift_scale) : t.ss);
-    }
-    SegmentScratch sscratch;
-    if (segment) {   // the tables, and the maps: one bit a sample of the int16 layout, every read's rounded up to 4 bytes
-        const uint64_t map_cap = dst_bytes / 16 + 4ull * n_const + 64;
-        uint8_t* const map = ensure_carved(c, c->segmtab, sscratch, n_const) ? ensure_array<uint8_t>(c, c->segmap, map_cap) : nullptr;
-        if (!map) return -1;
-        c->seg = segment_out(out->seg);
-        c->seg.map = map;
-        c->seg.map_cap = map_cap;
-        c->seg.map_off = sscratch.map_off;
-        c->seg.rows = sscratch.rows;
-    }
+    if (out && typed_outputs(c, bt, *out, &job, &dst_bytes, &sc) != 0) return -1;
     if (sized) {  // vbz.cpp:332-366: strip the header, the original size becomes the exact destination size
         SizedTables h;
         if (!ensure_carved(c, c->meta, h, n)) return -1;
@@ -1766,20 +1791,7 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
         rb.dst_cap = h.orig_size;
         rb.gate = h.gate;
     }
-    if (windows && !reads) {   // (the window check, and the pad, which wants the final int16 capacities: the headers' sizes when sized)
-        Timed t(c, "window_slots");
-        HIPCHK(c, launch_window_check(rb, Pod5Reads(), out->f->offset, out->f->scale, wscratch, s), "window check launch");
-        if (events) HIPCHK(c, launch_event_zero(rb, Pod5Reads(), wscratch, s), "event zero launch");
-        else HIPCHK(c, launch_window_pad(rb, Pod5Reads(), wscratch, s), "window pad launch");
-    } else if (segment && !reads) {   // (the maps' layout, from the final int16 capacities: the headers' sizes when sized)
-        Timed t(c, "segment_layout");
-        HIPCHK(c, launch_segment_layout(rb, Pod5Reads(), sscratch, s), "segment layout launch");
-    } else if (chunks && !reads) {   // (the chunk check sees the final int16 capacities: the headers' sizes when sized)
-        Timed t(c, "chunk_slots");
-        HIPCHK(c, launch_chunk_slots(n, rb.dst_cap, out->f->offset, out->f->scale, rb.sig.chunk_len, rb.sig.step, out->chunk_first, out->chunk_rows,
-                                     cal, const_cast<uint32_t*>(rb.gate), &rb.sig, s),
-               "chunk slots launch");
-    }
+    if (out && !reads && typed_front(c, *out, rb, sc) != 0) return -1;   // (a call over POD5 reads: its plan, in the svb stage)
     const bool by_shape = n != 0 && o->integer_size != 0 && !half_codec(o) && use_segments(c, dst_bytes, n, true);
     if (c->foreign_pending && hipEventQuery(c->ev_foreign.p) == hipSuccess) {   // what the call before this one found (see foreign_host)
         const uint32_t* const found = c->foreign_host.words();
@@ -1794,50 +1806,36 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     if (reads) {
         // The rows go through the entropy stage as any batch's (a split call's halves included; rows are not routed: a read's rows meet
         // again in ONE svb stage behind the join, where the plan, the counting passes over reads and the store see all of them).
-        ReadBatch streams = rb;
+        DecodeJob streams = job;   // (what the svb stage over reads decodes: the rows' streams under the call's sig, trim and seg)
         if (n != 0) {
-            ReadBatch e = rb;
-            e.sig = SignalOut();
-            const int rc = split ? decompress_split(c, e, dst_bytes, o, &streams) : decompress_group(c, e, dst_bytes, o, by_shape, nullptr, &streams);
+            DecodeJob e{ rb };   // (the entropy stage alone stores nothing and owes no trim or segmentation)
+            e.rb.sig = SignalOut();
+            const int rc = split ? decompress_split(c, e, dst_bytes, o, &streams.rb) : decompress_group(c, e, dst_bytes, o, by_shape, nullptr, &streams.rb);
             if (rc != 0) return rc;
-            streams.sig = rb.sig;
+            streams.rb.sig = rb.sig;
         }
         Timed t(c, "svb_decode");
-        if (segment) {   // (the pass over reads, then count, scan and emit)
-            HIPCHK(c, launch_svb16_segment_reads(streams, pr, c->seg, sscratch, s), "svb16 segment (reads) launch");
-            HIPCHK(c, launch_segment_emit(streams, pr, c->seg, sscratch, out->seg_first, out->seg_start, out->seg->start_cap, s), "segment emit launch");
-            return 0;
+        if (streams.seg.map) {   // (the pass over reads, then count, scan and emit)
+            HIPCHK(c, launch_svb16_segment_reads(streams.rb, pr, streams.seg, sc.seg, s), "svb16 segment (reads) launch");
+            return typed_finish(c, out, streams, pr, sc, 0);
         }
-        HIPCHK(c, launch_svb16_decode_reads(streams, pr, out->f->offset, out->f->scale, out->chunk_rows, s, c->trim.begin ? &c->trim : nullptr,
-                                            windows ? &wscratch : nullptr, events ? out->ev_out : nullptr),
+        HIPCHK(c, launch_svb16_decode_reads(streams.rb, pr, out->f->offset, out->f->scale, out->chunk_rows, s, streams.trim.begin ? &streams.trim : nullptr,
+                                            sc.win.scan ? &sc.win : nullptr, out->ev_out),
                "svb16_decode (reads) launch");
         return 0;
     }
-    // an event call: the records, behind everything the call has queued (the halves and the routed reads are joined by then); a
-    // segmentation call: count, scan and emit, at the same place
-    auto finish = [&](int rc) {
-        if (rc == 0 && segment) {
-            Timed t(c, "segment_emit");
-            HIPCHK(c, launch_segment_emit(rb, Pod5Reads(), c->seg, sscratch, out->seg_first, out->seg_start, out->seg->start_cap, s), "segment emit launch");
-            return 0;
-        }
-        if (rc != 0 || !events) return rc;
-        Timed t(c, "event_finish");
-        HIPCHK(c, launch_event_finish(rb, Pod5Reads(), out->f->offset, out->f->scale, wscratch, out->ev_out, s), "event finish launch");
-        return 0;
-    };
     if (by_shape || !routing_applies(c, o, dst_bytes, n))
-        return finish(split ? decompress_split(c, rb, dst_bytes, o) : decompress_group(c, rb, dst_bytes, o, by_shape));
+        return typed_finish(c, out, job, pr, sc, split ? decompress_split(c, job, dst_bytes, o) : decompress_group(c, job, dst_bytes, o, by_shape));
     Routed r;
-    if (route(c, rb, rb.dst_cap, &r) != 0) return -1;   // by the decoded size
-    ReadBatch small = rb;
-    small.gate = r.gate_small;
+    if (route(c, rb, rb.dst_cap, &r, job.trim, job.seg) != 0) return -1;   // by the decoded size
+    DecodeJob small = job;
+    small.rb.gate = r.gate_small;
     int rc = 0;   // (as in compress_batch_impl: the second stream is joined whatever happens)
     if (decompress_group(c->large, r.large, ROUTE_MAX_BYTES, o, true) != 0) rc = -1;
     if (rc == 0 && (split ? decompress_split(c, small, dst_bytes, o) : decompress_group(c, small, dst_bytes, o, false)) != 0) rc = -1;
     if (rc != 0 && c->error.empty() && !c->large->error.empty()) c->error = c->large->error;
     if (route_join(c, r, bt->result) != 0) rc = -1;
-    return finish(rc);
+    return typed_finish(c, out, job, pr, sc, rc);
 }
 
 // The one way into a typed decode: every check of every entry, in this order, then the decode.  A call with one fault gets that fault's

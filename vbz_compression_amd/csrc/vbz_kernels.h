@@ -103,8 +103,8 @@ constexpr uint32_t WINDOW_READ_ROWS_MAX = 0x7FFFFFFFu;   // rows one read may ow
 // Signal trim (vbz_gpu_*_signal_trim_batch; the rule: include/vbz_gpu.h): behind the counting passes of a statistics call one more pass of
 // the svb decoder (OUT = SIG_TRIM) counts, window by window, the samples above thr = shift + f * scale in the first
 // t0 + nW * W <= min(M, T) positions of every read, and the scan of those counts writes the read's trim point to begin[].  The trim is an
-// argument of its own of the kernels that take it, beside their ReadBatch: no other kernel's arguments change.  begin: the caller's table,
-// entry norm.map ? norm.map[r] : r (POD5 reads of several rows: per READ); nullptr: no trim pass.
+// argument of its own of the kernels that take it, beside their ReadBatch -- no other kernel's arguments change -- and the host keeps it there
+// too (DecodeJob).  begin: the caller's table, entry norm.map ? norm.map[r] : r (POD5 reads of several rows: per READ); nullptr: no trim pass.
 constexpr uint32_t TRIM_REJECT_AT_END = 1;   // (= VBZ_GPU_TRIM_REJECT_AT_END)
 constexpr uint32_t TRIM_MAX_WINDOWS = NORM_WINDOWS * NORM_BINS;   // a read's window counts live in the counting passes' bins (NormLds::h, NormOut::slab)
 struct TrimOut
@@ -301,7 +301,7 @@ hipError_t launch_event_finish(const ReadBatch& b, const Pod5Reads& pr, const fl
 // (svb_kernels.hip: SegmentStore) scores every position of a read's signal with the two-window t-statistic, picks the boundaries and
 // leaves them as one bit per position in the read's map -- bytes [map_off[i], map_off[i] + ceil(T' / 8)) of `map`, every byte written by
 // one lane, no sample stored -- and the read's row count (boundaries + 1; 0 for an empty signal) in rows[i].  Like the trim, the call's
-// state is an argument of its own of the kernels that take it.  i: the read's entry of the call's tables (rmap: a routed read's; the
+// state is an argument of its own of the kernels that take it (the host: DecodeJob).  i: the read's entry of the call's tables (rmap: a routed read's; the
 // upper half of a split call gets the tables offset).  A read whose map does not end inside map_cap gets E_OOM.
 constexpr uint32_t SEGMENT_WINDOW_MAX = 32, SEGMENT_RADIUS_MAX = 32;
 struct SegmentOut
@@ -314,6 +314,8 @@ struct SegmentOut
     uint32_t w1 = 1, w2 = 0, r = 1;      // the two windows (w2 0: one detector) and the radius
     double k1 = 1.0, k2 = 1.0;           // float64(t) * float64(t) of the two thresholds (exact: 48 bits)
 };
+// One launch group of a decompress call on the host (no kernel sees it).  What cuts a call into groups cuts the job (vbz_api.hip: upper_half, route).
+struct DecodeJob { ReadBatch rb; TrimOut trim; SegmentOut seg; };   // trim.begin == nullptr / seg.map == nullptr: none
 // The tables of a segmentation call, per read of the call (POD5 reads of several rows: per READ): the maps' sizes and offsets, the sinks'
 // row counts, the counts of the reads that passed and their scan.
 struct SegmentScratch
