@@ -251,7 +251,7 @@ def test_whole_suite_on_the_large_read_path():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VBZ_HIP_SEGMENTED="1")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.join(root, "tests", "test_gpu_parity.py"),
-                        os.path.join(root, "tests", "test_gpu_fuzz_corpus.py"), "-k",
+                        os.path.join(root, "tests", "test_gpu_fuzz_corpus.py"), os.path.join(root, "tests", "test_gpu_svb_verdicts.py"), "-k",
                         "not bench_line and not fast5 and not h5repack and not hdf5 and not cpp_caller and not many_threads"],
                        capture_output=True, text=True, timeout=3000, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
@@ -344,7 +344,8 @@ def test_svb_suites_with_the_scan_launches():
     test_whole_suite_on_the_large_read_path runs)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VBZ_HIP_SEGMENTED="1", VBZ_HIP_SEG_SELF_MAX="0")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.join(root, "tests", "test_gpu_parity.py"), "-k",
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.join(root, "tests", "test_gpu_parity.py"),
+                        os.path.join(root, "tests", "test_gpu_svb_verdicts.py"), "-k",
                         "svb or c_abi_known_answers or c_abi_error or batch_ragged or unaligned_arena or descriptor_tables"],
                        capture_output=True, text=True, timeout=3000, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
@@ -357,7 +358,8 @@ def test_whole_suite_on_the_one_wavefront_path():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, VBZ_HIP_SEGMENTED="0")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", os.path.join(root, "tests", "test_gpu_parity.py"),
-                        os.path.join(root, "tests", "test_gpu_fuzz_corpus.py"), os.path.join(root, "tests", "test_gpu_repeats.py"), "-k",
+                        os.path.join(root, "tests", "test_gpu_fuzz_corpus.py"), os.path.join(root, "tests", "test_gpu_repeats.py"),
+                        os.path.join(root, "tests", "test_gpu_svb_verdicts.py"), "-k",
                         "not bench_line and not fast5 and not h5repack and not hdf5 and not cpp_caller and not many_threads"],
                        capture_output=True, text=True, timeout=3000, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]

@@ -38,6 +38,7 @@ PAD = -1.0
 def timed(c, fns, reps, warm=3):
     """median milliseconds of every fn, the fns alternating call by call"""
     ms = {k: [] for k in fns}
+    c.stream.wait_stream(torch.cuda.current_stream(c.device))   # (the caller's tensors -- the unfused route's index -- were made on that stream)
     with torch.cuda.stream(c.stream):
         for _ in range(warm):
             for f in fns.values():

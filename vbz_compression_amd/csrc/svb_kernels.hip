@@ -38,6 +38,41 @@ __device__ __forceinline__ uint32_t svb_encode_check(uint32_t size, uint32_t cap
     return 0;
 }
 
+// Read r of an encode launch, opened: the gate (read_gate), then the check above.  true: code it -- *e holds its samples, its slot and its
+// sizes; false: *verdict is the read's result (GATE_SKIP: none to write).  The three launch shapes (one workgroup per read, segments with
+// self-summed prefixes, segments with scan launches) all open a read here.
+struct SvbEnc
+{
+    const uint8_t* in;
+    uint8_t* out;   // the read's slot (the sized header's place, when there is one)
+    uint32_t size, n, keyLen;
+};
+template <int ELEM, bool I16ZZ>
+__device__ __forceinline__ bool svb_enc_open(const ReadBatch& b, uint32_t r, uint32_t hdr, uint32_t strict_cap, SvbEnc* e, uint32_t* verdict)
+{
+    *verdict = read_gate(b, r, false);
+    if (*verdict) return false;
+    e->size = b.src_size[r];
+    *verdict = svb_encode_check<ELEM, I16ZZ>(e->size, b.dst_cap[r], hdr, strict_cap);
+    if (*verdict) return false;
+    e->n = e->size / ELEM;
+    e->keyLen = (e->n + 3u) >> 2;
+    e->in = b.src + b.src_off[r];
+    e->out = b.dst + b.dst_off[r];
+    return true;
+}
+
+// The result of a read of the large-read path, by one thread, from what svb_enc_open said of it (open, e, verdict) and the data bytes its
+// segments counted in all: whether one is to be written, and *res.  A read that is coded also gets its sized header here.
+__device__ __forceinline__ bool svb_seg_enc_result(bool open, const SvbEnc& e, uint32_t verdict, uint32_t hdr, uint64_t total, uint32_t* res)
+{
+    *res = open ? hdr + e.keyLen + (uint32_t)total : verdict;
+    if (open && hdr) {
+        for (int j = 0; j < 4; ++j) e.out[j] = (uint8_t)(e.size >> (8 * j));
+    }
+    return open || verdict != GATE_SKIP;
+}
+
 // ---- probe for a long repeat distance in the data bytes (consumed by zstd_encode.hip's long-repeat coder) -------------
 // libzstd's match finder (on at every level of the reference: vbz/vbz.cpp:194-207) turns signal that cycles a template --
 // the reference's own perf generator does, vbz/perf/test_data_generator.h:61-67 -- into a few long matches: the data bytes
@@ -598,22 +633,14 @@ __global__ __launch_bounds__(WG, VBZ_SVBENC_WAVES) void svb_encode_kernel(ReadBa
     const int tid = threadIdx.x;
     if (PROBE && tid == 0) period_hint[r] = 0;
     if (CNT && tid == 0) pre[r].hist_mode = 0;   // whatever becomes of the read, the entropy stage finds a verdict of this launch in its plan
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
-        return;
-    }
-    const uint32_t size = b.src_size[r];
-    const uint32_t err = svb_encode_check<ELEM, I16ZZ>(size, b.dst_cap[r], hdr, strict_cap);
-    if (err) {
-        if (tid == 0) b.result[r] = err;
-        return;
-    }
-    const uint32_t n = size / ELEM;
-    const uint32_t keyLen = (n + 3u) >> 2;
-    const uint8_t* in = b.src + b.src_off[r];
-    uint8_t* out = b.dst + b.dst_off[r];
+    SvbEnc e;
+    uint32_t verdict;
+    if (!svb_enc_open<ELEM, I16ZZ>(b, r, hdr, strict_cap, &e, &verdict)) return read_closed(b, r, verdict);
+    const uint32_t n = e.n, keyLen = e.keyLen;
+    const uint8_t* in = e.in;
+    uint8_t* out = e.out;
     if (hdr) {
-        if (tid < 4) out[tid] = (uint8_t)(size >> (8 * tid));
+        if (tid < 4) out[tid] = (uint8_t)(e.size >> (8 * tid));
         out += 4;
     }
     CntLds* const CL = reinterpret_cast<CntLds*>(&cntl[0]);
@@ -708,38 +735,24 @@ __global__ __launch_bounds__(WG) void svb_seg_encode_kernel(ReadBatch b, uint32_
     if (!seg_locate(seg_first, b.n_reads, blockIdx.x, r, k)) return;
     const int tid = threadIdx.x;
     if (COUNT_ONLY && tid == 0) seg_bytes[blockIdx.x] = 0;
+    SvbEnc e;
+    uint32_t verdict;
+    const bool open = svb_enc_open<ELEM, I16ZZ>(b, r, hdr, strict_cap, &e, &verdict);
     uint64_t self_off = 0;
     if (SELF && !COUNT_ONLY) {
         // the data offset of this segment, and (first workgroup of the read) the read's result: svb_seg_encode_scan_kernel's work
         uint64_t total;
         seg_sums(seg_bytes, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_off, total);
-        if (k == 0 && tid == 0 && !(b.gate && b.gate[r] == GATE_SKIP)) {
-            uint32_t res;
-            if (b.gate && b.gate[r] >= E_FIRST) res = b.gate[r];
-            else {
-                const uint32_t size0 = b.src_size[r];
-                res = svb_encode_check<ELEM, I16ZZ>(size0, b.dst_cap[r], hdr, strict_cap);
-                if (!res) {
-                    res = hdr + ((size0 / ELEM + 3u) >> 2) + (uint32_t)total;
-                    if (hdr) {
-                        uint8_t* o4 = b.dst + b.dst_off[r];
-                        for (int j = 0; j < 4; ++j) o4[j] = (uint8_t)(size0 >> (8 * j));
-                    }
-                }
-            }
-            b.result[r] = res;
-        }
+        uint32_t res;
+        if (k == 0 && tid == 0 && svb_seg_enc_result(open, e, verdict, hdr, total, &res)) b.result[r] = res;
     }
-    if (b.gate && b.gate[r] >= GATE_SKIP) return;
-    const uint32_t size = b.src_size[r];
-    if (svb_encode_check<ELEM, I16ZZ>(size, b.dst_cap[r], hdr, strict_cap)) return;
-    const uint32_t n = size / ELEM;
-    const uint32_t keyLen = (n + 3u) >> 2;
+    if (!open) return;   // (the scan, or the read's first workgroup, writes the verdict)
+    const uint32_t n = e.n, keyLen = e.keyLen;
     const uint32_t first = k * (uint32_t)SEG;
     const uint32_t end = n - first > (uint32_t)SEG ? first + SEG : n;
     if (first >= n) return;  // the single (empty) segment of an empty read
-    const uint8_t* in = b.src + b.src_off[r];
-    uint8_t* out = b.dst + b.dst_off[r] + hdr;
+    const uint8_t* in = e.in;
+    uint8_t* out = e.out + hdr;
     if (COUNT_ONLY) {
         const uint64_t bytes = svb_encode_range<ELEM, ZZ, I16ZZ, true>(in, first, end, nullptr, nullptr, stage, wsum);
         if (tid == 0) seg_bytes[blockIdx.x] = (uint32_t)bytes;
@@ -766,23 +779,10 @@ __global__ __launch_bounds__(WG) void svb_seg_encode_scan_kernel(ReadBatch b, ui
         if (i < s1) seg_off[i] = carry + ex;
         carry += tot;
     }
-    if (tid == 0 && !(b.gate && b.gate[r] == GATE_SKIP)) {
-        uint32_t res;
-        if (b.gate && b.gate[r] >= E_FIRST) res = b.gate[r];
-        else {
-            const uint32_t size = b.src_size[r];
-            res = svb_encode_check<ELEM, I16ZZ>(size, b.dst_cap[r], hdr, strict_cap);
-            if (!res) {
-                const uint32_t n = size / ELEM;
-                res = hdr + ((n + 3u) >> 2) + (uint32_t)carry;
-                if (hdr) {
-                    uint8_t* out = b.dst + b.dst_off[r];
-                    for (int j = 0; j < 4; ++j) out[j] = (uint8_t)(size >> (8 * j));
-                }
-            }
-        }
-        b.result[r] = res;
-    }
+    SvbEnc e;
+    uint32_t verdict, res;
+    const bool open = svb_enc_open<ELEM, I16ZZ>(b, r, hdr, strict_cap, &e, &verdict);
+    if (tid == 0 && svb_seg_enc_result(open, e, verdict, hdr, carry, &res)) b.result[r] = res;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -970,6 +970,59 @@ __device__ __forceinline__ bool svb_decode_check(uint32_t in_size, uint32_t out_
     return false;
 }
 
+// Read r of a decode launch, opened: the gate and the previous stage's verdict (read_gate), then the check above.  true: walk the read --
+// *rd holds its stream and its sizes; false: *verdict is the read's result (GATE_SKIP: none to write).  svb16_row_open's contract, and
+// where every sink of this decoder starts from, on all three launch shapes (one workgroup per read, segments with self-summed prefixes,
+// segments with scan launches).
+struct SvbRead
+{
+    const uint8_t* in;
+    uint32_t in_size, count, keyLen, dataBytes;
+};
+template <int ELEM, bool I16ZZ>
+__device__ __forceinline__ bool svb_read_open(const ReadBatch& b, uint32_t r, SvbRead* rd, uint32_t* verdict)
+{
+    *verdict = read_gate(b, r, true);
+    if (*verdict) return false;
+    rd->in_size = b.src_size[r];
+    const uint32_t out_size = b.dst_cap[r];   // exact decoded byte count
+    if (svb_decode_check<ELEM, I16ZZ>(rd->in_size, out_size, *verdict)) return false;
+    rd->count = out_size / ELEM;
+    rd->keyLen = (rd->count + 3u) >> 2;
+    rd->dataBytes = rd->in_size - rd->keyLen;
+    rd->in = b.src + b.src_off[r];
+    return true;
+}
+
+// The result of a read of the large-read path, from what svb_read_open said of it (open, rd, verdict) and the data bytes its segments'
+// control bytes announced in all (the stream is good iff that total equals the data bytes present): whether one is to be written, and
+// *res.  bytes_per_value: the store's.
+__device__ __forceinline__ bool svb_seg_read_result(bool open, const SvbRead& rd, uint32_t verdict, uint64_t announced, uint32_t bytes_per_value,
+                                                    uint32_t* res)
+{
+    *res = !open ? verdict : (announced == rd.dataBytes ? rd.count * bytes_per_value : E_STREAM);
+    return open || verdict != GATE_SKIP;
+}
+
+// The svb decoder's LDS, declared once per kernel (`const SvbDecLds<..> lds;`).  PAIRS: the kernel runs I16DecPairs (the two stage buffers
+// and the sums of that loop; the tile loop's 8240 bytes fit), else one tile's worst case.  (Two variables, as norm_lds() has one: a
+// kernel pays for the ones it touches.)
+template <int ELEM, bool PAIRS>
+struct SvbDecLds
+{
+    static constexpr int STAGE = PAIRS ? 2 * (int)I16DecPairs::BUF : WG * Vpl<ELEM>::value * 4 + 48;
+    static_assert(STAGE >= WG * Vpl<ELEM>::value * 4 + 48, "the tile loop's stage");
+    uint8_t* stage;
+    uint32_t* wsum;
+    __device__ __forceinline__ SvbDecLds()
+    {
+        __shared__ __attribute__((aligned(16))) uint8_t s[STAGE];
+        __shared__ __attribute__((aligned(16))) uint32_t w[PAIRS ? (int)I16DecPairs::WS_WORDS : 4];
+        stage = s;
+        wsum = w;
+    }
+};
+
 // MODE 0: decode values [first, end) of a stream of `count` values whose data bytes start at data[pos] and whose delta
 //         chain stands at `run`; store them.  MODE 1: only add up the data bytes the control bytes announce.
 //         MODE 2: decode without storing (the total of the deltas is wanted).  pos / run are updated; returns false when
@@ -1087,6 +1140,8 @@ __device__ __forceinline__ bool svb_decode_range(const uint8_t* in, const uint8_
 #ifndef VBZ_SVBDEC_WAVES
 #define VBZ_SVBDEC_WAVES 1
 #endif
+// This kernel keeps its prologue and its LDS pair as its own text (svb_read_open's order, spelled out): opened through the shared
+// statement, its float32 instantiation took 72 registers for 82 and measured 3 % slower, and the counting and window ones moved too.
 template <int ELEM, bool ZZ, bool I16ZZ, int OUT = SIG_NONE>
 __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_decode_kernel(ReadBatch b)
 {
@@ -1139,6 +1194,7 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
     static_assert(OUT == SIG_NONE || MODE == 0, "the typed stores are the storing pass's");
     const uint32_t* seg_run = seg_run_io;
     constexpr int SEG = WG * Vpl<ELEM>::value * SEG_TILES;
+    // (not SvbDecLds: arrays of the kernel's own are dropped where a MODE stages nothing, and the LDS of those instantiations stays what it was)
     constexpr int STAGE = MODE == 1 ? 16 : ((I16ZZ && MODE == 0) ? 2 * (int)I16DecPairs::BUF : WG * Vpl<ELEM>::value * 4 + 48);
     __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
     __shared__ __attribute__((aligned(16))) uint32_t wsum[(I16ZZ && MODE == 0) ? (int)I16DecPairs::WS_WORDS : 4];
@@ -1147,6 +1203,9 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
     if (!seg_locate(seg_first, b.n_reads, blockIdx.x, r, k)) return;
     const int tid = threadIdx.x;
     if (MODE != 0 && tid == 0) (SELF && MODE == 2 ? seg_run_io : seg_val)[blockIdx.x] = 0;
+    SvbRead rd;
+    uint32_t verdict;
+    const bool open = svb_read_open<ELEM, I16ZZ>(b, r, &rd, &verdict);
     uint64_t self_pos = 0, self_total = 0, self_run = 0;
     if (SELF && MODE != 1) {
         seg_sums(seg_val, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_pos, self_total);
@@ -1154,40 +1213,23 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_kernel(ReadBatch b, const u
             uint64_t dummy;
             seg_sums(seg_run, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_run, dummy);
         }
-        if (MODE == 0 && k == 0 && tid == 0 && !(b.gate && b.gate[r] == GATE_SKIP)) {   // svb_seg_decode_scan_kernel<.., VERDICT>'s first thread
-            uint32_t res0;
-            if (b.gate && b.gate[r] >= E_FIRST) res0 = b.gate[r];
-            else if (b.src_size[r] >= E_FIRST) res0 = b.src_size[r];
-            else if (!svb_decode_check<ELEM, I16ZZ>(b.src_size[r], b.dst_cap[r], res0)) {
-                const uint32_t count0 = b.dst_cap[r] / ELEM;
-                const uint32_t dataBytes0 = b.src_size[r] - ((count0 + 3u) >> 2);
-                res0 = self_total == dataBytes0 ? count0 * DecStore<ELEM, OUT>::BYTES : E_STREAM;
-            }
-            b.result[r] = res0;
-        }
+        uint32_t res0;   // (svb_seg_decode_scan_kernel<.., VERDICT>'s first thread)
+        if (MODE == 0 && k == 0 && tid == 0 && svb_seg_read_result(open, rd, verdict, self_total, DecStore<ELEM, OUT>::BYTES, &res0)) b.result[r] = res0;
     }
-    if (b.gate && b.gate[r] >= GATE_SKIP) return;
-    const uint32_t in_size = b.src_size[r];
-    if (in_size >= E_FIRST) return;
-    const uint32_t out_size = b.dst_cap[r];
-    uint32_t res;
-    if (svb_decode_check<ELEM, I16ZZ>(in_size, out_size, res)) return;
+    if (!open) return;   // (the scan, or the read's first MODE 0 workgroup, writes the verdict)
     if (SELF) {
-        if (MODE != 1 && self_total != (uint64_t)(in_size - ((out_size / ELEM + 3u) >> 2))) return;   // the stream is malformed
+        if (MODE != 1 && self_total != (uint64_t)rd.dataBytes) return;   // the stream is malformed
     } else if (MODE != 1 && b.result[r] >= E_FIRST) return;  // the scan found the stream malformed
     if ((OUT & SIG_COUNT) && b.sig.norm.st[r].phase == NORM_DONE) return;
-    const uint32_t count = out_size / ELEM;
-    const uint32_t keyLen = (count + 3u) >> 2;
+    const uint32_t count = rd.count;
     const uint32_t first = k * (uint32_t)SEG;
     if (first >= count) return;
     const uint32_t end = count - first > (uint32_t)SEG ? first + SEG : count;
-    const uint8_t* in = b.src + b.src_off[r];
-    const uint32_t dataBytes = in_size - keyLen;
     uint64_t pos = MODE == 1 ? 0 : (SELF ? self_pos : seg_pos[blockIdx.x]);
     uint32_t run = (MODE == 0 && ZZ) ? (SELF ? (uint32_t)self_run : seg_run[blockIdx.x]) : 0u;
     const uint64_t pos0 = pos;
     const DecStore<ELEM, OUT> st = dec_store<ELEM, OUT>(b.dst, b.dst_off, OUT == SIG_NONE ? nullptr : &b, r, count);
-    (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE>(in, in + keyLen, dataBytes, count, first, end, pos, run, st, stage, wsum);
+    (void)svb_decode_range<ELEM, ZZ, I16ZZ, MODE>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, first, end, pos, run, st, stage, wsum);
     if (MODE == 1 && tid == 0) seg_val[blockIdx.x] = (uint32_t)(pos - pos0);
     if (MODE == 2 && tid == 0) (SELF ? seg_run_io : seg_val)[blockIdx.x] = run;
 }
@@ -1214,17 +1256,10 @@ __global__ __launch_bounds__(WG) void svb_seg_decode_scan_kernel(ReadBatch b, co
         }
         carry += tot;
     }
-    if (VERDICT && tid == 0 && !(b.gate && b.gate[r] == GATE_SKIP)) {
-        uint32_t res;
-        if (b.gate && b.gate[r] >= E_FIRST) res = b.gate[r];
-        else if (b.src_size[r] >= E_FIRST) res = b.src_size[r];
-        else if (!svb_decode_check<ELEM, I16ZZ>(b.src_size[r], b.dst_cap[r], res)) {
-            const uint32_t count = b.dst_cap[r] / ELEM;
-            const uint32_t dataBytes = b.src_size[r] - ((count + 3u) >> 2);
-            res = carry == dataBytes ? count * RES : E_STREAM;
-        }
-        b.result[r] = res;
-    }
+    SvbRead rd;
+    uint32_t verdict, res;
+    const bool open = svb_read_open<ELEM, I16ZZ>(b, r, &rd, &verdict);
+    if (VERDICT && tid == 0 && svb_seg_read_result(open, rd, verdict, carry, RES, &res)) b.result[r] = res;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1244,10 +1279,7 @@ __global__ __launch_bounds__(WG) void svb_half_encode_kernel(ReadBatch b, uint32
 
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
-        return;
-    }
+    if (const uint32_t verdict = read_gate(b, r, false)) return read_closed(b, r, verdict);
     const uint32_t n = b.src_size[r];  // one byte per value
     const uint32_t cap = b.dst_cap[r];
     const uint32_t keyLen = (n + 3u) >> 2;
@@ -1348,15 +1380,8 @@ __global__ __launch_bounds__(WG) void svb_half_decode_kernel(ReadBatch b)
 
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
-        return;
-    }
+    if (const uint32_t verdict = read_gate(b, r, true)) return read_closed(b, r, verdict);
     const uint32_t in_size = b.src_size[r];
-    if (in_size >= E_FIRST) {
-        if (tid == 0) b.result[r] = in_size;
-        return;
-    }
     const uint32_t count = b.dst_cap[r];  // exact decoded byte count = value count
     // half validate_stream (vbz/v1/vbz_streamvbyte_impl.h)
     if (in_size == 0 || count == 0) {
@@ -1456,6 +1481,20 @@ __global__ __launch_bounds__(WG) void svb_half_decode_kernel(ReadBatch b)
 // DESIGN.md 4.13).
 // ------------------------------------------------------------------------------------------------
 constexpr int SVB16_TILE = WG * 8;
+// the svb16 decoder's LDS, declared once per kernel (`const Svb16Lds lds;`): one tile's worst case of data bytes behind the bytes short of
+// a line, and the scan's sums
+struct Svb16Lds
+{
+    uint8_t* stage;
+    uint32_t* wsum;
+    __device__ __forceinline__ Svb16Lds()
+    {
+        __shared__ __attribute__((aligned(16))) uint8_t s[SVB16_TILE * 2 + 48];
+        __shared__ __attribute__((aligned(16))) uint32_t w[4];
+        stage = s;
+        wsum = w;
+    }
+};
 
 __global__ __launch_bounds__(WG) void svb16_encode_kernel(ReadBatch b, uint32_t* period_hint)
 {
@@ -1465,10 +1504,7 @@ __global__ __launch_bounds__(WG) void svb16_encode_kernel(ReadBatch b, uint32_t*
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63;
     if (period_hint && tid == 0) period_hint[r] = 0;   // (the svb16 stream is not probed: the entropy stage's matcher stays off)
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
-        return;
-    }
+    if (const uint32_t verdict = read_gate(b, r, false)) return read_closed(b, r, verdict);
     const uint32_t size = b.src_size[r];
     if (size & 1u) {
         if (tid == 0) b.result[r] = E_INPUT_SIZE;
@@ -1610,13 +1646,9 @@ __device__ __forceinline__ bool svb16_decode_row(const uint8_t* in, uint32_t in_
 // none to write)
 __device__ __forceinline__ bool svb16_row_open(const ReadBatch& b, uint32_t r, uint32_t* in_size, uint32_t* count, uint32_t* verdict)
 {
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        *verdict = b.gate[r];
-        return false;
-    }
+    *verdict = read_gate(b, r, true);
+    if (*verdict) return false;
     *in_size = b.src_size[r];
-    *verdict = *in_size;
-    if (*in_size >= E_FIRST) return false;   // the previous stage failed for this row
     const uint32_t out_size = b.dst_cap[r];
     *verdict = E_DESTINATION_SIZE;
     if (out_size & 1u) return false;
@@ -1631,16 +1663,14 @@ __device__ __forceinline__ bool svb16_row_open(const ReadBatch& b, uint32_t r, u
 template <int OUT>
 __global__ __launch_bounds__(WG) void svb16_decode_kernel(ReadBatch b)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+    const Svb16Lds lds;
+    uint8_t* const stage = lds.stage;   // (the tile loop below keeps its own text)
+    uint32_t* const wsum = lds.wsum;
 
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
     uint32_t in_size = 0, count = 0, verdict;
-    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {   // (every pass gives the verdict)
-        if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
-        return;
-    }
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) return read_closed(b, r, verdict);   // (every pass gives the verdict)
     if ((OUT & SIG_COUNT) && b.sig.norm.st[r].phase == NORM_DONE) return;   // (a later counting pass: the read is finished)
     const uint32_t K = (count + 7u) >> 3;
     const uint8_t* in = b.src + b.src_off[r];
@@ -1724,9 +1754,9 @@ template <bool SVB16>
 __device__ __forceinline__ void norm_init_read(const ReadBatch& b, uint32_t zigzag)
 {
     const uint32_t r = blockIdx.x * WG + threadIdx.x;
-    if (r >= b.n_reads || (b.gate && b.gate[r] >= GATE_SKIP)) return;
+    if (r >= b.n_reads || read_gate(b, r, true)) return;
     const uint32_t in_size = b.src_size[r], out_size = b.dst_cap[r];
-    if (in_size >= E_FIRST || (out_size & 1u)) return;
+    if (out_size & 1u) return;
     const uint32_t T = out_size >> 1, keyLen = SVB16 ? (T + 7u) >> 3 : (T + 3u) >> 2;
     NormRead* sp = b.sig.norm.st + r;
     if (T == 0) {
@@ -1751,9 +1781,9 @@ template <bool RANGED>
 __device__ __forceinline__ void norm_select_read(const ReadBatch& b)
 {
     const uint32_t r = blockIdx.x;
-    if (b.gate && b.gate[r] >= GATE_SKIP) return;
-    const uint32_t in_size = b.src_size[r], out_size = b.dst_cap[r];
-    if (in_size >= E_FIRST || (out_size & 1u) || out_size == 0 || b.sig.norm.st[r].phase == NORM_DONE) return;
+    if (read_gate(b, r, true)) return;
+    const uint32_t out_size = b.dst_cap[r];
+    if ((out_size & 1u) || out_size == 0 || b.sig.norm.st[r].phase == NORM_DONE) return;
     uint32_t T = out_size >> 1;
     if (RANGED) {   // the ranks are the range's
         uint32_t rb, re;
@@ -1962,7 +1992,7 @@ __device__ __forceinline__ bool event_read_open(const ReadBatch& b, const Pod5Re
         }
         return true;
     }
-    if (b.gate[i] >= GATE_SKIP) return false;
+    if (read_gate(b, i, false)) return false;
     sample_range(b.sig, i, b.dst_cap[i] >> 1, rb, re);
     return true;
 }
@@ -2058,7 +2088,7 @@ __global__ __launch_bounds__(WG) void window_pad_kernel(ReadBatch b, Pod5Reads p
                 re = g.y;
             }
         } else {
-            if (b.gate[i] >= GATE_SKIP) continue;
+            if (read_gate(b, i, false)) continue;
             sample_range(b.sig, i, b.dst_cap[i] >> 1, &rb, &re);
         }
         const uint64_t c = b.sig.wfirst[i] + (j - scan[i]);
@@ -2118,21 +2148,17 @@ __device__ __forceinline__ auto row_store(const ReadBatch& b, const Pod5Reads& p
 template <int OUT>
 __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5Reads pr)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+    const Svb16Lds lds;
 
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
     const Pod5Row rw = pr.rows[r];
     if ((OUT & SIG_CHUNK) && !(OUT & SIG_WINDOW) && (rw.flags & POD5_ROW_PAD)) row_chunk_store<OUT>(b, pr, rw, 0u).finish();
     uint32_t in_size = 0, count = 0, verdict;
-    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-        if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
-        return;
-    }
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) return read_closed(b, r, verdict);
     const uint8_t* in = b.src + b.src_off[r];
     const auto st = row_store<OUT>(b, pr, rw, r, count);
-    const bool good = svb16_decode_row(in, in_size, count, st, stage, wsum);
+    const bool good = svb16_decode_row(in, in_size, count, st, lds.stage, lds.wsum);
     if (tid == 0) b.result[r] = good ? count * st.BYTES : E_STREAM;
 }
 
@@ -2142,8 +2168,7 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
 template <int OUT>
 __device__ __forceinline__ void svb16_count_reads(const ReadBatch& b, const Pod5Reads& pr, uint32_t verdicts)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+    const Svb16Lds lds;
 
     if (*pr.bad) return;
     const uint32_t k = blockIdx.x;
@@ -2162,11 +2187,11 @@ __device__ __forceinline__ void svb16_count_reads(const ReadBatch& b, const Pod5
     for (uint32_t r = first; r < end; ++r) {
         uint32_t in_size = 0, count = 0, verdict;
         if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-            if (verdicts && tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
+            if (verdicts) read_closed(b, r, verdict);
             continue;
         }
         st.begin_row(pr.rows[r].s0);   // (put() gets positions in the row)
-        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, stage, wsum);
+        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
         if (verdicts && tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
     }
     st.done();
@@ -2188,9 +2213,9 @@ __global__ __launch_bounds__(WG) void svb16_count_reads_range_kernel(ReadBatch b
 // written), it has an error verdict (begin 0) or no window (begin min(t0, T)); else *k is its state.
 __device__ __forceinline__ bool trim_read_open(const ReadBatch& b, const TrimOut& tr, uint32_t r, TrimK* k)
 {
-    const uint32_t g = b.gate ? b.gate[r] : 0u;
+    const uint32_t g = read_gate(b, r, true);
     if (g == GATE_SKIP) return false;
-    if (g >= E_FIRST || b.result[r] >= E_FIRST) {
+    if (g || b.result[r] >= E_FIRST) {
         if (threadIdx.x == 0) tr.begin[b.sig.norm.map ? b.sig.norm.map[r] : r] = 0;
         return false;
     }
@@ -2206,9 +2231,7 @@ __device__ __forceinline__ bool trim_read_open(const ReadBatch& b, const TrimOut
 template <bool ZZ, bool I16ZZ>
 __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_trim_kernel(ReadBatch b, TrimOut tr)
 {
-    constexpr int STAGE = I16ZZ ? 2 * (int)I16DecPairs::BUF : WG * Vpl<2>::value * 4 + 48;
-    __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[I16ZZ ? (int)I16DecPairs::WS_WORDS : 4];
+    const SvbDecLds<2, I16ZZ> lds;
 
     const uint32_t r = blockIdx.x;
     TrimK k;
@@ -2218,7 +2241,7 @@ __global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_trim_kernel(ReadBatc
     uint64_t pos = 0;
     uint32_t run = 0;
     const TrimStore st(k);
-    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, in_size - keyLen, count, 0, k.end, pos, run, st, stage, wsum);
+    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, in_size - keyLen, count, 0, k.end, pos, run, st, lds.stage, lds.wsum);
 }
 
 // The large-read path: svb_seg_decode_kernel's MODE 0 at the positions its passes left (seg_val / seg_pos / seg_run as that kernel reads
@@ -2228,14 +2251,14 @@ __global__ __launch_bounds__(WG) void svb_seg_trim_kernel(ReadBatch b, const uin
                                                           const uint32_t* seg_run, TrimOut tr)
 {
     constexpr uint32_t SEG = WG * Vpl<2>::value * SEG_TILES;
-    constexpr int STAGE = I16ZZ ? 2 * (int)I16DecPairs::BUF : WG * Vpl<2>::value * 4 + 48;
-    __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[I16ZZ ? (int)I16DecPairs::WS_WORDS : 4];
+    const SvbDecLds<2, I16ZZ> lds;
     __shared__ uint64_t sums_s[8];
     uint32_t r, sg;
     if (!seg_locate(seg_first, b.n_reads, blockIdx.x, r, sg)) return;
-    if ((b.gate && b.gate[r] >= GATE_SKIP) || b.result[r] >= E_FIRST) return;   // (trim_select_kernel writes the read's 0)
-    const uint32_t count = b.dst_cap[r] >> 1, first = sg * SEG;
+    SvbRead rd;
+    uint32_t verdict;
+    if (!svb_read_open<2, I16ZZ>(b, r, &rd, &verdict) || b.result[r] >= E_FIRST) return;   // (trim_select_kernel writes the read's 0)
+    const uint32_t count = rd.count, first = sg * SEG;
     TrimK k = trim_state(b, tr, r, count);
     if (first >= k.end) return;
     k.slab = b.sig.norm.slab + (size_t)r * NORM_SLAB;
@@ -2250,10 +2273,9 @@ __global__ __launch_bounds__(WG) void svb_seg_trim_kernel(ReadBatch b, const uin
         pos = seg_pos[blockIdx.x];
         run = ZZ ? seg_run[blockIdx.x] : 0u;
     }
-    const uint32_t end = k.end - first > SEG ? first + SEG : k.end, keyLen = (count + 3u) >> 2;
-    const uint8_t* in = b.src + b.src_off[r];
+    const uint32_t end = k.end - first > SEG ? first + SEG : k.end;
     const TrimStore st(k);
-    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, b.src_size[r] - keyLen, count, first, end, pos, run, st, stage, wsum);
+    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, first, end, pos, run, st, lds.stage, lds.wsum);
 }
 
 // one workgroup per read of the large-read path: the words the segments added to the read's slab (zeroed again) -> the scan
@@ -2275,14 +2297,13 @@ __global__ __launch_bounds__(WG) void trim_select_kernel(ReadBatch b, TrimOut tr
 // a POD5 row as a read of its own
 __global__ __launch_bounds__(WG) void svb16_trim_kernel(ReadBatch b, TrimOut tr)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+    const Svb16Lds lds;
 
     const uint32_t r = blockIdx.x;
     TrimK k;
     if (!trim_read_open(b, tr, r, &k)) return;
     const TrimStore st(k);
-    (void)svb16_decode_row<TrimStore, true>(b.src + b.src_off[r], b.src_size[r], k.T, st, stage, wsum, k.end);
+    (void)svb16_decode_row<TrimStore, true>(b.src + b.src_off[r], b.src_size[r], k.T, st, lds.stage, lds.wsum, k.end);
     st.done();
 }
 
@@ -2290,8 +2311,7 @@ __global__ __launch_bounds__(WG) void svb16_trim_kernel(ReadBatch b, TrimOut tr)
 // sample.  A read with a failing row gets 0; a bad first_row leaves begin alone.
 __global__ __launch_bounds__(WG) void svb16_trim_reads_kernel(ReadBatch b, Pod5Reads pr, TrimOut tr)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+    const Svb16Lds lds;
 
     if (*pr.bad) return;
     const uint32_t q = blockIdx.x;
@@ -2314,7 +2334,7 @@ __global__ __launch_bounds__(WG) void svb16_trim_reads_kernel(ReadBatch b, Pod5R
         uint32_t in_size = 0, count = 0, verdict;
         if (!svb16_row_open(b, r, &in_size, &count, &verdict)) continue;   // (an empty row)
         st.begin_row(s0);   // (put() gets positions in the row)
-        (void)svb16_decode_row<TrimStore, true>(b.src + b.src_off[r], in_size, count, st, stage, wsum, k.end - s0);
+        (void)svb16_decode_row<TrimStore, true>(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum, k.end - s0);
     }
     st.done();
 }
@@ -2334,56 +2354,36 @@ __device__ __forceinline__ bool segment_fits(const SegmentOut& so, uint32_t i, u
 template <bool ZZ, bool I16ZZ>
 __global__ __launch_bounds__(WG) void svb_segment_kernel(ReadBatch b, SegmentOut so)
 {
-    constexpr int STAGE = I16ZZ ? 2 * (int)I16DecPairs::BUF : WG * Vpl<2>::value * 4 + 48;
-    __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[I16ZZ ? (int)I16DecPairs::WS_WORDS : 4];
+    const SvbDecLds<2, I16ZZ> lds;
 
     const uint32_t r = blockIdx.x;
     const int tid = threadIdx.x;
-    if (b.gate && b.gate[r] >= GATE_SKIP) {
-        if (tid == 0 && b.gate[r] != GATE_SKIP) b.result[r] = b.gate[r];
-        return;
-    }
-    const uint32_t in_size = b.src_size[r];
-    if (in_size >= E_FIRST) {  // the previous stage failed for this read
-        if (tid == 0) b.result[r] = in_size;
-        return;
-    }
-    const uint32_t out_size = b.dst_cap[r];
-    uint32_t res;
-    if (svb_decode_check<2, I16ZZ>(in_size, out_size, res)) {
-        if (tid == 0) b.result[r] = res;
-        return;
-    }
-    const uint32_t count = out_size / 2u, keyLen = (count + 3u) >> 2;
+    SvbRead rd;
+    uint32_t verdict;
+    if (!svb_read_open<2, I16ZZ>(b, r, &rd, &verdict)) return read_closed(b, r, verdict);
+    const uint32_t count = rd.count;
     const uint32_t i = segment_entry(so, r);
     if (!segment_fits(so, i, count)) {
         if (tid == 0) b.result[r] = E_OOM;
         return;
     }
-    const uint8_t* in = b.src + b.src_off[r];
-    const uint32_t dataBytes = in_size - keyLen;
     uint32_t rb, re;
     sample_range(b.sig, r, count, &rb, &re);
     uint64_t pos = 0;
     uint32_t run = 0;
     const SegmentStore st(so, i, rb, re - rb, b.sig.bias);
-    const bool good = svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, dataBytes, count, 0, count, pos, run, st, stage, wsum);
-    if (tid == 0) b.result[r] = (!good || pos != dataBytes) ? E_STREAM : count * 2u;
+    const bool good = svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, 0, count, pos, run, st, lds.stage, lds.wsum);
+    if (tid == 0) b.result[r] = (!good || pos != rd.dataBytes) ? E_STREAM : count * 2u;
 }
 
 // a POD5 row as a read of its own
 __global__ __launch_bounds__(WG) void svb16_segment_kernel(ReadBatch b, SegmentOut so)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+    const Svb16Lds lds;
 
     const uint32_t r = blockIdx.x;
     uint32_t in_size = 0, count = 0, verdict;
-    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-        if (threadIdx.x == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
-        return;
-    }
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) return read_closed(b, r, verdict);
     const uint32_t i = segment_entry(so, r);
     if (!segment_fits(so, i, count)) {
         if (threadIdx.x == 0) b.result[r] = E_OOM;
@@ -2392,7 +2392,7 @@ __global__ __launch_bounds__(WG) void svb16_segment_kernel(ReadBatch b, SegmentO
     uint32_t rb, re;
     sample_range(b.sig, r, count, &rb, &re);
     const SegmentStore st(so, i, rb, re - rb, b.sig.bias);
-    const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, stage, wsum);
+    const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
     st.done();
     if (threadIdx.x == 0) b.result[r] = good ? count * 2u : E_STREAM;
 }
@@ -2401,8 +2401,7 @@ __global__ __launch_bounds__(WG) void svb16_segment_kernel(ReadBatch b, SegmentO
 // lies between rows: begin_row() places each in the read's signal.  A read the plan failed has its rows' gates closed.
 __global__ __launch_bounds__(WG) void svb16_segment_reads_kernel(ReadBatch b, Pod5Reads pr, SegmentOut so)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[SVB16_TILE * 2 + 48];
-    __shared__ __attribute__((aligned(16))) uint32_t wsum[4];
+    const Svb16Lds lds;
 
     if (*pr.bad) return;
     const uint32_t k = blockIdx.x;
@@ -2428,11 +2427,11 @@ __global__ __launch_bounds__(WG) void svb16_segment_reads_kernel(ReadBatch b, Po
     for (uint32_t r = first; r < end; ++r) {
         uint32_t in_size = 0, count = 0, verdict;
         if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-            if (tid == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
+            read_closed(b, r, verdict);
             continue;
         }
         st.begin_row(pr.rows[r].s0);   // (put() gets positions in the row)
-        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, stage, wsum);
+        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
         if (tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
     }
     st.done();

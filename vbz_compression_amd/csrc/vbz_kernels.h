@@ -177,6 +177,26 @@ struct ReadBatch
     SignalOut sig;   // decode only: what the svb stage stores (every other stage ignores it)
 };
 
+// The gate protocol of read r, the first thing every kernel over a ReadBatch decides: 0 = go on; GATE_SKIP = the read is another launch
+// group's (nothing of it is written); else the verdict the read keeps -- the gate's error, else (inherits: src_size can carry one, which
+// is so for every decoder and for no encoder) the previous stage's, left in src_size[r].  The order is part of the ABI: it decides which
+// verdict a read that is bad in two ways gets.
+// The passes of a normalising decode that stand around its counting passes (norm_init_read, norm_select_read, trim_read_open) ask no
+// more than this and an even dst_cap: the counting pass opens every read in full (svb_read_open / svb16_row_open) and writes its verdict,
+// the trim behind it tests result[], the select NormRead::phase and then touches only the read's own state and slab (no address comes
+// from the stream), and the init in front of it forms no address but the stream's first bytes, whose presence it checks itself.
+__device__ __forceinline__ uint32_t read_gate(const ReadBatch& b, uint32_t r, bool inherits)
+{
+    if (b.gate && b.gate[r] >= GATE_SKIP) return b.gate[r];
+    if (inherits && b.src_size[r] >= E_FIRST) return b.src_size[r];
+    return 0;
+}
+// a read that was not opened: thread 0 of the workgroup leaves its verdict (read_gate's, or an open function's), if one is to be written
+__device__ __forceinline__ void read_closed(const ReadBatch& b, uint32_t r, uint32_t verdict)
+{
+    if (threadIdx.x == 0 && verdict != GATE_SKIP) b.result[r] = verdict;
+}
+
 // ---- the per-read plans of the staged encoder (zstd_encode.hip), and what the svb encoder leaves in them ---------------------------
 // The entropy stage turns every run of >= RMIN equal control bytes into a zstd sequence and Huffman-codes what is left, each region from
 // its own byte histogram.  The one-wavefront path does that in stages that hand a read on through its EncPlan: the svb encoder counts
