@@ -2484,6 +2484,16 @@ VBZ_EXPORT int vbz_gpu_x_runs_counts(vbz_gpu_ctx* c, unsigned long long* out4, i
     HIPCHK(c, zstd_fast_runs_counts(out4, reset != 0), "runs counts");
     return 0;
 }
+// Measuring aid (experiments build only, VBZ_HIP_FS_COUNT=1): what fast_streams_kernel's refill path did since the last reset -- periods
+// walked, periods in which the wavefront took the path, lanes that issued (profiles/stream_refill.md).
+VBZ_EXPORT int vbz_gpu_x_streams_counts(vbz_gpu_ctx* c, unsigned long long* out3, int reset)
+{
+    if (!c || !out3) return -1;
+    DeviceGuard dg(c->device);
+    HIPCHK(c, hipStreamSynchronize(c->stream), "streams counts sync");
+    HIPCHK(c, zstd_fast_streams_counts(out3, reset != 0), "streams counts");
+    return 0;
+}
 #endif
 
 void vbz_gpu_profile_enable(vbz_gpu_ctx* c, int enable)

@@ -571,6 +571,7 @@ struct FastDecodeArgs
 hipError_t launch_zstd_decode_fast(const ReadBatch& b, const FastDecodeArgs& a, hipStream_t s);
 #ifdef VBZ_EXPERIMENTS
 hipError_t zstd_fast_runs_counts(unsigned long long out[4], bool reset);   // fast_runs_kernel's path counters (zstd_decode_fast.hip)
+hipError_t zstd_fast_streams_counts(unsigned long long out[3], bool reset);   // fast_streams_kernel's refill counters (zstd_decode_fast.hip)
 #endif
 size_t zstd_ref_lit_meta_bytes(uint32_t n_reads);
 uint32_t zstd_ref_lit_units();

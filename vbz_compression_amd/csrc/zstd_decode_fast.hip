@@ -8,8 +8,8 @@
 //   fast_scan_kernel     one LANE per frame: frame header, trailer, every block header; checks the shape (below) and leaves one
 //                        task per Huffman stream: where it starts, how long it is, where its bytes go, which table it uses
 //   fast_weights_kernel  one LANE per Huffman tree description: the FSE-coded weights (RFC 8878 4.2.1.1) -> 256 weight bytes
-//   fast_streams_kernel  one wavefront per frame, nothing but the streams: 64 lanes, one stream each, whole aligned 128-byte lines
-//                        requested per lane (a 64-dword ring per lane in LDS), 128 bytes stored per lane and burst
+//   fast_streams_kernel  one wavefront per frame, nothing but the streams: 64 lanes, one stream each, whole aligned 64-byte lines
+//                        requested per lane (a 32-dword ring per lane in LDS), 128 bytes stored per lane and burst
 //   fast_runs_kernel     one wavefront per frame: the zero-run block (state chains from the encoder's checkpoints, placement from
 //                        prefix sums: zstd_runs.h)
 //
@@ -23,6 +23,7 @@
 // zstd_tables.h, as in zstd_decode.hip.
 // Replaces, like zstd_decode.hip, the reference's ZSTD_decompress call (vbz/vbz.cpp:236-273).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #include "vbz_kernels.h"
@@ -302,39 +303,80 @@ __global__ __launch_bounds__(WAVE) void fast_weights_kernel(ReadBatch b, FastFra
 // room twice as often costs 0.85 ms per 65 536 frames by itself (VBZ_FS_RING=64 VBZ_FS_BATCH=32 VBZ_FS_PERIOD=16: 7.6 against 6.75 ms for the
 // whole stage), the four wavefronts more return it and a little more: 6.76 ms alone, and 608 against 597 GB/s for the step with the two
 // halves of a call in flight (round 5's 48-dword ring paid the first and got two wavefronts: it lost).
+//
+// The refill is shared by the wavefront (VBZ_FS_TRIGGER).  A lane may refill at any time between the moment it has room and the moment it
+// would run dry, and the 64 lanes are out of phase (the first line holds 0 - 63 bytes above the stream's end, and the streams drift apart):
+// left to themselves, some lane refills in nearly every period and the wavefront walks the whole masked path -- four loads, sixteen LDS
+// stores, the index arithmetic -- for a fifth of its lanes.  With a trigger T > 0 nobody refills until one lane with input left is down to
+// T unread dwords; then every lane that has room does, in that same period, and the request and the commit stand behind a scalar branch
+// that most periods do not take.  T = 0 is no trigger: every lane for itself, as soon as it has room.  Nothing else changes: the same
+// aligned requests, each line fetched once, the same store bursts.  (profiles/stream_refill.md has the counts and the times per variant.
+// ref_pieces_kernel below has its own copy of the walker and its own ring constants, is not on the own-frame path, and keeps refilling
+// lane by lane.)
 #ifndef VBZ_FS_RING
 #define VBZ_FS_RING 32
 #define VBZ_FS_BATCH 16
-#define VBZ_FS_PERIOD 16
+#endif
+#ifndef VBZ_FS_PERIOD
+#define VBZ_FS_PERIOD 8   // (shipped: period 8 at its trigger floor, 7 -- the variant that won the kernel and the step)
+#endif
+#ifndef VBZ_FS_TRIGGER
+#define VBZ_FS_TRIGGER trigger_floor(VBZ_FS_PERIOD)
 #endif
 constexpr int RING = VBZ_FS_RING;      // dwords per lane in the LDS ring
-constexpr int BATCH = VBZ_FS_BATCH;    // one request: a whole aligned line of 4 * BATCH bytes (128)
-constexpr int PERIOD = VBZ_FS_PERIOD;  // symbols between two requests (at most 11 bits each: PERIOD * 11 / 32 dwords)
+constexpr int BATCH = VBZ_FS_BATCH;    // one request: a whole aligned line of 4 * BATCH bytes (64)
 constexpr int BURST = 128;        // bytes a lane stores together
 constexpr unsigned long long LINE = 4ull * BATCH;
-// The ring cannot run dry between a request and its commit (one period later): a request is refused while more than RING - BATCH dwords
-// are unread, so a period starts with at least RING - BATCH + 1 - (a period's worst case) unread dwords, which must cover a period
-static_assert((RING & (RING - 1)) == 0 && RING - BATCH + 1 - (PERIOD * 11 + 31) / 32 >= (PERIOD * 11 + 31) / 32, "the ring would run dry");
-static_assert(BURST % PERIOD == 0 && PERIOD % 16 == 0 && BATCH % 4 == 0, "burst = whole periods, period = whole groups of 16 symbols");
+static_assert((RING & (RING - 1)) == 0 && BATCH % 4 == 0, "the ring is indexed by a mask, a request is whole 16-byte loads");
+// PERIOD: symbols between two looks at the ring (at most 11 bits each: W dwords); TRIGGER: the unread dwords at which a lane makes the
+// wavefront refill (0: none).  A period's request is committed at that period's END, so whatever a lane holds at the top of a period must
+// carry it through the period:
+//  * without a trigger a request is refused while more than RING - BATCH dwords are unread, so the period after a refusal starts with at
+//    least RING - BATCH + 1 - W, which must cover that period ("the ring would run dry");
+//  * with a trigger a lane is passed over while it holds more than T; at the top of the next period it holds at least T + 1 - W, triggers
+//    itself and is refilled only at that period's end.  Until then it consumes up to W dwords, and HUF_PAIR reads one ring dword AHEAD of the
+//    pair it decodes (w2): a ring that covers the period exactly returns wrong symbols of the right lengths (ref_pieces_kernel's 16-dword
+//    ring did).  Hence two dwords of margin, as in ref_pieces_kernel: T + 1 - W >= W + 2;
+//  * a lane that triggers must have room for the batch it then requests: T <= RING - BATCH.
+// The first bound is a floor, and the floor is what a variant uses: a lower trigger fires less often and finds more lanes with room.
+template <int PERIOD, int TRIGGER>
+struct RefillPolicy
+{
+    static constexpr int W = (PERIOD * 11 + 31) / 32;  // a period's worst case, dwords
+    static_assert(RING - BATCH + 1 - W >= W, "the ring would run dry");
+    static_assert(TRIGGER == 0 || TRIGGER + 1 - W >= W + 2, "a lane passed over would run dry (or read its look-ahead dword stale) before its own refill lands");
+    static_assert(TRIGGER == 0 || TRIGGER <= RING - BATCH, "a lane that triggers must have room for a batch");
+    static_assert(BURST % PERIOD == 0 && PERIOD % 4 == 0 && (16 % PERIOD == 0 || PERIOD % 16 == 0), "burst = whole periods, period = whole quads, a group of 16 = whole periods");
+    static constexpr int SUB = PERIOD < 16 ? PERIOD : 16;  // symbols per period in the head and the tail (groups of 16)
+};
+constexpr int trigger_floor(int period) { return 2 * ((period * 11 + 31) / 32) + 1; }
 constexpr uint32_t TBL_BIG = 2048, TBL_SMALL = 512;  // entries: one table of up to 11-bit codes, one of up to 9-bit codes
+#ifdef VBZ_EXPERIMENTS   // what the refill path did in a call (read by zstd_fast_streams_counts)
+__device__ unsigned long long streams_counts[3];
+#endif
 
 // The decoder of zstd_decode.hip's flush_tasks_ring (no bit buffer: the next 32 unread bits are one v_alignbit of two ring dwords held
 // in registers, two symbols per 32 fresh bits, the ring upside down with a mirror slot) around a different memory side:
-//  * a lane requests whole aligned 128-byte LINES, from the one that holds the stream's last byte down to the one that holds its
-//    first: never an address outside the lines the stream itself touches -- which may begin up to 127 bytes below the arena's first
-//    input byte and end up to 127 bytes behind its last one: vbz_gpu.h asks callers for memory that is readable to those line
-//    boundaries (any arena that is its own allocation is) --, and a line is fetched once.  Bit positions count from the top of the first line; the bytes between the stream's end and that top are consumed
+//  * a lane requests whole aligned 64-byte LINES, from the one that holds the stream's last byte down to the one that holds its
+//    first: never an address outside the lines the stream itself touches -- which may begin up to 63 bytes below the arena's first
+//    input byte and end up to 63 bytes behind its last one: vbz_gpu.h asks callers for memory that is readable to the 128-byte
+//    line boundaries around them (any arena that is its own allocation is) --, and a line is fetched once.  Bit positions count from the top of the first line; the bytes between the stream's end and that top are consumed
 //    before the first symbol;
 //  * request and commit of a batch are one stretch of straight-line code (request, decode a period, commit): the wait in front of
 //    the commit is a counted vmcnt, not the vmcnt(0) a loop-carried batch costs;
 //  * 128 decoded bytes per lane leave together.
+//  * COUNT (experiments build): periods walked, periods in which the wavefront took the refill path, lanes that issued -> streams_counts.
+template <int PERIOD, int TRIGGER, bool COUNT>
 __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const FastFrame* frames, const FastTask* tasks, const uint8_t* weights, uint32_t* redo)
 {
+    constexpr int SUB = RefillPolicy<PERIOD, TRIGGER>::SUB;
     __shared__ __attribute__((aligned(16))) uint16_t T[TBL_BIG + TBL_SMALL];
     __shared__ uint32_t ringbuf[RING + 1][WAVE];
+    __shared__ uint32_t counts[3];  // (COUNT only)
     const int lane = threadIdx.x;
     const uint32_t r = blockIdx.x;
     if (redo[r]) return;
+    if (COUNT && lane < 3) counts[lane] = 0;
     const FastFrame* F = frames + r;
     const uint32_t ntree = F->ntree, ntask = F->ntask;
     uint32_t tlog0 = F->tlog[0], tlog1 = ntree > 1 ? F->tlog[1] : 0u;
@@ -369,7 +411,7 @@ __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const F
     bool bad = false;
     int32_t n = -1;
     uint32_t widx = 0, end_bits = 0;
-    uint64_t nextline = 0, lowline = 0;  // the next request reads [nextline - 128, nextline); no line below lowline is read
+    uint64_t nextline = 0, lowline = 0;  // the next request reads [nextline - LINE, nextline); no line below lowline is read
     if (mine) {
         const uint8_t* p = src + t.src;
         const uint32_t last = nbytes ? p[nbytes - 1] : 0u;
@@ -440,17 +482,38 @@ __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const F
         n -= (int32_t)((e3 >> 8) + (e4 >> 8));                                                    \
         dstword = (e1 & 0xFFu) | ((e2 & 0xFFu) << 8) | ((e3 & 0xFFu) << 16) | (e4 << 24);         \
     } while (0)
-    // room for a batch: at most RING - BATCH dwords of the ring are still unread
-#define ROOM() (widx - (((uint32_t)~n) >> 5) <= (uint32_t)(RING - BATCH))
+    // A period opens with the look at the ring and the request, and closes with the commit.  `active`: the lane decodes in this period.
+    // room for a batch: at most RING - BATCH dwords of the ring are still unread; with a trigger, `go__` is wave-uniform and the request and
+    // the commit stand behind a scalar branch each (the lanes outside a divergent region neither trigger nor issue)
+#define UNREAD() (widx - (((uint32_t)~n) >> 5))
+#define PERIOD_OPEN(active)                                                                        \
+    uint32_t pend[BATCH];                                                                          \
+    const bool fed__ = (active) && MORE();                                                         \
+    const uint32_t unread__ = UNREAD();                                                            \
+    const bool issue = fed__ && unread__ <= (uint32_t)(RING - BATCH);                              \
+    const bool go__ = TRIGGER == 0 ? true : __any(fed__ && unread__ <= (uint32_t)TRIGGER) != 0;    \
+    if (COUNT) {                                                                                   \
+        const int took__ = __popcll(__ballot(issue && go__));                                      \
+        if (lane == __ffsll((long long)__ballot(true)) - 1) { /* one lane of those here */         \
+            counts[0] += 1u;                                                                       \
+            counts[1] += took__ ? 1u : 0u;                                                         \
+            counts[2] += (uint32_t)took__;                                                         \
+        }                                                                                          \
+    }                                                                                              \
+    if (go__) {                                                                                    \
+        if (issue) FETCH(pend);                                                                    \
+    }
+#define PERIOD_CLOSE()                 \
+    if (go__) {                        \
+        if (issue) RING_PUT(pend);     \
+    }
     typedef __attribute__((address_space(1), aligned(1))) u32x4 gs4;
     // symbols one at a time / in groups of 16 (one 16-byte store), as many as the lane asks for
     auto singles = [&](uint32_t k) {
         while (__any(k > 0)) {
-            uint32_t pend[BATCH];
-            const bool issue = k > 0 && ROOM() && MORE();
-            if (issue) FETCH(pend);
+            PERIOD_OPEN(k > 0);
 #pragma unroll 1
-            for (int i = 0; i < 16; ++i) {
+            for (int i = 0; i < SUB; ++i) {
                 if (k > 0) {
                     uint32_t e1, e2;
                     HUF_PAIR(e1, e2);
@@ -462,25 +525,28 @@ __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const F
                     --cnt;
                 }
             }
-            if (issue) RING_PUT(pend);
+            PERIOD_CLOSE();
         }
     };
     auto groups = [&](uint32_t g) {
         while (__any(g > 0)) {
-            uint32_t pend[BATCH];
-            const bool issue = g > 0 && ROOM() && MORE();
-            if (issue) FETCH(pend);
-            if (g > 0) {
-                uint32_t ow[4];
+            uint32_t ow[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) QUAD(ow[q]);
-                const u32x4 ov = { ow[0], ow[1], ow[2], ow[3] };
-                *(gs4*)o = ov;
-                o += 16;
-                cnt -= 16;
-                --g;
+            for (int h = 0; h < 16 / SUB; ++h) {
+                PERIOD_OPEN(g > 0);
+                if (g > 0) {
+#pragma unroll
+                    for (int q = h * SUB / 4; q < (h + 1) * SUB / 4; ++q) QUAD(ow[q]);
+                    if (h == 16 / SUB - 1) {
+                        const u32x4 ov = { ow[0], ow[1], ow[2], ow[3] };
+                        *(gs4*)o = ov;
+                        o += 16;
+                        cnt -= 16;
+                        --g;
+                    }
+                }
+                PERIOD_CLOSE();
             }
-            if (issue) RING_PUT(pend);
         }
     };
     // ---- head: up to the next 128-byte line of the output, so that every burst below writes whole aligned lines (the memory system
@@ -498,9 +564,7 @@ __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const F
             uint32_t ow[BURST / 4];
 #pragma unroll
             for (int h = 0; h < BURST / PERIOD; ++h) {
-                uint32_t pend[BATCH];
-                const bool issue = ROOM() && MORE();
-                if (issue) FETCH(pend);
+                PERIOD_OPEN(true);
 #pragma unroll
                 for (int q = h * PERIOD / 4; q < (h + 1) * PERIOD / 4; ++q) QUAD(ow[q]);
                 if (h == BURST / PERIOD - 1) {  // the stores go out in front of the last commit: its wait is vmcnt(stores)
@@ -510,7 +574,7 @@ __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const F
                         *(gs4*)(o + 16 * q) = ov;
                     }
                 }
-                if (issue) RING_PUT(pend);
+                PERIOD_CLOSE();
             }
             o += BURST;
             cnt -= BURST;
@@ -521,11 +585,19 @@ __global__ __launch_bounds__(WAVE) void fast_streams_kernel(ReadBatch b, const F
     singles(cnt);
 #undef HUF_PAIR
 #undef QUAD
-#undef ROOM
+#undef PERIOD_OPEN
+#undef PERIOD_CLOSE
+#undef UNREAD
 #undef MORE
 #undef RING_PUT
 #undef FETCH
     if (mine && !bad && n != -(int32_t)end_bits) bad = true;  // every bit of the stream must be consumed, none beyond
+#ifdef VBZ_EXPERIMENTS
+    if (COUNT) {
+        wave_lds_sync();
+        if (lane < 3) atomicAdd(&streams_counts[lane], (unsigned long long)counts[lane]);
+    }
+#endif
     if (__any(bad)) {
         if (lane == 0) redo[r] = 1;
     } else if (F->nseq == 0 && lane == 0) {
@@ -1048,7 +1120,48 @@ __global__ __launch_bounds__(WAVE, VBZ_RUNS_WAVES) void fast_runs_kernel(ReadBat
 
 }  // namespace
 
+// The stream kernel of a call.  The shipped library has one: VBZ_FS_PERIOD / VBZ_FS_TRIGGER.  The experiments build carries the variants
+// that profiles/stream_refill.md compares, each at its period's trigger floor, beside the untriggered kernel of the same period:
+// VBZ_HIP_FS_VARIANT="period,trigger" selects one (an unknown pair is an error, not a fall-back), VBZ_HIP_FS_COUNT=1 its counting twin.
+typedef void (*StreamsKernel)(ReadBatch, const FastFrame*, const FastTask*, const uint8_t*, uint32_t*);
+static StreamsKernel streams_kernel()
+{
 #ifdef VBZ_EXPERIMENTS
+    static const StreamsKernel k = []() -> StreamsKernel {
+        const char* v = getenv("VBZ_HIP_FS_VARIANT");
+        const char* c = getenv("VBZ_HIP_FS_COUNT");
+        const bool count = c && atoi(c) != 0;
+        if (!v && !count) return fast_streams_kernel<VBZ_FS_PERIOD, VBZ_FS_TRIGGER, false>;
+        int period = VBZ_FS_PERIOD, trigger = VBZ_FS_TRIGGER;
+        if (v && sscanf(v, "%d,%d", &period, &trigger) != 2) return nullptr;
+#define VARIANT(P, T) \
+    if (period == P && trigger == T) return count ? fast_streams_kernel<P, T, true> : fast_streams_kernel<P, T, false>
+        VARIANT(16, 0);
+        VARIANT(16, trigger_floor(16));
+        VARIANT(8, 0);
+        VARIANT(8, trigger_floor(8));
+        VARIANT(8, trigger_floor(8) + 1);  // (a period of 4 costs eight more registers and with them three wavefronts per CU: not built)
+#undef VARIANT
+        return nullptr;
+    }();
+    return k;
+#else
+    return fast_streams_kernel<VBZ_FS_PERIOD, VBZ_FS_TRIGGER, false>;
+#endif
+}
+
+#ifdef VBZ_EXPERIMENTS
+// { periods walked, periods in which the wavefront took the refill path, lanes that issued } by the counting stream kernels since the last
+// reset; the device must be idle.
+hipError_t zstd_fast_streams_counts(unsigned long long out[3], bool reset)
+{
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(streams_counts), sizeof(streams_counts));
+    if (e == hipSuccess && reset) {
+        const unsigned long long zero[3] = { 0, 0, 0 };
+        e = hipMemcpyToSymbol(HIP_SYMBOL(streams_counts), zero, sizeof(zero));
+    }
+    return e;
+}
 // { chunks of 64 sequences placed, of them built in LDS, sequences sections with checkpoints, of them staged in LDS } by fast_runs_kernel
 // since the last reset; the device must be idle.
 hipError_t zstd_fast_runs_counts(unsigned long long out[4], bool reset)
@@ -1164,6 +1277,8 @@ hipError_t launch_zstd_decode_fast(const ReadBatch& b, const FastDecodeArgs& a, 
     const FastSide side = a.side;
     const uint32_t n = b.n_reads;
     if (n == 0) return hipSuccess;
+    const StreamsKernel streams = streams_kernel();
+    if (!streams) return hipErrorInvalidValue;  // (experiments build: VBZ_HIP_FS_VARIANT names no kernel)
     const FastMeta M = fast_meta(meta, n);
     const RefLitMeta R = ref_lit_meta(ref_lits, n);
     FastFrame* const frames = M.frames;
@@ -1212,7 +1327,7 @@ hipError_t launch_zstd_decode_fast(const ReadBatch& b, const FastDecodeArgs& a, 
     }
     if (!dbg && e == hipSuccess) {
         hipLaunchKernelGGL(fast_weights_kernel, dim3((2 * n + WAVE - 1) / WAVE), dim3(WAVE), 0, s, b, frames, weights, redo, n);
-        hipLaunchKernelGGL(fast_streams_kernel, dim3(n), dim3(WAVE), 0, s, b, frames, tasks, weights, redo);
+        hipLaunchKernelGGL(streams, dim3(n), dim3(WAVE), 0, s, b, frames, tasks, weights, redo);
         hipLaunchKernelGGL(fast_runs_kernel, dim3(n), dim3(WAVE), 0, s, b, frames, reinterpret_cast<const SeqDTables*>(seq_dtables), redo);
         e = hipGetLastError();
     }
