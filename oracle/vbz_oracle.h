@@ -219,6 +219,31 @@ int vbo_zstd_census_count(void);
 const char* vbo_zstd_census_name(int k);  /* NULL beyond the list */
 int vbo_zstd_census_is_max(int k);        /* a maximum: merged over frames with max, the others with + */
 
+/* ---- the listing: every block and every sequence of a buffer's frames, as the restated decoder meets them.  Content positions count
+ * from the start of the buffer's content (over all its frames); a block's ordinal counts inside its frame. */
+typedef struct {
+    uint64_t begin, end; /* the block's content range [begin, end) */
+    uint32_t ordinal;
+    uint32_t type;       /* Block_Type: 0 raw, 1 RLE, 2 compressed */
+    uint32_t literals;   /* regenerated size of the literals section; of a raw or RLE block: its content */
+    uint32_t nseq;
+} VboSeqBlock;
+typedef struct {
+    uint64_t pos;        /* content position where the sequence's literals begin */
+    int64_t unread;      /* bits of the sequences bit stream still unread at the head of the loop, before the sequence's extra bits */
+    uint32_t block;      /* ordinal of its block */
+    uint32_t ll, ml;     /* literal length, match length */
+    uint32_t offset;     /* the resolved offset */
+    uint32_t ofv;        /* the raw Offset_Value: 1 .. 3 a repeat offset, else offset + 3 */
+    uint16_t ll_state, ml_state; /* the FSE states at the head of the loop */
+    uint8_t ll_code, of_code, ml_code, reserved0;
+    uint32_t reserved1;
+} VboSeq;
+/* Decodes as vbo_zstd_restate_census does and fills blocks[0 .. block_cap) and seqs[0 .. seq_cap) (either may be NULL); *nblocks (if not
+ * NULL) gets the number of blocks and the return value is the number of sequences -- of the whole buffer, also where they exceed the
+ * room given, so a call without room sizes the next.  (size_t)-1 for a buffer the decoder refuses (the arrays then hold what was met). */
+size_t vbo_zstd_restate_sequences(const void* src, size_t n, VboSeqBlock* blocks, size_t block_cap, size_t* nblocks, VboSeq* seqs, size_t seq_cap);
+
 /* ---- replay of the reference's fuzz target (oracle/vbz_oracle_fuzz.c; reference vbz/fuzzing/vbz_fuzz.cpp:138-161) */
 uint32_t vbo_fuzz_max_destination(uint32_t size, const VboOptions* o);
 int vbo_fuzz_decompress_sweep(const void* data, uint32_t size, const VboOptions* o, uint32_t max_destination, uint32_t* results);

@@ -349,6 +349,16 @@ static const uint32_t ML_BASE[53] = { 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 1
 static const uint8_t ML_BITS[53] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                      0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16 };
 
+/* the listing (vbo_zstd_restate_sequences): null on every other call, and nothing below decides anything by it.  Records beyond the
+ * caller's room are counted, not stored */
+typedef struct {
+    VboSeqBlock* blocks;
+    size_t block_cap, nblocks;
+    VboSeq* seqs;
+    size_t seq_cap, nseqs;
+    uint64_t origin; /* content of the buffer's earlier frames */
+} seq_listing;
+
 typedef struct {
     huf_table huf;
     fse_table ll, of, ml;
@@ -357,7 +367,24 @@ typedef struct {
     /* census only: the counters (null on the ordinary call), the block's ordinal and that of the block whose tree is held */
     uint64_t* cen;
     uint32_t block, tree_block;
+    seq_listing* lst;
 } frame_ctx;
+
+static void list_block(seq_listing* l, uint32_t ordinal, int type, uint64_t begin)
+{
+    if (!l) return;
+    if (l->nblocks < l->block_cap) {
+        VboSeqBlock* b = &l->blocks[l->nblocks];
+        memset(b, 0, sizeof(*b));
+        b->begin = b->end = l->origin + begin;
+        b->ordinal = ordinal;
+        b->type = (uint32_t)type;
+    }
+    l->nblocks++;
+}
+
+/* the block list_block opened last, or null if it was not stored */
+static VboSeqBlock* listed_block(seq_listing* l) { return (l && l->nblocks >= 1 && l->nblocks <= l->block_cap) ? &l->blocks[l->nblocks - 1] : NULL; }
 
 /* kind (census): 0 literal lengths, 1 offsets, 2 match lengths */
 static int seq_table(fse_table* t, int* have, int mode, const uint8_t** pp, const uint8_t* end, const int16_t* def, int def_n,
@@ -553,6 +580,11 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
     if (nu < 0) return ZR_ERR;
     p += nu;
     CEN(cen, nseq == 0 ? VBO_CEN_SEQ_NONE : VBO_CEN_SEQ_COUNT_1_BYTE + nu - 1);
+    seq_listing* const lst = fc->lst;
+    if (listed_block(lst)) {
+        listed_block(lst)->literals = (uint32_t)regen;
+        listed_block(lst)->nseq = (uint32_t)nseq;
+    }
     size_t opos = base; /* logical output position */
     size_t lpos = 0;
 #define PUT(byte_expr)                                    \
@@ -583,6 +615,8 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
     for (size_t i = 0; i < nseq; ++i) {
         int lc = fc->ll.e[sl].symbol, oc = fc->of.e[so].symbol, mc = fc->ml.e[sm].symbol;
         if (lc > 35 || mc > 52 || oc > 31) return ZR_ERR;
+        const int64_t unread = b.pos; /* the listing: the bits still unread and the states at the head of the loop */
+        const uint32_t sl0 = sl, sm0 = sm;
         uint32_t ofv = (1u << oc) + bitr_read(&b, oc);
         uint32_t mlen = ML_BASE[mc] + bitr_read(&b, ML_BITS[mc]);
         uint32_t llen = LL_BASE[lc] + bitr_read(&b, LL_BITS[lc]);
@@ -613,6 +647,25 @@ static size_t decode_block(frame_ctx* fc, const uint8_t* src, size_t n, uint8_t*
                 fc->rep[1] = fc->rep[0];
                 fc->rep[0] = offset;
             }
+        }
+        if (lst) {
+            if (lst->nseqs < lst->seq_cap) {
+                VboSeq* q = &lst->seqs[lst->nseqs];
+                memset(q, 0, sizeof(*q));
+                q->pos = lst->origin + opos;
+                q->unread = unread;
+                q->block = fc->block;
+                q->ll = llen;
+                q->ml = mlen;
+                q->offset = offset;
+                q->ofv = ofv;
+                q->ll_state = (uint16_t)sl0;
+                q->ml_state = (uint16_t)sm0;
+                q->ll_code = (uint8_t)lc;
+                q->of_code = (uint8_t)oc;
+                q->ml_code = (uint8_t)mc;
+            }
+            lst->nseqs++;
         }
         if (i + 1 < nseq) {
             sl = fc->ll.e[sl].base + bitr_read(&b, fc->ll.e[sl].nbits);
@@ -688,8 +741,10 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
     pos += (size_t)fcs_sz;
     if (single) window = fcs;
     uint64_t block_max = window < ZR_BLOCK_MAX ? window : ZR_BLOCK_MAX;
+    seq_listing* const lst = fc->lst;
     memset(fc, 0, sizeof(*fc));
     fc->cen = cen;
+    fc->lst = lst;
     if (cen) {
         CEN(cen, VBO_CEN_FRAMES);
         CEN(cen, single ? VBO_CEN_FRAME_SINGLE_SEGMENT : VBO_CEN_FRAME_WINDOW_DESCRIPTOR);
@@ -711,6 +766,8 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
         CEN(cen, last ? VBO_CEN_BLOCK_LAST : VBO_CEN_BLOCK_NOT_LAST);
         if (btype < 2) CEN_ADD(cen, VBO_CEN_LITERAL_BYTES, bsize);
         if (btype == 0 && bsize == 0) CEN(cen, VBO_CEN_BLOCK_RAW_EMPTY);
+        list_block(lst, fc->block, btype, out);
+        if (btype < 2 && listed_block(lst)) listed_block(lst)->literals = (uint32_t)bsize;
         if (btype == 0) {
             if (bsize > block_max) return ZR_ERR;
             if (pos + bsize > n) return ZR_ERR;
@@ -733,6 +790,7 @@ static size_t decode_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t ca
             out += r;
             pos += bsize;
         }
+        if (listed_block(lst)) listed_block(lst)->end = lst->origin + out;
         fc->block++;
         if (last) break;
     }
@@ -784,6 +842,28 @@ size_t vbo_zstd_restate_census(const void* src_, size_t n, uint64_t* counters, s
         n -= used;
     }
     return total;
+}
+
+/* The listing: the same decode again (nothing stored), writing down every block and every sequence it meets -- vbz_oracle.h, VboSeqBlock and
+ * VboSeq.  What a buffer holds beyond the caller's room is counted, not stored, so a call without room sizes the next one. */
+size_t vbo_zstd_restate_sequences(const void* src_, size_t n, VboSeqBlock* blocks, size_t block_cap, size_t* nblocks, VboSeq* seqs, size_t seq_cap)
+{
+    static _Thread_local uint8_t lit[ZR_BLOCK_MAX + 32];
+    static _Thread_local frame_ctx fc;
+    const uint8_t* src = (const uint8_t*)src_;
+    seq_listing l = { blocks, blocks ? block_cap : 0, 0, seqs, seqs ? seq_cap : 0, 0, 0 };
+    while (n > 0) {
+        size_t used = 0;
+        fc.lst = &l;
+        size_t r = decode_frame(src, n, NULL, 0, &used, lit, &fc);
+        fc.lst = NULL;
+        if (r == ZR_ERR) return ZR_ERR;
+        l.origin += r;
+        src += used;
+        n -= used;
+    }
+    if (nblocks) *nblocks = l.nblocks;
+    return l.nseqs;
 }
 
 static const char* const census_names[VBO_CEN_COUNT] = {

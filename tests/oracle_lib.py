@@ -79,6 +79,8 @@ def lib():
         L.vbo_zstd_restate_decompress.argtypes = [vp, sz, vp, sz]
         L.vbo_zstd_restate_census.restype = sz
         L.vbo_zstd_restate_census.argtypes = [vp, sz, vp, sz]
+        L.vbo_zstd_restate_sequences.restype = sz
+        L.vbo_zstd_restate_sequences.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz), vp, sz]
         L.vbo_zstd_census_count.restype = ctypes.c_int
         L.vbo_zstd_census_name.restype = ctypes.c_char_p
         L.vbo_zstd_census_name.argtypes = [ctypes.c_int]
@@ -268,6 +270,28 @@ def zstd_census(frame):
     out = {k: int(v) for k, v in zip(names, c)}
     out["content_size"] = int(r)
     return out
+
+
+# oracle/vbz_oracle.h: VboSeqBlock, VboSeq
+SEQ_BLOCK = np.dtype([("begin", "<u8"), ("end", "<u8"), ("ordinal", "<u4"), ("type", "<u4"), ("literals", "<u4"), ("nseq", "<u4")])
+SEQ = np.dtype([("pos", "<u8"), ("unread", "<i8"), ("block", "<u4"), ("ll", "<u4"), ("ml", "<u4"), ("offset", "<u4"), ("ofv", "<u4"),
+                ("ll_state", "<u2"), ("ml_state", "<u2"), ("ll_code", "u1"), ("of_code", "u1"), ("ml_code", "u1"), ("reserved0", "u1"),
+                ("reserved1", "<u4")])
+assert SEQ_BLOCK.itemsize == 32 and SEQ.itemsize == 48
+
+
+def zstd_sequences(frame):
+    """(blocks, seqs): every block and every sequence of the buffer's frames as the restated decoder meets them (oracle/vbz_oracle.h,
+    vbo_zstd_restate_sequences), two structured arrays of SEQ_BLOCK and SEQ; None where the restated decoder refuses the buffer."""
+    a, p, n = _buf(frame if isinstance(frame, np.ndarray) else np.frombuffer(bytes(frame), np.uint8))
+    nb = ctypes.c_size_t(0)
+    ns = lib().vbo_zstd_restate_sequences(p, n, None, 0, ctypes.byref(nb), None, 0)
+    if ns == 2**64 - 1:
+        return None
+    blocks, seqs = np.zeros(nb.value, SEQ_BLOCK), np.zeros(ns, SEQ)
+    r = lib().vbo_zstd_restate_sequences(p, n, blocks.ctypes.data if nb.value else None, nb.value, ctypes.byref(nb), seqs.ctypes.data if ns else None, ns)
+    assert r == ns and nb.value == len(blocks)
+    return blocks, seqs
 
 
 def zstd_content_size(frame):

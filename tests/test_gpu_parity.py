@@ -412,7 +412,11 @@ def test_sequences_section_round_and_lane_boundaries():
     """The encoder's sequences section runs its two FSE state chains on all lanes (four-state warm-up walks; a lane whose
     walks have not met takes its neighbour's state; rounds of 256 sequences).  Control-byte regions with exactly N runs, N
     around every boundary of that scheme, with literal-length and match-length codes of one, two, three and four table
-    cells, must decode with libzstd and the restated decoder to the same bytes."""
+    cells, must decode with libzstd and the restated decoder to the same bytes.
+
+    (The zstd stage called on its own, as here, has no slot of the library's to rewrite and never tokenises: these regions leave as raw or
+    Huffman blocks.  The same counts and styles reach the sequences section through the whole codec in tests/test_gpu_encoder_sequences.py,
+    test_sequence_rounds_and_lanes, where every sequence is compared.)"""
     import gpu_util as G
 
     rng = np.random.default_rng(11)
