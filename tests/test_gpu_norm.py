@@ -11,7 +11,7 @@ import torch
 import norm_ref as R
 import oracle_lib as O
 from signal_ref import typed_bits
-from typed_support import ELEM, Frames, arena, codec, key, norm_of, u32, walk_signal
+from typed_support import ELEM, Frames, arena, check_stats, codec, int16, key, norm_of, stats, u32, walk_signal
 from vbz_compression_amd import _lib, batch
 
 pytestmark = pytest.mark.gpu
@@ -45,36 +45,6 @@ def mixed_reads(seed, signed=True, long_len=100_003):
 
 def compress_oracle(c, reads, oopts, sized=False):
     return arena(c, [O.compress(x.view(np.int16), oopts, sized=sized) for x in reads], 64)
-
-
-def int16(case):
-    c = case.c
-    dst = torch.zeros(case.dst_bytes + 64, dtype=torch.uint8, device=c.device)
-    res = torch.zeros(case.n, dtype=torch.int32, device=c.device)
-    c.decompress(case.src, case.off, case.size, dst, case.doff, case.dcap, res, case.opts, sized=case.sized)
-    torch.cuda.synchronize()
-    return u32(res)
-
-
-def stats(case, p, signed=True):
-    c = case.c
-    res = torch.full((case.n,), -1, dtype=torch.int32, device=c.device)
-    ss = c.signal_norm(case.src, case.off, case.size, case.doff, case.dcap, res, case.opts, norm_of(p), signed=signed, sized=case.sized)
-    torch.cuda.synchronize()
-    return ss.cpu().numpy(), u32(res)
-
-
-def check_stats(case, p, signed=True):
-    ss, res = stats(case, p, signed)
-    assert (res == int16(case)).all()
-    for i, x in enumerate(case.reads):
-        x = x if signed else x.view(np.uint16)
-        assert res[i] == 2 * len(x), (i, res[i])
-        shift, scale = R.shift_scale(x, p)
-        got = ss[i]
-        assert got[0].view(np.uint32) == shift.view(np.uint32) and got[1].view(np.uint32) == scale.view(np.uint32), (
-            i, len(x), p, got, shift, scale)
-    return ss, res
 
 
 # ---- 1. the statistics --------------------------------------------------------------------------------------------------------

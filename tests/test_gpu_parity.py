@@ -254,10 +254,11 @@ def test_svb_int16_decoder_body_tail_split():
 
 
 def test_wave_svb_decoder_behind_the_entropy_stage():
-    """The int16 zig-zag stream behind the entropy stage is decoded by svb_decode_kernel with its block path (lanes own 32
-    consecutive values, packed 16-bit arithmetic).  Foreign and malformed svb streams (codes 2 / 3, wrong lengths, short and
-    long streams, every length class of the block paths) packed into frames by libzstd -- what a foreign writer could store --
-    must give the oracle's samples or the oracle's error."""
+    """The int16 zig-zag stream behind the entropy stage is decoded by svb_decode_range: pairs of whole tiles of one- and two-byte
+    codes by I16DecPairs (a lane owns 8 consecutive values of either tile, sums mod 2^32 of which the store keeps 16 bits), everything
+    else -- wide codes, the ragged end, every verdict -- by the tile loop.  Foreign and malformed svb streams (codes 2 / 3, wrong
+    lengths, short and long streams, sizes around a tile, a pair and a segment) packed into frames by libzstd -- what a foreign writer
+    could store -- must give the oracle's samples or the oracle's error."""
     import gpu_util as G
     from vbz_compression_amd import _lib
 

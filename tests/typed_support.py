@@ -1,7 +1,8 @@
 """Batches, frames and C structs for the typed-decode tests on the MI355X (test_gpu_signal, _chunks, _norm, _pod5, _pod5_reads, _ranges,
 _trim, _chunk_store, _typed_refusals; test_gpu_pack takes the codec): one definition of the codec cache, the table and arena helpers, the
 two signal generators, the compress step, compressed reads with their int16 layout, the C-struct builders, and the raw chunk calls with
-their checks against signal_ref / pod5_reads_ref / ranges_ref.  A plain module (no assertion rewriting): every assert here carries its
+their checks against signal_ref / pod5_reads_ref / ranges_ref, the typed decode beside the int16 decode (decode_both) and the statistics
+call's check (check_stats), which test_gpu_foreign_streams runs too.  A plain module (no assertion rewriting): every assert here carries its
 operands.  Output types are signal_ref's strings; key() takes a torch dtype to them."""
 import ctypes
 import os
@@ -14,6 +15,7 @@ import pod5_ref as P
 import pod5_reads_ref as PR
 import ranges_ref as G
 import signal_ref as SR
+from signal_ref import is_nan_bits, typed_bits
 from vbz_compression_amd import _lib, batch
 
 CANARY = 0x5A
@@ -390,3 +392,91 @@ class Run:
             owned[lo:hi] = True
         assert (got[~owned].view(np.uint8) == CANARY).all(), "a chunk row outside the reads' rows was written"
         return self
+
+
+# ---- the typed decode beside the int16 decode ---------------------------------------------------------------------------------------
+def decode_both(c, src, src_off, src_size, caps16, opts, sized, dtype, offset=None, scale=None, signed=True, skew=0, typed_cap=None,
+                typed_off=None, expect=None, after_typed=None):
+    """The batch decoded twice: typed (dtype), then int16 with the capacities caps16.  typed_cap / typed_off (bytes; default: caps16 / 2 * E
+    in a layout E / 2 times the int16 one, `skew` elements further on) may break the E-alignment rule; expect[i] overrides the expected
+    typed verdict.  Checks every verdict, every sample, and the canary around and between the typed slots.  Returns the typed results."""
+    dev = c.device
+    n = len(caps16)
+    dt = key(dtype)
+    E = ELEM[dt]
+    off16, tot16 = batch.layout([int(x) + 32 for x in caps16], 64)
+    off16 = off16.tolist()
+    tcap = [int(x) // 2 * E for x in caps16] if typed_cap is None else [int(x) for x in typed_cap]
+    toff = [o * E // 2 + skew * E for o in off16] if typed_off is None else [int(x) for x in typed_off]
+    tbytes = (max([o + cp for o, cp in zip(toff, tcap)] + [0]) + 64 + 15) // 16 * 16
+    tarena = torch.full((tbytes,), CANARY, dtype=torch.uint8, device=dev)
+    tres = torch.full((n,), -8, dtype=torch.int32, device=dev)
+    kw = {}
+    if offset is not None:
+        kw["offset"] = torch.from_numpy(np.asarray(offset, np.float32)).to(dev)
+    if scale is not None:
+        kw["scale"] = torch.from_numpy(np.asarray(scale, np.float32)).to(dev)
+    c.decompress_signal(src, src_off, src_size, tarena.view(dtype), torch.tensor(toff, dtype=torch.int64, device=dev), i32(tcap).to(dev), tres, opts,
+                        signed=signed, sized=sized, **kw)
+    if after_typed:
+        after_typed()
+    raw = torch.zeros(tot16 + 64, dtype=torch.uint8, device=dev)
+    res16 = torch.full((n,), -8, dtype=torch.int32, device=dev)
+    c.decompress(src, src_off, src_size, raw, torch.tensor(off16, dtype=torch.int64, device=dev), i32(caps16).to(dev), res16, opts, sized=sized)
+    torch.cuda.synchronize()
+    r16, rt = u32(res16), u32(tres)
+    raw_h = raw.cpu().numpy()
+    t_h = tarena.cpu().numpy()
+    o_all = np.zeros(n, np.float32) if offset is None else np.asarray(offset, np.float32)
+    s_all = np.ones(n, np.float32) if scale is None else np.asarray(scale, np.float32)
+    written = np.zeros(tbytes, bool)
+    for i in range(n):
+        want = int(r16[i]) if _lib.is_error(int(r16[i])) else int(r16[i]) // 2 * E
+        if expect and i in expect:
+            want = expect[i]
+        assert int(rt[i]) == want, (i, hex(int(rt[i])), hex(want), hex(int(r16[i])))
+        written[toff[i] : toff[i] + tcap[i]] = True
+        if _lib.is_error(want):
+            if expect and i in expect:   # (a slot refused by the alignment rule is never written)
+                assert (t_h[toff[i] : toff[i] + tcap[i]] == CANARY).all(), i
+            continue
+        k = want // E
+        x16 = raw_h[off16[i] : off16[i] + 2 * k].view(np.int16 if signed else np.uint16)
+        ref = typed_bits(x16, o_all[i], s_all[i], dt)
+        got = t_h[toff[i] : toff[i] + k * E].view(ref.dtype)
+        nan = is_nan_bits(ref, dt)
+        assert np.array_equal(got[~nan], ref[~nan]), (i, int(np.argmax(got != ref)))
+        assert is_nan_bits(got[nan], dt).all(), i
+    assert (t_h[~written] == CANARY).all(), "a byte outside every slot was written"
+    return rt
+
+
+# ---- the statistics call ------------------------------------------------------------------------------------------------------------
+def int16(case):
+    c = case.c
+    dst = torch.zeros(case.dst_bytes + 64, dtype=torch.uint8, device=c.device)
+    res = torch.zeros(case.n, dtype=torch.int32, device=c.device)
+    c.decompress(case.src, case.off, case.size, dst, case.doff, case.dcap, res, case.opts, sized=case.sized)
+    torch.cuda.synchronize()
+    return u32(res)
+
+
+def stats(case, p, signed=True):
+    c = case.c
+    res = torch.full((case.n,), -1, dtype=torch.int32, device=c.device)
+    ss = c.signal_norm(case.src, case.off, case.size, case.doff, case.dcap, res, case.opts, norm_of(p), signed=signed, sized=case.sized)
+    torch.cuda.synchronize()
+    return ss.cpu().numpy(), u32(res)
+
+
+def check_stats(case, p, signed=True):
+    ss, res = stats(case, p, signed)
+    assert (res == int16(case)).all()
+    for i, x in enumerate(case.reads):
+        x = x if signed else x.view(np.uint16)
+        assert res[i] == 2 * len(x), (i, res[i])
+        shift, scale = R.shift_scale(x, p)
+        got = ss[i]
+        assert got[0].view(np.uint32) == shift.view(np.uint32) and got[1].view(np.uint32) == scale.view(np.uint32), (
+            i, len(x), p, got, shift, scale)
+    return ss, res

@@ -853,6 +853,7 @@ struct I16DecPairs
         uint32_t kna = 0, knb = 0;
         if (more) load_keys(tn, kna, knb);
         if (tid == 0) ws[WS_FLAG] = 0;
+        wg_lds_barrier();   // the flag is cleared before any wavefront's first trip can set it (the control bytes stay in flight)
         uint32_t cur = 0, par = 0;
         uint32_t kca = 0, kcb = 0, exC = 0, totC = 0, misC = 0, tc = 0;   // the pair in the stage
         while (more || have) {
