@@ -685,19 +685,12 @@ __device__ __forceinline__ bool seg_locate(const uint32_t* seg_first, uint32_t n
     return true;
 }
 
-// SELF (calls whose segment tables are small: SEG_SELF_MAX): no scan launch between the passes -- a workgroup adds up what the segments
+// SELF (calls whose segment tables are small: self_max): no scan launch between the passes -- a workgroup adds up what the segments
 // of its read in front of it have announced by itself (a few loads per thread, the values sit in the L2), and a read's first
 // workgroup does what the scan kernel's first thread does (the read's result).  A call of few reads is a chain of short dependent
 // launches: each one saved is 4.5 us.  The loads grow with the square of the table (1024 segments: 4 MB out of the L2 per pass).
-constexpr uint32_t SEG_SELF_MAX = 1024;
-static uint32_t seg_self_max()
-{
-    static const uint32_t v = [] {
-        const char* e = getenv("VBZ_HIP_SEG_SELF_MAX");   // 0: always the scan launches
-        return e ? (uint32_t)strtoul(e, nullptr, 10) : SEG_SELF_MAX;
-    }();
-    return v;
-}
+// The bound is the caller's (self_max of the launchers: SVB_SEG_SELF_MAX in vbz_kernels.h, or what the context read from
+// VBZ_HIP_SEG_SELF_MAX when it was created; 0: always the scan launches).
 
 // all 256 threads: { sum of arr[lo .. mid), sum of arr[lo .. hi) }, lo <= mid <= hi
 __device__ __forceinline__ void seg_sums(const uint32_t* arr, uint32_t lo, uint32_t mid, uint32_t hi, uint64_t* sums_s, uint64_t& before, uint64_t& total)
@@ -2550,10 +2543,10 @@ hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, Init 
 // the segmented decode: MODE 1, then (SELF) MODE 2 and MODE 0, or the verdict scan, MODE 2 and its scan, and MODE 0; only MODE 0 stores
 template <int E, bool Z, bool I, int OUT>
 hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val, uint64_t* seg_pos,
-                                   uint32_t* seg_run, hipStream_t s, const TrimOut* trim)
+                                   uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim)
 {
     const dim3 segs(max_segs), reads(b.n_reads), t(WG);
-    const bool self = max_segs <= seg_self_max();
+    const bool self = max_segs <= self_max;
     auto mode0 = [&](auto o) {
         if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
         else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
@@ -2822,11 +2815,11 @@ uint32_t svb_seg_unit_bytes(int integer_size)
 }
 
 hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigzag, uint32_t hdr, bool strict_cap, const uint32_t* seg_first,
-                                 uint32_t max_segs, uint32_t* seg_bytes, uint64_t* seg_off, hipStream_t s)
+                                 uint32_t max_segs, uint32_t* seg_bytes, uint64_t* seg_off, uint32_t self_max, hipStream_t s)
 {
     if (b.n_reads == 0) return hipSuccess;
     const uint32_t sc = strict_cap ? 1u : 0u;
-    const bool self = max_segs <= seg_self_max();
+    const bool self = max_segs <= self_max;
     const dim3 segs(max_segs), reads(b.n_reads), t(WG);
     return svb_dispatch_elem(integer_size, zigzag, [&](auto e, auto z, auto i) {
         constexpr int E = e();
@@ -2843,13 +2836,13 @@ hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigz
 }
 
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
-                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s, const TrimOut* trim)
+                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim)
 {
     if (b.n_reads == 0) return hipSuccess;
     if (trim && !b.sig.norm.st) return hipErrorInvalidValue;
     return svb_dispatch_store(b, [&](auto out) {
         return svb_dispatch_elem<out() == SIG_NONE>(integer_size, zigzag, [&](auto e, auto z, auto i) {
-            return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, s, trim);
+            return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, self_max, s, trim);
         });
     });
 }

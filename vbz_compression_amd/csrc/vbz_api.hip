@@ -165,6 +165,7 @@ struct Knobs
     bool trailers = true;         // decoder hints (checkpoints, span index) in skippable frames behind the zstd frame
     bool checksum = false;        // vbz_gpu_set_checksum / VBZ_HIP_CHECKSUM=1: frames written with the content checksum (xxh64.hip)
     int segmented = -1;           // -1: by batch shape; 0 / 1: forced (VBZ_HIP_SEGMENTED, for tests)
+    uint32_t seg_self_max = SVB_SEG_SELF_MAX;   // VBZ_HIP_SEG_SELF_MAX: large-read path, calls of more segments get scan launches between the svb passes (0: every call)
     bool zero_run_sequences = true;
     bool long_repeats = true;     // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance
     int phase_timing = 0;         // VBZ_HIP_PHASE_TIMING: 1 phase counters of the entropy kernels (one launch per frame), 2 / 3 of the encoder's planning / packing launch (staged, under load)
@@ -702,7 +703,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
     if (o->zstd_compression_level == 0) {  // vbz.cpp:171-192: svb straight into dst
         Timed t(c, "svb_encode");
         if (segmented)
-            HIPCHK(c, launch_svb_encode_seg(rb, (int)o->integer_size, o->perform_delta_zig_zag, hdr, true, seg.first, seg.max_segs, seg.val, seg.off, s),
+            HIPCHK(c, launch_svb_encode_seg(rb, (int)o->integer_size, o->perform_delta_zig_zag, hdr, true, seg.first, seg.max_segs, seg.val, seg.off, c->knobs.seg_self_max, s),
                    "svb_encode (segmented) launch");
         else
             HIPCHK(c, launch_svb_encode(rb, (int)o->integer_size, o->perform_delta_zig_zag, hdr, true, half_codec(o), nullptr, nullptr, s), "svb_encode launch");
@@ -749,7 +750,7 @@ int compress_group(vbz_gpu_ctx* c, const ReadBatch& rb_in, uint64_t src_bytes, c
         if (pod5)   // (one workgroup per read on every path: DESIGN.md 4.13)
             HIPCHK(c, launch_svb16_encode(a, matcher ? p.m.deep_d : nullptr, s), "svb16_encode launch");
         else if (segmented)
-            HIPCHK(c, launch_svb_encode_seg(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, seg.first, seg.max_segs, seg.val, seg.off, s),
+            HIPCHK(c, launch_svb_encode_seg(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, seg.first, seg.max_segs, seg.val, seg.off, c->knobs.seg_self_max, s),
                    "svb_encode (segmented) launch");
         else
             HIPCHK(c, launch_svb_encode(a, (int)o->integer_size, o->perform_delta_zig_zag, 0, false, half_codec(o), matcher ? p.m.deep_d : nullptr,
@@ -874,7 +875,7 @@ int svb_decode_stage(vbz_gpu_ctx* c, const DecodeJob& j, const CompressionOption
     if (pod5_codec(o))   // (one workgroup per read on every path: DESIGN.md 4.13)
         HIPCHK(c, launch_svb16_decode(j.rb, c->stream, trim), "svb16_decode launch");
     else if (segmented)
-        HIPCHK(c, launch_svb_decode_seg(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->stream, trim),
+        HIPCHK(c, launch_svb_decode_seg(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->knobs.seg_self_max, c->stream, trim),
                "svb_decode (segmented) launch");
     else
         HIPCHK(c, launch_svb_decode(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream, trim), "svb_decode launch");
@@ -1944,6 +1945,7 @@ vbz_gpu_ctx* vbz_gpu_create(int device, void* stream)
     if (const char* e = getenv("VBZ_HIP_SHARED_TABLES")) c->knobs.shared_tables = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_ROUTING")) c->knobs.routing = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_SEGMENTED")) c->knobs.segmented = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_SEG_SELF_MAX")) c->knobs.seg_self_max = (uint32_t)strtoul(e, nullptr, 10);
     if (const char* e = getenv("VBZ_HIP_TRAILERS")) c->knobs.trailers = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_CANONICAL")) c->knobs.canonical = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_CHECKSUM")) c->knobs.checksum = atoi(e) != 0;

@@ -401,11 +401,13 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
 // bounds the total segment count (the grid); seg_* are scratch arrays of max_segs entries.  Not for the nibble codec.
+// self_max: calls of at most that many segments have no scan launch between the passes (svb_kernels.hip: SELF); 0: every call has them.
+constexpr uint32_t SVB_SEG_SELF_MAX = 1024;
 uint32_t svb_seg_unit_bytes(int integer_size);
 hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigzag, uint32_t hdr, bool strict_cap, const uint32_t* seg_first,
-                                 uint32_t max_segs, uint32_t* seg_bytes, uint64_t* seg_off, hipStream_t s);
+                                 uint32_t max_segs, uint32_t* seg_bytes, uint64_t* seg_off, uint32_t self_max, hipStream_t s);
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
-                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, hipStream_t s, const TrimOut* trim = nullptr);
+                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim = nullptr);
 
 // ---- zstd-format entropy stage (zstd_encode.hip / zstd_decode.hip) -----------------------------
 // encode: frame content = src read.  The launchers' arguments are host-side aggregates, filled field by field; what is not set is not used.
