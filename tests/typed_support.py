@@ -69,6 +69,35 @@ def arena(c, bufs, align):
     return torch.from_numpy(a).to(c.device), off.to(c.device), i32(sizes).to(c.device)
 
 
+class Stage:
+    """what run_stage leaves: out (per read the result's bytes, or the error verdict), the destination arena on the host, the slots'
+    offsets, and the extents the call declared (src_bytes, dst_bytes: what the library's shape rule sees)"""
+
+    def __init__(self, out, host, off, src_bytes, dst_bytes):
+        self.out, self.host, self.off, self.src_bytes, self.dst_bytes = out, host, off, src_bytes, dst_bytes
+
+
+def run_stage(c, fn, bufs, caps, align=64, pad=32, fill=0):
+    """gpu_util.run_stage on the codec c: fn(c, src, src_off, src_size, dst, dst_off, dst_cap, result) over host buffers, into slots of
+    caps[i] + pad bytes at multiples of `align` in an arena filled with `fill` (align = 1, pad = 0: slots without gaps) -> Stage"""
+    dev = c.device
+    src, src_off, src_size = arena(c, bufs, 64)
+    doff, dtotal = batch.layout([int(x) + pad for x in caps], align)
+    dst = torch.full((dtotal + 64,), fill, dtype=torch.uint8, device=dev)
+    result = torch.full((len(bufs),), -8, dtype=torch.int32, device=dev)
+    fn(c, src, src_off, src_size, dst, doff.to(dev), i32(caps).to(dev), result)
+    torch.cuda.synchronize()
+    host = dst.cpu().numpy()
+    out = []
+    for r, o, cap in zip(u32(result).tolist(), doff.tolist(), caps):
+        if _lib.is_error(int(r)):
+            out.append(int(r))
+        else:
+            assert r <= cap, (r, cap)
+            out.append(host[o : o + int(r)].copy())
+    return Stage(out, host, doff.tolist(), int(src.numel()), int(dst.numel()))
+
+
 # ---- signal -------------------------------------------------------------------------------------------------------------------------
 def walk_signal(rng, T):
     """a slow random walk under noise, inside [80, 580]"""
