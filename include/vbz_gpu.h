@@ -663,6 +663,83 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_segment_batch(vbz_gpu_ctx* ctx, const vbz_gpu
                                                  uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_sample_ranges* ranges,
                                                  const vbz_gpu_segmentation* segmentation, uint64_t* event_first, uint32_t* start);
 
+/* Signal spans.  Where a read's signal leaves its working band: open-pore spikes between molecules (read splitting), stalls and adapter
+ * plateaus (stretches below a level for at least so many samples), saturation at the ADC rails.  All are one primitive -- take the
+ * positions whose raw value lies above or below a per-read threshold, merge hits that are at most a gap apart, drop runs that are too
+ * short -- and the two calls below do it on the device with no sample stored.  The trim call above is a prefix-only, one-answer form of
+ * it.  This library was written without the source of any read splitter: the rule below is the contract (tests/spans_ref.py).
+ * The signal is the read's samples x[b:e) of T' = e - b raw 16-bit values (int16, or uint16 with is_signed == 0), ranges clamped exactly
+ * as in the *_range_batch calls (ranges NULL, or both tables NULL: the whole read).  Positions q are positions in this signal.
+ * The threshold: thr = float64(a) + float64(f) * float64(w), f = threshold_factor: one multiply, then one add, each rounded to nearest
+ * even, none fused (the trim call's expression).  With `norm`, {a, w} is the read's {shift, scale} exactly as the statistics-alone call
+ * gives it (vbz_gpu_signal_norm_range_batch with the same norm and ranges: ranges->stats has its usual meaning), shift_scale is written
+ * when given, and spans->level must be NULL.  Without `norm` (NULL), {a, w} = level[i] is given in raw counts, no counting pass runs,
+ * shift_scale is ignored and level must not be NULL: a shift_scale table from an earlier statistics call is a valid level, and a caller
+ * with calibrated units passes a = pA / scale - offset, w = 0.  A NaN thr makes nothing in; +inf and -inf behave as the comparison says.
+ * In: in(q) holds when q >= p0 = ignore_prefix and float64(x[q]) > thr (VBZ_GPU_SPAN_ABOVE) or float64(x[q]) < thr (VBZ_GPU_SPAN_BELOW).
+ * The comparison is strict: a sample equal to thr is not in.
+ * Spans: walk the in-positions in ascending order.  Two consecutive in-positions q < q' belong to one span when q' - q - 1 <= D,
+ * D = merge_gap, 0 ... 65535.  A span is [first, last + 1).  Spans with last + 1 - first < m, m = min_length, 1 ... 2^31 - 1, are
+ * dropped: the length test comes after the merge.  Equivalently a span opens at an in-position with no in-position in the D + 1
+ * positions before it and closes behind an in-position with none in the D + 1 positions after it.  Hence
+ * spans <= (T' + D + 1) / (m + D + 1) by integer division: a caller sizes edge[] -- two entries a span -- from that bound (and from
+ * vbz_gpu_range_samples_batch's output when ranges are used) without a synchronisation.
+ * The rows: span k of read i is the pair edge[edge_first[i] + 2k] = begin, edge[edge_first[i] + 2k + 1] = end; rows ascend and
+ * end <= T'.  edge_first[0] = 0 and edge_first[i + 1] - edge_first[i] is twice the read's span count: 0 for a read whose decode verdict
+ * is an error and for a POD5 read with a failing row.  The table is always complete and holds the true counts, whatever edge_cap is.
+ * Read i's pairs are written when edge_first[i + 1] <= edge_cap; a read whose rows end beyond edge_cap gets VBZ_DESTINATION_SIZE_ERROR
+ * (on every row of a POD5 read, and its read_result) and not one word of edge is written for it; nothing beyond edge_cap and no entry
+ * owned by no fitting read is ever written.  edge == NULL with edge_cap == 0 is the count-only call: it writes edge_first alone and
+ * leaves the verdicts alone.  result[i] is otherwise what the statistics-alone call gives: the int16 decode's verdict, T x 2 with the
+ * read's FULL sample count on success; the POD5 twin writes read_result[] as the POD5 statistics call does, its tables (edge_first,
+ * level, shift_scale, ranges) are per READ, positions those of the concatenated signal, and a bad first_row fails the whole call with
+ * nothing written.  A read whose bit map (below) finds no room in the call's scratch -- possible only when the int16 layout's slots
+ * overlap -- gets VBZ_OUT_OF_MEMORY_ERROR.  batch->dst may be NULL.
+ * Both return 0 when queued, -1 for a NULL context or batch or a launch failure, -2 (nothing launched) for everything
+ * vbz_gpu_signal_norm_range_batch / its POD5 twin refuse about the batch, the options, `reads` and `ranges` (a NULL norm is allowed
+ * here; a norm that is given must pass its rules), a NULL spans or edge_first, an unknown direction, merge_gap > 65535, min_length 0 or
+ * above 2^31 - 1, a threshold_factor that is not finite, flags != 0, level NULL without norm or not NULL with it, edge == NULL with
+ * edge_cap != 0, edge_cap * 4 beyond 2^46 bytes.
+ * The hand-over: edge_first and edge are a vbz_gpu_events as they stand -- event_first, start, event_rows = edge_cap (or the total when
+ * the caller has read it) -- with the same ranges, on the same stream.  Even rows of a read are then the spans' records (mean, sd,
+ * dwell), odd rows the stretches between spans, the last odd row running to T': for a split read those stretches are its sub-reads,
+ * and window starts for the windows call are built from them.  (The samples in front of the first span belong to no row.)
+ * How: one more sink of the svb decoder, and the cheap one: a position's bit depends on that sample alone, so there is
+ * no neighbourhood, no LDS and no seam.  Once per read the threshold becomes an integer bound on the 16-bit key; a lane turns its eight
+ * samples into eight bits with integer compares and stores one byte of the read's bit map in scratch (one bit per position of the READ,
+ * 1/16 of the int16 arena).  The pass runs on the one-workgroup path, on every SEGMENT of the large-read path (a 20 M-sample read is
+ * spread over ~1 200 workgroups) and over POD5 rows and reads; with `norm` it runs behind the last counting pass.  A count launch that
+ * reads result[] first (one workgroup per read walks the map a word a thread, carrying the last in-position and the open span's begin
+ * with two running maxima), the scan, and an emit launch that makes the same walk follow behind everything the call has queued.
+ * Measured on one MI355X (tools/time_spans.py, profiles/HISTORY.md "Signal spans"; the parent of the commit that adds these calls is bf9fbf2;
+ * median of 20, calls alternating in one process, every table checked bit for bit against the unfused route): 65 536 synthetic reads of
+ * ~100 k samples with three planted plateaus each, ABOVE, MED_MAD, f = 6, D = 50, m = 5, 196 608 spans: 19.77 ms with the normalisation
+ * against 11.44 ms for the statistics-alone call and 11.65 ms for the trim call; 14.94 ms with given constants against 10.25 ms for the
+ * int16 decode; 194.3 ms for the unfused route (statistics, int16 decode, torch compare, nonzero, diff, merge and filter).  The span pass
+ * costs what the int16 store pass costs (7.4 - 7.6 ms against 7.4 - 8.4 ms by the library's labels: the decode bounds both, not the
+ * store); count + scan + emit cost 5.1 ms.  One 20 M-sample read: 3.68 ms against 0.44 ms for the statistics alone and 9.50 ms unfused --
+ * the pass itself adds 0.02 ms there (it is spread over 1 221 segments); the rest is the two one-workgroup walks of count and emit. */
+#define VBZ_GPU_SPAN_ABOVE 0u   /* a sample is "in" when float64(x) >  thr */
+#define VBZ_GPU_SPAN_BELOW 1u   /* a sample is "in" when float64(x) <  thr */
+typedef struct vbz_gpu_spans
+{
+    uint32_t direction;      /* VBZ_GPU_SPAN_* */
+    uint32_t merge_gap;      /* D: 0 ... 65535 */
+    uint32_t min_length;     /* m: 1 ... 2^31 - 1 */
+    uint32_t ignore_prefix;  /* p0: positions q < p0 of the signal are never in */
+    float threshold_factor;  /* f, finite */
+    uint32_t flags;          /* must be 0 */
+    const float* level;      /* device, n_reads x {float a, float w}; required when norm is NULL, must be NULL otherwise */
+    uint64_t edge_cap;       /* entries of edge[] */
+} vbz_gpu_spans;             /* 40 bytes */
+VBZ_EXPORT int vbz_gpu_signal_spans_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                          uint32_t is_signed, const vbz_gpu_normalization* norm, float* shift_scale,
+                                          const vbz_gpu_sample_ranges* ranges, const vbz_gpu_spans* spans, uint64_t* edge_first, uint32_t* edge);
+VBZ_EXPORT int vbz_gpu_pod5_signal_spans_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                               uint32_t is_signed, const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm,
+                                               float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_spans* spans,
+                                               uint64_t* edge_first, uint32_t* edge);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -209,6 +209,25 @@ class GpuSegmentation(ctypes.Structure):
     ]
 
 
+VBZ_GPU_SPAN_ABOVE = 0
+VBZ_GPU_SPAN_BELOW = 1
+
+
+class GpuSpans(ctypes.Structure):
+    """struct vbz_gpu_spans of include/vbz_gpu.h (40 bytes)."""
+
+    _fields_ = [
+        ("direction", ctypes.c_uint32),
+        ("merge_gap", ctypes.c_uint32),
+        ("min_length", ctypes.c_uint32),
+        ("ignore_prefix", ctypes.c_uint32),
+        ("threshold_factor", ctypes.c_float),
+        ("flags", ctypes.c_uint32),
+        ("level", ctypes.c_void_p),
+        ("edge_cap", ctypes.c_uint64),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -254,6 +273,8 @@ GPU_API = [
     "vbz_gpu_pod5_signal_events_batch",
     "vbz_gpu_signal_segment_batch",
     "vbz_gpu_pod5_signal_segment_batch",
+    "vbz_gpu_signal_spans_batch",
+    "vbz_gpu_pod5_signal_spans_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -420,6 +441,15 @@ def load():
         L.vbz_gpu_signal_segment_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.c_uint32, gp, sp, vp, vp]
         L.vbz_gpu_pod5_signal_segment_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_signal_segment_batch.argtypes = [vp, bp, op, ctypes.c_uint32, rp, gp, sp, vp, vp]
+    if hasattr(L, "vbz_gpu_signal_spans_batch"):   # (likewise: builds of earlier rounds have no signal spans)
+        np_ = ctypes.POINTER(GpuNormalization)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        gp = ctypes.POINTER(GpuSampleRanges)
+        xp = ctypes.POINTER(GpuSpans)
+        L.vbz_gpu_signal_spans_batch.restype = ctypes.c_int
+        L.vbz_gpu_signal_spans_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.c_uint32, np_, vp, gp, xp, vp, vp]
+        L.vbz_gpu_pod5_signal_spans_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_signal_spans_batch.argtypes = [vp, bp, op, ctypes.c_uint32, rp, np_, vp, gp, xp, vp, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -92,6 +92,35 @@ class Segmentation:
         return 2 + int(samples) // (self.radius + 1)
 
 
+@dataclasses.dataclass(frozen=True)
+class Spans:
+    """Where a read's signal lies above or below a level (include/vbz_gpu.h: vbz_gpu_spans): a sample is in when it is above
+    (direction "above") or below ("below") thr = a + threshold_factor * w -- {a, w} the read's {shift, scale} of a normalisation, or
+    given per read -- and lies at or behind ignore_prefix; in-positions at most merge_gap apart form one span, and spans shorter than
+    min_length are dropped."""
+
+    direction: str = "above"
+    merge_gap: int = 0
+    min_length: int = 1
+    ignore_prefix: int = 0
+    threshold_factor: float = 0.0
+
+    _DIRECTIONS = {"above": _lib.VBZ_GPU_SPAN_ABOVE, "below": _lib.VBZ_GPU_SPAN_BELOW}
+
+    def c_struct(self, edge_cap=0, level=None):
+        g = _lib.GpuSpans()
+        g.direction = self._DIRECTIONS.get(self.direction, 0xFFFFFFFF)
+        g.merge_gap, g.min_length, g.ignore_prefix = self.merge_gap, self.min_length, self.ignore_prefix
+        g.threshold_factor = self.threshold_factor
+        g.level = level
+        g.edge_cap = int(edge_cap)
+        return g
+
+    def max_edges(self, samples):
+        """the bound on a read's entries of edge: two per span, spans <= (T' + D + 1) / (m + D + 1)"""
+        return 2 * ((int(samples) + self.merge_gap + 1) // (self.min_length + self.merge_gap + 1))
+
+
 def _u32(t):
     """view an int32 result tensor as python ints in [0, 2**32)"""
     return [int(x) & 0xFFFFFFFF for x in t.tolist()]
@@ -175,7 +204,7 @@ class GpuCodec:
 
     def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
                chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None, ev=None, moments=None, sg=None,
-               event_first=None, start=None):
+               event_first=None, start=None, sp=None):
         """One typed decode (include/vbz_gpu.h): the batch, the device entered and left once, and the most general C entry of the call's
         family, NULL for every part that is None.  dst None: nothing is stored in the batch's dst (a chunk decode, the statistics) --
         dst_off / dst_cap are the int16 layout that describes the reads, dst_bytes its extent.  f (a GpuSignalFormat): what is stored,
@@ -184,7 +213,8 @@ class GpuCodec:
         GpuPod5Reads (the pod5_ entries: unsized).  w (a GpuWindows, in place of ch): the samples go to the caller-listed windows, the
         rows of `chunks`.  ev (a GpuEvents, with f): no sample is stored -- one record per caller-listed event into `out` (int32 [rows, 4]), the
         exact sums into `moments` (int64 [rows, 2], or None).  sg (a GpuSegmentation, f None): every read's event starts, found on the
-        device, into event_first (int64 [reads + 1]) and start (int32, sg.start_cap entries; None: the count-only call)."""
+        device, into event_first (int64 [reads + 1]) and start (int32, sg.start_cap entries; None: the count-only call).  sp (a GpuSpans,
+        f None; m / ss optional): every read's spans into event_first (edge_first) and start (edge, sp.edge_cap entries or None)."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -203,6 +233,9 @@ class GpuCodec:
         elif ch is not None:
             name, args = "decompress_chunks_range", [ref(f), ref(ch)] + reads + [chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]), ref(m),
                                                                                  ss, ref(g)]
+        elif f is None and sp is not None:
+            name, args = "signal_spans", [int(bool(signed))] + reads + [ref(m), ss, ref(g), ref(sp), event_first.data_ptr(),
+                                                                        start.data_ptr() if start is not None else None]
         elif f is None and sg is not None:
             name, args = "signal_segment", [int(bool(signed))] + reads + [ref(g), ref(sg), event_first.data_ptr(), start.data_ptr() if start is not None else None]
         elif f is None and t is not None:
@@ -388,6 +421,57 @@ class GpuCodec:
         self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, self._extent(n, dst_off, dst_cap), signed=signed, g=g, sg=sg,
                     event_first=event_first, start=start)
         return event_first, start
+
+    # -- signal spans (include/vbz_gpu.h: vbz_gpu_spans) --------------------------------------------
+    def _span_args(self, n, spans, samples, edge_cap, edge_first, edge, norm, level, shift_scale):
+        """(the C struct, edge_first, edge, the GpuNormalization or None, the shift_scale pointer, shift_scale, what to keep alive) of a span
+        call over n reads of `samples` (an int tensor).  edge_cap None: the bound, sum of max_edges (one host copy); 0: the count-only call.
+        Exactly one of norm (a Normalization) and level (float32 [n, 2] of {a, w} on the device) is given"""
+        sp = Spans() if spans is None else spans
+        assert isinstance(sp, Spans), sp
+        assert (norm is None) != (level is None), "one of norm= and level="
+        if edge is not None:
+            edge_cap = int(edge.numel()) if edge_cap is None else edge_cap
+        elif edge_cap is None:
+            k = sp.min_length + sp.merge_gap + 1
+            edge_cap = int((2 * ((samples.to(torch.int64) + sp.merge_gap + 1) // k)).sum().item()) if n else 0
+        if edge is None and edge_cap:
+            edge = torch.empty(edge_cap, dtype=torch.int32, device=self.device)
+        if edge is not None:
+            assert edge.dtype == torch.int32 and edge.is_contiguous() and edge.device == self.device and int(edge.numel()) >= edge_cap, (
+                edge.dtype, edge.shape, edge_cap)
+        if edge_first is None:
+            edge_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        assert edge_first.dtype == torch.int64 and edge_first.is_contiguous() and edge_first.device == self.device and int(edge_first.numel()) == n + 1, (
+            edge_first.dtype, edge_first.shape)
+        m = ss = None
+        if norm is not None:
+            if shift_scale is True:
+                shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+            m, ss = self._norm_args(n, norm, shift_scale, None, None)
+        else:
+            assert shift_scale is None, "shift_scale= goes with norm="
+            assert level.dtype == torch.float32 and level.is_contiguous() and level.device == self.device and tuple(level.shape) == (n, 2), (
+                level.dtype, level.shape)
+        return sp.c_struct(edge_cap, level.data_ptr() if level is not None else None), edge_first, (edge if edge_cap else None), m, ss, shift_scale
+
+    def signal_spans(self, src, src_off, src_size, dst_off, dst_cap, result, opts, spans=None, edge_cap=None, signed=True, sized=False, begin=None,
+                     end=None, edge_first=None, edge=None, norm=None, level=None, shift_scale=None, stats=None):
+        """Every read's spans above or below its level, found on the device with no sample stored (include/vbz_gpu.h:
+        vbz_gpu_signal_spans_batch) -> (edge_first int64 [n + 1], edge int32 [edge_cap] or None), both on the device: span k of read i is
+        edge[edge_first[i] + 2 k] = begin, edge[edge_first[i] + 2 k + 1] = end, and the two tables go into signal_events as event_first and
+        start as they stand.  spans: a Spans (None: its defaults).  The level: norm (a Normalization: the read's shift + f scale; the
+        statistics are signal_norm's for the same begin / end / stats) or level (float32 [n, 2] of {a, w}: a + f w).  shift_scale (with
+        norm): True or a float32 [n, 2] tensor to get the constants as well; the return is then (edge_first, edge, shift_scale).  edge_cap:
+        entries of edge (None: the bound; 0: the count-only call) -- a read whose pairs end beyond it gets VBZ_DESTINATION_SIZE_ERROR and
+        no pair.  begin / end: the signal is that range of every read.  dst_off / dst_cap: the int16 layout of the reads."""
+        n = int(src_off.numel())
+        g, keep = self._ranges(n, begin, end, stats)
+        sp, edge_first, edge, m, ss, shift_scale = self._span_args(n, spans, dst_cap.to(torch.int64) // 2, edge_cap, edge_first, edge, norm, level,
+                                                                   shift_scale)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, self._extent(n, dst_off, dst_cap), signed=signed, m=m, ss=ss, g=g,
+                    sp=sp, event_first=edge_first, start=edge)
+        return (edge_first, edge) if shift_scale is None else (edge_first, edge, shift_scale)
 
     def decompress_signal(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, scale=None, offset=None, signed=True, sized=False,
                           norm=None, norm_out=None):
@@ -881,6 +965,24 @@ class GpuCodec:
         self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, pod5_options(), dst_bytes=dst_off[-1].item(), signed=signed, g=g, r=r,
                     sg=sg, event_first=event_first, start=start)
         return event_first, start, read_result
+
+    def pod5_signal_spans(self, src, src_off, src_size, row_samples, read_first_row, result, spans=None, edge_cap=None, signed=True, begin=None,
+                          end=None, edge_first=None, edge=None, norm=None, level=None, shift_scale=None, stats=None, read_result=None):
+        """signal_spans over POD5 signal rows grouped into reads by read_first_row (vbz_gpu_pod5_signal_spans_batch) ->
+        (edge_first int64 [n_reads + 1], edge, read_result), with shift_scale behind them when asked for: the tables, level and begin / end
+        are per READ, the positions those of the read's concatenated signal; result is per ROW."""
+        n = int(src_off.numel())
+        assert int(row_samples.numel()) == n
+        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        g, keep = self._ranges(r.n_reads, begin, end, stats)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        if edge_cap is None and edge is None:   # (the bound per read is at most the bound of all samples plus one span a read)
+            sp0 = spans or Spans()
+            edge_cap = 2 * (r.n_reads + int(torch.as_tensor(row_samples).to(torch.int64).sum().item()) // (sp0.min_length + sp0.merge_gap + 1))
+        sp, edge_first, edge, m, ss, shift_scale = self._span_args(r.n_reads, spans, None, edge_cap, edge_first, edge, norm, level, shift_scale)
+        self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, pod5_options(), dst_bytes=dst_off[-1].item(), signed=signed, m=m, ss=ss, g=g,
+                    r=r, sp=sp, event_first=edge_first, start=edge)
+        return (edge_first, edge, read_result) if shift_scale is None else (edge_first, edge, read_result, shift_scale)
 
     def pod5_decompress_signal_norm(self, src, src_off, src_size, row_samples, read_first_row, result, norm, dtype=torch.float32, signed=True,
                                     norm_out=None, align=16):

@@ -529,7 +529,172 @@ __global__ __launch_bounds__(1024) void segment_emit_kernel(ReadBatch b, Pod5Rea
     }
 }
 
+// ---- signal spans: count, scan, emit behind the span pass (vbz_kernels.h SpanOut; the rule: include/vbz_gpu.h) ------------------------------
+// running maximum of v over the 1024 threads in front of this one (0 in front of thread 0); total = the maximum of all
+__device__ __forceinline__ uint32_t block_excl_max_u32(uint32_t v, uint32_t* wmax, uint32_t& total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc = inc > t ? inc : t;
+    }
+    uint32_t ex = __shfl_up(inc, 1, 64);
+    if (lane == 0) ex = 0;
+    if (lane == 63) wmax[w] = inc;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t s = wmax[k];
+        pre = k < w && s > pre ? s : pre;
+        tot = s > tot ? s : tot;
+    }
+    __syncthreads();
+    total = tot;
+    return pre > ex ? pre : ex;
+}
+
+// The one statement of the walk, by the whole workgroup: the spans of the map's bits at positions [rb, re) of the read -- in-positions at
+// most D apart merged, spans shorter than m dropped -- counted (the return, workgroup-uniform) and, EMIT, written as pairs {begin, end}
+// in positions of the signal (p - rb) from edge[0] on, in order, `cap` pairs at the most (the count launch's: nothing is written beyond
+// them).  A word a thread, 32 768 positions a trip.  Positions travel as p + 1 (0: none).  Two running maxima carry what a thread must
+// know of the walk in front of it: the last in-position (whether the thread's first in-position opens a span: more than D positions lie
+// between) and the begin of the span that is open there.  A span is complete at its last in-position, which is known where the next
+// span opens -- there its length is tested -- or at the walk's end.  A thread loops over the span BEGINS of its word, not over its
+// in-positions (a plateau is words of 32 set bits and one begin): the begins are the bits with no set bit in the min(D + 1, 32)
+// positions below them inside the word, the word's lowest set bit being judged against the last in-position in front of the word.
+template <bool EMIT>
+__device__ __forceinline__ uint32_t span_walk(const uint32_t* map, uint32_t rb, uint32_t re, uint32_t D, uint32_t m, uint32_t* wmax, uint64_t* wsum,
+                                              uint32_t* edge, uint32_t cap)
+{
+    uint32_t last_in = 0, open_at = 0;   // (workgroup-uniform, p + 1) behind the trips so far: the last in-position, the open span's begin
+    uint64_t rank = 0;                   // complete spans that passed the length test so far
+    const uint32_t wend = (re + 31u) >> 5;
+    const uint32_t reach = D + 1u < 32u ? D + 1u : 32u;
+    for (uint32_t w0 = rb >> 5; w0 < wend && rb < re; w0 += 1024) {
+        const uint32_t w = w0 + threadIdx.x, p0 = 32u * w;
+        uint32_t bits = w < wend ? map[w] : 0u;
+        if (p0 < rb) bits &= 0xFFFFFFFFu << (rb - p0);                                         // (rb - p0 < 32: the walk begins in rb's word)
+        if (w < wend && re - p0 < 32u) bits &= 0xFFFFFFFFu >> (32u - (re - p0));                // (positions behind the range: other bits, or no writer)
+        uint32_t tot_in, tot_open;
+        const uint32_t prev0 = max(last_in, block_excl_max_u32(bits ? p0 + 32u - (uint32_t)__clz((int)bits) : 0u, wmax, tot_in));
+        // this thread's span begins: an in-position with no in-position in the D + 1 positions in front of it
+        uint32_t near = bits << 1;   // bit j: an in-position lies 1 ... `have` positions below j, inside the word
+        for (uint32_t have = 1; have < reach;) {
+            const uint32_t step = have < reach - have ? have : reach - have;
+            near |= near << step;
+            have += step;
+        }
+        uint32_t opens = bits & ~near;   // (the word's lowest set bit among them)
+        if (bits && prev0 != 0 && p0 + (uint32_t)__ffs((int)bits) - 1u - prev0 <= D) opens &= opens - 1u;   // ... which the walk in front of the word may reach
+        const uint32_t open0 = max(open_at, block_excl_max_u32(opens ? p0 + 32u - (uint32_t)__clz((int)opens) : 0u, wmax, tot_open));
+        // every begin but the read's first completes the span in front of it: [cur - 1, prev), prev behind the last in-position below the
+        // begin -- kept when it has m positions
+        auto spans_of = [&](auto&& take) {
+            uint32_t cur = open0;
+            for (uint32_t rest = opens; rest; rest &= rest - 1u) {
+                const uint32_t j = (uint32_t)__ffs((int)rest) - 1u, below = bits & ((1u << j) - 1u);
+                const uint32_t prev = below ? p0 + 32u - (uint32_t)__clz((int)below) : prev0;
+                if (prev != 0 && prev - cur + 1u >= m) take(cur, prev);
+                cur = p0 + j + 1u;
+            }
+        };
+        uint32_t cnt = 0;
+        spans_of([&](uint32_t, uint32_t) { ++cnt; });
+        uint64_t tot;
+        uint64_t at = rank + block_excl_scan_u64((uint64_t)cnt, wsum, tot);
+        if (EMIT && cnt)
+            spans_of([&](uint32_t cur, uint32_t prev) {
+                if (at < cap) {
+                    edge[2 * at] = cur - 1u - rb;
+                    edge[2 * at + 1] = prev - rb;
+                }
+                ++at;
+            });
+        rank += tot;
+        last_in = max(last_in, tot_in);
+        open_at = max(open_at, tot_open);
+    }
+    if (last_in != 0 && last_in - open_at + 1u >= m) {   // the span that is open at the walk's end
+        if (EMIT && threadIdx.x == 0 && rank < cap) {
+            edge[2 * rank] = open_at - 1u - rb;
+            edge[2 * rank + 1] = last_in - rb;
+        }
+        ++rank;
+    }
+    return (uint32_t)rank;
+}
+
+// the signal of read i of T samples: its clamped range, in positions of the read (segment_emit_kernel's)
+__device__ __forceinline__ void span_range(const ReadBatch& b, const Pod5Reads& pr, uint32_t i, uint32_t T, uint32_t* rb, uint32_t* re)
+{
+    *rb = 0, *re = T;
+    if (!pr.reads) sample_range(b.sig, i, T, rb, re);
+    else if (b.sig.ranged()) *rb = pr.range[i].x, *re = pr.range[i].y;
+}
+
+// the count launch, one workgroup per read: rows[i] = twice the read's spans -- result[] is read first, and the map of a read that did
+// not pass is not looked at (the sink cannot count: spans cross lanes, tiles and segments)
+__global__ __launch_bounds__(1024) void span_count_kernel(ReadBatch b, Pod5Reads pr, SpanOut so, uint32_t* rows)
+{
+    __shared__ uint64_t wsum[16];
+    __shared__ uint32_t wmax[16];
+    if (pr.reads && *pr.bad) return;
+    const uint32_t i = blockIdx.x;
+    uint32_t T = 0, spans = 0;
+    if (segment_passed(b, pr, i, &T) && T != 0) {
+        uint32_t rb, re;
+        span_range(b, pr, i, T, &rb, &re);
+        spans = span_walk<false>(reinterpret_cast<const uint32_t*>(so.map + so.map_off[i]), rb, re, so.D, so.m, wmax, wsum, nullptr, 0u);
+    }
+    if (threadIdx.x == 0) rows[i] = 2u * spans;
+}
+
+// the emit launch, one workgroup per read: its entry of edge_first and, where its pairs end at or in front of edge_cap, the pairs
+__global__ __launch_bounds__(1024) void span_emit_kernel(ReadBatch b, Pod5Reads pr, SpanOut so, const uint32_t* count, const uint64_t* scan,
+                                                         uint64_t* edge_first, uint32_t* edge, uint64_t edge_cap)
+{
+    __shared__ uint64_t wsum[16];
+    __shared__ uint32_t wmax[16];
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (pr.reads && *pr.bad) return;
+    const uint32_t i = blockIdx.x;
+    const uint64_t a = scan[i], z = scan[i + 1];
+    if (threadIdx.x == 0) {
+        edge_first[i] = a;
+        if (i + 1 == n) edge_first[n] = z;
+    }
+    if (count[i] == 0 || edge == nullptr) return;
+    if (z > edge_cap) {   // the read does not fit: not one word of edge
+        if (pr.reads) {
+            for (uint32_t r = pr.first_row[i] + threadIdx.x; r < pr.first_row[i + 1]; r += 1024) b.result[r] = E_DESTINATION_SIZE;
+            if (threadIdx.x == 0 && pr.read_result) pr.read_result[i] = E_DESTINATION_SIZE;
+        } else if (threadIdx.x == 0) {
+            b.result[i] = E_DESTINATION_SIZE;
+        }
+        return;
+    }
+    uint32_t T, rb, re;
+    (void)segment_passed(b, pr, i, &T);
+    span_range(b, pr, i, T, &rb, &re);
+    (void)span_walk<true>(reinterpret_cast<const uint32_t*>(so.map + so.map_off[i]), rb, re, so.D, so.m, wmax, wsum, edge + a, count[i] / 2u);   // (count[i] words: the same walk counted them)
+}
+
 }  // namespace
+
+hipError_t launch_span_emit(const ReadBatch& b, const Pod5Reads& pr, const SpanOut& so, const SegmentScratch& sc, uint64_t* edge_first, uint32_t* edge,
+                            uint64_t edge_cap, hipStream_t s)
+{
+    const uint32_t n = pr.reads ? pr.n_reads : b.n_reads;
+    if (n == 0) return hipMemsetAsync(edge_first, 0, 8, s);
+    hipLaunchKernelGGL(span_count_kernel, dim3(n), dim3(1024), 0, s, b, pr, so, sc.rows);
+    hipLaunchKernelGGL(segment_counts_kernel, dim3((n + TILE - 1) / TILE), dim3(1024), 0, s, b, pr, sc.rows, sc.scan, sc.count);
+    const hipError_t e = scan_launches(n, 1, sc.count, sc.scan, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(span_emit_kernel, dim3(n), dim3(1024), 0, s, b, pr, so, sc.count, sc.scan, edge_first, edge, edge_cap);
+    return hipGetLastError();
+}
 
 hipError_t launch_segment_layout(const ReadBatch& b, const Pod5Reads& pr, const SegmentScratch& sc, hipStream_t s)
 {

@@ -2333,16 +2333,178 @@ __global__ __launch_bounds__(WG) void svb16_trim_reads_kernel(ReadBatch b, Pod5R
     st.done();
 }
 
+// whether read i's map of ceil(T / 8) bytes lies inside the call's scratch: no byte of a map is written before this has passed
+__device__ __forceinline__ bool map_fits(const uint64_t* map_off, uint64_t map_cap, uint32_t i, uint32_t T)
+{
+    const uint64_t a = map_off[i], z = map_off[i + 1];
+    return z <= map_cap && a <= z && (uint64_t)((T + 7u) >> 3) <= z - a;   // (a map of ceil(T / 8) bytes: no byte is written outside it)
+}
+
+// ---- the span pass (vbz_kernels.h SpanOut; svb_store.h SpanStore), beside the trim pass and shaped like it ---------------------------------
+// Unlike the trim it walks every read to its end (every byte of the map gets its writer), and it runs in two settings.  Behind the
+// counting passes of a call with a normalisation (verdicts == 0) it owes no verdict: it reads result[] and walks the reads that have
+// none.  With the caller's constants no counting pass runs, and the pass writes the int16 decode's verdicts itself (verdicts != 0), as the
+// segmentation pass does.  The read's entry of the call's tables: segmentation's (rmap).
+__device__ __forceinline__ uint32_t span_entry(const SpanOut& so, uint32_t r) { return so.rmap ? so.rmap[r] : r; }
+
+// one workgroup per read: svb_decode_kernel's walk
+template <bool ZZ, bool I16ZZ>
+__global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_span_kernel(ReadBatch b, SpanOut so, uint32_t verdicts)
+{
+    const SvbDecLds<2, I16ZZ> lds;
+
+    const uint32_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    SvbRead rd;
+    uint32_t verdict;
+    if (!svb_read_open<2, I16ZZ>(b, r, &rd, &verdict)) {
+        if (verdicts) read_closed(b, r, verdict);
+        return;
+    }
+    if (!verdicts && b.result[r] >= E_FIRST) return;
+    const uint32_t count = rd.count, i = span_entry(so, r);
+    if (!map_fits(so.map_off, so.map_cap, i, count)) {
+        if (tid == 0) b.result[r] = E_OOM;
+        return;
+    }
+    uint32_t rb, re;
+    sample_range(b.sig, r, count, &rb, &re);
+    uint64_t pos = 0;
+    uint32_t run = 0;
+    const SpanStore<false> st(span_state(b, so, r, i, rb, re));
+    const bool good = svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, 0, count, pos, run, st, lds.stage, lds.wsum);
+    if (verdicts && tid == 0) b.result[r] = (!good || pos != rd.dataBytes) ? E_STREAM : count * 2u;
+}
+
+// The large-read path: svb_seg_decode_kernel's MODE 0 with the span sink, every segment of the read, no slab -- a segment begins at a
+// multiple of 16 384 samples, so its lanes own whole bytes of the map and store them plainly.  The verdict is that kernel's: the scan
+// launch's, or (SELF) written by the read's first workgroup from the announced lengths.
+template <bool ZZ, bool I16ZZ, bool SELF>
+__global__ __launch_bounds__(WG) void svb_seg_span_kernel(ReadBatch b, const uint32_t* seg_first, const uint32_t* seg_val, const uint64_t* seg_pos,
+                                                          const uint32_t* seg_run, SpanOut so)
+{
+    constexpr uint32_t SEG = WG * Vpl<2>::value * SEG_TILES;
+    const SvbDecLds<2, I16ZZ> lds;
+    __shared__ uint64_t sums_s[8];
+    uint32_t r, sg;
+    if (!seg_locate(seg_first, b.n_reads, blockIdx.x, r, sg)) return;
+    const int tid = threadIdx.x;
+    SvbRead rd;
+    uint32_t verdict;
+    const bool open = svb_read_open<2, I16ZZ>(b, r, &rd, &verdict);
+    uint64_t self_pos = 0, self_total = 0, self_run = 0;
+    if (SELF) {
+        seg_sums(seg_val, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_pos, self_total);
+        if (ZZ) {
+            uint64_t dummy;
+            seg_sums(seg_run, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_run, dummy);
+        }
+    }
+    const uint32_t i = span_entry(so, r);
+    const bool fits = !open || map_fits(so.map_off, so.map_cap, i, rd.count);
+    if (sg == 0 && tid == 0) {   // the read's verdict: one writer
+        uint32_t res0;
+        if (!fits) b.result[r] = E_OOM;
+        else if (SELF && svb_seg_read_result(open, rd, verdict, self_total, 2u, &res0)) b.result[r] = res0;
+    }
+    if (!open || !fits) return;
+    if (SELF) {
+        if (self_total != (uint64_t)rd.dataBytes) return;   // the stream is malformed
+    } else if (b.result[r] >= E_FIRST) return;              // the scan found it malformed (or a counting pass did)
+    const uint32_t count = rd.count, first = sg * SEG;
+    if (first >= count) return;
+    const uint32_t end = count - first > SEG ? first + SEG : count;
+    uint32_t rb, re;
+    sample_range(b.sig, r, count, &rb, &re);
+    uint64_t pos = SELF ? self_pos : seg_pos[blockIdx.x];
+    uint32_t run = ZZ ? (SELF ? (uint32_t)self_run : seg_run[blockIdx.x]) : 0u;
+    const SpanStore<false> st(span_state(b, so, r, i, rb, re));
+    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, first, end, pos, run, st, lds.stage, lds.wsum);
+}
+
+// a POD5 row as a read of its own
+__global__ __launch_bounds__(WG) void svb16_span_kernel(ReadBatch b, SpanOut so, uint32_t verdicts)
+{
+    const Svb16Lds lds;
+
+    const uint32_t r = blockIdx.x;
+    uint32_t in_size = 0, count = 0, verdict;
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
+        if (verdicts) read_closed(b, r, verdict);
+        return;
+    }
+    if (!verdicts && b.result[r] >= E_FIRST) return;
+    const uint32_t i = span_entry(so, r);
+    if (!map_fits(so.map_off, so.map_cap, i, count)) {
+        if (threadIdx.x == 0) b.result[r] = E_OOM;
+        return;
+    }
+    uint32_t rb, re;
+    sample_range(b.sig, r, count, &rb, &re);
+    const SpanStore<false> st(span_state(b, so, r, i, rb, re));
+    const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
+    if (verdicts && threadIdx.x == 0) b.result[r] = good ? count * 2u : E_STREAM;
+}
+
+// POD5 reads of several rows: one workgroup per READ walks its rows in turn, as svb16_trim_reads_kernel does (verdicts != 0: and writes
+// their verdicts, as svb16_segment_reads_kernel does).  A row may begin inside a map byte, so the workgroup zeroes the read's map and ORs
+// its bits in (SpanStore<true>).  A read with a failing row is not walked; a bad first_row leaves everything alone.
+__global__ __launch_bounds__(WG) void svb16_span_reads_kernel(ReadBatch b, Pod5Reads pr, SpanOut so, uint32_t verdicts)
+{
+    const Svb16Lds lds;
+
+    if (*pr.bad) return;
+    const uint32_t k = blockIdx.x;
+    const int tid = threadIdx.x;
+    const uint32_t first = pr.first_row[k], end = pr.first_row[k + 1];
+    const Pod5Read rd = pr.reads[k];
+    const bool failed = (rd.flags & POD5_READ_FAIL) != 0;   // (the plan has closed its rows' gates: every row has or gets that verdict)
+    const bool fits = map_fits(so.map_off, so.map_cap, k, rd.T);
+    if (failed || !fits) {
+        if (!verdicts && fits) return;
+        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) {
+            uint32_t in_size, count, verdict;
+            (void)svb16_row_open(b, r, &in_size, &count, &verdict);
+            if (verdict != GATE_SKIP) b.result[r] = failed || verdict >= E_FIRST ? verdict : E_OOM;
+        }
+        return;
+    }
+    if (!verdicts) {
+        int bad = 0;
+        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) bad |= b.result[r] >= E_FIRST ? 1 : 0;
+        if (__syncthreads_or(bad)) return;
+    }
+    uint32_t rb = 0, re = rd.T;
+    if (b.sig.ranged()) {
+        const uint2 g = pr.range[k];
+        rb = g.x;
+        re = g.y;
+    }
+    SpanStore<true> st(span_state(b, so, k, k, rb, re));
+    {
+        uint32_t* const w = reinterpret_cast<uint32_t*>(st.sk.map);
+        const uint32_t words = (((rd.T + 7u) >> 3) + 3u) >> 2;   // (map_off is a scan of sizes rounded up to 4: the words lie inside the read's map)
+        for (uint32_t j = (uint32_t)tid; j < words; j += WG) w[j] = 0;
+        __syncthreads();
+    }
+    for (uint32_t r = first; r < end; ++r) {
+        uint32_t in_size = 0, count = 0, verdict;
+        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
+            if (verdicts) read_closed(b, r, verdict);
+            continue;
+        }
+        st.begin_row(pr.rows[r].s0);   // (put() gets positions in the row)
+        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
+        if (verdicts && tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
+    }
+}
+
 // ---- the segmentation pass (vbz_kernels.h SegmentOut; svb_store.h SegmentStore) -----------------------------------------------------------
 // Kernels of their own, one workgroup per read on every path: the sink needs each sample's neighbourhood, and a workgroup that walks the
 // whole signal in order has it in LDS.  The verdicts are written here, as the int16 decode writes them (there is no counting pass in front).
 // The read's entry of the call's tables, and whether its map lies inside the scratch
 __device__ __forceinline__ uint32_t segment_entry(const SegmentOut& so, uint32_t r) { return so.rmap ? so.rmap[r] : r; }
-__device__ __forceinline__ bool segment_fits(const SegmentOut& so, uint32_t i, uint32_t T)
-{
-    const uint64_t a = so.map_off[i], z = so.map_off[i + 1];
-    return z <= so.map_cap && a <= z && (uint64_t)((T + 7u) >> 3) <= z - a;   // (a map of ceil(T / 8) bytes: no byte is written outside it)
-}
+__device__ __forceinline__ bool segment_fits(const SegmentOut& so, uint32_t i, uint32_t T) { return map_fits(so.map_off, so.map_cap, i, T); }
 
 // svb_decode_kernel's walk of an int16 read
 template <bool ZZ, bool I16ZZ>
@@ -2543,10 +2705,17 @@ hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, Init 
 // the segmented decode: MODE 1, then (SELF) MODE 2 and MODE 0, or the verdict scan, MODE 2 and its scan, and MODE 0; only MODE 0 stores
 template <int E, bool Z, bool I, int OUT>
 hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first, uint32_t max_segs, uint32_t* seg_val, uint64_t* seg_pos,
-                                   uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim)
+                                   uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim, const SpanOut* span)
 {
     const dim3 segs(max_segs), reads(b.n_reads), t(WG);
     const bool self = max_segs <= self_max;
+    auto span_pass = [&] {   // the span pass at the storing pass's positions (E == 2, OUT == SIG_NONE: launch_svb_decode_seg has looked)
+        if constexpr (E == 2) {
+            if (self) hipLaunchKernelGGL((svb_seg_span_kernel<Z, I, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *span);
+            else hipLaunchKernelGGL((svb_seg_span_kernel<Z, I, false>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *span);
+        }
+        return hipGetLastError();
+    };
     auto mode0 = [&](auto o) {
         if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
         else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
@@ -2581,8 +2750,9 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
             }
             return hipGetLastError();
         },
-        [&] {   // the trim pass at the same positions, behind it the scan launch
+        [&] {   // the trim pass at the same positions, behind it the scan launch (a span call: the span pass)
             if constexpr (E == 2) {
+                if (span) return span_pass();
                 if (!trim) return hipSuccess;
                 if (self) hipLaunchKernelGGL((svb_seg_trim_kernel<Z, I, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *trim);
                 else hipLaunchKernelGGL((svb_seg_trim_kernel<Z, I, false>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *trim);
@@ -2591,6 +2761,7 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
             return hipGetLastError();
         },
         &store);
+    if (span) return e == hipSuccess && !b.sig.norm.st ? span_pass() : e;   // (the caller's constants: the pass is all that runs behind the position passes)
     return e == hipSuccess && store ? mode0(Int<OUT>{}) : e;   // (no store: the statistics only)
 }
 
@@ -2626,9 +2797,16 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
     });
 }
 
-hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s, const TrimOut* trim)
+hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s, const TrimOut* trim, const SpanOut* span)
 {
     if (trim && (half || !b.sig.norm.st)) return hipErrorInvalidValue;
+    if (span && (half || integer_size != 2 || b.sig.type != SIG_NONE || trim)) return hipErrorInvalidValue;
+    if (span && b.n_reads == 0) return hipSuccess;
+    auto span_pass = [&](uint32_t verdicts) {
+        if (zigzag) hipLaunchKernelGGL((svb_span_kernel<true, true>), dim3(b.n_reads), dim3(WG), 0, s, b, *span, verdicts);
+        else hipLaunchKernelGGL((svb_span_kernel<false, false>), dim3(b.n_reads), dim3(WG), 0, s, b, *span, verdicts);
+        return hipGetLastError();
+    };
     if (half) {
         if (integer_size != 1 || b.sig.type != SIG_NONE) return hipErrorInvalidValue;
         return zigzag ? launch1(svb_half_decode_kernel<true>, b, s) : launch1(svb_half_decode_kernel<false>, b, s);
@@ -2638,12 +2816,14 @@ hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, 
         b, integer_size, false, [&] { return launch_norm_init(b, zigzag, s); }, [] { return hipSuccess; },
         [&] { return svb_dispatch_count(b, [&](auto out) { return svb_decode_launch<out()>(b, 2, zigzag, s); }); },
         [&] {
+            if (span) return span_pass(0u);
             if (!trim) return hipSuccess;
             if (zigzag) hipLaunchKernelGGL((svb_trim_kernel<true, true>), dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
             else hipLaunchKernelGGL((svb_trim_kernel<false, false>), dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
             return hipGetLastError();
         },
         &store);
+    if (span) return e == hipSuccess && !b.sig.norm.st ? span_pass(1u) : e;   // (the caller's constants: the pass is all that runs, verdicts included)
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return svb_decode_launch<out()>(b, integer_size, zigzag, s); });
 }
@@ -2656,10 +2836,15 @@ hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStr
     return hipGetLastError();
 }
 
-hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut* trim)
+hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut* trim, const SpanOut* span)
 {
     if (b.n_reads == 0) return hipSuccess;
     if (trim && !b.sig.norm.st) return hipErrorInvalidValue;
+    if (span && (b.sig.type != SIG_NONE || trim)) return hipErrorInvalidValue;
+    auto span_pass = [&](uint32_t verdicts) {
+        hipLaunchKernelGGL(svb16_span_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, *span, verdicts);
+        return hipGetLastError();
+    };
     bool store;   // the counting passes (each selects at its end: one workgroup per read), then the store
     const hipError_t e = norm_prepasses(
         b, 2, false,
@@ -2669,10 +2854,12 @@ hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut*
         },
         [] { return hipSuccess; }, [&] { return svb_dispatch_count(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); }); },
         [&] {
+            if (span) return span_pass(0u);
             if (trim) hipLaunchKernelGGL(svb16_trim_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
             return hipGetLastError();
         },
         &store);
+    if (span) return e == hipSuccess && !b.sig.norm.st ? span_pass(1u) : e;
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); });
 }
@@ -2724,11 +2911,13 @@ hipError_t launch_event_finish(const ReadBatch& b, const Pod5Reads& pr, const fl
 }
 
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s, const TrimOut* trim, const WindowScratch* win, void* event_out)
+                                     hipStream_t s, const TrimOut* trim, const WindowScratch* win, void* event_out, const SpanOut* span,
+                                     const SegmentScratch* spsc)
 {
     const uint32_t most = std::max(b.n_reads, pr.n_reads);
     if (most == 0) return hipSuccess;
-    if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st) || b.sig.norm.slab || (trim && !b.sig.norm.st)) return hipErrorInvalidValue;
+    if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st && !span) || b.sig.norm.slab || (trim && !b.sig.norm.st)) return hipErrorInvalidValue;
+    if (span && (!spsc || b.sig.type != SIG_NONE || trim || b.sig.wfirst || b.sig.row)) return hipErrorInvalidValue;
     const dim3 rows(b.n_reads), reads(pr.n_reads), t(WG);
     if (b.sig.ranged() && !pr.range) return hipErrorInvalidValue;
     if (b.sig.wfirst) {   // the plan with the first half of the window check, the second half, the pad
@@ -2740,6 +2929,10 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
         if (ew != hipSuccess) return ew;
     } else if (b.sig.ranged()) hipLaunchKernelGGL(pod5_reads_plan_range_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
     else hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, offset, scale, chunk_rows);
+    if (span) {   // (the maps' layout: from the reads' sample counts the plan has left)
+        const hipError_t el = launch_segment_layout(b, pr, *spsc, s);
+        if (el != hipSuccess) return el;
+    }
     const bool store = b.sig.type != SIG_NONE;
     if (b.sig.norm.st && pr.n_reads)
         for (uint32_t p = 0; p < norm_passes(b.sig.norm.method); ++p) {
@@ -2747,6 +2940,7 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
             else hipLaunchKernelGGL(svb16_count_reads_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
         }
     if (trim && pr.n_reads) hipLaunchKernelGGL(svb16_trim_reads_kernel, reads, t, 0, s, b, pr, *trim);
+    if (span && pr.n_reads) hipLaunchKernelGGL(svb16_span_reads_kernel, reads, t, 0, s, b, pr, *span, b.sig.norm.st ? 0u : 1u);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (b.n_reads) {
@@ -2836,13 +3030,15 @@ hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigz
 }
 
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
-                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim)
+                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim,
+                                 const SpanOut* span)
 {
     if (b.n_reads == 0) return hipSuccess;
     if (trim && !b.sig.norm.st) return hipErrorInvalidValue;
+    if (span && (integer_size != 2 || b.sig.type != SIG_NONE || b.sig.events || trim)) return hipErrorInvalidValue;
     return svb_dispatch_store(b, [&](auto out) {
         return svb_dispatch_elem<out() == SIG_NONE>(integer_size, zigzag, [&](auto e, auto z, auto i) {
-            return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, self_max, s, trim);
+            return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, self_max, s, trim, span);
         });
     });
 }

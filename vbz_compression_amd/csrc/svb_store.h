@@ -1346,6 +1346,87 @@ struct SegmentStore
     }
 };
 
+// ---- signal spans (vbz_kernels.h SpanOut; the rule: include/vbz_gpu.h) -------------------------------------------------------------------
+// The cheap sink: a position's bit depends on that sample alone -- no neighbourhood, no LDS, no barrier, no float arithmetic per sample.
+// Once per read the threshold becomes a pair of key bounds as trim_state makes hk (x = u - kx on the key u): ABOVE, float64(x) > thr is
+// u >= floor(thr) + 1 + kx; BELOW, float64(x) < thr is u < ceil(thr) + kx; each clamped to [0, 65536], a NaN thr giving the empty set.  Both
+// directions are one unsigned compare, u - lo < n.
+// The map is indexed by the sample's position in the READ (not in its range), so that a lane's eight samples are one byte wherever the
+// lane's values begin at a multiple of 8 of the read: on the one-workgroup walk (i0 = 8 x lane from 0) and in every segment of the
+// large-read path (segments begin at multiples of 16 384).  The invariant: every byte of a passing read's map has a defined value after
+// the pass, whatever the order in which workgroups run --
+//   SHARED == false (int16 reads on both paths; a POD5 row as a read): byte p / 8 has exactly one writer in the whole launch, the lane
+//   whose values begin at p, which stores it plainly, zeros too; the walk reaches the read's last sample, so ceil(T / 8) bytes are
+//   written and nothing zeroes the map in front.  The bits of a last byte behind T, and those outside [b + p0, e), are stored as 0.
+//   SHARED == true (POD5 reads of several rows, one workgroup per READ walking its rows: svb16_span_reads_kernel): a row that begins at
+//   s0 % 8 != 0 makes every lane's bits straddle two bytes, so no lane owns one.  The read's workgroup zeroes the read's map words
+//   itself, and behind a barrier the lanes OR their non-zero bits into the words (32-bit atomics: the map begins at a multiple of 4 and
+//   is rounded up to 4).  Only that workgroup touches the read's map, so the order of workgroups does not matter here either.
+// The emit launch masks the words to the range again, so the up to 3 bytes behind a map's last byte may hold anything.
+struct SpanK
+{
+    uint8_t* map = nullptr;   // the read's
+    uint32_t lo = 0, n = 0;   // in: u - lo < n
+    uint32_t kx = 0;
+    uint32_t pb = 0, pe = 0;  // the positions of the read that can be in: [b + p0, e), pb <= pe
+};
+
+// the state of read r (entry i of the call's tables) of samples [rb, re) whose constants are final
+__device__ __forceinline__ SpanK span_state(const ReadBatch& b, const SpanOut& so, uint32_t r, uint32_t i, uint32_t rb, uint32_t re)
+{
+    const NormOut& no = b.sig.norm;
+    SpanK k;
+    k.map = so.map + so.map_off[i];
+    k.kx = b.sig.bias ^ 0x8000u;
+    k.pe = re;
+    k.pb = so.p0 < re - rb ? rb + so.p0 : re;
+    const float2 aw = so.level ? so.level[i] : no.ss[no.map ? no.map[r] : r];
+    const double thr = __dadd_rn((double)aw.x, __dmul_rn((double)so.f, (double)aw.y));   // (multiply, then add: no FMA)
+    const double h = (so.below ? ceil(thr) : floor(thr) + 1.0) + (double)k.kx;   // the first key not below / above thr (exact where it is not clamped)
+    const uint32_t key = h >= 65536.0 ? 0x10000u : (h > 0.0 ? (uint32_t)h : 0u);
+    if (thr == thr) {
+        k.lo = so.below ? 0u : key;
+        k.n = so.below ? key : 0x10000u - key;
+    }
+    return k;
+}
+
+template <bool SHARED>
+struct SpanStore
+{
+    static constexpr uint32_t BYTES = 2;   // (result[] is the int16 decode's)
+    SpanK sk;
+    uint32_t s0 = 0;   // where the values handed to put() begin in the read (a POD5 read: row by row)
+    __device__ __forceinline__ explicit SpanStore(const SpanK& k) : sk(k) {}
+    __device__ __forceinline__ void begin_row(uint32_t s) { s0 = s; }
+    __device__ __forceinline__ bool aligned() const { return true; }   // (a byte a lane: any position)
+    __device__ __forceinline__ void put(uint32_t i0, int valid, uint32_t base, const uint32_t s[8]) const
+    {
+        if (valid <= 0) return;
+        uint32_t bits = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t u = ((base + s[k]) ^ sk.kx) & 0xFFFFu;
+            bits |= (u - sk.lo < sk.n ? 1u : 0u) << k;
+        }
+        const uint32_t p = s0 + i0;   // the position of bit 0 in the read
+        uint32_t keep = 0xFFu >> (8 - valid);
+        if (p < sk.pb) keep &= sk.pb - p >= 8u ? 0u : 0xFFu << (sk.pb - p);
+        if (p + 8u > sk.pe) keep &= sk.pe > p ? 0xFFu >> (8u - (sk.pe - p)) : 0u;
+        bits &= keep;
+        if constexpr (!SHARED) {
+            sk.map[p >> 3] = (uint8_t)bits;   // (p % 8 == 0: the lane's own byte)
+        } else if (bits) {
+            uint32_t* const w = reinterpret_cast<uint32_t*>(sk.map) + (p >> 5);
+            const uint64_t v = (uint64_t)bits << (p & 31u);
+            if ((uint32_t)v) atomicOr(w, (uint32_t)v);
+            if ((uint32_t)(v >> 32)) atomicOr(w + 1, (uint32_t)(v >> 32));   // (set bits lie in front of pe <= T: inside the map)
+        }
+    }
+    __device__ __forceinline__ void finish() const {}
+    __device__ __forceinline__ void done() const {}
+};
+
 // The selection and the builder in one: the sink of read r of `count` values for the whole-read and segment kernels' OUT.  | SIG_RANGE (the
 // chunk and window sinks and SIG_COUNT): the read is its samples [b, e).  b: the batch, for the typed stores only -- SIG_NONE gets nullptr
 // and the batch's fields (a reference to the kernel's ReadBatch argument would cost its loads their scalar form).  cr: whose constants

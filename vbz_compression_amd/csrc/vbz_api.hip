@@ -867,18 +867,19 @@ int svb_decode_stage(vbz_gpu_ctx* c, const DecodeJob& j, const CompressionOption
 {
     Timed t(c, "svb_decode");
     const TrimOut* const trim = j.trim.begin ? &j.trim : nullptr;
+    const SpanOut* const span = j.span.map ? &j.span : nullptr;   // (a span call: the span pass, on the segments of the large-read path too -- DESIGN.md 4.21)
     if (j.seg.map) {   // (a segmentation call: kernels of their own, one workgroup per read on every path -- DESIGN.md 4.20)
         if (pod5_codec(o)) HIPCHK(c, launch_svb16_segment(j.rb, j.seg, c->stream), "svb16 segment launch");
         else HIPCHK(c, launch_svb_segment(j.rb, o->perform_delta_zig_zag, j.seg, c->stream), "svb segment launch");
         return 0;
     }
     if (pod5_codec(o))   // (one workgroup per read on every path: DESIGN.md 4.13)
-        HIPCHK(c, launch_svb16_decode(j.rb, c->stream, trim), "svb16_decode launch");
+        HIPCHK(c, launch_svb16_decode(j.rb, c->stream, trim, span), "svb16_decode launch");
     else if (segmented)
-        HIPCHK(c, launch_svb_decode_seg(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->knobs.seg_self_max, c->stream, trim),
+        HIPCHK(c, launch_svb_decode_seg(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, seg.first, seg.max_segs, seg.val, seg.off, seg.run, c->knobs.seg_self_max, c->stream, trim, span),
                "svb_decode (segmented) launch");
     else
-        HIPCHK(c, launch_svb_decode(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream, trim), "svb_decode launch");
+        HIPCHK(c, launch_svb_decode(j.rb, (int)o->integer_size, o->perform_delta_zig_zag, half_codec(o), c->stream, trim, span), "svb_decode launch");
     return 0;
 }
 
@@ -1024,7 +1025,8 @@ int inherit_half(vbz_gpu_ctx* c)
     return 0;
 }
 
-int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed* r, const TrimOut& trim = {}, const SegmentOut& seg = {})
+int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed* r, const TrimOut& trim = {}, const SegmentOut& seg = {},
+          const SpanOut& span = {})
 {
     const uint32_t n = rb.n_reads;
     if (inherit_large(c) != 0) return -1;
@@ -1055,6 +1057,8 @@ int route(vbz_gpu_ctx* c, const ReadBatch& rb, const uint32_t* raw_size, Routed*
     if (rb.sig.wfirst) g.sig.wmap = r->map;     // (and their windows)
     r->large.trim = trim, r->large.seg = seg;   // (a decompress call's trim and segmentation: the routed reads share them)
     if (seg.map) r->large.seg.rmap = r->map;    // (their boundary maps and row counts: through the map too)
+    r->large.span = span;                       // (a span call's rule and tables, likewise)
+    if (span.map) r->large.span.rmap = r->map;
     Timed t(c, "route");
     a.raw_size = raw_size;
     a.min_bytes = ROUTE_MIN_BYTES;
@@ -1147,9 +1151,11 @@ ReadBatch upper_half(const ReadBatch& rb, uint32_t h)
 }
 DecodeJob upper_half(const DecodeJob& job, uint32_t h)   // (the same cut of a decompress job: its own per-read tables move with the batch's)
 {
-    DecodeJob u{ upper_half(job.rb, h), job.trim, job.seg };
+    DecodeJob u{ upper_half(job.rb, h), job.trim, job.seg, job.span };
     if (u.trim.begin) u.trim.begin += h;
     if (u.seg.map) u.seg.map_off += h, u.seg.rows += h;
+    if (u.span.map) u.span.map_off += h;
+    if (u.span.level) u.span.level += h;
     return u;
 }
 
@@ -1561,6 +1567,54 @@ SegmentOut segment_out(const vbz_gpu_segmentation* g)
     return so;
 }
 
+// the spans' fields (include/vbz_gpu.h) and their two tables; level: given exactly when there is no normalisation
+static_assert(SPAN_ABOVE == VBZ_GPU_SPAN_ABOVE && SPAN_BELOW == VBZ_GPU_SPAN_BELOW, "the ABI's span directions");
+static_assert(sizeof(vbz_gpu_spans) == 40, "vbz_gpu_spans is 40 bytes");
+static_assert(offsetof(vbz_gpu_spans, direction) == 0 && offsetof(vbz_gpu_spans, merge_gap) == 4 && offsetof(vbz_gpu_spans, min_length) == 8 &&
+                  offsetof(vbz_gpu_spans, ignore_prefix) == 12 && offsetof(vbz_gpu_spans, threshold_factor) == 16 && offsetof(vbz_gpu_spans, flags) == 20 &&
+                  offsetof(vbz_gpu_spans, level) == 24 && offsetof(vbz_gpu_spans, edge_cap) == 32,
+              "the fields of vbz_gpu_spans");
+bool spans_ok(vbz_gpu_ctx* c, const vbz_gpu_spans* g, const uint64_t* edge_first, const uint32_t* edge, bool with_norm)
+{
+    if (!g || !edge_first) {
+        set_error(c, "spans or edge_first is NULL");
+        return false;
+    }
+    if (!edge && g->edge_cap != 0) {
+        set_error(c, "edge is NULL with edge_cap %llu (the count-only call: NULL and 0)", (unsigned long long)g->edge_cap);
+        return false;
+    }
+    const bool fields = g->direction <= VBZ_GPU_SPAN_BELOW && g->merge_gap <= SPAN_GAP_MAX && g->min_length >= 1 && g->min_length <= SPAN_LENGTH_MAX &&
+                        std::isfinite(g->threshold_factor) && g->flags == 0;
+    if (!fields) {
+        set_error(c, "spans outside their rules (direction %u, merge_gap %u, min_length %u, threshold_factor %g, flags %u)", g->direction, g->merge_gap,
+                  g->min_length, (double)g->threshold_factor, g->flags);
+        return false;
+    }
+    if ((g->level != nullptr) == with_norm) {
+        set_error(c, with_norm ? "spans: level must be NULL with a normalisation (the statistics give the constants)"
+                               : "spans: level is NULL and there is no normalisation");
+        return false;
+    }
+    if (g->edge_cap > EXTENT_MAX / sizeof(uint32_t)) {
+        set_error(c, "declared edge table is not plausible (%llu entries of 4 bytes)", (unsigned long long)g->edge_cap);
+        return false;
+    }
+    return true;
+}
+// the rule's part of SpanOut (the map and its offsets: the call's scratch, typed_outputs)
+SpanOut span_out(const vbz_gpu_spans* g)
+{
+    SpanOut so;
+    so.level = reinterpret_cast<const float2*>(g->level);
+    so.below = g->direction == VBZ_GPU_SPAN_BELOW ? 1u : 0u;
+    so.D = g->merge_gap;
+    so.m = g->min_length;
+    so.p0 = g->ignore_prefix;
+    so.f = g->threshold_factor;
+    return so;
+}
+
 // POD5 reads of several rows (o nullable: a call without options)
 static_assert(sizeof(vbz_gpu_pod5_reads) == 24, "vbz_gpu_pod5_reads is 24 bytes");
 bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_pod5_reads* reads)
@@ -1578,9 +1632,10 @@ bool pod5_reads_ok(vbz_gpu_ctx* c, const CompressionOptions* o, const vbz_gpu_po
 
 // TypedCall: one typed decode as its entry point states it (the table of entries: in front of them, below).  A part the entry does not
 // have keeps its default.  Where the entries' rules for a NULL differ, the entry says which one holds (Null); it is not inferred.
-enum class Typed { SIGNAL, CHUNKS, STATISTICS, EVENTS, SEGMENT };   // what is stored: typed samples in the reads' slots; in chunks; nothing (the
+enum class Typed { SIGNAL, CHUNKS, STATISTICS, EVENTS, SEGMENT, SPANS };   // what is stored: typed samples in the reads' slots; in chunks; nothing (the
                                                                     // constants alone); one record per caller-listed event; nothing in the
-                                                                    // reads' slots either -- every read's event starts, found on the device
+                                                                    // reads' slots either -- every read's event starts, found on the device;
+                                                                    // the same for every read's spans above or below its level
 enum class Null { ALLOWED, REFUSED, REFUSED_WITH_READS };   // REFUSED_WITH_READS: refused unless the call has no read to write an entry for
 struct TypedCall
 {
@@ -1611,6 +1666,9 @@ struct TypedCall
     const vbz_gpu_segmentation* seg = nullptr;       // SEGMENT (is_signed as for STATISTICS): the rule, and the two tables the call fills --
     uint64_t* seg_first = nullptr;                   // ... event_first and start, the layout a vbz_gpu_events reads
     uint32_t* seg_start = nullptr;
+    const vbz_gpu_spans* spans = nullptr;            // SPANS (is_signed as for STATISTICS; norm nullable: the constants are then spans->level): the
+    uint64_t* edge_first = nullptr;                  // ... rule, and the two tables the call fills -- edge_first and edge, which a vbz_gpu_events
+    uint32_t* edge = nullptr;                        // ... reads as event_first and start
 
     TypedCall(Typed k, int s) : kind(k), sized(s) {}
     TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
@@ -1639,6 +1697,7 @@ struct TypedCall
     TypedCall& pod5_reads(const vbz_gpu_pod5_reads* r) { pod5 = true, reads = r; return *this; }
     TypedCall& trimmed(const vbz_gpu_trim* t, uint32_t* b) { with_trim = true, trim = t, begin = b; return *this; }
     TypedCall& segmented(const vbz_gpu_segmentation* g, uint64_t* first, uint32_t* start) { seg = g, seg_first = first, seg_start = start; return *this; }
+    TypedCall& spanned(const vbz_gpu_spans* g, uint64_t* first, uint32_t* e) { spans = g, edge_first = first, edge = e; return *this; }
 };
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
@@ -1715,6 +1774,14 @@ int typed_outputs(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const TypedCall& t, D
         j->seg.map_off = sc->seg.map_off, j->seg.rows = sc->seg.rows;
         break;
     }
+    case Typed::SPANS: {   // segmentation's tables and maps (launch_segment_layout lays them out, the carve sizes them)
+        const uint64_t map_cap = *dst_bytes / 16 + 4ull * n_const + 64;
+        uint8_t* const map = ensure_carved(c, c->segmtab, sc->seg, n_const) ? ensure_array<uint8_t>(c, c->segmap, map_cap) : nullptr;
+        if (!map) return -1;
+        j->span = span_out(t.spans);
+        j->span.map = map, j->span.map_cap = map_cap, j->span.map_off = sc->seg.map_off;
+        break;
+    }
     }
     if (t.reads) cal = sc->cal;   // (else, but for SIGNAL: the constants' table is chunk_slots' or the selects' to fill)
     else if (t.kind != Typed::SIGNAL && !(cal = ensure_array<float2>(c, c->sigmeta, n))) return -1;
@@ -1739,7 +1806,7 @@ int typed_front(vbz_gpu_ctx* c, const TypedCall& t, const ReadBatch& rb, const C
         Timed tm(c, "chunk_slots");
         HIPCHK(c, launch_chunk_slots(rb.n_reads, rb.dst_cap, t.f->offset, t.f->scale, rb.sig.chunk_len, rb.sig.step, t.chunk_first, t.chunk_rows,
                                      sc.cal, const_cast<uint32_t*>(rb.gate), &rb.sig, c->stream), "chunk slots launch");
-    } else if (t.kind == Typed::SEGMENT) {   // (the maps' layout)
+    } else if (t.kind == Typed::SEGMENT || t.kind == Typed::SPANS) {   // (the maps' layout)
         Timed tm(c, "segment_layout");
         HIPCHK(c, launch_segment_layout(rb, Pod5Reads(), sc.seg, c->stream), "segment layout launch");
     }
@@ -1755,6 +1822,9 @@ int typed_finish(vbz_gpu_ctx* c, const TypedCall* t, const DecodeJob& j, const P
     if (t->kind == Typed::SEGMENT) {   // (count, scan and emit)
         if (!pr.reads) tm.emplace(c, "segment_emit");
         HIPCHK(c, launch_segment_emit(j.rb, pr, j.seg, sc.seg, t->seg_first, t->seg_start, t->seg->start_cap, c->stream), "segment emit launch");
+    } else if (t->kind == Typed::SPANS) {   // (count, scan and emit)
+        if (!pr.reads) tm.emplace(c, "span_emit");
+        HIPCHK(c, launch_span_emit(j.rb, pr, j.span, sc.seg, t->edge_first, t->edge, t->spans->edge_cap, c->stream), "span emit launch");
     } else if (t->kind == Typed::EVENTS) {   // (the records)
         tm.emplace(c, "event_finish");
         HIPCHK(c, launch_event_finish(j.rb, pr, t->f->offset, t->f->scale, sc.win, t->ev_out, c->stream), "event finish launch");
@@ -1772,6 +1842,7 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     const vbz_gpu_pod5_reads* const reads = out ? out->reads : nullptr;
     hipStream_t s = c->stream;
     if (out && out->kind == Typed::SEGMENT && (reads ? reads->n_reads : n) == 0) HIPCHK(c, hipMemsetAsync(out->seg_first, 0, 8, s), "event_first of no reads");
+    if (out && out->kind == Typed::SPANS && (reads ? reads->n_reads : n) == 0) HIPCHK(c, hipMemsetAsync(out->edge_first, 0, 8, s), "edge_first of no reads");
     if (n == 0 && !(reads && reads->n_reads)) return 0;
     DecodeJob job{ to_rb(bt) };
     ReadBatch& rb = job.rb;
@@ -1821,14 +1892,14 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
             return typed_finish(c, out, streams, pr, sc, 0);
         }
         HIPCHK(c, launch_svb16_decode_reads(streams.rb, pr, out->f->offset, out->f->scale, out->chunk_rows, s, streams.trim.begin ? &streams.trim : nullptr,
-                                            sc.win.scan ? &sc.win : nullptr, out->ev_out),
+                                            sc.win.scan ? &sc.win : nullptr, out->ev_out, streams.span.map ? &streams.span : nullptr, &sc.seg),
                "svb16_decode (reads) launch");
-        return 0;
+        return streams.span.map ? typed_finish(c, out, streams, pr, sc, 0) : 0;   // (a span call: count, scan and emit behind the pass over reads)
     }
     if (by_shape || !routing_applies(c, o, dst_bytes, n))
         return typed_finish(c, out, job, pr, sc, split ? decompress_split(c, job, dst_bytes, o) : decompress_group(c, job, dst_bytes, o, by_shape));
     Routed r;
-    if (route(c, rb, rb.dst_cap, &r, job.trim, job.seg) != 0) return -1;   // by the decoded size
+    if (route(c, rb, rb.dst_cap, &r, job.trim, job.seg, job.span) != 0) return -1;   // by the decoded size
     DecodeJob small = job;
     small.rb.gate = r.gate_small;
     int rc = 0;   // (as in compress_batch_impl: the second stream is joined whatever happens)
@@ -1843,11 +1914,11 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
 // message; with several, the first in this order.
 int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const TypedCall& call)
 {
-    static const char* const WHAT[] = { "signal", "chunk", "statistics", "event", "segmentation" };
+    static const char* const WHAT[] = { "signal", "chunk", "statistics", "event", "segmentation", "span" };
     if (!c || !bt) return -1;                                                                                        // 1
     DeviceGuard dg(c->device);                                                                                       // 2
     TypedCall t = call;
-    const bool stats = t.kind == Typed::STATISTICS || t.kind == Typed::SEGMENT;   // (no format: is_signed alone)
+    const bool stats = t.kind == Typed::STATISTICS || t.kind == Typed::SEGMENT || t.kind == Typed::SPANS;   // (no format: is_signed alone)
     const bool type_ok = stats || (t.f && t.f->out_type >= VBZ_GPU_SIGNAL_F32 && t.f->out_type <= VBZ_GPU_SIGNAL_BF16);
     if (!typed_args_ok(c, o, t.sized, WHAT[(int)t.kind], type_ok, stats ? t.is_signed : t.f ? t.f->is_signed : 0u)) return -2;   // 3
     if (t.pod5 && !pod5_reads_ok(c, o, t.reads)) return -2;                                                         // 4
@@ -1856,6 +1927,7 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     const uint32_t n_out = t.pod5 ? t.reads->n_reads : bt->n_reads;   // the reads the per-read tables have an entry for
     if (t.with_trim && !trim_ok(c, t.trim, t.begin)) return -2;                                                      // 7
     if (t.kind == Typed::SEGMENT && !segmentation_ok(c, t.seg, t.seg_first, t.seg_start)) return -2;                 // 7 (a segmentation in the trim's place)
+    if (t.kind == Typed::SPANS && !spans_ok(c, t.spans, t.edge_first, t.edge, t.norm != nullptr)) return -2;         // 7 (spans, likewise)
     if (!t.shift_scale && (t.shift_scale_null == Null::REFUSED || (t.shift_scale_null == Null::REFUSED_WITH_READS && n_out != 0))) {
         set_error(c, "shift_scale is NULL");
         return -2;
@@ -2093,7 +2165,7 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
     return 0;
 }
 
-// The twenty typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
+// The twenty-two typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
 //
 //   vbz_gpu_..._batch             kind        sized  chunking  norm      shift_scale          ranges    reads  trim   (chunking "windows": a
 //                                                                                                                   vbz_gpu_windows in its place;
@@ -2118,6 +2190,8 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   pod5_signal_norm_range        STATISTICS  0      -         required  required with reads  nullable  yes    -
 //   pod5_signal_trim              STATISTICS  0      -         required  nullable             nullable  yes    yes
 //   pod5_signal_segment           SEGMENT     0      -         -         -                    nullable  yes    segmentation
+//   signal_spans                  SPANS       arg    -         nullable  nullable             nullable  -      spans (in the trim's place)
+//   pod5_signal_spans             SPANS       0      -         nullable  nullable             nullable  yes    spans
 //
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
@@ -2129,6 +2203,8 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   the event entries: event_first, start (with event_rows != 0) and the event arena.
 // - the segmentation entries: event_first is never NULL (a call of no reads writes event_first[0]); start is NULL exactly in the
 //   count-only call (start_cap == 0).
+// - the span entries: edge_first and edge, likewise; norm NULL means the constants are the caller's (spans->level, which must then be
+//   there and must not be otherwise); a shift_scale without a norm is ignored.
 int vbz_gpu_decompress_signal_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::SIGNAL, sized).format(f));
@@ -2274,6 +2350,22 @@ int vbz_gpu_pod5_signal_segment_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, c
 {
     return typed_decode(c, bt, o, TypedCall(Typed::SEGMENT, 0).statistics(is_signed).pod5_reads(reads).range(ranges)
                                       .segmented(segmentation, event_first, start));
+}
+
+int vbz_gpu_signal_spans_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, uint32_t is_signed,
+                               const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_spans* spans,
+                               uint64_t* edge_first, uint32_t* edge)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::SPANS, sized).statistics(is_signed).normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED)
+                                      .range(ranges).spanned(spans, edge_first, edge));
+}
+
+int vbz_gpu_pod5_signal_spans_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, uint32_t is_signed,
+                                    const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
+                                    const vbz_gpu_sample_ranges* ranges, const vbz_gpu_spans* spans, uint64_t* edge_first, uint32_t* edge)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::SPANS, 0).statistics(is_signed).pod5_reads(reads).normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED)
+                                      .range(ranges).spanned(spans, edge_first, edge));
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

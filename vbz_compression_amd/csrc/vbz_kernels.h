@@ -113,6 +113,7 @@ struct TrimOut
     uint32_t W = 0, m = 0, t0 = 0, M = 0, flags = 0;
     float f = 0.0f, max_fraction = 1.0f;
 };
+struct SpanOut;   // (signal spans: below, beside SegmentOut)
 
 // the clamped range of read r of T samples: *rb <= *re <= T (no address is formed from a table value before this)
 __device__ inline void sample_range(const SignalOut& sg, uint32_t r, uint32_t T, uint32_t* rb, uint32_t* re)
@@ -251,13 +252,16 @@ bool svb_encode_fills_plans(int integer_size, bool zigzag, bool half);   // does
 // b.sig.rbegin / rend (the chunk stores and the counting passes only; launch_svb16_decode and launch_svb_decode_seg too): the ranged
 // instantiations (OUT | SIG_RANGE) store the chunks of every read's clamped range, and with rstats == RANGE_STATS_RANGE count its values alone.
 // trim (nullable; with b.sig.norm.st only; every decode launcher below too): the trim pass behind the last counting pass.
-hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s, const TrimOut* trim = nullptr);
+// span (nullable; int16 samples, b.sig.type == SIG_NONE; every decode launcher below too): the span pass -- behind the last counting pass with
+// b.sig.norm.st, where result[] is the counting passes'; else it is all that runs and writes the int16 decode's verdicts itself.
+hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s, const TrimOut* trim = nullptr,
+                             const SpanOut* span = nullptr);
 // svb16, the svb stage of POD5 signal rows (int16 samples, delta + zig-zag; one key bit per sample): one workgroup per read, on every
 // path.  Encode: the worst case ceil(n / 8) + 2n must fit dst_cap (else E_DESTINATION_SIZE); period_hint (nullable) is zeroed (no
 // matcher).  Decode: the stores of launch_svb_decode(2, zigzag) (b.sig; b.sig.norm.slab must be NULL); a stream longer than
 // ceil(n / 8) + 2n is E_ZSTD, one whose length the key bits do not announce E_STREAM.
 hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStream_t s);
-hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut* trim = nullptr);
+hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut* trim = nullptr, const SpanOut* span = nullptr);
 // key_raw[i]: the raw size whose key region at key_elem = 4 is svb16's ceil(n / 8) bytes (the entropy stage's orig_size for POD5, hdr 0)
 hipError_t launch_svb16_key_raw(uint32_t n, const uint32_t* raw_size, uint32_t* key_raw, hipStream_t s);
 constexpr uint32_t SVB16_KEY_ELEM = 4;
@@ -334,8 +338,25 @@ struct SegmentOut
     uint32_t w1 = 1, w2 = 0, r = 1;      // the two windows (w2 0: one detector) and the radius
     double k1 = 1.0, k2 = 1.0;           // float64(t) * float64(t) of the two thresholds (exact: 48 bits)
 };
+// Signal spans (vbz_gpu_*_signal_spans_batch; the rule: include/vbz_gpu.h): a pass of the svb decoder (svb_store.h: SpanStore) compares every
+// sample of a read with the read's threshold thr = a + f w and leaves the verdicts as one bit per position OF THE READ in the read's map --
+// launch_segment_layout's, bytes [map_off[i], map_off[i] + ceil(T / 8)) of `map`; bit p is set when p lies in [b + p0, e) and sample p is in
+// -- and launch_span_emit (pack.hip) merges, filters and writes the pairs.  {a, w}: level[i], or with level == nullptr the read's
+// {shift, scale} of b.sig.norm.ss, behind the last counting pass.  i, rmap and the cut of a split call: as for SegmentOut.
+constexpr uint32_t SPAN_ABOVE = 0, SPAN_BELOW = 1;   // (= VBZ_GPU_SPAN_*)
+constexpr uint32_t SPAN_GAP_MAX = 65535, SPAN_LENGTH_MAX = 0x7FFFFFFFu;
+struct SpanOut
+{
+    uint8_t* map = nullptr;              // nullptr: not a span call
+    const uint64_t* map_off = nullptr;   // [n + 1], multiples of 4 (launch_segment_layout)
+    uint64_t map_cap = 0;
+    const uint32_t* rmap = nullptr;
+    const float2* level = nullptr;       // the caller's {a, w} per read, or nullptr: the statistics'
+    uint32_t below = 0, D = 0, m = 1, p0 = 0;
+    float f = 0.0f;
+};
 // One launch group of a decompress call on the host (no kernel sees it).  What cuts a call into groups cuts the job (vbz_api.hip: upper_half, route).
-struct DecodeJob { ReadBatch rb; TrimOut trim; SegmentOut seg; };   // trim.begin == nullptr / seg.map == nullptr: none
+struct DecodeJob { ReadBatch rb; TrimOut trim; SegmentOut seg; SpanOut span; };   // trim.begin == nullptr / seg.map == nullptr / span.map == nullptr: none
 // The tables of a segmentation call, per read of the call (POD5 reads of several rows: per READ): the maps' sizes and offsets, the sinks'
 // row counts, the counts of the reads that passed and their scan.
 struct SegmentScratch
@@ -371,6 +392,13 @@ hipError_t launch_segment_emit(const ReadBatch& b, const Pod5Reads& pr, const Se
 hipError_t launch_svb_segment(const ReadBatch& b, bool zigzag, const SegmentOut& so, hipStream_t s);
 hipError_t launch_svb16_segment(const ReadBatch& b, const SegmentOut& so, hipStream_t s);
 hipError_t launch_svb16_segment_reads(const ReadBatch& b, const Pod5Reads& pr, const SegmentOut& so, const SegmentScratch& sc, hipStream_t s);
+// launch_span_emit (pack.hip), behind everything a span call has queued: one workgroup per read walks the read's map (the bits of its
+// range [b, e)), merging in-positions at most so.D apart and dropping spans shorter than so.m -- sc.rows[i] = twice the spans of a read
+// whose result (POD5: every row's) is no error, else 0; their scan; then the same walk writes edge_first[i] (the last one edge_first[n]
+// too) and, where the read's pairs end at or in front of edge_cap, its {begin, end} pairs in positions of the signal -- else
+// E_DESTINATION_SIZE to its result (POD5: its rows' and read_result).  edge == nullptr: edge_first alone.  A bad first_row: nothing.
+hipError_t launch_span_emit(const ReadBatch& b, const Pod5Reads& pr, const SpanOut& so, const SegmentScratch& sc, uint64_t* edge_first, uint32_t* edge,
+                            uint64_t edge_cap, hipStream_t s);
 // row j of the rows counted in scan (n + 1 offsets, scan[0] = 0 <= j < scan[n]) -> its read: the last k with scan[k] <= j
 __device__ inline uint32_t scan_find(const uint64_t* scan, uint32_t n, uint64_t j)
 {
@@ -396,8 +424,10 @@ hipError_t launch_pod5_read_samples(const Pod5Reads& pr, const uint32_t* row_sam
 // pass gives the rows' verdicts), the read results.  b.sig.rbegin / rend: per READ; pr.range must then be set (the plan fills it).
 // b.sig.wfirst (a window call; b.sig.row must be NULL): win must be set; the window check and the pad launch follow the plan.
 // b.sig.events (an event call): the same with the zero launch in the pad's place, and the finish launch into event_out behind the passes.
+// span (a span call; spsc must be set): the maps' layout behind the plan, the span pass over reads behind the counting passes.
 hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, const float* offset, const float* scale, uint64_t chunk_rows,
-                                     hipStream_t s, const TrimOut* trim = nullptr, const WindowScratch* win = nullptr, void* event_out = nullptr);
+                                     hipStream_t s, const TrimOut* trim = nullptr, const WindowScratch* win = nullptr, void* event_out = nullptr,
+                                     const SpanOut* span = nullptr, const SegmentScratch* spsc = nullptr);
 // The same stage with one read spread over many workgroups ("segments" of svb_seg_unit_bytes raw bytes), for batches of few,
 // large reads (one 10 M-element buffer, one 400 k-sample read): seg_first[n_reads + 1] from launch_seg_plan; max_segs
 // bounds the total segment count (the grid); seg_* are scratch arrays of max_segs entries.  Not for the nibble codec.
@@ -407,7 +437,8 @@ uint32_t svb_seg_unit_bytes(int integer_size);
 hipError_t launch_svb_encode_seg(const ReadBatch& b, int integer_size, bool zigzag, uint32_t hdr, bool strict_cap, const uint32_t* seg_first,
                                  uint32_t max_segs, uint32_t* seg_bytes, uint64_t* seg_off, uint32_t self_max, hipStream_t s);
 hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigzag, const uint32_t* seg_first, uint32_t max_segs,
-                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim = nullptr);
+                                 uint32_t* seg_val, uint64_t* seg_pos, uint32_t* seg_run, uint32_t self_max, hipStream_t s, const TrimOut* trim = nullptr,
+                                 const SpanOut* span = nullptr);
 
 // ---- zstd-format entropy stage (zstd_encode.hip / zstd_decode.hip) -----------------------------
 // encode: frame content = src read.  The launchers' arguments are host-side aggregates, filled field by field; what is not set is not used.
