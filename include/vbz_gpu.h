@@ -740,6 +740,85 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_spans_batch(vbz_gpu_ctx* ctx, const vbz_gpu_b
                                                float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_spans* spans,
                                                uint64_t* edge_first, uint32_t* edge);
 
+/* Signal match.  Finding a known squiggle inside the start of every read: signal-space barcode demultiplexing, adapter location and target
+ * filtering all reduce to it.  The calls below run a subsequence DTW of every read's quantised, normalised prefix against every row of a
+ * matrix of reference squiggles, on the device.  This library was written without the source of any demultiplexer or squiggle filter: the
+ * rule below is the contract (tests/match_ref.py).
+ * Query.  The signal is the read's samples x[b:e) of T' = e - b values, ranges clamped exactly as in the *_range_batch calls.  The query
+ * is its first n = min(T', N) samples, N = query_len.  Sample j is converted as the windows call converts it: z_j = ((float)x_j + o) * s in
+ * float32, each operation rounded to nearest even, none fused; o and s are format->offset / scale when norm is NULL, otherwise the read's
+ * own statistics exactly as in the *_norm calls (o = -shift, s = float32(1 / float64(scale)); ranges->stats has its meaning).  It is then
+ * quantised: v = z_j * quant (one float32 multiply, RNE); k_j = 0 when v is NaN, otherwise clamp(rint(v), -127, 127), rint to nearest
+ * even, +-inf giving +-127.  quant is a finite float32 > 0 (levels per unit; 32 suits MAD-normalised signal).
+ * References.  R = n_refs rows of int8 in a device matrix ref[R][ref_stride]; row r has M_r = ref_len[r] valid entries, values taken as
+ * they are (-128 is legal).  ref_len is an untrusted device table: M_r == 0 or M_r > ref_stride makes column r of the output
+ * {0xFFFFFFFF, 0} for every read, and no address is formed from it.
+ * Cost.  For reference r_0 ... r_{M-1} and query k_0 ... k_{n-1}, c(i, j) = |r_i - k_j|, in integers:
+ *   D[0][j] = c(0, j)                                             (the alignment may start anywhere in the query)
+ *   D[i][0] = c(i, 0) + D[i-1][0]
+ *   D[i][j] = c(i, j) + min(D[i-1][j-1], D[i-1][j], D[i][j-1])
+ *   cost = min_j D[M-1][j]                                        (it may end anywhere)
+ *   end = 1 + the SMALLEST j that attains it
+ * The whole reference is aligned to a stretch of the query that ends at `end` (exclusive).  D[i][j] <= 255 (i + 1) < 2^20, so nothing
+ * wraps; integer minima do not depend on evaluation order, so the answer is reproducible bit for bit.  n == 0 gives {0xFFFFFFFF, 0}; so
+ * does an empty range, and so does a read whose verdict is an error.
+ * Output.  out is a row-major [n_reads, R] arena of vbz_gpu_match_hit (8 bytes), 16-byte aligned.  EVERY entry is written by every call
+ * that launches; nothing else is written, apart from query and shift_scale.
+ * vbz_gpu_match_batch is the stage-level entry: query is a row-major [n_reads, N] float32 arena, 16-byte aligned -- exactly what the
+ * windows call writes for one window per read -- and valid[i] (device, untrusted) is clamped to N; 0 gives the empty verdict.
+ * vbz_gpu_signal_match_batch and its POD5 twin are the windows call (one row per read, start 0, L = N, pad +0, under window tables of the
+ * library's own, so the window check cannot fail) followed by the match launch on the context's stream.  valid[i] is derived on the device
+ * from the verdicts and the range tables; an error gives 0.  query is REQUIRED and caller-owned (n_reads x N x 4 bytes): the hand-over
+ * between the two stages and an output the caller may keep; positions at and behind T' hold +0, rows of failing reads are unspecified.
+ * format->out_type must be F32.  result[] / read_result[] are exactly the windows call's, shift_scale is as there.  The POD5 tables are per
+ * READ over the concatenated signal, and a bad first_row fails the whole call: out still gets the empty verdict everywhere and query is
+ * not written.
+ * All return 0 when queued, -1 for a NULL context or batch or a launch failure, -2 (nothing launched, nothing written) for everything the
+ * windows call / its POD5 twin refuse about batch, options, format, norm, ranges and reads; a NULL match, ref, ref_len, query or out (the
+ * stage entry: valid) while the call has reads; query_len, n_refs, ref_stride or quant outside their rule (NaN and infinities included);
+ * flags or reserved != 0; ref, query or out not 16-byte aligned; n_reads * R * 8 or n_reads * N * 4 beyond 2^46 bytes; an out_type other
+ * than F32.
+ * How: no new sink of the svb decoder -- the prefix costs N x 4 bytes a read against a DP of N x M x R cells.  One
+ * wavefront per (read, reference) pair, the four wavefronts of a workgroup sharing a read.  The lanes are the reference: lane l owns
+ * rows l c ... l c + c - 1, c = 1, 2, 4, 8, 16 or 32 by M.  The schedule is systolic: at step t lane l takes sample t - l; a step is two
+ * wave_shr:1 DPP moves (the lane below's last row, and the sample) and c cells in registers, each a v_min3_u32 and a v_msad_u8.  Rows
+ * behind the reference's end cost nothing, so the last row of the lane that holds row M - 1 is the running minimum and the answer is
+ * tracked on one register with a strict <.  No LDS, no barrier.
+ * Measured on one MI355X (tools/time_match.py, profiles/HISTORY.md "Signal match"; the parent of the commit that adds these calls is
+ * 0465232; median of 20, calls alternating in one process, every hit checked bit for bit against the unfused route): 8 192 synthetic
+ * reads of ~100 k samples, MED_MAD, N = 2 048 behind the trim call's begin[], quant 32.  R = 24 references of M = 400: 18.00 ms
+ * against 2.64 ms for the windows call alone, 15.39 ms for the stage entry alone and 2 080 ms for the unfused route (the windows call,
+ * then a torch DTW over all pairs, one step per anti-diagonal); R = 96: 64.00 / 2.66 / 61.38 / 7 693 ms; R = 4 of M = 2 048: 10.74 /
+ * 2.74 / 8.15 / 2 854 ms.  That is 10.5 T cells/s at M = 400 and 16.9 T at M = 2 048, against an issue bound -- the kernel's own 9 + 2 c
+ * VALU instructions a step at 4.1 cycles each -- of 9.6 T and 16.8 T: the kernel stands at its bound (a little above it at c = 8,
+ * where three of the 25 instructions are moves that cost 2.2 cycles).  One 20 M-sample read: 0.63 / 0.49 / 0.16 / 168 ms at R = 24 --
+ * 24 wavefronts cannot fill 1 024 SIMDs; the stage entry is then the latency of one wavefront's 2 447 steps. */
+typedef struct vbz_gpu_match
+{
+    uint32_t query_len;      /* N: a multiple of 8, 8 ... 65536 */
+    uint32_t n_refs;         /* R: 1 ... 4096 */
+    uint32_t ref_stride;     /* bytes per row of ref: a multiple of 16, 16 ... 2048 */
+    uint32_t flags;          /* must be 0 */
+    float quant;             /* finite, > 0 */
+    uint32_t reserved;       /* must be 0 */
+    const int8_t* ref;       /* device, 16-byte aligned, n_refs x ref_stride */
+    const uint32_t* ref_len; /* device, n_refs words */
+} vbz_gpu_match;             /* 40 bytes */
+typedef struct vbz_gpu_match_hit
+{
+    uint32_t cost; /* min_j D[M-1][j]; 0xFFFFFFFF: the empty verdict */
+    uint32_t end;  /* 1 + the smallest j that attains it; 0: the empty verdict */
+} vbz_gpu_match_hit; /* 8 bytes */
+VBZ_EXPORT int vbz_gpu_match_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match,
+                                   vbz_gpu_match_hit* out);
+VBZ_EXPORT int vbz_gpu_signal_match_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                          const vbz_gpu_signal_format* format, const vbz_gpu_normalization* norm, float* shift_scale,
+                                          const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query, vbz_gpu_match_hit* out);
+VBZ_EXPORT int vbz_gpu_pod5_signal_match_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                               const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
+                                               const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
+                                               const vbz_gpu_match* match, float* query, vbz_gpu_match_hit* out);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

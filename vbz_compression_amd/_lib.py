@@ -228,6 +228,30 @@ class GpuSpans(ctypes.Structure):
     ]
 
 
+class GpuMatch(ctypes.Structure):
+    """struct vbz_gpu_match of include/vbz_gpu.h (40 bytes)."""
+
+    _fields_ = [
+        ("query_len", ctypes.c_uint32),
+        ("n_refs", ctypes.c_uint32),
+        ("ref_stride", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("quant", ctypes.c_float),
+        ("reserved", ctypes.c_uint32),
+        ("ref", ctypes.c_void_p),
+        ("ref_len", ctypes.c_void_p),
+    ]
+
+
+class GpuMatchHit(ctypes.Structure):
+    """struct vbz_gpu_match_hit of include/vbz_gpu.h (8 bytes)."""
+
+    _fields_ = [
+        ("cost", ctypes.c_uint32),
+        ("end", ctypes.c_uint32),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -275,6 +299,9 @@ GPU_API = [
     "vbz_gpu_pod5_signal_segment_batch",
     "vbz_gpu_signal_spans_batch",
     "vbz_gpu_pod5_signal_spans_batch",
+    "vbz_gpu_match_batch",
+    "vbz_gpu_signal_match_batch",
+    "vbz_gpu_pod5_signal_match_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -450,6 +477,18 @@ def load():
         L.vbz_gpu_signal_spans_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.c_uint32, np_, vp, gp, xp, vp, vp]
         L.vbz_gpu_pod5_signal_spans_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_signal_spans_batch.argtypes = [vp, bp, op, ctypes.c_uint32, rp, np_, vp, gp, xp, vp, vp]
+    if hasattr(L, "vbz_gpu_match_batch"):   # (likewise: builds of earlier rounds have no signal match)
+        np_ = ctypes.POINTER(GpuNormalization)
+        fp = ctypes.POINTER(GpuSignalFormat)
+        rp = ctypes.POINTER(GpuPod5Reads)
+        gp = ctypes.POINTER(GpuSampleRanges)
+        mp = ctypes.POINTER(GpuMatch)
+        L.vbz_gpu_match_batch.restype = ctypes.c_int
+        L.vbz_gpu_match_batch.argtypes = [vp, u32, vp, vp, mp, vp]
+        L.vbz_gpu_signal_match_batch.restype = ctypes.c_int
+        L.vbz_gpu_signal_match_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, np_, vp, gp, mp, vp, vp]
+        L.vbz_gpu_pod5_signal_match_batch.restype = ctypes.c_int
+        L.vbz_gpu_pod5_signal_match_batch.argtypes = [vp, bp, op, fp, rp, np_, vp, gp, mp, vp, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -228,6 +228,7 @@ struct vbz_gpu_ctx
     DevBuf normmeta;           // normalising decode: the per-read NormRead states of a call (NormTables)
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables, the reads' constants (Pod5Tables)
+    DevBuf matchmeta;          // signal match: the fused calls' own window tables, valid[] and, for a caller that takes none, read_result (MatchTables)
     bool profiling = false;    // (not a setting: outside Knobs; the upper half of a split call gets the call's)
     PinnedBuf pinned;          // the single-buffer API's pinned area (run_one)
     uint32_t one_seq = 0;      // the single-buffer API's hand-back flag: a number per call (run_one)
@@ -1384,6 +1385,60 @@ void window_out(const vbz_gpu_windows* w, void* out, ReadBatch* rb)
     rb->sig.pad = w->pad;
 }
 
+// the match of a *_match_batch call: the struct's rules, the tables and the arenas a call with reads needs, their alignment and extent
+static_assert(sizeof(vbz_gpu_match) == 40, "vbz_gpu_match is 40 bytes");
+static_assert(offsetof(vbz_gpu_match, query_len) == 0 && offsetof(vbz_gpu_match, n_refs) == 4 && offsetof(vbz_gpu_match, ref_stride) == 8 &&
+                  offsetof(vbz_gpu_match, flags) == 12 && offsetof(vbz_gpu_match, quant) == 16 && offsetof(vbz_gpu_match, reserved) == 20 &&
+                  offsetof(vbz_gpu_match, ref) == 24 && offsetof(vbz_gpu_match, ref_len) == 32,
+              "the fields of vbz_gpu_match");
+static_assert(sizeof(vbz_gpu_match_hit) == 8 && offsetof(vbz_gpu_match_hit, cost) == 0 && offsetof(vbz_gpu_match_hit, end) == 4,
+              "vbz_gpu_match_hit is 8 bytes: cost, end");
+bool match_ok(vbz_gpu_ctx* c, const vbz_gpu_match* m, const float* query, const vbz_gpu_match_hit* out, uint32_t n_out)
+{
+    if (!m) {
+        set_error(c, "match is NULL");
+        return false;
+    }
+    const uint32_t N = m->query_len, R = m->n_refs, S = m->ref_stride;
+    if (N < 8 || N > 65536 || N % 8 != 0 || R < 1 || R > 4096 || S < 16 || S > 2048 || S % 16 != 0 || !(m->quant > 0.0f) || !std::isfinite(m->quant) ||
+        m->flags != 0 || m->reserved != 0) {
+        set_error(c, "match outside the rules (query_len %u, n_refs %u, ref_stride %u, quant %g, flags %u, reserved %u)", N, R, S, (double)m->quant,
+                  m->flags, m->reserved);
+        return false;
+    }
+    if (n_out != 0 && (!m->ref || !m->ref_len || !query || !out)) {
+        set_error(c, "ref, ref_len, the query arena or the hit arena is NULL");
+        return false;
+    }
+    if ((((uintptr_t)m->ref | (uintptr_t)query | (uintptr_t)out) & 15u) != 0) {
+        set_error(c, "ref, the query arena or the hit arena is not 16-byte aligned");
+        return false;
+    }
+    if ((uint64_t)n_out * R > EXTENT_MAX / sizeof(vbz_gpu_match_hit) || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
+        set_error(c, "declared match arenas are not plausible (%u reads, %u references, %u samples)", n_out, R, N);
+        return false;
+    }
+    return true;
+}
+// The fused calls' scratch: the window tables of "one row per read, start 0" (the library's own, so the window check cannot fail), valid[],
+// and a read_result for a POD5 caller that passed none (the verdicts are where valid[] comes from)
+struct MatchTables
+{
+    uint64_t* first = nullptr;      // [n + 1]
+    int32_t* start = nullptr;       // [n]
+    uint32_t* valid = nullptr;      // [n]
+    uint32_t* read_result = nullptr;   // [n]
+    size_t carve(void* base, uint32_t n)
+    {
+        MetaCarver mc(base);
+        first = mc.take<uint64_t>((size_t)n + 1);
+        start = mc.take<int32_t>(n);
+        valid = mc.take<uint32_t>(n);
+        read_result = mc.take<uint32_t>(n);
+        return mc.bytes();
+    }
+};
+
 // the events of a *_signal_events_batch call: the struct's rules, the output type (records are float32), the tables and the arenas a call
 // with reads needs (n_out: the reads the tables have entries for), the arenas' alignment and extent
 static_assert(sizeof(vbz_gpu_events) == 32, "vbz_gpu_events is 32 bytes");
@@ -1669,6 +1724,10 @@ struct TypedCall
     const vbz_gpu_spans* spans = nullptr;            // SPANS (is_signed as for STATISTICS; norm nullable: the constants are then spans->level): the
     uint64_t* edge_first = nullptr;                  // ... rule, and the two tables the call fills -- edge_first and edge, which a vbz_gpu_events
     uint32_t* edge = nullptr;                        // ... reads as event_first and start
+    bool with_match = false;                         // CHUNKS, in place of a chunking or windows: the window call of one row per read at start 0
+    const vbz_gpu_match* match = nullptr;            // ... (untrusted like every struct: NULL is refused)
+    float* match_query = nullptr;                    // ... into match_query (the library's own window tables), then the match launch on the
+    vbz_gpu_match_hit* match_out = nullptr;          // ... context's stream: every pair's hit into match_out
 
     TypedCall(Typed k, int s) : kind(k), sized(s) {}
     TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
@@ -1698,6 +1757,7 @@ struct TypedCall
     TypedCall& trimmed(const vbz_gpu_trim* t, uint32_t* b) { with_trim = true, trim = t, begin = b; return *this; }
     TypedCall& segmented(const vbz_gpu_segmentation* g, uint64_t* first, uint32_t* start) { seg = g, seg_first = first, seg_start = start; return *this; }
     TypedCall& spanned(const vbz_gpu_spans* g, uint64_t* first, uint32_t* e) { spans = g, edge_first = first, edge = e; return *this; }
+    TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_hit* out) { with_match = true, match = m, match_query = query, match_out = out; return *this; }
 };
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
@@ -1910,6 +1970,37 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
     return typed_finish(c, out, job, pr, sc, rc);
 }
 
+// A fused match call that has passed every check: the window call of one row per read at start 0 (L = N, pad +0) into the caller's query
+// arena, under the library's own tables; valid[] from the verdicts it leaves and the range tables; the match launch.  Over POD5 reads the
+// verdicts are read_result's (the call's own table when the caller takes none): a bad first_row leaves an error in every entry, the window
+// call writes nothing, and every hit is the empty verdict.
+int match_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, TypedCall& t, uint32_t n_out)
+{
+    const vbz_gpu_match& m = *t.match;
+    MatchTables tab;
+    if (!ensure_carved(c, c->matchmeta, tab, n_out)) return -1;
+    {
+        Timed tm(c, "match_tables");
+        HIPCHK(c, launch_match_windows(n_out, tab.first, tab.start, c->stream), "match tables launch");
+    }
+    const vbz_gpu_windows win = { m.query_len, 0.0f, n_out, tab.first, tab.start, 0, 0 };
+    vbz_gpu_pod5_reads reads;
+    if (t.pod5) {
+        reads = *t.reads;
+        if (!reads.read_result) reads.read_result = tab.read_result;
+        t.reads = &reads;
+    }
+    t.windows(&win, t.match_query);
+    const int rc = decompress_batch_impl(c, bt, o, t.sized, false, &t);
+    if (rc != 0) return rc;
+    Timed tm(c, "match");
+    HIPCHK(c, launch_match_valid(n_out, t.pod5 ? reads.read_result : bt->result, t.ranges ? t.ranges->begin : nullptr, t.ranges ? t.ranges->end : nullptr,
+                                 m.query_len, tab.valid, c->stream), "match valid launch");
+    HIPCHK(c, launch_match(n_out, t.match_query, tab.valid, m.query_len, m.quant, m.ref, m.ref_len, m.n_refs, m.ref_stride, t.match_out, c->stream),
+           "match launch");
+    return 0;
+}
+
 // The one way into a typed decode: every check of every entry, in this order, then the decode.  A call with one fault gets that fault's
 // message; with several, the first in this order.
 int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const TypedCall& call)
@@ -1934,6 +2025,12 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     }
     if (t.kind == Typed::EVENTS) {                                                                                   // 8 (events)
         if (!events_ok(c, t.ev, t.f, t.ev_out, t.ev_moments, n_out)) return -2;
+    } else if (t.kind == Typed::CHUNKS && t.with_match) {                                                            // 8 (a match in place of a chunking)
+        if (!match_ok(c, t.match, t.match_query, t.match_out, n_out)) return -2;
+        if (t.f->out_type != VBZ_GPU_SIGNAL_F32) {
+            set_error(c, "the query of a match is float32 (out_type %u)", t.f->out_type);
+            return -2;
+        }
     } else if (t.kind == Typed::CHUNKS && t.with_windows) {                                                          // 8 (windows in place of a chunking)
         if (!windows_ok(c, t.win, t.win_out, n_out, t.f->out_type == VBZ_GPU_SIGNAL_F32 ? 4u : 2u)) return -2;
     } else if (t.kind == Typed::CHUNKS) {
@@ -1960,6 +2057,7 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     if (!plausible_extents(c, &b)) return -2;                                                                        // 10
     const vbz_gpu_signal_format none = { SIG_NONE, t.is_signed, nullptr, nullptr };
     if (stats) t.f = &none;
+    if (t.with_match) return match_decode(c, bt, o, t, n_out);                                                       // 11 (the window call, then the match)
     return decompress_batch_impl(c, bt, o, t.sized, false, &t);                                                      // 11
 }
 
@@ -2165,7 +2263,7 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
     return 0;
 }
 
-// The twenty-two typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
+// The twenty-four typed decodes.  Every entry fills a TypedCall and returns typed_decode's verdict; none has a check of its own.
 //
 //   vbz_gpu_..._batch             kind        sized  chunking  norm      shift_scale          ranges    reads  trim   (chunking "windows": a
 //                                                                                                                   vbz_gpu_windows in its place;
@@ -2192,6 +2290,8 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   pod5_signal_segment           SEGMENT     0      -         -         -                    nullable  yes    segmentation
 //   signal_spans                  SPANS       arg    -         nullable  nullable             nullable  -      spans (in the trim's place)
 //   pod5_signal_spans             SPANS       0      -         nullable  nullable             nullable  yes    spans
+//   signal_match                  CHUNKS      arg    match     nullable  nullable             nullable  -      -      (match: the library's own
+//   pod5_signal_match             CHUNKS      0      match     nullable  nullable             nullable  yes    -       windows, then match.hip)
 //
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
@@ -2366,6 +2466,37 @@ int vbz_gpu_pod5_signal_spans_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
 {
     return typed_decode(c, bt, o, TypedCall(Typed::SPANS, 0).statistics(is_signed).pod5_reads(reads).normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED)
                                       .range(ranges).spanned(spans, edge_first, edge));
+}
+
+int vbz_gpu_match_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match, vbz_gpu_match_hit* out)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!match_ok(c, match, query, out, n_reads)) return -2;
+    if (n_reads != 0 && !valid) {
+        set_error(c, "valid is NULL");
+        return -2;
+    }
+    Timed t(c, "match");
+    HIPCHK(c, launch_match(n_reads, query, valid, match->query_len, match->quant, match->ref, match->ref_len, match->n_refs, match->ref_stride, out, c->stream),
+           "match launch");
+    return 0;
+}
+
+int vbz_gpu_signal_match_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                               const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match,
+                               float* query, vbz_gpu_match_hit* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).matched(match, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_pod5_signal_match_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                    const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
+                                    const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query, vbz_gpu_match_hit* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).matched(match, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

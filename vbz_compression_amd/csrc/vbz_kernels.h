@@ -746,6 +746,16 @@ hipError_t launch_synth_signal(uint64_t seed, uint64_t first, uint32_t n, uint8_
                                const uint32_t* len, hipStream_t s);
 hipError_t launch_synth_u32(uint64_t seed, uint64_t first, uint32_t n, uint8_t* dst, const uint64_t* off,
                             const uint32_t* len, hipStream_t s);
+// Signal match (match.hip; the rule: include/vbz_gpu.h, vbz_gpu_match): out[i R + r] = {cost, end} of the subsequence DTW of reference row
+// r (ref + r ref_stride, ref_len[r] levels: untrusted, 0 or > ref_stride gives the empty verdict) against the first min(valid[i], N)
+// samples of query row i (N floats a row), quantised by `quant`.  Every entry of out is written.
+hipError_t launch_match(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* ref, const uint32_t* ref_len,
+                        uint32_t R, uint32_t ref_stride, void* out, hipStream_t s);
+// ... the fused calls' tables.  launch_match_windows: the window tables of "one row per read at start 0" (first: n + 1 entries, start: n).
+// launch_match_valid, behind the decode: valid[i] = min(T', N) from the verdict result[i] (T x 4 bytes; an error: 0) and the range tables
+// (nullable), clamped as sample_range clamps them.
+hipError_t launch_match_windows(uint32_t n, uint64_t* first, int32_t* start, hipStream_t s);
+hipError_t launch_match_valid(uint32_t n, const uint32_t* result, const uint32_t* rbegin, const uint32_t* rend, uint32_t N, uint32_t* valid, hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
