@@ -819,6 +819,55 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_match_batch(vbz_gpu_ctx* ctx, const vbz_gpu_b
                                                const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
                                                const vbz_gpu_match* match, float* query, vbz_gpu_match_hit* out);
 
+/* Signal match with the start of the aligned stretch.  The three calls below are the three above with one more answer per pair: where the
+ * stretch that `end` closes begins.  Query, quantisation, references, cost and `end` are exactly those of vbz_gpu_match; the arguments,
+ * the refusals and the return codes are those of their twins (vbz_gpu_match is the same 40 bytes, flags and reserved 0).  The rule
+ * (tests/match_span_ref.py):
+ *   A warping path of a pair runs from (0, s) to (M - 1, e - 1) in steps (i+1, j), (i, j+1), (i+1, j+1); horizontal steps inside row 0
+ *   count: a path may sit on row 0 for several samples.  start = the SMALLEST s over all paths of cost `cost` that end at column end - 1.
+ *   The reference is aligned to the query's samples [start, end); start < end always.
+ * As a DP over pairs P = (cost, start) ordered lexicographically, cost first and then start:
+ *   P[0][j] = (c(0, j), j)                   if j == 0 or P[0][j-1].cost > 0
+ *           = (c(0, j), P[0][j-1].start)     if P[0][j-1].cost == 0                 (equal cost, smaller start)
+ *   P[i][j] = c(i, j) + lexmin(P[i-1][j-1], P[i-1][j], P[i][j-1])                   (the cost is added to the first component)
+ * Adding one cell's cost to all three candidates keeps their order, so this DP is the minimum over all paths.  The first column that
+ * attains the minimum cost also holds the smallest start of all columns that attain it (a path that starts left of another and ends right
+ * of it shares a cell with it, and swapping tails there gives two paths of the minimum cost), so (end, start) is the lexicographic minimum
+ * of the last row's pairs at its first column.  This holds for the smallest start only, which is why the rule is the smallest.
+ * The empty verdict is {0xFFFFFFFF, 0, 0, 0}, under the conditions of the calls above: n == 0, an empty range, a read whose verdict is an
+ * error, M_r == 0 or M_r > ref_stride.
+ * Output.  out is a row-major [n_reads, R] arena of vbz_gpu_match_span (16 bytes), 16-byte aligned; EVERY entry is written by every call
+ * that launches, by one 16-byte store, `zero` as 0.  -2 as for the twins, the size rule being n_reads * R * 16 beyond 2^46 bytes.
+ * How ("The start").  A cell is the key cost << sb | start in one 32-bit word, sb = ceil(log2 N): v_min3_u32 over keys is
+ * the lexicographic minimum, and schedule, lanes and registers are those of the kernel above.  Lane 0's incoming pair is the key (0, j);
+ * a cell is v_min3_u32 and v_sad_u32 over levels shifted into the cost field, and the row that holds the answer is chosen once, by a
+ * scalar switch, not selected every step.  That packed kernel runs when 255 ref_stride < 2^(31 - sb) (ref_stride 2 048 up to
+ * N = 4 096, 400 up to 16 384, 128 up to 65 536); every other call inside the limits runs a second kernel that keeps the pair in a 64-bit
+ * key.  The host chooses between them from query_len and ref_stride alone; no call is refused for its size.
+ * Measured on one MI355X (tools/time_match.py, profiles/match_span_time.json; workload and shapes of the calls above, median of 20, the
+ * calls alternating in one process, every (cost, end) checked bit for bit against the cost-only call of the same run): the span stage
+ * entry 15.79 ms against 15.34 ms at R = 24, M = 400 (1.03 x), 62.92 against 61.13 ms at R = 96 (1.03 x), 8.11 against 8.03 ms at R = 4,
+ * M = 2 048 (1.01 x); the fused span call 18.46 / 65.70 / 10.83 ms.  That is the ratio of the kernels' instruction counts, 10 + 2 c against
+ * 9 + 2 c VALU instructions a step, and 1.00 - 1.05 of the packed kernel's own issue bound; running the cost-only kernel forward and
+ * reversed, the only other way to a start, costs 1.94 - 1.98 times as much. */
+typedef struct vbz_gpu_match_span
+{
+    uint32_t cost;  /* as vbz_gpu_match_hit; 0xFFFFFFFF: the empty verdict */
+    uint32_t end;   /* as vbz_gpu_match_hit; 0: the empty verdict */
+    uint32_t start; /* the smallest start of a path of that cost to end - 1; start < end */
+    uint32_t zero;  /* written 0 */
+} vbz_gpu_match_span; /* 16 bytes */
+VBZ_EXPORT int vbz_gpu_match_span_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match,
+                                        vbz_gpu_match_span* out);
+VBZ_EXPORT int vbz_gpu_signal_match_span_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                               const vbz_gpu_signal_format* format, const vbz_gpu_normalization* norm, float* shift_scale,
+                                               const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query,
+                                               vbz_gpu_match_span* out);
+VBZ_EXPORT int vbz_gpu_pod5_signal_match_span_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                    const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
+                                                    const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
+                                                    const vbz_gpu_match* match, float* query, vbz_gpu_match_span* out);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -20,6 +20,14 @@ Next to the measured cells per second stands the issue bound: VALU instructions 
 compare and two selects of the running minimum, three copies, and v_min3_u32 + v_msad_u8 per row: 9 + 2 c) times
 4.1 cycles an instruction (profiles/r06_valu_rate.txt: v_min3 / VOP3 / DPP at 4 and 8 wavefronts per SIMD), on 256 CUs x 4 SIMDs at 2.4 GHz.
 
+The span calls (vbz_gpu_match_span_batch, vbz_gpu_signal_match_span_batch) are two more legs of the same alternating loop:
+  span        the span stage entry alone, on the same query
+  fused_span  the fused span call
+Every (cost, end) they write is checked bit for bit against the cost-only call of the same run, and --sample reads against
+tests/match_span_ref.py on the host.  The packed kernel's inner loop is 10 + 2 c VALU instructions a step (SPAN_VALU_PER_STEP: v_min3_u32
+and v_sad_u32 per row; the cost-only step's nine, and the v_or that keeps lane 0's diagonal far -- the step number as the DPP move's
+`old` takes the place of the cost-only step's zero); three of them are plain v_mov, which issue in 2.2 cycles (SPAN_MOVES).
+
     python tools/time_match.py [--reads 8192] [--reps 20] [--unfused-reps 2] [--sample 6] [--long 20000000]"""
 import argparse
 import ctypes
@@ -36,6 +44,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import match_ref as MR  # noqa: E402
+import match_span_ref as SR  # noqa: E402
 from vbz_compression_amd import batch  # noqa: E402
 
 N = 2048
@@ -44,7 +53,10 @@ FAR = 1 << 30
 DIAGONAL_CELLS = 1 << 27
 # rows per lane -> VALU instructions per step of match_pair<C>'s inner loop (see the module text)
 VALU_PER_STEP = {1: 11, 2: 13, 4: 17, 8: 25, 16: 41, 32: 73}
+SPAN_VALU_PER_STEP = {c: 10 + 2 * c for c in (1, 2, 4, 8, 16, 32)}
+SPAN_MOVES = 3
 CYCLES_PER_VALU = 4.1
+CYCLES_PER_MOVE = 2.2
 SIMDS, HZ = 256 * 4, 2.4e9
 
 
@@ -116,6 +128,12 @@ def bound_cells_per_second(M):
     return M / (VALU_PER_STEP[C] * CYCLES_PER_VALU) * HZ * SIMDS, C
 
 
+def span_bound_cells_per_second(M):
+    C = next(c for c in (1, 2, 4, 8, 16, 32) if 64 * c >= M)
+    cycles = (SPAN_VALU_PER_STEP[C] - SPAN_MOVES) * CYCLES_PER_VALU + SPAN_MOVES * CYCLES_PER_MOVE
+    return M / cycles * HZ * SIMDS
+
+
 def case(c, lens, reps, unfused_reps, seed, shapes, sample):
     dev = c.device
     n = int(lens.numel())
@@ -169,6 +187,9 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
         ref_len = torch.full((R,), M, dtype=torch.int32, device=dev)
         hits_f = torch.empty((n, R, 2), dtype=torch.int32, device=dev)
         hits_s = torch.empty((n, R, 2), dtype=torch.int32, device=dev)
+        span_f = torch.empty((n, R, 4), dtype=torch.int32, device=dev)
+        span_s = torch.empty((n, R, 4), dtype=torch.int32, device=dev)
+        query_span = torch.zeros((n, N), dtype=torch.float32, device=dev)
         u = {}
 
         def stage():
@@ -178,11 +199,18 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
             c.signal_match(comp, coff, csize, off, size32, res, opts, ref, ref_len, mt, norm=batch.MED_MAD, norm_out=ss_f, begin=begin, query=query,
                            out=hits_f)
 
+        def span():
+            c.match_span(w["q"], valid, ref, ref_len, mt, out=span_s)
+
+        def fused_span():
+            c.signal_match_span(comp, coff, csize, off, size32, res, opts, ref, ref_len, mt, norm=batch.MED_MAD, norm_out=ss_f, begin=begin,
+                                query=query_span, out=span_f)
+
         def unfused():
             windows()
             u["hits"] = torch_dtw(torch_quantize(w["q"]), valid, ref[:, :M].to(torch.int32), ref_len)
 
-        ms = timed(c, {"windows": windows, "match": stage, "fused": fused}, reps)
+        ms = timed(c, {"windows": windows, "match": stage, "span": span, "fused": fused, "fused_span": fused_span}, reps)
         ms.update(timed(c, {"unfused": unfused}, unfused_reps, warm=0))
         torch.cuda.synchronize()
         assert torch.equal(res.to(torch.int64), lens64 * 4), "verdicts"
@@ -193,7 +221,12 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
         pick = np.linspace(0, n - 1, min(sample, n)).astype(int)
         want = MR.hits(q_h[pick], v_h[pick], QUANT, ref_h, [M] * R)
         assert (hits_f.cpu().numpy().view(np.uint32)[pick] == want).all(), "match_ref"
+        assert torch.equal(span_s[:, :, :2], hits_s) and torch.equal(span_f[:, :, :2], hits_f), "span (cost, end) != the cost-only call, bit for bit"
+        assert torch.equal(span_s, span_f) and torch.equal(query_span, query), "the fused span call != the span stage entry"
+        want = SR.spans(q_h[pick], v_h[pick], QUANT, ref_h, [M] * R)
+        assert (span_s.cpu().numpy().view(np.uint32)[pick] == want).all(), "match_span_ref"
         cells = int(valid.to(torch.int64).sum()) * R * M
+        span_bound = span_bound_cells_per_second(M)
         bound, C = bound_cells_per_second(M)
         dp_ms = ms["fused"] - ms["windows"]
         zero = int((hits_f[:, :, 0] == 0).sum())
@@ -201,7 +234,13 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
                              "match_gcells_per_s": round(cells / ms["match"] / 1e6, 1), "fused_minus_windows_gcells_per_s": round(cells / dp_ms / 1e6, 1),
                              "issue_bound_gcells_per_s": round(bound / 1e9, 1), "share_of_bound": round(cells / (ms["match"] * 1e-3) / bound, 3),
                              "unfused_over_fused": round(ms["unfused"] / ms["fused"], 1), "checked_against_unfused": True,
-                             "reads_checked_against_match_ref": len(pick)})
+                             "reads_checked_against_match_ref": len(pick),
+                             "span": {"over_match": round(ms["span"] / ms["match"], 3), "fused_span_over_fused": round(ms["fused_span"] / ms["fused"], 3),
+                                      "gcells_per_s": round(cells / ms["span"] / 1e6, 1), "valu_per_step": SPAN_VALU_PER_STEP[C], "moves_per_step": SPAN_MOVES,
+                                      "issue_bound_gcells_per_s": round(span_bound / 1e9, 1),
+                                      "share_of_bound": round(cells / (ms["span"] * 1e-3) / span_bound, 3),
+                                      "over_twice_the_cost_only_call": round(ms["span"] / (2 * ms["match"]), 3),
+                                      "cost_end_equal_cost_only": True, "reads_checked_against_match_span_ref": len(pick)}})
         print(json.dumps(out["cases"][-1]), file=sys.stderr, flush=True)
     return out
 

@@ -252,6 +252,17 @@ class GpuMatchHit(ctypes.Structure):
     ]
 
 
+class GpuMatchSpan(ctypes.Structure):
+    """struct vbz_gpu_match_span of include/vbz_gpu.h (16 bytes)."""
+
+    _fields_ = [
+        ("cost", ctypes.c_uint32),
+        ("end", ctypes.c_uint32),
+        ("start", ctypes.c_uint32),
+        ("zero", ctypes.c_uint32),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -302,6 +313,9 @@ GPU_API = [
     "vbz_gpu_match_batch",
     "vbz_gpu_signal_match_batch",
     "vbz_gpu_pod5_signal_match_batch",
+    "vbz_gpu_match_span_batch",
+    "vbz_gpu_signal_match_span_batch",
+    "vbz_gpu_pod5_signal_match_span_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -489,6 +503,11 @@ def load():
         L.vbz_gpu_signal_match_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, np_, vp, gp, mp, vp, vp]
         L.vbz_gpu_pod5_signal_match_batch.restype = ctypes.c_int
         L.vbz_gpu_pod5_signal_match_batch.argtypes = [vp, bp, op, fp, rp, np_, vp, gp, mp, vp, vp]
+    if hasattr(L, "vbz_gpu_match_span_batch"):   # (likewise: the hits are vbz_gpu_match_span, the arguments those of the three above)
+        for name in ("vbz_gpu_match_span_batch", "vbz_gpu_signal_match_span_batch", "vbz_gpu_pod5_signal_match_span_batch"):
+            twin = getattr(L, name.replace("_span", ""))
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = list(twin.argtypes)
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

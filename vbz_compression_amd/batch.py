@@ -235,7 +235,7 @@ class GpuCodec:
 
     def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
                chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None, ev=None, moments=None, sg=None,
-               event_first=None, start=None, sp=None, mt=None):
+               event_first=None, start=None, sp=None, mt=None, span=False):
         """One typed decode (include/vbz_gpu.h): the batch, the device entered and left once, and the most general C entry of the call's
         family, NULL for every part that is None.  dst None: nothing is stored in the batch's dst (a chunk decode, the statistics) --
         dst_off / dst_cap are the int16 layout that describes the reads, dst_bytes its extent.  f (a GpuSignalFormat): what is stored,
@@ -246,7 +246,8 @@ class GpuCodec:
         exact sums into `moments` (int64 [rows, 2], or None).  sg (a GpuSegmentation, f None): every read's event starts, found on the
         device, into event_first (int64 [reads + 1]) and start (int32, sg.start_cap entries; None: the count-only call).  sp (a GpuSpans,
         f None; m / ss optional): every read's spans into event_first (edge_first) and start (edge, sp.edge_cap entries or None).  mt (a GpuMatch,
-        in place of ch, with f): the reads' prefixes into `chunks` (float32 [reads, query_len]) and every pair's hit into `out`."""
+        in place of ch, with f): the reads' prefixes into `chunks` (float32 [reads, query_len]) and every pair's hit into `out`; with span
+        the hits are vbz_gpu_match_span (the *_match_span entries)."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -261,7 +262,7 @@ class GpuCodec:
             name, args = "signal_events", [ref(f)] + reads + [ref(ev), out.data_ptr(), moments.data_ptr() if moments is not None else None, ref(m), ss, ref(g)]
         elif mt is not None:
             assert ch is None and w is None, "a call has a chunking, windows, events or a match, never two of them"
-            name, args = "signal_match", [ref(f)] + reads + [ref(m), ss, ref(g), ref(mt), chunks.data_ptr(), out.data_ptr()]
+            name, args = "signal_match_span" if span else "signal_match", [ref(f)] + reads + [ref(m), ss, ref(g), ref(mt), chunks.data_ptr(), out.data_ptr()]
         elif w is not None:
             assert ch is None, "a call has a chunking or windows, never both"
             name, args = "decompress_windows", [ref(f)] + reads + [ref(w), chunks.data_ptr(), ref(m), ss, ref(g)]
@@ -821,47 +822,50 @@ class GpuCodec:
                                     window_len, pad, dtype, scale, offset, signed, norm, norm_out, begin, end, stats)
 
     # -- signal match (include/vbz_gpu.h: vbz_gpu_match) ------------------------------------------------
-    def _match_arenas(self, n, mt, query, out):
-        """(query float32 [n, N], hits int32 [n, R, 2]) of a match call: the caller's, checked, or new ones"""
+    def _match_arenas(self, n, mt, query, out, words=2):
+        """(query float32 [n, N], hits int32 [n, R, words]) of a match call: the caller's, checked, or new ones.  words: 2 (cost, end), or 4
+        of the span calls (cost, end, start, 0)"""
         N, R = int(mt.query_len), int(mt.n_refs)
         if query is None:
             query = torch.empty((n, N), dtype=torch.float32, device=self.device)
         if out is None:
-            out = torch.empty((n, R, 2), dtype=torch.int32, device=self.device)
+            out = torch.empty((n, R, words), dtype=torch.int32, device=self.device)
         assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, R, 2), (out.dtype, out.shape)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, R, words), (out.dtype, out.shape)
         return query, out
 
-    def match(self, query, valid, ref, ref_len, match=None, out=None):
+    def match(self, query, valid, ref, ref_len, match=None, out=None, span=False):
         """The stage entry (include/vbz_gpu.h: vbz_gpu_match_batch): subsequence DTW of every reference row (ref int8 [R, ref_stride],
         ref_len int32 [R], on the device) against the first min(valid[i], query_len) samples of query row i (float32 [n, query_len];
         valid int32 [n], uint32 bits) -> hits int32 [n, R, 2] = (cost, end) on the device (`out` when given).  match: a Match whose
-        query_len is the rows' length (None: quant 32 and that length).  No synchronisation."""
+        query_len is the rows' length (None: quant 32 and that length).  No synchronisation.  (span: match_span's route.)"""
         n = int(query.shape[0])
         mt = (match or Match(query_len=int(query.shape[1]))).c_struct(ref, ref_len)
         assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
-        query, out = self._match_arenas(n, mt, query, out)
+        query, out = self._match_arenas(n, mt, query, out, 4 if span else 2)
+        name = "match_span_batch" if span else "match_batch"
         cur = self._enter()
         try:
-            self._rc(self.L.vbz_gpu_match_batch(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(mt), out.data_ptr()), "match_batch")
+            self._rc(getattr(self.L, "vbz_gpu_" + name)(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(mt), out.data_ptr()), name)
         finally:
             self._exit(cur)
         return out
 
     def _signal_match(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, match, ref, ref_len, scale, offset, signed,
-                      norm, norm_out, begin, end, stats, query, out, r=None):
+                      norm, norm_out, begin, end, stats, query, out, r=None, span=False):
         mt = (match or Match()).c_struct(ref, ref_len)
-        query, out = self._match_arenas(n, mt, query, out)
+        query, out = self._match_arenas(n, mt, query, out, 4 if span else 2)
         g, keep_g = self._ranges(n, begin, end, stats)
         if norm is not None and norm_out is None:
             norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(torch.float32, n, scale, offset, signed)
-        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, mt=mt, out=out)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, mt=mt, out=out,
+                    span=span)
         return (out, query) if norm is None else (out, query, norm_out)
 
     def signal_match(self, src, src_off, src_size, dst_off, dst_cap, result, opts, ref, ref_len, match=None, scale=None, offset=None, signed=True,
-                     sized=False, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None):
+                     sized=False, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, span=False):
         """Decode every read's prefix and match it against every reference row on the device (include/vbz_gpu.h:
         vbz_gpu_signal_match_batch) -> (hits int32 [n, R, 2] = (cost, end), query float32 [n, query_len]), and with norm= also
         shift_scale float32 [n, 2].  The query is the first query_len samples of the read's signal -- of its range with begin / end --
@@ -869,10 +873,11 @@ class GpuCodec:
         dst_cap: the int16 layout of the reads (nothing is stored there); result[i] = samples * 4.  No synchronisation."""
         n = int(src_off.numel())
         return self._signal_match(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, match, ref, ref_len,
-                                  scale, offset, signed, norm, norm_out, begin, end, stats, query, out)
+                                  scale, offset, signed, norm, norm_out, begin, end, stats, query, out, span=span)
 
     def pod5_signal_match(self, src, src_off, src_size, row_samples, read_first_row, result, ref, ref_len, match=None, scale=None, offset=None,
-                          signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, read_result=None):
+                          signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, read_result=None,
+                          span=False):
         """signal_match over POD5 signal rows grouped into reads by read_first_row (include/vbz_gpu.h: vbz_gpu_pod5_signal_match_batch):
         hits, query, scale / offset / norm_out and begin / end are per READ, the positions those of the read's concatenated signal;
         result is per ROW, read_result (int32 [n_reads] on the device, optional) per read."""
@@ -881,7 +886,24 @@ class GpuCodec:
         r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._signal_match(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
-                                  match, ref, ref_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r)
+                                  match, ref, ref_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
+
+    # -- signal match with the start of the stretch (include/vbz_gpu.h: vbz_gpu_match_span) ------------------
+    def match_span(self, query, valid, ref, ref_len, match=None, out=None):
+        """match() with the start of the aligned stretch (include/vbz_gpu.h: vbz_gpu_match_span_batch): the same arguments -> hits int32
+        [n, R, 4] = (cost, end, start, 0); the reference is aligned to the query's samples [start, end), start the smallest of a path of
+        that cost to that end.  No synchronisation."""
+        return self.match(query, valid, ref, ref_len, match, out, span=True)
+
+    def signal_match_span(self, *args, **kw):
+        """signal_match() with the start of the aligned stretch (include/vbz_gpu.h: vbz_gpu_signal_match_span_batch): the same arguments,
+        hits int32 [n, R, 4] = (cost, end, start, 0)."""
+        return self.signal_match(*args, span=True, **kw)
+
+    def pod5_signal_match_span(self, *args, **kw):
+        """pod5_signal_match() with the start of the aligned stretch (include/vbz_gpu.h: vbz_gpu_pod5_signal_match_span_batch): the same
+        arguments, hits int32 [n, R, 4] = (cost, end, start, 0)."""
+        return self.pod5_signal_match(*args, span=True, **kw)
 
     # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
     def _events(self, n, event_first, start):

@@ -1393,7 +1393,11 @@ static_assert(offsetof(vbz_gpu_match, query_len) == 0 && offsetof(vbz_gpu_match,
               "the fields of vbz_gpu_match");
 static_assert(sizeof(vbz_gpu_match_hit) == 8 && offsetof(vbz_gpu_match_hit, cost) == 0 && offsetof(vbz_gpu_match_hit, end) == 4,
               "vbz_gpu_match_hit is 8 bytes: cost, end");
-bool match_ok(vbz_gpu_ctx* c, const vbz_gpu_match* m, const float* query, const vbz_gpu_match_hit* out, uint32_t n_out)
+static_assert(sizeof(vbz_gpu_match_span) == 16 && offsetof(vbz_gpu_match_span, cost) == 0 && offsetof(vbz_gpu_match_span, end) == 4 &&
+                  offsetof(vbz_gpu_match_span, start) == 8 && offsetof(vbz_gpu_match_span, zero) == 12,
+              "vbz_gpu_match_span is 16 bytes: cost, end, start, zero");
+// (out: n_out x R entries of hit_bytes each -- vbz_gpu_match_hit, or vbz_gpu_match_span of the span calls)
+bool match_ok(vbz_gpu_ctx* c, const vbz_gpu_match* m, const float* query, const void* out, size_t hit_bytes, uint32_t n_out)
 {
     if (!m) {
         set_error(c, "match is NULL");
@@ -1414,7 +1418,7 @@ bool match_ok(vbz_gpu_ctx* c, const vbz_gpu_match* m, const float* query, const 
         set_error(c, "ref, the query arena or the hit arena is not 16-byte aligned");
         return false;
     }
-    if ((uint64_t)n_out * R > EXTENT_MAX / sizeof(vbz_gpu_match_hit) || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
+    if ((uint64_t)n_out * R > EXTENT_MAX / hit_bytes || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
         set_error(c, "declared match arenas are not plausible (%u reads, %u references, %u samples)", n_out, R, N);
         return false;
     }
@@ -1727,7 +1731,8 @@ struct TypedCall
     bool with_match = false;                         // CHUNKS, in place of a chunking or windows: the window call of one row per read at start 0
     const vbz_gpu_match* match = nullptr;            // ... (untrusted like every struct: NULL is refused)
     float* match_query = nullptr;                    // ... into match_query (the library's own window tables), then the match launch on the
-    vbz_gpu_match_hit* match_out = nullptr;          // ... context's stream: every pair's hit into match_out
+    void* match_out = nullptr;                       // ... context's stream: every pair's hit into match_out -- vbz_gpu_match_hit, or with
+    bool match_span = false;                         // ... match_span vbz_gpu_match_span (the span launch in the match launch's place)
 
     TypedCall(Typed k, int s) : kind(k), sized(s) {}
     TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
@@ -1758,6 +1763,7 @@ struct TypedCall
     TypedCall& segmented(const vbz_gpu_segmentation* g, uint64_t* first, uint32_t* start) { seg = g, seg_first = first, seg_start = start; return *this; }
     TypedCall& spanned(const vbz_gpu_spans* g, uint64_t* first, uint32_t* e) { spans = g, edge_first = first, edge = e; return *this; }
     TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_hit* out) { with_match = true, match = m, match_query = query, match_out = out; return *this; }
+    TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_span* out) { matched(m, query, (vbz_gpu_match_hit*)nullptr); match_out = out, match_span = true; return *this; }
 };
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
@@ -1996,7 +2002,8 @@ int match_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     Timed tm(c, "match");
     HIPCHK(c, launch_match_valid(n_out, t.pod5 ? reads.read_result : bt->result, t.ranges ? t.ranges->begin : nullptr, t.ranges ? t.ranges->end : nullptr,
                                  m.query_len, tab.valid, c->stream), "match valid launch");
-    HIPCHK(c, launch_match(n_out, t.match_query, tab.valid, m.query_len, m.quant, m.ref, m.ref_len, m.n_refs, m.ref_stride, t.match_out, c->stream),
+    HIPCHK(c, (t.match_span ? launch_match_span : launch_match)(n_out, t.match_query, tab.valid, m.query_len, m.quant, m.ref, m.ref_len, m.n_refs,
+                                                                m.ref_stride, t.match_out, c->stream),
            "match launch");
     return 0;
 }
@@ -2026,7 +2033,7 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     if (t.kind == Typed::EVENTS) {                                                                                   // 8 (events)
         if (!events_ok(c, t.ev, t.f, t.ev_out, t.ev_moments, n_out)) return -2;
     } else if (t.kind == Typed::CHUNKS && t.with_match) {                                                            // 8 (a match in place of a chunking)
-        if (!match_ok(c, t.match, t.match_query, t.match_out, n_out)) return -2;
+        if (!match_ok(c, t.match, t.match_query, t.match_out, t.match_span ? sizeof(vbz_gpu_match_span) : sizeof(vbz_gpu_match_hit), n_out)) return -2;
         if (t.f->out_type != VBZ_GPU_SIGNAL_F32) {
             set_error(c, "the query of a match is float32 (out_type %u)", t.f->out_type);
             return -2;
@@ -2292,6 +2299,8 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   pod5_signal_spans             SPANS       0      -         nullable  nullable             nullable  yes    spans
 //   signal_match                  CHUNKS      arg    match     nullable  nullable             nullable  -      -      (match: the library's own
 //   pod5_signal_match             CHUNKS      0      match     nullable  nullable             nullable  yes    -       windows, then match.hip)
+//   signal_match_span             CHUNKS      arg    match     nullable  nullable             nullable  -      -      (as signal_match: 16-byte hits,
+//   pod5_signal_match_span        CHUNKS      0      match     nullable  nullable             nullable  yes    -       the span launch in its place)
 //
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
@@ -2472,7 +2481,7 @@ int vbz_gpu_match_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, co
 {
     if (!c) return -1;
     DeviceGuard dg(c->device);
-    if (!match_ok(c, match, query, out, n_reads)) return -2;
+    if (!match_ok(c, match, query, out, sizeof(vbz_gpu_match_hit), n_reads)) return -2;
     if (n_reads != 0 && !valid) {
         set_error(c, "valid is NULL");
         return -2;
@@ -2494,6 +2503,38 @@ int vbz_gpu_signal_match_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Co
 int vbz_gpu_pod5_signal_match_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
                                     const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
                                     const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query, vbz_gpu_match_hit* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).matched(match, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_match_span_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match, vbz_gpu_match_span* out)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!match_ok(c, match, query, out, sizeof(vbz_gpu_match_span), n_reads)) return -2;
+    if (n_reads != 0 && !valid) {
+        set_error(c, "valid is NULL");
+        return -2;
+    }
+    Timed t(c, "match");
+    HIPCHK(c, launch_match_span(n_reads, query, valid, match->query_len, match->quant, match->ref, match->ref_len, match->n_refs, match->ref_stride, out,
+                                c->stream),
+           "match span launch");
+    return 0;
+}
+
+int vbz_gpu_signal_match_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                    const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match,
+                                    float* query, vbz_gpu_match_span* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).matched(match, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_pod5_signal_match_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                         const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
+                                         const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query, vbz_gpu_match_span* out)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).matched(match, query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));

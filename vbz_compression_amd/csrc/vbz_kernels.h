@@ -751,6 +751,10 @@ hipError_t launch_synth_u32(uint64_t seed, uint64_t first, uint32_t n, uint8_t* 
 // samples of query row i (N floats a row), quantised by `quant`.  Every entry of out is written.
 hipError_t launch_match(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* ref, const uint32_t* ref_len,
                         uint32_t R, uint32_t ref_stride, void* out, hipStream_t s);
+// ... with the start of the aligned stretch (vbz_gpu_match_span): out[i R + r] = {cost, end, start, 0}, 16 bytes an entry.  The packed kernel
+// or the wide one, by match_select.h from N and ref_stride alone.
+hipError_t launch_match_span(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* ref,
+                             const uint32_t* ref_len, uint32_t R, uint32_t ref_stride, void* out, hipStream_t s);
 // ... the fused calls' tables.  launch_match_windows: the window tables of "one row per read at start 0" (first: n + 1 entries, start: n).
 // launch_match_valid, behind the decode: valid[i] = min(T', N) from the verdict result[i] (T x 4 bytes; an error: 0) and the range tables
 // (nullable), clamped as sample_range clamps them.
