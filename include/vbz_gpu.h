@@ -868,6 +868,72 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_match_span_batch(vbz_gpu_ctx* ctx, const vbz_
                                                     const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
                                                     const vbz_gpu_match* match, float* query, vbz_gpu_match_span* out);
 
+/* Signal match: the warping path of chosen pairs.  The span calls say which reference a read carries and where; these two stage-level
+ * calls say which samples belong to which reference level, for the pairs the caller lists -- typically the one winner per read -- without
+ * the arena or the query crossing to the host: span -> best -> path are three queued calls on one stream.
+ * The rule (tests/match_path_ref.py).  A pair names a read, a reference and a window [a, b) of the read's query, 0 <= a < b <= n,
+ * n = min(valid[read], N).  Query, quantisation, references and c(i, j) are exactly vbz_gpu_match's.  Over the window's columns alone run the
+ * span rule's DP of pairs P = (cost, start), ordered lexicographically: row 0 at column a is (c(0, a), a), a path may sit on row 0, and
+ * nothing left of a exists.  The path is the backtrace from cell (M - 1, b - 1):
+ *   at (i, j) with i > 0, j > a: step to the FIRST of diagonal (i-1, j-1), up (i-1, j), left (i, j-1) whose P equals the lexicographic
+ *                                minimum of the three;
+ *   at j == a, i > 0:            step up;
+ *   in row 0:                    step left while j > a and P[0][j-1].cost == 0; otherwise stop: that column is the path's start.
+ * The answer per pair is a hit {cost, end, start, rows} -- cost = P[M-1][b-1].cost, end = b, start = the column where the backtrace stops,
+ * rows = M -- and one {begin, end} per reference row: row i is aligned to the query's samples [begin_i, end_i).  begin_0 == start ==
+ * P[M-1][b-1].start, end_{M-1} == b, begin_i < end_i, and begin_{i+1} is end_i - 1 (a vertical step) or end_i (a diagonal step); the sum of
+ * c(i, j) over the path's cells is cost.  When (a, b) is a span call's (start, end) for that pair, or any a' <= start with the same b, the
+ * hit's cost and start are the span call's.  The hit reuses vbz_gpu_match_span: its fourth word, `zero`, carries rows HERE; the span calls
+ * still write 0 there.  The empty verdict is the hit {0xFFFFFFFF, 0, 0, 0} with every row {0, 0}.
+ * vbz_gpu_match_best_batch: the winners' table, made on the device.  spans is a span call's [n_reads, n_refs] arena; pairs[i] is read i with
+ * the reference of least cost among row i, ties to the smallest reference index; empty verdicts and costs above max_cost are skipped;
+ * begin and end are that hit's start and end.  If no reference qualifies, ref = 0xFFFFFFFF and begin = end = 0.  One wavefront per read.
+ * Returns 0 when queued, -1 for a NULL context or a launch failure, -2 (nothing launched) for NULL or not 16-byte aligned tables while
+ * the call has reads, n_refs outside 1 ... 4096, n_reads * n_refs * 16 beyond 2^46 bytes.
+ * vbz_gpu_match_path_batch: query is the [n_reads, N] arena the fused span calls leave with the caller; valid may be NULL, meaning every
+ * row has N samples (the fused calls do not hand their valid[] out; positions behind a read's end hold +0 there, and b bounds every
+ * access).  path->max_width is the largest b - a the call accepts, a multiple of 8 from 8 to 65536; it sizes the scratch.  rows is a
+ * row-major [n_pairs, ref_stride] arena of vbz_gpu_match_row (8 bytes), 16-byte aligned; entries at i >= M are written {0, 0}.  hit is
+ * [n_pairs], written by 16-byte stores.  pairs is an untrusted device table, 16-byte aligned: a pair gets the empty verdict, with no
+ * address formed from it, when read >= n_reads or ref >= R (the "none" of the best call included), begin >= end, end > min(valid, N),
+ * end - begin > max_width, M_r == 0 or M_r > ref_stride.  EVERY entry of hit and rows is written by every call that launches.
+ * Returns 0 when queued, -1 for a NULL context or a launch failure, -2, with nothing launched and nothing written, for NULL tables while
+ * the call has pairs (valid apart), misalignment, path flags or reserved != 0, max_width outside its rule, everything vbz_gpu_match is
+ * refused for, and n_pairs * ref_stride * 8 beyond 2^46 bytes.
+ * How ("The path").  A forward launch, one wavefront per pair, runs the span kernel's schedule over the window's W columns
+ * (W + la steps; the packed or the wide key by the span calls' rule with max_width in N's place, starts relative to a) and stores two
+ * direction bits a cell into a bit-matrix in the context's scratch: about 16 c max_width bytes a pair, c the rows per lane of ref_stride.
+ * A second launch, one wavefront per pair again, walks the bits back in scalar registers (at most W + M steps; 64 words of bits are
+ * fetched by one load) and writes rows and hit.  The host runs the pairs in groups so that the bit-matrix stays under a cap (4 GiB;
+ * VBZ_HIP_MATCH_PATH_CAP=<bytes> or vbz_gpu_set_match_path_cap; a pair larger than the cap runs alone): the answers do not depend on
+ * it.  The context keeps the bit-matrix of its largest call -- the bits of one group, at most the cap and a quarter -- until it is
+ * destroyed, like every scratch buffer of a context. */
+typedef struct vbz_gpu_match_pair
+{
+    uint32_t read;  /* < n_reads */
+    uint32_t ref;   /* < n_refs; 0xFFFFFFFF: none */
+    uint32_t begin; /* a */
+    uint32_t end;   /* b */
+} vbz_gpu_match_pair; /* 16 bytes */
+typedef struct vbz_gpu_match_path
+{
+    uint32_t max_width; /* the largest end - begin: a multiple of 8, 8 ... 65536 */
+    uint32_t flags;     /* must be 0 */
+    uint64_t reserved;  /* must be 0 */
+} vbz_gpu_match_path; /* 16 bytes */
+typedef struct vbz_gpu_match_row
+{
+    uint32_t begin; /* the first sample aligned to this reference row */
+    uint32_t end;   /* one behind the last; {0, 0}: no such row */
+} vbz_gpu_match_row; /* 8 bytes */
+VBZ_EXPORT int vbz_gpu_match_best_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const vbz_gpu_match_span* spans, uint32_t n_refs, uint32_t max_cost,
+                                        vbz_gpu_match_pair* pairs);
+VBZ_EXPORT int vbz_gpu_match_path_batch(vbz_gpu_ctx* ctx, uint32_t n_pairs, uint32_t n_reads, const float* query, const uint32_t* valid,
+                                        const vbz_gpu_match* match, const vbz_gpu_match_pair* pairs, const vbz_gpu_match_path* path,
+                                        vbz_gpu_match_span* hit, vbz_gpu_match_row* rows);
+/* The bytes of direction bits one group of a path call may take (0: the default). */
+VBZ_EXPORT void vbz_gpu_set_match_path_cap(vbz_gpu_ctx* ctx, uint64_t bytes);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -28,13 +28,26 @@ tests/match_span_ref.py on the host.  The packed kernel's inner loop is 10 + 2 c
 and v_sad_u32 per row; the cost-only step's nine, and the v_or that keeps lane 0's diagonal far -- the step number as the DPP move's
 `old` takes the place of the cost-only step's zero); three of them are plain v_mov, which issue in 2.2 cycles (SPAN_MOVES).
 
-    python tools/time_match.py [--reads 8192] [--reps 20] [--unfused-reps 2] [--sample 6] [--long 20000000]"""
+The path calls (vbz_gpu_match_best_batch, vbz_gpu_match_path_batch) are two more legs, on the winners of the span call of the same run:
+  best        the winners' table from the span stage entry's arena
+  path        the path stage: forward launch and traceback of every winner, max_width = N
+Every hit is checked against the span call of the same run (cost, end, start of the winner), and --sample reads against
+tests/match_path_ref.py on the host.  The forward kernel's inner loop is 6 + 6 c VALU instructions a step (PATH_VALU_PER_STEP, counted in
+the disassembly: per row v_min3_u32, v_sad_u32 and a subtraction and a v_alignbit_b32 for each of the two direction bits; the
+subtractions issue in 2.4 cycles, the rest in 4.1).  The
+traceback's share of the stage is read from the library's per-launch timers in one more call; --path-caps times the stage under other
+scratch caps (bytes).  The unfused path route -- the span arena and the query copied to the host, then match_path_ref's backtrace over
+the winners -- is timed on the --sample reads and SCALED to the batch.  --unfused-reps 0 leaves the torch DTW out (and the checks against
+it).
+
+    python tools/time_match.py [--reads 8192] [--reps 20] [--unfused-reps 2] [--sample 6] [--long 20000000] [--path-caps a,b,c]"""
 import argparse
 import ctypes
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -43,6 +56,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import match_path_ref as PR  # noqa: E402
 import match_ref as MR  # noqa: E402
 import match_span_ref as SR  # noqa: E402
 from vbz_compression_amd import batch  # noqa: E402
@@ -55,9 +69,16 @@ DIAGONAL_CELLS = 1 << 27
 VALU_PER_STEP = {1: 11, 2: 13, 4: 17, 8: 25, 16: 41, 32: 73}
 SPAN_VALU_PER_STEP = {c: 10 + 2 * c for c in (1, 2, 4, 8, 16, 32)}
 SPAN_MOVES = 3
+PATH_VALU_PER_STEP = {c: 6 + 6 * c for c in (1, 2, 4, 8, 16, 32)}
+PATH_SUBS_PER_ROW = 2    # v_sub_u32, which issues in CYCLES_PER_SUB (profiles/r06_valu_rate.txt: v_add_u32 at two wavefronts a SIMD and more)
+CYCLES_PER_SUB = 2.4
 CYCLES_PER_VALU = 4.1
 CYCLES_PER_MOVE = 2.2
 SIMDS, HZ = 256 * 4, 2.4e9
+
+
+def progress(*what):
+    print("#", *what, file=sys.stderr, flush=True)
 
 
 def timed(c, fns, reps, warm=2):
@@ -134,7 +155,53 @@ def span_bound_cells_per_second(M):
     return M / cycles * HZ * SIMDS
 
 
-def case(c, lens, reps, unfused_reps, seed, shapes, sample):
+def path_leg(c, ms, q, valid, ref, ref_len, mt, span_s, pairs, path_hit, path_rows, M, C, sample, caps):
+    """the checks and the figures of the best and path legs (ms: the alternating loop's medians)"""
+    n, R = span_s.shape[0], span_s.shape[1]
+    torch.cuda.synchronize()
+    sp, pr, hit = (t.cpu().numpy().view(np.uint32) for t in (span_s, pairs, path_hit))
+    assert (pr == PR.best(sp)).all(), "match_best != match_path_ref.best"
+    won = pr[:, 1] != PR.NONE
+    rows_i = np.arange(n)[won]
+    assert (hit[won, :3] == sp[rows_i, pr[won, 1], :3]).all() and (hit[won, 3] == M).all(), "path hits != the span call's winners"
+    assert (hit[~won] == np.array(PR.EMPTY, np.uint32)).all()
+    pick = np.linspace(0, n - 1, min(sample, n)).astype(int)
+    q_h, v_h, ref_h = q.cpu().numpy(), valid.cpu().numpy(), ref.cpu().numpy()
+    t0 = time.perf_counter()   # the unfused route on the sampled reads: arena and query are on the host, the backtrace over the winners
+    winners = PR.best(sp[pick])
+    winners[:, 0] = pick
+    want_hit, want_rows = PR.paths(q_h, v_h, QUANT, ref_h, [M] * R, winners, N)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    assert (hit[pick] == want_hit).all() and (path_rows.cpu().numpy().view(np.uint32)[pick] == want_rows).all(), "match_path_ref"
+    # the traceback's share, from the library's per-launch timers over one more call
+    c.profile_reset()
+    c.profile(True)
+    with torch.cuda.stream(c.stream):
+        c.match_path(q, valid, ref, ref_len, pairs, N, mt, hit=path_hit, rows=path_rows)
+    prof = c.profile_read()
+    c.profile(False)
+    fwd, trace = prof["match_path_forward"], prof["match_path_trace"]
+    steps = int((hit[won, 1].astype(np.int64) - hit[won, 2] + (M - 1) // C).sum())
+    waves = -(-int(won.sum()) // SIMDS)   # wavefronts a SIMD runs one after another when the pairs are spread evenly
+    step_cycles = (PATH_VALU_PER_STEP[C] - PATH_SUBS_PER_ROW * C) * CYCLES_PER_VALU + PATH_SUBS_PER_ROW * C * CYCLES_PER_SUB
+    bound_ms = steps / max(1, int(won.sum())) * waves * step_cycles / HZ * 1e3
+    out = {"best_ms": ms["best"], "path_ms": ms["path"], "path_over_span": round(ms["path"] / ms["span"], 4), "winners": int(won.sum()),
+           "mean_width": round(float((hit[won, 1].astype(np.int64) - hit[won, 2]).mean()), 1), "groups": fwd[0],
+           "forward_ms": round(fwd[1], 4), "trace_ms": round(trace[1], 4), "trace_share": round(trace[1] / (fwd[1] + trace[1]), 3),
+           "valu_per_step": PATH_VALU_PER_STEP[C], "forward_issue_bound_ms": round(bound_ms, 4),
+           "forward_cycles_per_step": round(fwd[1] * 1e-3 * HZ / (steps / max(1, int(won.sum())) * waves), 1),
+           "bound_cycles_per_step": round(step_cycles, 1),
+           "unfused_host_ms_scaled": round(host_ms * n / len(pick), 1), "unfused_is_scaled_from_reads": len(pick),
+           "hits_equal_span_winners": True, "reads_checked_against_match_path_ref": len(pick), "caps": {}}
+    for cap in caps:
+        progress("cap", cap)
+        c.L.vbz_gpu_set_match_path_cap(c.ctx, cap)
+        out["caps"][str(cap)] = timed(c, {"path": lambda: c.match_path(q, valid, ref, ref_len, pairs, N, mt, hit=path_hit, rows=path_rows)}, 10)["path"]
+    c.L.vbz_gpu_set_match_path_cap(c.ctx, 0)
+    return out
+
+
+def case(c, lens, reps, unfused_reps, seed, shapes, sample, path_caps=()):
     dev = c.device
     n = int(lens.numel())
     opts = c.options(True, 2, 1, 1)
@@ -152,6 +219,7 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
         csize = torch.zeros(n, dtype=torch.int32, device=dev)
         c.compress(raw, off, sizes.to(torch.int32), comp, coff, caps.to(torch.int32).to(dev), csize, opts)
     torch.cuda.synchronize()
+    progress("compressed", n, "reads")
     del raw
     size32 = sizes.to(torch.int32)
     res = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -190,6 +258,9 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
         span_f = torch.empty((n, R, 4), dtype=torch.int32, device=dev)
         span_s = torch.empty((n, R, 4), dtype=torch.int32, device=dev)
         query_span = torch.zeros((n, N), dtype=torch.float32, device=dev)
+        pairs = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        path_hit = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        path_rows = torch.empty((n, stride, 2), dtype=torch.int32, device=dev)
         u = {}
 
         def stage():
@@ -206,17 +277,28 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
             c.signal_match_span(comp, coff, csize, off, size32, res, opts, ref, ref_len, mt, norm=batch.MED_MAD, norm_out=ss_f, begin=begin,
                                 query=query_span, out=span_f)
 
+        def best():
+            c.match_best(span_s, out=pairs)
+
+        def path():
+            c.match_path(w["q"], valid, ref, ref_len, pairs, N, mt, hit=path_hit, rows=path_rows)
+
         def unfused():
             windows()
             u["hits"] = torch_dtw(torch_quantize(w["q"]), valid, ref[:, :M].to(torch.int32), ref_len)
 
-        ms = timed(c, {"windows": windows, "match": stage, "span": span, "fused": fused, "fused_span": fused_span}, reps)
-        ms.update(timed(c, {"unfused": unfused}, unfused_reps, warm=0))
+        legs = {"windows": windows, "match": stage, "span": span, "best": best, "path": path, "fused": fused, "fused_span": fused_span}
+        progress("case", R, M)
+        ms = timed(c, legs, reps)
+        progress("timed", ms)
+        if unfused_reps:
+            ms.update(timed(c, {"unfused": unfused}, unfused_reps, warm=0))
         torch.cuda.synchronize()
         assert torch.equal(res.to(torch.int64), lens64 * 4), "verdicts"
         assert torch.equal(query, w["q"]) and torch.equal(ss_f, ss_w), "the fused call's query or shift_scale != the windows call's"
-        assert torch.equal(hits_f, u["hits"]), "fused hits != the unfused route, bit for bit"
-        assert torch.equal(hits_s, u["hits"]), "stage hits != the unfused route, bit for bit"
+        assert torch.equal(hits_f, hits_s), "fused hits != the stage entry's, bit for bit"
+        if unfused_reps:
+            assert torch.equal(hits_f, u["hits"]), "fused hits != the unfused route, bit for bit"
         q_h, v_h, ref_h = w["q"].cpu().numpy(), valid.cpu().numpy(), ref.cpu().numpy()
         pick = np.linspace(0, n - 1, min(sample, n)).astype(int)
         want = MR.hits(q_h[pick], v_h[pick], QUANT, ref_h, [M] * R)
@@ -233,7 +315,8 @@ def case(c, lens, reps, unfused_reps, seed, shapes, sample):
         out["cases"].append({"R": R, "M": M, "rows_per_lane": C, "cells": cells, "ms": ms, "pairs_at_cost_0": zero,
                              "match_gcells_per_s": round(cells / ms["match"] / 1e6, 1), "fused_minus_windows_gcells_per_s": round(cells / dp_ms / 1e6, 1),
                              "issue_bound_gcells_per_s": round(bound / 1e9, 1), "share_of_bound": round(cells / (ms["match"] * 1e-3) / bound, 3),
-                             "unfused_over_fused": round(ms["unfused"] / ms["fused"], 1), "checked_against_unfused": True,
+                             "unfused_over_fused": round(ms["unfused"] / ms["fused"], 1) if unfused_reps else None, "checked_against_unfused": bool(unfused_reps),
+                             "path": path_leg(c, ms, w["q"], valid, ref, ref_len, mt, span_s, pairs, path_hit, path_rows, M, C, sample, path_caps),
                              "reads_checked_against_match_ref": len(pick),
                              "span": {"over_match": round(ms["span"] / ms["match"], 3), "fused_span_over_fused": round(ms["fused_span"] / ms["fused"], 3),
                                       "gcells_per_s": round(cells / ms["span"] / 1e6, 1), "valu_per_step": SPAN_VALU_PER_STEP[C], "moves_per_step": SPAN_MOVES,
@@ -253,11 +336,13 @@ def main():
     ap.add_argument("--sample", type=int, default=6)
     ap.add_argument("--long", type=int, default=20_000_000, help="samples of the one long read (0: none)")
     ap.add_argument("--shapes", default="24x400,96x400,4x2048", help="R x M, comma separated")
+    ap.add_argument("--path-caps", default="", help="scratch caps (bytes) to time the path stage under, comma separated")
     args = ap.parse_args()
     shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
     c = batch.GpuCodec(0)
     lens = (c.synth_lengths(5, 0, args.reads) // 32 * 32).to(torch.int32)
-    out = {"norm": "med_mad", "headline": case(c, lens, args.reps, args.unfused_reps, 5, shapes, args.sample)}
+    caps = [int(v) for v in args.path_caps.split(",") if v]
+    out = {"norm": "med_mad", "headline": case(c, lens, args.reps, args.unfused_reps, 5, shapes, args.sample, caps)}
     print(json.dumps(out), flush=True)
     if args.long:
         torch.cuda.empty_cache()

@@ -263,6 +263,36 @@ class GpuMatchSpan(ctypes.Structure):
     ]
 
 
+class GpuMatchPair(ctypes.Structure):
+    """struct vbz_gpu_match_pair of include/vbz_gpu.h (16 bytes)."""
+
+    _fields_ = [
+        ("read", ctypes.c_uint32),
+        ("ref", ctypes.c_uint32),
+        ("begin", ctypes.c_uint32),
+        ("end", ctypes.c_uint32),
+    ]
+
+
+class GpuMatchPath(ctypes.Structure):
+    """struct vbz_gpu_match_path of include/vbz_gpu.h (16 bytes)."""
+
+    _fields_ = [
+        ("max_width", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+
+class GpuMatchRow(ctypes.Structure):
+    """struct vbz_gpu_match_row of include/vbz_gpu.h (8 bytes)."""
+
+    _fields_ = [
+        ("begin", ctypes.c_uint32),
+        ("end", ctypes.c_uint32),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -316,6 +346,9 @@ GPU_API = [
     "vbz_gpu_match_span_batch",
     "vbz_gpu_signal_match_span_batch",
     "vbz_gpu_pod5_signal_match_span_batch",
+    "vbz_gpu_match_best_batch",
+    "vbz_gpu_match_path_batch",
+    "vbz_gpu_set_match_path_cap",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -508,6 +541,13 @@ def load():
             twin = getattr(L, name.replace("_span", ""))
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = list(twin.argtypes)
+    if hasattr(L, "vbz_gpu_match_path_batch"):   # (likewise: the winners' table and the warping path of listed pairs)
+        L.vbz_gpu_match_best_batch.restype = ctypes.c_int
+        L.vbz_gpu_match_best_batch.argtypes = [vp, u32, vp, u32, u32, vp]
+        L.vbz_gpu_match_path_batch.restype = ctypes.c_int
+        L.vbz_gpu_match_path_batch.argtypes = [vp, u32, u32, vp, vp, ctypes.POINTER(GpuMatch), vp, ctypes.POINTER(GpuMatchPath), vp, vp]
+        L.vbz_gpu_set_match_path_cap.restype = None
+        L.vbz_gpu_set_match_path_cap.argtypes = [vp, u64]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

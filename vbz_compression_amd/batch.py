@@ -905,6 +905,55 @@ class GpuCodec:
         arguments, hits int32 [n, R, 4] = (cost, end, start, 0)."""
         return self.pod5_signal_match(*args, span=True, **kw)
 
+    # -- signal match: the warping path of chosen pairs (include/vbz_gpu.h: vbz_gpu_match_path) ------------
+    def match_best(self, spans, max_cost=None, out=None):
+        """The winners' table of a span call (include/vbz_gpu.h: vbz_gpu_match_best_batch): spans int32 [n, R, 4] on the device -> pairs
+        int32 [n, 4] = (read, ref, begin, end) on the device (`out` when given): per read the reference of least cost, ties to the
+        smallest index, empty verdicts and costs above max_cost (None: no bound) skipped; ref 0xFFFFFFFF and begin = end = 0 when none
+        qualifies.  No synchronisation."""
+        assert spans.dtype == torch.int32 and spans.is_contiguous() and spans.device == self.device and spans.dim() == 3 and int(spans.shape[2]) == 4, (
+            spans.dtype, spans.shape)
+        n, R = int(spans.shape[0]), int(spans.shape[1])
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, 4), (out.dtype, out.shape)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_match_best_batch(self.ctx, n, spans.data_ptr(), R, 0xFFFFFFFF if max_cost is None else int(max_cost), out.data_ptr()),
+                     "match_best_batch")
+        finally:
+            self._exit(cur)
+        return out
+
+    def match_path(self, query, valid, ref, ref_len, pairs, max_width, match=None, hit=None, rows=None):
+        """The warping path of every listed pair (include/vbz_gpu.h: vbz_gpu_match_path_batch): pairs int32 [p, 4] = (read, ref, begin,
+        end) on the device (match_best's table, or any other: it is untrusted), query / ref / ref_len / match as for match(), valid int32
+        [n] or None (every row has query_len samples: the query arena of a fused span call) -> (hit int32 [p, 4] = (cost, end, start,
+        rows), rows int32 [p, ref_stride, 2] = (begin, end) per reference row, {0, 0} behind the reference's end) on the device.  A
+        pair's window is its samples [begin, end), at most max_width of them (a multiple of 8, 8 ... 65536; it sizes the scratch).  A
+        pair outside the rules gets the empty verdict.  No synchronisation."""
+        n, p = int(query.shape[0]), int(pairs.shape[0])
+        mt = (match or Match(query_len=int(query.shape[1]))).c_struct(ref, ref_len)
+        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, int(mt.query_len)), (
+            query.dtype, query.shape)
+        assert valid is None or (valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n)
+        assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.device == self.device and tuple(pairs.shape) == (p, 4), (pairs.dtype, pairs.shape)
+        if hit is None:
+            hit = torch.empty((p, 4), dtype=torch.int32, device=self.device)
+        if rows is None:
+            rows = torch.empty((p, int(mt.ref_stride), 2), dtype=torch.int32, device=self.device)
+        assert hit.dtype == torch.int32 and hit.is_contiguous() and hit.device == self.device and tuple(hit.shape) == (p, 4), (hit.dtype, hit.shape)
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.device == self.device and tuple(rows.shape) == (p, int(mt.ref_stride), 2), (
+            rows.dtype, rows.shape)
+        path = _lib.GpuMatchPath(int(max_width), 0, 0)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_match_path_batch(self.ctx, p, n, query.data_ptr(), valid.data_ptr() if valid is not None else None, ctypes.byref(mt),
+                                                     pairs.data_ptr(), ctypes.byref(path), hit.data_ptr(), rows.data_ptr()), "match_path_batch")
+        finally:
+            self._exit(cur)
+        return hit, rows
+
     # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
     def _events(self, n, event_first, start):
         """(the C struct, the tables it points to) of n reads' events: event_first int64 [n + 1] on the device; start int32 [rows] on the

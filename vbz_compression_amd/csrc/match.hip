@@ -301,6 +301,217 @@ __global__ __launch_bounds__(256) void match_span_wide_kernel(const float* __res
     match_span_body(WideKey{}, query, valid, N, quant, ref, ref_len, R, ref_stride, out);
 }
 
+// ---- the path calls (vbz_gpu_match_best_batch, vbz_gpu_match_path_batch) -------------------------------------------------------------------
+// The winners' table.  One wavefront per read, whatever R is: the lanes stride over the read's row of the span arena (16-byte loads, a
+// row of R = 24 is one load a lane), keep the least cost << 32 | ref each, and five xor-shuffles leave the wavefront's least in every lane
+// -- least cost first, then the smallest reference.  (One lane per read would walk R dependent 16-byte loads at a stride of 16 R bytes.)
+__global__ __launch_bounds__(256) void match_best_kernel(uint32_t n_reads, const uint4* __restrict__ spans, uint32_t R, uint32_t max_cost,
+                                                         uint4* __restrict__ pairs)
+{
+    const uint32_t read = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (read >= n_reads) return;
+    const uint4* const row = spans + (size_t)read * R;
+    uint64_t best = ~UINT64_C(0);
+    for (uint32_t r = lane; r < R; r += 64u) {
+        const uint32_t cost = row[r].x;
+        const uint64_t key = (uint64_t)cost << 32 | r;
+        if (cost != 0xFFFFFFFFu && cost <= max_cost && key < best) best = key;
+    }
+    for (int o = 32; o != 0; o >>= 1) {
+        const uint64_t other = __shfl_xor(best, o);
+        best = other < best ? other : best;
+    }
+    uint4 out = make_uint4(read, 0xFFFFFFFFu, 0u, 0u);
+    if (best != ~UINT64_C(0)) {   // (a cost of 0xFFFFFFFF never became a key)
+        const uint4 h = row[(uint32_t)best];
+        out = make_uint4(read, (uint32_t)best, h.z, h.y);
+    }
+    if (lane == 0) pairs[read] = out;   // (one 16-byte vector store)
+}
+
+// A pair of the untrusted table: the length of its reference when every condition of the header holds, 0 otherwise -- and then no address
+// was formed from the pair beyond valid[read] and ref_len[ref] of a read and a reference inside the call.
+__device__ __forceinline__ uint32_t match_path_open(const MatchPathArgs& p, uint4 pr)
+{
+    if (pr.x >= p.n_reads || pr.y >= p.R || pr.z >= pr.w) return 0u;
+    const uint32_t n0 = p.valid ? p.valid[pr.x] : p.N, n = n0 < p.N ? n0 : p.N;
+    if (pr.w > n || pr.w - pr.z > p.max_width) return 0u;
+    const uint32_t M = p.ref_len[pr.y];
+    return M <= p.ref_stride ? M : 0u;
+}
+
+// The forward pass of one pair over its window: match_span_pair's schedule over the W columns q[0 ... W), W + la steps, starts relative to
+// the window.  The answer is no running minimum: it is row M - 1 at the last step of lane la, read off the lane's rows once, behind the
+// loop.  Rows behind the reference's end are sinks for both keys here (WideKey's free rows would hold a running minimum nobody wants).
+// Directions.  Behind v_min3_u32, a cell emits two bits: b0 = (min < diag), b1 = (left < up).  b0 == 0 is the diagonal step, the first
+// of the three; otherwise the minimum is min(up, left) and up goes first unless left is strictly smaller.  (b1 means nothing when b0 is 0,
+// and the traceback does not look at it.)  Row 0: lane 0's diag is far, a diagonal step does not exist and the traceback does not look at
+// b0 there; its `up` is the key (0, j), which its left beats exactly when the left's cost is 0 -- b1 there is the sit on row 0, no b1 the
+// stop.  A bit is the sign of a difference, and v_alignbit_b32 shifts it into the lane's accumulator: a subtraction and an alignbit a
+// bit, 4 VALU instructions a cell more than the span kernel's two (compares and selects -- v_cmp, v_cndmask, v_lshl_or a bit -- were 6
+// more: DESIGN.md 4.22 "The path").  The sign is the comparison for operands below half the range, which the keys of every cell the
+// traceback reads are: it reads (i, j) with j > 0 alone, where left, up and (above row 0) diag are true cells, below the far value.
+// Layout.  A lane's cells, step after step and its C rows down, fill words of 16 cells, the first cell in the top bits: cell (t, i) of
+// lane l is cell number t C + i mod C of its stream, word g = number / 16 stands at bits[g * 64 + l].  Every lane closes word g at the same
+// step, so a store is one 256-byte line.  Lanes that have not met the window yet, or have left it, and sink rows store junk that the
+// traceback never reads: it reads (i, j) at step j + l of lane l <= la alone, and steps 0 ... W - 1 + la are all stored.  No LDS.
+__device__ __forceinline__ uint32_t match_sign_less(uint32_t a, uint32_t b) { return a - b; }                       // bit 31: a < b
+__device__ __forceinline__ uint32_t match_sign_less(uint64_t a, uint64_t b) { return (uint32_t)((a - b) >> 32); }
+
+template <int C, typename Key>
+__device__ __forceinline__ uint32_t match_path_forward(const Key key, const float* __restrict__ q, uint32_t W, float quant, const int8_t* __restrict__ ref,
+                                                       uint32_t M, uint32_t* __restrict__ bits)
+{
+    using T = typename Key::T;
+    constexpr int SPD = C <= 16 ? 16 / C : 1;   // steps per word (C = 32: two words a step)
+    constexpr int UN = SPD < 2 ? 2 : SPD;       // steps a turn: even, as in match_pair
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t la = (M - 1u) / (uint32_t)C;
+    const T far = key.far();
+    uint32_t r[C];
+    T cur[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        const uint32_t row = lane * (uint32_t)C + (uint32_t)i;
+        r[i] = row < M ? key.ref_word(ref[row]) : 0u;   // (no address behind M)
+        cur[i] = far;
+    }
+    const T far0 = lane == 0 ? far : (T)0;
+    T diag = far;
+    uint32_t k = key.query_word(0x180u);
+    uint32_t acc = 0;
+    uint32_t* const out = bits + lane;
+    const uint32_t steps = W + la;
+    float z = lane < W ? q[lane] : 0.0f;
+    for (uint32_t t0 = 0; t0 < steps; t0 += 64u) {
+        const uint32_t kq = key.query_word(match_level(z, quant));
+        const uint32_t next = t0 + 64u + lane;
+        z = next < W ? q[next] : 0.0f;
+        const uint32_t block = steps - t0 < 64u ? steps - t0 : 64u;
+        auto step = [&](uint32_t s, bool close) {   // close: the step fills the lane's word (C <= 16)
+            const T up = key.prev_lane(cur[C - 1], t0 + s);
+            const uint32_t k0 = (uint32_t)__builtin_amdgcn_readlane((int)kq, (int)s);
+            k = (uint32_t)__builtin_amdgcn_update_dpp((int)k0, (int)k, 0x138, 0xF, 0xF, false);
+            T d = diag, u = up;
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                const T left = cur[i];
+                const T m = min(min(d, u), left);
+                acc = __builtin_amdgcn_alignbit(acc, match_sign_less(m, d), 31);      // acc << 1 | (m < d)
+                acc = __builtin_amdgcn_alignbit(acc, match_sign_less(left, u), 31);   // acc << 1 | (left < u)
+                u = key.cell(k, r[i], m, m, m);
+                d = left;
+                cur[i] = u;
+                if (C == 32 && i % 16 == 15) out[((t0 + s) * 2u + (uint32_t)(i / 16)) * 64u] = acc;
+            }
+            diag = up | far0;
+            if (C <= 16 && close) out[((t0 + s) / (uint32_t)SPD) * 64u] = acc;
+        };
+        uint32_t s = 0;   // (t0 is a multiple of 64, 64 and UN of SPD: a word closes at the steps e with (e + 1) % SPD == 0 of a turn)
+        for (; s + (uint32_t)UN <= block; s += (uint32_t)UN) {
+#pragma unroll
+            for (int e = 0; e < UN; ++e) step(s + (uint32_t)e, (e + 1) % SPD == 0);
+        }
+        for (; s < block; ++s) step(s, (s + 1u) % (uint32_t)SPD == 0);
+    }
+    if (C <= 16 && steps % (uint32_t)SPD != 0)   // the open word: its cells to the top
+        out[(steps / (uint32_t)SPD) * 64u] = acc << (32u - 2u * (uint32_t)C * (steps % (uint32_t)SPD));
+    // row M - 1 of lane la at its last step, the last step of all
+    const uint32_t sel = (M - 1u) % (uint32_t)C;
+    T a = cur[0];
+#pragma unroll
+    for (int i = 1; i < C; ++i) a = sel == (uint32_t)i ? cur[i] : a;
+    return key.cost(key.uniform(a, la));
+}
+
+// grid ceil(count / 4) workgroups of four wavefronts, a wavefront a pair.  Besides the pass, the wavefront writes what the traceback
+// does not: the rows behind the reference's end as {0, 0}, and of a pair that fails match_path_open the empty verdict and every row.
+template <typename Key>
+__device__ __forceinline__ void match_path_forward_body(const Key key, const MatchPathArgs& p)
+{
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    if (w >= p.count) return;
+    const size_t pi = (size_t)p.first + w;
+    const uint4 pl = p.pairs[pi];
+    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
+                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint32_t M = __builtin_amdgcn_readfirstlane(match_path_open(p, pr));
+    uint2* const rows = p.rows + pi * p.ref_stride;
+    for (uint32_t i = M + lane; i < p.ref_stride; i += 64u) rows[i] = make_uint2(0u, 0u);
+    if (M == 0) {
+        if (lane == 0) p.hit[pi] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+        return;
+    }
+    const float* const q = p.query + (size_t)pr.x * p.N + pr.z;
+    const int8_t* const row = p.ref + (size_t)pr.y * p.ref_stride;
+    uint32_t* const bits = p.bits + (size_t)w * p.pair_words;
+    const uint32_t W = pr.w - pr.z;
+    uint32_t cost;
+    if (M <= 64u) cost = match_path_forward<1>(key, q, W, p.quant, row, M, bits);
+    else if (M <= 128u) cost = match_path_forward<2>(key, q, W, p.quant, row, M, bits);
+    else if (M <= 256u) cost = match_path_forward<4>(key, q, W, p.quant, row, M, bits);
+    else if (M <= 512u) cost = match_path_forward<8>(key, q, W, p.quant, row, M, bits);
+    else if (M <= 1024u) cost = match_path_forward<16>(key, q, W, p.quant, row, M, bits);
+    else cost = match_path_forward<32>(key, q, W, p.quant, row, M, bits);
+    if (lane == 0) p.cost[w] = cost;
+}
+
+__global__ __launch_bounds__(256) void match_path_forward_kernel(const MatchPathArgs p, uint32_t sb) { match_path_forward_body(PackedKey{ sb }, p); }
+__global__ __launch_bounds__(256) void match_path_forward_wide_kernel(const MatchPathArgs p) { match_path_forward_body(WideKey{}, p); }
+
+// The traceback, one wavefront per pair: at most W + M dependent steps.  It writes rows 0 ... M - 1 and the hit (one 16-byte store) of the
+// pairs that pass match_path_open; the forward launch wrote the rest.  The walk cannot leave the pair's words or run on whatever the bits
+// hold: every step lowers i or j, and j == 0 forces up.  The walk itself is one dependent chain whoever walks it, so the whole wavefront
+// walks it in scalar registers; what the wavefront adds is the fetch: the 64 words of lane l's stream that end at the word the walk needs are loaded
+// by one instruction, lane k taking word g - k, and a step reads its word out of that register by v_readlane.  Inside a lane's stream
+// the walk only moves to smaller cell numbers (up: one cell, left: c cells), so a fetch serves 1 024 cells -- 1 024 / c columns -- or lasts
+// until the walk crosses into the lane above.  Rows leave 64 at a time: lane i mod 64 keeps row i, and the 64 lanes store a 512-byte
+// stretch when the walk leaves row 64 k.
+__global__ __launch_bounds__(256) void match_path_trace_kernel(const MatchPathArgs p)
+{
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    if (w >= p.count) return;
+    const size_t pi = (size_t)p.first + w;
+    const uint4 pl = p.pairs[pi];
+    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
+                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint32_t M = __builtin_amdgcn_readfirstlane(match_path_open(p, pr));
+    if (M == 0) return;
+    const uint32_t lc = M <= 64u ? 0u : M <= 128u ? 1u : M <= 256u ? 2u : M <= 512u ? 3u : M <= 1024u ? 4u : 5u;
+    const uint32_t* const bits = p.bits + (size_t)w * p.pair_words;
+    uint2* const rows = p.rows + pi * p.ref_stride;
+    const uint32_t a = pr.z;
+    uint32_t i = M - 1u, j = pr.w - pr.z - 1u, end = j + 1u;
+    uint32_t have_l = 0xFFFFFFFFu, top = 0, cache = 0;   // lane k holds word top - k of lane have_l's stream
+    uint2 mine = make_uint2(0u, 0u);
+    for (;;) {
+        uint32_t dir = 2u;   // 0, 1: diagonal; 2: up (row 0: stop); 3: left.  Column a: up
+        if (j != 0) {
+            const uint32_t l = i >> lc, cell = ((j + l) << lc) + (i & ((1u << lc) - 1u)), g = cell >> 4;
+            if (l != have_l || g > top || g + 63u < top) {
+                have_l = l, top = g;
+                cache = lane <= g ? bits[(size_t)(g - lane) * 64u + l] : 0u;
+            }
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)cache, (int)(top - g));
+            dir = (word >> (30u - 2u * (cell & 15u))) & 3u;
+            if (i == 0) dir |= 2u;   // (row 0 has no diagonal step: b1 alone)
+        }
+        if (dir == 3u) {
+            --j;
+            continue;
+        }
+        if (i == 0) break;
+        if (lane == (i & 63u)) mine = make_uint2(a + j, a + end);
+        if ((i & 63u) == 0 && i + lane < M) rows[i + lane] = mine;   // rows i ... i + 63 are walked
+        --i;
+        if (dir < 2u) --j;
+        end = j + 1u;
+    }
+    if (lane == 0) mine = make_uint2(a + j, a + end);
+    if (lane < M) rows[lane] = mine;
+    if (lane == 0) p.hit[pi] = make_uint4(p.cost[w], pr.w, a + j, M);
+}
+
 // valid[i] of the fused calls: min(T', N) from the read's verdict (T x 4 bytes on success) and the range tables; an error: 0
 __global__ void match_valid_kernel(uint32_t n, const uint32_t* __restrict__ result, const uint32_t* __restrict__ rbegin, const uint32_t* __restrict__ rend,
                                    uint32_t N, uint32_t* __restrict__ valid)
@@ -347,6 +558,32 @@ hipError_t launch_match_span(uint32_t n_reads, const float* query, const uint32_
                            reinterpret_cast<uint4*>(out));
     else
         hipLaunchKernelGGL(match_span_wide_kernel, grid, dim3(256), 0, s, query, valid, N, quant, ref, ref_len, R, ref_stride, reinterpret_cast<uint4*>(out));
+    return hipGetLastError();
+}
+
+hipError_t launch_match_best(uint32_t n_reads, const void* spans, uint32_t R, uint32_t max_cost, void* pairs, hipStream_t s)
+{
+    if (n_reads == 0) return hipSuccess;
+    hipLaunchKernelGGL(match_best_kernel, dim3((n_reads + 3u) / 4u), dim3(256), 0, s, n_reads, reinterpret_cast<const uint4*>(spans), R, max_cost,
+                       reinterpret_cast<uint4*>(pairs));
+    return hipGetLastError();
+}
+
+hipError_t launch_match_path_forward(const MatchPathArgs& a, hipStream_t s)
+{
+    if (a.count == 0) return hipSuccess;
+    const dim3 grid((a.count + 3u) / 4u);
+    if (match_span_packed(a.max_width, a.ref_stride))
+        hipLaunchKernelGGL(match_path_forward_kernel, grid, dim3(256), 0, s, a, match_span_start_bits(a.max_width));
+    else
+        hipLaunchKernelGGL(match_path_forward_wide_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_path_trace(const MatchPathArgs& a, hipStream_t s)
+{
+    if (a.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(match_path_trace_kernel, dim3((a.count + 3u) / 4u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -149,6 +149,21 @@ struct Pod5Tables
     }
 };
 
+// One group of a path call (launch_match_path_forward, launch_match_path_trace): the pairs' direction bits, pair_words words a pair
+// (match_path_groups.h), and the forward pass's costs
+struct MatchPathScratch
+{
+    uint32_t* bits = nullptr;   // [pairs x pair_words]
+    uint32_t* cost = nullptr;   // [pairs]
+    size_t carve(void* base, uint32_t pairs, uint64_t pair_words)
+    {
+        MetaCarver mc(base);
+        bits = mc.take<uint32_t>((size_t)pairs * (size_t)pair_words);
+        cost = mc.take<uint32_t>(pairs);
+        return mc.bytes();
+    }
+};
+
 // One array of n elements in a buffer of its own: what to allocate for it
 template <typename T>
 size_t array_bytes(size_t n)

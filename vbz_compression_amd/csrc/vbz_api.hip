@@ -22,6 +22,7 @@
 #include "../../include/vbz_gpu.h"
 #include "vbz_kernels.h"
 #include "scratch_tables.h"
+#include "match_path_groups.h"
 
 using namespace vbzhip;
 
@@ -169,6 +170,7 @@ struct Knobs
     bool zero_run_sequences = true;
     bool long_repeats = true;     // VBZ_HIP_LONG_REPEATS=0: no search for a repeat distance
     int phase_timing = 0;         // VBZ_HIP_PHASE_TIMING: 1 phase counters of the entropy kernels (one launch per frame), 2 / 3 of the encoder's planning / packing launch (staged, under load)
+    uint64_t match_path_cap = MATCH_PATH_CAP_DEFAULT;   // vbz_gpu_set_match_path_cap / VBZ_HIP_MATCH_PATH_CAP: bytes of direction bits a group of a path call may take
     bool trace = false;           // VBZ_HIP_TRACE=1: synchronise after every launch group and name it on stderr (to find a faulting kernel)
 };
 
@@ -229,6 +231,7 @@ struct vbz_gpu_ctx
     DevBuf normslab;           // ... and, on the large-read path, the counts of a launch group (NORM_SLAB words per read)
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables, the reads' constants (Pod5Tables)
     DevBuf matchmeta;          // signal match: the fused calls' own window tables, valid[] and, for a caller that takes none, read_result (MatchTables)
+    DevBuf matchpath;          // the path call: one group's direction bits and costs (MatchPathScratch)
     bool profiling = false;    // (not a setting: outside Knobs; the upper half of a split call gets the call's)
     PinnedBuf pinned;          // the single-buffer API's pinned area (run_one)
     uint32_t one_seq = 0;      // the single-buffer API's hand-back flag: a number per call (run_one)
@@ -2126,6 +2129,7 @@ vbz_gpu_ctx* vbz_gpu_create(int device, void* stream)
     if (const char* e = getenv("VBZ_HIP_TRAILERS")) c->knobs.trailers = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_CANONICAL")) c->knobs.canonical = atoi(e) != 0;
     if (const char* e = getenv("VBZ_HIP_CHECKSUM")) c->knobs.checksum = atoi(e) != 0;
+    if (const char* e = getenv("VBZ_HIP_MATCH_PATH_CAP")) vbz_gpu_set_match_path_cap(c, strtoull(e, nullptr, 10));
     if (const char* e = getenv("VBZ_HIP_SPLIT_MIN")) c->knobs.split_min = (uint32_t)strtoul(e, nullptr, 10);   // 0: a batch is never coded as two halves
 #ifdef VBZ_EXPERIMENTS
     if (const char* e = getenv("VBZ_HIP_PHASE_TIMING")) c->knobs.phase_timing = atoi(e);   // timed instantiations of the entropy kernels
@@ -2183,6 +2187,10 @@ void vbz_gpu_set_canonical(vbz_gpu_ctx* c, int enable)
 void vbz_gpu_set_checksum(vbz_gpu_ctx* c, int enable)
 {
     if (c) c->knobs.checksum = enable != 0;
+}
+void vbz_gpu_set_match_path_cap(vbz_gpu_ctx* c, uint64_t bytes)
+{
+    if (c) c->knobs.match_path_cap = bytes != 0 ? bytes : MATCH_PATH_CAP_DEFAULT;
 }
 const char* vbz_gpu_last_error(vbz_gpu_ctx* c) { return c ? c->error.c_str() : "no context"; }
 
@@ -2538,6 +2546,78 @@ int vbz_gpu_pod5_signal_match_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).matched(match, query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+static_assert(sizeof(vbz_gpu_match_pair) == 16 && offsetof(vbz_gpu_match_pair, read) == 0 && offsetof(vbz_gpu_match_pair, ref) == 4 &&
+                  offsetof(vbz_gpu_match_pair, begin) == 8 && offsetof(vbz_gpu_match_pair, end) == 12,
+              "vbz_gpu_match_pair is 16 bytes: read, ref, begin, end");
+static_assert(sizeof(vbz_gpu_match_path) == 16 && offsetof(vbz_gpu_match_path, max_width) == 0 && offsetof(vbz_gpu_match_path, flags) == 4 &&
+                  offsetof(vbz_gpu_match_path, reserved) == 8,
+              "vbz_gpu_match_path is 16 bytes: max_width, flags, reserved");
+static_assert(sizeof(vbz_gpu_match_row) == 8 && offsetof(vbz_gpu_match_row, begin) == 0 && offsetof(vbz_gpu_match_row, end) == 4,
+              "vbz_gpu_match_row is 8 bytes: begin, end");
+
+int vbz_gpu_match_best_batch(vbz_gpu_ctx* c, uint32_t n_reads, const vbz_gpu_match_span* spans, uint32_t n_refs, uint32_t max_cost, vbz_gpu_match_pair* pairs)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (n_refs < 1 || n_refs > 4096 || (uint64_t)n_reads * n_refs > EXTENT_MAX / sizeof(vbz_gpu_match_span)) {
+        set_error(c, "match best outside the rules (%u reads, n_refs %u)", n_reads, n_refs);
+        return -2;
+    }
+    if ((n_reads != 0 && (!spans || !pairs)) || (((uintptr_t)spans | (uintptr_t)pairs) & 15u) != 0) {
+        set_error(c, "the span arena or the pair table is NULL or not 16-byte aligned");
+        return -2;
+    }
+    Timed t(c, "match_best");
+    HIPCHK(c, launch_match_best(n_reads, spans, n_refs, max_cost, pairs, c->stream), "match best launch");
+    return 0;
+}
+
+int vbz_gpu_match_path_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match,
+                             const vbz_gpu_match_pair* pairs, const vbz_gpu_match_path* path, vbz_gpu_match_span* hit, vbz_gpu_match_row* rows)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    // (the match's own rules, the query's extent and the alignment of ref, query and hit; the tables a call with pairs needs: below)
+    if (!match_ok(c, match, query, hit, sizeof(vbz_gpu_match_span), 0)) return -2;
+    if (!path || path->flags != 0 || path->reserved != 0 || path->max_width < 8 || path->max_width > 65536 || path->max_width % 8 != 0) {
+        set_error(c, "path is NULL or outside the rules (max_width %u, flags %u)", path ? path->max_width : 0u, path ? path->flags : 0u);
+        return -2;
+    }
+    if (n_pairs != 0 && (!match->ref || !match->ref_len || !query || !pairs || !hit || !rows)) {
+        set_error(c, "ref, ref_len, the query arena, the pair table, the hit table or the row arena is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)pairs | (uintptr_t)rows) & 15u) != 0) {
+        set_error(c, "the pair table or the row arena is not 16-byte aligned");
+        return -2;
+    }
+    if ((uint64_t)n_pairs * match->ref_stride > EXTENT_MAX / sizeof(vbz_gpu_match_row) || (uint64_t)n_reads * match->query_len > EXTENT_MAX / sizeof(float)) {
+        set_error(c, "declared path arenas are not plausible (%u pairs, %u reads)", n_pairs, n_reads);
+        return -2;
+    }
+    if (n_pairs == 0) return 0;
+    MatchPathArgs a{};
+    a.query = query, a.valid = valid, a.n_reads = n_reads, a.N = match->query_len, a.quant = match->quant;
+    a.ref = match->ref, a.ref_len = match->ref_len, a.R = match->n_refs, a.ref_stride = match->ref_stride;
+    a.pairs = reinterpret_cast<const uint4*>(pairs), a.max_width = path->max_width;
+    a.pair_words = match_path_pair_words(a.max_width, a.ref_stride);
+    a.hit = reinterpret_cast<uint4*>(hit), a.rows = reinterpret_cast<uint2*>(rows);
+    const uint32_t group = match_path_group_pairs(n_pairs, a.max_width, a.ref_stride, c->knobs.match_path_cap);
+    MatchPathScratch sc;
+    if (!ensure_carved(c, c->matchpath, sc, group, a.pair_words)) return -1;
+    a.bits = sc.bits, a.cost = sc.cost;
+    for (uint32_t first = 0; first < n_pairs; first += group) {   // (the groups share the scratch: the stream orders them)
+        a.first = first, a.count = n_pairs - first < group ? n_pairs - first : group;
+        {
+            Timed t(c, "match_path_forward");
+            HIPCHK(c, launch_match_path_forward(a, c->stream), "match path forward launch");
+        }
+        Timed t(c, "match_path_trace");
+        HIPCHK(c, launch_match_path_trace(a, c->stream), "match path traceback launch");
+    }
+    return 0;
 }
 
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)

@@ -755,6 +755,32 @@ hipError_t launch_match(uint32_t n_reads, const float* query, const uint32_t* va
 // or the wide one, by match_select.h from N and ref_stride alone.
 hipError_t launch_match_span(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* ref,
                              const uint32_t* ref_len, uint32_t R, uint32_t ref_stride, void* out, hipStream_t s);
+// The path calls (vbz_gpu_match_best_batch, vbz_gpu_match_path_batch).  launch_match_best: pairs[i] = {i, the reference of least cost
+// <= max_cost among spans[i R ... i R + R), its start, its end} or {i, 0xFFFFFFFF, 0, 0}; 16-byte entries both.
+hipError_t launch_match_best(uint32_t n_reads, const void* spans, uint32_t R, uint32_t max_cost, void* pairs, hipStream_t s);
+// One group of a path call: pairs first ... first + count - 1 of the caller's table, slot w = pair - first of the scratch.
+struct MatchPathArgs
+{
+    const float* query;      // [n_reads, N]
+    const uint32_t* valid;   // [n_reads], or nullptr: N samples a row
+    uint32_t n_reads, N;
+    float quant;
+    const int8_t* ref;       // [R, ref_stride]
+    const uint32_t* ref_len; // [R], untrusted
+    uint32_t R, ref_stride;
+    const uint4* pairs;      // {read, ref, begin, end}, untrusted
+    uint32_t max_width;
+    uint32_t first, count;
+    uint64_t pair_words;     // match_path_pair_words(max_width, ref_stride)
+    uint32_t* bits;          // [count x pair_words]: the direction bits (MatchPathScratch)
+    uint32_t* cost;          // [count]: the forward pass's cost
+    uint4* hit;              // [n_pairs]
+    uint2* rows;             // [n_pairs, ref_stride]
+};
+// The forward launch (the packed kernel or the wide one, by match_select.h with max_width in N's place) and the traceback behind it.  Between
+// them every hit and every row of the group's pairs is written.
+hipError_t launch_match_path_forward(const MatchPathArgs& a, hipStream_t s);
+hipError_t launch_match_path_trace(const MatchPathArgs& a, hipStream_t s);
 // ... the fused calls' tables.  launch_match_windows: the window tables of "one row per read at start 0" (first: n + 1 entries, start: n).
 // launch_match_valid, behind the decode: valid[i] = min(T', N) from the verdict result[i] (T x 4 bytes; an error: 0) and the range tables
 // (nullable), clamped as sample_range clamps them.
