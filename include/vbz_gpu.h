@@ -934,6 +934,69 @@ VBZ_EXPORT int vbz_gpu_match_path_batch(vbz_gpu_ctx* ctx, uint32_t n_pairs, uint
 /* The bytes of direction bits one group of a path call may take (0: the default). */
 VBZ_EXPORT void vbz_gpu_set_match_path_cap(vbz_gpu_ctx* ctx, uint64_t bytes);
 
+/* Signal locate.  The other orientation of the match calls, the one target filtering needs: the read's prefix is the sequence that is
+ * matched WHOLE, against a stretch of a long expected squiggle of a target -- an amplicon, a plasmid, a viral genome on both strands, tens
+ * of thousands to millions of levels.  The rule (tests/locate_ref.py):
+ * Query.  Exactly the match calls' query: n = min(T', N) samples of the read's range, converted as the windows call converts them and
+ * quantised with quant by the match rule (NaN -> 0, clamp to +-127, rint to nearest even).  N = query_len <= 2048.
+ * Targets.  G = n_targets rows of int8 in a device matrix target[G][target_stride]; row g has L_g = target_len[g] valid entries, taken as
+ * they are (-128 is legal).  target_len is an untrusted device table: L_g == 0 or L_g > target_stride gives column g the empty verdict for
+ * every read, and no address is formed from it.
+ * Cost.  c(i, j) = |k_i - g_j| in integers, rows the query, columns the target:
+ *   D[0][j] = c(0, j)                                             (the alignment may start anywhere in the target)
+ *   D[i][0] = c(i, 0) + D[i-1][0]
+ *   D[i][j] = c(i, j) + min(D[i-1][j-1], D[i-1][j], D[i][j-1])
+ *   cost = min_j D[n-1][j]          end = 1 + the SMALLEST j that attains it
+ * The whole query is aligned to a stretch of the target that ends at `end` (exclusive, in target coordinates).  D <= 255 n < 2^20 whatever
+ * L is, and end <= 2^30.  This is the match rule with its arguments exchanged: tests/match_ref.py's dtw_batch(levels of the read,
+ * target[None, :L], [L]).  The empty verdict {0xFFFFFFFF, 0}: n == 0, an empty range, a read whose verdict is an error, or a refused
+ * target_len.
+ * Output.  out is a row-major [n_reads, G] arena of vbz_gpu_match_hit (8 bytes), 16-byte aligned.  Every entry is written by every call
+ * that launches; nothing else is written, apart from query and shift_scale.
+ * The three calls have the argument lists of their match twins with vbz_gpu_locate in vbz_gpu_match's place.  vbz_gpu_locate_batch is the
+ * stage entry: query is a row-major [n_reads, N] float32 arena, 16-byte aligned, valid[i] (device, untrusted) is clamped to N.
+ * vbz_gpu_signal_locate_batch and its POD5 twin behave as the fused match calls do: the windows call into the caller's REQUIRED query
+ * arena under the library's own tables, valid[] from the verdicts and the range tables, then the locate launch on the context's stream; a
+ * bad first_row fails the whole call as there.  Return codes and refusals (-2, nothing launched, nothing written) are those of the match
+ * twins, with the rules of the struct below; the size rules are n_reads * G * 8, G * target_stride and n_reads * N * 4 beyond 2^46 bytes.
+ * How: match.hip's systolic schedule with the operands exchanged (csrc/locate.hip).  One wavefront per (read, target)
+ * pair; the lanes hold the read's quantised prefix, c = 1 ... 32 rows a lane by n; the target streams through as int8, a dword a lane for
+ * 256 steps, one level a step.  The four wavefronts of a workgroup take four reads against one target row.  A step is 8.25 + 2 c VALU
+ * instructions in the disassembly (match_kernel: 9 + 2 c).  No LDS, no barrier.
+ * Not here: the start of the stretch and the path (start bits of 17 and more rule out the packed key); cutting one target across
+ * wavefronts (a stretch has no bound in DTW, so a cut with overlap is not exact: a caller who wants more parallelism for a small batch
+ * passes overlapping tiles as target rows and reads one hit per tile).
+ * Measured on one MI355X (tools/time_locate.py, profiles/locate_time.json; the parent of the commit that adds these calls is b74e1b0; median
+ * of 20, calls alternating in one process): synthetic reads of ~100 k samples, MED_MAD, N = 2 048 behind the trim call's begin[], quant 32,
+ * G = 2 targets.  8 192 reads against L = 30 000: 58.59 ms fused, 2.65 ms for the windows call alone, 55.97 ms for the stage entry, and
+ * 58.21 ms for the parent's only route over the same cells -- vbz_gpu_match_batch with the roles swapped, the target written out as float32
+ * and the reads quantised by the caller -- whose hits equal these bit for bit; L = 48 000: 92.12 / 2.67 / 89.48 / 93.22 ms.  That is 18.0 T
+ * cells/s and 279 cycles a step, against an issue bound of 290 (72.25 VALU instructions at 4.1 cycles, the twelve plain moves of a turn at
+ * 2.2) and the swapped match's 17.3 T.  512 reads are one wavefront a SIMD, which issues an instruction every 5.1 cycles, not 4.1: 5.36 /
+ * 0.77 / 4.59 / 4.62 ms at L = 30 000 and 8.13 / 0.78 / 7.34 / 7.33 ms at L = 48 000 (13.7 T cells/s, 366 cycles a step, the swapped
+ * match's time to within its spread).  One target of L = 1 048 576 against 512 reads, which no match call can express: 160.99 / 0.81 /
+ * 160.31 ms -- 512 wavefronts on 1 024 SIMDs, each walking its 1 048 639 steps alone. */
+typedef struct vbz_gpu_locate
+{
+    uint32_t query_len;         /* N: a multiple of 8, 8 ... 2048 (64 lanes x 32 rows) */
+    uint32_t n_targets;         /* G: 1 ... 4096 */
+    uint32_t target_stride;     /* bytes per row of target: a multiple of 16, 16 ... 2^30 */
+    uint32_t flags;             /* must be 0 */
+    float quant;                /* finite, > 0 */
+    uint32_t reserved;          /* must be 0 */
+    const int8_t* target;       /* device, 16-byte aligned, n_targets x target_stride */
+    const uint32_t* target_len; /* device, n_targets words */
+} vbz_gpu_locate;               /* 40 bytes */
+VBZ_EXPORT int vbz_gpu_locate_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate,
+                                    vbz_gpu_match_hit* out);
+VBZ_EXPORT int vbz_gpu_signal_locate_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                           const vbz_gpu_signal_format* format, const vbz_gpu_normalization* norm, float* shift_scale,
+                                           const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate, float* query, vbz_gpu_match_hit* out);
+VBZ_EXPORT int vbz_gpu_pod5_signal_locate_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
+                                                const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
+                                                const vbz_gpu_locate* locate, float* query, vbz_gpu_match_hit* out);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -1,0 +1,234 @@
+#!/usr/bin/env python3
+"""Cost of the locate calls (vbz_gpu_locate_batch, vbz_gpu_signal_locate_batch) against the windows call alone and against the only route
+the parent has for the same cells, vbz_gpu_match_batch with the roles swapped; the calls alternate in one process.
+
+Workload: --reads reads of ~100 k int16 samples of the synthetic signal (the lengths of SURVEY.md 8d, rounded down to 32), synthesised on
+the device and compressed once; the trim call's begin[] (its defaults, MED_MAD) is the range's begin; the query is the first N = 2 048
+samples behind it, MED_MAD-normalised, quant 32.  The targets are synthetic squiggles -- plateaus of 6 levels under noise, inside +-127 --
+with the whole quantised query of a few reads planted in them, so some pairs cost nothing and most do not.  Cases (reads x G x L): 512 and
+8 192 reads against G = 2 targets of L = 30 000 and of L = 48 000, and 512 reads against one target of L = 1 048 576.  Each leg behind
+untimed warm-up calls and timed with HIP events on the codec's stream (median of --reps calls):
+  windows   the windows call alone (one row per read at start 0, L = N, float32): the fused call's floor
+  locate    the stage entry alone, on the query the windows call left
+  fused     the fused call: query, hits and shift_scale
+  swapped   wherever L <= 65 536: vbz_gpu_match_batch over the same cells -- the targets written out as float32 level / quant "queries" of
+            query_len = the target's stride, the reads' levels, quantised here with torch, as int8 "references" of M = 2 048 (4 096 of them a
+            call, the rule's most).  Its hits must equal the locate call's bit for bit in the same run.
+Six reads are checked against tests/locate_ref.py on the host where the target is short enough for numpy (L <= 65 536).
+
+Next to the measured cells per second and cycles a step stands the kernel's issue bound: VALU instructions a wavefront issues per step of
+locate_pair<C>'s four-step turn, counted in the disassembly of locate.hip (8.25 + 2 c: per turn eight DPP moves, one v_readlane, four
+v_min_u32 / v_cmp / v_cndmask of the running minimum and twelve v_mov_b32, and v_min3_u32 + v_msad_u8 per row and step), at 4.1 cycles an
+instruction and 2.2 for the plain moves (profiles/r06_valu_rate.txt), on 256 CUs x 4 SIMDs at 2.4 GHz.
+
+    python tools/time_locate.py [--reps 20] [--sample 6] [--cases 512x2x30000,...]"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import locate_ref as LR  # noqa: E402
+from vbz_compression_amd import batch  # noqa: E402
+
+N = 2048
+QUANT = 32.0
+TURN = 4                 # steps a turn of the inner loop
+TURN_VALU = 33           # VALU instructions a turn besides the cells
+TURN_MOVES = 12          # ... of which plain v_mov_b32
+CYCLES_PER_VALU = 4.1
+CYCLES_PER_MOVE = 2.2
+SIMDS, HZ = 256 * 4, 2.4e9
+MATCH_REFS = 4096        # vbz_gpu_match.n_refs at most
+
+
+def progress(*what):
+    print("#", *what, file=sys.stderr, flush=True)
+
+
+def timed(c, fns, reps, warm=2):
+    """(median, lowest, highest) milliseconds of every fn, the fns alternating call by call"""
+    ms = {k: [] for k in fns}
+    with torch.cuda.stream(c.stream):
+        for _ in range(warm):
+            for f in fns.values():
+                f()
+        for _ in range(reps):
+            for k, f in fns.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                f()
+                b.record()
+                b.synchronize()
+                ms[k].append(a.elapsed_time(b))
+    return {k: (round(statistics.median(v), 4), round(min(v), 4), round(max(v), 4)) for k, v in ms.items()}
+
+
+def torch_quantize(z):
+    v = z * QUANT
+    return torch.where(torch.isnan(v), torch.zeros_like(v), torch.clamp(torch.round(v), -127.0, 127.0)).to(torch.int8)
+
+
+def step_cycles(C):
+    """(VALU instructions a step, its cycles at 4.1 an instruction, its cycles with the plain moves at 2.2)"""
+    valu = TURN_VALU / TURN + 2 * C
+    return valu, valu * CYCLES_PER_VALU, valu * CYCLES_PER_VALU - TURN_MOVES / TURN * (CYCLES_PER_VALU - CYCLES_PER_MOVE)
+
+
+class Reads:
+    """--reads compressed reads, their trim points, and the query the windows call leaves"""
+
+    def __init__(self, c, n, seed=5):
+        self.c, self.n = c, n
+        dev = c.device
+        lens = (c.synth_lengths(seed, 0, n) // 32 * 32).to(torch.int32)
+        self.opts = opts = c.options(True, 2, 1, 1)
+        lens64 = lens.to(torch.int64)
+        sizes = lens64 * 2
+        self.off = off = torch.cumsum(sizes, 0) - sizes
+        with torch.cuda.stream(c.stream):
+            raw = torch.empty(int(lens64.sum()) * 2, dtype=torch.uint8, device=dev)
+            c.synth_signal(seed, 0, raw, off, lens)
+            caps = torch.tensor([c.L.vbz_max_compressed_size(int(s), ctypes.byref(opts)) for s in sizes.cpu().tolist()], dtype=torch.int64)
+            coff, ctotal = batch.layout(caps, 64)
+            self.comp = torch.empty(ctotal, dtype=torch.uint8, device=dev)
+            self.coff = coff.to(dev)
+            self.csize = torch.zeros(n, dtype=torch.int32, device=dev)
+            c.compress(raw, off, sizes.to(torch.int32), self.comp, self.coff, caps.to(torch.int32).to(dev), self.csize, opts)
+        torch.cuda.synchronize()
+        del raw
+        self.lens, self.lens64, self.size32 = lens, lens64, sizes.to(torch.int32)
+        self.res = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.begin = torch.zeros(n, dtype=torch.int32, device=dev)
+        c.signal_trim(self.comp, self.coff, self.csize, off, self.size32, self.res, opts, batch.MED_MAD, out=self.begin)
+        torch.cuda.synchronize()
+        self.valid = torch.clamp(lens64 - torch.minimum(self.begin.to(torch.int64), lens64), max=N).to(torch.int32)
+        self.wfirst = torch.arange(n + 1, dtype=torch.int64, device=dev)
+        self.wstart = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.ss_w = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+        self.q = None
+        with torch.cuda.stream(c.stream):
+            self.windows()
+        torch.cuda.synchronize()
+        self.levels = torch_quantize(self.q)
+        progress("compressed", n, "reads")
+
+    def windows(self):
+        self.q, _ = self.c.decompress_windows(self.comp, self.coff, self.csize, self.lens.clone(), self.res, self.opts, self.wfirst, self.wstart, N, 0.0,
+                                              torch.float32, norm=batch.MED_MAD, norm_out=self.ss_w, begin=self.begin)
+
+
+def targets(r, G, L, seed):
+    """G synthetic squiggles of L levels (int8 [G, stride], stride the next multiple of 16), a few reads' whole queries planted in them"""
+    dev = r.c.device
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    stride = (L + 15) // 16 * 16
+    plateaus = torch.randint(-70, 71, (G, stride // 6 + 1), generator=gen).repeat_interleave(6, dim=1)[:, :stride]
+    t = torch.clamp(plateaus + torch.randint(-6, 7, (G, stride), generator=gen), -127, 127).to(torch.int8).to(dev)
+    full = torch.nonzero(r.valid == N).flatten().tolist()
+    for k, i in enumerate(full[:: max(1, len(full) // 6)][:6]):
+        at = (k * 7919 * 13) % (L - N + 1)
+        t[k % G, at : at + N] = r.levels[i]
+    return t, stride
+
+
+def case(c, r, G, L, reps, sample, seed):
+    dev, n = c.device, r.n
+    t, stride = targets(r, G, L, seed)
+    t_len = torch.full((G,), L, dtype=torch.int32, device=dev)
+    lc = batch.Locate(N, QUANT)
+    hits_s = torch.empty((n, G, 2), dtype=torch.int32, device=dev)
+    hits_f = torch.empty((n, G, 2), dtype=torch.int32, device=dev)
+    query = torch.zeros((n, N), dtype=torch.float32, device=dev)
+    ss_f = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+
+    def stage():
+        c.locate(r.q, r.valid, t, t_len, lc, out=hits_s)
+
+    def fused():
+        c.signal_locate(r.comp, r.coff, r.csize, r.off, r.size32, r.res, r.opts, t, t_len, lc, norm=batch.MED_MAD, norm_out=ss_f, begin=r.begin,
+                        query=query, out=hits_f)
+
+    legs = {"windows": r.windows, "locate": stage, "fused": fused}
+    swap = L <= 65536
+    if swap:
+        tq = t.to(torch.float32) / QUANT   # (level / 32 * 32 is exact)
+        mt = batch.Match(stride, QUANT)
+        parts = [(a, min(n, a + MATCH_REFS)) for a in range(0, n, MATCH_REFS)]
+        swapped_hits = [torch.empty((G, b - a, 2), dtype=torch.int32, device=dev) for a, b in parts]
+        refs = [r.levels[a:b].contiguous() for a, b in parts]
+        ref_len = [r.valid[a:b].contiguous() for a, b in parts]
+
+        def swapped():
+            for k in range(len(parts)):
+                c.match(tq, t_len, refs[k], ref_len[k], mt, out=swapped_hits[k])
+
+        legs["swapped"] = swapped
+    progress("case", n, G, L)
+    spread = timed(c, legs, reps)
+    ms = {k: v[0] for k, v in spread.items()}
+    progress("timed", ms)
+    torch.cuda.synchronize()
+    assert torch.equal(r.res.to(torch.int64), r.lens64 * 4), "verdicts"
+    assert torch.equal(query, r.q) and torch.equal(ss_f, r.ss_w), "the fused call's query or shift_scale != the windows call's"
+    assert torch.equal(hits_f, hits_s), "fused hits != the stage entry's, bit for bit"
+    if swap:
+        assert torch.equal(torch.cat(swapped_hits, dim=1).transpose(0, 1).contiguous(), hits_s), "swapped match hits != the locate call's, bit for bit"
+    pick = np.linspace(0, n - 1, min(sample, n)).astype(int) if swap else []
+    if len(pick):
+        want = LR.hits(r.q.cpu().numpy()[pick], r.valid.cpu().numpy()[pick], QUANT, t.cpu().numpy(), [L] * G)
+        assert (hits_s.cpu().numpy().view(np.uint32)[pick] == want).all(), "locate_ref"
+    v64 = r.valid.to(torch.int64)
+    cells = int(v64.sum()) * G * L
+    C = 32
+    valu, bound_all, bound_moves = step_cycles(C)
+    pairs = n * G
+    la = (N - 1) // C
+    per_simd = max(1.0, pairs / SIMDS)        # wavefronts a SIMD issues for, when the pairs are spread evenly
+    cyc = ms["locate"] * 1e-3 * HZ / ((L + la) * per_simd)
+    bound_cells = N / bound_moves * HZ * SIMDS
+    out = {"reads": n, "G": G, "L": L, "target_stride": stride, "rows_per_lane": C, "cells": cells,
+           "ms": ms, "lowest_highest_ms": {k: v[1:] for k, v in spread.items()}, "pairs_at_cost_0": int((hits_s[:, :, 0] == 0).sum()),
+           "locate_tcells_per_s": round(cells / ms["locate"] / 1e9, 2), "fused_minus_windows_tcells_per_s": round(cells / (ms["fused"] - ms["windows"]) / 1e9, 2),
+           "valu_per_step": valu, "bound_cycles_per_step_all_at_4.1": round(bound_all, 1), "bound_cycles_per_step_moves_at_2.2": round(bound_moves, 1),
+           "locate_cycles_per_step": round(cyc, 1), "issue_bound_tcells_per_s": round(bound_cells / 1e12, 2),
+           "share_of_bound": round(cells / (ms["locate"] * 1e-3) / bound_cells, 3), "wavefronts_per_simd": round(pairs / SIMDS, 2),
+           "hits_equal_swapped_match": True if swap else None, "reads_checked_against_locate_ref": len(pick)}
+    if swap:
+        s = spread["swapped"]
+        out["swapped_tcells_per_s"] = round(cells / ms["swapped"] / 1e9, 2)
+        out["locate_over_swapped"] = round(ms["locate"] / ms["swapped"], 4)
+        out["swapped_spread_ms"] = round(s[2] - s[1], 4)
+        out["locate_minus_swapped_ms"] = round(ms["locate"] - ms["swapped"], 4)
+        out["target_bytes"] = {"locate": G * stride, "swapped": G * stride * 4}
+    print(json.dumps(out), file=sys.stderr, flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--sample", type=int, default=6)
+    ap.add_argument("--cases", default="512x2x30000,512x2x48000,8192x2x30000,8192x2x48000,512x1x1048576", help="reads x G x L, comma separated")
+    args = ap.parse_args()
+    cases = [tuple(int(v) for v in s.split("x")) for s in args.cases.split(",")]
+    c = batch.GpuCodec(0)
+    out = {"norm": "med_mad", "N": N, "quant": QUANT, "reps": args.reps, "cases": []}
+    reads = {}
+    for k, (n, G, L) in enumerate(cases):
+        if n not in reads:
+            reads[n] = Reads(c, n)
+        out["cases"].append(case(c, reads[n], G, L, args.reps, args.sample, 100 + k))
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -243,6 +243,21 @@ class GpuMatch(ctypes.Structure):
     ]
 
 
+class GpuLocate(ctypes.Structure):
+    """struct vbz_gpu_locate of include/vbz_gpu.h (40 bytes)."""
+
+    _fields_ = [
+        ("query_len", ctypes.c_uint32),
+        ("n_targets", ctypes.c_uint32),
+        ("target_stride", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("quant", ctypes.c_float),
+        ("reserved", ctypes.c_uint32),
+        ("target", ctypes.c_void_p),
+        ("target_len", ctypes.c_void_p),
+    ]
+
+
 class GpuMatchHit(ctypes.Structure):
     """struct vbz_gpu_match_hit of include/vbz_gpu.h (8 bytes)."""
 
@@ -349,6 +364,9 @@ GPU_API = [
     "vbz_gpu_match_best_batch",
     "vbz_gpu_match_path_batch",
     "vbz_gpu_set_match_path_cap",
+    "vbz_gpu_locate_batch",
+    "vbz_gpu_signal_locate_batch",
+    "vbz_gpu_pod5_signal_locate_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -548,6 +566,11 @@ def load():
         L.vbz_gpu_match_path_batch.argtypes = [vp, u32, u32, vp, vp, ctypes.POINTER(GpuMatch), vp, ctypes.POINTER(GpuMatchPath), vp, vp]
         L.vbz_gpu_set_match_path_cap.restype = None
         L.vbz_gpu_set_match_path_cap.argtypes = [vp, u64]
+    if hasattr(L, "vbz_gpu_locate_batch"):   # (likewise: a vbz_gpu_locate in vbz_gpu_match's place, the arguments those of the match calls)
+        for name in ("vbz_gpu_locate_batch", "vbz_gpu_signal_locate_batch", "vbz_gpu_pod5_signal_locate_batch"):
+            twin = getattr(L, name.replace("_locate", "_match"))
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = [ctypes.POINTER(GpuLocate) if a is ctypes.POINTER(GpuMatch) else a for a in twin.argtypes]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

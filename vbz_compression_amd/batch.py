@@ -141,6 +141,27 @@ class Match:
         return g
 
 
+@dataclasses.dataclass(frozen=True)
+class Locate:
+    """How reads are located in long target squiggles (include/vbz_gpu.h: vbz_gpu_locate): the query is the first query_len (<= 2048)
+    samples of a read's converted signal, quantised as Match quantises them; the WHOLE query is aligned to a stretch of every target row
+    by subsequence DTW under |k - g|, and a hit is (cost, end), end in target coordinates."""
+
+    query_len: int = 2048
+    quant: float = 32.0
+
+    def c_struct(self, target, target_len):
+        """target: int8 [G, target_stride] on the device; target_len: int32 [G] on the device (uint32 bits)"""
+        assert target.dtype == torch.int8 and target.is_contiguous() and target.dim() == 2, (target.dtype, target.shape)
+        assert (target_len.dtype == torch.int32 and target_len.is_contiguous() and target_len.device == target.device
+                and int(target_len.numel()) == int(target.shape[0]))
+        g = _lib.GpuLocate()
+        g.query_len, g.n_targets, g.target_stride = int(self.query_len), int(target.shape[0]), int(target.shape[1])
+        g.quant = self.quant
+        g.target, g.target_len = target.data_ptr(), target_len.data_ptr()
+        return g
+
+
 def quantize_levels(values, quant):
     """The match calls' quantisation in numpy (include/vbz_gpu.h: vbz_gpu_match): float32 v = float32(values) * float32(quant), one
     multiply; 0 for NaN, else clamp(rint(v), -127, 127) with rint to nearest even -> int8.  A caller builds `ref` with it."""
@@ -235,7 +256,7 @@ class GpuCodec:
 
     def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
                chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None, ev=None, moments=None, sg=None,
-               event_first=None, start=None, sp=None, mt=None, span=False):
+               event_first=None, start=None, sp=None, mt=None, span=False, lc=None):
         """One typed decode (include/vbz_gpu.h): the batch, the device entered and left once, and the most general C entry of the call's
         family, NULL for every part that is None.  dst None: nothing is stored in the batch's dst (a chunk decode, the statistics) --
         dst_off / dst_cap are the int16 layout that describes the reads, dst_bytes its extent.  f (a GpuSignalFormat): what is stored,
@@ -247,7 +268,7 @@ class GpuCodec:
         device, into event_first (int64 [reads + 1]) and start (int32, sg.start_cap entries; None: the count-only call).  sp (a GpuSpans,
         f None; m / ss optional): every read's spans into event_first (edge_first) and start (edge, sp.edge_cap entries or None).  mt (a GpuMatch,
         in place of ch, with f): the reads' prefixes into `chunks` (float32 [reads, query_len]) and every pair's hit into `out`; with span
-        the hits are vbz_gpu_match_span (the *_match_span entries)."""
+        the hits are vbz_gpu_match_span (the *_match_span entries).  lc (a GpuLocate, in mt's place): the *_locate entries."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -263,6 +284,9 @@ class GpuCodec:
         elif mt is not None:
             assert ch is None and w is None, "a call has a chunking, windows, events or a match, never two of them"
             name, args = "signal_match_span" if span else "signal_match", [ref(f)] + reads + [ref(m), ss, ref(g), ref(mt), chunks.data_ptr(), out.data_ptr()]
+        elif lc is not None:
+            assert ch is None and w is None, "a call has a chunking, windows, events, a match or a locate, never two of them"
+            name, args = "signal_locate", [ref(f)] + reads + [ref(m), ss, ref(g), ref(lc), chunks.data_ptr(), out.data_ptr()]
         elif w is not None:
             assert ch is None, "a call has a chunking or windows, never both"
             name, args = "decompress_windows", [ref(f)] + reads + [ref(w), chunks.data_ptr(), ref(m), ss, ref(g)]
@@ -887,6 +911,67 @@ class GpuCodec:
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._signal_match(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
                                   match, ref, ref_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
+
+    # -- signal locate (include/vbz_gpu.h: vbz_gpu_locate) ----------------------------------------------
+    def _locate_arenas(self, n, lc, query, out):
+        """(query float32 [n, N], hits int32 [n, G, 2]) of a locate call: the caller's, checked, or new ones"""
+        N, G = int(lc.query_len), int(lc.n_targets)
+        if query is None:
+            query = torch.empty((n, N), dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty((n, G, 2), dtype=torch.int32, device=self.device)
+        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, G, 2), (out.dtype, out.shape)
+        return query, out
+
+    def locate(self, query, valid, target, target_len, locate=None, out=None):
+        """The stage entry (include/vbz_gpu.h: vbz_gpu_locate_batch): the first min(valid[i], query_len) samples of query row i (float32
+        [n, query_len <= 2048]; valid int32 [n], uint32 bits), quantised and aligned WHOLE by subsequence DTW to a stretch of every target row
+        (target int8 [G, target_stride], target_len int32 [G], on the device) -> hits int32 [n, G, 2] = (cost, end) on the device (`out`
+        when given), end in target coordinates.  locate: a Locate whose query_len is the rows' length (None: quant 32 and that length).  No
+        synchronisation."""
+        n = int(query.shape[0])
+        lc = (locate or Locate(query_len=int(query.shape[1]))).c_struct(target, target_len)
+        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
+        query, out = self._locate_arenas(n, lc, query, out)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_locate_batch(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(lc), out.data_ptr()), "locate_batch")
+        finally:
+            self._exit(cur)
+        return out
+
+    def _signal_locate(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, locate, target, target_len, scale, offset, signed,
+                       norm, norm_out, begin, end, stats, query, out, r=None):
+        lc = (locate or Locate()).c_struct(target, target_len)
+        query, out = self._locate_arenas(n, lc, query, out)
+        g, keep_g = self._ranges(n, begin, end, stats)
+        if norm is not None and norm_out is None:
+            norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
+        f = self._signal_format(torch.float32, n, scale, offset, signed)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, lc=lc, out=out)
+        return (out, query) if norm is None else (out, query, norm_out)
+
+    def signal_locate(self, src, src_off, src_size, dst_off, dst_cap, result, opts, target, target_len, locate=None, scale=None, offset=None,
+                      signed=True, sized=False, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None):
+        """Decode every read's prefix and locate it in every target row on the device (include/vbz_gpu.h: vbz_gpu_signal_locate_batch) ->
+        (hits int32 [n, G, 2] = (cost, end), query float32 [n, query_len]), and with norm= also shift_scale float32 [n, 2].  The query is
+        signal_match's; target / target_len / locate: as for locate().  No synchronisation."""
+        n = int(src_off.numel())
+        return self._signal_locate(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, locate, target,
+                                   target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out)
+
+    def pod5_signal_locate(self, src, src_off, src_size, row_samples, read_first_row, result, target, target_len, locate=None, scale=None, offset=None,
+                           signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, read_result=None):
+        """signal_locate over POD5 signal rows grouped into reads by read_first_row (include/vbz_gpu.h: vbz_gpu_pod5_signal_locate_batch):
+        hits, query, scale / offset / norm_out and begin / end are per READ; result is per ROW, read_result (optional) per read."""
+        n = int(src_off.numel())
+        assert int(row_samples.numel()) == n
+        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        dst_off, dst_cap = self._row_layout(row_samples)
+        return self._signal_locate(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
+                                   locate, target, target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r)
 
     # -- signal match with the start of the stretch (include/vbz_gpu.h: vbz_gpu_match_span) ------------------
     def match_span(self, query, valid, ref, ref_len, match=None, out=None):

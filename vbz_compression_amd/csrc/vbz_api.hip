@@ -1427,6 +1427,39 @@ bool match_ok(vbz_gpu_ctx* c, const vbz_gpu_match* m, const float* query, const 
     }
     return true;
 }
+// the locate of a *_locate_batch call, likewise (out: n_out x G entries of vbz_gpu_match_hit)
+static_assert(sizeof(vbz_gpu_locate) == 40, "vbz_gpu_locate is 40 bytes");
+static_assert(offsetof(vbz_gpu_locate, query_len) == 0 && offsetof(vbz_gpu_locate, n_targets) == 4 && offsetof(vbz_gpu_locate, target_stride) == 8 &&
+                  offsetof(vbz_gpu_locate, flags) == 12 && offsetof(vbz_gpu_locate, quant) == 16 && offsetof(vbz_gpu_locate, reserved) == 20 &&
+                  offsetof(vbz_gpu_locate, target) == 24 && offsetof(vbz_gpu_locate, target_len) == 32,
+              "the fields of vbz_gpu_locate");
+bool locate_ok(vbz_gpu_ctx* c, const vbz_gpu_locate* m, const float* query, const void* out, uint32_t n_out)
+{
+    if (!m) {
+        set_error(c, "locate is NULL");
+        return false;
+    }
+    const uint32_t N = m->query_len, G = m->n_targets, S = m->target_stride;
+    if (N < 8 || N > 2048 || N % 8 != 0 || G < 1 || G > 4096 || S < 16 || S > (1u << 30) || S % 16 != 0 || !(m->quant > 0.0f) || !std::isfinite(m->quant) ||
+        m->flags != 0 || m->reserved != 0) {
+        set_error(c, "locate outside the rules (query_len %u, n_targets %u, target_stride %u, quant %g, flags %u, reserved %u)", N, G, S, (double)m->quant,
+                  m->flags, m->reserved);
+        return false;
+    }
+    if (n_out != 0 && (!m->target || !m->target_len || !query || !out)) {
+        set_error(c, "target, target_len, the query arena or the hit arena is NULL");
+        return false;
+    }
+    if ((((uintptr_t)m->target | (uintptr_t)query | (uintptr_t)out) & 15u) != 0) {
+        set_error(c, "target, the query arena or the hit arena is not 16-byte aligned");
+        return false;
+    }
+    if ((uint64_t)n_out * G > EXTENT_MAX / sizeof(vbz_gpu_match_hit) || (uint64_t)G * S > EXTENT_MAX || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
+        set_error(c, "declared locate arenas are not plausible (%u reads, %u targets of %u bytes, %u samples)", n_out, G, S, N);
+        return false;
+    }
+    return true;
+}
 // The fused calls' scratch: the window tables of "one row per read, start 0" (the library's own, so the window check cannot fail), valid[],
 // and a read_result for a POD5 caller that passed none (the verdicts are where valid[] comes from)
 struct MatchTables
@@ -1736,6 +1769,8 @@ struct TypedCall
     float* match_query = nullptr;                    // ... into match_query (the library's own window tables), then the match launch on the
     void* match_out = nullptr;                       // ... context's stream: every pair's hit into match_out -- vbz_gpu_match_hit, or with
     bool match_span = false;                         // ... match_span vbz_gpu_match_span (the span launch in the match launch's place)
+    bool with_locate = false;                        // ... or, beside with_match, a locate in the match's place (untrusted likewise): the same
+    const vbz_gpu_locate* locate = nullptr;          // ... window call and valid[], then the locate launch into match_out (vbz_gpu_match_hit)
 
     TypedCall(Typed k, int s) : kind(k), sized(s) {}
     TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
@@ -1767,6 +1802,7 @@ struct TypedCall
     TypedCall& spanned(const vbz_gpu_spans* g, uint64_t* first, uint32_t* e) { spans = g, edge_first = first, edge = e; return *this; }
     TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_hit* out) { with_match = true, match = m, match_query = query, match_out = out; return *this; }
     TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_span* out) { matched(m, query, (vbz_gpu_match_hit*)nullptr); match_out = out, match_span = true; return *this; }
+    TypedCall& located(const vbz_gpu_locate* l, float* query, vbz_gpu_match_hit* out) { with_match = with_locate = true, locate = l, match_query = query, match_out = out; return *this; }
 };
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
@@ -1985,14 +2021,14 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
 // call writes nothing, and every hit is the empty verdict.
 int match_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, TypedCall& t, uint32_t n_out)
 {
-    const vbz_gpu_match& m = *t.match;
+    const uint32_t N = t.with_locate ? t.locate->query_len : t.match->query_len;
     MatchTables tab;
     if (!ensure_carved(c, c->matchmeta, tab, n_out)) return -1;
     {
         Timed tm(c, "match_tables");
         HIPCHK(c, launch_match_windows(n_out, tab.first, tab.start, c->stream), "match tables launch");
     }
-    const vbz_gpu_windows win = { m.query_len, 0.0f, n_out, tab.first, tab.start, 0, 0 };
+    const vbz_gpu_windows win = { N, 0.0f, n_out, tab.first, tab.start, 0, 0 };
     vbz_gpu_pod5_reads reads;
     if (t.pod5) {
         reads = *t.reads;
@@ -2004,7 +2040,14 @@ int match_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     if (rc != 0) return rc;
     Timed tm(c, "match");
     HIPCHK(c, launch_match_valid(n_out, t.pod5 ? reads.read_result : bt->result, t.ranges ? t.ranges->begin : nullptr, t.ranges ? t.ranges->end : nullptr,
-                                 m.query_len, tab.valid, c->stream), "match valid launch");
+                                 N, tab.valid, c->stream), "match valid launch");
+    if (t.with_locate) {
+        const vbz_gpu_locate& l = *t.locate;
+        HIPCHK(c, launch_locate(n_out, t.match_query, tab.valid, N, l.quant, l.target, l.target_len, l.n_targets, l.target_stride, t.match_out, c->stream),
+               "locate launch");
+        return 0;
+    }
+    const vbz_gpu_match& m = *t.match;
     HIPCHK(c, (t.match_span ? launch_match_span : launch_match)(n_out, t.match_query, tab.valid, m.query_len, m.quant, m.ref, m.ref_len, m.n_refs,
                                                                 m.ref_stride, t.match_out, c->stream),
            "match launch");
@@ -2036,7 +2079,9 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     if (t.kind == Typed::EVENTS) {                                                                                   // 8 (events)
         if (!events_ok(c, t.ev, t.f, t.ev_out, t.ev_moments, n_out)) return -2;
     } else if (t.kind == Typed::CHUNKS && t.with_match) {                                                            // 8 (a match in place of a chunking)
-        if (!match_ok(c, t.match, t.match_query, t.match_out, t.match_span ? sizeof(vbz_gpu_match_span) : sizeof(vbz_gpu_match_hit), n_out)) return -2;
+        if (t.with_locate ? !locate_ok(c, t.locate, t.match_query, t.match_out, n_out)
+                          : !match_ok(c, t.match, t.match_query, t.match_out, t.match_span ? sizeof(vbz_gpu_match_span) : sizeof(vbz_gpu_match_hit), n_out))
+            return -2;
         if (t.f->out_type != VBZ_GPU_SIGNAL_F32) {
             set_error(c, "the query of a match is float32 (out_type %u)", t.f->out_type);
             return -2;
@@ -2309,6 +2354,8 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   pod5_signal_match             CHUNKS      0      match     nullable  nullable             nullable  yes    -       windows, then match.hip)
 //   signal_match_span             CHUNKS      arg    match     nullable  nullable             nullable  -      -      (as signal_match: 16-byte hits,
 //   pod5_signal_match_span        CHUNKS      0      match     nullable  nullable             nullable  yes    -       the span launch in its place)
+//   signal_locate                 CHUNKS      arg    locate    nullable  nullable             nullable  -      -      (as signal_match: a vbz_gpu_locate,
+//   pod5_signal_locate            CHUNKS      0      locate    nullable  nullable             nullable  yes    -       the locate launch in its place)
 //
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
@@ -2545,6 +2592,38 @@ int vbz_gpu_pod5_signal_match_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt
                                          const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query, vbz_gpu_match_span* out)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).matched(match, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_locate_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate, vbz_gpu_match_hit* out)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!locate_ok(c, locate, query, out, n_reads)) return -2;
+    if (n_reads != 0 && !valid) {
+        set_error(c, "valid is NULL");
+        return -2;
+    }
+    Timed t(c, "locate");
+    HIPCHK(c, launch_locate(n_reads, query, valid, locate->query_len, locate->quant, locate->target, locate->target_len, locate->n_targets,
+                            locate->target_stride, out, c->stream),
+           "locate launch");
+    return 0;
+}
+
+int vbz_gpu_signal_locate_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate,
+                                float* query, vbz_gpu_match_hit* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).located(locate, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_pod5_signal_locate_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                     const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
+                                     const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate, float* query, vbz_gpu_match_hit* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).located(locate, query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 

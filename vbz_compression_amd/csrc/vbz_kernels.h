@@ -786,6 +786,12 @@ hipError_t launch_match_path_trace(const MatchPathArgs& a, hipStream_t s);
 // (nullable), clamped as sample_range clamps them.
 hipError_t launch_match_windows(uint32_t n, uint64_t* first, int32_t* start, hipStream_t s);
 hipError_t launch_match_valid(uint32_t n, const uint32_t* result, const uint32_t* rbegin, const uint32_t* rend, uint32_t N, uint32_t* valid, hipStream_t s);
+// Signal locate (locate.hip; the rule: include/vbz_gpu.h, vbz_gpu_locate): out[i G + g] = {cost, end} of the subsequence DTW of the first
+// min(valid[i], N) samples of query row i (N <= 2048 floats a row), quantised by `quant` and aligned WHOLE, against target row g (target +
+// g target_stride, target_len[g] int8 levels: untrusted, 0 or > target_stride gives the empty verdict; the row is read in dwords, so
+// target is 4-byte aligned and target_stride a multiple of 4).  Every entry of out is written.
+hipError_t launch_locate(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* target,
+                         const uint32_t* target_len, uint32_t G, uint32_t target_stride, void* out, hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
