@@ -963,7 +963,7 @@ VBZ_EXPORT void vbz_gpu_set_match_path_cap(vbz_gpu_ctx* ctx, uint64_t bytes);
  * pair; the lanes hold the read's quantised prefix, c = 1 ... 32 rows a lane by n; the target streams through as int8, a dword a lane for
  * 256 steps, one level a step.  The four wavefronts of a workgroup take four reads against one target row.  A step is 8.25 + 2 c VALU
  * instructions in the disassembly (match_kernel: 9 + 2 c).  No LDS, no barrier.
- * Not here: the start of the stretch and the path (start bits of 17 and more rule out the packed key); cutting one target across
+ * Not here: the path in target coordinates (the start of the stretch: the span calls below); cutting one target across
  * wavefronts (a stretch has no bound in DTW, so a cut with overlap is not exact: a caller who wants more parallelism for a small batch
  * passes overlapping tiles as target rows and reads one hit per tile).
  * Measured on one MI355X (tools/time_locate.py, profiles/locate_time.json; the parent of the commit that adds these calls is b74e1b0; median
@@ -996,6 +996,50 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_locate_batch(vbz_gpu_ctx* ctx, const vbz_gpu_
                                                 const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
                                                 const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
                                                 const vbz_gpu_locate* locate, float* query, vbz_gpu_match_hit* out);
+
+/* Signal locate with the start of the aligned stretch: the interval [start, end) of the target that the read's prefix is aligned to -- what
+ * tells two amplicons apart, rejects a "hit" that smears over half a genome, and hands the stretch to a second stage.
+ * The rule (tests/locate_span_ref.py).  Query, quantisation, targets, c(i, j) = |k_i - g_j|, cost, end and the empty verdict are exactly
+ * vbz_gpu_locate's; rows the query, columns the target.  The start is the match-span rule with its arguments exchanged --
+ * tests/match_span_ref.py's span_brute(levels of the read, target[:L]): a warping path runs from (0, s) to (n - 1, e - 1) in steps (i+1, j),
+ * (i, j+1), (i+1, j+1); horizontal steps inside row 0 count (a path may sit on the query's first level over several target levels); start
+ * is the SMALLEST s over all paths of cost `cost` that end at column end - 1.  start < end always; both are in target coordinates,
+ * start <= 2^30 - 1.
+ * Output.  out is a row-major [n_reads, G] arena of vbz_gpu_match_span (16 bytes: {cost, end, start, 0}), 16-byte aligned, every entry
+ * written by one 16-byte store by every call that launches.  The empty verdict is {0xFFFFFFFF, 0, 0, 0}, under the locate calls'
+ * conditions: n == 0, an empty range, a read whose verdict is an error, target_len 0 or above target_stride.
+ * The three calls have the argument lists of their locate twins with vbz_gpu_match_span* out, the same vbz_gpu_locate (flags and reserved
+ * 0), the same refusals and the same return codes; the arena's size rule is n_reads * G * 16 beyond 2^46 bytes.
+ * The winners' table.  vbz_gpu_match_best_batch(ctx, n_reads, spans, G, max_cost, pairs) over a locate span arena (G <= 4096 in both) gives
+ * each read's best target -- least cost, ties to the smallest target index, empty verdicts and costs above max_cost skipped -- and its
+ * [begin, end) in TARGET coordinates: span -> best are two queued calls on one stream, nothing crosses to the host.  That kernel copies
+ * start and end as 32-bit words and assumes nothing about their range.
+ * How ("The start").  Phase 1 is the locate kernel's loop as it stands: (cost, end).  Phase 2, in the same wavefront, walks
+ * BACK from (cost, end) with an anchored DP in reversed coordinates -- the lanes hold the query reversed, the target streams backwards
+ * from level end - 1 -- whose row n - 1 holds `cost` exactly at the columns a path of that cost can start at; the last such column is the
+ * start.  The walk stops as soon as every live cell of the wavefront's fronts of two consecutive steps exceeds `cost` (tested once a block
+ * of 256 steps), or at the target's first level: it covers about the width of the stretch, not L.  A step of phase 2 is 6.25 + 3 c VALU
+ * instructions against phase 1's 8.25 + 2 c (c - 1 of them the selects that pick row n - 1 out of the lane's rows; 86.5 or 101.5 at c = 32).  No LDS, no barrier, no atomics, no scratch; 128
+ * VGPRs, four wavefronts a SIMD; locate_kernel is untouched.
+ * Measured on one MI355X (tools/time_locate.py, profiles/locate_span_time.json; workload and shapes of the locate calls above, median of 20,
+ * the legs alternating in one process, every (cost, end) checked bit for bit against the cost-only leg of the same run, six reads a case
+ * held to numpy): the span stage entry 59.13 ms against 55.87 ms at 8 192 reads, L = 30 000 (1.058 x) and 91.91 against 89.05 ms at
+ * L = 48 000 (1.032 x); the fused span call 61.77 / 94.69 ms.  That is the expectation 1 + (width + 63 + up to 256 steps at phase 2's count)
+ * / (L + 63 at phase 1's): 1.056 and 1.032, the stretch's width 788 and 482 levels in the median, 895 and 768 steps walked back by the
+ * numpy model of the rule.  The cost-only stage entry, timed before and after in the same loop, did not move (55.87 / 55.91, 89.05 /
+ * 89.09 ms).  With 512 reads -- one wavefront a SIMD -- the span stage took 4.69 against 4.63 ms, 7.19 against 7.38 ms and, at
+ * L = 1 048 576, 146.79 against 159.76 ms: there the span kernel's phase 1, the same instructions under another register allocation, runs
+ * faster than locate_kernel's own loop, which is not explained. */
+VBZ_EXPORT int vbz_gpu_locate_span_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate,
+                                         vbz_gpu_match_span* out);
+VBZ_EXPORT int vbz_gpu_signal_locate_span_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options, int sized,
+                                                const vbz_gpu_signal_format* format, const vbz_gpu_normalization* norm, float* shift_scale,
+                                                const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate, float* query,
+                                                vbz_gpu_match_span* out);
+VBZ_EXPORT int vbz_gpu_pod5_signal_locate_span_batch(vbz_gpu_ctx* ctx, const vbz_gpu_batch* batch, const struct CompressionOptions* options,
+                                                     const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
+                                                     const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
+                                                     const vbz_gpu_locate* locate, float* query, vbz_gpu_match_span* out);
 
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}

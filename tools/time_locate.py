@@ -11,15 +11,23 @@ untimed warm-up calls and timed with HIP events on the codec's stream (median of
   windows   the windows call alone (one row per read at start 0, L = N, float32): the fused call's floor
   locate    the stage entry alone, on the query the windows call left
   fused     the fused call: query, hits and shift_scale
+  span      the span stage entry (vbz_gpu_locate_span_batch) on the same query: (cost, end) and the start of the stretch, found by the walk
+            back.  Every (cost, end) must equal the cost-only leg's bit for bit in the same run
+  fused_span  the fused span call (vbz_gpu_signal_locate_span_batch)
+  locate_after  the cost-only stage entry once more, behind the span legs: against `locate` it shows whether the cost-only kernel moved
   swapped   wherever L <= 65 536: vbz_gpu_match_batch over the same cells -- the targets written out as float32 level / quant "queries" of
             query_len = the target's stride, the reads' levels, quantised here with torch, as int8 "references" of M = 2 048 (4 096 of them a
             call, the rule's most).  Its hits must equal the locate call's bit for bit in the same run.
-Six reads are checked against tests/locate_ref.py on the host where the target is short enough for numpy (L <= 65 536).
+Six reads are checked against tests/locate_ref.py and tests/locate_span_ref.py on the host where the target is short enough for numpy
+(L <= 65 536).  For those reads' pairs the steps the walk back takes are counted by the numpy model of the kernel's rule (the fronts of a
+block's last two steps, a block 256 virtual steps); for every pair the arena gives the least it can take, end - start + la.
 
 Next to the measured cells per second and cycles a step stands the kernel's issue bound: VALU instructions a wavefront issues per step of
 locate_pair<C>'s four-step turn, counted in the disassembly of locate.hip (8.25 + 2 c: per turn eight DPP moves, one v_readlane, four
 v_min_u32 / v_cmp / v_cndmask of the running minimum and twelve v_mov_b32, and v_min3_u32 + v_msad_u8 per row and step), at 4.1 cycles an
-instruction and 2.2 for the plain moves (profiles/r06_valu_rate.txt), on 256 CUs x 4 SIMDs at 2.4 GHz.
+instruction and 2.2 for the plain moves (profiles/r06_valu_rate.txt), on 256 CUs x 4 SIMDs at 2.4 GHz.  Phase 2 (locate_back<C>): 6.25 + 3 c
+-- per turn eight DPP moves, one v_readlane, four v_cmp_eq / v_cndmask of the last hit, twelve v_mov_b32, per row and step the cell's two and
+(c - 1 of c) a select; at c = 32 the compiler branches over half of the selects: 346 or 406 a turn, 86.5 or 101.5 a step.
 
     python tools/time_locate.py [--reps 20] [--sample 6] [--cases 512x2x30000,...]"""
 import argparse
@@ -37,6 +45,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import locate_ref as LR  # noqa: E402
+import locate_span_ref as LS  # noqa: E402
 from vbz_compression_amd import batch  # noqa: E402
 
 N = 2048
@@ -48,6 +57,7 @@ CYCLES_PER_VALU = 4.1
 CYCLES_PER_MOVE = 2.2
 SIMDS, HZ = 256 * 4, 2.4e9
 MATCH_REFS = 4096        # vbz_gpu_match.n_refs at most
+BACK_TURN_VALU = {32: (346, 406)}   # phase 2, VALU instructions a turn: otherwise 25 + 12 c
 
 
 def progress(*what):
@@ -81,6 +91,13 @@ def step_cycles(C):
     """(VALU instructions a step, its cycles at 4.1 an instruction, its cycles with the plain moves at 2.2)"""
     valu = TURN_VALU / TURN + 2 * C
     return valu, valu * CYCLES_PER_VALU, valu * CYCLES_PER_VALU - TURN_MOVES / TURN * (CYCLES_PER_VALU - CYCLES_PER_MOVE)
+
+
+def back_cycles(C):
+    """phase 2: (VALU instructions a step, least and most; the issue bound in cycles a step, the plain moves at 2.2, least and most)"""
+    turn = BACK_TURN_VALU.get(C, (25 + 12 * C,) * 2)
+    valu = [v / TURN for v in turn]
+    return valu, [v * CYCLES_PER_VALU - TURN_MOVES / TURN * (CYCLES_PER_VALU - CYCLES_PER_MOVE) for v in valu]
 
 
 class Reads:
@@ -157,7 +174,19 @@ def case(c, r, G, L, reps, sample, seed):
         c.signal_locate(r.comp, r.coff, r.csize, r.off, r.size32, r.res, r.opts, t, t_len, lc, norm=batch.MED_MAD, norm_out=ss_f, begin=r.begin,
                         query=query, out=hits_f)
 
-    legs = {"windows": r.windows, "locate": stage, "fused": fused}
+    spans_s = torch.empty((n, G, 4), dtype=torch.int32, device=dev)
+    spans_f = torch.empty((n, G, 4), dtype=torch.int32, device=dev)
+    query_sp = torch.zeros((n, N), dtype=torch.float32, device=dev)
+    ss_sp = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+
+    def span():
+        c.locate_span(r.q, r.valid, t, t_len, lc, out=spans_s)
+
+    def fused_span():
+        c.signal_locate_span(r.comp, r.coff, r.csize, r.off, r.size32, r.res, r.opts, t, t_len, lc, norm=batch.MED_MAD, norm_out=ss_sp, begin=r.begin,
+                             query=query_sp, out=spans_f)
+
+    legs = {"windows": r.windows, "locate": stage, "fused": fused, "span": span, "fused_span": fused_span, "locate_after": stage}
     swap = L <= 65536
     if swap:
         tq = t.to(torch.float32) / QUANT   # (level / 32 * 32 is exact)
@@ -182,10 +211,25 @@ def case(c, r, G, L, reps, sample, seed):
     assert torch.equal(hits_f, hits_s), "fused hits != the stage entry's, bit for bit"
     if swap:
         assert torch.equal(torch.cat(swapped_hits, dim=1).transpose(0, 1).contiguous(), hits_s), "swapped match hits != the locate call's, bit for bit"
+    assert torch.equal(spans_s[:, :, :2], hits_s), "the span call's (cost, end) != the cost-only call's, bit for bit"
+    assert torch.equal(spans_f, spans_s) and torch.equal(query_sp, r.q) and torch.equal(ss_sp, r.ss_w), "fused span call != the span stage entry"
+    got_sp = spans_s.cpu().numpy().view(np.uint32)
+    live = got_sp[:, :, 0] != 0xFFFFFFFF
+    assert (got_sp[:, :, 2][live] < got_sp[:, :, 1][live]).all() and (got_sp[:, :, 3] == 0).all()
     pick = np.linspace(0, n - 1, min(sample, n)).astype(int) if swap else []
+    walked = []
     if len(pick):
-        want = LR.hits(r.q.cpu().numpy()[pick], r.valid.cpu().numpy()[pick], QUANT, t.cpu().numpy(), [L] * G)
+        q_h, v_h, t_h = r.q.cpu().numpy()[pick], r.valid.cpu().numpy()[pick], t.cpu().numpy()
+        want = LR.hits(q_h, v_h, QUANT, t_h, [L] * G)
         assert (hits_s.cpu().numpy().view(np.uint32)[pick] == want).all(), "locate_ref"
+        assert (got_sp[pick] == LS.spans(q_h, v_h, QUANT, t_h, [L] * G)).all(), "locate_span_ref"
+        K = LR.M.quantize(q_h, QUANT)
+        for k, i in enumerate(pick):
+            for g in range(G):
+                cost, end, start, _ = (int(x) for x in got_sp[i][g])
+                if cost != 0xFFFFFFFF:
+                    nv = int(v_h[k])
+                    walked.append(LS.steps_back(K[k, :nv], t_h[g, :L].astype(np.int64), cost, end, start, LR.rows_per_lane(nv)))
     v64 = r.valid.to(torch.int64)
     cells = int(v64.sum()) * G * L
     C = 32
@@ -195,13 +239,33 @@ def case(c, r, G, L, reps, sample, seed):
     per_simd = max(1.0, pairs / SIMDS)        # wavefronts a SIMD issues for, when the pairs are spread evenly
     cyc = ms["locate"] * 1e-3 * HZ / ((L + la) * per_simd)
     bound_cells = N / bound_moves * HZ * SIMDS
+    # phase 2 from the arena: a pair walks at least to its start, end - start + la steps; the kernel tests its rule at block ends
+    width = (got_sp[:, :, 1].astype(np.int64) - got_sp[:, :, 2].astype(np.int64))[live]
+    least = width + la
+    back_ms = ms["span"] - ms["locate"]
+    back_valu, back_bound = back_cycles(C)
+    back_steps = float(np.minimum(least + 256 + 63, got_sp[:, :, 1].astype(np.int64)[live] + la).mean())   # (the expectation: width + 63 + up to 256)
+    span_out = {"span_over_locate": round(ms["span"] / ms["locate"], 4), "span_minus_locate_ms": round(back_ms, 4),
+                "fused_span_over_fused": round(ms["fused_span"] / ms["fused"], 4),
+                "locate_after_over_locate": round(ms["locate_after"] / ms["locate"], 4),
+                "locate_spread_ms": round(spread["locate"][2] - spread["locate"][1], 4),
+                "locate_after_minus_locate_ms": round(ms["locate_after"] - ms["locate"], 4),
+                "stretch_width_median_max": [float(np.median(width)), int(width.max())] if width.size else None,
+                "steps_back_at_least_median_max": [float(np.median(least)), int(least.max())] if width.size else None,
+                "steps_back_modelled_pairs": len(walked),
+                "steps_back_modelled_median_max": [float(np.median(walked)), int(max(walked))] if walked else None,
+                "expected_span_over_locate": round(1 + back_steps * back_valu[1] / ((L + la) * valu), 4),
+                "back_valu_per_step": back_valu, "back_bound_cycles_per_step": [round(b, 1) for b in back_bound],
+                # (means something only where span - locate is above the cost-only leg's own spread: not with one wavefront a SIMD)
+                "back_cycles_per_step_if_width_plus_319": round(back_ms * 1e-3 * HZ / (back_steps * per_simd), 1) if back_steps else None,
+                "cost_end_equal_cost_only": True, "reads_checked_against_locate_span_ref": len(pick)}
     out = {"reads": n, "G": G, "L": L, "target_stride": stride, "rows_per_lane": C, "cells": cells,
            "ms": ms, "lowest_highest_ms": {k: v[1:] for k, v in spread.items()}, "pairs_at_cost_0": int((hits_s[:, :, 0] == 0).sum()),
            "locate_tcells_per_s": round(cells / ms["locate"] / 1e9, 2), "fused_minus_windows_tcells_per_s": round(cells / (ms["fused"] - ms["windows"]) / 1e9, 2),
            "valu_per_step": valu, "bound_cycles_per_step_all_at_4.1": round(bound_all, 1), "bound_cycles_per_step_moves_at_2.2": round(bound_moves, 1),
            "locate_cycles_per_step": round(cyc, 1), "issue_bound_tcells_per_s": round(bound_cells / 1e12, 2),
            "share_of_bound": round(cells / (ms["locate"] * 1e-3) / bound_cells, 3), "wavefronts_per_simd": round(pairs / SIMDS, 2),
-           "hits_equal_swapped_match": True if swap else None, "reads_checked_against_locate_ref": len(pick)}
+           "hits_equal_swapped_match": True if swap else None, "reads_checked_against_locate_ref": len(pick), "span": span_out}
     if swap:
         s = spread["swapped"]
         out["swapped_tcells_per_s"] = round(cells / ms["swapped"] / 1e9, 2)

@@ -367,6 +367,9 @@ GPU_API = [
     "vbz_gpu_locate_batch",
     "vbz_gpu_signal_locate_batch",
     "vbz_gpu_pod5_signal_locate_batch",
+    "vbz_gpu_locate_span_batch",
+    "vbz_gpu_signal_locate_span_batch",
+    "vbz_gpu_pod5_signal_locate_span_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -571,6 +574,11 @@ def load():
             twin = getattr(L, name.replace("_locate", "_match"))
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = [ctypes.POINTER(GpuLocate) if a is ctypes.POINTER(GpuMatch) else a for a in twin.argtypes]
+    if hasattr(L, "vbz_gpu_locate_span_batch"):   # (likewise: the hits are vbz_gpu_match_span, the arguments those of the three above)
+        for name in ("vbz_gpu_locate_span_batch", "vbz_gpu_signal_locate_span_batch", "vbz_gpu_pod5_signal_locate_span_batch"):
+            twin = getattr(L, name.replace("_span", ""))
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = list(twin.argtypes)
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

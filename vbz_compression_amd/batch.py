@@ -268,7 +268,7 @@ class GpuCodec:
         device, into event_first (int64 [reads + 1]) and start (int32, sg.start_cap entries; None: the count-only call).  sp (a GpuSpans,
         f None; m / ss optional): every read's spans into event_first (edge_first) and start (edge, sp.edge_cap entries or None).  mt (a GpuMatch,
         in place of ch, with f): the reads' prefixes into `chunks` (float32 [reads, query_len]) and every pair's hit into `out`; with span
-        the hits are vbz_gpu_match_span (the *_match_span entries).  lc (a GpuLocate, in mt's place): the *_locate entries."""
+        the hits are vbz_gpu_match_span (the *_match_span entries).  lc (a GpuLocate, in mt's place): the *_locate entries, with span the *_locate_span ones."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -286,7 +286,7 @@ class GpuCodec:
             name, args = "signal_match_span" if span else "signal_match", [ref(f)] + reads + [ref(m), ss, ref(g), ref(mt), chunks.data_ptr(), out.data_ptr()]
         elif lc is not None:
             assert ch is None and w is None, "a call has a chunking, windows, events, a match or a locate, never two of them"
-            name, args = "signal_locate", [ref(f)] + reads + [ref(m), ss, ref(g), ref(lc), chunks.data_ptr(), out.data_ptr()]
+            name, args = "signal_locate_span" if span else "signal_locate", [ref(f)] + reads + [ref(m), ss, ref(g), ref(lc), chunks.data_ptr(), out.data_ptr()]
         elif w is not None:
             assert ch is None, "a call has a chunking or windows, never both"
             name, args = "decompress_windows", [ref(f)] + reads + [ref(w), chunks.data_ptr(), ref(m), ss, ref(g)]
@@ -913,57 +913,60 @@ class GpuCodec:
                                   match, ref, ref_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
 
     # -- signal locate (include/vbz_gpu.h: vbz_gpu_locate) ----------------------------------------------
-    def _locate_arenas(self, n, lc, query, out):
-        """(query float32 [n, N], hits int32 [n, G, 2]) of a locate call: the caller's, checked, or new ones"""
+    def _locate_arenas(self, n, lc, query, out, words=2):
+        """(query float32 [n, N], hits int32 [n, G, words]) of a locate call: the caller's, checked, or new ones"""
         N, G = int(lc.query_len), int(lc.n_targets)
         if query is None:
             query = torch.empty((n, N), dtype=torch.float32, device=self.device)
         if out is None:
-            out = torch.empty((n, G, 2), dtype=torch.int32, device=self.device)
+            out = torch.empty((n, G, words), dtype=torch.int32, device=self.device)
         assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, G, 2), (out.dtype, out.shape)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, G, words), (out.dtype, out.shape)
         return query, out
 
-    def locate(self, query, valid, target, target_len, locate=None, out=None):
+    def locate(self, query, valid, target, target_len, locate=None, out=None, span=False):
         """The stage entry (include/vbz_gpu.h: vbz_gpu_locate_batch): the first min(valid[i], query_len) samples of query row i (float32
         [n, query_len <= 2048]; valid int32 [n], uint32 bits), quantised and aligned WHOLE by subsequence DTW to a stretch of every target row
         (target int8 [G, target_stride], target_len int32 [G], on the device) -> hits int32 [n, G, 2] = (cost, end) on the device (`out`
         when given), end in target coordinates.  locate: a Locate whose query_len is the rows' length (None: quant 32 and that length).  No
-        synchronisation."""
+        synchronisation.  (span: locate_span's route.)"""
         n = int(query.shape[0])
         lc = (locate or Locate(query_len=int(query.shape[1]))).c_struct(target, target_len)
         assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
-        query, out = self._locate_arenas(n, lc, query, out)
+        query, out = self._locate_arenas(n, lc, query, out, 4 if span else 2)
+        name = "locate_span_batch" if span else "locate_batch"
         cur = self._enter()
         try:
-            self._rc(self.L.vbz_gpu_locate_batch(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(lc), out.data_ptr()), "locate_batch")
+            self._rc(getattr(self.L, "vbz_gpu_" + name)(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(lc), out.data_ptr()), name)
         finally:
             self._exit(cur)
         return out
 
     def _signal_locate(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, locate, target, target_len, scale, offset, signed,
-                       norm, norm_out, begin, end, stats, query, out, r=None):
+                       norm, norm_out, begin, end, stats, query, out, r=None, span=False):
         lc = (locate or Locate()).c_struct(target, target_len)
-        query, out = self._locate_arenas(n, lc, query, out)
+        query, out = self._locate_arenas(n, lc, query, out, 4 if span else 2)
         g, keep_g = self._ranges(n, begin, end, stats)
         if norm is not None and norm_out is None:
             norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(torch.float32, n, scale, offset, signed)
-        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, lc=lc, out=out)
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, lc=lc, out=out,
+                    span=span)
         return (out, query) if norm is None else (out, query, norm_out)
 
     def signal_locate(self, src, src_off, src_size, dst_off, dst_cap, result, opts, target, target_len, locate=None, scale=None, offset=None,
-                      signed=True, sized=False, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None):
+                      signed=True, sized=False, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, span=False):
         """Decode every read's prefix and locate it in every target row on the device (include/vbz_gpu.h: vbz_gpu_signal_locate_batch) ->
         (hits int32 [n, G, 2] = (cost, end), query float32 [n, query_len]), and with norm= also shift_scale float32 [n, 2].  The query is
         signal_match's; target / target_len / locate: as for locate().  No synchronisation."""
         n = int(src_off.numel())
         return self._signal_locate(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, locate, target,
-                                   target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out)
+                                   target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, span=span)
 
     def pod5_signal_locate(self, src, src_off, src_size, row_samples, read_first_row, result, target, target_len, locate=None, scale=None, offset=None,
-                           signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, read_result=None):
+                           signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, read_result=None,
+                           span=False):
         """signal_locate over POD5 signal rows grouped into reads by read_first_row (include/vbz_gpu.h: vbz_gpu_pod5_signal_locate_batch):
         hits, query, scale / offset / norm_out and begin / end are per READ; result is per ROW, read_result (optional) per read."""
         n = int(src_off.numel())
@@ -971,7 +974,24 @@ class GpuCodec:
         r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._signal_locate(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
-                                   locate, target, target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r)
+                                   locate, target, target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
+
+    # -- signal locate with the start of the stretch (include/vbz_gpu.h: vbz_gpu_locate_span_batch) ----------
+    def locate_span(self, query, valid, target, target_len, locate=None, out=None):
+        """locate() with the start of the aligned stretch (include/vbz_gpu.h: vbz_gpu_locate_span_batch): the same arguments -> hits int32
+        [n, G, 4] = (cost, end, start, 0); the whole query is aligned to the target's levels [start, end), start the smallest of a path of
+        that cost to that end.  A match_best() over these hits gives each read's best target and its stretch.  No synchronisation."""
+        return self.locate(query, valid, target, target_len, locate, out, span=True)
+
+    def signal_locate_span(self, *args, **kw):
+        """signal_locate() with the start of the aligned stretch (include/vbz_gpu.h: vbz_gpu_signal_locate_span_batch): the same arguments,
+        hits int32 [n, G, 4] = (cost, end, start, 0)."""
+        return self.signal_locate(*args, span=True, **kw)
+
+    def pod5_signal_locate_span(self, *args, **kw):
+        """pod5_signal_locate() with the start of the aligned stretch (include/vbz_gpu.h: vbz_gpu_pod5_signal_locate_span_batch): the same
+        arguments, hits int32 [n, G, 4] = (cost, end, start, 0)."""
+        return self.pod5_signal_locate(*args, span=True, **kw)
 
     # -- signal match with the start of the stretch (include/vbz_gpu.h: vbz_gpu_match_span) ------------------
     def match_span(self, query, valid, ref, ref_len, match=None, out=None):

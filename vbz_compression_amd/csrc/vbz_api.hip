@@ -1427,13 +1427,13 @@ bool match_ok(vbz_gpu_ctx* c, const vbz_gpu_match* m, const float* query, const 
     }
     return true;
 }
-// the locate of a *_locate_batch call, likewise (out: n_out x G entries of vbz_gpu_match_hit)
+// the locate of a *_locate_batch call, likewise (out: n_out x G entries of hit_bytes each -- vbz_gpu_match_hit, or vbz_gpu_match_span of the span calls)
 static_assert(sizeof(vbz_gpu_locate) == 40, "vbz_gpu_locate is 40 bytes");
 static_assert(offsetof(vbz_gpu_locate, query_len) == 0 && offsetof(vbz_gpu_locate, n_targets) == 4 && offsetof(vbz_gpu_locate, target_stride) == 8 &&
                   offsetof(vbz_gpu_locate, flags) == 12 && offsetof(vbz_gpu_locate, quant) == 16 && offsetof(vbz_gpu_locate, reserved) == 20 &&
                   offsetof(vbz_gpu_locate, target) == 24 && offsetof(vbz_gpu_locate, target_len) == 32,
               "the fields of vbz_gpu_locate");
-bool locate_ok(vbz_gpu_ctx* c, const vbz_gpu_locate* m, const float* query, const void* out, uint32_t n_out)
+bool locate_ok(vbz_gpu_ctx* c, const vbz_gpu_locate* m, const float* query, const void* out, size_t hit_bytes, uint32_t n_out)
 {
     if (!m) {
         set_error(c, "locate is NULL");
@@ -1454,7 +1454,7 @@ bool locate_ok(vbz_gpu_ctx* c, const vbz_gpu_locate* m, const float* query, cons
         set_error(c, "target, the query arena or the hit arena is not 16-byte aligned");
         return false;
     }
-    if ((uint64_t)n_out * G > EXTENT_MAX / sizeof(vbz_gpu_match_hit) || (uint64_t)G * S > EXTENT_MAX || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
+    if ((uint64_t)n_out * G > EXTENT_MAX / hit_bytes || (uint64_t)G * S > EXTENT_MAX || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
         set_error(c, "declared locate arenas are not plausible (%u reads, %u targets of %u bytes, %u samples)", n_out, G, S, N);
         return false;
     }
@@ -1770,7 +1770,8 @@ struct TypedCall
     void* match_out = nullptr;                       // ... context's stream: every pair's hit into match_out -- vbz_gpu_match_hit, or with
     bool match_span = false;                         // ... match_span vbz_gpu_match_span (the span launch in the match launch's place)
     bool with_locate = false;                        // ... or, beside with_match, a locate in the match's place (untrusted likewise): the same
-    const vbz_gpu_locate* locate = nullptr;          // ... window call and valid[], then the locate launch into match_out (vbz_gpu_match_hit)
+    const vbz_gpu_locate* locate = nullptr;          // ... window call and valid[], then the locate launch into match_out (vbz_gpu_match_hit; with
+                                                     // ... match_span vbz_gpu_match_span, the locate span launch in its place)
 
     TypedCall(Typed k, int s) : kind(k), sized(s) {}
     TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
@@ -1803,6 +1804,7 @@ struct TypedCall
     TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_hit* out) { with_match = true, match = m, match_query = query, match_out = out; return *this; }
     TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_span* out) { matched(m, query, (vbz_gpu_match_hit*)nullptr); match_out = out, match_span = true; return *this; }
     TypedCall& located(const vbz_gpu_locate* l, float* query, vbz_gpu_match_hit* out) { with_match = with_locate = true, locate = l, match_query = query, match_out = out; return *this; }
+    TypedCall& located(const vbz_gpu_locate* l, float* query, vbz_gpu_match_span* out) { located(l, query, (vbz_gpu_match_hit*)nullptr); match_out = out, match_span = true; return *this; }
 };
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
@@ -2043,7 +2045,8 @@ int match_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
                                  N, tab.valid, c->stream), "match valid launch");
     if (t.with_locate) {
         const vbz_gpu_locate& l = *t.locate;
-        HIPCHK(c, launch_locate(n_out, t.match_query, tab.valid, N, l.quant, l.target, l.target_len, l.n_targets, l.target_stride, t.match_out, c->stream),
+        HIPCHK(c, (t.match_span ? launch_locate_span : launch_locate)(n_out, t.match_query, tab.valid, N, l.quant, l.target, l.target_len, l.n_targets,
+                                                                      l.target_stride, t.match_out, c->stream),
                "locate launch");
         return 0;
     }
@@ -2079,8 +2082,9 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     if (t.kind == Typed::EVENTS) {                                                                                   // 8 (events)
         if (!events_ok(c, t.ev, t.f, t.ev_out, t.ev_moments, n_out)) return -2;
     } else if (t.kind == Typed::CHUNKS && t.with_match) {                                                            // 8 (a match in place of a chunking)
-        if (t.with_locate ? !locate_ok(c, t.locate, t.match_query, t.match_out, n_out)
-                          : !match_ok(c, t.match, t.match_query, t.match_out, t.match_span ? sizeof(vbz_gpu_match_span) : sizeof(vbz_gpu_match_hit), n_out))
+        const size_t hit_bytes = t.match_span ? sizeof(vbz_gpu_match_span) : sizeof(vbz_gpu_match_hit);
+        if (t.with_locate ? !locate_ok(c, t.locate, t.match_query, t.match_out, hit_bytes, n_out)
+                          : !match_ok(c, t.match, t.match_query, t.match_out, hit_bytes, n_out))
             return -2;
         if (t.f->out_type != VBZ_GPU_SIGNAL_F32) {
             set_error(c, "the query of a match is float32 (out_type %u)", t.f->out_type);
@@ -2356,6 +2360,8 @@ int vbz_gpu_pod5_read_samples_batch(vbz_gpu_ctx* c, uint32_t n_rows, const uint3
 //   pod5_signal_match_span        CHUNKS      0      match     nullable  nullable             nullable  yes    -       the span launch in its place)
 //   signal_locate                 CHUNKS      arg    locate    nullable  nullable             nullable  -      -      (as signal_match: a vbz_gpu_locate,
 //   pod5_signal_locate            CHUNKS      0      locate    nullable  nullable             nullable  yes    -       the locate launch in its place)
+//   signal_locate_span            CHUNKS      arg    locate    nullable  nullable             nullable  -      -      (as signal_locate: 16-byte hits,
+//   pod5_signal_locate_span       CHUNKS      0      locate    nullable  nullable             nullable  yes    -       the locate span launch in its place)
 //
 // The NULL rules that differ between entries, kept as they were when the entries were written one by one:
 // - shift_scale of the statistics alone: `required` refuses a NULL in a call of no reads too; `required with reads` (the POD5 twins)
@@ -2599,7 +2605,7 @@ int vbz_gpu_locate_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, c
 {
     if (!c) return -1;
     DeviceGuard dg(c->device);
-    if (!locate_ok(c, locate, query, out, n_reads)) return -2;
+    if (!locate_ok(c, locate, query, out, sizeof(vbz_gpu_match_hit), n_reads)) return -2;
     if (n_reads != 0 && !valid) {
         set_error(c, "valid is NULL");
         return -2;
@@ -2622,6 +2628,39 @@ int vbz_gpu_signal_locate_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const C
 int vbz_gpu_pod5_signal_locate_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
                                      const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
                                      const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate, float* query, vbz_gpu_match_hit* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).located(locate, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_locate_span_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate,
+                              vbz_gpu_match_span* out)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!locate_ok(c, locate, query, out, sizeof(vbz_gpu_match_span), n_reads)) return -2;
+    if (n_reads != 0 && !valid) {
+        set_error(c, "valid is NULL");
+        return -2;
+    }
+    Timed t(c, "locate");
+    HIPCHK(c, launch_locate_span(n_reads, query, valid, locate->query_len, locate->quant, locate->target, locate->target_len, locate->n_targets,
+                                 locate->target_stride, out, c->stream),
+           "locate span launch");
+    return 0;
+}
+
+int vbz_gpu_signal_locate_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
+                                     const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
+                                     const vbz_gpu_locate* locate, float* query, vbz_gpu_match_span* out)
+{
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).located(locate, query, out)
+                                      .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
+}
+
+int vbz_gpu_pod5_signal_locate_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, const vbz_gpu_signal_format* f,
+                                          const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
+                                          const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate, float* query, vbz_gpu_match_span* out)
 {
     return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).located(locate, query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));

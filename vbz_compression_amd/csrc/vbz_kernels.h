@@ -792,6 +792,10 @@ hipError_t launch_match_valid(uint32_t n, const uint32_t* result, const uint32_t
 // target is 4-byte aligned and target_stride a multiple of 4).  Every entry of out is written.
 hipError_t launch_locate(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* target,
                          const uint32_t* target_len, uint32_t G, uint32_t target_stride, void* out, hipStream_t s);
+// ... with the start of the aligned stretch: out[i G + g] = {cost, end, start, 0} (vbz_gpu_match_span, 16 bytes an entry), start in target
+// coordinates, found by a bounded walk back from (cost, end) in the same wavefront.
+hipError_t launch_locate_span(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* target,
+                              const uint32_t* target_len, uint32_t G, uint32_t target_stride, void* out, hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
