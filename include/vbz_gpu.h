@@ -963,7 +963,8 @@ VBZ_EXPORT void vbz_gpu_set_match_path_cap(vbz_gpu_ctx* ctx, uint64_t bytes);
  * pair; the lanes hold the read's quantised prefix, c = 1 ... 32 rows a lane by n; the target streams through as int8, a dword a lane for
  * 256 steps, one level a step.  The four wavefronts of a workgroup take four reads against one target row.  A step is 8.25 + 2 c VALU
  * instructions in the disassembly (match_kernel: 9 + 2 c).  No LDS, no barrier.
- * Not here: the path in target coordinates (the start of the stretch: the span calls below); cutting one target across
+ * Not here: the path of a located read and the start of its stretch, which these three calls do not give (the span calls and
+ * vbz_gpu_locate_path_batch below do); cutting one target across
  * wavefronts (a stretch has no bound in DTW, so a cut with overlap is not exact: a caller who wants more parallelism for a small batch
  * passes overlapping tiles as target rows and reads one hit per tile).
  * Measured on one MI355X (tools/time_locate.py, profiles/locate_time.json; the parent of the commit that adds these calls is b74e1b0; median
@@ -1040,6 +1041,59 @@ VBZ_EXPORT int vbz_gpu_pod5_signal_locate_span_batch(vbz_gpu_ctx* ctx, const vbz
                                                      const vbz_gpu_signal_format* format, const vbz_gpu_pod5_reads* reads,
                                                      const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
                                                      const vbz_gpu_locate* locate, float* query, vbz_gpu_match_span* out);
+
+/* Signal locate: the warping path of chosen pairs, in target coordinates.  The span calls say which target a read sits on and on which
+ * levels [start, end) of it; this stage-level call says which of those levels each sample of the read's prefix belongs to -- what
+ * adaptive sampling, methylation calling and resquiggling do with a located read -- for the pairs the caller lists, typically the one
+ * winner per read, without the arena or the query crossing to the host: span -> best -> path are three queued calls on one stream.
+ * The rule (tests/locate_path_ref.py).  It is the match-path rule with its arguments exchanged: tests/match_path_ref.py's
+ * path_pair(levels of the read[:n], target[:L], a, b).  A pair is a vbz_gpu_match_pair {read, ref = target index, begin = a, end = b} with
+ * [a, b) in TARGET coordinates -- exactly what vbz_gpu_match_best_batch writes over a locate span arena.  Rows are the query's
+ * n = min(valid[read], N) levels, quantised by the match rule; columns are the target levels a ... b - 1; c(i, j) = |k_i - g_j|.  Over the
+ * window's columns alone runs the DP of pairs P = (cost, start), ordered lexicographically: row 0 at column a is (c(0, a), a), nothing left
+ * of a exists, and a path may sit on row 0 while that costs 0.  The backtrace starts at (n - 1, b - 1):
+ *   at i > 0, j > a:  the FIRST of diagonal, up, left that equals the lexicographic minimum of the three;
+ *   at j == a:        up;
+ *   in row 0:         left while j > a and P[0][j-1].cost == 0, otherwise it stops.
+ * Answers.  hit = {cost, end = b, start, rows = n} (vbz_gpu_match_span; its fourth word carries rows here, as in the match path).  rows is
+ * a row-major [n_pairs, query_len] arena of vbz_gpu_match_row, 16-byte aligned: sample i of the prefix is aligned to target levels
+ * [begin_i, end_i); entries at i >= n are {0, 0}.  begin_0 == start, end_{n-1} == b, begin_i < end_i, begin_{i+1} is end_i - 1 or end_i,
+ * and the sum of c over the named cells is cost.  With (a, b) a locate span call's (start, end) for that pair, or any a' <= start with the
+ * same b, cost and start are the span call's.
+ * Untrusted tables.  pairs, valid and target_len are untrusted device tables.  A pair gets the hit {0xFFFFFFFF, 0, 0, 0} and every row
+ * {0, 0} when read >= n_reads or ref >= G (the best call's "none" included), begin >= end, n == 0, L_g == 0 or L_g > target_stride,
+ * end > L_g, or end - begin > max_width; no address is formed from such a pair beyond valid[read] and target_len[ref] of indices inside
+ * the call.  EVERY entry of hit and rows is written by every call that launches, hit by 16-byte stores; nothing else is written.
+ * path->max_width is the largest b - a the call accepts, a multiple of 8 from 8 to 65536; it sizes the scratch.
+ * Returns 0 when queued, -1 for a NULL context or a launch failure, -2, with nothing launched and nothing written, for everything
+ * vbz_gpu_locate_batch refuses about locate; query or hit not 16-byte aligned; path NULL, with flags or reserved != 0, or with max_width
+ * outside its rule; a NULL query, valid, target, target_len, pairs, hit or rows while the call has pairs (valid is REQUIRED here, unlike
+ * the match path: the whole query is aligned, so zero padding behind a short read would be aligned as signal); pairs or rows not 16-byte
+ * aligned; n_pairs * N * 8, n_reads * N * 4 or G * target_stride beyond 2^46 bytes.  n_pairs == 0 with good arguments returns 0 and
+ * launches nothing.
+ * vbz_gpu_query_valid_batch writes the valid[] that the fused match and locate calls derive internally and do not hand out: min(T', N),
+ * or 0 for an error verdict, from result[] -- what such a call leaves, T x 4 bytes or an error code; for the POD5 twins read_result[] -- and
+ * the range tables (ranges may be NULL; begin and end clamped as everywhere).  -2 for NULL tables while the call has reads, or for
+ * query_len outside 8 ... 65536 in multiples of 8.  With it the whole fused chain is queued on one stream with no host copy:
+ * vbz_gpu_signal_locate_span_batch -> vbz_gpu_query_valid_batch -> vbz_gpu_match_best_batch -> vbz_gpu_locate_path_batch.
+ * How ("The path").  Two launches per group of pairs, one wavefront per pair, as the match path.  The forward launch runs
+ * the locate kernel's schedule -- the query in the lanes, c = 1 ... 32 rows a lane by the pair's own n, the window streamed as int8, a dword
+ * a lane per 256 steps -- over the span kernels' keys cost << sb | start (starts relative to a; packed or wide by csrc/match_select.h with
+ * max_width in N's place and query_len in ref_stride's) and stores the match path's two direction bits a cell in the match path's layout.
+ * The window starts and ends at arbitrary bytes: aligned dwords are loaded and shifted by a % 4 bytes, and nothing at or behind dword
+ * (L_g + 3) / 4 of a row is read.  The traceback is the match path's, stated once (csrc/match_path.h).  The scratch is the context's
+ * match-path carve, match_path_pair_words(max_width, query_len) words a pair, grouped under VBZ_HIP_MATCH_PATH_CAP /
+ * vbz_gpu_set_match_path_cap; the answers do not depend on the cap.  No LDS, no barrier, no atomics.
+ * Measured on one MI355X (tools/time_locate.py, profiles/locate_path_time.json; workload and shapes of the locate calls above, median of 20,
+ * the legs alternating in one process, every winner's (cost, start) equal to its span's): span -> best -> path 66.63 ms against the span
+ * stage's 59.28 ms at 8 192 reads, L = 30 000, and 99.10 against 92.09 ms at L = 48 000; the path call alone 7.40 / 7.21 ms there and
+ * 1.29 ms at 512 reads whatever L is -- with one wavefront per pair a small call lasts as long as its widest pair -- which is what
+ * vbz_gpu_match_path_batch with the roles swapped takes where it can express the pairs (1.30 ms, the same bytes). */
+VBZ_EXPORT int vbz_gpu_locate_path_batch(vbz_gpu_ctx* ctx, uint32_t n_pairs, uint32_t n_reads, const float* query, const uint32_t* valid,
+                                         const vbz_gpu_locate* locate, const vbz_gpu_match_pair* pairs, const vbz_gpu_match_path* path,
+                                         vbz_gpu_match_span* hit, vbz_gpu_match_row* rows);
+VBZ_EXPORT int vbz_gpu_query_valid_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const uint32_t* result, const vbz_gpu_sample_ranges* ranges,
+                                         uint32_t query_len, uint32_t* valid);
 
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}

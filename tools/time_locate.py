@@ -15,6 +15,14 @@ untimed warm-up calls and timed with HIP events on the codec's stream (median of
             back.  Every (cost, end) must equal the cost-only leg's bit for bit in the same run
   fused_span  the fused span call (vbz_gpu_signal_locate_span_batch)
   locate_after  the cost-only stage entry once more, behind the span legs: against `locate` it shows whether the cost-only kernel moved
+  span_best_path  span -> best -> path (vbz_gpu_locate_span_batch, vbz_gpu_match_best_batch, vbz_gpu_locate_path_batch), queued on one stream with
+            no host copy; max_width is the smallest multiple of 8 that covers the widest winner (found by one untimed run).  `path` is the
+            path call alone on that winners' table.  Every winner's (cost, start) must equal its span's, the sampled reads' hits and rows
+            tests/locate_path_ref.py's
+  swapped_path  at 512 reads and L <= 65 536: the parent's only route to the same paths, vbz_gpu_match_path_batch with the roles swapped over
+            the same winners' table (the targets as float32 "queries", the reads' levels as int8 "references").  Its hits and rows must
+            equal the path leg's bit for bit in the same run
+  span_after  the span stage entry once more, behind the path legs: against `span` it shows whether the span kernel moved
   swapped   wherever L <= 65 536: vbz_gpu_match_batch over the same cells -- the targets written out as float32 level / quant "queries" of
             query_len = the target's stride, the reads' levels, quantised here with torch, as int8 "references" of M = 2 048 (4 096 of them a
             call, the rule's most).  Its hits must equal the locate call's bit for bit in the same run.
@@ -27,7 +35,11 @@ locate_pair<C>'s four-step turn, counted in the disassembly of locate.hip (8.25 
 v_min_u32 / v_cmp / v_cndmask of the running minimum and twelve v_mov_b32, and v_min3_u32 + v_msad_u8 per row and step), at 4.1 cycles an
 instruction and 2.2 for the plain moves (profiles/r06_valu_rate.txt), on 256 CUs x 4 SIMDs at 2.4 GHz.  Phase 2 (locate_back<C>): 6.25 + 3 c
 -- per turn eight DPP moves, one v_readlane, four v_cmp_eq / v_cndmask of the last hit, twelve v_mov_b32, per row and step the cell's two and
-(c - 1 of c) a select; at c = 32 the compiler branches over half of the selects: 346 or 406 a turn, 86.5 or 101.5 a step.
+(c - 1 of c) a select; at c = 32 the compiler branches over half of the selects: 346 or 406 a turn, 86.5 or 101.5 a step.  The path's forward
+pass (locate_path_forward<32>, packed key): 790 a turn, 197.5 a step -- per cell v_min3_u32, v_sad_u32, two subtractions and two
+v_alignbit_b32 (eight of the 256 folded away), and per turn eight DPP moves, eight plain moves and one v_readlane -- and eight 256-byte
+stores of direction bits a turn.  The expectation for the path of the winners: the span stage's time x (W + 63) / (L + 63) x 197.5 / 72.25
+per pair a read, W the median winner's width -- one wavefront per read where the span stage has G.
 
     python tools/time_locate.py [--reps 20] [--sample 6] [--cases 512x2x30000,...]"""
 import argparse
@@ -44,6 +56,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import locate_path_ref as LP  # noqa: E402
 import locate_ref as LR  # noqa: E402
 import locate_span_ref as LS  # noqa: E402
 from vbz_compression_amd import batch  # noqa: E402
@@ -58,6 +71,7 @@ CYCLES_PER_MOVE = 2.2
 SIMDS, HZ = 256 * 4, 2.4e9
 MATCH_REFS = 4096        # vbz_gpu_match.n_refs at most
 BACK_TURN_VALU = {32: (346, 406)}   # phase 2, VALU instructions a turn: otherwise 25 + 12 c
+PATH_TURN_VALU = 790     # locate_path_forward<32>, packed key: VALU instructions a turn of four steps
 
 
 def progress(*what):
@@ -186,7 +200,42 @@ def case(c, r, G, L, reps, sample, seed):
         c.signal_locate_span(r.comp, r.coff, r.csize, r.off, r.size32, r.res, r.opts, t, t_len, lc, norm=batch.MED_MAD, norm_out=ss_sp, begin=r.begin,
                              query=query_sp, out=spans_f)
 
-    legs = {"windows": r.windows, "locate": stage, "fused": fused, "span": span, "fused_span": fused_span, "locate_after": stage}
+    # the path of the winners: max_width from one untimed run of span -> best
+    with torch.cuda.stream(c.stream):
+        span()
+        table = c.match_best(spans_s)
+    torch.cuda.synchronize()
+    tb = table.cpu().numpy().view(np.uint32)
+    won = tb[:, 1] != 0xFFFFFFFF
+    widest = int((tb[:, 3] - tb[:, 2])[won].max()) if won.any() else 8
+    max_width = max(8, (widest + 7) // 8 * 8)
+    pairs_d = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    phit = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    prows = torch.empty((n, N, 2), dtype=torch.int32, device=dev)
+
+    def span_best_path():
+        c.locate_span(r.q, r.valid, t, t_len, lc, out=spans_s)
+        c.match_best(spans_s, out=pairs_d)
+        c.locate_path(r.q, r.valid, t, t_len, pairs_d, max_width, lc, hit=phit, rows=prows)
+
+    def path():
+        c.locate_path(r.q, r.valid, t, t_len, table, max_width, lc, hit=phit, rows=prows)
+
+    legs = {"windows": r.windows, "locate": stage, "fused": fused, "span": span, "fused_span": fused_span, "locate_after": stage,
+            "span_best_path": span_best_path, "path": path, "span_after": span}
+    swap_path = L <= 65536 and n <= MATCH_REFS and n <= 512
+    if swap_path:
+        sw_pairs = table[:, [1, 0, 2, 3]].contiguous()
+        sw_hit = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        sw_rows = torch.empty((n, N, 2), dtype=torch.int32, device=dev)
+        sw_q = t.to(torch.float32) / QUANT
+        sw_mt = batch.Match(stride, QUANT)
+        sw_ref = r.levels.contiguous()
+
+        def swapped_path():
+            c.match_path(sw_q, t_len, sw_ref, r.valid, sw_pairs, max_width, sw_mt, hit=sw_hit, rows=sw_rows)
+
+        legs["swapped_path"] = swapped_path
     swap = L <= 65536
     if swap:
         tq = t.to(torch.float32) / QUANT   # (level / 32 * 32 is exact)
@@ -214,6 +263,14 @@ def case(c, r, G, L, reps, sample, seed):
     assert torch.equal(spans_s[:, :, :2], hits_s), "the span call's (cost, end) != the cost-only call's, bit for bit"
     assert torch.equal(spans_f, spans_s) and torch.equal(query_sp, r.q) and torch.equal(ss_sp, r.ss_w), "fused span call != the span stage entry"
     got_sp = spans_s.cpu().numpy().view(np.uint32)
+    assert torch.equal(pairs_d, table), "the winners' table moved between runs"
+    hit_h, rows_h = phit.cpu().numpy().view(np.uint32), prows.cpu().numpy().view(np.uint32)
+    valid_h = r.valid.cpu().numpy()
+    for i in np.flatnonzero(won):
+        assert hit_h[i][:3].tolist() == got_sp[i][tb[i][1]][:3].tolist() and hit_h[i][3] == valid_h[i], ("the winner's (cost, start)", int(i))
+    assert (hit_h[~won] == np.array(LP.EMPTY, np.uint32)).all()
+    if swap_path:
+        assert torch.equal(sw_hit, phit) and torch.equal(sw_rows, prows), "swapped match path != the locate path, bit for bit"
     live = got_sp[:, :, 0] != 0xFFFFFFFF
     assert (got_sp[:, :, 2][live] < got_sp[:, :, 1][live]).all() and (got_sp[:, :, 3] == 0).all()
     pick = np.linspace(0, n - 1, min(sample, n)).astype(int) if swap else []
@@ -223,6 +280,9 @@ def case(c, r, G, L, reps, sample, seed):
         want = LR.hits(q_h, v_h, QUANT, t_h, [L] * G)
         assert (hits_s.cpu().numpy().view(np.uint32)[pick] == want).all(), "locate_ref"
         assert (got_sp[pick] == LS.spans(q_h, v_h, QUANT, t_h, [L] * G)).all(), "locate_span_ref"
+        sub = [(k, int(tb[i][1]), int(tb[i][2]), int(tb[i][3])) for k, i in enumerate(pick)]
+        whit, wrows = LP.paths(q_h, v_h, QUANT, t_h, [L] * G, sub, max_width)
+        assert (hit_h[pick] == whit).all() and (rows_h[pick] == wrows).all(), "locate_path_ref"
         K = LR.M.quantize(q_h, QUANT)
         for k, i in enumerate(pick):
             for g in range(G):
@@ -259,7 +319,25 @@ def case(c, r, G, L, reps, sample, seed):
                 # (means something only where span - locate is above the cost-only leg's own spread: not with one wavefront a SIMD)
                 "back_cycles_per_step_if_width_plus_319": round(back_ms * 1e-3 * HZ / (back_steps * per_simd), 1) if back_steps else None,
                 "cost_end_equal_cost_only": True, "reads_checked_against_locate_span_ref": len(pick)}
-    out = {"reads": n, "G": G, "L": L, "target_stride": stride, "rows_per_lane": C, "cells": cells,
+    wwin = (tb[:, 3].astype(np.int64) - tb[:, 2].astype(np.int64))[won]
+    path_valu = PATH_TURN_VALU / TURN
+    path_bound = path_valu * CYCLES_PER_VALU - 8 / TURN * (CYCLES_PER_VALU - CYCLES_PER_MOVE)
+    path_steps = float((wwin + la).mean()) if wwin.size else 0.0
+    path_simd = max(1.0, n / SIMDS)
+    path_out = {"max_width": max_width, "winners": int(won.sum()), "winner_width_median_max": [float(np.median(wwin)), int(wwin.max())] if wwin.size else None,
+                "path_ms": ms["path"], "span_best_path_minus_span_ms": round(ms["span_best_path"] - ms["span"], 4),
+                "path_over_span": round(ms["path"] / ms["span"], 4),
+                "expected_path_over_span": round((float(np.median(wwin)) + 63) / (L + 63) * path_valu / valu / G, 4) if wwin.size else None,
+                "forward_valu_per_step": path_valu, "forward_bound_cycles_per_step": round(path_bound, 1),
+                "path_cycles_per_step_both_launches": round(ms["path"] * 1e-3 * HZ / (path_steps * path_simd), 1) if path_steps else None,
+                "span_after_over_span": round(ms["span_after"] / ms["span"], 4), "span_spread_ms": round(spread["span"][2] - spread["span"][1], 4),
+                "span_after_minus_span_ms": round(ms["span_after"] - ms["span"], 4),
+                "winners_equal_their_spans": True, "reads_checked_against_locate_path_ref": len(pick)}
+    if swap_path:
+        path_out["swapped_path_ms"] = ms["swapped_path"]
+        path_out["path_over_swapped_path"] = round(ms["path"] / ms["swapped_path"], 4)
+        path_out["paths_equal_swapped_match_path"] = True
+    out = {"reads": n, "G": G, "L": L, "target_stride": stride, "rows_per_lane": C, "cells": cells, "path": path_out,
            "ms": ms, "lowest_highest_ms": {k: v[1:] for k, v in spread.items()}, "pairs_at_cost_0": int((hits_s[:, :, 0] == 0).sum()),
            "locate_tcells_per_s": round(cells / ms["locate"] / 1e9, 2), "fused_minus_windows_tcells_per_s": round(cells / (ms["fused"] - ms["windows"]) / 1e9, 2),
            "valu_per_step": valu, "bound_cycles_per_step_all_at_4.1": round(bound_all, 1), "bound_cycles_per_step_moves_at_2.2": round(bound_moves, 1),

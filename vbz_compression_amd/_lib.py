@@ -370,6 +370,8 @@ GPU_API = [
     "vbz_gpu_locate_span_batch",
     "vbz_gpu_signal_locate_span_batch",
     "vbz_gpu_pod5_signal_locate_span_batch",
+    "vbz_gpu_locate_path_batch",
+    "vbz_gpu_query_valid_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -579,6 +581,11 @@ def load():
             twin = getattr(L, name.replace("_span", ""))
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = list(twin.argtypes)
+    if hasattr(L, "vbz_gpu_locate_path_batch"):   # (likewise: the match path call's arguments with a vbz_gpu_locate, and the fused calls' valid[])
+        L.vbz_gpu_locate_path_batch.restype = ctypes.c_int
+        L.vbz_gpu_locate_path_batch.argtypes = [ctypes.POINTER(GpuLocate) if a is ctypes.POINTER(GpuMatch) else a for a in L.vbz_gpu_match_path_batch.argtypes]
+        L.vbz_gpu_query_valid_batch.restype = ctypes.c_int
+        L.vbz_gpu_query_valid_batch.argtypes = [vp, u32, vp, gp, u32, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

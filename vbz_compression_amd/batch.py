@@ -1059,6 +1059,53 @@ class GpuCodec:
             self._exit(cur)
         return hit, rows
 
+    # -- signal locate: the warping path of chosen pairs, in target coordinates (include/vbz_gpu.h: vbz_gpu_locate_path_batch) ------
+    def locate_path(self, query, valid, target, target_len, pairs, max_width, locate=None, hit=None, rows=None):
+        """The warping path of every listed pair of a located read (include/vbz_gpu.h: vbz_gpu_locate_path_batch): pairs int32 [p, 4] =
+        (read, target, begin, end) on the device with [begin, end) in TARGET coordinates (match_best's table over a locate span arena, or
+        any other: it is untrusted), query / valid / target / target_len / locate as for locate() (valid is required: query_valid() makes
+        the fused calls') -> (hit int32 [p, 4] = (cost, end, start, rows), rows int32 [p, query_len, 2] = the target levels [begin, end)
+        of every sample of the read's prefix, {0, 0} behind it) on the device.  A pair's window is at most max_width levels (a multiple of
+        8, 8 ... 65536; it sizes the scratch).  A pair outside the rules gets the empty verdict.  No synchronisation."""
+        n, p = int(query.shape[0]), int(pairs.shape[0])
+        lc = (locate or Locate(query_len=int(query.shape[1]))).c_struct(target, target_len)
+        N = int(lc.query_len)
+        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
+        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
+        assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.device == self.device and tuple(pairs.shape) == (p, 4), (pairs.dtype, pairs.shape)
+        if hit is None:
+            hit = torch.empty((p, 4), dtype=torch.int32, device=self.device)
+        if rows is None:
+            rows = torch.empty((p, N, 2), dtype=torch.int32, device=self.device)
+        assert hit.dtype == torch.int32 and hit.is_contiguous() and hit.device == self.device and tuple(hit.shape) == (p, 4), (hit.dtype, hit.shape)
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.device == self.device and tuple(rows.shape) == (p, N, 2), (rows.dtype, rows.shape)
+        path = _lib.GpuMatchPath(int(max_width), 0, 0)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_locate_path_batch(self.ctx, p, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(lc), pairs.data_ptr(),
+                                                      ctypes.byref(path), hit.data_ptr(), rows.data_ptr()), "locate_path_batch")
+        finally:
+            self._exit(cur)
+        return hit, rows
+
+    def query_valid(self, result, query_len, begin=None, end=None, out=None):
+        """The valid[] that the fused match and locate calls derive for themselves (include/vbz_gpu.h: vbz_gpu_query_valid_batch): result
+        int32 [n] on the device, what such a call left (T x 4 bytes or an error; over POD5 reads its read_result), begin / end the call's
+        range tables -> int32 [n] = min(T', query_len), 0 for an error, on the device (`out` when given).  No synchronisation."""
+        assert result.dtype == torch.int32 and result.is_contiguous() and result.device == self.device, (result.dtype, result.device)
+        n = int(result.numel())
+        g, keep = self._ranges(n, begin, end, None)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and int(out.numel()) == n, (out.dtype, out.shape)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_query_valid_batch(self.ctx, n, result.data_ptr(), ctypes.byref(g) if g is not None else None, int(query_len),
+                                                      out.data_ptr()), "query_valid_batch")
+        finally:
+            self._exit(cur)
+        return out
+
     # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
     def _events(self, n, event_first, start):
         """(the C struct, the tables it points to) of n reads' events: event_first int64 [n + 1] on the device; start int32 [rows] on the

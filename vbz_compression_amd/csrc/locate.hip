@@ -28,6 +28,8 @@
 // VALU instructions in the disassembly (profiles/locate_kernel_resources.txt).  A turn of the loop is four steps, one dword of the stream:
 // 8 DPP moves, 1 v_readlane, 4 v_min_u32 / v_cmp / v_cndmask of the running minimum, 12 v_mov_b32, and v_min3_u32 + v_msad_u8 per row
 // and step -- 41, 49, 65, 97, 161, 289 a turn for C = 1, 2, 4, 8, 16, 32: 8.25 + 2 C a step against match_pair's 9 + 2 C.
+#include "match_path.h"
+#include "match_select.h"
 #include "vbz_kernels.h"
 
 namespace vbzhip {
@@ -277,6 +279,174 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if ((threadIdx.x & 63u) == 0) out[(size_t)read * G + tg] = hit;   // (one 16-byte vector store)
 }
 
+// ---- the path (vbz_gpu_locate_path_batch) --------------------------------------------------------------------------------------------------
+// The warping path of listed pairs in target coordinates: match.hip's two path launches with the operands exchanged.  A pair names a read,
+// a target and a window [a, b) of TARGET levels; the rows of the cost matrix are the query's n levels, in the lanes as in locate_pair (c
+// rows a lane by the pair's own n), the columns the window's W = b - a levels, streamed.
+// A pair of the untrusted table: the rows of its read, n = min(valid, N), when every condition of the header holds, 0 otherwise -- and
+// then no address was formed from the pair beyond valid[read] and target_len[target] of a read and a target inside the call.
+__device__ __forceinline__ uint32_t locate_path_open(const LocatePathArgs& p, uint4 pr)
+{
+    if (pr.x >= p.n_reads || pr.y >= p.G || pr.z >= pr.w) return 0u;
+    const uint32_t n0 = p.valid[pr.x], n = n0 < p.N ? n0 : p.N;
+    const uint32_t L = p.target_len[pr.y];
+    if (L == 0 || L > p.target_stride || pr.w > L || pr.w - pr.z > p.max_width) return 0u;
+    return n;   // (0: nothing to align)
+}
+
+// The forward pass of one pair over its window: match_path_forward's cells, keys, direction bits and bit layout (match.hip; starts
+// relative to a, sb = ceil(log2 max_width)) under locate_pair's schedule -- the query quantised once into the lanes, the window streamed
+// as int8, a dword a lane per block of 256 steps, one v_readlane per four steps.  W + la steps; the answer is row n - 1 of lane la at the
+// last step, read off the lane's rows behind the loop.  Rows behind n are sinks for both keys.
+// The byte stream.  The window starts at an arbitrary byte a and ends at an arbitrary byte b of the row.  Only aligned dwords are
+// loaded: for the block that starts at step t0 lane l loads dwords a / 4 + t0 / 4 + l and the one behind it, each only when it lies in
+// front of dword (b + 3) / 4 <= (L + 3) / 4 of the row (0 otherwise), and v_alignbyte_b32 shifts the pair right by a % 4 bytes: the lane
+// then holds levels a + t0 + 4 l ... + 3, step t takes byte t % 4 of "dword" t / 4 as if the window began at a dword, and a word of
+// direction bits closes at the same steps as in match_path_forward.  Bytes in front of a are shifted out; bytes at and behind b (the
+// rest of the last dword, junk behind L, or zeros) reach lanes at steps >= W + l alone, which have left the window.
+// Nothing wraps and far stays far, for rows 0 ... n - 1 (PackedKey, under match_select.h's rule with max_width in N's place and
+// query_len in ref_stride's: 255 query_len < 2^(31 - sb), sb <= 16; WideKey's far value at bit 62 is out of every sum's reach).
+// (a) A true cell is D[i][j] <= 255 (i + 1) <= 255 query_len however wide the window is -- a path may enter row 0 at column j and leave
+// row i along that column alone -- and a start is < W <= 2^sb, so a true key is < (255 query_len + 1) 2^sb <= 2^31: below the far value.
+// (b) Lanes ahead of the window (t < l) compute on far values alone -- their rows, their diag and the `up` of a lane in the same state;
+// lane 0 never is in it: every value is >= 2^31, a row grows by at most 255 2^sb a step (a cell is at most its `left` plus one cost),
+// and the state lasts at most 63 steps: below 2^31 + 63 * 255 * 2^16 < 2^32.  So D[.][a - 1], which is such a row when level a arrives,
+// is above every true key, and a minimum of a true key and one of these is the true key.  (c) Lanes behind the window (t >= W + l)
+// compute on whatever they are handed -- bytes behind b, lane 0's `up` a step number >= W that may not fit the start field -- and may
+// wrap: only lanes in the same state read that (a lane reads the lane below it alone, which left the window a step earlier), and lane
+// la never is in it: its last level is the last step.  (d) The sign of a difference is the comparison for the operands of every cell
+// the traceback reads -- (i, j) with j > a, whose left, up and (above row 0) diag are true cells, below the far value, half the range.
+template <int C, typename Key>
+__device__ __forceinline__ uint32_t locate_path_forward(const Key key, const float* __restrict__ q, uint32_t n, float quant, const int8_t* __restrict__ row,
+                                                        uint32_t a, uint32_t b, uint32_t* __restrict__ bits)
+{
+    using T = typename Key::T;
+    constexpr int SPD = C <= 16 ? 16 / C : 1;   // steps per word (C = 32: two words a step)
+    constexpr int UN = SPD < 4 ? 4 : SPD;       // steps a turn: whole dwords of the stream and whole words of bits
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t la = (n - 1u) / (uint32_t)C;   // the lane that holds row n - 1
+    const T far = key.far();
+    uint32_t k[C];
+    T cur[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        const uint32_t r = lane * (uint32_t)C + (uint32_t)i;
+        k[i] = r < n ? key.query_word(locate_level(q[r], quant)) : 0u;   // (no address behind n)
+        cur[i] = far;
+    }
+    const T far0 = lane == 0 ? far : (T)0;   // lane 0's diag stays far
+    T diag = far;
+    uint32_t g = 0;   // this lane's level
+    uint32_t acc = 0;
+    uint32_t* const out = bits + lane;
+    const uint32_t W = b - a, steps = W + la;
+    const uint32_t* const words = reinterpret_cast<const uint32_t*>(row);
+    const uint32_t first = a >> 2, shift = a & 3u, n_words = (b + 3u) >> 2;
+    auto load = [&](uint32_t t0) {
+        const uint32_t at = first + t0 / 4u + lane;
+        const uint32_t lo = at < n_words ? words[at] : 0u;
+        const uint32_t hi = at + 1u < n_words ? words[at + 1u] : 0u;
+        return __builtin_amdgcn_alignbyte(hi, lo, shift);   // levels a + t0 + 4 lane ... + 3
+    };
+    uint32_t w = load(0u);
+    for (uint32_t t0 = 0; t0 < steps; t0 += 256u) {
+        const uint32_t lv = w ^ 0x80808080u;   // four levels + 128
+        w = load(t0 + 256u);                   // (in flight while this block is walked)
+        const uint32_t block = steps - t0 < 256u ? steps - t0 : 256u;
+        auto step = [&](uint32_t s, uint32_t level, bool close) {   // close: the step fills the lane's word (C <= 16)
+            const T up = key.prev_lane(cur[C - 1], t0 + s);   // D[l C - 1][j]; lane 0: the key (0, j), j = t0 + s relative to a
+            g = (uint32_t)__builtin_amdgcn_update_dpp((int)key.query_word(level), (int)g, 0x138, 0xF, 0xF, false);   // the lane below's level; lane 0: level t
+            T d = diag, u = up;
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                const T left = cur[i];
+                const T m = min(min(d, u), left);
+                acc = __builtin_amdgcn_alignbit(acc, match_sign_less(m, d), 31);      // acc << 1 | (m < d)
+                acc = __builtin_amdgcn_alignbit(acc, match_sign_less(left, u), 31);   // acc << 1 | (left < u)
+                u = key.cell(g, k[i], m, m, m);   // (the mask of v_msad_u8 is the lane-resident operand's: the query's)
+                d = left;
+                cur[i] = u;
+                if (C == 32 && i % 16 == 15) out[((t0 + s) * 2u + (uint32_t)(i / 16)) * 64u] = acc;
+            }
+            diag = up | far0;
+            if (C <= 16 && close) out[((t0 + s) / (uint32_t)SPD) * 64u] = acc;
+        };
+        uint32_t s = 0;   // (t0 is a multiple of 256, 256 and UN of SPD: a word closes at the steps e with (e + 1) % SPD == 0 of a turn)
+        for (; s + (uint32_t)UN <= block; s += (uint32_t)UN) {
+#pragma unroll
+            for (int e = 0; e < UN; e += 4) {
+                const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lv, (int)((s + (uint32_t)e) >> 2));
+                step(s + (uint32_t)e, x & 0xFFu, (e + 1) % SPD == 0);
+                step(s + (uint32_t)e + 1u, (x >> 8) & 0xFFu, (e + 2) % SPD == 0);
+                step(s + (uint32_t)e + 2u, (x >> 16) & 0xFFu, (e + 3) % SPD == 0);
+                step(s + (uint32_t)e + 3u, x >> 24, (e + 4) % SPD == 0);
+            }
+        }
+        for (; s < block; ++s) {
+            const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lv, (int)(s >> 2));
+            step(s, (x >> (8u * (s & 3u))) & 0xFFu, (s + 1u) % (uint32_t)SPD == 0);
+        }
+    }
+    if (C <= 16 && steps % (uint32_t)SPD != 0)   // the open word: its cells to the top
+        out[(steps / (uint32_t)SPD) * 64u] = acc << (32u - 2u * (uint32_t)C * (steps % (uint32_t)SPD));
+    // row n - 1 of lane la at its last step, the last step of all
+    const uint32_t sel = (n - 1u) % (uint32_t)C;
+    T x = cur[0];
+#pragma unroll
+    for (int i = 1; i < C; ++i) x = sel == (uint32_t)i ? cur[i] : x;
+    return key.cost(key.uniform(x, la));
+}
+
+// grid ceil(count / 4) workgroups of four wavefronts, a wavefront a pair.  Besides the pass, the wavefront writes what the traceback
+// does not: the rows behind n as {0, 0}, and of a pair that fails locate_path_open the empty verdict and every row.
+template <typename Key>
+__device__ __forceinline__ void locate_path_forward_body(const Key key, const LocatePathArgs& p)
+{
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    if (w >= p.count) return;
+    const size_t pi = (size_t)p.first + w;
+    const uint4 pl = p.pairs[pi];
+    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
+                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint32_t n = __builtin_amdgcn_readfirstlane(locate_path_open(p, pr));
+    uint2* const rows = p.rows + pi * p.N;
+    for (uint32_t i = n + lane; i < p.N; i += 64u) rows[i] = make_uint2(0u, 0u);
+    if (n == 0) {
+        if (lane == 0) p.hit[pi] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+        return;
+    }
+    const float* const q = p.query + (size_t)pr.x * p.N;
+    const int8_t* const row = p.target + (size_t)pr.y * p.target_stride;
+    uint32_t* const bits = p.bits + (size_t)w * p.pair_words;
+    uint32_t cost;
+    if (n <= 64u) cost = locate_path_forward<1>(key, q, n, p.quant, row, pr.z, pr.w, bits);
+    else if (n <= 128u) cost = locate_path_forward<2>(key, q, n, p.quant, row, pr.z, pr.w, bits);
+    else if (n <= 256u) cost = locate_path_forward<4>(key, q, n, p.quant, row, pr.z, pr.w, bits);
+    else if (n <= 512u) cost = locate_path_forward<8>(key, q, n, p.quant, row, pr.z, pr.w, bits);
+    else if (n <= 1024u) cost = locate_path_forward<16>(key, q, n, p.quant, row, pr.z, pr.w, bits);
+    else cost = locate_path_forward<32>(key, q, n, p.quant, row, pr.z, pr.w, bits);
+    if (lane == 0) p.cost[w] = cost;
+}
+
+__global__ __launch_bounds__(256) void locate_path_forward_kernel(const LocatePathArgs p, uint32_t sb) { locate_path_forward_body(PackedKey{ sb }, p); }
+__global__ __launch_bounds__(256) void locate_path_forward_wide_kernel(const LocatePathArgs p) { locate_path_forward_body(WideKey{}, p); }
+
+// The traceback, one wavefront per pair: match_path_walk (match_path.h) over the query's n rows.  It writes rows 0 ... n - 1 and the hit
+// (one 16-byte store) of the pairs that pass locate_path_open; the forward launch wrote the rest.
+__global__ __launch_bounds__(256) void locate_path_trace_kernel(const LocatePathArgs p)
+{
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+    if (w >= p.count) return;
+    const size_t pi = (size_t)p.first + w;
+    const uint4 pl = p.pairs[pi];
+    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
+                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint32_t n = __builtin_amdgcn_readfirstlane(locate_path_open(p, pr));
+    if (n == 0) return;
+    const uint32_t start = match_path_walk(n, pr.z, pr.w - pr.z, p.bits + (size_t)w * p.pair_words, p.rows + pi * p.N);
+    if (lane == 0) p.hit[pi] = make_uint4(p.cost[w], pr.w, start, n);
+}
+
 }  // namespace
 
 hipError_t launch_locate(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* target,
@@ -294,6 +464,24 @@ hipError_t launch_locate_span(uint32_t n_reads, const float* query, const uint32
     if (n_reads == 0) return hipSuccess;
     hipLaunchKernelGGL(locate_span_kernel, dim3((n_reads + 3u) / 4u, G), dim3(256), 0, s, n_reads, query, valid, N, quant, target, target_len, G,
                        target_stride, reinterpret_cast<uint4*>(out));
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_path_forward(const LocatePathArgs& a, hipStream_t s)
+{
+    if (a.count == 0) return hipSuccess;
+    const dim3 grid((a.count + 3u) / 4u);
+    if (match_span_packed(a.max_width, a.N))
+        hipLaunchKernelGGL(locate_path_forward_kernel, grid, dim3(256), 0, s, a, match_span_start_bits(a.max_width));
+    else
+        hipLaunchKernelGGL(locate_path_forward_wide_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_path_trace(const LocatePathArgs& a, hipStream_t s)
+{
+    if (a.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(locate_path_trace_kernel, dim3((a.count + 3u) / 4u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -2738,6 +2738,71 @@ int vbz_gpu_match_path_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads,
     return 0;
 }
 
+int vbz_gpu_locate_path_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate,
+                              const vbz_gpu_match_pair* pairs, const vbz_gpu_match_path* path, vbz_gpu_match_span* hit, vbz_gpu_match_row* rows)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    // (the locate's own rules, the targets' extent and the alignment of target, query and hit; the tables a call with pairs needs: below)
+    if (!locate_ok(c, locate, query, hit, sizeof(vbz_gpu_match_span), 0)) return -2;
+    if (!path || path->flags != 0 || path->reserved != 0 || path->max_width < 8 || path->max_width > 65536 || path->max_width % 8 != 0) {
+        set_error(c, "path is NULL or outside the rules (max_width %u, flags %u)", path ? path->max_width : 0u, path ? path->flags : 0u);
+        return -2;
+    }
+    if (n_pairs != 0 && (!locate->target || !locate->target_len || !query || !valid || !pairs || !hit || !rows)) {
+        set_error(c, "target, target_len, the query arena, valid, the pair table, the hit table or the row arena is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)pairs | (uintptr_t)rows) & 15u) != 0) {
+        set_error(c, "the pair table or the row arena is not 16-byte aligned");
+        return -2;
+    }
+    if ((uint64_t)n_pairs * locate->query_len > EXTENT_MAX / sizeof(vbz_gpu_match_row) || (uint64_t)n_reads * locate->query_len > EXTENT_MAX / sizeof(float)) {
+        set_error(c, "declared path arenas are not plausible (%u pairs, %u reads)", n_pairs, n_reads);
+        return -2;
+    }
+    if (n_pairs == 0) return 0;
+    LocatePathArgs a{};
+    a.query = query, a.valid = valid, a.n_reads = n_reads, a.N = locate->query_len, a.quant = locate->quant;
+    a.target = locate->target, a.target_len = locate->target_len, a.G = locate->n_targets, a.target_stride = locate->target_stride;
+    a.pairs = reinterpret_cast<const uint4*>(pairs), a.max_width = path->max_width;
+    a.pair_words = match_path_pair_words(a.max_width, a.N);   // (the rows of the cost matrix are the query's: query_len in ref_stride's place)
+    a.hit = reinterpret_cast<uint4*>(hit), a.rows = reinterpret_cast<uint2*>(rows);
+    const uint32_t group = match_path_group_pairs(n_pairs, a.max_width, a.N, c->knobs.match_path_cap);
+    MatchPathScratch sc;
+    if (!ensure_carved(c, c->matchpath, sc, group, a.pair_words)) return -1;
+    a.bits = sc.bits, a.cost = sc.cost;
+    for (uint32_t first = 0; first < n_pairs; first += group) {   // (the groups share the scratch: the stream orders them)
+        a.first = first, a.count = n_pairs - first < group ? n_pairs - first : group;
+        {
+            Timed t(c, "locate_path_forward");
+            HIPCHK(c, launch_locate_path_forward(a, c->stream), "locate path forward launch");
+        }
+        Timed t(c, "locate_path_trace");
+        HIPCHK(c, launch_locate_path_trace(a, c->stream), "locate path traceback launch");
+    }
+    return 0;
+}
+
+int vbz_gpu_query_valid_batch(vbz_gpu_ctx* c, uint32_t n_reads, const uint32_t* result, const vbz_gpu_sample_ranges* ranges, uint32_t query_len,
+                              uint32_t* valid)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (query_len < 8 || query_len > 65536 || query_len % 8 != 0) {
+        set_error(c, "query_len %u outside 8 ... 65536 in multiples of 8", query_len);
+        return -2;
+    }
+    if (n_reads != 0 && (!result || !valid)) {
+        set_error(c, "result or valid is NULL");
+        return -2;
+    }
+    Timed t(c, "query_valid");
+    HIPCHK(c, launch_match_valid(n_reads, result, ranges ? ranges->begin : nullptr, ranges ? ranges->end : nullptr, query_len, valid, c->stream),
+           "query valid launch");
+    return 0;
+}
+
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)
 {
     if (!c || !bt) return -1;

@@ -796,6 +796,30 @@ hipError_t launch_locate(uint32_t n_reads, const float* query, const uint32_t* v
 // coordinates, found by a bounded walk back from (cost, end) in the same wavefront.
 hipError_t launch_locate_span(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* target,
                               const uint32_t* target_len, uint32_t G, uint32_t target_stride, void* out, hipStream_t s);
+// One group of a locate path call (vbz_gpu_locate_path_batch), as MatchPathArgs: pairs first ... first + count - 1 of the caller's table,
+// slot w = pair - first of the scratch.  A pair's window [begin, end) is in TARGET coordinates and its rows are the query's.
+struct LocatePathArgs
+{
+    const float* query;         // [n_reads, N]
+    const uint32_t* valid;      // [n_reads], untrusted
+    uint32_t n_reads, N;
+    float quant;
+    const int8_t* target;       // [G, target_stride]
+    const uint32_t* target_len; // [G], untrusted
+    uint32_t G, target_stride;
+    const uint4* pairs;         // {read, target, begin, end}, untrusted
+    uint32_t max_width;
+    uint32_t first, count;
+    uint64_t pair_words;        // match_path_pair_words(max_width, N)
+    uint32_t* bits;             // [count x pair_words]: the direction bits (MatchPathScratch)
+    uint32_t* cost;             // [count]: the forward pass's cost
+    uint4* hit;                 // [n_pairs]
+    uint2* rows;                // [n_pairs, N]
+};
+// The forward launch (the packed key or the wide one, by match_select.h with max_width in N's place and N in ref_stride's) and the
+// traceback behind it.  Between them every hit and every row of the group's pairs is written.
+hipError_t launch_locate_path_forward(const LocatePathArgs& a, hipStream_t s);
+hipError_t launch_locate_path_trace(const LocatePathArgs& a, hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
