@@ -266,9 +266,10 @@ class GpuCodec:
         rows of `chunks`.  ev (a GpuEvents, with f): no sample is stored -- one record per caller-listed event into `out` (int32 [rows, 4]), the
         exact sums into `moments` (int64 [rows, 2], or None).  sg (a GpuSegmentation, f None): every read's event starts, found on the
         device, into event_first (int64 [reads + 1]) and start (int32, sg.start_cap entries; None: the count-only call).  sp (a GpuSpans,
-        f None; m / ss optional): every read's spans into event_first (edge_first) and start (edge, sp.edge_cap entries or None).  mt (a GpuMatch,
-        in place of ch, with f): the reads' prefixes into `chunks` (float32 [reads, query_len]) and every pair's hit into `out`; with span
-        the hits are vbz_gpu_match_span (the *_match_span entries).  lc (a GpuLocate, in mt's place): the *_locate entries, with span the *_locate_span ones."""
+        f None; m / ss optional): every read's spans into event_first (edge_first) and start (edge, sp.edge_cap entries or None).  mt (a GpuMatch
+        or a GpuLocate, in place of ch, with f): the reads' prefixes into `chunks` (float32 [reads, query_len]) and every pair's hit into
+        `out` by the *_match or the *_locate entries; with span the hits are vbz_gpu_match_span (the *_match_span and *_locate_span entries).
+        lc: mt under the name the locate callers know."""
         b = self._batch(src, src_off, src_size, dst if dst is not None else torch.empty(0, dtype=torch.uint8, device=self.device), dst_off, dst_cap,
                         result)
         if dst is None:
@@ -277,16 +278,15 @@ class GpuCodec:
         def ref(s):
             return ctypes.byref(s) if s is not None else None
 
+        mt = mt if mt is not None else lc
         reads = [ref(r)] if r is not None else []
         if ev is not None:
             assert ch is None and w is None, "a call has a chunking, windows or events, never two of them"
             name, args = "signal_events", [ref(f)] + reads + [ref(ev), out.data_ptr(), moments.data_ptr() if moments is not None else None, ref(m), ss, ref(g)]
         elif mt is not None:
-            assert ch is None and w is None, "a call has a chunking, windows, events or a match, never two of them"
-            name, args = "signal_match_span" if span else "signal_match", [ref(f)] + reads + [ref(m), ss, ref(g), ref(mt), chunks.data_ptr(), out.data_ptr()]
-        elif lc is not None:
             assert ch is None and w is None, "a call has a chunking, windows, events, a match or a locate, never two of them"
-            name, args = "signal_locate_span" if span else "signal_locate", [ref(f)] + reads + [ref(m), ss, ref(g), ref(lc), chunks.data_ptr(), out.data_ptr()]
+            name = ("signal_match" if isinstance(mt, _lib.GpuMatch) else "signal_locate") + ("_span" if span else "")
+            args = [ref(f)] + reads + [ref(m), ss, ref(g), ref(mt), chunks.data_ptr(), out.data_ptr()]
         elif w is not None:
             assert ch is None, "a call has a chunking or windows, never both"
             name, args = "decompress_windows", [ref(f)] + reads + [ref(w), chunks.data_ptr(), ref(m), ss, ref(g)]
@@ -846,10 +846,10 @@ class GpuCodec:
                                     window_len, pad, dtype, scale, offset, signed, norm, norm_out, begin, end, stats)
 
     # -- signal match (include/vbz_gpu.h: vbz_gpu_match) ------------------------------------------------
-    def _match_arenas(self, n, mt, query, out, words=2):
-        """(query float32 [n, N], hits int32 [n, R, words]) of a match call: the caller's, checked, or new ones.  words: 2 (cost, end), or 4
-        of the span calls (cost, end, start, 0)"""
-        N, R = int(mt.query_len), int(mt.n_refs)
+    def _align_arenas(self, n, al, query, out, words=2):
+        """(query float32 [n, N], hits int32 [n, R, words]) of a match or locate call (al: its GpuMatch or GpuLocate; R: its references or
+        targets): the caller's, checked, or new ones.  words: 2 (cost, end), or 4 of the span calls (cost, end, start, 0)"""
+        N, R = int(al.query_len), int(al.n_refs if isinstance(al, _lib.GpuMatch) else al.n_targets)
         if query is None:
             query = torch.empty((n, N), dtype=torch.float32, device=self.device)
         if out is None:
@@ -858,33 +858,40 @@ class GpuCodec:
         assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, R, words), (out.dtype, out.shape)
         return query, out
 
+    _match_arenas = _locate_arenas = _align_arenas   # (the names the two families' callers know)
+
+    def _align_stage(self, rule, query, valid, levels, levels_len, out, span):
+        """match() and locate(): rule a Match or a Locate, levels / levels_len its references or targets"""
+        n = int(query.shape[0])
+        al = rule.c_struct(levels, levels_len)
+        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
+        query, out = self._align_arenas(n, al, query, out, 4 if span else 2)
+        name = ("match" if isinstance(rule, Match) else "locate") + ("_span_batch" if span else "_batch")
+        cur = self._enter()
+        try:
+            self._rc(getattr(self.L, "vbz_gpu_" + name)(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(al), out.data_ptr()), name)
+        finally:
+            self._exit(cur)
+        return out
+
     def match(self, query, valid, ref, ref_len, match=None, out=None, span=False):
         """The stage entry (include/vbz_gpu.h: vbz_gpu_match_batch): subsequence DTW of every reference row (ref int8 [R, ref_stride],
         ref_len int32 [R], on the device) against the first min(valid[i], query_len) samples of query row i (float32 [n, query_len];
         valid int32 [n], uint32 bits) -> hits int32 [n, R, 2] = (cost, end) on the device (`out` when given).  match: a Match whose
         query_len is the rows' length (None: quant 32 and that length).  No synchronisation.  (span: match_span's route.)"""
-        n = int(query.shape[0])
-        mt = (match or Match(query_len=int(query.shape[1]))).c_struct(ref, ref_len)
-        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
-        query, out = self._match_arenas(n, mt, query, out, 4 if span else 2)
-        name = "match_span_batch" if span else "match_batch"
-        cur = self._enter()
-        try:
-            self._rc(getattr(self.L, "vbz_gpu_" + name)(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(mt), out.data_ptr()), name)
-        finally:
-            self._exit(cur)
-        return out
+        return self._align_stage(match or Match(query_len=int(query.shape[1])), query, valid, ref, ref_len, out, span)
 
-    def _signal_match(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, match, ref, ref_len, scale, offset, signed,
+    def _signal_align(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, rule, levels, levels_len, scale, offset, signed,
                       norm, norm_out, begin, end, stats, query, out, r=None, span=False):
-        mt = (match or Match()).c_struct(ref, ref_len)
-        query, out = self._match_arenas(n, mt, query, out, 4 if span else 2)
+        """signal_match(), signal_locate() and their pod5_ forms: rule a Match or a Locate, levels / levels_len its references or targets"""
+        al = rule.c_struct(levels, levels_len)
+        query, out = self._align_arenas(n, al, query, out, 4 if span else 2)
         g, keep_g = self._ranges(n, begin, end, stats)
         if norm is not None and norm_out is None:
             norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(torch.float32, n, scale, offset, signed)
-        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, mt=mt, out=out,
+        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, mt=al, out=out,
                     span=span)
         return (out, query) if norm is None else (out, query, norm_out)
 
@@ -896,7 +903,7 @@ class GpuCodec:
         converted as decompress_windows converts them, +0 behind the signal's end.  ref / ref_len / match: as for match().  dst_off /
         dst_cap: the int16 layout of the reads (nothing is stored there); result[i] = samples * 4.  No synchronisation."""
         n = int(src_off.numel())
-        return self._signal_match(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, match, ref, ref_len,
+        return self._signal_align(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, match or Match(), ref, ref_len,
                                   scale, offset, signed, norm, norm_out, begin, end, stats, query, out, span=span)
 
     def pod5_signal_match(self, src, src_off, src_size, row_samples, read_first_row, result, ref, ref_len, match=None, scale=None, offset=None,
@@ -909,51 +916,17 @@ class GpuCodec:
         assert int(row_samples.numel()) == n
         r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
-        return self._signal_match(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
-                                  match, ref, ref_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
+        return self._signal_align(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
+                                  match or Match(), ref, ref_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
 
     # -- signal locate (include/vbz_gpu.h: vbz_gpu_locate) ----------------------------------------------
-    def _locate_arenas(self, n, lc, query, out, words=2):
-        """(query float32 [n, N], hits int32 [n, G, words]) of a locate call: the caller's, checked, or new ones"""
-        N, G = int(lc.query_len), int(lc.n_targets)
-        if query is None:
-            query = torch.empty((n, N), dtype=torch.float32, device=self.device)
-        if out is None:
-            out = torch.empty((n, G, words), dtype=torch.int32, device=self.device)
-        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, G, words), (out.dtype, out.shape)
-        return query, out
-
     def locate(self, query, valid, target, target_len, locate=None, out=None, span=False):
         """The stage entry (include/vbz_gpu.h: vbz_gpu_locate_batch): the first min(valid[i], query_len) samples of query row i (float32
         [n, query_len <= 2048]; valid int32 [n], uint32 bits), quantised and aligned WHOLE by subsequence DTW to a stretch of every target row
         (target int8 [G, target_stride], target_len int32 [G], on the device) -> hits int32 [n, G, 2] = (cost, end) on the device (`out`
         when given), end in target coordinates.  locate: a Locate whose query_len is the rows' length (None: quant 32 and that length).  No
         synchronisation.  (span: locate_span's route.)"""
-        n = int(query.shape[0])
-        lc = (locate or Locate(query_len=int(query.shape[1]))).c_struct(target, target_len)
-        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
-        query, out = self._locate_arenas(n, lc, query, out, 4 if span else 2)
-        name = "locate_span_batch" if span else "locate_batch"
-        cur = self._enter()
-        try:
-            self._rc(getattr(self.L, "vbz_gpu_" + name)(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(lc), out.data_ptr()), name)
-        finally:
-            self._exit(cur)
-        return out
-
-    def _signal_locate(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, locate, target, target_len, scale, offset, signed,
-                       norm, norm_out, begin, end, stats, query, out, r=None, span=False):
-        lc = (locate or Locate()).c_struct(target, target_len)
-        query, out = self._locate_arenas(n, lc, query, out, 4 if span else 2)
-        g, keep_g = self._ranges(n, begin, end, stats)
-        if norm is not None and norm_out is None:
-            norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
-        f = self._signal_format(torch.float32, n, scale, offset, signed)
-        self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, lc=lc, out=out,
-                    span=span)
-        return (out, query) if norm is None else (out, query, norm_out)
+        return self._align_stage(locate or Locate(query_len=int(query.shape[1])), query, valid, target, target_len, out, span)
 
     def signal_locate(self, src, src_off, src_size, dst_off, dst_cap, result, opts, target, target_len, locate=None, scale=None, offset=None,
                       signed=True, sized=False, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, span=False):
@@ -961,8 +934,8 @@ class GpuCodec:
         (hits int32 [n, G, 2] = (cost, end), query float32 [n, query_len]), and with norm= also shift_scale float32 [n, 2].  The query is
         signal_match's; target / target_len / locate: as for locate().  No synchronisation."""
         n = int(src_off.numel())
-        return self._signal_locate(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, locate, target,
-                                   target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, span=span)
+        return self._signal_align(n, src, src_off, src_size, dst_off, dst_cap, self._extent(n, dst_off, dst_cap), result, opts, sized, locate or Locate(),
+                                  target, target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, span=span)
 
     def pod5_signal_locate(self, src, src_off, src_size, row_samples, read_first_row, result, target, target_len, locate=None, scale=None, offset=None,
                            signed=True, norm=None, norm_out=None, begin=None, end=None, stats=None, query=None, out=None, read_result=None,
@@ -973,8 +946,8 @@ class GpuCodec:
         assert int(row_samples.numel()) == n
         r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
-        return self._signal_locate(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
-                                   locate, target, target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
+        return self._signal_align(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
+                                  locate or Locate(), target, target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
 
     # -- signal locate with the start of the stretch (include/vbz_gpu.h: vbz_gpu_locate_span_batch) ----------
     def locate_span(self, query, valid, target, target_len, locate=None, out=None):

@@ -37,14 +37,6 @@ namespace {
 
 constexpr uint32_t LOCATE_FAR = 1u << 30;   // D[.][-1]
 
-// the match rule's quantisation of one converted sample, as the cell's lane-resident word: k + 128, 1 ... 255 (NaN: level 0)
-__device__ __forceinline__ uint32_t locate_level(float z, float quant)
-{
-    const float v = z * quant;
-    const float r = fminf(fmaxf(rintf(v), -127.0f), 127.0f);   // (NaN: fmaxf gives -127; taken out below)
-    return v != v ? 128u : (uint32_t)((int)r + 128);
-}
-
 // One pair.  q: the read's query row, n >= 1 its valid samples, 64 C >= n; row: the target row (16-byte aligned), L >= 1 levels, and
 // (L + 3) / 4 dwords of it may be read (L <= target_stride, a multiple of 16).
 template <int C>
@@ -56,7 +48,7 @@ __device__ __forceinline__ uint2 locate_pair(const float* __restrict__ q, uint32
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         const uint32_t r = lane * (uint32_t)C + (uint32_t)i;
-        k[i] = r < n ? locate_level(q[r], quant) : 0u;   // (no address behind n)
+        k[i] = r < n ? align_level(q[r], quant) : 0u;   // (no address behind n)
         cur[i] = LOCATE_FAR;
     }
     uint32_t diag = lane == 0 ? 0u : LOCATE_FAR;   // D[l C - 1][j - 1]: what `up` was a step ago
@@ -123,12 +115,7 @@ __global__ __launch_bounds__(256) void locate_kernel(uint32_t n_reads, const flo
     if (n != 0 && L != 0 && L <= target_stride) {   // (no address from a length that fails here; N <= 2048: 32 rows a lane hold every n)
         const float* const q = query + (size_t)read * N;
         const int8_t* const row = target + (size_t)tg * target_stride;
-        if (n <= 64u) hit = locate_pair<1>(q, n, quant, row, L);
-        else if (n <= 128u) hit = locate_pair<2>(q, n, quant, row, L);
-        else if (n <= 256u) hit = locate_pair<4>(q, n, quant, row, L);
-        else if (n <= 512u) hit = locate_pair<8>(q, n, quant, row, L);
-        else if (n <= 1024u) hit = locate_pair<16>(q, n, quant, row, L);
-        else hit = locate_pair<32>(q, n, quant, row, L);
+        with_rows(n, [&](auto C) VBZ_LAMBDA_INLINE { hit = locate_pair<decltype(C)::value>(q, n, quant, row, L); });
     }
     if ((threadIdx.x & 63u) == 0) out[(size_t)read * G + tg] = hit;   // (one 8-byte vector store)
 }
@@ -178,7 +165,7 @@ __device__ __forceinline__ uint32_t locate_back(const float* __restrict__ q, uin
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         const uint32_t r = lane * (uint32_t)C + (uint32_t)i;
-        k[i] = r < n ? locate_level(q[n - 1u - r], quant) : 0x100u;   // (no address behind n)
+        k[i] = r < n ? align_level(q[n - 1u - r], quant) : 0x100u;   // (no address behind n)
         cur[i] = LOCATE_FAR;
     }
     uint32_t diag = lane == 0 ? 0u : LOCATE_FAR;   // D'[-1][-1]
@@ -285,12 +272,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // rows a lane by the pair's own n), the columns the window's W = b - a levels, streamed.
 // A pair of the untrusted table: the rows of its read, n = min(valid, N), when every condition of the header holds, 0 otherwise -- and
 // then no address was formed from the pair beyond valid[read] and target_len[target] of a read and a target inside the call.
-__device__ __forceinline__ uint32_t locate_path_open(const LocatePathArgs& p, uint4 pr)
+__device__ __forceinline__ uint32_t locate_path_open(const AlignPathArgs& p, uint4 pr)
 {
-    if (pr.x >= p.n_reads || pr.y >= p.G || pr.z >= pr.w) return 0u;
+    if (pr.x >= p.n_reads || pr.y >= p.n_levels || pr.z >= pr.w) return 0u;
     const uint32_t n0 = p.valid[pr.x], n = n0 < p.N ? n0 : p.N;
-    const uint32_t L = p.target_len[pr.y];
-    if (L == 0 || L > p.target_stride || pr.w > L || pr.w - pr.z > p.max_width) return 0u;
+    const uint32_t L = p.levels_len[pr.y];
+    if (L == 0 || L > p.levels_stride || pr.w > L || pr.w - pr.z > p.max_width) return 0u;
     return n;   // (0: nothing to align)
 }
 
@@ -331,7 +318,7 @@ __device__ __forceinline__ uint32_t locate_path_forward(const Key key, const flo
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         const uint32_t r = lane * (uint32_t)C + (uint32_t)i;
-        k[i] = r < n ? key.query_word(locate_level(q[r], quant)) : 0u;   // (no address behind n)
+        k[i] = r < n ? key.query_word(align_level(q[r], quant)) : 0u;   // (no address behind n)
         cur[i] = far;
     }
     const T far0 = lane == 0 ? far : (T)0;   // lane 0's diag stays far
@@ -400,14 +387,12 @@ __device__ __forceinline__ uint32_t locate_path_forward(const Key key, const flo
 // grid ceil(count / 4) workgroups of four wavefronts, a wavefront a pair.  Besides the pass, the wavefront writes what the traceback
 // does not: the rows behind n as {0, 0}, and of a pair that fails locate_path_open the empty verdict and every row.
 template <typename Key>
-__device__ __forceinline__ void locate_path_forward_body(const Key key, const LocatePathArgs& p)
+__device__ __forceinline__ void locate_path_forward_body(const Key key, const AlignPathArgs& p)
 {
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
     if (w >= p.count) return;
     const size_t pi = (size_t)p.first + w;
-    const uint4 pl = p.pairs[pi];
-    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
-                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint4 pr = path_pair(p, pi);
     const uint32_t n = __builtin_amdgcn_readfirstlane(locate_path_open(p, pr));
     uint2* const rows = p.rows + pi * p.N;
     for (uint32_t i = n + lane; i < p.N; i += 64u) rows[i] = make_uint2(0u, 0u);
@@ -416,31 +401,24 @@ __device__ __forceinline__ void locate_path_forward_body(const Key key, const Lo
         return;
     }
     const float* const q = p.query + (size_t)pr.x * p.N;
-    const int8_t* const row = p.target + (size_t)pr.y * p.target_stride;
+    const int8_t* const row = p.levels + (size_t)pr.y * p.levels_stride;
     uint32_t* const bits = p.bits + (size_t)w * p.pair_words;
     uint32_t cost;
-    if (n <= 64u) cost = locate_path_forward<1>(key, q, n, p.quant, row, pr.z, pr.w, bits);
-    else if (n <= 128u) cost = locate_path_forward<2>(key, q, n, p.quant, row, pr.z, pr.w, bits);
-    else if (n <= 256u) cost = locate_path_forward<4>(key, q, n, p.quant, row, pr.z, pr.w, bits);
-    else if (n <= 512u) cost = locate_path_forward<8>(key, q, n, p.quant, row, pr.z, pr.w, bits);
-    else if (n <= 1024u) cost = locate_path_forward<16>(key, q, n, p.quant, row, pr.z, pr.w, bits);
-    else cost = locate_path_forward<32>(key, q, n, p.quant, row, pr.z, pr.w, bits);
+    with_rows(n, [&](auto C) VBZ_LAMBDA_INLINE { cost = locate_path_forward<decltype(C)::value>(key, q, n, p.quant, row, pr.z, pr.w, bits); });
     if (lane == 0) p.cost[w] = cost;
 }
 
-__global__ __launch_bounds__(256) void locate_path_forward_kernel(const LocatePathArgs p, uint32_t sb) { locate_path_forward_body(PackedKey{ sb }, p); }
-__global__ __launch_bounds__(256) void locate_path_forward_wide_kernel(const LocatePathArgs p) { locate_path_forward_body(WideKey{}, p); }
+__global__ __launch_bounds__(256) void locate_path_forward_kernel(const AlignPathArgs p, uint32_t sb) { locate_path_forward_body(PackedKey{ sb }, p); }
+__global__ __launch_bounds__(256) void locate_path_forward_wide_kernel(const AlignPathArgs p) { locate_path_forward_body(WideKey{}, p); }
 
 // The traceback, one wavefront per pair: match_path_walk (match_path.h) over the query's n rows.  It writes rows 0 ... n - 1 and the hit
 // (one 16-byte store) of the pairs that pass locate_path_open; the forward launch wrote the rest.
-__global__ __launch_bounds__(256) void locate_path_trace_kernel(const LocatePathArgs p)
+__global__ __launch_bounds__(256) void locate_path_trace_kernel(const AlignPathArgs p)
 {
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
     if (w >= p.count) return;
     const size_t pi = (size_t)p.first + w;
-    const uint4 pl = p.pairs[pi];
-    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
-                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint4 pr = path_pair(p, pi);
     const uint32_t n = __builtin_amdgcn_readfirstlane(locate_path_open(p, pr));
     if (n == 0) return;
     const uint32_t start = match_path_walk(n, pr.z, pr.w - pr.z, p.bits + (size_t)w * p.pair_words, p.rows + pi * p.N);
@@ -467,7 +445,7 @@ hipError_t launch_locate_span(uint32_t n_reads, const float* query, const uint32
     return hipGetLastError();
 }
 
-hipError_t launch_locate_path_forward(const LocatePathArgs& a, hipStream_t s)
+hipError_t launch_locate_path_forward(const AlignPathArgs& a, hipStream_t s)
 {
     if (a.count == 0) return hipSuccess;
     const dim3 grid((a.count + 3u) / 4u);
@@ -478,7 +456,7 @@ hipError_t launch_locate_path_forward(const LocatePathArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_locate_path_trace(const LocatePathArgs& a, hipStream_t s)
+hipError_t launch_locate_path_trace(const AlignPathArgs& a, hipStream_t s)
 {
     if (a.count == 0) return hipSuccess;
     hipLaunchKernelGGL(locate_path_trace_kernel, dim3((a.count + 3u) / 4u), dim3(256), 0, s, a);

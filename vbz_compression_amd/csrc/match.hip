@@ -28,14 +28,6 @@ constexpr uint32_t MATCH_FAR = 1u << 30;   // D[.][-1]
 // The cell's cost is one v_msad_u8 over the words of match_path.h (match_ref_word): a row behind the reference's end is the word 0 and costs
 // nothing.
 
-// the rule's quantisation of one converted sample, as the cell's query word
-__device__ __forceinline__ uint32_t match_level(float z, float quant)
-{
-    const float v = z * quant;
-    const float r = fminf(fmaxf(rintf(v), -127.0f), 127.0f);   // (NaN: fmaxf gives -127; taken out below)
-    return (v != v ? 128u : (uint32_t)((int)r + 128)) | 0x100u;
-}
-
 // One pair.  q: the read's query row; n >= 1 its valid samples; ref: the reference row, M >= 1 entries, 64 C >= M.
 template <int C>
 __device__ __forceinline__ uint2 match_pair(const float* __restrict__ q, uint32_t n, float quant, const int8_t* __restrict__ ref, uint32_t M)
@@ -268,13 +260,13 @@ __global__ __launch_bounds__(256) void match_best_kernel(uint32_t n_reads, const
 
 // A pair of the untrusted table: the length of its reference when every condition of the header holds, 0 otherwise -- and then no address
 // was formed from the pair beyond valid[read] and ref_len[ref] of a read and a reference inside the call.
-__device__ __forceinline__ uint32_t match_path_open(const MatchPathArgs& p, uint4 pr)
+__device__ __forceinline__ uint32_t match_path_open(const AlignPathArgs& p, uint4 pr)
 {
-    if (pr.x >= p.n_reads || pr.y >= p.R || pr.z >= pr.w) return 0u;
+    if (pr.x >= p.n_reads || pr.y >= p.n_levels || pr.z >= pr.w) return 0u;
     const uint32_t n0 = p.valid ? p.valid[pr.x] : p.N, n = n0 < p.N ? n0 : p.N;
     if (pr.w > n || pr.w - pr.z > p.max_width) return 0u;
-    const uint32_t M = p.ref_len[pr.y];
-    return M <= p.ref_stride ? M : 0u;
+    const uint32_t M = p.levels_len[pr.y];
+    return M <= p.levels_stride ? M : 0u;
 }
 
 // The forward pass of one pair over its window: match_span_pair's schedule over the W columns q[0 ... W), W + la steps, starts relative to
@@ -361,52 +353,43 @@ __device__ __forceinline__ uint32_t match_path_forward(const Key key, const floa
 // grid ceil(count / 4) workgroups of four wavefronts, a wavefront a pair.  Besides the pass, the wavefront writes what the traceback
 // does not: the rows behind the reference's end as {0, 0}, and of a pair that fails match_path_open the empty verdict and every row.
 template <typename Key>
-__device__ __forceinline__ void match_path_forward_body(const Key key, const MatchPathArgs& p)
+__device__ __forceinline__ void match_path_forward_body(const Key key, const AlignPathArgs& p)
 {
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
     if (w >= p.count) return;
     const size_t pi = (size_t)p.first + w;
-    const uint4 pl = p.pairs[pi];
-    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
-                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint4 pr = path_pair(p, pi);
     const uint32_t M = __builtin_amdgcn_readfirstlane(match_path_open(p, pr));
-    uint2* const rows = p.rows + pi * p.ref_stride;
-    for (uint32_t i = M + lane; i < p.ref_stride; i += 64u) rows[i] = make_uint2(0u, 0u);
+    uint2* const rows = p.rows + pi * p.levels_stride;
+    for (uint32_t i = M + lane; i < p.levels_stride; i += 64u) rows[i] = make_uint2(0u, 0u);
     if (M == 0) {
         if (lane == 0) p.hit[pi] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
         return;
     }
     const float* const q = p.query + (size_t)pr.x * p.N + pr.z;
-    const int8_t* const row = p.ref + (size_t)pr.y * p.ref_stride;
+    const int8_t* const row = p.levels + (size_t)pr.y * p.levels_stride;
     uint32_t* const bits = p.bits + (size_t)w * p.pair_words;
     const uint32_t W = pr.w - pr.z;
     uint32_t cost;
-    if (M <= 64u) cost = match_path_forward<1>(key, q, W, p.quant, row, M, bits);
-    else if (M <= 128u) cost = match_path_forward<2>(key, q, W, p.quant, row, M, bits);
-    else if (M <= 256u) cost = match_path_forward<4>(key, q, W, p.quant, row, M, bits);
-    else if (M <= 512u) cost = match_path_forward<8>(key, q, W, p.quant, row, M, bits);
-    else if (M <= 1024u) cost = match_path_forward<16>(key, q, W, p.quant, row, M, bits);
-    else cost = match_path_forward<32>(key, q, W, p.quant, row, M, bits);
+    with_rows(M, [&](auto C) VBZ_LAMBDA_INLINE { cost = match_path_forward<decltype(C)::value>(key, q, W, p.quant, row, M, bits); });
     if (lane == 0) p.cost[w] = cost;
 }
 
-__global__ __launch_bounds__(256) void match_path_forward_kernel(const MatchPathArgs p, uint32_t sb) { match_path_forward_body(PackedKey{ sb }, p); }
-__global__ __launch_bounds__(256) void match_path_forward_wide_kernel(const MatchPathArgs p) { match_path_forward_body(WideKey{}, p); }
+__global__ __launch_bounds__(256) void match_path_forward_kernel(const AlignPathArgs p, uint32_t sb) { match_path_forward_body(PackedKey{ sb }, p); }
+__global__ __launch_bounds__(256) void match_path_forward_wide_kernel(const AlignPathArgs p) { match_path_forward_body(WideKey{}, p); }
 
 // The traceback, one wavefront per pair: at most W + M dependent steps (match_path.h: match_path_walk, stated once for this call and for
 // the locate path).  It writes rows 0 ... M - 1 and the hit (one 16-byte store) of the pairs that pass match_path_open; the forward launch
 // wrote the rest.
-__global__ __launch_bounds__(256) void match_path_trace_kernel(const MatchPathArgs p)
+__global__ __launch_bounds__(256) void match_path_trace_kernel(const AlignPathArgs p)
 {
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
     if (w >= p.count) return;
     const size_t pi = (size_t)p.first + w;
-    const uint4 pl = p.pairs[pi];
-    const uint4 pr = make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
-                                __builtin_amdgcn_readfirstlane(pl.w));
+    const uint4 pr = path_pair(p, pi);
     const uint32_t M = __builtin_amdgcn_readfirstlane(match_path_open(p, pr));
     if (M == 0) return;
-    const uint32_t start = match_path_walk(M, pr.z, pr.w - pr.z, p.bits + (size_t)w * p.pair_words, p.rows + pi * p.ref_stride);
+    const uint32_t start = match_path_walk(M, pr.z, pr.w - pr.z, p.bits + (size_t)w * p.pair_words, p.rows + pi * p.levels_stride);
     if (lane == 0) p.hit[pi] = make_uint4(p.cost[w], pr.w, start, M);
 }
 
@@ -467,18 +450,18 @@ hipError_t launch_match_best(uint32_t n_reads, const void* spans, uint32_t R, ui
     return hipGetLastError();
 }
 
-hipError_t launch_match_path_forward(const MatchPathArgs& a, hipStream_t s)
+hipError_t launch_match_path_forward(const AlignPathArgs& a, hipStream_t s)
 {
     if (a.count == 0) return hipSuccess;
     const dim3 grid((a.count + 3u) / 4u);
-    if (match_span_packed(a.max_width, a.ref_stride))
+    if (match_span_packed(a.max_width, a.levels_stride))
         hipLaunchKernelGGL(match_path_forward_kernel, grid, dim3(256), 0, s, a, match_span_start_bits(a.max_width));
     else
         hipLaunchKernelGGL(match_path_forward_wide_kernel, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_match_path_trace(const MatchPathArgs& a, hipStream_t s)
+hipError_t launch_match_path_trace(const AlignPathArgs& a, hipStream_t s)
 {
     if (a.count == 0) return hipSuccess;
     hipLaunchKernelGGL(match_path_trace_kernel, dim3((a.count + 3u) / 4u), dim3(256), 0, s, a);

@@ -1,10 +1,42 @@
-// match_path.h -- what the span and path kernels of match.hip and the path kernels of locate.hip share: the keys (cost, start) of a cell and
-// the traceback over a pair's direction bits.  Device code; both files include it inside their own translation unit.
+// match_path.h -- what the kernels of match.hip and locate.hip share: the quantiser, the ladder over rows per lane, the keys (cost, start)
+// of a cell, a path kernel's pair and the traceback over a pair's direction bits.  Device code; both files include it inside their own
+// translation unit.
 #pragma once
+#include <type_traits>
+
 #include "vbz_kernels.h"
+
+// A lambda handed to with_rows is part of the kernel's one body, like a __forceinline__ function: stated after its parameters.
+#define VBZ_LAMBDA_INLINE __attribute__((always_inline))
 
 namespace vbzhip {
 namespace {
+
+// The rule's quantisation of one converted sample: the level k + 128, 1 ... 255 (NaN: level 0, the byte 128).  match.hip streams it as the
+// cell's query word, match_level; locate.hip keeps it in the lanes.
+__device__ __forceinline__ uint32_t align_level(float z, float quant)
+{
+    const float v = z * quant;
+    const float r = fminf(fmaxf(rintf(v), -127.0f), 127.0f);   // (NaN: fmaxf gives -127; taken out below)
+    return v != v ? 128u : (uint32_t)((int)r + 128);
+}
+__device__ __forceinline__ uint32_t match_level(float z, float quant) { return align_level(z, quant) | 0x100u; }
+
+// The ladder over rows per lane: f(std::integral_constant<int, C>) for the smallest C of 1, 2, 4, 8, 16, 32 with 64 C >= len (len <= 2048).
+// tests/locate_ref.py states the thresholds again as the reference.  match_kernel, match_span_body and locate_span_kernel keep the
+// ladder written out: through with_rows the compiler emits the same instructions for them in another order and with other scalar
+// registers (profiles/align_restate_isa.txt), and this header was to leave every code object as it was.
+template <typename F>
+__device__ __forceinline__ void with_rows(uint32_t len, F&& f)
+{
+    if (len <= 64u) f(std::integral_constant<int, 1>{});
+    else if (len <= 128u) f(std::integral_constant<int, 2>{});
+    else if (len <= 256u) f(std::integral_constant<int, 4>{});
+    else if (len <= 512u) f(std::integral_constant<int, 8>{});
+    else if (len <= 1024u) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 32>{});
+}
+
 
 // The cell's cost is one v_msad_u8: the sum over the four bytes of |a - b|, skipping the bytes where the REFERENCE operand is 0, plus
 // an accumulator.  Query level k (-127 ... 127) is the word {k + 128, 1, 0, 0}; reference level r >= -127 is {r + 128, 0, 0, 0}, so its
@@ -80,6 +112,14 @@ struct WideKey
 __device__ __forceinline__ uint32_t match_sign_less(uint32_t a, uint32_t b) { return a - b; }                       // bit 31: a < b
 __device__ __forceinline__ uint32_t match_sign_less(uint64_t a, uint64_t b) { return (uint32_t)((a - b) >> 32); }
 
+// Pair pi = first + w of a path launch (AlignPathArgs: vbz_kernels.h), uniform: {read, ref or target, begin, end}
+__device__ __forceinline__ uint4 path_pair(const AlignPathArgs& p, size_t pi)
+{
+    const uint4 pl = p.pairs[pi];
+    return make_uint4(__builtin_amdgcn_readfirstlane(pl.x), __builtin_amdgcn_readfirstlane(pl.y), __builtin_amdgcn_readfirstlane(pl.z),
+                      __builtin_amdgcn_readfirstlane(pl.w));
+}
+
 // The traceback of one pair, by its whole wavefront: the walk over the bit-matrix a forward pass left (match.hip, at match_path_forward:
 // the layout), which does not know which operand sat in the lanes.  M >= 1: the rows of the cost matrix, the operand in the lanes, c rows
 // a lane by M; a: the window's first column; W >= 1 its width; bits: the pair's words; rows: the pair's M entries.  It writes rows
@@ -93,7 +133,8 @@ __device__ __forceinline__ uint32_t match_sign_less(uint64_t a, uint64_t b) { re
 __device__ __forceinline__ uint32_t match_path_walk(uint32_t M, uint32_t a, uint32_t W, const uint32_t* __restrict__ bits, uint2* __restrict__ rows)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t lc = M <= 64u ? 0u : M <= 128u ? 1u : M <= 256u ? 2u : M <= 512u ? 3u : M <= 1024u ? 4u : 5u;
+    uint32_t lc = 0;   // log2 c
+    with_rows(M, [&](auto C) VBZ_LAMBDA_INLINE { lc = (uint32_t)__builtin_ctz((unsigned)C()); });
     uint32_t i = M - 1u, j = W - 1u, end = j + 1u;
     uint32_t have_l = 0xFFFFFFFFu, top = 0, cache = 0;   // lane k holds word top - k of lane have_l's stream
     uint2 mine = make_uint2(0u, 0u);

@@ -1399,63 +1399,76 @@ static_assert(sizeof(vbz_gpu_match_hit) == 8 && offsetof(vbz_gpu_match_hit, cost
 static_assert(sizeof(vbz_gpu_match_span) == 16 && offsetof(vbz_gpu_match_span, cost) == 0 && offsetof(vbz_gpu_match_span, end) == 4 &&
                   offsetof(vbz_gpu_match_span, start) == 8 && offsetof(vbz_gpu_match_span, zero) == 12,
               "vbz_gpu_match_span is 16 bytes: cost, end, start, zero");
-// (out: n_out x R entries of hit_bytes each -- vbz_gpu_match_hit, or vbz_gpu_match_span of the span calls)
-bool match_ok(vbz_gpu_ctx* c, const vbz_gpu_match* m, const float* query, const void* out, size_t hit_bytes, uint32_t n_out)
-{
-    if (!m) {
-        set_error(c, "match is NULL");
-        return false;
-    }
-    const uint32_t N = m->query_len, R = m->n_refs, S = m->ref_stride;
-    if (N < 8 || N > 65536 || N % 8 != 0 || R < 1 || R > 4096 || S < 16 || S > 2048 || S % 16 != 0 || !(m->quant > 0.0f) || !std::isfinite(m->quant) ||
-        m->flags != 0 || m->reserved != 0) {
-        set_error(c, "match outside the rules (query_len %u, n_refs %u, ref_stride %u, quant %g, flags %u, reserved %u)", N, R, S, (double)m->quant,
-                  m->flags, m->reserved);
-        return false;
-    }
-    if (n_out != 0 && (!m->ref || !m->ref_len || !query || !out)) {
-        set_error(c, "ref, ref_len, the query arena or the hit arena is NULL");
-        return false;
-    }
-    if ((((uintptr_t)m->ref | (uintptr_t)query | (uintptr_t)out) & 15u) != 0) {
-        set_error(c, "ref, the query arena or the hit arena is not 16-byte aligned");
-        return false;
-    }
-    if ((uint64_t)n_out * R > EXTENT_MAX / hit_bytes || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
-        set_error(c, "declared match arenas are not plausible (%u reads, %u references, %u samples)", n_out, R, N);
-        return false;
-    }
-    return true;
-}
-// the locate of a *_locate_batch call, likewise (out: n_out x G entries of hit_bytes each -- vbz_gpu_match_hit, or vbz_gpu_match_span of the span calls)
+// the locate of a *_locate_batch call, likewise
 static_assert(sizeof(vbz_gpu_locate) == 40, "vbz_gpu_locate is 40 bytes");
 static_assert(offsetof(vbz_gpu_locate, query_len) == 0 && offsetof(vbz_gpu_locate, n_targets) == 4 && offsetof(vbz_gpu_locate, target_stride) == 8 &&
                   offsetof(vbz_gpu_locate, flags) == 12 && offsetof(vbz_gpu_locate, quant) == 16 && offsetof(vbz_gpu_locate, reserved) == 20 &&
                   offsetof(vbz_gpu_locate, target) == 24 && offsetof(vbz_gpu_locate, target_len) == 32,
               "the fields of vbz_gpu_locate");
-bool locate_ok(vbz_gpu_ctx* c, const vbz_gpu_locate* m, const float* query, const void* out, size_t hit_bytes, uint32_t n_out)
+// What the two structs share, field for field: the view every check and launch below takes.  `levels` is the int8 matrix -- the references
+// of a match, the targets of a locate -- n_levels rows of levels_stride bytes.
+struct AlignView
 {
-    if (!m) {
-        set_error(c, "locate is NULL");
+    bool null;   // the caller's struct is NULL
+    uint32_t query_len, n_levels, levels_stride, flags;
+    float quant;
+    uint32_t reserved;
+    const int8_t* levels;
+    const uint32_t* levels_len;
+};
+AlignView align_view(const vbz_gpu_match* m)
+{
+    return m ? AlignView{ false, m->query_len, m->n_refs, m->ref_stride, m->flags, m->quant, m->reserved, m->ref, m->ref_len } : AlignView{ true };
+}
+AlignView align_view(const vbz_gpu_locate* l)
+{
+    return l ? AlignView{ false, l->query_len, l->n_targets, l->target_stride, l->flags, l->quant, l->reserved, l->target, l->target_len } : AlignView{ true };
+}
+// The two kinds: the nouns of their messages, the profile entries and launches of their calls, and their limits.  A match's references
+// sit in the lanes (32 rows a lane: 2048) and its query is streamed; a locate's query sits in the lanes (query_in_lanes) and its targets
+// are streamed, so they alone can be implausibly large, a path's rows are the query's, and its valid[] is never NULL.
+struct AlignKind
+{
+    const char *name, *level, *levels;   // "match", "ref", "refs"
+    uint32_t query_max, stride_max;
+    bool query_in_lanes;
+    const char *forward_entry, *trace_entry, *forward_launch, *trace_launch, *hit_launch, *span_launch;
+    hipError_t (*hit)(uint32_t, const float*, const uint32_t*, uint32_t, float, const int8_t*, const uint32_t*, uint32_t, uint32_t, void*, hipStream_t);
+    hipError_t (*span)(uint32_t, const float*, const uint32_t*, uint32_t, float, const int8_t*, const uint32_t*, uint32_t, uint32_t, void*, hipStream_t);
+    hipError_t (*path_forward)(const AlignPathArgs&, hipStream_t);
+    hipError_t (*path_trace)(const AlignPathArgs&, hipStream_t);
+};
+const AlignKind MATCH = { "match", "ref", "refs", 65536u, 2048u, false, "match_path_forward", "match_path_trace", "match path forward launch",
+                          "match path traceback launch", "match launch", "match span launch", launch_match, launch_match_span,
+                          launch_match_path_forward, launch_match_path_trace };
+const AlignKind LOCATE = { "locate", "target", "targets", 2048u, 1u << 30, true, "locate_path_forward", "locate_path_trace",
+                           "locate path forward launch", "locate path traceback launch", "locate launch", "locate span launch", launch_locate,
+                           launch_locate_span, launch_locate_path_forward, launch_locate_path_trace };
+// (out: n_out x n_levels entries of hit_bytes each -- vbz_gpu_match_hit, or vbz_gpu_match_span of the span calls)
+bool align_ok(vbz_gpu_ctx* c, const AlignKind& k, const AlignView& m, const float* query, const void* out, size_t hit_bytes, uint32_t n_out)
+{
+    if (m.null) {
+        set_error(c, "%s is NULL", k.name);
         return false;
     }
-    const uint32_t N = m->query_len, G = m->n_targets, S = m->target_stride;
-    if (N < 8 || N > 2048 || N % 8 != 0 || G < 1 || G > 4096 || S < 16 || S > (1u << 30) || S % 16 != 0 || !(m->quant > 0.0f) || !std::isfinite(m->quant) ||
-        m->flags != 0 || m->reserved != 0) {
-        set_error(c, "locate outside the rules (query_len %u, n_targets %u, target_stride %u, quant %g, flags %u, reserved %u)", N, G, S, (double)m->quant,
-                  m->flags, m->reserved);
+    const uint32_t N = m.query_len, R = m.n_levels, S = m.levels_stride;
+    if (N < 8 || N > k.query_max || N % 8 != 0 || R < 1 || R > 4096 || S < 16 || S > k.stride_max || S % 16 != 0 || !(m.quant > 0.0f) ||
+        !std::isfinite(m.quant) || m.flags != 0 || m.reserved != 0) {
+        set_error(c, "%s outside the rules (query_len %u, n_%s %u, %s_stride %u, quant %g, flags %u, reserved %u)", k.name, N, k.levels, R, k.level, S,
+                  (double)m.quant, m.flags, m.reserved);
         return false;
     }
-    if (n_out != 0 && (!m->target || !m->target_len || !query || !out)) {
-        set_error(c, "target, target_len, the query arena or the hit arena is NULL");
+    if (n_out != 0 && (!m.levels || !m.levels_len || !query || !out)) {
+        set_error(c, "%s, %s_len, the query arena or the hit arena is NULL", k.level, k.level);
         return false;
     }
-    if ((((uintptr_t)m->target | (uintptr_t)query | (uintptr_t)out) & 15u) != 0) {
-        set_error(c, "target, the query arena or the hit arena is not 16-byte aligned");
+    if ((((uintptr_t)m.levels | (uintptr_t)query | (uintptr_t)out) & 15u) != 0) {
+        set_error(c, "%s, the query arena or the hit arena is not 16-byte aligned", k.level);
         return false;
     }
-    if ((uint64_t)n_out * G > EXTENT_MAX / hit_bytes || (uint64_t)G * S > EXTENT_MAX || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
-        set_error(c, "declared locate arenas are not plausible (%u reads, %u targets of %u bytes, %u samples)", n_out, G, S, N);
+    if ((uint64_t)n_out * R > EXTENT_MAX / hit_bytes || (k.query_in_lanes && (uint64_t)R * S > EXTENT_MAX) || (uint64_t)n_out * N > EXTENT_MAX / sizeof(float)) {
+        if (k.query_in_lanes) set_error(c, "declared locate arenas are not plausible (%u reads, %u targets of %u bytes, %u samples)", n_out, R, S, N);
+        else set_error(c, "declared match arenas are not plausible (%u reads, %u references, %u samples)", n_out, R, N);
         return false;
     }
     return true;
@@ -1765,13 +1778,11 @@ struct TypedCall
     uint64_t* edge_first = nullptr;                  // ... rule, and the two tables the call fills -- edge_first and edge, which a vbz_gpu_events
     uint32_t* edge = nullptr;                        // ... reads as event_first and start
     bool with_match = false;                         // CHUNKS, in place of a chunking or windows: the window call of one row per read at start 0
-    const vbz_gpu_match* match = nullptr;            // ... (untrusted like every struct: NULL is refused)
-    float* match_query = nullptr;                    // ... into match_query (the library's own window tables), then the match launch on the
-    void* match_out = nullptr;                       // ... context's stream: every pair's hit into match_out -- vbz_gpu_match_hit, or with
-    bool match_span = false;                         // ... match_span vbz_gpu_match_span (the span launch in the match launch's place)
-    bool with_locate = false;                        // ... or, beside with_match, a locate in the match's place (untrusted likewise): the same
-    const vbz_gpu_locate* locate = nullptr;          // ... window call and valid[], then the locate launch into match_out (vbz_gpu_match_hit; with
-                                                     // ... match_span vbz_gpu_match_span, the locate span launch in its place)
+    const AlignKind* align = nullptr;                // ... into match_query (the library's own window tables), then the launch of a match or of a
+    AlignView match = { true };                      // ... locate (untrusted like every struct: NULL is refused) on the context's stream: every
+    float* match_query = nullptr;                    // ... pair's hit into match_out -- vbz_gpu_match_hit, or with match_span vbz_gpu_match_span
+    void* match_out = nullptr;                       // ... (the span launch in the other's place)
+    bool match_span = false;
 
     TypedCall(Typed k, int s) : kind(k), sized(s) {}
     TypedCall& format(const vbz_gpu_signal_format* f_) { f = f_; return *this; }
@@ -1801,10 +1812,8 @@ struct TypedCall
     TypedCall& trimmed(const vbz_gpu_trim* t, uint32_t* b) { with_trim = true, trim = t, begin = b; return *this; }
     TypedCall& segmented(const vbz_gpu_segmentation* g, uint64_t* first, uint32_t* start) { seg = g, seg_first = first, seg_start = start; return *this; }
     TypedCall& spanned(const vbz_gpu_spans* g, uint64_t* first, uint32_t* e) { spans = g, edge_first = first, edge = e; return *this; }
-    TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_hit* out) { with_match = true, match = m, match_query = query, match_out = out; return *this; }
-    TypedCall& matched(const vbz_gpu_match* m, float* query, vbz_gpu_match_span* out) { matched(m, query, (vbz_gpu_match_hit*)nullptr); match_out = out, match_span = true; return *this; }
-    TypedCall& located(const vbz_gpu_locate* l, float* query, vbz_gpu_match_hit* out) { with_match = with_locate = true, locate = l, match_query = query, match_out = out; return *this; }
-    TypedCall& located(const vbz_gpu_locate* l, float* query, vbz_gpu_match_span* out) { located(l, query, (vbz_gpu_match_hit*)nullptr); match_out = out, match_span = true; return *this; }
+    TypedCall& aligned(const AlignKind& k, const AlignView& m, float* query, vbz_gpu_match_hit* out) { with_match = true, align = &k, match = m, match_query = query, match_out = out; return *this; }
+    TypedCall& aligned(const AlignKind& k, const AlignView& m, float* query, vbz_gpu_match_span* out) { aligned(k, m, query, (vbz_gpu_match_hit*)nullptr); match_out = out, match_span = true; return *this; }
 };
 
 // Typed decode (vbz_gpu_decompress_signal_batch): the caller's dst side describes the typed arena, E bytes per sample.  The call decodes
@@ -2023,7 +2032,8 @@ int decompress_batch_impl(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const Compres
 // call writes nothing, and every hit is the empty verdict.
 int match_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, TypedCall& t, uint32_t n_out)
 {
-    const uint32_t N = t.with_locate ? t.locate->query_len : t.match->query_len;
+    const AlignView& m = t.match;
+    const uint32_t N = m.query_len;
     MatchTables tab;
     if (!ensure_carved(c, c->matchmeta, tab, n_out)) return -1;
     {
@@ -2043,17 +2053,9 @@ int match_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     Timed tm(c, "match");
     HIPCHK(c, launch_match_valid(n_out, t.pod5 ? reads.read_result : bt->result, t.ranges ? t.ranges->begin : nullptr, t.ranges ? t.ranges->end : nullptr,
                                  N, tab.valid, c->stream), "match valid launch");
-    if (t.with_locate) {
-        const vbz_gpu_locate& l = *t.locate;
-        HIPCHK(c, (t.match_span ? launch_locate_span : launch_locate)(n_out, t.match_query, tab.valid, N, l.quant, l.target, l.target_len, l.n_targets,
-                                                                      l.target_stride, t.match_out, c->stream),
-               "locate launch");
-        return 0;
-    }
-    const vbz_gpu_match& m = *t.match;
-    HIPCHK(c, (t.match_span ? launch_match_span : launch_match)(n_out, t.match_query, tab.valid, m.query_len, m.quant, m.ref, m.ref_len, m.n_refs,
-                                                                m.ref_stride, t.match_out, c->stream),
-           "match launch");
+    HIPCHK(c, (t.match_span ? t.align->span : t.align->hit)(n_out, t.match_query, tab.valid, N, m.quant, m.levels, m.levels_len, m.n_levels, m.levels_stride,
+                                                             t.match_out, c->stream),
+           t.align->hit_launch);
     return 0;
 }
 
@@ -2083,9 +2085,7 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
         if (!events_ok(c, t.ev, t.f, t.ev_out, t.ev_moments, n_out)) return -2;
     } else if (t.kind == Typed::CHUNKS && t.with_match) {                                                            // 8 (a match in place of a chunking)
         const size_t hit_bytes = t.match_span ? sizeof(vbz_gpu_match_span) : sizeof(vbz_gpu_match_hit);
-        if (t.with_locate ? !locate_ok(c, t.locate, t.match_query, t.match_out, hit_bytes, n_out)
-                          : !match_ok(c, t.match, t.match_query, t.match_out, hit_bytes, n_out))
-            return -2;
+        if (!align_ok(c, *t.align, t.match, t.match_query, t.match_out, hit_bytes, n_out)) return -2;
         if (t.f->out_type != VBZ_GPU_SIGNAL_F32) {
             set_error(c, "the query of a match is float32 (out_type %u)", t.f->out_type);
             return -2;
@@ -2118,6 +2118,72 @@ int typed_decode(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptio
     if (stats) t.f = &none;
     if (t.with_match) return match_decode(c, bt, o, t, n_out);                                                       // 11 (the window call, then the match)
     return decompress_batch_impl(c, bt, o, t.sized, false, &t);                                                      // 11
+}
+
+// A stage call on a query arena the caller filled (vbz_gpu_*_match_batch, ..._locate_batch and their span forms): the checks, then the launch
+int align_stage(vbz_gpu_ctx* c, const AlignKind& k, const AlignView& m, uint32_t n_reads, const float* query, const uint32_t* valid, void* out, bool span)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!align_ok(c, k, m, query, out, span ? sizeof(vbz_gpu_match_span) : sizeof(vbz_gpu_match_hit), n_reads)) return -2;
+    if (n_reads != 0 && !valid) {
+        set_error(c, "valid is NULL");
+        return -2;
+    }
+    Timed t(c, k.name);
+    HIPCHK(c, (span ? k.span : k.hit)(n_reads, query, valid, m.query_len, m.quant, m.levels, m.levels_len, m.n_levels, m.levels_stride, out, c->stream),
+           span ? k.span_launch : k.hit_launch);
+    return 0;
+}
+
+// The path call of a match or a locate: the view's and the path struct's rules, the tables a call with pairs needs, the extents, then the
+// groups -- forward launch and traceback -- over the context's scratch.  The rows of the cost matrix are the operand in the lanes: a pair
+// owns ref_stride rows of a match and query_len of a locate.  A match takes valid == NULL (every row has N samples); a locate refuses it.
+int path_call(vbz_gpu_ctx* c, const AlignKind& k, const AlignView& m, uint32_t n_pairs, uint32_t n_reads, const float* query, const uint32_t* valid,
+              const vbz_gpu_match_pair* pairs, const vbz_gpu_match_path* path, vbz_gpu_match_span* hit, vbz_gpu_match_row* rows)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    // (the view's own rules, the levels' extent and the alignment of the levels, query and hit; the tables a call with pairs needs: below)
+    if (!align_ok(c, k, m, query, hit, sizeof(vbz_gpu_match_span), 0)) return -2;
+    if (!path || path->flags != 0 || path->reserved != 0 || path->max_width < 8 || path->max_width > 65536 || path->max_width % 8 != 0) {
+        set_error(c, "path is NULL or outside the rules (max_width %u, flags %u)", path ? path->max_width : 0u, path ? path->flags : 0u);
+        return -2;
+    }
+    if (n_pairs != 0 && (!m.levels || !m.levels_len || !query || (!valid && k.query_in_lanes) || !pairs || !hit || !rows)) {
+        set_error(c, "%s, %s_len, the query arena, %sthe pair table, the hit table or the row arena is NULL", k.level, k.level, k.query_in_lanes ? "valid, " : "");
+        return -2;
+    }
+    if ((((uintptr_t)pairs | (uintptr_t)rows) & 15u) != 0) {
+        set_error(c, "the pair table or the row arena is not 16-byte aligned");
+        return -2;
+    }
+    const uint32_t rows_stride = k.query_in_lanes ? m.query_len : m.levels_stride;
+    if ((uint64_t)n_pairs * rows_stride > EXTENT_MAX / sizeof(vbz_gpu_match_row) || (uint64_t)n_reads * m.query_len > EXTENT_MAX / sizeof(float)) {
+        set_error(c, "declared path arenas are not plausible (%u pairs, %u reads)", n_pairs, n_reads);
+        return -2;
+    }
+    if (n_pairs == 0) return 0;
+    AlignPathArgs a{};
+    a.query = query, a.valid = valid, a.n_reads = n_reads, a.N = m.query_len, a.quant = m.quant;
+    a.levels = m.levels, a.levels_len = m.levels_len, a.n_levels = m.n_levels, a.levels_stride = m.levels_stride;
+    a.pairs = reinterpret_cast<const uint4*>(pairs), a.max_width = path->max_width;
+    a.pair_words = match_path_pair_words(a.max_width, rows_stride);
+    a.hit = reinterpret_cast<uint4*>(hit), a.rows = reinterpret_cast<uint2*>(rows);
+    const uint32_t group = match_path_group_pairs(n_pairs, a.max_width, rows_stride, c->knobs.match_path_cap);
+    MatchPathScratch sc;
+    if (!ensure_carved(c, c->matchpath, sc, group, a.pair_words)) return -1;
+    a.bits = sc.bits, a.cost = sc.cost;
+    for (uint32_t first = 0; first < n_pairs; first += group) {   // (the groups share the scratch: the stream orders them)
+        a.first = first, a.count = n_pairs - first < group ? n_pairs - first : group;
+        {
+            Timed t(c, k.forward_entry);
+            HIPCHK(c, k.path_forward(a, c->stream), k.forward_launch);
+        }
+        Timed t(c, k.trace_entry);
+        HIPCHK(c, k.path_trace(a, c->stream), k.trace_launch);
+    }
+    return 0;
 }
 
 }  // namespace
@@ -2540,24 +2606,14 @@ int vbz_gpu_pod5_signal_spans_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
 
 int vbz_gpu_match_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match, vbz_gpu_match_hit* out)
 {
-    if (!c) return -1;
-    DeviceGuard dg(c->device);
-    if (!match_ok(c, match, query, out, sizeof(vbz_gpu_match_hit), n_reads)) return -2;
-    if (n_reads != 0 && !valid) {
-        set_error(c, "valid is NULL");
-        return -2;
-    }
-    Timed t(c, "match");
-    HIPCHK(c, launch_match(n_reads, query, valid, match->query_len, match->quant, match->ref, match->ref_len, match->n_refs, match->ref_stride, out, c->stream),
-           "match launch");
-    return 0;
+    return align_stage(c, MATCH, align_view(match), n_reads, query, valid, out, false);
 }
 
 int vbz_gpu_signal_match_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
                                const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match,
                                float* query, vbz_gpu_match_hit* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).matched(match, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).aligned(MATCH, align_view(match), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
@@ -2565,31 +2621,20 @@ int vbz_gpu_pod5_signal_match_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, con
                                     const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
                                     const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query, vbz_gpu_match_hit* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).matched(match, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).aligned(MATCH, align_view(match), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
 int vbz_gpu_match_span_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match, vbz_gpu_match_span* out)
 {
-    if (!c) return -1;
-    DeviceGuard dg(c->device);
-    if (!match_ok(c, match, query, out, sizeof(vbz_gpu_match_span), n_reads)) return -2;
-    if (n_reads != 0 && !valid) {
-        set_error(c, "valid is NULL");
-        return -2;
-    }
-    Timed t(c, "match");
-    HIPCHK(c, launch_match_span(n_reads, query, valid, match->query_len, match->quant, match->ref, match->ref_len, match->n_refs, match->ref_stride, out,
-                                c->stream),
-           "match span launch");
-    return 0;
+    return align_stage(c, MATCH, align_view(match), n_reads, query, valid, out, true);
 }
 
 int vbz_gpu_signal_match_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
                                     const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match,
                                     float* query, vbz_gpu_match_span* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).matched(match, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).aligned(MATCH, align_view(match), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
@@ -2597,31 +2642,20 @@ int vbz_gpu_pod5_signal_match_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt
                                          const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
                                          const vbz_gpu_sample_ranges* ranges, const vbz_gpu_match* match, float* query, vbz_gpu_match_span* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).matched(match, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).aligned(MATCH, align_view(match), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
 int vbz_gpu_locate_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate, vbz_gpu_match_hit* out)
 {
-    if (!c) return -1;
-    DeviceGuard dg(c->device);
-    if (!locate_ok(c, locate, query, out, sizeof(vbz_gpu_match_hit), n_reads)) return -2;
-    if (n_reads != 0 && !valid) {
-        set_error(c, "valid is NULL");
-        return -2;
-    }
-    Timed t(c, "locate");
-    HIPCHK(c, launch_locate(n_reads, query, valid, locate->query_len, locate->quant, locate->target, locate->target_len, locate->n_targets,
-                            locate->target_stride, out, c->stream),
-           "locate launch");
-    return 0;
+    return align_stage(c, LOCATE, align_view(locate), n_reads, query, valid, out, false);
 }
 
 int vbz_gpu_signal_locate_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
                                 const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate,
                                 float* query, vbz_gpu_match_hit* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).located(locate, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).aligned(LOCATE, align_view(locate), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
@@ -2629,32 +2663,21 @@ int vbz_gpu_pod5_signal_locate_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, co
                                      const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
                                      const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate, float* query, vbz_gpu_match_hit* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).located(locate, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).aligned(LOCATE, align_view(locate), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
 int vbz_gpu_locate_span_batch(vbz_gpu_ctx* c, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate,
                               vbz_gpu_match_span* out)
 {
-    if (!c) return -1;
-    DeviceGuard dg(c->device);
-    if (!locate_ok(c, locate, query, out, sizeof(vbz_gpu_match_span), n_reads)) return -2;
-    if (n_reads != 0 && !valid) {
-        set_error(c, "valid is NULL");
-        return -2;
-    }
-    Timed t(c, "locate");
-    HIPCHK(c, launch_locate_span(n_reads, query, valid, locate->query_len, locate->quant, locate->target, locate->target_len, locate->n_targets,
-                                 locate->target_stride, out, c->stream),
-           "locate span launch");
-    return 0;
+    return align_stage(c, LOCATE, align_view(locate), n_reads, query, valid, out, true);
 }
 
 int vbz_gpu_signal_locate_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const CompressionOptions* o, int sized, const vbz_gpu_signal_format* f,
                                      const vbz_gpu_normalization* norm, float* shift_scale, const vbz_gpu_sample_ranges* ranges,
                                      const vbz_gpu_locate* locate, float* query, vbz_gpu_match_span* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).located(locate, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, sized).format(f).aligned(LOCATE, align_view(locate), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
@@ -2662,7 +2685,7 @@ int vbz_gpu_pod5_signal_locate_span_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* b
                                           const vbz_gpu_pod5_reads* reads, const vbz_gpu_normalization* norm, float* shift_scale,
                                           const vbz_gpu_sample_ranges* ranges, const vbz_gpu_locate* locate, float* query, vbz_gpu_match_span* out)
 {
-    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).located(locate, query, out)
+    return typed_decode(c, bt, o, TypedCall(Typed::CHUNKS, 0).format(f).pod5_reads(reads).aligned(LOCATE, align_view(locate), query, out)
                                       .normalise(norm, Null::ALLOWED, shift_scale, Null::ALLOWED).range(ranges));
 }
 
@@ -2695,93 +2718,13 @@ int vbz_gpu_match_best_batch(vbz_gpu_ctx* c, uint32_t n_reads, const vbz_gpu_mat
 int vbz_gpu_match_path_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_match* match,
                              const vbz_gpu_match_pair* pairs, const vbz_gpu_match_path* path, vbz_gpu_match_span* hit, vbz_gpu_match_row* rows)
 {
-    if (!c) return -1;
-    DeviceGuard dg(c->device);
-    // (the match's own rules, the query's extent and the alignment of ref, query and hit; the tables a call with pairs needs: below)
-    if (!match_ok(c, match, query, hit, sizeof(vbz_gpu_match_span), 0)) return -2;
-    if (!path || path->flags != 0 || path->reserved != 0 || path->max_width < 8 || path->max_width > 65536 || path->max_width % 8 != 0) {
-        set_error(c, "path is NULL or outside the rules (max_width %u, flags %u)", path ? path->max_width : 0u, path ? path->flags : 0u);
-        return -2;
-    }
-    if (n_pairs != 0 && (!match->ref || !match->ref_len || !query || !pairs || !hit || !rows)) {
-        set_error(c, "ref, ref_len, the query arena, the pair table, the hit table or the row arena is NULL");
-        return -2;
-    }
-    if ((((uintptr_t)pairs | (uintptr_t)rows) & 15u) != 0) {
-        set_error(c, "the pair table or the row arena is not 16-byte aligned");
-        return -2;
-    }
-    if ((uint64_t)n_pairs * match->ref_stride > EXTENT_MAX / sizeof(vbz_gpu_match_row) || (uint64_t)n_reads * match->query_len > EXTENT_MAX / sizeof(float)) {
-        set_error(c, "declared path arenas are not plausible (%u pairs, %u reads)", n_pairs, n_reads);
-        return -2;
-    }
-    if (n_pairs == 0) return 0;
-    MatchPathArgs a{};
-    a.query = query, a.valid = valid, a.n_reads = n_reads, a.N = match->query_len, a.quant = match->quant;
-    a.ref = match->ref, a.ref_len = match->ref_len, a.R = match->n_refs, a.ref_stride = match->ref_stride;
-    a.pairs = reinterpret_cast<const uint4*>(pairs), a.max_width = path->max_width;
-    a.pair_words = match_path_pair_words(a.max_width, a.ref_stride);
-    a.hit = reinterpret_cast<uint4*>(hit), a.rows = reinterpret_cast<uint2*>(rows);
-    const uint32_t group = match_path_group_pairs(n_pairs, a.max_width, a.ref_stride, c->knobs.match_path_cap);
-    MatchPathScratch sc;
-    if (!ensure_carved(c, c->matchpath, sc, group, a.pair_words)) return -1;
-    a.bits = sc.bits, a.cost = sc.cost;
-    for (uint32_t first = 0; first < n_pairs; first += group) {   // (the groups share the scratch: the stream orders them)
-        a.first = first, a.count = n_pairs - first < group ? n_pairs - first : group;
-        {
-            Timed t(c, "match_path_forward");
-            HIPCHK(c, launch_match_path_forward(a, c->stream), "match path forward launch");
-        }
-        Timed t(c, "match_path_trace");
-        HIPCHK(c, launch_match_path_trace(a, c->stream), "match path traceback launch");
-    }
-    return 0;
+    return path_call(c, MATCH, align_view(match), n_pairs, n_reads, query, valid, pairs, path, hit, rows);
 }
 
 int vbz_gpu_locate_path_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads, const float* query, const uint32_t* valid, const vbz_gpu_locate* locate,
                               const vbz_gpu_match_pair* pairs, const vbz_gpu_match_path* path, vbz_gpu_match_span* hit, vbz_gpu_match_row* rows)
 {
-    if (!c) return -1;
-    DeviceGuard dg(c->device);
-    // (the locate's own rules, the targets' extent and the alignment of target, query and hit; the tables a call with pairs needs: below)
-    if (!locate_ok(c, locate, query, hit, sizeof(vbz_gpu_match_span), 0)) return -2;
-    if (!path || path->flags != 0 || path->reserved != 0 || path->max_width < 8 || path->max_width > 65536 || path->max_width % 8 != 0) {
-        set_error(c, "path is NULL or outside the rules (max_width %u, flags %u)", path ? path->max_width : 0u, path ? path->flags : 0u);
-        return -2;
-    }
-    if (n_pairs != 0 && (!locate->target || !locate->target_len || !query || !valid || !pairs || !hit || !rows)) {
-        set_error(c, "target, target_len, the query arena, valid, the pair table, the hit table or the row arena is NULL");
-        return -2;
-    }
-    if ((((uintptr_t)pairs | (uintptr_t)rows) & 15u) != 0) {
-        set_error(c, "the pair table or the row arena is not 16-byte aligned");
-        return -2;
-    }
-    if ((uint64_t)n_pairs * locate->query_len > EXTENT_MAX / sizeof(vbz_gpu_match_row) || (uint64_t)n_reads * locate->query_len > EXTENT_MAX / sizeof(float)) {
-        set_error(c, "declared path arenas are not plausible (%u pairs, %u reads)", n_pairs, n_reads);
-        return -2;
-    }
-    if (n_pairs == 0) return 0;
-    LocatePathArgs a{};
-    a.query = query, a.valid = valid, a.n_reads = n_reads, a.N = locate->query_len, a.quant = locate->quant;
-    a.target = locate->target, a.target_len = locate->target_len, a.G = locate->n_targets, a.target_stride = locate->target_stride;
-    a.pairs = reinterpret_cast<const uint4*>(pairs), a.max_width = path->max_width;
-    a.pair_words = match_path_pair_words(a.max_width, a.N);   // (the rows of the cost matrix are the query's: query_len in ref_stride's place)
-    a.hit = reinterpret_cast<uint4*>(hit), a.rows = reinterpret_cast<uint2*>(rows);
-    const uint32_t group = match_path_group_pairs(n_pairs, a.max_width, a.N, c->knobs.match_path_cap);
-    MatchPathScratch sc;
-    if (!ensure_carved(c, c->matchpath, sc, group, a.pair_words)) return -1;
-    a.bits = sc.bits, a.cost = sc.cost;
-    for (uint32_t first = 0; first < n_pairs; first += group) {   // (the groups share the scratch: the stream orders them)
-        a.first = first, a.count = n_pairs - first < group ? n_pairs - first : group;
-        {
-            Timed t(c, "locate_path_forward");
-            HIPCHK(c, launch_locate_path_forward(a, c->stream), "locate path forward launch");
-        }
-        Timed t(c, "locate_path_trace");
-        HIPCHK(c, launch_locate_path_trace(a, c->stream), "locate path traceback launch");
-    }
-    return 0;
+    return path_call(c, LOCATE, align_view(locate), n_pairs, n_reads, query, valid, pairs, path, hit, rows);
 }
 
 int vbz_gpu_query_valid_batch(vbz_gpu_ctx* c, uint32_t n_reads, const uint32_t* result, const vbz_gpu_sample_ranges* ranges, uint32_t query_len,

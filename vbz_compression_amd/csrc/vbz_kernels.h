@@ -758,29 +758,34 @@ hipError_t launch_match_span(uint32_t n_reads, const float* query, const uint32_
 // The path calls (vbz_gpu_match_best_batch, vbz_gpu_match_path_batch).  launch_match_best: pairs[i] = {i, the reference of least cost
 // <= max_cost among spans[i R ... i R + R), its start, its end} or {i, 0xFFFFFFFF, 0, 0}; 16-byte entries both.
 hipError_t launch_match_best(uint32_t n_reads, const void* spans, uint32_t R, uint32_t max_cost, void* pairs, hipStream_t s);
-// One group of a path call: pairs first ... first + count - 1 of the caller's table, slot w = pair - first of the scratch.
-struct MatchPathArgs
+// One group of a path call (vbz_gpu_match_path_batch, vbz_gpu_locate_path_batch): pairs first ... first + count - 1 of the caller's table,
+// slot w = pair - first of the scratch.  `levels` is the int8 matrix: the references of a match, which sit in the lanes, or the targets of
+// a locate, which are streamed -- a pair's window [begin, end) is in query samples in the one and in TARGET levels in the other.  The rows
+// of the cost matrix are the lanes' operand, so a pair owns levels_stride entries of `rows` in a match and N in a locate.
+struct AlignPathArgs
 {
-    const float* query;      // [n_reads, N]
-    const uint32_t* valid;   // [n_reads], or nullptr: N samples a row
+    const float* query;          // [n_reads, N]
+    const uint32_t* valid;       // [n_reads], untrusted; a match: or nullptr, N samples a row
     uint32_t n_reads, N;
     float quant;
-    const int8_t* ref;       // [R, ref_stride]
-    const uint32_t* ref_len; // [R], untrusted
-    uint32_t R, ref_stride;
-    const uint4* pairs;      // {read, ref, begin, end}, untrusted
+    const int8_t* levels;        // [n_levels, levels_stride]
+    const uint32_t* levels_len;  // [n_levels], untrusted
+    uint32_t n_levels, levels_stride;
+    const uint4* pairs;          // {read, ref or target, begin, end}, untrusted
     uint32_t max_width;
     uint32_t first, count;
-    uint64_t pair_words;     // match_path_pair_words(max_width, ref_stride)
-    uint32_t* bits;          // [count x pair_words]: the direction bits (MatchPathScratch)
-    uint32_t* cost;          // [count]: the forward pass's cost
-    uint4* hit;              // [n_pairs]
-    uint2* rows;             // [n_pairs, ref_stride]
+    uint64_t pair_words;         // match_path_pair_words(max_width, the rows' stride)
+    uint32_t* bits;              // [count x pair_words]: the direction bits (MatchPathScratch)
+    uint32_t* cost;              // [count]: the forward pass's cost
+    uint4* hit;                  // [n_pairs]
+    uint2* rows;                 // [n_pairs, the rows' stride]
 };
-// The forward launch (the packed kernel or the wide one, by match_select.h with max_width in N's place) and the traceback behind it.  Between
-// them every hit and every row of the group's pairs is written.
-hipError_t launch_match_path_forward(const MatchPathArgs& a, hipStream_t s);
-hipError_t launch_match_path_trace(const MatchPathArgs& a, hipStream_t s);
+// The forward launch (the packed kernel or the wide one, by match_select.h with max_width in N's place and, in a locate, N in ref_stride's)
+// and the traceback behind it.  Between them every hit and every row of the group's pairs is written.
+hipError_t launch_match_path_forward(const AlignPathArgs& a, hipStream_t s);
+hipError_t launch_match_path_trace(const AlignPathArgs& a, hipStream_t s);
+hipError_t launch_locate_path_forward(const AlignPathArgs& a, hipStream_t s);
+hipError_t launch_locate_path_trace(const AlignPathArgs& a, hipStream_t s);
 // ... the fused calls' tables.  launch_match_windows: the window tables of "one row per read at start 0" (first: n + 1 entries, start: n).
 // launch_match_valid, behind the decode: valid[i] = min(T', N) from the verdict result[i] (T x 4 bytes; an error: 0) and the range tables
 // (nullable), clamped as sample_range clamps them.
@@ -796,30 +801,6 @@ hipError_t launch_locate(uint32_t n_reads, const float* query, const uint32_t* v
 // coordinates, found by a bounded walk back from (cost, end) in the same wavefront.
 hipError_t launch_locate_span(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* target,
                               const uint32_t* target_len, uint32_t G, uint32_t target_stride, void* out, hipStream_t s);
-// One group of a locate path call (vbz_gpu_locate_path_batch), as MatchPathArgs: pairs first ... first + count - 1 of the caller's table,
-// slot w = pair - first of the scratch.  A pair's window [begin, end) is in TARGET coordinates and its rows are the query's.
-struct LocatePathArgs
-{
-    const float* query;         // [n_reads, N]
-    const uint32_t* valid;      // [n_reads], untrusted
-    uint32_t n_reads, N;
-    float quant;
-    const int8_t* target;       // [G, target_stride]
-    const uint32_t* target_len; // [G], untrusted
-    uint32_t G, target_stride;
-    const uint4* pairs;         // {read, target, begin, end}, untrusted
-    uint32_t max_width;
-    uint32_t first, count;
-    uint64_t pair_words;        // match_path_pair_words(max_width, N)
-    uint32_t* bits;             // [count x pair_words]: the direction bits (MatchPathScratch)
-    uint32_t* cost;             // [count]: the forward pass's cost
-    uint4* hit;                 // [n_pairs]
-    uint2* rows;                // [n_pairs, N]
-};
-// The forward launch (the packed key or the wide one, by match_select.h with max_width in N's place and N in ref_stride's) and the
-// traceback behind it.  Between them every hit and every row of the group's pairs is written.
-hipError_t launch_locate_path_forward(const LocatePathArgs& a, hipStream_t s);
-hipError_t launch_locate_path_trace(const LocatePathArgs& a, hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
