@@ -1095,6 +1095,82 @@ VBZ_EXPORT int vbz_gpu_locate_path_batch(vbz_gpu_ctx* ctx, uint32_t n_pairs, uin
 VBZ_EXPORT int vbz_gpu_query_valid_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const uint32_t* result, const vbz_gpu_sample_ranges* ranges,
                                          uint32_t query_len, uint32_t* valid);
 
+/* Event-space alignment.  The alignment calls above take samples: at about ten samples a base, the 2 048 entries of a locate query reach
+ * some 200 target levels.  Squiggle mappers align EVENTS, one value a base, and an event-align or re-squiggle tool wants the answer as a
+ * table per target level.  The two stage-level calls below are those two links, so that
+ *   segment -> events -> events_query -> locate_span -> match_best -> locate_path -> locate_levels
+ * is a run of queued calls on one stream with no host copy.  No other call changes; the locate limit of 2 048 entries stands.
+ * vbz_gpu_events_query_batch: the event records as a query arena.  The rule (tests/eventalign_ref.py).  Read i owns rows
+ * c0 = event_first[i] ... c1 - 1 of `records` (a vbz_gpu_events, as the event calls read it; events->start is not read and may be NULL).
+ * Walk them in order and keep the rows with records[c].n >= min_n (0 keeps all).  The k-th kept row, k < N = query_len, gives
+ * query[i][k] = records[c].mean, the 32 bits copied (NaN payloads, -0), and index[i][k] = c - c0; the walk stops behind N kept rows.
+ * valid[i] is the number kept, at most N; positions at and behind it hold +0 in query and 0 in index.  index may be NULL.  result may be
+ * NULL, meaning every read is good; otherwise a read whose result[i] is an error verdict gets valid[i] = 0, by exactly the test of
+ * vbz_gpu_query_valid_batch.  event_first is untrusted: a read gets valid[i] = 0, and no address is formed from its rows, when
+ * event_first[i] > event_first[i + 1], event_first[i + 1] > event_rows, or it has more than 2^31 - 1 rows.  query and index are row-major
+ * [n_reads, N] arenas, 16-byte aligned.  EVERY entry of query, valid and index is written by every call that launches; nothing else is.
+ * Returns 0 when queued, -1 for a NULL context or a launch failure, -2, with nothing launched and nothing written, for a NULL events or
+ * q, flags or reserved != 0 in either, query_len outside its rule, a NULL event_first, records (when event_rows > 0), query or valid while
+ * the call has reads, query, records or index not 16-byte aligned, n_reads * N * 4 or event_rows * 16 beyond 2^46 bytes.
+ * vbz_gpu_locate_levels_batch: the path, transposed.  pairs, hit and rows ([n_pairs, query_len]) are what vbz_gpu_locate_path_batch took
+ * and wrote; of a pair only `read` is used.  index is the first call's [n_reads, query_len] table (NULL: entry k is row k); events -- with
+ * start REQUIRED here -- records and moments are the event call's tables.  The rule.  For pair p with hit {cost, end, start, n}: levels
+ * is a row-major [n_pairs, max_width] arena of vbz_gpu_level, 16-byte aligned, and row t of pair p is target level start + t, t < end -
+ * start.  The entries of level j are E_j = {k < n : begin_k <= j < end_k}: the path is monotone, so that is a range [k0, k1), never empty
+ * inside [start, end).  Entry k is event row c_k = event_first[read] + index[read][k].  first_sample = start[c_k0]; end_sample =
+ * start[c] + records[c].n of c = c_(k1-1); n_samples, sum and sumsq are the sums of records[c_k].n, moments[c_k].sum and
+ * moments[c_k].sumsq over k0 <= k < k1, modulo 2^32 and 2^64 -- the tables are inputs, and the rule is the same whether the sums are
+ * added up or taken as differences of prefix sums; n_entries = k1 - k0.  An entry aligned to several levels counts in each.
+ * n_levels[p] = end - start; rows at and behind it are 32 zero bytes.  Floating-point mean and sd of a level are the event call's
+ * formulas over its exact moments, the caller's to apply.
+ * Every table is untrusted.  A pair gets n_levels = 0 and every row zero, with no address formed from an unchecked value, when
+ * read >= n_reads; n == 0 (the empty verdict and the best call's "none" are that) or n > query_len; start >= end or end - start >
+ * max_width; a row breaks the path's invariants -- begin_0 == start, end_(n-1) == end, begin_k < end_k, begin_(k+1) one of end_k - 1 and
+ * end_k; an index[read][k], k < n, at or beyond the read's row count; or a bad event_first as above.  EVERY entry of n_levels and levels
+ * is written by every call that launches, the latter by 16-byte stores; nothing else is.
+ * Returns 0 / -1 as above; -2 for a NULL events or flags or reserved != 0 in it; query_len or max_width outside 8 ... 65536 in multiples
+ * of 8; a NULL pairs, hit, rows, event_first, n_levels or levels while the call has pairs -- and start, records or moments when
+ * event_rows > 0; pairs, hit, rows, records, moments or levels not 16-byte aligned; n_pairs * query_len * 8, n_pairs * max_width * 32,
+ * n_reads * query_len * 4 or event_rows * 16 beyond 2^46 bytes.
+ * How (csrc/eventalign.hip).  Both: one wavefront per read / pair, four to a workgroup; no LDS, no barrier, no atomics,
+ * no scratch.  The query is a stream compaction: 64 rows a turn, the keep mask by a ballot, the rank by mbcnt, and the wavefront leaves
+ * as soon as N are kept; it writes the zero tail itself, by 16-byte stores.  The levels are differences of prefix values with no prefix
+ * array: a pass over the path checks it; a second pass takes 64 entries a turn, scans n, S1 and S2 across the lanes with a carried total,
+ * and the LAST entry of a level writes its record -- the exclusive sums of the level's first entry come by one shuffle from the lane a
+ * running maximum names, or from a carry when a stall began in an earlier turn.  A turn costs the same whatever the path looks like; an
+ * entry spanning many levels is written by the whole wavefront: O(n + width) a pair.
+ * Measured on one MI355X (tools/time_eventalign.py, profiles/eventalign_time.json; the parent of the commit that adds these calls is f62cf9c
+ * and can run neither, so the comparison is the unfused route in the same run; median of 20, the legs alternating in one process, every
+ * table checked bit for bit against the stopped chains, the stage calls and the unfused routes, six reads held to numpy): 8 192 step-signal
+ * reads of ~100 k samples, 66.0 M events, N = 2 048, min_n = 4, G = 2 targets of 30 000 levels, winners 1 857 levels wide in the median,
+ * max_width 2 256.  events_query alone 0.109 ms against 5.80 ms for torch (repeat_interleave, cumsum ranks, one scatter: 53 x);
+ * locate_levels alone 0.462 ms against 6.14 ms for torch (cumsum over entries, two searchsorted, gathers: 13 x).  The chain 103.73 ms:
+ * segment -> events 30.52, stopped before locate_levels 103.36; the locate legs they stand beside are 63.27 ms (span) and 9.24 ms (path).
+ * Both calls move their tables about once -- some 0.4 GB and 1.5 GB, 3 - 4 TB/s -- and wait for memory. */
+typedef struct vbz_gpu_events_query
+{
+    uint32_t query_len; /* N: a multiple of 8, 8 ... 65536 */
+    uint32_t min_n;     /* events with n < min_n are dropped; 0 keeps all */
+    uint32_t flags;     /* must be 0 */
+    uint32_t reserved;  /* must be 0 */
+} vbz_gpu_events_query; /* 16 bytes */
+typedef struct vbz_gpu_level
+{
+    uint32_t first_sample; /* start[] of the first entry's event */
+    uint32_t end_sample;   /* start + n of the last entry's event */
+    uint32_t n_samples;    /* sum of n over the level's entries */
+    uint32_t n_entries;    /* query entries aligned to this level, >= 1 */
+    int64_t sum;           /* sum of S1, modulo 2^64 */
+    uint64_t sumsq;        /* sum of S2, modulo 2^64 */
+} vbz_gpu_level;           /* 32 bytes */
+VBZ_EXPORT int vbz_gpu_events_query_batch(vbz_gpu_ctx* ctx, uint32_t n_reads, const uint32_t* result, const vbz_gpu_events* events,
+                                          const vbz_gpu_event* records, const vbz_gpu_events_query* q, float* query, uint32_t* valid,
+                                          uint32_t* index);
+VBZ_EXPORT int vbz_gpu_locate_levels_batch(vbz_gpu_ctx* ctx, uint32_t n_pairs, uint32_t n_reads, uint32_t query_len, uint32_t max_width,
+                                           const vbz_gpu_match_pair* pairs, const vbz_gpu_match_span* hit, const vbz_gpu_match_row* rows,
+                                           const uint32_t* index, const vbz_gpu_events* events, const vbz_gpu_event* records,
+                                           const vbz_gpu_event_moments* moments, uint32_t* n_levels, vbz_gpu_level* levels);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

@@ -308,6 +308,30 @@ class GpuMatchRow(ctypes.Structure):
     ]
 
 
+class GpuEventsQuery(ctypes.Structure):
+    """struct vbz_gpu_events_query of include/vbz_gpu.h (16 bytes)."""
+
+    _fields_ = [
+        ("query_len", ctypes.c_uint32),
+        ("min_n", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class GpuLevel(ctypes.Structure):
+    """struct vbz_gpu_level of include/vbz_gpu.h (32 bytes)."""
+
+    _fields_ = [
+        ("first_sample", ctypes.c_uint32),
+        ("end_sample", ctypes.c_uint32),
+        ("n_samples", ctypes.c_uint32),
+        ("n_entries", ctypes.c_uint32),
+        ("sum", ctypes.c_int64),
+        ("sumsq", ctypes.c_uint64),
+    ]
+
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -372,6 +396,8 @@ GPU_API = [
     "vbz_gpu_pod5_signal_locate_span_batch",
     "vbz_gpu_locate_path_batch",
     "vbz_gpu_query_valid_batch",
+    "vbz_gpu_events_query_batch",
+    "vbz_gpu_locate_levels_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -586,6 +612,12 @@ def load():
         L.vbz_gpu_locate_path_batch.argtypes = [ctypes.POINTER(GpuLocate) if a is ctypes.POINTER(GpuMatch) else a for a in L.vbz_gpu_match_path_batch.argtypes]
         L.vbz_gpu_query_valid_batch.restype = ctypes.c_int
         L.vbz_gpu_query_valid_batch.argtypes = [vp, u32, vp, gp, u32, vp]
+    if hasattr(L, "vbz_gpu_events_query_batch"):   # (likewise: the event records as a query, the path as a table per target level)
+        ep = ctypes.POINTER(GpuEvents)
+        L.vbz_gpu_events_query_batch.restype = ctypes.c_int
+        L.vbz_gpu_events_query_batch.argtypes = [vp, u32, vp, ep, vp, ctypes.POINTER(GpuEventsQuery), vp, vp, vp]
+        L.vbz_gpu_locate_levels_batch.restype = ctypes.c_int
+        L.vbz_gpu_locate_levels_batch.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp, ep, vp, vp, vp, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

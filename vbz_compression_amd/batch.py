@@ -1079,6 +1079,74 @@ class GpuCodec:
             self._exit(cur)
         return out
 
+    # -- event-space alignment (include/vbz_gpu.h: vbz_gpu_events_query_batch, vbz_gpu_locate_levels_batch) ------
+    def events_query(self, event_first, records, query_len, min_n=0, result=None, index=True, query=None, valid=None):
+        """The event records as the query arena of the alignment calls (include/vbz_gpu.h: vbz_gpu_events_query_batch): event_first int64
+        [n + 1] and records int32 [rows, 4] on the device (the event call's arena: mean, sd, n, 0) -> (query float32 [n, query_len] = the
+        means of each read's first query_len events with n >= min_n, +0 behind them, valid int32 [n] = their count, index int32 [n,
+        query_len] = their row numbers within the read; None with index=False) on the device.  result int32 [n] (optional): a read with
+        an error verdict gets valid 0.  query, valid and index may be given.  No synchronisation."""
+        n, N = int(event_first.numel()) - 1, int(query_len)
+        assert event_first.dtype == torch.int64 and event_first.is_contiguous() and event_first.device == self.device and n >= 0, (event_first.dtype, event_first.shape)
+        assert records.dtype == torch.int32 and records.is_contiguous() and records.device == self.device and records.dim() == 2 and int(records.shape[1]) == 4, (
+            records.dtype, records.shape)
+        assert result is None or (result.dtype == torch.int32 and result.is_contiguous() and result.device == self.device and int(result.numel()) == n)
+        if query is None:
+            query = torch.empty((n, N), dtype=torch.float32, device=self.device)
+        if valid is None:
+            valid = torch.empty(n, dtype=torch.int32, device=self.device)
+        if index is True:
+            index = torch.empty((n, N), dtype=torch.int32, device=self.device)
+        elif index is False:
+            index = None
+        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
+        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
+        assert index is None or (index.dtype == torch.int32 and index.is_contiguous() and index.device == self.device and tuple(index.shape) == (n, N))
+        ev = _lib.GpuEvents()
+        ev.event_rows = int(records.shape[0])
+        ev.event_first = event_first.data_ptr()
+        q = _lib.GpuEventsQuery(N, int(min_n), 0, 0)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_events_query_batch(self.ctx, n, result.data_ptr() if result is not None else None, ctypes.byref(ev),
+                                                       records.data_ptr() if int(records.shape[0]) else None, ctypes.byref(q), query.data_ptr(),
+                                                       valid.data_ptr(), index.data_ptr() if index is not None else None), "events_query_batch")
+        finally:
+            self._exit(cur)
+        return query, valid, index
+
+    def locate_levels(self, pairs, hit, rows, event_first, start, records, moments, max_width, index=None, n_levels=None, levels=None):
+        """The path of every listed pair as a table per target level (include/vbz_gpu.h: vbz_gpu_locate_levels_batch): pairs int32 [p, 4],
+        hit int32 [p, 4] and rows int32 [p, query_len, 2] as locate_path() took and left them; event_first int64 [n + 1], start int32
+        [rows], records int32 [rows, 4] and moments int64 [rows, 2] the event call's tables; index int32 [n, query_len] the table of
+        events_query() (None: entry k is the read's row k) -> (n_levels int32 [p], levels int32 [p, max_width, 8]: per target level of the
+        pair's stretch (first_sample, end_sample, n_samples, n_entries, sum as two words, sumsq as two words), zeros behind n_levels[p]
+        rows; levels.view(torch.int64)[..., 2:] are the exact sums) on the device.  max_width: a multiple of 8, 8 ... 65536, at least the
+        widest stretch.  A pair outside the rules gets n_levels 0.  No synchronisation."""
+        p, N, W = int(pairs.shape[0]), int(rows.shape[1]), int(max_width)
+        n = int(event_first.numel()) - 1
+        ev, keep = self._events(n, event_first, start)
+        R = int(ev.event_rows)
+        for name, t, shape in (("pairs", pairs, (p, 4)), ("hit", hit, (p, 4)), ("rows", rows, (p, N, 2)), ("records", records, (R, 4))):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and tuple(t.shape) == shape, (name, t.dtype, t.shape)
+        assert moments.dtype == torch.int64 and moments.is_contiguous() and moments.device == self.device and tuple(moments.shape) == (R, 2), (moments.dtype, moments.shape)
+        assert index is None or (index.dtype == torch.int32 and index.is_contiguous() and index.device == self.device and tuple(index.shape) == (n, N))
+        if n_levels is None:
+            n_levels = torch.empty(p, dtype=torch.int32, device=self.device)
+        if levels is None:
+            levels = torch.empty((p, W, 8), dtype=torch.int32, device=self.device)
+        assert n_levels.dtype == torch.int32 and n_levels.is_contiguous() and n_levels.device == self.device and int(n_levels.numel()) == p
+        assert levels.dtype == torch.int32 and levels.is_contiguous() and levels.device == self.device and tuple(levels.shape) == (p, W, 8), (levels.dtype, levels.shape)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_locate_levels_batch(self.ctx, p, n, N, W, pairs.data_ptr(), hit.data_ptr(), rows.data_ptr(),
+                                                        index.data_ptr() if index is not None else None, ctypes.byref(ev),
+                                                        records.data_ptr() if R else None, moments.data_ptr() if R else None, n_levels.data_ptr(),
+                                                        levels.data_ptr()), "locate_levels_batch")
+        finally:
+            self._exit(cur)
+        return n_levels, levels
+
     # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
     def _events(self, n, event_first, start):
         """(the C struct, the tables it points to) of n reads' events: event_first int64 [n + 1] on the device; start int32 [rows] on the

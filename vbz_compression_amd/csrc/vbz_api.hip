@@ -2746,6 +2746,94 @@ int vbz_gpu_query_valid_batch(vbz_gpu_ctx* c, uint32_t n_reads, const uint32_t* 
     return 0;
 }
 
+static_assert(sizeof(vbz_gpu_events_query) == 16 && offsetof(vbz_gpu_events_query, query_len) == 0 && offsetof(vbz_gpu_events_query, min_n) == 4 &&
+                  offsetof(vbz_gpu_events_query, flags) == 8 && offsetof(vbz_gpu_events_query, reserved) == 12,
+              "vbz_gpu_events_query is 16 bytes: query_len, min_n, flags, reserved");
+static_assert(sizeof(vbz_gpu_level) == 32 && offsetof(vbz_gpu_level, first_sample) == 0 && offsetof(vbz_gpu_level, end_sample) == 4 &&
+                  offsetof(vbz_gpu_level, n_samples) == 8 && offsetof(vbz_gpu_level, n_entries) == 12 && offsetof(vbz_gpu_level, sum) == 16 &&
+                  offsetof(vbz_gpu_level, sumsq) == 24,
+              "vbz_gpu_level is 32 bytes: first_sample, end_sample, n_samples, n_entries, sum, sumsq");
+
+static bool entries_len_ok(uint32_t n) { return n >= 8 && n <= 65536 && n % 8 == 0; }
+
+// what the two event-space calls share about the event tables: the struct's own rule, and the rows' extent
+static bool eventalign_events_ok(vbz_gpu_ctx* c, const vbz_gpu_events* ev)
+{
+    if (!ev) {
+        set_error(c, "events is NULL");
+        return false;
+    }
+    if (ev->flags != 0 || ev->reserved != 0) {
+        set_error(c, "events outside the rules (flags %u, reserved %u)", ev->flags, ev->reserved);
+        return false;
+    }
+    if (ev->event_rows > EXTENT_MAX / sizeof(vbz_gpu_event)) {
+        set_error(c, "declared event arena is not plausible (%llu rows of 16 bytes)", (unsigned long long)ev->event_rows);
+        return false;
+    }
+    return true;
+}
+
+int vbz_gpu_events_query_batch(vbz_gpu_ctx* c, uint32_t n_reads, const uint32_t* result, const vbz_gpu_events* ev, const vbz_gpu_event* records,
+                               const vbz_gpu_events_query* q, float* query, uint32_t* valid, uint32_t* index)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!eventalign_events_ok(c, ev)) return -2;
+    if (!q || !entries_len_ok(q->query_len) || q->flags != 0 || q->reserved != 0) {
+        set_error(c, "events query is NULL or outside the rules (query_len %u, flags %u, reserved %u)", q ? q->query_len : 0u, q ? q->flags : 0u,
+                  q ? q->reserved : 0u);
+        return -2;
+    }
+    if (n_reads != 0 && (!ev->event_first || (!records && ev->event_rows != 0) || !query || !valid)) {
+        set_error(c, "event_first, the event arena, the query arena or valid is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)query | (uintptr_t)records | (uintptr_t)index) & 15u) != 0) {
+        set_error(c, "the query arena, the event arena or the index arena is not 16-byte aligned");
+        return -2;
+    }
+    if ((uint64_t)n_reads * q->query_len > EXTENT_MAX / sizeof(float)) {
+        set_error(c, "declared query arena is not plausible (%u reads of %u entries)", n_reads, q->query_len);
+        return -2;
+    }
+    Timed t(c, "events_query");
+    HIPCHK(c, launch_events_query(n_reads, result, ev->event_first, ev->event_rows, records, q->min_n, q->query_len, query, valid, index, c->stream),
+           "events query launch");
+    return 0;
+}
+
+int vbz_gpu_locate_levels_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads, uint32_t query_len, uint32_t max_width, const vbz_gpu_match_pair* pairs,
+                                const vbz_gpu_match_span* hit, const vbz_gpu_match_row* rows, const uint32_t* index, const vbz_gpu_events* ev,
+                                const vbz_gpu_event* records, const vbz_gpu_event_moments* moments, uint32_t* n_levels, vbz_gpu_level* levels)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!eventalign_events_ok(c, ev)) return -2;
+    if (!entries_len_ok(query_len) || !entries_len_ok(max_width)) {
+        set_error(c, "locate levels outside the rules (query_len %u, max_width %u: multiples of 8, 8 ... 65536)", query_len, max_width);
+        return -2;
+    }
+    if (n_pairs != 0 && (!pairs || !hit || !rows || !ev->event_first || ((!ev->start || !records || !moments) && ev->event_rows != 0) || !n_levels || !levels)) {
+        set_error(c, "the pair table, the hit table, the row arena, event_first, start, the event arena, the moments, n_levels or the level arena is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)pairs | (uintptr_t)hit | (uintptr_t)rows | (uintptr_t)records | (uintptr_t)moments | (uintptr_t)levels) & 15u) != 0) {
+        set_error(c, "the pair table, the hit table, the row arena, the event arena, the moments or the level arena is not 16-byte aligned");
+        return -2;
+    }
+    if ((uint64_t)n_pairs * query_len > EXTENT_MAX / sizeof(vbz_gpu_match_row) || (uint64_t)n_pairs * max_width > EXTENT_MAX / sizeof(vbz_gpu_level) ||
+        (uint64_t)n_reads * query_len > EXTENT_MAX / sizeof(uint32_t)) {
+        set_error(c, "declared level arenas are not plausible (%u pairs, %u reads, %u entries, %u levels)", n_pairs, n_reads, query_len, max_width);
+        return -2;
+    }
+    Timed t(c, "locate_levels");
+    HIPCHK(c, launch_locate_levels(n_pairs, n_reads, query_len, max_width, pairs, hit, rows, index, ev->event_first, ev->event_rows, ev->start, records,
+                                   moments, n_levels, levels, c->stream),
+           "locate levels launch");
+    return 0;
+}
+
 int vbz_gpu_svb_compress_batch(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, int integer_size, int zigzag, int version)
 {
     if (!c || !bt) return -1;

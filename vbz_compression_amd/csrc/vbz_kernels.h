@@ -801,6 +801,17 @@ hipError_t launch_locate(uint32_t n_reads, const float* query, const uint32_t* v
 // coordinates, found by a bounded walk back from (cost, end) in the same wavefront.
 hipError_t launch_locate_span(uint32_t n_reads, const float* query, const uint32_t* valid, uint32_t N, float quant, const int8_t* target,
                               const uint32_t* target_len, uint32_t G, uint32_t target_stride, void* out, hipStream_t s);
+// Event-space alignment (eventalign.hip; the rules: include/vbz_gpu.h, vbz_gpu_events_query and vbz_gpu_level).  launch_events_query: row i
+// of query / index ([n_reads, N]) = the means / the row numbers of read i's first N events with n >= min_n, zeros behind them, valid[i]
+// their count; result (nullable) gates a read as launch_match_valid does, event_first is untrusted, index is nullable.
+hipError_t launch_events_query(uint32_t n_reads, const uint32_t* result, const uint64_t* event_first, uint64_t event_rows, const void* records, uint32_t min_n,
+                               uint32_t N, float* query, uint32_t* valid, uint32_t* index, hipStream_t s);
+// launch_locate_levels: the path rows of pair p ([n_pairs, N] of {begin, end}, n = hit[p].w of them) inverted into one 32-byte record per
+// target level of [hit[p].z, hit[p].y) in levels ([n_pairs, max_width]), zeros behind them, n_levels[p] their count; every table is
+// untrusted, index is nullable.
+hipError_t launch_locate_levels(uint32_t n_pairs, uint32_t n_reads, uint32_t N, uint32_t max_width, const void* pairs, const void* hit, const void* rows,
+                                const uint32_t* index, const uint64_t* event_first, uint64_t event_rows, const uint32_t* start, const void* records,
+                                const void* moments, uint32_t* n_levels, void* levels, hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
