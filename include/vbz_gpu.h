@@ -1171,6 +1171,96 @@ VBZ_EXPORT int vbz_gpu_locate_levels_batch(vbz_gpu_ctx* ctx, uint32_t n_pairs, u
                                            const uint32_t* index, const vbz_gpu_events* events, const vbz_gpu_event* records,
                                            const vbz_gpu_event_moments* moments, uint32_t* n_levels, vbz_gpu_level* levels);
 
+/* Pore model on the device: the two ends of the event-space chain above.  In front of it, vbz_gpu_locate.target is an int8 matrix of
+ * expected levels that a caller had to make on the host, k-mer by k-mer, with a quantisation that matches the library's bit for bit;
+ * behind it, the exact moments per level that vbz_gpu_locate_levels_batch leaves exist so that each read's shift and scale can be
+ * re-estimated against the model.  vbz_gpu_squiggle_batch writes the target arena from bases and a k-mer table; vbz_gpu_levels_fit_batch
+ * turns a vbz_gpu_level arena into per-read {offset, scale} tables in the layout vbz_gpu_signal_format.offset / .scale take, so that a
+ * second round of the chain runs under the refined constants with nothing crossing to the host.  No other call changes.
+ * vbz_gpu_squiggle_batch: target levels from bases.  The rule (tests/squiggle_ref.py).  Rows = S = n_seqs, or 2 S with BOTH: row 2s is
+ * sequence s as given, row 2s + 1 its reverse complement.  Base codes are A/a = 0, C/c = 1, G/g = 2, T/t/U/u = 3; every other byte is
+ * invalid.  Sequence s has n = seq_len[s] bases b_0 ... b_(n-1), the first n bytes of row s of seq; n > seq_stride gives the row or rows
+ * of s length 0, and no address is formed from it.  The reverse complement strand is b'_i = 3 - b_(n-1-i); invalid stays invalid.
+ * L = n - k + 1 when k <= n, else 0; L > target_stride also gives 0.  The k-mer at j has index sum_(i<k) b_(j+i) 4^(k-1-i), the first
+ * base most significant, and its level is m = model[index].  Output position j < L holds the k-mer at j, or at L - 1 - j with REVERSED;
+ * with BOTH as well the order is strand first, then reversed.  The quantisation is exactly the query's of the match calls: v = m * quant
+ * (one float32 multiply), 0 when v is NaN, otherwise clamp(rint(v), -127, 127), rint to nearest even, +-inf giving +-127.  A k-mer that
+ * holds an invalid base gives int8 0 and float +0, and is counted in masked[row].  target[row][0 ... target_stride) is written whole, by
+ * 16-byte stores, with zeros at and behind L; level (nullable: [rows][target_stride] float32) holds the 32 bits of m, +0 where masked or
+ * behind L; target_len[row] = L.  EVERY entry of all four tables is written by every call that launches; nothing else is.
+ * Returns 0 when queued, -1 for a NULL context or a launch failure, -2, with nothing launched and nothing written, for a NULL struct;
+ * k, n_seqs, either stride or quant outside its rule (NaN and infinities included); unknown flag bits; a NULL seq, seq_len, model,
+ * target, target_len or masked; seq, target or level not 16-byte aligned; rows * target_stride * 4 or S * seq_stride beyond 2^46 bytes.
+ * vbz_gpu_levels_fit_batch: new constants per pair, from exact integers.  The rule.  pairs, hit, n_levels and levels ([n_pairs,
+ * max_width]) are what vbz_gpu_locate_levels_batch took and wrote, locate is the chain's own.  Pair p has hit {cost, end, start, n} and
+ * W = n_levels[p]; row t < W of its levels is target level start + t of row g = pairs[p].ref, and g_t is the int8 there.  The level's
+ * value is m_t = float64(sum_t) / float64(n_samples_t); the level is left out when n_samples_t < max(min_samples, 1), when n_entries_t >
+ * max_entries and max_entries != 0, and when |m_t| <= 32768 does not hold.  q_t = int64(rint(m_t * 64)), rint to nearest even.  Over the
+ * K kept levels, in exact integers: Sg = sum g_t, Sgg = sum g_t^2, Sq = sum q_t, Sgq = sum g_t q_t; num = K Sgq - Sg Sq, den = K Sgg -
+ * Sg^2.  With K <= 2^16, |g| <= 2^7 and |q| <= 2^21, |num| < 2^62 and den < 2^47: everything is int64, nothing wraps, and integer sums do
+ * not depend on their order, so the answer is reproducible bit for bit.  sums[p] = {Sg, Sgg, Sq, Sgq} when given.  In float64, each
+ * operation rounded to nearest even and none fused: A = float64(num) / float64(den), B = (float64(Sq) - A * float64(Sg)) / float64(K),
+ * a = A / 64, b = B / 64.  A read sample x on model level g is x ~ a g + b, and the constants under which ((float)x + o) * s * quant ~ g
+ * are scale = float32(1.0 / (a * float64(quant))) and offset = float32(-b).  ok = 1 when the pair is valid, K >= 2, den > 0, num > 0 and
+ * both float32 results are finite with scale > 0; otherwise ok = 0 and offset and scale are the prior's: offset = -shift, scale =
+ * float32(1 / float64(scale)) of prior_shift_scale[read], or 0 and 1 when the prior is NULL or read >= n_reads.  used = K, or 0 for an
+ * invalid pair.  offset[p] / scale[p] repeat the record's two floats: vbz_gpu_match_best_batch writes pair i for read i, so in the chain
+ * they are per-read tables.
+ * Every table is untrusted.  A pair is invalid, and no address is formed from an unchecked value, when read >= n_reads; ref >= G; W == 0
+ * or W > max_width; end - start != W; L_g == 0 or L_g > target_stride; end > L_g.  EVERY entry of out, offset, scale and sums, when given,
+ * is written by every call that launches; nothing else is.
+ * Returns 0 / -1 as above; -2 for everything vbz_gpu_locate_batch refuses about locate; a NULL fit, or flags != 0; max_width outside its
+ * rule; a NULL pairs, hit, n_levels, levels, out, offset or scale while the call has pairs; pairs, hit, levels or out not 16-byte aligned;
+ * n_pairs * max_width * 32 beyond 2^46 bytes.  n_pairs == 0 with good arguments returns 0 and launches nothing.
+ * How (csrc/squiggle.hip).  No LDS, no barrier, no atomics, no scratch memory in either.  The squiggle: one lane makes 16
+ * consecutive levels, so one 16-byte store of int8 and four of float32; it loads the seven aligned dwords that cover its 16 + k - 1
+ * bases, shifts them into place, rolls the index (shift by 2, mask, add) beside a bit mask of the last k bases' validity, and gathers the
+ * model from global memory; the reverse strand reads the same bytes from the other end.  masked is exact with no zeroing launch: a
+ * wavefront adds its lanes' counts by shuffles and stores one word of the context's scratch, and a second tiny launch, one wavefront a
+ * row, adds the words up.  The fit: one wavefront a pair, four to a workgroup, 64 levels a turn; a lane loads its 32-byte record by two
+ * 16-byte loads and its int8 level from the aligned dword that holds it; the five sums stay in registers, are added across the
+ * wavefront once, and one lane does the float64 arithmetic and the stores.
+ * Measured on one MI355X (tools/time_refit.py, profiles/refit_time.json; the parent of the commit that adds these calls is 43d0dce and can
+ * run neither, so the comparison is the unfused torch route in the same run; median of 20, the legs alternating in one process, every
+ * table checked bit for bit): squiggle of 4 rows (S = 2, BOTH) with levels, 30 000 bases 0.0225 ms, 1 048 576 bases 0.034 ms (k = 6) and
+ * 0.045 ms (k = 9), against 1.0 - 1.3 ms for torch: two launches, about 0.022 ms whatever they do, so 0.6 - 0.75 TB/s at the large shape
+ * and not a copy's rate.  levels_fit over 8 192 pairs, max_width 2 256, 15.2 M levels: 0.158 ms against 2.30 ms for torch, 3.2 TB/s
+ * over the records it reads, beside locate_levels at 0.459 ms and the span leg at 62.95 ms. */
+#define VBZ_GPU_SQUIGGLE_BOTH 1u     /* row 2s: sequence s as given; row 2s + 1: its reverse complement */
+#define VBZ_GPU_SQUIGGLE_REVERSED 2u /* levels in 3'->5' order (direct RNA) */
+typedef struct vbz_gpu_squiggle
+{
+    uint32_t k;              /* 1 ... 9 */
+    uint32_t n_seqs;         /* S: 1 ... 4096; 1 ... 2048 with BOTH (rows <= 4096 = the locate calls' G) */
+    uint32_t seq_stride;     /* bytes per row of seq: a multiple of 16, 16 ... 2^30 */
+    uint32_t target_stride;  /* entries per output row: a multiple of 16, 16 ... 2^30 */
+    uint32_t flags;          /* BOTH | REVERSED; other bits must be 0 */
+    float quant;             /* finite, > 0: the locate calls' quant */
+    const uint8_t* seq;      /* device, 16-byte aligned, S x seq_stride ASCII bytes */
+    const uint32_t* seq_len; /* device, S words, untrusted */
+    const float* model;      /* device, 4^k float32: the expected level of each k-mer in the query's units */
+} vbz_gpu_squiggle;          /* 48 bytes */
+typedef struct vbz_gpu_levels_fit
+{
+    uint32_t max_width;   /* of the levels arena: a multiple of 8, 8 ... 65536 */
+    uint32_t min_samples; /* levels with n_samples < max(min_samples, 1) are left out */
+    uint32_t max_entries; /* levels with n_entries > max_entries are left out (stalls); 0: no cap */
+    uint32_t flags;       /* must be 0 */
+} vbz_gpu_levels_fit;     /* 16 bytes */
+typedef struct vbz_gpu_level_fit
+{
+    float offset;  /* what format->offset takes: -b, or the prior's -shift */
+    float scale;   /* what format->scale takes: 1 / (a quant), or the prior's 1 / scale */
+    uint32_t used; /* K, the levels kept; 0 for an invalid pair */
+    uint32_t ok;   /* 1: a good fit; 0: offset and scale are the prior's */
+} vbz_gpu_level_fit; /* 16 bytes */
+VBZ_EXPORT int vbz_gpu_squiggle_batch(vbz_gpu_ctx* ctx, const vbz_gpu_squiggle* squiggle, int8_t* target, uint32_t* target_len, uint32_t* masked,
+                                      float* level);
+VBZ_EXPORT int vbz_gpu_levels_fit_batch(vbz_gpu_ctx* ctx, uint32_t n_pairs, uint32_t n_reads, const vbz_gpu_locate* locate,
+                                        const vbz_gpu_match_pair* pairs, const vbz_gpu_match_span* hit, const uint32_t* n_levels,
+                                        const vbz_gpu_level* levels, const vbz_gpu_levels_fit* fit, const float* prior_shift_scale,
+                                        vbz_gpu_level_fit* out, float* offset, float* scale, int64_t* sums);
+
 /* Stage-level entry points (the two halves of the path, used by tests and stage benchmarks).
  *   svb:  reference vbz_delta_zig_zag_streamvbyte_{compress,decompress}_v{0,1}
  *         (vbz/v0/vbz_streamvbyte.cpp:20-108, vbz/v1/vbz_streamvbyte.cpp:22-113)

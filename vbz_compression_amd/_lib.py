@@ -332,6 +332,46 @@ class GpuLevel(ctypes.Structure):
     ]
 
 
+class GpuSquiggle(ctypes.Structure):
+    """struct vbz_gpu_squiggle of include/vbz_gpu.h (48 bytes)."""
+
+    _fields_ = [
+        ("k", ctypes.c_uint32),
+        ("n_seqs", ctypes.c_uint32),
+        ("seq_stride", ctypes.c_uint32),
+        ("target_stride", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("quant", ctypes.c_float),
+        ("seq", ctypes.c_void_p),
+        ("seq_len", ctypes.c_void_p),
+        ("model", ctypes.c_void_p),
+    ]
+
+
+class GpuLevelsFit(ctypes.Structure):
+    """struct vbz_gpu_levels_fit of include/vbz_gpu.h (16 bytes)."""
+
+    _fields_ = [
+        ("max_width", ctypes.c_uint32),
+        ("min_samples", ctypes.c_uint32),
+        ("max_entries", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+    ]
+
+
+class GpuLevelFit(ctypes.Structure):
+    """struct vbz_gpu_level_fit of include/vbz_gpu.h (16 bytes)."""
+
+    _fields_ = [
+        ("offset", ctypes.c_float),
+        ("scale", ctypes.c_float),
+        ("used", ctypes.c_uint32),
+        ("ok", ctypes.c_uint32),
+    ]
+
+
+SQUIGGLE_BOTH, SQUIGGLE_REVERSED = 1, 2
+
 C_API = [
     "vbz_is_error",
     "vbz_error_string",
@@ -398,6 +438,8 @@ GPU_API = [
     "vbz_gpu_query_valid_batch",
     "vbz_gpu_events_query_batch",
     "vbz_gpu_locate_levels_batch",
+    "vbz_gpu_squiggle_batch",
+    "vbz_gpu_levels_fit_batch",
     "vbz_gpu_svb_compress_batch",
     "vbz_gpu_svb_decompress_batch",
     "vbz_gpu_zstd_compress_batch",
@@ -618,6 +660,11 @@ def load():
         L.vbz_gpu_events_query_batch.argtypes = [vp, u32, vp, ep, vp, ctypes.POINTER(GpuEventsQuery), vp, vp, vp]
         L.vbz_gpu_locate_levels_batch.restype = ctypes.c_int
         L.vbz_gpu_locate_levels_batch.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp, ep, vp, vp, vp, vp]
+    if hasattr(L, "vbz_gpu_squiggle_batch"):   # (likewise: target levels from bases, new constants along the path)
+        L.vbz_gpu_squiggle_batch.restype = ctypes.c_int
+        L.vbz_gpu_squiggle_batch.argtypes = [vp, ctypes.POINTER(GpuSquiggle), vp, vp, vp, vp]
+        L.vbz_gpu_levels_fit_batch.restype = ctypes.c_int
+        L.vbz_gpu_levels_fit_batch.argtypes = [vp, u32, u32, ctypes.POINTER(GpuLocate), vp, vp, vp, vp, ctypes.POINTER(GpuLevelsFit), vp, vp, vp, vp, vp]
     for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
         f = getattr(L, name)
         f.restype = ctypes.c_int

@@ -1147,6 +1147,83 @@ class GpuCodec:
             self._exit(cur)
         return n_levels, levels
 
+    # -- pore model: target levels from bases, new constants along the path (include/vbz_gpu.h: vbz_gpu_squiggle_batch, vbz_gpu_levels_fit_batch)
+    def squiggle(self, seq, seq_len, model, k, target_stride, quant=32.0, both=False, reversed=False, level=False, target=None, target_len=None,
+                 masked=None):
+        """Target levels from bases (include/vbz_gpu.h: vbz_gpu_squiggle_batch): seq uint8 [S, seq_stride] ASCII, seq_len int32 [S] and model
+        float32 [4 ** k] on the device -> (target int8 [rows, target_stride], target_len int32 [rows], masked int32 [rows], level float32
+        [rows, target_stride] or None) on the device, rows = S, or 2 S with both (row 2s the sequence, row 2s + 1 its reverse complement);
+        reversed: levels in 3'->5' order.  target and target_len are what the locate calls take.  level: True, False or a tensor; target,
+        target_len and masked may be given.  No synchronisation."""
+        S, k, T = int(seq.shape[0]), int(k), int(target_stride)
+        rows = 2 * S if both else S
+        assert seq.dtype == torch.uint8 and seq.is_contiguous() and seq.device == self.device and seq.dim() == 2, (seq.dtype, seq.shape)
+        assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.device == self.device and int(seq_len.numel()) == S, (seq_len.dtype, seq_len.shape)
+        assert model.dtype == torch.float32 and model.is_contiguous() and model.device == self.device and 1 <= k <= 9 and int(model.numel()) == 4 ** k, (
+            model.dtype, model.shape, k)
+        if target is None:
+            target = torch.empty((rows, T), dtype=torch.int8, device=self.device)
+        if target_len is None:
+            target_len = torch.empty(rows, dtype=torch.int32, device=self.device)
+        if masked is None:
+            masked = torch.empty(rows, dtype=torch.int32, device=self.device)
+        if level is True:
+            level = torch.empty((rows, T), dtype=torch.float32, device=self.device)
+        elif level is False:
+            level = None
+        assert target.dtype == torch.int8 and target.is_contiguous() and target.device == self.device and tuple(target.shape) == (rows, T), (target.dtype, target.shape)
+        for name, t in (("target_len", target_len), ("masked", masked)):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and int(t.numel()) == rows, (name, t.dtype, t.shape)
+        assert level is None or (level.dtype == torch.float32 and level.is_contiguous() and level.device == self.device and tuple(level.shape) == (rows, T))
+        sq = _lib.GpuSquiggle(k, S, int(seq.shape[1]), T, (_lib.SQUIGGLE_BOTH if both else 0) | (_lib.SQUIGGLE_REVERSED if reversed else 0), float(quant),
+                              seq.data_ptr(), seq_len.data_ptr(), model.data_ptr())
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_squiggle_batch(self.ctx, ctypes.byref(sq), target.data_ptr(), target_len.data_ptr(), masked.data_ptr(),
+                                                   level.data_ptr() if level is not None else None), "squiggle_batch")
+        finally:
+            self._exit(cur)
+        return target, target_len, masked, level
+
+    def levels_fit(self, pairs, hit, n_levels, levels, target, target_len, n_reads, locate=None, min_samples=0, max_entries=0, prior=None, sums=False,
+                   out=None, offset=None, scale=None):
+        """New constants per pair from the table per level (include/vbz_gpu.h: vbz_gpu_levels_fit_batch): pairs int32 [p, 4], hit int32
+        [p, 4], n_levels int32 [p] and levels int32 [p, max_width, 8] as locate_levels() took and left them; target int8 [G, target_stride]
+        and target_len int32 [G] the chain's targets; prior float32 [n_reads, 2] = (shift, scale) as the normalising calls write it, or
+        None -> (out int32 [p, 4] = (offset and scale as float32 bits, used, ok), offset float32 [p], scale float32 [p], sums int64 [p, 4] =
+        (Sg, Sgg, Sq, Sgq) or None) on the device.  offset and scale are what signal_events() and the other typed decodes take as
+        per-read tables when pairs came from match_best().  sums: True, False or a tensor; out, offset and scale may be given.  No
+        synchronisation."""
+        p, W, n = int(pairs.shape[0]), int(levels.shape[1]), int(n_reads)
+        loc = (locate or Locate()).c_struct(target, target_len)
+        assert target.device == self.device
+        for name, t, shape in (("pairs", pairs, (p, 4)), ("hit", hit, (p, 4)), ("n_levels", n_levels, (p,)), ("levels", levels, (p, W, 8))):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and tuple(t.shape) == shape, (name, t.dtype, t.shape)
+        assert prior is None or (prior.dtype == torch.float32 and prior.is_contiguous() and prior.device == self.device and tuple(prior.shape) == (n, 2))
+        if out is None:
+            out = torch.empty((p, 4), dtype=torch.int32, device=self.device)
+        if offset is None:
+            offset = torch.empty(p, dtype=torch.float32, device=self.device)
+        if scale is None:
+            scale = torch.empty(p, dtype=torch.float32, device=self.device)
+        if sums is True:
+            sums = torch.empty((p, 4), dtype=torch.int64, device=self.device)
+        elif sums is False:
+            sums = None
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (p, 4), (out.dtype, out.shape)
+        for name, t in (("offset", offset), ("scale", scale)):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) == p, (name, t.dtype, t.shape)
+        assert sums is None or (sums.dtype == torch.int64 and sums.is_contiguous() and sums.device == self.device and tuple(sums.shape) == (p, 4))
+        fit = _lib.GpuLevelsFit(W, int(min_samples), int(max_entries), 0)
+        cur = self._enter()
+        try:
+            self._rc(self.L.vbz_gpu_levels_fit_batch(self.ctx, p, n, ctypes.byref(loc), pairs.data_ptr(), hit.data_ptr(), n_levels.data_ptr(),
+                                                     levels.data_ptr(), ctypes.byref(fit), prior.data_ptr() if prior is not None else None, out.data_ptr(),
+                                                     offset.data_ptr(), scale.data_ptr(), sums.data_ptr() if sums is not None else None), "levels_fit_batch")
+        finally:
+            self._exit(cur)
+        return out, offset, scale, sums
+
     # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
     def _events(self, n, event_first, start):
         """(the C struct, the tables it points to) of n reads' events: event_first int64 [n + 1] on the device; start int32 [rows] on the

@@ -232,6 +232,7 @@ struct vbz_gpu_ctx
     DevBuf pod5meta;           // a call over POD5 reads: the rows' and the reads' tables, the reads' constants (Pod5Tables)
     DevBuf matchmeta;          // signal match: the fused calls' own window tables, valid[] and, for a caller that takes none, read_result (MatchTables)
     DevBuf matchpath;          // the path call: one group's direction bits and costs (MatchPathScratch)
+    DevBuf squigpart;          // the squiggle call: the masked counts of one call's wavefronts (squiggle_part_words)
     bool profiling = false;    // (not a setting: outside Knobs; the upper half of a split call gets the call's)
     PinnedBuf pinned;          // the single-buffer API's pinned area (run_one)
     uint32_t one_seq = 0;      // the single-buffer API's hand-back flag: a number per call (run_one)
@@ -2831,6 +2832,90 @@ int vbz_gpu_locate_levels_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_rea
     HIPCHK(c, launch_locate_levels(n_pairs, n_reads, query_len, max_width, pairs, hit, rows, index, ev->event_first, ev->event_rows, ev->start, records,
                                    moments, n_levels, levels, c->stream),
            "locate levels launch");
+    return 0;
+}
+
+static_assert(sizeof(vbz_gpu_squiggle) == 48 && offsetof(vbz_gpu_squiggle, k) == 0 && offsetof(vbz_gpu_squiggle, n_seqs) == 4 &&
+                  offsetof(vbz_gpu_squiggle, seq_stride) == 8 && offsetof(vbz_gpu_squiggle, target_stride) == 12 && offsetof(vbz_gpu_squiggle, flags) == 16 &&
+                  offsetof(vbz_gpu_squiggle, quant) == 20 && offsetof(vbz_gpu_squiggle, seq) == 24 && offsetof(vbz_gpu_squiggle, seq_len) == 32 &&
+                  offsetof(vbz_gpu_squiggle, model) == 40,
+              "vbz_gpu_squiggle is 48 bytes: k, n_seqs, seq_stride, target_stride, flags, quant, seq, seq_len, model");
+static_assert(sizeof(vbz_gpu_levels_fit) == 16 && offsetof(vbz_gpu_levels_fit, max_width) == 0 && offsetof(vbz_gpu_levels_fit, min_samples) == 4 &&
+                  offsetof(vbz_gpu_levels_fit, max_entries) == 8 && offsetof(vbz_gpu_levels_fit, flags) == 12,
+              "vbz_gpu_levels_fit is 16 bytes: max_width, min_samples, max_entries, flags");
+static_assert(sizeof(vbz_gpu_level_fit) == 16 && offsetof(vbz_gpu_level_fit, offset) == 0 && offsetof(vbz_gpu_level_fit, scale) == 4 &&
+                  offsetof(vbz_gpu_level_fit, used) == 8 && offsetof(vbz_gpu_level_fit, ok) == 12,
+              "vbz_gpu_level_fit is 16 bytes: offset, scale, used, ok");
+
+int vbz_gpu_squiggle_batch(vbz_gpu_ctx* c, const vbz_gpu_squiggle* sq, int8_t* target, uint32_t* target_len, uint32_t* masked, float* level)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!sq) {
+        set_error(c, "squiggle is NULL");
+        return -2;
+    }
+    const bool both = (sq->flags & VBZ_GPU_SQUIGGLE_BOTH) != 0;
+    const auto stride_ok = [](uint32_t s) { return s >= 16 && s <= (1u << 30) && s % 16 == 0; };
+    if (sq->k < 1 || sq->k > 9 || sq->n_seqs < 1 || sq->n_seqs > (both ? 2048u : 4096u) || !stride_ok(sq->seq_stride) || !stride_ok(sq->target_stride) ||
+        (sq->flags & ~(VBZ_GPU_SQUIGGLE_BOTH | VBZ_GPU_SQUIGGLE_REVERSED)) != 0 || !(sq->quant > 0.0f) || !std::isfinite(sq->quant)) {
+        set_error(c, "squiggle outside the rules (k %u, n_seqs %u, seq_stride %u, target_stride %u, flags %u, quant %g)", sq->k, sq->n_seqs, sq->seq_stride,
+                  sq->target_stride, sq->flags, (double)sq->quant);
+        return -2;
+    }
+    if (!sq->seq || !sq->seq_len || !sq->model || !target || !target_len || !masked) {
+        set_error(c, "seq, seq_len, the model, the target arena, target_len or masked is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)sq->seq | (uintptr_t)target | (uintptr_t)level) & 15u) != 0) {
+        set_error(c, "seq, the target arena or the level arena is not 16-byte aligned");
+        return -2;
+    }
+    const uint32_t rows = both ? 2u * sq->n_seqs : sq->n_seqs;
+    if ((uint64_t)rows * sq->target_stride > EXTENT_MAX / sizeof(float) || (uint64_t)sq->n_seqs * sq->seq_stride > EXTENT_MAX) {
+        set_error(c, "declared squiggle arenas are not plausible (%u sequences of %u bytes, %u rows of %u levels)", sq->n_seqs, sq->seq_stride, rows,
+                  sq->target_stride);
+        return -2;
+    }
+    uint32_t* const part = ensure_array<uint32_t>(c, c->squigpart, squiggle_part_words(rows, sq->target_stride));
+    if (!part) return -1;
+    Timed t(c, "squiggle");
+    HIPCHK(c, launch_squiggle(sq->k, rows, sq->seq_stride, sq->target_stride, sq->flags, sq->quant, sq->seq, sq->seq_len, sq->model, target, target_len, masked,
+                              level, part, c->stream),
+           "squiggle launch");
+    return 0;
+}
+
+int vbz_gpu_levels_fit_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads, const vbz_gpu_locate* locate, const vbz_gpu_match_pair* pairs,
+                             const vbz_gpu_match_span* hit, const uint32_t* n_levels, const vbz_gpu_level* levels, const vbz_gpu_levels_fit* fit,
+                             const float* prior_shift_scale, vbz_gpu_level_fit* out, float* offset, float* scale, int64_t* sums)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    // (the locate's own rules, the targets' extent and alignment: what vbz_gpu_locate_batch refuses about it; the tables a call with pairs needs: below)
+    const AlignView m = align_view(locate);
+    if (!align_ok(c, LOCATE, m, nullptr, nullptr, sizeof(vbz_gpu_match_span), 0)) return -2;
+    if (!fit || fit->flags != 0 || !entries_len_ok(fit->max_width)) {
+        set_error(c, "levels fit is NULL or outside the rules (max_width %u: a multiple of 8, 8 ... 65536; flags %u)", fit ? fit->max_width : 0u,
+                  fit ? fit->flags : 0u);
+        return -2;
+    }
+    if (n_pairs != 0 && (!m.levels || !m.levels_len || !pairs || !hit || !n_levels || !levels || !out || !offset || !scale)) {
+        set_error(c, "target, target_len, the pair table, the hit table, n_levels, the level arena, the fit table, offset or scale is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)pairs | (uintptr_t)hit | (uintptr_t)levels | (uintptr_t)out) & 15u) != 0) {
+        set_error(c, "the pair table, the hit table, the level arena or the fit table is not 16-byte aligned");
+        return -2;
+    }
+    if ((uint64_t)n_pairs * fit->max_width > EXTENT_MAX / sizeof(vbz_gpu_level)) {
+        set_error(c, "declared level arena is not plausible (%u pairs of %u levels)", n_pairs, fit->max_width);
+        return -2;
+    }
+    Timed t(c, "levels_fit");
+    HIPCHK(c, launch_levels_fit(n_pairs, n_reads, m.n_levels, m.levels_stride, m.quant, m.levels, m.levels_len, pairs, hit, n_levels, levels, fit->max_width,
+                                fit->min_samples, fit->max_entries, prior_shift_scale, out, offset, scale, sums, c->stream),
+           "levels fit launch");
     return 0;
 }
 

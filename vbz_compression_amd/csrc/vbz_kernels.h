@@ -812,6 +812,22 @@ hipError_t launch_events_query(uint32_t n_reads, const uint32_t* result, const u
 hipError_t launch_locate_levels(uint32_t n_pairs, uint32_t n_reads, uint32_t N, uint32_t max_width, const void* pairs, const void* hit, const void* rows,
                                 const uint32_t* index, const uint64_t* event_first, uint64_t event_rows, const uint32_t* start, const void* records,
                                 const void* moments, uint32_t* n_levels, void* levels, hipStream_t s);
+// The two ends of the event-space chain (squiggle.hip; the rules: include/vbz_gpu.h, vbz_gpu_squiggle and vbz_gpu_levels_fit).
+// launch_squiggle: row r of target / level ([rows, target_stride]) = the quantised / the float32 model levels of the k-mers of sequence r
+// (flags: VBZ_GPU_SQUIGGLE_*), zeros behind target_len[r]; masked[r] the k-mers that hold an invalid base, added up by a second launch
+// over part, squiggle_part_words(rows, target_stride) words of scratch that the first launch writes whole.  seq_len is untrusted, level
+// is nullable.
+uint32_t squiggle_part_words(uint32_t rows, uint32_t target_stride);
+hipError_t launch_squiggle(uint32_t k, uint32_t rows, uint32_t seq_stride, uint32_t target_stride, uint32_t flags, float quant, const uint8_t* seq,
+                           const uint32_t* seq_len, const float* model, int8_t* target, uint32_t* target_len, uint32_t* masked, float* level, uint32_t* part,
+                           hipStream_t s);
+// launch_levels_fit: pair p's {offset, scale, used, ok} in out and its two floats again in offset / scale, from the least-squares line
+// through (target level, mean of the level's record) over the rows of levels ([n_pairs, max_width]) that min_samples and max_entries keep;
+// sums ([n_pairs, 4] int64: Sg, Sgg, Sq, Sgq) and prior ([n_reads] {shift, scale}) are nullable; every table is untrusted.
+hipError_t launch_levels_fit(uint32_t n_pairs, uint32_t n_reads, uint32_t G, uint32_t target_stride, float quant, const int8_t* target,
+                             const uint32_t* target_len, const void* pairs, const void* hit, const uint32_t* n_levels, const void* levels, uint32_t max_width,
+                             uint32_t min_samples, uint32_t max_entries, const float* prior, void* out, float* offset, float* scale, int64_t* sums,
+                             hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
