@@ -459,6 +459,97 @@ GPU_API = [
     "vbz_gpu_version",
 ]
 
+def _prototypes():
+    """name -> (restype, argtypes) of every entry of C_API + GPU_API, as include/vbz.h and include/vbz_gpu.h declare them.  A new entry is
+    one row here; a family is derived from its base row below the literal rows."""
+    c_int, vp, u32, u64, P = ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER
+    op, bp, fp, cp, np_, rp, gp = P(CompressionOptions), P(GpuBatch), P(GpuSignalFormat), P(GpuChunking), P(GpuNormalization), P(GpuPod5Reads), P(GpuSampleRanges)
+    tp, wp, ep, sp, xp, mp = P(GpuTrim), P(GpuWindows), P(GpuEvents), P(GpuSegmentation), P(GpuSpans), P(GpuMatch)
+    t = {
+        "vbz_is_error": (ctypes.c_bool, [u32]),
+        "vbz_error_string": (ctypes.c_char_p, [u32]),
+        "vbz_max_compressed_size": (u32, [u32, op]),
+        "vbz_compress": (u32, [vp, u32, vp, u32, op]),
+        "vbz_decompressed_size": (u32, [vp, u32, op]),
+        "vbz_gpu_create": (vp, [c_int, vp]),
+        "vbz_gpu_destroy": (None, [vp]),
+        "vbz_gpu_stream": (vp, [vp]),
+        "vbz_gpu_last_error": (ctypes.c_char_p, [vp]),
+        "vbz_gpu_set_trailers": (None, [vp, c_int]),
+        "vbz_gpu_synchronize": (c_int, [vp]),
+        "vbz_gpu_compress_batch": (c_int, [vp, bp, op, c_int]),
+        "vbz_gpu_decompress_signal_batch": (c_int, [vp, bp, op, c_int, fp]),
+        "vbz_gpu_chunk_layout_batch": (c_int, [vp, u32, vp, cp, vp, vp, u64]),
+        "vbz_gpu_decompress_chunks_batch": (c_int, [vp, bp, op, c_int, fp, cp, vp, vp, u64]),
+        "vbz_gpu_signal_norm_batch": (c_int, [vp, bp, op, c_int, u32, np_, vp]),
+        "vbz_gpu_decompress_signal_norm_batch": (c_int, [vp, bp, op, c_int, fp, np_, vp]),
+        "vbz_gpu_decompress_chunks_norm_batch": (c_int, [vp, bp, op, c_int, fp, cp, vp, vp, u64, np_, vp]),
+        "vbz_gpu_pod5_max_compressed_size": (u64, [u32]),
+        "vbz_gpu_pod5_read_samples_batch": (c_int, [vp, u32, vp, rp, vp]),
+        "vbz_gpu_pod5_decompress_chunks_batch": (c_int, [vp, bp, op, fp, cp, rp, vp, vp, u64, np_, vp]),
+        "vbz_gpu_pod5_signal_norm_batch": (c_int, [vp, bp, op, u32, rp, np_, vp]),
+        "vbz_gpu_pod5_decompress_signal_norm_batch": (c_int, [vp, bp, op, fp, rp, np_, vp]),
+        "vbz_gpu_range_samples_batch": (c_int, [vp, u32, vp, gp, vp]),
+        "vbz_gpu_decompress_chunks_range_batch": (c_int, [vp, bp, op, c_int, fp, cp, vp, vp, u64, np_, vp, gp]),
+        "vbz_gpu_signal_norm_range_batch": (c_int, [vp, bp, op, c_int, u32, np_, vp, gp]),
+        "vbz_gpu_pod5_decompress_chunks_range_batch": (c_int, [vp, bp, op, fp, cp, rp, vp, vp, u64, np_, vp, gp]),
+        "vbz_gpu_pod5_signal_norm_range_batch": (c_int, [vp, bp, op, u32, rp, np_, vp, gp]),
+        "vbz_gpu_signal_trim_batch": (c_int, [vp, bp, op, c_int, u32, np_, gp, tp, vp, vp]),
+        "vbz_gpu_pod5_signal_trim_batch": (c_int, [vp, bp, op, u32, rp, np_, gp, tp, vp, vp]),
+        "vbz_gpu_decompress_windows_batch": (c_int, [vp, bp, op, c_int, fp, wp, vp, np_, vp, gp]),
+        "vbz_gpu_pod5_decompress_windows_batch": (c_int, [vp, bp, op, fp, rp, wp, vp, np_, vp, gp]),
+        "vbz_gpu_signal_events_batch": (c_int, [vp, bp, op, c_int, fp, ep, vp, vp, np_, vp, gp]),
+        "vbz_gpu_pod5_signal_events_batch": (c_int, [vp, bp, op, fp, rp, ep, vp, vp, np_, vp, gp]),
+        "vbz_gpu_signal_segment_batch": (c_int, [vp, bp, op, c_int, u32, gp, sp, vp, vp]),
+        "vbz_gpu_pod5_signal_segment_batch": (c_int, [vp, bp, op, u32, rp, gp, sp, vp, vp]),
+        "vbz_gpu_signal_spans_batch": (c_int, [vp, bp, op, c_int, u32, np_, vp, gp, xp, vp, vp]),
+        "vbz_gpu_pod5_signal_spans_batch": (c_int, [vp, bp, op, u32, rp, np_, vp, gp, xp, vp, vp]),
+        "vbz_gpu_match_batch": (c_int, [vp, u32, vp, vp, mp, vp]),
+        "vbz_gpu_signal_match_batch": (c_int, [vp, bp, op, c_int, fp, np_, vp, gp, mp, vp, vp]),
+        "vbz_gpu_pod5_signal_match_batch": (c_int, [vp, bp, op, fp, rp, np_, vp, gp, mp, vp, vp]),
+        "vbz_gpu_match_best_batch": (c_int, [vp, u32, vp, u32, u32, vp]),
+        "vbz_gpu_match_path_batch": (c_int, [vp, u32, u32, vp, vp, mp, vp, P(GpuMatchPath), vp, vp]),
+        "vbz_gpu_set_match_path_cap": (None, [vp, u64]),
+        "vbz_gpu_query_valid_batch": (c_int, [vp, u32, vp, gp, u32, vp]),
+        "vbz_gpu_events_query_batch": (c_int, [vp, u32, vp, ep, vp, P(GpuEventsQuery), vp, vp, vp]),
+        "vbz_gpu_locate_levels_batch": (c_int, [vp, u32, u32, u32, u32, vp, vp, vp, vp, ep, vp, vp, vp, vp]),
+        "vbz_gpu_squiggle_batch": (c_int, [vp, P(GpuSquiggle), vp, vp, vp, vp]),
+        "vbz_gpu_levels_fit_batch": (c_int, [vp, u32, u32, P(GpuLocate), vp, vp, vp, vp, P(GpuLevelsFit), vp, vp, vp, vp, vp]),
+        "vbz_gpu_svb_compress_batch": (c_int, [vp, bp, c_int, c_int, c_int]),
+        "vbz_gpu_zstd_compress_batch": (c_int, [vp, bp, vp]),
+        "vbz_gpu_zstd_decompress_batch": (c_int, [vp, bp]),
+        "vbz_gpu_xxh64_batch": (c_int, [vp, bp, vp]),
+        "vbz_gpu_pack_batch": (c_int, [vp, bp, u32, vp, u64, vp, vp]),
+        "vbz_gpu_decompressed_size_batch": (c_int, [vp, bp, op, u32, vp, vp]),
+        "vbz_gpu_synth_lengths": (c_int, [vp, u64, u64, u32, vp]),
+        "vbz_gpu_synth_signal": (c_int, [vp, u64, u64, u32, vp, vp, vp]),
+        "vbz_gpu_profile_enable": (None, [vp, c_int]),
+        "vbz_gpu_profile_reset": (None, [vp]),
+        "vbz_gpu_profile_read": (c_int, [vp, P(ctypes.c_char_p), P(u32), P(ctypes.c_double), c_int]),
+        "vbz_gpu_decode_paths": (c_int, [vp, P(u32), P(u32)]),
+        "vbz_gpu_decode_literals_ahead": (c_int, [vp]),
+        "vbz_gpu_decode_span_paths": (c_int, [vp, P(u32)]),
+        "vbz_gpu_version": (ctypes.c_char_p, []),
+    }
+    # the groups that share one signature
+    for base, same in (("vbz_compress", ("vbz_decompress", "vbz_compress_sized", "vbz_decompress_sized")),
+                       ("vbz_gpu_set_trailers", ("vbz_gpu_set_canonical", "vbz_gpu_set_checksum")),
+                       ("vbz_gpu_compress_batch", ("vbz_gpu_decompress_batch",)),
+                       ("vbz_gpu_svb_compress_batch", ("vbz_gpu_svb_decompress_batch",)),
+                       ("vbz_gpu_synth_signal", ("vbz_gpu_synth_u32",))):
+        for name in same:
+            t[name] = t[base]
+    # the locate forms: a vbz_gpu_locate in vbz_gpu_match's place, the arguments those of the match calls
+    for name in ("vbz_gpu_match_batch", "vbz_gpu_signal_match_batch", "vbz_gpu_pod5_signal_match_batch", "vbz_gpu_match_path_batch"):
+        t[name.replace("_match", "_locate", 1)] = (c_int, [P(GpuLocate) if a is mp else a for a in t[name][1]])
+    # the _span twins: the hits are vbz_gpu_match_span, the arguments those of the cost-only calls
+    for name in ("vbz_gpu_match_batch", "vbz_gpu_signal_match_batch", "vbz_gpu_pod5_signal_match_batch",
+                 "vbz_gpu_locate_batch", "vbz_gpu_signal_locate_batch", "vbz_gpu_pod5_signal_locate_batch"):
+        t[name.replace("_batch", "_span_batch")] = t[name]
+    return t
+
+
+PROTOTYPES = _prototypes()
 _lib = None
 
 
@@ -473,227 +564,13 @@ def load():
             "(there is no CPU fallback for the VBZ codec in this package)" % LIB_PATH
         )
     L = ctypes.CDLL(LIB_PATH)
-    vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-    op = ctypes.POINTER(CompressionOptions)
-    bp = ctypes.POINTER(GpuBatch)
-    L.vbz_is_error.restype = ctypes.c_bool
-    L.vbz_is_error.argtypes = [u32]
-    L.vbz_error_string.restype = ctypes.c_char_p
-    L.vbz_error_string.argtypes = [u32]
-    L.vbz_max_compressed_size.restype = u32
-    L.vbz_max_compressed_size.argtypes = [u32, op]
-    for name in ("vbz_compress", "vbz_decompress", "vbz_compress_sized", "vbz_decompress_sized"):
-        f = getattr(L, name)
-        f.restype = u32
-        f.argtypes = [vp, u32, vp, u32, op]
-    L.vbz_decompressed_size.restype = u32
-    L.vbz_decompressed_size.argtypes = [vp, u32, op]
-    L.vbz_gpu_create.restype = vp
-    L.vbz_gpu_create.argtypes = [ctypes.c_int, vp]
-    L.vbz_gpu_destroy.restype = None
-    L.vbz_gpu_destroy.argtypes = [vp]
-    L.vbz_gpu_stream.restype = vp
-    L.vbz_gpu_stream.argtypes = [vp]
-    L.vbz_gpu_last_error.restype = ctypes.c_char_p
-    L.vbz_gpu_last_error.argtypes = [vp]
-    L.vbz_gpu_set_trailers.restype = None
-    L.vbz_gpu_set_trailers.argtypes = [vp, ctypes.c_int]
-    if hasattr(L, "vbz_gpu_set_canonical"):   # (builds of earlier rounds, loaded through VBZ_HIP_LIB, do not have it)
-        L.vbz_gpu_set_canonical.restype = None
-        L.vbz_gpu_set_canonical.argtypes = [vp, ctypes.c_int]
-    if hasattr(L, "vbz_gpu_set_checksum"):   # (likewise: builds of earlier rounds have no content checksums)
-        L.vbz_gpu_set_checksum.restype = None
-        L.vbz_gpu_set_checksum.argtypes = [vp, ctypes.c_int]
-    if hasattr(L, "vbz_gpu_xxh64_batch"):
-        L.vbz_gpu_xxh64_batch.restype = ctypes.c_int
-        L.vbz_gpu_xxh64_batch.argtypes = [vp, bp, vp]
-    if hasattr(L, "vbz_gpu_pack_batch"):   # (likewise: builds of earlier rounds have no dense arenas)
-        L.vbz_gpu_pack_batch.restype = ctypes.c_int
-        L.vbz_gpu_pack_batch.argtypes = [vp, bp, u32, vp, u64, vp, vp]
-        L.vbz_gpu_decompressed_size_batch.restype = ctypes.c_int
-        L.vbz_gpu_decompressed_size_batch.argtypes = [vp, bp, op, u32, vp, vp]
-    L.vbz_gpu_synchronize.restype = ctypes.c_int
-    L.vbz_gpu_synchronize.argtypes = [vp]
-    for name in ("vbz_gpu_compress_batch", "vbz_gpu_decompress_batch"):
-        f = getattr(L, name)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, bp, op, ctypes.c_int]
-    if hasattr(L, "vbz_gpu_decompress_signal_batch"):   # (likewise: builds of earlier rounds decode to int16 only)
-        L.vbz_gpu_decompress_signal_batch.restype = ctypes.c_int
-        L.vbz_gpu_decompress_signal_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.POINTER(GpuSignalFormat)]
-    if hasattr(L, "vbz_gpu_decompress_chunks_batch"):   # (likewise: builds of earlier rounds have no chunk decode)
-        cp = ctypes.POINTER(GpuChunking)
-        L.vbz_gpu_chunk_layout_batch.restype = ctypes.c_int
-        L.vbz_gpu_chunk_layout_batch.argtypes = [vp, u32, vp, cp, vp, vp, u64]
-        L.vbz_gpu_decompress_chunks_batch.restype = ctypes.c_int
-        L.vbz_gpu_decompress_chunks_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.POINTER(GpuSignalFormat), cp, vp, vp, u64]
-    if hasattr(L, "vbz_gpu_signal_norm_batch"):   # (likewise: builds of earlier rounds have no normalising decode)
-        np_ = ctypes.POINTER(GpuNormalization)
-        fp = ctypes.POINTER(GpuSignalFormat)
-        cp = ctypes.POINTER(GpuChunking)
-        L.vbz_gpu_signal_norm_batch.restype = ctypes.c_int
-        L.vbz_gpu_signal_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, u32, np_, vp]
-        L.vbz_gpu_decompress_signal_norm_batch.restype = ctypes.c_int
-        L.vbz_gpu_decompress_signal_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, np_, vp]
-        L.vbz_gpu_decompress_chunks_norm_batch.restype = ctypes.c_int
-        L.vbz_gpu_decompress_chunks_norm_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, cp, vp, vp, u64, np_, vp]
-    if hasattr(L, "vbz_gpu_pod5_max_compressed_size"):   # (likewise: builds of earlier rounds have no POD5 codec)
-        L.vbz_gpu_pod5_max_compressed_size.restype = u64
-        L.vbz_gpu_pod5_max_compressed_size.argtypes = [u32]
-    if hasattr(L, "vbz_gpu_pod5_read_samples_batch"):   # (likewise: builds of earlier rounds take POD5 rows one by one)
-        np_ = ctypes.POINTER(GpuNormalization)
-        fp = ctypes.POINTER(GpuSignalFormat)
-        cp = ctypes.POINTER(GpuChunking)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        L.vbz_gpu_pod5_read_samples_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_read_samples_batch.argtypes = [vp, u32, vp, rp, vp]
-        L.vbz_gpu_pod5_decompress_chunks_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_decompress_chunks_batch.argtypes = [vp, bp, op, fp, cp, rp, vp, vp, u64, np_, vp]
-        L.vbz_gpu_pod5_signal_norm_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_signal_norm_batch.argtypes = [vp, bp, op, u32, rp, np_, vp]
-        L.vbz_gpu_pod5_decompress_signal_norm_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_decompress_signal_norm_batch.argtypes = [vp, bp, op, fp, rp, np_, vp]
-    if hasattr(L, "vbz_gpu_range_samples_batch"):   # (likewise: builds of earlier rounds have no sample ranges)
-        np_ = ctypes.POINTER(GpuNormalization)
-        fp = ctypes.POINTER(GpuSignalFormat)
-        cp = ctypes.POINTER(GpuChunking)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        gp = ctypes.POINTER(GpuSampleRanges)
-        L.vbz_gpu_range_samples_batch.restype = ctypes.c_int
-        L.vbz_gpu_range_samples_batch.argtypes = [vp, u32, vp, gp, vp]
-        L.vbz_gpu_decompress_chunks_range_batch.restype = ctypes.c_int
-        L.vbz_gpu_decompress_chunks_range_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, cp, vp, vp, u64, np_, vp, gp]
-        L.vbz_gpu_signal_norm_range_batch.restype = ctypes.c_int
-        L.vbz_gpu_signal_norm_range_batch.argtypes = [vp, bp, op, ctypes.c_int, u32, np_, vp, gp]
-        L.vbz_gpu_pod5_decompress_chunks_range_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_decompress_chunks_range_batch.argtypes = [vp, bp, op, fp, cp, rp, vp, vp, u64, np_, vp, gp]
-        L.vbz_gpu_pod5_signal_norm_range_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_signal_norm_range_batch.argtypes = [vp, bp, op, u32, rp, np_, vp, gp]
-    if hasattr(L, "vbz_gpu_signal_trim_batch"):   # (likewise: builds of earlier rounds find no trim point)
-        np_ = ctypes.POINTER(GpuNormalization)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        gp = ctypes.POINTER(GpuSampleRanges)
-        tp = ctypes.POINTER(GpuTrim)
-        L.vbz_gpu_signal_trim_batch.restype = ctypes.c_int
-        L.vbz_gpu_signal_trim_batch.argtypes = [vp, bp, op, ctypes.c_int, u32, np_, gp, tp, vp, vp]
-        L.vbz_gpu_pod5_signal_trim_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_signal_trim_batch.argtypes = [vp, bp, op, u32, rp, np_, gp, tp, vp, vp]
-    if hasattr(L, "vbz_gpu_decompress_windows_batch"):   # (likewise: builds of earlier rounds have no signal windows)
-        np_ = ctypes.POINTER(GpuNormalization)
-        fp = ctypes.POINTER(GpuSignalFormat)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        gp = ctypes.POINTER(GpuSampleRanges)
-        wp = ctypes.POINTER(GpuWindows)
-        L.vbz_gpu_decompress_windows_batch.restype = ctypes.c_int
-        L.vbz_gpu_decompress_windows_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, wp, vp, np_, vp, gp]
-        L.vbz_gpu_pod5_decompress_windows_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_decompress_windows_batch.argtypes = [vp, bp, op, fp, rp, wp, vp, np_, vp, gp]
-    if hasattr(L, "vbz_gpu_signal_events_batch"):   # (likewise: builds of earlier rounds have no signal events)
-        np_ = ctypes.POINTER(GpuNormalization)
-        fp = ctypes.POINTER(GpuSignalFormat)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        gp = ctypes.POINTER(GpuSampleRanges)
-        ep = ctypes.POINTER(GpuEvents)
-        L.vbz_gpu_signal_events_batch.restype = ctypes.c_int
-        L.vbz_gpu_signal_events_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, ep, vp, vp, np_, vp, gp]
-        L.vbz_gpu_pod5_signal_events_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_signal_events_batch.argtypes = [vp, bp, op, fp, rp, ep, vp, vp, np_, vp, gp]
-    if hasattr(L, "vbz_gpu_signal_segment_batch"):   # (likewise: builds of earlier rounds have no signal segmentation)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        gp = ctypes.POINTER(GpuSampleRanges)
-        sp = ctypes.POINTER(GpuSegmentation)
-        L.vbz_gpu_signal_segment_batch.restype = ctypes.c_int
-        L.vbz_gpu_signal_segment_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.c_uint32, gp, sp, vp, vp]
-        L.vbz_gpu_pod5_signal_segment_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_signal_segment_batch.argtypes = [vp, bp, op, ctypes.c_uint32, rp, gp, sp, vp, vp]
-    if hasattr(L, "vbz_gpu_signal_spans_batch"):   # (likewise: builds of earlier rounds have no signal spans)
-        np_ = ctypes.POINTER(GpuNormalization)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        gp = ctypes.POINTER(GpuSampleRanges)
-        xp = ctypes.POINTER(GpuSpans)
-        L.vbz_gpu_signal_spans_batch.restype = ctypes.c_int
-        L.vbz_gpu_signal_spans_batch.argtypes = [vp, bp, op, ctypes.c_int, ctypes.c_uint32, np_, vp, gp, xp, vp, vp]
-        L.vbz_gpu_pod5_signal_spans_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_signal_spans_batch.argtypes = [vp, bp, op, ctypes.c_uint32, rp, np_, vp, gp, xp, vp, vp]
-    if hasattr(L, "vbz_gpu_match_batch"):   # (likewise: builds of earlier rounds have no signal match)
-        np_ = ctypes.POINTER(GpuNormalization)
-        fp = ctypes.POINTER(GpuSignalFormat)
-        rp = ctypes.POINTER(GpuPod5Reads)
-        gp = ctypes.POINTER(GpuSampleRanges)
-        mp = ctypes.POINTER(GpuMatch)
-        L.vbz_gpu_match_batch.restype = ctypes.c_int
-        L.vbz_gpu_match_batch.argtypes = [vp, u32, vp, vp, mp, vp]
-        L.vbz_gpu_signal_match_batch.restype = ctypes.c_int
-        L.vbz_gpu_signal_match_batch.argtypes = [vp, bp, op, ctypes.c_int, fp, np_, vp, gp, mp, vp, vp]
-        L.vbz_gpu_pod5_signal_match_batch.restype = ctypes.c_int
-        L.vbz_gpu_pod5_signal_match_batch.argtypes = [vp, bp, op, fp, rp, np_, vp, gp, mp, vp, vp]
-    if hasattr(L, "vbz_gpu_match_span_batch"):   # (likewise: the hits are vbz_gpu_match_span, the arguments those of the three above)
-        for name in ("vbz_gpu_match_span_batch", "vbz_gpu_signal_match_span_batch", "vbz_gpu_pod5_signal_match_span_batch"):
-            twin = getattr(L, name.replace("_span", ""))
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = list(twin.argtypes)
-    if hasattr(L, "vbz_gpu_match_path_batch"):   # (likewise: the winners' table and the warping path of listed pairs)
-        L.vbz_gpu_match_best_batch.restype = ctypes.c_int
-        L.vbz_gpu_match_best_batch.argtypes = [vp, u32, vp, u32, u32, vp]
-        L.vbz_gpu_match_path_batch.restype = ctypes.c_int
-        L.vbz_gpu_match_path_batch.argtypes = [vp, u32, u32, vp, vp, ctypes.POINTER(GpuMatch), vp, ctypes.POINTER(GpuMatchPath), vp, vp]
-        L.vbz_gpu_set_match_path_cap.restype = None
-        L.vbz_gpu_set_match_path_cap.argtypes = [vp, u64]
-    if hasattr(L, "vbz_gpu_locate_batch"):   # (likewise: a vbz_gpu_locate in vbz_gpu_match's place, the arguments those of the match calls)
-        for name in ("vbz_gpu_locate_batch", "vbz_gpu_signal_locate_batch", "vbz_gpu_pod5_signal_locate_batch"):
-            twin = getattr(L, name.replace("_locate", "_match"))
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = [ctypes.POINTER(GpuLocate) if a is ctypes.POINTER(GpuMatch) else a for a in twin.argtypes]
-    if hasattr(L, "vbz_gpu_locate_span_batch"):   # (likewise: the hits are vbz_gpu_match_span, the arguments those of the three above)
-        for name in ("vbz_gpu_locate_span_batch", "vbz_gpu_signal_locate_span_batch", "vbz_gpu_pod5_signal_locate_span_batch"):
-            twin = getattr(L, name.replace("_span", ""))
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = list(twin.argtypes)
-    if hasattr(L, "vbz_gpu_locate_path_batch"):   # (likewise: the match path call's arguments with a vbz_gpu_locate, and the fused calls' valid[])
-        L.vbz_gpu_locate_path_batch.restype = ctypes.c_int
-        L.vbz_gpu_locate_path_batch.argtypes = [ctypes.POINTER(GpuLocate) if a is ctypes.POINTER(GpuMatch) else a for a in L.vbz_gpu_match_path_batch.argtypes]
-        L.vbz_gpu_query_valid_batch.restype = ctypes.c_int
-        L.vbz_gpu_query_valid_batch.argtypes = [vp, u32, vp, gp, u32, vp]
-    if hasattr(L, "vbz_gpu_events_query_batch"):   # (likewise: the event records as a query, the path as a table per target level)
-        ep = ctypes.POINTER(GpuEvents)
-        L.vbz_gpu_events_query_batch.restype = ctypes.c_int
-        L.vbz_gpu_events_query_batch.argtypes = [vp, u32, vp, ep, vp, ctypes.POINTER(GpuEventsQuery), vp, vp, vp]
-        L.vbz_gpu_locate_levels_batch.restype = ctypes.c_int
-        L.vbz_gpu_locate_levels_batch.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp, ep, vp, vp, vp, vp]
-    if hasattr(L, "vbz_gpu_squiggle_batch"):   # (likewise: target levels from bases, new constants along the path)
-        L.vbz_gpu_squiggle_batch.restype = ctypes.c_int
-        L.vbz_gpu_squiggle_batch.argtypes = [vp, ctypes.POINTER(GpuSquiggle), vp, vp, vp, vp]
-        L.vbz_gpu_levels_fit_batch.restype = ctypes.c_int
-        L.vbz_gpu_levels_fit_batch.argtypes = [vp, u32, u32, ctypes.POINTER(GpuLocate), vp, vp, vp, vp, ctypes.POINTER(GpuLevelsFit), vp, vp, vp, vp, vp]
-    for name in ("vbz_gpu_svb_compress_batch", "vbz_gpu_svb_decompress_batch"):
-        f = getattr(L, name)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, bp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.vbz_gpu_zstd_compress_batch.restype = ctypes.c_int
-    L.vbz_gpu_zstd_compress_batch.argtypes = [vp, bp, vp]
-    L.vbz_gpu_zstd_decompress_batch.restype = ctypes.c_int
-    L.vbz_gpu_zstd_decompress_batch.argtypes = [vp, bp]
-    L.vbz_gpu_synth_lengths.restype = ctypes.c_int
-    L.vbz_gpu_synth_lengths.argtypes = [vp, u64, u64, u32, vp]
-    for name in ("vbz_gpu_synth_signal", "vbz_gpu_synth_u32"):
-        f = getattr(L, name)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, u64, u64, u32, vp, vp, vp]
-    L.vbz_gpu_profile_enable.restype = None
-    L.vbz_gpu_profile_enable.argtypes = [vp, ctypes.c_int]
-    L.vbz_gpu_profile_reset.restype = None
-    L.vbz_gpu_profile_reset.argtypes = [vp]
-    L.vbz_gpu_profile_read.restype = ctypes.c_int
-    L.vbz_gpu_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_double), ctypes.c_int]
-    L.vbz_gpu_decode_paths.restype = ctypes.c_int
-    L.vbz_gpu_decode_paths.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-    L.vbz_gpu_decode_literals_ahead.restype = ctypes.c_int
-    L.vbz_gpu_decode_literals_ahead.argtypes = [vp]
-    if hasattr(L, "vbz_gpu_decode_span_paths"):   # (tools/ab_libs.py, tools/compare_libs.py load builds of earlier rounds through VBZ_HIP_LIB)
-        L.vbz_gpu_decode_span_paths.restype = ctypes.c_int
-        L.vbz_gpu_decode_span_paths.argtypes = [vp, ctypes.POINTER(u32)]
-    L.vbz_gpu_version.restype = ctypes.c_char_p
-    L.vbz_gpu_version.argtypes = []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        # (a name the library lacks is skipped: tools/ab_libs.py and tools/compare_libs.py load earlier builds through VBZ_HIP_LIB, and a
+        # call of such a name fails at its first use)
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.restype = restype
+            f.argtypes = list(argtypes)
     _lib = L
     return L
 

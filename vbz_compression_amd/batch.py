@@ -15,6 +15,56 @@ from . import _lib
 FLT_MIN = 1.1754943508222875e-38   # the smallest normal float32
 
 
+def ptr(t):
+    """a tensor's address, NULL for None"""
+    return t.data_ptr() if t is not None else None
+
+
+def ref(s):
+    """a C struct by reference, NULL for None"""
+    return ctypes.byref(s) if s is not None else None
+
+
+def table(name, t, dtype, device=None, shape=None, numel=None, at_least=None, none=False):
+    """What a device table must be, stated once -> t: of `dtype`, contiguous, on `device` (None: wherever it is) and, where a rule is given,
+    of `shape` (a None entry: any extent), of exactly `numel` entries or of `at_least` entries.  none: None passes, as the C entry's NULL."""
+    if t is None:
+        assert none, "%s is required" % name
+        return None
+    ok = t.dtype == dtype and t.is_contiguous() and (device is None or t.device == device)
+    if ok and shape is not None:
+        ok = t.dim() == len(shape) and all(w is None or int(s) == w for s, w in zip(t.shape, shape))
+    if ok and numel is not None:
+        ok = int(t.numel()) == numel
+    if ok and at_least is not None:
+        ok = int(t.numel()) >= at_least
+    assert ok, (name, t.dtype, tuple(t.shape), str(t.device))
+    return t
+
+
+def output(name, t, dtype, device, shape, three_state=False, at_least=False):
+    """An output the caller may give -> the tensor: None allocates torch.empty(shape, dtype, device); a given tensor must be a table of that
+    dtype and shape (shape an int: of that many entries, or with at_least of no fewer) and comes back as it is.  three_state: True
+    allocates, False or None means not wanted (-> None), a tensor is checked."""
+    if three_state:
+        if t is None or t is False:
+            return None
+        t = None if t is True else t
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if isinstance(shape, int):
+        return table(name, t, dtype, device, at_least=shape) if at_least else table(name, t, dtype, device, numel=shape)
+    return table(name, t, dtype, device, shape=shape)
+
+
+def wrap_u32(t):
+    """values 0 ... 0xFFFFFFFF (a tensor or a sequence) as an int32 tensor of the same 32 bits; an int32 tensor as it is"""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.int32:
+        return t
+    w = torch.as_tensor(t, dtype=torch.int64).reshape(-1)
+    return torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+
+
 @dataclasses.dataclass(frozen=True)
 class Normalization:
     """Per-read normalisation from the read's own statistics (include/vbz_gpu.h: vbz_gpu_normalization): method "med_mad" (c = median,
@@ -132,8 +182,8 @@ class Match:
 
     def c_struct(self, ref, ref_len):
         """ref: int8 [R, ref_stride] on the device; ref_len: int32 [R] on the device (uint32 bits)"""
-        assert ref.dtype == torch.int8 and ref.is_contiguous() and ref.dim() == 2, (ref.dtype, ref.shape)
-        assert ref_len.dtype == torch.int32 and ref_len.is_contiguous() and ref_len.device == ref.device and int(ref_len.numel()) == int(ref.shape[0])
+        table("ref", ref, torch.int8, shape=(None, None))
+        table("ref_len", ref_len, torch.int32, ref.device, numel=int(ref.shape[0]))
         g = _lib.GpuMatch()
         g.query_len, g.n_refs, g.ref_stride = int(self.query_len), int(ref.shape[0]), int(ref.shape[1])
         g.quant = self.quant
@@ -152,9 +202,8 @@ class Locate:
 
     def c_struct(self, target, target_len):
         """target: int8 [G, target_stride] on the device; target_len: int32 [G] on the device (uint32 bits)"""
-        assert target.dtype == torch.int8 and target.is_contiguous() and target.dim() == 2, (target.dtype, target.shape)
-        assert (target_len.dtype == torch.int32 and target_len.is_contiguous() and target_len.device == target.device
-                and int(target_len.numel()) == int(target.shape[0]))
+        table("target", target, torch.int8, shape=(None, None))
+        table("target_len", target_len, torch.int32, target.device, numel=int(target.shape[0]))
         g = _lib.GpuLocate()
         g.query_len, g.n_targets, g.target_stride = int(self.query_len), int(target.shape[0]), int(target.shape[1])
         g.quant = self.quant
@@ -233,26 +282,37 @@ class GpuCodec:
 
     # -- helpers ---------------------------------------------------------------------------------
     def _batch(self, src, src_off, src_size, dst, dst_off, dst_cap, result):
-        n = int(src_off.numel())
-        for t, dt in ((src_off, torch.int64), (dst_off, torch.int64), (src_size, torch.int32), (dst_cap, torch.int32), (result, torch.int32)):
-            assert t.dtype == dt and t.is_contiguous() and t.device == self.device, (t.dtype, dt, t.device)
+        table("src_off", src_off, torch.int64, self.device)
+        table("dst_off", dst_off, torch.int64, self.device)
+        table("src_size", src_size, torch.int32, self.device)
+        table("dst_cap", dst_cap, torch.int32, self.device)
+        table("result", result, torch.int32, self.device)
         assert src.dtype == torch.uint8 and dst.dtype == torch.uint8
+        b = self._src_batch(src, src_off, src_size)
+        b.dst, b.dst_off, b.dst_cap, b.dst_bytes, b.result = dst.data_ptr(), dst_off.data_ptr(), dst_cap.data_ptr(), dst.numel(), result.data_ptr()
+        return b
+
+    @staticmethod
+    def _src_batch(src, src_off, src_size):
+        """the source half of a GpuBatch (the tables checked by the caller)"""
         b = _lib.GpuBatch()
-        b.n_reads = n
-        b.src = src.data_ptr()
-        b.src_off = src_off.data_ptr()
-        b.src_size = src_size.data_ptr()
-        b.src_bytes = src.numel()
-        b.dst = dst.data_ptr()
-        b.dst_off = dst_off.data_ptr()
-        b.dst_cap = dst_cap.data_ptr()
-        b.dst_bytes = dst.numel()
-        b.result = result.data_ptr()
+        b.n_reads, b.src, b.src_off, b.src_size, b.src_bytes = int(src_off.numel()), src.data_ptr(), src_off.data_ptr(), src_size.data_ptr(), src.numel()
         return b
 
     def _rc(self, rc, what):
         if rc != 0:
             raise RuntimeError("%s failed (%d): %s" % (what, rc, self.L.vbz_gpu_last_error(self.ctx).decode()))
+
+    def _call(self, name, *args):
+        """One entry of the library, vbz_gpu_<name>(ctx, *args), on the codec's stream between the two waits (see the class) -> its return
+        code, after _rc has turned a failure into the RuntimeError that names the entry."""
+        cur = self._enter()
+        try:
+            rc = getattr(self.L, "vbz_gpu_" + name)(self.ctx, *args)
+            self._rc(rc, name)
+            return rc
+        finally:
+            self._exit(cur)
 
     def _typed(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False, dst_bytes=0, f=None, signed=True, ch=None,
                chunk_first=None, chunks=None, m=None, ss=None, g=None, r=None, t=None, out=None, w=None, ev=None, moments=None, sg=None,
@@ -274,15 +334,11 @@ class GpuCodec:
                         result)
         if dst is None:
             b.dst, b.dst_bytes = None, int(dst_bytes)
-
-        def ref(s):
-            return ctypes.byref(s) if s is not None else None
-
         mt = mt if mt is not None else lc
         reads = [ref(r)] if r is not None else []
         if ev is not None:
             assert ch is None and w is None, "a call has a chunking, windows or events, never two of them"
-            name, args = "signal_events", [ref(f)] + reads + [ref(ev), out.data_ptr(), moments.data_ptr() if moments is not None else None, ref(m), ss, ref(g)]
+            name, args = "signal_events", [ref(f)] + reads + [ref(ev), out.data_ptr(), ptr(moments), ref(m), ss, ref(g)]
         elif mt is not None:
             assert ch is None and w is None, "a call has a chunking, windows, events, a match or a locate, never two of them"
             name = ("signal_match" if isinstance(mt, _lib.GpuMatch) else "signal_locate") + ("_span" if span else "")
@@ -294,10 +350,9 @@ class GpuCodec:
             name, args = "decompress_chunks_range", [ref(f), ref(ch)] + reads + [chunk_first.data_ptr(), chunks.data_ptr(), int(chunks.shape[0]), ref(m),
                                                                                  ss, ref(g)]
         elif f is None and sp is not None:
-            name, args = "signal_spans", [int(bool(signed))] + reads + [ref(m), ss, ref(g), ref(sp), event_first.data_ptr(),
-                                                                        start.data_ptr() if start is not None else None]
+            name, args = "signal_spans", [int(bool(signed))] + reads + [ref(m), ss, ref(g), ref(sp), event_first.data_ptr(), ptr(start)]
         elif f is None and sg is not None:
-            name, args = "signal_segment", [int(bool(signed))] + reads + [ref(g), ref(sg), event_first.data_ptr(), start.data_ptr() if start is not None else None]
+            name, args = "signal_segment", [int(bool(signed))] + reads + [ref(g), ref(sg), event_first.data_ptr(), ptr(start)]
         elif f is None and t is not None:
             name, args = "signal_trim", [int(bool(signed))] + reads + [ref(m), ref(g), ref(t), ss, out.data_ptr()]
         elif f is None:
@@ -306,13 +361,7 @@ class GpuCodec:
             name, args = "decompress_signal", [ref(f)]
         else:
             name, args = "decompress_signal_norm", [ref(f)] + reads + [ref(m), ss]
-        name = ("pod5_" if r is not None else "") + name + "_batch"
-        head = [self.ctx, ref(b), ref(opts)] + ([int(sized)] if r is None else [])
-        cur = self._enter()
-        try:
-            self._rc(getattr(self.L, "vbz_gpu_" + name)(*head, *args), name)
-        finally:
-            self._exit(cur)
+        self._call(("pod5_" if r is not None else "") + name + "_batch", ref(b), ref(opts), *([int(sized)] if r is None else []), *args)
 
     @staticmethod
     def options(zigzag=True, size=2, level=1, version=1):
@@ -321,19 +370,11 @@ class GpuCodec:
     # -- full path -------------------------------------------------------------------------------
     def compress(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_compress_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized)), "compress_batch")
-        finally:
-            self._exit(cur)
+        self._call("compress_batch", ctypes.byref(b), ctypes.byref(opts), int(sized))
 
     def decompress(self, src, src_off, src_size, dst, dst_off, dst_cap, result, opts, sized=False):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_decompress_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), int(sized)), "decompress_batch")
-        finally:
-            self._exit(cur)
+        self._call("decompress_batch", ctypes.byref(b), ctypes.byref(opts), int(sized))
 
     _SIGNAL_TYPES = {torch.float32: _lib.VBZ_GPU_SIGNAL_F32, torch.float16: _lib.VBZ_GPU_SIGNAL_F16, torch.bfloat16: _lib.VBZ_GPU_SIGNAL_BF16}
 
@@ -342,20 +383,15 @@ class GpuCodec:
         f = _lib.GpuSignalFormat()
         f.out_type = self._SIGNAL_TYPES[dtype]
         f.is_signed = int(bool(signed))
-        for name, t in (("offset", offset), ("scale", scale)):
-            if t is not None:
-                assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) >= n, (name, t.dtype, t.device)
-                setattr(f, name, t.data_ptr())
+        f.offset = ptr(table("offset", offset, torch.float32, self.device, at_least=n, none=True))
+        f.scale = ptr(table("scale", scale, torch.float32, self.device, at_least=n, none=True))
         return f
 
     def _norm_args(self, n, norm, norm_out, scale, offset):
         """(the C struct, shift_scale pointer) of a normalising call; norm_out: a float32 [n, 2] tensor on the codec's device, or None"""
         assert scale is None and offset is None, "norm= replaces scale and offset"
         assert isinstance(norm, Normalization), norm
-        if norm_out is not None:
-            assert norm_out.dtype == torch.float32 and norm_out.is_contiguous() and norm_out.device == self.device and tuple(norm_out.shape) == (n, 2), (
-                norm_out.dtype, norm_out.shape)
-        return norm.c_struct(), (norm_out.data_ptr() if norm_out is not None else None)
+        return norm.c_struct(), ptr(table("norm_out", norm_out, torch.float32, self.device, shape=(n, 2), none=True))
 
     # -- per-read sample ranges (include/vbz_gpu.h: vbz_gpu_sample_ranges) ---------------------------
     _RANGE_STATS = {"range": _lib.VBZ_GPU_RANGE_STATS_RANGE, "read": _lib.VBZ_GPU_RANGE_STATS_READ}
@@ -364,10 +400,7 @@ class GpuCodec:
         """a begin / end table (a tensor or a sequence of n values 0 ... 0xFFFFFFFF, or None) as int32 on the device (uint32 bits)"""
         if t is None:
             return None
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32):
-            w = torch.as_tensor(t, dtype=torch.int64).reshape(-1)
-            t = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
-        t = t.to(self.device).contiguous()
+        t = wrap_u32(t).to(self.device).contiguous()
         assert int(t.numel()) == n, (int(t.numel()), n)
         return t
 
@@ -379,24 +412,17 @@ class GpuCodec:
         assert stats is None or stats in self._RANGE_STATS, stats
         tb, te = self._range_table(n, begin), self._range_table(n, end)
         g = _lib.GpuSampleRanges()
-        g.begin = tb.data_ptr() if tb is not None else None
-        g.end = te.data_ptr() if te is not None else None
+        g.begin, g.end = ptr(tb), ptr(te)
         g.stats = self._RANGE_STATS[stats or "range"]
         return g, (tb, te)
 
     def range_samples(self, samples, begin=None, end=None):
         """The sample counts of the reads' clamped ranges (include/vbz_gpu.h: vbz_gpu_range_samples_batch): min(end, T) - min(begin, end, T)
         for T = samples[i] (int32 on the device; 2^31 or more as uint32 passes through) -> int32 [n] on the device; it feeds chunk_layout."""
-        assert samples.dtype == torch.int32 and samples.is_contiguous() and samples.device == self.device, (samples.dtype, samples.device)
-        n = int(samples.numel())
+        n = int(table("samples", samples, torch.int32, self.device).numel())
         g, keep = self._ranges(n, begin, end, None)
         out = torch.empty(n, dtype=torch.int32, device=self.device)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_range_samples_batch(self.ctx, n, samples.data_ptr(), ctypes.byref(g) if g is not None else None, out.data_ptr()),
-                     "range_samples_batch")
-        finally:
-            self._exit(cur)
+        self._call("range_samples_batch", n, samples.data_ptr(), ref(g), out.data_ptr())
         return out
 
     @staticmethod
@@ -412,8 +438,7 @@ class GpuCodec:
         every read (vbz_gpu_signal_norm_range_batch)."""
         n = int(src_off.numel())
         g, keep = self._ranges(n, begin, end, stats)
-        if shift_scale is None:
-            shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        shift_scale = output("shift_scale", shift_scale, torch.float32, self.device, (n, 2))
         m, ss = self._norm_args(n, norm, shift_scale, None, None)
         self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, self._extent(n, dst_off, dst_cap), signed=signed, m=m, ss=ss, g=g)
         return shift_scale
@@ -423,12 +448,8 @@ class GpuCodec:
         device (allocated when None); shift_scale: None (not wanted), True (allocated) or a float32 [n, 2] tensor"""
         trim = Trim() if trim is None else trim
         assert isinstance(trim, Trim), trim
-        if out is None:
-            out = torch.empty(n, dtype=torch.int32, device=self.device)
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and int(out.numel()) == n, (out.dtype, out.shape)
-        if shift_scale is True:
-            shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        return trim.c_struct(), out, shift_scale
+        out = output("out", out, torch.int32, self.device, n)
+        return trim.c_struct(), out, output("shift_scale", shift_scale, torch.float32, self.device, (n, 2), three_state=True)
 
     def signal_trim(self, src, src_off, src_size, dst_off, dst_cap, result, opts, norm, trim=None, out=None, shift_scale=None, signed=True,
                     sized=False, begin=None, end=None, stats=None):
@@ -445,26 +466,24 @@ class GpuCodec:
                     t=t, out=out)
         return out if shift_scale is None else (out, shift_scale)
 
+    def _capped(self, name, t, cap, bound):
+        """(cap, the table or None) of an int32 output of at least `cap` entries: the caller's `t`, checked, or a new one.  cap None: t's
+        entries when t is given, else bound() (it may cost a host copy); cap 0: the count-only call, no table"""
+        if cap is None:
+            cap = int(t.numel()) if t is not None else bound()
+        if t is not None or cap:
+            t = output(name, t, torch.int32, self.device, cap, at_least=True)
+        return cap, (t if cap else None)
+
     # -- signal segmentation (include/vbz_gpu.h: vbz_gpu_segmentation) -------------------------------
     def _segment_args(self, n, segmentation, samples, start_cap, event_first, start):
         """(the C struct, event_first, start) of a segmentation call over n reads of `samples` (an int tensor: the reads' sample counts).
         start_cap None: the bound, sum of 2 + T / (radius + 1) (one host copy); 0: the count-only call, start is None"""
         sg = Segmentation() if segmentation is None else segmentation
         assert isinstance(sg, Segmentation), sg
-        if start is not None:
-            start_cap = int(start.numel()) if start_cap is None else start_cap
-        elif start_cap is None:
-            start_cap = int((samples.to(torch.int64) // (sg.radius + 1) + 2).sum().item()) if n else 0
-        if start is None and start_cap:
-            start = torch.empty(start_cap, dtype=torch.int32, device=self.device)
-        if start is not None:
-            assert start.dtype == torch.int32 and start.is_contiguous() and start.device == self.device and int(start.numel()) >= start_cap, (
-                start.dtype, start.shape, start_cap)
-        if event_first is None:
-            event_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        assert event_first.dtype == torch.int64 and event_first.is_contiguous() and event_first.device == self.device and int(event_first.numel()) == n + 1, (
-            event_first.dtype, event_first.shape)
-        return sg.c_struct(start_cap), event_first, (start if start_cap else None)
+        start_cap, start = self._capped("start", start, start_cap, lambda: int((samples.to(torch.int64) // (sg.radius + 1) + 2).sum().item()) if n else 0)
+        event_first = output("event_first", event_first, torch.int64, self.device, n + 1)
+        return sg.c_struct(start_cap), event_first, start
 
     def signal_segment(self, src, src_off, src_size, dst_off, dst_cap, result, opts, segmentation=None, start_cap=None, signed=True, sized=False,
                        begin=None, end=None, event_first=None, start=None):
@@ -490,30 +509,17 @@ class GpuCodec:
         sp = Spans() if spans is None else spans
         assert isinstance(sp, Spans), sp
         assert (norm is None) != (level is None), "one of norm= and level="
-        if edge is not None:
-            edge_cap = int(edge.numel()) if edge_cap is None else edge_cap
-        elif edge_cap is None:
-            k = sp.min_length + sp.merge_gap + 1
-            edge_cap = int((2 * ((samples.to(torch.int64) + sp.merge_gap + 1) // k)).sum().item()) if n else 0
-        if edge is None and edge_cap:
-            edge = torch.empty(edge_cap, dtype=torch.int32, device=self.device)
-        if edge is not None:
-            assert edge.dtype == torch.int32 and edge.is_contiguous() and edge.device == self.device and int(edge.numel()) >= edge_cap, (
-                edge.dtype, edge.shape, edge_cap)
-        if edge_first is None:
-            edge_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        assert edge_first.dtype == torch.int64 and edge_first.is_contiguous() and edge_first.device == self.device and int(edge_first.numel()) == n + 1, (
-            edge_first.dtype, edge_first.shape)
+        k = sp.min_length + sp.merge_gap + 1
+        edge_cap, edge = self._capped("edge", edge, edge_cap, lambda: int((2 * ((samples.to(torch.int64) + sp.merge_gap + 1) // k)).sum().item()) if n else 0)
+        edge_first = output("edge_first", edge_first, torch.int64, self.device, n + 1)
         m = ss = None
         if norm is not None:
-            if shift_scale is True:
-                shift_scale = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+            shift_scale = output("shift_scale", shift_scale, torch.float32, self.device, (n, 2), three_state=True)
             m, ss = self._norm_args(n, norm, shift_scale, None, None)
         else:
             assert shift_scale is None, "shift_scale= goes with norm="
-            assert level.dtype == torch.float32 and level.is_contiguous() and level.device == self.device and tuple(level.shape) == (n, 2), (
-                level.dtype, level.shape)
-        return sp.c_struct(edge_cap, level.data_ptr() if level is not None else None), edge_first, (edge if edge_cap else None), m, ss, shift_scale
+            table("level", level, torch.float32, self.device, shape=(n, 2))
+        return sp.c_struct(edge_cap, ptr(level)), edge_first, edge, m, ss, shift_scale
 
     def signal_spans(self, src, src_off, src_size, dst_off, dst_cap, result, opts, spans=None, edge_cap=None, signed=True, sized=False, begin=None,
                      end=None, edge_first=None, edge=None, norm=None, level=None, shift_scale=None, stats=None):
@@ -541,7 +547,8 @@ class GpuCodec:
         an error code.  scale / offset: float32 tensors of n entries on the codec's device, or None (1 / 0 for every read).  signed: the
         16-bit samples are int16 (True) or uint16.  norm (a Normalization; not with scale / offset): every read normalised by its own
         statistics instead (vbz_gpu_decompress_signal_norm_batch), its (shift, scale) left in norm_out (float32 [n, 2], or None)."""
-        assert dst.dtype in self._SIGNAL_TYPES and dst.dim() == 1 and dst.is_contiguous(), (dst.dtype, dst.shape)
+        assert dst.dtype in self._SIGNAL_TYPES, dst.dtype
+        table("dst", dst, dst.dtype, shape=(None,))
         n = int(src_off.numel())
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(dst.dtype, n, scale, offset, signed)
@@ -551,60 +558,34 @@ class GpuCodec:
     # (version: 0, 1, or _lib.VBZ_GPU_VERSION_POD5 -- the svb16 stream of POD5 rows, size 2 with zig-zag)
     def svb_compress(self, src, src_off, src_size, dst, dst_off, dst_cap, result, size=2, zigzag=True, version=0):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_svb_compress_batch(self.ctx, ctypes.byref(b), size, int(zigzag), version), "svb_compress_batch")
-        finally:
-            self._exit(cur)
+        self._call("svb_compress_batch", ctypes.byref(b), size, int(zigzag), version)
 
     def svb_decompress(self, src, src_off, src_size, dst, dst_off, dst_cap, result, size=2, zigzag=True, version=0):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_svb_decompress_batch(self.ctx, ctypes.byref(b), size, int(zigzag), version), "svb_decompress_batch")
-        finally:
-            self._exit(cur)
+        self._call("svb_decompress_batch", ctypes.byref(b), size, int(zigzag), version)
 
     def zstd_compress(self, src, src_off, src_size, dst, dst_off, dst_cap, result, key_bytes=None):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
-        kb = key_bytes.data_ptr() if key_bytes is not None else None
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_zstd_compress_batch(self.ctx, ctypes.byref(b), kb), "zstd_compress_batch")
-        finally:
-            self._exit(cur)
+        self._call("zstd_compress_batch", ctypes.byref(b), ptr(key_bytes))
 
     def zstd_decompress(self, src, src_off, src_size, dst, dst_off, dst_cap, result):
         b = self._batch(src, src_off, src_size, dst, dst_off, dst_cap, result)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_zstd_decompress_batch(self.ctx, ctypes.byref(b)), "zstd_decompress_batch")
-        finally:
-            self._exit(cur)
+        self._call("zstd_decompress_batch", ctypes.byref(b))
 
     def xxh64(self, src, src_off, src_size, out):
         """out[i] = XXH64 (seed 0) of src[src_off[i] : src_off[i] + src_size[i]]; out: an int64 tensor of n entries whose bits are
         the uint64 hashes (include/vbz_gpu.h: vbz_gpu_xxh64_batch)."""
         n = int(src_off.numel())
-        for t, dt in ((src_off, torch.int64), (src_size, torch.int32), (out, torch.int64)):
-            assert t.dtype == dt and t.is_contiguous() and t.device == self.device, (t.dtype, dt, t.device)
-        assert src.dtype == torch.uint8 and int(out.numel()) >= n
-        b = _lib.GpuBatch()
-        b.n_reads = n
-        b.src = src.data_ptr()
-        b.src_off = src_off.data_ptr()
-        b.src_size = src_size.data_ptr()
-        b.src_bytes = src.numel()
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_xxh64_batch(self.ctx, ctypes.byref(b), out.data_ptr()), "xxh64_batch")
-        finally:
-            self._exit(cur)
+        table("src_off", src_off, torch.int64, self.device)
+        table("src_size", src_size, torch.int32, self.device)
+        table("out", out, torch.int64, self.device, at_least=n)
+        assert src.dtype == torch.uint8
+        self._call("xxh64_batch", ctypes.byref(self._src_batch(src, src_off, src_size)), out.data_ptr())
 
     # -- dense arenas ------------------------------------------------------------------------------
     def _sync_total(self, off):
-        """off[-1] (an int64 table the codec's stream has written) on the host: one synchronisation"""
-        self._rc(self.L.vbz_gpu_synchronize(self.ctx), "synchronize")
+        """off[-1] (an int64 table the codec's stream has written) on the host: one synchronisation, between the two waits"""
+        self._call("synchronize")
         return int(off[-1].item())
 
     def pack(self, dst, dst_off, dst_cap, result, align=16, out=None):
@@ -614,51 +595,32 @@ class GpuCodec:
         the total and the arena is allocated (total + 64 bytes: the decoders' slack); with `out` (uint8) nothing synchronises, and an `out`
         smaller than the total is left untouched."""
         n = int(dst_off.numel())
-        for t, dt in ((dst_off, torch.int64), (dst_cap, torch.int32), (result, torch.int32)):
-            assert t.dtype == dt and t.is_contiguous() and t.device == self.device, (t.dtype, dt, t.device)
-        assert dst.dtype == torch.uint8 and int(dst_cap.numel()) == n and int(result.numel()) == n
+        table("dst_off", dst_off, torch.int64, self.device)
+        table("dst_cap", dst_cap, torch.int32, self.device, numel=n)
+        table("result", result, torch.int32, self.device, numel=n)
+        assert dst.dtype == torch.uint8
         b = _lib.GpuBatch()
-        b.n_reads = n
-        b.dst = dst.data_ptr()
-        b.dst_off = dst_off.data_ptr()
-        b.dst_cap = dst_cap.data_ptr()
-        b.dst_bytes = dst.numel()
-        b.result = result.data_ptr()
+        b.n_reads, b.dst, b.dst_off, b.dst_cap, b.dst_bytes, b.result = n, dst.data_ptr(), dst_off.data_ptr(), dst_cap.data_ptr(), dst.numel(), result.data_ptr()
         packed_off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         packed_size = torch.empty(n, dtype=torch.int32, device=self.device)
-        cur = self._enter()
-        try:
-            if out is None:
-                self._rc(self.L.vbz_gpu_pack_batch(self.ctx, ctypes.byref(b), align, None, 0, packed_off.data_ptr(), packed_size.data_ptr()), "pack_batch")
-                out = torch.empty(self._sync_total(packed_off) + 64, dtype=torch.uint8, device=self.device)
-            assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
-            self._rc(self.L.vbz_gpu_pack_batch(self.ctx, ctypes.byref(b), align, out.data_ptr(), out.numel(), packed_off.data_ptr(), packed_size.data_ptr()),
-                     "pack_batch")
-        finally:
-            self._exit(cur)
+        if out is None:
+            self._call("pack_batch", ctypes.byref(b), align, None, 0, packed_off.data_ptr(), packed_size.data_ptr())
+            out = torch.empty(self._sync_total(packed_off) + 64, dtype=torch.uint8, device=self.device)
+        table("out", out, torch.uint8, self.device)
+        self._call("pack_batch", ctypes.byref(b), align, out.data_ptr(), out.numel(), packed_off.data_ptr(), packed_size.data_ptr())
         return out, packed_off, packed_size
 
     def decompressed_sizes(self, src, src_off, src_size, opts, align=16):
         """n x vbz_decompressed_size of sized buffers and their output layout (include/vbz_gpu.h: vbz_gpu_decompressed_size_batch) ->
         (raw_size int32 [n], bits = the size or an error code; raw_off int64 [n + 1], raw_off[n] = the total)."""
         n = int(src_off.numel())
-        for t, dt in ((src_off, torch.int64), (src_size, torch.int32)):
-            assert t.dtype == dt and t.is_contiguous() and t.device == self.device, (t.dtype, dt, t.device)
-        assert src.dtype == torch.uint8 and int(src_size.numel()) == n
-        b = _lib.GpuBatch()
-        b.n_reads = n
-        b.src = src.data_ptr()
-        b.src_off = src_off.data_ptr()
-        b.src_size = src_size.data_ptr()
-        b.src_bytes = src.numel()
+        table("src_off", src_off, torch.int64, self.device)
+        table("src_size", src_size, torch.int32, self.device, numel=n)
+        assert src.dtype == torch.uint8
+        b = self._src_batch(src, src_off, src_size)
         raw_size = torch.empty(n, dtype=torch.int32, device=self.device)
         raw_off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_decompressed_size_batch(self.ctx, ctypes.byref(b), ctypes.byref(opts), align, raw_size.data_ptr(), raw_off.data_ptr()),
-                     "decompressed_size_batch")
-        finally:
-            self._exit(cur)
+        self._call("decompressed_size_batch", ctypes.byref(b), ctypes.byref(opts), align, raw_size.data_ptr(), raw_off.data_ptr())
         return raw_size, raw_off
 
     def decompress_packed(self, packed, packed_off, packed_size, opts, align=16):
@@ -668,11 +630,7 @@ class GpuCodec:
         n = int(packed_size.numel())
         src_off = packed_off[:n]
         raw_size, raw_off = self.decompressed_sizes(packed, src_off, packed_size, opts, align)
-        cur = self._enter()
-        try:
-            raw = torch.empty(self._sync_total(raw_off) + 64, dtype=torch.uint8, device=self.device)
-        finally:
-            self._exit(cur)
+        raw = torch.empty(self._sync_total(raw_off) + 64, dtype=torch.uint8, device=self.device)
         err = (raw_size < 0) & (raw_size >= _lib.VBZ_DEVICE_ERROR - (1 << 32))
         dst_cap = torch.where(err, torch.zeros_like(raw_size), raw_size)
         result = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -689,11 +647,7 @@ class GpuCodec:
         n = int(packed_size.numel())
         src_off = packed_off[:n]
         raw_size, raw_off = self.decompressed_sizes(packed, src_off, packed_size, opts, 16)   # (int16 bytes, 16-byte aligned)
-        cur = self._enter()
-        try:
-            total16 = self._sync_total(raw_off)
-        finally:
-            self._exit(cur)
+        total16 = self._sync_total(raw_off)
         elem = torch.empty(0, dtype=dtype).element_size()
         # an int16 slot of b bytes holds b / 2 samples: its typed slot, b / 2 * elem bytes, keeps the 16-byte alignment
         out = torch.empty(total16 // 2, dtype=dtype, device=self.device)
@@ -719,21 +673,15 @@ class GpuCodec:
         return ch
 
     def _chunk_layout_call(self, samples, ch, chunk_first, info=None, info_cap=0):
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_chunk_layout_batch(self.ctx, int(samples.numel()), samples.data_ptr(), ctypes.byref(ch), chunk_first.data_ptr(),
-                                                       info.data_ptr() if info is not None else None, int(info_cap)), "chunk_layout_batch")
-        finally:
-            self._exit(cur)
+        self._call("chunk_layout_batch", int(samples.numel()), samples.data_ptr(), ctypes.byref(ch), chunk_first.data_ptr(), ptr(info), int(info_cap))
 
     def _chunk_tables(self, samples, ch, info, also=None):
         """chunk_first (and chunk_info) of `samples` (int32 on the device, uint32 bits) under ch, with ONE synchronisation for the total;
         also: an int64 device scalar wanted on the host in the same synchronisation -> (chunk_first, chunk_info or None, also's value)"""
-        assert samples.dtype == torch.int32 and samples.is_contiguous() and samples.device == self.device, (samples.dtype, samples.device)
-        n = int(samples.numel())
+        n = int(table("samples", samples, torch.int32, self.device).numel())
         chunk_first = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         self._chunk_layout_call(samples, ch, chunk_first)
-        self._rc(self.L.vbz_gpu_synchronize(self.ctx), "synchronize")
+        self.synchronize()
         host = torch.stack([chunk_first[-1], also if also is not None else chunk_first[-1]]).cpu().tolist()
         chunk_info = None
         if info:
@@ -754,7 +702,8 @@ class GpuCodec:
 
     def _decode_chunks(self, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, ch, chunk_first, chunks, dtype, scale, offset,
                        signed, norm=None, norm_out=None, ranges=None):
-        assert dtype in self._SIGNAL_TYPES and chunks.dtype == dtype and chunks.is_contiguous(), (dtype, chunks.dtype)
+        assert dtype in self._SIGNAL_TYPES, dtype
+        table("chunks", chunks, dtype)
         n = int(src_off.numel())
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(dtype, n, scale, offset, signed)
@@ -807,15 +756,10 @@ class GpuCodec:
     # -- signal windows (include/vbz_gpu.h: vbz_gpu_windows) -------------------------------------------
     def _windows(self, n, window_first, start, window_len, pad):
         """(the C struct, the tables it points to) of n reads' windows: window_first int64 [n + 1] and start int32 [rows] on the device"""
-        assert window_first.dtype == torch.int64 and window_first.is_contiguous() and window_first.device == self.device, (window_first.dtype, window_first.device)
-        assert start.dtype == torch.int32 and start.is_contiguous() and start.device == self.device, (start.dtype, start.device)
-        assert int(window_first.numel()) == n + 1, (int(window_first.numel()), n)
+        table("window_first", window_first, torch.int64, self.device, numel=n + 1)
+        table("start", start, torch.int32, self.device)
         w = _lib.GpuWindows()
-        w.window_len = int(window_len)
-        w.pad = float(pad)
-        w.window_rows = int(start.numel())
-        w.window_first = window_first.data_ptr()
-        w.start = start.data_ptr()
+        w.window_len, w.pad, w.window_rows, w.window_first, w.start = int(window_len), float(pad), int(start.numel()), window_first.data_ptr(), start.data_ptr()
         return w, (window_first, start)
 
     def _decode_windows(self, n, src, src_off, src_size, dst_off, dst_cap, dst_bytes, result, opts, sized, window_first, start, window_len, pad, dtype,
@@ -823,8 +767,8 @@ class GpuCodec:
         assert dtype in self._SIGNAL_TYPES, dtype
         w, keep_w = self._windows(n, window_first, start, window_len, pad)
         g, keep_g = self._ranges(n, begin, end, stats)
-        if norm is not None and norm_out is None:
-            norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        if norm is not None:
+            norm_out = output("norm_out", norm_out, torch.float32, self.device, (n, 2))
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(dtype, n, scale, offset, signed)
         out = self._chunk_arena(int(start.numel()), window_len, dtype)
@@ -850,13 +794,7 @@ class GpuCodec:
         """(query float32 [n, N], hits int32 [n, R, words]) of a match or locate call (al: its GpuMatch or GpuLocate; R: its references or
         targets): the caller's, checked, or new ones.  words: 2 (cost, end), or 4 of the span calls (cost, end, start, 0)"""
         N, R = int(al.query_len), int(al.n_refs if isinstance(al, _lib.GpuMatch) else al.n_targets)
-        if query is None:
-            query = torch.empty((n, N), dtype=torch.float32, device=self.device)
-        if out is None:
-            out = torch.empty((n, R, words), dtype=torch.int32, device=self.device)
-        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, R, words), (out.dtype, out.shape)
-        return query, out
+        return output("query", query, torch.float32, self.device, (n, N)), output("out", out, torch.int32, self.device, (n, R, words))
 
     _match_arenas = _locate_arenas = _align_arenas   # (the names the two families' callers know)
 
@@ -864,14 +802,10 @@ class GpuCodec:
         """match() and locate(): rule a Match or a Locate, levels / levels_len its references or targets"""
         n = int(query.shape[0])
         al = rule.c_struct(levels, levels_len)
-        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
+        table("valid", valid, torch.int32, self.device, numel=n)
         query, out = self._align_arenas(n, al, query, out, 4 if span else 2)
-        name = ("match" if isinstance(rule, Match) else "locate") + ("_span_batch" if span else "_batch")
-        cur = self._enter()
-        try:
-            self._rc(getattr(self.L, "vbz_gpu_" + name)(self.ctx, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(al), out.data_ptr()), name)
-        finally:
-            self._exit(cur)
+        self._call(("match" if isinstance(rule, Match) else "locate") + ("_span_batch" if span else "_batch"), n, query.data_ptr(), valid.data_ptr(),
+                   ctypes.byref(al), out.data_ptr())
         return out
 
     def match(self, query, valid, ref, ref_len, match=None, out=None, span=False):
@@ -887,8 +821,8 @@ class GpuCodec:
         al = rule.c_struct(levels, levels_len)
         query, out = self._align_arenas(n, al, query, out, 4 if span else 2)
         g, keep_g = self._ranges(n, begin, end, stats)
-        if norm is not None and norm_out is None:
-            norm_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        if norm is not None:
+            norm_out = output("norm_out", norm_out, torch.float32, self.device, (n, 2))
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(torch.float32, n, scale, offset, signed)
         self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, chunks=query, m=m, ss=ss, g=g, r=r, mt=al, out=out,
@@ -914,7 +848,7 @@ class GpuCodec:
         result is per ROW, read_result (int32 [n_reads] on the device, optional) per read."""
         n = int(src_off.numel())
         assert int(row_samples.numel()) == n
-        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._signal_align(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
                                   match or Match(), ref, ref_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
@@ -944,7 +878,7 @@ class GpuCodec:
         hits, query, scale / offset / norm_out and begin / end are per READ; result is per ROW, read_result (optional) per read."""
         n = int(src_off.numel())
         assert int(row_samples.numel()) == n
-        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._signal_align(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
                                   locate or Locate(), target, target_len, scale, offset, signed, norm, norm_out, begin, end, stats, query, out, r=r, span=span)
@@ -989,18 +923,10 @@ class GpuCodec:
         int32 [n, 4] = (read, ref, begin, end) on the device (`out` when given): per read the reference of least cost, ties to the
         smallest index, empty verdicts and costs above max_cost (None: no bound) skipped; ref 0xFFFFFFFF and begin = end = 0 when none
         qualifies.  No synchronisation."""
-        assert spans.dtype == torch.int32 and spans.is_contiguous() and spans.device == self.device and spans.dim() == 3 and int(spans.shape[2]) == 4, (
-            spans.dtype, spans.shape)
+        table("spans", spans, torch.int32, self.device, shape=(None, None, 4))
         n, R = int(spans.shape[0]), int(spans.shape[1])
-        if out is None:
-            out = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (n, 4), (out.dtype, out.shape)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_match_best_batch(self.ctx, n, spans.data_ptr(), R, 0xFFFFFFFF if max_cost is None else int(max_cost), out.data_ptr()),
-                     "match_best_batch")
-        finally:
-            self._exit(cur)
+        out = output("out", out, torch.int32, self.device, (n, 4))
+        self._call("match_best_batch", n, spans.data_ptr(), R, 0xFFFFFFFF if max_cost is None else int(max_cost), out.data_ptr())
         return out
 
     def match_path(self, query, valid, ref, ref_len, pairs, max_width, match=None, hit=None, rows=None):
@@ -1010,27 +936,7 @@ class GpuCodec:
         rows), rows int32 [p, ref_stride, 2] = (begin, end) per reference row, {0, 0} behind the reference's end) on the device.  A
         pair's window is its samples [begin, end), at most max_width of them (a multiple of 8, 8 ... 65536; it sizes the scratch).  A
         pair outside the rules gets the empty verdict.  No synchronisation."""
-        n, p = int(query.shape[0]), int(pairs.shape[0])
-        mt = (match or Match(query_len=int(query.shape[1]))).c_struct(ref, ref_len)
-        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, int(mt.query_len)), (
-            query.dtype, query.shape)
-        assert valid is None or (valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n)
-        assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.device == self.device and tuple(pairs.shape) == (p, 4), (pairs.dtype, pairs.shape)
-        if hit is None:
-            hit = torch.empty((p, 4), dtype=torch.int32, device=self.device)
-        if rows is None:
-            rows = torch.empty((p, int(mt.ref_stride), 2), dtype=torch.int32, device=self.device)
-        assert hit.dtype == torch.int32 and hit.is_contiguous() and hit.device == self.device and tuple(hit.shape) == (p, 4), (hit.dtype, hit.shape)
-        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.device == self.device and tuple(rows.shape) == (p, int(mt.ref_stride), 2), (
-            rows.dtype, rows.shape)
-        path = _lib.GpuMatchPath(int(max_width), 0, 0)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_match_path_batch(self.ctx, p, n, query.data_ptr(), valid.data_ptr() if valid is not None else None, ctypes.byref(mt),
-                                                     pairs.data_ptr(), ctypes.byref(path), hit.data_ptr(), rows.data_ptr()), "match_path_batch")
-        finally:
-            self._exit(cur)
-        return hit, rows
+        return self._align_path(match or Match(query_len=int(query.shape[1])), query, valid, ref, ref_len, pairs, max_width, hit, rows)
 
     # -- signal locate: the warping path of chosen pairs, in target coordinates (include/vbz_gpu.h: vbz_gpu_locate_path_batch) ------
     def locate_path(self, query, valid, target, target_len, pairs, max_width, locate=None, hit=None, rows=None):
@@ -1040,43 +946,33 @@ class GpuCodec:
         the fused calls') -> (hit int32 [p, 4] = (cost, end, start, rows), rows int32 [p, query_len, 2] = the target levels [begin, end)
         of every sample of the read's prefix, {0, 0} behind it) on the device.  A pair's window is at most max_width levels (a multiple of
         8, 8 ... 65536; it sizes the scratch).  A pair outside the rules gets the empty verdict.  No synchronisation."""
-        n, p = int(query.shape[0]), int(pairs.shape[0])
-        lc = (locate or Locate(query_len=int(query.shape[1]))).c_struct(target, target_len)
-        N = int(lc.query_len)
-        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
-        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
-        assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.device == self.device and tuple(pairs.shape) == (p, 4), (pairs.dtype, pairs.shape)
-        if hit is None:
-            hit = torch.empty((p, 4), dtype=torch.int32, device=self.device)
-        if rows is None:
-            rows = torch.empty((p, N, 2), dtype=torch.int32, device=self.device)
-        assert hit.dtype == torch.int32 and hit.is_contiguous() and hit.device == self.device and tuple(hit.shape) == (p, 4), (hit.dtype, hit.shape)
-        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.device == self.device and tuple(rows.shape) == (p, N, 2), (rows.dtype, rows.shape)
+        return self._align_path(locate or Locate(query_len=int(query.shape[1])), query, valid, target, target_len, pairs, max_width, hit, rows)
+
+    def _align_path(self, rule, query, valid, levels, levels_len, pairs, max_width, hit, rows):
+        """match_path() and locate_path(): rule a Match or a Locate, levels / levels_len its references or targets.  The two differ in the
+        entry, in valid (a Match may leave it None, a Locate needs it) and in what rows has one row for: a Match every reference row
+        (ref_stride), a Locate every sample of the query (query_len)"""
+        n, p, matching = int(query.shape[0]), int(pairs.shape[0]), isinstance(rule, Match)
+        al = rule.c_struct(levels, levels_len)
+        N = int(al.query_len)
+        table("query", query, torch.float32, self.device, shape=(n, N))
+        table("valid", valid, torch.int32, self.device, numel=n, none=matching)
+        table("pairs", pairs, torch.int32, self.device, shape=(p, 4))
+        hit = output("hit", hit, torch.int32, self.device, (p, 4))
+        rows = output("rows", rows, torch.int32, self.device, (p, int(al.ref_stride) if matching else N, 2))
         path = _lib.GpuMatchPath(int(max_width), 0, 0)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_locate_path_batch(self.ctx, p, n, query.data_ptr(), valid.data_ptr(), ctypes.byref(lc), pairs.data_ptr(),
-                                                      ctypes.byref(path), hit.data_ptr(), rows.data_ptr()), "locate_path_batch")
-        finally:
-            self._exit(cur)
+        self._call("match_path_batch" if matching else "locate_path_batch", p, n, query.data_ptr(), ptr(valid), ctypes.byref(al), pairs.data_ptr(),
+                   ctypes.byref(path), hit.data_ptr(), rows.data_ptr())
         return hit, rows
 
     def query_valid(self, result, query_len, begin=None, end=None, out=None):
         """The valid[] that the fused match and locate calls derive for themselves (include/vbz_gpu.h: vbz_gpu_query_valid_batch): result
         int32 [n] on the device, what such a call left (T x 4 bytes or an error; over POD5 reads its read_result), begin / end the call's
         range tables -> int32 [n] = min(T', query_len), 0 for an error, on the device (`out` when given).  No synchronisation."""
-        assert result.dtype == torch.int32 and result.is_contiguous() and result.device == self.device, (result.dtype, result.device)
-        n = int(result.numel())
+        n = int(table("result", result, torch.int32, self.device).numel())
         g, keep = self._ranges(n, begin, end, None)
-        if out is None:
-            out = torch.empty(n, dtype=torch.int32, device=self.device)
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and int(out.numel()) == n, (out.dtype, out.shape)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_query_valid_batch(self.ctx, n, result.data_ptr(), ctypes.byref(g) if g is not None else None, int(query_len),
-                                                      out.data_ptr()), "query_valid_batch")
-        finally:
-            self._exit(cur)
+        out = output("out", out, torch.int32, self.device, n)
+        self._call("query_valid_batch", n, result.data_ptr(), ref(g), int(query_len), out.data_ptr())
         return out
 
     # -- event-space alignment (include/vbz_gpu.h: vbz_gpu_events_query_batch, vbz_gpu_locate_levels_batch) ------
@@ -1087,32 +983,17 @@ class GpuCodec:
         query_len] = their row numbers within the read; None with index=False) on the device.  result int32 [n] (optional): a read with
         an error verdict gets valid 0.  query, valid and index may be given.  No synchronisation."""
         n, N = int(event_first.numel()) - 1, int(query_len)
-        assert event_first.dtype == torch.int64 and event_first.is_contiguous() and event_first.device == self.device and n >= 0, (event_first.dtype, event_first.shape)
-        assert records.dtype == torch.int32 and records.is_contiguous() and records.device == self.device and records.dim() == 2 and int(records.shape[1]) == 4, (
-            records.dtype, records.shape)
-        assert result is None or (result.dtype == torch.int32 and result.is_contiguous() and result.device == self.device and int(result.numel()) == n)
-        if query is None:
-            query = torch.empty((n, N), dtype=torch.float32, device=self.device)
-        if valid is None:
-            valid = torch.empty(n, dtype=torch.int32, device=self.device)
-        if index is True:
-            index = torch.empty((n, N), dtype=torch.int32, device=self.device)
-        elif index is False:
-            index = None
-        assert query.dtype == torch.float32 and query.is_contiguous() and query.device == self.device and tuple(query.shape) == (n, N), (query.dtype, query.shape)
-        assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.device == self.device and int(valid.numel()) == n, (valid.dtype, valid.shape)
-        assert index is None or (index.dtype == torch.int32 and index.is_contiguous() and index.device == self.device and tuple(index.shape) == (n, N))
+        table("event_first", event_first, torch.int64, self.device, at_least=1)
+        table("records", records, torch.int32, self.device, shape=(None, 4))
+        table("result", result, torch.int32, self.device, numel=n, none=True)
+        query = output("query", query, torch.float32, self.device, (n, N))
+        valid = output("valid", valid, torch.int32, self.device, n)
+        index = output("index", index, torch.int32, self.device, (n, N), three_state=True)
         ev = _lib.GpuEvents()
-        ev.event_rows = int(records.shape[0])
-        ev.event_first = event_first.data_ptr()
+        ev.event_rows, ev.event_first = int(records.shape[0]), event_first.data_ptr()
         q = _lib.GpuEventsQuery(N, int(min_n), 0, 0)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_events_query_batch(self.ctx, n, result.data_ptr() if result is not None else None, ctypes.byref(ev),
-                                                       records.data_ptr() if int(records.shape[0]) else None, ctypes.byref(q), query.data_ptr(),
-                                                       valid.data_ptr(), index.data_ptr() if index is not None else None), "events_query_batch")
-        finally:
-            self._exit(cur)
+        self._call("events_query_batch", n, ptr(result), ctypes.byref(ev), records.data_ptr() if int(records.shape[0]) else None, ctypes.byref(q),
+                   query.data_ptr(), valid.data_ptr(), ptr(index))
         return query, valid, index
 
     def locate_levels(self, pairs, hit, rows, event_first, start, records, moments, max_width, index=None, n_levels=None, levels=None):
@@ -1128,23 +1009,13 @@ class GpuCodec:
         ev, keep = self._events(n, event_first, start)
         R = int(ev.event_rows)
         for name, t, shape in (("pairs", pairs, (p, 4)), ("hit", hit, (p, 4)), ("rows", rows, (p, N, 2)), ("records", records, (R, 4))):
-            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and tuple(t.shape) == shape, (name, t.dtype, t.shape)
-        assert moments.dtype == torch.int64 and moments.is_contiguous() and moments.device == self.device and tuple(moments.shape) == (R, 2), (moments.dtype, moments.shape)
-        assert index is None or (index.dtype == torch.int32 and index.is_contiguous() and index.device == self.device and tuple(index.shape) == (n, N))
-        if n_levels is None:
-            n_levels = torch.empty(p, dtype=torch.int32, device=self.device)
-        if levels is None:
-            levels = torch.empty((p, W, 8), dtype=torch.int32, device=self.device)
-        assert n_levels.dtype == torch.int32 and n_levels.is_contiguous() and n_levels.device == self.device and int(n_levels.numel()) == p
-        assert levels.dtype == torch.int32 and levels.is_contiguous() and levels.device == self.device and tuple(levels.shape) == (p, W, 8), (levels.dtype, levels.shape)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_locate_levels_batch(self.ctx, p, n, N, W, pairs.data_ptr(), hit.data_ptr(), rows.data_ptr(),
-                                                        index.data_ptr() if index is not None else None, ctypes.byref(ev),
-                                                        records.data_ptr() if R else None, moments.data_ptr() if R else None, n_levels.data_ptr(),
-                                                        levels.data_ptr()), "locate_levels_batch")
-        finally:
-            self._exit(cur)
+            table(name, t, torch.int32, self.device, shape=shape)
+        table("moments", moments, torch.int64, self.device, shape=(R, 2))
+        table("index", index, torch.int32, self.device, shape=(n, N), none=True)
+        n_levels = output("n_levels", n_levels, torch.int32, self.device, p)
+        levels = output("levels", levels, torch.int32, self.device, (p, W, 8))
+        self._call("locate_levels_batch", p, n, N, W, pairs.data_ptr(), hit.data_ptr(), rows.data_ptr(), ptr(index), ctypes.byref(ev),
+                   records.data_ptr() if R else None, moments.data_ptr() if R else None, n_levels.data_ptr(), levels.data_ptr())
         return n_levels, levels
 
     # -- pore model: target levels from bases, new constants along the path (include/vbz_gpu.h: vbz_gpu_squiggle_batch, vbz_gpu_levels_fit_batch)
@@ -1157,32 +1028,17 @@ class GpuCodec:
         target_len and masked may be given.  No synchronisation."""
         S, k, T = int(seq.shape[0]), int(k), int(target_stride)
         rows = 2 * S if both else S
-        assert seq.dtype == torch.uint8 and seq.is_contiguous() and seq.device == self.device and seq.dim() == 2, (seq.dtype, seq.shape)
-        assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.device == self.device and int(seq_len.numel()) == S, (seq_len.dtype, seq_len.shape)
-        assert model.dtype == torch.float32 and model.is_contiguous() and model.device == self.device and 1 <= k <= 9 and int(model.numel()) == 4 ** k, (
-            model.dtype, model.shape, k)
-        if target is None:
-            target = torch.empty((rows, T), dtype=torch.int8, device=self.device)
-        if target_len is None:
-            target_len = torch.empty(rows, dtype=torch.int32, device=self.device)
-        if masked is None:
-            masked = torch.empty(rows, dtype=torch.int32, device=self.device)
-        if level is True:
-            level = torch.empty((rows, T), dtype=torch.float32, device=self.device)
-        elif level is False:
-            level = None
-        assert target.dtype == torch.int8 and target.is_contiguous() and target.device == self.device and tuple(target.shape) == (rows, T), (target.dtype, target.shape)
-        for name, t in (("target_len", target_len), ("masked", masked)):
-            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and int(t.numel()) == rows, (name, t.dtype, t.shape)
-        assert level is None or (level.dtype == torch.float32 and level.is_contiguous() and level.device == self.device and tuple(level.shape) == (rows, T))
+        table("seq", seq, torch.uint8, self.device, shape=(None, None))
+        table("seq_len", seq_len, torch.int32, self.device, numel=S)
+        assert 1 <= k <= 9, k
+        table("model", model, torch.float32, self.device, numel=4 ** k)
+        target = output("target", target, torch.int8, self.device, (rows, T))
+        target_len = output("target_len", target_len, torch.int32, self.device, rows)
+        masked = output("masked", masked, torch.int32, self.device, rows)
+        level = output("level", level, torch.float32, self.device, (rows, T), three_state=True)
         sq = _lib.GpuSquiggle(k, S, int(seq.shape[1]), T, (_lib.SQUIGGLE_BOTH if both else 0) | (_lib.SQUIGGLE_REVERSED if reversed else 0), float(quant),
                               seq.data_ptr(), seq_len.data_ptr(), model.data_ptr())
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_squiggle_batch(self.ctx, ctypes.byref(sq), target.data_ptr(), target_len.data_ptr(), masked.data_ptr(),
-                                                   level.data_ptr() if level is not None else None), "squiggle_batch")
-        finally:
-            self._exit(cur)
+        self._call("squiggle_batch", ctypes.byref(sq), target.data_ptr(), target_len.data_ptr(), masked.data_ptr(), ptr(level))
         return target, target_len, masked, level
 
     def levels_fit(self, pairs, hit, n_levels, levels, target, target_len, n_reads, locate=None, min_samples=0, max_entries=0, prior=None, sums=False,
@@ -1198,45 +1054,25 @@ class GpuCodec:
         loc = (locate or Locate()).c_struct(target, target_len)
         assert target.device == self.device
         for name, t, shape in (("pairs", pairs, (p, 4)), ("hit", hit, (p, 4)), ("n_levels", n_levels, (p,)), ("levels", levels, (p, W, 8))):
-            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and tuple(t.shape) == shape, (name, t.dtype, t.shape)
-        assert prior is None or (prior.dtype == torch.float32 and prior.is_contiguous() and prior.device == self.device and tuple(prior.shape) == (n, 2))
-        if out is None:
-            out = torch.empty((p, 4), dtype=torch.int32, device=self.device)
-        if offset is None:
-            offset = torch.empty(p, dtype=torch.float32, device=self.device)
-        if scale is None:
-            scale = torch.empty(p, dtype=torch.float32, device=self.device)
-        if sums is True:
-            sums = torch.empty((p, 4), dtype=torch.int64, device=self.device)
-        elif sums is False:
-            sums = None
-        assert out.dtype == torch.int32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == (p, 4), (out.dtype, out.shape)
-        for name, t in (("offset", offset), ("scale", scale)):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) == p, (name, t.dtype, t.shape)
-        assert sums is None or (sums.dtype == torch.int64 and sums.is_contiguous() and sums.device == self.device and tuple(sums.shape) == (p, 4))
+            table(name, t, torch.int32, self.device, shape=shape)
+        table("prior", prior, torch.float32, self.device, shape=(n, 2), none=True)
+        out = output("out", out, torch.int32, self.device, (p, 4))
+        offset = output("offset", offset, torch.float32, self.device, p)
+        scale = output("scale", scale, torch.float32, self.device, p)
+        sums = output("sums", sums, torch.int64, self.device, (p, 4), three_state=True)
         fit = _lib.GpuLevelsFit(W, int(min_samples), int(max_entries), 0)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_levels_fit_batch(self.ctx, p, n, ctypes.byref(loc), pairs.data_ptr(), hit.data_ptr(), n_levels.data_ptr(),
-                                                     levels.data_ptr(), ctypes.byref(fit), prior.data_ptr() if prior is not None else None, out.data_ptr(),
-                                                     offset.data_ptr(), scale.data_ptr(), sums.data_ptr() if sums is not None else None), "levels_fit_batch")
-        finally:
-            self._exit(cur)
+        self._call("levels_fit_batch", p, n, ctypes.byref(loc), pairs.data_ptr(), hit.data_ptr(), n_levels.data_ptr(), levels.data_ptr(), ctypes.byref(fit),
+                   ptr(prior), out.data_ptr(), offset.data_ptr(), scale.data_ptr(), ptr(sums))
         return out, offset, scale, sums
 
     # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
     def _events(self, n, event_first, start):
         """(the C struct, the tables it points to) of n reads' events: event_first int64 [n + 1] on the device; start int32 [rows] on the
         device (uint32 bits), or any sequence of values 0 ... 0xFFFFFFFF"""
-        assert event_first.dtype == torch.int64 and event_first.is_contiguous() and event_first.device == self.device, (event_first.dtype, event_first.device)
-        assert int(event_first.numel()) == n + 1, (int(event_first.numel()), n)
-        if not (isinstance(start, torch.Tensor) and start.dtype == torch.int32):
-            w = torch.as_tensor(start, dtype=torch.int64).reshape(-1)
-            start = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
-        start = start.to(self.device).contiguous()
+        table("event_first", event_first, torch.int64, self.device, numel=n + 1)
+        start = wrap_u32(start).to(self.device).contiguous()
         ev = _lib.GpuEvents()
-        ev.event_rows = int(start.numel())
-        ev.event_first = event_first.data_ptr()
+        ev.event_rows, ev.event_first = int(start.numel()), event_first.data_ptr()
         ev.start = start.data_ptr() if int(start.numel()) else None
         return ev, (event_first, start)
 
@@ -1247,16 +1083,8 @@ class GpuCodec:
         g, keep_g = self._ranges(n, begin, end, stats)
         m, ss = self._norm_args(n, norm, norm_out, scale, offset) if norm is not None else (None, None)
         f = self._signal_format(torch.float32, n, scale, offset, signed)
-        if arena is None:
-            arena = torch.empty((rows, 4), dtype=torch.int32, device=self.device)
-        assert arena.dtype == torch.int32 and arena.is_contiguous() and arena.device == self.device and tuple(arena.shape) == (rows, 4), (arena.dtype, arena.shape)
-        if moments is True:
-            moments = torch.empty((rows, 2), dtype=torch.int64, device=self.device)
-        elif moments is False:
-            moments = None
-        if moments is not None:
-            assert moments.dtype == torch.int64 and moments.is_contiguous() and moments.device == self.device and tuple(moments.shape) == (rows, 2), (
-                moments.dtype, moments.shape)
+        arena = output("arena", arena, torch.int32, self.device, (rows, 4))
+        moments = output("moments", moments, torch.int64, self.device, (rows, 2), three_state=True)
         self._typed(src, src_off, src_size, None, dst_off, dst_cap, result, opts, sized, dst_bytes, f=f, m=m, ss=ss, g=g, r=r, ev=ev, out=arena, moments=moments)
         records = (arena[:, 0].view(torch.float32), arena[:, 1].view(torch.float32), arena[:, 2])
         return records if moments is None else records + (moments,)
@@ -1281,20 +1109,16 @@ class GpuCodec:
         every read, ascending from 0 (a tensor or a sequence of n_reads entries; the last read owns the rows up to the end)."""
         first = torch.as_tensor(read_first_row, dtype=torch.int64).reshape(-1).to(self.device)
         n_reads = int(first.numel())
-        table = torch.cat([first, torch.tensor([n_rows], dtype=torch.int64, device=self.device)]).to(torch.int32).contiguous()
-        if read_result is None:
-            read_result = torch.empty(n_reads, dtype=torch.int32, device=self.device)
-        assert read_result.dtype == torch.int32 and read_result.is_contiguous() and read_result.device == self.device and int(read_result.numel()) >= n_reads
+        first_row = torch.cat([first, torch.tensor([n_rows], dtype=torch.int64, device=self.device)]).to(torch.int32).contiguous()
+        read_result = output("read_result", read_result, torch.int32, self.device, n_reads, at_least=True)
         r = _lib.GpuPod5Reads()
-        r.n_reads = n_reads
-        r.first_row = table.data_ptr()
-        r.read_result = read_result.data_ptr()
-        return r, table, read_result
+        r.n_reads, r.first_row, r.read_result = n_reads, first_row.data_ptr(), read_result.data_ptr()
+        return r, first_row, read_result
 
     def _row_layout(self, row_samples):
         """the int16 layout that describes reads (or rows) of row_samples samples: (dst_off int64 [n + 1], dst_off[n] = the total; dst_cap int32 [n])"""
         n = int(row_samples.numel())
-        assert row_samples.dtype == torch.int32 and row_samples.is_contiguous() and row_samples.device == self.device
+        table("row_samples", row_samples, torch.int32, self.device)
         dst_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
         if n:
             dst_off[1:] = torch.cumsum(row_samples.to(torch.int64) * 2, 0)
@@ -1311,16 +1135,11 @@ class GpuCodec:
         assert int(row_samples.numel()) == n
         opts = pod5_options()
         ch = self._chunking(chunk_len, step, mode, end_align, pad)
-        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, None)
         g, keep = self._ranges(r.n_reads, begin, end, stats)
         read_samples = torch.empty(r.n_reads, dtype=torch.int32, device=self.device)
         dst_off, dst_cap = self._row_layout(row_samples)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_pod5_read_samples_batch(self.ctx, n, row_samples.data_ptr(), ctypes.byref(r), read_samples.data_ptr()),
-                     "pod5_read_samples_batch")
-        finally:
-            self._exit(cur)
+        self._call("pod5_read_samples_batch", n, row_samples.data_ptr(), ctypes.byref(r), read_samples.data_ptr())
         laid = read_samples if g is None else self.range_samples(read_samples, begin=keep[0], end=keep[1])
         chunk_first, chunk_info, host = self._chunk_tables(laid, ch, True, also=dst_off[-1])
         chunks = self._chunk_arena(host[0], chunk_len, dtype)
@@ -1339,7 +1158,7 @@ class GpuCodec:
         the read's concatenated signal; result is per ROW, read_result (int32 [n_reads] on the device, optional) per read."""
         n = int(src_off.numel())
         assert int(row_samples.numel()) == n
-        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._decode_windows(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
                                     window_first, start, window_len, pad, dtype, scale, offset, signed, norm, norm_out, begin, end, stats, r=r)
@@ -1351,7 +1170,7 @@ class GpuCodec:
         is per ROW, read_result (int32 [n_reads] on the device, optional) per read."""
         n = int(src_off.numel())
         assert int(row_samples.numel()) == n
-        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, read_result)
         dst_off, dst_cap = self._row_layout(row_samples)
         return self._signal_events(r.n_reads, src, src_off, src_size, dst_off[:n], dst_cap, int(dst_off[-1].item()), result, pod5_options(), False,
                                    event_first, start, scale, offset, signed, norm, norm_out, begin, end, stats, moments, arena, r=r)
@@ -1362,10 +1181,9 @@ class GpuCodec:
         begin / end: the statistics of that range of every read's concatenated signal (vbz_gpu_pod5_signal_norm_range_batch)."""
         n = int(src_off.numel())
         opts = pod5_options()
-        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, None)
         g, keep = self._ranges(r.n_reads, begin, end, stats)
-        if shift_scale is None:
-            shift_scale = torch.empty((r.n_reads, 2), dtype=torch.float32, device=self.device)
+        shift_scale = output("shift_scale", shift_scale, torch.float32, self.device, (r.n_reads, 2))
         m, ss = self._norm_args(r.n_reads, norm, shift_scale, None, None)
         dst_off, dst_cap = self._row_layout(row_samples)
         self._typed(src, src_off, src_size, None, dst_off[:n], dst_cap, result, opts, dst_bytes=dst_off[-1].item(), signed=signed, m=m, ss=ss, g=g, r=r)
@@ -1378,7 +1196,7 @@ class GpuCodec:
         per read; result is per ROW."""
         n = int(src_off.numel())
         opts = pod5_options()
-        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, None)
         g, keep = self._ranges(r.n_reads, begin, end, stats)
         t, out, shift_scale = self._trim_args(r.n_reads, trim, out, shift_scale)
         m, ss = self._norm_args(r.n_reads, norm, shift_scale, None, None)
@@ -1394,7 +1212,7 @@ class GpuCodec:
         concatenated signal; result is per ROW."""
         n = int(src_off.numel())
         assert int(row_samples.numel()) == n
-        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, read_result)
         g, keep = self._ranges(r.n_reads, begin, end, None)
         dst_off, dst_cap = self._row_layout(row_samples)
         if start_cap is None and start is None:   # (the bound: 2 + T / (radius + 1) per read, at most 2 n_reads + all samples / (radius + 1))
@@ -1412,7 +1230,7 @@ class GpuCodec:
         are per READ, the positions those of the read's concatenated signal; result is per ROW."""
         n = int(src_off.numel())
         assert int(row_samples.numel()) == n
-        r, table, read_result = self._pod5_reads(n, read_first_row, read_result)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, read_result)
         g, keep = self._ranges(r.n_reads, begin, end, stats)
         dst_off, dst_cap = self._row_layout(row_samples)
         if edge_cap is None and edge is None:   # (the bound per read is at most the bound of all samples plus one span a read)
@@ -1433,7 +1251,7 @@ class GpuCodec:
         opts = pod5_options()
         elem = torch.empty(0, dtype=dtype).element_size()
         lay = pod5_read_layout(torch.as_tensor(row_samples).cpu(), torch.as_tensor(read_first_row).cpu(), elem=elem, align=align, device=self.device)
-        r, table, read_result = self._pod5_reads(n, read_first_row, None)
+        r, first_row, read_result = self._pod5_reads(n, read_first_row, None)
         m, ss = self._norm_args(r.n_reads, norm, norm_out, None, None)
         f = self._signal_format(dtype, r.n_reads, None, None, signed)
         out = torch.empty(lay.total // elem + 32, dtype=dtype, device=self.device)
@@ -1443,26 +1261,14 @@ class GpuCodec:
     # -- synthetic workload ----------------------------------------------------------
     def synth_lengths(self, seed, first_read, n_reads):
         out = torch.empty(n_reads, dtype=torch.int32, device=self.device)
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_synth_lengths(self.ctx, seed, first_read, n_reads, out.data_ptr()), "synth_lengths")
-        finally:
-            self._exit(cur)
+        self._call("synth_lengths", seed, first_read, n_reads, out.data_ptr())
         return out
 
     def synth_signal(self, seed, first_read, dst, off, length):
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_synth_signal(self.ctx, seed, first_read, int(off.numel()), dst.data_ptr(), off.data_ptr(), length.data_ptr()), "synth_signal")
-        finally:
-            self._exit(cur)
+        self._call("synth_signal", seed, first_read, int(off.numel()), dst.data_ptr(), off.data_ptr(), length.data_ptr())
 
     def synth_u32(self, seed, first_read, dst, off, length):
-        cur = self._enter()
-        try:
-            self._rc(self.L.vbz_gpu_synth_u32(self.ctx, seed, first_read, int(off.numel()), dst.data_ptr(), off.data_ptr(), length.data_ptr()), "synth_u32")
-        finally:
-            self._exit(cur)
+        self._call("synth_u32", seed, first_read, int(off.numel()), dst.data_ptr(), off.data_ptr(), length.data_ptr())
 
     # -- profiling -------------------------------------------------------------------------------
     def profile(self, enable=True):
