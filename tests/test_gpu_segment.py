@@ -309,6 +309,23 @@ def test_pod5_read_with_a_failing_row_counts_none():
         assert call.refused == (set() if cap is None else {0, 2})
 
 
+@pytest.mark.parametrize("segmented", [0, 1])
+def test_pod5_rows_that_begin_inside_a_map_byte(segmented):
+    """One read of rows of 13, 2 049 and 5 samples -- a partial map byte, a tile seam, a tail: its second and third rows begin at 13 and
+    2 062 -- and beside it the same read with its middle row cut off, which gets no row; over the whole read and over a range that begins
+    and ends inside a row.  (test_pod5_reads has such seams; its failing read's rows run on the default path alone and begin at 1 000.)"""
+    c = codec(VBZ_HIP_SEGMENTED=segmented)
+    rows, first = pod5_rows(73, [[13, 2049, 5], [13, 2049, 5]])
+    frames = [PD.compress_row(x) for x in rows]
+    frames[4] = frames[4][: len(frames[4]) // 2]   # the middle row of read 1 cut off
+    for bg, en in ((None, None), ([11, 11], [2064, 2064])):
+        call = SegCall(c, frames, rows, first, S.DEFAULT, bg, en, failed={1})
+        assert call.call() == 0, c.L.vbz_gpu_last_error(c.ctx)
+        call.check(row_expect={4: 0xFFFFFFFF})
+        assert call.want_first[2] == call.want_first[1] and call.refused == set()
+        assert bg is not None or 13 in call.want_st[0].tolist()   # (the planted step on the seam at 13; the range begins too close to it)
+
+
 # ---- the cap on start[], the count-only call, failed reads -------------------------------------------------------------------------------------
 def cap_case(c):
     rng = np.random.default_rng(19)

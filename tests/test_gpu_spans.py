@@ -363,6 +363,29 @@ def test_pod5_read_with_a_failing_row_counts_none():
         assert call.refused == (set() if cap is None else {2})
 
 
+@pytest.mark.parametrize("segmented", [0, 1])
+def test_pod5_rows_that_begin_inside_a_map_byte(segmented):
+    """One read of rows of 13, 2 049 and 5 samples -- a partial map byte, a tile seam, a tail: its second and third rows begin at 13 and
+    2 062, inside a byte of the map -- and beside it the same read with its middle row cut off, which owns nothing.  With given constants
+    (the pass writes the verdicts) and behind a normalisation (it owes none), over the whole read and over a range that begins and ends
+    inside a row.  (test_pod5_reads has such seams with given constants, and behind a normalisation only with a range; its failing read's
+    rows run on the default path alone.)"""
+    c = codec(VBZ_HIP_SEGMENTED=segmented)
+    rows, first = pod5_rows([[13, 2049, 5], [13, 2049, 5]])
+    rng = np.random.default_rng(97)
+    noise = [S.noisy(rng, len(x), [(len(x) // 2, len(x) // 2 + 9)]) for x in rows]
+    for rws, kw, P in ((rows, dict(levels=[LEVEL] * 2), (S.ABOVE, 0, 1, 0, 0.0)), (noise, dict(norm=NORMS["med_mad"]), (S.ABOVE, 0, 2, 0, 6.0))):
+        frames = [PD.compress_row(x) for x in rws]
+        frames[4] = frames[4][: len(frames[4]) // 2]   # the middle row of read 1 cut off
+        for bg, en in ((None, None), ([11, 11], [2064, 2064])):
+            call = SpanCall(c, frames, rws, first, P, failed={1}, begin=bg, end=en, **kw)
+            assert call.call() == 0, c.L.vbz_gpu_last_error(c.ctx)
+            call.check(row_expect={4: 0xFFFFFFFF}, spans_min=2)
+            assert call.want_first[2] == call.want_first[1] and call.refused == set()
+            if rws is rows and bg is None:
+                assert call.want_ed[0].tolist() == [10, 16, 2063, 2067]   # (the run across the seam at 13, inside the map byte of 8 ... 15)
+
+
 # ---- the cap on edge[], the count-only call, failed reads -------------------------------------------------------------------------------------
 def cap_case(c):
     rng = np.random.default_rng(19)

@@ -216,10 +216,27 @@ def signal_segment(B):
     return B.done(_rows_of(first, start))
 
 
+SPANS = batch.Spans("above", 2, 2, 0, 1.0)
+
+
+def signal_spans_level(B):
+    """the caller's constants: no counting pass runs, the span pass writes the verdicts itself (thr = 330 + 40: the sine's crests)"""
+    level = torch.tensor([[330.0, 40.0]] * B.n, dtype=torch.float32, device=B.c.device).reshape(B.n, 2)
+    first, edge = B.c.signal_spans(*B.args(), B.doff, B.dcap, B.result, B.opts, SPANS, level=level)
+    return B.done(_rows_of(first, edge))
+
+
+def signal_spans_norm(B):
+    """a normalisation: the span pass runs behind the counting passes, which have left the verdicts"""
+    first, edge = B.c.signal_spans(*B.args(), B.doff, B.dcap, B.result, B.opts, SPANS, norm=MED_MAD)
+    return B.done(_rows_of(first, edge))
+
+
 CONSUMERS = {
     "decompress_signal": (2, decompress_signal), "decompress_chunks": (2, decompress_chunks), "decompress_windows": (2, decompress_windows),
     "signal_events": (2, signal_events), "signal_norm": (2, signal_norm), "signal_trim": (2, signal_trim), "signal_segment": (2, signal_segment),
     "decompress_signal with norm=": (2, decompress_signal_norm),
+    "signal_spans with level=": (2, signal_spans_level), "signal_spans with norm=": (2, signal_spans_norm),
 }
 
 

@@ -1585,7 +1585,7 @@ __global__ __launch_bounds__(WG) void svb16_encode_kernel(ReadBatch b, uint32_t*
 // whether the stream is exactly as long as its key bits announce.  stage / wsum: the kernel's LDS.  This is svb16_decode_kernel's tile
 // loop for the kernels over reads; that kernel keeps its own text, which as a call of this function compiles to other registers.
 // PREFIX (the trim pass): only the row's first min(stop, count) samples are walked, and the return says nothing about the stream's length.
-template <class Store, bool PREFIX = false>
+template <bool PREFIX = false, class Store>
 __device__ __forceinline__ bool svb16_decode_row(const uint8_t* in, uint32_t in_size, uint32_t count, const Store& st, uint8_t* stage, uint32_t* wsum,
                                                  uint32_t stop = 0)
 {
@@ -2156,9 +2156,63 @@ __global__ __launch_bounds__(WG) void svb16_decode_rows_kernel(ReadBatch b, Pod5
     if (tid == 0) b.result[r] = good ? count * st.BYTES : E_STREAM;
 }
 
-// A counting pass over reads: one workgroup per read walks its rows in turn -- the delta chain and the data position restart with every
-// row, the bins and the below-counts carry on -- and selects with the read's histogram in LDS.  verdicts != 0 (the first pass of the
-// statistics alone, which has no store pass): every row's result is written here, the int16 decode's.
+// ---- a POD5 read of several rows on one workgroup: what every kernel that walks a read's rows in turn is made of ---------------------------
+// The rows [first, end) of a read through one sink, by the read's workgroup: the delta chain and the data position restart with every
+// row, begin_row() places each in the read's signal and the sink's state carries on.  verdicts: every row's result is written here, the
+// int16 decode's.  PREFIX (the trim pass): only the read's first `stop` samples are walked, up to the row that holds the last of them.
+template <bool PREFIX = false, class Store>
+__device__ __forceinline__ void svb16_walk_rows(const ReadBatch& b, const Pod5Reads& pr, uint32_t first, uint32_t end, Store& st, const Svb16Lds& lds,
+                                                bool verdicts, uint32_t stop = 0)
+{
+    for (uint32_t r = first; r < end; ++r) {
+        if constexpr (PREFIX)
+            if (pr.rows[r].s0 >= stop) break;
+        uint32_t in_size = 0, count = 0, verdict;
+        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {   // (a closed gate, a failed stage, a refused size, an empty row)
+            if (verdicts) read_closed(b, r, verdict);
+            continue;
+        }
+        const uint32_t s0 = pr.rows[r].s0;
+        st.begin_row(s0);   // (put() gets positions in the row)
+        const bool good = svb16_decode_row<PREFIX>(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum, PREFIX ? stop - s0 : 0u);
+        if (verdicts && threadIdx.x == 0) b.result[r] = good ? count * 2u : E_STREAM;
+    }
+}
+
+// The rows' verdicts of a read that is not walked, a row a thread: what svb16_row_open says of the row, or -- where that is no error and
+// `instead` is one (E_OOM: the read's map does not fit) -- `instead`
+__device__ __forceinline__ void svb16_rows_closed(const ReadBatch& b, uint32_t first, uint32_t end, uint32_t instead)
+{
+    for (uint32_t r = first + threadIdx.x; r < end; r += WG) {
+        uint32_t in_size, count, verdict;
+        (void)svb16_row_open(b, r, &in_size, &count, &verdict);
+        if (verdict != GATE_SKIP) b.result[r] = instead == 0 || verdict >= E_FIRST ? verdict : instead;
+    }
+}
+
+// whether a row of the read has an error verdict in result[] (a pass behind the counting passes, which left them), by the read's workgroup
+__device__ __forceinline__ bool svb16_rows_failed(const ReadBatch& b, uint32_t first, uint32_t end)
+{
+    int failed = 0;
+    for (uint32_t r = first + threadIdx.x; r < end; r += WG) failed |= b.result[r] >= E_FIRST ? 1 : 0;
+    return __syncthreads_or(failed) != 0;
+}
+
+// the samples [*rb, *re) of read k of T samples that a ranged call takes (the plan has clamped them), else all
+__device__ __forceinline__ void pod5_read_range(const ReadBatch& b, const Pod5Reads& pr, uint32_t k, uint32_t T, uint32_t* rb, uint32_t* re)
+{
+    *rb = 0;
+    *re = T;
+    if (b.sig.ranged()) {
+        const uint2 g = pr.range[k];
+        *rb = g.x;
+        *re = g.y;
+    }
+}
+
+// A counting pass over reads: one workgroup per read walks its rows in turn -- the bins and the below-counts carry on from row to row --
+// and selects with the read's histogram in LDS.  verdicts != 0 (the first pass of the statistics alone, which has no store pass): every
+// row's result is written here.
 template <int OUT>
 __device__ __forceinline__ void svb16_count_reads(const ReadBatch& b, const Pod5Reads& pr, uint32_t verdicts)
 {
@@ -2166,28 +2220,13 @@ __device__ __forceinline__ void svb16_count_reads(const ReadBatch& b, const Pod5
 
     if (*pr.bad) return;
     const uint32_t k = blockIdx.x;
-    const int tid = threadIdx.x;
     const uint32_t first = pr.first_row[k], end = pr.first_row[k + 1];
     if (b.sig.norm.st[k].phase == NORM_DONE) {   // finished (no sample, or failed): no row of it has samples to walk
-        if (!verdicts) return;
-        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) {
-            uint32_t in_size, count, verdict;
-            (void)svb16_row_open(b, r, &in_size, &count, &verdict);
-            if (verdict != GATE_SKIP) b.result[r] = verdict;
-        }
+        if (verdicts) svb16_rows_closed(b, first, end, 0u);
         return;
     }
     DecStore<2, OUT> st = dec_store<2, OUT>(nullptr, nullptr, &b, k, pr.reads[k].T);
-    for (uint32_t r = first; r < end; ++r) {
-        uint32_t in_size = 0, count = 0, verdict;
-        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-            if (verdicts) read_closed(b, r, verdict);
-            continue;
-        }
-        st.begin_row(pr.rows[r].s0);   // (put() gets positions in the row)
-        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
-        if (verdicts && tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
-    }
+    svb16_walk_rows(b, pr, first, end, st, lds, verdicts != 0);
     st.done();
 }
 __global__ __launch_bounds__(WG) void svb16_count_reads_kernel(ReadBatch b, Pod5Reads pr, uint32_t verdicts)
@@ -2199,50 +2238,234 @@ __global__ __launch_bounds__(WG) void svb16_count_reads_range_kernel(ReadBatch b
     svb16_count_reads<SIG_COUNT | SIG_RANGE>(b, pr, verdicts);
 }
 
-// ---- the trim pass (OUT = SIG_TRIM; vbz_kernels.h TrimOut), behind the last counting pass ------------------------------------------------
-// The counting passes walked every stream to its end and left the verdicts, so this pass owes none: it reads result[] and walks only the
-// prefix [0, t0 + nW W) of every read that has no error -- whatever its NormRead::phase.  Every begin entry has one writer: the read's
-// workgroup (one wavefront of it), or on the large-read path trim_select_kernel's.
-// Read r of a trim launch, by the whole workgroup: false when there is nothing to decode -- the read is another launch group's (nothing is
-// written), it has an error verdict (begin 0) or no window (begin min(t0, T)); else *k is its state.
-__device__ __forceinline__ bool trim_read_open(const ReadBatch& b, const TrimOut& tr, uint32_t r, TrimK* k)
+// ---- the signal passes behind the decoder: trim, spans, segmentation (DESIGN.md 4.27 has the table of walks and passes) -------------------
+// TrimStore, SpanStore and SegmentStore store no sample and ride the decoder's walks.  Every stream form has ONE walk below, a function
+// template over a pass policy, and every kernel is a thin instantiation of it: svb_pass_read (one workgroup per int16 read),
+// svb_pass_segment (a segment of a large read: trim and spans), svb16_pass_row (a POD5 row as a read), svb16_pass_reads (a POD5 read of
+// several rows).  A policy is a plain struct around the pass's *Out, a kernel argument by value, and says only what differs, in constants
+// and inlined members, so that no pass pays for another's option: owes() -- whether this launch writes the int16 decode's verdicts;
+// closed() -- a read whose stream was not opened; admit() / admit_rows() / admit_segment() -- whether an opened read (a POD5 read's rows,
+// a segment) is walked, and its state, else what it gets instead is written; end() -- where the walk ends; sink<SHARED>() -- the sink
+// from that state (SHARED: rows may begin inside a map byte); WAVES -- the one-workgroup int16 kernel's second launch bound (0: none).
+// The sinks' done() is svb_decode_range's to call on the int16 walks and the walk's on the POD5 ones (SpanStore's is empty).  Every begin
+// entry and every byte of a map has one writer: the read's workgroup, or on the large-read path the lanes that own whole bytes (spans)
+// and trim_select_kernel (trim).
+
+// begin 0: a read with an error verdict (entry: trim_state's)
+__device__ __forceinline__ void trim_zero(const ReadBatch& b, const TrimOut& tr, uint32_t r)
 {
-    const uint32_t g = read_gate(b, r, true);
-    if (g == GATE_SKIP) return false;
-    if (g || b.result[r] >= E_FIRST) {
-        if (threadIdx.x == 0) tr.begin[b.sig.norm.map ? b.sig.norm.map[r] : r] = 0;
-        return false;
-    }
-    *k = trim_state(b, tr, r, b.dst_cap[r] >> 1);
-    if (k->nW == 0) {
-        if (threadIdx.x == 0) *k->out = k->t0 < k->T ? k->t0 : k->T;
-        return false;
-    }
-    return true;
+    if (threadIdx.x == 0) tr.begin[b.sig.norm.map ? b.sig.norm.map[r] : r] = 0;
+}
+// the state of read r of T samples that has no error; a read with no window gets begin = min(t0, T) and false
+__device__ __forceinline__ bool trim_windows(const ReadBatch& b, const TrimOut& tr, uint32_t r, uint32_t T, TrimK* k)
+{
+    *k = trim_state(b, tr, r, T);
+    if (k->nW != 0) return true;
+    if (threadIdx.x == 0) *k->out = k->t0 < k->T ? k->t0 : k->T;
+    return false;
 }
 
-// one workgroup per read: svb_decode_kernel's walk, left behind the prefix
-template <bool ZZ, bool I16ZZ>
-__global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_trim_kernel(ReadBatch b, TrimOut tr)
+// The trim pass (OUT = SIG_TRIM), behind the last counting pass: it reads result[] and walks only the prefix [0, t0 + nW W) of every read
+// that has no error -- whatever its NormRead::phase.
+struct TrimPass
+{
+    using Read = TrimK;
+    static constexpr int WAVES = VBZ_SVBDEC_WAVES;
+    static constexpr bool PREFIX = true, ZEROED_MAP = false, SEG_VERDICT = false;
+    TrimOut out;
+    __device__ static constexpr bool owes() { return false; }
+    __device__ __forceinline__ void closed(const ReadBatch& b, uint32_t r, uint32_t verdict) const
+    {
+        if (verdict != GATE_SKIP) trim_zero(b, out, r);   // (another launch group's read: nothing is written)
+    }
+    __device__ __forceinline__ bool admit(const ReadBatch& b, uint32_t r, uint32_t T, TrimK* k) const
+    {
+        if (b.result[r] < E_FIRST) return trim_windows(b, out, r, T, k);
+        trim_zero(b, out, r);
+        return false;
+    }
+    // (a read with a failing row gets 0)
+    __device__ __forceinline__ bool admit_rows(const ReadBatch& b, const Pod5Reads&, uint32_t q, uint32_t first, uint32_t end, const Pod5Read& rd,
+                                               TrimK* k) const
+    {
+        if (!svb16_rows_failed(b, first, end)) return trim_windows(b, out, q, rd.T, k);
+        trim_zero(b, out, q);
+        return false;
+    }
+    // (trim_select_kernel writes the read's 0 or min(t0, T), and scans the words the segments add to the read's slab)
+    template <bool SELF>
+    __device__ __forceinline__ bool admit_segment(const ReadBatch& b, uint32_t r, uint32_t, bool open, const SvbRead& rd, uint32_t, uint64_t,
+                                                  TrimK* k) const
+    {
+        if (!open || b.result[r] >= E_FIRST) return false;
+        *k = trim_state(b, out, r, rd.count);
+        k->slab = b.sig.norm.slab + (size_t)r * NORM_SLAB;
+        return true;
+    }
+    __device__ static uint32_t end(const TrimK& k, uint32_t) { return k.end; }
+    template <bool SHARED>
+    __device__ __forceinline__ TrimStore sink(const ReadBatch&, uint32_t, const TrimK& k) const { return TrimStore(k); }
+};
+
+// The two passes that leave a bit per position in the read's map (vbz_kernels.h ReadMaps): what they share.  Unlike the trim they walk
+// every read to its end -- every byte of the map gets its writer.
+struct MapRead
+{
+    uint32_t i, rb, re;   // the read's entry of the call's tables; its samples [rb, re)
+};
+template <class P>
+struct MapPass
+{
+    using Read = MapRead;
+    static constexpr bool PREFIX = false, SEG_VERDICT = true;
+    __device__ __forceinline__ const P& self() const { return static_cast<const P&>(*this); }
+    __device__ __forceinline__ void closed(const ReadBatch& b, uint32_t r, uint32_t verdict) const
+    {
+        if (self().owes()) read_closed(b, r, verdict);
+    }
+    __device__ __forceinline__ bool admit(const ReadBatch& b, uint32_t r, uint32_t T, MapRead* w) const
+    {
+        if (!self().owes() && b.result[r] >= E_FIRST) return false;
+        w->i = self().out.entry(r);
+        if (!self().out.fits(w->i, T)) {
+            if (threadIdx.x == 0) b.result[r] = E_OOM;
+            return false;
+        }
+        sample_range(b.sig, r, T, &w->rb, &w->re);
+        return true;
+    }
+    // (a read the plan failed has its rows' gates closed: every row has or gets that verdict; a read with a failing row is not walked)
+    __device__ __forceinline__ bool admit_rows(const ReadBatch& b, const Pod5Reads& pr, uint32_t k, uint32_t first, uint32_t end, const Pod5Read& rd,
+                                               MapRead* w) const
+    {
+        const bool failed = (rd.flags & POD5_READ_FAIL) != 0, fits = self().out.fits(k, rd.T);
+        if (failed || !fits) {
+            if (self().owes() || !fits) svb16_rows_closed(b, first, end, failed ? 0u : E_OOM);
+            return false;
+        }
+        if (!self().owes() && svb16_rows_failed(b, first, end)) return false;
+        w->i = k;
+        pod5_read_range(b, pr, k, rd.T, &w->rb, &w->re);
+        return true;
+    }
+    // The read's verdict is svb_seg_decode_kernel's MODE 0: the scan launch's, or (SELF) written by the read's first workgroup from the
+    // data bytes its segments announce (total).
+    template <bool SELF>
+    __device__ __forceinline__ bool admit_segment(const ReadBatch& b, uint32_t r, uint32_t sg, bool open, const SvbRead& rd, uint32_t verdict,
+                                                  uint64_t total, MapRead* w) const
+    {
+        w->i = self().out.entry(r);
+        const bool fits = !open || self().out.fits(w->i, rd.count);
+        if (sg == 0 && threadIdx.x == 0) {   // the read's verdict: one writer
+            uint32_t res0;
+            if (!fits) b.result[r] = E_OOM;
+            else if (SELF && svb_seg_read_result(open, rd, verdict, total, 2u, &res0)) b.result[r] = res0;
+        }
+        if (!open || !fits) return false;
+        if (SELF ? total != (uint64_t)rd.dataBytes : b.result[r] >= E_FIRST) return false;   // malformed: these sums say so, or the scan (or a counting pass) did
+        sample_range(b.sig, r, rd.count, &w->rb, &w->re);
+        return true;
+    }
+    __device__ static uint32_t end(const MapRead&, uint32_t T) { return T; }
+};
+
+// The span pass (svb_store.h SpanStore), in two settings.  Behind the counting passes of a call with a normalisation (verdicts == 0) it
+// owes no verdict and walks the reads that have none.  With the caller's constants no counting pass runs, and it writes them itself.
+// A segment of the large-read path begins at a multiple of 16 384 samples, so its lanes own whole bytes of the map and store them plainly.
+struct SpanPass : MapPass<SpanPass>
+{
+    static constexpr int WAVES = VBZ_SVBDEC_WAVES;
+    static constexpr bool ZEROED_MAP = true;
+    SpanOut out;
+    uint32_t verdicts;
+    __device__ bool owes() const { return verdicts != 0; }
+    template <bool SHARED>
+    __device__ __forceinline__ SpanStore<SHARED> sink(const ReadBatch& b, uint32_t r, const MapRead& w) const
+    {
+        return SpanStore<SHARED>(span_state(b, out, r, w.i, w.rb, w.re));
+    }
+    // a row may begin inside a map byte, so the read's workgroup zeroes the read's map and the lanes OR their bits in
+    __device__ __forceinline__ void zero_map(const SpanStore<true>& st, uint32_t T) const
+    {
+        uint32_t* const m = reinterpret_cast<uint32_t*>(st.sk.map);
+        const uint32_t words = (((T + 7u) >> 3) + 3u) >> 2;   // (map_off is a scan of sizes rounded up to 4: the words lie inside the read's map)
+        for (uint32_t j = threadIdx.x; j < words; j += WG) m[j] = 0;
+        __syncthreads();
+    }
+};
+
+// The segmentation pass (svb_store.h SegmentStore): the sink needs each sample's neighbourhood, and a workgroup that walks the whole
+// signal in order has it in LDS -- one workgroup per read on every path.  No seam lies between the rows of a POD5 read.
+struct SegmentPass : MapPass<SegmentPass>
+{
+    static constexpr int WAVES = 0;
+    static constexpr bool ZEROED_MAP = false;
+    SegmentOut out;
+    __device__ static constexpr bool owes() { return true; }
+    template <bool SHARED>
+    __device__ __forceinline__ SegmentStore sink(const ReadBatch& b, uint32_t, const MapRead& w) const
+    {
+        return SegmentStore(out, w.i, w.rb, w.re - w.rb, b.sig.bias);
+    }
+};
+
+// one workgroup per int16 read: svb_decode_kernel's walk
+template <bool ZZ, bool I16ZZ, class Pass>
+__device__ __forceinline__ void svb_pass_read(const ReadBatch& b, const Pass& p)
 {
     const SvbDecLds<2, I16ZZ> lds;
 
     const uint32_t r = blockIdx.x;
-    TrimK k;
-    if (!trim_read_open(b, tr, r, &k)) return;
-    const uint32_t in_size = b.src_size[r], count = k.T, keyLen = (count + 3u) >> 2;
-    const uint8_t* in = b.src + b.src_off[r];
+    SvbRead rd;
+    uint32_t verdict;
+    if (!svb_read_open<2, I16ZZ>(b, r, &rd, &verdict)) return p.closed(b, r, verdict);
+    typename Pass::Read w;
+    if (!p.admit(b, r, rd.count, &w)) return;
     uint64_t pos = 0;
     uint32_t run = 0;
-    const TrimStore st(k);
-    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(in, in + keyLen, in_size - keyLen, count, 0, k.end, pos, run, st, lds.stage, lds.wsum);
+    const auto st = p.template sink<false>(b, r, w);
+    const bool good = svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, rd.count, 0, Pass::end(w, rd.count), pos, run, st,
+                                                        lds.stage, lds.wsum);
+    if (p.owes() && threadIdx.x == 0) b.result[r] = (!good || pos != rd.dataBytes) ? E_STREAM : rd.count * 2u;
+}
+template <bool ZZ, bool I16ZZ, class Pass>
+__global__ __launch_bounds__(WG, Pass::WAVES) void svb_pass_kernel(ReadBatch b, Pass p) { svb_pass_read<ZZ, I16ZZ>(b, p); }
+
+// Where a segment of a large read begins in the read's data bytes (pos; total: the data bytes all its segments announce, SELF only) and
+// where its delta chain stands (run), as svb_seg_decode_kernel's passes left them: the SELF sums of seg_val / seg_run in front of this
+// segment, else the scan launches' seg_pos[] / seg_run[].  For the pass kernels only: svb_seg_decode_kernel states the same in its own
+// text and is left as it is -- its instantiations' registers move with where its read is opened and its sums are taken
+// (profiles/HISTORY.md, "svb stage: one statement of how a read is opened").
+struct SegAt
+{
+    uint64_t pos = 0, total = 0;
+    uint32_t run = 0;
+};
+template <bool ZZ, bool SELF>
+__device__ __forceinline__ SegAt seg_positions(const uint32_t* seg_first, const uint32_t* seg_val, const uint64_t* seg_pos, const uint32_t* seg_run,
+                                               uint32_t r, uint64_t* sums_s)
+{
+    SegAt at;
+    if (SELF) {
+        seg_sums(seg_val, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, at.pos, at.total);
+        if (ZZ) {
+            uint64_t run = 0, all;
+            seg_sums(seg_run, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, run, all);
+            at.run = (uint32_t)run;
+        }
+    } else {
+        at.pos = seg_pos[blockIdx.x];
+        at.run = ZZ ? seg_run[blockIdx.x] : 0u;
+    }
+    return at;
 }
 
-// The large-read path: svb_seg_decode_kernel's MODE 0 at the positions its passes left (seg_val / seg_pos / seg_run as that kernel reads
-// them).  A segment that starts at or behind the prefix's end returns at once; the others add their words to the read's slab.
-template <bool ZZ, bool I16ZZ, bool SELF>
-__global__ __launch_bounds__(WG) void svb_seg_trim_kernel(ReadBatch b, const uint32_t* seg_first, const uint32_t* seg_val, const uint64_t* seg_pos,
-                                                          const uint32_t* seg_run, TrimOut tr)
+// One segment of a large read: svb_seg_decode_kernel's MODE 0 at the positions its passes left, every segment that begins in front of
+// the walk's end (the trim: most segments of a long read lie behind the prefix and return at once; the others add their words to the
+// read's slab).
+template <bool ZZ, bool I16ZZ, bool SELF, class Pass>
+__device__ __forceinline__ void svb_pass_segment(const ReadBatch& b, const uint32_t* seg_first, const uint32_t* seg_val, const uint64_t* seg_pos,
+                                                 const uint32_t* seg_run, const Pass& p)
 {
     constexpr uint32_t SEG = WG * Vpl<2>::value * SEG_TILES;
     const SvbDecLds<2, I16ZZ> lds;
@@ -2251,25 +2474,36 @@ __global__ __launch_bounds__(WG) void svb_seg_trim_kernel(ReadBatch b, const uin
     if (!seg_locate(seg_first, b.n_reads, blockIdx.x, r, sg)) return;
     SvbRead rd;
     uint32_t verdict;
-    if (!svb_read_open<2, I16ZZ>(b, r, &rd, &verdict) || b.result[r] >= E_FIRST) return;   // (trim_select_kernel writes the read's 0)
-    const uint32_t count = rd.count, first = sg * SEG;
-    TrimK k = trim_state(b, tr, r, count);
-    if (first >= k.end) return;
-    k.slab = b.sig.norm.slab + (size_t)r * NORM_SLAB;
-    uint64_t pos = 0;
-    uint32_t run = 0;
-    if (SELF) {
-        uint64_t total, self_run = 0;
-        seg_sums(seg_val, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, pos, total);
-        if (ZZ) seg_sums(seg_run, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_run, total);
-        run = (uint32_t)self_run;
-    } else {
-        pos = seg_pos[blockIdx.x];
-        run = ZZ ? seg_run[blockIdx.x] : 0u;
+    const bool open = svb_read_open<2, I16ZZ>(b, r, &rd, &verdict);
+    SegAt at;
+    if constexpr (Pass::SEG_VERDICT) at = seg_positions<ZZ, SELF>(seg_first, seg_val, seg_pos, seg_run, r, sums_s);   // (in front of every return: the read's verdict takes the total)
+    typename Pass::Read w;
+    if (!p.template admit_segment<SELF>(b, r, sg, open, rd, verdict, at.total, &w)) return;
+    const uint32_t first = sg * SEG, lim = Pass::end(w, rd.count);
+    if (first >= lim) return;
+    if constexpr (!Pass::SEG_VERDICT) at = seg_positions<ZZ, SELF>(seg_first, seg_val, seg_pos, seg_run, r, sums_s);   // (behind them: no sums for a segment that walks nothing)
+    const auto st = p.template sink<false>(b, r, w);
+    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, rd.count, first, lim - first > SEG ? first + SEG : lim, at.pos,
+                                            at.run, st, lds.stage, lds.wsum);
+}
+template <bool ZZ, bool I16ZZ, bool SELF, class Pass>
+__global__ __launch_bounds__(WG) void svb_seg_pass_kernel(ReadBatch b, const uint32_t* seg_first, const uint32_t* seg_val, const uint64_t* seg_pos,
+                                                          const uint32_t* seg_run, Pass p)
+{
+    svb_pass_segment<ZZ, I16ZZ, SELF>(b, seg_first, seg_val, seg_pos, seg_run, p);
+}
+
+// Read r of a trim launch's select, by the whole workgroup: false when there is nothing to scan -- the read is another launch group's
+// (nothing is written), it has an error verdict (begin 0) or no window (begin min(t0, T)); else *k is its state.
+__device__ __forceinline__ bool trim_read_open(const ReadBatch& b, const TrimOut& tr, uint32_t r, TrimK* k)
+{
+    const uint32_t g = read_gate(b, r, true);
+    if (g == GATE_SKIP) return false;
+    if (g || b.result[r] >= E_FIRST) {
+        trim_zero(b, tr, r);
+        return false;
     }
-    const uint32_t end = k.end - first > SEG ? first + SEG : k.end;
-    const TrimStore st(k);
-    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, first, end, pos, run, st, lds.stage, lds.wsum);
+    return trim_windows(b, tr, r, b.dst_cap[r] >> 1, k);
 }
 
 // one workgroup per read of the large-read path: the words the segments added to the read's slab (zeroed again) -> the scan
@@ -2289,309 +2523,44 @@ __global__ __launch_bounds__(WG) void trim_select_kernel(ReadBatch b, TrimOut tr
 }
 
 // a POD5 row as a read of its own
-__global__ __launch_bounds__(WG) void svb16_trim_kernel(ReadBatch b, TrimOut tr)
-{
-    const Svb16Lds lds;
-
-    const uint32_t r = blockIdx.x;
-    TrimK k;
-    if (!trim_read_open(b, tr, r, &k)) return;
-    const TrimStore st(k);
-    (void)svb16_decode_row<TrimStore, true>(b.src + b.src_off[r], b.src_size[r], k.T, st, lds.stage, lds.wsum, k.end);
-    st.done();
-}
-
-// POD5 reads of several rows: one workgroup per READ walks its rows as svb16_count_reads does, up to the row that holds the prefix's last
-// sample.  A read with a failing row gets 0; a bad first_row leaves begin alone.
-__global__ __launch_bounds__(WG) void svb16_trim_reads_kernel(ReadBatch b, Pod5Reads pr, TrimOut tr)
-{
-    const Svb16Lds lds;
-
-    if (*pr.bad) return;
-    const uint32_t q = blockIdx.x;
-    const uint32_t first = pr.first_row[q], end = pr.first_row[q + 1];
-    int failed = 0;
-    for (uint32_t r = first + threadIdx.x; r < end; r += WG) failed |= b.result[r] >= E_FIRST ? 1 : 0;
-    if (__syncthreads_or(failed)) {
-        if (threadIdx.x == 0) tr.begin[q] = 0;
-        return;
-    }
-    const TrimK k = trim_state(b, tr, q, pr.reads[q].T);
-    if (k.nW == 0) {
-        if (threadIdx.x == 0) *k.out = k.t0 < k.T ? k.t0 : k.T;
-        return;
-    }
-    TrimStore st(k);
-    for (uint32_t r = first; r < end; ++r) {
-        const uint32_t s0 = pr.rows[r].s0;
-        if (s0 >= k.end) break;
-        uint32_t in_size = 0, count = 0, verdict;
-        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) continue;   // (an empty row)
-        st.begin_row(s0);   // (put() gets positions in the row)
-        (void)svb16_decode_row<TrimStore, true>(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum, k.end - s0);
-    }
-    st.done();
-}
-
-// whether read i's map of ceil(T / 8) bytes lies inside the call's scratch: no byte of a map is written before this has passed
-__device__ __forceinline__ bool map_fits(const uint64_t* map_off, uint64_t map_cap, uint32_t i, uint32_t T)
-{
-    const uint64_t a = map_off[i], z = map_off[i + 1];
-    return z <= map_cap && a <= z && (uint64_t)((T + 7u) >> 3) <= z - a;   // (a map of ceil(T / 8) bytes: no byte is written outside it)
-}
-
-// ---- the span pass (vbz_kernels.h SpanOut; svb_store.h SpanStore), beside the trim pass and shaped like it ---------------------------------
-// Unlike the trim it walks every read to its end (every byte of the map gets its writer), and it runs in two settings.  Behind the
-// counting passes of a call with a normalisation (verdicts == 0) it owes no verdict: it reads result[] and walks the reads that have
-// none.  With the caller's constants no counting pass runs, and the pass writes the int16 decode's verdicts itself (verdicts != 0), as the
-// segmentation pass does.  The read's entry of the call's tables: segmentation's (rmap).
-__device__ __forceinline__ uint32_t span_entry(const SpanOut& so, uint32_t r) { return so.rmap ? so.rmap[r] : r; }
-
-// one workgroup per read: svb_decode_kernel's walk
-template <bool ZZ, bool I16ZZ>
-__global__ __launch_bounds__(WG, VBZ_SVBDEC_WAVES) void svb_span_kernel(ReadBatch b, SpanOut so, uint32_t verdicts)
-{
-    const SvbDecLds<2, I16ZZ> lds;
-
-    const uint32_t r = blockIdx.x;
-    const int tid = threadIdx.x;
-    SvbRead rd;
-    uint32_t verdict;
-    if (!svb_read_open<2, I16ZZ>(b, r, &rd, &verdict)) {
-        if (verdicts) read_closed(b, r, verdict);
-        return;
-    }
-    if (!verdicts && b.result[r] >= E_FIRST) return;
-    const uint32_t count = rd.count, i = span_entry(so, r);
-    if (!map_fits(so.map_off, so.map_cap, i, count)) {
-        if (tid == 0) b.result[r] = E_OOM;
-        return;
-    }
-    uint32_t rb, re;
-    sample_range(b.sig, r, count, &rb, &re);
-    uint64_t pos = 0;
-    uint32_t run = 0;
-    const SpanStore<false> st(span_state(b, so, r, i, rb, re));
-    const bool good = svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, 0, count, pos, run, st, lds.stage, lds.wsum);
-    if (verdicts && tid == 0) b.result[r] = (!good || pos != rd.dataBytes) ? E_STREAM : count * 2u;
-}
-
-// The large-read path: svb_seg_decode_kernel's MODE 0 with the span sink, every segment of the read, no slab -- a segment begins at a
-// multiple of 16 384 samples, so its lanes own whole bytes of the map and store them plainly.  The verdict is that kernel's: the scan
-// launch's, or (SELF) written by the read's first workgroup from the announced lengths.
-template <bool ZZ, bool I16ZZ, bool SELF>
-__global__ __launch_bounds__(WG) void svb_seg_span_kernel(ReadBatch b, const uint32_t* seg_first, const uint32_t* seg_val, const uint64_t* seg_pos,
-                                                          const uint32_t* seg_run, SpanOut so)
-{
-    constexpr uint32_t SEG = WG * Vpl<2>::value * SEG_TILES;
-    const SvbDecLds<2, I16ZZ> lds;
-    __shared__ uint64_t sums_s[8];
-    uint32_t r, sg;
-    if (!seg_locate(seg_first, b.n_reads, blockIdx.x, r, sg)) return;
-    const int tid = threadIdx.x;
-    SvbRead rd;
-    uint32_t verdict;
-    const bool open = svb_read_open<2, I16ZZ>(b, r, &rd, &verdict);
-    uint64_t self_pos = 0, self_total = 0, self_run = 0;
-    if (SELF) {
-        seg_sums(seg_val, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_pos, self_total);
-        if (ZZ) {
-            uint64_t dummy;
-            seg_sums(seg_run, seg_first[r], blockIdx.x, seg_first[r + 1], sums_s, self_run, dummy);
-        }
-    }
-    const uint32_t i = span_entry(so, r);
-    const bool fits = !open || map_fits(so.map_off, so.map_cap, i, rd.count);
-    if (sg == 0 && tid == 0) {   // the read's verdict: one writer
-        uint32_t res0;
-        if (!fits) b.result[r] = E_OOM;
-        else if (SELF && svb_seg_read_result(open, rd, verdict, self_total, 2u, &res0)) b.result[r] = res0;
-    }
-    if (!open || !fits) return;
-    if (SELF) {
-        if (self_total != (uint64_t)rd.dataBytes) return;   // the stream is malformed
-    } else if (b.result[r] >= E_FIRST) return;              // the scan found it malformed (or a counting pass did)
-    const uint32_t count = rd.count, first = sg * SEG;
-    if (first >= count) return;
-    const uint32_t end = count - first > SEG ? first + SEG : count;
-    uint32_t rb, re;
-    sample_range(b.sig, r, count, &rb, &re);
-    uint64_t pos = SELF ? self_pos : seg_pos[blockIdx.x];
-    uint32_t run = ZZ ? (SELF ? (uint32_t)self_run : seg_run[blockIdx.x]) : 0u;
-    const SpanStore<false> st(span_state(b, so, r, i, rb, re));
-    (void)svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, first, end, pos, run, st, lds.stage, lds.wsum);
-}
-
-// a POD5 row as a read of its own
-__global__ __launch_bounds__(WG) void svb16_span_kernel(ReadBatch b, SpanOut so, uint32_t verdicts)
+template <class Pass>
+__device__ __forceinline__ void svb16_pass_row(const ReadBatch& b, const Pass& p)
 {
     const Svb16Lds lds;
 
     const uint32_t r = blockIdx.x;
     uint32_t in_size = 0, count = 0, verdict;
-    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-        if (verdicts) read_closed(b, r, verdict);
-        return;
-    }
-    if (!verdicts && b.result[r] >= E_FIRST) return;
-    const uint32_t i = span_entry(so, r);
-    if (!map_fits(so.map_off, so.map_cap, i, count)) {
-        if (threadIdx.x == 0) b.result[r] = E_OOM;
-        return;
-    }
-    uint32_t rb, re;
-    sample_range(b.sig, r, count, &rb, &re);
-    const SpanStore<false> st(span_state(b, so, r, i, rb, re));
-    const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
-    if (verdicts && threadIdx.x == 0) b.result[r] = good ? count * 2u : E_STREAM;
+    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) return p.closed(b, r, verdict);
+    typename Pass::Read w;
+    if (!p.admit(b, r, count, &w)) return;
+    const auto st = p.template sink<false>(b, r, w);
+    const bool good = svb16_decode_row<Pass::PREFIX>(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum, Pass::end(w, count));
+    st.done();
+    if (p.owes() && threadIdx.x == 0) b.result[r] = good ? count * 2u : E_STREAM;
 }
+template <class Pass>
+__global__ __launch_bounds__(WG) void svb16_pass_kernel(ReadBatch b, Pass p) { svb16_pass_row(b, p); }
 
-// POD5 reads of several rows: one workgroup per READ walks its rows in turn, as svb16_trim_reads_kernel does (verdicts != 0: and writes
-// their verdicts, as svb16_segment_reads_kernel does).  A row may begin inside a map byte, so the workgroup zeroes the read's map and ORs
-// its bits in (SpanStore<true>).  A read with a failing row is not walked; a bad first_row leaves everything alone.
-__global__ __launch_bounds__(WG) void svb16_span_reads_kernel(ReadBatch b, Pod5Reads pr, SpanOut so, uint32_t verdicts)
+// POD5 reads of several rows: one workgroup per READ walks its rows in turn, as svb16_count_reads does (and writes their verdicts where
+// the pass owes them).  A bad first_row leaves everything alone.
+template <class Pass>
+__device__ __forceinline__ void svb16_pass_reads(const ReadBatch& b, const Pod5Reads& pr, const Pass& p)
 {
     const Svb16Lds lds;
 
     if (*pr.bad) return;
     const uint32_t k = blockIdx.x;
-    const int tid = threadIdx.x;
     const uint32_t first = pr.first_row[k], end = pr.first_row[k + 1];
     const Pod5Read rd = pr.reads[k];
-    const bool failed = (rd.flags & POD5_READ_FAIL) != 0;   // (the plan has closed its rows' gates: every row has or gets that verdict)
-    const bool fits = map_fits(so.map_off, so.map_cap, k, rd.T);
-    if (failed || !fits) {
-        if (!verdicts && fits) return;
-        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) {
-            uint32_t in_size, count, verdict;
-            (void)svb16_row_open(b, r, &in_size, &count, &verdict);
-            if (verdict != GATE_SKIP) b.result[r] = failed || verdict >= E_FIRST ? verdict : E_OOM;
-        }
-        return;
-    }
-    if (!verdicts) {
-        int bad = 0;
-        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) bad |= b.result[r] >= E_FIRST ? 1 : 0;
-        if (__syncthreads_or(bad)) return;
-    }
-    uint32_t rb = 0, re = rd.T;
-    if (b.sig.ranged()) {
-        const uint2 g = pr.range[k];
-        rb = g.x;
-        re = g.y;
-    }
-    SpanStore<true> st(span_state(b, so, k, k, rb, re));
-    {
-        uint32_t* const w = reinterpret_cast<uint32_t*>(st.sk.map);
-        const uint32_t words = (((rd.T + 7u) >> 3) + 3u) >> 2;   // (map_off is a scan of sizes rounded up to 4: the words lie inside the read's map)
-        for (uint32_t j = (uint32_t)tid; j < words; j += WG) w[j] = 0;
-        __syncthreads();
-    }
-    for (uint32_t r = first; r < end; ++r) {
-        uint32_t in_size = 0, count = 0, verdict;
-        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-            if (verdicts) read_closed(b, r, verdict);
-            continue;
-        }
-        st.begin_row(pr.rows[r].s0);   // (put() gets positions in the row)
-        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
-        if (verdicts && tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
-    }
-}
-
-// ---- the segmentation pass (vbz_kernels.h SegmentOut; svb_store.h SegmentStore) -----------------------------------------------------------
-// Kernels of their own, one workgroup per read on every path: the sink needs each sample's neighbourhood, and a workgroup that walks the
-// whole signal in order has it in LDS.  The verdicts are written here, as the int16 decode writes them (there is no counting pass in front).
-// The read's entry of the call's tables, and whether its map lies inside the scratch
-__device__ __forceinline__ uint32_t segment_entry(const SegmentOut& so, uint32_t r) { return so.rmap ? so.rmap[r] : r; }
-__device__ __forceinline__ bool segment_fits(const SegmentOut& so, uint32_t i, uint32_t T) { return map_fits(so.map_off, so.map_cap, i, T); }
-
-// svb_decode_kernel's walk of an int16 read
-template <bool ZZ, bool I16ZZ>
-__global__ __launch_bounds__(WG) void svb_segment_kernel(ReadBatch b, SegmentOut so)
-{
-    const SvbDecLds<2, I16ZZ> lds;
-
-    const uint32_t r = blockIdx.x;
-    const int tid = threadIdx.x;
-    SvbRead rd;
-    uint32_t verdict;
-    if (!svb_read_open<2, I16ZZ>(b, r, &rd, &verdict)) return read_closed(b, r, verdict);
-    const uint32_t count = rd.count;
-    const uint32_t i = segment_entry(so, r);
-    if (!segment_fits(so, i, count)) {
-        if (tid == 0) b.result[r] = E_OOM;
-        return;
-    }
-    uint32_t rb, re;
-    sample_range(b.sig, r, count, &rb, &re);
-    uint64_t pos = 0;
-    uint32_t run = 0;
-    const SegmentStore st(so, i, rb, re - rb, b.sig.bias);
-    const bool good = svb_decode_range<2, ZZ, I16ZZ, 0>(rd.in, rd.in + rd.keyLen, rd.dataBytes, count, 0, count, pos, run, st, lds.stage, lds.wsum);
-    if (tid == 0) b.result[r] = (!good || pos != rd.dataBytes) ? E_STREAM : count * 2u;
-}
-
-// a POD5 row as a read of its own
-__global__ __launch_bounds__(WG) void svb16_segment_kernel(ReadBatch b, SegmentOut so)
-{
-    const Svb16Lds lds;
-
-    const uint32_t r = blockIdx.x;
-    uint32_t in_size = 0, count = 0, verdict;
-    if (!svb16_row_open(b, r, &in_size, &count, &verdict)) return read_closed(b, r, verdict);
-    const uint32_t i = segment_entry(so, r);
-    if (!segment_fits(so, i, count)) {
-        if (threadIdx.x == 0) b.result[r] = E_OOM;
-        return;
-    }
-    uint32_t rb, re;
-    sample_range(b.sig, r, count, &rb, &re);
-    const SegmentStore st(so, i, rb, re - rb, b.sig.bias);
-    const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
-    st.done();
-    if (threadIdx.x == 0) b.result[r] = good ? count * 2u : E_STREAM;
-}
-
-// POD5 reads of several rows: one workgroup per READ walks its rows in turn, as svb16_count_reads does, and writes their verdicts.  No seam
-// lies between rows: begin_row() places each in the read's signal.  A read the plan failed has its rows' gates closed.
-__global__ __launch_bounds__(WG) void svb16_segment_reads_kernel(ReadBatch b, Pod5Reads pr, SegmentOut so)
-{
-    const Svb16Lds lds;
-
-    if (*pr.bad) return;
-    const uint32_t k = blockIdx.x;
-    const int tid = threadIdx.x;
-    const uint32_t first = pr.first_row[k], end = pr.first_row[k + 1];
-    const Pod5Read rd = pr.reads[k];
-    const bool failed = (rd.flags & POD5_READ_FAIL) != 0;   // (the plan has closed its rows' gates: every row gets that verdict)
-    if (failed || !segment_fits(so, k, rd.T)) {
-        for (uint32_t r = first + (uint32_t)tid; r < end; r += WG) {
-            uint32_t in_size, count, verdict;
-            (void)svb16_row_open(b, r, &in_size, &count, &verdict);
-            if (verdict != GATE_SKIP) b.result[r] = failed || verdict >= E_FIRST ? verdict : E_OOM;
-        }
-        return;
-    }
-    uint32_t rb = 0, re = rd.T;
-    if (b.sig.ranged()) {
-        const uint2 g = pr.range[k];
-        rb = g.x;
-        re = g.y;
-    }
-    SegmentStore st(so, k, rb, re - rb, b.sig.bias);
-    for (uint32_t r = first; r < end; ++r) {
-        uint32_t in_size = 0, count = 0, verdict;
-        if (!svb16_row_open(b, r, &in_size, &count, &verdict)) {
-            read_closed(b, r, verdict);
-            continue;
-        }
-        st.begin_row(pr.rows[r].s0);   // (put() gets positions in the row)
-        const bool good = svb16_decode_row(b.src + b.src_off[r], in_size, count, st, lds.stage, lds.wsum);
-        if (tid == 0) b.result[r] = good ? count * 2u : E_STREAM;
-    }
+    typename Pass::Read w;
+    if (!p.admit_rows(b, pr, k, first, end, rd, &w)) return;
+    auto st = p.template sink<true>(b, k, w);
+    if constexpr (Pass::ZEROED_MAP) p.zero_map(st, rd.T);
+    svb16_walk_rows<Pass::PREFIX>(b, pr, first, end, st, lds, p.owes(), Pass::end(w, rd.T));
     st.done();
 }
+template <class Pass>
+__global__ __launch_bounds__(WG) void svb16_pass_reads_kernel(ReadBatch b, Pod5Reads pr, Pass p) { svb16_pass_reads(b, pr, p); }
 
 // read_result[k]: the code of the read's first failing row, else T * elem
 __global__ __launch_bounds__(WG) void pod5_read_results_kernel(ReadBatch b, Pod5Reads pr, uint32_t elem)
@@ -2614,11 +2583,12 @@ hipError_t launch_norm_init(const ReadBatch& b, bool zigzag, hipStream_t s)
     return hipGetLastError();
 }
 
-template <typename K>
-hipError_t launch1(K kernel, const ReadBatch& b, hipStream_t s)
+// one workgroup per read of the batch (more: the kernel's arguments behind it, a pass policy)
+template <typename K, typename... More>
+hipError_t launch1(K kernel, const ReadBatch& b, hipStream_t s, const More&... more)
 {
     if (b.n_reads == 0) return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3(b.n_reads), dim3(WG), 0, s, b);
+    hipLaunchKernelGGL(kernel, dim3(b.n_reads), dim3(WG), 0, s, b, more...);
     return hipGetLastError();
 }
 
@@ -2682,23 +2652,56 @@ hipError_t svb_dispatch_count(const ReadBatch& b, F&& f)
     return b.sig.ranged_stats() ? f(Int<SIG_COUNT | SIG_RANGE>{}) : f(Int<SIG_COUNT>{});
 }
 
-// The pre-passes of a normalising decode (b.sig.norm.st; int16 samples only), in front of the store: init(), `lead` (launches the counting
-// passes need behind the init: the segmented decoder's position passes), then norm_passes() x count(), every pass ending in its select.
-// *store = false: b.sig.type == SIG_NONE, the statistics are all that runs.  Without b.sig.norm.st: lead() alone.
-// slab: b.sig.norm.slab must be set (the segments add their counts there) or must not be (one workgroup per read counts in LDS).
-// trim(): the trim pass behind the last counting pass (a call without TrimOut: nothing).
-template <class Init, class Lead, class Count, class Trim>
-hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, Init init, Lead lead, Count count, Trim trim, bool* store)
+// ---- the signal pass of a decode launch: the span pass, else the trim pass, else none ---------------------------------------------------
+// what every decode launcher refuses of them: a trim without statistics, a span call with a typed output, both together
+bool pass_refused(const ReadBatch& b, const TrimOut* trim, const SpanOut* span)
 {
-    *store = true;
-    if (!b.sig.norm.st) return lead();
+    return (trim && !b.sig.norm.st) || (span && (b.sig.type != SIG_NONE || trim));
+}
+
+// launch(policy) launches the stream form's pass kernel.  verdicts: the span pass runs alone and owes them (SpanPass)
+template <class Launch>
+hipError_t launch_pass(const TrimOut* trim, const SpanOut* span, uint32_t verdicts, Launch&& launch)
+{
+    if (span) return launch(SpanPass{ {}, *span, verdicts });
+    if (trim) return launch(TrimPass{ *trim });
+    return hipSuccess;
+}
+// a form's pass kernel with the policy p: one workgroup per int16 read, per POD5 row (svb16_pass_kernel through launch1), per POD5 read
+template <class P>
+hipError_t svb_pass_launch(const ReadBatch& b, bool zigzag, const P& p, hipStream_t s)
+{
+    return zigzag ? launch1(svb_pass_kernel<true, true, P>, b, s, p) : launch1(svb_pass_kernel<false, false, P>, b, s, p);
+}
+template <class P>
+hipError_t svb16_pass_reads_launch(const ReadBatch& b, const Pod5Reads& pr, const P& p, hipStream_t s)
+{
+    if (pr.n_reads) hipLaunchKernelGGL(svb16_pass_reads_kernel<P>, dim3(pr.n_reads), dim3(WG), 0, s, b, pr, p);
+    return hipGetLastError();
+}
+
+// The launches of a decode in front of its store.  With a normalisation (b.sig.norm.st; int16 samples only): init(), `lead` (launches
+// the counting passes need behind the init: the segmented decoder's position passes), then norm_passes() x count(), every pass ending in
+// its select, and behind the last one the call's signal pass (launch_pass through `pass`).  Without: lead(), and behind it the span pass
+// of a call that brings its own constants -- all that runs for such a call, verdicts included.
+// *store: whether the store pass follows -- not for the statistics alone (b.sig.type == SIG_NONE), and not for a span call.
+// slab: b.sig.norm.slab must be set (the segments add their counts there) or must not be (one workgroup per read counts in LDS).
+template <class Init, class Lead, class Count, class Pass>
+hipError_t norm_prepasses(const ReadBatch& b, int integer_size, bool slab, const TrimOut* trim, const SpanOut* span, Init init, Lead lead, Count count,
+                          Pass pass, bool* store)
+{
+    *store = !span;
+    if (!b.sig.norm.st) {
+        const hipError_t e = lead();
+        return e == hipSuccess ? launch_pass(nullptr, span, 1u, pass) : e;
+    }
     if (integer_size != 2 || slab != (b.sig.norm.slab != nullptr)) return hipErrorInvalidValue;
-    *store = b.sig.type != SIG_NONE && b.n_reads != 0;
+    *store = !span && b.sig.type != SIG_NONE && b.n_reads != 0;
     if (b.n_reads == 0) return hipSuccess;
     hipError_t e = init();
     if (e == hipSuccess) e = lead();
     for (uint32_t p = 0; e == hipSuccess && p < norm_passes(b.sig.norm.method); ++p) e = count();
-    if (e == hipSuccess) e = trim();
+    if (e == hipSuccess) e = launch_pass(trim, span, 0u, pass);
     return e;
 }
 
@@ -2709,13 +2712,6 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
 {
     const dim3 segs(max_segs), reads(b.n_reads), t(WG);
     const bool self = max_segs <= self_max;
-    auto span_pass = [&] {   // the span pass at the storing pass's positions (E == 2, OUT == SIG_NONE: launch_svb_decode_seg has looked)
-        if constexpr (E == 2) {
-            if (self) hipLaunchKernelGGL((svb_seg_span_kernel<Z, I, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *span);
-            else hipLaunchKernelGGL((svb_seg_span_kernel<Z, I, false>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *span);
-        }
-        return hipGetLastError();
-    };
     auto mode0 = [&](auto o) {
         if (self) hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, true, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
         else hipLaunchKernelGGL((svb_seg_decode_kernel<E, Z, I, 0, false, o()>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run);
@@ -2723,7 +2719,7 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
     };
     bool store;
     const hipError_t e = norm_prepasses(
-        b, E, true,
+        b, E, true, trim, span,
         [&] {
             (void)hipMemsetAsync(b.sig.norm.slab, 0, 4ull * NORM_SLAB * b.n_reads, s);
             return launch_norm_init(b, Z, s);
@@ -2750,20 +2746,19 @@ hipError_t svb_decode_seg_sequence(const ReadBatch& b, const uint32_t* seg_first
             }
             return hipGetLastError();
         },
-        [&] {   // the trim pass at the same positions, behind it the scan launch (a span call: the span pass)
+        [&](auto p) {   // the pass at the same positions (E == 2, OUT == SIG_NONE: launch_svb_decode_seg has looked); behind a trim's segments its scan launch
+            using P = decltype(p);
             if constexpr (E == 2) {
-                if (span) return span_pass();
-                if (!trim) return hipSuccess;
-                if (self) hipLaunchKernelGGL((svb_seg_trim_kernel<Z, I, true>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *trim);
-                else hipLaunchKernelGGL((svb_seg_trim_kernel<Z, I, false>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, *trim);
-                hipLaunchKernelGGL(trim_select_kernel, reads, t, 0, s, b, *trim);
+                if (self) hipLaunchKernelGGL((svb_seg_pass_kernel<Z, I, true, P>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, p);
+                else hipLaunchKernelGGL((svb_seg_pass_kernel<Z, I, false, P>), segs, t, 0, s, b, seg_first, seg_val, seg_pos, seg_run, p);
+                if constexpr (std::is_same<P, TrimPass>::value) hipLaunchKernelGGL(trim_select_kernel, reads, t, 0, s, b, p.out);
             }
             return hipGetLastError();
         },
         &store);
-    if (span) return e == hipSuccess && !b.sig.norm.st ? span_pass() : e;   // (the caller's constants: the pass is all that runs behind the position passes)
-    return e == hipSuccess && store ? mode0(Int<OUT>{}) : e;   // (no store: the statistics only)
+    return e == hipSuccess && store ? mode0(Int<OUT>{}) : e;   // (no store: the statistics only, or a span call)
 }
+
 
 }  // namespace
 
@@ -2799,31 +2794,17 @@ hipError_t launch_svb_encode(const ReadBatch& b, int integer_size, bool zigzag, 
 
 hipError_t launch_svb_decode(const ReadBatch& b, int integer_size, bool zigzag, bool half, hipStream_t s, const TrimOut* trim, const SpanOut* span)
 {
-    if (trim && (half || !b.sig.norm.st)) return hipErrorInvalidValue;
-    if (span && (half || integer_size != 2 || b.sig.type != SIG_NONE || trim)) return hipErrorInvalidValue;
+    if (pass_refused(b, trim, span) || ((trim || span) && half) || (span && integer_size != 2)) return hipErrorInvalidValue;
     if (span && b.n_reads == 0) return hipSuccess;
-    auto span_pass = [&](uint32_t verdicts) {
-        if (zigzag) hipLaunchKernelGGL((svb_span_kernel<true, true>), dim3(b.n_reads), dim3(WG), 0, s, b, *span, verdicts);
-        else hipLaunchKernelGGL((svb_span_kernel<false, false>), dim3(b.n_reads), dim3(WG), 0, s, b, *span, verdicts);
-        return hipGetLastError();
-    };
     if (half) {
         if (integer_size != 1 || b.sig.type != SIG_NONE) return hipErrorInvalidValue;
         return zigzag ? launch1(svb_half_decode_kernel<true>, b, s) : launch1(svb_half_decode_kernel<false>, b, s);
     }
-    bool store;   // the counting passes (each selects at its end), then the store -- none for the statistics alone
+    bool store;   // the counting passes (each selects at its end) and the signal pass, then the store -- none for the statistics alone
     const hipError_t e = norm_prepasses(
-        b, integer_size, false, [&] { return launch_norm_init(b, zigzag, s); }, [] { return hipSuccess; },
+        b, integer_size, false, trim, span, [&] { return launch_norm_init(b, zigzag, s); }, [] { return hipSuccess; },
         [&] { return svb_dispatch_count(b, [&](auto out) { return svb_decode_launch<out()>(b, 2, zigzag, s); }); },
-        [&] {
-            if (span) return span_pass(0u);
-            if (!trim) return hipSuccess;
-            if (zigzag) hipLaunchKernelGGL((svb_trim_kernel<true, true>), dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
-            else hipLaunchKernelGGL((svb_trim_kernel<false, false>), dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
-            return hipGetLastError();
-        },
-        &store);
-    if (span) return e == hipSuccess && !b.sig.norm.st ? span_pass(1u) : e;   // (the caller's constants: the pass is all that runs, verdicts included)
+        [&](auto p) { return svb_pass_launch(b, zigzag, p, s); }, &store);
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return svb_decode_launch<out()>(b, integer_size, zigzag, s); });
 }
@@ -2839,27 +2820,16 @@ hipError_t launch_svb16_encode(const ReadBatch& b, uint32_t* period_hint, hipStr
 hipError_t launch_svb16_decode(const ReadBatch& b, hipStream_t s, const TrimOut* trim, const SpanOut* span)
 {
     if (b.n_reads == 0) return hipSuccess;
-    if (trim && !b.sig.norm.st) return hipErrorInvalidValue;
-    if (span && (b.sig.type != SIG_NONE || trim)) return hipErrorInvalidValue;
-    auto span_pass = [&](uint32_t verdicts) {
-        hipLaunchKernelGGL(svb16_span_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, *span, verdicts);
-        return hipGetLastError();
-    };
-    bool store;   // the counting passes (each selects at its end: one workgroup per read), then the store
+    if (pass_refused(b, trim, span)) return hipErrorInvalidValue;
+    bool store;   // the counting passes (each selects at its end: one workgroup per read) and the signal pass, then the store
     const hipError_t e = norm_prepasses(
-        b, 2, false,
+        b, 2, false, trim, span,
         [&] {
             hipLaunchKernelGGL(norm_init16_kernel, dim3((b.n_reads + WG - 1) / WG), dim3(WG), 0, s, b);
             return hipGetLastError();
         },
         [] { return hipSuccess; }, [&] { return svb_dispatch_count(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); }); },
-        [&] {
-            if (span) return span_pass(0u);
-            if (trim) hipLaunchKernelGGL(svb16_trim_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, *trim);
-            return hipGetLastError();
-        },
-        &store);
-    if (span) return e == hipSuccess && !b.sig.norm.st ? span_pass(1u) : e;
+        [&](auto p) { return launch1(svb16_pass_kernel<decltype(p)>, b, s, p); }, &store);
     if (e != hipSuccess || !store) return e;
     return svb_dispatch_store(b, [&](auto out) { return launch1(svb16_decode_kernel<out()>, b, s); });
 }
@@ -2916,8 +2886,8 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
 {
     const uint32_t most = std::max(b.n_reads, pr.n_reads);
     if (most == 0) return hipSuccess;
-    if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st && !span) || b.sig.norm.slab || (trim && !b.sig.norm.st)) return hipErrorInvalidValue;
-    if (span && (!spsc || b.sig.type != SIG_NONE || trim || b.sig.wfirst || b.sig.row)) return hipErrorInvalidValue;
+    if ((b.n_reads && !b.gate) || (b.sig.type == SIG_NONE && !b.sig.norm.st && !span) || b.sig.norm.slab || pass_refused(b, trim, span)) return hipErrorInvalidValue;
+    if (span && (!spsc || b.sig.wfirst || b.sig.row)) return hipErrorInvalidValue;
     const dim3 rows(b.n_reads), reads(pr.n_reads), t(WG);
     if (b.sig.ranged() && !pr.range) return hipErrorInvalidValue;
     if (b.sig.wfirst) {   // the plan with the first half of the window check, the second half, the pad
@@ -2939,9 +2909,8 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
             if (b.sig.ranged_stats()) hipLaunchKernelGGL(svb16_count_reads_range_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
             else hipLaunchKernelGGL(svb16_count_reads_kernel, reads, t, 0, s, b, pr, !store && p == 0 ? 1u : 0u);
         }
-    if (trim && pr.n_reads) hipLaunchKernelGGL(svb16_trim_reads_kernel, reads, t, 0, s, b, pr, *trim);
-    if (span && pr.n_reads) hipLaunchKernelGGL(svb16_span_reads_kernel, reads, t, 0, s, b, pr, *span, b.sig.norm.st ? 0u : 1u);
     hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_pass(trim, span, b.sig.norm.st ? 0u : 1u, [&](auto p) { return svb16_pass_reads_launch(b, pr, p, s); });
     if (e != hipSuccess) return e;
     if (b.n_reads) {
         if (store) {
@@ -2966,17 +2935,12 @@ hipError_t launch_svb16_decode_reads(const ReadBatch& b, const Pod5Reads& pr, co
 // ---- signal segmentation --------------------------------------------------------------------------------------------------------------
 hipError_t launch_svb_segment(const ReadBatch& b, bool zigzag, const SegmentOut& so, hipStream_t s)
 {
-    if (b.n_reads == 0) return hipSuccess;
-    if (zigzag) hipLaunchKernelGGL((svb_segment_kernel<true, true>), dim3(b.n_reads), dim3(WG), 0, s, b, so);
-    else hipLaunchKernelGGL((svb_segment_kernel<false, false>), dim3(b.n_reads), dim3(WG), 0, s, b, so);
-    return hipGetLastError();
+    return svb_pass_launch(b, zigzag, SegmentPass{ {}, so }, s);
 }
 
 hipError_t launch_svb16_segment(const ReadBatch& b, const SegmentOut& so, hipStream_t s)
 {
-    if (b.n_reads == 0) return hipSuccess;
-    hipLaunchKernelGGL(svb16_segment_kernel, dim3(b.n_reads), dim3(WG), 0, s, b, so);
-    return hipGetLastError();
+    return launch1(svb16_pass_kernel<SegmentPass>, b, s, SegmentPass{ {}, so });
 }
 
 hipError_t launch_svb16_segment_reads(const ReadBatch& b, const Pod5Reads& pr, const SegmentOut& so, const SegmentScratch& sc, hipStream_t s)
@@ -2989,8 +2953,8 @@ hipError_t launch_svb16_segment_reads(const ReadBatch& b, const Pod5Reads& pr, c
     else hipLaunchKernelGGL(pod5_reads_plan_kernel, dim3((most + WG - 1) / WG), t, 0, s, b, pr, nullptr, nullptr, 0ull);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = launch_segment_layout(b, pr, sc, s);
+    if (e == hipSuccess) e = svb16_pass_reads_launch(b, pr, SegmentPass{ {}, so }, s);
     if (e != hipSuccess) return e;
-    if (pr.n_reads) hipLaunchKernelGGL(svb16_segment_reads_kernel, dim3(pr.n_reads), t, 0, s, b, pr, so);
     if (pr.read_result && pr.n_reads) hipLaunchKernelGGL(pod5_read_results_kernel, dim3((pr.n_reads + WG - 1) / WG), t, 0, s, b, pr, 2u);
     return hipGetLastError();
 }
@@ -3034,8 +2998,7 @@ hipError_t launch_svb_decode_seg(const ReadBatch& b, int integer_size, bool zigz
                                  const SpanOut* span)
 {
     if (b.n_reads == 0) return hipSuccess;
-    if (trim && !b.sig.norm.st) return hipErrorInvalidValue;
-    if (span && (integer_size != 2 || b.sig.type != SIG_NONE || b.sig.events || trim)) return hipErrorInvalidValue;
+    if (pass_refused(b, trim, span) || (span && (integer_size != 2 || b.sig.events))) return hipErrorInvalidValue;
     return svb_dispatch_store(b, [&](auto out) {
         return svb_dispatch_elem<out() == SIG_NONE>(integer_size, zigzag, [&](auto e, auto z, auto i) {
             return svb_decode_seg_sequence<e(), z(), i(), out()>(b, seg_first, max_segs, seg_val, seg_pos, seg_run, self_max, s, trim, span);

@@ -1358,7 +1358,7 @@ struct SegmentStore
 //   SHARED == false (int16 reads on both paths; a POD5 row as a read): byte p / 8 has exactly one writer in the whole launch, the lane
 //   whose values begin at p, which stores it plainly, zeros too; the walk reaches the read's last sample, so ceil(T / 8) bytes are
 //   written and nothing zeroes the map in front.  The bits of a last byte behind T, and those outside [b + p0, e), are stored as 0.
-//   SHARED == true (POD5 reads of several rows, one workgroup per READ walking its rows: svb16_span_reads_kernel): a row that begins at
+//   SHARED == true (POD5 reads of several rows, one workgroup per READ walking its rows: svb16_pass_reads): a row that begins at
 //   s0 % 8 != 0 makes every lane's bits straddle two bytes, so no lane owns one.  The read's workgroup zeroes the read's map words
 //   itself, and behind a barrier the lanes OR their non-zero bits into the words (32-bit atomics: the map begins at a multiple of 4 and
 //   is rounded up to 4).  Only that workgroup touches the read's map, so the order of workgroups does not matter here either.

@@ -1858,6 +1858,16 @@ int pod5_reads_begin(vbz_gpu_ctx* c, uint32_t n_rows, const vbz_gpu_pod5_reads* 
 
 struct CallScratch { WindowScratch win; SegmentScratch seg; float2* cal = nullptr; };   // a window or an event call's (scan == nullptr: neither); a segmentation's; the per-read constants
 
+// The tables and the maps of a segmentation or a span call over n reads: one bit a sample of the int16 layout of dst_bytes, every read's
+// map rounded up to 4 bytes (launch_segment_layout lays them out, the carve sizes the tables)
+bool read_maps(vbz_gpu_ctx* c, uint64_t dst_bytes, uint32_t n, CallScratch* sc, ReadMaps* m)
+{
+    m->map_cap = dst_bytes / 16 + 4ull * n + 64;
+    m->map = ensure_carved(c, c->segmtab, sc->seg, n) ? ensure_array<uint8_t>(c, c->segmap, m->map_cap) : nullptr;
+    m->map_off = sc->seg.map_off;
+    return m->map != nullptr;
+}
+
 // Outputs: what the call stores and where.  j->rb (the caller's batch so far) gets its sig and the arena the svb stage writes, j->trim /
 // j->seg a trim's or a segmentation's rule and tables; *dst_bytes: the extent of the int16 layout the call decodes through (every kind
 // but SIGNAL: the caller's dst side as it is).  sc->cal comes in as the constants' table of a call over POD5 reads (pod5_reads_begin).
@@ -1882,23 +1892,15 @@ int typed_outputs(vbz_gpu_ctx* c, const vbz_gpu_batch* bt, const TypedCall& t, D
         break;
     }
     case Typed::STATISTICS: break;
-    case Typed::SEGMENT: {   // the tables, and the maps: one bit a sample of the int16 layout, every read's rounded up to 4 bytes
-        const uint64_t map_cap = *dst_bytes / 16 + 4ull * n_const + 64;
-        uint8_t* const map = ensure_carved(c, c->segmtab, sc->seg, n_const) ? ensure_array<uint8_t>(c, c->segmap, map_cap) : nullptr;
-        if (!map) return -1;
+    case Typed::SEGMENT:
         j->seg = segment_out(t.seg);
-        j->seg.map = map, j->seg.map_cap = map_cap;
-        j->seg.map_off = sc->seg.map_off, j->seg.rows = sc->seg.rows;
+        if (!read_maps(c, *dst_bytes, n_const, sc, &j->seg)) return -1;
+        j->seg.rows = sc->seg.rows;
         break;
-    }
-    case Typed::SPANS: {   // segmentation's tables and maps (launch_segment_layout lays them out, the carve sizes them)
-        const uint64_t map_cap = *dst_bytes / 16 + 4ull * n_const + 64;
-        uint8_t* const map = ensure_carved(c, c->segmtab, sc->seg, n_const) ? ensure_array<uint8_t>(c, c->segmap, map_cap) : nullptr;
-        if (!map) return -1;
+    case Typed::SPANS:   // (segmentation's tables and maps)
         j->span = span_out(t.spans);
-        j->span.map = map, j->span.map_cap = map_cap, j->span.map_off = sc->seg.map_off;
+        if (!read_maps(c, *dst_bytes, n_const, sc, &j->span)) return -1;
         break;
-    }
     }
     if (t.reads) cal = sc->cal;   // (else, but for SIGNAL: the constants' table is chunk_slots' or the selects' to fill)
     else if (t.kind != Typed::SIGNAL && !(cal = ensure_array<float2>(c, c->sigmeta, n))) return -1;

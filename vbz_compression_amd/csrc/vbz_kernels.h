@@ -328,13 +328,25 @@ hipError_t launch_event_finish(const ReadBatch& b, const Pod5Reads& pr, const fl
 // state is an argument of its own of the kernels that take it (the host: DecodeJob).  i: the read's entry of the call's tables (rmap: a routed read's; the
 // upper half of a split call gets the tables offset).  A read whose map does not end inside map_cap gets E_OOM.
 constexpr uint32_t SEGMENT_WINDOW_MAX = 32, SEGMENT_RADIUS_MAX = 32;
-struct SegmentOut
+// the maps of a segmentation or a span call: one bit per position, read i's in bytes [map_off[i], map_off[i + 1]) of the call's scratch
+struct ReadMaps
 {
-    uint8_t* map = nullptr;              // nullptr: not a segmentation call
+    uint8_t* map = nullptr;              // nullptr: not such a call
     const uint64_t* map_off = nullptr;   // [n + 1], multiples of 4 (launch_segment_layout)
     uint64_t map_cap = 0;
-    uint32_t* rows = nullptr;            // [n]
     const uint32_t* rmap = nullptr;
+    // read r's entry of the call's tables
+    __device__ uint32_t entry(uint32_t r) const { return rmap ? rmap[r] : r; }
+    // whether read i's map of ceil(T / 8) bytes lies inside the call's scratch: no byte of a map is written before this has passed
+    __device__ bool fits(uint32_t i, uint32_t T) const
+    {
+        const uint64_t a = map_off[i], z = map_off[i + 1];
+        return z <= map_cap && a <= z && (uint64_t)((T + 7u) >> 3) <= z - a;
+    }
+};
+struct SegmentOut : ReadMaps
+{
+    uint32_t* rows = nullptr;            // [n]
     uint32_t w1 = 1, w2 = 0, r = 1;      // the two windows (w2 0: one detector) and the radius
     double k1 = 1.0, k2 = 1.0;           // float64(t) * float64(t) of the two thresholds (exact: 48 bits)
 };
@@ -345,12 +357,8 @@ struct SegmentOut
 // {shift, scale} of b.sig.norm.ss, behind the last counting pass.  i, rmap and the cut of a split call: as for SegmentOut.
 constexpr uint32_t SPAN_ABOVE = 0, SPAN_BELOW = 1;   // (= VBZ_GPU_SPAN_*)
 constexpr uint32_t SPAN_GAP_MAX = 65535, SPAN_LENGTH_MAX = 0x7FFFFFFFu;
-struct SpanOut
+struct SpanOut : ReadMaps
 {
-    uint8_t* map = nullptr;              // nullptr: not a span call
-    const uint64_t* map_off = nullptr;   // [n + 1], multiples of 4 (launch_segment_layout)
-    uint64_t map_cap = 0;
-    const uint32_t* rmap = nullptr;
     const float2* level = nullptr;       // the caller's {a, w} per read, or nullptr: the statistics'
     uint32_t below = 0, D = 0, m = 1, p0 = 0;
     float f = 0.0f;
