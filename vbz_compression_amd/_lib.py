@@ -1,4 +1,4 @@
-"""ctypes loader of libvbz_hip.so (the C ABI in include/vbz.h and include/vbz_gpu.h).
+"""ctypes loader of libvbz_hip.so (the C ABI in include/vbz.h, include/vbz_gpu.h and include/vbz_gpu_pile.h).
 
 The library is the product: if it is missing this module raises -- there is no Python or CPU
 fallback for either stage of the codec.
@@ -370,7 +370,46 @@ class GpuLevelFit(ctypes.Structure):
     ]
 
 
+class GpuLevelsPile(ctypes.Structure):
+    """struct vbz_gpu_levels_pile of include/vbz_gpu_pile.h (32 bytes)."""
+
+    _fields_ = [
+        ("max_width", ctypes.c_uint32),
+        ("min_samples", ctypes.c_uint32),
+        ("max_entries", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("fix", ctypes.c_float),
+        ("reserved0", ctypes.c_uint32),
+        ("reserved1", ctypes.c_uint32),
+        ("reserved2", ctypes.c_uint32),
+    ]
+
+
+class GpuPileKmers(ctypes.Structure):
+    """struct vbz_gpu_pile_kmers of include/vbz_gpu_pile.h (16 bytes)."""
+
+    _fields_ = [
+        ("k", ctypes.c_uint32),
+        ("rows", ctypes.c_uint32),
+        ("target_stride", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+    ]
+
+
+class GpuModelUpdate(ctypes.Structure):
+    """struct vbz_gpu_model_update of include/vbz_gpu_pile.h (16 bytes)."""
+
+    _fields_ = [
+        ("k", ctypes.c_uint32),
+        ("min_obs", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("fix", ctypes.c_float),
+    ]
+
+
 SQUIGGLE_BOTH, SQUIGGLE_REVERSED = 1, 2
+PILE_CLEAR, PILE_REQUIRE_OK, PILE_DIRECT = 1, 2, 4
+KMER_MARK = 0xFFFFFFFF   # vbz_gpu_squiggle_kmers_batch: a masked k-mer, and at and behind target_len
 
 C_API = [
     "vbz_is_error",
@@ -457,6 +496,15 @@ GPU_API = [
     "vbz_gpu_decode_literals_ahead",
     "vbz_gpu_decode_span_paths",
     "vbz_gpu_version",
+]
+
+# The pile-up across reads: the entry points of include/vbz_gpu_pile.h.  They stand in lists of their own: C_API + GPU_API and PROTOTYPES are
+# held to tests/golden/prototypes.json, a recorded table no change edits; these are held to tests/golden/prototypes_pile.json.
+PILE_API = [
+    "vbz_gpu_levels_pile_batch",
+    "vbz_gpu_squiggle_kmers_batch",
+    "vbz_gpu_pile_kmers_batch",
+    "vbz_gpu_model_update_batch",
 ]
 
 def _prototypes():
@@ -550,6 +598,20 @@ def _prototypes():
 
 
 PROTOTYPES = _prototypes()
+
+
+def _pile_prototypes():
+    """name -> (restype, argtypes) of every entry of PILE_API, as include/vbz_gpu_pile.h declares them: PROTOTYPES' shape."""
+    c_int, vp, u32, P = ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER
+    return {
+        "vbz_gpu_levels_pile_batch": (c_int, [vp, u32, u32, P(GpuLocate), vp, vp, vp, vp, P(GpuLevelsPile), vp, vp]),
+        "vbz_gpu_squiggle_kmers_batch": (c_int, [vp, P(GpuSquiggle), vp, vp]),
+        "vbz_gpu_pile_kmers_batch": (c_int, [vp, P(GpuPileKmers), vp, vp, vp, vp]),
+        "vbz_gpu_model_update_batch": (c_int, [vp, P(GpuModelUpdate), vp, vp, vp, vp]),
+    }
+
+
+PILE_PROTOTYPES = _pile_prototypes()
 _lib = None
 
 
@@ -564,7 +626,7 @@ def load():
             "(there is no CPU fallback for the VBZ codec in this package)" % LIB_PATH
         )
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PILE_PROTOTYPES.items()):
         # (a name the library lacks is skipped: tools/ab_libs.py and tools/compare_libs.py load earlier builds through VBZ_HIP_LIB, and a
         # call of such a name fails at its first use)
         if hasattr(L, name):

@@ -1065,6 +1065,75 @@ class GpuCodec:
                    ptr(prior), out.data_ptr(), offset.data_ptr(), scale.data_ptr(), ptr(sums))
         return out, offset, scale, sums
 
+    # -- the pile-up across reads: per-position and per-k-mer sums, a model update (include/vbz_gpu_pile.h) ------
+    def squiggle_kmers(self, seq, seq_len, k, target_stride, both=False, reversed=False, kmer=None, target_len=None):
+        """The k-mer index under every target position (include/vbz_gpu_pile.h: vbz_gpu_squiggle_kmers_batch): seq, seq_len, k,
+        target_stride, both and reversed as for squiggle() -> (kmer int32 [rows, target_stride] = the index squiggle() would look up at
+        each position, _lib.KMER_MARK (-1 as int32) where it would count a masked k-mer and at and behind target_len, target_len int32
+        [rows]) on the device.  kmer and target_len may be given.  No synchronisation."""
+        S, k, T = int(seq.shape[0]), int(k), int(target_stride)
+        rows = 2 * S if both else S
+        table("seq", seq, torch.uint8, self.device, shape=(None, None))
+        table("seq_len", seq_len, torch.int32, self.device, numel=S)
+        kmer = output("kmer", kmer, torch.int32, self.device, (rows, T))
+        target_len = output("target_len", target_len, torch.int32, self.device, rows)
+        sq = _lib.GpuSquiggle(k, S, int(seq.shape[1]), T, (_lib.SQUIGGLE_BOTH if both else 0) | (_lib.SQUIGGLE_REVERSED if reversed else 0), 1.0,
+                              seq.data_ptr(), seq_len.data_ptr(), None)
+        self._call("squiggle_kmers_batch", ctypes.byref(sq), kmer.data_ptr(), target_len.data_ptr())
+        return kmer, target_len
+
+    def levels_pile(self, pairs, hit, n_levels, levels, target, target_len, n_reads, fix=256.0, fit=None, require_ok=False, clear=False, locate=None,
+                    min_samples=0, max_entries=0, pile=None):
+        """Every pair's levels added into their target positions (include/vbz_gpu_pile.h: vbz_gpu_levels_pile_batch): pairs, hit, n_levels,
+        levels, target, target_len, n_reads, locate, min_samples and max_entries as for levels_fit(); fit int32 [p, 4] its `out` table (None:
+        offset 0, scale 1), require_ok: pairs without a good fit contribute nothing -> pile int64 [4, G, target_stride] on the device: the
+        planes (count word = kept + 2^32 skipped, n_samples, sum, sumsq) of u = rint(((mean + offset) * scale) * fix) per kept level.
+        pile=None makes a zeroed arena; a given one is added to, after clearing it with clear=True.  No synchronisation."""
+        p, W = int(pairs.shape[0]), int(levels.shape[1])
+        loc = (locate or Locate()).c_struct(target, target_len)
+        assert target.device == self.device
+        for name, t, shape in (("pairs", pairs, (p, 4)), ("hit", hit, (p, 4)), ("n_levels", n_levels, (p,)), ("levels", levels, (p, W, 8))):
+            table(name, t, torch.int32, self.device, shape=shape)
+        table("fit", fit, torch.int32, self.device, shape=(p, 4), none=True)
+        clear = bool(clear) or pile is None
+        pile = output("pile", pile, torch.int64, self.device, (4, int(target.shape[0]), int(target.shape[1])))
+        par = _lib.GpuLevelsPile(W, int(min_samples), int(max_entries), (_lib.PILE_CLEAR if clear else 0) | (_lib.PILE_REQUIRE_OK if require_ok else 0),
+                                 float(fix), 0, 0, 0)
+        self._call("levels_pile_batch", p, int(n_reads), ctypes.byref(loc), pairs.data_ptr(), hit.data_ptr(), n_levels.data_ptr(), levels.data_ptr(),
+                   ctypes.byref(par), ptr(fit), pile.data_ptr())
+        return pile
+
+    def pile_kmers(self, pile, kmer, target_len, k, clear=False, direct=False, kmer_pile=None):
+        """The position cells added into the cells of their k-mers (include/vbz_gpu_pile.h: vbz_gpu_pile_kmers_batch): pile int64 [4, G,
+        target_stride] of levels_pile(), kmer int32 [G, target_stride] and target_len int32 [G] of squiggle_kmers() -> kmer_pile int64 [4,
+        4 ** k] on the device.  kmer_pile=None makes a zeroed arena; a given one is added to, after clearing it with clear=True.  direct:
+        global adds whatever k is.  No synchronisation."""
+        G, T, k = int(kmer.shape[0]), int(kmer.shape[1]), int(k)
+        assert 1 <= k <= 9, k
+        table("pile", pile, torch.int64, self.device, shape=(4, G, T))
+        table("kmer", kmer, torch.int32, self.device, shape=(G, T))
+        table("target_len", target_len, torch.int32, self.device, numel=G)
+        clear = bool(clear) or kmer_pile is None
+        kmer_pile = output("kmer_pile", kmer_pile, torch.int64, self.device, (4, 4 ** k))
+        par = _lib.GpuPileKmers(k, G, T, (_lib.PILE_CLEAR if clear else 0) | (_lib.PILE_DIRECT if direct else 0))
+        self._call("pile_kmers_batch", ctypes.byref(par), target_len.data_ptr(), kmer.data_ptr(), pile.data_ptr(), kmer_pile.data_ptr())
+        return kmer_pile
+
+    def model_update(self, kmer_pile, prior, k, fix=256.0, min_obs=0, sd=False, model=None):
+        """A new k-mer table from the k-mer pile (include/vbz_gpu_pile.h: vbz_gpu_model_update_batch): kmer_pile int64 [4, 4 ** k] of
+        pile_kmers(), prior float32 [4 ** k] -> (model float32 [4 ** k] = mean / fix where the k-mer has max(min_obs, 1) kept observations,
+        the prior's bits elsewhere; sd float32 [4 ** k] or None) on the device.  model may be given, and may be prior; sd: True, False or a
+        tensor.  What squiggle() takes as its model.  No synchronisation."""
+        k = int(k)
+        assert 1 <= k <= 9, k
+        table("kmer_pile", kmer_pile, torch.int64, self.device, shape=(4, 4 ** k))
+        table("prior", prior, torch.float32, self.device, numel=4 ** k)
+        model = output("model", model, torch.float32, self.device, 4 ** k)
+        sd = output("sd", sd, torch.float32, self.device, 4 ** k, three_state=True)
+        par = _lib.GpuModelUpdate(k, int(min_obs), 0, float(fix))
+        self._call("model_update_batch", ctypes.byref(par), kmer_pile.data_ptr(), prior.data_ptr(), model.data_ptr(), ptr(sd))
+        return model, sd
+
     # -- signal events (include/vbz_gpu.h: vbz_gpu_events) ---------------------------------------------
     def _events(self, n, event_first, start):
         """(the C struct, the tables it points to) of n reads' events: event_first int64 [n + 1] on the device; start int32 [rows] on the

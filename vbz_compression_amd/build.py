@@ -11,8 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-SOURCES = ["svb_kernels.hip", "zstd_encode.hip", "zstd_decode.hip", "zstd_decode_fast.hip", "zstd_decode_ref.hip", "helpers.hip", "xxh64.hip", "pack.hip", "match.hip", "locate.hip", "eventalign.hip", "squiggle.hip", "vbz_api.hip"]
-HEADERS = ["vbz_kernels.h", "scratch_tables.h", "match_path.h", "svb_store.h", "xxh64.h", "zstd_entropy.h", "zstd_runs.h", "zstd_tables.h", "zstd_frame.h", "match_select.h", "match_path_groups.h", "../../include/vbz.h", "../../include/vbz_gpu.h", "../../include/vbz_hdf_plugin.h"]
+SOURCES = ["svb_kernels.hip", "zstd_encode.hip", "zstd_decode.hip", "zstd_decode_fast.hip", "zstd_decode_ref.hip", "helpers.hip", "xxh64.hip", "pack.hip", "match.hip", "locate.hip", "eventalign.hip", "squiggle.hip", "pile.hip", "vbz_api.hip"]
+HEADERS = ["vbz_kernels.h", "scratch_tables.h", "match_path.h", "svb_store.h", "xxh64.h", "zstd_entropy.h", "zstd_runs.h", "zstd_tables.h", "zstd_frame.h", "match_select.h", "match_path_groups.h", "squiggle_bases.h", "../../include/vbz.h", "../../include/vbz_gpu.h", "../../include/vbz_gpu_pile.h", "../../include/vbz_hdf_plugin.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # The SDWA peephole is off: a byte-1 SDWA shift feeding v_bitop3_b16 produced a wrong block-header byte on hardware

@@ -6,6 +6,7 @@
 // No LDS, no barrier, no atomics, no private scratch: lanes talk through shuffles alone (the squiggle's wavefronts leave one word each in a
 // buffer of the context for the second launch).
 #include "match_path.h"
+#include "squiggle_bases.h"
 
 #pragma clang fp contract(off)
 
@@ -31,15 +32,13 @@ __device__ __forceinline__ T wave_sum(T v)
 // dwords that cover its 24 bytes -- each only when it lies inside the row's seq_stride bytes, 0 otherwise -- and v_alignbyte_b32 shifts
 // them into place; the reverse strand then swaps the bytes and the dwords and complements the codes.  lo may be negative (the last lane of a
 // reversed row) and bytes at and behind n are the caller's junk: both reach only k-mers outside [0, L), which are never gathered or stored.
-// Byte 0 of the 24 is strand base lo - (9 - k), so that byte i >= 8 closes k-mer lo + i - 8 whatever k is: the loop below is unrolled over
+// Byte 0 of the 24 is strand base lo - (9 - k), so that byte i >= 8 closes k-mer lo + i - 8 whatever k is: the roll (squiggle_bases.h, shared with pile.hip) is unrolled over
 // constants, and the 9 - k bases in front of the first k-mer have left both windows when it closes.
 // The roll.  index = (index << 2 | code) & (4^k - 1); bad = (bad << 1 | invalid) & (2^k - 1): after k bases both describe exactly the
 // last k, whatever came before.  A k-mer inside [0, L) with bad == 0 gathers model[index] (index < 4^k by the mask); with bad != 0 it
 // is counted, and holds int8 0 and float +0.
 // The count.  A wavefront adds its lanes' counts by shuffles and stores ONE word, part[row][wavefront]: every word of part is stored by
 // every call, so nothing is zeroed in front and no atomic is needed; squiggle_masked_kernel, one wavefront a row, adds them up.
-constexpr uint32_t SQ_KMAX = 9, SQ_LANE = 16, SQ_WAVE = 64u * SQ_LANE, SQ_BLOCK = 4u * SQ_WAVE;
-
 struct SquiggleArgs
 {
     uint32_t k, rows, seq_stride, target_stride, flags, waves_per_row;
@@ -53,28 +52,6 @@ struct SquiggleArgs
     uint32_t* part;          // [rows, waves_per_row]
 };
 
-// the strand's length and the row's L under an untrusted seq_len
-__device__ __forceinline__ uint32_t squiggle_len(const SquiggleArgs& a, uint32_t s, uint32_t& n)
-{
-    n = a.seq_len[s];
-    if (n > a.seq_stride) n = 0;   // (no address is formed from it)
-    const uint32_t L = n >= a.k ? n - a.k + 1u : 0u;
-    return L > a.target_stride ? 0u : L;
-}
-
-// Four bases of a dword as codes A 0, C 1, G 2, T/U 3 in the bytes' low bits ((b >> 1) & 3 is A 0, C 1, T/U 2, G 3: x ^ (x >> 1) puts G
-// and T right), complemented for the reverse strand; whether a byte IS one of the ten letters is asked per byte below.
-__device__ __forceinline__ uint32_t base_codes(uint32_t w, bool rc)
-{
-    const uint32_t c = (w >> 1) & 0x03030303u;
-    return c ^ ((c >> 1) & 0x01010101u) ^ (rc ? 0x03030303u : 0u);
-}
-__device__ __forceinline__ uint32_t base_invalid(uint32_t byte)
-{
-    const uint32_t i = (byte | 0x20u) - 0x61u;   // a 0, c 2, g 6, t 19, u 20; both bytes that give one of these are letters
-    return i <= 20u ? (~(0x180045u >> i)) & 1u : 1u;
-}
-
 __global__ __launch_bounds__(256) void squiggle_kernel(SquiggleArgs a)
 {
     const uint32_t row = blockIdx.y, wave = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
@@ -83,7 +60,7 @@ __global__ __launch_bounds__(256) void squiggle_kernel(SquiggleArgs a)
     const uint32_t s = both ? row >> 1 : row;
     const bool rc = both && (row & 1u) != 0;
     uint32_t n = 0;
-    const uint32_t L = squiggle_len(a, s, n);
+    const uint32_t L = squiggle_len(a.seq_len, a.seq_stride, a.k, a.target_stride, s, n);
     if (blockIdx.x == 0 && threadIdx.x == 0) a.target_len[row] = L;
 
     uint32_t q[4] = { 0u, 0u, 0u, 0u }, m[SQ_LANE];
@@ -91,47 +68,20 @@ __global__ __launch_bounds__(256) void squiggle_kernel(SquiggleArgs a)
     for (uint32_t e = 0; e < SQ_LANE; ++e) m[e] = 0u;
     uint32_t masked = 0;
     if (j0 < L) {
-        const int32_t lo = reversed ? (int32_t)L - (int32_t)SQ_LANE - (int32_t)j0 : (int32_t)j0;   // (>= -15)
-        const int32_t b0 = lo - (int32_t)(SQ_KMAX - a.k);                                          // the strand base of byte 0 (>= -23)
-        const int32_t at = rc ? (int32_t)n - 1 - b0 - 23 : b0;                                     // the first of the 24 bytes in seq
-        const int32_t d0 = at >> 2;                                                                // (floor)
-        const uint32_t shift = (uint32_t)at & 3u, n_words = a.seq_stride / 4u;
-        const uint32_t* const words = reinterpret_cast<const uint32_t*>(a.seq + (size_t)s * a.seq_stride);
-        uint32_t w[7];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            const uint32_t d = (uint32_t)(d0 + i);   // (a negative dword is a large one)
-            w[i] = d < n_words ? words[d] : 0u;
-        }
         uint32_t v[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) v[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], shift);
-        if (rc) {   // the same bytes from the other end
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const uint32_t x = __builtin_bswap32(v[i]);
-                v[i] = __builtin_bswap32(v[5 - i]);
-                v[5 - i] = x;
-            }
-        }
+        const int32_t lo = squiggle_bases(a.seq, a.seq_stride, s, n, a.k, L, j0, rc, reversed, v);
         const uint32_t index_mask = (1u << (2u * a.k)) - 1u, bad_mask = (1u << a.k) - 1u;
         uint32_t index = 0, bad = 0;
 #pragma unroll
         for (uint32_t i = 0; i < 24u; ++i) {
-            const uint32_t byte = (v[i / 4u] >> (8u * (i % 4u))) & 0xFFu, code = (base_codes(v[i / 4u], rc) >> (8u * (i % 4u))) & 3u;
-            index = (index << 2 | code) & index_mask;
-            bad = (bad << 1 | base_invalid(byte)) & bad_mask;
-            if (i < SQ_KMAX - 1u) continue;
-            const uint32_t e = i - (SQ_KMAX - 1u);   // byte i closes the k-mer at p = lo + e
-            const int32_t p = lo + (int32_t)e;
-            if (p >= 0 && (uint32_t)p < L) {
-                if (bad != 0) ++masked;
-                else {
-                    m[e] = a.model[index];
-                    const float val = __uint_as_float(m[e]) * a.quant;
-                    const float r = fminf(fmaxf(rintf(val), -127.0f), 127.0f);
-                    q[e / 4u] |= (val != val ? 0u : (uint32_t)(int)r & 0xFFu) << (8u * (e % 4u));
-                }
+            if (!squiggle_roll_step(v, i, rc, index_mask, bad_mask, lo, L, index, bad)) continue;
+            const uint32_t e = i - (SQ_KMAX - 1u);   // byte i closes the k-mer at p = lo + e, inside [0, L)
+            if (bad != 0) ++masked;
+            else {
+                m[e] = a.model[index];
+                const float val = __uint_as_float(m[e]) * a.quant;
+                const float r = fminf(fmaxf(rintf(val), -127.0f), 127.0f);
+                q[e / 4u] |= (val != val ? 0u : (uint32_t)(int)r & 0xFFu) << (8u * (e % 4u));
             }
         }
         if (reversed) {   // strand order -> output order
@@ -195,12 +145,8 @@ __global__ __launch_bounds__(256) void levels_fit_kernel(FitArgs a)
     const uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (p >= a.n_pairs) return;
     const uint4 pr = a.pairs[p], h = a.hit[p];
-    const uint32_t read = pr.x, ref = pr.y, end = h.y, start = h.z, W = a.n_levels[p];
-    bool valid = read < a.n_reads && ref < a.G && W != 0u && W <= a.max_width && end > start && end - start == W;
-    if (valid) {
-        const uint32_t Lg = a.target_len[ref];
-        valid = Lg != 0u && Lg <= a.target_stride && end <= Lg;
-    }
+    const uint32_t read = pr.x, ref = pr.y, start = h.z, W = a.n_levels[p];
+    const bool valid = levels_pair_valid(pr, h, W, a.n_reads, a.G, a.target_stride, a.max_width, a.target_len);
     uint32_t K = 0;
     int64_t Sg = 0, Sgg = 0, Sq = 0, Sgq = 0;
     if (valid) {

@@ -20,6 +20,7 @@
 
 #include "../../include/vbz.h"
 #include "../../include/vbz_gpu.h"
+#include "../../include/vbz_gpu_pile.h"
 #include "vbz_kernels.h"
 #include "scratch_tables.h"
 #include "match_path_groups.h"
@@ -2849,13 +2850,13 @@ static_assert(sizeof(vbz_gpu_level_fit) == 16 && offsetof(vbz_gpu_level_fit, off
                   offsetof(vbz_gpu_level_fit, used) == 8 && offsetof(vbz_gpu_level_fit, ok) == 12,
               "vbz_gpu_level_fit is 16 bytes: offset, scale, used, ok");
 
-int vbz_gpu_squiggle_batch(vbz_gpu_ctx* c, const vbz_gpu_squiggle* sq, int8_t* target, uint32_t* target_len, uint32_t* masked, float* level)
+// What the two calls over a vbz_gpu_squiggle share: the struct's own rules and the arenas' extent.  `tables`: the call's own pointers are
+// all there; `arenas`: those that must be 16-byte aligned, or-ed.
+static bool squiggle_ok(vbz_gpu_ctx* c, const vbz_gpu_squiggle* sq, bool tables, uintptr_t arenas, const char* null_msg, const char* align_msg)
 {
-    if (!c) return -1;
-    DeviceGuard dg(c->device);
     if (!sq) {
         set_error(c, "squiggle is NULL");
-        return -2;
+        return false;
     }
     const bool both = (sq->flags & VBZ_GPU_SQUIGGLE_BOTH) != 0;
     const auto stride_ok = [](uint32_t s) { return s >= 16 && s <= (1u << 30) && s % 16 == 0; };
@@ -2863,22 +2864,33 @@ int vbz_gpu_squiggle_batch(vbz_gpu_ctx* c, const vbz_gpu_squiggle* sq, int8_t* t
         (sq->flags & ~(VBZ_GPU_SQUIGGLE_BOTH | VBZ_GPU_SQUIGGLE_REVERSED)) != 0 || !(sq->quant > 0.0f) || !std::isfinite(sq->quant)) {
         set_error(c, "squiggle outside the rules (k %u, n_seqs %u, seq_stride %u, target_stride %u, flags %u, quant %g)", sq->k, sq->n_seqs, sq->seq_stride,
                   sq->target_stride, sq->flags, (double)sq->quant);
-        return -2;
+        return false;
     }
-    if (!sq->seq || !sq->seq_len || !sq->model || !target || !target_len || !masked) {
-        set_error(c, "seq, seq_len, the model, the target arena, target_len or masked is NULL");
-        return -2;
+    if (!sq->seq || !sq->seq_len || !tables) {
+        set_error(c, "%s", null_msg);
+        return false;
     }
-    if ((((uintptr_t)sq->seq | (uintptr_t)target | (uintptr_t)level) & 15u) != 0) {
-        set_error(c, "seq, the target arena or the level arena is not 16-byte aligned");
-        return -2;
+    if ((((uintptr_t)sq->seq | arenas) & 15u) != 0) {
+        set_error(c, "%s", align_msg);
+        return false;
     }
     const uint32_t rows = both ? 2u * sq->n_seqs : sq->n_seqs;
     if ((uint64_t)rows * sq->target_stride > EXTENT_MAX / sizeof(float) || (uint64_t)sq->n_seqs * sq->seq_stride > EXTENT_MAX) {
         set_error(c, "declared squiggle arenas are not plausible (%u sequences of %u bytes, %u rows of %u levels)", sq->n_seqs, sq->seq_stride, rows,
                   sq->target_stride);
-        return -2;
+        return false;
     }
+    return true;
+}
+
+int vbz_gpu_squiggle_batch(vbz_gpu_ctx* c, const vbz_gpu_squiggle* sq, int8_t* target, uint32_t* target_len, uint32_t* masked, float* level)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!squiggle_ok(c, sq, sq && sq->model && target && target_len && masked, (uintptr_t)target | (uintptr_t)level,
+                     "seq, seq_len, the model, the target arena, target_len or masked is NULL", "seq, the target arena or the level arena is not 16-byte aligned"))
+        return -2;
+    const uint32_t rows = (sq->flags & VBZ_GPU_SQUIGGLE_BOTH) != 0 ? 2u * sq->n_seqs : sq->n_seqs;
     uint32_t* const part = ensure_array<uint32_t>(c, c->squigpart, squiggle_part_words(rows, sq->target_stride));
     if (!part) return -1;
     Timed t(c, "squiggle");
@@ -2918,6 +2930,116 @@ int vbz_gpu_levels_fit_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads,
     HIPCHK(c, launch_levels_fit(n_pairs, n_reads, m.n_levels, m.levels_stride, m.quant, m.levels, m.levels_len, pairs, hit, n_levels, levels, fit->max_width,
                                 fit->min_samples, fit->max_entries, prior_shift_scale, out, offset, scale, sums, c->stream),
            "levels fit launch");
+    return 0;
+}
+
+// ---- the pile-up across reads (include/vbz_gpu_pile.h) ----
+static_assert(sizeof(vbz_gpu_levels_pile) == 32 && offsetof(vbz_gpu_levels_pile, max_width) == 0 && offsetof(vbz_gpu_levels_pile, min_samples) == 4 &&
+                  offsetof(vbz_gpu_levels_pile, max_entries) == 8 && offsetof(vbz_gpu_levels_pile, flags) == 12 && offsetof(vbz_gpu_levels_pile, fix) == 16 &&
+                  offsetof(vbz_gpu_levels_pile, reserved0) == 20,
+              "vbz_gpu_levels_pile is 32 bytes: max_width, min_samples, max_entries, flags, fix, three reserved words");
+static_assert(sizeof(vbz_gpu_pile_kmers) == 16 && offsetof(vbz_gpu_pile_kmers, k) == 0 && offsetof(vbz_gpu_pile_kmers, rows) == 4 &&
+                  offsetof(vbz_gpu_pile_kmers, target_stride) == 8 && offsetof(vbz_gpu_pile_kmers, flags) == 12,
+              "vbz_gpu_pile_kmers is 16 bytes: k, rows, target_stride, flags");
+static_assert(sizeof(vbz_gpu_model_update) == 16 && offsetof(vbz_gpu_model_update, k) == 0 && offsetof(vbz_gpu_model_update, min_obs) == 4 &&
+                  offsetof(vbz_gpu_model_update, flags) == 8 && offsetof(vbz_gpu_model_update, fix) == 12,
+              "vbz_gpu_model_update is 16 bytes: k, min_obs, flags, fix");
+
+int vbz_gpu_levels_pile_batch(vbz_gpu_ctx* c, uint32_t n_pairs, uint32_t n_reads, const vbz_gpu_locate* locate, const vbz_gpu_match_pair* pairs,
+                              const vbz_gpu_match_span* hit, const uint32_t* n_levels, const vbz_gpu_level* levels, const vbz_gpu_levels_pile* params,
+                              const vbz_gpu_level_fit* fit, uint64_t* pile)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    // (the checks of vbz_gpu_levels_fit_batch, in its order, with the pile in the place of its outputs)
+    const AlignView m = align_view(locate);
+    if (!align_ok(c, LOCATE, m, nullptr, nullptr, sizeof(vbz_gpu_match_span), 0)) return -2;
+    if (!params || (params->flags & ~(VBZ_GPU_PILE_CLEAR | VBZ_GPU_PILE_REQUIRE_OK)) != 0 || (params->reserved0 | params->reserved1 | params->reserved2) != 0 ||
+        !entries_len_ok(params->max_width) || !(params->fix > 0.0f) || !std::isfinite(params->fix)) {
+        set_error(c, "levels pile is NULL or outside the rules (max_width %u: a multiple of 8, 8 ... 65536; flags %u; fix %g: finite, > 0; reserved words 0)",
+                  params ? params->max_width : 0u, params ? params->flags : 0u, params ? (double)params->fix : 0.0);
+        return -2;
+    }
+    if (!pile || (n_pairs != 0 && (!m.levels || !m.levels_len || !pairs || !hit || !n_levels || !levels))) {
+        set_error(c, "the pile, target, target_len, the pair table, the hit table, n_levels or the level arena is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)pairs | (uintptr_t)hit | (uintptr_t)levels | (uintptr_t)fit | (uintptr_t)pile) & 15u) != 0) {
+        set_error(c, "the pair table, the hit table, the level arena, the fit table or the pile is not 16-byte aligned");
+        return -2;
+    }
+    if ((uint64_t)n_pairs * params->max_width > EXTENT_MAX / sizeof(vbz_gpu_level) || (uint64_t)m.n_levels * m.levels_stride > EXTENT_MAX / 32u) {
+        set_error(c, "declared level arena or pile is not plausible (%u pairs of %u levels, %u targets of %u cells)", n_pairs, params->max_width, m.n_levels,
+                  m.levels_stride);
+        return -2;
+    }
+    Timed t(c, "levels_pile");
+    HIPCHK(c, launch_levels_pile(n_pairs, n_reads, m.n_levels, m.levels_stride, m.levels_len, pairs, hit, n_levels, levels, params->max_width, params->min_samples,
+                                 params->max_entries, (params->flags & VBZ_GPU_PILE_REQUIRE_OK) != 0, (params->flags & VBZ_GPU_PILE_CLEAR) != 0, params->fix, fit,
+                                 pile, c->stream),
+           "levels pile launch");
+    return 0;
+}
+
+int vbz_gpu_squiggle_kmers_batch(vbz_gpu_ctx* c, const vbz_gpu_squiggle* sq, uint32_t* kmer, uint32_t* target_len)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!squiggle_ok(c, sq, kmer && target_len, (uintptr_t)kmer, "seq, seq_len, the kmer arena or target_len is NULL",
+                     "seq or the kmer arena is not 16-byte aligned"))
+        return -2;
+    const uint32_t rows = (sq->flags & VBZ_GPU_SQUIGGLE_BOTH) != 0 ? 2u * sq->n_seqs : sq->n_seqs;
+    Timed t(c, "squiggle_kmers");
+    HIPCHK(c, launch_squiggle_kmers(sq->k, rows, sq->seq_stride, sq->target_stride, sq->flags, sq->seq, sq->seq_len, kmer, target_len, c->stream),
+           "squiggle kmers launch");
+    return 0;
+}
+
+int vbz_gpu_pile_kmers_batch(vbz_gpu_ctx* c, const vbz_gpu_pile_kmers* params, const uint32_t* target_len, const uint32_t* kmer, const uint64_t* pile,
+                             uint64_t* kmer_pile)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!params || params->k < 1 || params->k > 9 || params->rows < 1 || params->rows > 4096 || params->target_stride < 16 ||
+        params->target_stride > (1u << 30) || params->target_stride % 16 != 0 || (params->flags & ~(VBZ_GPU_PILE_CLEAR | VBZ_GPU_PILE_DIRECT)) != 0) {
+        set_error(c, "pile kmers is NULL or outside the rules (k %u, rows %u, target_stride %u, flags %u)", params ? params->k : 0u, params ? params->rows : 0u,
+                  params ? params->target_stride : 0u, params ? params->flags : 0u);
+        return -2;
+    }
+    if (!target_len || !kmer || !pile || !kmer_pile) {
+        set_error(c, "target_len, the kmer arena, the pile or the k-mer pile is NULL");
+        return -2;
+    }
+    if ((((uintptr_t)kmer | (uintptr_t)pile | (uintptr_t)kmer_pile) & 15u) != 0) {
+        set_error(c, "the kmer arena, the pile or the k-mer pile is not 16-byte aligned");
+        return -2;
+    }
+    if ((uint64_t)params->rows * params->target_stride > EXTENT_MAX / 32u) {
+        set_error(c, "declared pile is not plausible (%u rows of %u cells)", params->rows, params->target_stride);
+        return -2;
+    }
+    Timed t(c, "pile_kmers");
+    HIPCHK(c, launch_pile_kmers(params->k, params->rows, params->target_stride, (params->flags & VBZ_GPU_PILE_CLEAR) != 0,
+                                (params->flags & VBZ_GPU_PILE_DIRECT) != 0, target_len, kmer, pile, kmer_pile, c->stream),
+           "pile kmers launch");
+    return 0;
+}
+
+int vbz_gpu_model_update_batch(vbz_gpu_ctx* c, const vbz_gpu_model_update* params, const uint64_t* kmer_pile, const float* prior, float* model, float* sd)
+{
+    if (!c) return -1;
+    DeviceGuard dg(c->device);
+    if (!params || params->k < 1 || params->k > 9 || params->flags != 0 || !(params->fix > 0.0f) || !std::isfinite(params->fix)) {
+        set_error(c, "model update is NULL or outside the rules (k %u, flags %u, fix %g)", params ? params->k : 0u, params ? params->flags : 0u,
+                  params ? (double)params->fix : 0.0);
+        return -2;
+    }
+    if (!kmer_pile || !prior || !model || ((uintptr_t)kmer_pile & 15u) != 0) {
+        set_error(c, "the k-mer pile, the prior or the model is NULL, or the k-mer pile is not 16-byte aligned");
+        return -2;
+    }
+    Timed t(c, "model_update");
+    HIPCHK(c, launch_model_update(params->k, params->min_obs, params->fix, kmer_pile, prior, model, sd, c->stream), "model update launch");
     return 0;
 }
 

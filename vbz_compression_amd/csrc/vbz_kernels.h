@@ -836,6 +836,26 @@ hipError_t launch_levels_fit(uint32_t n_pairs, uint32_t n_reads, uint32_t G, uin
                              const uint32_t* target_len, const void* pairs, const void* hit, const uint32_t* n_levels, const void* levels, uint32_t max_width,
                              uint32_t min_samples, uint32_t max_entries, const float* prior, void* out, float* offset, float* scale, int64_t* sums,
                              hipStream_t s);
+// The pile-up across reads (pile.hip; the rules: include/vbz_gpu_pile.h).  A pile is four planes of n_cells 64-bit words: count word,
+// n_samples, sum, sumsq.
+// launch_levels_pile: every kept level of every valid pair (levels_fit's test) added into cell ref * target_stride + start + t of pile
+// (G * target_stride cells), its value ((mean + offset) * scale) * fix in float64 rounded to an integer; fit ([n_pairs] {offset, scale,
+// used, ok}) is nullable; clear zeroes the arena in front, also with no pairs.
+hipError_t launch_levels_pile(uint32_t n_pairs, uint32_t n_reads, uint32_t G, uint32_t target_stride, const uint32_t* target_len, const void* pairs,
+                              const void* hit, const uint32_t* n_levels, const void* levels, uint32_t max_width, uint32_t min_samples, uint32_t max_entries,
+                              bool require_ok, bool clear, float fix, const void* fit, uint64_t* pile, hipStream_t s);
+// launch_squiggle_kmers: row r of kmer ([rows, target_stride] words) = the index of the k-mer launch_squiggle would look up there,
+// 0xFFFFFFFF where it would count a masked one and at and behind target_len[r], which is written too.
+hipError_t launch_squiggle_kmers(uint32_t k, uint32_t rows, uint32_t seq_stride, uint32_t target_stride, uint32_t flags, const uint8_t* seq,
+                                 const uint32_t* seq_len, uint32_t* kmer, uint32_t* target_len, hipStream_t s);
+// launch_pile_kmers: the four words of position cell (g, j), j < target_len[g] (untrusted), added to cell kmer[g][j] < 4^k of kmer_pile;
+// tables of k <= PILE_KMERS_LDS_KMAX are summed per workgroup in LDS first unless direct.
+constexpr uint32_t PILE_KMERS_LDS_KMAX = 6;
+hipError_t launch_pile_kmers(uint32_t k, uint32_t rows, uint32_t target_stride, bool clear, bool direct, const uint32_t* target_len, const uint32_t* kmer,
+                             const uint64_t* pile, uint64_t* kmer_pile, hipStream_t s);
+// launch_model_update: model[i] / sd[i] = mean / sd of k-mer cell i over fix when its count reaches max(min_obs, 1), else prior[i] / +0;
+// prior may be model, sd is nullable.
+hipError_t launch_model_update(uint32_t k, uint32_t min_obs, float fix, const uint64_t* kmer_pile, const float* prior, float* model, float* sd, hipStream_t s);
 
 // ---- wave / workgroup primitives ---------------------------------------------------------------
 // For single-wave workgroups.  The LDS operations of one wave execute in issue order, so lanes of the same
